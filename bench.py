@@ -26,6 +26,12 @@ Workloads (BASELINE.json configs):
 touches the GPU) and relays rank 0's JSON line; under torchrun (RANK set) it is one rank.  Ranks shard instances
 (weak scaling), no data-path collective.
 
+A plain run sets up, warms up, times the steps and prints the line.  `--full` adds what the headline figure does not need: the CPU
+baseline leg (the C oracle timed on this host's cores on the same workload, with its parity sample against the GPU) and, with
+--mode eval, the single-core oracle beside the B = 1 host path.  `--dump-outputs DIR` writes what the timed path computed in its
+last step (rank 0's shard: state, out, status and tau | f log, plus the gathered summaries) to DIR/<name>.npy in float64, at most
+DUMP_BYTES in all (an array that does not fit its share is written as a fixed, seeded sample of its elements).
+
 Prints ONE JSON line (rank 0).
 """
 import argparse
@@ -45,6 +51,7 @@ HBM_PEAK_GBS = 8000.0            # MI355X_MICROARCH.md: 8 TB/s HBM3E
 FP64_VALU_PEAK_TFLOPS = 78.6     # MI355X fp64 vector peak = 256 CU x 64 lanes x 2 flop x 2.4 GHz
 FP64_MFMA_PEAK_TFLOPS = 78.6     # v_mfma_f64_16x16x4_f64: fp64 matrix rate = fp64 vector rate on gfx950
 MFMA_MOP_FLOP = 512              # SQ_INSTS_VALU_MFMA_MOPS_F64 unit (one 16x16x4 f64 MFMA = 2048 flop = 4 MOPS)
+DUMP_BYTES = 64_000_000          # --dump-outputs: all files together, .npy headers included
 PROFILE_TAGS = {3: "r04_c3", 2: "r04_c2"}   # profiles/<tag>_rollout_summary.json: PMC passes of the committed kernel on the default command
 HARD_FLAGS = 1 | 2 | 4 | 8 | 32  # LMH_FLAG_QP_MAXITER | NONFINITE | ZMP_RANGE | NOT_SPD | UNFINISHED; LMH_FLAG_QP_FP64_ROUTE (16) is informational
 
@@ -84,8 +91,10 @@ def parse(argv=None):
     ap.add_argument("--mpc-dt", type=float, default=None, help="MPC sample time (lmh_config.mpc_dt); default per config, dt with --coupled")
     ap.add_argument("--cold", action="store_true", help="cold-start the QP active set every evaluation")
     ap.add_argument("--no-log", action="store_true", help="do not write the per-tick tau|f log")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also run the CPU baseline leg (and, with --mode eval, the single-core oracle line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline leg out")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU baseline leg (all of its lines together)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (float64)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse the N>1 path)")
     ap.add_argument("--reset-every", type=int, default=None,
                     help="restart the rollouts from the initial states after this many steps (0 = never: consecutive steps continue the same "
@@ -382,6 +391,25 @@ def profiled_pmc(args):
         return None
 
 
+def dump_outputs(outdir, arrays, seed=20260010):
+    """arrays: (name, tensor) pairs -> outdir/<name>.npy in float64, DUMP_BYTES in all.  Smallest first, each gets an equal share of what
+    is left; one that does not fit is written as a fixed, seeded sample of its elements (flattened, in index order)."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    left = DUMP_BYTES
+    arrays = sorted(arrays, key=lambda a: a[1].numel())
+    for i, (name, t) in enumerate(arrays):
+        cap = (left - 128 * (len(arrays) - i)) // (len(arrays) - i) // 8          # elements; 128 B = one .npy header
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(seed).choice(t.numel(), cap, replace=False))
+            t = t.reshape(-1)[torch.as_tensor(idx, device=t.device)]
+        a = t.detach().cpu().numpy().astype(np.float64)
+        path = os.path.join(outdir, name + ".npy")
+        np.save(path, a)
+        left -= os.path.getsize(path)
+
+
 # ------------------------------------------------------------------------------------------------ evaluation API (secondary lines)
 ALG_BYTES_PER_EVAL = 1008        # SURVEY 8d, eval-API mode: 60 f64 in + 66 f64 out per instance per evaluation
 
@@ -419,6 +447,8 @@ def main_eval(args, ctl, state, host, count):
         flagged = int(((status[:, 2] & HARD_FLAGS) != 0).sum().item())
         lines[name] = dict(evaluations_per_s=count * args.steps / el, launch_ms=kms, wall_ms_per_launch=el / args.steps * 1e3,
                            support_phase=int(host["phase"][int(status[0, 0].item())]) if host.get("phase") is not None else 0, instances_flagged=flagged)
+    if args.dump_outputs:                                          # the last timed launch is the single-support line's
+        dump_outputs(args.dump_outputs, [("state", st), ("out", out), ("status", status)])
     ss = lines["single_support"]
     hbm_g = count * ALG_BYTES_PER_EVAL / (ss["launch_ms"] * 1e-3) / 1e9
     fl = count * ALG_FLOP_PER_TICK / 4 / (ss["launch_ms"] * 1e-3) / 1e12
@@ -449,7 +479,7 @@ def main_eval(args, ctl, state, host, count):
         r = subprocess.run([app, "5", "0.01", "0.5"], capture_output=True, text=True)
         res_b1["offline_stand_app"] = {"wall_s": time.perf_counter() - t0, "ticks": len(r.stdout.split()), "returncode": r.returncode,
                                        "last_com_x": float(r.stdout.split()[-1]) if r.stdout.split() else None}
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle.pyoracle import Oracle
         o = Oracle(sim_time=5.0, dt=0.01, horizon_time=0.5, do_ik=True)
         x0 = np.concatenate([o.robot()["q"], np.zeros(30)])
@@ -603,6 +633,9 @@ def main():
 
     rc = 0
     if rank == 0:
+        if args.dump_outputs:                                      # before the CPU leg's parity replay overwrites state | out | status | log
+            dump_outputs(args.dump_outputs, [("state", state), ("out", out), ("status", status)]
+                         + ([("log", log)] if log is not None else []) + ([("summary", gathered)] if gathered is not None else []))
         total_instances = B * world
         ticks_total = total_instances * args.ticks * args.steps
         value = ticks_total / elapsed
@@ -662,7 +695,7 @@ def main():
             "instances_fp64_route": routed,
             "summary_rows_gathered": int(gathered.shape[0]) if gathered is not None else 0,
         }
-        if not args.no_cpu_baseline and world == 1:              # the CPU baseline is timed on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:   # the CPU baseline is timed on rank 0 at N = 1 only
             try:
                 def gpu_replay(n_inst, nticks):                   # parity sample for the CPU leg: the same robots from the initial states (untimed)
                     state.copy_(state0); status.zero_()

@@ -5,13 +5,14 @@ Why it exists: the reference ships no golden vectors and cannot be compiled here
 directory can never be pinned to reference outputs ("parity unpinned").  What can be done is to cross-examine it: this file restates the
 same path a second time, written from the reference SOURCES (file:line cited per function), not from oracle/*.c, in a different style --
 dense 4x4 / 6x6 numpy algebra exactly as the Eigen code multiplies it, the literal 74x74 Hessian and 50x74 constraint matrix, and a
-generic primal active-set KKT solver (numpy.linalg) instead of the oracle's Goldfarb-Idnani dual method.  The NAO inertial table is
-PARSED FROM THE TEXT of /root/reference/src/robotParameters.cpp (read as data; nothing of the reference is executed), so it does not share
-the oracle's hand-copied table either.  Agreement of two independent restatements shrinks the common-mode risk; it is not a pin.
+generic primal active-set KKT solver (numpy.linalg) instead of the oracle's Goldfarb-Idnani dual method.  The NAO inertial table was
+PARSED FROM THE TEXT of the reference's src/robotParameters.cpp (read as data; nothing of the reference is executed) into
+tests/golden/nao_links_text.json, so it does not share the oracle's hand-copied table either.  Agreement of two independent restatements
+shrinks the common-mode risk; it is not a pin.
 
-Runs only where /root/reference exists (the build container).  `python oracle/restatement_np.py` checks itself against
-tests/golden/eval_vectors.npz (tau, f, qdd, M, C, AG, J, ... at 1e-9) and regenerates the SURVEY 8c anchors into
-tests/golden/survey_anchors.json.
+`python oracle/restatement_np.py [--reference DIR] [TICKS]` checks itself against tests/golden/eval_vectors.npz (tau, f, qdd, M, C, AG,
+J, ... at 1e-9) and regenerates the SURVEY 8c anchors into tests/golden/survey_anchors.json; with --reference (a checkout of the
+reference) it first re-parses the inertial table from that checkout's text into tests/golden/nao_links_text.json.
 """
 import json
 import os
@@ -20,7 +21,6 @@ import sys
 
 import numpy as np
 
-REF = "/root/reference"
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 PI = 3.14159265358979323846                     # src/Robot.cpp:3
@@ -29,13 +29,13 @@ ACT = [0, 1, 2, 3, 4, 5, 6, 0, 7, 8, 9, 10, 11, 12, 0, 13, 14, 15, 16, 17, 18, 1
 NF, NQ = 28, 30
 
 
-def available():
-    return os.path.exists(os.path.join(REF, "src", "robotParameters.cpp"))
+LINKS_FIXTURE = os.path.join(ROOT, "tests", "golden", "nao_links_text.json")
 
 
 # ----------------------------------------------------------------------------- data: src/robotParameters.cpp, parsed as text
-def parse_links():
-    txt = open(os.path.join(REF, "src", "robotParameters.cpp")).read()
+def parse_links(ref_dir):
+    """The inertial table parsed from the text of <ref_dir>/src/robotParameters.cpp (regenerates LINKS_FIXTURE)."""
+    txt = open(os.path.join(ref_dir, "src", "robotParameters.cpp")).read()
     num = r"[-+]?(?:\d+\.?\d*|\.\d+)(?:[eE][-+]?\d+)?"
     links = [dict(mass=0.0, com=np.zeros(3), inertia=np.zeros((3, 3))) for _ in range(NF)]
     for m in re.finditer(r"links\[(\d+)\]\.mass\s*=\s*(" + num + r")\s*;", txt):
@@ -45,6 +45,17 @@ def parse_links():
     for m in re.finditer(r"links\[(\d+)\]\.inertia\s*<<\s*([^;]+);", txt):
         links[int(m.group(1))]["inertia"] = np.array([float(x) for x in re.findall(num, m.group(2))]).reshape(3, 3)
     return links
+
+
+def links_rows(links):
+    return [[float(l["mass"]), *map(float, l["com"]), *map(float, np.asarray(l["inertia"]).ravel())] for l in links]
+
+
+def load_links():
+    """The parsed table as stored in LINKS_FIXTURE: rows of mass, CoM (3), inertia (3 x 3, row-major)."""
+    with open(LINKS_FIXTURE) as f:
+        rows = np.array(json.load(f)["links"], dtype=float)
+    return [dict(mass=r[0], com=r[1:4].copy(), inertia=r[4:13].reshape(3, 3).copy()) for r in rows]
 
 
 # ----------------------------------------------------------------------------- src/generalizedFunctions.cpp
@@ -150,7 +161,7 @@ def forward_kinematics(q):                        # :45-160
 
 class Robot:                                      # Robot::Robot, :5-43
     def __init__(self):
-        self.links = parse_links()
+        self.links = load_links()
         self.update_state(np.zeros(NQ))
         self.mass = 0.0
         for i in range(NF):
@@ -503,11 +514,16 @@ def survey_anchors(ticks=500):
 
 
 if __name__ == "__main__":
-    if not available():
-        sys.exit("needs /root/reference (build container only)")
+    args = sys.argv[1:]
+    if args[:1] == ["--reference"]:
+        with open(LINKS_FIXTURE, "w") as f:
+            json.dump({"note": "NAO inertial table (createNaoParameters, src/robotParameters.cpp) parsed from the reference's source text by "
+                               "oracle/restatement_np.py parse_links(); one row per link: mass, CoM (3), inertia (3 x 3, row-major)",
+                       "links": links_rows(parse_links(args[1]))}, f, indent=1)
+        args = args[2:]
     w = check_against_golden()
     assert max(w.values()) < 1e-8, w
-    nt = int(sys.argv[1]) if len(sys.argv) > 1 else 500
+    nt = int(args[0]) if args else 500
     anc = survey_anchors(nt)
     with open(os.path.join(ROOT, "tests", "golden", "survey_anchors.json"), "w") as f:
         json.dump(anc, f, indent=1)

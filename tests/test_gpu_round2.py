@@ -507,7 +507,7 @@ def test_bench_under_torchrun_as_the_driver_launches_it():
 def test_bench_default_line_shape():
     """The JSON contract on a reduced workload: config 3 keys, binding roofline first, HBM / MFMA objects beside it, CPU
     baseline on the same workload with the last tick compared against the GPU."""
-    res = _run_bench(["--instances", "128", "--steps", "2", "--warmup", "1", "--ticks", "10", "--cpu-seconds", "4"])
+    res = _run_bench(["--instances", "128", "--steps", "2", "--warmup", "1", "--ticks", "10", "--cpu-seconds", "4", "--full"])
     assert res["n_gpus"] == 1 and res["config"]["baseline_config"] == 3 and "walking" in res["config"]["workload"]
     rf = res["roofline"]
     assert rf["bound"] == "fp64-valu" and rf["unit"] == "TFLOP/s" and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-12
@@ -519,7 +519,7 @@ def test_bench_default_line_shape():
     assert cb["parity_vs_gpu_last_tick_max_rel"] < 1e-6
     assert cb["literal_2wbc_value"] and cb["literal_2wbc_value"] < cb["value"] * 1.05
     # the informational PCIe-inclusive mode runs the same rollouts (and keeps the CPU leg's inputs intact)
-    hio = _run_bench(["--instances", "128", "--steps", "3", "--warmup", "1", "--ticks", "10", "--cpu-seconds", "3", "--host-io"])
+    hio = _run_bench(["--instances", "128", "--steps", "3", "--warmup", "1", "--ticks", "10", "--cpu-seconds", "3", "--host-io", "--full"])
     assert hio["config"]["host_io_over_pcie"] is True and hio["instances_flagged"] == 0 and hio["cpu_baseline"]["value"] > 0
     assert hio["cpu_baseline"]["parity_vs_gpu_last_tick_max_rel"] < 1e-6
 

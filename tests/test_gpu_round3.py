@@ -440,7 +440,7 @@ def test_bench_precision_2_and_config5_lines():
     jump from the initial state, restarted per step and reported so)."""
     r2 = _run_bench(["--instances", "128", "--steps", "2", "--warmup", "1", "--ticks", "10", "--no-cpu-baseline", "--precision", "2"])
     assert r2["dtype"].startswith("f32") and r2["instances_flagged"] == 0 and r2["instances_fp64_route"] >= 0
-    r5 = _run_bench(["--config", "5", "--instances", "256", "--steps", "2", "--warmup", "1", "--ticks", "700", "--cpu-seconds", "4"])
+    r5 = _run_bench(["--config", "5", "--instances", "256", "--steps", "2", "--warmup", "1", "--ticks", "700", "--cpu-seconds", "4", "--full"])
     assert r5["config"]["rollout_restarts"] == 2 and "jump" in r5["config"]["workload"] and r5["instances_flagged"] == 0
     assert r5["config"]["preview_s"] == pytest.approx(0.48) and r5["cpu_baseline"]["parity_vs_gpu_last_tick_max_rel"] < 1e-6
 

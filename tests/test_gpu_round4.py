@@ -166,7 +166,7 @@ def test_bench_eval_mode_reports_both_lines():
     double-support and a single-support state, with the HBM roofline on SURVEY 8d's 1 008 B per evaluation; (b) B = 1 through lmh_eval_host,
     four calls per tick as the shim's Controller::standStep is driven by apps/offline/main.cpp:66-89, beside the C oracle on one core and the
     shim-built apps/offline_stand run end to end (its CoM-x trace ends where SURVEY's anchor says: -1.34e-4)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "eval", "--instances", "512", "--steps", "30", "--warmup", "5"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--mode", "eval", "--instances", "512", "--steps", "30", "--warmup", "5", "--full"],
                        cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -182,6 +182,27 @@ def test_bench_eval_mode_reports_both_lines():
     assert b1["cpu_oracle_single_core"]["cores"] == 1 and b1["cpu_oracle_single_core"]["ms_per_tick"] > 0.0
     app = b1["offline_stand_app"]
     assert app["returncode"] == 0 and abs(app["last_com_x"] - (-1.34198e-4)) < 1e-8
+
+
+def test_bench_dump_outputs_repeat_exactly_and_plain_run_is_lean(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the last timed step's state | out | status | tau|f log and the gathered summaries in float64,
+    bit-identical from run to run with the same arguments; a plain run (no --full) carries no CPU-baseline leg and times --steps steps."""
+    argv = [sys.executable, os.path.join(ROOT, "bench.py"), "--instances", "128", "--steps", "3", "--warmup", "1", "--ticks", "10"]
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"run{k}"
+        r = subprocess.run(argv + ["--dump-outputs", str(d)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')][-1])
+        assert "cpu_baseline" not in res and res["steps"] == 3 and res["ms_per_step"] > 0 and res["instances_flagged"] == 0
+        runs.append({f.stem: np.load(f) for f in d.iterdir()})
+        assert sum(f.stat().st_size for f in d.iterdir()) <= 64_000_000
+    a, b = runs
+    assert set(a) == {"state", "out", "status", "log", "summary"}
+    assert a["state"].shape == (128, 96) and a["out"].shape == (128, 80) and a["status"].shape == (128, 4) and a["log"].shape == (10, 128, 36)
+    for name in a:
+        assert a[name].dtype == np.float64 and np.array_equal(a[name], b[name]), name
+    assert np.allclose(a["state"][:, 90], 4 * 10 * DT) and np.allclose(a["summary"][:, 6], 4 * 10 * DT)     # t after the 4th launch
 
 
 # ------------------------------------------------------------------------------- edge-contact push-through (cone_pushthrough, round 4)

@@ -214,6 +214,25 @@ def test_bench_gpus_flag_launches_ranks_and_propagates_failure():
     assert r.returncode != 0 and "disagrees with WORLD_SIZE" in r.stderr
 
 
+def test_bench_dump_outputs_fit_the_budget(tmp_path):
+    """--dump-outputs: every array as float64, all files within DUMP_BYTES; an array over its share is written as the same seeded sample
+    of its elements every time, in index order.  (Budget lowered here so that a small array overflows it.)"""
+    b, _ = _bench_mod()
+    b.DUMP_BYTES = 20_000
+    status = torch.arange(-6, 6, dtype=torch.int32).reshape(3, 4)
+    state = torch.linspace(0.0, 1.0, 20, dtype=torch.float64).reshape(4, 5)
+    log = torch.arange(6000, dtype=torch.float64).reshape(10, 20, 30)
+    for d in (tmp_path / "a", tmp_path / "b"):
+        b.dump_outputs(str(d), [("log", log), ("status", status), ("state", state)])
+        assert sum(f.stat().st_size for f in d.iterdir()) <= b.DUMP_BYTES
+    a = {f.stem: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert all(v.dtype == np.float64 for v in a.values())
+    assert np.array_equal(a["status"], status.numpy()) and np.array_equal(a["state"], state.numpy())
+    s = a["log"]
+    assert s.ndim == 1 and 1000 < s.size < 6000 and (np.diff(s) > 0).all() and np.isin(s, log.numpy()).all()
+    assert np.array_equal(s, np.load(tmp_path / "b" / "log.npy"))
+
+
 def test_c_abi_record_files_round_trip_and_match_the_python_format(tmp_path, hip_lib):
     """lmh_write_summary / lmh_read_summary / lmh_write_log / lmh_read_log (host-only entry points of the C ABI) against
     linearmpchumanoid_amd.wire: same 64-byte header, same payload, both directions; bad files are refused."""

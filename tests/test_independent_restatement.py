@@ -1,23 +1,19 @@
 """Cross-examination of the C oracle (it cannot be pinned to reference outputs: the reference ships none and cannot be built here).
 
 oracle/restatement_np.py restates the path a SECOND time, independently (dense numpy algebra written from the reference sources, inertial
-table parsed from the text of the reference's robotParameters.cpp, generic KKT active-set solver).  Where /root/reference exists (the build
-container) it must reproduce the committed oracle fixtures; everywhere, the anchors it wrote (tests/golden/survey_anchors.json) must agree
-with the C oracle and with the numbers SURVEY.md 8c quotes."""
+table parsed from the text of the reference's robotParameters.cpp, generic KKT active-set solver).  It must reproduce the committed oracle
+fixtures, and the anchors it wrote (tests/golden/survey_anchors.json) must agree with the C oracle and with the numbers SURVEY.md 8c quotes."""
 import json
 import os
 
 import numpy as np
-import pytest
 
 from oracle import restatement_np as R
 from oracle.pyoracle import Oracle
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-needs_ref = pytest.mark.skipif(not R.available(), reason="/root/reference is only present in the build container")
 
 
-@needs_ref
 def test_independent_restatement_reproduces_the_golden_eval_vectors():
     w = R.check_against_golden(verbose=False)
     for k in ("M", "C", "AG", "J", "CoM", "Jpqp", "u0", "Cg6", "AGpqp"):
@@ -26,16 +22,14 @@ def test_independent_restatement_reproduces_the_golden_eval_vectors():
         assert w[k] < 1e-8, (k, w[k])                              # through two different QP algorithms (KKT active set vs Goldfarb-Idnani)
 
 
-@needs_ref
 def test_inertial_table_parsed_from_the_reference_text_equals_the_oracle_table():
     from oracle.pyoracle import nao_raw_links
     raw = nao_raw_links()
-    links = R.parse_links()
+    links = R.load_links()                                         # tests/golden/nao_links_text.json
     for i in range(28):
         assert links[i]["mass"] == raw[i, 0] and np.array_equal(links[i]["com"], raw[i, 1:4]) and np.array_equal(links[i]["inertia"].ravel(), raw[i, 4:])
 
 
-@needs_ref
 def test_anchors_regenerate():
     a = R.survey_anchors(ticks=0)
     b = json.load(open(os.path.join(GOLD, "survey_anchors.json")))
