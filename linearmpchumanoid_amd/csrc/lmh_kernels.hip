@@ -660,6 +660,26 @@ __device__ __forceinline__ void dpp_fmac_lane(double &acc, double src, double m)
     if constexpr (NOP) asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(m), "n"(C));
     else asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(m), "n"(C));
 }
+// Dot products of a lane's row with the entries lanes 0..11 of its own 16-lane row hold, each a whole chain in ONE asm statement: the
+// leading s_nop 1 covers the "VALU write -> DPP read" hazard on `src` for whatever the compiler placed before it, and nothing inside writes
+// `src`.  Terms accumulate in k order with fused multiply-adds (the order and form of a plain `acc += m[k] * x[k]` loop).  Full exec mask
+// (wave-uniform control flow) only.
+#define LMH_DPM(d, s, m, c) "v_fmac_f64_dpp %" #d ", %" #s ", %" #m " row_newbcast:" #c " row_mask:0xf bank_mask:0xf\n\t"
+// r += sum_k lane_k(src) m[k], l += sum_k lane_(6 + k)(src) m[k] (k < 6): one foot's six entries each, interleaved
+__device__ __forceinline__ void dpp_dot6x2(double &r, double &l, double src, const double (&m)[6])
+{
+    asm volatile("s_nop 1\n\t" LMH_DPM(0, 2, 3, 0) LMH_DPM(1, 2, 3, 6) LMH_DPM(0, 2, 4, 1) LMH_DPM(1, 2, 4, 7) LMH_DPM(0, 2, 5, 2) LMH_DPM(1, 2, 5, 8)
+                 LMH_DPM(0, 2, 6, 3) LMH_DPM(1, 2, 6, 9) LMH_DPM(0, 2, 7, 4) LMH_DPM(1, 2, 7, 10) LMH_DPM(0, 2, 8, 5) LMH_DPM(1, 2, 8, 11)
+                 : "+v"(r), "+v"(l) : "v"(src), "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(m[4]), "v"(m[5]));
+}
+// acc += sum_k lane_k(src) m[k] (k < 12)
+__device__ __forceinline__ void dpp_dot12(double &acc, double src, const double (&m)[12])
+{
+    asm volatile("s_nop 1\n\t" LMH_DPM(0, 1, 2, 0) LMH_DPM(0, 1, 3, 1) LMH_DPM(0, 1, 4, 2) LMH_DPM(0, 1, 5, 3) LMH_DPM(0, 1, 6, 4) LMH_DPM(0, 1, 7, 5)
+                 LMH_DPM(0, 1, 8, 6) LMH_DPM(0, 1, 9, 7) LMH_DPM(0, 1, 10, 8) LMH_DPM(0, 1, 11, 9) LMH_DPM(0, 1, 12, 10) LMH_DPM(0, 1, 13, 11)
+                 : "+v"(acc) : "v"(src), "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(m[4]), "v"(m[5]),
+                   "v"(m[6]), "v"(m[7]), "v"(m[8]), "v"(m[9]), "v"(m[10]), "v"(m[11]));
+}
 // one pivot, then the next.  GUARD = true: `rowon` switches a whole 16-lane DPP row off (its pivots are replaced by 1) and a pivot that is
 // not above `dmin` is replaced by 1 and reported in `bad` (kinv_compute: two feet on two DPP rows, a rank-deficient K_f is an expected
 // outcome).  GUARD = false (gj_solve_regs): every DPP row carries a copy of the system, so the pivot a lane sees is always the true one --
@@ -2376,7 +2396,7 @@ __device__ __forceinline__ int cone_pushthrough(double *L, LmhCParams &P, unsign
     const int lane = LANE;
     const unsigned FR = F & 0xFFFFu, FL = F >> 16;
     const bool useR = FR != 0u, useL = FL != 0u;
-    double *Ki = (have_ki == 1) ? L + P_KI : L + C_LS + 72, *Yv = L + C_LS + 144;
+    double *Ki = (have_ki == 1) ? L + P_KI : L + C_LS + 72;
     if (have_ki == 2) return 0;
     if (have_ki == 0 && kinv_compute(L, F, L + C_LS + 72, L + C_LS + 240)) return 0;     // wave-uniform: some K_f is singular
     WSYNC();
@@ -2392,58 +2412,61 @@ __device__ __forceinline__ int cone_pushthrough(double *L, LmhCParams &P, unsign
         const double kz = isz ? (fi ? kapL : kapR) : 0.0;          // the f_z row takes kappa times the bound row
         const double eps = P.eps_coeff;
         const double *W1 = L + P_W + 12 * lr, *W2 = L + P_W + 12 * (6 * fi + ((dd > 0) ? dd : 0)), *Kr = Ki + 36 * fi + 6 * ri;
-        double base[12];
+        const double *gp = L + P_GCOL + 6 * l16;
+        double wrow[12], base[12], kv[6], g6[6];                   // the lane's W row, K~^-1 row and generator (read again after the solve)
 #pragma unroll
-        for (int c = 0; c < 12; c++) base[c] = W1[c] + kz * W2[c];
+        for (int c = 0; c < 12; c++) wrow[c] = W1[c];
+#pragma unroll
+        for (int k = 0; k < 6; k++) { kv[k] = Kr[k]; g6[k] = gp[k]; }
+#pragma unroll
+        for (int c = 0; c < 12; c++) base[c] = wrow[c] + kz * W2[c];
         base[5] += kapR * ((dR > 0) ? base[1] : base[0]);           // ... and the f_z column kappa times the bound column (kappa = 0: no edge)
         base[11] += kapL * ((dL > 0) ? base[7] : base[6]);
 #pragma unroll
         for (int c = 0; c < 12; c++) {                             // full rows, unconditional loads: rows / columns of a foot without force are
-            const double g = Kr[c % 6];                            // never pivots (live mask), so their entries are don't-cares
+            const double g = kv[c % 6];                            // never pivots (live mask), so their entries are don't-cares
             const bool colpin = (c % 6) == ((c < 6) ? dR : dL);
             const double v = base[c] + ((c / 6 == fi) ? eps * g : 0.0);
             a[c] = (rowpin || colpin) ? ((lr == c) ? 1.0 : 0.0) : v;
         }
-        const double hv = L[P_H12 + lr] + kz * L[P_H12 + 6 * fi + ((dd > 0) ? dd : 0)];
+        const double hl = L[P_H12 + lr];
+        const double hv = hl + kz * L[P_H12 + 6 * fi + ((dd > 0) ? dd : 0)];
         b[0] = rowpin ? 0.0 : hv;
         const unsigned live = (useR ? 0x03Fu : 0u) | (useL ? 0xFC0u : 0u);      // (a pinned row stays a pivot: skipping it measured neutral)
         if (gj_solve_regs<12, 1>(a, b, live)) *flags |= LMH_FLAG_NOT_SPD;
-        // w = E w~: the bound torque is kappa f_z (lanes 5 / 11 of the lane's own 16-lane row hold f_z)
+        // w = E w~: the bound torque is kappa f_z (lanes 5 / 11 of the lane's own 16-lane row hold f_z).  Lanes 0..11 of every DPP row
+        // hold w from here on, so y, the residual and s_j below are row-broadcast chains (no LDS hand-over)
         const double fzR = bcast16<5>(b[0]), fzL = bcast16<11>(b[0]);
         const double wv = rowpin ? (fi ? kapL * fzL : kapR * fzR) : b[0];
-        WSYNC();
-        if (lane < 12) { const double wo = rowuse ? wv : 0.0; Yv[lane] = wo; L[P_W12 + lane] = wo; }      // w: the wrench G c itself (cone_qp: w_done if the round is accepted)
-    }
-    WSYNC();
-    if (lane < 12) {                                               // y = K~^-1 w (free coefficients), -(W w - h) / eps (the others), foot by foot
-        const int fi = lane / 6, ri = lane % 6;
+        const double wo = rowuse ? wv : 0.0;
+        if (lane < 12) L[P_W12 + lane] = wo;                       // w: the wrench G c itself (cone_qp: w_done if the round is accepted)
+        // y = K~^-1 w (free coefficients; the bound column of the inverse is zero), -(W w - h) / eps (the others), foot by foot
+        double yR = 0.0, yL = 0.0;
+        dpp_dot6x2(yR, yL, wo, kv);
         const bool used = (fi == 0) ? useR : useL, edge = (fi ? dL : dR) >= 0;
-        double yv = 0.0, yn = 0.0;
-        if (used) {
-#pragma unroll
-            for (int k = 0; k < 6; k++) yv += Ki[36 * fi + 6 * ri + k] * Yv[6 * fi + k];     // (the bound column of the inverse is zero)
-            yn = yv;                                               // K regular: g_j'(W w - h) = -eps g_j'y for every coefficient of the foot
-        }
-        if (!used || edge) {
+        const double ky = fi ? yL : yR;
+        double yv = ky, yn = ky;                                   // K regular: g_j'(W w - h) = -eps g_j'y for every coefficient of the foot
+        if (!useR || !useL || dR >= 0 || dL >= 0) {                // wave-uniform
             // a foot with no free coefficient, or on an edge: the multipliers are g_j'(W w - h) with the foot's rows of the residual;
             // stored as -(W w - h)/eps so that the caller's -eps s_j reproduces them
-            double rv = -L[P_H12 + lane];
-#pragma unroll
-            for (int k = 0; k < 12; k++) rv += L[P_W + 12 * lane + k] * Yv[k];
-            yn = -rv / P.eps_coeff;
-            if (!used) yv = yn;
+            double rv = -hl;
+            dpp_dot12(rv, wo, wrow);
+            const double rn = -rv / P.eps_coeff;
+            if (!used || edge) yn = rn;
+            if (!used) yv = rn;
         }
-        Yv[12 + lane] = yv; Yv[24 + lane] = yn;
+        // s_j = g_j'y: row 0 (lanes 0..15, right foot) takes lanes 0..5, row 1 (left foot) lanes 6..11; the coefficients of F read y~, the
+        // others the residual form (they differ only on an edge foot)
+        double sR = 0.0, sL = 0.0;
+        dpp_dot6x2(sR, sL, yv, g6);
+        double sj = (lane & 16) ? sL : sR;
+        if (dR >= 0 || dL >= 0) {                                  // wave-uniform
+            double nR = 0.0, nL = 0.0;
+            dpp_dot6x2(nR, nL, yn, g6);
+            if (!((F >> (lane & 31)) & 1u)) sj = (lane & 16) ? nL : nR;
+        }
+        *s_out = (lane < 32) ? sj : 0.0;
     }
-    WSYNC();
-    double sj = 0.0;
-    if (lane < 32) {
-        const bool fr = (F >> lane) & 1u;
-        const double *g = L + P_GCOL + 6 * (lane & 15), *y = Yv + (fr ? 12 : 24) + 6 * (lane >> 4);
-#pragma unroll
-        for (int k = 0; k < 6; k++) sj += g[k] * y[k];
-    }
-    *s_out = sj;
     return 1;
 }
 
@@ -2749,9 +2772,7 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
             double g6[6], zr = 0.0, zl = 0.0;
 #pragma unroll
             for (int k = 0; k < 6; k++) g6[k] = gp[k];
-            dpp_fmac_lane<0>(zr, b[0], g6[0]); dpp_fmac_lane<6, false>(zl, b[0], g6[0]); dpp_fmac_lane<1, false>(zr, b[0], g6[1]); dpp_fmac_lane<7, false>(zl, b[0], g6[1]);
-            dpp_fmac_lane<2, false>(zr, b[0], g6[2]); dpp_fmac_lane<8, false>(zl, b[0], g6[2]); dpp_fmac_lane<3, false>(zr, b[0], g6[3]); dpp_fmac_lane<9, false>(zl, b[0], g6[3]);
-            dpp_fmac_lane<4, false>(zr, b[0], g6[4]); dpp_fmac_lane<10, false>(zl, b[0], g6[4]); dpp_fmac_lane<5, false>(zr, b[0], g6[5]); dpp_fmac_lane<11, false>(zl, b[0], g6[5]);
+            dpp_dot6x2(zr, zl, b[0], g6);
             zj = (lane < 32) ? ((lane & 16) ? zl : zr) : 0.0;
         }
         }
@@ -2772,10 +2793,22 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
         ninf = __popc(bad);
         F ^= bad;
     }
-    // the dual sign tests of the iteration below scale with max |q| (the all-free path above has no dual side)
-    if constexpr (!F32) qv_form(L);
-    double qmax = (lane < 32) ? fabs(L[P_QV + lane]) : 0.0;
-    qmax = wave_max(qmax);
+    // the dual sign tests of the iteration below scale with max |q| (the all-free path above has no dual side).  fp64: qv = G'h in
+    // registers, row 0 (right foot) from h_0..5, row 1 (left foot) from h_6..11, in qv_form's order and form; it reaches P_QV only when a
+    // route that reads it runs (qv_stored)
+    double qv = 0.0;
+    bool qv_stored = F32;
+    if constexpr (!F32) {
+        const int l16 = lane & 15;
+        const double *gp = L + P_GCOL + 6 * l16;
+        const double hl = L[P_H12 + ((l16 < 12) ? l16 : 0)];
+        double g6[6], qr = 0.0, ql = 0.0;
+#pragma unroll
+        for (int k = 0; k < 6; k++) g6[k] = gp[k];
+        dpp_dot6x2(qr, ql, hl, g6);
+        qv = (lane < 32) ? ((lane & 16) ? ql : qr) : 0.0;
+    } else qv = (lane < 32) ? L[P_QV + lane] : 0.0;
+    const double qmax = wave_max(fabs(qv));
     WSTAMP(31);
     const double toll = 1e-14 * (1.0 + qmax);                    // ~10x the round-off of (P c - q): a looser bound lets a warm start keep a coefficient
                                                                    // out whose multiplier is slightly negative (1e-6 relative error in tau after a contact switch)
@@ -2806,6 +2839,11 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
             }
         } else {
             if constexpr (F32) flags |= LMH_FLAG_QP_FP64_ROUTE;    // rank-deficient contact set (or the Lawson-Hanson pass): fp64 general route
+            if (!qv_stored) {                                      // the thin and general routes read qv from LDS
+                if (lane < 32) L[P_QV + lane] = qv;
+                WSYNC();
+                qv_stored = true;
+            }
 #ifdef LMH_NO_THIN                                                  // experiment switch: the general route for every set
             if (false) {
 #else

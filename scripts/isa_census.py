@@ -5,6 +5,8 @@ is straight-line between marks (exec-masked bodies, no counted loops except the 
 issues per phase.  Classes of VALU instructions: f64 = fp64 arithmetic (add / mul / fma / fmac incl. DPP forms, rcp, rndne, min / max ...),
 mfma, sel = v_cndmask, lane = v_readlane / v_readfirstlane / v_writelane, mov = v_mov (incl. DPP moves) / v_accvgpr, int = integer
 add / shift / mul / mad / logic, cmp = v_cmp*, cvt, oth.
+The listing is also checked for the DPP read hazard that the compiler does not pad inside inline asm: a VALU write of the source
+register of a v_fmac_f64_dpp needs two wait states before it (one instruction = one state, s_nop N = N + 1); each violation is listed.
 Usage: python scripts/isa_census.py [--reuse] [--out FILE] [extra -D flags]      (--reuse: take /tmp/lmh_census.s as it is)"""
 import collections
 import os
@@ -93,6 +95,42 @@ for key in ("sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count", 
     mm = re.search(r"\." + key + r":\s*(\d+)", meta)
     if mm:
         txt.append(f"{key}: {mm.group(1)}")
+
+
+def vregs(tok):
+    """set of VGPR numbers of an operand token (v7, v[4:5]); empty for anything else"""
+    m = re.fullmatch(r"v(\d+)", tok) or re.fullmatch(r"v\[(\d+):(\d+)\]", tok)
+    if not m:
+        return set()
+    lo = int(m.group(1)); hi = int(m.group(2)) if m.lastindex == 2 else lo
+    return set(range(lo, hi + 1))
+
+
+insts = []                                                         # (opcode, operand tokens) of the kernel, listing order
+for l in lines[start:end]:
+    t = l.split(";")[0].strip()
+    if not t or t.startswith((".", "//")) or t.split()[0].endswith(":"):
+        continue
+    op, _, rest = t.partition(" ")
+    insts.append((op, [x.strip() for x in rest.split(",")]))
+hazards = []
+for i, (op, ops) in enumerate(insts):
+    if op != "v_fmac_f64_dpp":
+        continue
+    src = vregs(ops[1].split()[0])
+    states, j = 0, i - 1
+    while j >= 0 and states < 2:
+        pop, pops = insts[j]
+        if pop == "s_nop":
+            states += int(pops[0], 0) + 1
+        else:
+            if pop.startswith("v_") and pops and pops[0] and vregs(pops[0].split()[0]) & src:
+                hazards.append(f"  {pop} {', '.join(pops)}  ->  {states} wait state(s)  ->  v_fmac_f64_dpp {', '.join(ops)}")
+            states += 1
+        j -= 1
+n_dpp = sum(1 for op, _ in insts if op == "v_fmac_f64_dpp")
+txt.append(f"dpp_read_hazards: {len(hazards)} of {n_dpp} v_fmac_f64_dpp (VALU write of the DPP source fewer than 2 wait states before)")
+txt += hazards
 print("\n".join(txt))
 if dest:
     open(dest, "w").write("\n".join(txt) + "\n")
