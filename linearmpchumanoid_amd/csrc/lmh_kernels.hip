@@ -681,7 +681,7 @@ __device__ __forceinline__ void dpp_dot12(double &acc, double src, const double 
                    "v"(m[6]), "v"(m[7]), "v"(m[8]), "v"(m[9]), "v"(m[10]), "v"(m[11]));
 }
 // one pivot, then the next.  GUARD = true: `rowon` switches a whole 16-lane DPP row off (its pivots are replaced by 1) and a pivot that is
-// not above `dmin` is replaced by 1 and reported in `bad` (kinv_compute: two feet on two DPP rows, a rank-deficient K_f is an expected
+// not above `dmin` is replaced by 1 and reported in `bad` (kinv_compute: each foot on two DPP rows, a rank-deficient K_f is an expected
 // outcome).  GUARD = false (gj_solve_regs): every DPP row carries a copy of the system, so the pivot a lane sees is always the true one --
 // no guard selects, no test per pivot: lane J keeps 1 / d_J, and the caller looks at the signs once at the end.
 template <int J, int N, int M, bool GUARD = true>
@@ -741,9 +741,11 @@ __device__ __forceinline__ void gj16_pipe(double (&a)[N], double (&b)[M], unsign
     }
 }
 // Lane l holds row l & 15 of the system (rows >= N: any finite copy, e.g. row 0 -- they are eliminated like every other row and never read):
-// all four 16-lane DPP rows then run the same elimination.  On exit b[r] of lane i < N holds x_i.  Returns non-zero (wave-uniform) if a
-// pivot was not positive (d_i > 0 <=> 0 < 1 / d_i < inf on the lane that kept it; the caller flags LMH_FLAG_NOT_SPD, and the non-finite
-// values that follow a bad pivot are flagged LMH_FLAG_NONFINITE by the evaluation's own check).
+// all four 16-lane DPP rows then run the same elimination.  The right-hand sides need not be the same in every DPP row: b[r] is updated
+// from the lane-J entry of its own row only, so a caller can give each DPP row its own slice of the columns (M per row) and every column
+// sees the same fused multiply-adds in the same order as in a full copy.  On exit b[r] of lane i < N holds x_i.  Returns non-zero
+// (wave-uniform) if a pivot was not positive (d_i > 0 <=> 0 < 1 / d_i < inf on the lane that kept it; the caller flags LMH_FLAG_NOT_SPD,
+// and the non-finite values that follow a bad pivot are flagged LMH_FLAG_NONFINITE by the evaluation's own check).
 template <int N, int M>
 __device__ __forceinline__ int gj_solve_regs(double (&a)[N], double (&b)[M], unsigned live)
 {
@@ -2365,25 +2367,28 @@ __device__ __forceinline__ int kinv_compute(double *L, unsigned F, double *Kdst,
     }
     WSYNC();
     int bad = 0;
-    {   // both 6 x 6 inverses at once: DPP row 0 = right foot, DPP row 1 = left foot (six unit right-hand sides each)
-        const bool rowon = (row == 0 && useR) || (row == 1 && useL);
+    {   // both 6 x 6 inverses at once, each foot on two DPP rows: rows 0 and 2 = right foot, rows 1 and 3 = left foot.  Both rows of a
+        // foot eliminate its full matrix; DPP row k carries unit right-hand sides 3 (k >> 1) .. 3 (k >> 1) + 2 of its foot
+        const int ft = row & 1, c0 = 3 * (row >> 1);
+        const bool rowon = (ft == 0) ? useR : useL;
         const bool on = rowon && l16 < 6;
-        const int rb = (row < 2) ? 36 * row : 0, lr = (l16 < 6) ? l16 : 0;
-        double a[6], bb[6], myinv = 0.0;
-        const int dd = (row == 0) ? dR : dL;                       // bound torque row of this DPP row's foot (-1: none)
+        const int rb = 36 * ft, lr = (l16 < 6) ? l16 : 0;
+        double a[6], bb[3], myinv = 0.0;
+        const int dd = (ft == 0) ? dR : dL;                        // bound torque row of this DPP row's foot (-1: none)
 #pragma unroll
         for (int c = 0; c < 6; c++) {                              // full rows (Gauss-Jordan), both feet at once; the bound row / column pinned
             const double kv = K[rb + 6 * lr + c];
             a[c] = (l16 == dd || c == dd) ? ((l16 == c) ? 1.0 : 0.0) : kv;
-            bb[c] = (l16 == c) ? 1.0 : 0.0;
         }
+#pragma unroll
+        for (int s = 0; s < 3; s++) bb[s] = (l16 == c0 + s) ? 1.0 : 0.0;
         // K_f entries are O(1e-3 .. 10); a rank-deficient block pivots at ~1e-17
         gj16_step<0>(a, bb, 0x3Fu, l16, rowon, 1e-12, bad, myinv);
 #pragma unroll
-        for (int c = 0; c < 6; c++) bb[c] *= myinv;
-        if (row < 2 && l16 < 6) {
+        for (int s = 0; s < 3; s++) bb[s] *= myinv;
+        if (l16 < 6) {
 #pragma unroll
-            for (int c = 0; c < 6; c++) Ki[36 * row + 6 * l16 + c] = (on && l16 != dd && c != dd) ? bb[c] : 0.0;       // K_f^-1 (symmetric); 0 for a foot without force
+            for (int s = 0; s < 3; s++) Ki[36 * ft + 6 * l16 + c0 + s] = (on && l16 != dd && c0 + s != dd) ? bb[s] : 0.0;   // K_f^-1 (symmetric); 0 for a foot without force
         }
     }
     WSYNC();
@@ -3095,19 +3100,19 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
     WSTAMP(13);
     // ---- Cm t = V (7 right-hand sides): wave 0  |  Z = Mb D^-1 U', Mb bp': helper wave
     if (NW == 1 || wid == 0) {
-        double a[nU], bb[7];
-        const int lr = lane & 15;                                  // every 16-lane DPP row carries a copy of the system (gj_solve_regs)
+        // every 16-lane DPP row carries a copy of the matrix (gj_solve_regs) but only two of the right-hand sides: DPP row k holds columns
+        // 2k and 2k + 1 (row 3: column 6 and a zero dummy that is never stored)
+        double a[nU], bb[2];
+        const int lr = lane & 15, c0 = 2 * (lane >> 4);
 #pragma unroll
         for (int c = 0; c < nU; c++) a[c] = L[Q_CM + 17 * lr + c];
-#pragma unroll
-        for (int r = 0; r < 7; r++) bb[r] = L[Q_TT + 18 * r + lr];
+        bb[0] = L[Q_TT + 18 * c0 + lr];
+        bb[1] = L[(c0 < 6) ? Q_TT + 18 * (c0 + 1) + lr : Q_ZERO];
         WSTAMP(14);
-        if (gj_solve_regs<nU, 7>(a, bb, (1u << nU) - 1u)) flags |= LMH_FLAG_NOT_SPD;
-        bb[0] -= L[Q_OB + lr];                                     // t'' = t_g - ob in column 0
-        if (lane < 16) {
-#pragma unroll
-            for (int r = 0; r < 7; r++) L[Q_TT + 18 * r + lane] = (lane < nU) ? bb[r] : 0.0;
-        }
+        if (gj_solve_regs<nU, 2>(a, bb, (1u << nU) - 1u)) flags |= LMH_FLAG_NOT_SPD;
+        bb[0] -= L[(lane < 16) ? Q_OB + lr : Q_ZERO];              // t'' = t_g - ob in column 0 (slot 0 of DPP row 0)
+        L[Q_TT + 18 * c0 + lr] = (lr < nU) ? bb[0] : 0.0;
+        L[(c0 < 6) ? Q_TT + 18 * (c0 + 1) + lr : Q_TRASH + lane] = (lr < nU) ? bb[1] : 0.0;
         WSTAMP(15);
     }
     if (NW == 1 || wid == 1) {
@@ -3162,16 +3167,20 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
         {   // Si = S^-1: six unit right-hand sides.  S is only moderately conditioned as far as LDL' is concerned, but Gauss-Jordan loses
             // ~cond(S) more digits and leaves S^-1 (hence W) unsymmetric at the 1e-10 level, which the active-set tests of the cone QP
             // (tolerances ~1e-14) do not survive: LDL' on the lower triangle here.
-            double a[6], bb[6];
-            const int l16 = lane & 15, lr = (l16 < 6) ? l16 : 0;   // (a copy of the system per DPP row)
+            double a[6], bb[2];
+            // (a copy of the matrix per DPP row; DPP row k < 3 carries unit columns 2k and 2k + 1, row 3 two zero dummies)
+            const int l16 = lane & 15, lr = (l16 < 6) ? l16 : 0, c0 = 2 * (lane >> 4);
             // Gauss-Jordan on the full S, then S^-1 <- (S^-1 + S^-T) / 2: plain Gauss-Jordan leaves S^-1 (hence W) unsymmetric at the 1e-10 level (it loses
             // ~cond(S) more digits than LDL'), which the active-set tests of the cone QP (tolerances ~1e-14) do not survive; symmetrised, W is symmetric to
             // round-off again and the solve is 1.5k cycles shorter than LDL' with its parked factor (LMH_LDL_SI keeps that form for comparison)
 #pragma unroll
-            for (int c = 0; c < 6; c++) { a[c] = L[Q_S + 7 * lr + c]; bb[c] = (l16 == c) ? 1.0 : 0.0; }
-            if (gj_solve_regs<6, 6>(a, bb, 0x3Fu)) flags |= LMH_FLAG_NOT_SPD;
-#pragma unroll
-            for (int c = 0; c < 6; c++) L[(lane < 6) ? Q_LS + 6 * lane + c : Q_TRASH + lane] = bb[c];
+            for (int c = 0; c < 6; c++) a[c] = L[Q_S + 7 * lr + c];
+            const bool own = c0 < 6 && l16 < 6;                    // lane l16 of this row's columns: an entry of Si
+            bb[0] = (c0 < 6 && l16 == c0) ? 1.0 : 0.0;
+            bb[1] = (c0 < 6 && l16 == c0 + 1) ? 1.0 : 0.0;
+            if (gj_solve_regs<6, 2>(a, bb, 0x3Fu)) flags |= LMH_FLAG_NOT_SPD;
+            L[own ? Q_LS + 6 * l16 + c0 : Q_TRASH + lane] = bb[0];
+            L[own ? Q_LS + 6 * l16 + c0 + 1 : Q_TRASH + lane] = bb[1];
             WSYNC();
             {
                 const int e = (lane < 36) ? lane : 0, i = e / 6, j = e % 6;

@@ -1,0 +1,124 @@
+"""The register Gauss-Jordan solves of the QP set-up give each 16-lane DPP row its own slice of the right-hand sides: the 15 x 15
+Woodbury core (two columns per row), S^-1 (two unit columns per row) and K_f^-1 of both feet in kinv_compute (each foot on two rows,
+three unit columns per row).  A standing robot pushed in several directions runs all of them in one evaluation through lmh_eval: the
+all-free set, sets with free coefficients on both feet, and feet that press on one edge of the sole (pinned row and column of K_f).
+The evaluation is compared with the C oracle at the tolerances of the stage-parity test, and the shipped library with the checker build
+`noedge` (register / general route on the edge sets)."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from helpers import TOL_REL, WEIGHT, close, rel_err, vec_err
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TH = 0.32 + 1e-9
+
+# base velocity pushes (x, y) of a standing robot; the oracle's final free sets (right | left foot, 16 bits each) of this configuration
+# are all free, partial on both feet (e.g. fff9 | fff9, bbff | bbff) and on one side of the sole (ff00, f0f0, 0f0f)
+PUSHES = [(0.05, 0.0), (0.2, 0.0), (-0.5, 0.0), (0.0, 0.05), (0.0, 0.1), (0.0, 0.15), (0.0, -0.05), (0.0, -0.1),
+          (0.1, 0.05), (0.1, -0.05), (-0.2, 0.1), (-0.2, -0.1), (-0.3, 0.15), (-0.3, -0.15), (-0.5, 0.25), (0.3, 0.0)]
+
+
+def _velocities():
+    v = np.zeros((len(PUSHES), 30))
+    v[:, 0] = [p[0] for p in PUSHES]
+    v[:, 1] = [p[1] for p in PUSHES]
+    return v
+
+
+def _edge_foot(m):
+    return m != 0 and bin(m).count("1") >= 6 and any((m & ~side) == 0 for side in (0x0F0F, 0xF0F0, 0x00FF, 0xFF00))
+
+
+def _partial_foot(m):
+    return m not in (0, 0xFFFF) and not _edge_foot(m)
+
+
+def test_pushed_standing_evaluation_against_oracle_stage_by_stage():
+    from linearmpchumanoid_amd.controller import BatchedController, default_config, unpack_debug
+    from oracle.pyoracle import Oracle
+    ik = json.load(open(os.path.join(ROOT, "tests", "golden", "ik_posture.json")))
+    q0 = np.array(ik["q"])
+    v = _velocities()
+    B = v.shape[0]
+    ctl = BatchedController(B, default_config(dt=1e-3, time_horizon=TH, z_com=ik["z_com"], mpc_dt=1e-2, warm_start=0))
+    ctl.set_refs_stance(1.0, 2)
+    st = ctl.new_state(q0, v, t=0.0)
+    out, status, dbg = ctl.stand_step(st, debug=True)
+    torch.cuda.synchronize()
+    out, status, dbg = out.cpu().numpy(), status.cpu().numpy(), dbg.cpu().numpy()
+    masks, mask_mismatch = [], 0
+    for i in range(B):
+        o = Oracle(sim_time=1.0, dt=1e-2, horizon_time=TH, do_ik=True)
+        e = o.eval(q0, v[i], 0.0)
+        qp = o.qp()
+        d = unpack_debug(dbg[i])
+        assert status[i, 0] == e["k"] and status[i, 2] == 0, (i, status[i])
+        assert rel_err(d["a"], qp["x"][:30]) < 1e-8, (i, rel_err(d["a"], qp["x"][:30]))
+        assert close(out[i, :24], e["tau"], TOL_REL), (i, vec_err(out[i, :24], e["tau"]))
+        assert close(out[i, 24:36], e["f"], TOL_REL, scale=WEIGHT), (i, vec_err(out[i, 24:36], e["f"]))
+        assert close(out[i, 36:66], e["qpp"], TOL_REL), (i, vec_err(out[i, 36:66], e["qpp"]))
+        F = (~int(e["active_mask"])) & 0xFFFFFFFF
+        masks.append(F)
+        mask_mismatch += int(((~int(status[i, 3])) & 0xFFFFFFFF) != F)
+    assert mask_mismatch <= B // 6                           # degenerate (c_j == 0) ties may differ
+    # the sets the solves met: all free, both feet partly free (K_f^-1 of both feet), an edge foot (pinned row / column)
+    assert any(F == 0xFFFFFFFF for F in masks)
+    assert any(_partial_foot(F & 0xFFFF) and _partial_foot(F >> 16) for F in masks)
+    assert sum(1 for F in masks if _edge_foot(F & 0xFFFF) or _edge_foot(F >> 16)) >= 3
+
+
+_PROBE = r"""
+import json, os, sys
+sys.path.insert(0, os.getcwd())
+import numpy as np, torch
+from linearmpchumanoid_amd.controller import BatchedController, default_config
+ik = json.load(open("tests/golden/ik_posture.json"))
+v = np.load(sys.argv[2])
+B = v.shape[0]
+ctl = BatchedController(B, default_config(dt=1e-3, time_horizon=0.32 + 1e-9, z_com=ik["z_com"], mpc_dt=1e-2, warm_start=0))
+ctl.set_refs_stance(1.0, 2)
+st = ctl.new_state(np.array(ik["q"]), v, t=0.0)
+out, status = ctl.stand_step(st)
+torch.cuda.synchronize()
+s = status.cpu().numpy()
+np.save(sys.argv[1], out.cpu().numpy())
+print(json.dumps({"flags": s[:, 2].tolist(), "rounds": s[:, 1].tolist(), "masks": [int((~int(x)) & 0xFFFFFFFF) for x in s[:, 3]]}))
+"""
+
+
+def _run_probe(code, variant, timeout=600):
+    env = {k: v for k, v in os.environ.items() if k not in ("LMH_VARIANT", "LMH_DIAG")}
+    if variant:
+        env["LMH_VARIANT"] = variant
+    r = subprocess.run([sys.executable, "-c", code], env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+
+
+def test_shipped_and_noedge_builds_agree_on_the_pushed_robots(tmp_path):
+    """The edge-contact push-through (shipped) and the register / general route (`noedge`) on the same evaluations: same rounds, same
+    final sets, no flags, results equal to rounding."""
+    from linearmpchumanoid_amd import build as hipbuild
+    hipbuild.build_variant("noedge")
+    vpath = str(tmp_path / "v.npy")
+    np.save(vpath, _velocities())
+    outs, res = {}, {}
+    for variant in ("", "noedge"):
+        path = str(tmp_path / f"out_{variant or 'shipped'}.npy")
+        res[variant] = _run_probe(_PROBE.replace("sys.argv[1]", repr(path)).replace("sys.argv[2]", repr(vpath)), variant)
+        outs[variant] = np.load(path)
+    a, b = outs[""], outs["noedge"]
+    assert all(f == 0 for f in res[""]["flags"]) and all(f == 0 for f in res["noedge"]["flags"])
+    assert res[""]["masks"] == res["noedge"]["masks"] and res[""]["rounds"] == res["noedge"]["rounds"]
+    assert any(_edge_foot(F & 0xFFFF) or _edge_foot(F >> 16) for F in res[""]["masks"])
+    worst = 0.0
+    for i in range(a.shape[0]):
+        worst = max(worst, vec_err(a[i, :24], b[i, :24]), np.abs(a[i, 24:36] - b[i, 24:36]).max() / WEIGHT, vec_err(a[i, 36:66], b[i, 36:66]))
+    assert worst < 1e-7, worst
