@@ -57,6 +57,41 @@ def perturbed_velocities(B, seed=20260001):
     return v
 
 
+SWEEP_BANDS = (0.3, 1.0, 3.1)    # half-widths [rad] of the posture sweep around the IK start posture
+SWEEP_SEED = 20261016
+SWEEP_TILT = 1.2                 # |roll|, |pitch| of the sweep's postures: the Euler-rate map of the integrator is singular at pitch = pi/2
+# theta offsets of the 24 joints in the DH table (Robot.cpp:59-87): theta_i = q[6 + i] + DH_OFFSET[i]
+DH_OFFSET = np.zeros(24)
+DH_OFFSET[[1, 6, 7, 13, 18, 23]] = np.array([0.75, -0.5, 0.25, 0.5, 0.5, -0.5]) * np.pi
+
+
+def posture_sweep(q0, B, band, seed=SWEEP_SEED, tilt=SWEEP_TILT):
+    """B states away from the start posture q0, the same draw for the CPU and the GPU tests: joints q0 + U(-band, band) rad, roll and
+    pitch U(-min(band, tilt), min(band, tilt)), yaw U(-band, band), base position q0 + U(-0.1, 0.1) m; velocities
+    perturbed_velocities plus N(0, 0.2^2) on the base's z and angular components; a random previous velocity (Robot::v_).
+    Returns q [B,30], v [B,30], v_prev [B,30]."""
+    q = np.tile(np.asarray(q0, dtype=np.float64), (B, 1))
+    v = perturbed_velocities(B, seed=seed + 1000003)
+    vprev = perturbed_velocities(B, seed=seed + 2000003)
+    lim = min(band, tilt)
+    for i in range(B):
+        rng = np.random.default_rng([seed, int(round(band * 1000)), i])
+        q[i, 0:3] += rng.uniform(-0.1, 0.1, 3)
+        q[i, 3:5] += rng.uniform(-lim, lim, 2)
+        q[i, 5] += rng.uniform(-band, band)
+        q[i, 6:] += rng.uniform(-band, band, 24)
+        v[i, 2:6] += rng.normal(0.0, 0.2, 4)
+    return q, v, vprev
+
+
+def sincos_quadrants(q):
+    """n = rint(theta * 2 / pi) of every angle the forward kinematics takes a sine and cosine of: [B,27] (24 joints with their DH
+    offsets, then roll, pitch, yaw).  n & 3 selects the quadrant branch of a reduced-range sin / cos."""
+    q = np.asarray(q, dtype=np.float64)
+    theta = np.concatenate([q[:, 6:] + DH_OFFSET[None, :], q[:, 3:6]], axis=1)
+    return np.rint(theta * (2.0 / np.pi)).astype(np.int64)
+
+
 def oracle_system(dt, horizon_time, sim_time=2.0, raw_links=None):
     return Oracle(sim_time=sim_time, dt=dt, horizon_time=horizon_time, do_ik=True, raw_links=raw_links)
 

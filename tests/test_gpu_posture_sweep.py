@@ -1,0 +1,424 @@
+"""Posture sweep: the kernel's rigid-body stages, the cone QP and the rollout away from the IK start posture.
+
+Every other stage comparison runs at the start posture with base roll / pitch / yaw = 0, where eight of the nine product terms of R(rpy)
+vanish, every joint angle sits in one quadrant of the reduced-range sin / cos, and the joints that are 0 there never tell the DH
+coefficient c1 from c0 + c1.  Here the joints, the base angles and the base position are drawn around that posture in three bands
+(helpers.posture_sweep: +-0.3, +-1.0 and +-3.1 rad), the same draw as the CPU cross-examination of the oracle uses
+(test_independent_restatement.py), and the device is compared with the C oracle stage by stage, robot by robot; no robot is left out of
+any comparison.  At these postures the feet are far from their references and the accepted free sets are tiny (0 to 5 of 32
+coefficients, single rays, a few rays of one sole edge, no contact force at all): the sets edge_bound_row / kinv_compute never saw.
+
+Tolerances are those of test_stage_parity_single_evaluation (1e-11 model terms, TOL_REL outputs with the WEIGHT floor, 1e-7 final
+state).  The oracle against its independent numpy restatement on this draw: model terms <= 4e-15, tau / f / qdd <= 1e-9, so they leave
+the reference more than three orders of magnitude."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from helpers import (DH_OFFSET, SWEEP_BANDS, SWEEP_SEED, TOL_REL, WEIGHT, close, dense_terms_from_debug, oracle_system, posture_sweep, rel_err,
+                     sincos_quadrants, vec_err)
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DT, TH = 1e-3, 0.016
+B_EVAL, B_ROLL, TICKS = 32, 8, 40
+SIDES = (0x0F0F, 0xF0F0, 0x00FF, 0xFF00)
+KP_FEET = 500.0                                  # controller.hpp:108
+MASS = WEIGHT / 9.81
+RF_Q0 = np.array([[0.0, 0, 1], [0, -1, 0], [1, 0, 0]])    # desired sole orientation (Robot.cpp:28-31)
+
+
+@pytest.fixture(scope="module")
+def consts():
+    o = oracle_system(DT, TH)
+    K = o.gain_row()
+    Px, _ = o.mpc_mats()
+    return dict(zcom=o.zcom, q0=o.robot()["q"].copy(), kpx=K @ Px)
+
+
+def eval_batch(q0, band):
+    """The evaluation batch of a band: B_EVAL states of the sweep; in the widest band B_EVAL more whose roll and pitch span the whole
+    band as well (a single evaluation has no singular pitch; the sweep proper keeps |roll|, |pitch| <= 1.2 for the integrator, which
+    leaves sin / cos of these two angles without their third quadrant)."""
+    q, v, vp = posture_sweep(q0, B_EVAL, band)
+    if band == SWEEP_BANDS[-1]:
+        q2, v2, vp2 = posture_sweep(q0, B_EVAL, band, seed=SWEEP_SEED + 1, tilt=band)
+        q, v, vp = np.concatenate([q, q2]), np.concatenate([v, v2]), np.concatenate([vp, vp2])
+    return q, v, vp
+
+
+def _popcount(m):
+    return bin(m).count("1")
+
+
+def _small_edge_foot(m):
+    return 1 <= _popcount(m) <= 5 and any((m & ~side) == 0 for side in SIDES)
+
+
+_cache = {}
+
+
+def _evaluated(consts, band):
+    """One lmh_eval_debug launch on the band's batch and the oracle's evaluation of every robot of it (cached per band)."""
+    if band in _cache:
+        return _cache[band]
+    from linearmpchumanoid_amd.controller import BatchedController, default_config
+    q, v, vp = eval_batch(consts["q0"], band)
+    B = q.shape[0]
+    ctl = BatchedController(B, default_config(dt=DT, time_horizon=TH, z_com=consts["zcom"], warm_start=0))
+    ctl.set_refs_stance(2.0, 2)
+    st = ctl.new_state(q, v, t=0.0, v_prev=vp)
+    out, status, dbg = ctl.stand_step(st, debug=True)
+    torch.cuda.synchronize()
+    dev = dict(out=out.cpu().numpy(), status=status.cpu().numpy(), dbg=dbg.cpu().numpy(), state=st.cpu().numpy())
+    ref = []
+    for i in range(B):
+        o = oracle_system(DT, TH)
+        o.set_prev_velocity(vp[i])
+        e = o.eval(q[i], v[i], 0.0)
+        ref.append(dict(e=e, t=o.terms(), qp=o.qp(), rb=o.robot()))
+    _cache[band] = dict(q=q, v=v, vp=vp, dev=dev, ref=ref)
+    return _cache[band]
+
+
+def _report(band, worst):
+    print("\nposture sweep, band %.1f: " % band + ", ".join("%s %.2e" % kv for kv in sorted(worst.items())))
+
+
+def test_the_draw_reaches_every_quadrant_of_every_angle(consts):
+    """What the widest band is for: over its evaluation batch every angle the forward kinematics takes a sine and a cosine of (24 joints
+    with their DH offsets, roll, pitch, yaw) falls into all four quadrants n & 3 of the reduced-range kernel; n of every sign and residue
+    occurs (n = -1, -2, -3 are the cases of `(int)n & 3` on a negative n), and every angle whose band reaches past +-pi/4 on both
+    sides (|centre| < 3.1 - pi/4) has negative and positive n of its own.  That is every angle but one: the right hip yaw-pitch joint
+    (joint 1, theta = q + 3 pi / 4) spans [-0.74, 5.46] rad in the widest band and cannot reach n < 0; it takes n = 0 .. 3."""
+    q, _, _ = eval_batch(consts["q0"], SWEEP_BANDS[-1])
+    n = sincos_quadrants(q)
+    for j in range(27):
+        assert set((n[:, j] & 3).tolist()) == {0, 1, 2, 3}, (j, sorted(set(n[:, j].tolist())))
+    assert {-3, -2, -1, 0, 1, 2, 3} <= set(n.ravel().tolist())
+    centre = np.concatenate([consts["q0"][6:] + DH_OFFSET, consts["q0"][3:6]])
+    two_sided = np.abs(centre) < SWEEP_BANDS[-1] - np.pi / 4
+    assert two_sided[24:].all() and [j for j in range(27) if not two_sided[j]] == [1]
+    assert ((n < 0).any(axis=0) & (n > 0).any(axis=0))[two_sided].all()
+    # the narrower bands stay nearer the start posture: the middle one already crosses a quadrant boundary on every angle
+    nm = sincos_quadrants(eval_batch(consts["q0"], SWEEP_BANDS[1])[0])
+    assert all(len(set(nm[:, j].tolist())) >= 2 for j in range(27))
+
+
+@pytest.mark.parametrize("band", SWEEP_BANDS)
+def test_stage_parity_over_the_joint_range(consts, band):
+    """T, X, C, Cg, M, AG, AGpqp, Jpqp, J, CoM, CoM velocity, angular momentum, MPC u0 and the PD references of every robot of the batch
+    against the oracle, with the tolerances and scale rules of test_stage_parity_single_evaluation.  Two of its scales name ingredients
+    that are fixed at the start posture and are taken from the posture here:
+    footAccRef = kp (p_ref - p_sole) + kp e_orientation + kd (0 - v_sole): 500 x 0.05 m there; here kp (0.05 + max|p_sole|) + kp max|e| with
+    the sole positions and the axis-angle orientation errors e = log(R_des' R_sole) of the oracle's own T (the velocity term is bounded by
+    the sum of the others and the result);
+    u0 = -(K Px) (x_com, v_com) + K z: (g / z_c) 0.05 m there; here that plus |K Px| . (max|x_com|, max|v_com|) of the oracle's robot."""
+    from linearmpchumanoid_amd.controller import unpack_debug
+    from oracle import restatement_np as restatement
+    S = _evaluated(consts, band)
+    B = S["q"].shape[0]
+    assert B >= 32
+    worst, bad = {}, []
+
+    def check(i, name, err, tol):
+        worst[name] = max(worst.get(name, 0.0), float(err))
+        if not err < tol:
+            bad.append((i, name, float(err)))
+
+    for i in range(B):
+        r = S["ref"][i]
+        t, qp, rb = r["t"], r["qp"], r["rb"]
+        d = unpack_debug(S["dev"]["dbg"][i]); dd = dense_terms_from_debug(d)
+        tight = dict(T=(dd["T"], t["T"]), X=(dd["X"], t["X"]), C=(d["C"], t["C"]), M=(dd["M"], t["M"]), AG=(d["AG"], t["AG"]),
+                     J=(dd["J"], t["J"]), CoM=(d["CoM"], rb["CoM"]), qref=(d["qppRef"], qp["qppRef"]), href=(d["hGpRef"], qp["hGpRef"]))
+        for name, (a, b) in tight.items():
+            check(i, name, rel_err(a, b), 1e-11)
+        cs = np.abs(t["C"]).max()                                 # velocity-product terms: differences of O(50) quantities
+        check(i, "Cg6", np.abs(d["Cg6"] - t["Cg"][:6]).max() / cs, 1e-11)
+        check(i, "AGpqp", np.abs(d["AGpqp"] - t["AGpqp"]).max() / cs, 1e-11)
+        check(i, "Jpqp", np.abs(d["Jpqp"] - t["Jpqp"]).max() / cs, 1e-11)
+        # momenta: AG vhat, sums of |AG| |vhat| terms
+        ms = np.abs(t["AG"]).max() * max(np.abs(S["v"][i]).max(), 1e-300)
+        check(i, "comVel", np.abs(d["comVel"] - rb["comVel"]).max() * MASS / ms, 1e-11)
+        check(i, "angMom", np.abs(d["angMom"] - rb["angMom"]).max() / ms, 1e-11)
+        psole = max(np.abs(t["T"][7][:3, 3]).max(), np.abs(t["T"][14][:3, 3]).max())
+        eori = max(np.abs(restatement.rot_to_axis_angle(RF_Q0.T @ t["T"][f][:3, :3])).max() for f in (7, 14))
+        fs = KP_FEET * (0.05 + psole) + KP_FEET * eori + np.abs(qp["footAccRef"]).max()
+        check(i, "footAccRef", np.abs(d["footAccRef"] - qp["footAccRef"]).max() / fs, 1e-10)
+        us = (9.81 / 0.26 * 0.05 + abs(consts["kpx"][0]) * np.abs(rb["CoM"][:2]).max() + abs(consts["kpx"][1]) * np.abs(rb["comVel"][:2]).max()
+              + np.abs(qp["u0"]).max())
+        check(i, "u0", np.abs(d["mpc"][:2] - qp["u0"]).max() / us, 1e-11)
+        assert np.array_equal(S["dev"]["state"][i, 60:90], S["v"][i])        # Robot::v_ <- dq
+    _report(band, worst)
+    assert not bad, (len(bad), bad[:12])
+
+
+@pytest.mark.parametrize("band", SWEEP_BANDS)
+def test_cone_qp_and_outputs_over_the_joint_range(consts, band):
+    """The same batches through the QP: k bit-exact and no flag on any robot; the accelerations a = x[:30] and the cone coefficients
+    c = x[42:74] against the oracle's solution; tau, f (on the robot's weight), qdd at TOL_REL;
+    the oracle-independent KKT conditions of test_cone_qp_kkt_at_scale on the device's own P, qv, c.  The final active sets may differ on
+    degenerate (c_j = 0) ties, at most B // 6 of them.  The batch must contain what it is for, judged by the ORACLE's masks: at most five
+    free coefficients in total, a foot whose 1..5 free coefficients all lie on one edge of the sole, and (widest band) a robot with
+    every bound active, i.e. no contact force.
+    c is compared on every robot through what the problem determines.  The objective sees c through the wrench G c (G = the oracle's
+    12 x 32 cone matrix, singular values 0.1 .. 4.0) and through eps_coeff |c|^2 = 1e-8 |c|^2 alone, so a gradient residual r moves c by
+    r / 1e-8 along the directions that leave the wrench unchanged: the oracle and its numpy restatement, whose f agree to 4e-11 of the
+    weight on this draw, differ there by up to 8e-6 of 1 + max c with equal final sets and by 0.58 with tied ones.  Compared are therefore
+    G c, at the 1e-8 of `a`, on the scale weight + max|G c|, and the component of c in the row space of G, pinv(G) G c, at 1e-8 / sigma_min(G)
+    of 1 + max c (the two CPU codings: 4e-11 and 1.8e-10, tied sets included).  The remaining component is printed beside the device's
+    own stationarity residual over eps_coeff, which bounds it; the KKT conditions judge it."""
+    from linearmpchumanoid_amd.controller import unpack_debug
+    S = _evaluated(consts, band)
+    B = S["q"].shape[0]
+    out, status = S["dev"]["out"], S["dev"]["status"]
+    worst, bad, mism, free_sets = {}, [], 0, []
+
+    def check(i, name, err, tol):
+        worst[name] = max(worst.get(name, 0.0), float(err))
+        if not err < tol:
+            bad.append((i, name, float(err)))
+
+    for i in range(B):
+        e, qp = S["ref"][i]["e"], S["ref"][i]["qp"]
+        assert e["qp_status"] == 0, (i, e["qp_status"])
+        if status[i, 0] != e["k"] or status[i, 2] != 0:
+            bad.append((i, "status", status[i].tolist()))
+        d = unpack_debug(S["dev"]["dbg"][i])
+        x = qp["x"]
+        check(i, "a", rel_err(d["a"], x[:30]), 1e-8)
+        G = qp["A"][6:18, 42:74]
+        Gp = np.linalg.pinv(G)
+        dc = d["c"] - x[42:74]
+        check(i, "Gc", np.abs(G @ dc).max() / (WEIGHT + np.abs(G @ x[42:74]).max()), 1e-8)
+        check(i, "c_rowspace", np.abs(Gp @ (G @ dc)).max() / (1.0 + x[42:74].max()), 1e-8 * np.linalg.norm(Gp, 2))
+        worst["c_nullspace (not asserted)"] = max(worst.get("c_nullspace (not asserted)", 0.0), float(np.abs(dc - Gp @ (G @ dc)).max() / (1.0 + x[42:74].max())))
+        check(i, "tau", vec_err(out[i, :24], e["tau"]), TOL_REL)
+        check(i, "qdd", vec_err(out[i, 36:66], e["qpp"]), TOL_REL)
+        worst["f/weight"] = max(worst.get("f/weight", 0.0), float(np.abs(out[i, 24:36] - e["f"]).max() / WEIGHT))
+        if not close(out[i, 24:36], e["f"], TOL_REL, scale=WEIGHT):
+            bad.append((i, "f", float(np.abs(out[i, 24:36] - e["f"]).max())))
+        # KKT of min 1/2 c'Pc - q'c, c >= 0 on the device's record
+        Pm, qv, c = d["P"], d["qv"], d["c"]
+        lam = Pm @ c - qv
+        scale = 1.0 + np.abs(qv).max()
+        free = c > 1e-9 * (1.0 + c.max())
+        check(i, "kkt_c_neg", max(-c.min(), 0.0) / (1.0 + c.max()), 1e-9)
+        check(i, "kkt_free", np.abs(lam[free]).max(initial=0.0) / scale, 1e-9)
+        check(i, "kkt_bound", max(-lam[~free].min(initial=0.0), 0.0) / scale, 1e-9)
+        worst["residual/eps (not asserted)"] = max(worst.get("residual/eps (not asserted)", 0.0),
+                                                   float(np.abs(lam[free]).max(initial=0.0) / 1e-8 / (1.0 + x[42:74].max())))
+        F = (~int(e["active_mask"])) & 0xFFFFFFFF
+        free_sets.append(F)
+        mism += int((int(status[i, 3]) & 0xFFFFFFFF) != e["active_mask"])
+    _report(band, worst)
+    print("free sets (oracle):", " ".join("%08x" % F for F in free_sets), "| mask mismatches", mism)
+    assert not bad, (len(bad), bad[:12])
+    assert mism <= B // 6, mism
+    assert any(_popcount(F) <= 5 for F in free_sets)
+    assert any(_small_edge_foot(F & 0xFFFF) or _small_edge_foot(F >> 16) for F in free_sets)
+    if band == SWEEP_BANDS[-1]:
+        assert any(F == 0 for F in free_sets)
+        i0 = free_sets.index(0)
+        assert np.abs(S["ref"][i0]["e"]["f"]).max() < TOL_REL * 1e-3 * WEIGHT
+
+
+_PROBE = r"""
+import json, os, sys
+sys.path.insert(0, os.getcwd())
+import numpy as np, torch
+from linearmpchumanoid_amd.controller import BatchedController, default_config
+s = np.load(sys.argv[2])
+B = s["q"].shape[0]
+ctl = BatchedController(B, default_config(dt=float(s["dt"]), time_horizon=float(s["th"]), z_com=float(s["zcom"]), warm_start=0))
+ctl.set_refs_stance(2.0, 2)
+st = ctl.new_state(s["q"], s["v"], t=0.0, v_prev=s["vp"])
+out, status = ctl.stand_step(st)
+torch.cuda.synchronize()
+st = status.cpu().numpy()
+np.save(sys.argv[1], out.cpu().numpy())
+print(json.dumps({"flags": st[:, 2].tolist(), "rounds": st[:, 1].tolist(), "masks": [int((~int(x)) & 0xFFFFFFFF) for x in st[:, 3]]}))
+"""
+
+
+def _run_probe(code, variant, timeout=600):
+    env = {k: v for k, v in os.environ.items() if k not in ("LMH_VARIANT", "LMH_DIAG")}
+    if variant:
+        env["LMH_VARIANT"] = variant
+    r = subprocess.run([sys.executable, "-c", code], env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+
+
+def test_shipped_and_noedge_builds_agree_on_the_small_edge_subsets(consts, tmp_path):
+    """edge_bound_row takes any non-empty subset of a sole edge for edge contact, a single ray included, and leaves rejection to
+    kinv_compute's pivot threshold.  All three bands through the shipped library and through the checker build `noedge` (register /
+    general route on those sets), each in a fresh process: same flags, rounds and final sets, outputs equal to 1e-7, and feet with 1..5
+    free coefficients on one edge among them."""
+    from linearmpchumanoid_amd import build as hipbuild
+    hipbuild.build_variant("noedge")
+    parts = [eval_batch(consts["q0"], band) for band in SWEEP_BANDS]
+    q, v, vp = (np.concatenate([p[j] for p in parts]) for j in range(3))
+    spath = str(tmp_path / "states.npz")
+    np.savez(spath, q=q, v=v, vp=vp, dt=DT, th=TH, zcom=consts["zcom"])
+    outs, res = {}, {}
+    for variant in ("", "noedge"):
+        path = str(tmp_path / f"out_{variant or 'shipped'}.npy")
+        res[variant] = _run_probe(_PROBE.replace("sys.argv[1]", repr(path)).replace("sys.argv[2]", repr(spath)), variant)
+        outs[variant] = np.load(path)
+    a, b = outs[""], outs["noedge"]
+    assert all(f == 0 for f in res[""]["flags"]) and all(f == 0 for f in res["noedge"]["flags"]), (res[""]["flags"], res["noedge"]["flags"])
+    assert res[""]["masks"] == res["noedge"]["masks"] and res[""]["rounds"] == res["noedge"]["rounds"]
+    small = [i for i, F in enumerate(res[""]["masks"]) if _small_edge_foot(F & 0xFFFF) or _small_edge_foot(F >> 16)]
+    assert len(small) >= 8, len(small)
+    worst = 0.0
+    for i in range(a.shape[0]):
+        worst = max(worst, vec_err(a[i, :24], b[i, :24]), np.abs(a[i, 24:36] - b[i, 24:36]).max() / WEIGHT, vec_err(a[i, 36:66], b[i, 36:66]))
+    print("\nshipped vs noedge over %d robots (%d with a small edge subset): worst %.2e" % (a.shape[0], len(small), worst))
+    assert worst < 1e-7, worst
+
+
+def _rollout_states(q0, band):
+    return posture_sweep(q0, B_ROLL, band)
+
+
+@pytest.mark.parametrize("band", SWEEP_BANDS)
+def test_rollout_away_from_the_start_posture_against_oracle(consts, band):
+    """40 RK4 ticks from the sweep's states: the helper wave's forward kinematics (configuration from registers through lane permutes),
+    the Euler-rate map with its 1 / cos(pitch) and the integrator, none of which the debug record shows.  k, the final state to 1e-7 and
+    tau / f of EVERY logged tick against the oracle's rollout."""
+    from linearmpchumanoid_amd.controller import BatchedController, default_config
+    q, v, vp = _rollout_states(consts["q0"], band)
+    B = q.shape[0]
+    assert B >= 8
+    ctl = BatchedController(B, default_config(dt=DT, time_horizon=TH, z_com=consts["zcom"]))
+    ctl.set_refs_stance(1.0, 2)
+    st = ctl.new_state(q, v, t=0.0, v_prev=vp)
+    out, status, log = ctl.rollout(st, TICKS, log=True)
+    torch.cuda.synchronize()
+    stn, log, status = st.cpu().numpy(), log.cpu().numpy(), status.cpu().numpy()
+    worst, bad = {"state": 0.0, "tau": 0.0, "f/weight": 0.0}, []
+    for i in range(B):
+        o = oracle_system(DT, TH, sim_time=1.0)
+        o.set_prev_velocity(vp[i])
+        r = o.rollout(np.concatenate([q[i], v[i]]), 0.0, TICKS, log=True)
+        assert np.isfinite(r["state"]).all() and abs(r["state"][4]) < 1.2            # the reference itself stays clear of pitch = pi/2
+        if status[i, 0] != r["k"][-1] or status[i, 2] != 0:
+            bad.append((i, "status", status[i].tolist()))
+        worst["state"] = max(worst["state"], vec_err(stn[i, :60], r["state"]))
+        if not close(stn[i, :60], r["state"], 1e-7):
+            bad.append((i, "state", vec_err(stn[i, :60], r["state"])))
+        for tk in range(TICKS):
+            ref = r["log"][tk]
+            worst["tau"] = max(worst["tau"], vec_err(log[tk, i, :24], ref[:24]))
+            worst["f/weight"] = max(worst["f/weight"], float(np.abs(log[tk, i, 24:] - ref[24:]).max() / WEIGHT))
+            if not close(log[tk, i, :24], ref[:24], TOL_REL):
+                bad.append((i, tk, "tau", vec_err(log[tk, i, :24], ref[:24])))
+            if not close(log[tk, i, 24:], ref[24:], TOL_REL, scale=WEIGHT):
+                bad.append((i, tk, "f", float(np.abs(log[tk, i, 24:] - ref[24:]).max())))
+    _report(band, worst)
+    assert not bad, (len(bad), bad[:12])
+
+
+def test_two_wave_and_single_wave_schedules_agree_bit_for_bit_away_from_the_start_posture(consts):
+    """As test_two_wave_schedule_is_deterministic_and_equals_the_single_wave_schedule, on the middle band: the plain evaluation (two
+    waves) equals the debug evaluation (one wave) bit for bit, and a one-tick rollout (whose first stage is that evaluation, its later
+    ones the helper wave's look-ahead kinematics) is identical over repeated launches, raises no flag and equals four chained plain
+    evaluations combined by RK4 on the host."""
+    from linearmpchumanoid_amd.controller import BatchedController, default_config
+    q, v, vp = eval_batch(consts["q0"], SWEEP_BANDS[1])
+    B = q.shape[0]
+    ctl = BatchedController(B, default_config(dt=DT, time_horizon=TH, z_com=consts["zcom"], warm_start=0))
+    ctl.set_refs_stance(2.0, 2)
+    st1 = ctl.new_state(q, v, t=0.0, v_prev=vp)
+    st2 = st1.clone()
+    o1, s1 = ctl.stand_step(st1)
+    o2, s2, _ = ctl.stand_step(st2, debug=True)
+    torch.cuda.synchronize()
+    assert torch.equal(o1[:, :78], o2[:, :78]) and torch.equal(s1, s2) and torch.equal(st1, st2)
+    runs = []
+    for _ in range(2):
+        st = ctl.new_state(q, v, t=0.0, v_prev=vp)
+        out, status, log = ctl.rollout(st, 1, log=True)
+        torch.cuda.synchronize()
+        runs.append((st.clone(), out.clone(), status.clone(), log.clone()))
+    assert all(torch.equal(a, b) for a, b in zip(runs[0], runs[1]))
+    assert (runs[0][2][:, 2] == 0).all()
+    assert (s1[:, 0] == 0).all() and (runs[0][2][:, 0] == 1).all()    # preview index of t = 0 | of the tick's last stage at t = dt
+    assert torch.equal(runs[0][1][:, :36], runs[0][3][0])         # the tick's log line is the output record of its last evaluation
+    # The log carries the tick's FOURTH stage (as the oracle's does), so the first stage cannot be read off it.  What can be compared is
+    # the whole tick: the rollout's helper-wave kinematics, Euler-rate map and RK4 sums against four chained PLAIN evaluations (each of
+    # which equals the debug kernel bit for bit, above) combined on the host as rk4.hpp / apps/offline/main.cpp:91-122 do.  The rollout's
+    # evaluations order their arithmetic differently from the plain kernel's, so the two agree as the rollout and the oracle do: final
+    # state at 1e-7, the fourth stage's tau / f at TOL_REL (measured: 4e-11, 1.7e-10, 2.7e-10 of the weight).
+    def xdot(x, qpp):
+        xd = np.zeros_like(x)
+        xd[:, :30] = x[:, 30:]
+        xd[:, :3] = x[:, 30:33] + np.cross(x[:, 33:36], x[:, :3])
+        p_, y_, w = x[:, 4], x[:, 5], x[:, 33:36]
+        xd[:, 3] = (np.cos(y_) * w[:, 0] + np.sin(y_) * w[:, 1]) / np.cos(p_)
+        xd[:, 4] = -np.sin(y_) * w[:, 0] + np.cos(y_) * w[:, 1]
+        xd[:, 5] = (np.cos(y_) * w[:, 0] + np.sin(y_) * w[:, 1]) * np.tan(p_) + w[:, 2]
+        xd[:, 30:] = qpp
+        return xd
+    x0 = np.concatenate([q, v], axis=1)
+    st = ctl.new_state(q, v, t=0.0, v_prev=vp)
+    ks, xs, last = [], x0, None
+    for stage, (h, ts) in enumerate(((0.0, 0.0), (0.5 * DT, 0.5 * DT), (0.5 * DT, 0.5 * DT), (DT, DT))):
+        xs = x0 if stage == 0 else x0 + h * ks[-1]
+        st[:, :60] = torch.as_tensor(xs).to(st.device)
+        st[:, 90] = ts
+        o, sst = ctl.stand_step(st)                               # leaves Robot::v_ (state[:, 60:90]) = this stage's velocity for the next
+        torch.cuda.synchronize()
+        assert (sst[:, 2] == 0).all()
+        last = o.cpu().numpy()
+        ks.append(xdot(xs, last[:, 36:66]))
+    x1 = x0 + (DT / 6.0) * (ks[0] + 2 * ks[1] + 2 * ks[2] + ks[3])
+    roll_state, roll_log = runs[0][0].cpu().numpy(), runs[0][3].cpu().numpy()
+    worst = dict(state=0.0, tau=0.0, f=0.0)
+    for i in range(B):
+        worst["state"] = max(worst["state"], vec_err(roll_state[i, :60], x1[i]))
+        worst["tau"] = max(worst["tau"], vec_err(roll_log[0, i, :24], last[i, :24]))
+        worst["f"] = max(worst["f"], float(np.abs(roll_log[0, i, 24:] - last[i, 24:36]).max() / WEIGHT))
+        assert close(roll_state[i, :60], x1[i], 1e-7), (i, vec_err(roll_state[i, :60], x1[i]))
+        assert close(roll_log[0, i, :24], last[i, :24], TOL_REL) and close(roll_log[0, i, 24:], last[i, 24:36], TOL_REL, scale=WEIGHT), i
+    print("\none-tick rollout vs four chained plain evaluations: state %.2e, tau %.2e, f/weight %.2e" % (worst["state"], worst["tau"], worst["f"]))
+
+
+def test_mixed_precision_mode_on_the_middle_band(consts):
+    """LMH_PRECISION_MIXED at +-1.0 rad (sincosf and the fp32 model-term chain at large angles), with the bounds of
+    test_mixed_precision_mode: k bit-exact, no flag, tau within 1e-4 of the fp64 oracle relative to its own largest entry, f within
+    1e-4 of the robot's weight (the forces of these postures range from nothing to several times the weight; an fp32 chain cannot
+    resolve a vanishing force relative to itself)."""
+    from linearmpchumanoid_amd import capi
+    from linearmpchumanoid_amd.controller import BatchedController, default_config
+    q, v, vp = _rollout_states(consts["q0"], SWEEP_BANDS[1])
+    B, nt = q.shape[0], 12
+    ctl = BatchedController(B, default_config(dt=DT, time_horizon=TH, z_com=consts["zcom"], warm_start=1, precision=capi.PRECISION_MIXED))
+    ctl.set_refs_stance(2.0, 2)
+    st = ctl.new_state(q, v, t=0.0, v_prev=vp)
+    out, status, log = ctl.rollout(st, nt, log=True)
+    torch.cuda.synchronize()
+    log, status = log.cpu().numpy(), status.cpu().numpy()
+    e_tau, e_f, bad = [], [], []
+    for i in range(B):
+        o = oracle_system(DT, TH, sim_time=1.0)
+        o.set_prev_velocity(vp[i])
+        r = o.rollout(np.concatenate([q[i], v[i]]), 0.0, nt, log=True)
+        if status[i, 0] != r["k"][-1] or status[i, 2] != 0:
+            bad.append((i, "status", status[i].tolist()))
+        for tk in range(nt):
+            e_tau.append(rel_err(log[tk, i, :24], r["log"][tk][:24]))
+            e_f.append(float(np.abs(log[tk, i, 24:] - r["log"][tk][24:]).max() / WEIGHT))
+            if not (e_tau[-1] < 1e-4 and e_f[-1] < 1e-4):
+                bad.append((i, tk, e_tau[-1], e_f[-1]))
+    print("\nmixed precision, band %.1f: tau median %.2e max %.2e, f/weight median %.2e max %.2e"
+          % (SWEEP_BANDS[1], np.median(e_tau), max(e_tau), np.median(e_f), max(e_f)))
+    assert not bad, (len(bad), bad[:12])
+    assert max(e_tau) > 1e-9                                       # fp32-sized, not fp64-sized, errors: the mode really ran
