@@ -3448,8 +3448,44 @@ __device__ __forceinline__ void kinv_prework(double *L, LmhCParams &P)
 // Controller::WBC Hessian/gradient + solveQP (controller.cpp:94-132,388-479), see file header.
 // PIPE (rollout): the helper wave prepares K_f^-1 at the end of its set-up share instead of at the start of the evaluation, and spends the
 // cone solve -- wave 0 alone -- inside `window` (the next evaluation's clock references and kinematics, lmh_rollout_kernel).
-template <int NW, bool F32 = false, bool PIPE = false, class WF = NoWindow, bool CGLIN = true>
-__device__ __forceinline__ int phase_qp(double *L, LmhCParams &P, int ph, int wid, unsigned *Fmask_io, int *iters_out, double *dbgp = nullptr, WF window = WF())
+// Entry k < 6 of the base acceleration in the world frame, X0 acc = a[0:6]: w = R0 a_ang ; v = R0 (a_lin - B0 w), linear part first.
+// X: the 21 entries of P_X0 (E0 | p0 | B0), er: row k % 3 of E0.  One body for the evaluation kernels (phase_outputs_qdd: six lanes, operands
+// from LDS) and the rollout's register tail (phase_qp: every lane, a from the recovery's registers), so that the two cannot drift apart.
+__device__ __forceinline__ double base_acc_world(const double (&X)[21], const double (&er)[3], const double (&a)[6], int k)
+{
+    const int r = k % 3;
+    const double *E0 = X, *B0 = X + 12;
+    const double w0 = E0[0] * a[0] + E0[1] * a[1] + E0[2] * a[2];
+    const double w1 = E0[3] * a[0] + E0[4] * a[1] + E0[5] * a[2];
+    const double w2 = E0[6] * a[0] + E0[7] * a[1] + E0[8] * a[2];
+    double val;
+    if (k < 3) {                                                   // linear part goes first in qdd
+        const double u0 = a[3] - (B0[0] * w0 + B0[1] * w1 + B0[2] * w2);
+        const double u1 = a[4] - (B0[3] * w0 + B0[4] * w1 + B0[5] * w2);
+        const double u2 = a[5] - (B0[6] * w0 + B0[7] * w1 + B0[8] * w2);
+        val = er[0] * u0 + er[1] * u1 + er[2] * u2;
+    } else val = (r == 0) ? w0 : (r == 1) ? w1 : w2;
+    return val;
+}
+// the operands of base_acc_world that do not depend on the accelerations (k: the lane's entry, < 6)
+__device__ __forceinline__ void base_acc_load(const double *L, int k, double (&X)[21], double (&er)[3])
+{
+    const int r = k % 3;
+#pragma unroll
+    for (int e = 0; e < 21; e++) X[e] = (e >= 9 && e < 12) ? 0.0 : L[P_X0 + e];      // (p0 is not used)
+#pragma unroll
+    for (int c = 0; c < 3; c++) er[c] = L[P_X0 + 3 * r + c];
+}
+// Register tail of the pipelined fp64 rollout (template flag TAIL, wave 0, and only without the plant: P.plant == 0 is read in the recovery,
+// which reports it in `on`, instead of being carried in scalar registers through the QP; `k4` is wave-uniform).  There the recovery hands the
+// integrator its xdot in a register instead of through L[P_A] / L[P_QDD]: lane i < 60 gets component i of xdot (i < 30: the position half
+// the helper left in L[P_XDQ]; 30..35: the base acceleration in the world frame; 36..59: a[6..29]), and the non-finite guard of the
+// accelerations and the contact wrench tests the registers they were formed in.  L[P_A] is stored only when `k4` (the helper forms
+// the torques at the fourth stage only); nobody stores L[P_QDD] here (the rollout loop does, at the fourth stage, for store_out).
+struct RkTail { bool on, k4; double xd; };
+#define P_XDQ P_AG                 // 30 doubles: the angular rows of AG are dead once the QP fills have read the references
+template <int NW, bool F32 = false, bool PIPE = false, class WF = NoWindow, bool CGLIN = true, bool TAIL = false>
+__device__ __forceinline__ int phase_qp(double *L, LmhCParams &P, int ph, int wid, unsigned *Fmask_io, int *iters_out, double *dbgp, WF window, RkTail &tail)
 {
     const int lane = LANE;
     int flags;
@@ -3531,8 +3567,20 @@ __device__ __forceinline__ int phase_qp(double *L, LmhCParams &P, int ph, int wi
     }
     {   // the three products in registers: lane l16 of every DPP row holds w[l16], r and lam come out in lanes 0..5 of every row, and each
         // sum takes its terms through row broadcasts -- one read of the wrench instead of three LDS round trips on the path both waves wait for
-        const int l16 = lane & 15, i6 = (l16 < 6) ? l16 : 0, j = lane & 31, js = (j < 30) ? j : 0;
+        // register tail (RkTail): lanes 30..59 take row lane - 30 instead, the integrator's lane of that acceleration (only the P_YT address
+        // moves; lanes 0..29 keep their rows: a[0..5] for the base transform, and the store of L[P_A] where somebody reads it)
+        // (the new rows serve the plant's path as well: it stores lanes 0..29 only.)  The plant flag is read here, behind the cone solve, and
+        // first needed behind the chains: carried through the QP it costs two scalar registers the kernel does not have
+        LmhCParams *Pq_ = &P;
+        asm volatile("" : "+s"(Pq_));
+        const bool fz = TAIL && Pq_->plant == 0;                   // wave-uniform
+        const int l16 = lane & 15, i6 = (l16 < 6) ? l16 : 0, j = TAIL ? ((lane >= 30) ? lane - 30 : lane) : (lane & 31), js = (j < 30) ? j : 0;
         const double wv = L[P_W12 + ((l16 < 12) ? l16 : 0)];
+        // what the tail needs besides a, ahead of the chains: P_X0 belongs to this evaluation until wave 0's next phase_com_x, the helper
+        // wrote P_XDQ before the "solve | tiles" join
+        double X0r[21], er[3], xdq = 0.0;
+        const int kb = (lane >= 30 && lane < 36) ? lane - 30 : 0;
+        if constexpr (TAIL) { base_acc_load(L, kb, X0r, er); xdq = L[P_XDQ + ((lane < 30) ? lane : 0)]; }
         const double *jc = L + P_JC + i6, *si = L + P_SI + 6 * i6, *yt = L + P_YT + js;      // base columns of the feet Jacobian: P_JC[foot][row][0..5]
         double jm[12], sm[6], ym[6];
 #pragma unroll
@@ -3550,7 +3598,24 @@ __device__ __forceinline__ int phase_qp(double *L, LmhCParams &P, int ph, int wi
         const double lam = -nl;                                    // lam = -Si r  (nothing else reads it)
         dpp_fmac_lane<0>(s, lam, ym[0]); dpp_fmac_lane<1, false>(s, lam, ym[1]); dpp_fmac_lane<2, false>(s, lam, ym[2]);
         dpp_fmac_lane<3, false>(s, lam, ym[3]); dpp_fmac_lane<4, false>(s, lam, ym[4]); dpp_fmac_lane<5, false>(s, lam, ym[5]);
-        if (lane < 30) L[P_A + lane] = -s;                         // a = -(Y_g + Y_M lam)
+        if ((!fz || tail.k4) && lane < 30) L[P_A + lane] = -s;     // a = -(Y_g + Y_M lam)
+        if (fz) {
+            WSYNC();
+            WSTAMP(26);
+            bsync<NW>();                                           // (stays: it publishes the helper's look-ahead kinematics; at k4, L[P_A] to the helper)
+            WSTAMP(27);
+            // wave 0 alone from here, nothing below touches LDS: the base rows of a from lanes 0..5, wave-uniform
+            const double av = -s;
+            double a6[6];
+#pragma unroll
+            for (int c = 0; c < 6; c++) a6[c] = bcast_lane(av, c);
+            const double val = base_acc_world(X0r, er, a6, kb);
+            tail.on = true;
+            tail.xd = (lane < 30) ? xdq : (lane < 36) ? val : av;
+            // non-finite guard (see controller_eval) on the registers: every a[i] and every w[i] sits in some lane
+            if (__ballot(!(fabs(av) <= 1.0e300) || !(fabs(wv) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
+            return flags;
+        }
     }
     WSYNC();
     WSTAMP(26);
@@ -3707,20 +3772,13 @@ __device__ __forceinline__ void phase_outputs_tau(double *L)
 __device__ __forceinline__ void phase_outputs_qdd(double *L, int a_src = P_A)
 {
     const int lane = LANE;
-    if (lane >= 32 && lane < 38) {                                 // X0 acc = a[0:6]: w = R0 a_ang ; v = R0 (a_lin - B0 w)
-        const int k = lane - 32, r = k % 3;
-        const double *E0 = L + P_X0, *B0 = L + P_X0 + 12, *a = L + a_src;
-        const double w0 = E0[0] * a[0] + E0[1] * a[1] + E0[2] * a[2];
-        const double w1 = E0[3] * a[0] + E0[4] * a[1] + E0[5] * a[2];
-        const double w2 = E0[6] * a[0] + E0[7] * a[1] + E0[8] * a[2];
-        double val;
-        if (k < 3) {                                               // linear part goes first in qdd
-            const double u0 = a[3] - (B0[0] * w0 + B0[1] * w1 + B0[2] * w2);
-            const double u1 = a[4] - (B0[3] * w0 + B0[4] * w1 + B0[5] * w2);
-            const double u2 = a[5] - (B0[6] * w0 + B0[7] * w1 + B0[8] * w2);
-            val = E0[3 * r] * u0 + E0[3 * r + 1] * u1 + E0[3 * r + 2] * u2;
-        } else val = (r == 0) ? w0 : (r == 1) ? w1 : w2;
-        L[P_QDD + k] = val;
+    if (lane >= 32 && lane < 38) {
+        const int k = lane - 32;
+        double X[21], er[3], a[6];
+        base_acc_load(L, k, X, er);
+#pragma unroll
+        for (int c = 0; c < 6; c++) a[c] = L[a_src + c];
+        L[P_QDD + k] = base_acc_world(X, er, a, k);
     }
     if (lane >= 40 && lane < 64) L[P_QDD + 6 + (lane - 40)] = L[a_src + 6 + (lane - 40)];
     WSYNC();
@@ -3732,11 +3790,13 @@ __device__ __forceinline__ void phase_outputs_qdd(double *L, int a_src = P_A)
 // into the next evaluation's forward kinematics.
 // PIPE (rollout kernel only): the kinematics of this evaluation were run ahead by the helper wave, inside the previous evaluation's
 // `window` (phase_qp), and so were the clock-only references; wave 0 starts at the X images.
-template <int NW, typename R, bool QF32 = false, bool PIPE = false, class WF = NoWindow>
+template <int NW, typename R, bool QF32 = false, bool PIPE = false, class WF = NoWindow, bool TAIL = false>
 __device__ __forceinline__ int controller_eval(double *L, LmhCParams &P, int inst, double t, int wid, unsigned *Fmask, int *k_out, int *iters_out, double *dbg, bool need_tau = true, WF window = WF(),
-                                               const IbPack *ibp = nullptr)
+                                               const IbPack *ibp = nullptr, RkTail *tailp = nullptr)
 {
     int flags = 0, ph = 0;
+    RkTail tail_off = {false, false, 0.0};
+    RkTail &tail = tailp ? *tailp : tail_off;                      // register tail (TAIL): the rollout's wave 0 only, never with the plant (tail.on comes back from phase_qp)
     // in-kernel stamps (debug build of the kernel only): s_memtime at the phase boundaries
 #define STAMP(i) do { if (dbg && LANE == 0) dbg[(wid ? 3950 : 4000) + (i)] = (double)clock64(); } while (0)   // wave 1 (diagnostic two-wave debug kernel): 3950..
     STAMP(0);
@@ -3809,12 +3869,20 @@ __device__ __forceinline__ int controller_eval(double *L, LmhCParams &P, int ins
     bsync<NW>();
     WSTAMP(8);
     STAMP(7);
-    flags |= phase_qp<NW, QF32, PIPE, WF, std::is_same_v<R, double>>(L, P, ph, wid, Fmask, iters_out, dbg, window);
+    tail.on = false;                                               // set by wave 0's recovery (phase_qp) unless the plant runs
+    tail.k4 = need_tau;
+    flags |= phase_qp<NW, QF32, PIPE, WF, std::is_same_v<R, double>, TAIL>(L, P, ph, wid, Fmask, iters_out, dbg, window, tail);
     STAMP(8);
-    if (plant && (NW == 1 || wid == 0)) phase_plant(L, P);         // the torques drive a plant instead of being thrown away (main.cpp:118-121)
+    if (TAIL && tail.on) {                                         // outputs and guard came out of the recovery's registers (phase_qp)
+        WSTAMP(28);
+        return flags;
+    }
+    // (TAIL: behind the return above wave 0 is here with the plant only, and the helper needs no plant flag: one scalar less across the QP)
+    const bool plant_w0 = TAIL ? wid == 0 : plant && (NW == 1 || wid == 0);
+    if (plant_w0) phase_plant(L, P);                               // the torques drive a plant instead of being thrown away (main.cpp:118-121)
     // need_tau (wave-uniform): the integrator never reads the torques -- the rollout asks for them at the k4 stage only (log, final record)
-    if constexpr (NW == 1) { if (need_tau) phase_outputs_tau(L); phase_outputs_qdd(L, plant ? (int)PL_AP : (int)P_A); }
-    else { if (wid == 0) phase_outputs_qdd(L, plant ? (int)PL_AP : (int)P_A); else if (need_tau) phase_outputs_tau(L); }
+    if constexpr (NW == 1) { if (need_tau) phase_outputs_tau(L); phase_outputs_qdd(L, plant_w0 ? (int)PL_AP : (int)P_A); }
+    else { if (wid == 0) phase_outputs_qdd(L, plant_w0 ? (int)PL_AP : (int)P_A); else if (need_tau) phase_outputs_tau(L); }
     WSTAMP(28);
     STAMP(9);
     if (dbg) {
@@ -3834,10 +3902,17 @@ __device__ __forceinline__ int controller_eval(double *L, LmhCParams &P, int ins
     // non-finite guard (reference aborts on NaN/Inf, controller.cpp:448-466)
     // checked on the QP solution (accelerations, contact wrench): tau = M a + C - J'w is finite iff they are, and the
     // torques may still be in flight on the helper wave
+    // TAIL: the helper's copy of the guard was never read (wave 0 alone writes the status record), and L[P_A] is not published at three
+    // stages of four any more
+    if (TAIL && wid != 0) return flags;
     double chk = 0.0;
     if (LANE < 30) chk = L[P_A + LANE]; else if (LANE >= 32 && LANE < 44) chk = L[P_W12 + LANE - 32];
     const bool nf = !(fabs(chk) <= 1.0e300);
     if (__ballot(nf) != 0ull) flags |= LMH_FLAG_NONFINITE;
+    if (TAIL && wid == 0) {                                        // (the plant: its xdot from where its path leaves it)
+        const int l60 = (LANE < 60) ? LANE : 0;
+        tail.xd = L[(l60 >= 30) ? P_QDD + l60 - 30 : P_XDQ + l60];
+    }
     return flags;
 }
 
@@ -3979,15 +4054,16 @@ __device__ __forceinline__ int rollout_claim(int *ticket, int n_inst, long long 
 // (its lanes >= 30 then hold don't-cares).
 // XDQ: 0 = plain; 1 = (helper wave, ahead) also leave the position half of xdot in L[P_XDQ]; 2 = (wave 0, behind the helper) take it from there
 // instead of forming it again -- three fp64 divisions and the cross product leave wave 0's path between two evaluations.
-#define P_XDQ P_AG                 // 30 doubles: the angular rows of AG are dead once the QP fills have read the references
+// 3 = (wave 0, register tail) xdot arrives in `xdr`: nothing is read from LDS
 template <int XDQ = 0>
-__device__ __forceinline__ void rk4_stage(double *L, int stage, int lane, double dt, int xd4, double &x, double &ksum, double &xs)
+__device__ __forceinline__ void rk4_stage(double *L, int stage, int lane, double dt, int xd4, double &x, double &ksum, double &xs, double xdr = 0.0)
 {
     // branch-free: every lane loads from a valid address and forms the few products of the base rows, the lane's class picks the result
     // (the lane-class branches and the four-way stage switch were ~100 scalar instructions per call)
     double xd;
     const int l60 = (lane < 60) ? lane : 0;
-    if constexpr (XDQ == 2) xd = L[(l60 >= 30) ? P_QDD + l60 - 30 : P_XDQ + l60];
+    if constexpr (XDQ == 3) xd = xdr;
+    else if constexpr (XDQ == 2) xd = L[(l60 >= 30) ? P_QDD + l60 - 30 : P_XDQ + l60];
     else {
         const int l30 = (l60 < 30) ? l60 : 0;
         const double vq = L[(l60 >= 30) ? P_QDD + l60 - 30 : P_V + l60];       // joint rates | accelerations: xdot as it stands
@@ -4088,6 +4164,7 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
     // forward kinematics there (window below).
     // Not with the fp32 QP (tolerance sweep): its set-up runs on wave 0 alone and uses all of the scratch; that build keeps the plain schedule.
     constexpr bool PIPE = !QF32;
+    constexpr bool TAIL = PIPE && std::is_same_v<R, double>;       // register tail of an evaluation (RkTail)
     double x = 0.0, t = st[90];
     unsigned F = 0xFFFFFFFFu;
     LMH_POISON_LDS(L, LDS_DOUBLES);
@@ -4127,13 +4204,16 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
             // sin / cos of pitch, yaw of this evaluation | of the next: the other buffer
             const int xd4 = (PIPE && (stage & 1)) ? (int)P_SCB : (int)P_SC + 52;
             const int xd4n = (stage & 1) ? (int)P_SC + 52 : (int)P_SCB;
-            if (wid == 0) {
+            LmhCParams *Pe = Pc;
+            asm volatile("" : "+s"(Pe));                           // opaque: the loads below belong to this evaluation
+            // TAIL (fp64 pipelined kernel): wave 0 gets xdot in a register (RkTail: from the recovery, with the plant from where its path
+            // leaves it) and the previous stage has already published this evaluation's state (below; the chunk's first: set-up above)
+            RkTail tail = {false, false, 0.0};
+            if (!TAIL && wid == 0) {
                 WSYNC();
                 if (lane < 60) L[P_Q + lane] = xs;
                 WSYNC();
             }
-            LmhCParams *Pe = Pc;
-            asm volatile("" : "+s"(Pe));                           // opaque: the loads below belong to this evaluation
 #ifdef LMH_DIAG_TL
             if (lane == 0) g_tl[wid] = (log && tick0 + tick == n_ticks - 1 && stage == LMH_DIAG_TL) ? log + (size_t)256 * inst : nullptr;
             WSYNC();
@@ -4166,9 +4246,19 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
                     WSTAMP(70);
                 }
             };
-            flags |= controller_eval<2, R, QF32, PIPE, decltype(window)>(L, *Pe, inst, ts, wid, &F, &k, &iters, nullptr, stage == 3, window, &ibp);
+            flags |= controller_eval<2, R, QF32, PIPE, decltype(window), TAIL>(L, *Pe, inst, ts, wid, &F, &k, &iters, nullptr, stage == 3, window, &ibp, &tail);
             WSTAMP(71);
-            if (wid == 0) {
+            if (TAIL && wid == 0) {
+                itmax = (iters > itmax) ? iters : itmax;
+                const double xprev = xs;
+                rk4_stage<3>(L, stage, lane, dt, xd4, x, ksum, xs, tail.xd);
+                if (stage == 3) xs = x;                            // the next tick starts from x (what `xs = x` at its top says)
+                // one publish: Robot::v_ <- dq and the state of the next evaluation; behind the recovery's join wave 0 has read nothing
+                // from LDS, and the helper touches neither.  The accelerations only where somebody reads them (store_out, end of a chunk)
+                if (lane >= 30 && lane < 60) { L[P_VP + lane - 30] = xprev; if (stage == 3) L[P_QDD + lane - 30] = tail.xd; }
+                if (lane < 60) L[P_Q + lane] = xs;
+                WSYNC();
+            } else if (wid == 0) {
                 itmax = (iters > itmax) ? iters : itmax;
                 const double xprev = xs;
                 if constexpr (PIPE) rk4_stage<2>(L, stage, lane, dt, xd4, x, ksum, xs); else rk4_stage<0>(L, stage, lane, dt, xd4, x, ksum, xs);
