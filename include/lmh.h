@@ -171,10 +171,39 @@ int lmh_set_segments(lmh_handle *h, const double *segs, int n_seg, const uint16_
 int lmh_gen_walk(lmh_handle *h, double simulation_time, int num_steps, double time_per_step, double ds_time, double step_height,
                  double settle_time, int first_support, double foot_y);
 int lmh_gen_jump(lmh_handle *h, double simulation_time, double stance_time, double flight_time);
-/* read the current reference set back (HOST out; any pointer may be NULL): n_samples doubles / bytes / uint16, n_seg x LMH_SEG_STRIDE doubles */
+/* Per-robot plans (build-defined): every robot of the handle walks / jumps on a schedule of its own.  The sample grid is
+ * shared -- n_samples = (int)((simulation_time + 0.5) / mpc_dt) for every robot, as lmh_gen_walk counts; mpc_dt, the horizon and
+ * simulation_time stay per handle -- and so is the stride of the segment table: n_seg = 2 max(num_steps) + 2 records per robot (what
+ * lmh_num_segments then returns); a robot with fewer steps uses its first 2 num_steps + 2 records, the rest of its slice is zero and no
+ * seg_of_sample entry of that robot points there.  Device layout: zmp_x, zmp_y, phase, seg_of_sample [n][n_samples], segs
+ * [n][n_seg][LMH_SEG_STRIDE]; a robot reads its slice when its preview index moves, nothing else in an evaluation changes.
+ * n must be n_instances.  A failed call (bad argument, failed allocation) leaves the handle on its previous plan.
+ * Every other reference setter (lmh_set_refs, lmh_set_refs_stance, lmh_set_segments, lmh_gen_walk, lmh_gen_jump) puts the handle back on
+ * ONE shared plan (lmh_set_segments alone on a per-robot handle keeps robot 0's samples as the shared ones); lmh_set_xscale keeps its
+ * meaning: robot i's x quantities are its own plan's times xscale[i]. */
+typedef struct lmh_walk_spec {   /* one robot's arguments of lmh_gen_walk */
+    double time_per_step, ds_time, step_height, settle_time, foot_y;
+    int32_t num_steps, first_support;
+} lmh_walk_spec;
+typedef struct lmh_jump_spec { double stance_time, flight_time; } lmh_jump_spec;   /* one robot's arguments of lmh_gen_jump */
+/* one plan per robot generated ON THE DEVICE (one workgroup per robot; no host arrays are uploaded).  specs: HOST [n].  Every spec is
+ * checked by the rules of lmh_gen_walk / lmh_gen_jump; the error text names the first offending robot ("robot 7: ..."). */
+int lmh_gen_walk_batch(lmh_handle *h, double simulation_time, const lmh_walk_spec *specs, int n);
+int lmh_gen_jump_batch(lmh_handle *h, double simulation_time, const lmh_jump_spec *specs, int n);
+/* one plan per robot uploaded from the host (what linearmpchumanoid_amd/trajectories.walk_plans / jump_plans state): zmp_x, zmp_y
+ * [n][n_samples], phase [n][n_samples] or NULL (all double support), segs [n][n_seg][LMH_SEG_STRIDE] and seg_of_sample [n][n_samples], or
+ * NULL / 0 / NULL for no segments.  The checks of lmh_set_refs / lmh_set_segments apply to every robot (seg_of_sample < n_seg; the
+ * error text names the robot). */
+int lmh_set_plans(lmh_handle *h, const double *zmp_x, const double *zmp_y, const uint8_t *phase, int n_samples,
+                  const double *segs, int n_seg, const uint16_t *seg_of_sample, int n);
+int lmh_plans_per_instance(const lmh_handle *h);          /* 0: one shared plan, 1: one plan per robot */
+/* read the current reference set back (HOST out; any pointer may be NULL): n_samples doubles / bytes / uint16, n_seg x LMH_SEG_STRIDE doubles.
+ * lmh_get_refs on a handle with per-robot plans returns robot 0's plan (as lmh_get_mpc_gain reports instance 0); lmh_get_plan reads robot
+ * `inst`'s (on a shared plan every inst in [0, n_instances) returns the shared one). */
 int lmh_num_ref_samples(const lmh_handle *h);
 int lmh_num_segments(const lmh_handle *h);
 int lmh_get_refs(lmh_handle *h, double *zmp_x, double *zmp_y, uint8_t *phase, double *segs, uint16_t *seg_of_sample);
+int lmh_get_plan(lmh_handle *h, int inst, double *zmp_x, double *zmp_y, uint8_t *phase, double *segs, uint16_t *seg_of_sample);
 /* per-instance scale of the ZMP x samples and of the x-axis foot polynomials (step length): HOST [n_instances]
  * or NULL for 1.0 */
 int lmh_set_xscale(lmh_handle *h, const double *xscale, int n);

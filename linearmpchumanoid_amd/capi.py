@@ -40,6 +40,7 @@ EXPORTS = [
     "lmh_synchronize", "lmh_robot_com", "lmh_robot_com_host", "lmh_last_out_host", "lmh_ik_host", "lmh_set_segments", "lmh_set_xscale",
     "lmh_make_summary", "lmh_write_summary", "lmh_read_summary", "lmh_write_log", "lmh_read_log",
     "lmh_gen_walk", "lmh_gen_jump", "lmh_num_ref_samples", "lmh_num_segments", "lmh_get_refs",
+    "lmh_gen_walk_batch", "lmh_gen_jump_batch", "lmh_set_plans", "lmh_plans_per_instance", "lmh_get_plan",
 ]
 
 
@@ -51,6 +52,17 @@ class LmhConfig(C.Structure):
         "w_com_lin", "w_com_ang", "w_base_pos", "w_base_ang", "w_joints", "w_force", "w_foot",
         "eps_coeff")] + [("warm_start", C.c_int32), ("max_qp_iters", C.c_int32), ("precision", C.c_int32), ("bpp_rounds", C.c_int32),
                                      ("plant", C.c_int32), ("reserved", C.c_int32)] + [(n, C.c_double) for n in ("contact_k", "contact_d", "contact_dt", "contact_mu", "mpc_dt")]
+
+
+class LmhWalkSpec(C.Structure):
+    """struct lmh_walk_spec (include/lmh.h): one robot's arguments of lmh_gen_walk."""
+    _fields_ = [(n, C.c_double) for n in ("time_per_step", "ds_time", "step_height", "settle_time", "foot_y")] + \
+               [("num_steps", C.c_int32), ("first_support", C.c_int32)]
+
+
+class LmhJumpSpec(C.Structure):
+    """struct lmh_jump_spec (include/lmh.h)."""
+    _fields_ = [("stance_time", C.c_double), ("flight_time", C.c_double)]
 
 
 _lib = None
@@ -104,6 +116,11 @@ def lib():
     L.lmh_num_ref_samples.argtypes = [vp]
     L.lmh_num_segments.argtypes = [vp]
     L.lmh_get_refs.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.lmh_gen_walk_batch.argtypes = [vp, dp, vp, ip]
+    L.lmh_gen_jump_batch.argtypes = [vp, dp, vp, ip]
+    L.lmh_set_plans.argtypes = [vp, vp, vp, vp, ip, vp, ip, vp, ip]
+    L.lmh_plans_per_instance.argtypes = [vp]
+    L.lmh_get_plan.argtypes = [vp, ip, vp, vp, vp, vp, vp]
     L.lmh_make_summary.argtypes = [vp, vp, vp, vp, vp, vp]
     L.lmh_write_summary.argtypes = [C.c_char_p, vp, u64, dp]
     L.lmh_read_summary.argtypes = [C.c_char_p, vp, u64, u64p, dpp]

@@ -10,7 +10,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import capi
+from . import capi, trajectories
 from .capi import LmhConfig, check
 
 
@@ -155,6 +155,61 @@ class BatchedController:
         ph = np.zeros(n, dtype=np.uint8)
         segs = np.zeros((ns, capi.SEG_STRIDE)); sos = np.zeros(n, dtype=np.uint16)
         check(capi.lib().lmh_get_refs(self._h, _np_ptr(zx), _np_ptr(zy), _np_ptr(ph), _np_ptr(segs) if ns else None, _np_ptr(sos) if ns else None))
+        return dict(zmp_x=zx, zmp_y=zy, phase=ph, segs=segs, seg_of_sample=sos)
+
+    # -- one plan per robot (include/lmh.h, "Per-robot plans")
+    def gen_walk_batch(self, simulation_time, specs):
+        """lmh_gen_walk_batch: one walking plan per robot, generated on the device.  specs: dict of arrays of length B with gen_walk's
+        keyword arguments (scalars broadcast, missing ones take gen_walk's defaults); the plans are trajectories.walk_plans(...)."""
+        sp, _ = trajectories.broadcast_specs(specs, trajectories.WALK_SPEC_DEFAULTS, self.B)
+        arr = (capi.LmhWalkSpec * self.B)()
+        for i in range(self.B):
+            for k, v in sp.items():
+                setattr(arr[i], k, v[i].item())
+        check(capi.lib().lmh_gen_walk_batch(self._h, float(simulation_time), arr, self.B))
+
+    def gen_jump_batch(self, simulation_time, specs):
+        """lmh_gen_jump_batch: one jumping schedule per robot (trajectories.jump_plans), generated on the device."""
+        sp, _ = trajectories.broadcast_specs(specs, trajectories.JUMP_SPEC_DEFAULTS, self.B)
+        arr = (capi.LmhJumpSpec * self.B)()
+        for i in range(self.B):
+            arr[i].stance_time, arr[i].flight_time = float(sp["stance_time"][i]), float(sp["flight_time"][i])
+        check(capi.lib().lmh_gen_jump_batch(self._h, float(simulation_time), arr, self.B))
+
+    def set_plans(self, zmp_x, zmp_y, phase=None, segs=None, seg_of_sample=None):
+        """lmh_set_plans: one plan per robot uploaded from the host -- zmp_x, zmp_y [n,n_samples], phase [n,n_samples] or None,
+        segs [n,n_seg,52] and seg_of_sample [n,n_samples] or None (trajectories.walk_plans / jump_plans return these as a dict:
+        ctl.set_plans(**plans)).  n must be B (the library checks it)."""
+        zx = np.ascontiguousarray(zmp_x, dtype=np.float64)
+        zy = np.ascontiguousarray(zmp_y, dtype=np.float64)
+        if zx.ndim != 2 or zy.shape != zx.shape:
+            raise ValueError("zmp_x, zmp_y must be [n,n_samples]")
+        ph = None if phase is None else np.ascontiguousarray(phase, dtype=np.uint8)
+        if ph is not None and ph.shape != zx.shape:
+            raise ValueError("phase must be [n,n_samples]")
+        sg = so = None
+        n_seg = 0
+        if segs is not None:
+            sg = np.ascontiguousarray(segs, dtype=np.float64)
+            so = np.ascontiguousarray(seg_of_sample, dtype=np.uint16)
+            if sg.ndim != 3 or sg.shape[0] != zx.shape[0] or sg.shape[2] != capi.SEG_STRIDE or so.shape != zx.shape:
+                raise ValueError("segs must be [n,n_seg,52] and seg_of_sample [n,n_samples]")
+            n_seg = sg.shape[1]
+        check(capi.lib().lmh_set_plans(self._h, _np_ptr(zx), _np_ptr(zy), None if ph is None else _np_ptr(ph), zx.shape[1],
+                                       None if sg is None else _np_ptr(sg), n_seg, None if so is None else _np_ptr(so), zx.shape[0]))
+
+    @property
+    def plans_per_instance(self):
+        """True while every robot has a plan of its own (gen_walk_batch / gen_jump_batch / set_plans); any other setter ends it."""
+        return bool(capi.lib().lmh_plans_per_instance(self._h))
+
+    def get_plan(self, i):
+        """Robot i's plan read back from the device (the shared one on a shared handle): the dict of get_refs."""
+        n, ns = capi.lib().lmh_num_ref_samples(self._h), capi.lib().lmh_num_segments(self._h)
+        zx, zy = np.zeros(n), np.zeros(n)
+        ph = np.zeros(n, dtype=np.uint8)
+        segs = np.zeros((ns, capi.SEG_STRIDE)); sos = np.zeros(n, dtype=np.uint16)
+        check(capi.lib().lmh_get_plan(self._h, int(i), _np_ptr(zx), _np_ptr(zy), _np_ptr(ph), _np_ptr(segs) if ns else None, _np_ptr(sos) if ns else None))
         return dict(zmp_x=zx, zmp_y=zy, phase=ph, segs=segs, seg_of_sample=sos)
 
     def set_xscale(self, xscale):

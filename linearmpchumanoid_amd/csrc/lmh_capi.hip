@@ -20,6 +20,8 @@ extern "C" void lmh_launch_com(const LmhDevParams *P, const double *q, double *c
 extern "C" void lmh_launch_ik(const LmhDevParams *P, double *q, const LmhIkTarget *target, int32_t *iters, hipStream_t s);
 extern "C" void lmh_launch_gen_walk(const LmhWalkSpec *W, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos, hipStream_t s);
 extern "C" void lmh_launch_gen_jump(int n, double time_step, double stance_time, double flight_time, double *zx, double *zy, uint8_t *phase, hipStream_t s);
+extern "C" void lmh_launch_gen_walk_batch(const LmhWalkSpec *d_specs, int n_plans, int seg_stride, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos, hipStream_t s);
+extern "C" void lmh_launch_gen_jump_batch(int n, double time_step, const LmhJumpSpec *d_specs, int n_plans, double *zx, double *zy, uint8_t *phase, hipStream_t s);
 extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
 
 static thread_local std::string g_err;
@@ -34,6 +36,7 @@ struct lmh_handle {
     double *d_segs = nullptr, *d_xscale = nullptr;
     uint16_t *d_sos = nullptr;
     int n_seg = 0;
+    bool per_robot = false;           // false: one shared plan; true: one plan per robot (the five reference buffers hold B slices)
     uint8_t *d_phase = nullptr;
     // staging for the host-buffer convenience calls
     double *d_state = nullptr, *d_out = nullptr;
@@ -232,6 +235,7 @@ static void fill_params(lmh_handle *h)
     const lmh_config &c = h->cfg;
     P.model = h->d_model; P.mpc = h->d_mpc; P.zmpx = h->d_zx; P.zmpy = h->d_zy; P.phase = h->d_phase; P.gcol = h->d_gcol;
     P.segs = h->d_segs; P.seg_of_sample = h->d_sos; P.xscale = h->d_xscale; P.n_seg = h->n_seg;
+    P.ref_stride = h->per_robot ? h->n_samples : 0; P.seg_stride = h->per_robot ? h->n_seg : 0;
     P.model_stride = (h->n_models > 1) ? LMH_MODEL_STRIDE : 0;
     P.mpc_stride = 3 * (h->N + 1) + 4;
     P.mpc_stride_inst = (h->n_gain > 1) ? P.mpc_stride : 0;
@@ -406,7 +410,7 @@ extern "C" int lmh_set_refs(lmh_handle *h, const double *zx, const double *zy, c
         HIPCHK(hipMalloc(&h->d_phase, (size_t)n));
         HIPCHK(hipMemcpy(h->d_phase, phase, (size_t)n, hipMemcpyHostToDevice));
     }
-    h->n_samples = n;
+    h->n_samples = n; h->per_robot = false;
     if (h->d_sos) { (void)hipFree(h->d_sos); h->d_sos = nullptr; }
     if (h->d_segs) { (void)hipFree(h->d_segs); h->d_segs = nullptr; }
     h->n_seg = 0;                                                    // segments are tied to the sample grid
@@ -441,7 +445,8 @@ extern "C" int lmh_set_segments(lmh_handle *h, const double *segs, int n_seg, co
     HIPCHK(hipSetDevice(h->device));
     if (h->d_segs) { HIPCHK(hipFree(h->d_segs)); h->d_segs = nullptr; }
     if (h->d_sos) { HIPCHK(hipFree(h->d_sos)); h->d_sos = nullptr; }
-    h->n_seg = 0;
+    h->n_seg = 0; h->per_robot = false;                              // back on one shared plan (of a per-robot set, robot 0's samples stay)
+    fill_params(h);                                                  // P never points at the freed table
     if (n_seg > 0) {
         if (!segs || !sos) return fail(LMH_ERR_BAD_ARG, "null segment table");
         if (n_samples != h->n_samples) return fail(LMH_ERR_BAD_ARG, "seg_of_sample must cover the ZMP reference samples (call lmh_set_refs first)");
@@ -759,18 +764,19 @@ extern "C" int lmh_read_log(const char *path, double *log, uint64_t capacity, ui
 }
 
 // ---------------------------------------------------------------------------- reference generators on the device
-static int alloc_refs(lmh_handle *h, int n, int n_seg)
+static int alloc_refs(lmh_handle *h, int n, int n_seg, int n_plans = 1)
 {
     // allocate the new set first, swap it in, then free the old one: a failed hipMalloc leaves the handle on its previous references
     // (still consistent with P), never on freed pointers
     double *zx = nullptr, *zy = nullptr, *segs = nullptr;
     uint8_t *ph = nullptr;
     uint16_t *sos = nullptr;
-    hipError_t e = hipMalloc(&zx, sizeof(double) * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc(&zy, sizeof(double) * (size_t)n);
-    if (e == hipSuccess) e = hipMalloc(&ph, (size_t)n);
-    if (e == hipSuccess && n_seg > 0) e = hipMalloc(&segs, sizeof(double) * LMH_SEG_STRIDE * (size_t)n_seg);
-    if (e == hipSuccess && n_seg > 0) e = hipMalloc(&sos, sizeof(uint16_t) * (size_t)n);
+    const size_t np = (size_t)n_plans;                              // slices per buffer: 1 (shared plan) or n_instances
+    hipError_t e = hipMalloc(&zx, sizeof(double) * (size_t)n * np);
+    if (e == hipSuccess) e = hipMalloc(&zy, sizeof(double) * (size_t)n * np);
+    if (e == hipSuccess) e = hipMalloc(&ph, (size_t)n * np);
+    if (e == hipSuccess && n_seg > 0) e = hipMalloc(&segs, sizeof(double) * LMH_SEG_STRIDE * (size_t)n_seg * np);
+    if (e == hipSuccess && n_seg > 0) e = hipMalloc(&sos, sizeof(uint16_t) * (size_t)n * np);
     if (e != hipSuccess) {
         void *fresh[] = {zx, zy, ph, segs, sos};
         for (void *b : fresh) if (b) (void)hipFree(b);
@@ -778,20 +784,27 @@ static int alloc_refs(lmh_handle *h, int n, int n_seg)
     }
     void *old[] = {h->d_zx, h->d_zy, h->d_phase, h->d_segs, h->d_sos};
     h->d_zx = zx; h->d_zy = zy; h->d_phase = ph; h->d_segs = segs; h->d_sos = sos;
-    h->n_seg = 0; h->n_samples = 0;                                 // the callers set both once the generator kernel has filled the buffers
+    h->n_seg = 0; h->n_samples = 0; h->per_robot = false;           // the callers set all three once the generator kernel has filled the buffers
     fill_params(h);                                                 // P never points at the freed set
     for (void *b : old) if (b) (void)hipFree(b);
     return LMH_OK;
+}
+
+// the argument rules of lmh_gen_walk (one spec of lmh_gen_walk_batch): nullptr = fine
+static const char *walk_spec_error(double simulation_time, int num_steps, double time_per_step, double ds_time, double settle_time, int first_support)
+{
+    if (num_steps < 1 || num_steps > LMH_GEN_MAX_STEPS) return "num_steps must be in [1, 1022]";
+    if (!(time_per_step > 0.0) || !(ds_time >= 0.0) || !(ds_time < time_per_step) || !(settle_time >= 0.0) || !(simulation_time > 0.0))
+        return "need 0 <= ds_time < time_per_step, settle_time >= 0, simulation_time > 0";
+    if (first_support != LMH_PHASE_RIGHT && first_support != LMH_PHASE_LEFT) return "first_support must be LMH_PHASE_RIGHT or LMH_PHASE_LEFT";
+    return nullptr;
 }
 
 extern "C" int lmh_gen_walk(lmh_handle *h, double simulation_time, int num_steps, double time_per_step, double ds_time, double step_height,
                             double settle_time, int first_support, double foot_y)
 {
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
-    if (num_steps < 1 || num_steps > LMH_GEN_MAX_STEPS) return fail(LMH_ERR_BAD_ARG, "num_steps must be in [1, 1022]");
-    if (!(time_per_step > 0.0) || !(ds_time >= 0.0) || !(ds_time < time_per_step) || !(settle_time >= 0.0) || !(simulation_time > 0.0))
-        return fail(LMH_ERR_BAD_ARG, "need 0 <= ds_time < time_per_step, settle_time >= 0, simulation_time > 0");
-    if (first_support != LMH_PHASE_RIGHT && first_support != LMH_PHASE_LEFT) return fail(LMH_ERR_BAD_ARG, "first_support must be LMH_PHASE_RIGHT or LMH_PHASE_LEFT");
+    if (const char *msg = walk_spec_error(simulation_time, num_steps, time_per_step, ds_time, settle_time, first_support)) return fail(LMH_ERR_BAD_ARG, msg);
     const int n = (int)((simulation_time + 0.5) / h->mpc_dt);       // zmpGeneration.cpp:41
     if (n < 1) return fail(LMH_ERR_BAD_ARG, "no samples");
     HIPCHK(hipSetDevice(h->device));
@@ -809,10 +822,16 @@ extern "C" int lmh_gen_walk(lmh_handle *h, double simulation_time, int num_steps
     return LMH_OK;
 }
 
+static const char *jump_spec_error(double simulation_time, double stance_time, double flight_time)
+{
+    if (!(stance_time >= 0.0) || !(flight_time >= 0.0) || !(simulation_time > 0.0)) return "times must be non-negative";
+    return nullptr;
+}
+
 extern "C" int lmh_gen_jump(lmh_handle *h, double simulation_time, double stance_time, double flight_time)
 {
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
-    if (!(stance_time >= 0.0) || !(flight_time >= 0.0) || !(simulation_time > 0.0)) return fail(LMH_ERR_BAD_ARG, "times must be non-negative");
+    if (const char *msg = jump_spec_error(simulation_time, stance_time, flight_time)) return fail(LMH_ERR_BAD_ARG, msg);
     const int n = (int)((simulation_time + 0.5) / h->mpc_dt);
     if (n < 1) return fail(LMH_ERR_BAD_ARG, "no samples");
     HIPCHK(hipSetDevice(h->device));
@@ -823,6 +842,138 @@ extern "C" int lmh_gen_jump(lmh_handle *h, double simulation_time, double stance
     HIPCHK(hipDeviceSynchronize());
     h->n_samples = n;
     fill_params(h);
+    return LMH_OK;
+}
+
+// ---------------------------------------------------------------------------- one plan per robot
+static std::string robot_msg(int i, const char *msg) { return "robot " + std::to_string(i) + ": " + msg; }
+
+// device copy of a host spec array for the batched generators (freed by the caller)
+template <class T> static int upload_specs(const std::vector<T> &specs, T **d_out)
+{
+    T *d = nullptr;
+    HIPCHK(hipMalloc(&d, sizeof(T) * specs.size()));
+    hipError_t e = hipMemcpy(d, specs.data(), sizeof(T) * specs.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); return fail(LMH_ERR_HIP, std::string("spec upload: ") + hipGetErrorString(e)); }
+    *d_out = d;
+    return LMH_OK;
+}
+
+extern "C" int lmh_gen_walk_batch(lmh_handle *h, double simulation_time, const lmh_walk_spec *specs, int n)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    if (!specs) return fail(LMH_ERR_BAD_ARG, "null spec array");
+    if (n != h->B) return fail(LMH_ERR_BAD_ARG, "n must be n_instances");
+    const int ns = (int)((simulation_time + 0.5) / h->mpc_dt);      // zmpGeneration.cpp:41: one sample grid for all robots
+    int max_steps = 0;
+    std::vector<LmhWalkSpec> W((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const lmh_walk_spec &s = specs[i];
+        if (const char *msg = walk_spec_error(simulation_time, s.num_steps, s.time_per_step, s.ds_time, s.settle_time, s.first_support))
+            return fail(LMH_ERR_BAD_ARG, robot_msg(i, msg));
+        LmhWalkSpec &w = W[(size_t)i];
+        w.time_step = h->mpc_dt; w.time_per_step = s.time_per_step; w.ds_time = s.ds_time; w.step_height = s.step_height;
+        w.settle_time = s.settle_time; w.foot_y = s.foot_y;
+        w.n_samples = ns; w.num_steps = s.num_steps; w.first_support = s.first_support; w.pad = 0;
+        if (s.num_steps > max_steps) max_steps = s.num_steps;
+    }
+    if (ns < 1) return fail(LMH_ERR_BAD_ARG, "no samples");
+    HIPCHK(hipSetDevice(h->device));
+    const int n_seg = 2 * max_steps + 2;                            // one stride for all robots
+    LmhWalkSpec *d_specs = nullptr;
+    int rc = upload_specs(W, &d_specs);
+    if (rc != LMH_OK) return rc;
+    rc = alloc_refs(h, ns, n_seg, n);
+    if (rc != LMH_OK) { (void)hipFree(d_specs); return rc; }
+    lmh_launch_gen_walk_batch(d_specs, n, n_seg, h->d_zx, h->d_zy, h->d_phase, h->d_segs, h->d_sos, nullptr);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    (void)hipFree(d_specs);
+    if (e != hipSuccess) return fail(LMH_ERR_HIP, std::string("lmh_gen_walk_batch: ") + hipGetErrorString(e));
+    h->n_samples = ns; h->n_seg = n_seg; h->per_robot = true;
+    fill_params(h);
+    return LMH_OK;
+}
+
+extern "C" int lmh_gen_jump_batch(lmh_handle *h, double simulation_time, const lmh_jump_spec *specs, int n)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    if (!specs) return fail(LMH_ERR_BAD_ARG, "null spec array");
+    if (n != h->B) return fail(LMH_ERR_BAD_ARG, "n must be n_instances");
+    std::vector<LmhJumpSpec> J((size_t)n);
+    for (int i = 0; i < n; i++) {
+        if (const char *msg = jump_spec_error(simulation_time, specs[i].stance_time, specs[i].flight_time)) return fail(LMH_ERR_BAD_ARG, robot_msg(i, msg));
+        J[(size_t)i].stance_time = specs[i].stance_time; J[(size_t)i].flight_time = specs[i].flight_time;
+    }
+    const int ns = (int)((simulation_time + 0.5) / h->mpc_dt);
+    if (ns < 1) return fail(LMH_ERR_BAD_ARG, "no samples");
+    HIPCHK(hipSetDevice(h->device));
+    LmhJumpSpec *d_specs = nullptr;
+    int rc = upload_specs(J, &d_specs);
+    if (rc != LMH_OK) return rc;
+    rc = alloc_refs(h, ns, 0, n);
+    if (rc != LMH_OK) { (void)hipFree(d_specs); return rc; }
+    lmh_launch_gen_jump_batch(ns, h->mpc_dt, d_specs, n, h->d_zx, h->d_zy, h->d_phase, nullptr);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    (void)hipFree(d_specs);
+    if (e != hipSuccess) return fail(LMH_ERR_HIP, std::string("lmh_gen_jump_batch: ") + hipGetErrorString(e));
+    h->n_samples = ns; h->per_robot = true;
+    fill_params(h);
+    return LMH_OK;
+}
+
+extern "C" int lmh_set_plans(lmh_handle *h, const double *zx, const double *zy, const uint8_t *phase, int n_samples,
+                             const double *segs, int n_seg, const uint16_t *sos, int n)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    if (!zx || !zy || n_samples < 1 || n_seg < 0) return fail(LMH_ERR_BAD_ARG, "bad argument");
+    if (n != h->B) return fail(LMH_ERR_BAD_ARG, "n must be n_instances");
+    if (n_seg > 0) {
+        if (!segs || !sos) return fail(LMH_ERR_BAD_ARG, "null segment table");
+        if (n_seg > 65536) return fail(LMH_ERR_BAD_ARG, "seg_of_sample is 16 bits wide: at most 65536 segments");
+        for (int i = 0; i < n; i++)
+            for (int k = 0; k < n_samples; k++)
+                if (sos[(size_t)i * n_samples + k] >= n_seg) return fail(LMH_ERR_BAD_ARG, robot_msg(i, "seg_of_sample entry out of range"));
+    }
+    HIPCHK(hipSetDevice(h->device));
+    int rc = alloc_refs(h, n_samples, n_seg, n);
+    if (rc != LMH_OK) return rc;
+    const size_t ns = (size_t)n_samples * (size_t)n;
+    HIPCHK(hipMemcpy(h->d_zx, zx, sizeof(double) * ns, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(h->d_zy, zy, sizeof(double) * ns, hipMemcpyHostToDevice));
+    if (phase) HIPCHK(hipMemcpy(h->d_phase, phase, ns, hipMemcpyHostToDevice));
+    else HIPCHK(hipMemset(h->d_phase, 0, ns));
+    if (n_seg > 0) {
+        HIPCHK(hipMemcpy(h->d_segs, segs, sizeof(double) * LMH_SEG_STRIDE * (size_t)n_seg * (size_t)n, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(h->d_sos, sos, sizeof(uint16_t) * ns, hipMemcpyHostToDevice));
+    }
+    h->n_samples = n_samples; h->n_seg = n_seg; h->per_robot = true;
+    fill_params(h);
+    return LMH_OK;
+}
+
+extern "C" int lmh_plans_per_instance(const lmh_handle *h)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    return h->per_robot ? 1 : 0;
+}
+
+extern "C" int lmh_get_plan(lmh_handle *h, int inst, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    if (inst < 0 || inst >= h->B) return fail(LMH_ERR_BAD_ARG, "instance out of range");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t n = (size_t)h->n_samples;
+    const size_t ro = (size_t)h->P.ref_stride * (size_t)inst, so = (size_t)LMH_SEG_STRIDE * (size_t)h->P.seg_stride * (size_t)inst;   // 0 on a shared plan
+    if (zx) HIPCHK(hipMemcpy(zx, h->d_zx + ro, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (zy) HIPCHK(hipMemcpy(zy, h->d_zy + ro, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (phase) {
+        if (h->d_phase) HIPCHK(hipMemcpy(phase, h->d_phase + ro, n, hipMemcpyDeviceToHost));
+        else std::memset(phase, 0, n);
+    }
+    if (segs && h->n_seg > 0) HIPCHK(hipMemcpy(segs, h->d_segs + so, sizeof(double) * LMH_SEG_STRIDE * (size_t)h->n_seg, hipMemcpyDeviceToHost));
+    if (sos && h->n_seg > 0) HIPCHK(hipMemcpy(sos, h->d_sos + ro, sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
     return LMH_OK;
 }
 

@@ -32,6 +32,8 @@ struct LmhDevParams {
     int32_t precision;          // 0: fp64 throughout; 1: mixed (fp32 model terms, fp64 references + QP); 2: fp32
     int32_t bpp_max;            // block-pivoting rounds before the Lawson-Hanson pass (< 0: Lawson-Hanson only)
     int32_t plant;              // 1: compliant-contact plant driven by the torques (lmh_config.plant)
+    int32_t ref_stride;         // per-robot plans: samples per robot in zmpx / zmpy / phase / seg_of_sample (= n_samples); 0 = one shared plan
+    int32_t seg_stride;         // per-robot plans: segment records per robot in segs (= n_seg); 0 = shared
     // ---- scalars (reference literals, see include/lmh.h lmh_config)
     double dt;                  // control step (RK4 step of the fused rollout, Clock::step)
     double mpc_dt;              // MPC sample time: k = int(t / mpc_dt), sample period of the reference arrays (lmh_config.mpc_dt; = dt when that is 0)
@@ -54,3 +56,4 @@ struct LmhWalkSpec {
     double time_step, time_per_step, ds_time, step_height, settle_time, foot_y;
     int32_t n_samples, num_steps, first_support, pad;
 };
+struct LmhJumpSpec { double stance_time, flight_time; };   // lmh_gen_jump_batch: one robot's schedule

@@ -1733,17 +1733,21 @@ __device__ __forceinline__ void refs_prepare(double *L, LmhCParams &P, int inst,
     if (k != __builtin_amdgcn_readfirstlane((int)L[P_RK])) {       // wave-uniform: the preview index moved
         const double *mp = P.mpc + (size_t)P.mpc_stride_inst * inst;
         const int ns = P.n_samples;
+        // per-robot plans (lmh_gen_walk_batch / lmh_set_plans): the robot's slice of the sample arrays and of the segment table; both
+        // strides are 0 on a shared plan.  inst is wave-uniform, so the bases are scalar arithmetic, formed only when k moves
+        const size_t ro = (size_t)P.ref_stride * (size_t)inst;
+        const double *zx = P.zmpx + ro, *zy = P.zmpy + ro;
         double sx = 0.0, sy = 0.0;
         for (int i = lane; i <= N; i += 64) {                      // only N = 64 reaches a second round
             int kk = k + i;
             kk = (kk < 0) ? 0 : (kk >= ns ? ns - 1 : kk);
             const double K = (N <= MPC_LDS_MAXN) ? L[P_MPCK + i] : mp[i];
-            sx += K * P.zmpx[kk]; sy += K * P.zmpy[kk];
+            sx += K * zx[kk]; sy += K * zy[kk];
         }
         const int k0 = (k < 0) ? 0 : (k >= ns ? ns - 1 : k);
-        const int ph = P.phase ? (int)P.phase[k0] : 0;
+        const int ph = P.phase ? (int)(P.phase + ro)[k0] : 0;
         if (P.n_seg > 0) {                                         // walking extension: swing-polynomial segment of sample k, x axis in units of the step length
-            const double *sg = P.segs + (size_t)LMH_SEG_STRIDE * (int)P.seg_of_sample[k0];
+            const double *sg = P.segs + (size_t)LMH_SEG_STRIDE * ((size_t)P.seg_stride * (size_t)inst + (size_t)(P.seg_of_sample + ro)[k0]);
             const double xs = L[P_RXS];
             if (lane < 48) L[P_POLY + lane] = sg[1 + lane] * (((lane % 24) < 8) ? xs : 1.0);
             else if (lane < 54) L[P_POLY + lane] = 8.0;
@@ -4683,10 +4687,19 @@ __device__ __forceinline__ int gen_idx(double t, double time_step, int n)      /
     const int i = (r < 0.0) ? 0 : (r > (double)n ? n : (int)r);
     return i;
 }
-__global__ void __launch_bounds__(256) lmh_gen_walk_kernel(LmhWalkSpec W, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos)
+// One workgroup per plan.  specs == nullptr: the single shared plan of lmh_gen_walk from the by-value W (grid 1).  Otherwise
+// (lmh_gen_walk_batch, grid = n_instances) workgroup b generates robot b's plan from specs[b] into its slice of the five buffers:
+// samples at [b][n_samples], segment records at [b][seg_stride]; the records beyond the robot's own 2 num_steps + 2 are written as zeros.
+__global__ void __launch_bounds__(256) lmh_gen_walk_kernel(LmhWalkSpec W, const LmhWalkSpec *specs, int seg_stride, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos)
 {
     __shared__ int s_a[LMH_GEN_MAX_STEPS + 1], s_b[LMH_GEN_MAX_STEPS], s_c[LMH_GEN_MAX_STEPS], s_sup[LMH_GEN_MAX_STEPS];
     __shared__ double s_xr[LMH_GEN_MAX_STEPS + 1], s_xl[LMH_GEN_MAX_STEPS + 1], s_t[LMH_GEN_MAX_STEPS + 1];
+    if (specs) {
+        W = specs[blockIdx.x];
+        const size_t so = (size_t)W.n_samples * blockIdx.x;
+        zx += so; zy += so; phase += so; sos += so;
+        segs += (size_t)LMH_SEG_STRIDE * (size_t)seg_stride * blockIdx.x;
+    }
     const int n = W.n_samples, ns = W.num_steps, tid = threadIdx.x;
     if (tid == 0) {                                                // the step boundaries accumulate t += time_per_step in order: one thread
         double t = W.settle_time, xr = 0.0, xl = 0.0;
@@ -4731,6 +4744,7 @@ __global__ void __launch_bounds__(256) lmh_gen_walk_kernel(LmhWalkSpec W, double
         }
         segs[e] = v;
     }
+    for (int e = n_seg * LMH_SEG_STRIDE + tid; e < seg_stride * LMH_SEG_STRIDE; e += blockDim.x) segs[e] = 0.0;   // unused records of a robot with fewer steps
     // ---- samples: the assignments of the host generator in their order (the last one that covers k wins)
     for (int k = tid; k < n; k += blockDim.x) {
         double x = 0.0, y = 0.0;
@@ -4755,9 +4769,30 @@ __global__ void __launch_bounds__(256) lmh_gen_jump_kernel(int n, double time_st
         phase[k] = (uint8_t)((k >= a && k < b) ? LMH_PHASE_FLIGHT : LMH_PHASE_DOUBLE);
     }
 }
+// per-robot jumping schedules (lmh_gen_jump_batch): workgroup b writes robot b's slice [b][n]
+__global__ void __launch_bounds__(256) lmh_gen_jump_batch_kernel(int n, double time_step, const LmhJumpSpec *specs, double *zx, double *zy, uint8_t *phase)
+{
+    const LmhJumpSpec J = specs[blockIdx.x];
+    const size_t so = (size_t)n * blockIdx.x;
+    const int a = gen_idx(J.stance_time, time_step, n), b = gen_idx(J.stance_time + J.flight_time, time_step, n);
+    for (int k = threadIdx.x; k < n; k += blockDim.x) {
+        zx[so + k] = 0.0; zy[so + k] = 0.0;
+        phase[so + k] = (uint8_t)((k >= a && k < b) ? LMH_PHASE_FLIGHT : LMH_PHASE_DOUBLE);
+    }
+}
 extern "C" void lmh_launch_gen_walk(const LmhWalkSpec *W, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos, hipStream_t s)
 {
-    hipLaunchKernelGGL(lmh_gen_walk_kernel, dim3(1), dim3(256), 0, s, *W, zx, zy, phase, segs, sos);
+    hipLaunchKernelGGL(lmh_gen_walk_kernel, dim3(1), dim3(256), 0, s, *W, (const LmhWalkSpec *)nullptr, 2 * W->num_steps + 2, zx, zy, phase, segs, sos);
+}
+// d_specs: DEVICE [n_plans], each with n_samples set to the shared grid; seg_stride: segment records per robot
+extern "C" void lmh_launch_gen_walk_batch(const LmhWalkSpec *d_specs, int n_plans, int seg_stride, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos, hipStream_t s)
+{
+    LmhWalkSpec none = {};
+    hipLaunchKernelGGL(lmh_gen_walk_kernel, dim3(n_plans), dim3(256), 0, s, none, d_specs, seg_stride, zx, zy, phase, segs, sos);
+}
+extern "C" void lmh_launch_gen_jump_batch(int n, double time_step, const LmhJumpSpec *d_specs, int n_plans, double *zx, double *zy, uint8_t *phase, hipStream_t s)
+{
+    hipLaunchKernelGGL(lmh_gen_jump_batch_kernel, dim3(n_plans), dim3(256), 0, s, n, time_step, d_specs, zx, zy, phase);
 }
 extern "C" void lmh_launch_gen_jump(int n, double time_step, double stance_time, double flight_time, double *zx, double *zy, uint8_t *phase, hipStream_t s)
 {

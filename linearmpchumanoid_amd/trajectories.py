@@ -123,5 +123,62 @@ def jump_plan(simulation_time, time_step, stance_time=0.4, flight_time=0.15):
     return dict(zmp_x=zx, zmp_y=zy, phase=ph)
 
 
-__all__ = ["stance_zmp", "find_poly_coeff", "foot_coeff_trajectory", "walk_plan", "jump_plan",
+WALK_SPEC_DEFAULTS = dict(num_steps=4, time_per_step=0.5, ds_time=0.1, step_height=0.02, settle_time=0.3, first_support=PHASE_RIGHT,
+                          foot_y=0.05)                 # the defaults of walk_plan / BatchedController.gen_walk
+JUMP_SPEC_DEFAULTS = dict(stance_time=0.4, flight_time=0.15)
+
+
+def broadcast_specs(specs, defaults, B=None):
+    """specs: dict of arrays of one length B (scalars broadcast; missing fields take `defaults`) -> (dict of [B] arrays, B).
+    Integer fields (num_steps, first_support) come back as int64, the others as float64."""
+    unknown = set(specs) - set(defaults)
+    if unknown:
+        raise KeyError(f"unknown spec fields {sorted(unknown)}")
+    vals = {k: np.asarray(specs.get(k, d)) for k, d in defaults.items()}
+    sizes = {v.shape[0] for v in vals.values() if v.ndim == 1}
+    if any(v.ndim > 1 for v in vals.values()) or len(sizes) > 1:
+        raise ValueError("spec fields must be scalars or arrays of one length")
+    n = sizes.pop() if sizes else (1 if B is None else B)
+    if B is not None and n != B:
+        raise ValueError(f"specs describe {n} robots, expected {B}")
+    out = {}
+    for k, v in vals.items():
+        if isinstance(defaults[k], int):
+            if not np.all(v == np.round(v)):                        # num_steps = 2.5 is a mistake, not a request to truncate
+                raise ValueError(f"{k} must be whole numbers")
+            out[k] = np.broadcast_to(v.astype(np.int64), (n,)).copy()
+        else:
+            out[k] = np.broadcast_to(v.astype(np.float64), (n,)).copy()
+    return out, n
+
+
+def spec_of(specs, i):
+    """Robot i's keyword arguments of walk_plan / jump_plan from a broadcast spec dict."""
+    return {k: (int(v[i]) if v.dtype.kind == "i" else float(v[i])) for k, v in specs.items()}
+
+
+def walk_plans(simulation_time, time_step, specs, B=None):
+    """One walk_plan per robot (the host statement of lmh_gen_walk_batch; what BatchedController.set_plans takes): specs is a dict of
+    arrays of length B with walk_plan's keyword arguments (scalars broadcast, missing ones take walk_plan's defaults).
+    Returns dict(zmp_x [B,n], zmp_y [B,n], phase [B,n], segs [B,n_seg,52], seg_of_sample [B,n]) with n_seg = 2 max(num_steps) + 2: a
+    robot with fewer steps fills its first 2 num_steps + 2 records, the rest of its slice is zero and its seg_of_sample never points there."""
+    sp, n = broadcast_specs(specs, WALK_SPEC_DEFAULTS, B)
+    plans = [walk_plan(simulation_time, time_step, **spec_of(sp, i)) for i in range(n)]
+    n_seg = max(p["segs"].shape[0] for p in plans)
+    segs = np.zeros((n, n_seg, 52))
+    for i, p in enumerate(plans):
+        segs[i, :p["segs"].shape[0]] = p["segs"]
+    out = {k: np.stack([p[k] for p in plans]) for k in ("zmp_x", "zmp_y", "phase", "seg_of_sample")}
+    out["segs"] = segs
+    return out
+
+
+def jump_plans(simulation_time, time_step, specs, B=None):
+    """One jump_plan per robot (the host statement of lmh_gen_jump_batch): dict(zmp_x, zmp_y, phase), each [B,n]."""
+    sp, n = broadcast_specs(specs, JUMP_SPEC_DEFAULTS, B)
+    plans = [jump_plan(simulation_time, time_step, **spec_of(sp, i)) for i in range(n)]
+    return {k: np.stack([p[k] for p in plans]) for k in ("zmp_x", "zmp_y", "phase")}
+
+
+__all__ = ["stance_zmp", "find_poly_coeff", "foot_coeff_trajectory", "walk_plan", "jump_plan", "walk_plans", "jump_plans",
            "PHASE_DOUBLE", "PHASE_RIGHT", "PHASE_LEFT", "PHASE_FLIGHT"]
