@@ -147,7 +147,12 @@ void lmh_nominal_links(double *raw_links);
 
 /* replaces: ZMP::getZmpXRef/getZmpYRef arrays copied into Controller (src/zmpGeneration.cpp:39-60,
  * src/controller.cpp:14) + the support-phase extension.  HOST pointers, n_samples each;
- * phase may be NULL (all double support). */
+ * phase may be NULL (all double support).
+ * This and the seven other reference setters (lmh_set_refs_stance, lmh_set_segments, lmh_gen_walk, lmh_gen_jump, lmh_gen_walk_batch,
+ * lmh_gen_jump_batch, lmh_set_plans) follow one rule: the arguments are checked first, the new plan is built in buffers of its own and
+ * replaces the current one in a single step at the end.  A refused or failed call (bad argument, failed allocation, copy or generator
+ * launch) leaves the handle on its previous plan, samples and segments, shared or per robot.  lmh_set_model, lmh_set_zcom and
+ * lmh_set_xscale replace their tables the same way. */
 int lmh_set_refs(lmh_handle *h, const double *zmp_x, const double *zmp_y, const uint8_t *phase, int n_samples);
 /* replaces: ZMP::stanceZMP (src/zmpGeneration.cpp:39-60) with timeStep = mpc_dt; support_foot: 0 Right,1 Left,2 Double */
 int lmh_set_refs_stance(lmh_handle *h, double simulation_time, int support_foot);
@@ -158,7 +163,8 @@ int lmh_set_foot_coeffs(lmh_handle *h, const double *r_coeff, const int32_t *r_n
  * defines it; footCoeffTrajectory produces one polynomial set per step).  Piecewise foot references:
  * segment record = LMH_SEG_STRIDE doubles: t0 | rF[3][8] | lF[3][8] | pad(3), ascending powers, evaluated
  * at (t - t0); seg_of_sample[k] selects the segment from the preview index k.  HOST pointers;
- * n_seg = 0 restores the single polynomial set of lmh_set_foot_coeffs. */
+ * n_seg = 0 restores the single polynomial set of lmh_set_foot_coeffs.  n_samples must be the current sample count and every
+ * seg_of_sample entry < n_seg; a call refused for either reason (or for a NULL table) releases nothing: the segments in place stay. */
 int lmh_set_segments(lmh_handle *h, const double *segs, int n_seg, const uint16_t *seg_of_sample, int n_samples);
 /* Reference generators ON THE DEVICE (no host arrays are uploaded): the same plans as the host statement in
  * linearmpchumanoid_amd/trajectories.py.  lmh_gen_walk: ZMP(Task, numSteps, timePerStep, simulationTime) as the reference declares it
@@ -177,7 +183,8 @@ int lmh_gen_jump(lmh_handle *h, double simulation_time, double stance_time, doub
  * lmh_num_segments then returns); a robot with fewer steps uses its first 2 num_steps + 2 records, the rest of its slice is zero and no
  * seg_of_sample entry of that robot points there.  Device layout: zmp_x, zmp_y, phase, seg_of_sample [n][n_samples], segs
  * [n][n_seg][LMH_SEG_STRIDE]; a robot reads its slice when its preview index moves, nothing else in an evaluation changes.
- * n must be n_instances.  A failed call (bad argument, failed allocation) leaves the handle on its previous plan.
+ * n must be n_instances.  A failed call leaves the handle on its previous plan (see lmh_set_refs).  On a handle of one robot a
+ * per-robot plan IS the shared plan: lmh_plans_per_instance reports 0 there.
  * Every other reference setter (lmh_set_refs, lmh_set_refs_stance, lmh_set_segments, lmh_gen_walk, lmh_gen_jump) puts the handle back on
  * ONE shared plan (lmh_set_segments alone on a per-robot handle keeps robot 0's samples as the shared ones); lmh_set_xscale keeps its
  * meaning: robot i's x quantities are its own plan's times xscale[i]. */
@@ -229,7 +236,8 @@ int lmh_eval_debug(lmh_handle *h, double *d_state, double *d_out, int32_t *d_sta
  * lmh_rollout(.., a, ..) followed by lmh_rollout(.., b, ..) bit for bit (with [1], [2] merged as max / OR).
  * Host side of "asynchronous": the call only enqueues (one small parameter copy + the kernel) on `stream`, except that a handle keeps
  * EIGHT launches in flight -- the ninth lmh_rollout waits on the host until the first has completed -- and that the first eight calls
- * allocate their launch slot (hipMalloc): not capturable into a hipGraph before every slot has been used once.
+ * allocate their launch slot (hipMalloc): not capturable into a hipGraph before every slot has been used once.  A slot is acquired whole
+ * or not at all: if one of its allocations fails the call returns LMH_ERR_HIP without launching, and the next call tries again.
  * Incomplete launches are loud: the queue's waits are bounded, and if one runs out (a workgroup stalled for minutes: preemption, a
  * debugger) the robots that did not get all their ticks carry LMH_FLAG_UNFINISHED in d_status[.][2], and lmh_synchronize -- or the next
  * lmh_rollout that reuses the launch slot -- returns LMH_ERR_UNFINISHED once (the reference prints and aborts, src/controller.cpp:448-476).

@@ -28,19 +28,45 @@ static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
 #define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) return fail(LMH_ERR_HIP, std::string(#x) + ": " + hipGetErrorString(e_)); } while (0)
 
+// The one owner of device memory in this file: move-only, freed in the destructor.  A buffer that is in use is never refilled: its
+// replacement is built aside and move-assigned over it, so a call that fails half-way leaves the handle as it was.
+template <class T> struct DevBuf {
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf &operator=(DevBuf &&o) noexcept { DevBuf old(std::move(o)); std::swap(p_, old.p_); return *this; }   // safe on itself
+    ~DevBuf() { release(); }
+    hipError_t alloc(size_t n) { release(); return hipMalloc(&p_, sizeof(T) * n); }
+    hipError_t upload(const T *host, size_t n)
+    {
+        const hipError_t e = alloc(n);
+        return (e != hipSuccess) ? e : hipMemcpy(p_, host, sizeof(T) * n, hipMemcpyHostToDevice);
+    }
+    T *get() const { return p_; }
+private:
+    void release() { if (p_) (void)hipFree(p_); p_ = nullptr; }
+    T *p_ = nullptr;
+};
+
+// The reference plan of a handle: ZMP / phase samples and the piecewise foot references.  n_plans = 1: one plan shared by all robots;
+// n_plans = n_instances > 1: every buffer holds one slice per robot.  phase may be empty on a shared plan (all double support); segs and
+// seg_of_sample are empty while n_seg = 0 (the single polynomial set of lmh_set_foot_coeffs).
+struct RefPlan {
+    DevBuf<double> zx, zy, segs;
+    DevBuf<uint8_t> phase;
+    DevBuf<uint16_t> sos;
+    int n_samples = 0, n_seg = 0, n_plans = 1;
+    bool per_robot() const { return n_plans > 1; }
+};
+
 struct lmh_handle {
     lmh_config cfg;
     double mpc_dt = 0.0;              // resolved MPC sample time (cfg.mpc_dt, or cfg.dt when that is 0)
-    int B = 0, device = 0, N = 0, n_models = 0, n_gain = 0, n_samples = 0;
-    double *d_model = nullptr, *d_mpc = nullptr, *d_zx = nullptr, *d_zy = nullptr, *d_gcol = nullptr, *d_raw = nullptr;
-    double *d_segs = nullptr, *d_xscale = nullptr;
-    uint16_t *d_sos = nullptr;
-    int n_seg = 0;
-    bool per_robot = false;           // false: one shared plan; true: one plan per robot (the five reference buffers hold B slices)
-    uint8_t *d_phase = nullptr;
+    int B = 0, device = 0, N = 0, n_models = 0, n_gain = 0;
+    DevBuf<double> d_model, d_raw, d_mpc, d_gcol, d_xscale;
+    RefPlan plan;                     // replaced as a whole, by commit_plan only
     // staging for the host-buffer convenience calls
-    double *d_state = nullptr, *d_out = nullptr;
-    int32_t *d_status = nullptr;
+    DevBuf<double> d_state, d_out;
+    DevBuf<int32_t> d_status;
     std::vector<double> h_state, h_out, h_gain;
     std::vector<int32_t> h_status;
     LmhDevParams P;
@@ -49,12 +75,29 @@ struct lmh_handle {
     // completed (normally long ago): launches on different streams of one handle never share a block that is being rewritten.
     static constexpr int kSlots = 8;
     struct Slot {
-        LmhDevParams *d_P = nullptr;  // device copy read by the rollout kernel
-        int *d_ticket = nullptr;      // work-unit counters, ring queue of robots, ticks done per robot (4 + 2 B ints, all zero between launches: the kernel leaves them so)
-        hipEvent_t done = nullptr;    // recorded behind the last launch that used this slot
+        DevBuf<LmhDevParams> d_P;     // device copy read by the rollout kernel
+        DevBuf<int> d_ticket;         // work-unit counters, ring queue of robots, ticks done per robot (4 + 2 B ints, all zero between launches: the kernel leaves them so)
+        hipEvent_t done = nullptr;    // recorded behind the last launch that used this slot; non-null = the slot has all three
         LmhDevParams P_dev;           // what d_P currently holds
         bool valid = false, used = false;
         bool checked = true;          // the error word of the last launch on this slot (d_ticket[3]) has been read
+        ~Slot() { if (done) (void)hipEventDestroy(done); }
+        bool ready() const { return done != nullptr; }
+        // acquires the parameter block, the zeroed ticket words and the event, or nothing: a failure releases what it got so far and leaves
+        // the slot empty, and the next lmh_rollout that draws it tries again
+        hipError_t init(int n_instances, hipStream_t s)
+        {
+            const size_t words = 4 + 2 * (size_t)n_instances;          // counters | error word | ring of robots | ticks done per robot
+            DevBuf<LmhDevParams> p;
+            DevBuf<int> t;
+            hipEvent_t ev = nullptr;
+            hipError_t e = p.alloc(1);
+            if (e == hipSuccess) e = t.alloc(words);
+            if (e == hipSuccess) e = hipMemsetAsync(t.get(), 0, words * sizeof(int), s);   // stream-ordered in front of the first launch on the slot
+            if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);  // last, so that nothing is left to undo by hand
+            if (e == hipSuccess) { d_P = std::move(p); d_ticket = std::move(t); done = ev; }
+            return e;
+        }
     } slot[kSlots];
     unsigned next_slot = 0;
 };
@@ -233,13 +276,14 @@ static void fill_params(lmh_handle *h)
 {
     LmhDevParams &P = h->P;
     const lmh_config &c = h->cfg;
-    P.model = h->d_model; P.mpc = h->d_mpc; P.zmpx = h->d_zx; P.zmpy = h->d_zy; P.phase = h->d_phase; P.gcol = h->d_gcol;
-    P.segs = h->d_segs; P.seg_of_sample = h->d_sos; P.xscale = h->d_xscale; P.n_seg = h->n_seg;
-    P.ref_stride = h->per_robot ? h->n_samples : 0; P.seg_stride = h->per_robot ? h->n_seg : 0;
+    const RefPlan &r = h->plan;
+    P.model = h->d_model.get(); P.mpc = h->d_mpc.get(); P.gcol = h->d_gcol.get(); P.xscale = h->d_xscale.get();
+    P.zmpx = r.zx.get(); P.zmpy = r.zy.get(); P.phase = r.phase.get(); P.segs = r.segs.get(); P.seg_of_sample = r.sos.get();
+    P.n_seg = r.n_seg; P.ref_stride = r.per_robot() ? r.n_samples : 0; P.seg_stride = r.per_robot() ? r.n_seg : 0;
     P.model_stride = (h->n_models > 1) ? LMH_MODEL_STRIDE : 0;
     P.mpc_stride = 3 * (h->N + 1) + 4;
     P.mpc_stride_inst = (h->n_gain > 1) ? P.mpc_stride : 0;
-    P.n_samples = h->n_samples; P.horizon = h->N; P.n_instances = h->B;
+    P.n_samples = r.n_samples; P.horizon = h->N; P.n_instances = h->B;
     P.warm_start = c.warm_start; P.max_qp_iters = c.max_qp_iters; P.precision = c.precision;
     P.bpp_max = (c.bpp_rounds == 0) ? 10 : c.bpp_rounds;            // < 0: Lawson-Hanson from the empty set (diagnostic)
     P.plant = c.plant; P.contact_k = c.contact_k; P.contact_d = c.contact_d; P.contact_dt = c.contact_dt; P.contact_mu = c.contact_mu;
@@ -257,14 +301,13 @@ static void fill_params(lmh_handle *h)
 static int upload_gain(lmh_handle *h, const double *zcom, int n)
 {
     const int stride = 3 * (h->N + 1) + 4;
-    h->h_gain.assign((size_t)n * stride, 0.0);
+    std::vector<double> rows((size_t)n * stride, 0.0);
     for (int i = 0; i < n; i++)
-        if (build_gain_row(h->cfg, h->mpc_dt, zcom[i], h->N, h->h_gain.data() + (size_t)i * stride))
+        if (build_gain_row(h->cfg, h->mpc_dt, zcom[i], h->N, rows.data() + (size_t)i * stride))
             return fail(LMH_ERR_BAD_ARG, "MPC Hessian not positive definite");
-    if (h->d_mpc) { HIPCHK(hipFree(h->d_mpc)); h->d_mpc = nullptr; }
-    HIPCHK(hipMalloc(&h->d_mpc, sizeof(double) * h->h_gain.size()));
-    HIPCHK(hipMemcpy(h->d_mpc, h->h_gain.data(), sizeof(double) * h->h_gain.size(), hipMemcpyHostToDevice));
-    h->n_gain = n;
+    DevBuf<double> d;
+    HIPCHK(d.upload(rows.data(), rows.size()));
+    h->d_mpc = std::move(d); h->h_gain.swap(rows); h->n_gain = n;
     fill_params(h);
     return LMH_OK;
 }
@@ -299,13 +342,12 @@ static int create_body(lmh_handle *h, const lmh_config *cfg, int n_instances)
     double g[16 * 6 + 36 + 96 + 3 * 336];
     build_gcol(cfg->mu, g);
     build_lcoef(g + 228);
-    HIPCHK(hipMalloc(&h->d_gcol, sizeof(g)));
-    HIPCHK(hipMemcpy(h->d_gcol, g, sizeof(g), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&h->d_state, sizeof(double) * LMH_STATE_STRIDE * (size_t)n_instances));
-    HIPCHK(hipMalloc(&h->d_out, sizeof(double) * LMH_OUT_STRIDE * (size_t)n_instances));
-    HIPCHK(hipMalloc(&h->d_status, sizeof(int32_t) * LMH_STATUS_STRIDE * (size_t)n_instances));
-    HIPCHK(hipMemset(h->d_state, 0, sizeof(double) * LMH_STATE_STRIDE * (size_t)n_instances));
-    HIPCHK(hipMemset(h->d_status, 0, sizeof(int32_t) * LMH_STATUS_STRIDE * (size_t)n_instances));
+    HIPCHK(h->d_gcol.upload(g, sizeof(g) / sizeof(double)));
+    HIPCHK(h->d_state.alloc(LMH_STATE_STRIDE * (size_t)n_instances));
+    HIPCHK(h->d_out.alloc(LMH_OUT_STRIDE * (size_t)n_instances));
+    HIPCHK(h->d_status.alloc(LMH_STATUS_STRIDE * (size_t)n_instances));
+    HIPCHK(hipMemset(h->d_state.get(), 0, sizeof(double) * LMH_STATE_STRIDE * (size_t)n_instances));
+    HIPCHK(hipMemset(h->d_status.get(), 0, sizeof(int32_t) * LMH_STATUS_STRIDE * (size_t)n_instances));
     h->h_state.assign((size_t)LMH_STATE_STRIDE * n_instances, 0.0);
     h->h_out.assign((size_t)LMH_OUT_STRIDE * n_instances, 0.0);
     h->h_status.assign((size_t)LMH_STATUS_STRIDE * n_instances, 0);
@@ -345,15 +387,8 @@ extern "C" int lmh_destroy(lmh_handle *h)
 {
     if (!h) return LMH_OK;
     (void)hipSetDevice(h->device);
-    void *bufs[] = {h->d_model, h->d_mpc, h->d_zx, h->d_zy, h->d_gcol, h->d_raw, h->d_phase, h->d_state, h->d_out, h->d_status,
-                    h->d_segs, h->d_xscale, h->d_sos};
-    for (void *b : bufs) if (b) (void)hipFree(b);
-    for (auto &sl : h->slot) {
-        if (sl.done) { if (sl.used) (void)hipEventSynchronize(sl.done); (void)hipEventDestroy(sl.done); }
-        if (sl.d_P) (void)hipFree(sl.d_P);
-        if (sl.d_ticket) (void)hipFree(sl.d_ticket);
-    }
-    delete h;
+    for (auto &sl : h->slot) if (sl.used) (void)hipEventSynchronize(sl.done);   // no launch still reads a slot
+    delete h;                                                       // the buffers and events go with their owners
     return LMH_OK;
 }
 
@@ -372,16 +407,13 @@ extern "C" int lmh_set_model(lmh_handle *h, const double *raw, int n_models)
             for (int e = 0; e < LMH_LINK_STRIDE; e++)
                 if (raw[((size_t)m * 28 + f) * LMH_LINK_STRIDE + e] != 0.0) return fail(LMH_ERR_BAD_ARG, "lmh_set_model: frames 7, 14, 27 are massless virtual frames: their records must be zero");
     HIPCHK(hipSetDevice(h->device));
-    if (h->d_raw) { HIPCHK(hipFree(h->d_raw)); h->d_raw = nullptr; }
-    if (h->d_model) { HIPCHK(hipFree(h->d_model)); h->d_model = nullptr; }
-    const size_t rawb = sizeof(double) * 28 * LMH_LINK_STRIDE * (size_t)n_models;
-    HIPCHK(hipMalloc(&h->d_raw, rawb));
-    HIPCHK(hipMalloc(&h->d_model, sizeof(double) * LMH_MODEL_STRIDE * (size_t)n_models));
-    HIPCHK(hipMemcpy(h->d_raw, raw, rawb, hipMemcpyHostToDevice));
-    lmh_launch_model(h->d_raw, h->d_model, n_models, h->d_gcol + 228, nullptr);
+    DevBuf<double> d_raw, d_model;
+    HIPCHK(d_raw.upload(raw, 28 * LMH_LINK_STRIDE * (size_t)n_models));
+    HIPCHK(d_model.alloc(LMH_MODEL_STRIDE * (size_t)n_models));
+    lmh_launch_model(d_raw.get(), d_model.get(), n_models, h->d_gcol.get() + 228, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    h->n_models = n_models;
+    h->d_raw = std::move(d_raw); h->d_model = std::move(d_model); h->n_models = n_models;
     fill_params(h);
     return LMH_OK;
 }
@@ -391,37 +423,66 @@ extern "C" int lmh_get_mass(lmh_handle *h, double *mass)
     if (!h || !mass) return fail(LMH_ERR_BAD_ARG, "bad argument");
     HIPCHK(hipSetDevice(h->device));
     for (int i = 0; i < h->n_models; i++)
-        HIPCHK(hipMemcpy(mass + i, h->d_model + (size_t)i * LMH_MODEL_STRIDE + 392, sizeof(double), hipMemcpyDeviceToHost));
+        HIPCHK(hipMemcpy(mass + i, h->d_model.get() + (size_t)i * LMH_MODEL_STRIDE + 392, sizeof(double), hipMemcpyDeviceToHost));
     return LMH_OK;
+}
+
+// ---------------------------------------------------------------------------- the reference plan
+// Every setter validates its arguments on the host, builds a fresh RefPlan aside (allocation, upload or generator launch, sync) and
+// commits it here: the one place where a handle changes plan.  Whatever fails before that leaves the handle on its previous plan.
+static int commit_plan(lmh_handle *h, RefPlan p)
+{
+    std::swap(h->plan, p);
+    fill_params(h);
+    return LMH_OK;                                                   // the previous plan dies with p, after P has left it
+}
+
+static std::string robot_msg(int i, const char *msg) { return "robot " + std::to_string(i) + ": " + msg; }
+
+// seg_of_sample < n_seg in every slice of n_samples entries: the first slice at fault, or -1
+static int sos_out_of_range(const uint16_t *sos, int n_seg, int n_samples, int n_plans)
+{
+    for (int i = 0; i < n_plans; i++)
+        for (int k = 0; k < n_samples; k++)
+            if (sos[(size_t)i * n_samples + k] >= n_seg) return i;
+    return -1;
+}
+
+// lmh_set_refs / lmh_set_refs_stance (one slice) and lmh_set_plans (n_instances slices); the arguments have been checked
+static int upload_plan(lmh_handle *h, const double *zx, const double *zy, const uint8_t *phase, int n_samples,
+                       const double *segs, int n_seg, const uint16_t *sos, int n_plans)
+{
+    HIPCHK(hipSetDevice(h->device));
+    RefPlan p;
+    const size_t ns = (size_t)n_samples * (size_t)n_plans;
+    HIPCHK(p.zx.upload(zx, ns));
+    HIPCHK(p.zy.upload(zy, ns));
+    if (phase) HIPCHK(p.phase.upload(phase, ns));
+    else if (n_plans > 1) {                                          // per-robot plans always carry a phase slice per robot
+        HIPCHK(p.phase.alloc(ns));
+        HIPCHK(hipMemset(p.phase.get(), 0, ns));
+    }
+    if (n_seg > 0) {
+        HIPCHK(p.segs.upload(segs, LMH_SEG_STRIDE * (size_t)n_seg * (size_t)n_plans));
+        HIPCHK(p.sos.upload(sos, ns));
+    }
+    p.n_samples = n_samples; p.n_seg = n_seg; p.n_plans = n_plans;
+    return commit_plan(h, std::move(p));
 }
 
 extern "C" int lmh_set_refs(lmh_handle *h, const double *zx, const double *zy, const uint8_t *phase, int n)
 {
     if (!h || !zx || !zy || n < 1) return fail(LMH_ERR_BAD_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    if (h->d_zx) { HIPCHK(hipFree(h->d_zx)); h->d_zx = nullptr; }
-    if (h->d_zy) { HIPCHK(hipFree(h->d_zy)); h->d_zy = nullptr; }
-    if (h->d_phase) { HIPCHK(hipFree(h->d_phase)); h->d_phase = nullptr; }
-    HIPCHK(hipMalloc(&h->d_zx, sizeof(double) * (size_t)n));
-    HIPCHK(hipMalloc(&h->d_zy, sizeof(double) * (size_t)n));
-    HIPCHK(hipMemcpy(h->d_zx, zx, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_zy, zy, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    if (phase) {
-        HIPCHK(hipMalloc(&h->d_phase, (size_t)n));
-        HIPCHK(hipMemcpy(h->d_phase, phase, (size_t)n, hipMemcpyHostToDevice));
-    }
-    h->n_samples = n; h->per_robot = false;
-    if (h->d_sos) { (void)hipFree(h->d_sos); h->d_sos = nullptr; }
-    if (h->d_segs) { (void)hipFree(h->d_segs); h->d_segs = nullptr; }
-    h->n_seg = 0;                                                    // segments are tied to the sample grid
-    fill_params(h);
-    return LMH_OK;
+    return upload_plan(h, zx, zy, phase, n, nullptr, 0, nullptr, 1);  // no segments: they are tied to the sample grid
 }
+
+// (int)((simulation_time + 0.5) / mpc_dt): zmpGeneration.cpp:41 with timeStep_ = the MPC sample time
+static int sample_count(const lmh_handle *h, double simulation_time) { return (int)((simulation_time + 0.5) / h->mpc_dt); }
 
 extern "C" int lmh_set_refs_stance(lmh_handle *h, double simulation_time, int support_foot)
 {
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
-    const int samples = (int)((simulation_time + 0.5) / h->mpc_dt);  // zmpGeneration.cpp:41 (timeStep_ = the MPC sample time)
+    const int samples = sample_count(h, simulation_time);
     if (samples < 1) return fail(LMH_ERR_BAD_ARG, "no samples");
     std::vector<double> zx((size_t)samples, 0.0), zy((size_t)samples, (support_foot == 0) ? -0.05 : (support_foot == 1) ? 0.05 : 0.0);
     return lmh_set_refs(h, zx.data(), zy.data(), nullptr, samples);
@@ -442,35 +503,31 @@ extern "C" int lmh_set_foot_coeffs(lmh_handle *h, const double *r, const int32_t
 extern "C" int lmh_set_segments(lmh_handle *h, const double *segs, int n_seg, const uint16_t *sos, int n_samples)
 {
     if (!h || n_seg < 0) return fail(LMH_ERR_BAD_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    if (h->d_segs) { HIPCHK(hipFree(h->d_segs)); h->d_segs = nullptr; }
-    if (h->d_sos) { HIPCHK(hipFree(h->d_sos)); h->d_sos = nullptr; }
-    h->n_seg = 0; h->per_robot = false;                              // back on one shared plan (of a per-robot set, robot 0's samples stay)
-    fill_params(h);                                                  // P never points at the freed table
     if (n_seg > 0) {
         if (!segs || !sos) return fail(LMH_ERR_BAD_ARG, "null segment table");
-        if (n_samples != h->n_samples) return fail(LMH_ERR_BAD_ARG, "seg_of_sample must cover the ZMP reference samples (call lmh_set_refs first)");
-        for (int i = 0; i < n_samples; i++) if (sos[i] >= n_seg) return fail(LMH_ERR_BAD_ARG, "seg_of_sample entry out of range");
-        HIPCHK(hipMalloc(&h->d_segs, sizeof(double) * LMH_SEG_STRIDE * (size_t)n_seg));
-        HIPCHK(hipMalloc(&h->d_sos, sizeof(uint16_t) * (size_t)n_samples));
-        HIPCHK(hipMemcpy(h->d_segs, segs, sizeof(double) * LMH_SEG_STRIDE * (size_t)n_seg, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_sos, sos, sizeof(uint16_t) * (size_t)n_samples, hipMemcpyHostToDevice));
-        h->n_seg = n_seg;
+        if (n_samples != h->plan.n_samples) return fail(LMH_ERR_BAD_ARG, "seg_of_sample must cover the ZMP reference samples (call lmh_set_refs first)");
+        if (sos_out_of_range(sos, n_seg, n_samples, 1) >= 0) return fail(LMH_ERR_BAD_ARG, "seg_of_sample entry out of range");
     }
-    fill_params(h);
-    return LMH_OK;
+    HIPCHK(hipSetDevice(h->device));
+    RefPlan p;                                                       // one shared plan: the new table ...
+    if (n_seg > 0) {
+        HIPCHK(p.segs.upload(segs, LMH_SEG_STRIDE * (size_t)n_seg));
+        HIPCHK(p.sos.upload(sos, (size_t)n_samples));
+    }
+    RefPlan &cur = h->plan;                                          // ... on the current samples (of a per-robot set, robot 0's slice); nothing below fails
+    p.zx = std::move(cur.zx); p.zy = std::move(cur.zy); p.phase = std::move(cur.phase);
+    p.n_samples = cur.n_samples; p.n_seg = n_seg;
+    return commit_plan(h, std::move(p));
 }
 
 extern "C" int lmh_set_xscale(lmh_handle *h, const double *xscale, int n)
 {
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    if (xscale && n != h->B) return fail(LMH_ERR_BAD_ARG, "n must be n_instances");
     HIPCHK(hipSetDevice(h->device));
-    if (h->d_xscale) { HIPCHK(hipFree(h->d_xscale)); h->d_xscale = nullptr; }
-    if (xscale) {
-        if (n != h->B) return fail(LMH_ERR_BAD_ARG, "n must be n_instances");
-        HIPCHK(hipMalloc(&h->d_xscale, sizeof(double) * (size_t)n));
-        HIPCHK(hipMemcpy(h->d_xscale, xscale, sizeof(double) * (size_t)n, hipMemcpyHostToDevice));
-    }
+    DevBuf<double> d;
+    if (xscale) HIPCHK(d.upload(xscale, (size_t)n));
+    h->d_xscale = std::move(d);
     fill_params(h);
     return LMH_OK;
 }
@@ -492,41 +549,40 @@ extern "C" int lmh_get_mpc_gain(lmh_handle *h, double *K)
 static int ready(lmh_handle *h)
 {
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
-    if (!h->d_model || !h->d_mpc || !h->d_zx || h->n_samples < 1) return fail(LMH_ERR_NOT_READY, "model / references not set");
+    if (!h->d_model.get() || !h->d_mpc.get() || !h->plan.zx.get() || h->plan.n_samples < 1) return fail(LMH_ERR_NOT_READY, "model / references not set");
     return LMH_OK;
 }
 
-extern "C" int lmh_eval(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, void *stream)
+static int eval_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_debug, bool debug, void *stream)
 {
     int rc = ready(h); if (rc) return rc;
-    if (!d_state || !d_out || !d_status) return fail(LMH_ERR_BAD_ARG, "null device pointer");
-    HIPCHK(hipSetDevice(h->device));
-    lmh_launch_eval(&h->P, d_state, d_out, d_status, nullptr, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return LMH_OK;
-}
-
-extern "C" int lmh_eval_debug(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_debug, void *stream)
-{
-    int rc = ready(h); if (rc) return rc;
-    if (!d_state || !d_out || !d_status || !d_debug) return fail(LMH_ERR_BAD_ARG, "null device pointer");
+    if (!d_state || !d_out || !d_status || (debug && !d_debug)) return fail(LMH_ERR_BAD_ARG, "null device pointer");
     HIPCHK(hipSetDevice(h->device));
     lmh_launch_eval(&h->P, d_state, d_out, d_status, d_debug, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     return LMH_OK;
 }
 
+extern "C" int lmh_eval(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, void *stream)
+{
+    return eval_body(h, d_state, d_out, d_status, nullptr, false, stream);
+}
+
+extern "C" int lmh_eval_debug(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_debug, void *stream)
+{
+    return eval_body(h, d_state, d_out, d_status, d_debug, true, stream);
+}
+
 // The error word of a COMPLETED launch on this slot (d_ticket[3], lmh_rollout_kernel): read once, cleared, reported.  The kernel has already
 // flagged the robots concerned and put the slot's ring / progress words back to zero.
-static int slot_take_error(lmh_handle *h, lmh_handle::Slot &sl)
+static int slot_take_error(lmh_handle::Slot &sl)
 {
     if (sl.checked) return LMH_OK;
     int err = 0;
-    HIPCHK(hipMemcpy(&err, sl.d_ticket + 3, sizeof(int), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&err, sl.d_ticket.get() + 3, sizeof(int), hipMemcpyDeviceToHost));
     sl.checked = true;
     if (err == 0) return LMH_OK;
-    HIPCHK(hipMemset(sl.d_ticket + 3, 0, sizeof(int)));
-    (void)h;
+    HIPCHK(hipMemset(sl.d_ticket.get() + 3, 0, sizeof(int)));
     return fail(LMH_ERR_UNFINISHED, "lmh_rollout: a wait of the kernel's work queue ran out (error word " + std::to_string(err) +
                 "); the robots that did not get all their ticks carry LMH_FLAG_UNFINISHED in their status records");
 }
@@ -538,25 +594,19 @@ extern "C" int lmh_rollout(lmh_handle *h, double *d_state, double *d_out, int32_
     if (n_ticks == 0) return LMH_OK;
     HIPCHK(hipSetDevice(h->device));
     lmh_handle::Slot &sl = h->slot[h->next_slot % lmh_handle::kSlots];
-    if (!sl.d_P) {
-        HIPCHK(hipMalloc(&sl.d_P, sizeof(LmhDevParams)));
-        const size_t tbytes = (4 + 2 * (size_t)h->P.n_instances) * sizeof(int);   // counters | error word | ring of robots | ticks done per robot
-        HIPCHK(hipMalloc(&sl.d_ticket, tbytes));
-        HIPCHK(hipMemsetAsync(sl.d_ticket, 0, tbytes, (hipStream_t)stream));     // stream-ordered in front of the first launch on the slot
-        HIPCHK(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
-    }
+    if (!sl.ready()) HIPCHK(sl.init(h->B, (hipStream_t)stream));
     if (sl.used) {
         HIPCHK(hipEventSynchronize(sl.done));                       // the launch that last used this slot (kSlots launches ago) has left it
-        rc = slot_take_error(h, sl);                                // ... and if it was incomplete, this call reports it instead of launching
+        rc = slot_take_error(sl);                                // ... and if it was incomplete, this call reports it instead of launching
         if (rc) return rc;
     }
     h->next_slot++;
     if (!sl.valid || std::memcmp(&sl.P_dev, &h->P, sizeof(LmhDevParams)) != 0) {   // set-up calls changed the block since this slot was filled
         std::memcpy(&sl.P_dev, &h->P, sizeof(LmhDevParams));
-        HIPCHK(hipMemcpyAsync(sl.d_P, &sl.P_dev, sizeof(LmhDevParams), hipMemcpyHostToDevice, (hipStream_t)stream));   // stream-ordered in front of the launch; the slot is idle
+        HIPCHK(hipMemcpyAsync(sl.d_P.get(), &sl.P_dev, sizeof(LmhDevParams), hipMemcpyHostToDevice, (hipStream_t)stream));   // stream-ordered in front of the launch; the slot is idle
         sl.valid = true;
     }
-    lmh_launch_rollout(&h->P, sl.d_P, sl.d_ticket, d_state, d_out, d_status, d_log, n_ticks, (hipStream_t)stream);
+    lmh_launch_rollout(&h->P, sl.d_P.get(), sl.d_ticket.get(), d_state, d_out, d_status, d_log, n_ticks, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(sl.done, (hipStream_t)stream));
     sl.used = true;
@@ -590,12 +640,12 @@ extern "C" int lmh_eval_host(lmh_handle *h, const double *q, const double *dq, d
         std::memcpy(s + 30, dq + 30 * (size_t)i, 30 * sizeof(double));
         s[90] = t;
     }
-    HIPCHK(hipMemcpy(h->d_state, h->h_state.data(), sizeof(double) * h->h_state.size(), hipMemcpyHostToDevice));
-    lmh_launch_eval(&h->P, h->d_state, h->d_out, h->d_status, nullptr, nullptr);
+    HIPCHK(hipMemcpy(h->d_state.get(), h->h_state.data(), sizeof(double) * h->h_state.size(), hipMemcpyHostToDevice));
+    lmh_launch_eval(&h->P, h->d_state.get(), h->d_out.get(), h->d_status.get(), nullptr, nullptr);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpy(h->h_state.data(), h->d_state, sizeof(double) * h->h_state.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h->h_out.data(), h->d_out, sizeof(double) * h->h_out.size(), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(h->h_status.data(), h->d_status, sizeof(int32_t) * h->h_status.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h->h_state.data(), h->d_state.get(), sizeof(double) * h->h_state.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h->h_out.data(), h->d_out.get(), sizeof(double) * h->h_out.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(h->h_status.data(), h->d_status.get(), sizeof(int32_t) * h->h_status.size(), hipMemcpyDeviceToHost));
     for (int i = 0; i < h->B; i++) {
         const double *o = h->h_out.data() + (size_t)LMH_OUT_STRIDE * i;
         if (tau) std::memcpy(tau + 24 * (size_t)i, o, 24 * sizeof(double));
@@ -621,10 +671,10 @@ extern "C" int lmh_robot_com_host(lmh_handle *h, const double *q, double *com)
     int rc = ready(h); if (rc) return rc;
     if (!q || !com) return fail(LMH_ERR_BAD_ARG, "bad argument");
     HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipMemcpy(h->d_state, q, sizeof(double) * 30 * (size_t)h->B, hipMemcpyHostToDevice));
-    rc = lmh_robot_com(h, h->d_state, h->d_out, nullptr);
+    HIPCHK(hipMemcpy(h->d_state.get(), q, sizeof(double) * 30 * (size_t)h->B, hipMemcpyHostToDevice));
+    rc = lmh_robot_com(h, h->d_state.get(), h->d_out.get(), nullptr);
     if (rc) return rc;
-    HIPCHK(hipMemcpy(com, h->d_out, sizeof(double) * 3 * (size_t)h->B, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(com, h->d_out.get(), sizeof(double) * 3 * (size_t)h->B, hipMemcpyDeviceToHost));
     return LMH_OK;
 }
 
@@ -640,17 +690,17 @@ extern "C" int lmh_ik_host(lmh_handle *h, double *q, const double *com_target, c
     int rc = ready(h); if (rc) return rc;
     if (!q || !com_target || !rf6 || !lf6) return fail(LMH_ERR_BAD_ARG, "bad argument");
     HIPCHK(hipSetDevice(h->device));
-    double *d_q = h->d_state;                                        // staging: reuse the state buffer
-    double *d_com = h->d_out;
+    double *d_q = h->d_state.get();                                       // staging: reuse the state buffer
+    double *d_com = h->d_out.get();
     HIPCHK(hipMemcpy(d_q, q, sizeof(double) * 30 * (size_t)h->B, hipMemcpyHostToDevice));
-    rc = lmh_ik(h, d_q, com_target, rf6, lf6, h->d_status, nullptr);
+    rc = lmh_ik(h, d_q, com_target, rf6, lf6, h->d_status.get(), nullptr);
     if (rc) return rc;
     rc = lmh_robot_com(h, d_q, d_com, nullptr);
     if (rc) return rc;
     HIPCHK(hipMemcpy(q, d_q, sizeof(double) * 30 * (size_t)h->B, hipMemcpyDeviceToHost));
     if (com) HIPCHK(hipMemcpy(com, d_com, sizeof(double) * 3 * (size_t)h->B, hipMemcpyDeviceToHost));
-    if (iters) HIPCHK(hipMemcpy(iters, h->d_status, sizeof(int32_t) * (size_t)h->B, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemset(h->d_status, 0, sizeof(int32_t) * LMH_STATUS_STRIDE * (size_t)h->B));
+    if (iters) HIPCHK(hipMemcpy(iters, h->d_status.get(), sizeof(int32_t) * (size_t)h->B, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemset(h->d_status.get(), 0, sizeof(int32_t) * LMH_STATUS_STRIDE * (size_t)h->B));
     return LMH_OK;
 }
 
@@ -668,7 +718,7 @@ extern "C" int lmh_synchronize(lmh_handle *h, void *stream)
     HIPCHK(hipStreamSynchronize((hipStream_t)stream));
     int rc = LMH_OK;
     for (auto &sl : h->slot)                                         // launches that have completed (on this stream or any other) and were not looked at yet
-        if (sl.used && !sl.checked && hipEventQuery(sl.done) == hipSuccess) { const int e = slot_take_error(h, sl); if (e) rc = e; }
+        if (sl.used && !sl.checked && hipEventQuery(sl.done) == hipSuccess) { const int e = slot_take_error(sl); if (e) rc = e; }
     return rc;
 }
 
@@ -764,99 +814,64 @@ extern "C" int lmh_read_log(const char *path, double *log, uint64_t capacity, ui
 }
 
 // ---------------------------------------------------------------------------- reference generators on the device
-static int alloc_refs(lmh_handle *h, int n, int n_seg, int n_plans = 1)
+// fresh buffers for a generator kernel to fill: every plan has a phase slice, segments only where n_seg > 0
+static int alloc_plan(RefPlan &p, int n_samples, int n_seg, int n_plans)
 {
-    // allocate the new set first, swap it in, then free the old one: a failed hipMalloc leaves the handle on its previous references
-    // (still consistent with P), never on freed pointers
-    double *zx = nullptr, *zy = nullptr, *segs = nullptr;
-    uint8_t *ph = nullptr;
-    uint16_t *sos = nullptr;
-    const size_t np = (size_t)n_plans;                              // slices per buffer: 1 (shared plan) or n_instances
-    hipError_t e = hipMalloc(&zx, sizeof(double) * (size_t)n * np);
-    if (e == hipSuccess) e = hipMalloc(&zy, sizeof(double) * (size_t)n * np);
-    if (e == hipSuccess) e = hipMalloc(&ph, (size_t)n * np);
-    if (e == hipSuccess && n_seg > 0) e = hipMalloc(&segs, sizeof(double) * LMH_SEG_STRIDE * (size_t)n_seg * np);
-    if (e == hipSuccess && n_seg > 0) e = hipMalloc(&sos, sizeof(uint16_t) * (size_t)n * np);
-    if (e != hipSuccess) {
-        void *fresh[] = {zx, zy, ph, segs, sos};
-        for (void *b : fresh) if (b) (void)hipFree(b);
-        return fail(LMH_ERR_HIP, std::string("reference buffers: ") + hipGetErrorString(e));
+    const size_t ns = (size_t)n_samples * (size_t)n_plans;
+    HIPCHK(p.zx.alloc(ns));
+    HIPCHK(p.zy.alloc(ns));
+    HIPCHK(p.phase.alloc(ns));
+    if (n_seg > 0) {
+        HIPCHK(p.segs.alloc(LMH_SEG_STRIDE * (size_t)n_seg * (size_t)n_plans));
+        HIPCHK(p.sos.alloc(ns));
     }
-    void *old[] = {h->d_zx, h->d_zy, h->d_phase, h->d_segs, h->d_sos};
-    h->d_zx = zx; h->d_zy = zy; h->d_phase = ph; h->d_segs = segs; h->d_sos = sos;
-    h->n_seg = 0; h->n_samples = 0; h->per_robot = false;           // the callers set all three once the generator kernel has filled the buffers
-    fill_params(h);                                                 // P never points at the freed set
-    for (void *b : old) if (b) (void)hipFree(b);
+    p.n_samples = n_samples; p.n_seg = n_seg; p.n_plans = n_plans;
     return LMH_OK;
 }
 
 // the argument rules of lmh_gen_walk (one spec of lmh_gen_walk_batch): nullptr = fine
-static const char *walk_spec_error(double simulation_time, int num_steps, double time_per_step, double ds_time, double settle_time, int first_support)
+static const char *walk_spec_error(double simulation_time, const lmh_walk_spec &s)
 {
-    if (num_steps < 1 || num_steps > LMH_GEN_MAX_STEPS) return "num_steps must be in [1, 1022]";
-    if (!(time_per_step > 0.0) || !(ds_time >= 0.0) || !(ds_time < time_per_step) || !(settle_time >= 0.0) || !(simulation_time > 0.0))
+    if (s.num_steps < 1 || s.num_steps > LMH_GEN_MAX_STEPS) return "num_steps must be in [1, 1022]";
+    if (!(s.time_per_step > 0.0) || !(s.ds_time >= 0.0) || !(s.ds_time < s.time_per_step) || !(s.settle_time >= 0.0) || !(simulation_time > 0.0))
         return "need 0 <= ds_time < time_per_step, settle_time >= 0, simulation_time > 0";
-    if (first_support != LMH_PHASE_RIGHT && first_support != LMH_PHASE_LEFT) return "first_support must be LMH_PHASE_RIGHT or LMH_PHASE_LEFT";
+    if (s.first_support != LMH_PHASE_RIGHT && s.first_support != LMH_PHASE_LEFT) return "first_support must be LMH_PHASE_RIGHT or LMH_PHASE_LEFT";
     return nullptr;
+}
+
+// lmh_gen_walk (batch = false: specs[0], today's single-plan launch) and lmh_gen_walk_batch (one spec and one workgroup per robot)
+static int gen_walk(lmh_handle *h, double simulation_time, const lmh_walk_spec *specs, int n, bool batch)
+{
+    const int ns = sample_count(h, simulation_time);                // one sample grid for all robots
+    int max_steps = 0;
+    std::vector<LmhWalkSpec> W((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const lmh_walk_spec &s = specs[i];
+        if (const char *msg = walk_spec_error(simulation_time, s)) return fail(LMH_ERR_BAD_ARG, batch ? robot_msg(i, msg) : msg);
+        W[(size_t)i] = LmhWalkSpec{h->mpc_dt, s.time_per_step, s.ds_time, s.step_height, s.settle_time, s.foot_y, ns, s.num_steps, s.first_support, 0};
+        if (s.num_steps > max_steps) max_steps = s.num_steps;
+    }
+    if (ns < 1) return fail(LMH_ERR_BAD_ARG, "no samples");
+    HIPCHK(hipSetDevice(h->device));
+    RefPlan p;
+    const int rc = alloc_plan(p, ns, 2 * max_steps + 2, n);         // one segment stride for all robots
+    if (rc != LMH_OK) return rc;
+    DevBuf<LmhWalkSpec> d_specs;
+    if (batch) {
+        HIPCHK(d_specs.upload(W.data(), W.size()));
+        lmh_launch_gen_walk_batch(d_specs.get(), n, p.n_seg, p.zx.get(), p.zy.get(), p.phase.get(), p.segs.get(), p.sos.get(), nullptr);
+    } else lmh_launch_gen_walk(&W[0], p.zx.get(), p.zy.get(), p.phase.get(), p.segs.get(), p.sos.get(), nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    return commit_plan(h, std::move(p));
 }
 
 extern "C" int lmh_gen_walk(lmh_handle *h, double simulation_time, int num_steps, double time_per_step, double ds_time, double step_height,
                             double settle_time, int first_support, double foot_y)
 {
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
-    if (const char *msg = walk_spec_error(simulation_time, num_steps, time_per_step, ds_time, settle_time, first_support)) return fail(LMH_ERR_BAD_ARG, msg);
-    const int n = (int)((simulation_time + 0.5) / h->mpc_dt);       // zmpGeneration.cpp:41
-    if (n < 1) return fail(LMH_ERR_BAD_ARG, "no samples");
-    HIPCHK(hipSetDevice(h->device));
-    const int n_seg = 2 * num_steps + 2;
-    int rc = alloc_refs(h, n, n_seg);
-    if (rc != LMH_OK) return rc;
-    LmhWalkSpec W;
-    W.time_step = h->mpc_dt; W.time_per_step = time_per_step; W.ds_time = ds_time; W.step_height = step_height; W.settle_time = settle_time; W.foot_y = foot_y;
-    W.n_samples = n; W.num_steps = num_steps; W.first_support = first_support; W.pad = 0;
-    lmh_launch_gen_walk(&W, h->d_zx, h->d_zy, h->d_phase, h->d_segs, h->d_sos, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    h->n_samples = n; h->n_seg = n_seg;
-    fill_params(h);
-    return LMH_OK;
-}
-
-static const char *jump_spec_error(double simulation_time, double stance_time, double flight_time)
-{
-    if (!(stance_time >= 0.0) || !(flight_time >= 0.0) || !(simulation_time > 0.0)) return "times must be non-negative";
-    return nullptr;
-}
-
-extern "C" int lmh_gen_jump(lmh_handle *h, double simulation_time, double stance_time, double flight_time)
-{
-    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
-    if (const char *msg = jump_spec_error(simulation_time, stance_time, flight_time)) return fail(LMH_ERR_BAD_ARG, msg);
-    const int n = (int)((simulation_time + 0.5) / h->mpc_dt);
-    if (n < 1) return fail(LMH_ERR_BAD_ARG, "no samples");
-    HIPCHK(hipSetDevice(h->device));
-    int rc = alloc_refs(h, n, 0);
-    if (rc != LMH_OK) return rc;
-    lmh_launch_gen_jump(n, h->mpc_dt, stance_time, flight_time, h->d_zx, h->d_zy, h->d_phase, nullptr);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipDeviceSynchronize());
-    h->n_samples = n;
-    fill_params(h);
-    return LMH_OK;
-}
-
-// ---------------------------------------------------------------------------- one plan per robot
-static std::string robot_msg(int i, const char *msg) { return "robot " + std::to_string(i) + ": " + msg; }
-
-// device copy of a host spec array for the batched generators (freed by the caller)
-template <class T> static int upload_specs(const std::vector<T> &specs, T **d_out)
-{
-    T *d = nullptr;
-    HIPCHK(hipMalloc(&d, sizeof(T) * specs.size()));
-    hipError_t e = hipMemcpy(d, specs.data(), sizeof(T) * specs.size(), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); return fail(LMH_ERR_HIP, std::string("spec upload: ") + hipGetErrorString(e)); }
-    *d_out = d;
-    return LMH_OK;
+    const lmh_walk_spec s = {time_per_step, ds_time, step_height, settle_time, foot_y, num_steps, first_support};
+    return gen_walk(h, simulation_time, &s, 1, false);
 }
 
 extern "C" int lmh_gen_walk_batch(lmh_handle *h, double simulation_time, const lmh_walk_spec *specs, int n)
@@ -864,35 +879,44 @@ extern "C" int lmh_gen_walk_batch(lmh_handle *h, double simulation_time, const l
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
     if (!specs) return fail(LMH_ERR_BAD_ARG, "null spec array");
     if (n != h->B) return fail(LMH_ERR_BAD_ARG, "n must be n_instances");
-    const int ns = (int)((simulation_time + 0.5) / h->mpc_dt);      // zmpGeneration.cpp:41: one sample grid for all robots
-    int max_steps = 0;
-    std::vector<LmhWalkSpec> W((size_t)n);
+    return gen_walk(h, simulation_time, specs, n, true);
+}
+
+static const char *jump_spec_error(double simulation_time, const lmh_jump_spec &s)
+{
+    if (!(s.stance_time >= 0.0) || !(s.flight_time >= 0.0) || !(simulation_time > 0.0)) return "times must be non-negative";
+    return nullptr;
+}
+
+// lmh_gen_jump (batch = false: specs[0], today's single-plan launch) and lmh_gen_jump_batch
+static int gen_jump(lmh_handle *h, double simulation_time, const lmh_jump_spec *specs, int n, bool batch)
+{
+    std::vector<LmhJumpSpec> J((size_t)n);
     for (int i = 0; i < n; i++) {
-        const lmh_walk_spec &s = specs[i];
-        if (const char *msg = walk_spec_error(simulation_time, s.num_steps, s.time_per_step, s.ds_time, s.settle_time, s.first_support))
-            return fail(LMH_ERR_BAD_ARG, robot_msg(i, msg));
-        LmhWalkSpec &w = W[(size_t)i];
-        w.time_step = h->mpc_dt; w.time_per_step = s.time_per_step; w.ds_time = s.ds_time; w.step_height = s.step_height;
-        w.settle_time = s.settle_time; w.foot_y = s.foot_y;
-        w.n_samples = ns; w.num_steps = s.num_steps; w.first_support = s.first_support; w.pad = 0;
-        if (s.num_steps > max_steps) max_steps = s.num_steps;
+        if (const char *msg = jump_spec_error(simulation_time, specs[i])) return fail(LMH_ERR_BAD_ARG, batch ? robot_msg(i, msg) : msg);
+        J[(size_t)i] = LmhJumpSpec{specs[i].stance_time, specs[i].flight_time};
     }
+    const int ns = sample_count(h, simulation_time);
     if (ns < 1) return fail(LMH_ERR_BAD_ARG, "no samples");
     HIPCHK(hipSetDevice(h->device));
-    const int n_seg = 2 * max_steps + 2;                            // one stride for all robots
-    LmhWalkSpec *d_specs = nullptr;
-    int rc = upload_specs(W, &d_specs);
+    RefPlan p;
+    const int rc = alloc_plan(p, ns, 0, n);
     if (rc != LMH_OK) return rc;
-    rc = alloc_refs(h, ns, n_seg, n);
-    if (rc != LMH_OK) { (void)hipFree(d_specs); return rc; }
-    lmh_launch_gen_walk_batch(d_specs, n, n_seg, h->d_zx, h->d_zy, h->d_phase, h->d_segs, h->d_sos, nullptr);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(d_specs);
-    if (e != hipSuccess) return fail(LMH_ERR_HIP, std::string("lmh_gen_walk_batch: ") + hipGetErrorString(e));
-    h->n_samples = ns; h->n_seg = n_seg; h->per_robot = true;
-    fill_params(h);
-    return LMH_OK;
+    DevBuf<LmhJumpSpec> d_specs;
+    if (batch) {
+        HIPCHK(d_specs.upload(J.data(), J.size()));
+        lmh_launch_gen_jump_batch(ns, h->mpc_dt, d_specs.get(), n, p.zx.get(), p.zy.get(), p.phase.get(), nullptr);
+    } else lmh_launch_gen_jump(ns, h->mpc_dt, J[0].stance_time, J[0].flight_time, p.zx.get(), p.zy.get(), p.phase.get(), nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    return commit_plan(h, std::move(p));
+}
+
+extern "C" int lmh_gen_jump(lmh_handle *h, double simulation_time, double stance_time, double flight_time)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    const lmh_jump_spec s = {stance_time, flight_time};
+    return gen_jump(h, simulation_time, &s, 1, false);
 }
 
 extern "C" int lmh_gen_jump_batch(lmh_handle *h, double simulation_time, const lmh_jump_spec *specs, int n)
@@ -900,29 +924,10 @@ extern "C" int lmh_gen_jump_batch(lmh_handle *h, double simulation_time, const l
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
     if (!specs) return fail(LMH_ERR_BAD_ARG, "null spec array");
     if (n != h->B) return fail(LMH_ERR_BAD_ARG, "n must be n_instances");
-    std::vector<LmhJumpSpec> J((size_t)n);
-    for (int i = 0; i < n; i++) {
-        if (const char *msg = jump_spec_error(simulation_time, specs[i].stance_time, specs[i].flight_time)) return fail(LMH_ERR_BAD_ARG, robot_msg(i, msg));
-        J[(size_t)i].stance_time = specs[i].stance_time; J[(size_t)i].flight_time = specs[i].flight_time;
-    }
-    const int ns = (int)((simulation_time + 0.5) / h->mpc_dt);
-    if (ns < 1) return fail(LMH_ERR_BAD_ARG, "no samples");
-    HIPCHK(hipSetDevice(h->device));
-    LmhJumpSpec *d_specs = nullptr;
-    int rc = upload_specs(J, &d_specs);
-    if (rc != LMH_OK) return rc;
-    rc = alloc_refs(h, ns, 0, n);
-    if (rc != LMH_OK) { (void)hipFree(d_specs); return rc; }
-    lmh_launch_gen_jump_batch(ns, h->mpc_dt, d_specs, n, h->d_zx, h->d_zy, h->d_phase, nullptr);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    (void)hipFree(d_specs);
-    if (e != hipSuccess) return fail(LMH_ERR_HIP, std::string("lmh_gen_jump_batch: ") + hipGetErrorString(e));
-    h->n_samples = ns; h->per_robot = true;
-    fill_params(h);
-    return LMH_OK;
+    return gen_jump(h, simulation_time, specs, n, true);
 }
 
+// ---------------------------------------------------------------------------- one plan per robot, uploaded / read back
 extern "C" int lmh_set_plans(lmh_handle *h, const double *zx, const double *zy, const uint8_t *phase, int n_samples,
                              const double *segs, int n_seg, const uint16_t *sos, int n)
 {
@@ -932,31 +937,16 @@ extern "C" int lmh_set_plans(lmh_handle *h, const double *zx, const double *zy, 
     if (n_seg > 0) {
         if (!segs || !sos) return fail(LMH_ERR_BAD_ARG, "null segment table");
         if (n_seg > 65536) return fail(LMH_ERR_BAD_ARG, "seg_of_sample is 16 bits wide: at most 65536 segments");
-        for (int i = 0; i < n; i++)
-            for (int k = 0; k < n_samples; k++)
-                if (sos[(size_t)i * n_samples + k] >= n_seg) return fail(LMH_ERR_BAD_ARG, robot_msg(i, "seg_of_sample entry out of range"));
+        const int bad = sos_out_of_range(sos, n_seg, n_samples, n);
+        if (bad >= 0) return fail(LMH_ERR_BAD_ARG, robot_msg(bad, "seg_of_sample entry out of range"));
     }
-    HIPCHK(hipSetDevice(h->device));
-    int rc = alloc_refs(h, n_samples, n_seg, n);
-    if (rc != LMH_OK) return rc;
-    const size_t ns = (size_t)n_samples * (size_t)n;
-    HIPCHK(hipMemcpy(h->d_zx, zx, sizeof(double) * ns, hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_zy, zy, sizeof(double) * ns, hipMemcpyHostToDevice));
-    if (phase) HIPCHK(hipMemcpy(h->d_phase, phase, ns, hipMemcpyHostToDevice));
-    else HIPCHK(hipMemset(h->d_phase, 0, ns));
-    if (n_seg > 0) {
-        HIPCHK(hipMemcpy(h->d_segs, segs, sizeof(double) * LMH_SEG_STRIDE * (size_t)n_seg * (size_t)n, hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(h->d_sos, sos, sizeof(uint16_t) * ns, hipMemcpyHostToDevice));
-    }
-    h->n_samples = n_samples; h->n_seg = n_seg; h->per_robot = true;
-    fill_params(h);
-    return LMH_OK;
+    return upload_plan(h, zx, zy, phase, n_samples, segs, n_seg, sos, n);
 }
 
 extern "C" int lmh_plans_per_instance(const lmh_handle *h)
 {
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
-    return h->per_robot ? 1 : 0;
+    return h->plan.per_robot() ? 1 : 0;
 }
 
 extern "C" int lmh_get_plan(lmh_handle *h, int inst, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos)
@@ -964,34 +954,24 @@ extern "C" int lmh_get_plan(lmh_handle *h, int inst, double *zx, double *zy, uin
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
     if (inst < 0 || inst >= h->B) return fail(LMH_ERR_BAD_ARG, "instance out of range");
     HIPCHK(hipSetDevice(h->device));
-    const size_t n = (size_t)h->n_samples;
+    const RefPlan &r = h->plan;
+    const size_t n = (size_t)r.n_samples;
     const size_t ro = (size_t)h->P.ref_stride * (size_t)inst, so = (size_t)LMH_SEG_STRIDE * (size_t)h->P.seg_stride * (size_t)inst;   // 0 on a shared plan
-    if (zx) HIPCHK(hipMemcpy(zx, h->d_zx + ro, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (zy) HIPCHK(hipMemcpy(zy, h->d_zy + ro, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (zx) HIPCHK(hipMemcpy(zx, r.zx.get() + ro, sizeof(double) * n, hipMemcpyDeviceToHost));
+    if (zy) HIPCHK(hipMemcpy(zy, r.zy.get() + ro, sizeof(double) * n, hipMemcpyDeviceToHost));
     if (phase) {
-        if (h->d_phase) HIPCHK(hipMemcpy(phase, h->d_phase + ro, n, hipMemcpyDeviceToHost));
+        if (r.phase.get()) HIPCHK(hipMemcpy(phase, r.phase.get() + ro, n, hipMemcpyDeviceToHost));
         else std::memset(phase, 0, n);
     }
-    if (segs && h->n_seg > 0) HIPCHK(hipMemcpy(segs, h->d_segs + so, sizeof(double) * LMH_SEG_STRIDE * (size_t)h->n_seg, hipMemcpyDeviceToHost));
-    if (sos && h->n_seg > 0) HIPCHK(hipMemcpy(sos, h->d_sos + ro, sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
+    if (segs && r.n_seg > 0) HIPCHK(hipMemcpy(segs, r.segs.get() + so, sizeof(double) * LMH_SEG_STRIDE * (size_t)r.n_seg, hipMemcpyDeviceToHost));
+    if (sos && r.n_seg > 0) HIPCHK(hipMemcpy(sos, r.sos.get() + ro, sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
     return LMH_OK;
 }
 
-extern "C" int lmh_num_ref_samples(const lmh_handle *h) { return h ? h->n_samples : 0; }
-extern "C" int lmh_num_segments(const lmh_handle *h) { return h ? h->n_seg : 0; }
+extern "C" int lmh_num_ref_samples(const lmh_handle *h) { return h ? h->plan.n_samples : 0; }
+extern "C" int lmh_num_segments(const lmh_handle *h) { return h ? h->plan.n_seg : 0; }
 
 extern "C" int lmh_get_refs(lmh_handle *h, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos)
 {
-    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
-    HIPCHK(hipSetDevice(h->device));
-    const size_t n = (size_t)h->n_samples;
-    if (zx) HIPCHK(hipMemcpy(zx, h->d_zx, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (zy) HIPCHK(hipMemcpy(zy, h->d_zy, sizeof(double) * n, hipMemcpyDeviceToHost));
-    if (phase) {
-        if (h->d_phase) HIPCHK(hipMemcpy(phase, h->d_phase, n, hipMemcpyDeviceToHost));
-        else std::memset(phase, 0, n);
-    }
-    if (segs && h->n_seg > 0) HIPCHK(hipMemcpy(segs, h->d_segs, sizeof(double) * LMH_SEG_STRIDE * (size_t)h->n_seg, hipMemcpyDeviceToHost));
-    if (sos && h->n_seg > 0) HIPCHK(hipMemcpy(sos, h->d_sos, sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
-    return LMH_OK;
+    return lmh_get_plan(h, 0, zx, zy, phase, segs, sos);
 }

@@ -6,7 +6,7 @@ VARS=$1; shift
 mkdir -p $O
 for v in "" $VARS ""; do
   n=${v:-shipped}
-  LMH_VARIANT=$v timeout -k 10 300 python bench.py --no-cpu-baseline --steps 4 --warmup 1 "$@" > $O/ab_$n.json 2> $O/ab_$n.err || echo "variant $n failed"
+  LMH_VARIANT=$v timeout -k 10 300 python bench.py --no-cpu-baseline --steps 4 --warmup 1 "$@" > $O/ab_$n.json 2> $O/ab_$n.err || { echo "variant $n failed: nothing more is started"; exit 1; }
   python - "$O/ab_$n.json" "$n" <<'PY'
 import json, sys
 try:

@@ -1,7 +1,7 @@
 """Per-robot gait and jump schedules (lmh_gen_walk_batch / lmh_gen_jump_batch / lmh_set_plans): the batched generators against the host
 statement, a per-robot handle with equal specs against the shared handle, robot i of a mixed batch against robot i alone, closed-loop /
-plain / debug evaluation against the CPU oracle on each robot's own plan, the upload path, argument checks and the way back to one
-shared plan.  The draw (ranges, seed 20261016, order) is tests/plan_draw.py.  Rules as in the other GPU files: the HIP path through the
+plain / debug evaluation against the CPU oracle on each robot's own plan, the upload path, argument checks, the way back to one
+shared plan and a refused lmh_set_segments, which releases nothing.  The draw (ranges, seed 20261016, order) is tests/plan_draw.py.  Rules as in the other GPU files: the HIP path through the
 C ABI against the oracle, 1e-6 relative on tau / f (helpers.close), bit-exact k; "the same computation" means bit-identical."""
 import json
 import os
@@ -443,6 +443,64 @@ def test_shared_plan_after_per_robot_plans_is_a_fresh_handle(nao):
     fresh.gen_walk(2.0, **spec)
     assert same_bits(back, run(fresh, fresh.new_state(nao["q0"], v, t=0.0), nt))
     fresh.close()
+
+
+# ------------------------------------------------------------------------------- 10b. a refused lmh_set_segments releases nothing
+def test_refused_set_segments_leaves_the_handle_on_its_plan(nao):
+    """set_segments with a seg_of_sample entry >= n_seg, and with a wrong n_samples, is LMH_ERR_BAD_ARG.  On a handle carrying a
+    generated walking plan, after each refusal num_segments and get_refs() return exactly what they returned before, and a rollout into
+    the first swing is bit-identical to the one of an untouched twin handle.  On a handle with per-robot plans the same refusals leave
+    plans_per_instance true and every robot's get_plan unchanged."""
+    from linearmpchumanoid_amd import capi
+    from linearmpchumanoid_amd.capi import LmhError
+    B, nt = 8, 400
+    spec = dict(num_steps=3, time_per_step=0.45, ds_time=0.12, step_height=0.02, settle_time=0.1, first_support=2, foot_y=0.05)
+    xs = np.linspace(0.02, 0.05, B)
+
+    def walker():
+        c = make_controller(B, zcom=nao["zcom"], warm_start=1)
+        c.gen_walk(SIM_TIME, **spec)
+        c.set_xscale(xs)
+        return c
+
+    def refusals(plan):
+        """The two refused calls on a handle whose (robot 0's) plan is `plan`."""
+        beyond = plan["seg_of_sample"].copy()
+        beyond[17] = len(plan["segs"])
+        return (lambda c: c.set_segments(plan["segs"], beyond)), (lambda c: c.set_segments(plan["segs"], plan["seg_of_sample"][:-1]))
+
+    def refused(fn, c):
+        with pytest.raises(LmhError) as ei:
+            fn(c)
+        assert ei.value.code == -2, str(ei.value)
+
+    ctl, twin = walker(), walker()
+    before = ctl.get_refs()
+    n_seg = capi.lib().lmh_num_segments(ctl._h)
+    assert n_seg == 2 * spec["num_steps"] + 2 == len(before["segs"])
+    assert before["phase"][int(nt * DT / MPC_DT) - 1] != 0             # the rollout reaches a swing: its foot references are the segments'
+    want = run(twin, twin.new_state(nao["q0"], np.zeros(30), t=0.0), nt)
+    twin.close()
+    assert np.isfinite(want["log"]).all()
+    for fn in refusals(before):
+        refused(fn, ctl)
+        assert capi.lib().lmh_num_segments(ctl._h) == n_seg
+        after = ctl.get_refs()
+        assert all(np.array_equal(after[k], before[k]) for k in before)
+        assert same_bits(want, run(ctl, ctl.new_state(nao["q0"], np.zeros(30), t=0.0), nt))
+    ctl.close()
+
+    sp, _ = draw_walk_specs(B)
+    per = make_controller(B, zcom=nao["zcom"], warm_start=1)
+    per.gen_walk_batch(SIM_TIME, sp)
+    plans = [per.get_plan(i) for i in range(B)]
+    for fn in refusals(plans[0]):
+        refused(fn, per)
+        assert per.plans_per_instance
+        for i in range(B):
+            g = per.get_plan(i)
+            assert all(np.array_equal(g[k], plans[i][k]) for k in g), i
+    per.close()
 
 
 # ------------------------------------------------------------------------------- 11. no result depends on LDS nobody wrote
