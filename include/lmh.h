@@ -43,6 +43,8 @@ extern "C" {
 #define LMH_MAX_HORIZON 64
 #define LMH_DEBUG_STRIDE 4096
 #define LMH_SEG_STRIDE 52
+#define LMH_PUSH_STRIDE 32        /* one timed velocity push: tick (as a double) | dv[30] | pad, see lmh_set_pushes */
+#define LMH_MAX_PUSHES 16         /* push records per robot */
 
 /* status flags */
 #define LMH_FLAG_QP_MAXITER 1     /* active-set iteration cap hit (reference: "QP failed", controller.cpp:472-476) */
@@ -219,6 +221,26 @@ int lmh_set_zcom(lmh_handle *h, const double *z_com, int n);
 /* MPC gain row K (HOST out [N+1]) with u0 = -K (Px x_k - zmp[k:k+N+1]); instance 0 */
 int lmh_get_mpc_gain(lmh_handle *h, double *K);
 
+/* Timed velocity pushes inside lmh_rollout (build-defined; BASELINE config 2's perturbation at any tick instead of at t = 0 only).
+ * A push is a tick number n >= 0 and an increment dv[30] of the generalised velocity, laid out as the v half of the state record
+ * (dv[0:2] is the planar base kick).  A robot's tick number is absolute: n = llrint(t / dt) of its own clock state[90] at the start of a
+ * tick (the kernel rounds with rint and compares in fp64: the same whole number).  At the start of tick n, before that tick's first controller evaluation, v += dv; q, v_prev (Robot::v_) and t are not touched:
+ * exactly what a host does that stops lmh_rollout when the robot's clock reaches n dt, adds dv to state[i][30:60] and goes on.  Hence
+ * lmh_rollout(a + b) is still lmh_rollout(a) followed by lmh_rollout(b) bit for bit: a record written to d_state never holds a push
+ * whose tick has not started (a push at tick a is applied by the second call when it loads the robot; the 250-tick hand-overs inside a
+ * launch follow the same rule).  A push whose tick is below the robot's tick number at the start of the launch is in the past and is
+ * ignored; one beyond the last tick is never applied.  Same with plant = 0 and 1 and in every precision.  External forces on the plant
+ * are not modelled.  lmh_eval, lmh_eval_debug and lmh_eval_host do not integrate and ignore the schedule.
+ * records: HOST [n_sets][n_push][LMH_PUSH_STRIDE], n_sets = 1 (one schedule shared by all robots) or n_instances; per schedule the
+ * ticks are whole numbers below 2^31, strictly increasing, dv finite; unused trailing records carry tick -1 (their dv is ignored).
+ * n_push <= LMH_MAX_PUSHES.  records = NULL or n_push = 0 clears the schedule.  A refused call (the error text names the first offending
+ * robot, "robot 7: ...") leaves the previous schedule in place, as every table setter does (see lmh_set_refs). */
+int lmh_set_pushes(lmh_handle *h, const double *records, int n_push, int n_sets);
+int lmh_num_pushes(const lmh_handle *h);                  /* records per schedule; 0: none set */
+int lmh_pushes_per_instance(const lmh_handle *h);         /* 0: none or one shared schedule, 1: one schedule per robot */
+/* robot `inst`'s schedule (the shared one on a shared schedule): HOST out [lmh_num_pushes][LMH_PUSH_STRIDE] */
+int lmh_get_pushes(lmh_handle *h, int inst, double *records);
+
 /* replaces: Controller::standStep + Controller::WBC (src/controller.cpp:48-154) for all
  * instances.  DEVICE pointers; d_state is read AND updated (v_prev <- v, as Robot::v_ is);
  * stream is a hipStream_t (NULL = default stream).  Asynchronous. */
@@ -234,6 +256,7 @@ int lmh_eval_debug(lmh_handle *h, double *d_state, double *d_out, int32_t *d_sta
  * Inside the call a robot is advanced in chunks of 250 ticks by whichever resident workgroup claims it next (its record in
  * d_state / d_out / d_status is the hand-over); the result does not depend on that: lmh_rollout(.., a + b, ..) equals
  * lmh_rollout(.., a, ..) followed by lmh_rollout(.., b, ..) bit for bit (with [1], [2] merged as max / OR).
+ * The velocity pushes of lmh_set_pushes are applied here, at the start of their ticks.
  * Host side of "asynchronous": the call only enqueues (one small parameter copy + the kernel) on `stream`, except that a handle keeps
  * EIGHT launches in flight -- the ninth lmh_rollout waits on the host until the first has completed -- and that the first eight calls
  * allocate their launch slot (hipMalloc): not capturable into a hipGraph before every slot has been used once.  A slot is acquired whole

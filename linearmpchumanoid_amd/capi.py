@@ -18,6 +18,8 @@ STATUS_STRIDE = 4
 DEBUG_STRIDE = 4096
 LINK_STRIDE = 13
 SEG_STRIDE = 52
+PUSH_STRIDE = 32              # one timed velocity push: tick (as a double) | dv[30] | pad (lmh_set_pushes)
+MAX_PUSHES = 16               # push records per robot
 
 FLAG_QP_MAXITER = 1
 FLAG_NONFINITE = 2
@@ -41,6 +43,7 @@ EXPORTS = [
     "lmh_make_summary", "lmh_write_summary", "lmh_read_summary", "lmh_write_log", "lmh_read_log",
     "lmh_gen_walk", "lmh_gen_jump", "lmh_num_ref_samples", "lmh_num_segments", "lmh_get_refs",
     "lmh_gen_walk_batch", "lmh_gen_jump_batch", "lmh_set_plans", "lmh_plans_per_instance", "lmh_get_plan",
+    "lmh_set_pushes", "lmh_num_pushes", "lmh_pushes_per_instance", "lmh_get_pushes",
 ]
 
 
@@ -121,6 +124,10 @@ def lib():
     L.lmh_set_plans.argtypes = [vp, vp, vp, vp, ip, vp, ip, vp, ip]
     L.lmh_plans_per_instance.argtypes = [vp]
     L.lmh_get_plan.argtypes = [vp, ip, vp, vp, vp, vp, vp]
+    L.lmh_set_pushes.argtypes = [vp, vp, ip, ip]
+    L.lmh_num_pushes.argtypes = [vp]
+    L.lmh_pushes_per_instance.argtypes = [vp]
+    L.lmh_get_pushes.argtypes = [vp, ip, vp]
     L.lmh_make_summary.argtypes = [vp, vp, vp, vp, vp, vp]
     L.lmh_write_summary.argtypes = [C.c_char_p, vp, u64, dp]
     L.lmh_read_summary.argtypes = [C.c_char_p, vp, u64, u64p, dpp]

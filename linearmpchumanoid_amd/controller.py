@@ -212,6 +212,29 @@ class BatchedController:
         check(capi.lib().lmh_get_plan(self._h, int(i), _np_ptr(zx), _np_ptr(zy), _np_ptr(ph), _np_ptr(segs) if ns else None, _np_ptr(sos) if ns else None))
         return dict(zmp_x=zx, zmp_y=zy, phase=ph, segs=segs, seg_of_sample=sos)
 
+    # -- timed velocity pushes inside rollout (include/lmh.h, lmh_set_pushes)
+    def set_pushes(self, ticks, dv=None):
+        """lmh_set_pushes: velocity increments applied inside rollout at the start of given ticks.  ticks [B,n] or [n] (one schedule shared
+        by all robots), whole numbers, -1 = unused; dv [..,n,30] laid out as state[:, 30:60].  trajectories.push_schedule sorts and pads
+        them into records (and refuses what the library refuses, in the same words).  ticks=None clears the schedule."""
+        if ticks is None:
+            check(capi.lib().lmh_set_pushes(self._h, None, 0, 1))
+            return
+        rec = trajectories.push_schedule(ticks, dv, n_instances=self.B)
+        check(capi.lib().lmh_set_pushes(self._h, _np_ptr(rec), rec.shape[1], rec.shape[0]))
+
+    @property
+    def pushes_per_instance(self):
+        """True while every robot has a push schedule of its own."""
+        return bool(capi.lib().lmh_pushes_per_instance(self._h))
+
+    def get_pushes(self, i):
+        """Robot i's schedule read back from the device (the shared one on a shared schedule): dict(ticks [n] int64, dv [n,30])."""
+        n = capi.lib().lmh_num_pushes(self._h)
+        rec = np.zeros((n, capi.PUSH_STRIDE))
+        check(capi.lib().lmh_get_pushes(self._h, int(i), _np_ptr(rec) if n else None))
+        return dict(ticks=rec[:, 0].astype(np.int64), dv=rec[:, 1:31].copy())
+
     def set_xscale(self, xscale):
         """Per-instance step-length scale of ZMP x and x-axis foot polynomials ([B] or None)."""
         if xscale is None:

@@ -64,6 +64,8 @@ struct lmh_handle {
     int B = 0, device = 0, N = 0, n_models = 0, n_gain = 0;
     DevBuf<double> d_model, d_raw, d_mpc, d_gcol, d_xscale;
     RefPlan plan;                     // replaced as a whole, by commit_plan only
+    DevBuf<double> d_pushes;          // timed velocity pushes [n_push_sets][n_push][LMH_PUSH_STRIDE] (lmh_set_pushes); empty while n_push = 0
+    int n_push = 0, n_push_sets = 1;
     // staging for the host-buffer convenience calls
     DevBuf<double> d_state, d_out;
     DevBuf<int32_t> d_status;
@@ -280,6 +282,7 @@ static void fill_params(lmh_handle *h)
     P.model = h->d_model.get(); P.mpc = h->d_mpc.get(); P.gcol = h->d_gcol.get(); P.xscale = h->d_xscale.get();
     P.zmpx = r.zx.get(); P.zmpy = r.zy.get(); P.phase = r.phase.get(); P.segs = r.segs.get(); P.seg_of_sample = r.sos.get();
     P.n_seg = r.n_seg; P.ref_stride = r.per_robot() ? r.n_samples : 0; P.seg_stride = r.per_robot() ? r.n_seg : 0;
+    P.pushes = h->d_pushes.get(); P.n_push = h->n_push; P.push_stride = (h->n_push_sets > 1) ? h->n_push : 0;
     P.model_stride = (h->n_models > 1) ? LMH_MODEL_STRIDE : 0;
     P.mpc_stride = 3 * (h->N + 1) + 4;
     P.mpc_stride_inst = (h->n_gain > 1) ? P.mpc_stride : 0;
@@ -518,6 +521,57 @@ extern "C" int lmh_set_segments(lmh_handle *h, const double *segs, int n_seg, co
     p.zx = std::move(cur.zx); p.zy = std::move(cur.zy); p.phase = std::move(cur.phase);
     p.n_samples = cur.n_samples; p.n_seg = n_seg;
     return commit_plan(h, std::move(p));
+}
+
+// ---------------------------------------------------------------------------- timed velocity pushes (lmh_rollout)
+// the rules of one schedule (n_push records): nullptr = fine.  trajectories.push_schedule states the same rules with the same words.
+static const char *push_schedule_error(const double *rec, int n_push)
+{
+    double prev = -1.0;
+    bool unused = false;
+    for (int j = 0; j < n_push; j++, rec += LMH_PUSH_STRIDE) {
+        const double tk = rec[0];
+        if (tk == -1.0) { unused = true; continue; }                // padding: its dv is ignored
+        if (!(tk >= 0.0) || !(tk < 2147483648.0) || tk != std::floor(tk)) return "push ticks must be whole numbers in [0, 2^31), or -1 for an unused record";
+        if (unused) return "a used push record follows an unused one";
+        if (!(tk > prev)) return "push ticks must be strictly increasing";
+        for (int e = 1; e <= LMH_NQ; e++) if (!std::isfinite(rec[e])) return "push dv must be finite";
+        prev = tk;
+    }
+    return nullptr;
+}
+
+extern "C" int lmh_set_pushes(lmh_handle *h, const double *records, int n_push, int n_sets)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    if (n_push < 0) return fail(LMH_ERR_BAD_ARG, "n_push must be >= 0");
+    if (!records) n_push = 0;
+    if (n_push > LMH_MAX_PUSHES) return fail(LMH_ERR_BAD_ARG, "n_push must be at most LMH_MAX_PUSHES (16)");
+    if (n_push == 0) n_sets = 1;
+    if (n_sets != 1 && n_sets != h->B) return fail(LMH_ERR_BAD_ARG, "n_sets must be 1 or n_instances");
+    for (int i = 0; i < n_sets && n_push > 0; i++)
+        if (const char *msg = push_schedule_error(records + (size_t)LMH_PUSH_STRIDE * n_push * i, n_push)) return fail(LMH_ERR_BAD_ARG, robot_msg(i, msg));
+    HIPCHK(hipSetDevice(h->device));
+    DevBuf<double> d;
+    if (n_push > 0) HIPCHK(d.upload(records, (size_t)LMH_PUSH_STRIDE * n_push * n_sets));
+    h->d_pushes = std::move(d); h->n_push = n_push; h->n_push_sets = n_sets;     // nothing above changed the handle; nothing below fails
+    fill_params(h);
+    return LMH_OK;
+}
+
+extern "C" int lmh_num_pushes(const lmh_handle *h) { return h ? h->n_push : 0; }
+extern "C" int lmh_pushes_per_instance(const lmh_handle *h) { return (h && h->n_push > 0 && h->n_push_sets > 1) ? 1 : 0; }
+
+extern "C" int lmh_get_pushes(lmh_handle *h, int inst, double *records)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    if (inst < 0 || inst >= h->B) return fail(LMH_ERR_BAD_ARG, "instance out of range");
+    if (h->n_push == 0) return LMH_OK;
+    if (!records) return fail(LMH_ERR_BAD_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t n = (size_t)LMH_PUSH_STRIDE * h->n_push;
+    HIPCHK(hipMemcpy(records, h->d_pushes.get() + ((h->n_push_sets > 1) ? n * (size_t)inst : 0), sizeof(double) * n, hipMemcpyDeviceToHost));
+    return LMH_OK;
 }
 
 extern "C" int lmh_set_xscale(lmh_handle *h, const double *xscale, int n)

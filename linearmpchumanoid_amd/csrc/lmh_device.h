@@ -5,6 +5,7 @@
 #define LMH_MODEL_STRIDE 400  // per model: 28 x 14 doubles (Ibar 9 | m*c 3 | m | Robot::desiredPosture of coordinate i, the record's spare slot) + [392] total mass
 #define LMH_BODY_STRIDE 14
 #define LMH_SEG_STRIDE 52
+#define LMH_PUSH_STRIDE 32    // one velocity push: tick (as a double) | dv[30] | pad (include/lmh.h, lmh_set_pushes)
 #define LMH_ROLLOUT_THREADS 128   // fused rollout: two waves per robot (lmh_kernels.hip, bsync)
 
 struct LmhIkTarget { double v[16]; };   // rF(6) | lF(6) | com(3) | pad: passed by value in the IK kernel's arguments
@@ -20,6 +21,7 @@ struct LmhDevParams {
     const double *segs;         // [n_seg][LMH_SEG_STRIDE] walking segments: t0 | rF[3][8] | lF[3][8] | pad, or nullptr
     const uint16_t *seg_of_sample; // [n_samples] segment of preview index k
     const double *xscale;       // [n_instances] per-instance scale of ZMP x and x-axis foot polynomials, or nullptr
+    const double *pushes;       // [n_sets][n_push][LMH_PUSH_STRIDE] timed velocity pushes (lmh_rollout only), or nullptr while n_push = 0
     int32_t model_stride;       // 0 = shared model
     int32_t mpc_stride_inst;    // 0 = shared gain row
     int32_t mpc_stride;         // 3*(N+1)+4
@@ -34,6 +36,8 @@ struct LmhDevParams {
     int32_t plant;              // 1: compliant-contact plant driven by the torques (lmh_config.plant)
     int32_t ref_stride;         // per-robot plans: samples per robot in zmpx / zmpy / phase / seg_of_sample (= n_samples); 0 = one shared plan
     int32_t seg_stride;         // per-robot plans: segment records per robot in segs (= n_seg); 0 = shared
+    int32_t push_stride;        // push records per robot in pushes (= n_push); 0 = one schedule shared by all robots
+    int32_t n_push;             // push records per schedule (<= LMH_MAX_PUSHES); 0 = no schedule
     // ---- scalars (reference literals, see include/lmh.h lmh_config)
     double dt;                  // control step (RK4 step of the fused rollout, Clock::step)
     double mpc_dt;              // MPC sample time: k = int(t / mpc_dt), sample period of the reference arrays (lmh_config.mpc_dt; = dt when that is 0)

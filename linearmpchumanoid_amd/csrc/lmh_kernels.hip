@@ -1720,6 +1720,8 @@ __device__ __forceinline__ double jdense(const double *L, int row, int col)
 // mpc_dt / dt ticks x 4 stages (40 evaluations at 1 kHz / 10 ms): the robot keeps {k, phase, sum K zmp, the swing segment's coefficients
 // already scaled by its step length, the segment's t0} in LDS and goes back to HBM / L2 only when k moves.  One wave maintains the cache
 // (NW = 2: the helper wave, beside the forward kinematics); the other reads k / phase after the first join.
+// P_TIME + 0 itself belongs to the rollout's push cursor (P_PUSH, two ints punned into the slot): nothing may read or write it as a double
+// in a path the rollout kernel runs (the evaluation kernel parks t there, which nobody reads)
 #define P_RK (P_TIME + 1)          // cached preview index (as a double; set to -2^30 when a robot is loaded)
 #define P_RPH (P_TIME + 2)         // support phase of sample k
 #define P_RXS (P_TIME + 3)         // the robot's step-length scale (lmh_set_xscale), 1 without
@@ -4095,6 +4097,53 @@ __device__ __forceinline__ void rk4_stage(double *L, int stage, int lane, double
     xs = fma(c, xd, x);
 }
 
+// ---- timed velocity pushes (include/lmh.h, lmh_set_pushes): wave 0 of the rollout only.
+// The cursor lives in the one persistent LDS slot the rollout does not use (P_TIME: the evaluation kernel parks t there, nobody reads it),
+// as two ints: [0] the next push's tick counted from the chunk's first tick, PUSH_NONE when no push falls inside this chunk | [1] its
+// record.  Nothing is carried in registers across an evaluation: the tick loop reads [0] once per tick and compares.
+#define P_PUSH P_TIME
+#define PUSH_NONE 0x3fffffff
+static_assert(P_PUSH == P_Q + 90 && P_PUSH + 1 == P_TIME + 1 && sizeof(double) == 2 * sizeof(int), "the push cursor is two ints in the one slot between v_prev and the reference cache");
+// chunk load: the robot's tick number from its clock (rint: t is a float-accumulated sum of dt), then the first record not in the past
+// (ticks are strictly increasing, unused trailing records carry -1).  Returns the ticks until that push (`lim` = ticks of this chunk;
+// PUSH_NONE at or beyond it: the next chunk finds it again) and its record in *cur.
+__device__ __forceinline__ int push_seek(double *L, LmhCParams &P, int inst, int lane, double t, int lim, int *cur)
+{
+    const int np = P.n_push;
+    int rel = PUSH_NONE, c = 0;
+    if (np > 0) {
+        const double n0 = rint(t / P.dt);
+        const double *tb = P.pushes + (size_t)LMH_PUSH_STRIDE * ((size_t)P.push_stride * inst);
+        const double tk = (lane < np) ? tb[LMH_PUSH_STRIDE * lane] : -1.0;
+        const bool live = tk >= 0.0 && tk >= n0;
+        const double d = tk - n0;
+        const int di = (live && d < (double)lim) ? (int)d : PUSH_NONE;
+        const unsigned long long m = __builtin_amdgcn_ballot_w64(live);
+        if (m != 0ull) { c = __builtin_ctzll(m); rel = __builtin_amdgcn_readlane(di, c); }
+    }
+    if (lane == 0) { int *pw = (int *)(L + P_PUSH); pw[0] = rel; pw[1] = c; }
+    *cur = c;
+    return rel;
+}
+// the push of record `cur` is due (`rel` ticks into the chunk): v += dv on lanes 30..59, and the cursor moves to the next record
+__device__ __forceinline__ void push_apply(double *L, LmhCParams &P, int inst, int lane, int rel, int cur, int lim, double &x)
+{
+    const double *rec = P.pushes + (size_t)LMH_PUSH_STRIDE * ((size_t)P.push_stride * inst + cur);
+    const bool vl = lane >= 30 && lane < 60;
+    const double dv = rec[vl ? 1 + lane - 30 : 1];
+    if (vl) x += dv;
+    const double tn = (cur + 1 < P.n_push) ? rec[LMH_PUSH_STRIDE] : -1.0;
+    const double d = (double)rel + (tn - rec[0]);
+    if (lane == 0) { int *pw = (int *)(L + P_PUSH); pw[0] = (tn >= 0.0 && d < (double)lim) ? (int)d : PUSH_NONE; pw[1] = cur + 1; }
+}
+// per tick (wave 0, once the tick's state is final): is a push due at the start of tick `next` of this chunk?
+__device__ __forceinline__ void push_poll(double *L, LmhCParams &P, int inst, int lane, int next, int lim, double &x)
+{
+    const int *pw = (const int *)(L + P_PUSH);
+    const int rel = __builtin_amdgcn_readfirstlane(pw[0]);
+    if (rel == next) push_apply(L, P, inst, lane, rel, __builtin_amdgcn_readfirstlane(pw[1]), lim, x);
+}
+
 // Closed loop of apps/offline/main.cpp:66-122: n_ticks x rk4Step(dynamics) with Clock::step.
 // Workgroup = LMH_ROLLOUT_THREADS = 2 waves per robot (see bsync): 4 robots = 8 waves per CU, two per SIMD, so the
 // kernel is held to 256 registers.  Wave 0 owns the RK4 state (lane i < 60 <-> component i) and everything
@@ -4175,6 +4224,11 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
     if (wid == 0) {
         load_common(L, P, inst);
         x = (lane < 60) ? st[lane] : 0.0;
+        {   // velocity pushes: the record in HBM never holds a push whose tick has not started, so one due at this chunk's first tick goes in here
+            int pc = 0;
+            const int pr = push_seek(L, P, inst, lane, t, n_here, &pc);
+            if (pr == 0) push_apply(L, P, inst, lane, 0, pc, n_here, x);
+        }
         if (lane < 30) L[P_VP + lane] = st[60 + lane];
         F = (unsigned)status[LMH_STATUS_STRIDE * inst + 3];
         F = P.warm_start ? ~F : 0xFFFFFFFFu;
@@ -4256,7 +4310,10 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
                 itmax = (iters > itmax) ? iters : itmax;
                 const double xprev = xs;
                 rk4_stage<3>(L, stage, lane, dt, xd4, x, ksum, xs, tail.xd);
-                if (stage == 3) xs = x;                            // the next tick starts from x (what `xs = x` at its top says)
+                if (stage == 3) {
+                    push_poll(L, *Pe, inst, lane, tick + 1, n_here, x);     // a push at the start of the next tick joins the state published for it
+                    xs = x;                                        // the next tick starts from x (what `xs = x` at its top says)
+                }
                 // one publish: Robot::v_ <- dq and the state of the next evaluation; behind the recovery's join wave 0 has read nothing
                 // from LDS, and the helper touches neither.  The accelerations only where somebody reads them (store_out, end of a chunk)
                 if (lane >= 30 && lane < 60) { L[P_VP + lane - 30] = xprev; if (stage == 3) L[P_QDD + lane - 30] = tail.xd; }
@@ -4266,6 +4323,7 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
                 itmax = (iters > itmax) ? iters : itmax;
                 const double xprev = xs;
                 if constexpr (PIPE) rk4_stage<2>(L, stage, lane, dt, xd4, x, ksum, xs); else rk4_stage<0>(L, stage, lane, dt, xd4, x, ksum, xs);
+                if (stage == 3) push_poll(L, *Pe, inst, lane, tick + 1, n_here, x);     // the next tick publishes x at its top
                 // Robot::v_ <- dq for the next evaluation
                 WSYNC();
                 if (lane >= 30 && lane < 60) L[P_VP + lane - 30] = xprev;

@@ -8,7 +8,7 @@ definition on top of the reference's conventions (SupportFoot -> ZMP y of -/+0.0
 """
 import numpy as np
 
-from .capi import PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT
+from .capi import MAX_PUSHES, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE
 
 
 def stance_zmp(simulation_time, time_step, support_foot=2):
@@ -180,5 +180,85 @@ def jump_plans(simulation_time, time_step, specs, B=None):
     return {k: np.stack([p[k] for p in plans]) for k in ("zmp_x", "zmp_y", "phase")}
 
 
+# the refusals of lmh_set_pushes, word for word (lmh_capi.hip, push_schedule_error)
+PUSH_ERR_TICK = "push ticks must be whole numbers in [0, 2^31), or -1 for an unused record"
+PUSH_ERR_ORDER = "a used push record follows an unused one"
+PUSH_ERR_INCREASING = "push ticks must be strictly increasing"
+PUSH_ERR_DV = "push dv must be finite"
+PUSH_ERR_COUNT = "n_push must be at most LMH_MAX_PUSHES (16)"
+PUSH_ERR_SETS = "n_sets must be 1 or n_instances"
+
+
+def check_push_records(records, n_instances=None):
+    """The rules of lmh_set_pushes on records [n_sets, n_push, 32] as they stand (nothing is sorted): raises ValueError with the
+    library's wording, the first offending robot named ("robot 7: ...")."""
+    rec = np.asarray(records, dtype=np.float64)
+    if rec.ndim != 3 or rec.shape[2] != PUSH_STRIDE:
+        raise ValueError("push records must be [n_sets, n_push, 32]")
+    if rec.shape[1] > MAX_PUSHES:
+        raise ValueError(PUSH_ERR_COUNT)
+    if n_instances is not None and rec.shape[0] not in (1, n_instances):
+        raise ValueError(PUSH_ERR_SETS)
+    for i, sched in enumerate(rec):
+        prev, unused = -1.0, False
+        for r in sched:
+            tk = r[0]
+            if tk == -1.0:
+                unused = True
+                continue
+            if not (tk >= 0.0) or not (tk < 2147483648.0) or tk != np.floor(tk):
+                raise ValueError(f"robot {i}: {PUSH_ERR_TICK}")
+            if unused:
+                raise ValueError(f"robot {i}: {PUSH_ERR_ORDER}")
+            if not (tk > prev):
+                raise ValueError(f"robot {i}: {PUSH_ERR_INCREASING}")
+            if not np.isfinite(r[1:31]).all():
+                raise ValueError(f"robot {i}: {PUSH_ERR_DV}")
+            prev = tk
+    return rec
+
+
+def push_schedule(ticks, dv, n_instances=None):
+    """Host statement of the push table of lmh_set_pushes: ticks [B,n] or [n] (whole numbers; -1 = unused), dv [..,n,30] laid out as the v
+    half of the state record -> records [n_sets, n, 32] = tick (as a double) | dv[30] | pad, per robot sorted by tick with the unused
+    records last (tick -1, dv zero).  A [n] schedule is one shared set (n_sets = 1).  Everything lmh_set_pushes refuses is refused here
+    with the same words (check_push_records): a tick that is not a whole number >= 0, two pushes of one robot on one tick, a non-finite
+    dv, more than MAX_PUSHES records, n_sets not in {1, n_instances}."""
+    if ticks is None or dv is None:
+        raise ValueError("push_schedule needs both ticks and dv (dv [..,n,30])")
+    tk = np.asarray(ticks, dtype=np.float64)
+    d = np.asarray(dv, dtype=np.float64)
+    if tk.ndim == 1:
+        tk, d = tk[None, :], (d[None, ...] if d.ndim == 2 else d)
+    if tk.ndim != 2 or d.shape != tk.shape + (30,):
+        raise ValueError("ticks must be [B,n] or [n] and dv [..,n,30]")
+    n_sets, n = tk.shape
+    rec = np.zeros((n_sets, n, PUSH_STRIDE))
+    for i in range(n_sets):
+        used = tk[i] != -1.0
+        order = np.concatenate([np.flatnonzero(used)[np.argsort(tk[i][used], kind="stable")], np.flatnonzero(~used)])
+        rec[i, :, 0] = tk[i][order]
+        rec[i, :, 1:31] = np.where(used[order][:, None], d[i][order], 0.0)
+    return check_push_records(rec, n_instances)
+
+
+def draw_pushes(B, n, tick_range, amplitude, seed):
+    """n planar base kicks per robot in the manner of tests/helpers.perturbed_velocities (BASELINE config 2): robot i draws from
+    numpy.random.default_rng(seed + i), first its n ticks -- distinct integers of [tick_range[0], tick_range[1]), in drawing order --
+    then dv[:, 0:2] ~ U(-amplitude, amplitude) m/s; every other component of dv is zero.  Robot i of a batch of 16 is robot i of a
+    batch of 4096.  -> (ticks [B,n] int64, dv [B,n,30])."""
+    lo, hi = int(tick_range[0]), int(tick_range[1])
+    if hi - lo < n:
+        raise ValueError("tick_range holds fewer than n ticks")
+    ticks = np.zeros((B, n), dtype=np.int64)
+    dv = np.zeros((B, n, 30))
+    for i in range(B):
+        rng = np.random.default_rng(seed + i)
+        ticks[i] = lo + rng.choice(hi - lo, size=n, replace=False)
+        dv[i, :, 0:2] = rng.uniform(-amplitude, amplitude, (n, 2))
+    return ticks, dv
+
+
 __all__ = ["stance_zmp", "find_poly_coeff", "foot_coeff_trajectory", "walk_plan", "jump_plan", "walk_plans", "jump_plans",
+           "push_schedule", "check_push_records", "draw_pushes",
            "PHASE_DOUBLE", "PHASE_RIGHT", "PHASE_LEFT", "PHASE_FLIGHT"]
