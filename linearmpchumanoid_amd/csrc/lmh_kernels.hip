@@ -294,475 +294,7 @@ struct LV {
     __device__ __forceinline__ LRef<R> operator[](int i) const { return LRef<R>{p + i}; }
 };
 
-// Lane exchange inside a 16-lane row through DPP (two 32-bit v_mov_dpp per double, ~10 cycles) instead of
-// ds_bpermute (an LDS round trip per step).  CTRL: 0xB1 = quad_perm[1,0,3,2] (lane ^ 1), 0x4E = quad_perm[2,3,0,1]
-// (lane ^ 2), 0x141 = row_half_mirror, 0x140 = row_mirror.  Needs a full exec mask (wave-uniform control flow).
-template <int CTRL>
-__device__ __forceinline__ double dpp_row(double x)
-{
-    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xf, 0xf, true);
-    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xf, 0xf, true);
-    return __hiloint2double(hi, lo);
-}
-template <int CTRL>
-__device__ __forceinline__ float dpp_row(float x)
-{
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ double read_lane_f64(double x, int l)
-{
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
-}
-// all-reduce over the 64 lanes: four DPP steps leave every lane with its row's total, the four row totals are
-// combined through SGPRs in a fixed order (wave-uniform result)
-__device__ __forceinline__ double wave_sum(double v)
-{
-    v += dpp_row<0xB1>(v); v += dpp_row<0x4E>(v); v += dpp_row<0x141>(v); v += dpp_row<0x140>(v);
-    return (read_lane_f64(v, 0) + read_lane_f64(v, 16)) + (read_lane_f64(v, 32) + read_lane_f64(v, 48));
-}
-__device__ __forceinline__ float wave_sum(float v)
-{
-    v += dpp_row<0xB1>(v); v += dpp_row<0x4E>(v); v += dpp_row<0x141>(v); v += dpp_row<0x140>(v);
-    return (__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)) + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16)))
-         + (__int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)) + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48)));
-}
-__device__ __forceinline__ double wave_max(double v)
-{
-    v = fmax(v, dpp_row<0xB1>(v)); v = fmax(v, dpp_row<0x4E>(v)); v = fmax(v, dpp_row<0x141>(v)); v = fmax(v, dpp_row<0x140>(v));
-    return fmax(fmax(read_lane_f64(v, 0), read_lane_f64(v, 16)), fmax(read_lane_f64(v, 32), read_lane_f64(v, 48)));
-}
-
-__device__ __forceinline__ double fast_rcp(double d)
-{
-    double y = __builtin_amdgcn_rcp(d);            // v_rcp_f64 (~2^-26) + two Newton steps -> full fp64
-    y = fma(fma(-d, y, 1.0), y, y);
-    y = fma(fma(-d, y, 1.0), y, y);
-    return y;
-}
-
-// one Newton step: ~2 ulp.  For the multipliers of a Gauss-Jordan elimination that is as good as the exact quotient (the error is a 1e-16
-// relative perturbation of the row operation; the eliminated column is never read again), and it takes two instructions off the dependent
-// chain pivot -> reciprocal -> multiplier -> update of every pivot.
-__device__ __forceinline__ double fast_rcp1(double d)
-{
-    const double y = __builtin_amdgcn_rcp(d);
-    return fma(fma(-d, y, 1.0), y, y);
-}
-
-__device__ __forceinline__ double bcast_lane(double x, int l)     // l is a compile-time constant after unrolling
-{
-    const int lo = __builtin_amdgcn_readlane(__double2loint(x), l);
-    const int hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
-    return __hiloint2double(hi, lo);
-}
-
-// ---- DPP row broadcast (gfx90a+: 64-bit DPP with row_newbcast): lane l of every 16-lane row reads lane C of
-// its own row.  One instruction, no SGPR round trip (v_readlane needs two per double plus the VALU->SGPR hazard).
-extern "C" __device__ double lmh_update_dpp_f64(double, double, int, int, int, bool) __asm("llvm.amdgcn.update.dpp.f64");
-template <int C>
-__device__ __forceinline__ double bcast16(double x)               // compiler-visible v_mov_b64_dpp (hazards handled by llc)
-{
-    return lmh_update_dpp_f64(x, x, 0x150 + C, 0xf, 0xf, true);
-}
-// acc_k += bcast16<C0 + k>(src) * m for k < K, as ONE asm block of v_fmac_f64_dpp: the leading s_nop covers the
-// "VALU write -> DPP read" hazard on src for whatever the compiler placed before the block; inside the block
-// nothing writes src.  Must run with a full exec mask (wave-uniform control flow only).
-#define LMH_FD(k, s, m, c) "v_fmac_f64_dpp %" #k ", %" #s ", %" #m " row_newbcast:%" #c " row_mask:0xf bank_mask:0xf\n\t"
-template <int A0, int B0, int K, int N>
-__device__ __forceinline__ void dpp_fmac_cols(double (&a)[N], double src, double m)    // a[A0 + k] += bcast16<B0 + k>(src) * m
-{
-    static_assert(K == 1 || K == 2 || K == 4 || K == 8, "chunk size");
-    constexpr int C0 = A0;
-    if constexpr (K == 8)
-        asm volatile("s_nop 1\n\t" LMH_FD(0, 8, 9, 10) LMH_FD(1, 8, 9, 11) LMH_FD(2, 8, 9, 12) LMH_FD(3, 8, 9, 13)
-                     LMH_FD(4, 8, 9, 14) LMH_FD(5, 8, 9, 15) LMH_FD(6, 8, 9, 16) LMH_FD(7, 8, 9, 17)
-                     : "+v"(a[C0]), "+v"(a[C0 + 1]), "+v"(a[C0 + 2]), "+v"(a[C0 + 3]), "+v"(a[C0 + 4]), "+v"(a[C0 + 5]), "+v"(a[C0 + 6]), "+v"(a[C0 + 7])
-                     : "v"(src), "v"(m), "n"(B0), "n"(B0 + 1), "n"(B0 + 2), "n"(B0 + 3), "n"(B0 + 4), "n"(B0 + 5), "n"(B0 + 6), "n"(B0 + 7));
-    else if constexpr (K == 4)
-        asm volatile("s_nop 1\n\t" LMH_FD(0, 4, 5, 6) LMH_FD(1, 4, 5, 7) LMH_FD(2, 4, 5, 8) LMH_FD(3, 4, 5, 9)
-                     : "+v"(a[C0]), "+v"(a[C0 + 1]), "+v"(a[C0 + 2]), "+v"(a[C0 + 3])
-                     : "v"(src), "v"(m), "n"(B0), "n"(B0 + 1), "n"(B0 + 2), "n"(B0 + 3));
-    else if constexpr (K == 2)
-        asm volatile("s_nop 1\n\t" LMH_FD(0, 2, 3, 4) LMH_FD(1, 2, 3, 5)
-                     : "+v"(a[C0]), "+v"(a[C0 + 1]) : "v"(src), "v"(m), "n"(B0), "n"(B0 + 1));
-    else
-        asm volatile("s_nop 1\n\t" LMH_FD(0, 1, 2, 3) : "+v"(a[C0]) : "v"(src), "v"(m), "n"(B0));
-}
-// a[c] += bcast16<c>(src) * m for c in [C0, N)
-template <int C0, int N>
-__device__ __forceinline__ void dpp_fmac_tail(double (&a)[N], double src, double m)
-{
-    constexpr int R = N - C0;
-    if constexpr (R >= 8) { dpp_fmac_cols<C0, C0, 8>(a, src, m); dpp_fmac_tail<C0 + 8>(a, src, m); }
-    else if constexpr (R >= 4) { dpp_fmac_cols<C0, C0, 4>(a, src, m); dpp_fmac_tail<C0 + 4>(a, src, m); }
-    else if constexpr (R >= 2) { dpp_fmac_cols<C0, C0, 2>(a, src, m); dpp_fmac_tail<C0 + 2>(a, src, m); }
-    else if constexpr (R == 1) { dpp_fmac_cols<C0, C0, 1>(a, src, m); }
-}
-// a[A0 + k] += bcast16<B0 + k>(src) * m for k < CNT
-template <int A0, int B0, int CNT, int N>
-__device__ __forceinline__ void dpp_fmac_range(double (&a)[N], double src, double m)
-{
-    if constexpr (CNT >= 8) { dpp_fmac_cols<A0, B0, 8>(a, src, m); dpp_fmac_range<A0 + 8, B0 + 8, CNT - 8>(a, src, m); }
-    else if constexpr (CNT >= 4) { dpp_fmac_cols<A0, B0, 4>(a, src, m); dpp_fmac_range<A0 + 4, B0 + 4, CNT - 4>(a, src, m); }
-    else if constexpr (CNT >= 2) { dpp_fmac_cols<A0, B0, 2>(a, src, m); dpp_fmac_range<A0 + 2, B0 + 2, CNT - 2>(a, src, m); }
-    else if constexpr (CNT == 1) { dpp_fmac_cols<A0, B0, 1>(a, src, m); }
-}
-// acc += bcast16<J>(src) * m (acc and src may be the same register)
-template <int J>
-__device__ __forceinline__ void dpp_fmac_one(double &acc, double src, double m)
-{
-    asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(m), "n"(J));
-}
-// b[r] += bcast16<J>(b[r]) * m for r < M (each right-hand side broadcasts its own lane-J entry)
-#define LMH_FS(k, m, c) "v_fmac_f64_dpp %" #k ", %" #k ", %" #m " row_newbcast:%" #c " row_mask:0xf bank_mask:0xf\n\t"
-template <int J, int M>
-__device__ __forceinline__ void dpp_fmac_rhs(double (&b)[M], double m)
-{
-    static_assert(M == 1 || M == 6 || M == 7, "right-hand-side counts in use");
-    if constexpr (M == 1)
-        asm volatile("s_nop 1\n\t" LMH_FS(0, 1, 2) : "+v"(b[0]) : "v"(m), "n"(J));
-    else if constexpr (M == 6)
-        asm volatile("s_nop 1\n\t" LMH_FS(0, 6, 7) LMH_FS(1, 6, 7) LMH_FS(2, 6, 7) LMH_FS(3, 6, 7) LMH_FS(4, 6, 7) LMH_FS(5, 6, 7)
-                     : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]) : "v"(m), "n"(J));
-    else
-        asm volatile("s_nop 1\n\t" LMH_FS(0, 7, 8) LMH_FS(1, 7, 8) LMH_FS(2, 7, 8) LMH_FS(3, 7, 8) LMH_FS(4, 7, 8) LMH_FS(5, 7, 8) LMH_FS(6, 7, 8)
-                     : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]) : "v"(m), "n"(J));
-}
-
-// One pivot of the row-per-lane LDL' for N <= 16 (all rows inside DPP row 0), then the next (compile-time recursion).
-// `dadd`: a constant on the diagonal of the matrix, added where the pivot is read (the diagonal entry is touched nowhere else: lane J's own
-// column entry is only ever used through this broadcast), so that the caller does not have to place it with a select per column.
-template <int J, int N, int M>
-__device__ __forceinline__ void ldl16_forward(double (&a)[N], double (&b)[M], unsigned live, int lane, int &bad, double &myinv, double dadd = 0.0)
-{
-    if constexpr (J < N) {
-        if ((live >> J) & 1u) {                                   // wave-uniform
-            // (DPP rows 1..3 hold no matrix rows: whatever they compute -- possibly non-finite -- stays in their lanes; `bad` is read from lane 0)
-            const double d = bcast16<J>(a[J]) + dadd;
-            if (!(d > 0.0)) bad = 1;
-            const double invd = fast_rcp(d);
-            const double f = a[J] * invd;                         // L_iJ in lanes i > J
-            const double nfm = (lane > J) ? -f : 0.0;
-            if (lane == J) myinv = invd;
-            dpp_fmac_tail<J + 1>(a, a[J], -f);                    // a[c] -= f * (d_J L_cJ held by lane c)
-            dpp_fmac_rhs<J>(b, nfm);                              // forward substitution
-            a[J] = f;                                             // (rows <= J keep a don't-care there: only L_iJ, i > J, is read back)
-        }
-        ldl16_forward<J + 1>(a, b, live, lane, bad, myinv, dadd);
-    }
-}
-template <int J, int N, int M>
-__device__ __forceinline__ void ldl16_backward(double (&b)[M], unsigned live, int lane, const double *Ls)
-{
-    if constexpr (J > 0) {
-        if ((live >> J) & 1u) {
-            const double lv = Ls[J * (N + 1) + ((lane < N) ? lane : 0)];      // unconditional load (clamped), masked by value: no exec branch
-            const double nl = (lane < J) ? -lv : 0.0;
-            dpp_fmac_rhs<J>(b, nl);
-        }
-        ldl16_backward<J - 1, N>(b, live, lane, Ls);
-    }
-}
-
-// ---- 16 < N <= 32, one right-hand side: TWO matrix rows per lane so that every row lives in DPP row 0 and the
-// pivot broadcast is again a row_newbcast.  Lane i < 16 holds row i in a0[0..15] and row 16 + i in a1[0..N-1]
-// (lower triangles), rhs entries b0 / b1.  Pivot J < 16: the scaled pivot column sits in a0[J] (rows < 16, lane c)
-// and a1[J] (rows >= 16, lane c - 16); pivot J >= 16: in a1[J].
-template <int J, int N2>
-__device__ __forceinline__ void ldl2_forward(double (&a0)[16], double (&a1)[16 + N2], double &b0, double &b1, unsigned live, int lane,
-                                             int &bad, double &inv0, double &inv1)
-{
-    constexpr int N = 16 + N2;
-    if constexpr (J < N) {
-        if ((live >> J) & 1u) {                                   // wave-uniform
-            if constexpr (J < 16) {
-                double d = bcast16<J>(a0[J]);
-                d = (lane < 16) ? d : 1.0;
-                if (!(d > 0.0)) bad = 1;
-                const double invd = fast_rcp(d);
-                const double f0 = a0[J] * invd, f1 = a1[J] * invd;     // L_iJ (rows < 16, valid for lane > J) | L_(16+i)J
-                const double nfm0 = (lane > J) ? -f0 : 0.0;
-                if (lane == J) inv0 = invd;
-                dpp_fmac_range<J + 1, J + 1, 15 - J>(a0, a0[J], -f0);  // columns J+1..15: lane c holds d_J L_cJ in a0[J]
-                dpp_fmac_range<J + 1, J + 1, 15 - J>(a1, a0[J], -f1);
-                dpp_fmac_range<16, 0, N2>(a1, a1[J], -f1);             // columns 16..N-1: lane c - 16 holds d_J L_cJ in a1[J]
-                dpp_fmac_one<J>(b1, b0, -f1);                          // forward substitution (lane J's b0 is z_J, untouched below)
-                dpp_fmac_one<J>(b0, b0, nfm0);
-                if (lane > J) a0[J] = f0;
-                a1[J] = f1;
-            } else {
-                constexpr int Jp = J - 16;
-                double d = bcast16<Jp>(a1[J]);
-                d = (lane < 16) ? d : 1.0;
-                if (!(d > 0.0)) bad = 1;
-                const double invd = fast_rcp(d);
-                const double f1 = a1[J] * invd;
-                const double nfm1 = (lane > Jp) ? -f1 : 0.0;
-                if (lane == Jp) inv1 = invd;
-                dpp_fmac_range<J + 1, Jp + 1, N - 1 - J>(a1, a1[J], -f1);
-                dpp_fmac_one<Jp>(b1, b1, nfm1);
-                if (lane > Jp) a1[J] = f1;
-            }
-        }
-        ldl2_forward<J + 1, N2>(a0, a1, b0, b1, live, lane, bad, inv0, inv1);
-    }
-}
-template <int J, int N2>
-__device__ __forceinline__ void ldl2_backward(double &b0, double &b1, unsigned live, int lane, const double *Ls)
-{
-    constexpr int N = 16 + N2;
-    if constexpr (J > 0) {
-        if ((live >> J) & 1u) {
-            const int l16 = (lane < 16) ? lane : 0;                // lanes outside DPP row 0 read a valid address
-            if constexpr (J >= 16) {
-                constexpr int Jp = J - 16;
-                const double l0 = (lane < 16) ? Ls[J * (N + 1) + l16] : 0.0;             // L[J][lane], rows < 16
-                const double l1 = (lane < Jp) ? Ls[J * (N + 1) + 16 + l16] : 0.0;        // L[J][16 + lane], rows 16 .. J-1
-                dpp_fmac_one<Jp>(b0, b1, -l0);
-                dpp_fmac_one<Jp>(b1, b1, -l1);
-            } else {
-                const double l0 = (lane < J) ? Ls[J * (N + 1) + l16] : 0.0;
-                dpp_fmac_one<J>(b0, b0, -l0);
-            }
-        }
-        ldl2_backward<J - 1, N2>(b0, b1, live, lane, Ls);
-    }
-}
-// On exit b0 of lane i < 16 holds x_i and b1 holds x_(16+i).  Returns non-zero (wave-uniform) if a pivot was not positive.
-template <int N2>
-__device__ __forceinline__ int ldl2_solve_regs(double (&a0)[16], double (&a1)[16 + N2], double &b0, double &b1, unsigned live, double *Ls)
-{
-    constexpr int N = 16 + N2;
-    const int lane = LANE;
-    int bad = 0;
-    double inv0 = 0.0, inv1 = 0.0;
-    ldl2_forward<0, N2>(a0, a1, b0, b1, live, lane, bad, inv0, inv1);
-    bad = __builtin_amdgcn_readfirstlane(bad);
-    b0 *= inv0; b1 *= inv1;                                       // w = D^-1 z
-    WSYNC();
-    if (lane < 16) {
-#pragma unroll
-        for (int c = 0; c < 15; c++) Ls[lane * (N + 1) + c] = a0[c];                 // L[lane][c], c < lane
-    }
-    if (lane < N2) {
-#pragma unroll
-        for (int c = 0; c < N - 1; c++) Ls[(16 + lane) * (N + 1) + c] = a1[c];       // L[16 + lane][c], c < 16 + lane
-    }
-    WSYNC();
-    ldl2_backward<N - 1, N2>(b0, b1, live, lane, Ls);
-    return bad;
-}
-
-// Register-resident LDL' solve of an SPD system with M right-hand sides, N <= 32.
-// Lane i < N holds row i of the matrix in a[] (entries a[c], c <= i, are used; rows / columns whose
-// bit is clear in `live` must be zero and are skipped) and its rhs entries in b[].  The pivot column
-// is broadcast lane to lane (DPP row broadcast for N <= 16, v_readlane above; no LDS round trip inside the
-// factorisation); the rows of L are parked once in Ls (row stride N+1, conflict free) for the backward
-// substitution.  On exit b[r] of lane i holds x_i.  Returns non-zero (wave-uniform) if a pivot was not positive.
-template <int N, int M>
-__device__ __forceinline__ int ldl_solve_regs(double (&a)[N], double (&b)[M], unsigned live, double *Ls, double dadd = 0.0)
-{
-    const int lane = LANE;
-    int bad = 0;
-    double myinv = 0.0;                                           // 1 / d_lane (0 on rows that are not live)
-    if constexpr (N <= 16) {
-        WSTAMP(40);
-        ldl16_forward<0>(a, b, live, lane, bad, myinv, dadd);
-        bad = __builtin_amdgcn_readfirstlane(bad);
-#pragma unroll
-        for (int r = 0; r < M; r++) b[r] *= myinv;                // w = D^-1 z
-        WSTAMP(41);
-        WSYNC();
-        if (lane < N) {
-#pragma unroll
-            for (int c = 0; c < N - 1; c++) Ls[lane * (N + 1) + c] = a[c];          // L[lane][c], c < lane
-        }
-        WSYNC();
-        WSTAMP(42);
-        ldl16_backward<N - 1, N>(b, live, lane, Ls);
-        WSTAMP(43);
-        return bad;
-    }
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        if (!((live >> j) & 1u)) continue;                        // wave-uniform
-        const double d = bcast_lane(a[j], j);
-        if (!(d > 0.0)) bad = 1;
-        const double invd = fast_rcp(d);
-        const double f = a[j] * invd;                             // L_ij in lanes i > j
-        const double fm = (lane > j) ? f : 0.0;
-        if (lane == j) myinv = invd;
-#pragma unroll
-        for (int c = j + 1; c < N; c++) a[c] = fma(-f, bcast_lane(a[j], c), a[c]);   // lane c still holds d_j L_cj
-#pragma unroll
-        for (int r = 0; r < M; r++) b[r] = fma(-fm, bcast_lane(b[r], j), b[r]);      // forward substitution
-        if (lane > j) a[j] = f;
-    }
-#pragma unroll
-    for (int r = 0; r < M; r++) b[r] *= myinv;                    // w = D^-1 z
-    WSYNC();
-    if (lane < N) {
-#pragma unroll
-        for (int c = 0; c < N - 1; c++) Ls[lane * (N + 1) + c] = a[c];              // L[lane][c], c < lane
-    }
-    WSYNC();
-#pragma unroll
-    for (int j = N - 1; j > 0; j--) {
-        if (!((live >> j) & 1u)) continue;
-        const double lji = (lane < j) ? Ls[j * (N + 1) + lane] : 0.0;
-#pragma unroll
-        for (int r = 0; r < M; r++) b[r] = fma(-lji, bcast_lane(b[r], j), b[r]);
-    }
-    return bad;
-}
-
-// ---- Gauss-Jordan form of the register-resident SPD solve for N <= 16 (the well-conditioned systems of the QP set-up: Woodbury core,
-// Schur complement, push-through system, K_f).  Lane i < N holds the FULL row i in a[]; pivot J eliminates column J from every other
-// row, rows above the pivot included: a[c] += bcast16<J>(a[c]) * nf, b[r] += bcast16<J>(b[r]) * nf with nf = -a_iJ / d_J (0 on row J) --
-// every register broadcasts its own lane-J entry, one v_fmac_f64_dpp each.  The instruction count per pivot equals the LDL' forward
-// step's, and there is no backward substitution, no L parked in LDS and no fence: x_i = b_i / d_i at the end.  Without pivoting this is
-// as accurate as LDL' on an SPD matrix (measured on the Woodbury core: 7e-14 both, condition 1e4).
-#define LMH_GS8(J) LMH_FS(0, 8, 9) LMH_FS(1, 8, 9) LMH_FS(2, 8, 9) LMH_FS(3, 8, 9) LMH_FS(4, 8, 9) LMH_FS(5, 8, 9) LMH_FS(6, 8, 9) LMH_FS(7, 8, 9)
-template <int C0, int CNT, int J, int N>
-__device__ __forceinline__ void dpp_fmac_self(double (&a)[N], double m)         // a[c] += bcast16<J>(a[c]) * m for c in [C0, C0 + CNT)
-{
-    if constexpr (CNT >= 8) {
-        asm volatile("s_nop 1\n\t" LMH_GS8(J)
-                     : "+v"(a[C0]), "+v"(a[C0 + 1]), "+v"(a[C0 + 2]), "+v"(a[C0 + 3]), "+v"(a[C0 + 4]), "+v"(a[C0 + 5]), "+v"(a[C0 + 6]), "+v"(a[C0 + 7])
-                     : "v"(m), "n"(J));
-        dpp_fmac_self<C0 + 8, CNT - 8, J>(a, m);
-    } else if constexpr (CNT == 7) {
-        asm volatile("s_nop 1\n\t" LMH_FS(0, 7, 8) LMH_FS(1, 7, 8) LMH_FS(2, 7, 8) LMH_FS(3, 7, 8) LMH_FS(4, 7, 8) LMH_FS(5, 7, 8) LMH_FS(6, 7, 8)
-                     : "+v"(a[C0]), "+v"(a[C0 + 1]), "+v"(a[C0 + 2]), "+v"(a[C0 + 3]), "+v"(a[C0 + 4]), "+v"(a[C0 + 5]), "+v"(a[C0 + 6]) : "v"(m), "n"(J));
-    } else if constexpr (CNT == 6) {
-        asm volatile("s_nop 1\n\t" LMH_FS(0, 6, 7) LMH_FS(1, 6, 7) LMH_FS(2, 6, 7) LMH_FS(3, 6, 7) LMH_FS(4, 6, 7) LMH_FS(5, 6, 7)
-                     : "+v"(a[C0]), "+v"(a[C0 + 1]), "+v"(a[C0 + 2]), "+v"(a[C0 + 3]), "+v"(a[C0 + 4]), "+v"(a[C0 + 5]) : "v"(m), "n"(J));
-    } else if constexpr (CNT == 5) {
-        asm volatile("s_nop 1\n\t" LMH_FS(0, 5, 6) LMH_FS(1, 5, 6) LMH_FS(2, 5, 6) LMH_FS(3, 5, 6) LMH_FS(4, 5, 6)
-                     : "+v"(a[C0]), "+v"(a[C0 + 1]), "+v"(a[C0 + 2]), "+v"(a[C0 + 3]), "+v"(a[C0 + 4]) : "v"(m), "n"(J));
-    } else if constexpr (CNT == 4) {
-        asm volatile("s_nop 1\n\t" LMH_FS(0, 4, 5) LMH_FS(1, 4, 5) LMH_FS(2, 4, 5) LMH_FS(3, 4, 5)
-                     : "+v"(a[C0]), "+v"(a[C0 + 1]), "+v"(a[C0 + 2]), "+v"(a[C0 + 3]) : "v"(m), "n"(J));
-    } else if constexpr (CNT == 3) {
-        asm volatile("s_nop 1\n\t" LMH_FS(0, 3, 4) LMH_FS(1, 3, 4) LMH_FS(2, 3, 4) : "+v"(a[C0]), "+v"(a[C0 + 1]), "+v"(a[C0 + 2]) : "v"(m), "n"(J));
-    } else if constexpr (CNT == 2) {
-        asm volatile("s_nop 1\n\t" LMH_FS(0, 2, 3) LMH_FS(1, 2, 3) : "+v"(a[C0]), "+v"(a[C0 + 1]) : "v"(m), "n"(J));
-    } else if constexpr (CNT == 1) {
-        asm volatile("s_nop 1\n\t" LMH_FS(0, 1, 2) : "+v"(a[C0]) : "v"(m), "n"(J));
-    }
-}
-#define LMH_DPP1(k) "v_fmac_f64_dpp %0, %1, %2 row_newbcast:" #k " row_mask:0xf bank_mask:0xf"
-// NOP = false: `src` was not written by the instruction before (a DPP operand needs two wait states behind the VALU write of its register, and
-// the compiler does not look inside the asm): the later members of a chain on the same `src`
-template <int C, bool NOP = true>
-__device__ __forceinline__ void dpp_fmac_lane(double &acc, double src, double m)     // acc += lane_C(src) * m   (C < 16, own 16-lane row)
-{
-    if constexpr (NOP) asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(m), "n"(C));
-    else asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(acc) : "v"(src), "v"(m), "n"(C));
-}
-// Dot products of a lane's row with the entries lanes 0..11 of its own 16-lane row hold, each a whole chain in ONE asm statement: the
-// leading s_nop 1 covers the "VALU write -> DPP read" hazard on `src` for whatever the compiler placed before it, and nothing inside writes
-// `src`.  Terms accumulate in k order with fused multiply-adds (the order and form of a plain `acc += m[k] * x[k]` loop).  Full exec mask
-// (wave-uniform control flow) only.
-#define LMH_DPM(d, s, m, c) "v_fmac_f64_dpp %" #d ", %" #s ", %" #m " row_newbcast:" #c " row_mask:0xf bank_mask:0xf\n\t"
-// r += sum_k lane_k(src) m[k], l += sum_k lane_(6 + k)(src) m[k] (k < 6): one foot's six entries each, interleaved
-__device__ __forceinline__ void dpp_dot6x2(double &r, double &l, double src, const double (&m)[6])
-{
-    asm volatile("s_nop 1\n\t" LMH_DPM(0, 2, 3, 0) LMH_DPM(1, 2, 3, 6) LMH_DPM(0, 2, 4, 1) LMH_DPM(1, 2, 4, 7) LMH_DPM(0, 2, 5, 2) LMH_DPM(1, 2, 5, 8)
-                 LMH_DPM(0, 2, 6, 3) LMH_DPM(1, 2, 6, 9) LMH_DPM(0, 2, 7, 4) LMH_DPM(1, 2, 7, 10) LMH_DPM(0, 2, 8, 5) LMH_DPM(1, 2, 8, 11)
-                 : "+v"(r), "+v"(l) : "v"(src), "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(m[4]), "v"(m[5]));
-}
-// acc += sum_k lane_k(src) m[k] (k < 12)
-__device__ __forceinline__ void dpp_dot12(double &acc, double src, const double (&m)[12])
-{
-    asm volatile("s_nop 1\n\t" LMH_DPM(0, 1, 2, 0) LMH_DPM(0, 1, 3, 1) LMH_DPM(0, 1, 4, 2) LMH_DPM(0, 1, 5, 3) LMH_DPM(0, 1, 6, 4) LMH_DPM(0, 1, 7, 5)
-                 LMH_DPM(0, 1, 8, 6) LMH_DPM(0, 1, 9, 7) LMH_DPM(0, 1, 10, 8) LMH_DPM(0, 1, 11, 9) LMH_DPM(0, 1, 12, 10) LMH_DPM(0, 1, 13, 11)
-                 : "+v"(acc) : "v"(src), "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(m[4]), "v"(m[5]),
-                   "v"(m[6]), "v"(m[7]), "v"(m[8]), "v"(m[9]), "v"(m[10]), "v"(m[11]));
-}
-// one pivot, then the next.  GUARD = true: `rowon` switches a whole 16-lane DPP row off (its pivots are replaced by 1) and a pivot that is
-// not above `dmin` is replaced by 1 and reported in `bad` (kinv_compute: each foot on two DPP rows, a rank-deficient K_f is an expected
-// outcome).  GUARD = false (gj_solve_regs): every DPP row carries a copy of the system, so the pivot a lane sees is always the true one --
-// no guard selects, no test per pivot: lane J keeps 1 / d_J, and the caller looks at the signs once at the end.
-template <int J, int N, int M, bool GUARD = true>
-__device__ __forceinline__ void gj16_step(double (&a)[N], double (&b)[M], unsigned live, int l16, bool rowon, double dmin, int &bad, double &myinv)
-{
-    if constexpr (J < N) {
-        if ((live >> J) & 1u) {                                   // wave-uniform
-            double d = bcast16<J>(a[J]);
-            if constexpr (GUARD) {
-                if (rowon && !(d > dmin)) bad = 1;
-                d = (rowon && d > dmin) ? d : 1.0;
-            }
-            const double invd = fast_rcp1(d);
-            const bool piv = l16 == J;
-            const double nf = piv ? 0.0 : -(a[J] * invd);
-            myinv = piv ? invd : myinv;
-            dpp_fmac_self<J + 1, N - 1 - J, J>(a, nf);
-            dpp_fmac_self<0, M, J>(b, nf);
-        }
-        gj16_step<J + 1, N, M, GUARD>(a, b, live, l16, rowon, dmin, bad, myinv);
-    }
-}
-// (-DLMH_GJ_PIPE only; measured and not shipped: wave 0's chain gets shorter, but the extra wait states it takes are issue slots the SIMD's
-// other wave -- another robot's helper -- no longer gets, and the kernel's throughput follows the SIMD's total instruction count:
-// 16.36 -> 16.00 M ticks/s on config 3.)
-// The guard-free form, software-pipelined: the reciprocal of pivot J + 1 -- broadcast, v_rcp_f64, one Newton step: ~100 cycles of dependent
-// latency, the longest link of a pivot's chain -- needs column J + 1 of pivot J's update only, so that column is updated by its own asm
-// statement, the reciprocal chain starts, and the block of the other columns and the right-hand sides issues inside its latency
-// (with all of a pivot's updates in one asm statement the chain could only start behind the block: a 15 x 15 solve with 7 right-hand
-// sides spent 21..7 issue slots per pivot that way).  `invd`: 1 / d_J handed over by pivot J - 1 (`have`: it is; wave-uniform).
-template <int J, int N, int M>
-__device__ __forceinline__ void gj16_pipe(double (&a)[N], double (&b)[M], unsigned live, int l16, double &myinv, double invd, bool have)
-{
-    if constexpr (J < N) {
-        bool have_next = false;
-        double invn = 0.0;
-        if ((live >> J) & 1u) {                                   // wave-uniform
-            if (!have) invd = fast_rcp1(bcast16<J>(a[J]));         // (first live pivot, or the one before was not live)
-            const bool piv = l16 == J;
-            const double nf = piv ? 0.0 : -(a[J] * invd);
-            myinv = piv ? invd : myinv;
-            if constexpr (J + 1 < N) {
-                // column J + 1, then straight away the broadcast of the next pivot and its v_rcp_f64 -- inside ONE asm statement: the compiler's
-                // scheduler sees no latency in an asm and had moved a separately written reciprocal behind the block of the other columns
-                double dn, rn;
-                asm volatile("s_nop 1\n\tv_fmac_f64_dpp %0, %0, %3 row_newbcast:%4 row_mask:0xf bank_mask:0xf\n\ts_nop 1\n\t"
-                             "v_mov_b64_dpp %1, %0 row_newbcast:%5 row_mask:0xf bank_mask:0xf\n\tv_rcp_f64_e32 %2, %1"
-                             : "+v"(a[J + 1]), "=&v"(dn), "=&v"(rn) : "v"(nf), "n"(J), "n"(J + 1));
-                dpp_fmac_self<J + 2, N - 2 - J, J>(a, nf);
-                dpp_fmac_self<0, M, J>(b, nf);
-                asm volatile("" : "+v"(dn), "+v"(rn));             // the Newton step stays behind the blocks
-                invn = fma(fma(-dn, rn, 1.0), rn, rn);
-                have_next = ((live >> (J + 1)) & 1u) != 0u;
-            } else dpp_fmac_self<0, M, J>(b, nf);
-        }
-        gj16_pipe<J + 1, N, M>(a, b, live, l16, myinv, invn, have_next);
-    }
-}
-// Lane l holds row l & 15 of the system (rows >= N: any finite copy, e.g. row 0 -- they are eliminated like every other row and never read):
-// all four 16-lane DPP rows then run the same elimination.  The right-hand sides need not be the same in every DPP row: b[r] is updated
-// from the lane-J entry of its own row only, so a caller can give each DPP row its own slice of the columns (M per row) and every column
-// sees the same fused multiply-adds in the same order as in a full copy.  On exit b[r] of lane i < N holds x_i.  Returns non-zero
-// (wave-uniform) if a pivot was not positive (d_i > 0 <=> 0 < 1 / d_i < inf on the lane that kept it; the caller flags LMH_FLAG_NOT_SPD,
-// and the non-finite values that follow a bad pivot are flagged LMH_FLAG_NONFINITE by the evaluation's own check).
-template <int N, int M>
-__device__ __forceinline__ int gj_solve_regs(double (&a)[N], double (&b)[M], unsigned live)
-{
-    static_assert(N <= 16, "one DPP row");
-    const int l16 = LANE & 15;
-    int bad = 0;
-    double myinv = 0.0;
-#ifdef LMH_GJ_PIPE                                                  // experiment switch: the software-pipelined pivots (gj16_pipe): measured -2.2 %
-    gj16_pipe<0, N, M>(a, b, live, l16, myinv, 0.0, false);
-#else
-    gj16_step<0, N, M, false>(a, b, live, l16, true, 0.0, bad, myinv);
-#endif
-#pragma unroll
-    for (int r = 0; r < M; r++) b[r] *= myinv;
-    const bool pivot_lane = ((live >> l16) & 1u) != 0u;            // (bits >= N of `live` are clear)
-    return (__ballot(pivot_lane && !(myinv > 0.0 && myinv <= 1.7976931348623157e308)) != 0ull) ? 1 : 0;
-}
+#include "lmh_dpp.h"          // DPP lane primitives, broadcast-FMA chains, register LDL' / Gauss-Jordan solves
 
 
 // ------------------------------------------------------------------ fp64 matrix-core tiles
@@ -929,25 +461,7 @@ __device__ __forceinline__ void phase_fk(LV<R> L, const LV<R> lcoef, R qn = (R)0
 // "Multiply by X" is then six v_fmac_f64_dpp with row_newbcast (lane k of the own row supplies component k) -- no LDS round trip per
 // level, no index arithmetic: the coefficients come from the full 6 x 6 images A_XF of X_i = [A 0; B A] (row r contiguous, column r at
 // stride 6, the zero block stored), addressed as (per-lane base) + (compile-time offset of the level).
-// acc += sum_k lane_k(src) * m_k, k = 0..5; needs a full exec mask (wave-uniform control flow).
-// NOP (default): `src` may have been written by the VALU instruction right in front of the block -- the compiler is free to place the
-// instruction that produces an operand there, "VALU write -> DPP read" needs two wait states, and the hazard recognizer does not look
-// into inline asm.  NOP = false only where the source is the accumulator of an earlier block with other blocks in between.
-#define LMH_BD6(op) op " %0, %1, %2 row_newbcast:0 row_mask:0xf bank_mask:0xf\n\t" op " %0, %1, %3 row_newbcast:1 row_mask:0xf bank_mask:0xf\n\t" \
-                    op " %0, %1, %4 row_newbcast:2 row_mask:0xf bank_mask:0xf\n\t" op " %0, %1, %5 row_newbcast:3 row_mask:0xf bank_mask:0xf\n\t" \
-                    op " %0, %1, %6 row_newbcast:4 row_mask:0xf bank_mask:0xf\n\t" op " %0, %1, %7 row_newbcast:5 row_mask:0xf bank_mask:0xf"
-template <bool NOP = true>
-__device__ __forceinline__ void bdot6(double &acc, double src, const double (&m)[6])
-{
-    if constexpr (NOP) asm volatile("s_nop 1\n\t" LMH_BD6("v_fmac_f64_dpp") : "+v"(acc) : "v"(src), "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(m[4]), "v"(m[5]));
-    else asm volatile(LMH_BD6("v_fmac_f64_dpp") : "+v"(acc) : "v"(src), "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(m[4]), "v"(m[5]));
-}
-template <bool NOP = true>
-__device__ __forceinline__ void bdot6(float &acc, float src, const float (&m)[6])
-{
-    if constexpr (NOP) asm volatile("s_nop 1\n\t" LMH_BD6("v_fmac_f32_dpp") : "+v"(acc) : "v"(src), "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(m[4]), "v"(m[5]));
-    else asm volatile(LMH_BD6("v_fmac_f32_dpp") : "+v"(acc) : "v"(src), "v"(m[0]), "v"(m[1]), "v"(m[2]), "v"(m[3]), "v"(m[4]), "v"(m[5]));
-}
+// The six-term chain is bdot6 (lmh_dpp.h).
 // Exec-masked LDS stores (s_and_saveexec / ds_write / s_or) cost ~28 cycles each; a store whose address is switched to a dump slot for
 // the lanes that have nothing to write costs one v_cndmask more than a plain one.
 #define P_DUMP (P_TIME + 5)        // never read
@@ -1871,10 +1385,7 @@ __device__ __forceinline__ int refs_chain_a(double *L, LmhCParams &P, int inst, 
     o[c0] = ag0; o[c1] = ag1;                                       // (lanes 14, 15 repeat their first entry)
     const double part = ag0 * v0 + ag1 * v1, one = 1.0;
     double s0 = 0.0, s1 = 0.0;
-    dpp_fmac_lane<0>(s0, part, one); dpp_fmac_lane<1, false>(s1, part, one); dpp_fmac_lane<2, false>(s0, part, one); dpp_fmac_lane<3, false>(s1, part, one);
-    dpp_fmac_lane<4, false>(s0, part, one); dpp_fmac_lane<5, false>(s1, part, one); dpp_fmac_lane<6, false>(s0, part, one); dpp_fmac_lane<7, false>(s1, part, one);
-    dpp_fmac_lane<8, false>(s0, part, one); dpp_fmac_lane<9, false>(s1, part, one); dpp_fmac_lane<10, false>(s0, part, one); dpp_fmac_lane<11, false>(s1, part, one);
-    dpp_fmac_lane<12, false>(s0, part, one); dpp_fmac_lane<13, false>(s1, part, one); dpp_fmac_lane<14, false>(s0, part, one); dpp_fmac_lane<15, false>(s1, part, one);
+    dpp_sum16_alt(s0, s1, part, one);
     const double cv = (s0 + s1) / mass;                             // CoM velocity, component a, on every lane of row a
     const double vxp = readlane_f64(cv, 0), vyp = readlane_f64(cv, 16), vzp = readlane_f64(cv, 32);
     int flags = 0;
@@ -2201,10 +1712,8 @@ __device__ __forceinline__ int solve_free_set(double *L, unsigned F, double eps,
 // 16-lane row), then lam_j = g_j . (W w - h) of the coefficient's foot: one LDS hand-over instead of four.
 // Returns like solve_free_set: z_j for lane j in F (0 otherwise), lam_j for lanes j < 32 outside F.
 // MODE 0: every free coefficient belongs to the right foot, 1: to the left foot (single support: the usual thin set), 2: mixed
-// NT = 8 | 16 rows.  NT = 16 is the double-support set right after a touch-down: both feet press on one edge of their polygons (two vertices,
-// 4 + 4 rays each: F = 0f0f0f0f for ~130 of the 200 ticks of every double-support phase of the walking workload, scripts/route_probe.py); each
-// foot's K_f = G_F G_F' then has rank 5, the push-through route does not apply, and the |F| x |F| solve through the LDS image took 16.8k
-// cycles of such an evaluation (profiles/r04_prod_timeline.txt).
+// NT = 8 rows.  (The double-support set right after a touch-down, F = 0f0f0f0f with rank-5 K_f, has 16: a 16-row form of this solve was
+// measured no faster than the general route and removed; the edge-contact push-through takes that set.)
 // The set bits of F are walked with a scalar mask (no index array held in scalar registers across the solve).
 template <int NT, int C, int MODE>
 __device__ __forceinline__ void thin_cols(double *L, int nF, unsigned m, const double (&uR)[6], const double (&uL)[6], double (&a)[NT])
@@ -2234,14 +1743,14 @@ __device__ __forceinline__ void thin_wrench(double *L, int nF, unsigned m, doubl
             const int j = __builtin_amdgcn_readfirstlane(__builtin_ctz(m));
             const bool match = ((j >> 4) != 0) == leftlane;        // the coefficient pushes on this lane's foot
             const double gv = L[P_GCOL + 6 * (j & 15) + kk];       // (no zero slot of the set-up scratch survives the cone phase: select on the value)
-            dpp_fmac_lane<C>(wz, z, match ? gv : 0.0);
+            dpp_fmac_one<C>(wz, z, match ? gv : 0.0);
         }
         thin_wrench<NT, C + 1>(L, nF, m & (m - 1u), z, kk, leftlane, wz);
     }
 }
-template <int NT>
 __device__ __forceinline__ int solve_free_set_thin(double *L, unsigned F_in, double eps, double *z_out, double *lam_out)
 {
+    constexpr int NT = 8;
     const int lane = LANE;
     const unsigned F = (unsigned)__builtin_amdgcn_readfirstlane((int)F_in);       // wave-uniform by construction (ballots); make it a scalar
     const int nF = __popc(F);
@@ -2271,12 +1780,9 @@ __device__ __forceinline__ int solve_free_set_thin(double *L, unsigned F_in, dou
         }
     }
     double a[NT], b[1];
-    if constexpr (NT == 16) thin_cols<NT, 0, 2>(L, nF, F, uR, uL, a);       // (9..16 free coefficients with a singular K_f: both feet)
-    else {
-        if ((F >> 16) == 0u) thin_cols<NT, 0, 0>(L, nF, F, uR, uL, a);       // wave-uniform three-way: no per-column choice between u_R and u_L in the usual cases
-        else if ((F & 0xFFFFu) == 0u) thin_cols<NT, 0, 1>(L, nF, F, uR, uL, a);
-        else thin_cols<NT, 0, 2>(L, nF, F, uR, uL, a);
-    }
+    if ((F >> 16) == 0u) thin_cols<NT, 0, 0>(L, nF, F, uR, uL, a);           // wave-uniform three-way: no per-column choice between u_R and u_L in the usual cases
+    else if ((F & 0xFFFFu) == 0u) thin_cols<NT, 0, 1>(L, nF, F, uR, uL, a);
+    else thin_cols<NT, 0, 2>(L, nF, F, uR, uL, a);
     b[0] = L[P_QV + ia];
     const int bad = ldl_solve_regs<NT, 1>(a, b, (nF >= 32) ? 0xFFFFFFFFu : ((1u << nF) - 1u), L + C_LS, eps);     // + eps I: added where the pivots are read
     const double z = (lane < nF) ? b[0] : 0.0;                     // z_r in lane r; lanes 8..15 of the row must read as zeros below
@@ -2293,9 +1799,7 @@ __device__ __forceinline__ int solve_free_set_thin(double *L, unsigned F_in, dou
         double wr[12];
 #pragma unroll
         for (int m2 = 0; m2 < 12; m2++) wr[m2] = Wk[m2];
-        dpp_fmac_lane<0>(y, wz, wr[0]); dpp_fmac_lane<1, false>(y, wz, wr[1]); dpp_fmac_lane<2, false>(y, wz, wr[2]); dpp_fmac_lane<3, false>(y, wz, wr[3]);
-        dpp_fmac_lane<4, false>(y, wz, wr[4]); dpp_fmac_lane<5, false>(y, wz, wr[5]); dpp_fmac_lane<6, false>(y, wz, wr[6]); dpp_fmac_lane<7, false>(y, wz, wr[7]);
-        dpp_fmac_lane<8, false>(y, wz, wr[8]); dpp_fmac_lane<9, false>(y, wz, wr[9]); dpp_fmac_lane<10, false>(y, wz, wr[10]); dpp_fmac_lane<11, false>(y, wz, wr[11]);
+        dpp_dot12(y, wz, wr);
     }
     WSYNC();                                                       // (the L rows parked by the solve are dead)
     L[(lane < 12) ? C_LS + lane : C_LS + 16 + (lane & 15)] = y;    // r = W w - h
@@ -2855,26 +2359,12 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
                 WSYNC();
                 qv_stored = true;
             }
-#ifdef LMH_NO_THIN                                                  // experiment switch: the general route for every set
-            if (false) {
-#else
             if (__builtin_amdgcn_readfirstlane(__popc(F)) <= 8) {  // thin set (wave-uniform): everything in registers
-#endif
                 WSTAMP(80);
                 RT_COUNT(2);
-                if (solve_free_set_thin<8>(L, F, P.eps_coeff, &zj, &lj)) flags |= LMH_FLAG_NOT_SPD;
+                if (solve_free_set_thin(L, F, P.eps_coeff, &zj, &lj)) flags |= LMH_FLAG_NOT_SPD;
                 w_thin = true;
                 WSTAMP(81);
-#ifdef LMH_THIN16                                                   // experiment switch: measured 17.0k cycles against the general route's 16.8k for |F| = 16 (a
-            // 16-pivot dependent chain does not get cheaper by staying in registers), so the shipped kernel does not carry it; what removed that
-            // solve from the walking workload is the edge-contact push-through (cone_pushthrough)
-            } else if (__builtin_amdgcn_readfirstlane(__popc(F)) <= 16) {      // up to 16 rows: the same solve, one DPP row full
-                WSTAMP(84);
-                RT_COUNT(2);
-                if (solve_free_set_thin<16>(L, F, P.eps_coeff, &zj, &lj)) flags |= LMH_FLAG_NOT_SPD;
-                w_thin = true;
-                WSTAMP(85);
-#endif
             } else {
                 WSTAMP(82);
                 RT_COUNT(3);
@@ -3052,17 +2542,14 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
         const double beta = (rr < 6) ? agp - L[P_HREF + rr] : bj;
         const double ob = in ? ((rr < 6) ? P.w_com_lin : P.w_foot) * beta : 0.0;
         const int ci = lane & 31;
-        const double *ucol = L + (Q_U + ci), *agc = L + (P_AG + 90 + ((ci < 30) ? ci : 29));        // rows 12..14 of U = AG's linear rows (wave 0 is storing them beside this)
+        const double *ucol = L + (Q_U + ci), *agc = L + (P_AG + 90 + ((ci < 30) ? ci : 29));        // rows 12..14 of U = AG's linear rows, read at their source (this wave has just stored its copies of them in U)
         double ur[nU];
 #pragma unroll
         for (int r = 0; r < 12; r++) ur[r] = ucol[34 * r];
 #pragma unroll
         for (int r = 12; r < nU; r++) ur[r] = agc[30 * (r - 12)];
         double q = 0.0;
-        dpp_fmac_lane<0>(q, ob, ur[0]); dpp_fmac_lane<1, false>(q, ob, ur[1]); dpp_fmac_lane<2, false>(q, ob, ur[2]); dpp_fmac_lane<3, false>(q, ob, ur[3]);
-        dpp_fmac_lane<4, false>(q, ob, ur[4]); dpp_fmac_lane<5, false>(q, ob, ur[5]); dpp_fmac_lane<6, false>(q, ob, ur[6]); dpp_fmac_lane<7, false>(q, ob, ur[7]);
-        dpp_fmac_lane<8, false>(q, ob, ur[8]); dpp_fmac_lane<9, false>(q, ob, ur[9]); dpp_fmac_lane<10, false>(q, ob, ur[10]); dpp_fmac_lane<11, false>(q, ob, ur[11]);
-        dpp_fmac_lane<12, false>(q, ob, ur[12]); dpp_fmac_lane<13, false>(q, ob, ur[13]); dpp_fmac_lane<14, false>(q, ob, ur[14]);
+        dpp_dot15(q, ob, ur);
         const double iDi = (ci < 3) ? idp : (ci < 6) ? ida : idj;
         const double qr = -L[P_QREF + ((ci < 30) ? ci : 0)];
         L[Q_BPT + 34 * 7 + ci] = (ci < 30) ? qr + q * iDi : 0.0;   // (lanes 32..63 repeat lanes 0..31)
@@ -3594,16 +3081,12 @@ __device__ __forceinline__ int phase_qp(double *L, LmhCParams &P, int ph, int wi
 #pragma unroll
         for (int k = 0; k < 6; k++) { sm[k] = si[k]; ym[k] = yt[30 * (1 + k)]; }
         double r0 = -L[P_D6 + i6], r1 = 0.0, s = yt[0];
-        dpp_fmac_lane<0>(r0, wv, jm[0]); dpp_fmac_lane<1, false>(r1, wv, jm[1]); dpp_fmac_lane<2, false>(r0, wv, jm[2]); dpp_fmac_lane<3, false>(r1, wv, jm[3]);
-        dpp_fmac_lane<4, false>(r0, wv, jm[4]); dpp_fmac_lane<5, false>(r1, wv, jm[5]); dpp_fmac_lane<6, false>(r0, wv, jm[6]); dpp_fmac_lane<7, false>(r1, wv, jm[7]);
-        dpp_fmac_lane<8, false>(r0, wv, jm[8]); dpp_fmac_lane<9, false>(r1, wv, jm[9]); dpp_fmac_lane<10, false>(r0, wv, jm[10]); dpp_fmac_lane<11, false>(r1, wv, jm[11]);
+        dpp_dot12_alt(r0, r1, wv, jm);
         const double r = r0 + r1;                                  // r = Jb' w - d
         double nl = 0.0;
-        dpp_fmac_lane<0>(nl, r, sm[0]); dpp_fmac_lane<1, false>(nl, r, sm[1]); dpp_fmac_lane<2, false>(nl, r, sm[2]);
-        dpp_fmac_lane<3, false>(nl, r, sm[3]); dpp_fmac_lane<4, false>(nl, r, sm[4]); dpp_fmac_lane<5, false>(nl, r, sm[5]);
+        bdot6(nl, r, sm);
         const double lam = -nl;                                    // lam = -Si r  (nothing else reads it)
-        dpp_fmac_lane<0>(s, lam, ym[0]); dpp_fmac_lane<1, false>(s, lam, ym[1]); dpp_fmac_lane<2, false>(s, lam, ym[2]);
-        dpp_fmac_lane<3, false>(s, lam, ym[3]); dpp_fmac_lane<4, false>(s, lam, ym[4]); dpp_fmac_lane<5, false>(s, lam, ym[5]);
+        bdot6(s, lam, ym);
         if ((!fz || tail.k4) && lane < 30) L[P_A + lane] = -s;     // a = -(Y_g + Y_M lam)
         if (fz) {
             WSYNC();

@@ -5,9 +5,10 @@ is straight-line between marks (exec-masked bodies, no counted loops except the 
 issues per phase.  Classes of VALU instructions: f64 = fp64 arithmetic (add / mul / fma / fmac incl. DPP forms, rcp, rndne, min / max ...),
 mfma, sel = v_cndmask, lane = v_readlane / v_readfirstlane / v_writelane, mov = v_mov (incl. DPP moves) / v_accvgpr, int = integer
 add / shift / mul / mad / logic, cmp = v_cmp*, cvt, oth.
-The listing is also checked for the DPP read hazard that the compiler does not pad inside inline asm: a VALU write of the source
-register of a v_fmac_f64_dpp needs two wait states before it (one instruction = one state, s_nop N = N + 1); each violation is listed.
-Usage: python scripts/isa_census.py [--reuse] [--out FILE] [extra -D flags]      (--reuse: take /tmp/lmh_census.s as it is)"""
+Every function of the listing is also checked for the DPP read hazard that the compiler does not pad inside inline asm: a VALU write of
+the source register of a v_fmac_f64_dpp / v_fmac_f32_dpp needs two wait states before it (one instruction = one state, s_nop N = N + 1);
+each violation is listed.
+Usage: python scripts/isa_census.py [--reuse] [--rollout-only] [--out FILE] [extra -D flags]      (--reuse: take /tmp/lmh_census.s as it is)"""
 import collections
 import os
 import re
@@ -21,8 +22,9 @@ argv = sys.argv[1:]
 reuse = "--reuse" in argv
 dest = argv[argv.index("--out") + 1] if "--out" in argv else None
 extra = [a for a in argv if a.startswith("-D")]
+rollout_only = ["-DLMH_ROLLOUT_ONLY"] if "--rollout-only" in argv else []       # (faster; the hazard scan then sees the fp64 rollout kernel alone)
 if not reuse:
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-DLMH_PMARK", "-DLMH_ROLLOUT_ONLY",
+    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-S", "--cuda-device-only", "-DLMH_PMARK", *rollout_only,
                            "-mllvm", "-amdgpu-sched-strategy=iterative-ilp", "-mllvm", "-disable-machine-licm", *extra, src, "-o", out],
                           stderr=subprocess.DEVNULL if "--verbose" not in argv else None)
 lines = open(out).read().split("\n")
@@ -90,7 +92,7 @@ for n, c in rows:
         continue
     txt.append("%-30s %6d %5d %5d %5d | " % (n, c.get("valu", 0), c.get("salu", 0), c.get("lds", 0), c.get("vmem", 0)) + " ".join("%5d" % c.get(k, 0) for k in CLS) + " | %5d" % c.get("nopwait", 0))
 txt.append("%-30s %6d %5d %5d %5d | " % ("TOTAL (static)", tot["valu"], tot["salu"], tot["lds"], tot["vmem"]) + " ".join("%5d" % tot[k] for k in CLS) + " | %5d" % tot["nopwait"])
-meta = "\n".join(lines).split(".name:           _Z18lmh_rollout_kernelIdLb0EE")[1][:900] if ".name:           _Z18lmh_rollout_kernelIdLb0EE" in "\n".join(lines) else ""
+meta = next((b for b in "\n".join(lines).split("\n  - ") if ".name:           _Z18lmh_rollout_kernelIdLb0EE" in b), "")   # the kernel's metadata block
 for key in ("sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size"):
     mm = re.search(r"\." + key + r":\s*(\d+)", meta)
     if mm:
@@ -106,30 +108,53 @@ def vregs(tok):
     return set(range(lo, hi + 1))
 
 
-insts = []                                                         # (opcode, operand tokens) of the kernel, listing order
-for l in lines[start:end]:
-    t = l.split(";")[0].strip()
-    if not t or t.startswith((".", "//")) or t.split()[0].endswith(":"):
-        continue
-    op, _, rest = t.partition(" ")
-    insts.append((op, [x.strip() for x in rest.split(",")]))
+def instructions(a, b):
+    """(opcode, operand tokens) of listing lines [a, b), in order"""
+    res = []
+    for l in lines[a:b]:
+        t = l.split(";")[0].strip()
+        if not t or t.startswith((".", "//")) or t.split()[0].endswith(":"):
+            continue
+        op, _, rest = t.partition(" ")
+        res.append((op, [x.strip() for x in rest.split(",")]))
+    return res
+
+
+txt.append("s_nop: %d" % sum(1 for op, _ in instructions(start, end) if op == "s_nop"))
+mm = re.search(r";\s*Occupancy:\s*(\d+)", "\n".join(lines[end:end + 60]))
+if mm:
+    txt.append(f"occupancy: {mm.group(1)}")
+# DPP read hazard, every function of the listing (a function: from its label to its .Lfunc_end)
+DPP_FMAC = ("v_fmac_f64_dpp", "v_fmac_f32_dpp")
 hazards = []
-for i, (op, ops) in enumerate(insts):
-    if op != "v_fmac_f64_dpp":
-        continue
-    src = vregs(ops[1].split()[0])
-    states, j = 0, i - 1
-    while j >= 0 and states < 2:
-        pop, pops = insts[j]
-        if pop == "s_nop":
-            states += int(pops[0], 0) + 1
-        else:
-            if pop.startswith("v_") and pops and pops[0] and vregs(pops[0].split()[0]) & src:
-                hazards.append(f"  {pop} {', '.join(pops)}  ->  {states} wait state(s)  ->  v_fmac_f64_dpp {', '.join(ops)}")
-            states += 1
-        j -= 1
-n_dpp = sum(1 for op, _ in insts if op == "v_fmac_f64_dpp")
-txt.append(f"dpp_read_hazards: {len(hazards)} of {n_dpp} v_fmac_f64_dpp (VALU write of the DPP source fewer than 2 wait states before)")
+n_dpp = collections.Counter()
+n_fn = 0
+fn = None
+for i, l in enumerate(lines):
+    if fn is None and re.match(r"[A-Za-z_][\w$.]*:", l) and not l.startswith(".L"):
+        fn = (l.split(":")[0], i + 1)
+    elif fn is not None and l.startswith(".Lfunc_end"):
+        insts = instructions(fn[1], i)
+        n_fn += 1
+        for k, (op, ops) in enumerate(insts):
+            if op not in DPP_FMAC:
+                continue
+            n_dpp[op] += 1
+            src = vregs(ops[1].split()[0])
+            states, j = 0, k - 1
+            while j >= 0 and states < 2:
+                pop, pops = insts[j]
+                if pop == "s_nop":
+                    states += int(pops[0], 0) + 1
+                else:
+                    if pop.startswith("v_") and pops and pops[0] and vregs(pops[0].split()[0]) & src:
+                        hazards.append(f"  {fn[0]}: {pop} {', '.join(pops)}  ->  {states} wait state(s)  ->  {op} {', '.join(ops)}")
+                    states += 1
+                j -= 1
+        fn = None
+n_here = sum(1 for op, _ in instructions(start, end) if op == "v_fmac_f64_dpp")
+txt.append(f"dpp_read_hazards: {len(hazards)} of {n_dpp[DPP_FMAC[0]]} v_fmac_f64_dpp ({n_here} in lmh_rollout_kernel<double>) + {n_dpp[DPP_FMAC[1]]} v_fmac_f32_dpp"
+           f" in {n_fn} functions (VALU write of the DPP source fewer than 2 wait states before)")
 txt += hazards
 print("\n".join(txt))
 if dest:
