@@ -45,6 +45,7 @@ extern "C" {
 #define LMH_SEG_STRIDE 52
 #define LMH_PUSH_STRIDE 32        /* one timed velocity push: tick (as a double) | dv[30] | pad, see lmh_set_pushes */
 #define LMH_MAX_PUSHES 16         /* push records per robot */
+#define LMH_TRACE_STRIDE 180      /* one trace sample: state(96) | out(80) | status(4, as doubles), see lmh_rollout_trace */
 
 /* status flags */
 #define LMH_FLAG_QP_MAXITER 1     /* active-set iteration cap hit (reference: "QP failed", controller.cpp:472-476) */
@@ -267,6 +268,31 @@ int lmh_eval_debug(lmh_handle *h, double *d_state, double *d_out, int32_t *d_sta
  * The launch slot is clean again afterwards; the caller decides whether to re-run those robots. */
 int lmh_rollout(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_log,
                 int n_ticks, void *stream);
+/* lmh_rollout that also records where every robot was DURING the launch (build-defined; the reference prints CoM x per tick and keeps
+ * nothing, apps/offline/main.cpp:86).  d_trace: DEVICE [n_samples][B][LMH_TRACE_STRIDE], sample-major like d_log, n_samples =
+ * lmh_trace_samples(n_ticks, trace_every) = n_ticks / trace_every.  Sample j of robot i is taken when the robot has completed
+ * (j + 1) * trace_every ticks OF THIS LAUNCH (sample ticks are relative to the launch, not to the robot's clock) and holds exactly what
+ * lmh_rollout(.., (j + 1) * trace_every, ..) would have left in that robot's three records, bit for bit:
+ *   [0, 96)    the state record: q | v | v_prev | t, pads zero;
+ *   [96, 176)  the out record of that tick's k4 evaluation: tau | f | qdd (the plant's acceleration when plant = 1) | CoM | comVel | xRef |
+ *              yRef, pads [174, 176) zero;
+ *   [176, 180) the status record as doubles: k | the maximum of the QP rounds so far in this launch | the OR of the flags so far in this
+ *              launch | the active mask as its int32 value (all exact in a double).
+ * Pushes (lmh_set_pushes): a sample never holds a push whose tick has not started -- one scheduled at tick n is absent from the sample
+ * taken at the end of tick n - 1 and present in every later one.
+ * Restart: the state part of any sample is a valid d_state row, and a launch started from it continues the same rollout bit for bit --
+ * except with warm_start = 1, where the active mask (sample[179], as int32 into d_status[.][3]) must be restored as well.
+ * Launch splitting: when a is a multiple of trace_every, the trace of lmh_rollout_trace(.., a + b, ..) is the traces of a and of b
+ * one after the other.
+ * d_trace == NULL together with trace_every == 0 means no trace: the call is lmh_rollout exactly (lmh_rollout is this call with NULL, 0).
+ * Exactly one of the two given, or trace_every < 0, returns LMH_ERR_BAD_ARG before a launch slot is taken; nothing is enqueued.
+ * trace_every > n_ticks is legal: zero samples, nothing is written.  The caller sizes the buffer; the call writes the samples and
+ * nothing else to it, and the samples a robot flagged LMH_FLAG_UNFINISHED did not reach are left untouched.  The launch-slot rules are
+ * lmh_rollout's (eight in flight, stream ordering, LMH_ERR_UNFINISHED reporting).  Each wave of a robot stores its share of a sample
+ * from where the values are at the fourth stage of the tick; a launch without a trace runs a kernel instantiation that holds none of it. */
+int lmh_rollout_trace(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_log,
+                      int n_ticks, double *d_trace, int trace_every, void *stream);
+int lmh_trace_samples(int n_ticks, int trace_every);      /* n_ticks / trace_every; 0 when trace_every <= 0 */
 
 /* replaces: Kinematics::desiredOperationalState + Kinematics::compute
  * (src/invKinematics.cpp:11-52): Newton IK to feet (0,-/+0.05,0), com target, per instance.
@@ -299,14 +325,18 @@ int lmh_synchronize(lmh_handle *h, void *stream);
  *   base pose(6) | t | max|tau| | f_z R + f_z L | f_z R | f_z L | k | qp iterations | flags | active-bound count |
  *   checksum (sum of the 60 state doubles, in index order).  This record is what the one RCCL gather moves. */
 int lmh_make_summary(lmh_handle *h, const double *d_state, const double *d_out, const int32_t *d_status, double *d_summary, void *stream);
-/* Files: 64-byte little-endian header { char magic[8] "LMHSUM1\0" | "LMHLOG1\0"; uint32 version = 1; uint32 dtype = 1 (f64);
- * uint64 n_instances; uint64 n_ticks (0 for a summary); uint32 width (16 | 36); uint32 0; double dt; double t0; uint64 0 }
- * followed by the raw f64 payload: summary [n][16]; log [n_ticks][n][36] = lmh_rollout's d_log copied to the host.
+/* Files: 64-byte little-endian header { char magic[8] "LMHSUM1\0" | "LMHLOG1\0" | "LMHTRJ1\0"; uint32 version = 1; uint32 dtype = 1 (f64);
+ * uint64 n_instances; uint64 n_ticks (0 for a summary; the sample count of a trace); uint32 width (16 | 36 | 180); uint32 0; double dt
+ * (a trace: the sample period trace_every * dt); double t0 (a trace: the clock of the first sample); uint64 0 }
+ * followed by the raw f64 payload: summary [n][16]; log [n_ticks][n][36] = lmh_rollout's d_log copied to the host; trace
+ * [n_samples][n][180] = lmh_rollout_trace's d_trace copied to the host.
  * HOST pointers.  Readers return LMH_ERR_BAD_ARG on a bad magic / version / size; `capacity` is in doubles. */
 int lmh_write_summary(const char *path, const double *summary, uint64_t n_instances, double dt);
 int lmh_read_summary(const char *path, double *summary, uint64_t capacity, uint64_t *n_instances, double *dt);
 int lmh_write_log(const char *path, const double *log, uint64_t n_ticks, uint64_t n_instances, double dt, double t0);
 int lmh_read_log(const char *path, double *log, uint64_t capacity, uint64_t *n_ticks, uint64_t *n_instances, double *dt, double *t0);
+int lmh_write_trace(const char *path, const double *trace, uint64_t n_samples, uint64_t n_instances, double sample_dt, double t0);
+int lmh_read_trace(const char *path, double *trace, uint64_t capacity, uint64_t *n_samples, uint64_t *n_instances, double *sample_dt, double *t0);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,7 @@ LINK_STRIDE = 13
 SEG_STRIDE = 52
 PUSH_STRIDE = 32              # one timed velocity push: tick (as a double) | dv[30] | pad (lmh_set_pushes)
 MAX_PUSHES = 16               # push records per robot
+TRACE_STRIDE = 180            # one trace sample: state(96) | out(80) | status(4, as doubles) (lmh_rollout_trace)
 
 FLAG_QP_MAXITER = 1
 FLAG_NONFINITE = 2
@@ -44,6 +45,7 @@ EXPORTS = [
     "lmh_gen_walk", "lmh_gen_jump", "lmh_num_ref_samples", "lmh_num_segments", "lmh_get_refs",
     "lmh_gen_walk_batch", "lmh_gen_jump_batch", "lmh_set_plans", "lmh_plans_per_instance", "lmh_get_plan",
     "lmh_set_pushes", "lmh_num_pushes", "lmh_pushes_per_instance", "lmh_get_pushes",
+    "lmh_rollout_trace", "lmh_trace_samples", "lmh_write_trace", "lmh_read_trace",
 ]
 
 
@@ -103,6 +105,8 @@ def lib():
     L.lmh_eval.argtypes = [vp, vp, vp, vp, vp]
     L.lmh_eval_debug.argtypes = [vp, vp, vp, vp, vp, vp]
     L.lmh_rollout.argtypes = [vp, vp, vp, vp, vp, ip, vp]
+    L.lmh_rollout_trace.argtypes = [vp, vp, vp, vp, vp, ip, vp, ip, vp]
+    L.lmh_trace_samples.argtypes = [ip, ip]
     L.lmh_ik.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.lmh_eval_host.argtypes = [vp, vp, vp, dp, vp, vp, vp, vp]
     L.lmh_set_prev_velocity_host.argtypes = [vp, vp]
@@ -133,6 +137,8 @@ def lib():
     L.lmh_read_summary.argtypes = [C.c_char_p, vp, u64, u64p, dpp]
     L.lmh_write_log.argtypes = [C.c_char_p, vp, u64, u64, dp, dp]
     L.lmh_read_log.argtypes = [C.c_char_p, vp, u64, u64p, u64p, dpp, dpp]
+    L.lmh_write_trace.argtypes = [C.c_char_p, vp, u64, u64, dp, dp]
+    L.lmh_read_trace.argtypes = [C.c_char_p, vp, u64, u64p, u64p, dpp, dpp]
     for name in EXPORTS:
         fn = getattr(L, name)
         if fn.restype is C.c_int and name not in ("lmh_last_error", "lmh_config_default", "lmh_nominal_links"):

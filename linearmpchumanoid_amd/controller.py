@@ -295,6 +295,30 @@ class BatchedController:
                                      None if lg is None else _dev_ptr(lg), int(n_ticks), self._stream()))
         return out, status, lg
 
+    def rollout_trace(self, state, n_ticks, every, out=None, status=None, log=False, trace=None):
+        """lmh_rollout_trace: rollout that also stores a sample [state(96) | out(80) | status(4, as doubles)] of every robot each time it
+        has completed `every` more ticks of this launch -- what rollout(state, (j + 1) * every) would have left, bit for bit.
+        trace: a [n_ticks // every, B, 180] float64 device tensor (or larger), allocated here when None.  -> (out, status, log, trace)."""
+        out = self.new_out() if out is None else out
+        status = self.new_status() if status is None else status
+        lg = torch.zeros((n_ticks, self.B, 36), dtype=torch.float64, device=self.device) if log is True else (log if log is not False else None)
+        if trace is None:
+            trace = torch.zeros((capi.lib().lmh_trace_samples(int(n_ticks), int(every)), self.B, capi.TRACE_STRIDE), dtype=torch.float64, device=self.device)
+        check(capi.lib().lmh_rollout_trace(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), None if lg is None else _dev_ptr(lg),
+                                           int(n_ticks), _dev_ptr(trace), int(every), self._stream()))
+        return out, status, lg, trace
+
+    @staticmethod
+    def split_trace(trace):
+        """Named views of a trace [.., 180] (tensor or array): state, q, v, v_prev, t, the split_out fields tau, f, qpp and com, com_vel,
+        x_ref, y_ref, out; k, qp_iterations, flags, active_mask as integer tensors / arrays (exact: they were stored from int32)."""
+        s, o, w = trace[..., 0:96], trace[..., 96:176], trace[..., 176:180]
+        wi = w.to(torch.int64) if isinstance(w, torch.Tensor) else np.asarray(w).astype(np.int64)
+        return dict(state=s, q=s[..., 0:30], v=s[..., 30:60], v_prev=s[..., 60:90], t=s[..., 90],
+                    out=o, tau=o[..., 0:24], f=o[..., 24:36], qpp=o[..., 36:66], com=o[..., 66:69], com_vel=o[..., 69:72],
+                    x_ref=o[..., 72:75], y_ref=o[..., 75:78],
+                    k=wi[..., 0], qp_iterations=wi[..., 1], flags=wi[..., 2], active_mask=wi[..., 3])
+
     def synchronize(self):
         """lmh_synchronize on the current stream: waits for it, and raises LmhError (code ERR_UNFINISHED) if a completed rollout of this
         handle left robots part-way (they carry FLAG_UNFINISHED in their status records)."""
@@ -350,6 +374,23 @@ class BatchedController:
         check(capi.lib().lmh_read_log(str(path).encode(), None, 0, C.byref(nt), C.byref(n), C.byref(dt), C.byref(t0)))
         a = np.zeros((nt.value, n.value, 36), dtype=np.float64)
         check(capi.lib().lmh_read_log(str(path).encode(), _np_ptr(a), a.size, C.byref(nt), C.byref(n), C.byref(dt), C.byref(t0)))
+        return a, dt.value, t0.value
+
+    @staticmethod
+    def write_trace(path, trace, sample_dt, t0=0.0):
+        """lmh_write_trace: [n_samples,B,180] host array (lmh_rollout_trace's d_trace copied back); sample_dt = every * dt, t0 = the
+        clock of the first sample."""
+        a = np.ascontiguousarray(trace, dtype=np.float64)
+        if a.ndim != 3 or a.shape[2] != capi.TRACE_STRIDE:
+            raise ValueError("trace must be [samples,B,180]")
+        check(capi.lib().lmh_write_trace(str(path).encode(), _np_ptr(a), a.shape[0], a.shape[1], float(sample_dt), float(t0)))
+
+    @staticmethod
+    def read_trace(path):
+        ns, n, dt, t0 = C.c_uint64(0), C.c_uint64(0), C.c_double(0.0), C.c_double(0.0)
+        check(capi.lib().lmh_read_trace(str(path).encode(), None, 0, C.byref(ns), C.byref(n), C.byref(dt), C.byref(t0)))
+        a = np.zeros((ns.value, n.value, capi.TRACE_STRIDE), dtype=np.float64)
+        check(capi.lib().lmh_read_trace(str(path).encode(), _np_ptr(a), a.size, C.byref(ns), C.byref(n), C.byref(dt), C.byref(t0)))
         return a, dt.value, t0.value
 
     @staticmethod

@@ -14,7 +14,7 @@
 #include "lmh_nao_model.h"
 
 extern "C" void lmh_launch_eval(const LmhDevParams *P, double *state, double *out, int32_t *status, double *debug, hipStream_t s);
-extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks, hipStream_t s);
+extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks, double *trace, int trace_every, hipStream_t s);
 extern "C" void lmh_launch_model(const double *raw, double *model, int n_models, const double *lcoef, hipStream_t s);
 extern "C" void lmh_launch_com(const LmhDevParams *P, const double *q, double *com, hipStream_t s);
 extern "C" void lmh_launch_ik(const LmhDevParams *P, double *q, const LmhIkTarget *target, int32_t *iters, hipStream_t s);
@@ -641,10 +641,19 @@ static int slot_take_error(lmh_handle::Slot &sl)
                 "); the robots that did not get all their ticks carry LMH_FLAG_UNFINISHED in their status records");
 }
 
-extern "C" int lmh_rollout(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_log, int n_ticks, void *stream)
+extern "C" int lmh_trace_samples(int n_ticks, int trace_every)
+{
+    return (trace_every <= 0 || n_ticks <= 0) ? 0 : n_ticks / trace_every;
+}
+
+extern "C" int lmh_rollout_trace(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_log, int n_ticks,
+                                 double *d_trace, int trace_every, void *stream)
 {
     int rc = ready(h); if (rc) return rc;
     if (!d_state || !d_out || !d_status || n_ticks < 0) return fail(LMH_ERR_BAD_ARG, "bad argument");
+    // decided before a launch slot is taken: the buffer and its period come together or not at all
+    if (trace_every < 0 || (d_trace != nullptr) != (trace_every > 0))
+        return fail(LMH_ERR_BAD_ARG, "lmh_rollout_trace: d_trace and trace_every > 0 go together (NULL and 0: no trace)");
     if (n_ticks == 0) return LMH_OK;
     HIPCHK(hipSetDevice(h->device));
     lmh_handle::Slot &sl = h->slot[h->next_slot % lmh_handle::kSlots];
@@ -660,12 +669,17 @@ extern "C" int lmh_rollout(lmh_handle *h, double *d_state, double *d_out, int32_
         HIPCHK(hipMemcpyAsync(sl.d_P.get(), &sl.P_dev, sizeof(LmhDevParams), hipMemcpyHostToDevice, (hipStream_t)stream));   // stream-ordered in front of the launch; the slot is idle
         sl.valid = true;
     }
-    lmh_launch_rollout(&h->P, sl.d_P.get(), sl.d_ticket.get(), d_state, d_out, d_status, d_log, n_ticks, (hipStream_t)stream);
+    lmh_launch_rollout(&h->P, sl.d_P.get(), sl.d_ticket.get(), d_state, d_out, d_status, d_log, n_ticks, d_trace, trace_every, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(sl.done, (hipStream_t)stream));
     sl.used = true;
     sl.checked = false;
     return LMH_OK;
+}
+
+extern "C" int lmh_rollout(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_log, int n_ticks, void *stream)
+{
+    return lmh_rollout_trace(h, d_state, d_out, d_status, d_log, n_ticks, nullptr, 0, stream);
 }
 
 extern "C" int lmh_ik(lmh_handle *h, double *d_q, const double *com_target, const double *rf6, const double *lf6, int32_t *d_iters, void *stream)
@@ -793,7 +807,8 @@ struct RecHeader {                                                   // 64 bytes
 };
 #pragma pack(pop)
 static_assert(sizeof(RecHeader) == 64, "record header is 64 bytes");
-const char kMagicSum[8] = {'L', 'M', 'H', 'S', 'U', 'M', '1', 0}, kMagicLog[8] = {'L', 'M', 'H', 'L', 'O', 'G', '1', 0};
+const char kMagicSum[8] = {'L', 'M', 'H', 'S', 'U', 'M', '1', 0}, kMagicLog[8] = {'L', 'M', 'H', 'L', 'O', 'G', '1', 0},
+           kMagicTrace[8] = {'L', 'M', 'H', 'T', 'R', 'J', '1', 0};
 
 int write_rec(const char *path, const char *magic, const double *data, uint64_t n_inst, uint64_t n_ticks, uint32_t width, double dt, double t0)
 {
@@ -820,8 +835,8 @@ int read_rec(const char *path, const char *magic, uint32_t width, double *data, 
     else if (std::memcmp(hd->magic, magic, 8) != 0) rc = fail(LMH_ERR_BAD_ARG, "bad magic");
     else if (hd->version != 1 || hd->dtype != 1 || hd->width != width) rc = fail(LMH_ERR_BAD_ARG, "unsupported version / dtype / width");
     else {
-        const bool is_log = std::memcmp(magic, kMagicLog, 8) == 0;
-        const uint64_t count = hd->n_instances * width * (is_log ? hd->n_ticks : 1);
+        const bool per_tick = std::memcmp(magic, kMagicSum, 8) != 0;       // a log or a trace: one record per robot and tick / sample
+        const uint64_t count = hd->n_instances * width * (per_tick ? hd->n_ticks : 1);
         long pos = std::ftell(f);
         std::fseek(f, 0, SEEK_END);
         const long end = std::ftell(f);
@@ -863,6 +878,22 @@ extern "C" int lmh_read_log(const char *path, double *log, uint64_t capacity, ui
     if (n_ticks) *n_ticks = hd.n_ticks;
     if (n_instances) *n_instances = hd.n_instances;
     if (dt) *dt = hd.dt;
+    if (t0) *t0 = hd.t0;
+    return LMH_OK;
+}
+extern "C" int lmh_write_trace(const char *path, const double *trace, uint64_t n_samples, uint64_t n_instances, double sample_dt, double t0)
+{
+    if (n_samples == 0) return fail(LMH_ERR_BAD_ARG, "a trace holds at least one sample");
+    return write_rec(path, kMagicTrace, trace, n_instances, n_samples, LMH_TRACE_STRIDE, sample_dt, t0);
+}
+extern "C" int lmh_read_trace(const char *path, double *trace, uint64_t capacity, uint64_t *n_samples, uint64_t *n_instances, double *sample_dt, double *t0)
+{
+    RecHeader hd;
+    const int rc = read_rec(path, kMagicTrace, LMH_TRACE_STRIDE, trace, capacity, &hd);
+    if (rc != LMH_OK) return rc;
+    if (n_samples) *n_samples = hd.n_ticks;
+    if (n_instances) *n_instances = hd.n_instances;
+    if (sample_dt) *sample_dt = hd.dt;
     if (t0) *t0 = hd.t0;
     return LMH_OK;
 }

@@ -3627,6 +3627,44 @@ __device__ __forceinline__ void push_poll(double *L, LmhCParams &P, int inst, in
     if (rel == next) push_apply(L, P, inst, lane, rel, __builtin_amdgcn_readfirstlane(pw[1]), lim, x);
 }
 
+// ---- rollout trace (include/lmh.h, lmh_rollout_trace): sample j of a robot is the three records a launch that ended after
+// (j + 1) * trace_every ticks would have left, [state(96) | out(80) | status(4, as doubles)], stored from where the values are at the fourth
+// stage of that tick -- no LDS staging, no join: each wave stores what IT produced in this evaluation, as the log does, because the two
+// waves are not joined between a tick's last evaluation and the next tick's first (the pipelined kernel without the plant): a wave that
+// read the other's words there could find the next evaluation's.  Wave 0: the state from the integrator's registers, the wrench, the
+// accelerations, the status record.  Helper wave: the torques, CoM | comVel and the MPC state (phase_com_x and chain A run on it).
+// `done`: the ticks of THIS launch the robot has behind it (wave-uniform), so that a sample falls where it does whatever the 250-tick chunks
+// are; a sample is due when trace_every divides it (every > 0 whenever the buffer is there: lmh_rollout_trace refuses anything else).
+__device__ __forceinline__ double *trace_slot(double *tr, int every, int done, int n_inst, int inst)
+{
+    const unsigned j = (unsigned)__builtin_amdgcn_readfirstlane((int)((unsigned)done / (unsigned)every));
+    return (j * (unsigned)every == (unsigned)done) ? tr + ((size_t)(j - 1u) * (size_t)n_inst + (size_t)inst) * LMH_TRACE_STRIDE : nullptr;
+}
+// wave 0, between the fourth stage's rk4_stage and push_poll (a sample never holds a push whose tick has not started): x = q | v (lanes
+// 0..59), xprev = the next tick's Robot::v_ (lanes 30..59), tnext = t + dt; the pads of the three records are written as zeros.
+// QDD_REG: xdot is at hand in a register (register tail; lanes 30..59 = the accelerations), else they are read where phase_outputs_qdd left them
+template <bool QDD_REG>
+__device__ __forceinline__ void trace_wave0(double *tr, const double *L, int lane, double x, double xprev, double xd, double tnext, int k, int itmax, int flags, unsigned F)
+{
+    tr[(lane < 60) ? lane : 30 + lane] = (lane < 60) ? x : (lane == 60) ? tnext : 0.0;      // q | v | t and the pads [91, 94)
+    const bool vp = lane >= 30 && lane < 60;
+    // lanes 0..11 the wrench | 12..15 the status record | 16, 17 the state's pads [94, 96) | 18, 19 the out record's pads | 30..59 v_prev
+    const double w = L[P_W12 + ((lane < 12) ? lane : 0)];
+    const double sv = (lane == 12) ? (double)k : (lane == 13) ? (double)itmax : (lane == 14) ? (double)flags : (lane == 15) ? (double)(int32_t)(~F) : 0.0;
+    const int idx = (lane < 12) ? LMH_STATE_STRIDE + 24 + lane : (lane < 16) ? LMH_STATE_STRIDE + LMH_OUT_STRIDE + lane - 12
+                  : (lane < 18) ? 94 + lane - 16 : (lane < 20) ? LMH_STATE_STRIDE + 78 + lane - 18 : 30 + lane;
+    if (lane < 20 || vp) tr[idx] = (lane < 12) ? w : (lane < 20) ? sv : xprev;
+    if constexpr (QDD_REG) { if (vp) tr[LMH_STATE_STRIDE + 36 + lane - 30] = xd; }
+    else { if (lane < 30) tr[LMH_STATE_STRIDE + 36 + lane] = L[P_QDD + lane]; }
+}
+// helper wave, behind the fourth stage's evaluation (beside its log store): the words of store_out that it wrote itself
+__device__ __forceinline__ void trace_wave1(double *tr, const double *L, int lane)
+{
+    const bool a = lane < 24, b = lane >= 32 && lane < 38, c = lane >= 40 && lane < 46;
+    const double v = L[a ? P_TAU + lane : b ? P_COM + lane - 32 : c ? P_MPC + 2 + lane - 40 : (int)P_TAU];
+    if (a || b || c) tr[LMH_STATE_STRIDE + (a ? lane : b ? 66 + lane - 32 : 72 + lane - 40)] = v;
+}
+
 // Closed loop of apps/offline/main.cpp:66-122: n_ticks x rk4Step(dynamics) with Clock::step.
 // Workgroup = LMH_ROLLOUT_THREADS = 2 waves per robot (see bsync): 4 robots = 8 waves per CU, two per SIMD, so the
 // kernel is held to 256 registers.  Wave 0 owns the RK4 state (lane i < 60 <-> component i) and everything
@@ -3634,7 +3672,9 @@ __device__ __forceinline__ void push_poll(double *L, LmhCParams &P, int inst, in
 #ifndef LMH_CHUNK_TICKS
 #define LMH_CHUNK_TICKS 250          // ticks of one robot a workgroup runs before the robot goes back to the queue (see lmh_rollout_kernel)
 #endif
-template <typename R, bool QF32 = false>
+// TRACE: the instantiation lmh_rollout_trace launches (trace_slot above); without a trace buffer the launch runs the instantiation that has
+// no word of it -- the same code as before the trace existed, so that it costs nothing when off
+template <typename R, bool QF32 = false, bool TRACE = false>
 #ifndef LMH_ROLLOUT_ATTR
 #ifndef LMH_WAVES_PER_EU
 #define LMH_WAVES_PER_EU 2
@@ -3646,16 +3686,16 @@ template <typename R, bool QF32 = false>
 #endif
 #endif
 __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) LMH_ROLLOUT_ATTR
-lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket_a, double *state_a, double *out_a, int32_t *status_a, double *log_a, int n_ticks_a)
+lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket_a, double *state_a, double *out_a, int32_t *status_a, double *log_a, int n_ticks_a, double *trace_a, int trace_every_a)
 {
     // The parameter block is read through a pointer that is made opaque once per evaluation (params_of): hoisting its ~70 scalars out
     // of the tick loop pins them in SGPRs for the whole launch (round 1: 189 SGPR + 16 VGPR spills, 60 B of scratch per lane that reached
     // HBM); re-reading them costs a few scalar-cache loads per evaluation.
     __shared__ double L[LDS_DOUBLES];
     // The kernel's own arguments are read from the kernarg segment where they are used (a scalar load each: chunk start, chunk end, the log
-    // once per tick) instead of being carried in scalar registers across the tick loop, where they were spilled to vector lanes and read back.
-    (void)ticket_a; (void)state_a; (void)out_a; (void)status_a; (void)log_a; (void)n_ticks_a;
-    struct Args { const LmhDevParams *Pg; int *ticket; double *state, *out; int32_t *status; double *log; int n_ticks; };
+    // and the trace once per tick) instead of being carried in scalar registers across the tick loop, where they were spilled to vector lanes and read back.
+    (void)ticket_a; (void)state_a; (void)out_a; (void)status_a; (void)log_a; (void)n_ticks_a; (void)trace_a; (void)trace_every_a;
+    struct Args { const LmhDevParams *Pg; int *ticket; double *state, *out; int32_t *status; double *log; int n_ticks; double *trace; int trace_every; };
     typedef const __attribute__((address_space(4))) Args CArgs;
     auto KA = [&]() -> CArgs & { CArgs *p_ = (CArgs *)__builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(p_)); return *p_; };
 #define ticket (KA().ticket)
@@ -3664,6 +3704,8 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
 #define status (KA().status)
 #define log (KA().log)
 #define n_ticks (KA().n_ticks)
+#define trace (KA().trace)
+#define trace_every (KA().trace_every)
     LmhCParams *Pc = (LmhCParams *)(uintptr_t)Pg;
     LmhCParams &P = *Pc;
     // One workgroup runs several robots one after the other (grid = the number of workgroups the chip holds at once, lmh_launch_rollout):
@@ -3794,6 +3836,10 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
                 const double xprev = xs;
                 rk4_stage<3>(L, stage, lane, dt, xd4, x, ksum, xs, tail.xd);
                 if (stage == 3) {
+                    if constexpr (TRACE) {                         // the sample of this tick: the state as a launch ending here would store it
+                        double *tr = trace_slot(trace, trace_every, tick0 + tick + 1, Pe->n_instances, inst);
+                        if (tr) trace_wave0<true>(tr, L, lane, x, xprev, tail.xd, t + dt, k, itmax, flags, F);
+                    }
                     push_poll(L, *Pe, inst, lane, tick + 1, n_here, x);     // a push at the start of the next tick joins the state published for it
                     xs = x;                                        // the next tick starts from x (what `xs = x` at its top says)
                 }
@@ -3806,7 +3852,13 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
                 itmax = (iters > itmax) ? iters : itmax;
                 const double xprev = xs;
                 if constexpr (PIPE) rk4_stage<2>(L, stage, lane, dt, xd4, x, ksum, xs); else rk4_stage<0>(L, stage, lane, dt, xd4, x, ksum, xs);
-                if (stage == 3) push_poll(L, *Pe, inst, lane, tick + 1, n_here, x);     // the next tick publishes x at its top
+                if (stage == 3) {
+                    if constexpr (TRACE) {                         // (phase_outputs_qdd's words are wave 0's own, behind its fence)
+                        double *tr = trace_slot(trace, trace_every, tick0 + tick + 1, Pe->n_instances, inst);
+                        if (tr) trace_wave0<false>(tr, L, lane, x, xprev, 0.0, t + dt, k, itmax, flags, F);
+                    }
+                    push_poll(L, *Pe, inst, lane, tick + 1, n_here, x);     // the next tick publishes x at its top
+                }
                 // Robot::v_ <- dq for the next evaluation
                 WSYNC();
                 if (lane >= 30 && lane < 60) L[P_VP + lane - 30] = xprev;
@@ -3826,6 +3878,10 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
             double *lg = log + ((size_t)(tick0 + tick) * P.n_instances + inst) * 36;
             if (wid != 0) { if (lane < 24) lg[lane] = L[P_TAU + lane]; }
             else if (lane >= 24 && lane < 36) lg[lane] = L[P_W12 + lane - 24];
+        }
+        if (TRACE && wid != 0) {                                    // the helper's share of the tick's sample (wave 0's left at the fourth stage)
+            double *tr = trace_slot(trace, trace_every, tick0 + tick + 1, P.n_instances, inst);
+            if (tr) trace_wave1(tr, L, lane);
         }
         t += dt;                                                    // Clock::step, Clock.hpp:11
     }
@@ -3921,6 +3977,8 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
 #undef status
 #undef log
 #undef n_ticks
+#undef trace
+#undef trace_every
 
 // Robot::Robot model preparation (Robot.cpp:14-22) + Dynamics::spatialInertiaMatrix pieces
 // (Dynamics.cpp:4-13): raw [28][13] -> device model record.
@@ -4409,16 +4467,22 @@ extern "C" int lmh_debug_build_flags(void)
     return f;
 }
 // d_ticket: zero-initialised device memory owned by this launch until it completes (work-unit counters, ring, progress: see the kernel)
-extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks, hipStream_t s)
+extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks, double *trace, int trace_every, hipStream_t s)
 {
     const int slots = rollout_resident_groups();
     const dim3 grid((unsigned)((P->n_instances < slots) ? P->n_instances : slots));
+    // (the untraced instantiations ignore the two trace arguments)
+#define LMH_LAUNCH_ROLLOUT(R, QF32) do { \
+        if (trace) hipLaunchKernelGGL((lmh_rollout_kernel<R, QF32, true>), grid, dim3(LMH_ROLLOUT_THREADS), 0, s, d_P, d_ticket, state, out, status, log, n_ticks, trace, trace_every); \
+        else hipLaunchKernelGGL((lmh_rollout_kernel<R, QF32, false>), grid, dim3(LMH_ROLLOUT_THREADS), 0, s, d_P, d_ticket, state, out, status, log, n_ticks, trace, trace_every); \
+    } while (0)
 #ifndef LMH_ROLLOUT_ONLY
-    if (P->precision == 2) hipLaunchKernelGGL((lmh_rollout_kernel<float, true>), grid, dim3(LMH_ROLLOUT_THREADS), 0, s, d_P, d_ticket, state, out, status, log, n_ticks);
-    else if (P->precision == 1) hipLaunchKernelGGL(lmh_rollout_kernel<float>, grid, dim3(LMH_ROLLOUT_THREADS), 0, s, d_P, d_ticket, state, out, status, log, n_ticks);
+    if (P->precision == 2) LMH_LAUNCH_ROLLOUT(float, true);
+    else if (P->precision == 1) LMH_LAUNCH_ROLLOUT(float, false);
     else
 #endif
-    hipLaunchKernelGGL(lmh_rollout_kernel<double>, grid, dim3(LMH_ROLLOUT_THREADS), 0, s, d_P, d_ticket, state, out, status, log, n_ticks);
+    LMH_LAUNCH_ROLLOUT(double, false);
+#undef LMH_LAUNCH_ROLLOUT
 }
 #ifndef LMH_ROLLOUT_ONLY
 extern "C" void lmh_launch_model(const double *raw, double *model, int n_models, const double *lcoef, hipStream_t s)

@@ -4,18 +4,21 @@ The reference writes nothing but stdout (apps/offline/main.cpp:86 prints CoM x p
 record formats below are the build's own; they are plain little-endian arrays behind a fixed 64-byte
 header so that a C reader is a struct and an fread:
 
-    offset  0  char[8]   magic   "LMHSUM1\0" (run summary) | "LMHLOG1\0" (trajectory log)
+    offset  0  char[8]   magic   "LMHSUM1\0" (run summary) | "LMHLOG1\0" (torque / wrench log) | "LMHTRJ1\0" (rollout trace)
             8  uint32    version (1)
            12  uint32    dtype code (1 = float64)
            16  uint64    n_instances
-           24  uint64    n_ticks          (log; 0 for a summary)
-           32  uint32    record width in doubles (16 summary | 36 log: tau(24) | f(12))
+           24  uint64    n_ticks          (log; 0 for a summary; the sample count of a trace)
+           32  uint32    record width in doubles (16 summary | 36 log: tau(24) | f(12) | 180 trace: state(96) | out(80) | status(4))
            36  uint32    reserved
-           40  float64   dt
-           48  float64   t0  (clock at the first logged tick)
+           40  float64   dt               (a trace: the sample period trace_every * dt)
+           48  float64   t0  (clock at the first logged tick; a trace: the clock of the first sample)
            56  uint64    reserved
     payload: summary [n_instances][16] f64 (sharding.make_summary layout);
-             log     [n_ticks][n_instances][36] f64 (exactly the d_log buffer of lmh_rollout).
+             log     [n_ticks][n_instances][36] f64 (exactly the d_log buffer of lmh_rollout);
+             trace   [n_samples][n_instances][180] f64 (exactly the d_trace buffer of lmh_rollout_trace: the state, out and status
+                     records -- the latter as doubles -- every robot would have been left with had the launch ended at that sample;
+                     this is the record a walk is replayed or plotted from).
 
 The MuJoCo-side adapter restates the three small conversions the reference does between MuJoCo's
 generalized coordinates and the controller's (simulators/mujoco/MujocoSim.cpp:119-146,
@@ -31,6 +34,8 @@ MAGIC_SUMMARY = b"LMHSUM1\0"
 MAGIC_LOG = b"LMHLOG1\0"
 SUMMARY_WIDTH = 16
 LOG_WIDTH = 36
+MAGIC_TRACE = b"LMHTRJ1\0"
+TRACE_WIDTH = 180
 SUMMARY_FIELDS = ("base_x", "base_y", "base_z", "roll", "pitch", "yaw", "t", "max_abs_tau", "sum_fz", "fz_right", "fz_left",
                   "k", "qp_iterations", "flags", "active_count", "state_checksum")
 
@@ -52,7 +57,9 @@ def _read(path, magic):
             raise ValueError(f"{path}: bad magic {mg!r}")
         if ver != 1 or dtype != 1:
             raise ValueError(f"{path}: unsupported version/dtype {ver}/{dtype}")
-        count = n_inst * width * (n_ticks if magic == MAGIC_LOG else 1)
+        if magic == MAGIC_TRACE and width != TRACE_WIDTH:
+            raise ValueError(f"{path}: a trace record is {TRACE_WIDTH} doubles wide, header says {width}")
+        count = n_inst * width * (1 if magic == MAGIC_SUMMARY else n_ticks)
         data = np.frombuffer(f.read(), dtype="<f8")
         if data.size != count:
             raise ValueError(f"{path}: payload holds {data.size} doubles, header says {count}")
@@ -83,6 +90,19 @@ def write_log(path, log, dt, t0=0.0):
 def read_log(path):
     data, n, nt, w, dt, t0 = _read(path, MAGIC_LOG)
     return data.reshape(nt, n, w).copy(), dt, t0
+
+
+def write_trace(path, trace, sample_dt, t0=0.0):
+    """trace: [n_samples, B, 180] -- lmh_rollout_trace's d_trace; sample_dt = trace_every * dt, t0 = the clock of the first sample."""
+    tr = np.asarray(trace, dtype=np.float64)
+    if tr.ndim != 3 or tr.shape[2] != TRACE_WIDTH or tr.shape[0] == 0:
+        raise ValueError("trace must be [samples >= 1,B,180]")
+    _write(path, MAGIC_TRACE, tr, tr.shape[1], tr.shape[0], TRACE_WIDTH, sample_dt, t0)
+
+
+def read_trace(path):
+    data, n, ns, w, dt, t0 = _read(path, MAGIC_TRACE)
+    return data.reshape(ns, n, w).copy(), dt, t0
 
 
 # ----------------------------------------------------------------------------- MuJoCo-side adapter

@@ -8,7 +8,8 @@ add / shift / mul / mad / logic, cmp = v_cmp*, cvt, oth.
 Every function of the listing is also checked for the DPP read hazard that the compiler does not pad inside inline asm: a VALU write of
 the source register of a v_fmac_f64_dpp / v_fmac_f32_dpp needs two wait states before it (one instruction = one state, s_nop N = N + 1);
 each violation is listed.
-Usage: python scripts/isa_census.py [--reuse] [--rollout-only] [--out FILE] [extra -D flags]      (--reuse: take /tmp/lmh_census.s as it is)"""
+Usage: python scripts/isa_census.py [--reuse] [--rollout-only] [--trace] [--out FILE] [extra -D flags]      (--trace: the instantiation lmh_rollout_trace launches)
+            (--reuse: take /tmp/lmh_census.s as it is)"""
 import collections
 import os
 import re
@@ -28,7 +29,8 @@ if not reuse:
                            "-mllvm", "-amdgpu-sched-strategy=iterative-ilp", "-mllvm", "-disable-machine-licm", *extra, src, "-o", out],
                           stderr=subprocess.DEVNULL if "--verbose" not in argv else None)
 lines = open(out).read().split("\n")
-start = next(i for i, l in enumerate(lines) if l.startswith("_Z18lmh_rollout_kernelIdLb0EE"))
+KNAME = "_Z18lmh_rollout_kernelIdLb0ELb%dEE" % int("--trace" in argv)     # lmh_rollout_kernel<double, false, TRACE>
+start = next(i for i, l in enumerate(lines) if l.startswith(KNAME))
 end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
 names = {0: "eval start", 1: "fk / prep done", 2: "joined", 3: "com_x share", 4: "joined", 5: "tree share", 6: "(no join)", 7: "refs share (+prefill)", 8: "joined",
          10: "qp fills", 11: "joined", 12: "Cm | V tile", 13: "joined", 14: "rows loaded", 15: "15x15 solve", 16: "joined", 17: "Y tiles", 18: "set-up done",
@@ -92,7 +94,7 @@ for n, c in rows:
         continue
     txt.append("%-30s %6d %5d %5d %5d | " % (n, c.get("valu", 0), c.get("salu", 0), c.get("lds", 0), c.get("vmem", 0)) + " ".join("%5d" % c.get(k, 0) for k in CLS) + " | %5d" % c.get("nopwait", 0))
 txt.append("%-30s %6d %5d %5d %5d | " % ("TOTAL (static)", tot["valu"], tot["salu"], tot["lds"], tot["vmem"]) + " ".join("%5d" % tot[k] for k in CLS) + " | %5d" % tot["nopwait"])
-meta = next((b for b in "\n".join(lines).split("\n  - ") if ".name:           _Z18lmh_rollout_kernelIdLb0EE" in b), "")   # the kernel's metadata block
+meta = next((b for b in "\n".join(lines).split("\n  - ") if ".name:           " + KNAME in b), "")   # the kernel's metadata block
 for key in ("sgpr_count", "sgpr_spill_count", "vgpr_count", "vgpr_spill_count", "private_segment_fixed_size", "group_segment_fixed_size"):
     mm = re.search(r"\." + key + r":\s*(\d+)", meta)
     if mm:

@@ -1,0 +1,248 @@
+"""The rollout trace (lmh_rollout_trace): strided samples of the state, out and status records of every robot inside one launch.  A
+sample is what lmh_rollout of that many ticks would have left, so the reference is a second handle cut into plain launches of `every`
+ticks (tests/trace_cases.py) -- a sequence the chunk and parity tests already pin against the oracle -- and "equal" means equal as
+bytes, all 180 doubles of every sample.  Parity with the CPU oracle itself is helpers.close's 1e-6 relative, k exact."""
+import json
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+from helpers import WEIGHT, close, vec_err
+from push_cases import bits_differ, walking_controller
+from trace_cases import (ONLY_TICK_7, SPLIT_CASES, TRACE_B, TRACE_NT, UNPUSHED, cold_walking_controller, first_difference, push_schedule,
+                         same_bytes, split_trace, trace_against_split, traced, untraced)
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+_CHILD = r"""
+import json, os, sys
+sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
+from linearmpchumanoid_amd import capi
+from trace_cases import SPLIT_CASES, trace_against_split
+capi.lib().lmh_debug_build_flags.restype = int
+res = {"build_flags": capi.lib().lmh_debug_build_flags(), "cases": [trace_against_split(*c) for c in SPLIT_CASES]}
+print(json.dumps(res))
+"""
+
+
+def check_split_result(res, precision, plant, every, nt):
+    print("trace against split launches:", precision, plant, every, nt, res)
+    assert res["samples"] == res["launches"] == nt // every >= 2
+    assert res["finite"]                                            # numbers are compared, not NaNs
+    assert res["moving"] > 0.0                                      # ... and the samples are not copies of one another
+    if precision == 0 and plant == 0:
+        assert res["flags"] == 0 and res["trace_flags"] == 0        # the reference loop in fp64 walks these 520 ticks without a flag
+    assert res["first_diff"] is None, res                           # (sample, robot, double) of the first differing word
+    assert res["final_diff"] == [], res                             # the traced launch leaves what the untraced one leaves
+
+
+@pytest.fixture(scope="module")
+def poison_results():
+    """Every case of SPLIT_CASES on the checker build that fills each robot's LDS with NaNs first, in ONE fresh child process."""
+    from linearmpchumanoid_amd import build as hipbuild
+    assert os.path.exists(hipbuild.build_variant("poison", ["-DLMH_POISON"]))
+    env = {k: v for k, v in os.environ.items() if k not in ("LMH_VARIANT", "LMH_DIAG")}
+    env["LMH_VARIANT"] = "poison"
+    r = subprocess.run([sys.executable, "-c", _CHILD], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    assert res["build_flags"] & 1 == 1, res["build_flags"]
+    return {tuple(c): v for c, v in zip(SPLIT_CASES, res["cases"])}
+
+
+# ------------------------------------------------------------------------------- 1. trace = split launches, bit for bit
+@pytest.mark.parametrize("precision,plant,every,nt", SPLIT_CASES)
+def test_trace_equals_split_launches_bit_for_bit(precision, plant, every, nt):
+    """16 robots on the mixed per-robot walking plan (with the plant: the standing robots of push_cases.scenario_controller), 520 ticks
+    = two full 250-tick chunks and a tail.  Reference: a second handle run with plain lmh_rollout in launches of `every` ticks, state /
+    out / status copied back after each, status [1] / [2] merged as max / OR.  Every sample equal as bytes, all 180 doubles; the final
+    state / out / status / log of the traced launch equal those of an untraced launch of the same length; every compared number
+    finite; no flag in fp64 without the plant.  every = 1 (over 260 ticks), 7 (does not divide the chunk), 250 (a chunk), 260 (more
+    than a chunk) in fp64, 7 in mixed and fp32 precision, each with and without the plant."""
+    check_split_result(trace_against_split(precision, plant, every, nt), precision, plant, every, nt)
+
+
+@pytest.mark.parametrize("precision,plant,every,nt", SPLIT_CASES)
+def test_trace_equals_split_launches_on_the_poisoned_lds_build(poison_results, precision, plant, every, nt):
+    """The same cases on the checker build whose robots start from an LDS image full of NaNs (a fresh child process;
+    lmh_debug_build_flags bit 0 says which library ran): no word of a sample comes from LDS that nobody wrote."""
+    check_split_result(poison_results[(precision, plant, every, nt)], precision, plant, every, nt)
+
+
+# ------------------------------------------------------------------------------- 2. push rule
+@pytest.fixture(scope="module")
+def unscheduled_traces():
+    ctl, q0 = walking_controller(B=TRACE_B)
+    res = {ev: traced(ctl, q0, TRACE_NT, ev)["trace"] for ev in (7, 250)}
+    ctl.close()
+    return res
+
+
+@pytest.mark.parametrize("every", [7, 250])
+def test_a_sample_never_holds_a_push_whose_tick_has_not_started(unscheduled_traces, every):
+    """Per-robot schedules with pushes at ticks 0, 6, 7, 8, 249, 250 and 251 (trace_cases.PUSH_TICKS).  The samples equal a host that
+    runs a handle WITHOUT a schedule, adds each dv itself and stops at the sample ticks (push_cases.host_split).  The robot pushed at
+    tick 7 only: its sample at the end of tick 6 is the unpushed robot's, the next one is not.  The robot without a push: its trace is
+    the trace with no schedule set."""
+    ticks, dv = push_schedule()
+    ctl, q0 = walking_controller(B=TRACE_B)
+    ctl.set_pushes(ticks, dv)
+    got = traced(ctl, q0, TRACE_NT, every)["trace"]
+    ctl.close()
+    ref_ctl, _ = walking_controller(B=TRACE_B)
+    ref, launches = split_trace(ref_ctl, q0, TRACE_NT, every, pushes=(ticks, dv))
+    ref_ctl.close()
+    plain = unscheduled_traces[every]
+    assert launches > TRACE_NT // every                             # the host also stopped at push ticks
+    assert np.isfinite(got).all() and np.isfinite(ref).all()
+    assert first_difference(got, ref) is None
+    assert same_bytes(got[:, UNPUSHED], plain[:, UNPUSHED])
+    moved = [i for i in range(TRACE_B) if not same_bytes(got[:, i], plain[:, i])]
+    assert moved == [i for i in range(TRACE_B) if i != UNPUSHED]   # every pushed robot's trace shows it
+    if every == 7:
+        i = ONLY_TICK_7
+        assert same_bytes(got[0, i], plain[0, i])                   # end of tick 6: the push of tick 7 has not started
+        assert not same_bytes(got[1, i, :60], plain[1, i, :60])     # end of tick 13: it has
+
+
+# ------------------------------------------------------------------------------- 3. composition and restart
+def test_traces_of_two_launches_are_the_trace_of_the_whole():
+    """rollout_trace(280) then rollout_trace(240), every = 7 (280 is a multiple of it), concatenated = rollout_trace(520)."""
+    ctl, q0 = walking_controller(B=TRACE_B)
+    whole = traced(ctl, q0, TRACE_NT, 7)
+    st = ctl.new_state(q0, np.zeros(30), t=0.0)
+    out, status = ctl.new_out(), ctl.new_status()
+    _, _, _, ta = ctl.rollout_trace(st, 280, 7, out, status)
+    torch.cuda.synchronize()
+    first = status.cpu().numpy().copy()
+    _, _, _, tb = ctl.rollout_trace(st, 240, 7, out, status)
+    torch.cuda.synchronize()
+    ctl.close()
+    ta, tb = ta.cpu().numpy(), tb.cpu().numpy()
+    assert ta.shape[0] == 40 and tb.shape[0] == 34 and whole["trace"].shape[0] == 74
+    # status [1] / [2] count from the launch's start: the second launch's samples merge with the first launch's record as max / OR
+    tb[:, :, 177] = np.maximum(tb[:, :, 177], first[None, :, 1])
+    tb[:, :, 178] = (tb[:, :, 178].astype(np.int64) | first[None, :, 2]).astype(np.float64)
+    assert np.isfinite(whole["trace"]).all()
+    assert first_difference(np.concatenate([ta, tb]), whole["trace"]) is None
+    assert same_bytes(st.cpu().numpy(), whole["state"]) and same_bytes(out.cpu().numpy(), whole["out"])
+
+
+def test_the_state_part_of_a_sample_restarts_the_run():
+    """warm_start = 0: a fresh state built from sample 10's state part (tick 77) and run for the remaining ticks reproduces the later
+    samples' state parts bit for bit (and their out parts: with a cold start an evaluation depends on the state record alone)."""
+    ctl, q0 = cold_walking_controller()
+    whole = traced(ctl, q0, TRACE_NT, 7)["trace"]
+    j = 10
+    rest = traced(ctl, q0, TRACE_NT - 7 * (j + 1), 7, state=whole[j, :, :96].copy())["trace"]
+    ctl.close()
+    assert rest.shape[0] == whole.shape[0] - (j + 1) == 63 and np.isfinite(whole).all()
+    assert first_difference(rest[:, :, :176], whole[j + 1:, :, :176]) is None
+    assert not same_bytes(whole[j, :, :60], whole[-1, :, :60])
+
+
+# ------------------------------------------------------------------------------- 4. arguments
+def test_refused_arguments_take_no_launch_slot_and_a_long_period_writes_nothing():
+    from linearmpchumanoid_amd import capi
+    L, vp = capi.lib(), capi.C.c_void_p
+    ctl, q0 = walking_controller(B=TRACE_B)
+    st, out, status = ctl.new_state(q0, np.zeros(30), t=0.0), ctl.new_out(), ctl.new_status()
+    before = st.cpu().numpy().copy()
+    buf = torch.full((1, TRACE_B, capi.TRACE_STRIDE), float("nan"), dtype=torch.float64, device=ctl.device)
+
+    def call(trace, every, nt=20):
+        return L.lmh_rollout_trace(ctl._h, vp(st.data_ptr()), vp(out.data_ptr()), vp(status.data_ptr()), None, nt,
+                                   None if trace is None else vp(trace.data_ptr()), every, ctl._stream())
+
+    for trace, every in ((None, 5), (buf, 0), (buf, -1), (None, -3)):
+        assert call(trace, every) == -2                             # LMH_ERR_BAD_ARG
+        assert "lmh_rollout_trace" in L.lmh_last_error().decode()
+    torch.cuda.synchronize()
+    assert same_bytes(st.cpu().numpy(), before) and torch.isnan(buf).all()      # nothing was enqueued
+    assert [L.lmh_trace_samples(520, 7), L.lmh_trace_samples(5, 9), L.lmh_trace_samples(520, 0), L.lmh_trace_samples(520, -2)] == [74, 0, 0, 0]
+    # a period longer than the launch: zero samples, the buffer stays as it was
+    assert call(buf, 9, nt=5) == 0
+    torch.cuda.synchronize()
+    assert torch.isnan(buf).all() and not same_bytes(st.cpu().numpy(), before)
+    # NULL, 0 is lmh_rollout: five more ticks on st equal ten plain ticks from the start
+    assert call(None, 0, nt=5) == 0
+    torch.cuda.synchronize()
+    ten = untraced(ctl, q0, 10)
+    assert same_bytes(st.cpu().numpy(), ten["state"]) and same_bytes(out.cpu().numpy(), ten["out"])
+    # the refusals took no launch slot: the next plain rollout on this handle is the one a fresh handle runs
+    a = untraced(ctl, q0, 300)
+    fresh, _ = walking_controller(B=TRACE_B)
+    b = untraced(fresh, q0, 300)
+    ctl.close(); fresh.close()
+    assert np.isfinite(a["log"]).all() and bits_differ(a, b) == []
+
+
+def test_two_traced_launches_in_flight_on_two_streams():
+    """Two traced launches of one handle in flight on two streams, each with records and a trace buffer of its own, equal their solo runs."""
+    ctl, q0 = walking_controller(B=TRACE_B)
+    solo = [traced(ctl, q0, nt, ev) for nt, ev in ((TRACE_NT, 7), (300, 50))]
+    streams = [torch.cuda.Stream(device=ctl.device) for _ in range(2)]
+    torch.cuda.synchronize()
+    runs = []
+    for s, (nt, ev) in zip(streams, ((TRACE_NT, 7), (300, 50))):
+        st = ctl.new_state(q0, np.zeros(30), t=0.0)
+        torch.cuda.synchronize()
+        with torch.cuda.stream(s):
+            runs.append((st,) + ctl.rollout_trace(st, nt, ev, log=True))
+    torch.cuda.synchronize()
+    ctl.close()
+    for (st, out, status, lg, tr), ref in zip(runs, solo):
+        assert first_difference(tr.cpu().numpy(), ref["trace"]) is None
+        assert same_bytes(st.cpu().numpy(), ref["state"]) and same_bytes(out.cpu().numpy(), ref["out"])
+        assert same_bytes(status.cpu().numpy(), ref["status"]) and same_bytes(lg.cpu().numpy(), ref["log"])
+
+
+# ------------------------------------------------------------------------------- 5. against the oracle
+ORC_B, ORC_NT, ORC_SEED, ORC_AMP = 4, 64, 20261020, 0.1
+ORC_DT, ORC_MPC_DT, ORC_N = 1e-3, 2e-2, 16                        # bench.py's config 2: 1 kHz control, 16 x 20 ms preview, stance references
+
+
+def test_sampled_balance_against_the_oracle():
+    """The balance task of tests/test_gpu_pushes.py (config-2 settings, stance references, warm start, two planar pushes per robot of at
+    most 0.1 m/s at ticks of [5, 40)), 4 robots, 64 ticks, every = 1: the oracle is ticked one tick at a time (Oracle.rollout of one tick,
+    dv added to the state between the ticks) and q, v, tau and f of EVERY sample are compared within helpers.close's 1e-6 relative, k
+    exact, the sample clock against the oracle's, no flag."""
+    from linearmpchumanoid_amd import trajectories
+    from linearmpchumanoid_amd.controller import BatchedController, default_config
+    from oracle.pyoracle import Oracle
+    o = Oracle(sim_time=1.0, dt=ORC_MPC_DT, horizon_time=ORC_N * ORC_MPC_DT + 1e-9, do_ik=True)
+    q0, zcom = o.robot()["q"].copy(), o.zcom
+    o.close()
+    ticks, dv = trajectories.draw_pushes(ORC_B, 2, (5, 40), ORC_AMP, ORC_SEED)
+    ctl = BatchedController(ORC_B, default_config(dt=ORC_DT, time_horizon=ORC_N * ORC_MPC_DT + 1e-9, z_com=zcom, mpc_dt=ORC_MPC_DT, warm_start=1))
+    ctl.set_refs_stance(ORC_NT * ORC_DT + 1.0, 2)
+    ctl.set_pushes(ticks, dv)
+    got = traced(ctl, q0, ORC_NT, 1)
+    ctl.close()
+    f = BatchedController.split_trace(got["trace"])
+    assert (f["flags"] == 0).all()
+    assert same_bytes(got["trace"][-1, :, :96], got["state"]) and same_bytes(got["trace"][:, :, 96:132], got["log"])
+    worst = dict(q=0.0, v=0.0, tau=0.0, f=0.0)
+    for i in range(ORC_B):
+        o = Oracle(sim_time=ORC_NT * ORC_DT + 1.0, dt=ORC_MPC_DT, horizon_time=ORC_N * ORC_MPC_DT + 1e-9, do_ik=True)
+        state, t = np.concatenate([q0, np.zeros(30)]), 0.0
+        for n in range(ORC_NT):
+            for j in np.flatnonzero(ticks[i] == n):
+                state = state.copy(); state[30:60] += dv[i, j]
+            r = o.rollout(state, t, 1, dt=ORC_DT, log=True)
+            state, t = r["state"], r["t"]
+            assert r["info"][3] == 0, (i, n)
+            worst["q"] = max(worst["q"], vec_err(f["q"][n, i], state[:30])); worst["v"] = max(worst["v"], vec_err(f["v"][n, i], state[30:]))
+            worst["tau"] = max(worst["tau"], vec_err(f["tau"][n, i], r["log"][0, :24]))
+            worst["f"] = max(worst["f"], float(np.abs(f["f"][n, i] - r["log"][0, 24:]).max() / WEIGHT))
+            assert f["k"][n, i] == r["k"][0], (i, n)
+            assert abs(f["t"][n, i] - t) <= 1e-12, (i, n)
+            assert close(f["q"][n, i], state[:30]) and close(f["v"][n, i], state[30:]), (i, n, worst)
+            assert close(f["tau"][n, i], r["log"][0, :24]) and close(f["f"][n, i], r["log"][0, 24:], scale=WEIGHT), (i, n, worst)
+        o.close()
+    print("sampled balance against the oracle, worst relative errors:", worst)
