@@ -46,6 +46,20 @@ extern "C" {
 #define LMH_PUSH_STRIDE 32        /* one timed velocity push: tick (as a double) | dv[30] | pad, see lmh_set_pushes */
 #define LMH_MAX_PUSHES 16         /* push records per robot */
 #define LMH_TRACE_STRIDE 180      /* one trace sample: state(96) | out(80) | status(4, as doubles), see lmh_rollout_trace */
+#define LMH_TERMS_STRIDE 1840     /* one rigid-body terms record, see lmh_terms */
+/* offsets into one terms record (doubles, every array row-major) */
+#define LMH_TERMS_OFF_M 0         /* [30][30] mass matrix, structural zeros written (Dynamics::getM) */
+#define LMH_TERMS_OFF_C 900       /* [30] Coriolis / centrifugal / gravity vector (getC) */
+#define LMH_TERMS_OFF_CG 930      /* [6] base rows of the same vector without gravity (getCg; the rows the controller reads) */
+#define LMH_TERMS_OFF_AG 936      /* [6][30] centroidal momentum matrix, angular rows first (getAG) */
+#define LMH_TERMS_OFF_AGPQP 1116  /* [6] its velocity product AGdot qdot (getAGpqp) */
+#define LMH_TERMS_OFF_J 1122      /* [12][30] feet Jacobian, rows n_R f_R n_L f_L like out.f (Kinematics::feetJacobian) */
+#define LMH_TERMS_OFF_JPQP 1482   /* [12] Jdot qdot of the soles (getJpqp) */
+#define LMH_TERMS_OFF_COM 1494    /* [3] Robot::getCoM */
+#define LMH_TERMS_OFF_COMVEL 1497 /* [3] Robot::getComVel */
+#define LMH_TERMS_OFF_ANGMOM 1500 /* [3] Robot::getComAngMom */
+#define LMH_TERMS_OFF_MASS 1503   /* Robot::getMass of the robot's model */
+#define LMH_TERMS_OFF_T 1504      /* [28][3][4] world transform of every frame, rows 0..2 of Robot::getT (row 3 is 0 0 0 1) */
 
 /* status flags */
 #define LMH_FLAG_QP_MAXITER 1     /* active-set iteration cap hit (reference: "QP failed", controller.cpp:472-476) */
@@ -304,6 +318,34 @@ int lmh_ik(lmh_handle *h, double *d_q, const double *com_target, const double *r
  * DEVICE d_q [B][30] in, d_com [B][3] out. */
 int lmh_robot_com(lmh_handle *h, const double *d_q, double *d_com, void *stream);
 
+/* ---- Rigid-body terms, inverse and forward dynamics for a batch of states (one kernel family of its own, one wave per robot, fp64).
+ * Velocity semantics: these are PURE functions of the (q, v) given.  Every velocity-dependent term (C, Cg, AGpqp, Jpqp, comVel, angMom) is
+ * evaluated at that one v.  lmh_eval evaluates C, Cg and Jdot*qdot at the stale v_prev (Robot::v_, see the state layout above), so the two
+ * agree when the state's v_prev equals v.
+ * Coordinates: M, C, AG and J are in the reference's own generalised velocity, which is not the state's v: the six base entries are
+ * [angular(3) | linear(3)] expressed in the BASE frame, followed by the 24 joint rates (Robot::swapBaseVelocityAndRefToWorldFrame; the QP's
+ * acceleration variable, controller.cpp:138).  qdd and tau30 of the two dynamics calls are in that ordering too; out.qdd of lmh_eval is the
+ * same acceleration turned back to the state's ordering and the world frame.
+ * DEVICE pointers: d_q, d_v, d_qdd, d_tau30 [B][30], d_w [B][12], d_terms [B][LMH_TERMS_STRIDE], d_flags [B] (may be NULL).  d_v == NULL means
+ * v = 0; d_w == NULL means no contact wrench; w has the layout of out.f (n_R f_R n_L f_L) and multiplies J' as is.  Per-robot models
+ * (lmh_set_model with n_models = n_instances) are honoured.  The calls are asynchronous on `stream`, read nothing of the handle but its
+ * model tables and write nothing into it: a later lmh_eval or lmh_rollout is bit for bit unaffected.  NULL for a required pointer returns
+ * LMH_ERR_BAD_ARG before anything is enqueued.
+ *
+ * lmh_terms replaces: Dynamics::computeAll + getM / getC / getCg / getAG / getAGpqp / getJpqp (controller/Dynamics.hpp, src/Dynamics.cpp),
+ * Kinematics::feetJacobian (src/invKinematics.cpp:72-149) and Robot::getT / getCoM / getComVel / getComAngMom (robotInfo/Robot.hpp) for every
+ * robot of the handle.  The record is laid out by the LMH_TERMS_OFF_* offsets above; row and column order of every array is the reference's
+ * Eigen shape.  Cg is its first six entries only: the kernels form only those, and the controller uses only those. */
+int lmh_terms(lmh_handle *h, const double *d_q, const double *d_v, double *d_terms, void *stream);
+/* Build-defined (the reference has no general inverse dynamics: forwardNewtonEuler never uses its qDD, src/Dynamics.cpp:124-146, and tau
+ * comes only from M qdd + C - J'f of the QP's own solution, src/controller.cpp:138).  tau30 = M qdd + C - J'w for ANY qdd and w:
+ * all 30 rows are returned, rows 0..5 are the residual wrench on the floating base, rows 6..29 the joint torques. */
+int lmh_inverse_dynamics(lmh_handle *h, const double *d_q, const double *d_v, const double *d_qdd, const double *d_w, double *d_tau30, void *stream);
+/* Build-defined, the inverse of the call above: solves M qdd = tau30 + J'w - C by an LDL' factorisation of the dense mass matrix without
+ * pivoting (M is symmetric positive definite).  d_flags[i]: LMH_FLAG_NOT_SPD when a pivot of robot i's matrix was not positive,
+ * LMH_FLAG_NONFINITE when its result holds a NaN / Inf; neither stops the other robots. */
+int lmh_forward_dynamics(lmh_handle *h, const double *d_q, const double *d_v, const double *d_tau30, const double *d_w, double *d_qdd, int32_t *d_flags, void *stream);
+
 /* host-buffer convenience used by the C++ shim (B instances, staged through internal
  * device buffers, synchronous): q/dq [B][30], t, outputs tau[B][24], f[B][12], qdd[B][30] */
 int lmh_eval_host(lmh_handle *h, const double *q, const double *dq, double t,
@@ -314,6 +356,9 @@ int lmh_robot_com_host(lmh_handle *h, const double *q, double *com);
 int lmh_last_out_host(lmh_handle *h, double *out);
 /* Kinematics::compute + Robot::getCoM through host buffers: q [B][30] in/out, com [B][3] out, iters [B] out */
 int lmh_ik_host(lmh_handle *h, double *q, const double *com_target, const double *rf6, const double *lf6, double *com, int32_t *iters);
+/* lmh_terms through host buffers (Dynamics::computeAll of the shim): q [B][30], v [B][30] or NULL (= 0) in, terms [B][LMH_TERMS_STRIDE] out.
+ * Staged through a device buffer the handle allocates on the first call; synchronous. */
+int lmh_terms_host(lmh_handle *h, const double *q, const double *v, double *terms);
 /* overwrite the staged Robot::v_ (v_prev) used by the next lmh_eval_host call: HOST [B][30] */
 int lmh_set_prev_velocity_host(lmh_handle *h, const double *v);
 /* hipStreamSynchronize(stream), then LMH_ERR_UNFINISHED if a completed lmh_rollout of this handle reported an incomplete launch (see there) */

@@ -21,6 +21,13 @@ SEG_STRIDE = 52
 PUSH_STRIDE = 32              # one timed velocity push: tick (as a double) | dv[30] | pad (lmh_set_pushes)
 MAX_PUSHES = 16               # push records per robot
 TRACE_STRIDE = 180            # one trace sample: state(96) | out(80) | status(4, as doubles) (lmh_rollout_trace)
+TERMS_STRIDE = 1840           # one rigid-body terms record (lmh_terms)
+# name -> (offset, shape) inside a terms record: the LMH_TERMS_OFF_* defines of include/lmh.h, every array row-major
+TERMS_FIELDS = {
+    "M": (0, (30, 30)), "C": (900, (30,)), "Cg": (930, (6,)), "AG": (936, (6, 30)), "AGpqp": (1116, (6,)),
+    "J": (1122, (12, 30)), "Jpqp": (1482, (12,)), "CoM": (1494, (3,)), "comVel": (1497, (3,)), "angMom": (1500, (3,)),
+    "mass": (1503, ()), "T": (1504, (28, 3, 4)),
+}
 
 FLAG_QP_MAXITER = 1
 FLAG_NONFINITE = 2
@@ -46,6 +53,7 @@ EXPORTS = [
     "lmh_gen_walk_batch", "lmh_gen_jump_batch", "lmh_set_plans", "lmh_plans_per_instance", "lmh_get_plan",
     "lmh_set_pushes", "lmh_num_pushes", "lmh_pushes_per_instance", "lmh_get_pushes",
     "lmh_rollout_trace", "lmh_trace_samples", "lmh_write_trace", "lmh_read_trace",
+    "lmh_terms", "lmh_inverse_dynamics", "lmh_forward_dynamics", "lmh_terms_host",
 ]
 
 
@@ -115,6 +123,10 @@ def lib():
     L.lmh_last_out_host.argtypes = [vp, vp]
     L.lmh_robot_com_host.argtypes = [vp, vp, vp]
     L.lmh_ik_host.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.lmh_terms.argtypes = [vp, vp, vp, vp, vp]
+    L.lmh_inverse_dynamics.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.lmh_forward_dynamics.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lmh_terms_host.argtypes = [vp, vp, vp, vp]
     L.lmh_set_segments.argtypes = [vp, vp, ip, vp, ip]
     L.lmh_set_xscale.argtypes = [vp, vp, ip]
     u64, u64p, dpp = C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)

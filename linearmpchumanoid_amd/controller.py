@@ -338,6 +338,53 @@ class BatchedController:
         check(capi.lib().lmh_robot_com(self._h, _dev_ptr(q), _dev_ptr(com), self._stream()))
         return com
 
+    # -- rigid-body terms, inverse and forward dynamics (include/lmh.h, lmh_terms): pure functions of the (q, v) given
+    def _batch(self, name, t, width, optional=False):
+        """A [B,width] float64 tensor on this controller's device, made contiguous; None passes when optional."""
+        if t is None:
+            if optional:
+                return None
+            raise ValueError(f"{name} is required")
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != (self.B, width) or t.device != self.device:
+            raise ValueError(f"{name} must be a [{self.B},{width}] float64 tensor on {self.device}")
+        return t.contiguous()
+
+    def terms(self, q, v=None):
+        """Dynamics::computeAll + its getters, Kinematics::feetJacobian and Robot::getT / getCoM / getComVel / getComAngMom for q, v
+        [B,30] (device tensors; v=None is v = 0) -> [B,1840], one record per robot (split_terms names its fields).  Every
+        velocity-dependent term is taken at the v given."""
+        q, v = self._batch("q", q, 30), self._batch("v", v, 30, optional=True)
+        t = torch.empty((self.B, capi.TERMS_STRIDE), dtype=torch.float64, device=self.device)
+        check(capi.lib().lmh_terms(self._h, _dev_ptr(q), None if v is None else _dev_ptr(v), _dev_ptr(t), self._stream()))
+        return t
+
+    def inverse_dynamics(self, q, v, qdd, w=None):
+        """tau30 = M qdd + C - J'w -> [B,30]: rows 0..5 the residual wrench on the base, 6..29 the joint torques.  qdd is in the
+        coordinates of M (include/lmh.h); w [B,12] has the layout of out.f (w=None: no contact wrench); v=None is v = 0."""
+        q, v = self._batch("q", q, 30), self._batch("v", v, 30, optional=True)
+        qdd, w = self._batch("qdd", qdd, 30), self._batch("w", w, 12, optional=True)
+        tau = torch.empty((self.B, 30), dtype=torch.float64, device=self.device)
+        check(capi.lib().lmh_inverse_dynamics(self._h, _dev_ptr(q), None if v is None else _dev_ptr(v), _dev_ptr(qdd),
+                                              None if w is None else _dev_ptr(w), _dev_ptr(tau), self._stream()))
+        return tau
+
+    def forward_dynamics(self, q, v, tau, w=None):
+        """Solves M qdd = tau30 + J'w - C -> (qdd [B,30], flags [B] int32: FLAG_NOT_SPD / FLAG_NONFINITE per robot)."""
+        q, v = self._batch("q", q, 30), self._batch("v", v, 30, optional=True)
+        tau, w = self._batch("tau", tau, 30), self._batch("w", w, 12, optional=True)
+        qdd = torch.empty((self.B, 30), dtype=torch.float64, device=self.device)
+        flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+        check(capi.lib().lmh_forward_dynamics(self._h, _dev_ptr(q), None if v is None else _dev_ptr(v), _dev_ptr(tau),
+                                              None if w is None else _dev_ptr(w), _dev_ptr(qdd), _dev_ptr(flags), self._stream()))
+        return qdd, flags
+
+    @staticmethod
+    def split_terms(t):
+        """Named views of terms records [.., 1840] (tensor or array): M [..,30,30], C, Cg (first six), AG [..,6,30], AGpqp, J [..,12,30],
+        Jpqp, CoM, comVel, angMom, mass [..], T [..,28,3,4] -- capi.TERMS_FIELDS."""
+        lead = tuple(t.shape[:-1])
+        return {k: t[..., o:o + int(np.prod(s, dtype=np.int64))].reshape(lead + tuple(s)) for k, (o, s) in capi.TERMS_FIELDS.items()}
+
     def make_summary(self, state, out, status):
         """End-of-run summary [B,16] (include/lmh.h lmh_make_summary): the record the RCCL gather moves."""
         s = torch.empty((self.B, capi.SUMMARY_WIDTH), dtype=torch.float64, device=self.device)

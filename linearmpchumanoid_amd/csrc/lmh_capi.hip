@@ -22,6 +22,7 @@ extern "C" void lmh_launch_gen_walk(const LmhWalkSpec *W, double *zx, double *zy
 extern "C" void lmh_launch_gen_jump(int n, double time_step, double stance_time, double flight_time, double *zx, double *zy, uint8_t *phase, hipStream_t s);
 extern "C" void lmh_launch_gen_walk_batch(const LmhWalkSpec *d_specs, int n_plans, int seg_stride, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos, hipStream_t s);
 extern "C" void lmh_launch_gen_jump_batch(int n, double time_step, const LmhJumpSpec *d_specs, int n_plans, double *zx, double *zy, uint8_t *phase, hipStream_t s);
+extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *q, const double *v, const double *x, const double *w, double *res, int32_t *flags, hipStream_t s);
 extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
 
 static thread_local std::string g_err;
@@ -68,6 +69,7 @@ struct lmh_handle {
     int n_push = 0, n_push_sets = 1;
     // staging for the host-buffer convenience calls
     DevBuf<double> d_state, d_out;
+    DevBuf<double> d_terms;           // lmh_terms_host only: q | v | terms records, allocated on its first call
     DevBuf<int32_t> d_status;
     std::vector<double> h_state, h_out, h_gain;
     std::vector<int32_t> h_status;
@@ -743,6 +745,49 @@ extern "C" int lmh_robot_com_host(lmh_handle *h, const double *q, double *com)
     rc = lmh_robot_com(h, h->d_state.get(), h->d_out.get(), nullptr);
     if (rc) return rc;
     HIPCHK(hipMemcpy(com, h->d_out.get(), sizeof(double) * 3 * (size_t)h->B, hipMemcpyDeviceToHost));
+    return LMH_OK;
+}
+
+// ---------------------------------------------------------------------------- rigid-body terms, inverse / forward dynamics
+// mode: 0 terms, 1 inverse dynamics, 2 forward dynamics (lmh_kernels.hip, lmh_terms_kernel).  The kernels read h->P's model tables only.
+static int terms_body(lmh_handle *h, int mode, const double *d_q, const double *d_v, const double *d_x, const double *d_w, double *d_res, int32_t *d_flags, void *stream)
+{
+    int rc = ready(h); if (rc) return rc;
+    if (!d_q || !d_res || (mode != 0 && !d_x)) return fail(LMH_ERR_BAD_ARG, "null device pointer");
+    HIPCHK(hipSetDevice(h->device));
+    lmh_launch_terms(&h->P, mode, d_q, d_v, d_x, d_w, d_res, d_flags, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return LMH_OK;
+}
+
+extern "C" int lmh_terms(lmh_handle *h, const double *d_q, const double *d_v, double *d_terms, void *stream)
+{
+    return terms_body(h, 0, d_q, d_v, nullptr, nullptr, d_terms, nullptr, stream);
+}
+
+extern "C" int lmh_inverse_dynamics(lmh_handle *h, const double *d_q, const double *d_v, const double *d_qdd, const double *d_w, double *d_tau30, void *stream)
+{
+    return terms_body(h, 1, d_q, d_v, d_qdd, d_w, d_tau30, nullptr, stream);
+}
+
+extern "C" int lmh_forward_dynamics(lmh_handle *h, const double *d_q, const double *d_v, const double *d_tau30, const double *d_w, double *d_qdd, int32_t *d_flags, void *stream)
+{
+    return terms_body(h, 2, d_q, d_v, d_tau30, d_w, d_qdd, d_flags, stream);
+}
+
+extern "C" int lmh_terms_host(lmh_handle *h, const double *q, const double *v, double *terms)
+{
+    int rc = ready(h); if (rc) return rc;
+    if (!q || !terms) return fail(LMH_ERR_BAD_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t n = (size_t)h->B;
+    if (!h->d_terms.get()) HIPCHK(h->d_terms.alloc((60 + LMH_TERMS_STRIDE) * n));
+    double *d_q = h->d_terms.get(), *d_v = d_q + 30 * n, *d_t = d_q + 60 * n;
+    HIPCHK(hipMemcpy(d_q, q, sizeof(double) * 30 * n, hipMemcpyHostToDevice));
+    if (v) HIPCHK(hipMemcpy(d_v, v, sizeof(double) * 30 * n, hipMemcpyHostToDevice));
+    rc = lmh_terms(h, d_q, v ? d_v : nullptr, d_t, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(terms, d_t, sizeof(double) * LMH_TERMS_STRIDE * n, hipMemcpyDeviceToHost));
     return LMH_OK;
 }
 

@@ -4268,6 +4268,151 @@ extern "C" void lmh_launch_com(const LmhDevParams *P, const double *q, double *c
 }
 
 #endif
+// ============================================================================ rigid-body terms, inverse and forward dynamics
+// lmh_terms / lmh_inverse_dynamics / lmh_forward_dynamics (include/lmh.h): Robot::updateState + Dynamics::computeAll +
+// Kinematics::feetJacobian as PURE functions of the (q, v) given -- the stale-velocity slot (Robot::v_, P_VP) is loaded with the same v, so
+// every velocity product is taken at that one velocity.  One wave per robot in the single-wave schedule of the debug evaluation kernel
+// (kinematics -> X images -> Newton-Euler -> CRBA -> Jacobian); no reference plan, MPC step, QP or clock is touched.
+// TERMS expands the compact on-chip forms (Mtop | Hl, Jc) into the dense record; INVDYN forms tau30 = M qdd + C - J'w from them;
+// FWDDYN builds the dense [M | tau30 + J'w - C] (30 x 31, row stride 31) behind the robot's image and eliminates it without pivoting
+// (right-looking LDL': the multipliers are L, the pivots D; M is SPD), the pattern of the IK kernel's solve less its pivot search.
+enum { TM_TERMS = 0, TM_INVDYN = 1, TM_FWDDYN = 2 };
+enum { TM_A = LDS_DOUBLES, TM_X = LDS_DOUBLES + 930, TM_W = LDS_DOUBLES + 960, TM_LDS = LDS_DOUBLES + 1040 };    // the IK kernel's extent
+static_assert(TM_LDS * sizeof(double) <= 65536, "one workgroup's LDS");
+static_assert(LMH_TERMS_OFF_T + 336 == LMH_TERMS_STRIDE && LMH_TERMS_OFF_COMVEL == LMH_TERMS_OFF_COM + 3 && LMH_TERMS_OFF_ANGMOM == LMH_TERMS_OFF_COM + 6
+              && LMH_TERMS_OFF_MASS == LMH_TERMS_OFF_COM + 9 && P_COMV == P_COM + 3 && P_ANGM == P_COM + 6, "CoM | comVel | angMom are stored as one run");
+
+// M[r][c] of the dense 30 x 30 mass matrix from the compact store: Mtop = [Ic0 | F2] (6 x 30), Hl = the joint block of every limb, row per joint
+__device__ __forceinline__ double mdense(const double *L, int r, int c)
+{
+    const bool top = r < 6, left = c < 6;
+    const int a = top ? 0 : r - 6, b = c - 6 - f_jstart(a), nl = (a < 12) ? 6 : (a < 22) ? 5 : 2;
+    const bool limb = (b >= 0) && (b < nl);
+    const double v = L[top ? P_MTOP + 30 * r + c : left ? P_MTOP + 30 * c + r : limb ? P_HL + 6 * a + b : (int)P_MTOP];
+    return (top || left || limb) ? v : 0.0;
+}
+
+// Dynamics::centroidalMatrixAndBias (AG, Dynamics.cpp:103-121) + Robot::computeComMomentum (Robot.cpp:300-310) with the expressions of
+// refs_chain_a, without the MPC step and the PD law that ride on them there: all six rows of AG, comVel = AG_lin vhat / m, angMom = AG_ang vhat
+__device__ __forceinline__ void terms_momentum(double *L, double mass)
+{
+    const int lane = LANE;
+    const double *T0 = L + P_TB;
+    const double p0 = L[P_MTOP + 30 * 2 + 4] / mass, p1 = L[P_MTOP + 30 * 0 + 5] / mass, p2 = L[P_MTOP + 30 * 1 + 3] / mass;
+    for (int e = lane; e < 180; e += 64) {
+        const int r6 = e / 30, c = e % 30, r = r6 % 3;
+        const double *Mt = L + P_MTOP + c;
+        const double R0 = T0[4 * r], R1 = T0[4 * r + 1], R2 = T0[4 * r + 2];
+        const double u0 = -(R1 * p2 + R2 * (-p1)), u1 = -(R0 * (-p2) + R2 * p0), u2 = -(R0 * p1 + R1 * (-p0));
+        const double lin = R0 * Mt[90] + R1 * Mt[120] + R2 * Mt[150];
+        const double ang = R0 * Mt[0] + R1 * Mt[30] + R2 * Mt[60] + u0 * Mt[90] + u1 * Mt[120] + u2 * Mt[150];
+        L[P_AG + e] = (r6 < 3) ? ang : lin;
+    }
+    WSYNC();
+    if (lane < 6) {
+        double s = 0.0;
+        for (int c = 0; c < 30; c++) s += L[P_AG + 30 * lane + c] * L[P_VHN + c];
+        L[(lane < 3) ? P_ANGM + lane : P_COMV + lane - 3] = (lane < 3) ? s : s / mass;
+    }
+    WSYNC();
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(64) lmh_terms_kernel(LmhDevParams P_arg, const double *q, const double *v, const double *x, const double *w, double *res, int32_t *flags_out)
+{
+    LmhCParams &P = LMH_KERNARG_PARAMS();
+    __shared__ double L[MODE == TM_TERMS ? (int)LDS_DOUBLES : (int)TM_LDS];
+    const int inst = blockIdx.x;
+    if (inst >= P.n_instances) return;
+    const int lane = LANE;
+    SET_GDBG(nullptr);
+    load_common(L, P, inst);
+    if (lane < 30) {
+        const double vv = v ? v[30 * (size_t)inst + lane] : 0.0;
+        L[P_Q + lane] = q[30 * (size_t)inst + lane];
+        L[P_V + lane] = vv; L[P_VP + lane] = vv;                   // one velocity for every term
+    }
+    if constexpr (MODE != TM_TERMS) {
+        if (lane < 30) L[TM_X + lane] = x[30 * (size_t)inst + lane];
+        else if (lane >= 32 && lane < 44) L[TM_W + lane - 32] = w ? w[12 * (size_t)inst + lane - 32] : 0.0;
+    }
+    WSYNC();
+    const IbSel ibsel = ib_select();
+    phase_fk<double>(L, P.gcol + 228);
+    phase_com_x<1, double>(L, 0);
+    if constexpr (MODE == TM_TERMS) {                              // the world transforms, before the Newton-Euler arrays take their place
+        double *o = res + (size_t)LMH_TERMS_STRIDE * inst + LMH_TERMS_OFF_T;
+        for (int e = lane; e < 336; e += 64) o[e] = L[A_T + e];
+    }
+    phase_newton_euler<double>(L);
+    phase_crba<double>(L, ibsel);
+    phase_jacobian<double>(L);
+    if constexpr (MODE == TM_TERMS) {
+        const double mass = L[P_MODEL + 392];
+        refs_jpqp(L);
+        terms_momentum(L, mass);
+        refs_agpqp<true>(L, mass, true);
+        WSYNC();
+        double *o = res + (size_t)LMH_TERMS_STRIDE * inst;
+        for (int e = lane; e < 900; e += 64) o[LMH_TERMS_OFF_M + e] = mdense(L, e / 30, e % 30);
+        for (int e = lane; e < 360; e += 64) o[LMH_TERMS_OFF_J + e] = jdense(L, e / 30, e % 30);
+        for (int e = lane; e < 180; e += 64) o[LMH_TERMS_OFF_AG + e] = L[P_AG + e];
+        if (lane < 30) o[LMH_TERMS_OFF_C + lane] = L[P_C + lane];
+        else if (lane < 36) o[LMH_TERMS_OFF_CG + lane - 30] = L[P_C + lane - 30] - L[P_CG + lane - 30];        // P_CG holds Ic_0 gamma_0 (phase_crba)
+        else if (lane < 42) o[LMH_TERMS_OFF_AGPQP + lane - 36] = L[P_AGPQP + lane - 36];
+        else if (lane < 54) o[LMH_TERMS_OFF_JPQP + lane - 42] = L[P_JPQP + lane - 42];
+        else o[LMH_TERMS_OFF_COM + lane - 54] = (lane < 63) ? L[P_COM + lane - 54] : mass;                     // CoM | comVel | angMom | mass
+    } else {
+        double jw = 0.0;                                           // (J'w)[lane]: base and leg columns only
+        if (lane < 18) {
+#pragma unroll
+            for (int row = 0; row < 12; row++) jw += jdense(L, row, lane) * L[TM_W + row];
+        }
+        if constexpr (MODE == TM_INVDYN) {
+            if (lane < 30) {
+                double s = 0.0;
+                for (int c = 0; c < 30; c++) s += mdense(L, lane, c) * L[TM_X + c];
+                res[30 * (size_t)inst + lane] = s + L[P_C + lane] - jw;
+            }
+        } else {
+            int flags = 0;
+            for (int e = lane; e < 900; e += 64) L[TM_A + 31 * (e / 30) + e % 30] = mdense(L, e / 30, e % 30);
+            if (lane < 30) L[TM_A + 31 * lane + 30] = L[TM_X + lane] + jw - L[P_C + lane];
+            WSYNC();
+            for (int c = 0; c < 30; c++) {
+                const double piv = L[TM_A + 31 * c + c];
+                if (!(piv > 0.0)) flags |= LMH_FLAG_NOT_SPD;       // (every lane reads the same pivot)
+                const int nr = 29 - c, nc = 30 - c;                // rows below, columns right (incl. rhs)
+                for (int el = lane; el < nr * nc; el += 64) {
+                    const int r = c + 1 + el / nc, cc = c + 1 + el % nc;
+                    L[TM_A + 31 * r + cc] -= (L[TM_A + 31 * r + c] / piv) * L[TM_A + 31 * c + cc];
+                }
+                WSYNC();
+            }
+            for (int r = 29; r >= 0; r--) {                        // back substitution
+                const double xr = L[TM_A + 31 * r + 30] / L[TM_A + 31 * r + r];
+                WSYNC();
+                if (lane < r) L[TM_A + 31 * lane + 30] -= L[TM_A + 31 * lane + r] * xr;
+                if (lane == 0) L[TM_X + r] = xr;
+                WSYNC();
+            }
+            const double xo = L[TM_X + ((lane < 30) ? lane : 0)];
+            if (__ballot(!(fabs(xo) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
+            if (lane < 30) res[30 * (size_t)inst + lane] = xo;
+            if (lane == 0 && flags_out) flags_out[inst] = flags;
+        }
+    }
+}
+#ifndef LMH_ROLLOUT_ONLY
+extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *q, const double *v, const double *x, const double *w, double *res, int32_t *flags, hipStream_t s)
+{
+    const dim3 grid(P->n_instances), block(64);
+    if (mode == TM_TERMS) hipLaunchKernelGGL(lmh_terms_kernel<TM_TERMS>, grid, block, 0, s, *P, q, v, x, w, res, flags);
+    else if (mode == TM_INVDYN) hipLaunchKernelGGL(lmh_terms_kernel<TM_INVDYN>, grid, block, 0, s, *P, q, v, x, w, res, flags);
+    else hipLaunchKernelGGL(lmh_terms_kernel<TM_FWDDYN>, grid, block, 0, s, *P, q, v, x, w, res, flags);
+}
+
+#endif
 // ============================================================================ reference generators on the device
 // The reference declares a walking generator (ZMP(Task, numSteps, timePerStep, simulationTime) / walkZMP, zmpGeneration.hpp:15-22) but never
 // defines it, and produces one polynomial set per step with footCoeffTrajectory / findPolyCoeff (footRefTrajectory.cpp:4-47,

@@ -2,6 +2,7 @@
 #include <Eigen/Dense>
 #include <vector>
 #include "linearMpcHumanoid/controller/mpcLinearPendulum.hpp"
+#include "linearMpcHumanoid/controller/Dynamics.hpp"
 #include "linearMpcHumanoid/controller/invKinematics.hpp"
 #include "linearMpcHumanoid/robotInfo/Robot.hpp"
 #include "linearMpcHumanoid/trajectories/zmpGeneration.hpp"

@@ -1,6 +1,7 @@
 #pragma once
 #include <Eigen/Dense>
 #include <cmath>
+#include <vector>
 #include "linearMpcHumanoid/general/generalizedFunctions.hpp"
 #define NUM_JOINTS 30
 #define NUM_ACTUAL_JOINTS 24
@@ -20,13 +21,18 @@ public:
     const Eigen::VectorXd &getJointsVelocity() const { return v_; }
     const Eigen::Vector3d &getCoM() const { return CoM_; }
     const Eigen::Vector3d &getComVel() const { return comVel_; }
+    const Eigen::Vector3d &getComAngMom() const { return comAngMom_; }   // of the last Dynamics::computeAll(robot) (zero before)
+    const std::vector<Eigen::Matrix4d> &getT() const;               // world transform of every frame at the current q (one lmh_terms_host call)
     double getMass() const { return mass_; }
     void updateState(const Eigen::VectorXd &q_new);                 // Robot.cpp:264-269 (FK + CoM on the GPU)
     // used by the shim's Controller / Kinematics
     void setFromDevice(const double *q, const double *v, const double *com, const double *comVel);
+    void setMomentumFromDevice(const double *comVel, const double *angMom) const;    // Dynamics::computeAll: the pair Robot::computeComMomentum forms
 private:
     Eigen::VectorXd q_, v_;
-    Eigen::Vector3d CoM_, comVel_;
+    Eigen::Vector3d CoM_;
+    mutable Eigen::Vector3d comVel_, comAngMom_;
+    mutable std::vector<Eigen::Matrix4d> T_;                        // filled by getT()
     double mass_ = 0;
 };
 Eigen::VectorXd initialConfiguration();                             // Robot.cpp:242-251

@@ -130,6 +130,45 @@ void Robot::setFromDevice(const double *q, const double *v, const double *com, c
     for (int i = 0; i < 30; i++) { if (q) q_(i) = q[i]; if (v) v_(i) = v[i]; }
     for (int i = 0; i < 3; i++) { if (com) CoM_(i) = com[i]; if (comVel) comVel_(i) = comVel[i]; }
 }
+void Robot::setMomentumFromDevice(const double *comVel, const double *angMom) const
+{
+    for (int i = 0; i < 3; i++) { comVel_(i) = comVel[i]; comAngMom_(i) = angMom[i]; }
+}
+const std::vector<Eigen::Matrix4d> &Robot::getT() const
+{
+    std::vector<double> t(LMH_TERMS_STRIDE);
+    if (lmh_terms_host(scratch_handle(), q_.data(), v_.data(), t.data()) != LMH_OK) die("Robot::getT");
+    T_.assign(NUM_FRAMES, Eigen::Matrix4d::Identity());
+    for (int f = 0; f < NUM_FRAMES; f++)
+        for (int r = 0; r < 3; r++)
+            for (int c = 0; c < 4; c++) T_[static_cast<size_t>(f)](r, c) = t[static_cast<size_t>(LMH_TERMS_OFF_T + 12 * f + 4 * r + c)];
+    return T_;
+}
+
+// ------------------------------------------------------------------ Dynamics
+void Dynamics::computeAll(const Robot &robot)
+{
+    std::vector<double> t(LMH_TERMS_STRIDE);
+    if (lmh_terms_host(scratch_handle(), robot.getJoints().data(), robot.getJointsVelocity().data(), t.data()) != LMH_OK) die("Dynamics::computeAll");
+    auto vec = [&t](int off, int n, int filled) {
+        Eigen::VectorXd x = Eigen::VectorXd::Zero(n);
+        for (int i = 0; i < filled; i++) x(i) = t[static_cast<size_t>(off + i)];
+        return x;
+    };
+    auto mat = [&t](int off, int r, int c) {
+        Eigen::MatrixXd m(r, c);
+        for (int i = 0; i < r; i++)
+            for (int j = 0; j < c; j++) m(i, j) = t[static_cast<size_t>(off + c * i + j)];
+        return m;
+    };
+    M_ = mat(LMH_TERMS_OFF_M, 30, 30);
+    AG_ = mat(LMH_TERMS_OFF_AG, 6, 30);
+    C_ = vec(LMH_TERMS_OFF_C, 30, 30);
+    Cg_ = vec(LMH_TERMS_OFF_CG, 30, 6);
+    AGpqp_ = vec(LMH_TERMS_OFF_AGPQP, 6, 6);
+    Jpqp_ = vec(LMH_TERMS_OFF_JPQP, 12, 12);
+    robot.setMomentumFromDevice(t.data() + LMH_TERMS_OFF_COMVEL, t.data() + LMH_TERMS_OFF_ANGMOM);
+}
 
 // ------------------------------------------------------------------ Kinematics
 Eigen::VectorXd Kinematics::desiredOperationalState(const Robot &robot, const Eigen::VectorXd &Rf, const Eigen::VectorXd &Lf, const Eigen::Vector3d &com)

@@ -1,0 +1,350 @@
+"""lmh_terms / lmh_inverse_dynamics / lmh_forward_dynamics on the GPU against the CPU oracle.
+
+States: helpers.posture_sweep(q0, 16, band=1.0) around the IK start posture -- the draw of the posture-sweep parity test.  The oracle's stale
+velocity (Robot::v_) is set to the state's v, so its terms are the pure (q, v) ones the new calls return.  Tolerances: those of
+test_stage_parity_single_evaluation / test_stage_parity_over_the_joint_range for the same quantities from the same phase code (1e-11); the
+forward dynamics is accepted on the backward error of an SPD factorisation (1e-12, about 300 x its 30 * 2^-53 bound) and on the forward
+error that bound implies (1e-12 * cond(M))."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+import pytest
+import torch
+
+from helpers import WEIGHT, close_on, dense_terms_from_debug, oracle_system, posture_sweep, rel_err
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+DT, TH = 1e-3, 0.016
+B = 16
+
+
+def _controller(n, zcom, **kw):
+    from linearmpchumanoid_amd.controller import BatchedController, default_config
+    return BatchedController(n, default_config(dt=DT, time_horizon=TH, z_com=zcom, **kw))
+
+
+def _dev(ctl, a):
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(ctl.device)
+
+
+def _oracle_terms(q, v, raw_links=None):
+    o = oracle_system(DT, TH, raw_links=raw_links)
+    o.set_prev_velocity(v)
+    o.eval(q, v, 0.0)
+    return dict(t=o.terms(), rb=o.robot(), mass=o.mass)
+
+
+_cache = {}
+
+
+def _setup():
+    """The 16 states, their oracle terms (computed once, shared, never written) and the random qdd / w of the dynamics tests."""
+    if _cache:
+        return _cache
+    from linearmpchumanoid_amd.controller import ik_start_posture
+    q0, zcom = ik_start_posture()
+    q, v, _ = posture_sweep(q0, B, band=1.0)
+    ref = [_oracle_terms(q[i], v[i]) for i in range(B)]
+    qdd = np.random.default_rng(20261101).normal(0.0, 10.0, (B, 30))
+    w = np.random.default_rng(20261102).normal(0.0, WEIGHT / 2, (B, 12))
+    tau = np.stack([r["t"]["M"] @ qdd[i] + r["t"]["C"] - r["t"]["J"].T @ w[i] for i, r in enumerate(ref)])
+    _cache.update(q0=q0, zcom=zcom, q=q, v=v, ref=ref, qdd=qdd, w=w, tau=tau)
+    return _cache
+
+
+def _check_terms(rec, r, v, mass, worst, tag):
+    """One record against one oracle evaluation: the checks of test 1."""
+    from linearmpchumanoid_amd.controller import BatchedController
+    s = BatchedController.split_terms(rec)
+    t, rb = r["t"], r["rb"]
+    bad = []
+
+    def check(name, err, tol):
+        worst[name] = max(worst.get(name, 0.0), float(err))
+        if not err < tol:
+            bad.append((tag, name, float(err)))
+
+    for name, a, b in (("M", s["M"], t["M"]), ("C", s["C"], t["C"]), ("AG", s["AG"], t["AG"]), ("J", s["J"], t["J"]),
+                       ("T", s["T"], t["T"][:, :3, :]), ("CoM", s["CoM"], rb["CoM"])):
+        check(name, rel_err(a, b), 1e-11)
+    cs = np.abs(t["C"]).max()                                     # velocity-product terms: differences of O(50) quantities
+    check("Cg", np.abs(s["Cg"] - t["Cg"][:6]).max() / cs, 1e-11)
+    check("AGpqp", np.abs(s["AGpqp"] - t["AGpqp"]).max() / cs, 1e-11)
+    check("Jpqp", np.abs(s["Jpqp"] - t["Jpqp"]).max() / cs, 1e-11)
+    ms = np.abs(t["AG"]).max() * max(np.abs(v).max(), 1e-300)     # momenta: AG vhat, sums of |AG| |vhat| terms
+    check("comVel", np.abs(s["comVel"] - rb["comVel"]).max() * mass / ms, 1e-11)      # (m comVel = AG_lin vhat, as the posture sweep scales it)
+    check("angMom", np.abs(s["angMom"] - rb["angMom"]).max() / ms, 1e-11)
+    assert float(s["mass"]) == mass, (tag, float(s["mass"]), mass)
+    return bad
+
+
+def test_terms_parity():
+    S = _setup()
+    ctl = _controller(B, S["zcom"])
+    rec = ctl.terms(_dev(ctl, S["q"]), _dev(ctl, S["v"]))
+    torch.cuda.synchronize()
+    rec = rec.cpu().numpy()
+    masses = ctl.mass()
+    worst, bad = {}, []
+    for i in range(B):
+        bad += _check_terms(rec[i], S["ref"][i], S["v"][i], float(masses[0]), worst, i)
+    print("\nterms parity, band 1.0: " + ", ".join("%s %.2e" % kv for kv in sorted(worst.items())))
+    assert not bad, bad[:12]
+    # v = None is v = 0: the velocity products vanish from C (gravity stays), Cg, AGpqp, Jpqp and the momenta are zero
+    z = ctl.terms(_dev(ctl, S["q"]))
+    z0 = ctl.terms(_dev(ctl, S["q"]), _dev(ctl, np.zeros((B, 30))))
+    torch.cuda.synchronize()
+    assert torch.equal(z, z0)
+    sz = ctl.split_terms(z.cpu().numpy())
+    assert np.abs(sz["comVel"]).max() == 0.0 and np.abs(sz["angMom"]).max() == 0.0
+    assert np.abs(sz["Cg"]).max() < 1e-11 * np.abs(sz["C"]).max()
+    assert np.array_equal(sz["M"], ctl.split_terms(rec)["M"])
+
+
+def test_terms_with_per_robot_models():
+    """Raw link tables randomised as test_gpu_parity does for config 4: a kernel that reads model 0 for everyone fails."""
+    from linearmpchumanoid_amd.controller import nominal_links
+    S = _setup()
+    n = 4
+    raw = np.tile(nominal_links(), (n, 1, 1))
+    rng = np.random.default_rng(20260004)
+    raw[:, :, 0] *= rng.uniform(0.9, 1.1, (n, 28))
+    raw[:, :, 1:4] += rng.uniform(-5e-3, 5e-3, (n, 28, 3)) * (raw[:, :, 0:1] > 0)
+    ctl = _controller(n, S["zcom"])
+    ctl.set_model(raw)
+    masses = ctl.mass()
+    rec = ctl.terms(_dev(ctl, S["q"][:n]), _dev(ctl, S["v"][:n]))
+    torch.cuda.synchronize()
+    rec = rec.cpu().numpy()
+    worst, bad = {}, []
+    for i in range(n):
+        r = _oracle_terms(S["q"][i], S["v"][i], raw_links=raw[i])
+        assert abs(masses[i] - r["mass"]) < 1e-13
+        bad += _check_terms(rec[i], r, S["v"][i], float(masses[i]), worst, i)
+    print("\nterms parity, per-robot models: " + ", ".join("%s %.2e" % kv for kv in sorted(worst.items())))
+    assert not bad, bad
+    assert len({float(rec[i, 1503]) for i in range(n)}) == n     # four different robots
+
+
+def test_terms_equal_the_product_path():
+    """lmh_eval_debug on states whose v_prev equals v dumps the same M, C, J, AG (the two-path schedules differ: no bit equality asked)."""
+    from linearmpchumanoid_amd.controller import unpack_debug
+    S = _setup()
+    ctl = _controller(B, S["zcom"], warm_start=0)
+    ctl.set_refs_stance(2.0, 2)
+    st = ctl.new_state(S["q"], S["v"], t=0.0, v_prev=S["v"])
+    _, _, dbg = ctl.stand_step(st, debug=True)
+    rec = ctl.terms(_dev(ctl, S["q"]), _dev(ctl, S["v"]))
+    torch.cuda.synchronize()
+    dbg, rec = dbg.cpu().numpy(), rec.cpu().numpy()
+    worst = {}
+    for i in range(B):
+        d = unpack_debug(dbg[i]); dd = dense_terms_from_debug(d)
+        s = ctl.split_terms(rec[i])
+        for name, a, b in (("M", s["M"], dd["M"]), ("C", s["C"], d["C"]), ("J", s["J"], dd["J"]), ("AG", s["AG"], d["AG"])):
+            e = rel_err(a, b)
+            worst[name] = max(worst.get(name, 0.0), e)
+            assert e < 1e-11, (i, name, e)
+    print("\nterms vs debug record: " + ", ".join("%s %.2e" % kv for kv in sorted(worst.items())))
+
+
+def test_inverse_dynamics():
+    S = _setup()
+    ctl = _controller(B, S["zcom"])
+    q, v, qdd, w = (_dev(ctl, S[k]) for k in ("q", "v", "qdd", "w"))
+    tau = ctl.inverse_dynamics(q, v, qdd, w)
+    tau_now = ctl.inverse_dynamics(q, v, qdd)
+    tau_w0 = ctl.inverse_dynamics(q, v, qdd, torch.zeros_like(w))
+    tau_nov = ctl.inverse_dynamics(q, None, qdd, w)
+    tau_v0 = ctl.inverse_dynamics(q, torch.zeros_like(v), qdd, w)
+    torch.cuda.synchronize()
+    assert torch.equal(tau_now, tau_w0) and torch.equal(tau_nov, tau_v0)
+    assert not torch.equal(tau, tau_now) and not torch.equal(tau, tau_nov)
+    tau = tau.cpu().numpy()
+    worst = 0.0
+    for i in range(B):
+        t = S["ref"][i]["t"]
+        scale = (np.abs(t["M"]).sum(axis=1).max() * np.abs(S["qdd"][i]).max() + np.abs(t["C"]).max()
+                 + np.abs(t["J"].T).sum(axis=1).max() * np.abs(S["w"][i]).max())
+        worst = max(worst, float(np.abs(tau[i] - S["tau"][i]).max() / scale))
+        assert close_on(tau[i], S["tau"][i], 1e-11, scale), (i, np.abs(tau[i] - S["tau"][i]).max() / scale)
+    print("\ninverse dynamics: worst error on its scale %.2e" % worst)
+
+
+def _check_forward(x, i, S, worst):
+    t = S["ref"][i]["t"]
+    M, rhs = t["M"], S["tau"][i] + t["J"].T @ S["w"][i] - t["C"]
+    ninf = lambda a: float(np.abs(a).sum(axis=1).max()) if np.ndim(a) == 2 else float(np.abs(a).max())
+    back = ninf(M @ x - rhs) / (ninf(M) * ninf(x) + ninf(rhs))
+    fwd = ninf(x - S["qdd"][i]) / (np.linalg.cond(M) * ninf(S["qdd"][i]))
+    worst["backward"] = max(worst.get("backward", 0.0), back)
+    worst["forward"] = max(worst.get("forward", 0.0), fwd)
+    assert np.isfinite(x).all() and back <= 1e-12 and fwd <= 1e-12, (i, back, fwd)
+
+
+def test_forward_dynamics():
+    S = _setup()
+    ctl = _controller(B, S["zcom"])
+    q, v, qdd, w, tau = (_dev(ctl, S[k]) for k in ("q", "v", "qdd", "w", "tau"))
+    x, flags = ctl.forward_dynamics(q, v, tau, w)
+    x2, flags2 = ctl.forward_dynamics(q, v, ctl.inverse_dynamics(q, v, qdd, w), w)      # round trip on the device alone
+    torch.cuda.synchronize()
+    assert flags.dtype == torch.int32 and int(flags.abs().max()) == 0 and int(flags2.abs().max()) == 0
+    x, x2 = x.cpu().numpy(), x2.cpu().numpy()
+    worst, worst2 = {}, {}
+    for i in range(B):
+        _check_forward(x[i], i, S, worst)
+        fwd = np.abs(x2[i] - S["qdd"][i]).max() / (np.linalg.cond(S["ref"][i]["t"]["M"]) * np.abs(S["qdd"][i]).max())
+        worst2["forward"] = max(worst2.get("forward", 0.0), float(fwd))
+        assert fwd <= 1e-12, (i, fwd)
+    print("\nforward dynamics: backward %.2e forward/cond %.2e, device round trip forward/cond %.2e (cond(M) up to %.1e)"
+          % (worst["backward"], worst["forward"], worst2["forward"], max(np.linalg.cond(r["t"]["M"]) for r in S["ref"])))
+
+
+def test_flags_are_per_robot():
+    """Robot 2's link table has every mass and inertia negated (M is negative definite): its flag word carries FLAG_NOT_SPD, the others
+    carry 0 and meet the forward-dynamics bounds.  An input check of the status path: the kernel finishes normally."""
+    from linearmpchumanoid_amd import capi
+    from linearmpchumanoid_amd.controller import nominal_links
+    S = _setup()
+    n = 4
+    raw = np.tile(nominal_links(), (n, 1, 1))
+    raw[2, :, 0] *= -1.0
+    raw[2, :, 4:13] *= -1.0
+    ctl = _controller(n, S["zcom"])
+    ctl.set_model(raw)
+    x, flags = ctl.forward_dynamics(_dev(ctl, S["q"][:n]), _dev(ctl, S["v"][:n]), _dev(ctl, S["tau"][:n]), _dev(ctl, S["w"][:n]))
+    torch.cuda.synchronize()
+    flags, x = flags.cpu().numpy(), x.cpu().numpy()
+    assert flags[2] & capi.FLAG_NOT_SPD
+    worst = {}
+    for i in (0, 1, 3):
+        assert flags[i] == 0
+        _check_forward(x[i], i, S, worst)
+
+
+def test_the_handle_is_untouched():
+    """stand_step and a 50-tick rollout from a fixed state give the same bits before and after a burst of the three new calls."""
+    S = _setup()
+    ctl = _controller(B, S["zcom"], warm_start=1)
+    ctl.set_refs_stance(2.0, 2)
+    st0 = ctl.new_state(S["q0"], S["v"] * 0.2, t=0.0)
+
+    def run():
+        a = st0.clone()
+        o1, s1 = ctl.stand_step(a)
+        b = st0.clone()
+        o2, s2, _ = ctl.rollout(b, 50)
+        torch.cuda.synchronize()
+        return a, o1, s1, b, o2, s2
+
+    before = run()
+    q, v, qdd, w = (_dev(ctl, S[k]) for k in ("q", "v", "qdd", "w"))
+    for _ in range(3):
+        ctl.terms(q, v)
+        tau = ctl.inverse_dynamics(q, v, qdd, w)
+        ctl.forward_dynamics(q, v, tau, w)
+    torch.cuda.synchronize()
+    after = run()
+    for a, b in zip(before, after):
+        assert torch.equal(a, b)
+
+
+def test_refusals():
+    from linearmpchumanoid_amd import capi
+    S = _setup()
+    ctl = _controller(B, S["zcom"])
+    L = capi.lib()
+    q, v, w = _dev(ctl, S["q"]), _dev(ctl, S["v"]), _dev(ctl, S["w"])
+    out = torch.zeros((B, capi.TERMS_STRIDE), dtype=torch.float64, device=ctl.device)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    for rc in (L.lmh_terms(ctl._h, None, p(v), p(out), None), L.lmh_terms(ctl._h, p(q), p(v), None, None),
+               L.lmh_inverse_dynamics(ctl._h, p(q), p(v), None, p(w), p(out), None), L.lmh_inverse_dynamics(ctl._h, p(q), p(v), p(q), p(w), None, None),
+               L.lmh_forward_dynamics(ctl._h, p(q), p(v), None, p(w), p(out), None, None), L.lmh_forward_dynamics(ctl._h, None, p(v), p(q), p(w), p(out), None, None),
+               L.lmh_terms_host(ctl._h, None, None, S["q"].ctypes.data_as(C.c_void_p))):
+        assert rc == -2 and len(L.lmh_last_error()) > 0
+    torch.cuda.synchronize()
+    assert float(out.abs().max()) == 0.0                          # nothing was enqueued
+    with pytest.raises(ValueError):
+        ctl.terms(q[:, :29].contiguous())
+    with pytest.raises(ValueError):
+        ctl.terms(q[:B - 1])
+    with pytest.raises(ValueError):
+        ctl.terms(q, v.to(torch.float32))
+    with pytest.raises(ValueError):
+        ctl.terms(S["q"])
+    with pytest.raises(ValueError):
+        ctl.inverse_dynamics(q, v, None)
+    with pytest.raises(ValueError):
+        ctl.inverse_dynamics(q, v, q, w[:, :6].contiguous())
+    with pytest.raises(ValueError):
+        ctl.forward_dynamics(q, v, w)
+
+
+SHIM_PROGRAM = """#include <cstdio>
+#include "linearMpcHumanoid/controller/Dynamics.hpp"
+int main(int argc, char **argv)
+{
+    if (argc < 2) return 2;
+    std::FILE *f = std::fopen(argv[1], "r");
+    if (!f) return 2;
+    Eigen::VectorXd q(30);
+    double v[30];
+    for (int i = 0; i < 30; i++) if (std::fscanf(f, "%lf", &q(i)) != 1) return 2;
+    for (int i = 0; i < 30; i++) if (std::fscanf(f, "%lf", &v[i]) != 1) return 2;
+    std::fclose(f);
+    Robot robot;
+    robot.updateState(q);
+    robot.setFromDevice(nullptr, v, nullptr, nullptr);
+    Dynamics dyn;
+    dyn.computeAll(robot);
+    const Eigen::MatrixXd &M = dyn.getM(), &AG = dyn.getAG();
+    const Eigen::VectorXd &Cv = dyn.getC();
+    std::printf("M %d %d\\n", M.rows(), M.cols());
+    for (int i = 0; i < M.rows(); i++) for (int j = 0; j < M.cols(); j++) std::printf("%.17g\\n", M(i, j));
+    std::printf("C %d 1\\n", Cv.size());
+    for (int i = 0; i < Cv.size(); i++) std::printf("%.17g\\n", Cv(i));
+    std::printf("AG %d %d\\n", AG.rows(), AG.cols());
+    for (int i = 0; i < AG.rows(); i++) for (int j = 0; j < AG.cols(); j++) std::printf("%.17g\\n", AG(i, j));
+    const std::vector<Eigen::Matrix4d> &T = robot.getT();
+    std::printf("T %d 16\\n", (int)T.size());
+    for (const Eigen::Matrix4d &t : T) for (int i = 0; i < 4; i++) for (int j = 0; j < 4; j++) std::printf("%.17g\\n", t(i, j));
+    std::printf("h 3 1\\n");
+    for (int i = 0; i < 3; i++) std::printf("%.17g\\n", robot.getComAngMom()(i));
+    return 0;
+}
+"""
+
+
+def test_shim_dynamics_on_the_gpu(tmp_path):
+    """Dynamics::computeAll of the shim (host staging, lmh_terms_host) returns what terms() returns for the same (q, v): the same kernel."""
+    from linearmpchumanoid_amd import build as b
+    from linearmpchumanoid_amd.controller import BatchedController, default_config
+    S = _setup()
+    b.build_shim()
+    src, exe, inp = tmp_path / "dyn_print.cpp", tmp_path / "dyn_print", tmp_path / "state.txt"
+    src.write_text(SHIM_PROGRAM)
+    libdir = os.path.dirname(b.SHIM_SO)
+    subprocess.check_call(["g++", "-std=c++17", "-O2", "-I" + b.SHIM_DIR, "-I" + os.path.join(ROOT, "include"), str(src), "-o", str(exe),
+                           "-L" + libdir, "-llmh_shim", "-llmh_hip", "-Wl,-rpath," + libdir])
+    q, v = S["q"][3], S["v"][3]
+    inp.write_text("\n".join("%.17g" % x for x in np.concatenate([q, v])))
+    lines = subprocess.check_output([str(exe), str(inp)], timeout=120).decode().split("\n")
+    got, k = {}, 0
+    while k < len(lines) and lines[k].strip():
+        name, r, c = lines[k].split()
+        n = int(r) * int(c)
+        got[name] = np.array([float(x) for x in lines[k + 1:k + 1 + n]]).reshape(int(r), int(c))
+        k += 1 + n
+    ctl = BatchedController(1, default_config())                  # the shim's set-up handle: default configuration, nominal model
+    rec = ctl.terms(_dev(ctl, q[None, :]), _dev(ctl, v[None, :]))
+    torch.cuda.synchronize()
+    s = ctl.split_terms(rec.cpu().numpy()[0])
+    assert got["M"].shape == (30, 30) and got["AG"].shape == (6, 30) and got["C"].shape == (30, 1) and got["T"].shape == (28, 16)
+    assert rel_err(got["M"], s["M"]) < 1e-12 and rel_err(got["C"][:, 0], s["C"]) < 1e-12 and rel_err(got["AG"], s["AG"]) < 1e-12
+    T = got["T"].reshape(28, 4, 4)
+    assert rel_err(T[:, :3, :], s["T"]) < 1e-12 and np.array_equal(T[:, 3, :], np.tile([0.0, 0, 0, 1], (28, 1)))
+    assert rel_err(got["h"][:, 0], s["angMom"]) < 1e-12
