@@ -45,6 +45,27 @@ extern "C" {
 #define LMH_SEG_STRIDE 52
 #define LMH_PUSH_STRIDE 32        /* one timed velocity push: tick (as a double) | dv[30] | pad, see lmh_set_pushes */
 #define LMH_MAX_PUSHES 16         /* push records per robot */
+#define LMH_PARAM_STRIDE 20       /* one per-robot parameter record, see lmh_set_params */
+/* offsets into one parameter record (doubles, in lmh_config's own order) */
+#define LMH_PARAM_OFF_MU 0
+#define LMH_PARAM_OFF_KP_JOINTS 1
+#define LMH_PARAM_OFF_KD_JOINTS 2
+#define LMH_PARAM_OFF_KP_MOM 3
+#define LMH_PARAM_OFF_KD_MOM 4
+#define LMH_PARAM_OFF_KP_FEET 5
+#define LMH_PARAM_OFF_KD_FEET 6
+#define LMH_PARAM_OFF_W_COM_LIN 7
+#define LMH_PARAM_OFF_W_COM_ANG 8
+#define LMH_PARAM_OFF_W_BASE_POS 9
+#define LMH_PARAM_OFF_W_BASE_ANG 10
+#define LMH_PARAM_OFF_W_JOINTS 11
+#define LMH_PARAM_OFF_W_FORCE 12
+#define LMH_PARAM_OFF_W_FOOT 13
+#define LMH_PARAM_OFF_EPS_COEFF 14
+#define LMH_PARAM_OFF_CONTACT_K 15
+#define LMH_PARAM_OFF_CONTACT_D 16
+#define LMH_PARAM_OFF_CONTACT_DT 17
+#define LMH_PARAM_OFF_CONTACT_MU 18   /* [19] pad */
 #define LMH_TRACE_STRIDE 180      /* one trace sample: state(96) | out(80) | status(4, as doubles), see lmh_rollout_trace */
 #define LMH_TERMS_STRIDE 1840     /* one rigid-body terms record, see lmh_terms */
 /* offsets into one terms record (doubles, every array row-major) */
@@ -255,6 +276,32 @@ int lmh_num_pushes(const lmh_handle *h);                  /* records per schedul
 int lmh_pushes_per_instance(const lmh_handle *h);         /* 0: none or one shared schedule, 1: one schedule per robot */
 /* robot `inst`'s schedule (the shared one on a shared schedule): HOST out [lmh_num_pushes][LMH_PUSH_STRIDE] */
 int lmh_get_pushes(lmh_handle *h, int inst, double *records);
+
+/* Per-robot controller parameters (build-defined; the reference's gains, weights and friction coefficient are compile-time literals,
+ * controller.hpp:80-124): every robot of the handle runs its own PD gains, QP weights, eps_coeff, friction coefficient and -- with
+ * plant = 1 -- contact constants, in one launch.  A gain or weight sweep, or a friction / ground-stiffness randomisation beside per-robot
+ * models, is one handle.
+ * records: HOST [n][LMH_PARAM_STRIDE], n must be n_instances; one record is, in lmh_config's own order (LMH_PARAM_OFF_*),
+ *   mu | kp_joints kd_joints kp_mom kd_mom kp_feet kd_feet | w_com_lin w_com_ang w_base_pos w_base_ang w_joints w_force w_foot | eps_coeff |
+ *   contact_k contact_d contact_dt contact_mu | pad (ignored).
+ * Every record is checked by the rules lmh_create applies to the same fields of its lmh_config (weights positive, w_com_ang >= 0, mu and
+ * eps_coeff positive, gains finite; the contact constants only when the handle's plant is 1); the error text names the first offending
+ * robot ("robot 7: ...").  A refused or failed call leaves the handle on its previous parameters, under the rule of lmh_set_refs: check
+ * first, build aside, replace in one step.  records = NULL or n = 0 puts the handle back on the values of its lmh_config.
+ * Robot i then computes, bit for bit, what robot i of a handle created with record i in its lmh_config computes: it reads the same
+ * friction generators (built on the host by the routine lmh_create uses) and the same quotients 1 / w.  w_com_ang chooses between the 15-
+ * and the 18-row QP set-up per robot.  lmh_eval, lmh_eval_debug, lmh_eval_host and lmh_rollout honour the records; lmh_ik, lmh_robot_com and
+ * the lmh_terms family read none of these fields.
+ * These stay per handle, because they select kernel instantiations or size tables every robot shares: dt, mpc_dt, time_horizon, alpha, beta,
+ * gravity, warm_start, max_qp_iters, bpp_rounds, precision, plant (z_com is per robot through lmh_set_zcom).
+ * Device side: the handle keeps one whole parameter block per robot, rewritten by a small kernel whenever another setter (lmh_set_model,
+ * lmh_set_zcom, the reference setters, lmh_set_foot_coeffs, lmh_set_pushes, lmh_set_xscale) moves a table, in any order with this call; such
+ * a setter waits for that kernel, and if the rewrite itself fails (LMH_ERR_HIP) the setter fails as a whole: its own change is not applied.
+ * On a handle of one robot a per-robot set IS the shared set: lmh_params_per_instance reports 0 there. */
+int lmh_set_params(lmh_handle *h, const double *records, int n);
+int lmh_params_per_instance(const lmh_handle *h);         /* 0: the config's one set, 1: one set per robot */
+/* robot `inst`'s record (the config's values for every inst on a handle without per-robot parameters): HOST out [LMH_PARAM_STRIDE], pad 0 */
+int lmh_get_params(lmh_handle *h, int inst, double *record);
 
 /* replaces: Controller::standStep + Controller::WBC (src/controller.cpp:48-154) for all
  * instances.  DEVICE pointers; d_state is read AND updated (v_prev <- v, as Robot::v_ is);

@@ -20,6 +20,13 @@ LINK_STRIDE = 13
 SEG_STRIDE = 52
 PUSH_STRIDE = 32              # one timed velocity push: tick (as a double) | dv[30] | pad (lmh_set_pushes)
 MAX_PUSHES = 16               # push records per robot
+PARAM_STRIDE = 20             # one per-robot parameter record (lmh_set_params)
+# name -> offset inside a parameter record: the LMH_PARAM_OFF_* defines of include/lmh.h (lmh_config's own order; [19] is a pad)
+PARAM_FIELDS = {
+    "mu": 0, "kp_joints": 1, "kd_joints": 2, "kp_mom": 3, "kd_mom": 4, "kp_feet": 5, "kd_feet": 6,
+    "w_com_lin": 7, "w_com_ang": 8, "w_base_pos": 9, "w_base_ang": 10, "w_joints": 11, "w_force": 12, "w_foot": 13,
+    "eps_coeff": 14, "contact_k": 15, "contact_d": 16, "contact_dt": 17, "contact_mu": 18,
+}
 TRACE_STRIDE = 180            # one trace sample: state(96) | out(80) | status(4, as doubles) (lmh_rollout_trace)
 TERMS_STRIDE = 1840           # one rigid-body terms record (lmh_terms)
 # name -> (offset, shape) inside a terms record: the LMH_TERMS_OFF_* defines of include/lmh.h, every array row-major
@@ -54,6 +61,7 @@ EXPORTS = [
     "lmh_set_pushes", "lmh_num_pushes", "lmh_pushes_per_instance", "lmh_get_pushes",
     "lmh_rollout_trace", "lmh_trace_samples", "lmh_write_trace", "lmh_read_trace",
     "lmh_terms", "lmh_inverse_dynamics", "lmh_forward_dynamics", "lmh_terms_host",
+    "lmh_set_params", "lmh_params_per_instance", "lmh_get_params",
 ]
 
 
@@ -144,6 +152,9 @@ def lib():
     L.lmh_num_pushes.argtypes = [vp]
     L.lmh_pushes_per_instance.argtypes = [vp]
     L.lmh_get_pushes.argtypes = [vp, ip, vp]
+    L.lmh_set_params.argtypes = [vp, vp, ip]
+    L.lmh_params_per_instance.argtypes = [vp]
+    L.lmh_get_params.argtypes = [vp, ip, vp]
     L.lmh_make_summary.argtypes = [vp, vp, vp, vp, vp, vp]
     L.lmh_write_summary.argtypes = [C.c_char_p, vp, u64, dp]
     L.lmh_read_summary.argtypes = [C.c_char_p, vp, u64, u64p, dpp]

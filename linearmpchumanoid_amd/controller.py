@@ -59,6 +59,25 @@ def ik_start_posture(device=0, com_target=(-0.02, 0.0, 0.26)):
     return out
 
 
+def param_records(cfg, n_instances, **fields):
+    """The [B,20] records BatchedController.set_params uploads (include/lmh.h, lmh_set_params): every field of capi.PARAM_FIELDS is a
+    scalar or a length-B array, unnamed fields keep the value of cfg.  Unknown names, wrong lengths and non-finite values raise
+    ValueError; nothing here touches the device."""
+    B = int(n_instances)
+    unknown = sorted(set(fields) - set(capi.PARAM_FIELDS))
+    if unknown:
+        raise ValueError(f"unknown parameter field(s) {unknown}; the per-robot fields are {sorted(capi.PARAM_FIELDS)}")
+    rec = np.zeros((B, capi.PARAM_STRIDE), dtype=np.float64)
+    for name, off in capi.PARAM_FIELDS.items():
+        v = np.asarray(fields.get(name, getattr(cfg, name)), dtype=np.float64)
+        if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != B):
+            raise ValueError(f"{name} must be a scalar or an array of length {B}")
+        if not np.all(np.isfinite(v)):
+            raise ValueError(f"{name} must be finite")
+        rec[:, off] = v
+    return rec
+
+
 def _np_ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -234,6 +253,26 @@ class BatchedController:
         rec = np.zeros((n, capi.PUSH_STRIDE))
         check(capi.lib().lmh_get_pushes(self._h, int(i), _np_ptr(rec) if n else None))
         return dict(ticks=rec[:, 0].astype(np.int64), dv=rec[:, 1:31].copy())
+
+    # -- per-robot gains, QP weights, friction and contact parameters (include/lmh.h, lmh_set_params)
+    def set_params(self, **fields):
+        """lmh_set_params: one set of PD gains, QP weights, eps_coeff, mu and contact constants per robot, e.g.
+        set_params(kp_joints=np.linspace(200, 400, B), mu=0.5).  With no arguments the handle goes back to the values of its config."""
+        if not fields:
+            check(capi.lib().lmh_set_params(self._h, None, 0))
+            return
+        rec = param_records(self.cfg, self.B, **fields)           # ValueError before any device call
+        check(capi.lib().lmh_set_params(self._h, _np_ptr(rec), self.B))
+
+    def params_per_instance(self):
+        """True while every robot has a parameter set of its own (set_params with arguments, B > 1)."""
+        return bool(capi.lib().lmh_params_per_instance(self._h))
+
+    def get_params(self, i):
+        """Robot i's parameters as a dict over capi.PARAM_FIELDS (the config's values on a handle without per-robot parameters)."""
+        rec = np.zeros(capi.PARAM_STRIDE, dtype=np.float64)
+        check(capi.lib().lmh_get_params(self._h, int(i), _np_ptr(rec)))
+        return {name: float(rec[off]) for name, off in capi.PARAM_FIELDS.items()}
 
     def set_xscale(self, xscale):
         """Per-instance step-length scale of ZMP x and x-axis foot polynomials ([B] or None)."""

@@ -23,6 +23,7 @@ extern "C" void lmh_launch_gen_jump(int n, double time_step, double stance_time,
 extern "C" void lmh_launch_gen_walk_batch(const LmhWalkSpec *d_specs, int n_plans, int seg_stride, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos, hipStream_t s);
 extern "C" void lmh_launch_gen_jump_batch(int n, double time_step, const LmhJumpSpec *d_specs, int n_plans, double *zx, double *zy, uint8_t *phase, hipStream_t s);
 extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *q, const double *v, const double *x, const double *w, double *res, int32_t *flags, hipStream_t s);
+extern "C" void lmh_launch_params_expand(const LmhDevParams *P, const double *d_rec, const double *d_gcol_tab, LmhDevParams *d_blocks, int n, hipStream_t s);
 extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
 
 static thread_local std::string g_err;
@@ -67,6 +68,15 @@ struct lmh_handle {
     RefPlan plan;                     // replaced as a whole, by commit_plan only
     DevBuf<double> d_pushes;          // timed velocity pushes [n_push_sets][n_push][LMH_PUSH_STRIDE] (lmh_set_pushes); empty while n_push = 0
     int n_push = 0, n_push_sets = 1;
+    // Per-robot parameters (lmh_set_params): the records, one friction table per robot and the table of whole parameter blocks the controller
+    // kernels select from.  All empty while the handle runs on its config's one set.  The block table is rebuilt by fill_params, i.e. by
+    // every setter that moves a pointer or a stride, and replaces the previous one in one step.
+    struct InstParams {
+        std::vector<double> h_rec;    // [B][LMH_PARAM_STRIDE], what lmh_get_params returns
+        DevBuf<double> d_rec, d_gcol; // the same on the device | [B][LMH_GCOL_STRIDE]
+        DevBuf<LmhDevParams> d_blocks;
+        bool on() const { return d_rec.get() != nullptr; }
+    } inst;
     // staging for the host-buffer convenience calls
     DevBuf<double> d_state, d_out;
     DevBuf<double> d_terms;           // lmh_terms_host only: q | v | terms records, allocated on its first call
@@ -276,12 +286,31 @@ static void build_lcoef(double *t /*[336][3]*/)
         for (int k = 0; k < 12; k++) t[3 * (12 * s + k)] = aux[s - 25][k];
 }
 
-static void fill_params(lmh_handle *h)
+// the table of per-robot blocks from the block `base` (its inst_blocks aside): built aside, complete when this returns
+static int expand_blocks(const lmh_handle *h, LmhDevParams base, const double *d_rec, const double *d_gcol, DevBuf<LmhDevParams> &table)
 {
-    LmhDevParams &P = h->P;
+    base.inst_blocks = nullptr;
+    HIPCHK(table.alloc((size_t)h->B));
+    lmh_launch_params_expand(&base, d_rec, d_gcol, table.get(), h->B, nullptr);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());                                  // the setter waits for the kernel; no launch in flight reads the old table either
+    return LMH_OK;
+}
+
+// Every setter that moves a pointer, a stride or a shared scalar ends here: it has put its new buffers into the handle, and this forms the
+// block that goes with them.  With per-robot parameters on, the block table is written again from that block, into a table of its own, so
+// that no robot's block ever holds a stale pointer.  The handle's block and table are replaced together at the end; if the table cannot be
+// built (allocation or launch) neither is touched, and the setter puts its previous buffers back: the call fails as a whole.
+// the FK coefficient table sits behind the handle's friction table (create_body): the one statement of where
+static const double *lcoef_of(const lmh_handle *h) { return h->d_gcol.get() + LMH_GCOL_STRIDE; }
+
+static int fill_params(lmh_handle *h)
+{
+    LmhDevParams P = h->P;                                           // (the foot polynomials live in the block alone)
     const lmh_config &c = h->cfg;
     const RefPlan &r = h->plan;
     P.model = h->d_model.get(); P.mpc = h->d_mpc.get(); P.gcol = h->d_gcol.get(); P.xscale = h->d_xscale.get();
+    P.lcoef = lcoef_of(h);
     P.zmpx = r.zx.get(); P.zmpy = r.zy.get(); P.phase = r.phase.get(); P.segs = r.segs.get(); P.seg_of_sample = r.sos.get();
     P.n_seg = r.n_seg; P.ref_stride = r.per_robot() ? r.n_samples : 0; P.seg_stride = r.per_robot() ? r.n_seg : 0;
     P.pushes = h->d_pushes.get(); P.n_push = h->n_push; P.push_stride = (h->n_push_sets > 1) ? h->n_push : 0;
@@ -301,6 +330,16 @@ static void fill_params(lmh_handle *h)
     P.inv_w_com_lin = 1.0 / c.w_com_lin; P.inv_w_foot = 1.0 / c.w_foot;
     const double md = h->mpc_dt;                                     // mpcLinearPendulum.cpp:45-47 with the Mpc3dLip ctor's dt
     P.a00 = 1; P.a01 = md; P.a10 = 0; P.a11 = 1; P.b0 = (md * md) / 2; P.b1 = md;
+    P.inst_blocks = nullptr;
+    if (h->inst.on()) {
+        DevBuf<LmhDevParams> table;
+        const int rc = expand_blocks(h, P, h->inst.d_rec.get(), h->inst.d_gcol.get(), table);
+        if (rc != LMH_OK) return rc;                                 // the handle still has its previous block and table
+        h->inst.d_blocks = std::move(table);
+        P.inst_blocks = h->inst.d_blocks.get();
+    }
+    h->P = P;
+    return LMH_OK;
 }
 
 static int upload_gain(lmh_handle *h, const double *zcom, int n)
@@ -312,9 +351,10 @@ static int upload_gain(lmh_handle *h, const double *zcom, int n)
             return fail(LMH_ERR_BAD_ARG, "MPC Hessian not positive definite");
     DevBuf<double> d;
     HIPCHK(d.upload(rows.data(), rows.size()));
-    h->d_mpc = std::move(d); h->h_gain.swap(rows); h->n_gain = n;
-    fill_params(h);
-    return LMH_OK;
+    std::swap(h->d_mpc, d); h->h_gain.swap(rows); std::swap(h->n_gain, n);
+    const int rc = fill_params(h);
+    if (rc != LMH_OK) { std::swap(h->d_mpc, d); h->h_gain.swap(rows); std::swap(h->n_gain, n); }   // back on the previous rows
+    return rc;
 }
 
 // every literal the kernels divide by or take a Cholesky pivot from must be positive (a zero weight is 1/0 in the
@@ -344,9 +384,9 @@ static const char *validate_config(const lmh_config *c)
 static int create_body(lmh_handle *h, const lmh_config *cfg, int n_instances)
 {
     std::memset(&h->P, 0, sizeof(h->P));
-    double g[16 * 6 + 36 + 96 + 3 * 336];
+    double g[LMH_GCOL_STRIDE + 3 * 336];
     build_gcol(cfg->mu, g);
-    build_lcoef(g + 228);
+    build_lcoef(g + LMH_GCOL_STRIDE);
     HIPCHK(h->d_gcol.upload(g, sizeof(g) / sizeof(double)));
     HIPCHK(h->d_state.alloc(LMH_STATE_STRIDE * (size_t)n_instances));
     HIPCHK(h->d_out.alloc(LMH_OUT_STRIDE * (size_t)n_instances));
@@ -415,12 +455,13 @@ extern "C" int lmh_set_model(lmh_handle *h, const double *raw, int n_models)
     DevBuf<double> d_raw, d_model;
     HIPCHK(d_raw.upload(raw, 28 * LMH_LINK_STRIDE * (size_t)n_models));
     HIPCHK(d_model.alloc(LMH_MODEL_STRIDE * (size_t)n_models));
-    lmh_launch_model(d_raw.get(), d_model.get(), n_models, h->d_gcol.get() + 228, nullptr);
+    lmh_launch_model(d_raw.get(), d_model.get(), n_models, lcoef_of(h), nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    h->d_raw = std::move(d_raw); h->d_model = std::move(d_model); h->n_models = n_models;
-    fill_params(h);
-    return LMH_OK;
+    std::swap(h->d_raw, d_raw); std::swap(h->d_model, d_model); std::swap(h->n_models, n_models);
+    const int rc = fill_params(h);
+    if (rc != LMH_OK) { std::swap(h->d_raw, d_raw); std::swap(h->d_model, d_model); std::swap(h->n_models, n_models); }   // back on the previous model
+    return rc;
 }
 
 extern "C" int lmh_get_mass(lmh_handle *h, double *mass)
@@ -438,8 +479,9 @@ extern "C" int lmh_get_mass(lmh_handle *h, double *mass)
 static int commit_plan(lmh_handle *h, RefPlan p)
 {
     std::swap(h->plan, p);
-    fill_params(h);
-    return LMH_OK;                                                   // the previous plan dies with p, after P has left it
+    const int rc = fill_params(h);
+    if (rc != LMH_OK) std::swap(h->plan, p);                         // back on the previous plan; the new one dies with p
+    return rc;                                                       // else the previous plan dies with p, after P (and every robot's block) has left it
 }
 
 static std::string robot_msg(int i, const char *msg) { return "robot " + std::to_string(i) + ": " + msg; }
@@ -496,13 +538,19 @@ extern "C" int lmh_set_refs_stance(lmh_handle *h, double simulation_time, int su
 extern "C" int lmh_set_foot_coeffs(lmh_handle *h, const double *r, const int32_t *rn, const double *l, const int32_t *ln)
 {
     if (!h || !r || !rn || !l || !ln) return fail(LMH_ERR_BAD_ARG, "bad argument");
-    for (int a = 0; a < 3; a++) {
+    for (int a = 0; a < 3; a++)
         if (rn[a] < 1 || rn[a] > 8 || ln[a] < 1 || ln[a] > 8) return fail(LMH_ERR_BAD_ARG, "coefficient count must be 1..8");
+    const LmhDevParams prev = h->P;
+    for (int a = 0; a < 3; a++) {
         h->P.rFn[a] = rn[a]; h->P.lFn[a] = ln[a];
         // entries beyond the count are stored as zeros: the kernels evaluate all eight terms (a zero coefficient adds an exact zero)
         for (int k = 0; k < 8; k++) { h->P.rF[a][k] = (k < rn[a]) ? r[8 * a + k] : 0.0; h->P.lF[a][k] = (k < ln[a]) ? l[8 * a + k] : 0.0; }
     }
-    return LMH_OK;
+    if (!h->inst.on()) return LMH_OK;
+    HIPCHK(hipSetDevice(h->device));
+    const int rc = fill_params(h);                                   // the polynomials live in every robot's block
+    if (rc != LMH_OK) h->P = prev;
+    return rc;
 }
 
 extern "C" int lmh_set_segments(lmh_handle *h, const double *segs, int n_seg, const uint16_t *sos, int n_samples)
@@ -556,9 +604,10 @@ extern "C" int lmh_set_pushes(lmh_handle *h, const double *records, int n_push, 
     HIPCHK(hipSetDevice(h->device));
     DevBuf<double> d;
     if (n_push > 0) HIPCHK(d.upload(records, (size_t)LMH_PUSH_STRIDE * n_push * n_sets));
-    h->d_pushes = std::move(d); h->n_push = n_push; h->n_push_sets = n_sets;     // nothing above changed the handle; nothing below fails
-    fill_params(h);
-    return LMH_OK;
+    std::swap(h->d_pushes, d); std::swap(h->n_push, n_push); std::swap(h->n_push_sets, n_sets);     // nothing above changed the handle
+    const int rc = fill_params(h);
+    if (rc != LMH_OK) { std::swap(h->d_pushes, d); std::swap(h->n_push, n_push); std::swap(h->n_push_sets, n_sets); }   // back on the previous schedule
+    return rc;
 }
 
 extern "C" int lmh_num_pushes(const lmh_handle *h) { return h ? h->n_push : 0; }
@@ -583,9 +632,10 @@ extern "C" int lmh_set_xscale(lmh_handle *h, const double *xscale, int n)
     HIPCHK(hipSetDevice(h->device));
     DevBuf<double> d;
     if (xscale) HIPCHK(d.upload(xscale, (size_t)n));
-    h->d_xscale = std::move(d);
-    fill_params(h);
-    return LMH_OK;
+    std::swap(h->d_xscale, d);
+    const int rc = fill_params(h);
+    if (rc != LMH_OK) std::swap(h->d_xscale, d);
+    return rc;
 }
 
 extern "C" int lmh_set_zcom(lmh_handle *h, const double *z, int n)
@@ -599,6 +649,71 @@ extern "C" int lmh_get_mpc_gain(lmh_handle *h, double *K)
 {
     if (!h || !K) return fail(LMH_ERR_BAD_ARG, "bad argument");
     std::memcpy(K, h->h_gain.data(), sizeof(double) * (size_t)(h->N + 1));
+    return LMH_OK;
+}
+
+// ---------------------------------------------------------------------------- per-robot controller parameters
+// the config's values in the record's order (LMH_PARAM_OFF_*)
+static void config_record(const lmh_config &c, double *r)
+{
+    const double v[LMH_PARAM_STRIDE] = {c.mu, c.kp_joints, c.kd_joints, c.kp_mom, c.kd_mom, c.kp_feet, c.kd_feet,
+                                        c.w_com_lin, c.w_com_ang, c.w_base_pos, c.w_base_ang, c.w_joints, c.w_force, c.w_foot, c.eps_coeff,
+                                        c.contact_k, c.contact_d, c.contact_dt, c.contact_mu, 0.0};
+    std::memcpy(r, v, sizeof(v));
+}
+
+// the rules validate_config applies to the same fields, in its words: nullptr = fine
+static const char *param_record_error(const double *r, bool plant)
+{
+    if (!(r[LMH_PARAM_OFF_MU] > 0.0)) return "mu must be positive";
+    if (!(r[LMH_PARAM_OFF_EPS_COEFF] > 0.0)) return "eps_coeff must be positive";
+    for (int o : {LMH_PARAM_OFF_W_COM_LIN, LMH_PARAM_OFF_W_BASE_POS, LMH_PARAM_OFF_W_BASE_ANG, LMH_PARAM_OFF_W_JOINTS, LMH_PARAM_OFF_W_FORCE, LMH_PARAM_OFF_W_FOOT})
+        if (!(r[o] > 0.0)) return "weights w_com_lin, w_base_pos, w_base_ang, w_joints, w_force, w_foot must be positive";
+    if (!(r[LMH_PARAM_OFF_W_COM_ANG] >= 0.0)) return "w_com_ang must be >= 0";
+    for (int o = LMH_PARAM_OFF_KP_JOINTS; o <= LMH_PARAM_OFF_KD_FEET; o++) if (!std::isfinite(r[o])) return "PD gains must be finite";
+    if (plant && (!(r[LMH_PARAM_OFF_CONTACT_K] > 0.0) || !(r[LMH_PARAM_OFF_CONTACT_D] >= 0.0) || !(r[LMH_PARAM_OFF_CONTACT_DT] >= 0.0) || !(r[LMH_PARAM_OFF_CONTACT_MU] >= 0.0)))
+        return "contact_k must be positive, contact_d / contact_dt / contact_mu non-negative";
+    return nullptr;
+}
+
+extern "C" int lmh_set_params(lmh_handle *h, const double *records, int n)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    if (n < 0) return fail(LMH_ERR_BAD_ARG, "n must be >= 0");
+    HIPCHK(hipSetDevice(h->device));
+    if (!records || n == 0) {                                        // back on the config's one set
+        h->P.inst_blocks = nullptr;                                  // first: nothing may launch on a table that is about to go
+        h->inst = lmh_handle::InstParams();
+        return fill_params(h);
+    }
+    if (n != h->B) return fail(LMH_ERR_BAD_ARG, "n must be n_instances");
+    for (int i = 0; i < n; i++)
+        if (const char *msg = param_record_error(records + (size_t)LMH_PARAM_STRIDE * i, h->cfg.plant != 0)) return fail(LMH_ERR_BAD_ARG, robot_msg(i, msg));
+    // built aside: the records (pad zeroed), one friction table per robot by the routine lmh_create uses, the block table
+    lmh_handle::InstParams p;
+    p.h_rec.assign(records, records + (size_t)LMH_PARAM_STRIDE * n);
+    std::vector<double> g((size_t)LMH_GCOL_STRIDE * n);
+    for (int i = 0; i < n; i++) {
+        p.h_rec[(size_t)LMH_PARAM_STRIDE * i + LMH_PARAM_STRIDE - 1] = 0.0;
+        build_gcol(records[(size_t)LMH_PARAM_STRIDE * i + LMH_PARAM_OFF_MU], g.data() + (size_t)LMH_GCOL_STRIDE * i);
+    }
+    HIPCHK(p.d_rec.upload(p.h_rec.data(), p.h_rec.size()));
+    HIPCHK(p.d_gcol.upload(g.data(), g.size()));
+    const int rc = expand_blocks(h, h->P, p.d_rec.get(), p.d_gcol.get(), p.d_blocks);
+    if (rc != LMH_OK) return rc;
+    h->P.inst_blocks = p.d_blocks.get();                             // nothing above changed the handle; nothing below fails
+    h->inst = std::move(p);
+    return LMH_OK;
+}
+
+extern "C" int lmh_params_per_instance(const lmh_handle *h) { return (h && h->B > 1 && h->inst.on()) ? 1 : 0; }
+
+extern "C" int lmh_get_params(lmh_handle *h, int inst, double *record)
+{
+    if (!h || !record) return fail(LMH_ERR_BAD_ARG, "bad argument");
+    if (inst < 0 || inst >= h->B) return fail(LMH_ERR_BAD_ARG, "instance out of range");
+    if (h->inst.on()) std::memcpy(record, h->inst.h_rec.data() + (size_t)LMH_PARAM_STRIDE * inst, sizeof(double) * LMH_PARAM_STRIDE);
+    else config_record(h->cfg, record);
     return LMH_OK;
 }
 

@@ -5,6 +5,8 @@
 #define LMH_MODEL_STRIDE 400  // per model: 28 x 14 doubles (Ibar 9 | m*c 3 | m | Robot::desiredPosture of coordinate i, the record's spare slot) + [392] total mass
 #define LMH_BODY_STRIDE 14
 #define LMH_SEG_STRIDE 52
+#define LMH_PARAM_STRIDE 20   // one per-robot parameter record (include/lmh.h, lmh_set_params)
+#define LMH_GCOL_STRIDE 228   // one friction table: generators [16][6] | (G G')^-1 [6][6] | G'(G G')^-1 [16][6]
 #define LMH_PUSH_STRIDE 32    // one velocity push: tick (as a double) | dv[30] | pad (include/lmh.h, lmh_set_pushes)
 #define LMH_ROLLOUT_THREADS 128   // fused rollout: two waves per robot (lmh_kernels.hip, bsync)
 
@@ -22,6 +24,10 @@ struct LmhDevParams {
     const uint16_t *seg_of_sample; // [n_samples] segment of preview index k
     const double *xscale;       // [n_instances] per-instance scale of ZMP x and x-axis foot polynomials, or nullptr
     const double *pushes;       // [n_sets][n_push][LMH_PUSH_STRIDE] timed velocity pushes (lmh_rollout only), or nullptr while n_push = 0
+    const double *lcoef;        // [336][3] local-transform coefficients of the forward kinematics (build_lcoef): one table per handle
+    const LmhDevParams *inst_blocks;   // per-robot parameters (lmh_set_params): [n_instances] whole blocks, block i = this block with robot i's 19
+                                // scalars, the five inv_w_* and gcol -> robot i's friction table (lmh_params_expand_kernel); nullptr = this block
+                                // serves every robot.  The controller kernels pick the robot's block once and read everything through it
     int32_t model_stride;       // 0 = shared model
     int32_t mpc_stride_inst;    // 0 = shared gain row
     int32_t mpc_stride;         // 3*(N+1)+4

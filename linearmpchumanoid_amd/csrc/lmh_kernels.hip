@@ -38,6 +38,15 @@
 typedef const __attribute__((address_space(4))) LmhDevParams LmhCParams;
 // by-value kernel argument at offset 0 of the kernarg segment, seen through the constant address space
 #define LMH_KERNARG_PARAMS() (*(LmhCParams *)__builtin_amdgcn_kernarg_segment_ptr())
+// Per-robot parameters (include/lmh.h, lmh_set_params): the launch's block P0 carries a table of whole blocks, one per robot, and a controller
+// kernel reads every scalar and the friction table of robot `inst` (wave-uniform) through that robot's block -- still one pointer.  The table
+// is device memory written by lmh_params_expand_kernel before the launch and never during it: constant for the kernel, like the slot's copy
+// the rollout reads.  Without a table P0 serves every robot.
+__device__ __forceinline__ LmhCParams *params_of_robot(LmhCParams *P0, int inst)
+{
+    const LmhDevParams *tab = P0->inst_blocks;
+    return tab ? (LmhCParams *)(uintptr_t)(tab + inst) : P0;
+}
 #include "../../include/lmh.h"
 
 // Wave-level fence: orders this wave's LDS traffic for the compiler; the LDS unit executes one wave's
@@ -3303,7 +3312,7 @@ __device__ __forceinline__ int controller_eval(double *L, LmhCParams &P, int ins
         refs_prepare(L, P, inst, t);
         WSYNC();
     }
-    if (wid == 0 && !PIPE) phase_fk<R>(L, P.gcol + 228);
+    if (wid == 0 && !PIPE) phase_fk<R>(L, P.lcoef);
     WSTAMP(1);
     const bool plant = P.plant != 0;                               // wave-uniform
     // PIPE: the join that ended the previous evaluation already published the world transforms, and until the next join neither wave
@@ -3462,10 +3471,11 @@ __device__ __forceinline__ void store_out(const double *L, double *out, bool kee
 template <bool DEBUG, typename R, int NW = (DEBUG ? 1 : 2), bool QF32 = false>
 __global__ void __launch_bounds__(64 * NW) lmh_eval_kernel(LmhDevParams P_arg, double *state, double *out, int32_t *status, double *debug)
 {
-    LmhCParams &P = LMH_KERNARG_PARAMS();
+    LmhCParams &P0 = LMH_KERNARG_PARAMS();
     __shared__ double L[LDS_DOUBLES];
     const int inst = blockIdx.x;
-    if (inst >= P.n_instances) return;
+    if (inst >= P0.n_instances) return;
+    LmhCParams &P = *params_of_robot(&P0, inst);                   // per-robot parameters (lmh_set_params): the robot's own block
     const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     double *st = state + (size_t)LMH_STATE_STRIDE * inst;
     const double t = st[90];
@@ -3674,7 +3684,10 @@ __device__ __forceinline__ void trace_wave1(double *tr, const double *L, int lan
 #endif
 // TRACE: the instantiation lmh_rollout_trace launches (trace_slot above); without a trace buffer the launch runs the instantiation that has
 // no word of it -- the same code as before the trace existed, so that it costs nothing when off
-template <typename R, bool QF32 = false, bool TRACE = false>
+// PARAMS: the instantiation a handle with per-robot parameters launches (lmh_set_params): it picks the robot's block when it claims a unit.
+// Holding that pointer across the tick loop costs six more scalar spill slots (117 against 111 on the fp64 kernel), so a handle on its
+// config's one set runs the instantiation without it -- the same code, and the same resource line, as before per-robot parameters existed
+template <typename R, bool QF32 = false, bool TRACE = false, bool PARAMS = false>
 #ifndef LMH_ROLLOUT_ATTR
 #ifndef LMH_WAVES_PER_EU
 #define LMH_WAVES_PER_EU 2
@@ -3706,8 +3719,7 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
 #define n_ticks (KA().n_ticks)
 #define trace (KA().trace)
 #define trace_every (KA().trace_every)
-    LmhCParams *Pc = (LmhCParams *)(uintptr_t)Pg;
-    LmhCParams &P = *Pc;
+    LmhCParams *P0 = (LmhCParams *)(uintptr_t)Pg;                  // the launch's block: n_instances and the queue arithmetic read it
     // One workgroup runs several robots one after the other (grid = the number of workgroups the chip holds at once, lmh_launch_rollout):
     // when the hardware dispatcher refills the chip from a longer grid, throughput drops by ~15 % (measured: 1024 robots 4.1 ms per launch,
     // 2048 robots 11.4 ms, 4096 robots 19.2 ms for the same 40 ticks); looping inside the resident workgroups keeps the first round's placement.
@@ -3723,7 +3735,7 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
     if (threadIdx.x == 0) g_L = L;                                 // bsync's wait counters live in the robot's LDS image
     __syncthreads();
 #endif
-    const int n_inst = P.n_instances;
+    const int n_inst = P0->n_instances;
     int *const ring = ticket + 4, *const prog = ticket + 4 + n_inst;
     const int n_chunks = (n_ticks + LMH_CHUNK_TICKS - 1) / LMH_CHUNK_TICKS;
     const long long n_units = (long long)n_inst * n_chunks;
@@ -3731,6 +3743,10 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
     __syncthreads();
     int inst = __builtin_amdgcn_readfirstlane(s_next), tick0 = __builtin_amdgcn_readfirstlane(s_tick0);
     while (inst >= 0 && inst < n_inst) {                           // workgroup-uniform
+    // the robot's parameter block (lmh_set_params), once per unit and outside the tick loop: everything that depends on it is re-read
+    // below -- load_common copies its friction table into LDS and empties the K_f^-1, orientation and reference caches
+    LmhCParams *Pc = PARAMS ? params_of_robot(P0, inst) : P0;
+    LmhCParams &P = *Pc;
     const int n_here = (n_ticks - tick0 < LMH_CHUNK_TICKS) ? n_ticks - tick0 : LMH_CHUNK_TICKS;
     const int lane = LANE;
     const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -3761,7 +3777,7 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
         if constexpr (PIPE) {
             if (lane < 60) L[P_Q + lane] = x;
             WSYNC();
-            phase_fk<R>(L, P.gcol + 228);                          // kinematics of the first evaluation (every later one is run ahead by wave 1)
+            phase_fk<R>(L, P.lcoef);                               // kinematics of the first evaluation (every later one is run ahead by wave 1)
         }
     } else x = (lane < 30) ? st[lane] : 0.0;
     bsync<2>();
@@ -3817,7 +3833,7 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
                     WSTAMP(61);
                     if (tn != ts) refs_prepare(L, *Pe, inst, tn);
                     WSTAMP(62);
-                    phase_fk<R, true>(L, Pe->gcol + 228, (R)xs, xd4n);
+                    phase_fk<R, true>(L, Pe->lcoef, (R)xs, xd4n);
                     {   // the feet's orientation term of that evaluation (acos + sin, ~250 instructions; P_FREF is dead since the QP fills): here when
                         // the coming evaluation is in single support or flight -- wave 0's share behind this join (general-route cone solve) is
                         // then much the longer one (the helper waited ~9.6k cycles here, profiles/r04_barrier_share_mid.txt); in double support the
@@ -4078,7 +4094,7 @@ __global__ void __launch_bounds__(64) lmh_ik_kernel(LmhDevParams P_arg, double *
     const double mass = L[P_MODEL + 392];
     int iter = 0;
     for (;;) {
-        phase_fk<double>(L, P.gcol + 228);
+        phase_fk<double>(L, P.lcoef);
         phase_com_x<1, double>(L, 0);
         phase_jacobian<double>(L);
         // operationalState (:54-70)
@@ -4257,7 +4273,7 @@ __global__ void __launch_bounds__(64) lmh_com_kernel(LmhDevParams P_arg, const d
     if (LANE < 30) L[P_Q + LANE] = q[30 * (size_t)inst + LANE];
     if (LANE < 60) L[P_V + LANE] = 0.0;
     WSYNC();
-    phase_fk<double>(L, P.gcol + 228);
+    phase_fk<double>(L, P.lcoef);
     phase_com_x<1, double>(L, 0);
     if (LANE < 3) com[3 * (size_t)inst + LANE] = L[P_COM + LANE];
 }
@@ -4338,7 +4354,7 @@ __global__ void __launch_bounds__(64) lmh_terms_kernel(LmhDevParams P_arg, const
     }
     WSYNC();
     const IbSel ibsel = ib_select();
-    phase_fk<double>(L, P.gcol + 228);
+    phase_fk<double>(L, P.lcoef);
     phase_com_x<1, double>(L, 0);
     if constexpr (MODE == TM_TERMS) {                              // the world transforms, before the Newton-Euler arrays take their place
         double *o = res + (size_t)LMH_TERMS_STRIDE * inst + LMH_TERMS_OFF_T;
@@ -4524,6 +4540,29 @@ __global__ void __launch_bounds__(256) lmh_gen_jump_batch_kernel(int n, double t
         phase[so + k] = (uint8_t)((k >= a && k < b) ? LMH_PHASE_FLIGHT : LMH_PHASE_DOUBLE);
     }
 }
+// Per-robot parameter blocks (include/lmh.h, lmh_set_params): block i = the handle's block with robot i's record laid over the 19 scalars,
+// the five quotients 1.0 / w formed by plain fp64 divisions (correctly rounded: bit for bit the host's 1.0 / c.w_* of fill_params) and gcol
+// pointing at robot i's friction table.  One thread per robot; rec [n][LMH_PARAM_STRIDE], gcol_tab [n][LMH_GCOL_STRIDE], blocks [n].
+__global__ void __launch_bounds__(256) lmh_params_expand_kernel(LmhDevParams P, const double *rec, const double *gcol_tab, LmhDevParams *blocks, int n)
+{
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= n) return;
+    const double *r = rec + (size_t)LMH_PARAM_STRIDE * i;
+    // r[0] (mu) is in the friction table already; the record's order is lmh_config's
+    P.kp_joints = r[1]; P.kd_joints = r[2]; P.kp_mom = r[3]; P.kd_mom = r[4]; P.kp_feet = r[5]; P.kd_feet = r[6];
+    P.w_com_lin = r[7]; P.w_com_ang = r[8]; P.w_base_pos = r[9]; P.w_base_ang = r[10]; P.w_joints = r[11]; P.w_force = r[12]; P.w_foot = r[13];
+    P.eps_coeff = r[14];
+    P.contact_k = r[15]; P.contact_d = r[16]; P.contact_dt = r[17]; P.contact_mu = r[18];
+    P.inv_w_base_pos = 1.0 / r[9]; P.inv_w_base_ang = 1.0 / r[10]; P.inv_w_joints = 1.0 / r[11];
+    P.inv_w_com_lin = 1.0 / r[7]; P.inv_w_foot = 1.0 / r[13];
+    P.gcol = gcol_tab + (size_t)LMH_GCOL_STRIDE * i;
+    P.inst_blocks = nullptr;                                       // a robot's block is never a launch's block
+    blocks[i] = P;
+}
+extern "C" void lmh_launch_params_expand(const LmhDevParams *P, const double *d_rec, const double *d_gcol_tab, LmhDevParams *d_blocks, int n, hipStream_t s)
+{
+    hipLaunchKernelGGL(lmh_params_expand_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, *P, d_rec, d_gcol_tab, d_blocks, n);
+}
 extern "C" void lmh_launch_gen_walk(const LmhWalkSpec *W, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos, hipStream_t s)
 {
     hipLaunchKernelGGL(lmh_gen_walk_kernel, dim3(1), dim3(256), 0, s, *W, (const LmhWalkSpec *)nullptr, 2 * W->num_steps + 2, zx, zy, phase, segs, sos);
@@ -4617,9 +4656,15 @@ extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_
     const int slots = rollout_resident_groups();
     const dim3 grid((unsigned)((P->n_instances < slots) ? P->n_instances : slots));
     // (the untraced instantiations ignore the two trace arguments)
+    // (per-robot parameter blocks, lmh_set_params: the instantiations that select the robot's block)
+    const bool per_robot = P->inst_blocks != nullptr;
+#define LMH_LAUNCH_ROLLOUT_AS(R, QF32, TRACE, PARAMS) \
+        hipLaunchKernelGGL((lmh_rollout_kernel<R, QF32, TRACE, PARAMS>), grid, dim3(LMH_ROLLOUT_THREADS), 0, s, d_P, d_ticket, state, out, status, log, n_ticks, trace, trace_every)
 #define LMH_LAUNCH_ROLLOUT(R, QF32) do { \
-        if (trace) hipLaunchKernelGGL((lmh_rollout_kernel<R, QF32, true>), grid, dim3(LMH_ROLLOUT_THREADS), 0, s, d_P, d_ticket, state, out, status, log, n_ticks, trace, trace_every); \
-        else hipLaunchKernelGGL((lmh_rollout_kernel<R, QF32, false>), grid, dim3(LMH_ROLLOUT_THREADS), 0, s, d_P, d_ticket, state, out, status, log, n_ticks, trace, trace_every); \
+        if (trace && per_robot) LMH_LAUNCH_ROLLOUT_AS(R, QF32, true, true); \
+        else if (trace) LMH_LAUNCH_ROLLOUT_AS(R, QF32, true, false); \
+        else if (per_robot) LMH_LAUNCH_ROLLOUT_AS(R, QF32, false, true); \
+        else LMH_LAUNCH_ROLLOUT_AS(R, QF32, false, false); \
     } while (0)
 #ifndef LMH_ROLLOUT_ONLY
     if (P->precision == 2) LMH_LAUNCH_ROLLOUT(float, true);
@@ -4628,6 +4673,7 @@ extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_
 #endif
     LMH_LAUNCH_ROLLOUT(double, false);
 #undef LMH_LAUNCH_ROLLOUT
+#undef LMH_LAUNCH_ROLLOUT_AS
 }
 #ifndef LMH_ROLLOUT_ONLY
 extern "C" void lmh_launch_model(const double *raw, double *model, int n_models, const double *lcoef, hipStream_t s)

@@ -29,7 +29,7 @@ if not reuse:
                            "-mllvm", "-amdgpu-sched-strategy=iterative-ilp", "-mllvm", "-disable-machine-licm", *extra, src, "-o", out],
                           stderr=subprocess.DEVNULL if "--verbose" not in argv else None)
 lines = open(out).read().split("\n")
-KNAME = "_Z18lmh_rollout_kernelIdLb0ELb%dEE" % int("--trace" in argv)     # lmh_rollout_kernel<double, false, TRACE>
+KNAME = "_Z18lmh_rollout_kernelIdLb0ELb%dELb0EE" % int("--trace" in argv)     # lmh_rollout_kernel<double, false, TRACE, false>
 start = next(i for i, l in enumerate(lines) if l.startswith(KNAME))
 end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
 names = {0: "eval start", 1: "fk / prep done", 2: "joined", 3: "com_x share", 4: "joined", 5: "tree share", 6: "(no join)", 7: "refs share (+prefill)", 8: "joined",
