@@ -81,6 +81,11 @@ extern "C" {
 #define LMH_TERMS_OFF_ANGMOM 1500 /* [3] Robot::getComAngMom */
 #define LMH_TERMS_OFF_MASS 1503   /* Robot::getMass of the robot's model */
 #define LMH_TERMS_OFF_T 1504      /* [28][3][4] world transform of every frame, rows 0..2 of Robot::getT (row 3 is 0 0 0 1) */
+#define LMH_CONTACT_STRIDE 40     /* one contact record, see lmh_contact_wrench */
+/* offsets into one contact record (doubles) */
+#define LMH_CONTACT_OFF_W 0       /* [12] contact wrench n_R f_R n_L f_L about the sole origins, world axes, like out.f */
+#define LMH_CONTACT_OFF_VF 12     /* [8][3] force at every sole vertex, foot-major (right foot first), vertices in the order of Robot.cpp:38-42 */
+#define LMH_CONTACT_OFF_PAD 36    /* [4] zero */
 
 /* status flags */
 #define LMH_FLAG_QP_MAXITER 1     /* active-set iteration cap hit (reference: "QP failed", controller.cpp:472-476) */
@@ -266,7 +271,7 @@ int lmh_get_mpc_gain(lmh_handle *h, double *K);
  * whose tick has not started (a push at tick a is applied by the second call when it loads the robot; the 250-tick hand-overs inside a
  * launch follow the same rule).  A push whose tick is below the robot's tick number at the start of the launch is in the past and is
  * ignored; one beyond the last tick is never applied.  Same with plant = 0 and 1 and in every precision.  External forces on the plant
- * are not modelled.  lmh_eval, lmh_eval_debug and lmh_eval_host do not integrate and ignore the schedule.
+ * are not part of lmh_rollout; lmh_plant_derivative / lmh_plant_step take an external wrench on the base (rows 0..5 of their tau30).  lmh_eval, lmh_eval_debug and lmh_eval_host do not integrate and ignore the schedule.
  * records: HOST [n_sets][n_push][LMH_PUSH_STRIDE], n_sets = 1 (one schedule shared by all robots) or n_instances; per schedule the
  * ticks are whole numbers below 2^31, strictly increasing, dv finite; unused trailing records carry tick -1 (their dv is ignored).
  * n_push <= LMH_MAX_PUSHES.  records = NULL or n_push = 0 clears the schedule.  A refused call (the error text names the first offending
@@ -392,6 +397,39 @@ int lmh_inverse_dynamics(lmh_handle *h, const double *d_q, const double *d_v, co
  * pivoting (M is symmetric positive definite).  d_flags[i]: LMH_FLAG_NOT_SPD when a pivot of robot i's matrix was not positive,
  * LMH_FLAG_NONFINITE when its result holds a NaN / Inf; neither stops the other robots. */
 int lmh_forward_dynamics(lmh_handle *h, const double *d_q, const double *d_v, const double *d_tau30, const double *d_w, double *d_qdd, int32_t *d_flags, void *stream);
+
+/* ---- Torque-driven plant (build-defined): the compliant-contact plant of lmh_config.plant = 1 as calls of its own, driven by torques the CALLER
+ * supplies -- a learned policy, the controller of lmh_eval held over several physics steps (zero-order hold), or none (a passive robot).
+ * One kernel family of its own, one wave per robot, fp64.  The calls are asynchronous on `stream`, read the handle's model tables (per-robot
+ * models honoured) and the robot's contact constants -- lmh_config's contact_k / contact_d / contact_dt / contact_mu, or the robot's record of
+ * lmh_set_params -- and write nothing into the handle: a later lmh_eval or lmh_rollout is bit for bit unaffected.  They work on a handle
+ * with plant = 0 too; such a handle never had its contact constants checked, so every call checks the host copy (the config, or every
+ * per-robot record) by lmh_create's rules for plant = 1 and refuses with LMH_ERR_BAD_ARG, naming the robot ("robot 7: ..."), before anything
+ * is enqueued.  NULL for a required pointer returns LMH_ERR_BAD_ARG before anything is enqueued.
+ * Contact model: see lmh_config.plant.  Vertex v of a sole at x = o_sole + r_v moving with xdot = v_o + w x r_v (the sole's twist J vhat at the
+ * v given): penetration d = -x_z > 0 gives the normal force max(0, k d - c xdot_z) and the tangential force -c_t xdot_xy scaled back onto the
+ * friction disc mu f_n; a vertex out of the ground carries exactly 0.
+ * DEVICE pointers: d_q, d_v [B][30] (the state's ordering), d_tau30 [B][30], d_contact [B][LMH_CONTACT_STRIDE], d_xdot [B][60], d_state
+ * [B][LMH_STATE_STRIDE], d_flags [B].
+ * d_tau30 is in the coordinates of M, exactly as lmh_forward_dynamics takes it: rows 6..29 are the joint torques, rows 0..5 an EXTERNAL WRENCH
+ * ON THE BASE ([angular | linear], base frame) -- this is how external forces enter the plant.  NULL means zero: a passive robot.
+ *
+ * lmh_contact_wrench: the ground's forces for a batch of states.  d_v == NULL means v = 0.  Record (LMH_CONTACT_OFF_*): w(12: n_R f_R n_L f_L,
+ * about the sole origins, world axes, like out.f) | vertex force [8][3] | pad(4) = 0. */
+int lmh_contact_wrench(lmh_handle *h, const double *d_q, const double *d_v, double *d_contact, void *stream);
+/* xdot = d/dt (q, v) of the plant: xdot[0:30] is qdot from v (v_lin + omega x p_base, the Euler rates Omega(rpy) omega, the joint rates:
+ * apps/offline/main.cpp:107-116); xdot[30:60] is the acceleration solving M a = tau30 + J'w_c - C(q, v), turned back to the state's ordering
+ * and the world frame -- what out.qdd carries with plant = 1.  Every velocity product is taken at the v given, as in lmh_terms.  The solve
+ * uses the structure of M (four limb blocks, the head's, a 6 x 6 Schur complement on the base).  d_contact (may be NULL) receives the
+ * contact record of the state.  d_flags[i] (may be NULL): LMH_FLAG_NOT_SPD when a pivot of robot i's solve was rejected, LMH_FLAG_NONFINITE
+ * when its result holds a NaN / Inf; neither stops the other robots. */
+int lmh_plant_derivative(lmh_handle *h, const double *d_q, const double *d_v, const double *d_tau30, double *d_xdot, double *d_contact, int32_t *d_flags, void *stream);
+/* n_substeps classic RK4 steps (rk4.hpp:5-18) of lmh_config.dt on (q, v) of the state records with the torques held, state on chip for the
+ * whole launch; t += dt after every substep (Clock::step's accumulation order).  v_prev and the pads of the record are left untouched: a
+ * caller alternating lmh_eval and this call sees the stale-velocity convention of a zero-order-hold loop (lmh_eval stores v_prev <- v).
+ * n_substeps = 0 is legal and enqueues nothing; a negative value returns LMH_ERR_BAD_ARG.  lmh_plant_step(a + b) equals lmh_plant_step(a)
+ * followed by lmh_plant_step(b) bit for bit.  d_flags[i] (may be NULL): the flags of lmh_plant_derivative, OR-ed over the substeps. */
+int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_tau30, int n_substeps, int32_t *d_flags, void *stream);
 
 /* host-buffer convenience used by the C++ shim (B instances, staged through internal
  * device buffers, synchronous): q/dq [B][30], t, outputs tau[B][24], f[B][12], qdd[B][30] */

@@ -36,6 +36,10 @@ TERMS_FIELDS = {
     "mass": (1503, ()), "T": (1504, (28, 3, 4)),
 }
 
+CONTACT_STRIDE = 40           # one contact record (lmh_contact_wrench, lmh_plant_derivative)
+# name -> (offset, shape) inside a contact record: the LMH_CONTACT_OFF_* defines of include/lmh.h
+CONTACT_FIELDS = {"w": (0, (12,)), "vertex_force": (12, (8, 3)), "pad": (36, (4,))}
+
 FLAG_QP_MAXITER = 1
 FLAG_NONFINITE = 2
 FLAG_ZMP_RANGE = 4
@@ -62,6 +66,7 @@ EXPORTS = [
     "lmh_rollout_trace", "lmh_trace_samples", "lmh_write_trace", "lmh_read_trace",
     "lmh_terms", "lmh_inverse_dynamics", "lmh_forward_dynamics", "lmh_terms_host",
     "lmh_set_params", "lmh_params_per_instance", "lmh_get_params",
+    "lmh_contact_wrench", "lmh_plant_derivative", "lmh_plant_step",
 ]
 
 
@@ -135,6 +140,9 @@ def lib():
     L.lmh_inverse_dynamics.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     L.lmh_forward_dynamics.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.lmh_terms_host.argtypes = [vp, vp, vp, vp]
+    L.lmh_contact_wrench.argtypes = [vp, vp, vp, vp, vp]
+    L.lmh_plant_derivative.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.lmh_plant_step.argtypes = [vp, vp, vp, ip, vp, vp]
     L.lmh_set_segments.argtypes = [vp, vp, ip, vp, ip]
     L.lmh_set_xscale.argtypes = [vp, vp, ip]
     u64, u64p, dpp = C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)

@@ -424,6 +424,47 @@ class BatchedController:
         lead = tuple(t.shape[:-1])
         return {k: t[..., o:o + int(np.prod(s, dtype=np.int64))].reshape(lead + tuple(s)) for k, (o, s) in capi.TERMS_FIELDS.items()}
 
+    # -- torque-driven plant (include/lmh.h, lmh_contact_wrench): the compliant-contact plant under torques the caller supplies
+    def contact_wrench(self, q, v=None):
+        """The ground's forces on the soles for q, v [B,30] (device tensors; v=None is v = 0) -> [B,40], one record per robot
+        (split_contact names its fields): the spring-damper contact of lmh_config.plant with the robot's own contact constants."""
+        q, v = self._batch("q", q, 30), self._batch("v", v, 30, optional=True)
+        c = torch.empty((self.B, capi.CONTACT_STRIDE), dtype=torch.float64, device=self.device)
+        check(capi.lib().lmh_contact_wrench(self._h, _dev_ptr(q), None if v is None else _dev_ptr(v), _dev_ptr(c), self._stream()))
+        return c
+
+    def plant_derivative(self, q, v, tau=None):
+        """xdot of the plant for q, v [B,30] under tau [B,30] in the coordinates of M (rows 6..29 joint torques, rows 0..5 an external wrench
+        on the base; None: a passive robot) -> (xdot [B,60], contact [B,40], flags [B] int32: FLAG_NOT_SPD / FLAG_NONFINITE per robot).
+        xdot[:, :30] is qdot from v, xdot[:, 30:] solves M a = tau + J'w_c - C(q, v) (state ordering, world frame)."""
+        q, v, tau = self._batch("q", q, 30), self._batch("v", v, 30), self._batch("tau", tau, 30, optional=True)
+        xdot = torch.empty((self.B, 60), dtype=torch.float64, device=self.device)
+        c = torch.empty((self.B, capi.CONTACT_STRIDE), dtype=torch.float64, device=self.device)
+        flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+        check(capi.lib().lmh_plant_derivative(self._h, _dev_ptr(q), _dev_ptr(v), None if tau is None else _dev_ptr(tau), _dev_ptr(xdot), _dev_ptr(c),
+                                              _dev_ptr(flags), self._stream()))
+        return xdot, c, flags
+
+    def plant_step(self, state, tau=None, n_substeps=1):
+        """n_substeps RK4 steps of cfg.dt on (q, v) of the state records [B,96], in place, with tau [B,30] held (None: passive); t advances,
+        v_prev stays.  -> (state, flags [B] int32, OR-ed over the substeps)."""
+        tau = self._batch("tau", tau, 30, optional=True)
+        if not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or tuple(state.shape) != (self.B, capi.STATE_STRIDE) \
+                or state.device != self.device or not state.is_contiguous():
+            raise ValueError(f"state must be a contiguous [{self.B},{capi.STATE_STRIDE}] float64 tensor on {self.device} (it is updated in place)")
+        if int(n_substeps) != n_substeps or n_substeps < 0:
+            raise ValueError("n_substeps must be a whole number >= 0")
+        flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+        check(capi.lib().lmh_plant_step(self._h, _dev_ptr(state), None if tau is None else _dev_ptr(tau), int(n_substeps), _dev_ptr(flags), self._stream()))
+        return state, flags
+
+    @staticmethod
+    def split_contact(c):
+        """Named views of contact records [.., 40] (tensor or array): w [..,12] (n_R f_R n_L f_L), vertex_force [..,8,3], pad [..,4] --
+        capi.CONTACT_FIELDS."""
+        lead = tuple(c.shape[:-1])
+        return {k: c[..., o:o + int(np.prod(s, dtype=np.int64))].reshape(lead + tuple(s)) for k, (o, s) in capi.CONTACT_FIELDS.items()}
+
     def make_summary(self, state, out, status):
         """End-of-run summary [B,16] (include/lmh.h lmh_make_summary): the record the RCCL gather moves."""
         s = torch.empty((self.B, capi.SUMMARY_WIDTH), dtype=torch.float64, device=self.device)

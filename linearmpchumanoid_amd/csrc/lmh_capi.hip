@@ -23,6 +23,8 @@ extern "C" void lmh_launch_gen_jump(int n, double time_step, double stance_time,
 extern "C" void lmh_launch_gen_walk_batch(const LmhWalkSpec *d_specs, int n_plans, int seg_stride, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos, hipStream_t s);
 extern "C" void lmh_launch_gen_jump_batch(int n, double time_step, const LmhJumpSpec *d_specs, int n_plans, double *zx, double *zy, uint8_t *phase, hipStream_t s);
 extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *q, const double *v, const double *x, const double *w, double *res, int32_t *flags, hipStream_t s);
+extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact, int32_t *flags,
+                                 int n_substeps, hipStream_t s);
 extern "C" void lmh_launch_params_expand(const LmhDevParams *P, const double *d_rec, const double *d_gcol_tab, LmhDevParams *d_blocks, int n, hipStream_t s);
 extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
 
@@ -888,6 +890,57 @@ extern "C" int lmh_inverse_dynamics(lmh_handle *h, const double *d_q, const doub
 extern "C" int lmh_forward_dynamics(lmh_handle *h, const double *d_q, const double *d_v, const double *d_tau30, const double *d_w, double *d_qdd, int32_t *d_flags, void *stream)
 {
     return terms_body(h, 2, d_q, d_v, d_tau30, d_w, d_qdd, d_flags, stream);
+}
+
+// ---------------------------------------------------------------------------- torque-driven plant
+// A handle with plant = 0 never had its contact constants checked (validate_config, param_record_error): the plant calls check the host copy
+static int plant_constants_ok(const lmh_handle *h)
+{
+    const char *rule = "contact_k must be positive, contact_d / contact_dt / contact_mu non-negative";
+    auto bad = [](double k, double d, double dt, double mu) { return !(k > 0.0) || !(d >= 0.0) || !(dt >= 0.0) || !(mu >= 0.0); };
+    if (!h->inst.on()) {
+        const lmh_config &c = h->cfg;
+        return bad(c.contact_k, c.contact_d, c.contact_dt, c.contact_mu) ? fail(LMH_ERR_BAD_ARG, rule) : LMH_OK;
+    }
+    for (int i = 0; i < h->B; i++) {
+        const double *r = h->inst.h_rec.data() + (size_t)LMH_PARAM_STRIDE * i;
+        if (bad(r[LMH_PARAM_OFF_CONTACT_K], r[LMH_PARAM_OFF_CONTACT_D], r[LMH_PARAM_OFF_CONTACT_DT], r[LMH_PARAM_OFF_CONTACT_MU])) return fail(LMH_ERR_BAD_ARG, robot_msg(i, rule));
+    }
+    return LMH_OK;
+}
+
+// mode: 0 contact wrench, 1 derivative, 2 RK4 step (lmh_kernels.hip, lmh_plant_kernel).  The caller has checked its required pointers.
+static int plant_body(lmh_handle *h, int mode, const double *d_q, const double *d_v, const double *d_tau30, double *d_state, double *d_xdot, double *d_contact, int32_t *d_flags,
+                      int n_substeps, void *stream)
+{
+    int rc = plant_constants_ok(h); if (rc) return rc;
+    HIPCHK(hipSetDevice(h->device));
+    lmh_launch_plant(&h->P, mode, d_q, d_v, d_tau30, d_state, d_xdot, d_contact, d_flags, n_substeps, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
+    return LMH_OK;
+}
+
+extern "C" int lmh_contact_wrench(lmh_handle *h, const double *d_q, const double *d_v, double *d_contact, void *stream)
+{
+    int rc = ready(h); if (rc) return rc;
+    if (!d_q || !d_contact) return fail(LMH_ERR_BAD_ARG, "lmh_contact_wrench: null device pointer");
+    return plant_body(h, 0, d_q, d_v, nullptr, nullptr, nullptr, d_contact, nullptr, 0, stream);
+}
+
+extern "C" int lmh_plant_derivative(lmh_handle *h, const double *d_q, const double *d_v, const double *d_tau30, double *d_xdot, double *d_contact, int32_t *d_flags, void *stream)
+{
+    int rc = ready(h); if (rc) return rc;
+    if (!d_q || !d_v || !d_xdot) return fail(LMH_ERR_BAD_ARG, "lmh_plant_derivative: null device pointer");
+    return plant_body(h, 1, d_q, d_v, d_tau30, nullptr, d_xdot, d_contact, d_flags, 0, stream);
+}
+
+extern "C" int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_tau30, int n_substeps, int32_t *d_flags, void *stream)
+{
+    int rc = ready(h); if (rc) return rc;
+    if (!d_state) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step: null device pointer");
+    if (n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step: n_substeps must be >= 0");
+    if (n_substeps == 0) return plant_constants_ok(h);               // nothing to enqueue
+    return plant_body(h, 2, nullptr, nullptr, d_tau30, d_state, nullptr, nullptr, d_flags, n_substeps, stream);
 }
 
 extern "C" int lmh_terms_host(lmh_handle *h, const double *q, const double *v, double *terms)

@@ -3140,9 +3140,10 @@ enum { PL_0 = S0 + 384,     // above S0 + [0, 384): the next evaluation's world 
        PL_DAB = PL_0 + 300, // 6
        PL_AP = PL_0 + 306,  // 30 : plant acceleration (WBC coordinates)
        PL_ZERO = PL_0 + 336 }; // 32
-__device__ __forceinline__ void phase_plant(double *L, LmhCParams &P)
+// The plant in pieces, shared by phase_plant and lmh_plant_kernel (the caller passes its LANE: the helpers add no opaque lane reads).
+// (1) spring-damper force of every sole vertex -> PL_VF (r_v x f_v | f_v); clears PL_ZERO
+__device__ __forceinline__ void plant_vertex_forces(double *L, LmhCParams &P, int lane)
 {
-    const int lane = LANE;
     if (lane < 8) {                                                // one lane per (foot, vertex)
         const int ft = lane >> 2, vi = lane & 3;
         const double pwx = (vi < 2) ? 0.1 : -0.05, pwy = (vi & 1) ? -0.025 : 0.025, pwz = 0.0;        // Robot.cpp:38-42
@@ -3171,22 +3172,30 @@ __device__ __forceinline__ void phase_plant(double *L, LmhCParams &P)
     }
     if (lane >= 32) L[PL_ZERO + lane - 32] = 0.0;
     WSYNC();
-    if (lane < 12) {                                               // wrench about the sole origin, vertices summed in order
-        const int ft = lane / 6, k = lane % 6;
-        const double *v = L + PL_VF + 24 * ft + k;
-        const double wc = (((0.0 + v[0]) + v[6]) + v[12]) + v[18];
-        L[PL_DW + lane] = wc - L[P_W12 + lane];
-    }
-    WSYNC();
-    if (lane < 30) {                                               // r = J'(w_c - w) (base and leg columns only) + C(q, v_prev) - C(q, v)
-        double r = 0.0;
-        if (lane < 18) {
+}
+// entry `lane` < 12 of the contact wrench about the sole origins, vertices summed in order
+__device__ __forceinline__ double plant_wrench_entry(const double *L, int lane)
+{
+    const int ft = lane / 6, k = lane % 6;
+    const double *v = L + PL_VF + 24 * ft + k;
+    return (((0.0 + v[0]) + v[6]) + v[12]) + v[18];
+}
+// (J' PL_DW)[lane], lane < 30: base and leg columns only
+__device__ __forceinline__ double plant_jt_dw(const double *L, int lane)
+{
+    double r = 0.0;
+    if (lane < 18) {
 #pragma unroll
-            for (int row = 0; row < 12; row++) r += jdense(L, row, lane) * L[PL_DW + row];
-        }
-        L[PL_R + lane] = r + (L[P_C + lane] - L[P_VHS + lane]);    // P_VHS: the plant's own Newton-Euler pass at the current velocity
+        for (int row = 0; row < 12; row++) r += jdense(L, row, lane) * L[PL_DW + row];
     }
-    WSYNC();
+    return r;
+}
+// (2) M^-1 PL_R by the structure above; lane < 30 hands entry `lane` to sink(da).  CHECK: returns LMH_FLAG_NOT_SPD (wave-uniform) when a
+// pivot of a limb block, the head's block or the Schur complement was not positive -- nobody pays for the test otherwise
+template <bool CHECK, class SINK>
+__device__ __forceinline__ int plant_minv(double *L, int lane, SINK sink)
+{
+    int notspd = 0;
     {   // limb blocks: DPP row dr = limb (RL, LL, RA, LA), lane l16 < 6 = joint of the limb (arms: a unit row pads 5 -> 6)
         const int dr = lane >> 4, l16 = lane & 15;
         const int nl = (dr < 2) ? 6 : 5, js = (dr == 0) ? 0 : (dr == 1) ? 6 : (dr == 2) ? 12 : 17;
@@ -3203,6 +3212,7 @@ __device__ __forceinline__ void phase_plant(double *L, LmhCParams &P)
         gj16_step<0>(a, b, 0x3Fu, l16, true, 0.0, bad, myinv);
 #pragma unroll
         for (int c = 0; c < 7; c++) L[real ? PL_B + 7 * ja + c : Q_TRASH + lane] = b[c] * myinv;
+        if constexpr (CHECK) notspd |= bad;
     }
     if (lane < 14) {                                               // head: 2 x 2 in closed form
         const int i = lane / 7, c = lane % 7;
@@ -3210,6 +3220,7 @@ __device__ __forceinline__ void phase_plant(double *L, LmhCParams &P)
         const double r0 = (c == 0) ? L[PL_R + 6 + 22] : L[P_MTOP + 30 * (c - 1) + 6 + 22], r1 = (c == 0) ? L[PL_R + 6 + 23] : L[P_MTOP + 30 * (c - 1) + 6 + 23];
         const double det = h00 * h11 - h01 * h10;
         L[PL_B + 7 * (22 + i) + c] = (i == 0) ? (h11 * r0 - h01 * r1) / det : (h00 * r1 - h10 * r0) / det;
+        if constexpr (CHECK) notspd |= (int)!(h00 > 0.0 && det > 0.0);
     }
     WSYNC();
     {   // base: S_b = Ic0 - F2 B_M, rhs = r_b - F2 B_r   (one matrix-core tile, K = 24)
@@ -3231,7 +3242,8 @@ __device__ __forceinline__ void phase_plant(double *L, LmhCParams &P)
 #pragma unroll
         for (int c = 0; c < 6; c++) a[c] = L[PL_SB + 7 * lr + 1 + c];
         b[0] = L[PL_SB + 7 * lr];
-        (void)gj_solve_regs<6, 1>(a, b, 0x3Fu);
+        const int bad6 = gj_solve_regs<6, 1>(a, b, 0x3Fu);
+        if constexpr (CHECK) notspd |= bad6; else (void)bad6;
         if (lane < 6) L[PL_DAB + lane] = b[0];
     }
     WSYNC();
@@ -3244,9 +3256,21 @@ __device__ __forceinline__ void phase_plant(double *L, LmhCParams &P)
 #pragma unroll
             for (int n = 0; n < 6; n++) da -= B[1 + n] * L[PL_DAB + n];
         }
-        L[PL_AP + lane] = L[P_A + lane] + da;
+        sink(da);
     }
     WSYNC();
+    if constexpr (CHECK) return (__ballot(notspd != 0) != 0ull) ? LMH_FLAG_NOT_SPD : 0;
+    else return 0;
+}
+__device__ __forceinline__ void phase_plant(double *L, LmhCParams &P)
+{
+    const int lane = LANE;
+    plant_vertex_forces(L, P, lane);
+    if (lane < 12) L[PL_DW + lane] = plant_wrench_entry(L, lane) - L[P_W12 + lane];      // w_c - w
+    WSYNC();
+    if (lane < 30) L[PL_R + lane] = plant_jt_dw(L, lane) + (L[P_C + lane] - L[P_VHS + lane]);    // + C(q, v_prev) - C(q, v); P_VHS: the plant's own Newton-Euler pass at the current velocity
+    WSYNC();
+    (void)plant_minv<false>(L, lane, [&](double da) { L[PL_AP + lane] = L[P_A + lane] + da; });
 }
 
 // Controller::WBC tail (controller.cpp:134-153): tau, base acceleration back to the world frame.
@@ -4419,6 +4443,112 @@ __global__ void __launch_bounds__(64) lmh_terms_kernel(LmhDevParams P_arg, const
         }
     }
 }
+// ============================================================================ torque-driven plant: contact wrench, derivative, RK4 step
+// lmh_contact_wrench / lmh_plant_derivative / lmh_plant_step (include/lmh.h): the compliant-contact plant of lmh_config.plant = 1 without the
+// controller in front of it.  One wave per robot in the single-wave schedule of lmh_terms_kernel; the caller's tau30 (joint torques and an
+// external wrench on the base) takes the place of the WBC's torques, so one derivative is
+//     kinematics -> X images -> Newton-Euler at v (P_VP = P_V) -> CRBA -> Jacobian -> sole twists -> vertex forces, wrench w_c ->
+//     r = tau30 + J'w_c - C -> a = M^-1 r (plant_minv: limb blocks on the DPP rows, 6 x 6 Schur complement) -> world frame (phase_outputs_qdd)
+// and reads no reference plan, MPC row, QP or clock.  CONTACT stops behind the wrench and runs neither Newton-Euler nor the CRBA.
+// STEP keeps (q, v) in registers, lane i < 60 = component i as in the rollout (rk4_stage), for all substeps of the launch: HBM sees the
+// state record once in and once out; v_prev and the pads of the record are not written.  The contact constants are the robot's own
+// (params_of_robot); the kernel reads no other per-robot parameter.
+enum { PM_CONTACT = 0, PM_DERIV = 1, PM_STEP = 2 };
+static_assert(LMH_CONTACT_STRIDE == 12 + 24 + 4, "w | vertex forces | pad");
+
+// the contact wrench of the state in L[P_Q], L[P_V] -> PL_DW (PL_VF: the vertex forces); the tree phases up to the Jacobian have run
+__device__ __forceinline__ void plant_contact(double *L, LmhCParams &P, int lane)
+{
+    refs_vfoot_pdjoints(L, P);                                     // sole twists J vhat -> P_VFOOT (its PD law on lanes 32..61 rides along unread)
+    WSYNC();
+    plant_vertex_forces(L, P, lane);
+    if (lane < 12) L[PL_DW + lane] = plant_wrench_entry(L, lane);
+    WSYNC();
+}
+// one derivative of the state in L[P_Q], L[P_V]: accelerations -> L[P_QDD] (state ordering, world frame); `tau`: lane i < 30 holds tau30[i]
+__device__ __forceinline__ int plant_derivative(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau)
+{
+    if (lane < 30) L[P_VP + lane] = L[P_V + lane];                 // one velocity for every term
+    WSYNC();
+    phase_fk<double>(L, P.lcoef);
+    phase_com_x<1, double>(L, 0);
+    phase_newton_euler<double>(L);
+    phase_crba<double>(L, ib_unpack(ibp));
+    phase_jacobian<double>(L);
+    plant_contact(L, P, lane);
+    if (lane < 30) L[PL_R + lane] = (tau + plant_jt_dw(L, lane)) - L[P_C + lane];
+    WSYNC();
+    const int flags = plant_minv<true>(L, lane, [&](double a) { L[PL_AP + lane] = a; });
+    phase_outputs_qdd(L, PL_AP);
+    return flags;
+}
+__device__ __forceinline__ void plant_store_contact(const double *L, double *o, int lane)
+{
+    const int e = (lane >= 12 && lane < 36) ? lane - 12 : 0;
+    const double w = L[PL_DW + ((lane < 12) ? lane : 0)], f = L[PL_VF + 6 * (e / 3) + 3 + e % 3];
+    if (lane < LMH_CONTACT_STRIDE) o[lane] = (lane < 12) ? w : (lane < 36) ? f : 0.0;
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(64) lmh_plant_kernel(LmhDevParams P_arg, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact,
+                                                       int32_t *flags_out, int n_substeps)
+{
+    LmhCParams &P0 = LMH_KERNARG_PARAMS();
+    __shared__ double L[LDS_DOUBLES];
+    const int inst = blockIdx.x;
+    if (inst >= P0.n_instances) return;
+    LmhCParams &P = *params_of_robot(&P0, inst);
+    const int lane = LANE;
+    SET_GDBG(nullptr);
+    load_common(L, P, inst);
+    if constexpr (MODE == PM_CONTACT) {
+        if (lane < 30) {
+            const double vv = v ? v[30 * (size_t)inst + lane] : 0.0;
+            L[P_Q + lane] = q[30 * (size_t)inst + lane];
+            L[P_V + lane] = vv; L[P_VP + lane] = vv;
+        }
+        WSYNC();
+        phase_fk<double>(L, P.lcoef);
+        phase_com_x<1, double>(L, 0);
+        phase_jacobian<double>(L);
+        plant_contact(L, P, lane);
+        plant_store_contact(L, contact + (size_t)LMH_CONTACT_STRIDE * inst, lane);
+    } else {
+        const IbPack ibp = ib_pack();
+        const double tau = (tau30 && lane < 30) ? tau30[30 * (size_t)inst + lane] : 0.0;
+        int flags = 0;
+        if constexpr (MODE == PM_DERIV) {
+            if (lane < 30) { L[P_Q + lane] = q[30 * (size_t)inst + lane]; L[P_V + lane] = v[30 * (size_t)inst + lane]; }
+            WSYNC();
+            flags |= plant_derivative(L, P, ibp, lane, tau);
+            double x = 0.0, xd = 0.0, xs = 0.0;
+            rk4_stage<0>(L, 0, lane, 0.0, P_SC + 52, x, xd, xs);   // the first stage leaves xdot itself in its sum: fma(1, xdot, 0 * 0)
+            if (__ballot(lane < 60 && !(fabs(xd) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
+            if (lane < 60) xdot[60 * (size_t)inst + lane] = xd;
+            if (contact) plant_store_contact(L, contact + (size_t)LMH_CONTACT_STRIDE * inst, lane);
+        } else {
+            double *st = state + (size_t)LMH_STATE_STRIDE * inst;
+            double x = (lane < 60) ? st[lane] : 0.0, t = st[90];
+            const double dt = P.dt;
+#pragma unroll 1
+            for (int sub = 0; sub < n_substeps; sub++) {
+                double ksum = 0.0, xs = x;
+#pragma unroll 1
+                for (int stage = 0; stage < 4; stage++) {          // rk4.hpp:5-18 with the torques held
+                    WSYNC();
+                    if (lane < 60) L[P_Q + lane] = xs;             // q | v are one run
+                    WSYNC();
+                    flags |= plant_derivative(L, P, ibp, lane, tau);
+                    rk4_stage<0>(L, stage, lane, dt, P_SC + 52, x, ksum, xs);
+                }
+                if (__ballot(lane < 60 && !(fabs(x) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
+                t += dt;                                           // Clock::step, Clock.hpp:11
+            }
+            if (lane < 60) st[lane] = x; else if (lane == 60) st[90] = t;
+        }
+        if (lane == 0 && flags_out) flags_out[inst] = flags;
+    }
+}
 #ifndef LMH_ROLLOUT_ONLY
 extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *q, const double *v, const double *x, const double *w, double *res, int32_t *flags, hipStream_t s)
 {
@@ -4426,6 +4556,14 @@ extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *
     if (mode == TM_TERMS) hipLaunchKernelGGL(lmh_terms_kernel<TM_TERMS>, grid, block, 0, s, *P, q, v, x, w, res, flags);
     else if (mode == TM_INVDYN) hipLaunchKernelGGL(lmh_terms_kernel<TM_INVDYN>, grid, block, 0, s, *P, q, v, x, w, res, flags);
     else hipLaunchKernelGGL(lmh_terms_kernel<TM_FWDDYN>, grid, block, 0, s, *P, q, v, x, w, res, flags);
+}
+extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact, int32_t *flags,
+                                 int n_substeps, hipStream_t s)
+{
+    const dim3 grid(P->n_instances), block(64);
+    if (mode == PM_CONTACT) hipLaunchKernelGGL(lmh_plant_kernel<PM_CONTACT>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps);
+    else if (mode == PM_DERIV) hipLaunchKernelGGL(lmh_plant_kernel<PM_DERIV>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps);
+    else hipLaunchKernelGGL(lmh_plant_kernel<PM_STEP>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps);
 }
 
 #endif
