@@ -52,23 +52,6 @@ PHASE_DOUBLE, PHASE_RIGHT, PHASE_LEFT, PHASE_FLIGHT = 0, 1, 2, 3
 PRECISION_FP64, PRECISION_MIXED, PRECISION_FP32 = 0, 1, 2   # lmh_config.precision (include/lmh.h)
 SUMMARY_WIDTH = 16
 
-# every symbol include/lmh.h declares (checked by tests/test_abi.py)
-EXPORTS = [
-    "lmh_config_default", "lmh_last_error", "lmh_device_count", "lmh_create", "lmh_destroy",
-    "lmh_num_instances", "lmh_horizon", "lmh_set_model", "lmh_get_mass", "lmh_nominal_links",
-    "lmh_set_refs", "lmh_set_refs_stance", "lmh_set_foot_coeffs", "lmh_set_zcom", "lmh_get_mpc_gain",
-    "lmh_eval", "lmh_eval_debug", "lmh_rollout", "lmh_ik", "lmh_eval_host", "lmh_set_prev_velocity_host",
-    "lmh_synchronize", "lmh_robot_com", "lmh_robot_com_host", "lmh_last_out_host", "lmh_ik_host", "lmh_set_segments", "lmh_set_xscale",
-    "lmh_make_summary", "lmh_write_summary", "lmh_read_summary", "lmh_write_log", "lmh_read_log",
-    "lmh_gen_walk", "lmh_gen_jump", "lmh_num_ref_samples", "lmh_num_segments", "lmh_get_refs",
-    "lmh_gen_walk_batch", "lmh_gen_jump_batch", "lmh_set_plans", "lmh_plans_per_instance", "lmh_get_plan",
-    "lmh_set_pushes", "lmh_num_pushes", "lmh_pushes_per_instance", "lmh_get_pushes",
-    "lmh_rollout_trace", "lmh_trace_samples", "lmh_write_trace", "lmh_read_trace",
-    "lmh_terms", "lmh_inverse_dynamics", "lmh_forward_dynamics", "lmh_terms_host",
-    "lmh_set_params", "lmh_params_per_instance", "lmh_get_params",
-    "lmh_contact_wrench", "lmh_plant_derivative", "lmh_plant_step",
-]
-
 
 class LmhConfig(C.Structure):
     """struct lmh_config (include/lmh.h); defaults are the reference's literals."""
@@ -91,6 +74,74 @@ class LmhJumpSpec(C.Structure):
     _fields_ = [("stance_time", C.c_double), ("flight_time", C.c_double)]
 
 
+_vp, _ip, _dp, _str, _u64 = C.c_void_p, C.c_int, C.c_double, C.c_char_p, C.c_uint64
+_u64p, _dpp = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
+# name -> (restype, argtypes) of every symbol include/lmh.h declares; tests/test_abi.py holds each row against its prototype
+PROTOTYPES = {
+    "lmh_config_default": (None, [C.POINTER(LmhConfig)]),
+    "lmh_last_error": (_str, []),
+    "lmh_device_count": (_ip, []),
+    "lmh_create": (_ip, [C.POINTER(LmhConfig), _ip, _ip, C.POINTER(_vp)]),
+    "lmh_destroy": (_ip, [_vp]),
+    "lmh_num_instances": (_ip, [_vp]),
+    "lmh_horizon": (_ip, [_vp]),
+    "lmh_set_model": (_ip, [_vp, _vp, _ip]),
+    "lmh_get_mass": (_ip, [_vp, _vp]),
+    "lmh_nominal_links": (None, [_vp]),
+    "lmh_set_refs": (_ip, [_vp, _vp, _vp, _vp, _ip]),
+    "lmh_set_refs_stance": (_ip, [_vp, _dp, _ip]),
+    "lmh_set_foot_coeffs": (_ip, [_vp, _vp, _vp, _vp, _vp]),
+    "lmh_set_segments": (_ip, [_vp, _vp, _ip, _vp, _ip]),
+    "lmh_gen_walk": (_ip, [_vp, _dp, _ip, _dp, _dp, _dp, _dp, _ip, _dp]),
+    "lmh_gen_jump": (_ip, [_vp, _dp, _dp, _dp]),
+    "lmh_gen_walk_batch": (_ip, [_vp, _dp, _vp, _ip]),
+    "lmh_gen_jump_batch": (_ip, [_vp, _dp, _vp, _ip]),
+    "lmh_set_plans": (_ip, [_vp, _vp, _vp, _vp, _ip, _vp, _ip, _vp, _ip]),
+    "lmh_plans_per_instance": (_ip, [_vp]),
+    "lmh_num_ref_samples": (_ip, [_vp]),
+    "lmh_num_segments": (_ip, [_vp]),
+    "lmh_get_refs": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "lmh_get_plan": (_ip, [_vp, _ip, _vp, _vp, _vp, _vp, _vp]),
+    "lmh_set_xscale": (_ip, [_vp, _vp, _ip]),
+    "lmh_set_zcom": (_ip, [_vp, _vp, _ip]),
+    "lmh_get_mpc_gain": (_ip, [_vp, _vp]),
+    "lmh_set_pushes": (_ip, [_vp, _vp, _ip, _ip]),
+    "lmh_num_pushes": (_ip, [_vp]),
+    "lmh_pushes_per_instance": (_ip, [_vp]),
+    "lmh_get_pushes": (_ip, [_vp, _ip, _vp]),
+    "lmh_set_params": (_ip, [_vp, _vp, _ip]),
+    "lmh_params_per_instance": (_ip, [_vp]),
+    "lmh_get_params": (_ip, [_vp, _ip, _vp]),
+    "lmh_eval": (_ip, [_vp, _vp, _vp, _vp, _vp]),
+    "lmh_eval_debug": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "lmh_rollout": (_ip, [_vp, _vp, _vp, _vp, _vp, _ip, _vp]),
+    "lmh_rollout_trace": (_ip, [_vp, _vp, _vp, _vp, _vp, _ip, _vp, _ip, _vp]),
+    "lmh_trace_samples": (_ip, [_ip, _ip]),
+    "lmh_ik": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lmh_robot_com": (_ip, [_vp, _vp, _vp, _vp]),
+    "lmh_terms": (_ip, [_vp, _vp, _vp, _vp, _vp]),
+    "lmh_inverse_dynamics": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lmh_forward_dynamics": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lmh_contact_wrench": (_ip, [_vp, _vp, _vp, _vp, _vp]),
+    "lmh_plant_derivative": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lmh_plant_step": (_ip, [_vp, _vp, _vp, _ip, _vp, _vp]),
+    "lmh_eval_host": (_ip, [_vp, _vp, _vp, _dp, _vp, _vp, _vp, _vp]),
+    "lmh_robot_com_host": (_ip, [_vp, _vp, _vp]),
+    "lmh_last_out_host": (_ip, [_vp, _vp]),
+    "lmh_ik_host": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lmh_terms_host": (_ip, [_vp, _vp, _vp, _vp]),
+    "lmh_set_prev_velocity_host": (_ip, [_vp, _vp]),
+    "lmh_synchronize": (_ip, [_vp, _vp]),
+    "lmh_make_summary": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "lmh_write_summary": (_ip, [_str, _vp, _u64, _dp]),
+    "lmh_read_summary": (_ip, [_str, _vp, _u64, _u64p, _dpp]),
+    "lmh_write_log": (_ip, [_str, _vp, _u64, _u64, _dp, _dp]),
+    "lmh_read_log": (_ip, [_str, _vp, _u64, _u64p, _u64p, _dpp, _dpp]),
+    "lmh_write_trace": (_ip, [_str, _vp, _u64, _u64, _dp, _dp]),
+    "lmh_read_trace": (_ip, [_str, _vp, _u64, _u64p, _u64p, _dpp, _dpp]),
+}
+EXPORTS = list(PROTOTYPES)
+
 _lib = None
 
 
@@ -105,75 +156,9 @@ def lib():
             "(run `python __graft_entry__.py` or `python linearmpchumanoid_amd/build.py`). "
             "There is no CPU fallback.")
     L = C.CDLL(SO_PATH)
-    vp, ip, dp = C.c_void_p, C.c_int, C.c_double
-    L.lmh_config_default.argtypes = [C.POINTER(LmhConfig)]
-    L.lmh_config_default.restype = None
-    L.lmh_last_error.restype = C.c_char_p
-    L.lmh_device_count.restype = ip
-    L.lmh_create.argtypes = [C.POINTER(LmhConfig), ip, ip, C.POINTER(vp)]
-    L.lmh_destroy.argtypes = [vp]
-    L.lmh_num_instances.argtypes = [vp]
-    L.lmh_horizon.argtypes = [vp]
-    L.lmh_set_model.argtypes = [vp, vp, ip]
-    L.lmh_get_mass.argtypes = [vp, vp]
-    L.lmh_nominal_links.argtypes = [vp]
-    L.lmh_nominal_links.restype = None
-    L.lmh_set_refs.argtypes = [vp, vp, vp, vp, ip]
-    L.lmh_set_refs_stance.argtypes = [vp, dp, ip]
-    L.lmh_set_foot_coeffs.argtypes = [vp, vp, vp, vp, vp]
-    L.lmh_set_zcom.argtypes = [vp, vp, ip]
-    L.lmh_get_mpc_gain.argtypes = [vp, vp]
-    L.lmh_eval.argtypes = [vp, vp, vp, vp, vp]
-    L.lmh_eval_debug.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.lmh_rollout.argtypes = [vp, vp, vp, vp, vp, ip, vp]
-    L.lmh_rollout_trace.argtypes = [vp, vp, vp, vp, vp, ip, vp, ip, vp]
-    L.lmh_trace_samples.argtypes = [ip, ip]
-    L.lmh_ik.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.lmh_eval_host.argtypes = [vp, vp, vp, dp, vp, vp, vp, vp]
-    L.lmh_set_prev_velocity_host.argtypes = [vp, vp]
-    L.lmh_synchronize.argtypes = [vp, vp]
-    L.lmh_robot_com.argtypes = [vp, vp, vp, vp]
-    L.lmh_last_out_host.argtypes = [vp, vp]
-    L.lmh_robot_com_host.argtypes = [vp, vp, vp]
-    L.lmh_ik_host.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.lmh_terms.argtypes = [vp, vp, vp, vp, vp]
-    L.lmh_inverse_dynamics.argtypes = [vp, vp, vp, vp, vp, vp, vp]
-    L.lmh_forward_dynamics.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.lmh_terms_host.argtypes = [vp, vp, vp, vp]
-    L.lmh_contact_wrench.argtypes = [vp, vp, vp, vp, vp]
-    L.lmh_plant_derivative.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.lmh_plant_step.argtypes = [vp, vp, vp, ip, vp, vp]
-    L.lmh_set_segments.argtypes = [vp, vp, ip, vp, ip]
-    L.lmh_set_xscale.argtypes = [vp, vp, ip]
-    u64, u64p, dpp = C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_double)
-    L.lmh_gen_walk.argtypes = [vp, dp, ip, dp, dp, dp, dp, ip, dp]
-    L.lmh_gen_jump.argtypes = [vp, dp, dp, dp]
-    L.lmh_num_ref_samples.argtypes = [vp]
-    L.lmh_num_segments.argtypes = [vp]
-    L.lmh_get_refs.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.lmh_gen_walk_batch.argtypes = [vp, dp, vp, ip]
-    L.lmh_gen_jump_batch.argtypes = [vp, dp, vp, ip]
-    L.lmh_set_plans.argtypes = [vp, vp, vp, vp, ip, vp, ip, vp, ip]
-    L.lmh_plans_per_instance.argtypes = [vp]
-    L.lmh_get_plan.argtypes = [vp, ip, vp, vp, vp, vp, vp]
-    L.lmh_set_pushes.argtypes = [vp, vp, ip, ip]
-    L.lmh_num_pushes.argtypes = [vp]
-    L.lmh_pushes_per_instance.argtypes = [vp]
-    L.lmh_get_pushes.argtypes = [vp, ip, vp]
-    L.lmh_set_params.argtypes = [vp, vp, ip]
-    L.lmh_params_per_instance.argtypes = [vp]
-    L.lmh_get_params.argtypes = [vp, ip, vp]
-    L.lmh_make_summary.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.lmh_write_summary.argtypes = [C.c_char_p, vp, u64, dp]
-    L.lmh_read_summary.argtypes = [C.c_char_p, vp, u64, u64p, dpp]
-    L.lmh_write_log.argtypes = [C.c_char_p, vp, u64, u64, dp, dp]
-    L.lmh_read_log.argtypes = [C.c_char_p, vp, u64, u64p, u64p, dpp, dpp]
-    L.lmh_write_trace.argtypes = [C.c_char_p, vp, u64, u64, dp, dp]
-    L.lmh_read_trace.argtypes = [C.c_char_p, vp, u64, u64p, u64p, dpp, dpp]
-    for name in EXPORTS:
+    for name, (restype, argtypes) in PROTOTYPES.items():
         fn = getattr(L, name)
-        if fn.restype is C.c_int and name not in ("lmh_last_error", "lmh_config_default", "lmh_nominal_links"):
-            fn.restype = ip
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 

@@ -83,7 +83,14 @@ def _np_ptr(a):
 
 
 def _dev_ptr(t):
-    return C.c_void_p(t.data_ptr())
+    """Device address of a tensor; None (an optional argument left out) stays None, the C side's NULL."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _split(rec, fields):
+    """Named views of records [.., stride] (tensor or array) by one of the name -> (offset, shape) tables."""
+    lead = tuple(rec.shape[:-1])
+    return {k: rec[..., o:o + int(np.prod(s, dtype=np.int64))].reshape(lead + tuple(s)) for k, (o, s) in fields.items()}
 
 
 class BatchedController:
@@ -168,13 +175,9 @@ class BatchedController:
         check(capi.lib().lmh_gen_jump(self._h, float(simulation_time), float(stance_time), float(flight_time)))
 
     def get_refs(self):
-        """The reference set the handle currently holds, read back from the device: dict(zmp_x, zmp_y, phase, segs, seg_of_sample)."""
-        n, ns = capi.lib().lmh_num_ref_samples(self._h), capi.lib().lmh_num_segments(self._h)
-        zx, zy = np.zeros(n), np.zeros(n)
-        ph = np.zeros(n, dtype=np.uint8)
-        segs = np.zeros((ns, capi.SEG_STRIDE)); sos = np.zeros(n, dtype=np.uint16)
-        check(capi.lib().lmh_get_refs(self._h, _np_ptr(zx), _np_ptr(zy), _np_ptr(ph), _np_ptr(segs) if ns else None, _np_ptr(sos) if ns else None))
-        return dict(zmp_x=zx, zmp_y=zy, phase=ph, segs=segs, seg_of_sample=sos)
+        """The reference set the handle currently holds, read back from the device: dict(zmp_x, zmp_y, phase, segs, seg_of_sample).
+        With per-robot plans it is robot 0's (lmh_get_refs is lmh_get_plan of robot 0)."""
+        return self.get_plan(0)
 
     # -- one plan per robot (include/lmh.h, "Per-robot plans")
     def gen_walk_batch(self, simulation_time, specs):
@@ -325,25 +328,27 @@ class BatchedController:
         check(capi.lib().lmh_eval(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), self._stream()))
         return out, status
 
-    def rollout(self, state, n_ticks, out=None, status=None, log=False):
-        """n_ticks of rk4Step(dynamics) + Clock::step (apps/offline/main.cpp:66-122), fused on chip."""
+    def _rollout_buffers(self, n_ticks, out, status, log):
+        """out, status and log of a rollout: the caller's, or fresh ones (log=True: a zeroed [n_ticks,B,36]; False: none)."""
         out = self.new_out() if out is None else out
         status = self.new_status() if status is None else status
         lg = torch.zeros((n_ticks, self.B, 36), dtype=torch.float64, device=self.device) if log is True else (log if log is not False else None)
-        check(capi.lib().lmh_rollout(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status),
-                                     None if lg is None else _dev_ptr(lg), int(n_ticks), self._stream()))
+        return out, status, lg
+
+    def rollout(self, state, n_ticks, out=None, status=None, log=False):
+        """n_ticks of rk4Step(dynamics) + Clock::step (apps/offline/main.cpp:66-122), fused on chip."""
+        out, status, lg = self._rollout_buffers(n_ticks, out, status, log)
+        check(capi.lib().lmh_rollout(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), _dev_ptr(lg), int(n_ticks), self._stream()))
         return out, status, lg
 
     def rollout_trace(self, state, n_ticks, every, out=None, status=None, log=False, trace=None):
         """lmh_rollout_trace: rollout that also stores a sample [state(96) | out(80) | status(4, as doubles)] of every robot each time it
         has completed `every` more ticks of this launch -- what rollout(state, (j + 1) * every) would have left, bit for bit.
         trace: a [n_ticks // every, B, 180] float64 device tensor (or larger), allocated here when None.  -> (out, status, log, trace)."""
-        out = self.new_out() if out is None else out
-        status = self.new_status() if status is None else status
-        lg = torch.zeros((n_ticks, self.B, 36), dtype=torch.float64, device=self.device) if log is True else (log if log is not False else None)
+        out, status, lg = self._rollout_buffers(n_ticks, out, status, log)
         if trace is None:
             trace = torch.zeros((capi.lib().lmh_trace_samples(int(n_ticks), int(every)), self.B, capi.TRACE_STRIDE), dtype=torch.float64, device=self.device)
-        check(capi.lib().lmh_rollout_trace(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), None if lg is None else _dev_ptr(lg),
+        check(capi.lib().lmh_rollout_trace(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), _dev_ptr(lg),
                                            int(n_ticks), _dev_ptr(trace), int(every), self._stream()))
         return out, status, lg, trace
 
@@ -378,14 +383,19 @@ class BatchedController:
         return com
 
     # -- rigid-body terms, inverse and forward dynamics (include/lmh.h, lmh_terms): pure functions of the (q, v) given
-    def _batch(self, name, t, width, optional=False):
-        """A [B,width] float64 tensor on this controller's device, made contiguous; None passes when optional."""
+    def _batch(self, name, t, width, optional=False, in_place=False):
+        """A [B,width] float64 tensor on this controller's device, made contiguous; None passes when optional.  in_place: the call writes
+        into t itself, so it has to be contiguous as it comes."""
         if t is None:
             if optional:
                 return None
             raise ValueError(f"{name} is required")
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != (self.B, width) or t.device != self.device:
-            raise ValueError(f"{name} must be a [{self.B},{width}] float64 tensor on {self.device}")
+        what = f"[{self.B},{width}] float64 tensor on {self.device}"
+        if in_place:
+            what = f"contiguous {what} (it is updated in place)"
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != (self.B, width) or t.device != self.device \
+                or (in_place and not t.is_contiguous()):
+            raise ValueError(f"{name} must be a {what}")
         return t.contiguous()
 
     def terms(self, q, v=None):
@@ -394,7 +404,7 @@ class BatchedController:
         velocity-dependent term is taken at the v given."""
         q, v = self._batch("q", q, 30), self._batch("v", v, 30, optional=True)
         t = torch.empty((self.B, capi.TERMS_STRIDE), dtype=torch.float64, device=self.device)
-        check(capi.lib().lmh_terms(self._h, _dev_ptr(q), None if v is None else _dev_ptr(v), _dev_ptr(t), self._stream()))
+        check(capi.lib().lmh_terms(self._h, _dev_ptr(q), _dev_ptr(v), _dev_ptr(t), self._stream()))
         return t
 
     def inverse_dynamics(self, q, v, qdd, w=None):
@@ -403,8 +413,7 @@ class BatchedController:
         q, v = self._batch("q", q, 30), self._batch("v", v, 30, optional=True)
         qdd, w = self._batch("qdd", qdd, 30), self._batch("w", w, 12, optional=True)
         tau = torch.empty((self.B, 30), dtype=torch.float64, device=self.device)
-        check(capi.lib().lmh_inverse_dynamics(self._h, _dev_ptr(q), None if v is None else _dev_ptr(v), _dev_ptr(qdd),
-                                              None if w is None else _dev_ptr(w), _dev_ptr(tau), self._stream()))
+        check(capi.lib().lmh_inverse_dynamics(self._h, _dev_ptr(q), _dev_ptr(v), _dev_ptr(qdd), _dev_ptr(w), _dev_ptr(tau), self._stream()))
         return tau
 
     def forward_dynamics(self, q, v, tau, w=None):
@@ -413,16 +422,14 @@ class BatchedController:
         tau, w = self._batch("tau", tau, 30), self._batch("w", w, 12, optional=True)
         qdd = torch.empty((self.B, 30), dtype=torch.float64, device=self.device)
         flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
-        check(capi.lib().lmh_forward_dynamics(self._h, _dev_ptr(q), None if v is None else _dev_ptr(v), _dev_ptr(tau),
-                                              None if w is None else _dev_ptr(w), _dev_ptr(qdd), _dev_ptr(flags), self._stream()))
+        check(capi.lib().lmh_forward_dynamics(self._h, _dev_ptr(q), _dev_ptr(v), _dev_ptr(tau), _dev_ptr(w), _dev_ptr(qdd), _dev_ptr(flags), self._stream()))
         return qdd, flags
 
     @staticmethod
     def split_terms(t):
         """Named views of terms records [.., 1840] (tensor or array): M [..,30,30], C, Cg (first six), AG [..,6,30], AGpqp, J [..,12,30],
         Jpqp, CoM, comVel, angMom, mass [..], T [..,28,3,4] -- capi.TERMS_FIELDS."""
-        lead = tuple(t.shape[:-1])
-        return {k: t[..., o:o + int(np.prod(s, dtype=np.int64))].reshape(lead + tuple(s)) for k, (o, s) in capi.TERMS_FIELDS.items()}
+        return _split(t, capi.TERMS_FIELDS)
 
     # -- torque-driven plant (include/lmh.h, lmh_contact_wrench): the compliant-contact plant under torques the caller supplies
     def contact_wrench(self, q, v=None):
@@ -430,7 +437,7 @@ class BatchedController:
         (split_contact names its fields): the spring-damper contact of lmh_config.plant with the robot's own contact constants."""
         q, v = self._batch("q", q, 30), self._batch("v", v, 30, optional=True)
         c = torch.empty((self.B, capi.CONTACT_STRIDE), dtype=torch.float64, device=self.device)
-        check(capi.lib().lmh_contact_wrench(self._h, _dev_ptr(q), None if v is None else _dev_ptr(v), _dev_ptr(c), self._stream()))
+        check(capi.lib().lmh_contact_wrench(self._h, _dev_ptr(q), _dev_ptr(v), _dev_ptr(c), self._stream()))
         return c
 
     def plant_derivative(self, q, v, tau=None):
@@ -441,29 +448,25 @@ class BatchedController:
         xdot = torch.empty((self.B, 60), dtype=torch.float64, device=self.device)
         c = torch.empty((self.B, capi.CONTACT_STRIDE), dtype=torch.float64, device=self.device)
         flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
-        check(capi.lib().lmh_plant_derivative(self._h, _dev_ptr(q), _dev_ptr(v), None if tau is None else _dev_ptr(tau), _dev_ptr(xdot), _dev_ptr(c),
+        check(capi.lib().lmh_plant_derivative(self._h, _dev_ptr(q), _dev_ptr(v), _dev_ptr(tau), _dev_ptr(xdot), _dev_ptr(c),
                                               _dev_ptr(flags), self._stream()))
         return xdot, c, flags
 
     def plant_step(self, state, tau=None, n_substeps=1):
         """n_substeps RK4 steps of cfg.dt on (q, v) of the state records [B,96], in place, with tau [B,30] held (None: passive); t advances,
         v_prev stays.  -> (state, flags [B] int32, OR-ed over the substeps)."""
-        tau = self._batch("tau", tau, 30, optional=True)
-        if not isinstance(state, torch.Tensor) or state.dtype != torch.float64 or tuple(state.shape) != (self.B, capi.STATE_STRIDE) \
-                or state.device != self.device or not state.is_contiguous():
-            raise ValueError(f"state must be a contiguous [{self.B},{capi.STATE_STRIDE}] float64 tensor on {self.device} (it is updated in place)")
+        tau, state = self._batch("tau", tau, 30, optional=True), self._batch("state", state, capi.STATE_STRIDE, in_place=True)
         if int(n_substeps) != n_substeps or n_substeps < 0:
             raise ValueError("n_substeps must be a whole number >= 0")
         flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
-        check(capi.lib().lmh_plant_step(self._h, _dev_ptr(state), None if tau is None else _dev_ptr(tau), int(n_substeps), _dev_ptr(flags), self._stream()))
+        check(capi.lib().lmh_plant_step(self._h, _dev_ptr(state), _dev_ptr(tau), int(n_substeps), _dev_ptr(flags), self._stream()))
         return state, flags
 
     @staticmethod
     def split_contact(c):
         """Named views of contact records [.., 40] (tensor or array): w [..,12] (n_R f_R n_L f_L), vertex_force [..,8,3], pad [..,4] --
         capi.CONTACT_FIELDS."""
-        lead = tuple(c.shape[:-1])
-        return {k: c[..., o:o + int(np.prod(s, dtype=np.int64))].reshape(lead + tuple(s)) for k, (o, s) in capi.CONTACT_FIELDS.items()}
+        return _split(c, capi.CONTACT_FIELDS)
 
     def make_summary(self, state, out, status):
         """End-of-run summary [B,16] (include/lmh.h lmh_make_summary): the record the RCCL gather moves."""
@@ -472,53 +475,50 @@ class BatchedController:
         return s
 
     @staticmethod
+    def _write_record(write, path, name, a, shape, *scalars):
+        """One writer for the three record files: a as a float64 array of the rank and record width of shape, e.g. ("ticks", "B", 36)."""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.ndim != len(shape) or a.shape[-1] != shape[-1]:
+            raise ValueError(f"{name} must be [{','.join(map(str, shape))}]")
+        check(write(str(path).encode(), _np_ptr(a), *a.shape[:-1], *map(float, scalars)))
+
+    @staticmethod
+    def _read_record(read, path, width, per_tick=True):
+        """One reader: the header alone (no buffer), then the payload -> (array, dt, t0).  A summary (per_tick=False) has no tick count, no t0."""
+        nt, n, dt, t0 = C.c_uint64(0), C.c_uint64(0), C.c_double(0.0), C.c_double(0.0)
+        header = (C.byref(nt), C.byref(n), C.byref(dt), C.byref(t0)) if per_tick else (C.byref(n), C.byref(dt))
+        check(read(str(path).encode(), None, 0, *header))
+        a = np.zeros((nt.value, n.value, width) if per_tick else (n.value, width), dtype=np.float64)
+        check(read(str(path).encode(), _np_ptr(a), a.size, *header))
+        return a, dt.value, t0.value
+
+    @staticmethod
     def write_summary(path, summary, dt=0.0):
         """lmh_write_summary: [n,16] host array -> 64-byte header + raw f64 file."""
-        a = np.ascontiguousarray(summary, dtype=np.float64)
-        if a.ndim != 2 or a.shape[1] != capi.SUMMARY_WIDTH:
-            raise ValueError("summary must be [n,16]")
-        check(capi.lib().lmh_write_summary(str(path).encode(), _np_ptr(a), a.shape[0], float(dt)))
+        BatchedController._write_record(capi.lib().lmh_write_summary, path, "summary", summary, ("n", capi.SUMMARY_WIDTH), dt)
 
     @staticmethod
     def read_summary(path):
-        n, dt = C.c_uint64(0), C.c_double(0.0)
-        check(capi.lib().lmh_read_summary(str(path).encode(), None, 0, C.byref(n), C.byref(dt)))      # header only
-        a = np.zeros((n.value, capi.SUMMARY_WIDTH), dtype=np.float64)
-        check(capi.lib().lmh_read_summary(str(path).encode(), _np_ptr(a), a.size, C.byref(n), C.byref(dt)))
-        return a, dt.value
+        return BatchedController._read_record(capi.lib().lmh_read_summary, path, capi.SUMMARY_WIDTH, per_tick=False)[:2]
 
     @staticmethod
     def write_log(path, log, dt, t0=0.0):
         """lmh_write_log: [n_ticks,B,36] host array (lmh_rollout's d_log copied back)."""
-        a = np.ascontiguousarray(log, dtype=np.float64)
-        if a.ndim != 3 or a.shape[2] != 36:
-            raise ValueError("log must be [ticks,B,36]")
-        check(capi.lib().lmh_write_log(str(path).encode(), _np_ptr(a), a.shape[0], a.shape[1], float(dt), float(t0)))
+        BatchedController._write_record(capi.lib().lmh_write_log, path, "log", log, ("ticks", "B", 36), dt, t0)
 
     @staticmethod
     def read_log(path):
-        nt, n, dt, t0 = C.c_uint64(0), C.c_uint64(0), C.c_double(0.0), C.c_double(0.0)
-        check(capi.lib().lmh_read_log(str(path).encode(), None, 0, C.byref(nt), C.byref(n), C.byref(dt), C.byref(t0)))
-        a = np.zeros((nt.value, n.value, 36), dtype=np.float64)
-        check(capi.lib().lmh_read_log(str(path).encode(), _np_ptr(a), a.size, C.byref(nt), C.byref(n), C.byref(dt), C.byref(t0)))
-        return a, dt.value, t0.value
+        return BatchedController._read_record(capi.lib().lmh_read_log, path, 36)
 
     @staticmethod
     def write_trace(path, trace, sample_dt, t0=0.0):
         """lmh_write_trace: [n_samples,B,180] host array (lmh_rollout_trace's d_trace copied back); sample_dt = every * dt, t0 = the
         clock of the first sample."""
-        a = np.ascontiguousarray(trace, dtype=np.float64)
-        if a.ndim != 3 or a.shape[2] != capi.TRACE_STRIDE:
-            raise ValueError("trace must be [samples,B,180]")
-        check(capi.lib().lmh_write_trace(str(path).encode(), _np_ptr(a), a.shape[0], a.shape[1], float(sample_dt), float(t0)))
+        BatchedController._write_record(capi.lib().lmh_write_trace, path, "trace", trace, ("samples", "B", capi.TRACE_STRIDE), sample_dt, t0)
 
     @staticmethod
     def read_trace(path):
-        ns, n, dt, t0 = C.c_uint64(0), C.c_uint64(0), C.c_double(0.0), C.c_double(0.0)
-        check(capi.lib().lmh_read_trace(str(path).encode(), None, 0, C.byref(ns), C.byref(n), C.byref(dt), C.byref(t0)))
-        a = np.zeros((ns.value, n.value, capi.TRACE_STRIDE), dtype=np.float64)
-        check(capi.lib().lmh_read_trace(str(path).encode(), _np_ptr(a), a.size, C.byref(ns), C.byref(n), C.byref(dt), C.byref(t0)))
-        return a, dt.value, t0.value
+        return BatchedController._read_record(capi.lib().lmh_read_trace, path, capi.TRACE_STRIDE)
 
     @staticmethod
     def split_out(out):
@@ -540,5 +540,4 @@ DEBUG_FIELDS = {
 
 def unpack_debug(dbg_row):
     """numpy views of one instance's debug record."""
-    d = np.asarray(dbg_row)
-    return {k: d[o:o + int(np.prod(s))].reshape(s) for k, (o, s) in DEBUG_FIELDS.items()}
+    return _split(np.asarray(dbg_row), DEBUG_FIELDS)

@@ -344,6 +344,17 @@ static int fill_params(lmh_handle *h)
     return LMH_OK;
 }
 
+// The one setter transaction.  swap() exchanges members of the handle with what the caller has just built aside, so the one statement is
+// both the change and its undo: if the block (or, with per-robot parameters, the block table) cannot be formed for the new members, the
+// second swap() puts the previous ones back and the call fails as a whole.  What ends up in the caller's locals dies with them.
+template <class Swap> static int commit(lmh_handle *h, Swap swap)
+{
+    swap();
+    const int rc = fill_params(h);
+    if (rc != LMH_OK) swap();
+    return rc;
+}
+
 static int upload_gain(lmh_handle *h, const double *zcom, int n)
 {
     const int stride = 3 * (h->N + 1) + 4;
@@ -353,31 +364,54 @@ static int upload_gain(lmh_handle *h, const double *zcom, int n)
             return fail(LMH_ERR_BAD_ARG, "MPC Hessian not positive definite");
     DevBuf<double> d;
     HIPCHK(d.upload(rows.data(), rows.size()));
-    std::swap(h->d_mpc, d); h->h_gain.swap(rows); std::swap(h->n_gain, n);
-    const int rc = fill_params(h);
-    if (rc != LMH_OK) { std::swap(h->d_mpc, d); h->h_gain.swap(rows); std::swap(h->n_gain, n); }   // back on the previous rows
-    return rc;
+    return commit(h, [&] { std::swap(h->d_mpc, d); h->h_gain.swap(rows); std::swap(h->n_gain, n); });
 }
 
-// every literal the kernels divide by or take a Cholesky pivot from must be positive (a zero weight is 1/0 in the
-// Woodbury set-up; the reference has no such check because its literals are compile-time constants)
+// ---------------------------------------------------------------------------- the rules of a configuration
+// the config's values in the record's order (LMH_PARAM_OFF_*)
+static void config_record(const lmh_config &c, double *r)
+{
+    const double v[LMH_PARAM_STRIDE] = {c.mu, c.kp_joints, c.kd_joints, c.kp_mom, c.kd_mom, c.kp_feet, c.kd_feet,
+                                        c.w_com_lin, c.w_com_ang, c.w_base_pos, c.w_base_ang, c.w_joints, c.w_force, c.w_foot, c.eps_coeff,
+                                        c.contact_k, c.contact_d, c.contact_dt, c.contact_mu, 0.0};
+    std::memcpy(r, v, sizeof(v));
+}
+
+// The rules of one parameter record, stated once: lmh_create applies them to its config's record, lmh_set_params to every robot's, the
+// plant calls the contact rule alone.  nullptr = fine.  Every literal the kernels divide by or take a Cholesky pivot from must be positive
+// (a zero weight is 1/0 in the Woodbury set-up; the reference has no such check because its literals are compile-time constants).
+static const char *contact_error(const double *r)
+{
+    if (!(r[LMH_PARAM_OFF_CONTACT_K] > 0.0) || !(r[LMH_PARAM_OFF_CONTACT_D] >= 0.0) || !(r[LMH_PARAM_OFF_CONTACT_DT] >= 0.0) || !(r[LMH_PARAM_OFF_CONTACT_MU] >= 0.0))
+        return "contact_k must be positive, contact_d / contact_dt / contact_mu non-negative";
+    return nullptr;
+}
+
+static const char *param_record_error(const double *r, bool plant)
+{
+    if (!(r[LMH_PARAM_OFF_MU] > 0.0)) return "mu must be positive";
+    if (!(r[LMH_PARAM_OFF_EPS_COEFF] > 0.0)) return "eps_coeff must be positive";
+    for (int o : {LMH_PARAM_OFF_W_COM_LIN, LMH_PARAM_OFF_W_BASE_POS, LMH_PARAM_OFF_W_BASE_ANG, LMH_PARAM_OFF_W_JOINTS, LMH_PARAM_OFF_W_FORCE, LMH_PARAM_OFF_W_FOOT})
+        if (!(r[o] > 0.0)) return "weights w_com_lin, w_base_pos, w_base_ang, w_joints, w_force, w_foot must be positive";
+    if (!(r[LMH_PARAM_OFF_W_COM_ANG] >= 0.0)) return "w_com_ang must be >= 0";
+    for (int o = LMH_PARAM_OFF_KP_JOINTS; o <= LMH_PARAM_OFF_KD_FEET; o++) if (!std::isfinite(r[o])) return "PD gains must be finite";
+    return plant ? contact_error(r) : nullptr;
+}
+
+// The fields that are not in the record, around the record's rules.  The order of the refusals is part of the interface: the contact
+// rule is asked after max_qp_iters and plant, as it always was, so the record is walked without it first.
 static const char *validate_config(const lmh_config *c)
 {
     if (!(c->dt > 0.0) || !(c->time_horizon > 0.0)) return "dt and time_horizon must be positive";
     if (!(c->mpc_dt >= 0.0) || !std::isfinite(c->mpc_dt)) return "mpc_dt must be >= 0 (0 = dt)";
     if (!(c->z_com > 0.0) || !(c->gravity > 0.0)) return "z_com and gravity must be positive";
     if (!(c->alpha > 0.0) || !(c->beta > 0.0)) return "alpha and beta must be positive";
-    if (!(c->mu > 0.0)) return "mu must be positive";
-    if (!(c->eps_coeff > 0.0)) return "eps_coeff must be positive";
-    if (!(c->w_com_lin > 0.0) || !(c->w_base_pos > 0.0) || !(c->w_base_ang > 0.0) || !(c->w_joints > 0.0) || !(c->w_force > 0.0) || !(c->w_foot > 0.0))
-        return "weights w_com_lin, w_base_pos, w_base_ang, w_joints, w_force, w_foot must be positive";
-    if (!(c->w_com_ang >= 0.0)) return "w_com_ang must be >= 0";
-    const double g[6] = {c->kp_joints, c->kd_joints, c->kp_mom, c->kd_mom, c->kp_feet, c->kd_feet};
-    for (double v : g) if (!std::isfinite(v)) return "PD gains must be finite";
+    double rec[LMH_PARAM_STRIDE];
+    config_record(*c, rec);
+    if (const char *why = param_record_error(rec, false)) return why;
     if (c->max_qp_iters < 1) return "max_qp_iters must be >= 1";
     if (c->plant != 0 && c->plant != 1) return "plant must be 0 or 1";
-    if (c->plant && (!(c->contact_k > 0.0) || !(c->contact_d >= 0.0) || !(c->contact_dt >= 0.0) || !(c->contact_mu >= 0.0)))
-        return "contact_k must be positive, contact_d / contact_dt / contact_mu non-negative";
+    if (const char *why = c->plant ? contact_error(rec) : nullptr) return why;
     if (c->precision != LMH_PRECISION_FP64 && c->precision != LMH_PRECISION_MIXED && c->precision != LMH_PRECISION_FP32)
         return "precision must be LMH_PRECISION_FP64, LMH_PRECISION_MIXED or LMH_PRECISION_FP32";
     return nullptr;
@@ -460,10 +494,7 @@ extern "C" int lmh_set_model(lmh_handle *h, const double *raw, int n_models)
     lmh_launch_model(d_raw.get(), d_model.get(), n_models, lcoef_of(h), nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipDeviceSynchronize());
-    std::swap(h->d_raw, d_raw); std::swap(h->d_model, d_model); std::swap(h->n_models, n_models);
-    const int rc = fill_params(h);
-    if (rc != LMH_OK) { std::swap(h->d_raw, d_raw); std::swap(h->d_model, d_model); std::swap(h->n_models, n_models); }   // back on the previous model
-    return rc;
+    return commit(h, [&] { std::swap(h->d_raw, d_raw); std::swap(h->d_model, d_model); std::swap(h->n_models, n_models); });
 }
 
 extern "C" int lmh_get_mass(lmh_handle *h, double *mass)
@@ -478,13 +509,8 @@ extern "C" int lmh_get_mass(lmh_handle *h, double *mass)
 // ---------------------------------------------------------------------------- the reference plan
 // Every setter validates its arguments on the host, builds a fresh RefPlan aside (allocation, upload or generator launch, sync) and
 // commits it here: the one place where a handle changes plan.  Whatever fails before that leaves the handle on its previous plan.
-static int commit_plan(lmh_handle *h, RefPlan p)
-{
-    std::swap(h->plan, p);
-    const int rc = fill_params(h);
-    if (rc != LMH_OK) std::swap(h->plan, p);                         // back on the previous plan; the new one dies with p
-    return rc;                                                       // else the previous plan dies with p, after P (and every robot's block) has left it
-}
+// The plan that loses dies with p: the new one after a failure, else the previous one, after P (and every robot's block) has left it.
+static int commit_plan(lmh_handle *h, RefPlan p) { return commit(h, [&] { std::swap(h->plan, p); }); }
 
 static std::string robot_msg(int i, const char *msg) { return "robot " + std::to_string(i) + ": " + msg; }
 
@@ -542,17 +568,18 @@ extern "C" int lmh_set_foot_coeffs(lmh_handle *h, const double *r, const int32_t
     if (!h || !r || !rn || !l || !ln) return fail(LMH_ERR_BAD_ARG, "bad argument");
     for (int a = 0; a < 3; a++)
         if (rn[a] < 1 || rn[a] > 8 || ln[a] < 1 || ln[a] > 8) return fail(LMH_ERR_BAD_ARG, "coefficient count must be 1..8");
-    const LmhDevParams prev = h->P;
+    double rF[3][8], lF[3][8];
+    int32_t rFn[3], lFn[3];
     for (int a = 0; a < 3; a++) {
-        h->P.rFn[a] = rn[a]; h->P.lFn[a] = ln[a];
+        rFn[a] = rn[a]; lFn[a] = ln[a];
         // entries beyond the count are stored as zeros: the kernels evaluate all eight terms (a zero coefficient adds an exact zero)
-        for (int k = 0; k < 8; k++) { h->P.rF[a][k] = (k < rn[a]) ? r[8 * a + k] : 0.0; h->P.lF[a][k] = (k < ln[a]) ? l[8 * a + k] : 0.0; }
+        for (int k = 0; k < 8; k++) { rF[a][k] = (k < rn[a]) ? r[8 * a + k] : 0.0; lF[a][k] = (k < ln[a]) ? l[8 * a + k] : 0.0; }
     }
-    if (!h->inst.on()) return LMH_OK;
+    LmhDevParams &P = h->P;                                          // the polynomials live in the block alone, and in every robot's copy of it
+    auto swap = [&] { std::swap(P.rF, rF); std::swap(P.lF, lF); std::swap(P.rFn, rFn); std::swap(P.lFn, lFn); };
+    if (!h->inst.on()) { swap(); return LMH_OK; }                    // no table to rewrite: no HIP call at all
     HIPCHK(hipSetDevice(h->device));
-    const int rc = fill_params(h);                                   // the polynomials live in every robot's block
-    if (rc != LMH_OK) h->P = prev;
-    return rc;
+    return commit(h, swap);
 }
 
 extern "C" int lmh_set_segments(lmh_handle *h, const double *segs, int n_seg, const uint16_t *sos, int n_samples)
@@ -606,10 +633,7 @@ extern "C" int lmh_set_pushes(lmh_handle *h, const double *records, int n_push, 
     HIPCHK(hipSetDevice(h->device));
     DevBuf<double> d;
     if (n_push > 0) HIPCHK(d.upload(records, (size_t)LMH_PUSH_STRIDE * n_push * n_sets));
-    std::swap(h->d_pushes, d); std::swap(h->n_push, n_push); std::swap(h->n_push_sets, n_sets);     // nothing above changed the handle
-    const int rc = fill_params(h);
-    if (rc != LMH_OK) { std::swap(h->d_pushes, d); std::swap(h->n_push, n_push); std::swap(h->n_push_sets, n_sets); }   // back on the previous schedule
-    return rc;
+    return commit(h, [&] { std::swap(h->d_pushes, d); std::swap(h->n_push, n_push); std::swap(h->n_push_sets, n_sets); });
 }
 
 extern "C" int lmh_num_pushes(const lmh_handle *h) { return h ? h->n_push : 0; }
@@ -634,10 +658,7 @@ extern "C" int lmh_set_xscale(lmh_handle *h, const double *xscale, int n)
     HIPCHK(hipSetDevice(h->device));
     DevBuf<double> d;
     if (xscale) HIPCHK(d.upload(xscale, (size_t)n));
-    std::swap(h->d_xscale, d);
-    const int rc = fill_params(h);
-    if (rc != LMH_OK) std::swap(h->d_xscale, d);
-    return rc;
+    return commit(h, [&] { std::swap(h->d_xscale, d); });
 }
 
 extern "C" int lmh_set_zcom(lmh_handle *h, const double *z, int n)
@@ -655,29 +676,6 @@ extern "C" int lmh_get_mpc_gain(lmh_handle *h, double *K)
 }
 
 // ---------------------------------------------------------------------------- per-robot controller parameters
-// the config's values in the record's order (LMH_PARAM_OFF_*)
-static void config_record(const lmh_config &c, double *r)
-{
-    const double v[LMH_PARAM_STRIDE] = {c.mu, c.kp_joints, c.kd_joints, c.kp_mom, c.kd_mom, c.kp_feet, c.kd_feet,
-                                        c.w_com_lin, c.w_com_ang, c.w_base_pos, c.w_base_ang, c.w_joints, c.w_force, c.w_foot, c.eps_coeff,
-                                        c.contact_k, c.contact_d, c.contact_dt, c.contact_mu, 0.0};
-    std::memcpy(r, v, sizeof(v));
-}
-
-// the rules validate_config applies to the same fields, in its words: nullptr = fine
-static const char *param_record_error(const double *r, bool plant)
-{
-    if (!(r[LMH_PARAM_OFF_MU] > 0.0)) return "mu must be positive";
-    if (!(r[LMH_PARAM_OFF_EPS_COEFF] > 0.0)) return "eps_coeff must be positive";
-    for (int o : {LMH_PARAM_OFF_W_COM_LIN, LMH_PARAM_OFF_W_BASE_POS, LMH_PARAM_OFF_W_BASE_ANG, LMH_PARAM_OFF_W_JOINTS, LMH_PARAM_OFF_W_FORCE, LMH_PARAM_OFF_W_FOOT})
-        if (!(r[o] > 0.0)) return "weights w_com_lin, w_base_pos, w_base_ang, w_joints, w_force, w_foot must be positive";
-    if (!(r[LMH_PARAM_OFF_W_COM_ANG] >= 0.0)) return "w_com_ang must be >= 0";
-    for (int o = LMH_PARAM_OFF_KP_JOINTS; o <= LMH_PARAM_OFF_KD_FEET; o++) if (!std::isfinite(r[o])) return "PD gains must be finite";
-    if (plant && (!(r[LMH_PARAM_OFF_CONTACT_K] > 0.0) || !(r[LMH_PARAM_OFF_CONTACT_D] >= 0.0) || !(r[LMH_PARAM_OFF_CONTACT_DT] >= 0.0) || !(r[LMH_PARAM_OFF_CONTACT_MU] >= 0.0)))
-        return "contact_k must be positive, contact_d / contact_dt / contact_mu non-negative";
-    return nullptr;
-}
-
 extern "C" int lmh_set_params(lmh_handle *h, const double *records, int n)
 {
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
@@ -726,14 +724,22 @@ static int ready(lmh_handle *h)
     return LMH_OK;
 }
 
-static int eval_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_debug, bool debug, void *stream)
+// The one launch path of the asynchronous entry points: the handle is ready, the entry point's own argument check did not fire
+// (refusal: its message, nullptr = fine), then the device, the launch and the launch's error.  Nothing is enqueued by a refused call.
+template <class Launch> static int launch(lmh_handle *h, const char *refusal, Launch go)
 {
-    int rc = ready(h); if (rc) return rc;
-    if (!d_state || !d_out || !d_status || (debug && !d_debug)) return fail(LMH_ERR_BAD_ARG, "null device pointer");
+    const int rc = ready(h); if (rc) return rc;
+    if (refusal) return fail(LMH_ERR_BAD_ARG, refusal);
     HIPCHK(hipSetDevice(h->device));
-    lmh_launch_eval(&h->P, d_state, d_out, d_status, d_debug, (hipStream_t)stream);
+    go();
     HIPCHK(hipGetLastError());
     return LMH_OK;
+}
+
+static int eval_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_debug, bool debug, void *stream)
+{
+    return launch(h, (!d_state || !d_out || !d_status || (debug && !d_debug)) ? "null device pointer" : nullptr,
+                  [&] { lmh_launch_eval(&h->P, d_state, d_out, d_status, d_debug, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_eval(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, void *stream)
@@ -803,16 +809,13 @@ extern "C" int lmh_rollout(lmh_handle *h, double *d_state, double *d_out, int32_
 
 extern "C" int lmh_ik(lmh_handle *h, double *d_q, const double *com_target, const double *rf6, const double *lf6, int32_t *d_iters, void *stream)
 {
-    int rc = ready(h); if (rc) return rc;
-    if (!d_q || !com_target || !rf6 || !lf6) return fail(LMH_ERR_BAD_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    LmhIkTarget tgt;                                                 // travels by value in the kernel arguments: no shared staging buffer, no sync
-    for (int k = 0; k < 6; k++) { tgt.v[k] = rf6[k]; tgt.v[6 + k] = lf6[k]; }
-    for (int k = 0; k < 3; k++) tgt.v[12 + k] = com_target[k];
-    tgt.v[15] = 0.0;
-    lmh_launch_ik(&h->P, d_q, &tgt, d_iters, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return LMH_OK;
+    return launch(h, (!d_q || !com_target || !rf6 || !lf6) ? "bad argument" : nullptr, [&] {
+        LmhIkTarget tgt;                                             // travels by value in the kernel arguments: no shared staging buffer, no sync
+        for (int k = 0; k < 6; k++) { tgt.v[k] = rf6[k]; tgt.v[6 + k] = lf6[k]; }
+        for (int k = 0; k < 3; k++) tgt.v[12 + k] = com_target[k];
+        tgt.v[15] = 0.0;
+        lmh_launch_ik(&h->P, d_q, &tgt, d_iters, (hipStream_t)stream);
+    });
 }
 
 extern "C" int lmh_eval_host(lmh_handle *h, const double *q, const double *dq, double t, double *tau, double *f, double *qdd, int32_t *status)
@@ -845,12 +848,7 @@ extern "C" int lmh_eval_host(lmh_handle *h, const double *q, const double *dq, d
 
 extern "C" int lmh_robot_com(lmh_handle *h, const double *d_q, double *d_com, void *stream)
 {
-    int rc = ready(h); if (rc) return rc;
-    if (!d_q || !d_com) return fail(LMH_ERR_BAD_ARG, "null device pointer");
-    HIPCHK(hipSetDevice(h->device));
-    lmh_launch_com(&h->P, d_q, d_com, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return LMH_OK;
+    return launch(h, (!d_q || !d_com) ? "null device pointer" : nullptr, [&] { lmh_launch_com(&h->P, d_q, d_com, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_robot_com_host(lmh_handle *h, const double *q, double *com)
@@ -869,12 +867,8 @@ extern "C" int lmh_robot_com_host(lmh_handle *h, const double *q, double *com)
 // mode: 0 terms, 1 inverse dynamics, 2 forward dynamics (lmh_kernels.hip, lmh_terms_kernel).  The kernels read h->P's model tables only.
 static int terms_body(lmh_handle *h, int mode, const double *d_q, const double *d_v, const double *d_x, const double *d_w, double *d_res, int32_t *d_flags, void *stream)
 {
-    int rc = ready(h); if (rc) return rc;
-    if (!d_q || !d_res || (mode != 0 && !d_x)) return fail(LMH_ERR_BAD_ARG, "null device pointer");
-    HIPCHK(hipSetDevice(h->device));
-    lmh_launch_terms(&h->P, mode, d_q, d_v, d_x, d_w, d_res, d_flags, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return LMH_OK;
+    return launch(h, (!d_q || !d_res || (mode != 0 && !d_x)) ? "null device pointer" : nullptr,
+                  [&] { lmh_launch_terms(&h->P, mode, d_q, d_v, d_x, d_w, d_res, d_flags, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_terms(lmh_handle *h, const double *d_q, const double *d_v, double *d_terms, void *stream)
@@ -893,31 +887,27 @@ extern "C" int lmh_forward_dynamics(lmh_handle *h, const double *d_q, const doub
 }
 
 // ---------------------------------------------------------------------------- torque-driven plant
-// A handle with plant = 0 never had its contact constants checked (validate_config, param_record_error): the plant calls check the host copy
+// A handle with plant = 0 never had its contact constants checked (validate_config, lmh_set_params): the plant calls check the host copy
 static int plant_constants_ok(const lmh_handle *h)
 {
-    const char *rule = "contact_k must be positive, contact_d / contact_dt / contact_mu non-negative";
-    auto bad = [](double k, double d, double dt, double mu) { return !(k > 0.0) || !(d >= 0.0) || !(dt >= 0.0) || !(mu >= 0.0); };
     if (!h->inst.on()) {
-        const lmh_config &c = h->cfg;
-        return bad(c.contact_k, c.contact_d, c.contact_dt, c.contact_mu) ? fail(LMH_ERR_BAD_ARG, rule) : LMH_OK;
+        double rec[LMH_PARAM_STRIDE];
+        config_record(h->cfg, rec);
+        const char *why = contact_error(rec);
+        return why ? fail(LMH_ERR_BAD_ARG, why) : LMH_OK;
     }
-    for (int i = 0; i < h->B; i++) {
-        const double *r = h->inst.h_rec.data() + (size_t)LMH_PARAM_STRIDE * i;
-        if (bad(r[LMH_PARAM_OFF_CONTACT_K], r[LMH_PARAM_OFF_CONTACT_D], r[LMH_PARAM_OFF_CONTACT_DT], r[LMH_PARAM_OFF_CONTACT_MU])) return fail(LMH_ERR_BAD_ARG, robot_msg(i, rule));
-    }
+    for (int i = 0; i < h->B; i++)
+        if (const char *why = contact_error(h->inst.h_rec.data() + (size_t)LMH_PARAM_STRIDE * i)) return fail(LMH_ERR_BAD_ARG, robot_msg(i, why));
     return LMH_OK;
 }
 
-// mode: 0 contact wrench, 1 derivative, 2 RK4 step (lmh_kernels.hip, lmh_plant_kernel).  The caller has checked its required pointers.
+// mode: 0 contact wrench, 1 derivative, 2 RK4 step (lmh_kernels.hip, lmh_plant_kernel).  The caller has found the handle ready and checked
+// its required pointers, which come before the constants in the order of the refusals.
 static int plant_body(lmh_handle *h, int mode, const double *d_q, const double *d_v, const double *d_tau30, double *d_state, double *d_xdot, double *d_contact, int32_t *d_flags,
                       int n_substeps, void *stream)
 {
-    int rc = plant_constants_ok(h); if (rc) return rc;
-    HIPCHK(hipSetDevice(h->device));
-    lmh_launch_plant(&h->P, mode, d_q, d_v, d_tau30, d_state, d_xdot, d_contact, d_flags, n_substeps, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return LMH_OK;
+    const int rc = plant_constants_ok(h); if (rc) return rc;
+    return launch(h, nullptr, [&] { lmh_launch_plant(&h->P, mode, d_q, d_v, d_tau30, d_state, d_xdot, d_contact, d_flags, n_substeps, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_contact_wrench(lmh_handle *h, const double *d_q, const double *d_v, double *d_contact, void *stream)
@@ -1007,10 +997,7 @@ extern "C" int lmh_synchronize(lmh_handle *h, void *stream)
 extern "C" int lmh_make_summary(lmh_handle *h, const double *d_state, const double *d_out, const int32_t *d_status, double *d_summary, void *stream)
 {
     if (!h || !d_state || !d_out || !d_status || !d_summary) return fail(LMH_ERR_BAD_ARG, "bad argument");
-    HIPCHK(hipSetDevice(h->device));
-    lmh_launch_summary(h->B, d_state, d_out, d_status, d_summary, (hipStream_t)stream);
-    HIPCHK(hipGetLastError());
-    return LMH_OK;
+    return launch(h, nullptr, [&] { lmh_launch_summary(h->B, d_state, d_out, d_status, d_summary, (hipStream_t)stream); });
 }
 
 namespace {
@@ -1038,9 +1025,10 @@ int write_rec(const char *path, const char *magic, const double *data, uint64_t 
     return LMH_OK;
 }
 
-int read_rec(const char *path, const char *magic, uint32_t width, double *data, uint64_t capacity, RecHeader *hd)
+// per_tick: a log or a trace, one record per robot and tick / sample; else a summary, one record per robot
+int read_rec(const char *path, const char *magic, uint32_t width, bool per_tick, double *data, uint64_t capacity, RecHeader *hd)
 {
-    if (!path || !hd) return fail(LMH_ERR_BAD_ARG, "bad argument");
+    if (!path) return fail(LMH_ERR_BAD_ARG, "bad argument");
     FILE *f = std::fopen(path, "rb");
     if (!f) return fail(LMH_ERR_BAD_ARG, std::string("cannot open ") + path);
     int rc = LMH_OK;
@@ -1048,7 +1036,6 @@ int read_rec(const char *path, const char *magic, uint32_t width, double *data, 
     else if (std::memcmp(hd->magic, magic, 8) != 0) rc = fail(LMH_ERR_BAD_ARG, "bad magic");
     else if (hd->version != 1 || hd->dtype != 1 || hd->width != width) rc = fail(LMH_ERR_BAD_ARG, "unsupported version / dtype / width");
     else {
-        const bool per_tick = std::memcmp(magic, kMagicSum, 8) != 0;       // a log or a trace: one record per robot and tick / sample
         const uint64_t count = hd->n_instances * width * (per_tick ? hd->n_ticks : 1);
         long pos = std::ftell(f);
         std::fseek(f, 0, SEEK_END);
@@ -1063,6 +1050,15 @@ int read_rec(const char *path, const char *magic, uint32_t width, double *data, 
     std::fclose(f);
     return rc;
 }
+
+// what a reader reports beside the payload: every out-pointer is optional
+void header_out(const RecHeader &hd, uint64_t *n_ticks, uint64_t *n_instances, double *dt, double *t0)
+{
+    if (n_ticks) *n_ticks = hd.n_ticks;
+    if (n_instances) *n_instances = hd.n_instances;
+    if (dt) *dt = hd.dt;
+    if (t0) *t0 = hd.t0;
+}
 }  // namespace
 
 extern "C" int lmh_write_summary(const char *path, const double *summary, uint64_t n_instances, double dt)
@@ -1072,11 +1068,9 @@ extern "C" int lmh_write_summary(const char *path, const double *summary, uint64
 extern "C" int lmh_read_summary(const char *path, double *summary, uint64_t capacity, uint64_t *n_instances, double *dt)
 {
     RecHeader hd;
-    const int rc = read_rec(path, kMagicSum, LMH_SUMMARY_WIDTH, summary, capacity, &hd);
-    if (rc != LMH_OK) return rc;
-    if (n_instances) *n_instances = hd.n_instances;
-    if (dt) *dt = hd.dt;
-    return LMH_OK;
+    const int rc = read_rec(path, kMagicSum, LMH_SUMMARY_WIDTH, false, summary, capacity, &hd);
+    if (rc == LMH_OK) header_out(hd, nullptr, n_instances, dt, nullptr);
+    return rc;
 }
 extern "C" int lmh_write_log(const char *path, const double *log, uint64_t n_ticks, uint64_t n_instances, double dt, double t0)
 {
@@ -1086,13 +1080,9 @@ extern "C" int lmh_write_log(const char *path, const double *log, uint64_t n_tic
 extern "C" int lmh_read_log(const char *path, double *log, uint64_t capacity, uint64_t *n_ticks, uint64_t *n_instances, double *dt, double *t0)
 {
     RecHeader hd;
-    const int rc = read_rec(path, kMagicLog, 36, log, capacity, &hd);
-    if (rc != LMH_OK) return rc;
-    if (n_ticks) *n_ticks = hd.n_ticks;
-    if (n_instances) *n_instances = hd.n_instances;
-    if (dt) *dt = hd.dt;
-    if (t0) *t0 = hd.t0;
-    return LMH_OK;
+    const int rc = read_rec(path, kMagicLog, 36, true, log, capacity, &hd);
+    if (rc == LMH_OK) header_out(hd, n_ticks, n_instances, dt, t0);
+    return rc;
 }
 extern "C" int lmh_write_trace(const char *path, const double *trace, uint64_t n_samples, uint64_t n_instances, double sample_dt, double t0)
 {
@@ -1102,13 +1092,9 @@ extern "C" int lmh_write_trace(const char *path, const double *trace, uint64_t n
 extern "C" int lmh_read_trace(const char *path, double *trace, uint64_t capacity, uint64_t *n_samples, uint64_t *n_instances, double *sample_dt, double *t0)
 {
     RecHeader hd;
-    const int rc = read_rec(path, kMagicTrace, LMH_TRACE_STRIDE, trace, capacity, &hd);
-    if (rc != LMH_OK) return rc;
-    if (n_samples) *n_samples = hd.n_ticks;
-    if (n_instances) *n_instances = hd.n_instances;
-    if (sample_dt) *sample_dt = hd.dt;
-    if (t0) *t0 = hd.t0;
-    return LMH_OK;
+    const int rc = read_rec(path, kMagicTrace, LMH_TRACE_STRIDE, true, trace, capacity, &hd);
+    if (rc == LMH_OK) header_out(hd, n_samples, n_instances, sample_dt, t0);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------- reference generators on the device

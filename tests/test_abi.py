@@ -22,6 +22,43 @@ def test_header_symbols_exported(hip_lib):
     assert sorted(capi.EXPORTS) == names
 
 
+def declared_prototypes():
+    """name -> (return type, [parameter, ..]) of every prototype in include/lmh.h, comments stripped; (void) is no parameter."""
+    src = open(os.path.join(ROOT, "include", "lmh.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    protos = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][A-Za-z0-9_ ]*?[ *]+)(lmh_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        params = [p.strip() for p in params.split(",")]              # no parameter of this header has a comma or a parenthesis of its own
+        protos[name] = (" ".join(ret.split()), [] if params == ["void"] else params)
+    return protos
+
+
+def test_binding_table_agrees_with_the_header():
+    """capi.PROTOTYPES against include/lmh.h: the same number of arguments for every entry point, and position by position a pointer
+    where the header has one, c_double for double, c_int for int / int32_t, c_uint64 for uint64_t.  A wrong arity in the table would
+    corrupt a call silently."""
+    from linearmpchumanoid_amd import capi
+    protos = declared_prototypes()
+    assert sorted(protos) == declared_symbols() == sorted(capi.PROTOTYPES) == sorted(capi.EXPORTS)
+    scalar = {"double": C.c_double, "int": C.c_int, "int32_t": C.c_int, "uint64_t": C.c_uint64}
+    returns = {"void": None, "int": C.c_int, "const char *": C.c_char_p}
+
+    def is_pointer(t):
+        return t in (C.c_void_p, C.c_char_p) or (isinstance(t, type) and issubclass(t, C._Pointer))
+
+    for name, (ret, params) in protos.items():
+        restype, argtypes = capi.PROTOTYPES[name]
+        assert restype is returns[ret], f"{name}: returns {ret}"
+        assert len(argtypes) == len(params), f"{name}: {len(params)} parameters in the header, {len(argtypes)} in the table"
+        for i, (c_param, t) in enumerate(zip(params, argtypes)):
+            if "*" in c_param:
+                assert is_pointer(t), f"{name}, argument {i}: '{c_param}' is a pointer"
+            else:
+                c_type = " ".join(c_param.replace("const ", "").split()[:-1])
+                assert t is scalar[c_type], f"{name}, argument {i}: '{c_param}' is a {c_type}"
+    assert C.sizeof(C.c_int) == 4                                    # int32_t parameters travel as c_int
+
+
 def test_no_torch_types_in_abi():
     src = open(os.path.join(ROOT, "include", "lmh.h")).read()
     assert "torch" not in src and "at::" not in src and "std::" not in src
