@@ -431,6 +431,34 @@ int lmh_plant_derivative(lmh_handle *h, const double *d_q, const double *d_v, co
  * followed by lmh_plant_step(b) bit for bit.  d_flags[i] (may be NULL): the flags of lmh_plant_derivative, OR-ed over the substeps. */
 int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_tau30, int n_substeps, int32_t *d_flags, void *stream);
 
+/* ---- Zero-order-hold closed loop (build-defined; what apps/mujoco/main.cpp:115-122 intended before its feedback path was commented out):
+ * the controller at its own rate, the torque-driven plant at a finer step with the torques held, n_ticks control ticks in ONE launch with
+ * every robot on chip from the first tick to the last.
+ * DEFINITION.  For every robot the call leaves exactly what this host loop leaves, bit for bit:
+ *     repeat n_ticks times:
+ *         lmh_eval(h, d_state, d_out, d_status, s)                  reads t = state[90], stores v_prev <- v
+ *         tau30 = [ base_wrench[i] (6) | out.tau (24) ]
+ *         lmh_plant_step(h, d_state, tau30, n_substeps, d_flags, s)
+ * d_state: the state after the last hold (v_prev = the v the last evaluation saw; pads untouched).  d_out: the out record of the last
+ * evaluation.  d_status: [0] k and [3] the active mask of the last evaluation, [1] the maximum of the QP rounds over all ticks of the call,
+ * [2] the OR of the controller's flags and of lmh_plant_step's flags over all ticks.  d_log (DEVICE [n_ticks][B][36], may be NULL): tau | f of
+ * every tick's evaluation, as in lmh_rollout.  d_base_wrench (DEVICE [B][6], may be NULL = zero): rows 0..5 of lmh_plant_step's tau30, an
+ * external wrench on the base ([angular | linear], base frame), held for the whole launch -- this is how a disturbance enters this loop.
+ * d_state, d_out and d_status have lmh_eval's layout and meaning.
+ * Consequence: lmh_rollout_zoh(a + b) equals (a) followed by (b) bit for bit, with [1] and [2] merged as max / OR; with warm_start = 1 too,
+ * because d_status[.][3] carries the mask across the split.
+ * The control period is n_substeps * lmh_config.dt; mpc_dt keeps its meaning.  Per-robot models, plans, xscale, z_com and lmh_set_params
+ * records are honoured as the two composed calls honour them.  The velocity pushes of lmh_set_pushes are NOT applied (as in lmh_eval).
+ * This is not lmh_rollout with plant = 1, which evaluates the controller at all four RK4 stages of every step (the reference's loop); on a
+ * plant = 1 handle the evaluation here is whatever lmh_eval does there.
+ * n_ticks < 0 or n_substeps < 0, or NULL for d_state / d_out / d_status, return LMH_ERR_BAD_ARG before anything is enqueued; n_ticks = 0
+ * enqueues nothing; n_substeps = 0 is legal (n_ticks evaluations of a state that does not move).  The contact constants are checked as
+ * lmh_plant_step checks them, on a plant = 0 handle too ("robot 7: ...").  LMH_PRECISION_FP64 handles only: another precision is refused
+ * with LMH_ERR_BAD_ARG.  Asynchronous on `stream`; the parameter block travels in the kernel arguments (no launch slot, no work queue), so
+ * the call can be captured into a hipGraph from the first call on and writes nothing into the handle. */
+int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
+                    int n_ticks, int n_substeps, void *stream);
+
 /* host-buffer convenience used by the C++ shim (B instances, staged through internal
  * device buffers, synchronous): q/dq [B][30], t, outputs tau[B][24], f[B][12], qdd[B][30] */
 int lmh_eval_host(lmh_handle *h, const double *q, const double *dq, double t,

@@ -125,6 +125,7 @@ PROTOTYPES = {
     "lmh_contact_wrench": (_ip, [_vp, _vp, _vp, _vp, _vp]),
     "lmh_plant_derivative": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lmh_plant_step": (_ip, [_vp, _vp, _vp, _ip, _vp, _vp]),
+    "lmh_rollout_zoh": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _vp]),
     "lmh_eval_host": (_ip, [_vp, _vp, _vp, _dp, _vp, _vp, _vp, _vp]),
     "lmh_robot_com_host": (_ip, [_vp, _vp, _vp]),
     "lmh_last_out_host": (_ip, [_vp, _vp]),

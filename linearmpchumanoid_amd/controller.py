@@ -462,6 +462,21 @@ class BatchedController:
         check(capi.lib().lmh_plant_step(self._h, _dev_ptr(state), _dev_ptr(tau), int(n_substeps), _dev_ptr(flags), self._stream()))
         return state, flags
 
+    def rollout_zoh(self, state, n_ticks, n_substeps, base_wrench=None, log=False, out=None, status=None):
+        """lmh_rollout_zoh: n_ticks rounds of { stand_step ; plant_step([base_wrench | out.tau], n_substeps) } in one launch, bit for bit
+        what that loop leaves; state [B,96] is updated in place.  The control period is n_substeps * cfg.dt.  base_wrench [B,6]: an external
+        wrench on the base held for the launch ([angular | linear], base frame; None: zero).  status (given or fresh): [:, 3] is the active
+        mask a warm-started handle continues from; afterwards [:, 1] is the maximum of the QP rounds and [:, 2] the OR of the controller's
+        and the plant's flags over all ticks.  -> (out, status), plus the log [n_ticks,B,36] (tau | f of every tick) when log is asked for."""
+        state, bw = self._batch("state", state, capi.STATE_STRIDE, in_place=True), self._batch("base_wrench", base_wrench, 6, optional=True)
+        for name, n in (("n_ticks", n_ticks), ("n_substeps", n_substeps)):
+            if int(n) != n or n < 0:
+                raise ValueError(f"{name} must be a whole number >= 0")
+        out, status, lg = self._rollout_buffers(int(n_ticks), out, status, log)
+        check(capi.lib().lmh_rollout_zoh(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), _dev_ptr(bw), _dev_ptr(lg),
+                                         int(n_ticks), int(n_substeps), self._stream()))
+        return (out, status) if lg is None else (out, status, lg)
+
     @staticmethod
     def split_contact(c):
         """Named views of contact records [.., 40] (tensor or array): w [..,12] (n_R f_R n_L f_L), vertex_force [..,8,3], pad [..,4] --

@@ -25,6 +25,10 @@ extern "C" void lmh_launch_gen_jump_batch(int n, double time_step, const LmhJump
 extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *q, const double *v, const double *x, const double *w, double *res, int32_t *flags, hipStream_t s);
 extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact, int32_t *flags,
                                  int n_substeps, hipStream_t s);
+// (a weak reference: a program that links this file without lmh_kernels.hip and without a stub of this launcher still links, and the entry
+// point refuses loudly there)
+extern "C" __attribute__((weak)) void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, int n_ticks, int n_substeps,
+                                       hipStream_t s);
 extern "C" void lmh_launch_params_expand(const LmhDevParams *P, const double *d_rec, const double *d_gcol_tab, LmhDevParams *d_blocks, int n, hipStream_t s);
 extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
 
@@ -931,6 +935,23 @@ extern "C" int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_ta
     if (n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step: n_substeps must be >= 0");
     if (n_substeps == 0) return plant_constants_ok(h);               // nothing to enqueue
     return plant_body(h, 2, nullptr, nullptr, d_tau30, d_state, nullptr, nullptr, d_flags, n_substeps, stream);
+}
+
+// ---------------------------------------------------------------------------- zero-order-hold closed loop
+// n_ticks rounds of { lmh_eval ; lmh_plant_step(tau30 = [base_wrench | out.tau], n_substeps) } in one launch (lmh_kernels.hip,
+// lmh_rollout_zoh_kernel).  Refusals in the order of the two calls it composes: the handle, the pointers, the counts, then the precision and the
+// contact constants; the parameter block travels by value, so the call takes no launch slot.
+extern "C" int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
+                               int n_ticks, int n_substeps, void *stream)
+{
+    int rc = ready(h); if (rc) return rc;
+    if (!d_state || !d_out || !d_status) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: null device pointer");
+    if (n_ticks < 0 || n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: n_ticks and n_substeps must be >= 0");
+    if (h->cfg.precision != LMH_PRECISION_FP64) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: LMH_PRECISION_FP64 handles only (this handle's precision has no instantiation of the kernel)");
+    rc = plant_constants_ok(h); if (rc) return rc;
+    if (!lmh_launch_rollout_zoh) return fail(LMH_ERR_NOT_READY, "lmh_rollout_zoh: this program was linked without the kernel's launcher");
+    if (n_ticks == 0) return LMH_OK;                                 // nothing to enqueue
+    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, n_ticks, n_substeps, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_terms_host(lmh_handle *h, const double *q, const double *v, double *terms)

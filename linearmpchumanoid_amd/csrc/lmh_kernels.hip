@@ -4566,6 +4566,112 @@ extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *
     else hipLaunchKernelGGL(lmh_plant_kernel<PM_STEP>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps);
 }
 
+// ============================================================================ zero-order-hold closed loop: controller and plant rates in one launch
+// lmh_rollout_zoh (include/lmh.h): for every robot exactly what n_ticks rounds of { lmh_eval ; lmh_plant_step(tau30 = [base_wrench | out.tau],
+// n_substeps) } leave, bit for bit, with the robot on chip for the whole launch.  One workgroup per robot, the two-wave schedule of
+// lmh_eval_kernel for the evaluation; the hold is lmh_plant_kernel<PM_STEP>'s loop on wave 0 (wave-scope fences only) while the helper wave
+// waits at the join that ends the tick, so both waves pass the same number of workgroup barriers.
+// What the separate launches did between two evaluations, and what happens to it here:
+//   v_prev      lmh_eval stores v_prev <- v and lmh_plant_step leaves it alone, but plant_derivative overwrites L[P_VP] with the velocity of
+//               its stage: the v the evaluation saw rides in a register across the hold and goes back to L[P_VP] behind it.
+//   state       wave 0's lanes 0..59 hold q | v during the hold (as lmh_plant_kernel), L[P_Q..] holds it across the evaluation, which writes
+//               neither.  The fourth stage's xs is fma(0, xdot, x), not x, when xdot is not finite: x itself is written back.
+//   clock       t += dt once per substep on both waves (wave-uniform, the same fp64 sum as the state record's t through the launches).
+//   warm start  F stays in wave 0's register (the launches carry ~F through status[3]); L[P_KF] is what phase_qp published, which is F.
+//   LDS words   per-launch tables (P_MODEL, P_GCOL.., P_MPCK, P_PRE + 2..3, P_RXS): read-only after load_common, the hold writes none.
+//               Reference cache (P_RK, P_RPH, P_RT0, P_PRE + 0..1, P_POLY): the hold reads and writes none of it and every entry is a pure
+//               function of the preview index k, so a hit returns the bits a fresh launch would form again: it survives.
+//               K_f^-1 cache (P_KI, P_KF + 1..2): P_KI is outside the scratch the hold uses (kinv_compute's own scratch, A_XR, is not:
+//               it is recomputed whenever it is needed) and the stored inverse is a pure function of the free set and the robot's friction
+//               table: it survives.  P_ORI is read by the rollout kernel's pipelined evaluation only: cleared once.
+//               Everything else an evaluation reads it has written itself (lmh_eval_kernel starts from an LDS image nobody initialised).
+__global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) lmh_rollout_zoh_kernel(LmhDevParams P_arg, double *state, double *out, int32_t *status, const double *base_wrench, double *log,
+                                                                               int n_ticks, int n_substeps)
+{
+    LmhCParams &P0 = LMH_KERNARG_PARAMS();
+    __shared__ double L[LDS_DOUBLES];
+    const int inst = blockIdx.x;
+    if (inst >= P0.n_instances) return;
+    LmhCParams &P = *params_of_robot(&P0, inst);
+    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    double *st = state + (size_t)LMH_STATE_STRIDE * inst;
+    double t = st[90];
+    unsigned F = 0xFFFFFFFFu;
+    SET_GDBG(nullptr);
+#ifdef LMH_SUBSTAMPS
+    if (threadIdx.x == 0) g_L = L;
+    __syncthreads();
+#endif
+    LMH_POISON_LDS(L, LDS_DOUBLES);
+    double bw = 0.0;                                               // lane i < 6: the wrench on the base, held for the launch
+    if (wid == 0) {
+        load_common(L, P, inst);
+        for (int e = LANE; e < 91; e += 64) L[P_Q + e] = st[e];    // q | v | v_prev | t
+        F = (unsigned)status[LMH_STATUS_STRIDE * inst + 3];
+        F = P.warm_start ? ~F : 0xFFFFFFFFu;
+        if (LANE == 0) { L[P_KF] = (double)F; L[P_KF + 2] = 0.0; L[P_ORI] = 0.0; }
+        if (base_wrench && LANE < 6) bw = base_wrench[6 * (size_t)inst + LANE];
+        WSYNC();
+    }
+    bsync<2>();
+    if (wid == 0) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);               // see lmh_rollout_kernel
+    const double dt = P.dt;
+    int k = 0, itmax = 0, flags = 0;
+#pragma unroll 1
+    for (int tick = 0; tick < n_ticks; tick++) {
+        int iters = 0;
+        flags |= controller_eval<2, double, false>(L, P, inst, t, wid, &F, &k, &iters, nullptr);
+        itmax = (iters > itmax) ? iters : itmax;
+        bsync<2>();                                                // torques of the helper wave
+        if (wid == 0) {
+            const int lane = LANE;
+            // the record of the launch's last evaluation leaves before the hold overwrites the accelerations and the CoM
+            if (tick == n_ticks - 1) store_out(L, out + (size_t)LMH_OUT_STRIDE * inst);
+            if (log) {
+                double *lg = log + ((size_t)tick * P0.n_instances + inst) * 36;
+                if (lane < 24) lg[lane] = L[P_TAU + lane]; else if (lane < 36) lg[lane] = L[P_W12 + lane - 24];
+            }
+            double x = L[P_Q + ((lane < 60) ? lane : 0)];          // q | v are one run
+            const double vp = L[P_V + ((lane < 30) ? lane : 0)];   // Robot::v_ <- dq (controller.cpp:59): what the next evaluation sees
+            const double tau = (lane < 6) ? bw : L[P_TAU + ((lane >= 6 && lane < 30) ? lane - 6 : 0)];         // lane i < 30: tau30[i] = [base wrench | out.tau]
+            const IbPack ibp = ib_pack();
+#pragma unroll 1
+            for (int sub = 0; sub < n_substeps; sub++) {           // lmh_plant_kernel<PM_STEP>
+                double ksum = 0.0, xs = x;
+#pragma unroll 1
+                for (int stage = 0; stage < 4; stage++) {
+                    WSYNC();
+                    if (lane < 60) L[P_Q + lane] = xs;
+                    WSYNC();
+                    flags |= plant_derivative(L, P, ibp, lane, tau);
+                    rk4_stage<0>(L, stage, lane, dt, P_SC + 52, x, ksum, xs);
+                }
+                if (__ballot(lane < 60 && !(fabs(x) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
+            }
+            WSYNC();
+            if (lane < 60) L[P_Q + lane] = x;
+            if (lane < 30) L[P_VP + lane] = vp;
+            WSYNC();
+        }
+#pragma unroll 1
+        for (int sub = 0; sub < n_substeps; sub++) t += dt;        // Clock::step, Clock.hpp:11
+        bsync<2>();                                                // the helper wave starts the next evaluation's references on the new state
+    }
+    if (wid == 0) {
+        for (int e = LANE; e < 90; e += 64) st[e] = L[P_Q + e];    // q | v | v_prev
+        if (LANE == 0) {
+            st[90] = t;
+            int32_t *s = status + LMH_STATUS_STRIDE * inst;
+            s[0] = k; s[1] = itmax; s[2] = flags; s[3] = (int32_t)(~F);
+        }
+    }
+}
+extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, int n_ticks, int n_substeps,
+                                       hipStream_t s)
+{
+    hipLaunchKernelGGL(lmh_rollout_zoh_kernel, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, state, out, status, base_wrench, log, n_ticks, n_substeps);
+}
+
 #endif
 // ============================================================================ reference generators on the device
 // The reference declares a walking generator (ZMP(Task, numSteps, timePerStep, simulationTime) / walkZMP, zmpGeneration.hpp:15-22) but never
