@@ -3477,6 +3477,17 @@ __device__ __forceinline__ void load_common(double *L, LmhCParams &P, int inst)
     }
     WSYNC();
 }
+// The single-wave kernels' input: the caller's (q, v) of the robot -> L[P_Q], L[P_V]; v == nullptr stands for zero.  `with_vp`: the stale-velocity
+// slot (Robot::v_, P_VP) takes the same v, so that every velocity product is taken at that one velocity.  The caller fences.
+__device__ __forceinline__ void load_qv(double *L, const double *q, const double *v, int inst, int lane, bool with_vp)
+{
+    if (lane < 30) {
+        const double vv = v ? v[30 * (size_t)inst + lane] : 0.0;
+        L[P_Q + lane] = q[30 * (size_t)inst + lane];
+        L[P_V + lane] = vv;
+        if (with_vp) L[P_VP + lane] = vv;
+    }
+}
 
 __device__ __forceinline__ void store_out(const double *L, double *out, bool keep_qdd_slots = false)
 {
@@ -3486,6 +3497,38 @@ __device__ __forceinline__ void store_out(const double *L, double *out, bool kee
     if (!keep_qdd_slots) for (int e = lane; e < 30; e += 64) out[36 + e] = L[P_QDD + e];   // (the diagnostic rollout keeps its counters there)
     if (lane >= 32 && lane < 38) out[66 + lane - 32] = L[P_COM + lane - 32];        // CoM | comVel (Robot::getCoM / getComVel)
     if (lane >= 40 && lane < 46) out[72 + lane - 40] = L[P_MPC + 2 + lane - 40];    // Mpc3dLip::getXRef | getYRef
+}
+
+// What a launch of the NW-wave evaluation schedule does before its first controller_eval (lmh_eval_kernel, lmh_rollout_zoh_kernel): wave 0
+// brings the per-launch tables and the robot's state record q | v | v_prev | t into the image `L`, the waves join, and wave 0 takes the
+// priority (see lmh_rollout_kernel).  Returns the free-set guess F: the complement of the ACTIVE mask the last launch left in status[3], or all
+// ones without warm start (valid on wave 0; the helper wave's copy is never read).
+template <int NW>
+__device__ __forceinline__ unsigned eval_begin(double *L, LmhCParams &P, int inst, const double *st, const int32_t *status, int wid)
+{
+    unsigned F = 0xFFFFFFFFu;
+#ifdef LMH_SUBSTAMPS
+    if (threadIdx.x == 0) g_L = L;                                 // bsync's wait counters (unused here, but the pointer must be valid)
+    __syncthreads();
+#endif
+    LMH_POISON_LDS(L, LDS_DOUBLES);
+    if (wid == 0) {
+        load_common(L, P, inst);
+        for (int e = LANE; e < 91; e += 64) L[P_Q + e] = st[e];    // q | v | v_prev | t
+        F = (unsigned)status[LMH_STATUS_STRIDE * inst + 3];
+        F = P.warm_start ? ~F : 0xFFFFFFFFu;                       // status keeps the ACTIVE mask
+        if (LANE == 0) { L[P_KF] = (double)F; L[P_KF + 2] = 0.0; L[P_ORI] = 0.0; }             // no K_f^-1 stored yet, no orientation term formed ahead
+        WSYNC();
+    }
+    bsync<NW>();
+    if constexpr (NW == 2) { if (wid == 0) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0); }
+    return F;
+}
+// the robot's status record (include/lmh.h): preview index | QP rounds | flags | ACTIVE mask (what eval_begin turns back into F); one lane calls it
+__device__ __forceinline__ void store_status(int32_t *status, int inst, int k, int iters, int flags, unsigned F)
+{
+    int32_t *s = status + LMH_STATUS_STRIDE * inst;
+    s[0] = k; s[1] = iters; s[2] = flags; s[3] = (int32_t)(~F);
 }
 
 // ============================================================================ kernels
@@ -3503,33 +3546,15 @@ __global__ void __launch_bounds__(64 * NW) lmh_eval_kernel(LmhDevParams P_arg, d
     const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     double *st = state + (size_t)LMH_STATE_STRIDE * inst;
     const double t = st[90];
-    unsigned F = 0xFFFFFFFFu;
     SET_GDBG(DEBUG ? debug + (size_t)LMH_DEBUG_STRIDE * inst : nullptr);
-#ifdef LMH_SUBSTAMPS
-    if (threadIdx.x == 0) g_L = L;                                 // bsync's wait counters (unused here, but the pointer must be valid)
-    __syncthreads();
-#endif
-    LMH_POISON_LDS(L, LDS_DOUBLES);
-    if (wid == 0) {
-        load_common(L, P, inst);
-        for (int e = LANE; e < 91; e += 64) L[P_Q + e] = st[e];    // q | v | v_prev | t
-        F = (unsigned)status[LMH_STATUS_STRIDE * inst + 3];
-        F = P.warm_start ? ~F : 0xFFFFFFFFu;                       // status keeps the ACTIVE mask
-        if (LANE == 0) { L[P_KF] = (double)F; L[P_KF + 2] = 0.0; L[P_ORI] = 0.0; }             // no K_f^-1 stored yet, no orientation term formed ahead
-        WSYNC();
-    }
-    bsync<NW>();
-    if constexpr (NW == 2) { if (wid == 0) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0); }   // see lmh_rollout_kernel
+    unsigned F = eval_begin<NW>(L, P, inst, st, status, wid);
     int k = 0, iters = 0;
     const int flags = controller_eval<NW, R, QF32>(L, P, inst, t, wid, &F, &k, &iters, DEBUG ? debug + (size_t)LMH_DEBUG_STRIDE * inst : nullptr);
     bsync<NW>();                                                   // torques of the helper wave
     if (wid == 0) {
         store_out(L, out + (size_t)LMH_OUT_STRIDE * inst);
         if (LANE < 30) st[60 + LANE] = L[P_V + LANE];              // Robot::v_ <- dq (controller.cpp:59)
-        if (LANE == 0) {
-            int32_t *s = status + LMH_STATUS_STRIDE * inst;
-            s[0] = k; s[1] = iters; s[2] = flags; s[3] = (int32_t)(~F);
-        }
+        if (LANE == 0) store_status(status, inst, k, iters, flags, F);
     }
 }
 
@@ -4294,8 +4319,7 @@ __global__ void __launch_bounds__(64) lmh_com_kernel(LmhDevParams P_arg, const d
     if (inst >= P.n_instances) return;
     SET_GDBG(nullptr);
     load_common(L, P, inst);
-    if (LANE < 30) L[P_Q + LANE] = q[30 * (size_t)inst + LANE];
-    if (LANE < 60) L[P_V + LANE] = 0.0;
+    load_qv(L, q, nullptr, inst, LANE, true);
     WSYNC();
     phase_fk<double>(L, P.lcoef);
     phase_com_x<1, double>(L, 0);
@@ -4367,11 +4391,7 @@ __global__ void __launch_bounds__(64) lmh_terms_kernel(LmhDevParams P_arg, const
     const int lane = LANE;
     SET_GDBG(nullptr);
     load_common(L, P, inst);
-    if (lane < 30) {
-        const double vv = v ? v[30 * (size_t)inst + lane] : 0.0;
-        L[P_Q + lane] = q[30 * (size_t)inst + lane];
-        L[P_V + lane] = vv; L[P_VP + lane] = vv;                   // one velocity for every term
-    }
+    load_qv(L, q, v, inst, lane, true);                            // one velocity for every term
     if constexpr (MODE != TM_TERMS) {
         if (lane < 30) L[TM_X + lane] = x[30 * (size_t)inst + lane];
         else if (lane >= 32 && lane < 44) L[TM_W + lane - 32] = w ? w[12 * (size_t)inst + lane - 32] : 0.0;
@@ -4482,6 +4502,26 @@ __device__ __forceinline__ int plant_derivative(double *L, LmhCParams &P, const 
     phase_outputs_qdd(L, PL_AP);
     return flags;
 }
+// n_substeps x rk4Step (rk4.hpp:5-18) with the torques held: `x` (lane i < 60 = component i of q | v, as in the rollout's rk4_stage) comes in
+// and goes out in a register, L[P_Q], L[P_V] carry each stage's state (and are left at the last stage's, not at x: a caller that wants x in
+// LDS writes it), `flags` collects plant_derivative's and LMH_FLAG_NONFINITE of x behind every substep.  Wave-scope fences only; no clock:
+// the callers advance theirs by n_substeps additions of dt (lmh_plant_kernel<PM_STEP>; wave 0 of lmh_rollout_zoh_kernel)
+__device__ __forceinline__ void plant_hold(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau, double dt, int n_substeps, double &x, int &flags)
+{
+#pragma unroll 1
+    for (int sub = 0; sub < n_substeps; sub++) {
+        double ksum = 0.0, xs = x;
+#pragma unroll 1
+        for (int stage = 0; stage < 4; stage++) {
+            WSYNC();
+            if (lane < 60) L[P_Q + lane] = xs;                     // q | v are one run
+            WSYNC();
+            flags |= plant_derivative(L, P, ibp, lane, tau);
+            rk4_stage<0>(L, stage, lane, dt, P_SC + 52, x, ksum, xs);
+        }
+        if (__ballot(lane < 60 && !(fabs(x) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
+    }
+}
 __device__ __forceinline__ void plant_store_contact(const double *L, double *o, int lane)
 {
     const int e = (lane >= 12 && lane < 36) ? lane - 12 : 0;
@@ -4502,11 +4542,7 @@ __global__ void __launch_bounds__(64) lmh_plant_kernel(LmhDevParams P_arg, const
     SET_GDBG(nullptr);
     load_common(L, P, inst);
     if constexpr (MODE == PM_CONTACT) {
-        if (lane < 30) {
-            const double vv = v ? v[30 * (size_t)inst + lane] : 0.0;
-            L[P_Q + lane] = q[30 * (size_t)inst + lane];
-            L[P_V + lane] = vv; L[P_VP + lane] = vv;
-        }
+        load_qv(L, q, v, inst, lane, true);
         WSYNC();
         phase_fk<double>(L, P.lcoef);
         phase_com_x<1, double>(L, 0);
@@ -4518,7 +4554,7 @@ __global__ void __launch_bounds__(64) lmh_plant_kernel(LmhDevParams P_arg, const
         const double tau = (tau30 && lane < 30) ? tau30[30 * (size_t)inst + lane] : 0.0;
         int flags = 0;
         if constexpr (MODE == PM_DERIV) {
-            if (lane < 30) { L[P_Q + lane] = q[30 * (size_t)inst + lane]; L[P_V + lane] = v[30 * (size_t)inst + lane]; }
+            load_qv(L, q, v, inst, lane, false);                   // (plant_derivative sets P_VP itself)
             WSYNC();
             flags |= plant_derivative(L, P, ibp, lane, tau);
             double x = 0.0, xd = 0.0, xs = 0.0;
@@ -4530,20 +4566,9 @@ __global__ void __launch_bounds__(64) lmh_plant_kernel(LmhDevParams P_arg, const
             double *st = state + (size_t)LMH_STATE_STRIDE * inst;
             double x = (lane < 60) ? st[lane] : 0.0, t = st[90];
             const double dt = P.dt;
+            plant_hold(L, P, ibp, lane, tau, dt, n_substeps, x, flags);
 #pragma unroll 1
-            for (int sub = 0; sub < n_substeps; sub++) {
-                double ksum = 0.0, xs = x;
-#pragma unroll 1
-                for (int stage = 0; stage < 4; stage++) {          // rk4.hpp:5-18 with the torques held
-                    WSYNC();
-                    if (lane < 60) L[P_Q + lane] = xs;             // q | v are one run
-                    WSYNC();
-                    flags |= plant_derivative(L, P, ibp, lane, tau);
-                    rk4_stage<0>(L, stage, lane, dt, P_SC + 52, x, ksum, xs);
-                }
-                if (__ballot(lane < 60 && !(fabs(x) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
-                t += dt;                                           // Clock::step, Clock.hpp:11
-            }
+            for (int sub = 0; sub < n_substeps; sub++) t += dt;    // Clock::step, Clock.hpp:11
             if (lane < 60) st[lane] = x; else if (lane == 60) st[90] = t;
         }
         if (lane == 0 && flags_out) flags_out[inst] = flags;
@@ -4568,13 +4593,14 @@ extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *
 
 // ============================================================================ zero-order-hold closed loop: controller and plant rates in one launch
 // lmh_rollout_zoh (include/lmh.h): for every robot exactly what n_ticks rounds of { lmh_eval ; lmh_plant_step(tau30 = [base_wrench | out.tau],
-// n_substeps) } leave, bit for bit, with the robot on chip for the whole launch.  One workgroup per robot, the two-wave schedule of
-// lmh_eval_kernel for the evaluation; the hold is lmh_plant_kernel<PM_STEP>'s loop on wave 0 (wave-scope fences only) while the helper wave
-// waits at the join that ends the tick, so both waves pass the same number of workgroup barriers.
+// n_substeps) } leave, bit for bit, with the robot on chip for the whole launch.  One workgroup per robot; the launch opens with
+// lmh_eval_kernel's eval_begin and runs its two-wave schedule for the evaluation; the hold is plant_hold, the loop lmh_plant_kernel<PM_STEP>
+// calls, on wave 0 (wave-scope fences only) while the helper wave waits at the join that ends the tick, so both waves pass the same number of
+// workgroup barriers.
 // What the separate launches did between two evaluations, and what happens to it here:
 //   v_prev      lmh_eval stores v_prev <- v and lmh_plant_step leaves it alone, but plant_derivative overwrites L[P_VP] with the velocity of
 //               its stage: the v the evaluation saw rides in a register across the hold and goes back to L[P_VP] behind it.
-//   state       wave 0's lanes 0..59 hold q | v during the hold (as lmh_plant_kernel), L[P_Q..] holds it across the evaluation, which writes
+//   state       wave 0's lanes 0..59 hold q | v during the hold (plant_hold's x), L[P_Q..] holds it across the evaluation, which writes
 //               neither.  The fourth stage's xs is fma(0, xdot, x), not x, when xdot is not finite: x itself is written back.
 //   clock       t += dt once per substep on both waves (wave-uniform, the same fp64 sum as the state record's t through the launches).
 //   warm start  F stays in wave 0's register (the launches carry ~F through status[3]); L[P_KF] is what phase_qp published, which is F.
@@ -4596,25 +4622,10 @@ __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_wav
     const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     double *st = state + (size_t)LMH_STATE_STRIDE * inst;
     double t = st[90];
-    unsigned F = 0xFFFFFFFFu;
     SET_GDBG(nullptr);
-#ifdef LMH_SUBSTAMPS
-    if (threadIdx.x == 0) g_L = L;
-    __syncthreads();
-#endif
-    LMH_POISON_LDS(L, LDS_DOUBLES);
     double bw = 0.0;                                               // lane i < 6: the wrench on the base, held for the launch
-    if (wid == 0) {
-        load_common(L, P, inst);
-        for (int e = LANE; e < 91; e += 64) L[P_Q + e] = st[e];    // q | v | v_prev | t
-        F = (unsigned)status[LMH_STATUS_STRIDE * inst + 3];
-        F = P.warm_start ? ~F : 0xFFFFFFFFu;
-        if (LANE == 0) { L[P_KF] = (double)F; L[P_KF + 2] = 0.0; L[P_ORI] = 0.0; }
-        if (base_wrench && LANE < 6) bw = base_wrench[6 * (size_t)inst + LANE];
-        WSYNC();
-    }
-    bsync<2>();
-    if (wid == 0) __builtin_amdgcn_s_setprio(3); else __builtin_amdgcn_s_setprio(0);               // see lmh_rollout_kernel
+    if (wid == 0 && base_wrench && LANE < 6) bw = base_wrench[6 * (size_t)inst + LANE];
+    unsigned F = eval_begin<2>(L, P, inst, st, status, wid);
     const double dt = P.dt;
     int k = 0, itmax = 0, flags = 0;
 #pragma unroll 1
@@ -4634,20 +4645,7 @@ __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_wav
             double x = L[P_Q + ((lane < 60) ? lane : 0)];          // q | v are one run
             const double vp = L[P_V + ((lane < 30) ? lane : 0)];   // Robot::v_ <- dq (controller.cpp:59): what the next evaluation sees
             const double tau = (lane < 6) ? bw : L[P_TAU + ((lane >= 6 && lane < 30) ? lane - 6 : 0)];         // lane i < 30: tau30[i] = [base wrench | out.tau]
-            const IbPack ibp = ib_pack();
-#pragma unroll 1
-            for (int sub = 0; sub < n_substeps; sub++) {           // lmh_plant_kernel<PM_STEP>
-                double ksum = 0.0, xs = x;
-#pragma unroll 1
-                for (int stage = 0; stage < 4; stage++) {
-                    WSYNC();
-                    if (lane < 60) L[P_Q + lane] = xs;
-                    WSYNC();
-                    flags |= plant_derivative(L, P, ibp, lane, tau);
-                    rk4_stage<0>(L, stage, lane, dt, P_SC + 52, x, ksum, xs);
-                }
-                if (__ballot(lane < 60 && !(fabs(x) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
-            }
+            plant_hold(L, P, ib_pack(), lane, tau, dt, n_substeps, x, flags);
             WSYNC();
             if (lane < 60) L[P_Q + lane] = x;
             if (lane < 30) L[P_VP + lane] = vp;
@@ -4659,11 +4657,7 @@ __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_wav
     }
     if (wid == 0) {
         for (int e = LANE; e < 90; e += 64) st[e] = L[P_Q + e];    // q | v | v_prev
-        if (LANE == 0) {
-            st[90] = t;
-            int32_t *s = status + LMH_STATUS_STRIDE * inst;
-            s[0] = k; s[1] = itmax; s[2] = flags; s[3] = (int32_t)(~F);
-        }
+        if (LANE == 0) { st[90] = t; store_status(status, inst, k, itmax, flags, F); }
     }
 }
 extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, int n_ticks, int n_substeps,
