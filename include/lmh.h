@@ -362,7 +362,11 @@ int lmh_trace_samples(int n_ticks, int trace_every);      /* n_ticks / trace_eve
 
 /* replaces: Kinematics::desiredOperationalState + Kinematics::compute
  * (src/invKinematics.cpp:11-52): Newton IK to feet (0,-/+0.05,0), com target, per instance.
- * DEVICE d_q [B][30] in/out (start posture in, solution out); com_target HOST [3]. */
+ * DEVICE d_q [B][30] in/out (start posture in, solution out); com_target HOST [3]; rf6, lf6 HOST [6]: the soles' targets
+ * [x y z | roll pitch yaw], the angles those of R * Rf_q0 (invKinematics.cpp:256-267).  d_iters [B] (optional): Newton steps taken.
+ * The iteration stops when max|e| <= 1e-10 or after 200 steps (the reference has no cap).  Not converged: d_iters[i] == 200, or a
+ * non-finite entry in d_q[i] (a target out of reach drives the iteration through singular postures; a NaN criterion also ends it).
+ * Either way the call returns and the other robots of the launch are not affected; there is no error code for it. */
 int lmh_ik(lmh_handle *h, double *d_q, const double *com_target, const double *rf6, const double *lf6,
            int32_t *d_iters, void *stream);
 

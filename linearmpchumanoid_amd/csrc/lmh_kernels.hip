@@ -4249,7 +4249,10 @@ __global__ void __launch_bounds__(64) lmh_ik_kernel(LmhDevParams P_arg, double *
         WSYNC();
         // ---- Gaussian elimination with partial pivoting on [J | e] (30 x 31)
         for (int c = 0; c < 30; c++) {
-            double best = (lane >= c && lane < 30) ? fabs(L[IK_J + 31 * lane + c]) : -1.0;
+            // a NaN entry ranks as +inf: every comparison with a NaN is false, which would leave each lane with a pivot row of its own
+            // (row 30 among them, outside the matrix) once a diverging iteration has gone non-finite
+            double best = -1.0;
+            if (lane >= c && lane < 30) { const double a = fabs(L[IK_J + 31 * lane + c]); best = (a == a) ? a : __builtin_huge_val(); }
             int bi = lane;
             for (int o = 32; o > 0; o >>= 1) {
                 const double ob = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);

@@ -159,6 +159,9 @@ void orc_dynamics_compute_all(orc_dynamics *d, const orc_robot *r);   /* Dynamic
 void orc_dynamics_bias_now(const orc_dynamics *d, const orc_robot *r, double C[ORC_NQ]); /* Dynamics.cpp:29-60 at the CURRENT Robot::v_ (plant only) */
 void orc_feet_jacobian(const orc_robot *r, double *JFeet /*12x30*/);  /* invKinematics.cpp:72-149 */
 int  orc_ik_compute(orc_robot *r, const double *desOp);               /* invKinematics.cpp:27-52 */
+extern int orc_ik_test_no_foot_omega;                                 /* test switch, see orc_dynamics.c */
+#define ORC_IK_MAXIT 200                                              /* the iteration cap of orc_ik_compute */
+int  orc_ik_compute_crit(orc_robot *r, const double *desOp, double *crit_log /* ORC_IK_MAXIT + 1 or NULL */, int *n_crit);
 void orc_ik_desired_op(const orc_robot *r, const double *Rf, const double *Lf,
                        const double *com, double *Qd);                /* invKinematics.cpp:11-25 */
 

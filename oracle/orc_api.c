@@ -86,6 +86,22 @@ void orc_sys_get_robot(void *h, double *q, double *v, double *CoM, double *comVe
 /* overwrite Robot::v_ (the stale velocity the next evaluation's C/Cg/Jpqp will see) */
 void orc_sys_set_prev_velocity(void *h, const double *v) { memcpy(((orc_box *)h)->sys.robot.v, v, ORC_NQ * sizeof(double)); }
 void orc_sys_set_q(void *h, const double *q) { orc_robot_update_state(&((orc_box *)h)->sys.robot, q); }
+
+/* Kinematics::desiredOperationalState + compute from a caller-chosen start posture to caller-chosen targets (invKinematics.cpp:11-52):
+ * sets the posture, forms the desired operational state (arm / head joints of the START posture, zero base attitude) and iterates.
+ * q_out [30]: the robot's posture afterwards; crit [ORC_IK_MAXIT + 1]: max|e| before each Newton step and after the last, *n_crit of
+ * them.  Returns the iteration count, -1 on a singular solve (q_out is then the posture the failed step started from). */
+int orc_sys_ik(void *h, const double *q_start, const double *com, const double *rf6, const double *lf6,
+               double *q_out, double *crit, int *n_crit)
+{
+    orc_robot *r = &((orc_box *)h)->sys.robot;
+    double Qd[ORC_NQ];
+    orc_robot_update_state(r, q_start);
+    orc_ik_desired_op(r, rf6, lf6, com, Qd);
+    const int it = orc_ik_compute_crit(r, Qd, crit, n_crit);
+    memcpy(q_out, r->q, sizeof(r->q));
+    return it;
+}
 void orc_sys_set_wbc_calls(void *h, int n, int faithful) { orc_box *b = (orc_box *)h; b->sys.ctl.wbc_calls_per_eval = n; b->sys.mpc.faithful_rebuild = faithful; }
 
 void orc_sys_set_refs(void *h, int n, const double *zx, const double *zy, const unsigned char *phase)

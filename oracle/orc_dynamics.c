@@ -296,6 +296,10 @@ static void com_jacobian(const orc_robot *r, double J[3 * ORC_NQ])   /* :206-244
         for (int b = 0; b < 3; b++) J[a * ORC_NQ + 3 + b] = o[a * 3 + b];
 }
 
+/* test switch: 1 leaves the OmegaFoot product (:191-197) out of the Jacobian, so that a test can show that its cases tell the two
+ * apart (tests/test_ik_cases.py); never set by anything else */
+int orc_ik_test_no_foot_omega = 0;
+
 static void jac_inv_kinematics(const orc_robot *r, double J[ORC_NQ * ORC_NQ])  /* :151-204 */
 {
     double Jf[12 * ORC_NQ], tmp;
@@ -327,7 +331,7 @@ static void jac_inv_kinematics(const orc_robot *r, double J[ORC_NQ * ORC_NQ])  /
         orc_omega_to_euler_rate(eta, Of);
         for (int a = 0; a < 3; a++)
             for (int b = 0; b < 3; b++) blk[a * 3 + b] = Jf[(6 * s + 3 + a) * ORC_NQ + 3 + b];
-        orc_mm(3, 3, 3, Of, blk, o);
+        if (orc_ik_test_no_foot_omega) memcpy(o, blk, sizeof(o)); else orc_mm(3, 3, 3, Of, blk, o);
         for (int a = 0; a < 3; a++)
             for (int b = 0; b < 3; b++) Jf[(6 * s + 3 + a) * ORC_NQ + 3 + b] = o[a * 3 + b];
     }
@@ -345,16 +349,21 @@ void orc_ik_desired_op(const orc_robot *r, const double *Rf, const double *Lf, c
 }
 
 /* :27-52.  The reference never increments `iter`; the cap below (A9 in SURVEY) only
- * prevents an endless loop, the shipped target converges in 4 Newton steps. */
-int orc_ik_compute(orc_robot *r, const double *desOp)
+ * prevents an endless loop, the shipped target converges in 4 Newton steps.
+ * crit_log (optional, ORC_IK_MAXIT + 1 doubles): the convergence criterion max|e| before each
+ * Newton step and after the last, *n_crit of them. */
+int orc_ik_compute_crit(orc_robot *r, const double *desOp, double *crit_log, int *n_crit)
 {
     double q[ORC_NQ], Q[ORC_NQ], e[ORC_NQ], J[ORC_NQ * ORC_NQ], dq[ORC_NQ];
     memcpy(q, r->q, sizeof(q));
     operational_state(r, Q);
     double crit = 0;
+    int nc = 0;
     for (int k = 0; k < ORC_NQ; k++) { e[k] = desOp[k] - Q[k]; if (fabs(e[k]) > crit) crit = fabs(e[k]); }
+    if (crit_log) crit_log[nc++] = crit;
+    if (n_crit) *n_crit = nc;
     int iter = 0;
-    while (crit > 1e-10 && iter < 200) {
+    while (crit > 1e-10 && iter < ORC_IK_MAXIT) {
         jac_inv_kinematics(r, J);
         if (orc_solve_ge(ORC_NQ, J, e, dq)) return -1;
         for (int k = 0; k < ORC_NQ; k++) q[k] += dq[k];
@@ -362,7 +371,11 @@ int orc_ik_compute(orc_robot *r, const double *desOp)
         operational_state(r, Q);
         crit = 0;
         for (int k = 0; k < ORC_NQ; k++) { e[k] = desOp[k] - Q[k]; if (fabs(e[k]) > crit) crit = fabs(e[k]); }
+        if (crit_log) crit_log[nc++] = crit;
+        if (n_crit) *n_crit = nc;
         iter++;
     }
     return iter;
 }
+
+int orc_ik_compute(orc_robot *r, const double *desOp) { return orc_ik_compute_crit(r, desOp, NULL, NULL); }

@@ -40,6 +40,8 @@ def lib():
         _lib.orc_sys_set_gains.argtypes = [C.c_void_p, C.c_void_p]
         _lib.orc_sys_get_gains.argtypes = [C.c_void_p, C.c_void_p]
         _lib.orc_batch_rollout_ex.restype = C.c_double
+        _lib.orc_sys_ik.restype = C.c_int
+        _lib.orc_sys_ik.argtypes = [C.c_void_p] * 8
         for name in ("orc_sys_destroy", "orc_sys_mass", "orc_sys_horizon", "orc_sys_zcom", "orc_sys_nzmp"):
             getattr(_lib, name).argtypes = [C.c_void_p]
     return _lib
@@ -114,6 +116,23 @@ class Oracle:
     def set_q(self, q):
         q = np.ascontiguousarray(q, dtype=np.float64)
         lib().orc_sys_set_q(self._h, _p(q))
+
+    def ik(self, q_start, com_target=(-0.02, 0.0, 0.26), rf6=(0, -0.05, 0, 0, 0, 0), lf6=(0, 0.05, 0, 0, 0, 0), foot_omega=True):
+        """Kinematics::desiredOperationalState + compute from q_start to the targets given (feet [position | roll pitch yaw], CoM):
+        dict(q, iters, crit).  crit is the stop criterion max|e| before each Newton step and after the last; iters is -1 on a singular
+        solve.  The oracle's robot is left at q.  foot_omega=False is a test switch: the Jacobian without its OmegaFoot product."""
+        qs = np.ascontiguousarray(q_start, dtype=np.float64)
+        ct = np.ascontiguousarray(com_target, dtype=np.float64)
+        r6, l6 = np.ascontiguousarray(rf6, dtype=np.float64), np.ascontiguousarray(lf6, dtype=np.float64)
+        assert qs.shape == (30,) and ct.shape == (3,) and r6.shape == (6,) and l6.shape == (6,)
+        q, crit, n = _f64(30), _f64(201), C.c_int(0)
+        switch = C.c_int.in_dll(lib(), "orc_ik_test_no_foot_omega")
+        switch.value = 0 if foot_omega else 1
+        try:
+            it = lib().orc_sys_ik(self._h, _p(qs), _p(ct), _p(r6), _p(l6), _p(q), _p(crit), C.byref(n))
+        finally:
+            switch.value = 0
+        return dict(q=q, iters=int(it), crit=crit[:n.value].copy())
 
     def set_zcom(self, z):
         lib().orc_sys_set_zcom(self._h, C.c_double(z))
