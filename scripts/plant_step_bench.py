@@ -6,15 +6,11 @@ millimetre into the default ground with small random velocities and are driven b
 maximum of `--steps` launches after `--warmup` warm-up launches are reported, in robot-substeps per second.
 Usage: python scripts/plant_step_bench.py [--instances 4096] [--substeps 100] [--steps 7] [--warmup 2] [--out FILE]"""
 import argparse
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 import numpy as np
 import torch
 
+from _bench_common import summary, time_launches, write_lines
 from linearmpchumanoid_amd.controller import BatchedController, default_config, ik_start_posture
 
 ap = argparse.ArgumentParser()
@@ -34,25 +30,21 @@ v = np.zeros((B, 30)); v[:, 0:2] = rng.uniform(-0.05, 0.05, (B, 2)); v[:, 6:] = 
 st0 = ctl.new_state(q, v, t=0.0)
 out, _ = ctl.stand_step(st0.clone())
 tau = torch.cat([torch.zeros((B, 6), dtype=torch.float64, device=ctl.device), out[:, 0:24]], dim=1).contiguous()
-times, flagged = [], 0
-for it in range(args.warmup + args.steps):
-    st = st0.clone()
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    st, flags = ctl.plant_step(st, tau, n)
-    e1.record()
-    torch.cuda.synchronize()
-    if it >= args.warmup:
-        times.append(e0.elapsed_time(e1))
-    flagged = int((flags != 0).sum())
-ms = float(np.median(times))
+
+
+def launch(s):
+    global st, flags                                                # of the last launch
+    st, flags = ctl.plant_step(s, tau, n)
+
+
+times = time_launches(launch, args.steps, warmup=args.warmup, before=st0.clone)
+flagged = int((flags != 0).sum())
+ms, lo, hi = summary(times)
 rate = lambda t: B * n / t / 1e3
 lines = ["lmh_plant_step: %d robots x %d substeps, fp64, one wave per robot (%s)" % (B, n, torch.cuda.get_device_name(0)),
-         "%.3f ms / launch (median of %d after %d warm-up; min %.3f max %.3f)" % (ms, len(times), args.warmup, min(times), max(times)),
+         "%.3f ms / launch (median of %d after %d warm-up; min %.3f max %.3f)" % (ms, len(times), args.warmup, lo, hi),
          "%.3f M robot-substeps/s (median; %.3f .. %.3f over the launches, spread %.1f %%)" % (
-             rate(ms), rate(max(times)), rate(min(times)), 100.0 * (max(times) - min(times)) / ms),
+             rate(ms), rate(hi), rate(lo), 100.0 * (hi - lo) / ms),
          "flagged robots %d of %d; finite %s" % (flagged, B, bool(torch.isfinite(st[:, 0:60]).all()))]
 print("\n".join(lines))
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    open(args.out, "w").write("\n".join(lines) + "\n")
+write_lines(args.out, lines)

@@ -5,15 +5,11 @@ the posture sweep's draw around the IK start posture (joints +-1 rad) with veloc
 is launched `--reps` times back to back between two events, the median of `--steps` such groups after one warm-up group is reported.
 Usage: python scripts/terms_bench.py [--instances 4096] [--reps 20] [--steps 5] [--out FILE]"""
 import argparse
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 import numpy as np
 import torch
 
+from _bench_common import summary, time_launches, write_lines
 from linearmpchumanoid_amd import capi
 from linearmpchumanoid_amd.controller import BatchedController, default_config, ik_start_posture
 
@@ -38,25 +34,14 @@ calls = [("terms", lambda: ctl.terms(q, v), capi.TERMS_STRIDE * 8),
          ("forward_dynamics", lambda: ctl.forward_dynamics(q, v, tau, w), 244)]
 lines = ["rigid-body calls: %d robots, fp64, one wave per robot (%s)" % (B, torch.cuda.get_device_name(0))]
 for name, fn, nbytes in calls:
-    times = []
-    for it in range(args.steps + 1):                                # the first group warms up
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for _ in range(args.reps):
-            res = fn()
-        e1.record()
-        torch.cuda.synchronize()
-        if it:
-            times.append(e0.elapsed_time(e1) / args.reps)
-    ms = float(np.median(times))
+    times = time_launches(fn, args.steps, reps=args.reps)           # the first group warms up
+    ms, lo, hi = summary(times)
     line = "%-17s %8.3f ms / call (median of %d groups of %d; min %.3f max %.3f)  %8.3f M robots/s  %6.2f GB/s written" % (
-        name, ms, len(times), args.reps, min(times), max(times), B / ms / 1e3, B * nbytes / ms / 1e6)
+        name, ms, len(times), args.reps, lo, hi, B / ms / 1e3, B * nbytes / ms / 1e6)
     print(line, flush=True)
     lines.append(line)
 x, flags = ctl.forward_dynamics(q, v, tau, w)
 torch.cuda.synchronize()
 lines.append("forward_dynamics(inverse_dynamics(qdd)) - qdd: max %.3e; flagged robots %d of %d" % (float((x - qdd).abs().max()), int((flags != 0).sum()), B))
 print(lines[-1])
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    open(args.out, "w").write("\n".join(lines) + "\n")
+write_lines(args.out, lines)

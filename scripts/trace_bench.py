@@ -10,17 +10,12 @@ Lines, in this order on the same handle:
   none      : 4000 ticks again, the drift of the visit
 Usage: python scripts/trace_bench.py [--instances 4096] [--ticks 4000] [--short-ticks 1000] [--steps 3] [--out FILE]"""
 import argparse
-import os
-import sys
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 import numpy as np
 import torch
 
+from _bench_common import DT, MPC_DT, N_PREVIEW, config3_walkers, summary, time_launches, write_lines
 from linearmpchumanoid_amd import capi
-from linearmpchumanoid_amd.controller import BatchedController, default_config, ik_start_posture
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--instances", type=int, default=4096)
@@ -30,39 +25,33 @@ ap.add_argument("--steps", type=int, default=3)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 B, nt = args.instances, args.ticks
-dt, mpc_dt, N = 1e-3, 1e-2, 32
-sim = nt * dt + 1.0
-q0, zcom = ik_start_posture(0)
-ctl = BatchedController(B, default_config(dt=dt, time_horizon=N * mpc_dt + 1e-9, z_com=zcom, mpc_dt=mpc_dt, warm_start=1))
-ctl.set_xscale(np.array([np.random.default_rng(20260003 + i).uniform(0.02, 0.05) for i in range(B)]))     # bench.py's step lengths
-ctl.gen_walk(sim, num_steps=max(2, int((sim - 0.3) / 0.5)), time_per_step=0.5, ds_time=0.2, step_height=0.02, settle_time=0.3)
-out, status = ctl.new_out(), ctl.new_status()
-log = torch.zeros((nt, B, 36), dtype=torch.float64, device=ctl.device)
+ctl, q0, out, status, log = config3_walkers(B, nt)
 
 
 def measure(name, ticks, every):
     ns = capi.lib().lmh_trace_samples(ticks, every)
     trace = torch.zeros((ns, B, capi.TRACE_STRIDE), dtype=torch.float64, device=ctl.device) if every else None
-    times, flagged = [], 0
-    for it in range(args.steps + 1):                                # the first launch warms up
+    st = None                                                       # the state of the last launch
+
+    def fresh():
+        nonlocal st
         st = ctl.new_state(q0, np.zeros(30), t=0.0)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
+        return st
+
+    def launch(s):
         if every:
-            ctl.rollout_trace(st, ticks, every, out, status, log[:ticks], trace)
+            ctl.rollout_trace(s, ticks, every, out, status, log[:ticks], trace)
         else:
-            ctl.rollout(st, ticks, out, status, log[:ticks])
-        e1.record()
-        torch.cuda.synchronize()
-        if it:
-            times.append(e0.elapsed_time(e1))
-        flagged = int((status[:, 2] != 0).sum().item())
+            ctl.rollout(s, ticks, out, status, log[:ticks])
+
+    times = time_launches(launch, args.steps, before=fresh)         # the first launch warms up
+    flagged = int((status[:, 2] != 0).sum().item())
     if every:                                                       # the last sample is the launch's own final record
         assert torch.equal(trace[-1, :, :96], st) and torch.equal(trace[-1, :, 96:176], out)
-    ms = float(np.median(times))
+    ms, lo, hi = summary(times)
     gb = ns * B * capi.TRACE_STRIDE * 8 / 1e9
     line = "%-9s %5d ticks  %5d samples  %7.3f GB written  %9.2f ms / launch (median of %d; min %.2f max %.2f)  %8.3f M ticks/s  flagged robots %d of %d" % (
-        name, ticks, ns, gb, ms, len(times), min(times), max(times), B * ticks / ms / 1e3, flagged, B)
+        name, ticks, ns, gb, ms, len(times), lo, hi, B * ticks / ms / 1e3, flagged, B)
     print(line, flush=True)
     del trace
     torch.cuda.empty_cache()
@@ -70,12 +59,10 @@ def measure(name, ticks, every):
 
 
 lines = ["rollout trace: %d robots, dt=%g, N=%d x mpc_dt=%g, log on, same handle (%s); a sample is %d B per robot"
-         % (B, dt, N, mpc_dt, torch.cuda.get_device_name(0), capi.TRACE_STRIDE * 8)]
+         % (B, DT, N_PREVIEW, MPC_DT, torch.cuda.get_device_name(0), capi.TRACE_STRIDE * 8)]
 lines.append(measure("none", nt, 0))
 lines.append(measure("every=10", nt, 10))
 lines.append(measure("none", args.short_ticks, 0))
 lines.append(measure("every=1", args.short_ticks, 1))
 lines.append(measure("none", nt, 0))
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    open(args.out, "w").write("\n".join(lines) + "\n")
+write_lines(args.out, lines)

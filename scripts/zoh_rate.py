@@ -10,16 +10,12 @@ The host loop forms tau30 = [base wrench | out.tau] with one device copy per tic
 small random velocities) at n_substeps = 1 and 10, base height, tilt and flags every tenth of the run.  An observation, not a check.
 Usage: python scripts/zoh_rate.py [--instances 4096] [--ticks 200] [--steps 5] [--warmup 2] [--stand] [--out FILE]"""
 import argparse
-import os
-import sys
 import time
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 
 import numpy as np
 import torch
 
+from _bench_common import write_lines
 from linearmpchumanoid_amd.controller import BatchedController, default_config, ik_start_posture
 
 ap = argparse.ArgumentParser()
@@ -112,6 +108,4 @@ else:
                 n_sub, mf * 1e3, min(tf) * 1e3, max(tf) * 1e3, spread(tf, mf), B * nt / mf / 1e6, B * nt * n_sub / mf / 1e6,
                 mh * 1e3, min(th) * 1e3, max(th) * 1e3, spread(th, mh), B * nt / mh / 1e6, B * nt * n_sub / mh / 1e6, mh / mf,
                 same, int((xa[:, 2] != 0).sum()), bool(torch.isfinite(sa[:, 0:60]).all())))
-if args.out:
-    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    open(args.out, "w").write("\n".join(lines) + "\n")
+write_lines(args.out, lines)

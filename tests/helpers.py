@@ -1,7 +1,24 @@
-"""Shared helpers for the parity tests (oracle = checker; HIP path = thing under test)."""
+"""Shared helpers for the parity tests (oracle = checker; HIP path = thing under test), and the one home of the tests' scaffolding:
+
+  tolerances      rel_err, vec_err, close, close_on, TOL_REL, TOL_FLOOR, WEIGHT
+  draws           perturbed_velocities, posture_sweep, sincos_quadrants
+  oracles         oracle_system, make_oracle, start_posture, the cfg2 fixture, dense_terms_from_debug
+  controllers     horizon_time, make_controller (dt, th given), horizon_controller (N, mpc_dt given), to_device
+  bit identity    same_bits (one array), bits_differ (the fields of two rollout results)
+  child processes child_env / run_probe (a fresh Python on a chosen build), bench_env / run_bench (bench.py)
+
+Nothing here imports linearmpchumanoid_amd at module level, so the CPU tests can import it without the HIP library."""
+import json
+import os
+import subprocess
+import sys
+
 import numpy as np
+import pytest
 
 from oracle.pyoracle import Oracle
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 TOL_REL = 1e-6      # north_star: 1e-6 relative on torques / forces
 TOL_FLOOR = 1e-9    # absolute floor as a fraction of max|.| (near-zero entries such as n_z)
@@ -94,6 +111,102 @@ def sincos_quadrants(q):
 
 def oracle_system(dt, horizon_time, sim_time=2.0, raw_links=None):
     return Oracle(sim_time=sim_time, dt=dt, horizon_time=horizon_time, do_ik=True, raw_links=raw_links)
+
+
+def horizon_time(N, mpc_dt):
+    return N * mpc_dt + 1e-9                                       # int(th / mpc_dt) == N whatever the rounding of the quotient
+
+
+def make_oracle(N, sim_time, mpc_dt):
+    return Oracle(sim_time=sim_time, dt=mpc_dt, horizon_time=horizon_time(N, mpc_dt), do_ik=True)
+
+
+def start_posture(o):
+    """The LIPM height and the IK start posture of an oracle: what a handle and its first state are made from."""
+    return dict(zcom=o.zcom, q0=o.robot()["q"].copy())
+
+
+@pytest.fixture(scope="module")
+def cfg2():
+    """BASELINE config 2 constants: dt = 1 ms, N = 16.  Imported by the modules that use it; built once per importing module."""
+    return dict(dt=1e-3, th=0.016, **start_posture(oracle_system(1e-3, 0.016)))
+
+
+def make_controller(B, dt, th, zcom, **cfg):
+    from linearmpchumanoid_amd.controller import BatchedController, default_config
+    return BatchedController(B, default_config(dt=dt, time_horizon=th, z_com=zcom, **cfg))
+
+
+def horizon_controller(B, N, zcom, mpc_dt, dt, **cfg):
+    """A handle whose preview is N samples of mpc_dt, integrated at dt."""
+    return make_controller(B, dt, horizon_time(N, mpc_dt), zcom, mpc_dt=mpc_dt, **cfg)
+
+
+def to_device(ctl, a):
+    import torch
+    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(ctl.device)
+
+
+def same_bits(a, b):
+    """Two numpy arrays or two torch tensors (on any device) are the same shape, dtype and bytes: -0.0 is not 0.0, and a NaN equals only
+    the same NaN pattern."""
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    if isinstance(a, np.ndarray):
+        return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
+    import torch
+    return torch.equal(a.contiguous().reshape(-1).view(torch.uint8), b.contiguous().reshape(-1).view(torch.uint8))
+
+
+def bits_differ(a, b, rows=None, rows_b=None):
+    """Names of the fields (state, out, status, log) of two rollout results that are not bit-identical: [] = the same computation.
+    rows / rows_b select the robots of a / b."""
+    ra = slice(None) if rows is None else rows
+    rb = ra if rows_b is None else rows_b
+    bad = [k for k in ("state", "out", "status") if not same_bits(a[k][ra], b[k][rb])]
+    if not same_bits(a["log"][:, ra], b["log"][:, rb]):
+        bad.append("log")
+    return bad
+
+
+RANK_VARS = ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")     # what a launcher around the suite would hand down to bench.py
+
+
+def child_env(variant=None, extra=None):
+    """The environment of a child on a chosen build: this one's without LMH_VARIANT and LMH_DIAG, then LMH_VARIANT = variant when
+    that is non-empty, then `extra`."""
+    env = {k: v for k, v in os.environ.items() if k not in ("LMH_VARIANT", "LMH_DIAG")}
+    if variant:
+        env["LMH_VARIANT"] = variant
+    env.update(extra or {})
+    return env
+
+
+def bench_env(extra=None):
+    """The environment bench.py is started in: this one's without the rank variables, then `extra`."""
+    env = {k: v for k, v in os.environ.items() if k not in RANK_VARS}
+    env.update(extra or {})
+    return env
+
+
+def run_probe(code, variant="", timeout=900, env_extra=None, args=()):
+    """`python -c code args...` from the repository root on the build `variant` ("" = the shipped library), which must exit with
+    status 0: -> the last line of its output that starts with `{`, parsed as JSON.  A child, because capi chooses the library
+    (LMH_VARIANT) when it is imported: a process that has loaded one build cannot run another."""
+    r = subprocess.run([sys.executable, "-c", code, *args], env=child_env(variant, env_extra), cwd=ROOT, capture_output=True, text=True,
+                       timeout=timeout)
+    assert r.returncode == 0, r.stderr[-3000:]
+    return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+
+
+def run_bench(argv, env_extra=None, expect_rc=0, timeout=900):
+    """bench.py with argv, which must exit with expect_rc and print exactly one result line: -> that line, parsed."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, env=bench_env(env_extra), capture_output=True, text=True,
+                       timeout=timeout)
+    assert r.returncode == expect_rc, (r.returncode, r.stderr[-2000:])
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
+    assert len(lines) == 1, r.stdout[-2000:]
+    return json.loads(lines[0])
 
 
 def dense_terms_from_debug(d):

@@ -10,7 +10,7 @@ from memory, 64 the only one whose window sum takes a second trip of the 64-lane
 of the sizes the rest of the suite runs (16, 64)."""
 import numpy as np
 
-from helpers import perturbed_velocities
+from helpers import horizon_time, perturbed_velocities
 
 H = (1, 2, 15, 17, 44, 45, 46, 47, 63, 64)
 H_ROLLOUT = (1, 45, 46, 63, 64)
@@ -28,10 +28,6 @@ B_EVAL = 3
 SEED = 20261018
 T_FRONT = -0.0035                # the front clamp: k = int(t / mpc_dt) = -3 coupled, 0 decoupled (the cast truncates towards zero)
 PAST_END = 5                     # the end clamp: k + N runs this many samples past the last one
-
-
-def horizon_time(N, mpc_dt):
-    return N * mpc_dt + 1e-9                                       # int(th / mpc_dt) == N whatever the rounding of the quotient
 
 
 def zmp_arrays(n):

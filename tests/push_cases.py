@@ -14,6 +14,7 @@ import os
 import numpy as np
 import torch
 
+from helpers import bits_differ
 from plan_draw import DT, MPC_DT, N_PREVIEW, SIM_TIME, draw_walk_specs
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -95,16 +96,6 @@ def host_split(run, ticks, dv, start, stop):
         run.add_dv(rows, dv[rows, cols])
     if stop > cur:
         run.launch(stop - cur)
-
-
-def bits_differ(a, b, rows=None, rows_b=None):
-    """Names of the fields of two results that are not bit-identical, compared as bytes: [] = the same computation."""
-    ra = slice(None) if rows is None else rows
-    rb = ra if rows_b is None else rows_b
-    bad = [k for k in ("state", "out", "status") if np.ascontiguousarray(a[k][ra]).tobytes() != np.ascontiguousarray(b[k][rb]).tobytes()]
-    if np.ascontiguousarray(a["log"][:, ra]).tobytes() != np.ascontiguousarray(b["log"][:, rb]).tobytes():
-        bad.append("log")
-    return bad
 
 
 def scenario_controller(plant, **kw):

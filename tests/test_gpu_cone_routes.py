@@ -6,15 +6,14 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import TOL_REL, WEIGHT, close, oracle_system
+from helpers import TOL_REL, WEIGHT, close, oracle_system, start_posture
 
 pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
 def consts():
-    o = oracle_system(1e-3, 0.032)
-    return dict(zcom=o.zcom, q0=o.robot()["q"].copy())
+    return start_posture(oracle_system(1e-3, 0.032))
 
 
 def _check_against_oracle(stn, log, status, nt, make_oracle, v0):

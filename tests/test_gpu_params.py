@@ -12,17 +12,11 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import TOL_REL, WEIGHT, close, oracle_system, perturbed_velocities
+from helpers import TOL_REL, WEIGHT, cfg2, close, oracle_system, perturbed_velocities  # noqa: F401
 from params_cases import PLANT_SETS, SIX_SETS, assert_robot_equal, columns, make_controller, run, states
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def cfg2():
-    o = oracle_system(1e-3, 0.016)
-    return dict(dt=1e-3, th=0.016, zcom=o.zcom, q0=o.robot()["q"].copy())
 
 
 @pytest.fixture(scope="module")

@@ -3,21 +3,19 @@ statement, a per-robot handle with equal specs against the shared handle, robot 
 plain / debug evaluation against the CPU oracle on each robot's own plan, the upload path, argument checks, the way back to one
 shared plan and a refused lmh_set_segments, which releases nothing.  The draw (ranges, seed 20261016, order) is tests/plan_draw.py.  Rules as in the other GPU files: the HIP path through the
 C ABI against the oracle, 1e-6 relative on tau / f (helpers.close), bit-exact k; "the same computation" means bit-identical."""
-import json
 import os
-import subprocess
-import sys
 from concurrent.futures import ThreadPoolExecutor
+from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import TOL_REL, WEIGHT, close, perturbed_velocities, vec_err
+import helpers
+from helpers import TOL_REL, WEIGHT, bits_differ, close, horizon_controller, perturbed_velocities, run_probe, vec_err
 from plan_draw import DT, MPC_DT, N_PREVIEW, SIM_TIME, draw_jump_specs, draw_walk_specs, spec_i
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 KP_FEET = 500.0                                   # controller.hpp:108
 
 # the four parameter sets of test_gpu_round2.test_walk_generator_kernel_matches_the_host_plan (without their simulation_time: the sample
@@ -30,18 +28,8 @@ ROUND2_GAITS = [
 ]
 
 
-def horizon_time(N, mpc_dt):
-    return N * mpc_dt + 1e-9                                       # int(th / mpc_dt) == N whatever the rounding of the quotient
-
-
-def make_controller(B, N=N_PREVIEW, zcom=0.26, dt=DT, mpc_dt=MPC_DT, **kw):
-    from linearmpchumanoid_amd.controller import BatchedController, default_config
-    return BatchedController(B, default_config(dt=dt, time_horizon=horizon_time(N, mpc_dt), z_com=zcom, mpc_dt=mpc_dt, **kw))
-
-
-def make_oracle(N, sim_time, mpc_dt=MPC_DT):
-    from oracle.pyoracle import Oracle
-    return Oracle(sim_time=sim_time, dt=mpc_dt, horizon_time=horizon_time(N, mpc_dt), do_ik=True)
+make_controller = partial(horizon_controller, N=N_PREVIEW, zcom=0.26, mpc_dt=MPC_DT, dt=DT)
+make_oracle = partial(helpers.make_oracle, mpc_dt=MPC_DT)
 
 
 @pytest.fixture(scope="module")
@@ -69,9 +57,7 @@ def run(ctl, st, nt, log=True):
 
 def same_bits(a, b, rows=None, rows_b=None):
     """state, out, status and log rows of two results bit for bit; rows / rows_b select the robots of a / b."""
-    ra = slice(None) if rows is None else rows
-    rb = ra if rows_b is None else rows_b
-    return all(np.array_equal(a[k][ra], b[k][rb]) for k in ("state", "out", "status")) and np.array_equal(a["log"][:, ra], b["log"][:, rb])
+    return not bits_differ(a, b, rows, rows_b)
 
 
 def parallel(fn, items, workers=8):
@@ -538,12 +524,7 @@ def test_per_robot_plans_do_not_depend_on_uninitialised_lds():
     assert os.path.exists(so)
     res = {}
     for variant in ("", "poison"):
-        env = {k: v for k, v in os.environ.items() if k not in ("LMH_VARIANT", "LMH_DIAG")}
-        if variant:
-            env["LMH_VARIANT"] = variant
-        r = subprocess.run([sys.executable, "-c", _POISON_PROBE], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        res[variant] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        res[variant] = run_probe(_POISON_PROBE, variant, timeout=600)
     assert res[""]["build_flags"] & 1 == 0 and res["poison"]["build_flags"] & 1 == 1, res
     assert res[""]["per_robot"] and res["poison"]["per_robot"] and res[""]["finite"] and res["poison"]["finite"], res
     assert res[""]["sha"] == res["poison"]["sha"], res

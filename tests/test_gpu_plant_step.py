@@ -15,19 +15,10 @@ import pytest
 import torch
 
 import plant_step_cases as pc
-from helpers import close, close_on, perturbed_velocities, rel_err
+from helpers import close, close_on, make_controller, perturbed_velocities, rel_err, to_device
 
 pytestmark = pytest.mark.gpu
 DT, TH, B = pc.DT, pc.TH, pc.B
-
-
-def _controller(n, zcom, **kw):
-    from linearmpchumanoid_amd.controller import BatchedController, default_config
-    return BatchedController(n, default_config(dt=DT, time_horizon=TH, z_com=zcom, **kw))
-
-
-def _dev(ctl, a):
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(ctl.device)
 
 
 _cache = {}
@@ -75,17 +66,17 @@ def _check_contact(rec, r, tag):
 
 def test_contact_wrench():
     S = _setup()
-    ctl = _controller(B, S["zcom"])
-    c = ctl.contact_wrench(_dev(ctl, S["q"]), _dev(ctl, S["v"]))
-    c0 = ctl.contact_wrench(_dev(ctl, S["q"]))
-    cz = ctl.contact_wrench(_dev(ctl, S["q"]), _dev(ctl, np.zeros((B, 30))))
+    ctl = make_controller(B, DT, TH, S["zcom"])
+    c = ctl.contact_wrench(to_device(ctl, S["q"]), to_device(ctl, S["v"]))
+    c0 = ctl.contact_wrench(to_device(ctl, S["q"]))
+    cz = ctl.contact_wrench(to_device(ctl, S["q"]), to_device(ctl, np.zeros((B, 30))))
     torch.cuda.synchronize()
     assert torch.equal(c0, cz) and not torch.equal(c, c0)          # v = None is v = 0
     c = c.cpu().numpy()
     worst = max(_check_contact(c[i], S["ref"][i], i) for i in range(B))
     print("\ncontact wrench: worst error on the force scale %.2e" % worst)
     # against terms()-derived quantities alone: the sole twist is J vhat and the vertex sits at T_sole's origin plus its turned offset
-    t = ctl.split_terms(ctl.terms(_dev(ctl, S["q"]), _dev(ctl, S["v"])).cpu().numpy())
+    t = ctl.split_terms(ctl.terms(to_device(ctl, S["q"]), to_device(ctl, S["v"])).cpu().numpy())
     for i in range(B):
         r, g = S["ref"][i], pc.GROUND
         for f, frame in enumerate((7, 14)):
@@ -100,8 +91,8 @@ def test_contact_wrench():
 
 def test_plant_derivative_against_the_helper():
     S = _setup()
-    ctl = _controller(B, S["zcom"])
-    q, v, tau = (_dev(ctl, S[k]) for k in ("q", "v", "tau"))
+    ctl = make_controller(B, DT, TH, S["zcom"])
+    q, v, tau = (to_device(ctl, S[k]) for k in ("q", "v", "tau"))
     xdot, c, flags = ctl.plant_derivative(q, v, tau)
     xdot0, _, _ = ctl.plant_derivative(q, v)
     xdotz, _, _ = ctl.plant_derivative(q, v, torch.zeros_like(tau))
@@ -130,12 +121,12 @@ def test_plant_derivative_reproduces_the_device_plant():
     """On a plant = 1 handle with v_prev = v, stand_step's out.qdd is the plant's acceleration under its own out.tau: the new call, given
     tau30 = [0 | out.tau], must return it (forward criterion on the oracle's M; two schedules, no bit equality asked)."""
     S = _setup()
-    ctl = _controller(B, S["zcom"], plant=1, warm_start=0)
+    ctl = make_controller(B, DT, TH, S["zcom"], plant=1, warm_start=0)
     ctl.set_refs_stance(2.0, 2)
     st = ctl.new_state(S["q"], S["v"], t=0.0, v_prev=S["v"])
     out, status = ctl.stand_step(st)
     tau = torch.cat([torch.zeros((B, 6), dtype=torch.float64, device=ctl.device), out[:, 0:24]], dim=1).contiguous()
-    xdot, _, flags = ctl.plant_derivative(_dev(ctl, S["q"]), _dev(ctl, S["v"]), tau)
+    xdot, _, flags = ctl.plant_derivative(to_device(ctl, S["q"]), to_device(ctl, S["v"]), tau)
     torch.cuda.synchronize()
     assert int(flags.abs().max()) == 0
     xdot, qdd = xdot.cpu().numpy(), out.cpu().numpy()[:, 36:66]
@@ -150,9 +141,9 @@ def test_plant_derivative_reproduces_the_device_plant():
 
 def test_plant_step_parity_and_composition():
     S = _setup()
-    ctl = _controller(B, S["zcom"])
+    ctl = make_controller(B, DT, TH, S["zcom"])
     tau_np = np.random.default_rng(20261020).normal(0.0, 0.05, (B, 30))
-    tau = _dev(ctl, tau_np)
+    tau = to_device(ctl, tau_np)
     vprev = np.random.default_rng(20261021).normal(0.0, 1.0, (B, 30))
     t0 = 0.25
 
@@ -196,7 +187,7 @@ def test_passive_drop_is_ballistic():
     the model's own 5.4e-4 m/s^2 inconsistency x 50 ms)."""
     S = _setup()
     n, nt = 4, 50
-    ctl = _controller(n, S["zcom"])
+    ctl = make_controller(n, DT, TH, S["zcom"])
     q = np.tile(S["q0"], (n, 1)); q[:, 2] += 0.2
     v = np.zeros((n, 30))
     for i in range(1, n):
@@ -221,7 +212,7 @@ def test_zero_order_hold_loop():
     controller sees Robot::v_ of its own previous call (plant_step leaves v_prev alone), which the oracle loop restores after the helper."""
     S = _setup()
     n, nt = 4, 20
-    ctl = _controller(n, S["zcom"], warm_start=0)
+    ctl = make_controller(n, DT, TH, S["zcom"], warm_start=0)
     ctl.set_refs_stance(2.0, 2)
     q = np.tile(S["q0"], (n, 1)); q[:, 2] -= 5.0e-4              # every vertex half a millimetre in: no vertex on the knife edge z = 0
     v = perturbed_velocities(n, seed=20261022) * 0.2
@@ -267,20 +258,20 @@ def test_per_robot_grounds_and_models():
     grounds = dict(contact_k=np.array([2.0e4, 1.0e4, 3.0e4, 1.5e4]), contact_d=np.array([3.0, 1.0, 5.0, 0.0]),
                    contact_dt=np.array([3.0, 6.0, 0.0, 2.0]), contact_mu=np.array([0.7, 0.3, 1.0, 0.5]))
     idx = [5, 6, 13, 14]                                           # sliding, lifted and sticking vertices on both feet
-    ctl = _controller(n, S["zcom"])
+    ctl = make_controller(n, DT, TH, S["zcom"])
     ctl.set_model(raw)
     ctl.set_params(**grounds)
     q, v, tau = S["q"][idx], S["v"][idx], S["tau"][idx] * 0.025
-    xdot, c, flags = ctl.plant_derivative(_dev(ctl, q), _dev(ctl, v), _dev(ctl, tau))
-    cw = ctl.contact_wrench(_dev(ctl, q), _dev(ctl, v))
-    st, fs = ctl.plant_step(ctl.new_state(q, v, t=0.0), _dev(ctl, tau), 5)
+    xdot, c, flags = ctl.plant_derivative(to_device(ctl, q), to_device(ctl, v), to_device(ctl, tau))
+    cw = ctl.contact_wrench(to_device(ctl, q), to_device(ctl, v))
+    st, fs = ctl.plant_step(ctl.new_state(q, v, t=0.0), to_device(ctl, tau), 5)
     torch.cuda.synchronize()
     assert int(flags.abs().max()) == 0 and int(fs.abs().max()) == 0 and torch.equal(c, cw)
     for i in range(n):
-        one = _controller(1, S["zcom"], **{k: float(a[i]) for k, a in grounds.items()})
+        one = make_controller(1, DT, TH, S["zcom"], **{k: float(a[i]) for k, a in grounds.items()})
         one.set_model(raw[i])
-        x1, c1, _ = one.plant_derivative(_dev(one, q[i:i + 1]), _dev(one, v[i:i + 1]), _dev(one, tau[i:i + 1]))
-        s1, _ = one.plant_step(one.new_state(q[i:i + 1], v[i:i + 1], t=0.0), _dev(one, tau[i:i + 1]), 5)
+        x1, c1, _ = one.plant_derivative(to_device(one, q[i:i + 1]), to_device(one, v[i:i + 1]), to_device(one, tau[i:i + 1]))
+        s1, _ = one.plant_step(one.new_state(q[i:i + 1], v[i:i + 1], t=0.0), to_device(one, tau[i:i + 1]), 5)
         torch.cuda.synchronize()
         assert torch.equal(x1[0], xdot[i]) and torch.equal(c1[0], c[i]) and torch.equal(s1[0], st[i]), i
     assert len({float(c[i, 5] + c[i, 11]) for i in range(n)}) == n       # four different grounds
@@ -296,11 +287,11 @@ def test_flags_are_per_robot():
     raw = np.tile(nominal_links(), (n, 1, 1))
     raw[2, :, 0] *= -1.0
     raw[2, :, 4:13] *= -1.0
-    ctl, clean = _controller(n, S["zcom"]), _controller(n, S["zcom"])
+    ctl, clean = make_controller(n, DT, TH, S["zcom"]), make_controller(n, DT, TH, S["zcom"])
     ctl.set_model(raw)
     res = []
     for c in (ctl, clean):
-        q, v, tau = _dev(c, S["q"][:n]), _dev(c, S["v"][:n]), _dev(c, S["tau"][:n] * 0.025)
+        q, v, tau = to_device(c, S["q"][:n]), to_device(c, S["v"][:n]), to_device(c, S["tau"][:n] * 0.025)
         xdot, _, flags = c.plant_derivative(q, v, tau)
         st, fs = c.plant_step(c.new_state(S["q"][:n], S["v"][:n], t=0.0), tau, 3)
         torch.cuda.synchronize()
@@ -316,9 +307,9 @@ def test_flags_are_per_robot():
 def test_refusals():
     from linearmpchumanoid_amd import capi
     S = _setup()
-    ctl = _controller(B, S["zcom"])
+    ctl = make_controller(B, DT, TH, S["zcom"])
     L = capi.lib()
-    q, v, tau = _dev(ctl, S["q"]), _dev(ctl, S["v"]), _dev(ctl, S["tau"])
+    q, v, tau = to_device(ctl, S["q"]), to_device(ctl, S["v"]), to_device(ctl, S["tau"])
     st = ctl.new_state(S["q"], S["v"], t=0.0)
     st_before = st.clone()
     out = torch.zeros((B, 60), dtype=torch.float64, device=ctl.device)
@@ -346,8 +337,8 @@ def test_refusals():
     with pytest.raises(ValueError):
         ctl.plant_step(st, tau[:B - 1])
     # a plant = 0 handle never had its contact constants checked: the three calls do, before anything is enqueued
-    bad = _controller(B, S["zcom"], plant=0, contact_k=-1.0)
-    q, v, tau = _dev(bad, S["q"]), _dev(bad, S["v"]), _dev(bad, S["tau"])
+    bad = make_controller(B, DT, TH, S["zcom"], plant=0, contact_k=-1.0)
+    q, v, tau = to_device(bad, S["q"]), to_device(bad, S["v"]), to_device(bad, S["tau"])
     st = bad.new_state(S["q"], S["v"], t=0.0)
     for call in (lambda: bad.contact_wrench(q, v), lambda: bad.plant_derivative(q, v, tau), lambda: bad.plant_step(st, tau, 1), lambda: bad.plant_step(st, tau, 0)):
         with pytest.raises(capi.LmhError) as e:
@@ -356,20 +347,20 @@ def test_refusals():
     torch.cuda.synchronize()
     assert torch.equal(st, st_before)
     k = np.full(B, 2.0e4); k[7] = 0.0
-    ok = _controller(B, S["zcom"], plant=0)
+    ok = make_controller(B, DT, TH, S["zcom"], plant=0)
     ok.set_params(contact_k=k)                                     # accepted: plant = 0 checks no contact constant there
     with pytest.raises(capi.LmhError) as e:
-        ok.plant_derivative(_dev(ok, S["q"]), _dev(ok, S["v"]))
+        ok.plant_derivative(to_device(ok, S["q"]), to_device(ok, S["v"]))
     assert e.value.code == -2 and "robot 7:" in str(e.value)
     ok.set_params()
-    ok.plant_derivative(_dev(ok, S["q"]), _dev(ok, S["v"]))
+    ok.plant_derivative(to_device(ok, S["q"]), to_device(ok, S["v"]))
     torch.cuda.synchronize()
 
 
 def test_the_handle_is_untouched():
     """stand_step and a 50-tick rollout from a fixed state give the same bits before and after a burst of the three new calls."""
     S = _setup()
-    ctl = _controller(B, S["zcom"], warm_start=1)
+    ctl = make_controller(B, DT, TH, S["zcom"], warm_start=1)
     ctl.set_refs_stance(2.0, 2)
     st0 = ctl.new_state(S["q0"], S["v"] * 0.2, t=0.0)
 
@@ -382,7 +373,7 @@ def test_the_handle_is_untouched():
         return a, o1, s1, b, o2, s2
 
     before = run()
-    q, v, tau = (_dev(ctl, S[k]) for k in ("q", "v", "tau"))
+    q, v, tau = (to_device(ctl, S[k]) for k in ("q", "v", "tau"))
     for _ in range(3):
         ctl.contact_wrench(q, v)
         ctl.plant_derivative(q, v, tau)

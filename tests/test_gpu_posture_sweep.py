@@ -11,20 +11,14 @@ coefficients, single rays, a few rays of one sole edge, no contact force at all)
 Tolerances are those of test_stage_parity_single_evaluation (1e-11 model terms, TOL_REL outputs with the WEIGHT floor, 1e-7 final
 state).  The oracle against its independent numpy restatement on this draw: model terms <= 4e-15, tau / f / qdd <= 1e-9, so they leave
 the reference more than three orders of magnitude."""
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 import torch
 
 from helpers import (DH_OFFSET, SWEEP_BANDS, SWEEP_SEED, TOL_REL, WEIGHT, close, dense_terms_from_debug, oracle_system, posture_sweep, rel_err,
-                     sincos_quadrants, vec_err)
+                     run_probe, sincos_quadrants, start_posture, vec_err)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DT, TH = 1e-3, 0.016
 B_EVAL, B_ROLL, TICKS = 32, 8, 40
 SIDES = (0x0F0F, 0xF0F0, 0x00FF, 0xFF00)
@@ -38,7 +32,7 @@ def consts():
     o = oracle_system(DT, TH)
     K = o.gain_row()
     Px, _ = o.mpc_mats()
-    return dict(zcom=o.zcom, q0=o.robot()["q"].copy(), kpx=K @ Px)
+    return dict(start_posture(o), kpx=K @ Px)
 
 
 def eval_batch(q0, band):
@@ -247,15 +241,6 @@ print(json.dumps({"flags": st[:, 2].tolist(), "rounds": st[:, 1].tolist(), "mask
 """
 
 
-def _run_probe(code, variant, timeout=600):
-    env = {k: v for k, v in os.environ.items() if k not in ("LMH_VARIANT", "LMH_DIAG")}
-    if variant:
-        env["LMH_VARIANT"] = variant
-    r = subprocess.run([sys.executable, "-c", code], env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
-
-
 def test_shipped_and_noedge_builds_agree_on_the_small_edge_subsets(consts, tmp_path):
     """edge_bound_row takes any non-empty subset of a sole edge for edge contact, a single ray included, and leaves rejection to
     kinv_compute's pivot threshold.  All three bands through the shipped library and through the checker build `noedge` (register /
@@ -270,7 +255,7 @@ def test_shipped_and_noedge_builds_agree_on_the_small_edge_subsets(consts, tmp_p
     outs, res = {}, {}
     for variant in ("", "noedge"):
         path = str(tmp_path / f"out_{variant or 'shipped'}.npy")
-        res[variant] = _run_probe(_PROBE.replace("sys.argv[1]", repr(path)).replace("sys.argv[2]", repr(spath)), variant)
+        res[variant] = run_probe(_PROBE.replace("sys.argv[1]", repr(path)).replace("sys.argv[2]", repr(spath)), variant, timeout=600)
         outs[variant] = np.load(path)
     a, b = outs[""], outs["noedge"]
     assert all(f == 0 for f in res[""]["flags"]) and all(f == 0 for f in res["noedge"]["flags"]), (res[""]["flags"], res["noedge"]["flags"])

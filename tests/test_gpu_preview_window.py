@@ -11,16 +11,15 @@ import pytest
 import torch
 
 import preview_cases as pc
-from helpers import TOL_REL, WEIGHT, close, rel_err
+from helpers import TOL_REL, WEIGHT, close, horizon_controller, rel_err
 
 pytestmark = pytest.mark.gpu
 MODE_IDS = list(pc.MODES)
 
 
-def make_controller(B, N, mode, zcom, **kw):
-    from linearmpchumanoid_amd.controller import BatchedController, default_config
+def mode_controller(B, N, mode, zcom, **kw):
     m = pc.MODES[mode]
-    ctl = BatchedController(B, default_config(dt=pc.DT, time_horizon=pc.horizon_time(N, m["mpc_dt"]), z_com=zcom, mpc_dt=m["mpc_dt"], **kw))
+    ctl = horizon_controller(B, N, zcom, m["mpc_dt"], pc.DT, **kw)
     assert ctl.N == N
     zx, zy, ph = pc.zmp_arrays(m["n"])
     ctl.set_refs(zx, zy, ph)
@@ -97,7 +96,7 @@ def test_gain_row_at_every_horizon(nao, first, mode):
 def test_single_evaluation_on_a_varying_window(nao, N, mode):
     m = pc.MODES[mode]
     v = pc.velocities(pc.B_EVAL)
-    ctl = make_controller(pc.B_EVAL, N, mode, nao["zcom"], warm_start=0)
+    ctl = mode_controller(pc.B_EVAL, N, mode, nao["zcom"], warm_start=0)
     st = ctl.new_state(nao["q0"], v, t=m["t"])
     out, status = ctl.stand_step(st)
     torch.cuda.synchronize()
@@ -124,7 +123,7 @@ def test_short_rollout_on_a_varying_window(nao, N, pushed, mode):
     N = 45 case has active bounds (test_preview_cases.py), so the K_f^-1 block that starts where the N = 45 gain record ends is live."""
     nt = pc.ROLLOUT_TICKS
     v = pc.pushed_velocities(pc.B_EVAL) if pushed else pc.velocities(pc.B_EVAL)
-    ctl = make_controller(pc.B_EVAL, N, mode, nao["zcom"], warm_start=1)
+    ctl = mode_controller(pc.B_EVAL, N, mode, nao["zcom"], warm_start=1)
     st = ctl.new_state(nao["q0"], v, t=0.0)
     out, status, log = ctl.rollout(st, nt, log=True)
     torch.cuda.synchronize()
@@ -143,7 +142,7 @@ def test_per_robot_gain_rows_across_the_seam(nao, N, mode):
     B = len(pc.ZCOMS)
     v = pc.velocities(B)
     worst = 0.0
-    ctl = make_controller(B, N, mode, nao["zcom"], warm_start=0)
+    ctl = mode_controller(B, N, mode, nao["zcom"], warm_start=0)
     ctl.set_zcom(np.array(pc.ZCOMS))
     st = ctl.new_state(nao["q0"], v, t=m["t"])
     out, status = ctl.stand_step(st)
@@ -154,7 +153,7 @@ def test_per_robot_gain_rows_across_the_seam(nao, N, mode):
     for i, o in enumerate(oracles):
         e = o.eval(nao["q0"], v[i], m["t"])
         worst = max(worst, _check_eval(out[i], status[i], o, e, mode, e["k"]))
-    ctl = make_controller(B, N, mode, nao["zcom"], warm_start=1)
+    ctl = mode_controller(B, N, mode, nao["zcom"], warm_start=1)
     ctl.set_zcom(np.array(pc.ZCOMS))
     st = ctl.new_state(nao["q0"], v, t=0.0)
     out, status, log = ctl.rollout(st, pc.ZCOM_TICKS, log=True)
@@ -173,7 +172,7 @@ def test_clamped_window_values(nao, N, mode, where, t):
     padded by repeating the end sample and the clock of an in-range sample with the same window (preview_cases.clamp_oracle)."""
     from linearmpchumanoid_amd import capi
     v = pc.velocities(pc.B_EVAL)
-    ctl = make_controller(pc.B_EVAL, N, mode, nao["zcom"], warm_start=0)
+    ctl = mode_controller(pc.B_EVAL, N, mode, nao["zcom"], warm_start=0)
     st = ctl.new_state(nao["q0"], v, t=t)
     out, status = ctl.stand_step(st)
     torch.cuda.synchronize()

@@ -3,20 +3,16 @@ launch at every push tick and adds dv to state[:, 30:60] itself, launch splittin
 the CPU oracle pushed the same way.  Scenarios and the split-launch host: tests/push_cases.py.  "The same computation" means
 bit-identical (compared as bytes); parity with the oracle is helpers.close's 1e-6 relative on
 tau / f and on the final state, k bit-exact."""
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import WEIGHT, close, vec_err
+from helpers import WEIGHT, close, run_probe, vec_err
 from push_cases import WALK_B, WALK_NT, Run, bits_differ, in_kernel_against_split, walking_controller, walking_pushes
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 _CHILD = r"""
 import json, os, sys
@@ -62,11 +58,7 @@ def test_in_kernel_pushes_equal_split_launches_bit_for_bit(build, precision, pla
     else:
         from linearmpchumanoid_amd import build as hipbuild
         assert os.path.exists(hipbuild.build_variant("poison", ["-DLMH_POISON"]))
-        env = {k: v for k, v in os.environ.items() if k not in ("LMH_VARIANT", "LMH_DIAG")}
-        env["LMH_VARIANT"] = "poison"
-        r = subprocess.run([sys.executable, "-c", _CHILD, str(precision), str(plant)], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
-        assert r.returncode == 0, r.stderr[-2000:]
-        res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        res = run_probe(_CHILD, "poison", timeout=900, args=(str(precision), str(plant)))
         assert res["build_flags"] & 1 == 1, res
     check_in_kernel_result(res, precision, plant)
 

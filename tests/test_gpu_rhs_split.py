@@ -6,14 +6,12 @@ The evaluation is compared with the C oracle at the tolerances of the stage-pari
 `noedge` (register / general route on the edge sets)."""
 import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import TOL_REL, WEIGHT, close, rel_err, vec_err
+from helpers import TOL_REL, WEIGHT, close, rel_err, run_probe, vec_err
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -93,15 +91,6 @@ print(json.dumps({"flags": s[:, 2].tolist(), "rounds": s[:, 1].tolist(), "masks"
 """
 
 
-def _run_probe(code, variant, timeout=600):
-    env = {k: v for k, v in os.environ.items() if k not in ("LMH_VARIANT", "LMH_DIAG")}
-    if variant:
-        env["LMH_VARIANT"] = variant
-    r = subprocess.run([sys.executable, "-c", code], env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
-
-
 def test_shipped_and_noedge_builds_agree_on_the_pushed_robots(tmp_path):
     """The edge-contact push-through (shipped) and the register / general route (`noedge`) on the same evaluations: same rounds, same
     final sets, no flags, results equal to rounding."""
@@ -112,7 +101,7 @@ def test_shipped_and_noedge_builds_agree_on_the_pushed_robots(tmp_path):
     outs, res = {}, {}
     for variant in ("", "noedge"):
         path = str(tmp_path / f"out_{variant or 'shipped'}.npy")
-        res[variant] = _run_probe(_PROBE.replace("sys.argv[1]", repr(path)).replace("sys.argv[2]", repr(vpath)), variant)
+        res[variant] = run_probe(_PROBE.replace("sys.argv[1]", repr(path)).replace("sys.argv[2]", repr(vpath)), variant, timeout=600)
         outs[variant] = np.load(path)
     a, b = outs[""], outs["noedge"]
     assert all(f == 0 for f in res[""]["flags"]) and all(f == 0 for f in res["noedge"]["flags"])

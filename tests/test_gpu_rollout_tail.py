@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import SWEEP_BANDS, TOL_REL, WEIGHT, close, oracle_system, perturbed_velocities, posture_sweep, vec_err
+from helpers import SWEEP_BANDS, TOL_REL, WEIGHT, close, make_controller, oracle_system, perturbed_velocities, posture_sweep, start_posture, vec_err
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(not torch.cuda.is_available(), reason="needs a GPU")]
 DT, TH = 1e-3, 0.016
@@ -18,13 +18,7 @@ CHUNK = 250                      # LMH_CHUNK_TICKS of the shipped build
 
 @pytest.fixture(scope="module")
 def consts():
-    o = oracle_system(DT, TH)
-    return dict(zcom=o.zcom, q0=o.robot()["q"].copy())
-
-
-def _controller(B, zcom, **kw):
-    from linearmpchumanoid_amd.controller import BatchedController, default_config
-    return BatchedController(B, default_config(dt=DT, time_horizon=TH, z_com=zcom, **kw))
+    return start_posture(oracle_system(DT, TH))
 
 
 def _xdot(x, qpp):
@@ -48,7 +42,7 @@ def test_short_rollouts_equal_host_rk4_over_plain_evaluations_accelerations_incl
     state of the last tick.  The tolerances are those of the one-tick comparison in tests/test_gpu_posture_sweep.py; every robot counts."""
     q, v, vp = posture_sweep(consts["q0"], B_ROLL, band)
     B = q.shape[0]
-    ctl = _controller(B, consts["zcom"], warm_start=0)
+    ctl = make_controller(B, DT, TH, consts["zcom"], warm_start=0)
     ctl.set_refs_stance(2.0, 2)
     st = ctl.new_state(q, v, t=0.0, v_prev=vp)
     out, status, log = ctl.rollout(st, ticks, log=True)
@@ -98,7 +92,7 @@ def test_launch_and_chunk_ends_publish_what_single_tick_launches_publish(consts,
     and status ([0] k and [3] active set of the last tick, [1] the maximum and [2] the OR over the launches)."""
     B = 96
     v = perturbed_velocities(B, seed=4242)
-    ctl = _controller(B, consts["zcom"], warm_start=1)
+    ctl = make_controller(B, DT, TH, consts["zcom"], warm_start=1)
     ctl.set_refs_stance(2.0, 2)
     st = ctl.new_state(consts["q0"], v, t=0.0)
     out, status, _ = ctl.rollout(st, ticks)
@@ -124,7 +118,7 @@ def test_non_finite_state_in_a_rollout_is_flagged_and_stays_with_its_robot(const
     """The rollout form of test_non_finite_state_is_flagged_not_propagated_silently (which goes through the evaluation kernel): three
     robots, the middle one with a NaN joint velocity, three ticks.  The rollout's guard tests the recovery's registers."""
     from linearmpchumanoid_amd import capi
-    ctl = _controller(3, consts["zcom"])
+    ctl = make_controller(3, DT, TH, consts["zcom"])
     ctl.set_refs_stance(2.0, 2)
     v = np.zeros((3, 30)); v[1, 7] = np.nan
     st = ctl.new_state(consts["q0"], v, t=0.0)

@@ -12,22 +12,11 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import TOL_REL, WEIGHT, close, close_on, oracle_system, perturbed_velocities, rel_err, vec_err
+from helpers import (TOL_REL, WEIGHT, cfg2, close, close_on, make_controller, oracle_system, perturbed_velocities, rel_err, run_bench,  # noqa: F401
+                     vec_err)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def make_controller(B, dt, th, zcom, **kw):
-    from linearmpchumanoid_amd.controller import BatchedController, default_config
-    return BatchedController(B, default_config(dt=dt, time_horizon=th, z_com=zcom, **kw))
-
-
-@pytest.fixture(scope="module")
-def cfg2():
-    o = oracle_system(1e-3, 0.016)
-    return dict(dt=1e-3, th=0.016, zcom=o.zcom, q0=o.robot()["q"].copy())
-
 
 # ------------------------------------------------------------------------------- (a) the regime bench.py --config 2 times
 def test_config2_benched_regime_against_oracle(cfg2):
@@ -453,31 +442,21 @@ def test_summary_kernel_matches_the_host_form(cfg2):
     assert (s_host[:, 14] == torch.tensor([bin(int(x) & 0xFFFFFFFF).count("1") for x in status.cpu()[:, 3]], dtype=torch.float64)).all()
 
 
-def _run_bench(argv, env_extra=None, timeout=900):
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    env.update(env_extra or {})
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, env=env, capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stderr[-2000:]
-    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
-    assert len(lines) == 1, r.stdout[-2000:]
-    return json.loads(lines[0])
-
-
 def test_bench_two_ranks_through_the_gpus_flag(tmp_path):
     """`bench.py --gpus 2` (the command the driver runs for the scaling table) starts two ranks by itself; here both share
     card 0 and talk over gloo (a one-GPU box).  n_gpus, the gathered summary (written through lmh_write_summary, read back
     through lmh_read_summary) and the per-rank workloads (instance ids continue across ranks) are checked."""
     from linearmpchumanoid_amd.controller import BatchedController
     p = tmp_path / "run.lmhsum"
-    res = _run_bench(["--gpus", "2", "--backend", "gloo", "--instances", "256", "--steps", "2", "--warmup", "1", "--ticks", "8",
-                      "--summary-out", str(p)], {"LMH_BENCH_DEVICE": "0"})
+    res = run_bench(["--gpus", "2", "--backend", "gloo", "--instances", "256", "--steps", "2", "--warmup", "1", "--ticks", "8",
+                     "--summary-out", str(p)], {"LMH_BENCH_DEVICE": "0"})
     assert res["n_gpus"] == 2 and res["summary_rows_gathered"] == 512 and res["instances_flagged"] == 0
     assert res["config"]["baseline_config"] == 4 and res["scaling"] == "weak"
     s, dt = BatchedController.read_summary(p)
     assert s.shape == (512, 16) and dt == 1e-3
     assert np.allclose(s[:, 6], 24 * 1e-3) and (s[:, 13] == 0).all() and (s[:, 8] > 30).all()     # t, flags, sum f_z ~ m g
-    one = _run_bench(["--config", "4", "--instances", "512", "--steps", "2", "--warmup", "1", "--ticks", "8", "--no-cpu-baseline",
-                      "--summary-out", str(tmp_path / "one.lmhsum")])
+    one = run_bench(["--config", "4", "--instances", "512", "--steps", "2", "--warmup", "1", "--ticks", "8", "--no-cpu-baseline",
+                     "--summary-out", str(tmp_path / "one.lmhsum")])
     s1, _ = BatchedController.read_summary(tmp_path / "one.lmhsum")
     assert np.array_equal(s1, s)                                    # sharding does not change any robot's result
 
@@ -507,7 +486,7 @@ def test_bench_under_torchrun_as_the_driver_launches_it():
 def test_bench_default_line_shape():
     """The JSON contract on a reduced workload: config 3 keys, binding roofline first, HBM / MFMA objects beside it, CPU
     baseline on the same workload with the last tick compared against the GPU."""
-    res = _run_bench(["--instances", "128", "--steps", "2", "--warmup", "1", "--ticks", "10", "--cpu-seconds", "4", "--full"])
+    res = run_bench(["--instances", "128", "--steps", "2", "--warmup", "1", "--ticks", "10", "--cpu-seconds", "4", "--full"])
     assert res["n_gpus"] == 1 and res["config"]["baseline_config"] == 3 and "walking" in res["config"]["workload"]
     rf = res["roofline"]
     assert rf["bound"] == "fp64-valu" and rf["unit"] == "TFLOP/s" and abs(rf["frac"] - rf["achieved"] / rf["peak"]) < 1e-12
@@ -519,7 +498,7 @@ def test_bench_default_line_shape():
     assert cb["parity_vs_gpu_last_tick_max_rel"] < 1e-6
     assert cb["literal_2wbc_value"] and cb["literal_2wbc_value"] < cb["value"] * 1.05
     # the informational PCIe-inclusive mode runs the same rollouts (and keeps the CPU leg's inputs intact)
-    hio = _run_bench(["--instances", "128", "--steps", "3", "--warmup", "1", "--ticks", "10", "--cpu-seconds", "3", "--host-io", "--full"])
+    hio = run_bench(["--instances", "128", "--steps", "3", "--warmup", "1", "--ticks", "10", "--cpu-seconds", "3", "--host-io", "--full"])
     assert hio["config"]["host_io_over_pcie"] is True and hio["instances_flagged"] == 0 and hio["cpu_baseline"]["value"] > 0
     assert hio["cpu_baseline"]["parity_vs_gpu_last_tick_max_rel"] < 1e-6
 

@@ -4,16 +4,16 @@ products at the current state, the dynamic robot -> workgroup assignment of the 
 Same rules as the other GPU files: HIP path through the C ABI against the CPU oracle; relative 1e-6 on tau / f (helpers.close:
 max|a - b| / max|b| of the same vector, no absolute floor), bit-exact k.
 """
-import json
 import os
-import subprocess
 import sys
+from functools import partial
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import TOL_REL, WEIGHT, close, close_on, perturbed_velocities, vec_err
+import helpers
+from helpers import TOL_REL, WEIGHT, close, close_on, horizon_controller, horizon_time, perturbed_velocities, run_bench, run_probe, vec_err
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -21,18 +21,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DT, MPC_DT = 1e-3, 1e-2
 
 
-def horizon_time(N, mpc_dt):
-    return N * mpc_dt + 1e-9                                       # int(th / mpc_dt) == N whatever the rounding of the quotient
-
-
-def make_controller(B, N, zcom, mpc_dt=MPC_DT, **kw):
-    from linearmpchumanoid_amd.controller import BatchedController, default_config
-    return BatchedController(B, default_config(dt=DT, time_horizon=horizon_time(N, mpc_dt), z_com=zcom, mpc_dt=mpc_dt, **kw))
-
-
-def make_oracle(N, sim_time, mpc_dt=MPC_DT):
-    from oracle.pyoracle import Oracle
-    return Oracle(sim_time=sim_time, dt=mpc_dt, horizon_time=horizon_time(N, mpc_dt), do_ik=True)
+make_controller = partial(horizon_controller, mpc_dt=MPC_DT, dt=DT)
+make_oracle = partial(helpers.make_oracle, mpc_dt=MPC_DT)
 
 
 @pytest.fixture(scope="module")
@@ -413,24 +403,15 @@ def test_chunked_work_units_equal_a_sequence_of_short_launches(nao):
 
 
 # ------------------------------------------------------------------------------- bench.py: flag accounting, precision 2, config 5
-def _run_bench(argv, expect_rc=0, timeout=900):
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, env=env, capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == expect_rc, (r.returncode, r.stderr[-2000:])
-    lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{"metric"')]
-    assert len(lines) == 1, r.stdout[-2000:]
-    return json.loads(lines[0])
-
-
 def test_bench_counts_flags_of_every_launch_not_only_the_last():
     """the rollout kernel overwrites status[:, 2] per launch, so a flag raised in a middle launch used to vanish from the
     bench line.  Jump schedule in five launches of 200 ticks with the QP round cap at 3: the landing (launch 3, ticks 400..600) needs
     more rounds -> LMH_FLAG_QP_MAXITER there, the settled last launch is clean: exit code 3 and instances_flagged > 0 although
     the last launch alone shows none.  The same run without the cap is clean (exit code 0)."""
     argv = ["--config", "5", "--instances", "64", "--ticks", "200", "--warmup", "0", "--steps", "8", "--reset-every", "0", "--no-cpu-baseline"]
-    res = _run_bench(argv + ["--max-qp-iters", "3"], expect_rc=3)
+    res = run_bench(argv + ["--max-qp-iters", "3"], expect_rc=3)
     assert res["instances_flagged"] > 0 and res["instances_flagged_in_last_launch"] == 0
-    ok = _run_bench(argv)
+    ok = run_bench(argv)
     assert ok["instances_flagged"] == 0 and ok["config"]["baseline_config"] == 5 and ok["config"]["rollout_restarts"] == 0
 
 
@@ -438,9 +419,9 @@ def test_bench_precision_2_and_config5_lines():
     """`--precision 2` (LMH_PRECISION_FP32) prints its line (the dtype table used to raise KeyError after the timed run) and does not
     count the informational LMH_FLAG_QP_FP64_ROUTE as a failure; `--config 5` is the entry point of BASELINE configs[4] (one step = one
     jump from the initial state, restarted per step and reported so)."""
-    r2 = _run_bench(["--instances", "128", "--steps", "2", "--warmup", "1", "--ticks", "10", "--no-cpu-baseline", "--precision", "2"])
+    r2 = run_bench(["--instances", "128", "--steps", "2", "--warmup", "1", "--ticks", "10", "--no-cpu-baseline", "--precision", "2"])
     assert r2["dtype"].startswith("f32") and r2["instances_flagged"] == 0 and r2["instances_fp64_route"] >= 0
-    r5 = _run_bench(["--config", "5", "--instances", "256", "--steps", "2", "--warmup", "1", "--ticks", "700", "--cpu-seconds", "4", "--full"])
+    r5 = run_bench(["--config", "5", "--instances", "256", "--steps", "2", "--warmup", "1", "--ticks", "700", "--cpu-seconds", "4", "--full"])
     assert r5["config"]["rollout_restarts"] == 2 and "jump" in r5["config"]["workload"] and r5["instances_flagged"] == 0
     assert r5["config"]["preview_s"] == pytest.approx(0.48) and r5["cpu_baseline"]["parity_vs_gpu_last_tick_max_rel"] < 1e-6
 
@@ -452,8 +433,8 @@ def test_bench_config5_on_two_ranks_over_gloo():
     env_dev = os.environ.get("LMH_BENCH_DEVICE")
     os.environ["LMH_BENCH_DEVICE"] = "0"
     try:
-        res = _run_bench(["--gpus", "2", "--backend", "gloo", "--config", "5", "--instances", "128", "--steps", "2", "--warmup", "1", "--ticks", "700",
-                          "--no-cpu-baseline"])
+        res = run_bench(["--gpus", "2", "--backend", "gloo", "--config", "5", "--instances", "128", "--steps", "2", "--warmup", "1", "--ticks", "700",
+                         "--no-cpu-baseline"])
     finally:
         if env_dev is None: os.environ.pop("LMH_BENCH_DEVICE", None)
         else: os.environ["LMH_BENCH_DEVICE"] = env_dev
@@ -535,11 +516,6 @@ def test_results_do_not_depend_on_uninitialised_lds():
     assert os.path.exists(so)
     res = {}
     for variant in ("", "poison"):
-        env = {k: v for k, v in os.environ.items() if k not in ("LMH_VARIANT", "LMH_DIAG")}
-        if variant:
-            env["LMH_VARIANT"] = variant
-        r = subprocess.run([sys.executable, "-c", _POISON_PROBE], env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
-        assert r.returncode == 0, r.stderr[-2000:]
-        res[variant] = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        res[variant] = run_probe(_POISON_PROBE, variant, timeout=600)
     assert res[""]["flags"] == 0 and res["poison"]["flags"] == 0, res
     assert res[""]["sha"] == res["poison"]["sha"], res

@@ -11,20 +11,11 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import WEIGHT, close, perturbed_velocities, vec_err
+from helpers import WEIGHT, close, perturbed_velocities, run_probe, vec_err
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DT = 1e-3
-
-
-def _run_probe(code, variant, timeout=900):
-    env = {k: v for k, v in os.environ.items() if k not in ("LMH_VARIANT", "LMH_DIAG")}
-    if variant:
-        env["LMH_VARIANT"] = variant
-    r = subprocess.run([sys.executable, "-c", code], env=env, cwd=ROOT, capture_output=True, text=True, timeout=timeout)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
 
 
 # ------------------------------------------------------------------------------- an incomplete rollout is loud
@@ -83,8 +74,8 @@ def test_incomplete_rollout_is_loud_and_leaves_a_clean_slot():
     from linearmpchumanoid_amd import build as hipbuild
     from linearmpchumanoid_amd import capi
     hipbuild.build_variant("qfault")
-    good = _run_probe(_QFAULT_PROBE, "")
-    bad = _run_probe(_QFAULT_PROBE, "qfault")
+    good = run_probe(_QFAULT_PROBE, "", timeout=900)
+    bad = run_probe(_QFAULT_PROBE, "qfault", timeout=900)
     assert good["build_flags"] == 0 and bad["build_flags"] == 4 | 32, (good["build_flags"], bad["build_flags"])
     assert good["sync_codes"] == [0, 0] and all(f == 0 for f in good["flags"]) and all(t == 620 for t in good["ticks"])
     assert bad["sync_codes"] == [capi.ERR_UNFINISHED, 0], bad["sync_codes"]
@@ -111,7 +102,7 @@ def test_poison_build_really_is_the_poison_build():
             "print(json.dumps({'flags': L.lmh_debug_build_flags(), 'so': capi.SO_PATH}))\n")
     from linearmpchumanoid_amd import build as hipbuild
     hipbuild.build_variant("poison")
-    a, b = _run_probe(code, ""), _run_probe(code, "poison")
+    a, b = run_probe(code, "", timeout=900), run_probe(code, "poison", timeout=900)
     assert a["flags"] == 0 and a["so"].endswith("liblmh_hip.so")
     assert b["flags"] == 1 and b["so"].endswith("liblmh_hip_var_poison.so")
 
@@ -243,7 +234,7 @@ def test_edge_contact_pushthrough_against_the_other_routes_and_the_oracle(tmp_pa
     for variant in ("", "noedge"):
         path = str(tmp_path / f"edge_{variant or 'shipped'}.npy")
         code = _EDGE_PROBE.replace("sys.argv[1]", repr(path))
-        res[variant] = _run_probe(code, variant)
+        res[variant] = run_probe(code, variant, timeout=900)
         logs[variant] = np.load(path)
         assert res[variant]["flags"] == 0
     # the gait met edge sets: some foot's free mask lies on one side of the sole (vertices 0, 2 | 1, 3 | 0, 1 | 2, 3) with at least six members
@@ -321,7 +312,7 @@ def test_edge_contact_on_every_side_of_the_sole_against_the_general_route_and_th
     outs, res = {}, {}
     for variant in ("", "noedge"):
         path = str(tmp_path / f"sides_{variant or 'shipped'}.npy")
-        res[variant] = _run_probe(_EDGE_SIDES_PROBE.replace("sys.argv[1]", repr(path)).replace("sys.argv[2]", repr(vpath)), variant)
+        res[variant] = run_probe(_EDGE_SIDES_PROBE.replace("sys.argv[1]", repr(path)).replace("sys.argv[2]", repr(vpath)), variant, timeout=900)
         outs[variant] = np.load(path)
     a, b = outs[""], outs["noedge"]
     assert all(f == 0 for f in res[""]["flags"]) and all(f == 0 for f in res["noedge"]["flags"])

@@ -13,21 +13,12 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import WEIGHT, close_on, dense_terms_from_debug, oracle_system, posture_sweep, rel_err
+from helpers import WEIGHT, close_on, dense_terms_from_debug, make_controller, oracle_system, posture_sweep, rel_err, to_device
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DT, TH = 1e-3, 0.016
 B = 16
-
-
-def _controller(n, zcom, **kw):
-    from linearmpchumanoid_amd.controller import BatchedController, default_config
-    return BatchedController(n, default_config(dt=DT, time_horizon=TH, z_com=zcom, **kw))
-
-
-def _dev(ctl, a):
-    return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(ctl.device)
 
 
 def _oracle_terms(q, v, raw_links=None):
@@ -83,8 +74,8 @@ def _check_terms(rec, r, v, mass, worst, tag):
 
 def test_terms_parity():
     S = _setup()
-    ctl = _controller(B, S["zcom"])
-    rec = ctl.terms(_dev(ctl, S["q"]), _dev(ctl, S["v"]))
+    ctl = make_controller(B, DT, TH, S["zcom"])
+    rec = ctl.terms(to_device(ctl, S["q"]), to_device(ctl, S["v"]))
     torch.cuda.synchronize()
     rec = rec.cpu().numpy()
     masses = ctl.mass()
@@ -94,8 +85,8 @@ def test_terms_parity():
     print("\nterms parity, band 1.0: " + ", ".join("%s %.2e" % kv for kv in sorted(worst.items())))
     assert not bad, bad[:12]
     # v = None is v = 0: the velocity products vanish from C (gravity stays), Cg, AGpqp, Jpqp and the momenta are zero
-    z = ctl.terms(_dev(ctl, S["q"]))
-    z0 = ctl.terms(_dev(ctl, S["q"]), _dev(ctl, np.zeros((B, 30))))
+    z = ctl.terms(to_device(ctl, S["q"]))
+    z0 = ctl.terms(to_device(ctl, S["q"]), to_device(ctl, np.zeros((B, 30))))
     torch.cuda.synchronize()
     assert torch.equal(z, z0)
     sz = ctl.split_terms(z.cpu().numpy())
@@ -113,10 +104,10 @@ def test_terms_with_per_robot_models():
     rng = np.random.default_rng(20260004)
     raw[:, :, 0] *= rng.uniform(0.9, 1.1, (n, 28))
     raw[:, :, 1:4] += rng.uniform(-5e-3, 5e-3, (n, 28, 3)) * (raw[:, :, 0:1] > 0)
-    ctl = _controller(n, S["zcom"])
+    ctl = make_controller(n, DT, TH, S["zcom"])
     ctl.set_model(raw)
     masses = ctl.mass()
-    rec = ctl.terms(_dev(ctl, S["q"][:n]), _dev(ctl, S["v"][:n]))
+    rec = ctl.terms(to_device(ctl, S["q"][:n]), to_device(ctl, S["v"][:n]))
     torch.cuda.synchronize()
     rec = rec.cpu().numpy()
     worst, bad = {}, []
@@ -133,11 +124,11 @@ def test_terms_equal_the_product_path():
     """lmh_eval_debug on states whose v_prev equals v dumps the same M, C, J, AG (the two-path schedules differ: no bit equality asked)."""
     from linearmpchumanoid_amd.controller import unpack_debug
     S = _setup()
-    ctl = _controller(B, S["zcom"], warm_start=0)
+    ctl = make_controller(B, DT, TH, S["zcom"], warm_start=0)
     ctl.set_refs_stance(2.0, 2)
     st = ctl.new_state(S["q"], S["v"], t=0.0, v_prev=S["v"])
     _, _, dbg = ctl.stand_step(st, debug=True)
-    rec = ctl.terms(_dev(ctl, S["q"]), _dev(ctl, S["v"]))
+    rec = ctl.terms(to_device(ctl, S["q"]), to_device(ctl, S["v"]))
     torch.cuda.synchronize()
     dbg, rec = dbg.cpu().numpy(), rec.cpu().numpy()
     worst = {}
@@ -153,8 +144,8 @@ def test_terms_equal_the_product_path():
 
 def test_inverse_dynamics():
     S = _setup()
-    ctl = _controller(B, S["zcom"])
-    q, v, qdd, w = (_dev(ctl, S[k]) for k in ("q", "v", "qdd", "w"))
+    ctl = make_controller(B, DT, TH, S["zcom"])
+    q, v, qdd, w = (to_device(ctl, S[k]) for k in ("q", "v", "qdd", "w"))
     tau = ctl.inverse_dynamics(q, v, qdd, w)
     tau_now = ctl.inverse_dynamics(q, v, qdd)
     tau_w0 = ctl.inverse_dynamics(q, v, qdd, torch.zeros_like(w))
@@ -187,8 +178,8 @@ def _check_forward(x, i, S, worst):
 
 def test_forward_dynamics():
     S = _setup()
-    ctl = _controller(B, S["zcom"])
-    q, v, qdd, w, tau = (_dev(ctl, S[k]) for k in ("q", "v", "qdd", "w", "tau"))
+    ctl = make_controller(B, DT, TH, S["zcom"])
+    q, v, qdd, w, tau = (to_device(ctl, S[k]) for k in ("q", "v", "qdd", "w", "tau"))
     x, flags = ctl.forward_dynamics(q, v, tau, w)
     x2, flags2 = ctl.forward_dynamics(q, v, ctl.inverse_dynamics(q, v, qdd, w), w)      # round trip on the device alone
     torch.cuda.synchronize()
@@ -214,9 +205,9 @@ def test_flags_are_per_robot():
     raw = np.tile(nominal_links(), (n, 1, 1))
     raw[2, :, 0] *= -1.0
     raw[2, :, 4:13] *= -1.0
-    ctl = _controller(n, S["zcom"])
+    ctl = make_controller(n, DT, TH, S["zcom"])
     ctl.set_model(raw)
-    x, flags = ctl.forward_dynamics(_dev(ctl, S["q"][:n]), _dev(ctl, S["v"][:n]), _dev(ctl, S["tau"][:n]), _dev(ctl, S["w"][:n]))
+    x, flags = ctl.forward_dynamics(to_device(ctl, S["q"][:n]), to_device(ctl, S["v"][:n]), to_device(ctl, S["tau"][:n]), to_device(ctl, S["w"][:n]))
     torch.cuda.synchronize()
     flags, x = flags.cpu().numpy(), x.cpu().numpy()
     assert flags[2] & capi.FLAG_NOT_SPD
@@ -229,7 +220,7 @@ def test_flags_are_per_robot():
 def test_the_handle_is_untouched():
     """stand_step and a 50-tick rollout from a fixed state give the same bits before and after a burst of the three new calls."""
     S = _setup()
-    ctl = _controller(B, S["zcom"], warm_start=1)
+    ctl = make_controller(B, DT, TH, S["zcom"], warm_start=1)
     ctl.set_refs_stance(2.0, 2)
     st0 = ctl.new_state(S["q0"], S["v"] * 0.2, t=0.0)
 
@@ -242,7 +233,7 @@ def test_the_handle_is_untouched():
         return a, o1, s1, b, o2, s2
 
     before = run()
-    q, v, qdd, w = (_dev(ctl, S[k]) for k in ("q", "v", "qdd", "w"))
+    q, v, qdd, w = (to_device(ctl, S[k]) for k in ("q", "v", "qdd", "w"))
     for _ in range(3):
         ctl.terms(q, v)
         tau = ctl.inverse_dynamics(q, v, qdd, w)
@@ -256,9 +247,9 @@ def test_the_handle_is_untouched():
 def test_refusals():
     from linearmpchumanoid_amd import capi
     S = _setup()
-    ctl = _controller(B, S["zcom"])
+    ctl = make_controller(B, DT, TH, S["zcom"])
     L = capi.lib()
-    q, v, w = _dev(ctl, S["q"]), _dev(ctl, S["v"]), _dev(ctl, S["w"])
+    q, v, w = to_device(ctl, S["q"]), to_device(ctl, S["v"]), to_device(ctl, S["w"])
     out = torch.zeros((B, capi.TERMS_STRIDE), dtype=torch.float64, device=ctl.device)
     p = lambda t: C.c_void_p(t.data_ptr())
     for rc in (L.lmh_terms(ctl._h, None, p(v), p(out), None), L.lmh_terms(ctl._h, p(q), p(v), None, None),
@@ -340,7 +331,7 @@ def test_shim_dynamics_on_the_gpu(tmp_path):
         got[name] = np.array([float(x) for x in lines[k + 1:k + 1 + n]]).reshape(int(r), int(c))
         k += 1 + n
     ctl = BatchedController(1, default_config())                  # the shim's set-up handle: default configuration, nominal model
-    rec = ctl.terms(_dev(ctl, q[None, :]), _dev(ctl, v[None, :]))
+    rec = ctl.terms(to_device(ctl, q[None, :]), to_device(ctl, v[None, :]))
     torch.cuda.synchronize()
     s = ctl.split_terms(rec.cpu().numpy()[0])
     assert got["M"].shape == (30, 30) and got["AG"].shape == (6, 30) and got["C"].shape == (30, 1) and got["T"].shape == (28, 16)

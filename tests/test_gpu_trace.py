@@ -2,22 +2,18 @@
 sample is what lmh_rollout of that many ticks would have left, so the reference is a second handle cut into plain launches of `every`
 ticks (tests/trace_cases.py) -- a sequence the chunk and parity tests already pin against the oracle -- and "equal" means equal as
 bytes, all 180 doubles of every sample.  Parity with the CPU oracle itself is helpers.close's 1e-6 relative, k exact."""
-import json
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from helpers import WEIGHT, close, vec_err
+from helpers import WEIGHT, close, run_probe, vec_err
 from push_cases import bits_differ, walking_controller
 from trace_cases import (ONLY_TICK_7, SPLIT_CASES, TRACE_B, TRACE_NT, UNPUSHED, cold_walking_controller, first_difference, push_schedule,
                          same_bytes, split_trace, trace_against_split, traced, untraced)
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 _CHILD = r"""
 import json, os, sys
@@ -46,11 +42,7 @@ def poison_results():
     """Every case of SPLIT_CASES on the checker build that fills each robot's LDS with NaNs first, in ONE fresh child process."""
     from linearmpchumanoid_amd import build as hipbuild
     assert os.path.exists(hipbuild.build_variant("poison", ["-DLMH_POISON"]))
-    env = {k: v for k, v in os.environ.items() if k not in ("LMH_VARIANT", "LMH_DIAG")}
-    env["LMH_VARIANT"] = "poison"
-    r = subprocess.run([sys.executable, "-c", _CHILD], env=env, cwd=ROOT, capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stderr[-2000:]
-    res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+    res = run_probe(_CHILD, "poison", timeout=900)
     assert res["build_flags"] & 1 == 1, res["build_flags"]
     return {tuple(c): v for c, v in zip(SPLIT_CASES, res["cases"])}
 

@@ -3,7 +3,7 @@
 The call is DEFINED as the host loop of lmh_eval and lmh_plant_step (include/lmh.h), so the reference of every bit-for-bit case is that loop
 on a second copy of the same buffers (_host_loop); only test_against_the_oracle goes to the CPU (zoh_cases.oracle_run).  Inputs:
 plant_step_cases.contact_states(), 16 states around touch-down, v_prev = v, t = 0.  Every case runs at most 16 robots, 12 control ticks
-and 4 substeps.  "Bit for bit" is torch.equal on the int64 image of the float64 buffers (a NaN equals the same NaN, -0 is not +0)."""
+and 4 substeps.  "Bit for bit" is helpers.same_bits, the byte image of the buffers (a NaN equals the same NaN, -0 is not +0)."""
 import ctypes as C
 
 import numpy as np
@@ -13,21 +13,10 @@ import torch
 import params_cases as pcs
 import plant_step_cases as pc
 import zoh_cases as zc
-from helpers import TOL_REL, WEIGHT, close, rel_err, vec_err
+from helpers import TOL_REL, WEIGHT, close, make_controller, rel_err, same_bits as _same, vec_err
 
 pytestmark = pytest.mark.gpu
 DT, TH, B = pc.DT, pc.TH, pc.B
-
-
-def _controller(n, zcom, **kw):
-    from linearmpchumanoid_amd.controller import BatchedController, default_config
-    return BatchedController(n, default_config(dt=DT, time_horizon=TH, z_com=zcom, **kw))
-
-
-def _same(a, b):
-    if a.dtype == torch.float64:
-        return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))
-    return torch.equal(a, b)
 
 
 def _fresh(ctl, S, n=B):
@@ -72,7 +61,7 @@ def _compare(ctl, S, n_ticks, n_substeps, bw=None, tag=""):
 def test_composition_bit_for_bit(run, warm_start):
     """mpc_dt = 0 (= dt): the preview index moves with every substep."""
     S = pc.contact_states()
-    ctl = _controller(B, S["zcom"], warm_start=warm_start)
+    ctl = make_controller(B, DT, TH, S["zcom"], warm_start=warm_start)
     ctl.set_refs_stance(2.0, 2)
     st, out, status, log = _compare(ctl, S, *run)
     n_ticks, n_substeps = run
@@ -93,7 +82,7 @@ def test_composition_with_a_slower_preview(warm_start):
     """mpc_dt = 4 ms under a control period of 2 ms: k moves every second control tick, so the reference cache of the fused launch both hits
     and misses where the separate launches always start empty."""
     S = pc.contact_states()
-    ctl = _controller(B, S["zcom"], warm_start=warm_start, mpc_dt=4e-3)
+    ctl = make_controller(B, DT, TH, S["zcom"], warm_start=warm_start, mpc_dt=4e-3)
     ctl.set_refs_stance(2.0, 2)
     for n_ticks in (5, 12):
         _, _, status, log = _compare(ctl, S, n_ticks, 2)
@@ -118,7 +107,7 @@ def test_per_robot_everything_bit_for_bit(warm_start):
     base wrench per robot; the plans are short enough that the robots change segment (settle -> double support -> swing -> ...) at different
     ticks inside the 12 x 2 ms of the run."""
     S = pc.contact_states()
-    ctl = _controller(B, S["zcom"], warm_start=warm_start)
+    ctl = make_controller(B, DT, TH, S["zcom"], warm_start=warm_start)
     ctl.set_model(_randomised_links(B))
     sets = [dict(pcs.SIX_SETS[i % 6], **pcs.PLANT_SETS[i % 4]) for i in range(B)]
     ctl.set_params(**pcs.columns(sets, ctl.cfg))
@@ -140,7 +129,7 @@ def test_per_robot_everything_bit_for_bit(warm_start):
 def test_splitting():
     """rollout_zoh(7) = rollout_zoh(3) ; rollout_zoh(4) with the status record handed on (warm_start = 1: [3] carries the mask)."""
     S = pc.contact_states()
-    ctl = _controller(B, S["zcom"], warm_start=1)
+    ctl = make_controller(B, DT, TH, S["zcom"], warm_start=1)
     ctl.set_refs_stance(2.0, 2)
     bw = torch.as_tensor(np.random.default_rng(20261024).normal(0.0, 1.0, (B, 6))).to(ctl.device)
     s7, sp = _fresh(ctl, S), _fresh(ctl, S)
@@ -159,7 +148,7 @@ def test_splitting():
 def test_the_handle_is_untouched():
     """stand_step and a 20-tick rollout from a fixed state give the same bits before and after rollout_zoh calls on other buffers."""
     S = pc.contact_states()
-    ctl = _controller(B, S["zcom"], warm_start=1)
+    ctl = make_controller(B, DT, TH, S["zcom"], warm_start=1)
     ctl.set_refs_stance(2.0, 2)
     st0 = ctl.new_state(S["q0"], S["v"] * 0.2, t=0.0)
 
@@ -185,7 +174,7 @@ def test_against_the_oracle():
     the last evaluation to helpers' 1e-6 (f with the weight's floor), k exact.  All 16 robots, every figure printed before it is asserted."""
     S = pc.contact_states()
     ref = zc.oracle_run()
-    ctl = _controller(B, S["zcom"])
+    ctl = make_controller(B, DT, TH, S["zcom"])
     ctl.set_refs_stance(2.0, 2)
     st = _fresh(ctl, S)
     out, status = ctl.rollout_zoh(st, *zc.ORACLE_RUN)
@@ -220,7 +209,7 @@ def test_refusals():
         torch.cuda.synchronize()
         return all(_same(a, b) for a, b in zip(bufs[:3], bufs[3]))
 
-    ctl = _controller(B, S["zcom"])
+    ctl = make_controller(B, DT, TH, S["zcom"])
     ctl.set_refs_stance(2.0, 2)
     bufs = buffers(ctl)
     st, out, status, _ = bufs
@@ -237,13 +226,13 @@ def test_refusals():
         with pytest.raises(ValueError):
             bad_call()
     assert untouched(bufs)
-    mixed = _controller(B, S["zcom"], precision=capi.PRECISION_MIXED)
+    mixed = make_controller(B, DT, TH, S["zcom"], precision=capi.PRECISION_MIXED)
     mixed.set_refs_stance(2.0, 2)
     bufs = buffers(mixed)
     with pytest.raises(capi.LmhError) as e:
         mixed.rollout_zoh(bufs[0], 2, 2, out=bufs[1], status=bufs[2])
     assert e.value.code == -2 and "FP64" in str(e.value) and untouched(bufs)
-    bad = _controller(B, S["zcom"], plant=0, contact_k=-1.0)
+    bad = make_controller(B, DT, TH, S["zcom"], plant=0, contact_k=-1.0)
     bad.set_refs_stance(2.0, 2)
     bufs = buffers(bad)
     for n_ticks in (2, 0):
@@ -252,7 +241,7 @@ def test_refusals():
         assert e.value.code == -2 and "contact_k" in str(e.value)
     assert untouched(bufs)
     k = np.full(B, 2.0e4); k[7] = 0.0
-    ok = _controller(B, S["zcom"], plant=0)
+    ok = make_controller(B, DT, TH, S["zcom"], plant=0)
     ok.set_refs_stance(2.0, 2)
     ok.set_params(contact_k=k)                                     # accepted: plant = 0 checks no contact constant there
     bufs = buffers(ok)

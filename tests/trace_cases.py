@@ -9,6 +9,7 @@ tail -- and, with the plant, push_cases.scenario_controller's standing robots (t
 import numpy as np
 import torch
 
+from helpers import same_bits as same_bytes
 from plan_draw import DT, MPC_DT, N_PREVIEW, SIM_TIME, draw_walk_specs
 from push_cases import Run, host_split, ik_posture, scenario_controller, walking_controller
 
@@ -86,10 +87,6 @@ def split_trace(ctl, q0, nt, every, pushes=None):
             host_split(r, pushes[0], pushes[1], j * every, (j + 1) * every)
         samples.append(sample_of(r.result()))
     return np.stack(samples), len(r.logs)
-
-
-def same_bytes(a, b):
-    return np.ascontiguousarray(a).tobytes() == np.ascontiguousarray(b).tobytes()
 
 
 def first_difference(a, b):
