@@ -111,6 +111,26 @@ def build_shim(force=False, verbose=False):
     return SHIM_SO, OFFLINE_BIN
 
 
+DPP_HARNESS_SRC = os.path.join(ROOT, "tests", "kernels", "dpp_harness.hip")
+DPP_HARNESS_SO = os.path.join(_HERE, "liblmh_dpp_harness.so")
+
+
+def build_dpp_harness(force=False, verbose=False):
+    """Test harness of the DPP layer (tests/kernels/dpp_harness.hip: one kernel per primitive, chain and register solve of lmh_dpp.h)
+    into liblmh_dpp_harness.so -- test infrastructure, never part of the shipped library.  Plain -O3: the scheduler flags are the
+    rollout kernel's."""
+    srcs = [DPP_HARNESS_SRC, os.path.join(CSRC, "lmh_dpp.h")]
+    so = DPP_HARNESS_SO
+    if not force and os.path.exists(so) and all(os.path.getmtime(f) <= os.path.getmtime(so) for f in srcs):
+        return so
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I" + CSRC, DPP_HARNESS_SRC, "-o", so]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return so
+
+
 if __name__ == "__main__":
     print(build(force=True, verbose=True))
     print(build_shim(force=True, verbose=True))
