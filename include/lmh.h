@@ -45,6 +45,7 @@ extern "C" {
 #define LMH_SEG_STRIDE 52
 #define LMH_PUSH_STRIDE 32        /* one timed velocity push: tick (as a double) | dv[30] | pad, see lmh_set_pushes */
 #define LMH_MAX_PUSHES 16         /* push records per robot */
+#define LMH_IK_TARGET_STRIDE 16   /* one inverse-kinematics target record: rf6 (x y z | roll pitch yaw) | lf6 | com(3) | pad, see lmh_ik_batch */
 #define LMH_PARAM_STRIDE 20       /* one per-robot parameter record, see lmh_set_params */
 /* offsets into one parameter record (doubles, in lmh_config's own order) */
 #define LMH_PARAM_OFF_MU 0
@@ -369,6 +370,29 @@ int lmh_trace_samples(int n_ticks, int trace_every);      /* n_ticks / trace_eve
  * Either way the call returns and the other robots of the launch are not affected; there is no error code for it. */
 int lmh_ik(lmh_handle *h, double *d_q, const double *com_target, const double *rf6, const double *lf6,
            int32_t *d_iters, void *stream);
+
+/* lmh_ik with the targets on the DEVICE, one record per robot, and n_targets of them solved one after the other in one launch: the robot
+ * stays on chip, target j starts from the solution of target j-1 and target 0 from d_q_start.  Build-defined composition (the reference
+ * solves one posture per call).  All pointers are DEVICE pointers; sequences are sample-major like d_log and d_trace:
+ *   d_q_start [B][30]                                  start postures
+ *   d_targets [n_targets][B][LMH_IK_TARGET_STRIDE]     rf6 | lf6 | com(3) | pad (ignored), the fields of lmh_ik
+ *   d_q       [n_targets][B][30]                       solutions
+ *   d_iters   [n_targets][B]   (may be NULL)           Newton steps taken
+ *   d_crit    [n_targets][B]   (may be NULL)           the criterion max|e| the kernel held when it left the Newton loop of that solve
+ * d_q may alias d_q_start only when n_targets == 1 (lmh_ik's in-place use).  Every solve follows lmh_ik's rules: the arm and head rows
+ * hold the posture's CURRENT arm and head joints (a sequence keeps the start's arms throughout), the base-attitude target is zero, the
+ * loop stops at max|e| <= 1e-10 or after 200 steps, a NaN criterion ends it.
+ * Definition, bit for bit: for every robot, the call with n_targets = n leaves in d_q[j], d_iters[j], d_crit[j] what n calls with
+ * n_targets = 1 leave, call j starting from d_q[j-1] and call 0 from d_q_start; where all robots' records at step j are equal, d_q[j]
+ * and d_iters[j] are the bits of lmh_ik from the same starts with that target (the two kernels share one copy of the iteration).
+ * A robot that does not converge goes on to its next target from whatever it has; a NaN posture gives a NaN criterion, zero steps and
+ * NaN out.  No other robot is affected.  Not converged: d_iters == 200, a non-finite posture, or d_crit not <= 1e-10.
+ * NULL d_q_start, d_targets or d_q, n_targets < 0, or n_targets > 1 with d_q == d_q_start return LMH_ERR_BAD_ARG before anything is
+ * enqueued; n_targets == 0 is legal and enqueues nothing.  Asynchronous on `stream`; reads the handle's model tables (per-robot models
+ * honoured) and writes nothing into the handle: a later lmh_eval or lmh_rollout is bit for bit unaffected.  No host staging and no launch
+ * slot: the call can be captured into a graph from the first call on. */
+int lmh_ik_batch(lmh_handle *h, const double *d_q_start, const double *d_targets, int n_targets,
+                 double *d_q, int32_t *d_iters, double *d_crit, void *stream);
 
 /* replaces: Robot::updateState + Robot::getCoM (src/Robot.cpp:264-269,225-238).
  * DEVICE d_q [B][30] in, d_com [B][3] out. */

@@ -20,6 +20,7 @@ LINK_STRIDE = 13
 SEG_STRIDE = 52
 PUSH_STRIDE = 32              # one timed velocity push: tick (as a double) | dv[30] | pad (lmh_set_pushes)
 MAX_PUSHES = 16               # push records per robot
+IK_TARGET_STRIDE = 16         # one inverse-kinematics target record: rf6 | lf6 | com(3) | pad (lmh_ik_batch)
 PARAM_STRIDE = 20             # one per-robot parameter record (lmh_set_params)
 # name -> offset inside a parameter record: the LMH_PARAM_OFF_* defines of include/lmh.h (lmh_config's own order; [19] is a pad)
 PARAM_FIELDS = {
@@ -118,6 +119,7 @@ PROTOTYPES = {
     "lmh_rollout_trace": (_ip, [_vp, _vp, _vp, _vp, _vp, _ip, _vp, _ip, _vp]),
     "lmh_trace_samples": (_ip, [_ip, _ip]),
     "lmh_ik": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "lmh_ik_batch": (_ip, [_vp, _vp, _vp, _ip, _vp, _vp, _vp, _vp]),
     "lmh_robot_com": (_ip, [_vp, _vp, _vp, _vp]),
     "lmh_terms": (_ip, [_vp, _vp, _vp, _vp, _vp]),
     "lmh_inverse_dynamics": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -376,6 +376,23 @@ class BatchedController:
         check(capi.lib().lmh_ik(self._h, _dev_ptr(q), _np_ptr(ct), _np_ptr(r6), _np_ptr(l6), _dev_ptr(iters), self._stream()))
         return q, iters
 
+    def ik_batch(self, q, targets):
+        """lmh_ik_batch: per-robot targets, and sequences of them solved one after the other in one launch (target j from the solution
+        of target j-1).  q [B,30] device tensor (left as it is); targets [B,16] or [n,B,16] records (trajectories.ik_targets /
+        start_targets; array or tensor).  -> (q [n,B,30], iters [n,B] int32, crit [n,B]); [B,30], [B], [B] when targets is [B,16]."""
+        q = self._batch("q", q, 30)
+        t = torch.as_tensor(targets, dtype=torch.float64).to(self.device).contiguous()
+        if t.ndim not in (2, 3) or tuple(t.shape[-2:]) != (self.B, capi.IK_TARGET_STRIDE):
+            raise ValueError(f"targets must be [{self.B},{capi.IK_TARGET_STRIDE}] or [n,{self.B},{capi.IK_TARGET_STRIDE}]")
+        lead = tuple(t.shape[:-1])
+        n = 1 if t.ndim == 2 else int(t.shape[0])
+        out = torch.zeros(lead + (30,), dtype=torch.float64, device=self.device)
+        iters = torch.zeros(lead, dtype=torch.int32, device=self.device)
+        crit = torch.zeros(lead, dtype=torch.float64, device=self.device)
+        if n > 0:                                                  # (an empty tensor has no address to pass)
+            check(capi.lib().lmh_ik_batch(self._h, _dev_ptr(q), _dev_ptr(t), n, _dev_ptr(out), _dev_ptr(iters), _dev_ptr(crit), self._stream()))
+        return out, iters, crit
+
     def robot_com(self, q):
         """Robot::updateState + getCoM (Robot.cpp:264-269,225-238) for q [B,30] (device tensor) -> [B,3]."""
         com = torch.zeros((self.B, 3), dtype=torch.float64, device=self.device)

@@ -29,6 +29,8 @@ extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *
 // point refuses loudly there)
 extern "C" __attribute__((weak)) void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, int n_ticks, int n_substeps,
                                        hipStream_t s);
+// (weak for the same reason)
+extern "C" __attribute__((weak)) void lmh_launch_ik_batch(const LmhDevParams *P, const double *q_start, const double *targets, int n_targets, double *q, int32_t *iters, double *crit, hipStream_t s);
 extern "C" void lmh_launch_params_expand(const LmhDevParams *P, const double *d_rec, const double *d_gcol_tab, LmhDevParams *d_blocks, int n, hipStream_t s);
 extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
 
@@ -820,6 +822,17 @@ extern "C" int lmh_ik(lmh_handle *h, double *d_q, const double *com_target, cons
         tgt.v[15] = 0.0;
         lmh_launch_ik(&h->P, d_q, &tgt, d_iters, (hipStream_t)stream);
     });
+}
+
+extern "C" int lmh_ik_batch(lmh_handle *h, const double *d_q_start, const double *d_targets, int n_targets, double *d_q, int32_t *d_iters, double *d_crit, void *stream)
+{
+    const char *refusal = nullptr;
+    if (!d_q_start || !d_targets || !d_q) refusal = "lmh_ik_batch: null device pointer";
+    else if (n_targets < 0) refusal = "lmh_ik_batch: n_targets must be >= 0";
+    else if (n_targets > 1 && d_q == d_q_start) refusal = "lmh_ik_batch: d_q may alias d_q_start only when n_targets == 1";
+    if (!refusal && !lmh_launch_ik_batch) return fail(LMH_ERR_NOT_READY, "lmh_ik_batch: this program was linked without the kernel's launcher");
+    // the records are read on the device and no launch slot is taken: nothing of the handle is written, nothing is staged on the host
+    return launch(h, refusal, [&] { if (n_targets > 0) lmh_launch_ik_batch(&h->P, d_q_start, d_targets, n_targets, d_q, d_iters, d_crit, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_eval_host(lmh_handle *h, const double *q, const double *dq, double t, double *tau, double *f, double *qdd, int32_t *status)

@@ -4120,30 +4120,28 @@ __device__ void inv3_dev(const double *A, double *Ai)
     Ai[6] = (A[3] * A[7] - A[4] * A[6]) / det; Ai[7] = (A[1] * A[6] - A[0] * A[7]) / det; Ai[8] = (A[0] * A[4] - A[1] * A[3]) / det;
 }
 
-__global__ void __launch_bounds__(64) lmh_ik_kernel(LmhDevParams P_arg, double *qio, LmhIkTarget tgt, int32_t *iters_out)
+// desiredOperationalState (:11-25) of the robot in LDS from the 16-double target record at L[IK_E] (LmhIkTarget's order): feet pose,
+// CURRENT arm/head joints, zero base attitude, CoM target.  Lane i < 30 holds row i.  The record's slots are free again on return.
+__device__ __forceinline__ double ik_desired(double *L, int lane)
 {
-    LmhCParams &P = LMH_KERNARG_PARAMS();
-    __shared__ double L[IK_LDS];
-    const int inst = blockIdx.x;
-    if (inst >= P.n_instances) return;
-    const int lane = LANE;
-    SET_GDBG(nullptr);
-    load_common(L, P, inst);
-    if (lane < 30) L[P_Q + lane] = qio[30 * (size_t)inst + lane];
-    WSYNC();
-    // desiredOperationalState (:11-25): feet pose, CURRENT arm/head joints, zero base attitude, CoM target
     double des = 0.0;
-    if (lane < 16) L[IK_E + lane] = tgt.v[lane];                  // kernel-argument record -> LDS (a per-lane index into it would be a scratch copy)
-    WSYNC();
     if (lane < 12) des = L[IK_E + lane];
     else if (lane < 24) des = L[P_Q + 18 + (lane - 12)];
     else if (lane < 27) des = 0.0;
     else if (lane < 30) des = L[IK_E + 12 + (lane - 27)];
     WSYNC();
+    return des;
+}
+
+// Kinematics::compute's Newton loop (:27-52) on the posture at L[P_Q] towards `des` (ik_desired): leaves the posture the loop ended on at
+// L[P_Q], returns the steps taken and in `crit` the criterion max|e| the loop left on.  The one copy of the IK arithmetic: lmh_ik_kernel
+// and lmh_ik_batch_kernel both call it, so that what one computes for a target is bit for bit what the other computes.
+__device__ __forceinline__ int ik_newton(double *L, const double *lcoef, int lane, double des, double &crit)
+{
     const double mass = L[P_MODEL + 392];
     int iter = 0;
     for (;;) {
-        phase_fk<double>(L, P.lcoef);
+        phase_fk<double>(L, lcoef);
         phase_com_x<1, double>(L, 0);
         phase_jacobian<double>(L);
         // operationalState (:54-70)
@@ -4157,7 +4155,7 @@ __global__ void __launch_bounds__(64) lmh_ik_kernel(LmhDevParams P_arg, double *
         else if (lane < 27) Qv = L[P_Q + 3 + (lane - 24)];
         else if (lane < 30) Qv = L[P_COM + (lane - 27)];
         const double e = (lane < 30) ? des - Qv : 0.0;
-        const double crit = wave_max(fabs(e));
+        crit = wave_max(fabs(e));
         if (!(crit > 1e-10) || iter >= 200) break;
         if (lane < 30) L[IK_E + lane] = e;
         // ---- jacInvKinematics (:151-204)
@@ -4279,14 +4277,69 @@ __global__ void __launch_bounds__(64) lmh_ik_kernel(LmhDevParams P_arg, double *
         WSYNC();
         iter++;
     }
+    return iter;
+}
+
+__global__ void __launch_bounds__(64) lmh_ik_kernel(LmhDevParams P_arg, double *qio, LmhIkTarget tgt, int32_t *iters_out)
+{
+    LmhCParams &P = LMH_KERNARG_PARAMS();
+    __shared__ double L[IK_LDS];
+    const int inst = blockIdx.x;
+    if (inst >= P.n_instances) return;
+    const int lane = LANE;
+    SET_GDBG(nullptr);
+    load_common(L, P, inst);
+    if (lane < 30) L[P_Q + lane] = qio[30 * (size_t)inst + lane];
+    WSYNC();
+    if (lane < 16) L[IK_E + lane] = tgt.v[lane];                  // kernel-argument record -> LDS (a per-lane index into it would be a scratch copy)
+    WSYNC();
+    const double des = ik_desired(L, lane);
+    double crit;
+    const int iter = ik_newton(L, P.lcoef, lane, des, crit);
     if (lane < 30) qio[30 * (size_t)inst + lane] = L[P_Q + lane];
     if (lane == 0 && iters_out) iters_out[inst] = iter;
+}
+
+// lmh_ik_batch (include/lmh.h): per-robot target records from device memory, n_targets of them solved one after the other with the robot
+// on chip -- target j starts from the posture target j-1 ended on.  One wave per robot; every pass is lmh_ik_kernel's own sequence (record
+// -> LDS, ik_desired, ik_newton, store), so a sequence is bit for bit the chain of single-target launches it replaces.  Sample-major
+// buffers: targets [n][B][16], q_out [n][B][30], iters / crit [n][B].  q_out may be q_start when n_targets == 1 (the wave has read its
+// start before it writes).
+__global__ void __launch_bounds__(64) lmh_ik_batch_kernel(LmhDevParams P_arg, const double *q_start, const double *targets, int n_targets, double *q_out,
+                                                          int32_t *iters_out, double *crit_out)
+{
+    LmhCParams &P = LMH_KERNARG_PARAMS();
+    __shared__ double L[IK_LDS];
+    const int inst = blockIdx.x;
+    if (inst >= P.n_instances) return;
+    const int lane = LANE;
+    SET_GDBG(nullptr);
+    load_common(L, P, inst);
+    if (lane < 30) L[P_Q + lane] = q_start[30 * (size_t)inst + lane];
+    WSYNC();
+    const size_t B = (size_t)P.n_instances;
+#pragma unroll 1
+    for (int j = 0; j < n_targets; j++) {
+        const size_t rec = (size_t)j * B + inst;
+        if (lane < 16) L[IK_E + lane] = targets[LMH_IK_TARGET_STRIDE * rec + lane];
+        WSYNC();
+        const double des = ik_desired(L, lane);
+        double crit;
+        const int iter = ik_newton(L, P.lcoef, lane, des, crit);
+        if (lane < 30) q_out[30 * rec + lane] = L[P_Q + lane];
+        if (lane == 0 && iters_out) iters_out[rec] = iter;
+        if (lane == 0 && crit_out) crit_out[rec] = crit;
+    }
 }
 
 #ifndef LMH_ROLLOUT_ONLY              // (scripts/isa_census.py compiles the fp64 rollout kernel alone)
 extern "C" void lmh_launch_ik(const LmhDevParams *P, double *q, const LmhIkTarget *target, int32_t *iters, hipStream_t s)
 {
     hipLaunchKernelGGL(lmh_ik_kernel, dim3(P->n_instances), dim3(64), 0, s, *P, q, *target, iters);
+}
+extern "C" void lmh_launch_ik_batch(const LmhDevParams *P, const double *q_start, const double *targets, int n_targets, double *q, int32_t *iters, double *crit, hipStream_t s)
+{
+    hipLaunchKernelGGL(lmh_ik_batch_kernel, dim3(P->n_instances), dim3(64), 0, s, *P, q_start, targets, n_targets, q, iters, crit);
 }
 
 #endif

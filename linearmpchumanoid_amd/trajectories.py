@@ -8,7 +8,7 @@ definition on top of the reference's conventions (SupportFoot -> ZMP y of -/+0.0
 """
 import numpy as np
 
-from .capi import MAX_PUSHES, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE
+from .capi import IK_TARGET_STRIDE, MAX_PUSHES, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE
 
 
 def stance_zmp(simulation_time, time_step, support_foot=2):
@@ -178,6 +178,55 @@ def jump_plans(simulation_time, time_step, specs, B=None):
     sp, n = broadcast_specs(specs, JUMP_SPEC_DEFAULTS, B)
     plans = [jump_plan(simulation_time, time_step, **spec_of(sp, i)) for i in range(n)]
     return {k: np.stack([p[k] for p in plans]) for k in ("zmp_x", "zmp_y", "phase")}
+
+
+# the default targets of lmh_ik / BatchedController.ik: CoM, right and left sole [x y z | roll pitch yaw]
+IK_DEFAULT_COM = (-0.02, 0.0, 0.26)
+IK_DEFAULT_RF = (0.0, -0.05, 0.0, 0.0, 0.0, 0.0)
+IK_DEFAULT_LF = (0.0, 0.05, 0.0, 0.0, 0.0, 0.0)
+
+
+def ik_targets(com=IK_DEFAULT_COM, rf=IK_DEFAULT_RF, lf=IK_DEFAULT_LF, B=None, n=None):
+    """Target records of lmh_ik_batch / BatchedController.ik_batch: [n,B,16] float64, each record rf(6) | lf(6) | com(3) | pad (zero).
+    com is a scalar, [3], [B,3] or [n,B,3]; rf and lf a scalar, [6], [B,6] or [n,B,6]; the smaller forms broadcast over robots and
+    targets.  B and n are taken from the arrays that carry them (1 where none does) and must agree with the B, n given."""
+    fields = (("rf", rf, 6), ("lf", lf, 6), ("com", com, 3))
+    vals, Bs, ns = {}, set(), set()
+    for name, v, w in fields:
+        v = np.asarray(v, dtype=np.float64)
+        if v.ndim > 3 or (v.ndim >= 1 and v.shape[-1] != w):
+            raise ValueError(f"{name} must be a scalar, [{w}], [B,{w}] or [n,B,{w}]")
+        if v.ndim >= 2:
+            Bs.add(v.shape[-2])
+        if v.ndim == 3:
+            ns.add(v.shape[0])
+        vals[name] = v
+    if len(Bs) > 1 or len(ns) > 1:
+        raise ValueError("target fields must describe one number of robots and one number of targets")
+    nb = Bs.pop() if Bs else (1 if B is None else B)
+    nn = ns.pop() if ns else (1 if n is None else n)
+    if B is not None and nb != B:
+        raise ValueError(f"targets describe {nb} robots, expected {B}")
+    if n is not None and nn != n:
+        raise ValueError(f"targets describe {nn} targets, expected {n}")
+    rec = np.zeros((nn, nb, IK_TARGET_STRIDE))
+    rec[..., 0:6], rec[..., 6:12], rec[..., 12:15] = vals["rf"], vals["lf"], vals["com"]
+    return rec
+
+
+def start_targets(z_com=None, foot_y=None, com_xy=(-0.02, 0.0), B=None):
+    """Start-posture records [B,16] for ik_batch: robot i's CoM at (com_xy, z_com[i]) and its soles flat on the ground at y = -/+
+    foot_y[i] -- the values the caller passes to set_zcom and to the walk specs' foot_y.  z_com, foot_y: scalars or [B] (None: lmh_ik's
+    defaults 0.26 and 0.05); com_xy: [2] or [B,2]."""
+    sp, nb = broadcast_specs({k: v for k, v in (("z_com", z_com), ("foot_y", foot_y)) if v is not None},
+                             dict(z_com=IK_DEFAULT_COM[2], foot_y=IK_DEFAULT_LF[1]), B)
+    xy = np.asarray(com_xy, dtype=np.float64)
+    if xy.ndim not in (1, 2) or xy.shape[-1] != 2 or (xy.ndim == 2 and xy.shape[0] != nb):
+        raise ValueError(f"com_xy must be [2] or [{nb},2]")
+    rec = np.zeros((nb, IK_TARGET_STRIDE))
+    rec[:, 1], rec[:, 7] = -sp["foot_y"], sp["foot_y"]
+    rec[:, 12:14], rec[:, 14] = xy, sp["z_com"]
+    return rec
 
 
 # the refusals of lmh_set_pushes, word for word (lmh_capi.hip, push_schedule_error)
