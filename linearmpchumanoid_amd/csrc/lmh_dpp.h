@@ -408,6 +408,8 @@ __device__ __forceinline__ int ldl_solve_regs(double (&a)[N], double (&b)[M], un
 // not above `dmin` is replaced by 1 and reported in `bad` (kinv_compute: each foot on two DPP rows, a rank-deficient K_f is an expected
 // outcome).  GUARD = false (gj_solve_regs): every DPP row carries a copy of the system, so the pivot a lane sees is always the true one --
 // no guard selects, no test per pivot: lane J keeps 1 / d_J, and the caller looks at the signs once at the end.
+// `l16` MUST be lane & 15 of the calling lane: the pivot-lane predicate l16 == J is taken from the constant lane mask 0x0001000100010001 << J
+// (two scalar moves instead of a vector compare per pivot), so the argument only states the layout the callers have to be in.
 template <int J, int N, int M, bool GUARD = true>
 __device__ __forceinline__ void gj16_step(double (&a)[N], double (&b)[M], unsigned live, int l16, bool rowon, double dmin, int &bad, double &myinv)
 {
@@ -419,7 +421,7 @@ __device__ __forceinline__ void gj16_step(double (&a)[N], double (&b)[M], unsign
                 d = (rowon && d > dmin) ? d : 1.0;
             }
             const double invd = fast_rcp1(d);
-            const bool piv = l16 == J;
+            const bool piv = __builtin_amdgcn_inverse_ballot_w64(0x0001000100010001ull << J);   // l16 == J as a constant lane mask: no compare per pivot
             const double nf = piv ? 0.0 : -(a[J] * invd);
             myinv = piv ? invd : myinv;
             dpp_fmac_self<J + 1, N - 1 - J, J>(a, nf);
@@ -438,7 +440,7 @@ template <int N, int M>
 __device__ __forceinline__ int gj_solve_regs(double (&a)[N], double (&b)[M], unsigned live)
 {
     static_assert(N <= 16, "one DPP row");
-    const int l16 = LANE & 15;
+    const int l16 = LANE & 15;                                     // (what gj16_step's pivot masks assume)
     int bad = 0;
     double myinv = 0.0;
     gj16_step<0, N, M, false>(a, b, live, l16, true, 0.0, bad, myinv);

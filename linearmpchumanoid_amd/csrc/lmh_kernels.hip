@@ -243,6 +243,7 @@ __device__ __forceinline__ int lane_opaque()
 {
     int l = (int)(threadIdx.x & 63u);
     asm volatile("" : "+v"(l));
+    __builtin_assume(l >= 0 && l < 64);                            // the asm hides the range with the value: lane >> 4 <= 3, lane & 15 <= 15 fold guards and divisions again
     return l;
 }
 #define LANE lane_opaque()
@@ -1902,7 +1903,7 @@ __device__ __forceinline__ int kinv_compute(double *L, unsigned F, double *Kdst,
 #pragma unroll
         for (int s = 0; s < 3; s++) bb[s] = (l16 == c0 + s) ? 1.0 : 0.0;
         // K_f entries are O(1e-3 .. 10); a rank-deficient block pivots at ~1e-17
-        gj16_step<0>(a, bb, 0x3Fu, l16, rowon, 1e-12, bad, myinv);
+        gj16_step<0>(a, bb, 0x3Fu, l16, rowon, 1e-12, bad, myinv);  // (l16 = LANE & 15, as gj16_step's pivot masks assume)
 #pragma unroll
         for (int s = 0; s < 3; s++) bb[s] *= myinv;
         if (l16 < 6) {
@@ -2583,19 +2584,17 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
         }
         const double *b_row = (tr == 0) ? L + Q_BPT + 34 * 7 + tq : (tr < 7) ? L + Q_BPT + 34 * tr + tq : zero;
         const v4d vv = mfma_ptr<8, 4, 4>(u_row, b_row);
+        double *const tt = (tr < 8) ? L + Q_TT + 18 * tr + tq : L + Q_TRASH + lane;       // (trash: + 4 g <= lane + 12)
 #pragma unroll
-        for (int g = 0; g < 4; g++) {                              // V[r][n] -> TT[n][r], r = tq + 4 g < 16 (row 15 of U is zero: TT[n][15] = 0)
-            const int r = tq + 4 * g;
-            L[(tr < 8) ? Q_TT + 18 * tr + r : Q_TRASH + lane] = vv[g];
-        }
+        for (int g = 0; g < 4; g++) tt[4 * g] = vv[g];             // V[r][n] -> TT[n][r], r = tq + 4 g < 16 (row 15 of U is zero: TT[n][15] = 0)
     }
     if (NW == 1 || wid == 0) {
         const v4d cm = mfma_ptr<8, 4, 4>(u_row, L + Q_UD + 34 * tr + tq);
+        const double iom = L[Q_OB + 16 + tr];                      // 1 / Om_r of the diagonal entry r = tr: one load, whichever register holds it
+        const int dg = tr - tq;                                    // r == tr <=> dg == 4 g
+        double *const cmo = L + Q_CM + 17 * tq + tr;
 #pragma unroll
-        for (int g = 0; g < 4; g++) {
-            const int r = tq + 4 * g;
-            L[Q_CM + 17 * r + tr] = cm[g] + ((r == tr) ? L[Q_OB + 16 + r] : 0.0);
-        }
+        for (int g = 0; g < 4; g++) cmo[68 * g] = cm[g] + ((dg == 4 * g) ? iom : 0.0);
     }
     WSTAMP(12);
     bsync<NW>();
@@ -2621,12 +2620,12 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
         const double *m_row = (tr < 6) ? L + P_MTOP + 30 * tr + tq : zero;        // k = 30, 31 read the next row's first entries: finite, times the zero padding of B
         const v4d zz = mfma_ptr<8, 4, 4>(m_row, (tr < nU) ? L + Q_UD + 34 * tr + tq : zero);
         const v4d mb = mfma_ptr<8, 4, 4>(m_row, (tr < 7) ? L + Q_BPT + 34 * tr + tq : zero);
-#pragma unroll
-        for (int g = 0; g < 2; g++) {                              // rows m = tq + 4 g < 6
-            const int m = tq + 4 * g;
-            L[(m < 6) ? Q_Z + 18 * m + tr : Q_TRASH + lane] = zz[g];
-            L[(m < 6 && tr < 8) ? Q_MBP + 8 * m + tr : Q_TRASH + lane] = mb[g];
-        }
+        // rows m = tq + 4 g < 6: register 0 always holds one, register 1 for tq < 2
+        double *const trash = L + Q_TRASH + lane;
+        double *const z0 = L + Q_Z + 18 * tq + tr, *const z1 = (tq < 2) ? z0 + 72 : trash;
+        double *const m0 = (tr < 8) ? L + Q_MBP + 8 * tq + tr : trash, *const m1 = (tr < 8 && tq < 2) ? m0 + 32 : trash;
+        z0[0] = zz[0]; m0[0] = mb[0];
+        z1[0] = zz[1]; m1[0] = mb[1];
         if constexpr (NW == 2) slack(0);                           // (the helper waits ~1.7k cycles at this join otherwise: profiles/r04_barrier_share_mid2.txt)
     }
     bsync<NW>();
@@ -2635,16 +2634,26 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
     const double *t_row = (tr < 7) ? L + Q_TT + 18 * tr + tq : zero;              // B fragment of t'' (column tr)
     // ---- helper wave: Y = bp' - D^-1 U' t''  (30 x 7, stored transposed; only the recovery reads it)
     if (NW == 1 || wid == 1) {
+        // result register (mt, g) holds row i = tq + off, off = 16 mt + 4 g, of column tr: everything that depends on the lane is formed here,
+        // once, and the registers differ by the immediate `off` alone.  1 / D_i is idj except at off = 0 (i = tq: 0..2 position, 3 angle) and
+        // off = 4 (i = 4 + tq: 4, 5 angle, 6, 7 joints); i < 30 fails at off = 28 for tq >= 2 only, which gets its own store pointer (its bp'
+        // entry is a stored zero of the padding columns 30, 31, or one of Q_ZERO's 32).  Lanes of the columns tr >= 7 read zeros and store
+        // into Q_TRASH + (lane & 31) + off < Q_TRASH + 64.
+        const bool col = tr < 7;
+        double *const trash = L + Q_TRASH + (lane & 31);
+        const double *const bpc = col ? L + Q_BPT + 34 * tr + tq : zero;
+        double *const ytc = col ? L + P_YT + 30 * tr + tq : trash;
+        double *const yt28 = (col && tq < 2) ? ytc + 28 : trash;
+        const double id0 = (tq < 3) ? idp : ida, id4 = (tq < 2) ? ida : idj;
 #pragma unroll
         for (int mt = 0; mt < 2; mt++) {
             const v4d yy = mfma_ptr<4, 136, 4>(L + Q_U + 34 * tq + 16 * mt + tr, t_row);        // A[m = i][k] = U[k][i]
 #pragma unroll
             for (int g = 0; g < 4; g++) {
-                const int i = 16 * mt + tq + 4 * g;
-                const double iDi = (i < 3) ? idp : (i < 6) ? ida : idj;
-                const bool ok = (i < 30) && (tr < 7);
-                const double bpv = L[ok ? Q_BPT + 34 * tr + i : Q_ZERO];
-                L[ok ? P_YT + 30 * tr + i : Q_TRASH + lane] = bpv - yy[g] * iDi;
+                const int off = 16 * mt + 4 * g;
+                const double iDi = (off == 0) ? id0 : (off == 4) ? id4 : idj;
+                const double bpv = bpc[off];
+                *((off == 28) ? yt28 : ytc + off) = bpv - yy[g] * iDi;
             }
         }
         WSTAMP(17);
@@ -2655,14 +2664,17 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
     if (NW == 1 || wid == 0) {
         {
             const v4d sy = mfma_ptr<4, 4, 4>((tr < 6) ? L + Q_Z + 18 * tr + tq : zero, t_row);
-#pragma unroll
-            for (int g = 0; g < 2; g++) {
-                const int m = tq + 4 * g;
-                const bool ok = (m < 6) && (tr < 7);
-                const double val = L[ok ? Q_MBP + 8 * m + tr : Q_ZERO] - sy[g];
-                const double cv = L[P_C + ((m < 6) ? m : 0)];
-                L[!ok ? Q_TRASH + lane : (tr == 0) ? P_D6 + m : Q_S + 7 * m + (tr - 1)] = (tr == 0) ? cv - val : val;
-            }
+            // rows m = tq + 4 g < 6 (register 1: tq < 2) of the columns tr < 7; column 0 is d = C - (Mb bp' - Z t'')[.][0], columns 1..6 are S
+            const bool col = tr < 7, dcol = tr == 0, ok1 = col && tq < 2;
+            double *const trash = L + Q_TRASH + lane;
+            const double *const s0 = col ? L + Q_MBP + 8 * tq + tr : zero, *const s1 = ok1 ? s0 + 32 : zero;
+            const double *const c0 = L + P_C + tq, *const c1 = (tq < 2) ? c0 + 4 : L + P_C;
+            double *const d0 = !col ? trash : dcol ? L + P_D6 + tq : L + Q_S + 7 * tq + (tr - 1);
+            double *const d1 = !ok1 ? trash : dcol ? d0 + 4 : d0 + 28;
+            const double val0 = s0[0] - sy[0], val1 = s1[0] - sy[1];
+            const double cv0 = c0[0], cv1 = c1[0];
+            d0[0] = dcol ? cv0 - val0 : val0;
+            d1[0] = dcol ? cv1 - val1 : val1;
         }
         WSYNC();
         WSTAMP(19);
@@ -2681,8 +2693,9 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
             bb[0] = (c0 < 6 && l16 == c0) ? 1.0 : 0.0;
             bb[1] = (c0 < 6 && l16 == c0 + 1) ? 1.0 : 0.0;
             if (gj_solve_regs<6, 2>(a, bb, 0x3Fu)) flags |= LMH_FLAG_NOT_SPD;
-            L[own ? Q_LS + 6 * l16 + c0 : Q_TRASH + lane] = bb[0];
-            L[own ? Q_LS + 6 * l16 + c0 + 1 : Q_TRASH + lane] = bb[1];
+            double *const lso = own ? L + Q_LS + 6 * l16 + c0 : L + Q_TRASH + lane;      // (trash: slots lane, lane + 1 <= Q_TRASH + 64)
+            lso[0] = bb[0];
+            lso[1] = bb[1];
             WSYNC();
             {
                 const int e = (lane < 36) ? lane : 0, i = e / 6, j = e % 6;
@@ -2711,11 +2724,12 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
             ww = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, xt[0], ww, 0, 0, 0);
             ww = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, xt[1], ww, 0, 0, 0);
             const double wf = P.w_force;
+            // row m = tq + 4 g of column tr: W (tr < 12, rows 48 apart), h (tr == 12, entries 4 apart) or trash (+ 4 g <= lane + 8)
+            double *const wo = (tr < 12) ? L + P_W + 12 * tq + tr : (tr == 12) ? L + P_H12 + tq : L + Q_TRASH + lane;
+            const int ws = (tr < 12) ? 48 : 4;
+            const int dg = tr - tq;                                // m == tr <=> dg == 4 g
 #pragma unroll
-            for (int g = 0; g < 3; g++) {
-                const int m = tq + 4 * g;
-                L[(tr < 12) ? P_W + 12 * m + tr : (tr == 12) ? P_H12 + m : Q_TRASH + lane] = ww[g] + ((m == tr) ? wf : 0.0);
-            }
+            for (int g = 0; g < 3; g++) wo[g * ws] = ww[g] + ((dg == 4 * g) ? wf : 0.0);
         }
         WSTAMP(22);
         if (dbgp && LANE == 0) dbgp[4011] = (double)clock64();
@@ -3209,7 +3223,7 @@ __device__ __forceinline__ int plant_minv(double *L, int lane, SINK sink)
         for (int m = 0; m < 6; m++) { const double fv = L[P_MTOP + 30 * m + 6 + ja]; b[1 + m] = real ? fv : 0.0; }
         int bad = 0;
         double myinv = 0.0;
-        gj16_step<0>(a, b, 0x3Fu, l16, true, 0.0, bad, myinv);
+        gj16_step<0>(a, b, 0x3Fu, l16, true, 0.0, bad, myinv);     // (l16 = lane & 15 of the caller's LANE, as gj16_step's pivot masks assume)
 #pragma unroll
         for (int c = 0; c < 7; c++) L[real ? PL_B + 7 * ja + c : Q_TRASH + lane] = b[c] * myinv;
         if constexpr (CHECK) notspd |= bad;
