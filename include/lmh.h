@@ -68,6 +68,21 @@ extern "C" {
 #define LMH_PARAM_OFF_CONTACT_DT 17
 #define LMH_PARAM_OFF_CONTACT_MU 18   /* [19] pad */
 #define LMH_TRACE_STRIDE 180      /* one trace sample: state(96) | out(80) | status(4, as doubles), see lmh_rollout_trace */
+#define LMH_METRICS_STRIDE 208     /* one per-robot metrics record, see lmh_rollout_metrics */
+/* offsets into one metrics record (doubles) */
+#define LMH_METRICS_OFF_COUNT       0   /* ticks accumulated since the reset (a whole number in a double) */
+#define LMH_METRICS_OFF_FIRST_FLAG  1   /* COUNT before the first accumulated tick at whose end (launch-cumulative flags & 15) != 0; -1: none */
+#define LMH_METRICS_OFF_FIRST_FALL  2   /* COUNT before the first accumulated tick at whose end the robot is "down" (lmh_rollout_metrics); -1: none */
+#define LMH_METRICS_OFF_Z_MIN       3   /* threshold: written by the reset (or the caller), read by the kernel, never written by a rollout */
+#define LMH_METRICS_OFF_TILT_MAX    4   /* threshold, same rule; [5, 8) pad, zero */
+#define LMH_METRICS_OFF_XMIN        8   /* [60] min of every state component q | v at the end of a tick */
+#define LMH_METRICS_OFF_XMAX       68   /* [60] max */
+#define LMH_METRICS_OFF_WMIN      128   /* [12] min of the k4 contact wrench n_R f_R n_L f_L (out.f, the log's words) */
+#define LMH_METRICS_OFF_WMAX      140   /* [12] max */
+#define LMH_METRICS_OFF_TAU_MAXABS 152  /* [24] max |tau_j| of the k4 torques */
+#define LMH_METRICS_OFF_TAU_SQ    176   /* [24] sum of tau_j^2 (times dt: the effort integral) */
+#define LMH_METRICS_OFF_ERR_MAXABS 200  /* [2] max |CoM_x - xRef[0]|, max |CoM_y - yRef[0]| (out[66] - out[72], out[67] - out[75]) */
+#define LMH_METRICS_OFF_ERR_SQ    202   /* [2] sums of their squares; [204, 208) pad, zero */
 #define LMH_TERMS_STRIDE 1840     /* one rigid-body terms record, see lmh_terms */
 /* offsets into one terms record (doubles, every array row-major) */
 #define LMH_TERMS_OFF_M 0         /* [30][30] mass matrix, structural zeros written (Dynamics::getM) */
@@ -360,6 +375,41 @@ int lmh_rollout(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status
 int lmh_rollout_trace(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_log,
                       int n_ticks, double *d_trace, int trace_every, void *stream);
 int lmh_trace_samples(int n_ticks, int trace_every);      /* n_ticks / trace_every; 0 when trace_every <= 0 */
+
+/* lmh_rollout that also scores every robot DURING the launch (build-defined): d_metrics, DEVICE [B][LMH_METRICS_STRIDE], one small record per
+ * robot, accumulated on chip -- what a gain or weight sweep needs to rank its robots without an every-tick trace (1440 B per robot and
+ * tick).  The record is DEFINED as a reduction of that trace.  Let sample s = 0 .. n - 1 be the samples of
+ * lmh_rollout_trace(.., n_ticks = n, .., trace_every = 1) of the same launch; they are folded into the robot's record in order:
+ *   down_s        = !(q[2] >= Z_MIN) || !(|q[3]| <= TILT_MAX) || !(|q[4]| <= TILT_MAX) on sample s (base height, roll, pitch; a NaN pose
+ *                   therefore counts as down);
+ *   FIRST_FALL    = COUNT, if FIRST_FALL < 0 and down_s;
+ *   FIRST_FLAG    = COUNT, if FIRST_FLAG < 0 and ((int)sample[178] & 15) != 0 -- the flags are the launch-cumulative ones of the sample;
+ *                   the informational LMH_FLAG_QP_FP64_ROUTE and LMH_FLAG_UNFINISHED do not count;
+ *   XMIN / XMAX   = min / max with sample[0, 60), WMIN / WMAX with sample[96 + 24, 96 + 36).  The state words are those of the sample, so
+ *                   a push whose tick has not started is not in them (lmh_rollout_trace's rule);
+ *   TAU_MAXABS    = max(acc, |tau_j|), ERR_MAXABS = max(acc, |e|) with e = sample[96 + 66] - sample[96 + 72] and sample[96 + 67] - sample[96 + 75];
+ *   TAU_SQ, ERR_SQ: acc = acc + v * v, the product and the sum rounded separately (no fused multiply-add), in tick order -- numpy's
+ *                   acc += v * v gives the same bits;
+ *   COUNT        += 1, last.
+ * min and max are IEEE fmin / fmax: a NaN operand is ignored (v < acc ? v : acc, v > acc ? v : acc -- of two zeros of different sign the
+ * accumulator's is kept; the accumulator itself is never a NaN).  A sum that meets a NaN is a NaN from then on.
+ * The record is NOT reset by the call: metrics(a + b) is metrics(a) followed by metrics(b) on the same record, bit for bit, and FIRST_FLAG /
+ * FIRST_FALL, once set, stay -- a sweep scored over several launches needs nothing special (COUNT counts the ticks since the reset, while
+ * the flags of a sample count from its launch's start).
+ * lmh_metrics_reset writes the identity record of every robot of the handle: COUNT 0, FIRST_FLAG and FIRST_FALL -1, the two thresholds as
+ * given, minima +inf, maxima -inf, MAXABS words and sums 0, pads 0.  z_min = -INFINITY together with tilt_max = +INFINITY: the robot is never
+ * down (a NaN pose excepted).  A NaN threshold returns LMH_ERR_BAD_ARG.  It is one small kernel on `stream`: asynchronous, capturable, no
+ * launch slot.  Per-robot thresholds: overwrite words LMH_METRICS_OFF_Z_MIN and LMH_METRICS_OFF_TILT_MAX of the records after the reset
+ * (stream-ordered in front of the rollout) -- that is legal; a rollout reads the two words every tick and never writes them.
+ * lmh_rollout_metrics is lmh_rollout exactly -- the same launch-slot rules (eight in flight, LMH_ERR_UNFINISHED), the pushes applied, byte
+ * for byte the same d_state, d_out, d_status and d_log -- and additionally folds every tick of the launch.  d_metrics == NULL returns
+ * LMH_ERR_BAD_ARG before a launch slot is taken; the other argument checks are lmh_rollout's; n_ticks == 0 enqueues nothing and leaves
+ * the record's bytes alone.  There is no entry point for a trace and metrics together: a caller who wants both launches the trace and
+ * folds it (linearmpchumanoid_amd/metrics.py: fold_trace).  Each wave of a robot folds what it produced itself, where the trace takes its
+ * words; a launch without a record runs a kernel instantiation that holds none of it. */
+int lmh_metrics_reset(lmh_handle *h, double *d_metrics, double z_min, double tilt_max, void *stream);
+int lmh_rollout_metrics(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_log,
+                        int n_ticks, double *d_metrics, void *stream);
 
 /* replaces: Kinematics::desiredOperationalState + Kinematics::compute
  * (src/invKinematics.cpp:11-52): Newton IK to feet (0,-/+0.05,0), com target, per instance.

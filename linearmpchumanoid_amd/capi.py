@@ -29,6 +29,14 @@ PARAM_FIELDS = {
     "eps_coeff": 14, "contact_k": 15, "contact_d": 16, "contact_dt": 17, "contact_mu": 18,
 }
 TRACE_STRIDE = 180            # one trace sample: state(96) | out(80) | status(4, as doubles) (lmh_rollout_trace)
+METRICS_STRIDE = 208          # one per-robot metrics record (lmh_rollout_metrics)
+# name -> (offset, shape) inside a metrics record: the LMH_METRICS_OFF_* defines of include/lmh.h
+METRICS_FIELDS = {
+    "count": (0, ()), "first_flag": (1, ()), "first_fall": (2, ()), "z_min": (3, ()), "tilt_max": (4, ()),
+    "xmin": (8, (60,)), "xmax": (68, (60,)), "wmin": (128, (12,)), "wmax": (140, (12,)),
+    "tau_maxabs": (152, (24,)), "tau_sq": (176, (24,)), "err_maxabs": (200, (2,)), "err_sq": (202, (2,)),
+}
+METRICS_PADS = ((5, 8), (204, 208))   # zero
 TERMS_STRIDE = 1840           # one rigid-body terms record (lmh_terms)
 # name -> (offset, shape) inside a terms record: the LMH_TERMS_OFF_* defines of include/lmh.h, every array row-major
 TERMS_FIELDS = {
@@ -118,6 +126,8 @@ PROTOTYPES = {
     "lmh_rollout": (_ip, [_vp, _vp, _vp, _vp, _vp, _ip, _vp]),
     "lmh_rollout_trace": (_ip, [_vp, _vp, _vp, _vp, _vp, _ip, _vp, _ip, _vp]),
     "lmh_trace_samples": (_ip, [_ip, _ip]),
+    "lmh_metrics_reset": (_ip, [_vp, _vp, _dp, _dp, _vp]),
+    "lmh_rollout_metrics": (_ip, [_vp, _vp, _vp, _vp, _vp, _ip, _vp, _vp]),
     "lmh_ik": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lmh_ik_batch": (_ip, [_vp, _vp, _vp, _ip, _vp, _vp, _vp, _vp]),
     "lmh_robot_com": (_ip, [_vp, _vp, _vp, _vp]),

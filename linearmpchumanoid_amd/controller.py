@@ -363,6 +363,45 @@ class BatchedController:
                     x_ref=o[..., 72:75], y_ref=o[..., 75:78],
                     k=wi[..., 0], qp_iterations=wi[..., 1], flags=wi[..., 2], active_mask=wi[..., 3])
 
+    # ------------------------------------------------------------------ per-robot metrics (lmh_rollout_metrics)
+    def new_metrics(self, z_min=-np.inf, tilt_max=np.inf):
+        """A reset record per robot, [B,208] on the device.  z_min / tilt_max: the "down" thresholds on the base height and on |roll|,
+        |pitch|, scalars or arrays of length B (-inf / inf: never down)."""
+        m = torch.empty((self.B, capi.METRICS_STRIDE), dtype=torch.float64, device=self.device)
+        return self.metrics_reset(m, z_min, tilt_max)
+
+    def metrics_reset(self, metrics, z_min=-np.inf, tilt_max=np.inf):
+        """lmh_metrics_reset: the identity record for every robot; arrays of length B then overwrite words 3 / 4 (stream-ordered)."""
+        z, a = np.asarray(z_min, dtype=np.float64), np.asarray(tilt_max, dtype=np.float64)
+        for name, v in (("z_min", z), ("tilt_max", a)):
+            if v.ndim > 1 or (v.ndim == 1 and v.shape[0] != self.B):
+                raise ValueError(f"{name} must be a scalar or an array of length {self.B}")
+            if np.isnan(v).any():
+                raise ValueError(f"{name} must not be NaN")
+        check(capi.lib().lmh_metrics_reset(self._h, _dev_ptr(metrics), float(z) if z.ndim == 0 else -np.inf, float(a) if a.ndim == 0 else np.inf,
+                                           self._stream()))
+        for (off, _), v in ((capi.METRICS_FIELDS["z_min"], z), (capi.METRICS_FIELDS["tilt_max"], a)):
+            if v.ndim == 1:
+                metrics[:, off] = torch.as_tensor(v.copy()).to(self.device)
+        return metrics
+
+    def rollout_metrics(self, state, n_ticks, metrics, out=None, status=None, log=False):
+        """lmh_rollout_metrics: rollout that also folds every tick into the robots' records (new_metrics); the records are not reset by
+        the call, so consecutive launches accumulate.  -> (out, status, log)"""
+        out, status, lg = self._rollout_buffers(n_ticks, out, status, log)
+        check(capi.lib().lmh_rollout_metrics(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), _dev_ptr(lg), int(n_ticks),
+                                             _dev_ptr(metrics), self._stream()))
+        return out, status, lg
+
+    @staticmethod
+    def split_metrics(m):
+        """Named views of records [.., 208] (tensor or array) by capi.METRICS_FIELDS; count, first_flag and first_fall as integers
+        (exact: whole numbers in doubles; -1 = never)."""
+        f = _split(m, capi.METRICS_FIELDS)
+        for k in ("count", "first_flag", "first_fall"):
+            f[k] = f[k].to(torch.int64) if isinstance(f[k], torch.Tensor) else np.asarray(f[k]).astype(np.int64)
+        return f
+
     def synchronize(self):
         """lmh_synchronize on the current stream: waits for it, and raises LmhError (code ERR_UNFINISHED) if a completed rollout of this
         handle left robots part-way (they carry FLAG_UNFINISHED in their status records)."""

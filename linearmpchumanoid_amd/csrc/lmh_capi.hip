@@ -29,6 +29,10 @@ extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *
 // point refuses loudly there)
 extern "C" __attribute__((weak)) void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, int n_ticks, int n_substeps,
                                        hipStream_t s);
+// (weak for the same reason: lmh_rollout_metrics, lmh_metrics_reset)
+extern "C" __attribute__((weak)) void lmh_launch_rollout_metrics(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks,
+                                                                 double *metrics, hipStream_t s);
+extern "C" __attribute__((weak)) void lmh_launch_metrics_reset(double *metrics, int n_instances, double z_min, double tilt_max, hipStream_t s);
 // (weak for the same reason)
 extern "C" __attribute__((weak)) void lmh_launch_ik_batch(const LmhDevParams *P, const double *q_start, const double *targets, int n_targets, double *q, int32_t *iters, double *crit, hipStream_t s);
 extern "C" void lmh_launch_params_expand(const LmhDevParams *P, const double *d_rec, const double *d_gcol_tab, LmhDevParams *d_blocks, int n, hipStream_t s);
@@ -777,15 +781,12 @@ extern "C" int lmh_trace_samples(int n_ticks, int trace_every)
     return (trace_every <= 0 || n_ticks <= 0) ? 0 : n_ticks / trace_every;
 }
 
-extern "C" int lmh_rollout_trace(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_log, int n_ticks,
-                                 double *d_trace, int trace_every, void *stream)
+// The one launch path of lmh_rollout, lmh_rollout_trace and lmh_rollout_metrics, behind their own argument checks: a launch slot, the
+// parameter block, the kernel (a trace, a metrics record or neither), the slot's event
+static int rollout_launch(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_log, int n_ticks, double *d_trace, int trace_every,
+                          double *d_metrics, void *stream)
 {
-    int rc = ready(h); if (rc) return rc;
-    if (!d_state || !d_out || !d_status || n_ticks < 0) return fail(LMH_ERR_BAD_ARG, "bad argument");
-    // decided before a launch slot is taken: the buffer and its period come together or not at all
-    if (trace_every < 0 || (d_trace != nullptr) != (trace_every > 0))
-        return fail(LMH_ERR_BAD_ARG, "lmh_rollout_trace: d_trace and trace_every > 0 go together (NULL and 0: no trace)");
-    if (n_ticks == 0) return LMH_OK;
+    int rc = LMH_OK;
     HIPCHK(hipSetDevice(h->device));
     lmh_handle::Slot &sl = h->slot[h->next_slot % lmh_handle::kSlots];
     if (!sl.ready()) HIPCHK(sl.init(h->B, (hipStream_t)stream));
@@ -800,11 +801,46 @@ extern "C" int lmh_rollout_trace(lmh_handle *h, double *d_state, double *d_out, 
         HIPCHK(hipMemcpyAsync(sl.d_P.get(), &sl.P_dev, sizeof(LmhDevParams), hipMemcpyHostToDevice, (hipStream_t)stream));   // stream-ordered in front of the launch; the slot is idle
         sl.valid = true;
     }
-    lmh_launch_rollout(&h->P, sl.d_P.get(), sl.d_ticket.get(), d_state, d_out, d_status, d_log, n_ticks, d_trace, trace_every, (hipStream_t)stream);
+    if (d_metrics) lmh_launch_rollout_metrics(&h->P, sl.d_P.get(), sl.d_ticket.get(), d_state, d_out, d_status, d_log, n_ticks, d_metrics, (hipStream_t)stream);
+    else lmh_launch_rollout(&h->P, sl.d_P.get(), sl.d_ticket.get(), d_state, d_out, d_status, d_log, n_ticks, d_trace, trace_every, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(sl.done, (hipStream_t)stream));
     sl.used = true;
     sl.checked = false;
+    return LMH_OK;
+}
+
+extern "C" int lmh_rollout_trace(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_log, int n_ticks,
+                                 double *d_trace, int trace_every, void *stream)
+{
+    const int rc = ready(h); if (rc) return rc;
+    if (!d_state || !d_out || !d_status || n_ticks < 0) return fail(LMH_ERR_BAD_ARG, "bad argument");
+    // decided before a launch slot is taken: the buffer and its period come together or not at all
+    if (trace_every < 0 || (d_trace != nullptr) != (trace_every > 0))
+        return fail(LMH_ERR_BAD_ARG, "lmh_rollout_trace: d_trace and trace_every > 0 go together (NULL and 0: no trace)");
+    if (n_ticks == 0) return LMH_OK;
+    return rollout_launch(h, d_state, d_out, d_status, d_log, n_ticks, d_trace, trace_every, nullptr, stream);
+}
+
+extern "C" int lmh_rollout_metrics(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_log, int n_ticks, double *d_metrics, void *stream)
+{
+    const int rc = ready(h); if (rc) return rc;
+    if (!d_state || !d_out || !d_status || n_ticks < 0) return fail(LMH_ERR_BAD_ARG, "bad argument");
+    if (!d_metrics) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_metrics: d_metrics is NULL (lmh_rollout is the call without a record)");      // before a launch slot is taken
+    if (!lmh_launch_rollout_metrics) return fail(LMH_ERR_NOT_READY, "lmh_rollout_metrics: this program was linked without the kernel's launcher");
+    if (n_ticks == 0) return LMH_OK;
+    return rollout_launch(h, d_state, d_out, d_status, d_log, n_ticks, nullptr, 0, d_metrics, stream);
+}
+
+extern "C" int lmh_metrics_reset(lmh_handle *h, double *d_metrics, double z_min, double tilt_max, void *stream)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    if (!d_metrics) return fail(LMH_ERR_BAD_ARG, "lmh_metrics_reset: d_metrics is NULL");
+    if (std::isnan(z_min) || std::isnan(tilt_max)) return fail(LMH_ERR_BAD_ARG, "lmh_metrics_reset: a threshold is NaN (-INFINITY / +INFINITY: never down)");
+    if (!lmh_launch_metrics_reset) return fail(LMH_ERR_NOT_READY, "lmh_metrics_reset: this program was linked without the kernel's launcher");
+    HIPCHK(hipSetDevice(h->device));
+    lmh_launch_metrics_reset(d_metrics, h->B, z_min, tilt_max, (hipStream_t)stream);
+    HIPCHK(hipGetLastError());
     return LMH_OK;
 }
 

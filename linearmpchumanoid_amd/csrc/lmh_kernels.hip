@@ -3738,6 +3738,69 @@ __device__ __forceinline__ void trace_wave1(double *tr, const double *L, int lan
     if (a || b || c) tr[LMH_STATE_STRIDE + (a ? lane : b ? 66 + lane - 32 : 72 + lane - 40)] = v;
 }
 
+// ---- rollout metrics (include/lmh.h, lmh_rollout_metrics): the robot's record [LMH_METRICS_STRIDE] is a reduction of the every-tick trace,
+// folded where the trace takes its words and for the same reason split the same way: each wave folds what IT produced in the tick's fourth
+// evaluation.  Wave 0: the state extrema, the wrench extrema and the three header words; helper wave: the torque and tracking-error words.
+// The two waves own disjoint words of the record.  One read-modify-write of the record per tick (it stays in L2): nothing is carried
+// across controller_eval, where the kernel has no registers to spare.  Between chunks the record travels like the state record does (the
+// __syncthreads / __threadfence hand-over at the end of a unit, the acquire fence behind the claim of the next).
+// min / max: a NaN operand is ignored (the accumulator is never one: it starts at +-inf or 0), and of two zeros of different sign the
+// accumulator's is kept -- v < acc ? v : acc, the rule metrics.fold_trace states on the host.
+// wave 0, where trace_wave0 stands (in front of push_poll: the state words are the sample's): x = q | v on lanes 0..59.  An extreme is
+// stored only where it moved (after the first ticks: rarely)
+__device__ __forceinline__ void metrics_wave0(double *m, const double *L, double x, int flags)
+{
+    const int lane = LANE;                                         // its own opaque lane id: the word addresses are formed here, every tick, not carried across the tick loop
+    if (lane < 60) {
+        double *p = m + LMH_METRICS_OFF_XMIN + lane;
+        { const double lo = p[0]; if (x < lo) p[0] = x; }
+        { const double hi = p[LMH_METRICS_OFF_XMAX - LMH_METRICS_OFF_XMIN]; if (x > hi) p[LMH_METRICS_OFF_XMAX - LMH_METRICS_OFF_XMIN] = x; }
+    }
+    if (lane < 12) {
+        double *p = m + LMH_METRICS_OFF_WMIN + lane;
+        const double w = L[P_W12 + lane];
+        { const double lo = p[0]; if (w < lo) p[0] = w; }
+        { const double hi = p[LMH_METRICS_OFF_WMAX - LMH_METRICS_OFF_WMIN]; if (w > hi) p[LMH_METRICS_OFF_WMAX - LMH_METRICS_OFF_WMIN] = w; }
+    }
+    // down: lane 2 holds the base height, lanes 3 and 4 roll and pitch; each compares its own word against its threshold (a NaN is down)
+    bool dn = false;
+    if (lane >= 2 && lane < 5) {
+        const double thr = m[(lane == 2) ? LMH_METRICS_OFF_Z_MIN : LMH_METRICS_OFF_TILT_MAX];
+        dn = (lane == 2) ? !(x >= thr) : !(fabs(x) <= thr);
+    }
+    const bool down = __ballot(dn) != 0;
+    if (lane == 0) {
+        const double c = m[LMH_METRICS_OFF_COUNT];
+        if ((flags & 15) != 0 && m[LMH_METRICS_OFF_FIRST_FLAG] < 0.0) m[LMH_METRICS_OFF_FIRST_FLAG] = c;
+        if (down && m[LMH_METRICS_OFF_FIRST_FALL] < 0.0) m[LMH_METRICS_OFF_FIRST_FALL] = c;
+        m[LMH_METRICS_OFF_COUNT] = c + 1.0;
+    }
+}
+// helper wave, beside its log store: lanes 0..23 the torques, lanes 32 | 33 CoM x - xRef[0] | CoM y - yRef[0] (out[66] - out[72], out[67] - out[75]).
+// UNIT_LANE: the word addresses come from the kernel's own lane id and may be formed once per unit.  Decided from the resource lines
+// (profiles/r22_resource_usage.txt): the fp64 and mixed kernels have no registers to carry them across the tick loop (4 VGPRs spilled, 20 B
+// of scratch on the mixed one) and form them every tick from an opaque lane id of their own; the fp32-QP kernel is the other way round --
+// formed per tick its allocation ends where the instantiation without METRICS ends, at 256 registers with 2 spilled; carried, at 228 and none
+template <bool UNIT_LANE>
+__device__ __forceinline__ void metrics_wave1(double *m, const double *L, int lane_unit)
+{
+    const int lane = UNIT_LANE ? lane_unit : LANE;
+    const bool a = lane < 24, e = lane == 32 || lane == 33;
+    if (a || e) {
+        double v = L[a ? P_TAU + lane : P_COM + lane - 32];
+        if (e) v = v - L[P_MPC + 2 + 3 * (lane - 32)];
+        double *pm = m + (a ? LMH_METRICS_OFF_TAU_MAXABS + lane : LMH_METRICS_OFF_ERR_MAXABS + lane - 32);
+        double *ps = m + (a ? LMH_METRICS_OFF_TAU_SQ + lane : LMH_METRICS_OFF_ERR_SQ + lane - 32);
+        const double mx = *pm, sum = *ps, av = fabs(v);
+        if (av > mx) *pm = av;
+        // acc + v * v with the product and the sum rounded separately (numpy's acc += v * v): __dmul_rn / __dadd_rn are a plain * and + in
+        // this toolchain's headers, which the contraction would fuse, so the product goes through an opaque register first
+        double sq = __dmul_rn(v, v);
+        asm volatile("" : "+v"(sq));
+        *ps = __dadd_rn(sum, sq);
+    }
+}
+
 // Closed loop of apps/offline/main.cpp:66-122: n_ticks x rk4Step(dynamics) with Clock::step.
 // Workgroup = LMH_ROLLOUT_THREADS = 2 waves per robot (see bsync): 4 robots = 8 waves per CU, two per SIMD, so the
 // kernel is held to 256 registers.  Wave 0 owns the RK4 state (lane i < 60 <-> component i) and everything
@@ -3750,7 +3813,9 @@ __device__ __forceinline__ void trace_wave1(double *tr, const double *L, int lan
 // PARAMS: the instantiation a handle with per-robot parameters launches (lmh_set_params): it picks the robot's block when it claims a unit.
 // Holding that pointer across the tick loop costs six more scalar spill slots (117 against 111 on the fp64 kernel), so a handle on its
 // config's one set runs the instantiation without it -- the same code, and the same resource line, as before per-robot parameters existed
-template <typename R, bool QF32 = false, bool TRACE = false, bool PARAMS = false>
+// METRICS: the instantiation lmh_rollout_metrics launches (metrics_wave0 / metrics_wave1 above), never together with TRACE; a launch
+// without a record runs an instantiation that has no word of it, for the reason given for TRACE
+template <typename R, bool QF32 = false, bool TRACE = false, bool PARAMS = false, bool METRICS = false>
 #ifndef LMH_ROLLOUT_ATTR
 #ifndef LMH_WAVES_PER_EU
 #define LMH_WAVES_PER_EU 2
@@ -3762,16 +3827,17 @@ template <typename R, bool QF32 = false, bool TRACE = false, bool PARAMS = false
 #endif
 #endif
 __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) LMH_ROLLOUT_ATTR
-lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket_a, double *state_a, double *out_a, int32_t *status_a, double *log_a, int n_ticks_a, double *trace_a, int trace_every_a)
+lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket_a, double *state_a, double *out_a, int32_t *status_a, double *log_a, int n_ticks_a, double *trace_a, int trace_every_a, double *metrics_a)
 {
+    static_assert(!(TRACE && METRICS), "a caller who wants both launches the trace");
     // The parameter block is read through a pointer that is made opaque once per evaluation (params_of): hoisting its ~70 scalars out
     // of the tick loop pins them in SGPRs for the whole launch (round 1: 189 SGPR + 16 VGPR spills, 60 B of scratch per lane that reached
     // HBM); re-reading them costs a few scalar-cache loads per evaluation.
     __shared__ double L[LDS_DOUBLES];
     // The kernel's own arguments are read from the kernarg segment where they are used (a scalar load each: chunk start, chunk end, the log
     // and the trace once per tick) instead of being carried in scalar registers across the tick loop, where they were spilled to vector lanes and read back.
-    (void)ticket_a; (void)state_a; (void)out_a; (void)status_a; (void)log_a; (void)n_ticks_a; (void)trace_a; (void)trace_every_a;
-    struct Args { const LmhDevParams *Pg; int *ticket; double *state, *out; int32_t *status; double *log; int n_ticks; double *trace; int trace_every; };
+    (void)ticket_a; (void)state_a; (void)out_a; (void)status_a; (void)log_a; (void)n_ticks_a; (void)trace_a; (void)trace_every_a; (void)metrics_a;
+    struct Args { const LmhDevParams *Pg; int *ticket; double *state, *out; int32_t *status; double *log; int n_ticks; double *trace; int trace_every; double *metrics; };
     typedef const __attribute__((address_space(4))) Args CArgs;
     auto KA = [&]() -> CArgs & { CArgs *p_ = (CArgs *)__builtin_amdgcn_kernarg_segment_ptr(); asm volatile("" : "+s"(p_)); return *p_; };
 #define ticket (KA().ticket)
@@ -3782,6 +3848,7 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
 #define n_ticks (KA().n_ticks)
 #define trace (KA().trace)
 #define trace_every (KA().trace_every)
+#define metrics (KA().metrics)
     LmhCParams *P0 = (LmhCParams *)(uintptr_t)Pg;                  // the launch's block: n_instances and the queue arithmetic read it
     // One workgroup runs several robots one after the other (grid = the number of workgroups the chip holds at once, lmh_launch_rollout):
     // when the hardware dispatcher refills the chip from a longer grid, throughput drops by ~15 % (measured: 1024 robots 4.1 ms per launch,
@@ -3919,6 +3986,7 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
                         double *tr = trace_slot(trace, trace_every, tick0 + tick + 1, Pe->n_instances, inst);
                         if (tr) trace_wave0<true>(tr, L, lane, x, xprev, tail.xd, t + dt, k, itmax, flags, F);
                     }
+                    if constexpr (METRICS) metrics_wave0(metrics + (size_t)LMH_METRICS_STRIDE * inst, L, x, flags);      // this tick into the robot's record
                     push_poll(L, *Pe, inst, lane, tick + 1, n_here, x);     // a push at the start of the next tick joins the state published for it
                     xs = x;                                        // the next tick starts from x (what `xs = x` at its top says)
                 }
@@ -3936,6 +4004,7 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
                         double *tr = trace_slot(trace, trace_every, tick0 + tick + 1, Pe->n_instances, inst);
                         if (tr) trace_wave0<false>(tr, L, lane, x, xprev, 0.0, t + dt, k, itmax, flags, F);
                     }
+                    if constexpr (METRICS) metrics_wave0(metrics + (size_t)LMH_METRICS_STRIDE * inst, L, x, flags);
                     push_poll(L, *Pe, inst, lane, tick + 1, n_here, x);     // the next tick publishes x at its top
                 }
                 // Robot::v_ <- dq for the next evaluation
@@ -3962,6 +4031,7 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
             double *tr = trace_slot(trace, trace_every, tick0 + tick + 1, P.n_instances, inst);
             if (tr) trace_wave1(tr, L, lane);
         }
+        if (METRICS && wid != 0) metrics_wave1<QF32>(metrics + (size_t)LMH_METRICS_STRIDE * inst, L, lane);      // the helper's share of the fold
         t += dt;                                                    // Clock::step, Clock.hpp:11
     }
     bsync<2>();                                                    // the last torques (helper wave) are in LDS
@@ -4058,6 +4128,7 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
 #undef n_ticks
 #undef trace
 #undef trace_every
+#undef metrics
 
 // Robot::Robot model preparation (Robot.cpp:14-22) + Dynamics::spatialInertiaMatrix pieces
 // (Dynamics.cpp:4-13): raw [28][13] -> device model record.
@@ -4959,20 +5030,24 @@ extern "C" int lmh_debug_build_flags(void)
     return f;
 }
 // d_ticket: zero-initialised device memory owned by this launch until it completes (work-unit counters, ring, progress: see the kernel)
-extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks, double *trace, int trace_every, hipStream_t s)
+// metrics: the per-robot records of lmh_rollout_metrics (never together with a trace), NULL = none
+static void launch_rollout(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks, double *trace, int trace_every,
+                           double *metrics, hipStream_t s)
 {
     const int slots = rollout_resident_groups();
     const dim3 grid((unsigned)((P->n_instances < slots) ? P->n_instances : slots));
-    // (the untraced instantiations ignore the two trace arguments)
+    // (the untraced instantiations ignore the two trace arguments, those without METRICS the record pointer)
     // (per-robot parameter blocks, lmh_set_params: the instantiations that select the robot's block)
     const bool per_robot = P->inst_blocks != nullptr;
-#define LMH_LAUNCH_ROLLOUT_AS(R, QF32, TRACE, PARAMS) \
-        hipLaunchKernelGGL((lmh_rollout_kernel<R, QF32, TRACE, PARAMS>), grid, dim3(LMH_ROLLOUT_THREADS), 0, s, d_P, d_ticket, state, out, status, log, n_ticks, trace, trace_every)
+#define LMH_LAUNCH_ROLLOUT_AS(R, QF32, TRACE, PARAMS, METRICS) \
+        hipLaunchKernelGGL((lmh_rollout_kernel<R, QF32, TRACE, PARAMS, METRICS>), grid, dim3(LMH_ROLLOUT_THREADS), 0, s, d_P, d_ticket, state, out, status, log, n_ticks, trace, trace_every, metrics)
 #define LMH_LAUNCH_ROLLOUT(R, QF32) do { \
-        if (trace && per_robot) LMH_LAUNCH_ROLLOUT_AS(R, QF32, true, true); \
-        else if (trace) LMH_LAUNCH_ROLLOUT_AS(R, QF32, true, false); \
-        else if (per_robot) LMH_LAUNCH_ROLLOUT_AS(R, QF32, false, true); \
-        else LMH_LAUNCH_ROLLOUT_AS(R, QF32, false, false); \
+        if (trace && per_robot) LMH_LAUNCH_ROLLOUT_AS(R, QF32, true, true, false); \
+        else if (trace) LMH_LAUNCH_ROLLOUT_AS(R, QF32, true, false, false); \
+        else if (metrics && per_robot) LMH_LAUNCH_ROLLOUT_AS(R, QF32, false, true, true); \
+        else if (metrics) LMH_LAUNCH_ROLLOUT_AS(R, QF32, false, false, true); \
+        else if (per_robot) LMH_LAUNCH_ROLLOUT_AS(R, QF32, false, true, false); \
+        else LMH_LAUNCH_ROLLOUT_AS(R, QF32, false, false, false); \
     } while (0)
 #ifndef LMH_ROLLOUT_ONLY
     if (P->precision == 2) LMH_LAUNCH_ROLLOUT(float, true);
@@ -4983,6 +5058,34 @@ extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_
 #undef LMH_LAUNCH_ROLLOUT
 #undef LMH_LAUNCH_ROLLOUT_AS
 }
+extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks, double *trace, int trace_every, hipStream_t s)
+{
+    launch_rollout(P, d_P, d_ticket, state, out, status, log, n_ticks, trace, trace_every, nullptr, s);
+}
+extern "C" void lmh_launch_rollout_metrics(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks, double *metrics, hipStream_t s)
+{
+    launch_rollout(P, d_P, d_ticket, state, out, status, log, n_ticks, nullptr, 0, metrics, s);
+}
+#ifndef LMH_ROLLOUT_ONLY
+// the identity record of lmh_metrics_reset for n robots (grid-stride over the words)
+__global__ void __launch_bounds__(256) lmh_metrics_reset_kernel(double *m, int n, double z_min, double tilt_max)
+{
+    const size_t words = (size_t)n * LMH_METRICS_STRIDE;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += (size_t)gridDim.x * blockDim.x) {
+        const int w = (int)(i % LMH_METRICS_STRIDE);
+        const bool lo = (w >= LMH_METRICS_OFF_XMIN && w < LMH_METRICS_OFF_XMAX) || (w >= LMH_METRICS_OFF_WMIN && w < LMH_METRICS_OFF_WMAX);
+        const bool hi = (w >= LMH_METRICS_OFF_XMAX && w < LMH_METRICS_OFF_WMIN) || (w >= LMH_METRICS_OFF_WMAX && w < LMH_METRICS_OFF_TAU_MAXABS);
+        m[i] = (w == LMH_METRICS_OFF_FIRST_FLAG || w == LMH_METRICS_OFF_FIRST_FALL) ? -1.0 : (w == LMH_METRICS_OFF_Z_MIN) ? z_min
+             : (w == LMH_METRICS_OFF_TILT_MAX) ? tilt_max : lo ? (double)INFINITY : hi ? -(double)INFINITY : 0.0;
+    }
+}
+extern "C" void lmh_launch_metrics_reset(double *metrics, int n_instances, double z_min, double tilt_max, hipStream_t s)
+{
+    const size_t words = (size_t)n_instances * LMH_METRICS_STRIDE;
+    const unsigned blocks = (unsigned)((words + 255) / 256 < 1024 ? (words + 255) / 256 : 1024);
+    hipLaunchKernelGGL(lmh_metrics_reset_kernel, dim3(blocks), dim3(256), 0, s, metrics, n_instances, z_min, tilt_max);
+}
+#endif
 #ifndef LMH_ROLLOUT_ONLY
 extern "C" void lmh_launch_model(const double *raw, double *model, int n_models, const double *lcoef, hipStream_t s)
 {

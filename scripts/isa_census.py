@@ -8,7 +8,7 @@ add / shift / mul / mad / logic, cmp = v_cmp*, cvt, oth.
 Every function of the listing is also checked for the DPP read hazard that the compiler does not pad inside inline asm: a VALU write of
 the source register of a v_fmac_f64_dpp / v_fmac_f32_dpp needs two wait states before it (one instruction = one state, s_nop N = N + 1);
 each violation is listed.
-Usage: python scripts/isa_census.py [--reuse] [--rollout-only] [--trace] [--out FILE] [extra -D flags]      (--trace: the instantiation lmh_rollout_trace launches)
+Usage: python scripts/isa_census.py [--reuse] [--rollout-only] [--trace | --metrics] [--out FILE] [extra -D flags]      (--trace / --metrics: the instantiation lmh_rollout_trace / lmh_rollout_metrics launches)
             (--reuse: take /tmp/lmh_census.s as it is)"""
 import collections
 import os
@@ -29,7 +29,7 @@ if not reuse:
                            "-mllvm", "-amdgpu-sched-strategy=iterative-ilp", "-mllvm", "-disable-machine-licm", *extra, src, "-o", out],
                           stderr=subprocess.DEVNULL if "--verbose" not in argv else None)
 lines = open(out).read().split("\n")
-KNAME = "_Z18lmh_rollout_kernelIdLb0ELb%dELb0EE" % int("--trace" in argv)     # lmh_rollout_kernel<double, false, TRACE, false>
+KNAME = "_Z18lmh_rollout_kernelIdLb0ELb%dELb0ELb%dEE" % (int("--trace" in argv), int("--metrics" in argv))     # lmh_rollout_kernel<double, false, TRACE, false, METRICS>
 start = next(i for i, l in enumerate(lines) if l.startswith(KNAME))
 end = next(i for i in range(start, len(lines)) if lines[i].startswith(".Lfunc_end"))
 names = {0: "eval start", 1: "fk / prep done", 2: "joined", 3: "com_x share", 4: "joined", 5: "tree share", 6: "(no join)", 7: "refs share (+prefill)", 8: "joined",
