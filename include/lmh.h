@@ -102,6 +102,35 @@ extern "C" {
 #define LMH_CONTACT_OFF_W 0       /* [12] contact wrench n_R f_R n_L f_L about the sole origins, world axes, like out.f */
 #define LMH_CONTACT_OFF_VF 12     /* [8][3] force at every sole vertex, foot-major (right foot first), vertices in the order of Robot.cpp:38-42 */
 #define LMH_CONTACT_OFF_PAD 36    /* [4] zero */
+#define LMH_LIP_STRIDE 8          /* the reduced (LIPM) state of one robot, see lmh_mpc_step */
+/* offsets into one LIP state record (doubles) */
+#define LMH_LIP_OFF_X 0           /* CoM x */
+#define LMH_LIP_OFF_XDOT 1        /* CoM velocity x */
+#define LMH_LIP_OFF_Y 2
+#define LMH_LIP_OFF_YDOT 3
+#define LMH_LIP_OFF_T 4           /* the robot's clock; [5, 8) pad */
+#define LMH_MPC_STRIDE 16         /* one MPC sample, see lmh_mpc_step */
+/* offsets into one MPC sample (doubles) */
+#define LMH_MPC_OFF_XREF 0        /* [3] Mpc3dLip::getXRef: x_next, xdot_next, u_x */
+#define LMH_MPC_OFF_YREF 3        /* [3] Mpc3dLip::getYRef */
+#define LMH_MPC_OFF_ZMP 6         /* [2] zmp_x, zmp_y = x_k + D u: the model's output row C x + D u, D = -z_com / gravity */
+#define LMH_MPC_OFF_STATE 8       /* [4] the LIP state the sample was computed from: x, xdot, y, ydot */
+#define LMH_MPC_OFF_T 12          /* its clock */
+#define LMH_MPC_OFF_K 13          /* the preview index k = (int)(t / mpc_dt), as a double */
+#define LMH_MPC_OFF_FLAGS 14      /* this sample's flags (LMH_FLAG_ZMP_RANGE, LMH_FLAG_NONFINITE), as a double; [15] zero */
+#define LMH_MPC_PREVIEW_STRIDE 536 /* one horizon preview record, see lmh_mpc_preview: a header of 8, then eight arrays of 66 */
+/* offsets into one preview record (doubles); of every array the entries beyond the count named are zero */
+#define LMH_MPC_PREVIEW_OFF_K 0       /* the preview index, as a double */
+#define LMH_MPC_PREVIEW_OFF_FLAGS 1   /* LMH_FLAG_ZMP_RANGE, LMH_FLAG_NOT_SPD, LMH_FLAG_NONFINITE, as a double */
+#define LMH_MPC_PREVIEW_OFF_N 2       /* the horizon N, as a double; [3, 8) pad, zero */
+#define LMH_MPC_PREVIEW_OFF_U_X 8     /* [N + 1] the unconstrained solution U = -H^-1 g, x axis */
+#define LMH_MPC_PREVIEW_OFF_U_Y 74    /* [N + 1] */
+#define LMH_MPC_PREVIEW_OFF_Z_X 140   /* [N + 1] the predicted ZMP Px x_k + Pu U */
+#define LMH_MPC_PREVIEW_OFF_Z_Y 206   /* [N + 1] */
+#define LMH_MPC_PREVIEW_OFF_C_X 272   /* [N + 2] the predicted CoM position: c_0 = x_k, c_{j+1} = A c_j + B u_j */
+#define LMH_MPC_PREVIEW_OFF_CV_X 338  /* [N + 2] its velocity */
+#define LMH_MPC_PREVIEW_OFF_C_Y 404   /* [N + 2] */
+#define LMH_MPC_PREVIEW_OFF_CV_Y 470  /* [N + 2] */
 
 /* status flags */
 #define LMH_FLAG_QP_MAXITER 1     /* active-set iteration cap hit (reference: "QP failed", controller.cpp:472-476) */
@@ -537,6 +566,47 @@ int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_tau30, int n_
 int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
                     int n_ticks, int n_substeps, void *stream);
 
+/* ---- LIPM preview MPC for a batch of reduced states (one kernel family of its own, one wave per robot, fp64): the stage of the controller
+ * that lmh_eval runs between the momentum and the PD law, as calls of its own.
+ * replaces: Mpc3dLip::compute (src/mpcLinearPendulum.cpp:78-109) for every robot of the handle, at that robot's own clock.
+ * The calls read the handle's gain records (lmh_create's z_com, or per robot through lmh_set_zcom), its plan (shared or per robot), xscale,
+ * mpc_dt, alpha, beta, gravity and the horizon, and write nothing into the handle: a later lmh_eval or lmh_rollout is bit for bit
+ * unaffected.  They work on a handle of any precision and plant.  All pointers are DEVICE pointers; the calls are asynchronous on `stream`,
+ * stage nothing on the host and take no launch slot, so they can be captured into a hipGraph from the first call on.  NULL for a required
+ * pointer or a negative count returns LMH_ERR_BAD_ARG before anything is enqueued; a count of 0 enqueues nothing.
+ *   d_lip     [B][LMH_LIP_STRIDE]            x | xdot | y | ydot | t | pad(3)   (LMH_LIP_OFF_*)
+ *   d_mpc     [B][LMH_MPC_STRIDE]            one sample per robot                 (LMH_MPC_OFF_*)
+ *   d_traj    [n_ticks][B][LMH_MPC_STRIDE]   sample-major like d_log
+ *   d_preview [B][LMH_MPC_PREVIEW_STRIDE]    header | U_x U_y Z_x Z_y C_x Cv_x C_y Cv_y   (LMH_MPC_PREVIEW_OFF_*)
+ *
+ * lmh_mpc_step: k = (int)(t / mpc_dt);  u = -((sum K Px0 * x + sum K Px1 * xdot) - xscale_i * sum_j K_j z[k + j]) per axis (the y axis has
+ * no xscale; every index k + j is pinned to the robot's sample array, as in lmh_eval);  xRef = (a00 x + a01 xdot + b0 u, a10 x + a11 xdot +
+ * b1 u, u).  d_lip is read only.  The sample: xRef(3) | yRef(3) | zmp_x zmp_y | the state it was computed from (4) | its t | k | flags | 0.
+ * zmp = x + D * u with D = -z_com / gravity of the robot's own z_com (the fp64 quotient the gain row was built from), the product and the
+ * sum rounded separately (no fused multiply-add): numpy's x + D * u gives the same bits.  Flags: LMH_FLAG_ZMP_RANGE exactly as lmh_eval
+ * raises it (k < 0 || k + N >= n_samples), LMH_FLAG_NONFINITE when one of the first eight words is not finite.
+ * Definition, bit for bit: take a state on which lmh_eval leaves CoM, comVel, xRef, yRef in out[66:78] and k and the flags in status[0],
+ * status[2]; the call with x = out[66], xdot = out[69], y = out[67], ydot = out[70] and that state's t leaves out[72:78] in words [0, 6), k
+ * in word 13 and LMH_FLAG_ZMP_RANGE as status[2] & 4 (the step's kernel repeats the evaluation's window sum, gain sums and six
+ * expressions operation for operation). */
+int lmh_mpc_step(lmh_handle *h, const double *d_lip, double *d_mpc, void *stream);
+/* The reduced model in closed loop, on chip: the CoM trajectory the LIPM tracks under the plan -- what trajectories.ik_targets / lmh_ik_batch
+ * take as their com sequence, without a whole-body rollout.  Definition, bit for bit: n_ticks times { lmh_mpc_step, its sample to d_traj[j]
+ * (d_traj may be NULL: no samples); x <- sample[0], xdot <- sample[1], y <- sample[3], ydot <- sample[4], t <- t + mpc_dt (one fp64 add per
+ * tick, Clock::step's accumulation order: k is taken from the accumulated clock) }.  d_lip is updated in place (its pads are left alone).
+ * Hence lmh_mpc_rollout(a + b) is lmh_mpc_rollout(a) followed by lmh_mpc_rollout(b).  A robot whose window runs off its plan keeps going on
+ * the clamped window and carries LMH_FLAG_ZMP_RANGE in those samples only.  The gain row stays in registers for the launch; a tick is two
+ * coalesced window loads, the wave reductions and ten flops. */
+int lmh_mpc_rollout(lmh_handle *h, double *d_lip, int n_ticks, double *d_traj, void *stream);
+/* The whole unconstrained solution at each robot's state, for plotting the predicted ZMP and CoM against the plan: H = alpha I + beta Pu'Pu,
+ * g = beta Pu'(Px x_k - z) with z the same clamped, xscale-scaled window, U = -H^-1 g per axis, Z = Px x_k + Pu U and the N + 2 CoM states
+ * c_0 = x_k, c_{j+1} = A c_j + B u_j.  d_lip is read only.  The handle keeps the gain row K = beta e0' H^-1 Pu' alone (U[0] = -K (Px x_k - z)
+ * is lmh_mpc_step's u to rounding); here every robot's wave forms Pu and H from mpc_dt and its own D in LDS, factors H = L L' there and
+ * solves both axes -- no (N + 1)^2 table per robot is kept.  About (N + 1)^3 / 3 multiply-adds per robot: a diagnostic call, of the cost
+ * of a controller evaluation.  A pivot that is not positive raises LMH_FLAG_NOT_SPD in the header and leaves NaNs in the arrays (lmh_create
+ * and lmh_set_zcom refuse such a Hessian, so a handle that exists does not get there); LMH_FLAG_NONFINITE: an entry is not finite. */
+int lmh_mpc_preview(lmh_handle *h, const double *d_lip, double *d_preview, void *stream);
+
 /* host-buffer convenience used by the C++ shim (B instances, staged through internal
  * device buffers, synchronous): q/dq [B][30], t, outputs tau[B][24], f[B][12], qdd[B][30] */
 int lmh_eval_host(lmh_handle *h, const double *q, const double *dq, double t,
@@ -550,6 +620,9 @@ int lmh_ik_host(lmh_handle *h, double *q, const double *com_target, const double
 /* lmh_terms through host buffers (Dynamics::computeAll of the shim): q [B][30], v [B][30] or NULL (= 0) in, terms [B][LMH_TERMS_STRIDE] out.
  * Staged through a device buffer the handle allocates on the first call; synchronous. */
 int lmh_terms_host(lmh_handle *h, const double *q, const double *v, double *terms);
+/* lmh_mpc_step through host buffers (Mpc3dLip::compute of the shim): lip [B][LMH_LIP_STRIDE] in, mpc [B][LMH_MPC_STRIDE] out.  Staged through a
+ * device buffer the handle allocates on the first call; synchronous. */
+int lmh_mpc_step_host(lmh_handle *h, const double *lip, double *mpc);
 /* overwrite the staged Robot::v_ (v_prev) used by the next lmh_eval_host call: HOST [B][30] */
 int lmh_set_prev_velocity_host(lmh_handle *h, const double *v);
 /* hipStreamSynchronize(stream), then LMH_ERR_UNFINISHED if a completed lmh_rollout of this handle reported an incomplete launch (see there) */

@@ -49,6 +49,16 @@ CONTACT_STRIDE = 40           # one contact record (lmh_contact_wrench, lmh_plan
 # name -> (offset, shape) inside a contact record: the LMH_CONTACT_OFF_* defines of include/lmh.h
 CONTACT_FIELDS = {"w": (0, (12,)), "vertex_force": (12, (8, 3)), "pad": (36, (4,))}
 
+LIP_STRIDE = 8                # the reduced (LIPM) state of one robot: x | xdot | y | ydot | t | pad(3) (lmh_mpc_step)
+MPC_STRIDE = 16               # one MPC sample (lmh_mpc_step, lmh_mpc_rollout)
+# name -> (offset, shape) inside an MPC sample: the LMH_MPC_OFF_* defines of include/lmh.h; [15] is a pad (zero)
+MPC_FIELDS = {"x_ref": (0, (3,)), "y_ref": (3, (3,)), "zmp": (6, (2,)), "state": (8, (4,)), "t": (12, ()), "k": (13, ()), "flags": (14, ())}
+MPC_PREVIEW_STRIDE = 536      # one horizon preview record (lmh_mpc_preview): header(8) | eight arrays of 66
+MPC_PREVIEW_ARRAY = 66
+# name -> (offset, entries used at horizon N as a function of N): the LMH_MPC_PREVIEW_OFF_* defines of include/lmh.h
+MPC_PREVIEW_ARRAYS = {"U_x": (8, 1), "U_y": (74, 1), "Z_x": (140, 1), "Z_y": (206, 1),
+                      "C_x": (272, 2), "Cv_x": (338, 2), "C_y": (404, 2), "Cv_y": (470, 2)}   # (offset, count - N)
+
 FLAG_QP_MAXITER = 1
 FLAG_NONFINITE = 2
 FLAG_ZMP_RANGE = 4
@@ -138,11 +148,15 @@ PROTOTYPES = {
     "lmh_plant_derivative": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lmh_plant_step": (_ip, [_vp, _vp, _vp, _ip, _vp, _vp]),
     "lmh_rollout_zoh": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _vp]),
+    "lmh_mpc_step": (_ip, [_vp, _vp, _vp, _vp]),
+    "lmh_mpc_rollout": (_ip, [_vp, _vp, _ip, _vp, _vp]),
+    "lmh_mpc_preview": (_ip, [_vp, _vp, _vp, _vp]),
     "lmh_eval_host": (_ip, [_vp, _vp, _vp, _dp, _vp, _vp, _vp, _vp]),
     "lmh_robot_com_host": (_ip, [_vp, _vp, _vp]),
     "lmh_last_out_host": (_ip, [_vp, _vp]),
     "lmh_ik_host": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lmh_terms_host": (_ip, [_vp, _vp, _vp, _vp]),
+    "lmh_mpc_step_host": (_ip, [_vp, _vp, _vp]),
     "lmh_set_prev_velocity_host": (_ip, [_vp, _vp]),
     "lmh_synchronize": (_ip, [_vp, _vp]),
     "lmh_make_summary": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp]),

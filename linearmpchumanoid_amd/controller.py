@@ -539,6 +539,66 @@ class BatchedController:
         capi.CONTACT_FIELDS."""
         return _split(c, capi.CONTACT_FIELDS)
 
+    # -- LIPM preview MPC (include/lmh.h, lmh_mpc_step): the MPC stage of the controller on reduced states, as calls of its own
+    def new_lip(self, com_xy=(0.0, 0.0), vel_xy=(0.0, 0.0), t=0.0):
+        """LIP state records [B,8]: x | xdot | y | ydot | t | pad.  com_xy, vel_xy: [2] or [B,2]; t: a scalar or [B]."""
+        lip = np.zeros((self.B, capi.LIP_STRIDE))
+        lip[:, [0, 2]] = np.broadcast_to(np.asarray(com_xy, dtype=np.float64), (self.B, 2))
+        lip[:, [1, 3]] = np.broadcast_to(np.asarray(vel_xy, dtype=np.float64), (self.B, 2))
+        lip[:, 4] = np.broadcast_to(np.asarray(t, dtype=np.float64), (self.B,))
+        return torch.as_tensor(lip).to(self.device)
+
+    def mpc_step(self, lip):
+        """lmh_mpc_step: Mpc3dLip::compute for every robot at its own clock; lip [B,8] (left as it is) -> samples [B,16] (split_mpc)."""
+        lip = self._batch("lip", lip, capi.LIP_STRIDE)
+        rec = torch.empty((self.B, capi.MPC_STRIDE), dtype=torch.float64, device=self.device)
+        check(capi.lib().lmh_mpc_step(self._h, _dev_ptr(lip), _dev_ptr(rec), self._stream()))
+        return rec
+
+    def mpc_rollout(self, lip, n_ticks, traj=True):
+        """lmh_mpc_rollout: n_ticks MPC steps of the reduced model in closed loop, in one launch; lip [B,8] is updated in place.
+        traj=True: -> the samples [n_ticks,B,16]; False: -> None (only the final state); a tensor: filled and returned."""
+        lip = self._batch("lip", lip, capi.LIP_STRIDE, in_place=True)
+        if int(n_ticks) != n_ticks or n_ticks < 0:
+            raise ValueError("n_ticks must be a whole number >= 0")
+        n = int(n_ticks)
+        tr = torch.zeros((n, self.B, capi.MPC_STRIDE), dtype=torch.float64, device=self.device) if traj is True else (traj if traj is not False else None)
+        if tr is not None and (tr.dtype != torch.float64 or tr.device != self.device or not tr.is_contiguous() or tr.numel() < n * self.B * capi.MPC_STRIDE):
+            raise ValueError(f"traj must be a contiguous [{n},{self.B},{capi.MPC_STRIDE}] float64 tensor on {self.device}")
+        if n > 0:                                                  # (an empty tensor has no address to pass)
+            check(capi.lib().lmh_mpc_rollout(self._h, _dev_ptr(lip), n, _dev_ptr(tr), self._stream()))
+        return tr
+
+    def mpc_preview(self, lip):
+        """lmh_mpc_preview: the whole unconstrained solution over the horizon at every robot's state; lip [B,8] (left as it is) ->
+        records [B,536] (split_preview)."""
+        lip = self._batch("lip", lip, capi.LIP_STRIDE)
+        rec = torch.empty((self.B, capi.MPC_PREVIEW_STRIDE), dtype=torch.float64, device=self.device)
+        check(capi.lib().lmh_mpc_preview(self._h, _dev_ptr(lip), _dev_ptr(rec), self._stream()))
+        return rec
+
+    @staticmethod
+    def split_mpc(rec):
+        """Named views of MPC samples [.., 16] (tensor or array): x_ref [..,3], y_ref [..,3], zmp [..,2], state [..,4], t, and k, flags as
+        integers (exact: whole numbers in doubles) -- capi.MPC_FIELDS."""
+        f = _split(rec, capi.MPC_FIELDS)
+        for k in ("k", "flags"):
+            f[k] = f[k].to(torch.int64) if isinstance(f[k], torch.Tensor) else np.asarray(f[k]).astype(np.int64)
+        return f
+
+    @staticmethod
+    def split_preview(rec, N=None):
+        """Named views of preview records [.., 536] (tensor or array): k, flags, N as integers and the eight arrays U_x, U_y, Z_x, Z_y
+        (N + 1 entries) and C_x, Cv_x, C_y, Cv_y (N + 2) cut to their used length -- capi.MPC_PREVIEW_ARRAYS.  N: the horizon (taken from
+        the first record's header when None)."""
+        as_int = (lambda v: v.to(torch.int64)) if isinstance(rec, torch.Tensor) else (lambda v: np.asarray(v).astype(np.int64))
+        f = dict(k=as_int(rec[..., 0]), flags=as_int(rec[..., 1]), N=as_int(rec[..., 2]))
+        if N is None:
+            N = int(f["N"].reshape(-1)[0])
+        for name, (off, extra) in capi.MPC_PREVIEW_ARRAYS.items():
+            f[name] = rec[..., off:off + N + extra]
+        return f
+
     def make_summary(self, state, out, status):
         """End-of-run summary [B,16] (include/lmh.h lmh_make_summary): the record the RCCL gather moves."""
         s = torch.empty((self.B, capi.SUMMARY_WIDTH), dtype=torch.float64, device=self.device)

@@ -35,6 +35,10 @@ extern "C" __attribute__((weak)) void lmh_launch_rollout_metrics(const LmhDevPar
 extern "C" __attribute__((weak)) void lmh_launch_metrics_reset(double *metrics, int n_instances, double z_min, double tilt_max, hipStream_t s);
 // (weak for the same reason)
 extern "C" __attribute__((weak)) void lmh_launch_ik_batch(const LmhDevParams *P, const double *q_start, const double *targets, int n_targets, double *q, int32_t *iters, double *crit, hipStream_t s);
+// (weak for the same reason: lmh_mpc_step, lmh_mpc_rollout, lmh_mpc_preview; the launchers live in lmh_mpc.hip)
+extern "C" __attribute__((weak)) void lmh_launch_mpc_step(const LmhDevParams *P, const double *lip, double *mpc, hipStream_t s);
+extern "C" __attribute__((weak)) void lmh_launch_mpc_rollout(const LmhDevParams *P, double *lip, int n_ticks, double *traj, hipStream_t s);
+extern "C" __attribute__((weak)) void lmh_launch_mpc_preview(const LmhDevParams *P, double alpha, double beta, const double *lip, double *preview, hipStream_t s);
 extern "C" void lmh_launch_params_expand(const LmhDevParams *P, const double *d_rec, const double *d_gcol_tab, LmhDevParams *d_blocks, int n, hipStream_t s);
 extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
 
@@ -92,6 +96,7 @@ struct lmh_handle {
     // staging for the host-buffer convenience calls
     DevBuf<double> d_state, d_out;
     DevBuf<double> d_terms;           // lmh_terms_host only: q | v | terms records, allocated on its first call
+    DevBuf<double> d_mpc_host;        // lmh_mpc_step_host only: lip | mpc records, allocated on its first call
     DevBuf<int32_t> d_status;
     std::vector<double> h_state, h_out, h_gain;
     std::vector<int32_t> h_status;
@@ -158,7 +163,8 @@ extern "C" void lmh_nominal_links(double *raw) { std::memcpy(raw, kLmhNaoLinks, 
 
 // ---- Mpc3dLip::initialize (src/mpcLinearPendulum.cpp:41-68) + the algebraic gain row:
 // u = -H^-1 g, g = beta Pu'(Px x - z), H = alpha I + beta Pu'Pu  =>  u0 = -K (Px x - z),
-// K = beta e0' H^-1 Pu'.  Record layout: K | Px[:,0] | Px[:,1] | zcom | pad(3).
+// K = beta e0' H^-1 Pu'.  Record layout: K | Px[:,0] | Px[:,1] | zcom | D | pad(2); D = -zcom / gravity is the quotient Pu is built from
+// here, carried for the lmh_mpc_* kernels (the controller kernels and lmh_get_mpc_gain do not read that word).
 static int build_gain_row(const lmh_config &c, double dt /* MPC sample time */, double zcom, int N, double *rec)
 {
     const int n = N + 1;
@@ -215,7 +221,7 @@ static int build_gain_row(const lmh_config &c, double dt /* MPC sample time */, 
         for (int j = 0; j < n; j++) s += Pu[(size_t)i * n + j] * h0[j];
         K[i] = c.beta * s;
     }
-    rec[3 * n] = zcom; rec[3 * n + 1] = rec[3 * n + 2] = rec[3 * n + 3] = 0.0;
+    rec[3 * n] = zcom; rec[3 * n + 1] = D; rec[3 * n + 2] = rec[3 * n + 3] = 0.0;
     return 0;
 }
 
@@ -871,6 +877,31 @@ extern "C" int lmh_ik_batch(lmh_handle *h, const double *d_q_start, const double
     return launch(h, refusal, [&] { if (n_targets > 0) lmh_launch_ik_batch(&h->P, d_q_start, d_targets, n_targets, d_q, d_iters, d_crit, (hipStream_t)stream); });
 }
 
+// ---------------------------------------------------------------------------- LIPM preview MPC (lmh_mpc.hip)
+// the records are read on the device and no launch slot is taken: nothing of the handle is written, nothing is staged on the host
+extern "C" int lmh_mpc_step(lmh_handle *h, const double *d_lip, double *d_mpc, void *stream)
+{
+    const char *refusal = (!d_lip || !d_mpc) ? "lmh_mpc_step: null device pointer" : nullptr;
+    if (!refusal && !lmh_launch_mpc_step) return fail(LMH_ERR_NOT_READY, "lmh_mpc_step: this program was linked without the kernel's launcher");
+    return launch(h, refusal, [&] { lmh_launch_mpc_step(&h->P, d_lip, d_mpc, (hipStream_t)stream); });
+}
+
+extern "C" int lmh_mpc_rollout(lmh_handle *h, double *d_lip, int n_ticks, double *d_traj, void *stream)
+{
+    const char *refusal = nullptr;
+    if (!d_lip) refusal = "lmh_mpc_rollout: null device pointer";
+    else if (n_ticks < 0) refusal = "lmh_mpc_rollout: n_ticks must be >= 0";
+    if (!refusal && !lmh_launch_mpc_rollout) return fail(LMH_ERR_NOT_READY, "lmh_mpc_rollout: this program was linked without the kernel's launcher");
+    return launch(h, refusal, [&] { if (n_ticks > 0) lmh_launch_mpc_rollout(&h->P, d_lip, n_ticks, d_traj, (hipStream_t)stream); });
+}
+
+extern "C" int lmh_mpc_preview(lmh_handle *h, const double *d_lip, double *d_preview, void *stream)
+{
+    const char *refusal = (!d_lip || !d_preview) ? "lmh_mpc_preview: null device pointer" : nullptr;
+    if (!refusal && !lmh_launch_mpc_preview) return fail(LMH_ERR_NOT_READY, "lmh_mpc_preview: this program was linked without the kernel's launcher");
+    return launch(h, refusal, [&] { lmh_launch_mpc_preview(&h->P, h->cfg.alpha, h->cfg.beta, d_lip, d_preview, (hipStream_t)stream); });
+}
+
 extern "C" int lmh_eval_host(lmh_handle *h, const double *q, const double *dq, double t, double *tau, double *f, double *qdd, int32_t *status)
 {
     int rc = ready(h); if (rc) return rc;
@@ -1016,6 +1047,21 @@ extern "C" int lmh_terms_host(lmh_handle *h, const double *q, const double *v, d
     rc = lmh_terms(h, d_q, v ? d_v : nullptr, d_t, nullptr);
     if (rc) return rc;
     HIPCHK(hipMemcpy(terms, d_t, sizeof(double) * LMH_TERMS_STRIDE * n, hipMemcpyDeviceToHost));
+    return LMH_OK;
+}
+
+extern "C" int lmh_mpc_step_host(lmh_handle *h, const double *lip, double *mpc)
+{
+    int rc = ready(h); if (rc) return rc;
+    if (!lip || !mpc) return fail(LMH_ERR_BAD_ARG, "bad argument");
+    HIPCHK(hipSetDevice(h->device));
+    const size_t n = (size_t)h->B;
+    if (!h->d_mpc_host.get()) HIPCHK(h->d_mpc_host.alloc((LMH_LIP_STRIDE + LMH_MPC_STRIDE) * n));
+    double *d_lip = h->d_mpc_host.get(), *d_rec = d_lip + LMH_LIP_STRIDE * n;
+    HIPCHK(hipMemcpy(d_lip, lip, sizeof(double) * LMH_LIP_STRIDE * n, hipMemcpyHostToDevice));
+    rc = lmh_mpc_step(h, d_lip, d_rec, nullptr);
+    if (rc) return rc;
+    HIPCHK(hipMemcpy(mpc, d_rec, sizeof(double) * LMH_MPC_STRIDE * n, hipMemcpyDeviceToHost));
     return LMH_OK;
 }
 

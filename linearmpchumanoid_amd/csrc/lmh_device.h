@@ -15,7 +15,7 @@ struct LmhIkTarget { double v[16]; };   // rF(6) | lF(6) | com(3) | pad: passed 
 struct LmhDevParams {
     // ---- device buffers
     const double *model;        // [n_models][LMH_MODEL_STRIDE]
-    const double *mpc;          // [n_gain][mpc_stride]: K(N+1) | Px0(N+1) | Px1(N+1) | zcom | pad(3)
+    const double *mpc;          // [n_gain][mpc_stride]: K(N+1) | Px0(N+1) | Px1(N+1) | zcom | D = -zcom / gravity (the lmh_mpc_* kernels) | pad(2)
     const double *zmpx;         // [n_samples]
     const double *zmpy;
     const uint8_t *phase;       // [n_samples] or nullptr

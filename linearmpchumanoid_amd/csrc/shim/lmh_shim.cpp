@@ -193,6 +193,36 @@ void Kinematics::compute(Robot &robot, const Eigen::VectorXd &desOp)
     robot.setFromDevice(q.data(), nullptr, com, nullptr);
 }
 
+// ------------------------------------------------------------------ Mpc3dLip
+struct Mpc3dLip::Device {
+    lmh_handle *h = nullptr;
+    std::vector<double> zx, zy;                                     // what the handle's plan was last set from
+    ~Device() { if (h) lmh_destroy(h); }
+};
+
+void Mpc3dLip::compute(const Eigen::Vector2d &posCom, const Eigen::Vector2d &velCom, const Eigen::VectorXd &zmpXRef, const Eigen::VectorXd &zmpYRef, double t)
+{
+    if (!dev_) {
+        auto d = std::make_shared<Device>();
+        lmh_config cfg;
+        lmh_config_default(&cfg);
+        cfg.dt = dt_; cfg.mpc_dt = dt_; cfg.time_horizon = timeHorizon_; cfg.z_com = zCom_; cfg.alpha = alpha_; cfg.beta = beta_;
+        if (lmh_create(&cfg, 1, 0, &d->h) != LMH_OK) die("Mpc3dLip::compute: lmh_create");
+        dev_ = d;
+    }
+    const int n = zmpXRef.size();
+    if (n < 1 || zmpYRef.size() != n) { std::cerr << "Mpc3dLip::compute: zmpXRef and zmpYRef must have one length >= 1" << std::endl; std::abort(); }
+    const std::vector<double> zx(zmpXRef.data(), zmpXRef.data() + n), zy(zmpYRef.data(), zmpYRef.data() + n);
+    if (zx != dev_->zx || zy != dev_->zy) {                         // the arrays moved since the last call: upload them
+        if (lmh_set_refs(dev_->h, zx.data(), zy.data(), nullptr, n) != LMH_OK) die("Mpc3dLip::compute: lmh_set_refs");
+        dev_->zx = zx; dev_->zy = zy;
+    }
+    const double lip[LMH_LIP_STRIDE] = {posCom(0), velCom(0), posCom(1), velCom(1), t, 0, 0, 0};
+    double rec[LMH_MPC_STRIDE];
+    if (lmh_mpc_step_host(dev_->h, lip, rec) != LMH_OK) die("Mpc3dLip::compute: lmh_mpc_step_host");
+    setRefs(rec + LMH_MPC_OFF_XREF, rec + LMH_MPC_OFF_YREF);
+}
+
 // ------------------------------------------------------------------ Controller
 Controller::Controller(Robot &robot, Mpc3dLip &mpc, ZMP &zmp, std::vector<Eigen::VectorXd> &rFCoeff, std::vector<Eigen::VectorXd> &lFCoeff)
     : robot_(robot), mpc_(mpc)

@@ -8,7 +8,7 @@ definition on top of the reference's conventions (SupportFoot -> ZMP y of -/+0.0
 """
 import numpy as np
 
-from .capi import IK_TARGET_STRIDE, MAX_PUSHES, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE
+from .capi import FLAG_NONFINITE, FLAG_ZMP_RANGE, IK_TARGET_STRIDE, LIP_STRIDE, MAX_PUSHES, MPC_STRIDE, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE
 
 
 def stance_zmp(simulation_time, time_step, support_foot=2):
@@ -229,6 +229,76 @@ def start_targets(z_com=None, foot_y=None, com_xy=(-0.02, 0.0), B=None):
     return rec
 
 
+def preview_index(t, mpc_dt):
+    """k = (int)(t / mpc_dt) of mpcLinearPendulum.cpp:92 as the kernels form it: the fp64 quotient truncated towards zero, saturated to
+    int32, 0 for a NaN."""
+    q = np.float64(t) / np.float64(mpc_dt)
+    if np.isnan(q):
+        return 0
+    return int(np.clip(np.trunc(q), -2147483648.0, 2147483647.0))
+
+
+def lip_rollout(K, Px0, Px1, zx, zy, lip, n_ticks, mpc_dt, z_com, gravity=9.81, xscale=1.0):
+    """The numpy statement of lmh_mpc_rollout (include/lmh.h) for ONE robot: n_ticks times { the MPC step at (x, xdot, y, ydot, t); the
+    sample; x <- x_next, ..., t <- t + mpc_dt }.  K, Px0, Px1 [N+1]: the robot's gain row (lmh_get_mpc_gain) and the two columns of Px
+    (Px0 = 1, Px1 = j mpc_dt accumulated); zx, zy [n]: its plan's samples; lip [8] (or [5]): x | xdot | y | ydot | t; z_com, xscale: its
+    LIPM height and step-length scale.  -> (lip [8] after the last tick, samples [n_ticks,16] laid out as capi.MPC_FIELDS).
+    The step: k = (int)(t / mpc_dt); w = sum_j K_j z[clip(k + j)]; u = -((K.Px0 x + K.Px1 xdot) - xscale w) (y: no xscale);
+    x_ref = (x + mpc_dt xdot + mpc_dt^2 / 2 u, xdot + mpc_dt u, u); zmp = x + D u, D = -z_com / gravity; FLAG_ZMP_RANGE when k < 0 or
+    k + N >= n.  The sums are numpy's, so the kernel agrees to rounding, not to the bit; everything else is the kernel's operation order."""
+    K, Px0, Px1 = (np.asarray(a, dtype=np.float64) for a in (K, Px0, Px1))
+    zx, zy = np.asarray(zx, dtype=np.float64), np.asarray(zy, dtype=np.float64)
+    N, n = len(K) - 1, len(zx)
+    if Px0.shape != K.shape or Px1.shape != K.shape or zy.shape != zx.shape or zx.ndim != 1 or n < 1:
+        raise ValueError("K, Px0, Px1 must be [N+1] and zx, zy [n]")
+    if int(n_ticks) != n_ticks or n_ticks < 0:
+        raise ValueError("n_ticks must be a whole number >= 0")
+    dt = np.float64(mpc_dt)
+    a01, b0, b1 = dt, (dt * dt) / 2, dt
+    D = -np.float64(z_com) / np.float64(gravity)
+    kp0, kp1 = K @ Px0, K @ Px1
+    st = np.zeros(LIP_STRIDE)
+    st[:min(len(lip), LIP_STRIDE)] = np.asarray(lip, dtype=np.float64)[:LIP_STRIDE]
+    x, xd, y, yd, t = (np.float64(v) for v in st[:5])
+    out = np.zeros((int(n_ticks), MPC_STRIDE))
+    j = np.arange(N + 1)
+    with np.errstate(all="ignore"):
+        for tick in range(int(n_ticks)):
+            k = preview_index(t, dt)
+            idx = np.clip(k + j, 0, n - 1)
+            ux = -((kp0 * x + kp1 * xd) - np.float64(xscale) * (K @ zx[idx]))
+            uy = -((kp0 * y + kp1 * yd) - (K @ zy[idx]))
+            rec = out[tick]
+            rec[0:3] = x + a01 * xd + b0 * ux, xd + b1 * ux, ux
+            rec[3:6] = y + a01 * yd + b0 * uy, yd + b1 * uy, uy
+            rec[6:8] = x + D * ux, y + D * uy
+            rec[8:13] = x, xd, y, yd, t
+            flags = FLAG_ZMP_RANGE if (k < 0 or k + N >= n) else 0
+            if not np.isfinite(rec[0:8]).all():
+                flags |= FLAG_NONFINITE
+            rec[13], rec[14] = k, flags
+            x, xd, y, yd = rec[0], rec[1], rec[3], rec[4]
+            t = t + dt
+    st[:5] = x, xd, y, yd, t
+    return st, out
+
+
+def com_targets(traj, z_com):
+    """The `com` argument of ik_targets from an MPC trajectory (lmh_mpc_rollout / lip_rollout): traj [n,B,16] or [n,16] samples ->
+    [n,B,3] (or [n,3]) with x = x_ref[0], y = y_ref[0] of every sample -- where the LIPM is at the END of that tick -- and z = z_com (a
+    scalar or [B], the values given to set_zcom)."""
+    tr = np.asarray(traj, dtype=np.float64)
+    if tr.ndim not in (2, 3) or tr.shape[-1] != MPC_STRIDE:
+        raise ValueError(f"traj must be [n,B,{MPC_STRIDE}] or [n,{MPC_STRIDE}]")
+    z = np.asarray(z_com, dtype=np.float64)
+    if z.ndim > 1 or (z.ndim == 1 and (tr.ndim != 3 or z.shape[0] != tr.shape[1])):
+        raise ValueError("z_com must be a scalar or [B]")
+    com = np.zeros(tr.shape[:-1] + (3,))
+    com[..., 0], com[..., 1] = tr[..., 0], tr[..., 3]
+    com[..., 2] = z
+    return com
+
+
 # the refusals of lmh_set_pushes, word for word (lmh_capi.hip, push_schedule_error)
 PUSH_ERR_TICK = "push ticks must be whole numbers in [0, 2^31), or -1 for an unused record"
 PUSH_ERR_ORDER = "a used push record follows an unused one"
@@ -309,5 +379,5 @@ def draw_pushes(B, n, tick_range, amplitude, seed):
 
 
 __all__ = ["stance_zmp", "find_poly_coeff", "foot_coeff_trajectory", "walk_plan", "jump_plan", "walk_plans", "jump_plans",
-           "push_schedule", "check_push_records", "draw_pushes",
+           "push_schedule", "check_push_records", "draw_pushes", "preview_index", "lip_rollout", "com_targets",
            "PHASE_DOUBLE", "PHASE_RIGHT", "PHASE_LEFT", "PHASE_FLIGHT"]
