@@ -168,6 +168,8 @@ PROTOTYPES = {
     "lmh_read_trace": (_ip, [_str, _vp, _u64, _u64p, _u64p, _dpp, _dpp]),
 }
 EXPORTS = list(PROTOTYPES)
+# the diagnostics csrc/lmh_launch.h declares beside the C ABI: bound where the loaded library has them (a build of an earlier tree may not)
+DEBUG_PROTOTYPES = {"lmh_debug_build_flags": (_ip, []), "lmh_debug_rollout_occupancy": (_ip, [C.POINTER(C.c_int)] * 3)}
 
 _lib = None
 
@@ -183,7 +185,7 @@ def lib():
             "(run `python __graft_entry__.py` or `python linearmpchumanoid_amd/build.py`). "
             "There is no CPU fallback.")
     L = C.CDLL(SO_PATH)
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + [d for d in DEBUG_PROTOTYPES.items() if hasattr(L, d[0])]:
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L

@@ -12,35 +12,7 @@
 #include "../../include/lmh.h"
 #include "lmh_device.h"
 #include "lmh_nao_model.h"
-
-extern "C" void lmh_launch_eval(const LmhDevParams *P, double *state, double *out, int32_t *status, double *debug, hipStream_t s);
-extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks, double *trace, int trace_every, hipStream_t s);
-extern "C" void lmh_launch_model(const double *raw, double *model, int n_models, const double *lcoef, hipStream_t s);
-extern "C" void lmh_launch_com(const LmhDevParams *P, const double *q, double *com, hipStream_t s);
-extern "C" void lmh_launch_ik(const LmhDevParams *P, double *q, const LmhIkTarget *target, int32_t *iters, hipStream_t s);
-extern "C" void lmh_launch_gen_walk(const LmhWalkSpec *W, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos, hipStream_t s);
-extern "C" void lmh_launch_gen_jump(int n, double time_step, double stance_time, double flight_time, double *zx, double *zy, uint8_t *phase, hipStream_t s);
-extern "C" void lmh_launch_gen_walk_batch(const LmhWalkSpec *d_specs, int n_plans, int seg_stride, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos, hipStream_t s);
-extern "C" void lmh_launch_gen_jump_batch(int n, double time_step, const LmhJumpSpec *d_specs, int n_plans, double *zx, double *zy, uint8_t *phase, hipStream_t s);
-extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *q, const double *v, const double *x, const double *w, double *res, int32_t *flags, hipStream_t s);
-extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact, int32_t *flags,
-                                 int n_substeps, hipStream_t s);
-// (a weak reference: a program that links this file without lmh_kernels.hip and without a stub of this launcher still links, and the entry
-// point refuses loudly there)
-extern "C" __attribute__((weak)) void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, int n_ticks, int n_substeps,
-                                       hipStream_t s);
-// (weak for the same reason: lmh_rollout_metrics, lmh_metrics_reset)
-extern "C" __attribute__((weak)) void lmh_launch_rollout_metrics(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks,
-                                                                 double *metrics, hipStream_t s);
-extern "C" __attribute__((weak)) void lmh_launch_metrics_reset(double *metrics, int n_instances, double z_min, double tilt_max, hipStream_t s);
-// (weak for the same reason)
-extern "C" __attribute__((weak)) void lmh_launch_ik_batch(const LmhDevParams *P, const double *q_start, const double *targets, int n_targets, double *q, int32_t *iters, double *crit, hipStream_t s);
-// (weak for the same reason: lmh_mpc_step, lmh_mpc_rollout, lmh_mpc_preview; the launchers live in lmh_mpc.hip)
-extern "C" __attribute__((weak)) void lmh_launch_mpc_step(const LmhDevParams *P, const double *lip, double *mpc, hipStream_t s);
-extern "C" __attribute__((weak)) void lmh_launch_mpc_rollout(const LmhDevParams *P, double *lip, int n_ticks, double *traj, hipStream_t s);
-extern "C" __attribute__((weak)) void lmh_launch_mpc_preview(const LmhDevParams *P, double alpha, double beta, const double *lip, double *preview, hipStream_t s);
-extern "C" void lmh_launch_params_expand(const LmhDevParams *P, const double *d_rec, const double *d_gcol_tab, LmhDevParams *d_blocks, int n, hipStream_t s);
-extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
+#include "lmh_launch.h"
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string &msg) { g_err = msg; return code; }
@@ -807,8 +779,7 @@ static int rollout_launch(lmh_handle *h, double *d_state, double *d_out, int32_t
         HIPCHK(hipMemcpyAsync(sl.d_P.get(), &sl.P_dev, sizeof(LmhDevParams), hipMemcpyHostToDevice, (hipStream_t)stream));   // stream-ordered in front of the launch; the slot is idle
         sl.valid = true;
     }
-    if (d_metrics) lmh_launch_rollout_metrics(&h->P, sl.d_P.get(), sl.d_ticket.get(), d_state, d_out, d_status, d_log, n_ticks, d_metrics, (hipStream_t)stream);
-    else lmh_launch_rollout(&h->P, sl.d_P.get(), sl.d_ticket.get(), d_state, d_out, d_status, d_log, n_ticks, d_trace, trace_every, (hipStream_t)stream);
+    lmh_launch_rollout(&h->P, sl.d_P.get(), sl.d_ticket.get(), d_state, d_out, d_status, d_log, n_ticks, d_trace, trace_every, d_metrics, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(sl.done, (hipStream_t)stream));
     sl.used = true;
@@ -833,7 +804,6 @@ extern "C" int lmh_rollout_metrics(lmh_handle *h, double *d_state, double *d_out
     const int rc = ready(h); if (rc) return rc;
     if (!d_state || !d_out || !d_status || n_ticks < 0) return fail(LMH_ERR_BAD_ARG, "bad argument");
     if (!d_metrics) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_metrics: d_metrics is NULL (lmh_rollout is the call without a record)");      // before a launch slot is taken
-    if (!lmh_launch_rollout_metrics) return fail(LMH_ERR_NOT_READY, "lmh_rollout_metrics: this program was linked without the kernel's launcher");
     if (n_ticks == 0) return LMH_OK;
     return rollout_launch(h, d_state, d_out, d_status, d_log, n_ticks, nullptr, 0, d_metrics, stream);
 }
@@ -843,7 +813,6 @@ extern "C" int lmh_metrics_reset(lmh_handle *h, double *d_metrics, double z_min,
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
     if (!d_metrics) return fail(LMH_ERR_BAD_ARG, "lmh_metrics_reset: d_metrics is NULL");
     if (std::isnan(z_min) || std::isnan(tilt_max)) return fail(LMH_ERR_BAD_ARG, "lmh_metrics_reset: a threshold is NaN (-INFINITY / +INFINITY: never down)");
-    if (!lmh_launch_metrics_reset) return fail(LMH_ERR_NOT_READY, "lmh_metrics_reset: this program was linked without the kernel's launcher");
     HIPCHK(hipSetDevice(h->device));
     lmh_launch_metrics_reset(d_metrics, h->B, z_min, tilt_max, (hipStream_t)stream);
     HIPCHK(hipGetLastError());
@@ -872,7 +841,6 @@ extern "C" int lmh_ik_batch(lmh_handle *h, const double *d_q_start, const double
     if (!d_q_start || !d_targets || !d_q) refusal = "lmh_ik_batch: null device pointer";
     else if (n_targets < 0) refusal = "lmh_ik_batch: n_targets must be >= 0";
     else if (n_targets > 1 && d_q == d_q_start) refusal = "lmh_ik_batch: d_q may alias d_q_start only when n_targets == 1";
-    if (!refusal && !lmh_launch_ik_batch) return fail(LMH_ERR_NOT_READY, "lmh_ik_batch: this program was linked without the kernel's launcher");
     // the records are read on the device and no launch slot is taken: nothing of the handle is written, nothing is staged on the host
     return launch(h, refusal, [&] { if (n_targets > 0) lmh_launch_ik_batch(&h->P, d_q_start, d_targets, n_targets, d_q, d_iters, d_crit, (hipStream_t)stream); });
 }
@@ -881,9 +849,7 @@ extern "C" int lmh_ik_batch(lmh_handle *h, const double *d_q_start, const double
 // the records are read on the device and no launch slot is taken: nothing of the handle is written, nothing is staged on the host
 extern "C" int lmh_mpc_step(lmh_handle *h, const double *d_lip, double *d_mpc, void *stream)
 {
-    const char *refusal = (!d_lip || !d_mpc) ? "lmh_mpc_step: null device pointer" : nullptr;
-    if (!refusal && !lmh_launch_mpc_step) return fail(LMH_ERR_NOT_READY, "lmh_mpc_step: this program was linked without the kernel's launcher");
-    return launch(h, refusal, [&] { lmh_launch_mpc_step(&h->P, d_lip, d_mpc, (hipStream_t)stream); });
+    return launch(h, (!d_lip || !d_mpc) ? "lmh_mpc_step: null device pointer" : nullptr, [&] { lmh_launch_mpc_step(&h->P, d_lip, d_mpc, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_mpc_rollout(lmh_handle *h, double *d_lip, int n_ticks, double *d_traj, void *stream)
@@ -891,15 +857,12 @@ extern "C" int lmh_mpc_rollout(lmh_handle *h, double *d_lip, int n_ticks, double
     const char *refusal = nullptr;
     if (!d_lip) refusal = "lmh_mpc_rollout: null device pointer";
     else if (n_ticks < 0) refusal = "lmh_mpc_rollout: n_ticks must be >= 0";
-    if (!refusal && !lmh_launch_mpc_rollout) return fail(LMH_ERR_NOT_READY, "lmh_mpc_rollout: this program was linked without the kernel's launcher");
     return launch(h, refusal, [&] { if (n_ticks > 0) lmh_launch_mpc_rollout(&h->P, d_lip, n_ticks, d_traj, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_mpc_preview(lmh_handle *h, const double *d_lip, double *d_preview, void *stream)
 {
-    const char *refusal = (!d_lip || !d_preview) ? "lmh_mpc_preview: null device pointer" : nullptr;
-    if (!refusal && !lmh_launch_mpc_preview) return fail(LMH_ERR_NOT_READY, "lmh_mpc_preview: this program was linked without the kernel's launcher");
-    return launch(h, refusal, [&] { lmh_launch_mpc_preview(&h->P, h->cfg.alpha, h->cfg.beta, d_lip, d_preview, (hipStream_t)stream); });
+    return launch(h, (!d_lip || !d_preview) ? "lmh_mpc_preview: null device pointer" : nullptr, [&] { lmh_launch_mpc_preview(&h->P, h->cfg.alpha, h->cfg.beta, d_lip, d_preview, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_eval_host(lmh_handle *h, const double *q, const double *dq, double t, double *tau, double *f, double *qdd, int32_t *status)
@@ -948,26 +911,26 @@ extern "C" int lmh_robot_com_host(lmh_handle *h, const double *q, double *com)
 }
 
 // ---------------------------------------------------------------------------- rigid-body terms, inverse / forward dynamics
-// mode: 0 terms, 1 inverse dynamics, 2 forward dynamics (lmh_kernels.hip, lmh_terms_kernel).  The kernels read h->P's model tables only.
+// The kernels read h->P's model tables only.
 static int terms_body(lmh_handle *h, int mode, const double *d_q, const double *d_v, const double *d_x, const double *d_w, double *d_res, int32_t *d_flags, void *stream)
 {
-    return launch(h, (!d_q || !d_res || (mode != 0 && !d_x)) ? "null device pointer" : nullptr,
+    return launch(h, (!d_q || !d_res || (mode != TM_TERMS && !d_x)) ? "null device pointer" : nullptr,
                   [&] { lmh_launch_terms(&h->P, mode, d_q, d_v, d_x, d_w, d_res, d_flags, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_terms(lmh_handle *h, const double *d_q, const double *d_v, double *d_terms, void *stream)
 {
-    return terms_body(h, 0, d_q, d_v, nullptr, nullptr, d_terms, nullptr, stream);
+    return terms_body(h, TM_TERMS, d_q, d_v, nullptr, nullptr, d_terms, nullptr, stream);
 }
 
 extern "C" int lmh_inverse_dynamics(lmh_handle *h, const double *d_q, const double *d_v, const double *d_qdd, const double *d_w, double *d_tau30, void *stream)
 {
-    return terms_body(h, 1, d_q, d_v, d_qdd, d_w, d_tau30, nullptr, stream);
+    return terms_body(h, TM_INVDYN, d_q, d_v, d_qdd, d_w, d_tau30, nullptr, stream);
 }
 
 extern "C" int lmh_forward_dynamics(lmh_handle *h, const double *d_q, const double *d_v, const double *d_tau30, const double *d_w, double *d_qdd, int32_t *d_flags, void *stream)
 {
-    return terms_body(h, 2, d_q, d_v, d_tau30, d_w, d_qdd, d_flags, stream);
+    return terms_body(h, TM_FWDDYN, d_q, d_v, d_tau30, d_w, d_qdd, d_flags, stream);
 }
 
 // ---------------------------------------------------------------------------- torque-driven plant
@@ -985,8 +948,7 @@ static int plant_constants_ok(const lmh_handle *h)
     return LMH_OK;
 }
 
-// mode: 0 contact wrench, 1 derivative, 2 RK4 step (lmh_kernels.hip, lmh_plant_kernel).  The caller has found the handle ready and checked
-// its required pointers, which come before the constants in the order of the refusals.
+// The caller has found the handle ready and checked its required pointers, which come before the constants in the order of the refusals.
 static int plant_body(lmh_handle *h, int mode, const double *d_q, const double *d_v, const double *d_tau30, double *d_state, double *d_xdot, double *d_contact, int32_t *d_flags,
                       int n_substeps, void *stream)
 {
@@ -998,14 +960,14 @@ extern "C" int lmh_contact_wrench(lmh_handle *h, const double *d_q, const double
 {
     int rc = ready(h); if (rc) return rc;
     if (!d_q || !d_contact) return fail(LMH_ERR_BAD_ARG, "lmh_contact_wrench: null device pointer");
-    return plant_body(h, 0, d_q, d_v, nullptr, nullptr, nullptr, d_contact, nullptr, 0, stream);
+    return plant_body(h, PM_CONTACT, d_q, d_v, nullptr, nullptr, nullptr, d_contact, nullptr, 0, stream);
 }
 
 extern "C" int lmh_plant_derivative(lmh_handle *h, const double *d_q, const double *d_v, const double *d_tau30, double *d_xdot, double *d_contact, int32_t *d_flags, void *stream)
 {
     int rc = ready(h); if (rc) return rc;
     if (!d_q || !d_v || !d_xdot) return fail(LMH_ERR_BAD_ARG, "lmh_plant_derivative: null device pointer");
-    return plant_body(h, 1, d_q, d_v, d_tau30, nullptr, d_xdot, d_contact, d_flags, 0, stream);
+    return plant_body(h, PM_DERIV, d_q, d_v, d_tau30, nullptr, d_xdot, d_contact, d_flags, 0, stream);
 }
 
 extern "C" int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_tau30, int n_substeps, int32_t *d_flags, void *stream)
@@ -1014,7 +976,7 @@ extern "C" int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_ta
     if (!d_state) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step: null device pointer");
     if (n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step: n_substeps must be >= 0");
     if (n_substeps == 0) return plant_constants_ok(h);               // nothing to enqueue
-    return plant_body(h, 2, nullptr, nullptr, d_tau30, d_state, nullptr, nullptr, d_flags, n_substeps, stream);
+    return plant_body(h, PM_STEP, nullptr, nullptr, d_tau30, d_state, nullptr, nullptr, d_flags, n_substeps, stream);
 }
 
 // ---------------------------------------------------------------------------- zero-order-hold closed loop
@@ -1029,7 +991,6 @@ extern "C" int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, in
     if (n_ticks < 0 || n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: n_ticks and n_substeps must be >= 0");
     if (h->cfg.precision != LMH_PRECISION_FP64) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: LMH_PRECISION_FP64 handles only (this handle's precision has no instantiation of the kernel)");
     rc = plant_constants_ok(h); if (rc) return rc;
-    if (!lmh_launch_rollout_zoh) return fail(LMH_ERR_NOT_READY, "lmh_rollout_zoh: this program was linked without the kernel's launcher");
     if (n_ticks == 0) return LMH_OK;                                 // nothing to enqueue
     return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, n_ticks, n_substeps, (hipStream_t)stream); });
 }

@@ -31,6 +31,7 @@
 #include <stdlib.h>
 #include <type_traits>
 #include "lmh_device.h"
+#include "lmh_launch.h"
 
 // The parameter block is read through the CONSTANT address space: a wave-uniform load from it is a scalar-cache s_load into SGPRs
 // (a generic pointer makes every field read a vector flat_load followed by a full s_waitcnt).  The block is written by the host
@@ -4481,7 +4482,6 @@ extern "C" void lmh_launch_com(const LmhDevParams *P, const double *q, double *c
 // TERMS expands the compact on-chip forms (Mtop | Hl, Jc) into the dense record; INVDYN forms tau30 = M qdd + C - J'w from them;
 // FWDDYN builds the dense [M | tau30 + J'w - C] (30 x 31, row stride 31) behind the robot's image and eliminates it without pivoting
 // (right-looking LDL': the multipliers are L, the pivots D; M is SPD), the pattern of the IK kernel's solve less its pivot search.
-enum { TM_TERMS = 0, TM_INVDYN = 1, TM_FWDDYN = 2 };
 enum { TM_A = LDS_DOUBLES, TM_X = LDS_DOUBLES + 930, TM_W = LDS_DOUBLES + 960, TM_LDS = LDS_DOUBLES + 1040 };    // the IK kernel's extent
 static_assert(TM_LDS * sizeof(double) <= 65536, "one workgroup's LDS");
 static_assert(LMH_TERMS_OFF_T + 336 == LMH_TERMS_STRIDE && LMH_TERMS_OFF_COMVEL == LMH_TERMS_OFF_COM + 3 && LMH_TERMS_OFF_ANGMOM == LMH_TERMS_OFF_COM + 6
@@ -4614,7 +4614,6 @@ __global__ void __launch_bounds__(64) lmh_terms_kernel(LmhDevParams P_arg, const
 // STEP keeps (q, v) in registers, lane i < 60 = component i as in the rollout (rk4_stage), for all substeps of the launch: HBM sees the
 // state record once in and once out; v_prev and the pads of the record are not written.  The contact constants are the robot's own
 // (params_of_robot); the kernel reads no other per-robot parameter.
-enum { PM_CONTACT = 0, PM_DERIV = 1, PM_STEP = 2 };
 static_assert(LMH_CONTACT_STRIDE == 12 + 24 + 4, "w | vertex forces | pad");
 
 // the contact wrench of the state in L[P_Q], L[P_V] -> PL_DW (PL_VF: the vertex forces); the tree phases up to the Jacobian have run
@@ -4946,7 +4945,6 @@ extern "C" void lmh_launch_gen_walk(const LmhWalkSpec *W, double *zx, double *zy
 {
     hipLaunchKernelGGL(lmh_gen_walk_kernel, dim3(1), dim3(256), 0, s, *W, (const LmhWalkSpec *)nullptr, 2 * W->num_steps + 2, zx, zy, phase, segs, sos);
 }
-// d_specs: DEVICE [n_plans], each with n_samples set to the shared grid; seg_stride: segment records per robot
 extern "C" void lmh_launch_gen_walk_batch(const LmhWalkSpec *d_specs, int n_plans, int seg_stride, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos, hipStream_t s)
 {
     LmhWalkSpec none = {};
@@ -4975,7 +4973,6 @@ extern "C" void lmh_launch_eval(const LmhDevParams *P, double *state, double *ou
     else hipLaunchKernelGGL((lmh_eval_kernel<false, double>), dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, state, out, status, debug);
 }
 #endif
-// d_P: device copy of *P (the rollout kernel reads its parameters through a pointer, see lmh_rollout_kernel)
 // Workgroups the device holds at once: LDS admits four robots per CU (40 KB each of 160 KB).
 static int rollout_resident_groups()
 {
@@ -4995,7 +4992,7 @@ static int rollout_resident_groups()
     return cached[dev];
 }
 // Diagnostic (scripts/occupancy_probe.py): what the runtime's occupancy calculator and the code object say about lmh_rollout_kernel<double>:
-// workgroups per CU, architected registers per lane, static LDS per workgroup.  Not part of the C ABI of include/lmh.h.
+// workgroups per CU, architected registers per lane, static LDS per workgroup.
 extern "C" int lmh_debug_rollout_occupancy(int *groups_per_cu, int *num_regs, int *static_lds_bytes)
 {
     hipFuncAttributes at;
@@ -5007,7 +5004,7 @@ extern "C" int lmh_debug_rollout_occupancy(int *groups_per_cu, int *num_regs, in
 }
 // Diagnostic: which experiment switches THIS library was compiled with (bit 0 LMH_POISON, bit 1 LMH_SUBSTAMPS, bit 2 a non-default
 // LMH_SPIN_LIMIT, bit 3 LMH_NUM_VGPR, bit 4 LMH_LDS_PROBE_DOUBLES, bit 5 LMH_TEST_LOSE_PUSH); the checker tests assert it, so that a variant library built without
-// its flag cannot pass them vacuously.  Not part of the C ABI of include/lmh.h.
+// its flag cannot pass them vacuously.
 extern "C" int lmh_debug_build_flags(void)
 {
     int f = 0;
@@ -5029,10 +5026,8 @@ extern "C" int lmh_debug_build_flags(void)
 #endif
     return f;
 }
-// d_ticket: zero-initialised device memory owned by this launch until it completes (work-unit counters, ring, progress: see the kernel)
-// metrics: the per-robot records of lmh_rollout_metrics (never together with a trace), NULL = none
-static void launch_rollout(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks, double *trace, int trace_every,
-                           double *metrics, hipStream_t s)
+extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks,
+                                   double *trace, int trace_every, double *metrics, hipStream_t s)
 {
     const int slots = rollout_resident_groups();
     const dim3 grid((unsigned)((P->n_instances < slots) ? P->n_instances : slots));
@@ -5057,14 +5052,6 @@ static void launch_rollout(const LmhDevParams *P, const LmhDevParams *d_P, int *
     LMH_LAUNCH_ROLLOUT(double, false);
 #undef LMH_LAUNCH_ROLLOUT
 #undef LMH_LAUNCH_ROLLOUT_AS
-}
-extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks, double *trace, int trace_every, hipStream_t s)
-{
-    launch_rollout(P, d_P, d_ticket, state, out, status, log, n_ticks, trace, trace_every, nullptr, s);
-}
-extern "C" void lmh_launch_rollout_metrics(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks, double *metrics, hipStream_t s)
-{
-    launch_rollout(P, d_P, d_ticket, state, out, status, log, n_ticks, nullptr, 0, metrics, s);
 }
 #ifndef LMH_ROLLOUT_ONLY
 // the identity record of lmh_metrics_reset for n robots (grid-stride over the words)

@@ -1,0 +1,38 @@
+// lmh_launch.h -- the seam between the host layer (lmh_capi.hip) and the kernels (lmh_kernels.hip, lmh_mpc.hip): every kernel launcher and the two
+// lmh_debug_* diagnostics, declared once.  All three files include it, so a definition that disagrees with its declaration does not compile.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "lmh_device.h"
+
+enum { TM_TERMS, TM_INVDYN, TM_FWDDYN };    // lmh_launch_terms: the dense terms record | inverse dynamics | forward dynamics (lmh_terms_kernel)
+enum { PM_CONTACT, PM_DERIV, PM_STEP };     // lmh_launch_plant: contact wrench | derivative | RK4 step (lmh_plant_kernel)
+
+extern "C" void lmh_launch_model(const double *raw, double *model, int n_models, const double *lcoef, hipStream_t s);
+extern "C" void lmh_launch_params_expand(const LmhDevParams *P, const double *d_rec, const double *d_gcol_tab, LmhDevParams *d_blocks, int n, hipStream_t s);
+extern "C" void lmh_launch_gen_walk(const LmhWalkSpec *W, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos, hipStream_t s);
+extern "C" void lmh_launch_gen_jump(int n, double time_step, double stance_time, double flight_time, double *zx, double *zy, uint8_t *phase, hipStream_t s);
+// d_specs: DEVICE [n_plans], each with n_samples set to the shared grid; seg_stride: segment records per robot
+extern "C" void lmh_launch_gen_walk_batch(const LmhWalkSpec *d_specs, int n_plans, int seg_stride, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos, hipStream_t s);
+extern "C" void lmh_launch_gen_jump_batch(int n, double time_step, const LmhJumpSpec *d_specs, int n_plans, double *zx, double *zy, uint8_t *phase, hipStream_t s);
+extern "C" void lmh_launch_eval(const LmhDevParams *P, double *state, double *out, int32_t *status, double *debug, hipStream_t s);
+// d_P: device copy of *P (the rollout kernel reads its parameters through a pointer, see lmh_rollout_kernel)
+// d_ticket: zero-initialised device memory owned by this launch until it completes (work-unit counters, ring, progress: see the kernel)
+// trace, trace_every: the samples of lmh_rollout_trace, NULL and 0 = none; metrics: the records of lmh_rollout_metrics, NULL = none; never both
+extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks,
+                                   double *trace, int trace_every, double *metrics, hipStream_t s);
+extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, int n_ticks, int n_substeps, hipStream_t s);
+extern "C" void lmh_launch_metrics_reset(double *metrics, int n_instances, double z_min, double tilt_max, hipStream_t s);
+extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
+extern "C" void lmh_launch_com(const LmhDevParams *P, const double *q, double *com, hipStream_t s);
+extern "C" void lmh_launch_ik(const LmhDevParams *P, double *q, const LmhIkTarget *target, int32_t *iters, hipStream_t s);
+extern "C" void lmh_launch_ik_batch(const LmhDevParams *P, const double *q_start, const double *targets, int n_targets, double *q, int32_t *iters, double *crit, hipStream_t s);
+extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *q, const double *v, const double *x, const double *w, double *res, int32_t *flags, hipStream_t s);
+extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact, int32_t *flags,
+                                 int n_substeps, hipStream_t s);
+extern "C" void lmh_launch_mpc_step(const LmhDevParams *P, const double *lip, double *mpc, hipStream_t s);
+extern "C" void lmh_launch_mpc_rollout(const LmhDevParams *P, double *lip, int n_ticks, double *traj, hipStream_t s);
+extern "C" void lmh_launch_mpc_preview(const LmhDevParams *P, double alpha, double beta, const double *lip, double *preview, hipStream_t s);
+// Diagnostics exported beside the C ABI of include/lmh.h, not part of it (capi.DEBUG_PROTOTYPES binds them): see their definitions
+extern "C" int lmh_debug_rollout_occupancy(int *groups_per_cu, int *num_regs, int *static_lds_bytes);
+extern "C" int lmh_debug_build_flags(void);

@@ -16,6 +16,7 @@
 #include <stdint.h>
 #include "../../include/lmh.h"
 #include "lmh_device.h"
+#include "lmh_launch.h"
 
 #define LANE ((int)(threadIdx.x & 63u))
 #define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)

@@ -12,12 +12,13 @@
 #include <vector>
 #include "lmh.h"
 
-// the kernel launchers live in lmh_kernels.hip, which is not part of this program: nothing here may get as far as a launch
+// every kernel launcher of csrc/lmh_launch.h is a stub here (a missing one does not link): nothing in this program may get as far as a launch
 #define LAUNCH_STUB(name) extern "C" void name(void) { std::fprintf(stderr, #name " was reached\n"); std::abort(); }
 LAUNCH_STUB(lmh_launch_eval) LAUNCH_STUB(lmh_launch_rollout) LAUNCH_STUB(lmh_launch_model) LAUNCH_STUB(lmh_launch_com)
 LAUNCH_STUB(lmh_launch_ik) LAUNCH_STUB(lmh_launch_gen_walk) LAUNCH_STUB(lmh_launch_gen_jump) LAUNCH_STUB(lmh_launch_gen_walk_batch)
 LAUNCH_STUB(lmh_launch_gen_jump_batch) LAUNCH_STUB(lmh_launch_terms) LAUNCH_STUB(lmh_launch_plant) LAUNCH_STUB(lmh_launch_params_expand)
-LAUNCH_STUB(lmh_launch_summary)
+LAUNCH_STUB(lmh_launch_summary) LAUNCH_STUB(lmh_launch_rollout_zoh) LAUNCH_STUB(lmh_launch_metrics_reset) LAUNCH_STUB(lmh_launch_ik_batch)
+LAUNCH_STUB(lmh_launch_mpc_step) LAUNCH_STUB(lmh_launch_mpc_rollout) LAUNCH_STUB(lmh_launch_mpc_preview)
 
 static int g_failures = 0;
 static void expect(bool ok, const std::string &what)
@@ -162,6 +163,14 @@ static void check_null_handles()
     TEXT("null handle", lmh_terms_host(nullptr, x, x, x));
     TEXT("bad argument", lmh_set_prev_velocity_host(nullptr, x));
     TEXT("null handle", lmh_synchronize(nullptr, nullptr));
+    TEXT("null handle", lmh_rollout_zoh(nullptr, x, x, i4, nullptr, nullptr, 1, 1, nullptr));
+    TEXT("null handle", lmh_rollout_metrics(nullptr, x, x, i4, nullptr, 1, x, nullptr));
+    TEXT("null handle", lmh_metrics_reset(nullptr, x, 0.1, 0.5, nullptr));
+    TEXT("null handle", lmh_ik_batch(nullptr, x, x, 1, x + 30, i4, x, nullptr));
+    TEXT("null handle", lmh_mpc_step(nullptr, x, x, nullptr));
+    TEXT("null handle", lmh_mpc_rollout(nullptr, x, 1, x, nullptr));
+    TEXT("null handle", lmh_mpc_preview(nullptr, x, x, nullptr));
+    TEXT("null handle", lmh_mpc_step_host(nullptr, x, x));
 #undef TEXT
     expect(lmh_trace_samples(10, 3) == 3 && lmh_trace_samples(10, 0) == 0 && lmh_trace_samples(0, 3) == 0 && lmh_trace_samples(2, 3) == 0 &&
            lmh_trace_samples(10, -1) == 0, "lmh_trace_samples");

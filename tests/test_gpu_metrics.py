@@ -23,7 +23,6 @@ import json, os, sys
 sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
 from linearmpchumanoid_amd import capi
 from metrics_cases import POISON_FOLD_CASES, first_flag_case, fold_against_trace
-capi.lib().lmh_debug_build_flags.restype = int
 res = {"build_flags": capi.lib().lmh_debug_build_flags(), "fold": [fold_against_trace(*c) for c in POISON_FOLD_CASES], "flag": first_flag_case()}
 print(json.dumps(res))
 """

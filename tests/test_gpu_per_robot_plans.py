@@ -497,7 +497,6 @@ import numpy as np, torch
 from linearmpchumanoid_amd import capi
 from linearmpchumanoid_amd.controller import BatchedController, default_config
 from plan_draw import SIM_TIME, draw_walk_specs
-capi.lib().lmh_debug_build_flags.restype = int
 ik = json.load(open("tests/golden/ik_posture.json"))
 B = 256
 sp, xs = draw_walk_specs(B)

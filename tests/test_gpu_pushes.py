@@ -19,7 +19,6 @@ import json, os, sys
 sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
 from linearmpchumanoid_amd import capi
 from push_cases import in_kernel_against_split
-capi.lib().lmh_debug_build_flags.restype = int
 res = in_kernel_against_split(precision=int(sys.argv[1]), plant=int(sys.argv[2]))
 res["build_flags"] = capi.lib().lmh_debug_build_flags()
 print(json.dumps(res))

@@ -99,7 +99,6 @@ sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "t
 import numpy as np, torch                     # torch before the library is loaded, as in the suite's other children
 from linearmpchumanoid_amd import capi
 from qp_tiles_cases import walk_run
-capi.lib().lmh_debug_build_flags.restype = int
 q0 = np.load(sys.argv[1])
 res = walk_run(q0["q0"], float(q0["zcom"]))
 np.savez(sys.argv[2], **res)

@@ -28,7 +28,6 @@ from linearmpchumanoid_amd.controller import BatchedController, default_config
 from helpers import perturbed_velocities
 ik = json.load(open("tests/golden/ik_posture.json"))
 B, NT = 96, 620                                    # 620 ticks = chunks of 250 + 250 + 120: every robot passes through the ring queue twice
-capi.lib().lmh_debug_build_flags.restype = int
 ctl = BatchedController(B, default_config(dt=1e-3, time_horizon=0.32 + 1e-9, z_com=ik["z_com"], mpc_dt=1e-2, warm_start=1))
 ctl.gen_walk(2.0, num_steps=3, time_per_step=0.3, ds_time=0.1, step_height=0.02, settle_time=0.05)
 ctl.set_xscale(np.linspace(0.02, 0.05, B))
@@ -98,7 +97,7 @@ def test_poison_build_really_is_the_poison_build():
     with -DLMH_POISON (lmh_debug_build_flags bit 0), the shipped one was not."""
     code = ("import json, os, sys; sys.path.insert(0, os.getcwd())\n"
             "from linearmpchumanoid_amd import capi\n"
-            "L = capi.lib(); L.lmh_debug_build_flags.restype = int\n"
+            "L = capi.lib()\n"
             "print(json.dumps({'flags': L.lmh_debug_build_flags(), 'so': capi.SO_PATH}))\n")
     from linearmpchumanoid_amd import build as hipbuild
     hipbuild.build_variant("poison")

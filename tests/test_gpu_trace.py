@@ -20,7 +20,6 @@ import json, os, sys
 sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
 from linearmpchumanoid_amd import capi
 from trace_cases import SPLIT_CASES, trace_against_split
-capi.lib().lmh_debug_build_flags.restype = int
 res = {"build_flags": capi.lib().lmh_debug_build_flags(), "cases": [trace_against_split(*c) for c in SPLIT_CASES]}
 print(json.dumps(res))
 """
