@@ -118,6 +118,7 @@ extern "C" {
 #define LMH_MPC_OFF_T 12          /* its clock */
 #define LMH_MPC_OFF_K 13          /* the preview index k = (int)(t / mpc_dt), as a double */
 #define LMH_MPC_OFF_FLAGS 14      /* this sample's flags (LMH_FLAG_ZMP_RANGE, LMH_FLAG_NONFINITE), as a double; [15] zero */
+#define LMH_MPC_OFF_ACTIVE 15     /* lmh_mpc_box_step / lmh_mpc_box_rollout only: the active samples of both axes, as a double */
 #define LMH_MPC_PREVIEW_STRIDE 536 /* one horizon preview record, see lmh_mpc_preview: a header of 8, then eight arrays of 66 */
 /* offsets into one preview record (doubles); of every array the entries beyond the count named are zero */
 #define LMH_MPC_PREVIEW_OFF_K 0       /* the preview index, as a double */
@@ -131,6 +132,22 @@ extern "C" {
 #define LMH_MPC_PREVIEW_OFF_CV_X 338  /* [N + 2] its velocity */
 #define LMH_MPC_PREVIEW_OFF_C_Y 404   /* [N + 2] */
 #define LMH_MPC_PREVIEW_OFF_CV_Y 470  /* [N + 2] */
+#define LMH_MPC_BOX_STRIDE 668     /* one constrained preview record, see lmh_mpc_box_preview: the preview record, then two arrays of 66 */
+/* the words a constrained preview record has beyond the LMH_MPC_PREVIEW_OFF_* layout (doubles; [7] stays zero) */
+#define LMH_MPC_BOX_OFF_ROUNDS_X 3    /* exchange rounds taken in x, as a double */
+#define LMH_MPC_BOX_OFF_ROUNDS_Y 4
+#define LMH_MPC_BOX_OFF_ACTIVE_X 5    /* active samples in x, as a double */
+#define LMH_MPC_BOX_OFF_ACTIVE_Y 6
+#define LMH_MPC_BOX_OFF_LAM_X 536     /* [N + 1] multipliers of the x bounds: > 0 at an upper bound, < 0 at a lower one, 0 exactly at an inactive sample */
+#define LMH_MPC_BOX_OFF_LAM_Y 602     /* [N + 1] */
+/* the rows of one set of bounds d_box[set][4][n_samples], see lmh_mpc_box_preview */
+#define LMH_BOX_LO_X 0
+#define LMH_BOX_HI_X 1
+#define LMH_BOX_LO_Y 2
+#define LMH_BOX_HI_Y 3
+/* exchange rounds per axis and solve before lmh_mpc_box_* give up with LMH_FLAG_QP_MAXITER and keep the last iterate: four times the largest
+ * number of samples, twice what lets every sample of a window enter and leave its working set once (2 (N + 1)) */
+#define LMH_MPC_BOX_MAX_ROUNDS 260
 
 /* status flags */
 #define LMH_FLAG_QP_MAXITER 1     /* active-set iteration cap hit (reference: "QP failed", controller.cpp:472-476) */
@@ -139,6 +156,7 @@ extern "C" {
 #define LMH_FLAG_NOT_SPD 8        /* a Cholesky pivot was not positive */
 #define LMH_FLAG_UNFINISHED 32    /* lmh_rollout only: a wait of the kernel's work queue ran out and this robot did not get all its ticks (its state / out
                                    * records are those of the last chunk it completed); the call reports LMH_ERR_UNFINISHED, see lmh_rollout */
+#define LMH_FLAG_BOX_EMPTY 64      /* lmh_mpc_box_* only: a sample of the window has lo > hi or a NaN bound; the robot's results are NaN */
 #define LMH_FLAG_QP_FP64_ROUTE 16 /* LMH_PRECISION_FP32 only, informational: a contact-force solve of this instance met a rank-deficient free set
                                    * (or the Lawson-Hanson pass) and went the fp64 general route -- that system (cond ~1e13) has no fp32 form */
 
@@ -606,6 +624,52 @@ int lmh_mpc_rollout(lmh_handle *h, double *d_lip, int n_ticks, double *d_traj, v
  * of a controller evaluation.  A pivot that is not positive raises LMH_FLAG_NOT_SPD in the header and leaves NaNs in the arrays (lmh_create
  * and lmh_set_zcom refuse such a Hessian, so a handle that exists does not get there); LMH_FLAG_NONFINITE: an entry is not finite. */
 int lmh_mpc_preview(lmh_handle *h, const double *d_lip, double *d_preview, void *stream);
+
+/* ---- The preview problem with the predicted ZMP held inside the support polygon (the reference hands its QP solver no bounds,
+ * src/mpcLinearPendulum.cpp:120-127; build-defined).  Per robot and axis, with n = N + 1, p = Px x_k and z the clamped, xscale-scaled window
+ * of lmh_mpc_preview:
+ *     min_U  1/2 alpha |U|^2 + 1/2 beta |p + Pu U - z|^2     s.t.   lo_j <= (p + Pu U)_j <= hi_j,  j = 0 .. N
+ * Pu is lower triangular with D != 0 on its diagonal, so the problem is feasible whenever lo_j <= hi_j, strictly convex (one solution), and
+ * the Schur complement of every working set is positive definite.
+ *   d_box  DEVICE [n_sets][4][n_samples], rows lo_x | hi_x | lo_y | hi_y (LMH_BOX_*), read at the same clamped indices k + j as z.  Metres,
+ *          absolute: NOT multiplied by xscale (a sole does not stretch with the step length).  -INFINITY / +INFINITY: no bound.
+ *          n_sets = 1: one set for every robot; n_sets = n_instances: one per robot.  n_samples must be lmh_num_ref_samples(h).
+ * The wording and refusal rules are those of the lmh_mpc_* block above: NULL for a required pointer, a negative count, another n_samples or
+ * an n_sets other than 1 or n_instances returns LMH_ERR_BAD_ARG before anything is enqueued; a count of 0 enqueues nothing; asynchronous on
+ * `stream`, no launch slot, no host staging, nothing written into the handle (the bounds travel in the kernel arguments and the handle
+ * keeps nothing of them), capturable from the first call.  One wave per robot, fp64, the factor of H and the working set's system in LDS.
+ * Method: working-set rounds on lmh_mpc_preview's factor.  An iterate belongs to a working set W (each of its samples at one side, b_W the
+ * bounds there): lambda_W = S^-1 (Z0_W - b_W) with S = Pu_W H^-1 Pu_W' and Z0 = p + Pu U0, U0 = -H^-1 g; U = -H^-1 (g + Pu' lambda);
+ * Z = p + Pu U.  It is wrong at an inactive sample with Z_j < lo_j or Z_j > hi_j and at an active one whose multiplier has the wrong sign,
+ * compared exactly in fp64.  Nothing wrong: done.  Otherwise a round: while the number of wrong samples has just reached a new minimum, or
+ * at most three rounds after it did, all violated samples enter and all wrong-signed ones leave together; after that only the wrong sample
+ * of the largest index changes (Judice-Pires, Kim-Park; the whole-body solver's bpp_rounds follows the same idea).  Every solve starts
+ * from the empty working set.  After LMH_MPC_BOX_MAX_ROUNDS rounds of an axis without an end: LMH_FLAG_QP_MAXITER and the last iterate.
+ * A window sample with !(lo <= hi) in either axis (a NaN bound included): LMH_FLAG_BOX_EMPTY, and NaNs for U, Z, lambda and the CoM
+ * arrays.  Neither disturbs another robot.
+ *
+ * lmh_mpc_box_preview: d_record [B][LMH_MPC_BOX_STRIDE].  Words [0, 536) have lmh_mpc_preview's layout with U, Z and the CoM arrays of the
+ * constrained solution; [3], [4]: rounds taken in x, in y; [5], [6]: active samples in x, in y; [7]: 0; then LAM_X and LAM_Y
+ * (LMH_MPC_BOX_OFF_*), N + 1 used entries each, tails zero.  A multiplier is > 0 at an upper bound, < 0 at a lower bound and 0 exactly at
+ * an inactive sample; for an active sample Z_j is written as the bound itself; without LMH_FLAG_QP_MAXITER every Z_j satisfies
+ * lo_j <= Z_j <= hi_j exactly.  Flags: lmh_mpc_preview's, LMH_FLAG_QP_MAXITER, LMH_FLAG_BOX_EMPTY (LMH_FLAG_NONFINITE covers the
+ * multipliers too; LMH_FLAG_NOT_SPD also when a working set's S has a pivot that is not positive).
+ * Identities, bit for bit:
+ *   (I1) lmh_mpc_box_step's words [0, 8) are formed from this record at the same state: u = U_X[0] / U_Y[0], x_next = A x + B u by
+ *        lmh_mpc_step's expressions, the zmp words Z_X[0] / Z_Y[0].
+ *   (I2) lmh_mpc_box_rollout is the host loop { lmh_mpc_box_step, move the state on, t += mpc_dt }; hence (a + b) is (a) followed by (b).
+ *   (I3) where no bound ever enters a working set (rounds 0 in both axes, an all-infinite box for instance), the first 536 words are byte
+ *        for byte lmh_mpc_preview's record: one copy of the set-up, factorisation and solves serves both kernels. */
+int lmh_mpc_box_preview(lmh_handle *h, const double *d_lip, const double *d_box, int n_samples, int n_sets, double *d_record, void *stream);
+/* One constrained step per robot: an LMH_MPC_STRIDE sample like lmh_mpc_step's with u = U[0] and zmp = Z[0] of the constrained solution
+ * (I1), word LMH_MPC_OFF_ACTIVE the active samples of both axes, and LMH_FLAG_QP_MAXITER / LMH_FLAG_BOX_EMPTY / LMH_FLAG_NOT_SPD among
+ * the flags (LMH_FLAG_NONFINITE: one of the first eight words is not finite).  d_lip is read only.  Unlike lmh_mpc_step, which applies a
+ * stored gain row, every call forms and factors H: about 2 (N + 1)^3 multiply-adds per robot before the first round. */
+int lmh_mpc_box_step(lmh_handle *h, const double *d_lip, const double *d_box, int n_samples, int n_sets, double *d_mpc, void *stream);
+/* The closed loop of lmh_mpc_rollout with the constrained step (I2): d_lip is updated in place, d_traj [n_ticks][B][LMH_MPC_STRIDE] may be
+ * NULL.  H does not depend on the state, so it is factored once per launch and stays in LDS with G = Pu H^-1 Pu'; every tick starts from
+ * the empty working set (no warm start across ticks: it would break (I2)). */
+int lmh_mpc_box_rollout(lmh_handle *h, double *d_lip, const double *d_box, int n_samples, int n_sets, int n_ticks, double *d_traj, void *stream);
 
 /* host-buffer convenience used by the C++ shim (B instances, staged through internal
  * device buffers, synchronous): q/dq [B][30], t, outputs tau[B][24], f[B][12], qdd[B][30] */

@@ -58,12 +58,20 @@ MPC_PREVIEW_ARRAY = 66
 # name -> (offset, entries used at horizon N as a function of N): the LMH_MPC_PREVIEW_OFF_* defines of include/lmh.h
 MPC_PREVIEW_ARRAYS = {"U_x": (8, 1), "U_y": (74, 1), "Z_x": (140, 1), "Z_y": (206, 1),
                       "C_x": (272, 2), "Cv_x": (338, 2), "C_y": (404, 2), "Cv_y": (470, 2)}   # (offset, count - N)
+MPC_BOX_STRIDE = 668          # one constrained preview record (lmh_mpc_box_preview): the preview record | LAM_x(66) | LAM_y(66)
+# the box record's own words: rounds and active samples per axis in the header, the multipliers behind the preview record
+MPC_BOX_HEADER = {"rounds_x": 3, "rounds_y": 4, "active_x": 5, "active_y": 6}
+MPC_BOX_ARRAYS = dict(MPC_PREVIEW_ARRAYS, lam_x=(536, 1), lam_y=(602, 1))
+MPC_OFF_ACTIVE = 15           # an lmh_mpc_box_step sample's active samples of both axes (zero in lmh_mpc_step's)
+MPC_BOX_MAX_ROUNDS = 260      # exchange rounds per axis before LMH_FLAG_QP_MAXITER
+BOX_ROWS = {"lo_x": 0, "hi_x": 1, "lo_y": 2, "hi_y": 3}      # the rows of one set of bounds [4][n_samples]: the LMH_BOX_* defines
 
 FLAG_QP_MAXITER = 1
 FLAG_NONFINITE = 2
 FLAG_ZMP_RANGE = 4
 FLAG_NOT_SPD = 8
 FLAG_QP_FP64_ROUTE = 16
+FLAG_BOX_EMPTY = 64           # lmh_mpc_box_*: a sample of the window has lo > hi or a NaN bound
 FLAG_UNFINISHED = 32          # lmh_rollout: the robot did not get all its ticks (a wait of the kernel's work queue ran out)
 ERR_UNFINISHED = -5
 
@@ -151,6 +159,9 @@ PROTOTYPES = {
     "lmh_mpc_step": (_ip, [_vp, _vp, _vp, _vp]),
     "lmh_mpc_rollout": (_ip, [_vp, _vp, _ip, _vp, _vp]),
     "lmh_mpc_preview": (_ip, [_vp, _vp, _vp, _vp]),
+    "lmh_mpc_box_preview": (_ip, [_vp, _vp, _vp, _ip, _ip, _vp, _vp]),
+    "lmh_mpc_box_step": (_ip, [_vp, _vp, _vp, _ip, _ip, _vp, _vp]),
+    "lmh_mpc_box_rollout": (_ip, [_vp, _vp, _vp, _ip, _ip, _ip, _vp, _vp]),
     "lmh_eval_host": (_ip, [_vp, _vp, _vp, _dp, _vp, _vp, _vp, _vp]),
     "lmh_robot_com_host": (_ip, [_vp, _vp, _vp]),
     "lmh_last_out_host": (_ip, [_vp, _vp]),

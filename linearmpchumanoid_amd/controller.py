@@ -577,6 +577,65 @@ class BatchedController:
         check(capi.lib().lmh_mpc_preview(self._h, _dev_ptr(lip), _dev_ptr(rec), self._stream()))
         return rec
 
+    # -- the box-constrained preview MPC (include/lmh.h, lmh_mpc_box_preview): the predicted ZMP kept inside per-sample bounds
+    def _box(self, box):
+        """box: [4,n_samples] (shared) or [B,4,n_samples] (per robot), rows lo_x | hi_x | lo_y | hi_y in metres (trajectories.zmp_box /
+        zmp_boxes), a tensor or an array -> (contiguous float64 device tensor, n_samples, n_sets)."""
+        t = box if isinstance(box, torch.Tensor) else torch.as_tensor(np.array(box, dtype=np.float64))
+        if t.ndim == 2:
+            t = t.unsqueeze(0)
+        if t.ndim != 3 or t.shape[1] != 4 or t.shape[0] not in (1, self.B) or t.dtype != torch.float64:
+            raise ValueError(f"box must be float64 [4,n_samples] or [{self.B},4,n_samples]")
+        return t.to(self.device).contiguous(), int(t.shape[2]), int(t.shape[0])
+
+    def mpc_box_step(self, lip, box):
+        """lmh_mpc_box_step: the MPC step with the predicted ZMP held inside `box` over the horizon; lip [B,8] (left as it is) ->
+        samples [B,16] (split_mpc; word 15: the active samples of both axes)."""
+        lip = self._batch("lip", lip, capi.LIP_STRIDE)
+        bx, ns, sets = self._box(box)
+        rec = torch.empty((self.B, capi.MPC_STRIDE), dtype=torch.float64, device=self.device)
+        check(capi.lib().lmh_mpc_box_step(self._h, _dev_ptr(lip), _dev_ptr(bx), ns, sets, _dev_ptr(rec), self._stream()))
+        return rec
+
+    def mpc_box_rollout(self, lip, box, n_ticks, traj=True):
+        """lmh_mpc_box_rollout: n_ticks constrained steps of the reduced model in closed loop, in one launch on one factorisation;
+        lip [B,8] is updated in place.  traj as in mpc_rollout."""
+        lip = self._batch("lip", lip, capi.LIP_STRIDE, in_place=True)
+        if int(n_ticks) != n_ticks or n_ticks < 0:
+            raise ValueError("n_ticks must be a whole number >= 0")
+        n = int(n_ticks)
+        bx, ns, sets = self._box(box)
+        tr = torch.zeros((n, self.B, capi.MPC_STRIDE), dtype=torch.float64, device=self.device) if traj is True else (traj if traj is not False else None)
+        if tr is not None and (tr.dtype != torch.float64 or tr.device != self.device or not tr.is_contiguous() or tr.numel() < n * self.B * capi.MPC_STRIDE):
+            raise ValueError(f"traj must be a contiguous [{n},{self.B},{capi.MPC_STRIDE}] float64 tensor on {self.device}")
+        if n > 0:
+            check(capi.lib().lmh_mpc_box_rollout(self._h, _dev_ptr(lip), _dev_ptr(bx), ns, sets, n, _dev_ptr(tr), self._stream()))
+        return tr
+
+    def mpc_box_preview(self, lip, box):
+        """lmh_mpc_box_preview: the whole constrained solution over the horizon with its multipliers; lip [B,8] (left as it is) ->
+        records [B,668] (split_box_preview)."""
+        lip = self._batch("lip", lip, capi.LIP_STRIDE)
+        bx, ns, sets = self._box(box)
+        rec = torch.empty((self.B, capi.MPC_BOX_STRIDE), dtype=torch.float64, device=self.device)
+        check(capi.lib().lmh_mpc_box_preview(self._h, _dev_ptr(lip), _dev_ptr(bx), ns, sets, _dev_ptr(rec), self._stream()))
+        return rec
+
+    @staticmethod
+    def split_box_preview(rec, N=None):
+        """Named views of constrained preview records [.., 668]: what split_preview gives of the first 536 words, rounds_x, rounds_y,
+        active_x, active_y as integers and the multipliers lam_x, lam_y (N + 1 entries: > 0 at an upper bound, < 0 at a lower one, 0 at
+        an inactive sample) -- capi.MPC_BOX_HEADER, capi.MPC_BOX_ARRAYS."""
+        as_int = (lambda v: v.to(torch.int64)) if isinstance(rec, torch.Tensor) else (lambda v: np.asarray(v).astype(np.int64))
+        f = BatchedController.split_preview(rec, N)
+        N = f["U_x"].shape[-1] - 1
+        for name, off in capi.MPC_BOX_HEADER.items():
+            f[name] = as_int(rec[..., off])
+        for name in ("lam_x", "lam_y"):
+            off, extra = capi.MPC_BOX_ARRAYS[name]
+            f[name] = rec[..., off:off + N + extra]
+        return f
+
     @staticmethod
     def split_mpc(rec):
         """Named views of MPC samples [.., 16] (tensor or array): x_ref [..,3], y_ref [..,3], zmp [..,2], state [..,4], t, and k, flags as

@@ -849,7 +849,7 @@ extern "C" int lmh_ik_batch(lmh_handle *h, const double *d_q_start, const double
 // the records are read on the device and no launch slot is taken: nothing of the handle is written, nothing is staged on the host
 extern "C" int lmh_mpc_step(lmh_handle *h, const double *d_lip, double *d_mpc, void *stream)
 {
-    return launch(h, (!d_lip || !d_mpc) ? "lmh_mpc_step: null device pointer" : nullptr, [&] { lmh_launch_mpc_step(&h->P, d_lip, d_mpc, (hipStream_t)stream); });
+    return launch(h, (!d_lip || !d_mpc) ? "lmh_mpc_step: null device pointer" : nullptr, [&] { lmh_launch_mpc_step(&h->P, h->cfg.alpha, h->cfg.beta, d_lip, nullptr, 0, d_mpc, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_mpc_rollout(lmh_handle *h, double *d_lip, int n_ticks, double *d_traj, void *stream)
@@ -857,12 +857,47 @@ extern "C" int lmh_mpc_rollout(lmh_handle *h, double *d_lip, int n_ticks, double
     const char *refusal = nullptr;
     if (!d_lip) refusal = "lmh_mpc_rollout: null device pointer";
     else if (n_ticks < 0) refusal = "lmh_mpc_rollout: n_ticks must be >= 0";
-    return launch(h, refusal, [&] { if (n_ticks > 0) lmh_launch_mpc_rollout(&h->P, d_lip, n_ticks, d_traj, (hipStream_t)stream); });
+    return launch(h, refusal, [&] { if (n_ticks > 0) lmh_launch_mpc_rollout(&h->P, h->cfg.alpha, h->cfg.beta, d_lip, nullptr, 0, n_ticks, d_traj, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_mpc_preview(lmh_handle *h, const double *d_lip, double *d_preview, void *stream)
 {
-    return launch(h, (!d_lip || !d_preview) ? "lmh_mpc_preview: null device pointer" : nullptr, [&] { lmh_launch_mpc_preview(&h->P, h->cfg.alpha, h->cfg.beta, d_lip, d_preview, (hipStream_t)stream); });
+    return launch(h, (!d_lip || !d_preview) ? "lmh_mpc_preview: null device pointer" : nullptr, [&] { lmh_launch_mpc_preview(&h->P, h->cfg.alpha, h->cfg.beta, d_lip, nullptr, 0, d_preview, (hipStream_t)stream); });
+}
+
+// the box-constrained calls: the refusal of the bounds' shape (nullptr = fine) and the stride from one robot's bounds to the next
+static const char *box_refusal(const lmh_handle *h, const void *d_box, int n_samples, int n_sets, const char *null_text, const char *samples_text, const char *sets_text)
+{
+    if (!d_box) return null_text;
+    if (h && n_samples != h->plan.n_samples) return samples_text;
+    if (h && n_sets != 1 && n_sets != h->B) return sets_text;
+    return nullptr;
+}
+static size_t box_stride(const lmh_handle *h, int n_sets) { return (n_sets > 1) ? (size_t)4 * (size_t)h->plan.n_samples : 0; }
+
+extern "C" int lmh_mpc_box_preview(lmh_handle *h, const double *d_lip, const double *d_box, int n_samples, int n_sets, double *d_record, void *stream)
+{
+    const char *refusal = (!d_lip || !d_record) ? "lmh_mpc_box_preview: null device pointer"
+                        : box_refusal(h, d_box, n_samples, n_sets, "lmh_mpc_box_preview: null device pointer",
+                                      "lmh_mpc_box_preview: n_samples must be lmh_num_ref_samples", "lmh_mpc_box_preview: n_sets must be 1 or n_instances");
+    return launch(h, refusal, [&] { lmh_launch_mpc_preview(&h->P, h->cfg.alpha, h->cfg.beta, d_lip, d_box, box_stride(h, n_sets), d_record, (hipStream_t)stream); });
+}
+
+extern "C" int lmh_mpc_box_step(lmh_handle *h, const double *d_lip, const double *d_box, int n_samples, int n_sets, double *d_mpc, void *stream)
+{
+    const char *refusal = (!d_lip || !d_mpc) ? "lmh_mpc_box_step: null device pointer"
+                        : box_refusal(h, d_box, n_samples, n_sets, "lmh_mpc_box_step: null device pointer",
+                                      "lmh_mpc_box_step: n_samples must be lmh_num_ref_samples", "lmh_mpc_box_step: n_sets must be 1 or n_instances");
+    return launch(h, refusal, [&] { lmh_launch_mpc_step(&h->P, h->cfg.alpha, h->cfg.beta, d_lip, d_box, box_stride(h, n_sets), d_mpc, (hipStream_t)stream); });
+}
+
+extern "C" int lmh_mpc_box_rollout(lmh_handle *h, double *d_lip, const double *d_box, int n_samples, int n_sets, int n_ticks, double *d_traj, void *stream)
+{
+    const char *refusal = !d_lip ? "lmh_mpc_box_rollout: null device pointer"
+                        : box_refusal(h, d_box, n_samples, n_sets, "lmh_mpc_box_rollout: null device pointer",
+                                      "lmh_mpc_box_rollout: n_samples must be lmh_num_ref_samples", "lmh_mpc_box_rollout: n_sets must be 1 or n_instances");
+    if (!refusal && n_ticks < 0) refusal = "lmh_mpc_box_rollout: n_ticks must be >= 0";
+    return launch(h, refusal, [&] { if (n_ticks > 0) lmh_launch_mpc_rollout(&h->P, h->cfg.alpha, h->cfg.beta, d_lip, d_box, box_stride(h, n_sets), n_ticks, d_traj, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_eval_host(lmh_handle *h, const double *q, const double *dq, double t, double *tau, double *f, double *qdd, int32_t *status)

@@ -30,9 +30,12 @@ extern "C" void lmh_launch_ik_batch(const LmhDevParams *P, const double *q_start
 extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *q, const double *v, const double *x, const double *w, double *res, int32_t *flags, hipStream_t s);
 extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact, int32_t *flags,
                                  int n_substeps, hipStream_t s);
-extern "C" void lmh_launch_mpc_step(const LmhDevParams *P, const double *lip, double *mpc, hipStream_t s);
-extern "C" void lmh_launch_mpc_rollout(const LmhDevParams *P, double *lip, int n_ticks, double *traj, hipStream_t s);
-extern "C" void lmh_launch_mpc_preview(const LmhDevParams *P, double alpha, double beta, const double *lip, double *preview, hipStream_t s);
+// The three MPC launchers carry the box-constrained variants (lmh_mpc_box_*): box NULL = the unconstrained kernels exactly as they are (alpha, beta and
+// box_stride are then not read by step and rollout); otherwise box + box_stride * robot is that robot's [4][n_samples] bounds (box_stride 0: one shared set)
+// and `mpc` / `traj` / `record` take the constrained call's records (record: LMH_MPC_BOX_STRIDE words per robot instead of LMH_MPC_PREVIEW_STRIDE).
+extern "C" void lmh_launch_mpc_step(const LmhDevParams *P, double alpha, double beta, const double *lip, const double *box, size_t box_stride, double *mpc, hipStream_t s);
+extern "C" void lmh_launch_mpc_rollout(const LmhDevParams *P, double alpha, double beta, double *lip, const double *box, size_t box_stride, int n_ticks, double *traj, hipStream_t s);
+extern "C" void lmh_launch_mpc_preview(const LmhDevParams *P, double alpha, double beta, const double *lip, const double *box, size_t box_stride, double *record, hipStream_t s);
 // Diagnostics exported beside the C ABI of include/lmh.h, not part of it (capi.DEBUG_PROTOTYPES binds them): see their definitions
 extern "C" int lmh_debug_rollout_occupancy(int *groups_per_cu, int *num_regs, int *static_lds_bytes);
 extern "C" int lmh_debug_build_flags(void);

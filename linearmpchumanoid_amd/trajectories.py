@@ -8,7 +8,7 @@ definition on top of the reference's conventions (SupportFoot -> ZMP y of -/+0.0
 """
 import numpy as np
 
-from .capi import FLAG_NONFINITE, FLAG_ZMP_RANGE, IK_TARGET_STRIDE, LIP_STRIDE, MAX_PUSHES, MPC_STRIDE, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE
+from .capi import FLAG_BOX_EMPTY, FLAG_NONFINITE, FLAG_NOT_SPD, FLAG_QP_MAXITER, FLAG_ZMP_RANGE, IK_TARGET_STRIDE, LIP_STRIDE, MAX_PUSHES, MPC_BOX_MAX_ROUNDS, MPC_STRIDE, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE
 
 
 def stance_zmp(simulation_time, time_step, support_foot=2):
@@ -297,6 +297,194 @@ def com_targets(traj, z_com):
     com[..., 0], com[..., 1] = tr[..., 0], tr[..., 3]
     com[..., 2] = z
     return com
+
+
+# ------------------------------------------------------------------------------- the box-constrained preview MPC (lmh_mpc_box_*)
+def zmp_box(plan, xscale=1.0, fwd=0.1, back=0.05, half_width=0.025, margin=0.0):
+    """The support region of every sample of a plan as an axis-aligned box, the `box` argument of mpc_box_step / _rollout / _preview:
+    -> [4, n_samples], rows lo_x | hi_x | lo_y | hi_y in metres (capi.BOX_ROWS).
+    Single support: the stance sole's rectangle (the sole of Robot.cpp:38-42: `fwd` ahead of the foot's origin, `back` behind it,
+    `half_width` to either side) about the stance foot's position in the plan -- the plan's ZMP sample there --, x times xscale, every
+    side moved inwards by `margin`.  Double support: the axis-aligned hull of both soles (the feet's positions from the plan's segment
+    records; a plan without them, stance_zmp / jump_plan, has its feet at zmp_y -+ 0.05 beside zmp_x): exact with the feet side by side,
+    an OUTER approximation of the support polygon with one foot ahead of the other, whose hull has two corners the polygon lacks.
+    PHASE_FLIGHT: -inf | +inf, no bound.  A sole does not stretch with the step length: only the feet's x positions take xscale."""
+    zx, zy = np.asarray(plan["zmp_x"], dtype=np.float64), np.asarray(plan["zmp_y"], dtype=np.float64)
+    n = len(zx)
+    ph = np.asarray(plan["phase"]) if plan.get("phase") is not None else np.full(n, PHASE_DOUBLE)
+    xs = float(xscale)
+    if plan.get("segs") is not None and plan.get("seg_of_sample") is not None:
+        g = np.asarray(plan["segs"], dtype=np.float64)[np.asarray(plan["seg_of_sample"], dtype=np.int64)]
+        xr, yr, xl, yl = g[:, 1], g[:, 1 + 8], g[:, 1 + 24], g[:, 1 + 24 + 8]
+    else:
+        xr, yr, xl, yl = zx, zy + IK_DEFAULT_RF[1], zx, zy + IK_DEFAULT_LF[1]
+    single = (ph == PHASE_RIGHT) | (ph == PHASE_LEFT)
+    x_lo = np.where(single, zx, np.minimum(xr, xl)) * xs
+    x_hi = np.where(single, zx, np.maximum(xr, xl)) * xs
+    y_lo = np.where(single, zy, np.minimum(yr, yl))
+    y_hi = np.where(single, zy, np.maximum(yr, yl))
+    box = np.stack([x_lo - back + margin, x_hi + fwd - margin, y_lo - half_width + margin, y_hi + half_width - margin])
+    box[0::2, ph == PHASE_FLIGHT] = -np.inf
+    box[1::2, ph == PHASE_FLIGHT] = np.inf
+    return box
+
+
+def zmp_boxes(plans, xscale=1.0, fwd=0.1, back=0.05, half_width=0.025, margin=0.0):
+    """zmp_box for per-robot plans (walk_plans / jump_plans: every field [B, ...]) -> [B, 4, n_samples]; xscale and margin: scalars or [B]."""
+    B = np.asarray(plans["zmp_x"]).shape[0]
+    xs, mg = np.broadcast_to(np.asarray(xscale, dtype=np.float64), (B,)), np.broadcast_to(np.asarray(margin, dtype=np.float64), (B,))
+    return np.stack([zmp_box({k: v[i] for k, v in plans.items()}, xs[i], fwd, back, half_width, mg[i]) for i in range(B)])
+
+
+def lip_matrices(N, mpc_dt, z_com, gravity=9.81):
+    """Px [N+1,2] and Pu [N+1,N+1] of the LIPM preview (Mpc3dLip::initialize): Px row j = (1, j mpc_dt); Pu lower triangular Toeplitz,
+    D = -z_com / gravity on the diagonal and mpc_dt^2 / 2 + (m mpc_dt) mpc_dt below it, m = r - c - 1."""
+    dt, n = np.float64(mpc_dt), N + 1
+    j = np.arange(n, dtype=np.float64)
+    Px = np.stack([np.ones(n), j * dt], axis=1)
+    col = (dt * dt) / 2 + (j * dt) * dt
+    Pu = np.zeros((n, n))
+    for c in range(n):
+        Pu[c, c] = -np.float64(z_com) / np.float64(gravity)
+        Pu[c + 1:, c] = col[:n - c - 1]
+    return Px, Pu
+
+
+def box_exchange(H, Pu, g, p, lo, hi, max_rounds=MPC_BOX_MAX_ROUNDS):
+    """One axis of the box-constrained preview problem, min 1/2 U'HU + g'U s.t. lo <= p + Pu U <= hi, by the kernels' exchange rule with
+    dense fp64 solves.  -> dict(U, Z, lam, side [n] (-1 lower, +1 upper, 0 inactive), rounds, flags).
+    An iterate belongs to a working set (each of its samples at one side): lam_W = S^-1 (Z0_W - b_W), S = Pu_W H^-1 Pu_W', Z0 = p + Pu U0,
+    U0 = -H^-1 g; U = -H^-1 (g + Pu' lam); Z = p + Pu U with Z_W = b_W written as the bounds themselves.  It is wrong at an inactive
+    sample with Z < lo or Z > hi and at an active one whose multiplier has the wrong sign (> 0 belongs to an upper bound, < 0 to a lower
+    one), compared exactly.  Nothing wrong: done.  Otherwise a round: while the number of wrong samples has just reached a new minimum,
+    or at most three rounds after it did, all violated samples enter and all wrong-signed ones leave together; after that only the wrong
+    sample of the largest index changes (Judice-Pires, Kim-Park).  max_rounds rounds without an end: FLAG_QP_MAXITER, the last iterate."""
+    n = len(g)
+    U0 = -np.linalg.solve(H, g)
+    Z0 = p + Pu @ U0
+    G = Pu @ np.linalg.solve(H, Pu.T)
+    side = np.zeros(n, dtype=np.int64)
+    U, Z, lam = U0.copy(), Z0.copy(), np.zeros(n)
+    rounds, best, block, flags = 0, n + 1, 3, 0
+    while True:
+        want = side.copy()
+        off = side == 0
+        want[off & (Z < lo)] = -1
+        want[off & (Z > hi)] = 1
+        want[((side > 0) & (lam < 0)) | ((side < 0) & (lam > 0))] = 0
+        bad = np.flatnonzero(want != side)
+        if len(bad) == 0:
+            break
+        if rounds >= max_rounds:
+            flags |= FLAG_QP_MAXITER
+            break
+        rounds += 1
+        single = False
+        if len(bad) < best:
+            best, block = len(bad), 3
+        elif block > 0:
+            block -= 1
+        else:
+            single = True
+        if single:
+            side[bad[-1]] = want[bad[-1]]
+        else:
+            side = want
+        W = np.flatnonzero(side)
+        b = np.where(side > 0, hi, lo)
+        lam = np.zeros(n)
+        if len(W):
+            lam[W] = np.linalg.solve(G[np.ix_(W, W)], Z0[W] - b[W])
+        U = -np.linalg.solve(H, g + Pu.T @ lam)
+        Z = p + Pu @ U
+        Z[W] = b[W]
+    return dict(U=U, Z=Z, lam=lam, side=side, rounds=rounds, flags=flags)
+
+
+def lip_box_preview(zx, zy, box, lip, N, mpc_dt, z_com, alpha=1e-3, beta=1.0, gravity=9.81, xscale=1.0, max_rounds=MPC_BOX_MAX_ROUNDS):
+    """The numpy statement of lmh_mpc_box_preview for ONE robot: zx, zy [n] its plan, box [4,n] its bounds (zmp_box), lip [5..8] its state.
+    -> dict(k, flags, rounds [2], active [2], U [2,N+1], Z [2,N+1], lam [2,N+1], side [2,N+1], C [2,N+2], Cv [2,N+2], lo [2,N+1], hi [2,N+1]).
+    A window sample with not (lo <= hi) raises FLAG_BOX_EMPTY and leaves NaNs."""
+    zx, zy, box = np.asarray(zx, dtype=np.float64), np.asarray(zy, dtype=np.float64), np.asarray(box, dtype=np.float64)
+    n = len(zx)
+    if box.shape != (4, n) or zy.shape != zx.shape:
+        raise ValueError("zx, zy must be [n] and box [4,n]")
+    x = np.asarray(lip, dtype=np.float64)
+    k = preview_index(x[4], mpc_dt)
+    idx = np.clip(k + np.arange(N + 1), 0, n - 1)
+    flags = FLAG_ZMP_RANGE if (k < 0 or k + N >= n) else 0
+    Px, Pu = lip_matrices(N, mpc_dt, z_com, gravity)
+    H = np.float64(alpha) * np.eye(N + 1) + np.float64(beta) * (Pu.T @ Pu)
+    lo, hi = box[0::2, idx], box[1::2, idx]
+    out = dict(k=k, rounds=np.zeros(2, dtype=np.int64), lo=lo, hi=hi)
+    nanv = np.full(N + 1, np.nan)
+    sols = []
+    with np.errstate(all="ignore"):
+        if not (lo <= hi).all():
+            flags |= FLAG_BOX_EMPTY
+            sols = [dict(U=nanv, Z=nanv, lam=nanv, side=np.zeros(N + 1, dtype=np.int64), rounds=0, flags=0)] * 2
+        else:
+            for ax, (z, s) in enumerate(((zx, np.float64(xscale)), (zy, np.float64(1.0)))):
+                p = Px @ x[2 * ax:2 * ax + 2]
+                g = np.float64(beta) * (Pu.T @ (p - s * z[idx]))
+                sols.append(box_exchange(H, Pu, g, p, lo[ax], hi[ax], max_rounds))
+        dt = np.float64(mpc_dt)
+        C, Cv = np.zeros((2, N + 2)), np.zeros((2, N + 2))
+        for ax in range(2):
+            c, cv = (x[2 * ax], x[2 * ax + 1]) if not flags & FLAG_BOX_EMPTY else (np.nan, np.nan)
+            for j in range(N + 2):
+                C[ax, j], Cv[ax, j] = c, cv
+                if j <= N:
+                    u = sols[ax]["U"][j]
+                    c, cv = c + dt * cv + (dt * dt) / 2 * u, cv + dt * u
+    for name in ("U", "Z", "lam", "side"):
+        out[name] = np.stack([sols[0][name], sols[1][name]])
+    out["rounds"] = np.array([sols[0]["rounds"], sols[1]["rounds"]])
+    out["active"] = (out["side"] != 0).sum(axis=1)
+    out["C"], out["Cv"] = C, Cv
+    flags |= sols[0]["flags"] | sols[1]["flags"]
+    if not all(np.isfinite(out[a]).all() for a in ("U", "Z", "lam", "C", "Cv")):
+        flags |= FLAG_NONFINITE
+    out["flags"] = flags
+    return out
+
+
+def lip_box_step(zx, zy, box, lip, N, mpc_dt, z_com, alpha=1e-3, beta=1.0, gravity=9.81, xscale=1.0, max_rounds=MPC_BOX_MAX_ROUNDS):
+    """The numpy statement of lmh_mpc_box_step for ONE robot -> (sample [16], the lip_box_preview dict it was formed from): u = U[0] and
+    zmp = Z[0] of the constrained solution per axis, x_ref = (x + mpc_dt xdot + mpc_dt^2 / 2 u, xdot + mpc_dt u, u), word 15 the active
+    samples of both axes; flags: those of the solve, FLAG_NONFINITE when one of the first eight words is not finite."""
+    pv = lip_box_preview(zx, zy, box, lip, N, mpc_dt, z_com, alpha, beta, gravity, xscale, max_rounds)
+    st = np.zeros(LIP_STRIDE)
+    st[:min(len(lip), LIP_STRIDE)] = np.asarray(lip, dtype=np.float64)[:LIP_STRIDE]
+    dt = np.float64(mpc_dt)
+    rec = np.zeros(MPC_STRIDE)
+    with np.errstate(all="ignore"):
+        for ax in range(2):
+            x, xd, u = st[2 * ax], st[2 * ax + 1], pv["U"][ax, 0]
+            rec[3 * ax:3 * ax + 3] = x + dt * xd + (dt * dt) / 2 * u, xd + dt * u, u
+            rec[6 + ax] = pv["Z"][ax, 0]
+    rec[8:13] = st[:5]
+    flags = pv["flags"] & ~FLAG_NONFINITE
+    if not np.isfinite(rec[0:8]).all():
+        flags |= FLAG_NONFINITE
+    rec[13], rec[14], rec[15] = pv["k"], flags, pv["active"].sum()
+    return rec, pv
+
+
+def lip_box_rollout(zx, zy, box, lip, n_ticks, N, mpc_dt, z_com, alpha=1e-3, beta=1.0, gravity=9.81, xscale=1.0, max_rounds=MPC_BOX_MAX_ROUNDS):
+    """The numpy statement of lmh_mpc_box_rollout for ONE robot: n_ticks times { lip_box_step; its sample; x <- sample[0], xdot <-
+    sample[1], y <- sample[3], ydot <- sample[4], t <- t + mpc_dt }, every tick from the empty working set.
+    -> (lip [8] after the last tick, samples [n_ticks,16])."""
+    if int(n_ticks) != n_ticks or n_ticks < 0:
+        raise ValueError("n_ticks must be a whole number >= 0")
+    st = np.zeros(LIP_STRIDE)
+    st[:min(len(lip), LIP_STRIDE)] = np.asarray(lip, dtype=np.float64)[:LIP_STRIDE]
+    out = np.zeros((int(n_ticks), MPC_STRIDE))
+    for tick in range(int(n_ticks)):
+        out[tick], _ = lip_box_step(zx, zy, box, st, N, mpc_dt, z_com, alpha, beta, gravity, xscale, max_rounds)
+        st[0], st[1], st[2], st[3] = out[tick, 0], out[tick, 1], out[tick, 3], out[tick, 4]
+        st[4] = st[4] + np.float64(mpc_dt)
+    return st, out
 
 
 # the refusals of lmh_set_pushes, word for word (lmh_capi.hip, push_schedule_error)
