@@ -584,6 +584,37 @@ int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_tau30, int n_
 int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
                     int n_ticks, int n_substeps, void *stream);
 
+/* ---- Caller-supplied CoM references (build-defined; the reference has no counterpart): the whole-body controller tracking a CoM plan that
+ * was made elsewhere -- the box-constrained preview MPC below, a capture-point or DCM plan, a learned policy, a plan computed once and
+ * replayed -- instead of the unconstrained preview step lmh_eval forms itself from the robot's measured CoM state.
+ * d_ref: DEVICE, records of LMH_MPC_STRIDE doubles, [B][LMH_MPC_STRIDE] for lmh_eval_ref and [n_ticks][B][LMH_MPC_STRIDE] (sample-major like
+ * d_log; record j serves control tick j of THIS launch) for lmh_rollout_zoh_ref.  Only words LMH_MPC_OFF_XREF .. + 2 and LMH_MPC_OFF_YREF .. + 2
+ * are read: position, velocity and acceleration reference of the axis, in metres, absolute (not multiplied by xscale), fp64 in every
+ * precision; words [6, 16) are ignored.  A d_traj of lmh_mpc_rollout / lmh_mpc_box_rollout, or a d_mpc of the step calls, is a valid d_ref as
+ * it stands.
+ * DEFINITION of lmh_eval_ref.  lmh_eval with the six values Mpc3dLip::getXRef / getYRef would have returned replaced by the record's: posRef,
+ * velRef and accRef of axes x and y of PDMomentumAcc (controller.cpp:310-325), and out[72:78], which then carry the supplied words.
+ * Everything else is lmh_eval's: k = (int)(t / mpc_dt), the support phase, the foot polynomials and LMH_FLAG_ZMP_RANGE still come from the
+ * handle's plan at the robot's clock; the z reference stays the robot's z_com and the angular-momentum reference zero; v_prev <- v, the warm
+ * start through status[3], per-robot models, plans, xscale, z_com and lmh_set_params records, every precision lmh_eval supports.  A
+ * non-finite word among the six raises LMH_FLAG_NONFINITE for that robot (checked on the words themselves, whatever the solver makes of
+ * them) and disturbs no other robot.  There is no debug-dump variant.
+ * DEFINITION of lmh_rollout_zoh_ref.  For every robot the call leaves exactly what this host loop leaves, bit for bit:
+ *     for j in 0 .. n_ticks - 1:
+ *         lmh_eval_ref(h, d_state, d_ref + j * B * LMH_MPC_STRIDE, d_out, d_status, s)
+ *         tau30 = [ base_wrench[i] (6) | out.tau (24) ]
+ *         lmh_plant_step(h, d_state, tau30, n_substeps, d_flags, s)
+ * d_out, d_status and d_log keep lmh_rollout_zoh's meaning.  Consequence: (a + b) equals (a) followed by (b) with d_ref advanced by a records
+ * per robot (a * B * LMH_MPC_STRIDE doubles).  lmh_rollout_zoh's other rules apply as they are: LMH_PRECISION_FP64 handles only, the contact
+ * constants checked, no launch slot, capturable into a hipGraph from the first call on, nothing written into the handle.
+ * d_ref == NULL returns LMH_ERR_BAD_ARG before anything is enqueued, in both calls; the other refusals are those of lmh_eval /
+ * lmh_rollout_zoh, word for word; n_ticks = 0 enqueues nothing.  The caller supplies one record per control tick: nothing is interpolated.
+ * lmh_rollout (the RK4 reference loop, which evaluates the controller at four stage times per tick) is not offered with an external
+ * reference, nor are its _trace and _metrics forms. */
+int lmh_eval_ref(lmh_handle *h, double *d_state, const double *d_ref, double *d_out, int32_t *d_status, void *stream);
+int lmh_rollout_zoh_ref(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
+                        const double *d_ref, int n_ticks, int n_substeps, void *stream);
+
 /* ---- LIPM preview MPC for a batch of reduced states (one kernel family of its own, one wave per robot, fp64): the stage of the controller
  * that lmh_eval runs between the momentum and the PD law, as calls of its own.
  * replaces: Mpc3dLip::compute (src/mpcLinearPendulum.cpp:78-109) for every robot of the handle, at that robot's own clock.

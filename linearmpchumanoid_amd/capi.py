@@ -140,6 +140,7 @@ PROTOTYPES = {
     "lmh_params_per_instance": (_ip, [_vp]),
     "lmh_get_params": (_ip, [_vp, _ip, _vp]),
     "lmh_eval": (_ip, [_vp, _vp, _vp, _vp, _vp]),
+    "lmh_eval_ref": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "lmh_eval_debug": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "lmh_rollout": (_ip, [_vp, _vp, _vp, _vp, _vp, _ip, _vp]),
     "lmh_rollout_trace": (_ip, [_vp, _vp, _vp, _vp, _vp, _ip, _vp, _ip, _vp]),
@@ -156,6 +157,7 @@ PROTOTYPES = {
     "lmh_plant_derivative": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lmh_plant_step": (_ip, [_vp, _vp, _vp, _ip, _vp, _vp]),
     "lmh_rollout_zoh": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _vp]),
+    "lmh_rollout_zoh_ref": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _vp]),
     "lmh_mpc_step": (_ip, [_vp, _vp, _vp, _vp]),
     "lmh_mpc_rollout": (_ip, [_vp, _vp, _ip, _vp, _vp]),
     "lmh_mpc_preview": (_ip, [_vp, _vp, _vp, _vp]),

@@ -315,12 +315,37 @@ class BatchedController:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ------------------------------------------------------------------ hot path
-    def stand_step(self, state, out=None, status=None, debug=False):
+    def _ref_records(self, ref, lead):
+        """Caller-supplied CoM references (lmh_eval_ref): a tensor or array of shape lead + [B, 16] -> contiguous float64 records on this
+        controller's device.  Words 0:3 | 3:6 of a record are xRef | yRef (position, velocity, acceleration); the others are not read."""
+        shape = tuple(lead) + (self.B, capi.MPC_STRIDE)
+        if isinstance(ref, np.ndarray):
+            if ref.dtype != np.float64:
+                raise ValueError(f"ref must be float64, not {ref.dtype}")
+            ref = torch.from_numpy(np.ascontiguousarray(ref))
+        if not isinstance(ref, torch.Tensor):
+            raise ValueError("ref must be a tensor or an array")
+        if ref.dtype != torch.float64:
+            raise ValueError(f"ref must be float64, not {ref.dtype}")
+        if tuple(ref.shape) != shape:
+            raise ValueError(f"ref must have shape {list(shape)}, not {list(ref.shape)}")
+        return ref.to(self.device).contiguous()
+
+    def stand_step(self, state, out=None, status=None, debug=False, ref=None):
         """Controller::standStep(ControllerInput{q,dq,time}) for all instances (controller.cpp:48-79).
 
-        Updates state[:, 60:90] (Robot::v_) in place like the reference mutates its Robot."""
+        Updates state[:, 60:90] (Robot::v_) in place like the reference mutates its Robot.
+        ref [B,16] (lmh_eval_ref; None: the built-in preview step): the CoM reference the momentum task tracks, xRef | yRef in words 0:6 --
+        a record of mpc_step / mpc_box_step or a tick of their rollouts' traj as it stands.  Not with debug."""
+        if ref is not None:
+            if debug:
+                raise ValueError("stand_step: ref has no debug-dump variant")
+            ref = self._ref_records(ref, ())
         out = self.new_out() if out is None else out
         status = self.new_status() if status is None else status
+        if ref is not None:
+            check(capi.lib().lmh_eval_ref(self._h, _dev_ptr(state), _dev_ptr(ref), _dev_ptr(out), _dev_ptr(status), self._stream()))
+            return out, status
         if debug:
             dbg = torch.zeros((self.B, capi.DEBUG_STRIDE), dtype=torch.float64, device=self.device)
             check(capi.lib().lmh_eval_debug(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), _dev_ptr(dbg), self._stream()))
@@ -518,17 +543,26 @@ class BatchedController:
         check(capi.lib().lmh_plant_step(self._h, _dev_ptr(state), _dev_ptr(tau), int(n_substeps), _dev_ptr(flags), self._stream()))
         return state, flags
 
-    def rollout_zoh(self, state, n_ticks, n_substeps, base_wrench=None, log=False, out=None, status=None):
+    def rollout_zoh(self, state, n_ticks, n_substeps, base_wrench=None, log=False, out=None, status=None, ref=None):
         """lmh_rollout_zoh: n_ticks rounds of { stand_step ; plant_step([base_wrench | out.tau], n_substeps) } in one launch, bit for bit
         what that loop leaves; state [B,96] is updated in place.  The control period is n_substeps * cfg.dt.  base_wrench [B,6]: an external
         wrench on the base held for the launch ([angular | linear], base frame; None: zero).  status (given or fresh): [:, 3] is the active
         mask a warm-started handle continues from; afterwards [:, 1] is the maximum of the QP rounds and [:, 2] the OR of the controller's
-        and the plant's flags over all ticks.  -> (out, status), plus the log [n_ticks,B,36] (tau | f of every tick) when log is asked for."""
+        and the plant's flags over all ticks.  ref [n_ticks,B,16] (lmh_rollout_zoh_ref; None: the built-in preview step): record j is the
+        CoM reference of control tick j of this launch, as in stand_step(ref=...) -- the traj of mpc_rollout / mpc_box_rollout as it stands.
+        -> (out, status), plus the log [n_ticks,B,36] (tau | f of every tick) when log is asked for."""
         state, bw = self._batch("state", state, capi.STATE_STRIDE, in_place=True), self._batch("base_wrench", base_wrench, 6, optional=True)
         for name, n in (("n_ticks", n_ticks), ("n_substeps", n_substeps)):
             if int(n) != n or n < 0:
                 raise ValueError(f"{name} must be a whole number >= 0")
         out, status, lg = self._rollout_buffers(int(n_ticks), out, status, log)
+        if ref is not None:
+            ref = self._ref_records(ref, (int(n_ticks),))
+            if ref.numel() == 0:                                   # (an empty tensor has no address to pass; with no tick no record is read)
+                ref = torch.empty((1,), dtype=torch.float64, device=self.device)
+            check(capi.lib().lmh_rollout_zoh_ref(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), _dev_ptr(bw), _dev_ptr(lg), _dev_ptr(ref),
+                                                 int(n_ticks), int(n_substeps), self._stream()))
+            return (out, status) if lg is None else (out, status, lg)
         check(capi.lib().lmh_rollout_zoh(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), _dev_ptr(bw), _dev_ptr(lg),
                                          int(n_ticks), int(n_substeps), self._stream()))
         return (out, status) if lg is None else (out, status, lg)

@@ -724,20 +724,26 @@ template <class Launch> static int launch(lmh_handle *h, const char *refusal, La
     return LMH_OK;
 }
 
-static int eval_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_debug, bool debug, void *stream)
+// with_ref (lmh_eval_ref): d_ref is required too, refused behind lmh_eval's own pointers with a message of its own
+static int eval_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_debug, bool debug, const double *d_ref, bool with_ref, void *stream)
 {
-    return launch(h, (!d_state || !d_out || !d_status || (debug && !d_debug)) ? "null device pointer" : nullptr,
-                  [&] { lmh_launch_eval(&h->P, d_state, d_out, d_status, d_debug, (hipStream_t)stream); });
+    return launch(h, (!d_state || !d_out || !d_status || (debug && !d_debug)) ? "null device pointer" : (with_ref && !d_ref) ? "lmh_eval_ref: null d_ref" : nullptr,
+                  [&] { lmh_launch_eval(&h->P, d_state, d_out, d_status, d_debug, d_ref, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_eval(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, void *stream)
 {
-    return eval_body(h, d_state, d_out, d_status, nullptr, false, stream);
+    return eval_body(h, d_state, d_out, d_status, nullptr, false, nullptr, false, stream);
 }
 
 extern "C" int lmh_eval_debug(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_debug, void *stream)
 {
-    return eval_body(h, d_state, d_out, d_status, d_debug, true, stream);
+    return eval_body(h, d_state, d_out, d_status, d_debug, true, nullptr, false, stream);
+}
+
+extern "C" int lmh_eval_ref(lmh_handle *h, double *d_state, const double *d_ref, double *d_out, int32_t *d_status, void *stream)
+{
+    return eval_body(h, d_state, d_out, d_status, nullptr, false, d_ref, true, stream);
 }
 
 // The error word of a COMPLETED launch on this slot (d_ticket[3], lmh_rollout_kernel): read once, cleared, reported.  The kernel has already
@@ -913,7 +919,7 @@ extern "C" int lmh_eval_host(lmh_handle *h, const double *q, const double *dq, d
         s[90] = t;
     }
     HIPCHK(hipMemcpy(h->d_state.get(), h->h_state.data(), sizeof(double) * h->h_state.size(), hipMemcpyHostToDevice));
-    lmh_launch_eval(&h->P, h->d_state.get(), h->d_out.get(), h->d_status.get(), nullptr, nullptr);
+    lmh_launch_eval(&h->P, h->d_state.get(), h->d_out.get(), h->d_status.get(), nullptr, nullptr, nullptr);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpy(h->h_state.data(), h->d_state.get(), sizeof(double) * h->h_state.size(), hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(h->h_out.data(), h->d_out.get(), sizeof(double) * h->h_out.size(), hipMemcpyDeviceToHost));
@@ -1018,16 +1024,28 @@ extern "C" int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_ta
 // n_ticks rounds of { lmh_eval ; lmh_plant_step(tau30 = [base_wrench | out.tau], n_substeps) } in one launch (lmh_kernels.hip,
 // lmh_rollout_zoh_kernel).  Refusals in the order of the two calls it composes: the handle, the pointers, the counts, then the precision and the
 // contact constants; the parameter block travels by value, so the call takes no launch slot.
-extern "C" int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
-                               int n_ticks, int n_substeps, void *stream)
+// with_ref (lmh_rollout_zoh_ref): d_ref is required too, refused behind the call's own pointers; every other refusal is lmh_rollout_zoh's, word for word.
+static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log, const double *d_ref, bool with_ref,
+                    int n_ticks, int n_substeps, void *stream)
 {
     int rc = ready(h); if (rc) return rc;
     if (!d_state || !d_out || !d_status) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: null device pointer");
+    if (with_ref && !d_ref) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ref: null d_ref");
     if (n_ticks < 0 || n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: n_ticks and n_substeps must be >= 0");
     if (h->cfg.precision != LMH_PRECISION_FP64) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: LMH_PRECISION_FP64 handles only (this handle's precision has no instantiation of the kernel)");
     rc = plant_constants_ok(h); if (rc) return rc;
     if (n_ticks == 0) return LMH_OK;                                 // nothing to enqueue
-    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, n_ticks, n_substeps, (hipStream_t)stream); });
+    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, (hipStream_t)stream); });
+}
+extern "C" int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
+                               int n_ticks, int n_substeps, void *stream)
+{
+    return zoh_body(h, d_state, d_out, d_status, d_base_wrench, d_log, nullptr, false, n_ticks, n_substeps, stream);
+}
+extern "C" int lmh_rollout_zoh_ref(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log, const double *d_ref,
+                                   int n_ticks, int n_substeps, void *stream)
+{
+    return zoh_body(h, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, true, n_ticks, n_substeps, stream);
 }
 
 extern "C" int lmh_terms_host(lmh_handle *h, const double *q, const double *v, double *terms)

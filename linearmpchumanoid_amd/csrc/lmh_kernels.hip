@@ -1371,9 +1371,19 @@ __device__ __forceinline__ double readlane_f64(double v, int src_lane)       // 
 // l16 and l16 + 16 with the expressions of refs_ag, multiplies them with vhat and the row sums go round through row broadcasts (the order
 // of the 30-term sum differs from refs_momentum's: 1e-16 relative); the three quotients reach every lane as scalars (v_readlane), so the MPC
 // step and the PD law follow in registers.
-__device__ __forceinline__ int refs_chain_a(double *L, LmhCParams &P, int inst, int k, double mass, bool ang)
+// REF (lmh_eval_ref, lmh_rollout_zoh_ref): xRef | yRef are the caller's, words LMH_MPC_OFF_XREF.. and LMH_MPC_OFF_YREF.. of this robot's record
+// `ref` (global memory nobody writes during the launch, wave-uniform address).  The wave that runs this chain loads the six words itself,
+// here, ahead of the AG rows whose sums they follow, so no other wave and no join is involved; the gain sums are not formed.  The CoM velocity,
+// the PD law and the stores to L[P_MPC ..] are the built-in path's.
+template <bool REF = false>
+__device__ __forceinline__ int refs_chain_a(double *L, LmhCParams &P, int inst, int k, double mass, bool ang, const double *ref = nullptr)
 {
     const int lane = LANE, l16 = lane & 15, q4 = lane >> 4, a = (q4 < 3) ? q4 : 2;
+    double rx[3] = {0.0, 0.0, 0.0}, ry[3] = {0.0, 0.0, 0.0};
+    if constexpr (REF) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) { rx[i] = ref[LMH_MPC_OFF_XREF + i]; ry[i] = ref[LMH_MPC_OFF_YREF + i]; }
+    }
     if (ang) {                                                     // wave-uniform: rows 0..2 of AG (refs_ag)
         const double *T0 = L + P_TB;
         for (int e = lane; e < 90; e += 64) {
@@ -1406,11 +1416,15 @@ __device__ __forceinline__ int refs_chain_a(double *L, LmhCParams &P, int inst, 
     const double zcom = mp[3 * (N + 1)];
     // MPC: u0 = -K (Px x_k - z[k : k+N+1]) (refs_mpc)
     const double cxp = L[P_COM], cyp = L[P_COM + 1], czp = L[P_COM + 2];
-    const double kp0 = L[P_PRE + 2], kp1 = L[P_PRE + 3];
-    const double ux = -((kp0 * cxp + kp1 * vxp) - L[P_RXS] * L[P_PRE]);
-    const double uy = -((kp0 * cyp + kp1 * vyp) - L[P_PRE + 1]);
-    const double xp = P.a00 * cxp + P.a01 * vxp + P.b0 * ux, xv = P.a10 * cxp + P.a11 * vxp + P.b1 * ux;
-    const double yp = P.a00 * cyp + P.a01 * vyp + P.b0 * uy, yv = P.a10 * cyp + P.a11 * vyp + P.b1 * uy;
+    double ux, uy, xp, xv, yp, yv;
+    if constexpr (REF) { xp = rx[0]; xv = rx[1]; ux = rx[2]; yp = ry[0]; yv = ry[1]; uy = ry[2]; }
+    else {
+        const double kp0 = L[P_PRE + 2], kp1 = L[P_PRE + 3];
+        ux = -((kp0 * cxp + kp1 * vxp) - L[P_RXS] * L[P_PRE]);
+        uy = -((kp0 * cyp + kp1 * vyp) - L[P_PRE + 1]);
+        xp = P.a00 * cxp + P.a01 * vxp + P.b0 * ux; xv = P.a10 * cxp + P.a11 * vxp + P.b1 * ux;
+        yp = P.a00 * cyp + P.a01 * vyp + P.b0 * uy; yv = P.a10 * cyp + P.a11 * vyp + P.b1 * uy;
+    }
     if (lane == 0) {
         L[P_MPC + 0] = ux; L[P_MPC + 1] = uy;
         L[P_MPC + 2] = xp; L[P_MPC + 3] = xv; L[P_MPC + 4] = ux;
@@ -1486,8 +1500,8 @@ __device__ __forceinline__ void refs_pd_feet(double *L, LmhCParams &P, int inst,
     }
 }
 
-template <int NW, bool ORI_MAYBE = false, bool CGLIN = true>
-__device__ __forceinline__ int phase_refs(double *L, LmhCParams &P, int inst, double t, int wid, int *k_out, int *phase_out, bool ang)
+template <int NW, bool ORI_MAYBE = false, bool CGLIN = true, bool REF = false>
+__device__ __forceinline__ int phase_refs(double *L, LmhCParams &P, int inst, double t, int wid, int *k_out, int *phase_out, bool ang, const double *ref = nullptr)
 {
     int flags = 0;
     const double mass = L[P_MODEL + 392];
@@ -1495,7 +1509,7 @@ __device__ __forceinline__ int phase_refs(double *L, LmhCParams &P, int inst, do
     *k_out = k; *phase_out = __builtin_amdgcn_readfirstlane((int)L[P_RPH]);
     if (k < 0 || k + P.horizon >= P.n_samples) flags |= LMH_FLAG_ZMP_RANGE;    // on every wave (wave 0 reports)
     if constexpr (NW == 1) {
-        flags |= refs_chain_a(L, P, inst, k, mass, ang);           // the same code on either schedule: the results agree bit for bit
+        flags |= refs_chain_a<REF>(L, P, inst, k, mass, ang, ref); // the same code on either schedule: the results agree bit for bit
         refs_agpqp<CGLIN>(L, mass, ang);
         SUBSTAMP(12);
         refs_vfoot_pdjoints(L, P);
@@ -1506,7 +1520,7 @@ __device__ __forceinline__ int phase_refs(double *L, LmhCParams &P, int inst, do
         WSYNC();
     } else if (wid == 1) {                                         // chain A
         WSTAMP(66);
-        flags |= refs_chain_a(L, P, inst, k, mass, ang);
+        flags |= refs_chain_a<REF>(L, P, inst, k, mass, ang, ref);
         WSYNC();
     } else {                                                       // chain B
         WSTAMP(67);
@@ -3327,9 +3341,11 @@ __device__ __forceinline__ void phase_outputs_qdd(double *L, int a_src = P_A)
 // into the next evaluation's forward kinematics.
 // PIPE (rollout kernel only): the kinematics of this evaluation were run ahead by the helper wave, inside the previous evaluation's
 // `window` (phase_qp), and so were the clock-only references; wave 0 starts at the X images.
-template <int NW, typename R, bool QF32 = false, bool PIPE = false, class WF = NoWindow, bool TAIL = false>
+// REF: the momentum task tracks the caller's CoM reference `ref` (this robot's record of this evaluation, see refs_chain_a) instead of the
+// built-in preview step's.
+template <int NW, typename R, bool QF32 = false, bool PIPE = false, class WF = NoWindow, bool TAIL = false, bool REF = false>
 __device__ __forceinline__ int controller_eval(double *L, LmhCParams &P, int inst, double t, int wid, unsigned *Fmask, int *k_out, int *iters_out, double *dbg, bool need_tau = true, WF window = WF(),
-                                               const IbPack *ibp = nullptr, RkTail *tailp = nullptr)
+                                               const IbPack *ibp = nullptr, RkTail *tailp = nullptr, const double *ref = nullptr)
 {
     int flags = 0, ph = 0;
     RkTail tail_off = {false, false, 0.0};
@@ -3400,10 +3416,16 @@ __device__ __forceinline__ int controller_eval(double *L, LmhCParams &P, int ins
     WSTAMP(6);
     STAMP(6);
     const bool ang = (P.w_com_ang != 0.0) || (dbg != nullptr);     // angular-momentum rows: only when weighted (or dumped)
-    flags |= phase_refs<NW, PIPE, std::is_same_v<R, double>>(L, P, inst, t, wid, k_out, &ph, ang);        // PIPE: the feet's orientation term may have been formed behind the look-ahead kinematics
+    flags |= phase_refs<NW, PIPE, std::is_same_v<R, double>, REF>(L, P, inst, t, wid, k_out, &ph, ang, ref);        // PIPE: the feet's orientation term may have been formed behind the look-ahead kinematics
     if (NW == 2 && wid == 0 && P.w_com_ang == 0.0 && !QF32) { WSTAMP(68); qp_prefill15(L, P); }      // ahead of the join: wave 1's chain is the longer one
     WSTAMP(7);
     bsync<NW>();
+    if constexpr (REF) {
+        // a non-finite word of the caller's reference is the robot's LMH_FLAG_NONFINITE whatever the solver makes of it: on the words chain A
+        // published (behind the join: wave 0 writes the status record)
+        const double w = L[P_MPC + 2 + ((LANE < 6) ? LANE : 0)];
+        if (__ballot(!(fabs(w) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
+    }
     WSTAMP(8);
     STAMP(7);
     tail.on = false;                                               // set by wave 0's recovery (phase_qp) unless the plant runs
@@ -3550,11 +3572,12 @@ __device__ __forceinline__ void store_status(int32_t *status, int inst, int k, i
 // Controller::standStep + WBC for every instance (src/controller.cpp:48-154).
 // The plain kernel runs two waves per robot like the rollout; the debug kernel (intermediate dumps, stamps) keeps
 // the single-wave schedule.
-template <bool DEBUG, typename R, int NW = (DEBUG ? 1 : 2), bool QF32 = false>
-__global__ void __launch_bounds__(64 * NW) lmh_eval_kernel(LmhDevParams P_arg, double *state, double *out, int32_t *status, double *debug)
+// lmh_eval_body: the kernel's text, shared with lmh_eval_ref_kernel (REF, include/lmh.h lmh_eval_ref: `ref` [B][LMH_MPC_STRIDE], the CoM
+// reference of every robot) so that the kernels of before keep their symbols and their kernel arguments.
+template <bool DEBUG, typename R, int NW, bool QF32, bool REF>
+__device__ __forceinline__ void lmh_eval_body(double *L, double *state, double *out, int32_t *status, double *debug, const double *ref)
 {
     LmhCParams &P0 = LMH_KERNARG_PARAMS();
-    __shared__ double L[LDS_DOUBLES];
     const int inst = blockIdx.x;
     if (inst >= P0.n_instances) return;
     LmhCParams &P = *params_of_robot(&P0, inst);                   // per-robot parameters (lmh_set_params): the robot's own block
@@ -3564,13 +3587,26 @@ __global__ void __launch_bounds__(64 * NW) lmh_eval_kernel(LmhDevParams P_arg, d
     SET_GDBG(DEBUG ? debug + (size_t)LMH_DEBUG_STRIDE * inst : nullptr);
     unsigned F = eval_begin<NW>(L, P, inst, st, status, wid);
     int k = 0, iters = 0;
-    const int flags = controller_eval<NW, R, QF32>(L, P, inst, t, wid, &F, &k, &iters, DEBUG ? debug + (size_t)LMH_DEBUG_STRIDE * inst : nullptr);
+    const int flags = controller_eval<NW, R, QF32, false, NoWindow, false, REF>(L, P, inst, t, wid, &F, &k, &iters, DEBUG ? debug + (size_t)LMH_DEBUG_STRIDE * inst : nullptr, true, NoWindow(),
+                                                                                nullptr, nullptr, REF ? ref + (size_t)LMH_MPC_STRIDE * inst : nullptr);
     bsync<NW>();                                                   // torques of the helper wave
     if (wid == 0) {
         store_out(L, out + (size_t)LMH_OUT_STRIDE * inst);
         if (LANE < 30) st[60 + LANE] = L[P_V + LANE];              // Robot::v_ <- dq (controller.cpp:59)
         if (LANE == 0) store_status(status, inst, k, iters, flags, F);
     }
+}
+template <bool DEBUG, typename R, int NW = (DEBUG ? 1 : 2), bool QF32 = false>
+__global__ void __launch_bounds__(64 * NW) lmh_eval_kernel(LmhDevParams P_arg, double *state, double *out, int32_t *status, double *debug)
+{
+    __shared__ double L[LDS_DOUBLES];
+    lmh_eval_body<DEBUG, R, NW, QF32, false>(L, state, out, status, debug, nullptr);
+}
+template <typename R, bool QF32 = false>
+__global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) lmh_eval_ref_kernel(LmhDevParams P_arg, double *state, double *out, int32_t *status, const double *ref)
+{
+    __shared__ double L[LDS_DOUBLES];
+    lmh_eval_body<false, R, 2, QF32, true>(L, state, out, status, nullptr, ref);
 }
 
 // One claim on the rollout's work queue (called by one thread of the workgroup): -1 when no unit is left, else the robot, with the ticks it has
@@ -4751,11 +4787,12 @@ extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *
 //               it is recomputed whenever it is needed) and the stored inverse is a pure function of the free set and the robot's friction
 //               table: it survives.  P_ORI is read by the rollout kernel's pipelined evaluation only: cleared once.
 //               Everything else an evaluation reads it has written itself (lmh_eval_kernel starts from an LDS image nobody initialised).
-__global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) lmh_rollout_zoh_kernel(LmhDevParams P_arg, double *state, double *out, int32_t *status, const double *base_wrench, double *log,
-                                                                               int n_ticks, int n_substeps)
+// REF (lmh_rollout_zoh_ref_kernel): `ref` [n_ticks][B][LMH_MPC_STRIDE], record `tick` of the robot is the CoM reference of that tick's evaluation;
+// the helper wave, which runs chain A, reads it from global memory inside the chain (refs_chain_a): no broadcast, no further join.
+template <bool REF>
+__device__ __forceinline__ void lmh_rollout_zoh_body(double *L, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps)
 {
     LmhCParams &P0 = LMH_KERNARG_PARAMS();
-    __shared__ double L[LDS_DOUBLES];
     const int inst = blockIdx.x;
     if (inst >= P0.n_instances) return;
     LmhCParams &P = *params_of_robot(&P0, inst);
@@ -4771,7 +4808,8 @@ __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_wav
 #pragma unroll 1
     for (int tick = 0; tick < n_ticks; tick++) {
         int iters = 0;
-        flags |= controller_eval<2, double, false>(L, P, inst, t, wid, &F, &k, &iters, nullptr);
+        flags |= controller_eval<2, double, false, false, NoWindow, false, REF>(L, P, inst, t, wid, &F, &k, &iters, nullptr, true, NoWindow(), nullptr, nullptr,
+                                                                                REF ? ref + ((size_t)tick * P0.n_instances + inst) * LMH_MPC_STRIDE : nullptr);
         itmax = (iters > itmax) ? iters : itmax;
         bsync<2>();                                                // torques of the helper wave
         if (wid == 0) {
@@ -4800,10 +4838,24 @@ __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_wav
         if (LANE == 0) { st[90] = t; store_status(status, inst, k, itmax, flags, F); }
     }
 }
-extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, int n_ticks, int n_substeps,
+__global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) lmh_rollout_zoh_kernel(LmhDevParams P_arg, double *state, double *out, int32_t *status, const double *base_wrench, double *log,
+                                                                               int n_ticks, int n_substeps)
+{
+    __shared__ double L[LDS_DOUBLES];
+    lmh_rollout_zoh_body<false>(L, state, out, status, base_wrench, log, nullptr, n_ticks, n_substeps);
+}
+__global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) lmh_rollout_zoh_ref_kernel(LmhDevParams P_arg, double *state, double *out, int32_t *status, const double *base_wrench, double *log,
+                                                                                   const double *ref, int n_ticks, int n_substeps)
+{
+    __shared__ double L[LDS_DOUBLES];
+    lmh_rollout_zoh_body<true>(L, state, out, status, base_wrench, log, ref, n_ticks, n_substeps);
+}
+// ref NULL: lmh_rollout_zoh's kernel exactly as it is; otherwise lmh_rollout_zoh_ref's
+extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
                                        hipStream_t s)
 {
-    hipLaunchKernelGGL(lmh_rollout_zoh_kernel, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, state, out, status, base_wrench, log, n_ticks, n_substeps);
+    if (ref) hipLaunchKernelGGL(lmh_rollout_zoh_ref_kernel, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, state, out, status, base_wrench, log, ref, n_ticks, n_substeps);
+    else hipLaunchKernelGGL(lmh_rollout_zoh_kernel, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, state, out, status, base_wrench, log, n_ticks, n_substeps);
 }
 
 #endif
@@ -4960,8 +5012,15 @@ extern "C" void lmh_launch_gen_jump(int n, double time_step, double stance_time,
 }
 
 #ifndef LMH_ROLLOUT_ONLY
-extern "C" void lmh_launch_eval(const LmhDevParams *P, double *state, double *out, int32_t *status, double *debug, hipStream_t s)
+extern "C" void lmh_launch_eval(const LmhDevParams *P, double *state, double *out, int32_t *status, double *debug, const double *ref, hipStream_t s)
 {
+    // ref (lmh_eval_ref; never with debug): the same schedule with the caller's CoM reference, in every precision
+    if (ref) {
+        if (P->precision == 2) hipLaunchKernelGGL((lmh_eval_ref_kernel<float, true>), dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, state, out, status, ref);
+        else if (P->precision == 1) hipLaunchKernelGGL((lmh_eval_ref_kernel<float>), dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, state, out, status, ref);
+        else hipLaunchKernelGGL((lmh_eval_ref_kernel<double>), dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, state, out, status, ref);
+        return;
+    }
     // precision 1 (LMH_PRECISION_MIXED): model terms in fp32 arithmetic, references and QP in fp64; the debug kernel is fp64 only
     // LMH_DIAG_NW2=1: the debug kernel on the two-wave schedule (per-wave phase stamps; diagnostics only)
     static const bool diag_nw2 = getenv("LMH_DIAG_NW2") != nullptr;     // read once

@@ -15,13 +15,16 @@ extern "C" void lmh_launch_gen_jump(int n, double time_step, double stance_time,
 // d_specs: DEVICE [n_plans], each with n_samples set to the shared grid; seg_stride: segment records per robot
 extern "C" void lmh_launch_gen_walk_batch(const LmhWalkSpec *d_specs, int n_plans, int seg_stride, double *zx, double *zy, uint8_t *phase, double *segs, uint16_t *sos, hipStream_t s);
 extern "C" void lmh_launch_gen_jump_batch(int n, double time_step, const LmhJumpSpec *d_specs, int n_plans, double *zx, double *zy, uint8_t *phase, hipStream_t s);
-extern "C" void lmh_launch_eval(const LmhDevParams *P, double *state, double *out, int32_t *status, double *debug, hipStream_t s);
+// ref (lmh_eval_ref, lmh_rollout_zoh_ref): NULL = the kernels of lmh_eval / lmh_rollout_zoh exactly as they are; otherwise the caller's CoM references,
+// [B][LMH_MPC_STRIDE] for the evaluation (never with `debug`) and [n_ticks][B][LMH_MPC_STRIDE] for the closed loop
+extern "C" void lmh_launch_eval(const LmhDevParams *P, double *state, double *out, int32_t *status, double *debug, const double *ref, hipStream_t s);
 // d_P: device copy of *P (the rollout kernel reads its parameters through a pointer, see lmh_rollout_kernel)
 // d_ticket: zero-initialised device memory owned by this launch until it completes (work-unit counters, ring, progress: see the kernel)
 // trace, trace_every: the samples of lmh_rollout_trace, NULL and 0 = none; metrics: the records of lmh_rollout_metrics, NULL = none; never both
 extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks,
                                    double *trace, int trace_every, double *metrics, hipStream_t s);
-extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, int n_ticks, int n_substeps, hipStream_t s);
+extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
+                                       hipStream_t s);
 extern "C" void lmh_launch_metrics_reset(double *metrics, int n_instances, double z_min, double tilt_max, hipStream_t s);
 extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
 extern "C" void lmh_launch_com(const LmhDevParams *P, const double *q, double *com, hipStream_t s);
