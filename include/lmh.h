@@ -573,7 +573,8 @@ int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_tau30, int n_
  * Consequence: lmh_rollout_zoh(a + b) equals (a) followed by (b) bit for bit, with [1] and [2] merged as max / OR; with warm_start = 1 too,
  * because d_status[.][3] carries the mask across the split.
  * The control period is n_substeps * lmh_config.dt; mpc_dt keeps its meaning.  Per-robot models, plans, xscale, z_com and lmh_set_params
- * records are honoured as the two composed calls honour them.  The velocity pushes of lmh_set_pushes are NOT applied (as in lmh_eval).
+ * records are honoured as the two composed calls honour them.  The velocity pushes of lmh_set_pushes are NOT applied (as in lmh_eval; lmh_rollout_zoh_ex
+ * applies them).
  * This is not lmh_rollout with plant = 1, which evaluates the controller at all four RK4 stages of every step (the reference's loop); on a
  * plant = 1 handle the evaluation here is whatever lmh_eval does there.
  * n_ticks < 0 or n_substeps < 0, or NULL for d_state / d_out / d_status, return LMH_ERR_BAD_ARG before anything is enqueued; n_ticks = 0
@@ -614,6 +615,68 @@ int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, int32_t *d_st
 int lmh_eval_ref(lmh_handle *h, double *d_state, const double *d_ref, double *d_out, int32_t *d_status, void *stream);
 int lmh_rollout_zoh_ref(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
                         const double *d_ref, int n_ticks, int n_substeps, void *stream);
+
+/* ---- The zero-order-hold loop with timed pushes, a wrench per control tick, a trace and a metrics record (build-defined): what a push-recovery
+ * study or a scored sweep on the torque-driven plant needs, in the one launch, instead of a host loop around lmh_eval and lmh_plant_step.
+ * One options record, one entry point; an all-zero record, or opts == NULL, is lmh_rollout_zoh(h, state, out, status, NULL, NULL, n_ticks,
+ * n_substeps, s) exactly (the same kernel), and a record with only d_base_wrench, d_ref and d_log set is lmh_rollout_zoh / lmh_rollout_zoh_ref
+ * with those arguments.  d_ref == NULL means the built-in preview step.
+ * DEFINITION.  For every robot the call leaves, bit for bit, what this host loop leaves (B = n_instances; n is a whole number):
+ *     n = llrint(state[90] / dt)                 the robot's plant substep number at the start of the launch; counted in integers from here on
+ *     for j in 0 .. n_ticks - 1:
+ *         if pushes and the robot's schedule has a record with tick == n:  state.v += dv      before the evaluation; q, v_prev, t untouched
+ *         lmh_eval (d_ref == NULL)  or  lmh_eval_ref(d_ref + j * B * LMH_MPC_STRIDE)
+ *         tau30 = [ wrench (6) | out.tau (24) ]      wrench = d_base_wrench[i], or d_base_wrench[j][i] when wrench_per_tick
+ *         r = n_substeps
+ *         while r > 0:
+ *             p = the smallest schedule tick with n < p < n + r   (pushes only; else none)
+ *             s = p - n if p exists else r
+ *             lmh_plant_step(s substeps);  n += s;  r -= s
+ *             if p exists:  state.v += dv(p)
+ *         the sample / the fold of this control tick (below)
+ * PUSHES (pushes = 1: the handle's lmh_set_pushes schedule).  A push tick is a PLANT SUBSTEP number, in units of lmh_config.dt on the robot's
+ * own clock -- the meaning it has in lmh_rollout, where a tick is one step of dt.  A push that falls on the start of a control tick is seen by
+ * that tick's evaluation (whose v_prev <- v then stores the pushed v); one inside a hold is applied between two substeps and the controller
+ * meets it at its next evaluation.  A record whose tick equals the substep number the launch ends on is not applied: the next launch applies it
+ * when it loads the robot, so (a + b) is (a) followed by (b) bit for bit, with d_ref advanced by a records and d_base_wrench too when it is per
+ * tick.  A state record or a sample never holds a push whose substep has not started; records in the past at the start of the launch are
+ * ignored; pushes = 1 on a handle without a schedule is legal and changes nothing.  pushes = 1 with n_substeps == 0 and n_ticks > 0 returns
+ * LMH_ERR_BAD_ARG (the clock does not move, the rule has no meaning), and so does pushes = 1 with n_ticks * n_substeps >= 2^30 - 1.
+ * TRACE (d_trace with trace_every > 0; lmh_rollout_trace's layout and rules as they are).  Sample j is taken when the robot has completed
+ * (j + 1) * trace_every CONTROL ticks of this launch and holds what the same call with n_ticks = (j + 1) * trace_every would have left in the
+ * robot's three records: the state words after that tick's hold, q | v | v_prev (the v the evaluation saw) | t, pads written as zeros; the out
+ * record of that tick's evaluation (out.qdd is the evaluation's, not the plant's); the status words as doubles: k, the maximum of the QP rounds
+ * so far in this launch, the OR of the controller's and the plant's flags so far in this launch including this tick's hold, the active mask.  Exactly one of d_trace /
+ * trace_every given, or trace_every < 0, returns LMH_ERR_BAD_ARG; trace_every > n_ticks writes nothing; the trace of (a + b) is the trace of
+ * (a) followed by the trace of (b) when trace_every divides a.  lmh_write_trace's sample_dt of such a trace is trace_every * n_substeps * dt.
+ * METRICS (d_metrics: lmh_metrics_reset's records, the same 208 doubles and the same accumulation over launches as lmh_rollout_metrics).  The
+ * record is the fold (lmh_rollout_metrics; linearmpchumanoid_amd/metrics.py: fold_trace) of the every-control-tick trace of the same launch.
+ * COUNT counts control ticks.  The state extrema XMIN / XMAX (and FIRST_FALL) are taken at the ENDS OF CONTROL TICKS, not at every plant
+ * substep: an excursion inside a hold that has decayed by its end is not in them.  WMIN / WMAX are the CONTROLLER'S contact wrench out.f, as
+ * in the trace, not the wrench the plant's compliant contact produced.  d_trace and d_metrics may both be given.  n_ticks == 0 enqueues
+ * nothing and leaves the record's bytes alone.
+ * Everything else is lmh_rollout_zoh's: LMH_PRECISION_FP64 handles only, the contact constants checked on the host before anything is
+ * enqueued, no launch slot, no work queue, no host staging, capturable into a hipGraph from the first call on a fresh handle, nothing written
+ * into the handle, the meaning of d_state / d_out / d_status, per-robot models, plans, xscale, z_com and lmh_set_params records honoured.
+ * Refusals, each LMH_ERR_BAD_ARG before anything is enqueued and with a message of its own: wrench_per_tick, pushes or reserved outside its
+ * values; wrench_per_tick = 1 with a NULL wrench; the trace rules and the pushes rules above.  The others are lmh_rollout_zoh's, word for word.
+ * Cost (one MI355X, 4096 standing robots x 200 control ticks): with no option set the call launches lmh_rollout_zoh's
+ * kernel; at n_substeps = 1 each option alone costs 1.6 .. 2.6 % (inside the plain loop's own range of timings) and all of them with an
+ * every-tick trace 5.8 %; at n_substeps = 10 every combination lies inside the plain loop's own range of timings.  Other batch sizes and
+ * anything multi-GPU were not measured. */
+typedef struct lmh_zoh_opts {
+    const double *d_base_wrench;  /* DEVICE [B][6], or [n_ticks][B][6] when wrench_per_tick = 1; NULL = zero */
+    const double *d_ref;          /* DEVICE [n_ticks][B][LMH_MPC_STRIDE] as lmh_rollout_zoh_ref takes it; NULL = the built-in preview step */
+    double *d_log;                /* DEVICE [n_ticks][B][36] or NULL, as lmh_rollout_zoh */
+    double *d_trace;              /* DEVICE [lmh_trace_samples(n_ticks, trace_every)][B][LMH_TRACE_STRIDE] or NULL */
+    double *d_metrics;            /* DEVICE [B][LMH_METRICS_STRIDE] or NULL; lmh_metrics_reset's records */
+    int32_t trace_every;          /* control ticks per sample; 0 together with d_trace == NULL: no trace */
+    int32_t wrench_per_tick;      /* 0 | 1 */
+    int32_t pushes;               /* 0 | 1: apply the handle's lmh_set_pushes schedule */
+    int32_t reserved;             /* must be 0 */
+} lmh_zoh_opts;
+int lmh_rollout_zoh_ex(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts,
+                       int n_ticks, int n_substeps, void *stream);
 
 /* ---- LIPM preview MPC for a batch of reduced states (one kernel family of its own, one wave per robot, fp64): the stage of the controller
  * that lmh_eval runs between the momentum and the PD law, as calls of its own.

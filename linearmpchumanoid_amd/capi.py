@@ -101,6 +101,12 @@ class LmhJumpSpec(C.Structure):
     _fields_ = [("stance_time", C.c_double), ("flight_time", C.c_double)]
 
 
+class LmhZohOpts(C.Structure):
+    """struct lmh_zoh_opts (include/lmh.h): the options of lmh_rollout_zoh_ex; all zero = lmh_rollout_zoh."""
+    _fields_ = [(n, C.c_void_p) for n in ("d_base_wrench", "d_ref", "d_log", "d_trace", "d_metrics")] + \
+               [(n, C.c_int32) for n in ("trace_every", "wrench_per_tick", "pushes", "reserved")]
+
+
 _vp, _ip, _dp, _str, _u64 = C.c_void_p, C.c_int, C.c_double, C.c_char_p, C.c_uint64
 _u64p, _dpp = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
 # name -> (restype, argtypes) of every symbol include/lmh.h declares; tests/test_abi.py holds each row against its prototype
@@ -158,6 +164,7 @@ PROTOTYPES = {
     "lmh_plant_step": (_ip, [_vp, _vp, _vp, _ip, _vp, _vp]),
     "lmh_rollout_zoh": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _vp]),
     "lmh_rollout_zoh_ref": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _vp]),
+    "lmh_rollout_zoh_ex": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), _ip, _ip, _vp]),
     "lmh_mpc_step": (_ip, [_vp, _vp, _vp, _vp]),
     "lmh_mpc_rollout": (_ip, [_vp, _vp, _ip, _vp, _vp]),
     "lmh_mpc_preview": (_ip, [_vp, _vp, _vp, _vp]),

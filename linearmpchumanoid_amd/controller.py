@@ -567,6 +567,54 @@ class BatchedController:
                                          int(n_ticks), int(n_substeps), self._stream()))
         return (out, status) if lg is None else (out, status, lg)
 
+    def rollout_zoh_ex(self, state, n_ticks, n_substeps, base_wrench=None, ref=None, pushes=False, log=False, trace_every=0, trace=None,
+                       metrics=None, out=None, status=None):
+        """lmh_rollout_zoh_ex: rollout_zoh with the set_pushes schedule applied (pushes=True; push ticks are plant substeps of cfg.dt on the
+        robot's clock, trajectories.zoh_hold_pieces states where each one falls), a wrench per control tick (base_wrench [n_ticks,B,6]
+        instead of [B,6]), a trace (trace_every > 0: a sample [state | out | status] of every robot each time it has completed that many
+        control ticks, as rollout_trace lays it out; trace: a [n_ticks // trace_every, B, 180] device tensor, allocated here when None;
+        write_trace's sample_dt is trace_every * n_substeps * cfg.dt) and a metrics record (metrics: new_metrics' [B,208], folded once per
+        control tick at the tick's end; the records accumulate over launches).  With none of them the call is rollout_zoh's launch.
+        -> dict(out, status, log, trace); log and trace are None when not asked for."""
+        state = self._batch("state", state, capi.STATE_STRIDE, in_place=True)
+        for name, n in (("n_ticks", n_ticks), ("n_substeps", n_substeps), ("trace_every", trace_every)):
+            if int(n) != n or n < 0:
+                raise ValueError(f"{name} must be a whole number >= 0")
+        n_ticks, n_substeps, trace_every = int(n_ticks), int(n_substeps), int(trace_every)
+        per_tick = base_wrench is not None and getattr(base_wrench, "ndim", 0) == 3
+        if per_tick:
+            if isinstance(base_wrench, np.ndarray) and base_wrench.dtype == np.float64:           # (arrays as _ref_records takes them)
+                base_wrench = torch.from_numpy(np.ascontiguousarray(base_wrench)).to(self.device)
+            if not isinstance(base_wrench, torch.Tensor) or base_wrench.dtype != torch.float64 or tuple(base_wrench.shape) != (n_ticks, self.B, 6) \
+                    or base_wrench.device != self.device:
+                raise ValueError(f"base_wrench must be a [{self.B},6] or [{n_ticks},{self.B},6] float64 tensor on {self.device} (or such an array)")
+            bw = base_wrench.contiguous()
+            if bw.numel() == 0:                                    # (an empty tensor has no address to pass; with no tick no record is read)
+                bw = torch.empty((1,), dtype=torch.float64, device=self.device)
+        else:
+            bw = self._batch("base_wrench", base_wrench, 6, optional=True)
+        if trace is not None:                                      # the kernel writes n_samples records into it: a smaller buffer is an out-of-bounds write
+            n_samples = capi.lib().lmh_trace_samples(n_ticks, trace_every)
+            if not isinstance(trace, torch.Tensor) or trace.dtype != torch.float64 or trace.device != self.device or not trace.is_contiguous() \
+                    or trace.ndim != 3 or tuple(trace.shape[1:]) != (self.B, capi.TRACE_STRIDE) or trace.shape[0] < n_samples:
+                raise ValueError(f"trace must be a contiguous [n,{self.B},{capi.TRACE_STRIDE}] float64 tensor on {self.device} with n >= {n_samples}")
+        out, status, lg = self._rollout_buffers(n_ticks, out, status, log)
+        if ref is not None:
+            ref = self._ref_records(ref, (n_ticks,))
+            if ref.numel() == 0:
+                ref = torch.empty((1,), dtype=torch.float64, device=self.device)
+        if trace is None and trace_every > 0:
+            trace = torch.zeros((capi.lib().lmh_trace_samples(n_ticks, trace_every), self.B, capi.TRACE_STRIDE), dtype=torch.float64, device=self.device)
+        if trace is not None and trace.numel() == 0:               # zero samples: nothing is written, but the pointer has to be one
+            tr_arg = torch.empty((1,), dtype=torch.float64, device=self.device)
+        else:
+            tr_arg = trace
+        metrics = self._batch("metrics", metrics, capi.METRICS_STRIDE, optional=True, in_place=True)
+        opts = capi.LmhZohOpts(d_base_wrench=_dev_ptr(bw), d_ref=_dev_ptr(ref), d_log=_dev_ptr(lg), d_trace=_dev_ptr(tr_arg), d_metrics=_dev_ptr(metrics),
+                               trace_every=trace_every, wrench_per_tick=int(per_tick), pushes=int(bool(pushes)), reserved=0)
+        check(capi.lib().lmh_rollout_zoh_ex(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), n_ticks, n_substeps, self._stream()))
+        return dict(out=out, status=status, log=lg, trace=trace)
+
     @staticmethod
     def split_contact(c):
         """Named views of contact records [.., 40] (tensor or array): w [..,12] (n_R f_R n_L f_L), vertex_force [..,8,3], pad [..,4] --
@@ -737,7 +785,7 @@ class BatchedController:
     @staticmethod
     def write_trace(path, trace, sample_dt, t0=0.0):
         """lmh_write_trace: [n_samples,B,180] host array (lmh_rollout_trace's d_trace copied back); sample_dt = every * dt, t0 = the
-        clock of the first sample."""
+        clock of the first sample.  A trace of rollout_zoh_ex: sample_dt = trace_every * n_substeps * dt."""
         BatchedController._write_record(capi.lib().lmh_write_trace, path, "trace", trace, ("samples", "B", capi.TRACE_STRIDE), sample_dt, t0)
 
     @staticmethod

@@ -1025,17 +1025,35 @@ extern "C" int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_ta
 // lmh_rollout_zoh_kernel).  Refusals in the order of the two calls it composes: the handle, the pointers, the counts, then the precision and the
 // contact constants; the parameter block travels by value, so the call takes no launch slot.
 // with_ref (lmh_rollout_zoh_ref): d_ref is required too, refused behind the call's own pointers; every other refusal is lmh_rollout_zoh's, word for word.
+// opts (lmh_rollout_zoh_ex; nullptr in the two calls above it): its own refusals stand behind the counts they depend on and in front of the precision; an
+// all-zero record launches the kernels of the two calls above, anything else lmh_rollout_zoh_ex_kernel.
 static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log, const double *d_ref, bool with_ref,
-                    int n_ticks, int n_substeps, void *stream)
+                    int n_ticks, int n_substeps, void *stream, const lmh_zoh_opts *opts = nullptr)
 {
     int rc = ready(h); if (rc) return rc;
     if (!d_state || !d_out || !d_status) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: null device pointer");
     if (with_ref && !d_ref) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ref: null d_ref");
     if (n_ticks < 0 || n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: n_ticks and n_substeps must be >= 0");
+    LmhZohEx ex = {nullptr, nullptr, 0, 0, 0, 0};
+    if (opts) {
+        if ((opts->wrench_per_tick | 1) != 1) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ex: wrench_per_tick must be 0 or 1");
+        if ((opts->pushes | 1) != 1) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ex: pushes must be 0 or 1");
+        if (opts->reserved != 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ex: reserved must be 0");
+        if (opts->wrench_per_tick && !d_base_wrench) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ex: wrench_per_tick = 1 needs d_base_wrench");
+        if (opts->trace_every < 0 || (opts->d_trace != nullptr) != (opts->trace_every > 0))
+            return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ex: d_trace and trace_every > 0 go together (NULL and 0: no trace)");
+        if (opts->pushes && n_substeps == 0 && n_ticks > 0)
+            return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ex: pushes = 1 needs n_substeps > 0 (push ticks are plant substeps: with none the clock does not move)");
+        if (opts->pushes && (long long)n_ticks * n_substeps >= 0x3fffffffll)
+            return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ex: pushes = 1 needs n_ticks * n_substeps < 2^30 - 1");
+        ex.trace = opts->d_trace; ex.metrics = opts->d_metrics; ex.trace_every = opts->trace_every;
+        ex.wrench_per_tick = opts->wrench_per_tick; ex.pushes = opts->pushes;
+    }
     if (h->cfg.precision != LMH_PRECISION_FP64) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: LMH_PRECISION_FP64 handles only (this handle's precision has no instantiation of the kernel)");
     rc = plant_constants_ok(h); if (rc) return rc;
     if (n_ticks == 0) return LMH_OK;                                 // nothing to enqueue
-    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, (hipStream_t)stream); });
+    const bool plain = !ex.trace && !ex.metrics && !ex.wrench_per_tick && !ex.pushes;     // no new option: the kernels of before
+    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, plain ? nullptr : &ex, (hipStream_t)stream); });
 }
 extern "C" int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
                                int n_ticks, int n_substeps, void *stream)
@@ -1046,6 +1064,13 @@ extern "C" int lmh_rollout_zoh_ref(lmh_handle *h, double *d_state, double *d_out
                                    int n_ticks, int n_substeps, void *stream)
 {
     return zoh_body(h, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, true, n_ticks, n_substeps, stream);
+}
+// the wrench, the reference and the log ride in the record: NULL there is what NULL is in the two calls above (d_ref NULL: the built-in preview step)
+extern "C" int lmh_rollout_zoh_ex(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts, int n_ticks, int n_substeps, void *stream)
+{
+    static const lmh_zoh_opts none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
+    const lmh_zoh_opts *o = opts ? opts : &none;
+    return zoh_body(h, d_state, d_out, d_status, o->d_base_wrench, o->d_log, o->d_ref, false, n_ticks, n_substeps, stream, o);
 }
 
 extern "C" int lmh_terms_host(lmh_handle *h, const double *q, const double *v, double *terms)

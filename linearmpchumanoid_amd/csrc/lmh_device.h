@@ -23,7 +23,7 @@ struct LmhDevParams {
     const double *segs;         // [n_seg][LMH_SEG_STRIDE] walking segments: t0 | rF[3][8] | lF[3][8] | pad, or nullptr
     const uint16_t *seg_of_sample; // [n_samples] segment of preview index k
     const double *xscale;       // [n_instances] per-instance scale of ZMP x and x-axis foot polynomials, or nullptr
-    const double *pushes;       // [n_sets][n_push][LMH_PUSH_STRIDE] timed velocity pushes (lmh_rollout only), or nullptr while n_push = 0
+    const double *pushes;       // [n_sets][n_push][LMH_PUSH_STRIDE] timed velocity pushes (lmh_rollout, lmh_rollout_zoh_ex), or nullptr while n_push = 0
     const double *lcoef;        // [336][3] local-transform coefficients of the forward kinematics (build_lcoef): one table per handle
     const LmhDevParams *inst_blocks;   // per-robot parameters (lmh_set_params): [n_instances] whole blocks, block i = this block with robot i's 19
                                 // scalars, the five inv_w_* and gcol -> robot i's friction table (lmh_params_expand_kernel); nullptr = this block
@@ -58,6 +58,16 @@ struct LmhDevParams {
     double lF[3][8];
     int32_t rFn[3];
     int32_t lFn[3];
+};
+
+// lmh_rollout_zoh_ex (include/lmh.h, lmh_zoh_opts): what the launch takes beyond lmh_rollout_zoh's own arguments, by value in the kernel arguments
+struct LmhZohEx {
+    double *trace;              // [n_ticks / trace_every][n_instances][LMH_TRACE_STRIDE], or nullptr
+    double *metrics;            // [n_instances][LMH_METRICS_STRIDE], or nullptr
+    int32_t trace_every;        // control ticks per sample (> 0 whenever trace is there)
+    int32_t wrench_per_tick;    // 1: base_wrench is [n_ticks][n_instances][6]
+    int32_t pushes;             // 1: the block's push schedule is applied, ticks counted in plant substeps (n_ticks * n_substeps < 2^30 - 1)
+    int32_t pad;
 };
 
 // walking-plan generator (lmh_gen_walk): arguments of the device kernel

@@ -4789,6 +4789,8 @@ extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *
 //               Everything else an evaluation reads it has written itself (lmh_eval_kernel starts from an LDS image nobody initialised).
 // REF (lmh_rollout_zoh_ref_kernel): `ref` [n_ticks][B][LMH_MPC_STRIDE], record `tick` of the robot is the CoM reference of that tick's evaluation;
 // the helper wave, which runs chain A, reads it from global memory inside the chain (refs_chain_a): no broadcast, no further join.
+// TWIN: lmh_rollout_zoh_ex_body below repeats these statements (evaluation, log, hold, write-back, final store) with the options of
+// lmh_rollout_zoh_ex between them: a fix to the loop here belongs there too.
 template <bool REF>
 __device__ __forceinline__ void lmh_rollout_zoh_body(double *L, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps)
 {
@@ -4850,11 +4852,147 @@ __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_wav
     __shared__ double L[LDS_DOUBLES];
     lmh_rollout_zoh_body<true>(L, state, out, status, base_wrench, log, ref, n_ticks, n_substeps);
 }
-// ref NULL: lmh_rollout_zoh's kernel exactly as it is; otherwise lmh_rollout_zoh_ref's
-extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
-                                       hipStream_t s)
+// ---- lmh_rollout_zoh_ex (include/lmh.h): the loop above with timed pushes, a wrench per control tick, a trace and a metrics record.  A body
+// of its own, lmh_rollout_zoh_body's statements in its order: the two kernels above keep their text, and with it their code.  What is new:
+//   arguments   everything but the parameter block is read from the kernel-argument segment where it is used (ZohExArgs, as lmh_rollout_kernel
+//               reads its own): nothing of it is carried across controller_eval, where the kernels above already spill 74 / 80 scalars.
+//   pushes      ticks are plant substeps.  The cursor is the rollout's (P_PUSH: push_seek once, behind eval_begin, whose state load parks t in
+//               the slot; neither the evaluation nor the hold touches it), counted in substeps done, lim = n_ticks * n_substeps: a push on the
+//               substep the launch ends on stays for the next launch.  One due at a control tick's start goes into L[P_V] (not L[P_VP]) before
+//               the join in front of the evaluation -- the launch's first behind one more join, every later one behind the hold of the tick
+//               before it, after that tick's sample.  One inside a hold splits it: plant_hold keeps nothing but x between substeps, so
+//               plant_hold(a) ; v += dv ; plant_hold(b) is lmh_plant_step(a), the add, lmh_plant_step(b).
+//   wrench      lanes 0..5 of wave 0 load theirs once per control tick (record `tick` when there is one per tick): no register across the evaluation.
+//   sample/fold wave 0 alone, both halves.  Before the hold, behind the join that publishes the helper's torques: the out record (store_out:
+//               the hold overwrites the accelerations and the CoM) and metrics_wave1's words (torques, tracking error).  The helper cannot take
+//               them behind that join -- the hold's first phase_com_x would race with it -- and in this schedule it does not own the CoM words
+//               in front of it.  Behind the hold: q | v from x, v_prev, the clock, the flags, and metrics_wave0 (the wrench in P_W12 is the
+//               evaluation's still: the torque-driven plant keeps its own in PL_DW and writes P_W12 nowhere).
+struct ZohExArgs { double *state, *out; int32_t *status; const double *base_wrench; double *log; const double *ref; LmhZohEx ex; int n_ticks, n_substeps; };
+static_assert(sizeof(LmhDevParams) % 8 == 0 && alignof(ZohExArgs) == 8, "ZohExArgs mirrors the kernel arguments behind the parameter block");
+// wave 0, behind the hold: the state and status words of a sample and the pads of its three records (the out words left before the hold)
+__device__ __forceinline__ void zoh_trace_state(double *tr, int lane, double x, double vp, double t, int k, int itmax, int flags, unsigned F)
 {
-    if (ref) hipLaunchKernelGGL(lmh_rollout_zoh_ref_kernel, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, state, out, status, base_wrench, log, ref, n_ticks, n_substeps);
+    if (lane < 60) tr[lane] = x;                                   // q | v
+    if (lane < 30) tr[60 + lane] = vp;                             // v_prev: the v the evaluation saw
+    else if (lane < 36) tr[60 + lane] = (lane == 30) ? t : 0.0;    // t | pads [91, 96)
+    else if (lane < 38) tr[LMH_STATE_STRIDE + 78 + lane - 36] = 0.0;
+    else if (lane < 42) tr[LMH_STATE_STRIDE + LMH_OUT_STRIDE + lane - 38] = (lane == 38) ? (double)k : (lane == 39) ? (double)itmax : (lane == 40) ? (double)flags : (double)(int32_t)(~F);
+}
+template <bool REF>
+__device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
+{
+    LmhCParams &P0 = LMH_KERNARG_PARAMS();
+    typedef const __attribute__((address_space(4))) ZohExArgs CArgs;
+    auto KA = [&]() -> CArgs & {
+        CArgs *p_ = (CArgs *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(LmhDevParams));
+        asm volatile("" : "+s"(p_));
+        return *p_;
+    };
+    const int inst = blockIdx.x;
+    if (inst >= P0.n_instances) return;
+    LmhCParams &P = *params_of_robot(&P0, inst);
+    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    double t = KA().state[(size_t)LMH_STATE_STRIDE * inst + 90];
+    SET_GDBG(nullptr);
+    unsigned F = eval_begin<2>(L, P, inst, KA().state + (size_t)LMH_STATE_STRIDE * inst, KA().status, wid);
+    if (KA().ex.pushes) {                                          // (workgroup-uniform: both waves pass the join)
+        if (wid == 0) {
+            const int lane = LANE, lim = KA().n_ticks * KA().n_substeps;
+            int pc = 0;
+            if (push_seek(L, P, inst, lane, t, lim, &pc) == 0) {   // due at the launch's first substep: the first evaluation sees it
+                double x = L[P_Q + ((lane < 60) ? lane : 0)];
+                push_apply(L, P, inst, lane, 0, pc, lim, x);
+                if (lane >= 30 && lane < 60) L[P_Q + lane] = x;
+            }
+            WSYNC();
+        }
+        bsync<2>();
+    }
+    const double dt = P.dt;
+    int k = 0, itmax = 0, flags = 0;
+#pragma unroll 1
+    for (int tick = 0; tick < KA().n_ticks; tick++) {
+        int iters = 0;
+        flags |= controller_eval<2, double, false, false, NoWindow, false, REF>(L, P, inst, t, wid, &F, &k, &iters, nullptr, true, NoWindow(), nullptr, nullptr,
+                                                                                REF ? KA().ref + ((size_t)tick * P0.n_instances + inst) * LMH_MPC_STRIDE : nullptr);
+        itmax = (iters > itmax) ? iters : itmax;
+        bsync<2>();                                                // torques of the helper wave
+        const int nsub = KA().n_substeps;
+#pragma unroll 1
+        for (int sub = 0; sub < nsub; sub++) t += dt;              // Clock::step, Clock.hpp:11: the clock behind this tick's hold
+        if (wid == 0) {
+            const int lane = LANE, n_inst = P0.n_instances;
+            double bw = 0.0;                                       // lane i < 6: the wrench on the base during this hold
+            if (const double *wr = KA().base_wrench) { if (lane < 6) bw = wr[((size_t)(KA().ex.wrench_per_tick ? tick : 0) * n_inst + inst) * 6 + lane]; }
+            // what the evaluation produced leaves before the hold overwrites the accelerations and the CoM
+            if (tick == KA().n_ticks - 1) store_out(L, KA().out + (size_t)LMH_OUT_STRIDE * inst);
+            if (double *lg = KA().log) {
+                lg += ((size_t)tick * n_inst + inst) * 36;
+                if (lane < 24) lg[lane] = L[P_TAU + lane]; else if (lane < 36) lg[lane] = L[P_W12 + lane - 24];
+            }
+            if (double *trace = KA().ex.trace) {
+                double *tr = trace_slot(trace, KA().ex.trace_every, tick + 1, n_inst, inst);
+                if (tr) store_out(L, tr + LMH_STATE_STRIDE);
+            }
+            if (double *m = KA().ex.metrics) metrics_wave1<false>(m + (size_t)LMH_METRICS_STRIDE * inst, L, lane);
+            double x = L[P_Q + ((lane < 60) ? lane : 0)];          // q | v are one run
+            const double vp = L[P_V + ((lane < 30) ? lane : 0)];   // Robot::v_ <- dq (controller.cpp:59): what the next evaluation sees
+            const double tau = (lane < 6) ? bw : L[P_TAU + ((lane >= 6 && lane < 30) ? lane - 6 : 0)];         // lane i < 30: tau30[i] = [base wrench | out.tau]
+            const bool pushes = KA().ex.pushes != 0;
+            // substeps of the launch | of them behind the robot: the cursor's units, formed with pushes only (the host bounds the product then)
+            const int lim = pushes ? KA().n_ticks * nsub : 0;
+            int done = pushes ? tick * nsub : 0, r = nsub;         // r: substeps left of this hold
+#pragma unroll 1
+            while (r > 0) {                                        // one piece without pushes; a push inside the hold ends a piece
+                int s = r;
+                if (pushes) {
+                    const int rel = __builtin_amdgcn_readfirstlane(((const int *)(L + P_PUSH))[0]);
+                    if (rel > done && rel < done + r) s = rel - done;
+                }
+                plant_hold(L, P, ib_pack(), lane, tau, dt, s, x, flags);
+                done += s; r -= s;
+                if (r > 0) push_poll(L, P, inst, lane, done, lim, x);      // between two substeps: v += dv on the integrator's register
+            }
+            // the sample and the fold of this control tick: the state, the clock and the flags are the hold's
+            if (double *trace = KA().ex.trace) {
+                double *tr = trace_slot(trace, KA().ex.trace_every, tick + 1, n_inst, inst);
+                if (tr) zoh_trace_state(tr, lane, x, vp, t, k, itmax, flags, F);
+            }
+            if (double *m = KA().ex.metrics) metrics_wave0(m + (size_t)LMH_METRICS_STRIDE * inst, L, x, flags);
+            // a push on the first substep of the next control tick joins the state its evaluation reads, behind the sample (lim: never the
+            // substep the launch ends on)
+            if (pushes) push_poll(L, P, inst, lane, done, lim, x);
+            WSYNC();
+            if (lane < 60) L[P_Q + lane] = x;
+            if (lane < 30) L[P_VP + lane] = vp;
+            WSYNC();
+        }
+        bsync<2>();                                                // the helper wave starts the next evaluation's references on the new state
+    }
+    if (wid == 0) {
+        double *st = KA().state + (size_t)LMH_STATE_STRIDE * inst;
+        for (int e = LANE; e < 90; e += 64) st[e] = L[P_Q + e];    // q | v | v_prev
+        if (LANE == 0) { st[90] = t; store_status(KA().status, inst, k, itmax, flags, F); }
+    }
+}
+template <bool REF>
+__global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) lmh_rollout_zoh_ex_kernel(LmhDevParams P_arg, ZohExArgs A_arg)
+{
+    __shared__ double L[LDS_DOUBLES];
+    (void)A_arg;
+    lmh_rollout_zoh_ex_body<REF>(L);
+}
+// ex NULL: lmh_rollout_zoh's kernel exactly as it is when ref is NULL, otherwise lmh_rollout_zoh_ref's; with ex the kernel that takes the options
+extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
+                                       const LmhZohEx *ex, hipStream_t s)
+{
+    if (ex) {
+        const ZohExArgs a = {state, out, status, base_wrench, log, ref, *ex, n_ticks, n_substeps};
+        if (ref) hipLaunchKernelGGL(lmh_rollout_zoh_ex_kernel<true>, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, a);
+        else hipLaunchKernelGGL(lmh_rollout_zoh_ex_kernel<false>, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, a);
+    }
+    else if (ref) hipLaunchKernelGGL(lmh_rollout_zoh_ref_kernel, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, state, out, status, base_wrench, log, ref, n_ticks, n_substeps);
     else hipLaunchKernelGGL(lmh_rollout_zoh_kernel, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, state, out, status, base_wrench, log, n_ticks, n_substeps);
 }
 

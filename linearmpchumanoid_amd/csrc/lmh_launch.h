@@ -23,8 +23,10 @@ extern "C" void lmh_launch_eval(const LmhDevParams *P, double *state, double *ou
 // trace, trace_every: the samples of lmh_rollout_trace, NULL and 0 = none; metrics: the records of lmh_rollout_metrics, NULL = none; never both
 extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_P, int *d_ticket, double *state, double *out, int32_t *status, double *log, int n_ticks,
                                    double *trace, int trace_every, double *metrics, hipStream_t s);
+// ex (lmh_rollout_zoh_ex): NULL = the kernels of lmh_rollout_zoh / lmh_rollout_zoh_ref exactly as they are; otherwise lmh_rollout_zoh_ex_kernel with
+// these options (base_wrench is then [n_ticks][B][6] when ex->wrench_per_tick)
 extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
-                                       hipStream_t s);
+                                       const LmhZohEx *ex, hipStream_t s);
 extern "C" void lmh_launch_metrics_reset(double *metrics, int n_instances, double z_min, double tilt_max, hipStream_t s);
 extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
 extern "C" void lmh_launch_com(const LmhDevParams *P, const double *q, double *com, hipStream_t s);

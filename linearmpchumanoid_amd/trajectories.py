@@ -566,6 +566,32 @@ def draw_pushes(B, n, tick_range, amplitude, seed):
     return ticks, dv
 
 
+def zoh_hold_pieces(ticks, n0, n_ticks, n_substeps):
+    """Host statement of where one robot's pushes fall in a launch of lmh_rollout_zoh_ex (include/lmh.h): ticks [n] is the robot's schedule
+    as lmh_set_pushes keeps it (plant substep numbers, strictly increasing, unused trailing records -1), n0 = llrint(state[90] / dt) the
+    robot's substep number at the start of the launch.  -> one (start, pieces) per control tick: `start` is the index of the record applied
+    before that tick's evaluation (v += dv; None: none), `pieces` the hold as a list of (substeps, record or None) -- plant_step(substeps),
+    then v += dv of that record; the substeps of a tick's pieces add up to n_substeps and only the last piece may end without a push.
+    Records below n0 are in the past and appear nowhere; nor does one on the substep the launch ends on, n0 + n_ticks * n_substeps: the
+    next launch applies it before its first evaluation."""
+    n0, n_ticks, n_substeps = int(n0), int(n_ticks), int(n_substeps)
+    if n_ticks < 0 or n_substeps < 0:
+        raise ValueError("n_ticks and n_substeps must be >= 0")
+    due = {int(tk): c for c, tk in enumerate(np.asarray(ticks, dtype=np.float64)) if tk >= 0.0}
+    if len(due) and n_ticks > 0 and n_substeps == 0:
+        raise ValueError("pushes need n_substeps > 0 (push ticks are plant substeps: with none the clock does not move)")
+    result, n = [], n0
+    for _ in range(n_ticks):
+        start, pieces, r = due.get(n), [], n_substeps
+        while r > 0:
+            inside = [p for p in due if n < p < n + r]
+            s = min(inside) - n if inside else r
+            n, r = n + s, r - s
+            pieces.append((s, due[n] if inside else None))
+        result.append((start, pieces))
+    return result
+
+
 __all__ = ["stance_zmp", "find_poly_coeff", "foot_coeff_trajectory", "walk_plan", "jump_plan", "walk_plans", "jump_plans",
-           "push_schedule", "check_push_records", "draw_pushes", "preview_index", "lip_rollout", "com_targets",
+           "push_schedule", "check_push_records", "draw_pushes", "zoh_hold_pieces", "preview_index", "lip_rollout", "com_targets",
            "PHASE_DOUBLE", "PHASE_RIGHT", "PHASE_LEFT", "PHASE_FLIGHT"]

@@ -1,0 +1,587 @@
+"""lmh_rollout_zoh_ex on the GPU: the zero-order-hold loop with timed pushes, a wrench per control tick, a trace and a metrics record.
+
+The call is DEFINED by a host loop of calls that exist (include/lmh.h), so the reference of every bit-for-bit case is that loop on a second
+copy of the same buffers (_host_loop: stand_step, plant_step in the pieces trajectories.zoh_hold_pieces gives, v += dv in torch); only
+test_against_the_oracle goes to the CPU (zoh_ex_cases.oracle_ex_run).  Inputs: plant_step_cases.contact_states(), 16 states around
+touch-down, v_prev = v, warm_start = 1, a 2 s stance plan; six control ticks everywhere.  "Bit for bit" is helpers.same_bits.
+The pushes and wrenches are small enough that the host loop itself leaves no counted flag (flags & 15) on any robot -- asserted on the host
+loop's status wherever it runs, never on the kernel's."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import plant_step_cases as pc
+import zoh_ex_cases as zx
+from helpers import TOL_REL, WEIGHT, close, make_controller, rel_err, same_bits as _same, vec_err
+
+pytestmark = pytest.mark.gpu
+DT, TH, B, NT = pc.DT, pc.TH, pc.B, zx.N_TICKS
+FIVE_DT = sum([DT] * 5)           # a clock of five accumulated dt: the robot's substep number is 5
+NO_PUSH = 8
+# per-robot schedules (plant substep numbers, -1 = unused): between the four runs (n_substeps 3 | 1, from substep 0 | 5) they hold every
+# case of zoh_ex_cases.PIECE_CASES -- substep 0, control-tick boundaries, just behind one, two in one hold, the last substep, the launch's
+# end substep, the past, trailing -1 records
+SCHEDULES = [[0], [6], [7], [4, 5], [17], [18], [3, 9], [2, 6, -1, -1], [-1], [5, 8, 9, 10, 23, 24], [0, 1, 3, 5], [10, 11],
+             [1, 2, 22], [12, 15, 16], [8, 20, 21], [5, 6, 7, 11]]
+SHARED_SCHEDULE = [0, 4, 6, 7, 17, 18]
+
+
+def _schedules():
+    ticks = np.full((B, 6), -1, dtype=np.int64)
+    for i, s in enumerate(SCHEDULES):
+        ticks[i, :len(s)] = s
+    dv = np.stack([zx.push_dv(20261110 + i, 6) for i in range(B)])
+    return ticks, dv
+
+
+def _fresh(ctl, S, t=0.0):
+    return ctl.new_state(S["q"], S["v"], t=t, v_prev=S["v"])       # pads zero: a trace sample writes them as zeros
+
+
+def _applied(ticks, n0, n_ticks, n_substeps):
+    """per robot: (records applied before an evaluation, records applied inside a hold)"""
+    from linearmpchumanoid_amd.trajectories import zoh_hold_pieces
+    res = []
+    for i in range(B):
+        p = zoh_hold_pieces(ticks[i] if ticks.ndim == 2 else ticks, n0, n_ticks, n_substeps)
+        res.append(([(j, s) for j, (s, _) in enumerate(p) if s is not None], [r for _, h in p for _, r in h if r is not None]))
+    return res
+
+
+def _host_loop(ctl, st, status, n_ticks, n_substeps, bw=None, sched=None, refs=None):
+    """The definition on a handle WITHOUT a schedule.  bw: None | [B,6] | [n_ticks,B,6]; sched: None | (ticks [B,n] or [n], dv [B,n,30]).
+    -> dict(out, status with [1] / [2] merged as max / OR over the ticks and the plant's flags, log [n_ticks,B,36], trace [n_ticks,B,180]:
+    the three records after every control tick)."""
+    from linearmpchumanoid_amd.trajectories import zoh_hold_pieces
+    dev = ctl.device
+    out = ctl.new_out()
+    zero = torch.zeros((B, 6), dtype=torch.float64, device=dev)
+    rounds = torch.zeros((B,), dtype=torch.int32, device=dev)
+    flags = torch.zeros((B,), dtype=torch.int32, device=dev)
+    log = torch.zeros((n_ticks, B, 36), dtype=torch.float64, device=dev)
+    trace = torch.zeros((n_ticks, B, 180), dtype=torch.float64, device=dev)
+    pieces = None
+    if sched is not None:
+        ticks, dv = sched
+        n0 = np.rint(st[:, 90].cpu().numpy() / DT).astype(np.int64)
+        pieces = [zoh_hold_pieces(ticks[i] if ticks.ndim == 2 else ticks, n0[i], n_ticks, n_substeps) for i in range(B)]
+        dvt = torch.as_tensor(dv).to(dev)
+
+    def push(rows, recs):
+        if rows:
+            r = torch.as_tensor(rows, device=dev)
+            st[r, 30:60] += dvt[r, torch.as_tensor(recs, device=dev)]
+
+    for tick in range(n_ticks):
+        if pieces:
+            rows = [i for i in range(B) if pieces[i][tick][0] is not None]
+            push(rows, [pieces[i][tick][0] for i in rows])
+        ctl.stand_step(st, out, status, ref=None if refs is None else refs[tick])
+        log[tick] = out[:, 0:36]
+        base = zero if bw is None else (bw[tick] if bw.ndim == 3 else bw)
+        tau30 = torch.cat([base, out[:, 0:24]], dim=1).contiguous()
+        # the robots' holds are cut where any robot has a push: plant_step(a + b) is plant_step(a) ; plant_step(b) bit for bit
+        cuts = {}
+        if pieces:
+            for i in range(B):
+                at = 0
+                for s, rec in pieces[i][tick][1]:
+                    at += s
+                    if rec is not None:
+                        cuts.setdefault(at, []).append((i, rec))
+        at = 0
+        for c in sorted(cuts) + [n_substeps]:
+            if c > at:
+                _, pf = ctl.plant_step(st, tau30, c - at)
+                flags = flags | pf
+                at = c
+            if c in cuts:
+                push([i for i, _ in cuts[c]], [r for _, r in cuts[c]])
+        rounds = torch.maximum(rounds, status[:, 1])
+        flags = flags | status[:, 2]
+        trace[tick, :, 0:96] = st
+        trace[tick, :, 96:176] = out
+        trace[tick, :, 176] = status[:, 0].double()
+        trace[tick, :, 177] = rounds.double()
+        trace[tick, :, 178] = flags.double()
+        trace[tick, :, 179] = status[:, 3].double()
+    status[:, 1] = rounds
+    status[:, 2] = flags
+    return dict(out=out, status=status, log=log, trace=trace)
+
+
+def _no_counted_flag(status, but=()):
+    f = (status[:, 2] & 15).tolist()
+    assert all(v == 0 for i, v in enumerate(f) if i not in but), ("the host loop itself raised a counted flag", f)
+
+
+def _assert_same(tag, pairs):
+    for name, a, b in pairs:
+        if not _same(a, b):
+            d = (a.double() - b.double()).abs()
+            where = torch.nonzero(d.reshape(-1, d.shape[-1]).amax(dim=1) > 0).flatten().tolist()
+            raise AssertionError((tag, name, "rows that differ", where[:8], "max |difference|", float(d.max())))
+
+
+@pytest.fixture(scope="module")
+def zoh():
+    S = pc.contact_states()
+    ticks, dv = _schedules()
+    mk = lambda: make_controller(B, DT, TH, S["zcom"], warm_start=1)
+    ctl, shared, plain = mk(), mk(), mk()                          # per-robot schedules | one shared schedule | none: the host loop's handle
+    for c in (ctl, shared, plain):
+        c.set_refs_stance(2.0, 2)
+    ctl.set_pushes(ticks, dv)
+    shared.set_pushes(np.array(SHARED_SCHEDULE), dv[0])
+    dev = ctl.device
+    bw_seq = torch.as_tensor(zx.wrench_sequence(20261111, NT)).to(dev)
+    bw = torch.as_tensor(np.random.default_rng(20261112).normal(0.0, 1.0, (B, 6))).to(dev)
+    # a CoM reference per control tick and robot: the built-in step's words at the start state, moved per tick and robot by up to 5 mm,
+    # 2 cm/s and 0.1 m/s^2 (every record differs from every other: a wrong record shows); the words that are not read carry a sentinel
+    out0, _ = plain.stand_step(_fresh(plain, S))
+    refs = torch.full((NT, B, 16), -7.0e3, dtype=torch.float64, device=dev)
+    d = np.random.default_rng(20261113).uniform(-1.0, 1.0, (NT, B, 6)) * np.array([0.005, 0.02, 0.1, 0.005, 0.02, 0.1])
+    refs[:, :, 0:6] = out0[:, 72:78] + torch.as_tensor(d).to(dev)
+    yield dict(S=S, ctl=ctl, shared=shared, plain=plain, ticks=ticks, dv=dv, bw_seq=bw_seq, bw=bw, refs=refs)
+    for c in (ctl, shared, plain):
+        c.close()
+
+
+# ------------------------------------------------------------------------------- 1. no option set
+def test_no_option_is_rollout_zoh(zoh):
+    ctl, S, bw = zoh["ctl"], zoh["S"], zoh["bw"]                   # (a handle WITH a schedule: pushes=False must not apply it)
+    sa, sb = _fresh(ctl, S), _fresh(ctl, S)
+    ra = ctl.rollout_zoh_ex(sa, NT, 3, base_wrench=bw, log=True)
+    out_b, status_b, log_b = ctl.rollout_zoh(sb, NT, 3, base_wrench=bw, log=True)
+    _assert_same("plain", (("state", sa, sb), ("out", ra["out"], out_b), ("status", ra["status"], status_b), ("log", ra["log"], log_b)))
+    assert ra["trace"] is None
+    refs = zoh["refs"]
+    sa, sb = _fresh(ctl, S), _fresh(ctl, S)
+    ra = ctl.rollout_zoh_ex(sa, NT, 3, ref=refs, log=True)
+    out_b, status_b, log_b = ctl.rollout_zoh(sb, NT, 3, ref=refs, log=True)
+    _assert_same("ref alone", (("state", sa, sb), ("out", ra["out"], out_b), ("status", ra["status"], status_b), ("log", ra["log"], log_b)))
+    # the C call with no record at all, and with an all-zero one
+    from linearmpchumanoid_amd import capi
+    p = lambda t: C.c_void_p(t.data_ptr())
+    sb = _fresh(ctl, S)
+    out_b, status_b = ctl.rollout_zoh(sb, NT, 3)
+    for opts in (None, C.byref(capi.LmhZohOpts())):
+        sa, out_a, status_a = _fresh(ctl, S), ctl.new_out(), ctl.new_status()
+        assert capi.lib().lmh_rollout_zoh_ex(ctl._h, p(sa), p(out_a), p(status_a), opts, NT, 3, ctl._stream()) == 0
+        _assert_same("NULL / zero record", (("state", sa, sb), ("out", out_a, out_b), ("status", status_a, status_b)))
+
+
+# ------------------------------------------------------------------------------- 2. pushes against the host loop
+@pytest.mark.parametrize("t0", [0.0, FIVE_DT], ids=["from substep 0", "from substep 5"])
+@pytest.mark.parametrize("n_substeps", [1, 3])
+def test_pushes_are_the_host_loop_bit_for_bit(zoh, n_substeps, t0):
+    S, ticks, dv, plain = zoh["S"], zoh["ticks"], zoh["dv"], zoh["plain"]
+    n0 = int(np.rint(t0 / DT))
+    assert n0 == (0 if t0 == 0.0 else 5)
+    for name, sched in (("ctl", (ticks, dv)), ("shared", (np.array(SHARED_SCHEDULE), np.tile(dv[0], (B, 1, 1))))):
+        ctl = zoh[name]
+        sa, sb, sc = _fresh(ctl, S, t0), _fresh(plain, S, t0), _fresh(ctl, S, t0)
+        ra = ctl.rollout_zoh_ex(sa, NT, n_substeps, pushes=True, log=True)
+        rb = _host_loop(plain, sb, plain.new_status(), NT, n_substeps, sched=sched)
+        rc = ctl.rollout_zoh_ex(sc, NT, n_substeps, pushes=False, log=True)
+        torch.cuda.synchronize()
+        _no_counted_flag(rb["status"])
+        _assert_same((name, n_substeps, t0), (("state", sa, sb), ("out", ra["out"], rb["out"]), ("status", ra["status"], rb["status"]), ("log", ra["log"], rb["log"])))
+        assert float(sa[0, 90]) == sum([t0] + [DT] * (NT * n_substeps))
+        applied = _applied(sched[0], n0, NT, n_substeps)
+        pushed = [i for i in range(B) if applied[i][0] or applied[i][1]]
+        assert len(pushed) >= (8 if name == "ctl" else B)
+        for i in range(B):
+            assert _same(sa[i], sc[i]) == (i not in pushed), (name, i, "a pushed robot differs from pushes=False, an unpushed one does not")
+        if name == "ctl":
+            assert NO_PUSH not in pushed
+        # a robot pushed at a control tick's start: the evaluation saw the pushed v, and v_prev <- v kept it.  Checked on the launch's last
+        # tick through a one-tick launch from the host loop's state before it
+        last = [(i, s) for i in range(B) for j, s in applied[i][0] if j == NT - 1]
+        assert last or name == "shared"                              # (the per-robot schedules always hold such a push; the trace test checks the rule at sample 2 as well)
+        if last:
+            sd = _fresh(plain, S, t0)
+            _host_loop(plain, sd, plain.new_status(), NT - 1, n_substeps, sched=sched)
+            for i, rec in last:
+                assert _same(sa[i, 60:90], (sd[i, 30:60] + torch.as_tensor(sched[1][i, rec]).to(sd.device)))
+
+
+@pytest.mark.parametrize("t0", [0.0, FIVE_DT], ids=["from substep 0", "from substep 5"])
+@pytest.mark.parametrize("n_substeps", [1, 3])
+def test_pushes_wrench_sequence_and_reference_are_the_host_loop(zoh, n_substeps, t0):
+    """The kernel that takes a caller's CoM reference, with the options on: record j of the robot serves control tick j.  Against the host
+    loop of stand_step(ref=refs[j]); and not the bytes of the same launch with the records of two ticks exchanged."""
+    ctl, plain, S, refs, bw_seq = zoh["ctl"], zoh["plain"], zoh["S"], zoh["refs"], zoh["bw_seq"]
+    sa, sb, sc = _fresh(ctl, S, t0), _fresh(plain, S, t0), _fresh(ctl, S, t0)
+    ra = ctl.rollout_zoh_ex(sa, NT, n_substeps, base_wrench=bw_seq, ref=refs, pushes=True, log=True)
+    rb = _host_loop(plain, sb, plain.new_status(), NT, n_substeps, bw=bw_seq, sched=(zoh["ticks"], zoh["dv"]), refs=refs)
+    swapped = refs.clone()
+    swapped[[1, 4]] = refs[[4, 1]]
+    rc = ctl.rollout_zoh_ex(sc, NT, n_substeps, base_wrench=bw_seq, ref=swapped, pushes=True, log=True)
+    torch.cuda.synchronize()
+    _no_counted_flag(rb["status"])
+    _assert_same(("ref", n_substeps, t0), (("state", sa, sb), ("out", ra["out"], rb["out"]), ("status", ra["status"], rb["status"]), ("log", ra["log"], rb["log"])))
+    assert _same(ra["out"][:, 72:78].contiguous(), refs[NT - 1, :, 0:6].contiguous())      # the last tick's record
+    assert all(not _same(sa[i], sc[i]) for i in range(B)) and _same(ra["log"][0], rc["log"][0]) and not _same(ra["log"][1], rc["log"][1])
+
+
+def test_pushes_on_per_robot_walking_plans(zoh):
+    """One handle with a walking plan, a step length and a CoM height per robot (test_gpu_ref.py's plans for sixteen robots), pushes and a
+    wrench sequence on: the plans change segment at different ticks inside the run."""
+    S, ticks, dv, bw_seq = zoh["S"], zoh["ticks"], zoh["dv"], zoh["bw_seq"]
+    sp = dict(num_steps=4, time_per_step=0.006 + 0.001 * (np.arange(B) % 5), ds_time=0.002 + 0.001 * (np.arange(B) % 3), step_height=0.002,
+              settle_time=0.001 * (1 + np.arange(B) % 7), first_support=1 + np.arange(B) % 2)
+    ctls = []
+    for with_pushes in (True, False):
+        c = make_controller(B, DT, TH, S["zcom"], warm_start=1)
+        c.gen_walk_batch(0.2, sp)
+        c.set_xscale(0.002 + 0.0005 * np.arange(B))
+        c.set_zcom(S["zcom"] + 0.002 * np.arange(B))
+        if with_pushes:
+            c.set_pushes(ticks, dv)
+        ctls.append(c)
+    ctl, plain = ctls
+    sa, sb = _fresh(ctl, S), _fresh(plain, S)
+    ra = ctl.rollout_zoh_ex(sa, NT, 3, base_wrench=bw_seq, pushes=True, log=True)
+    rb = _host_loop(plain, sb, plain.new_status(), NT, 3, bw=bw_seq, sched=(ticks, dv))
+    torch.cuda.synchronize()
+    _assert_same("walking plans", (("state", sa, sb), ("out", ra["out"], rb["out"]), ("status", ra["status"], rb["status"]), ("log", ra["log"], rb["log"])))
+    assert len({tuple(ctl.get_plan(i)["seg_of_sample"][:18].tolist()) for i in range(B)}) >= 8
+    for c in ctls:
+        c.close()
+
+
+# ------------------------------------------------------------------------------- 3. per-tick wrench
+def test_wrench_sequence(zoh):
+    ctl, plain, S, bw_seq, bw = zoh["ctl"], zoh["plain"], zoh["S"], zoh["bw_seq"], zoh["bw"]
+    sa, sb = _fresh(ctl, S), _fresh(plain, S)
+    ra = ctl.rollout_zoh_ex(sa, NT, 3, base_wrench=bw_seq, log=True)
+    rb = _host_loop(plain, sb, plain.new_status(), NT, 3, bw=bw_seq)
+    torch.cuda.synchronize()
+    _no_counted_flag(rb["status"])
+    _assert_same("sequence", (("state", sa, sb), ("out", ra["out"], rb["out"]), ("status", ra["status"], rb["status"]), ("log", ra["log"], rb["log"])))
+    sn = _fresh(ctl, S)
+    rn = ctl.rollout_zoh_ex(sn, NT, 3, base_wrench=bw_seq.cpu().numpy(), log=True)          # the sequence as an array
+    _assert_same("sequence as an array", (("state", sn, sa), ("out", rn["out"], ra["out"]), ("log", rn["log"], ra["log"])))
+    sa, sb, sc = _fresh(ctl, S), _fresh(ctl, S), _fresh(ctl, S)
+    ra = ctl.rollout_zoh_ex(sa, NT, 3, base_wrench=bw.unsqueeze(0).repeat(NT, 1, 1), log=True)
+    out_b, status_b, log_b = ctl.rollout_zoh(sb, NT, 3, base_wrench=bw, log=True)
+    ctl.rollout_zoh(sc, NT, 3)
+    _assert_same("six copies", (("state", sa, sb), ("out", ra["out"], out_b), ("status", ra["status"], status_b), ("log", ra["log"], log_b)))
+    assert not _same(sa, sc)                                       # the wrench matters
+
+
+# ------------------------------------------------------------------------------- 4. trace
+def _everything(ctl, S, zoh, n_ticks, every=0, trace=None, metrics=None, status=None, st=None, first_tick=0, with_ref=True):
+    """Pushes, the wrench sequence, the log and (with_ref) the reference sequence on, both sequences sliced from first_tick."""
+    st = _fresh(ctl, S) if st is None else st
+    cut = slice(first_tick, first_tick + n_ticks)
+    r = ctl.rollout_zoh_ex(st, n_ticks, 3, base_wrench=zoh["bw_seq"][cut], ref=zoh["refs"][cut] if with_ref else None, pushes=True, log=True,
+                           trace_every=every, trace=trace, metrics=metrics, status=status)
+    return dict(r, state=st)
+
+
+def _everything_on_the_host(zoh, with_ref):
+    plain = zoh["plain"]
+    host = _host_loop(plain, _fresh(plain, zoh["S"]), plain.new_status(), NT, 3, bw=zoh["bw_seq"], sched=(zoh["ticks"], zoh["dv"]),
+                      refs=zoh["refs"] if with_ref else None)
+    torch.cuda.synchronize()
+    _no_counted_flag(host["status"])
+    return host
+
+
+WITH_REF = pytest.mark.parametrize("with_ref", [False, True], ids=["built-in preview", "caller's reference"])
+
+
+@WITH_REF
+@pytest.mark.parametrize("every", [1, 2, 4, 7])
+def test_trace_samples_are_the_records_of_shorter_launches(zoh, every, with_ref):
+    ctl, S = zoh["ctl"], zoh["S"]
+    n = NT // every
+    buf = torch.full((max(n, 1) + 1, B, 180), -7.0, dtype=torch.float64, device=ctl.device)      # one sample more than the call may write
+    r = _everything(ctl, S, zoh, NT, every, trace=buf, with_ref=with_ref)
+    whole = _everything(ctl, S, zoh, NT, with_ref=with_ref)
+    torch.cuda.synchronize()
+    _assert_same("the launch itself", (("state", r["state"], whole["state"]), ("out", r["out"], whole["out"]), ("status", r["status"], whole["status"]), ("log", r["log"], whole["log"])))
+    assert bool((buf[n:] == -7.0).all()) and (every != 4 or n == 1) and (every != 7 or n == 0)
+    host = _everything_on_the_host(zoh, with_ref)
+    for j in range(n):
+        m = (j + 1) * every
+        short = _everything(ctl, S, zoh, m, with_ref=with_ref)
+        torch.cuda.synchronize()
+        want = torch.cat([short["state"], short["out"], short["status"].double()], dim=1)
+        _assert_same(("sample", every, j), (("against the shorter launch", buf[j], want), ("against the host loop", buf[j], host["trace"][m - 1])))
+    if every == 1:
+        # robot 1's push is due at substep 6, the start of control tick 2: absent from sample 1's v, present in sample 2's (the evaluation
+        # of tick 2 saw it: it is that sample's v_prev)
+        unpushed = ctl.rollout_zoh_ex(_fresh(ctl, S), NT, 3, base_wrench=zoh["bw_seq"], ref=zoh["refs"] if with_ref else None, trace_every=1)["trace"]
+        torch.cuda.synchronize()
+        assert SCHEDULES[1] == [6] and _same(buf[1, 1, 0:60], unpushed[1, 1, 0:60]) and not _same(buf[2, 1, 30:60], unpushed[2, 1, 30:60])
+        assert _same(buf[2, 1, 60:90], buf[1, 1, 30:60] + torch.as_tensor(zoh["dv"][1, 0]).to(ctl.device))
+        assert bool((buf[:NT, :, 91:96] == 0).all()) and bool((buf[:NT, :, 174:176] == 0).all())
+
+
+# ------------------------------------------------------------------------------- 5. metrics
+@WITH_REF
+def test_metrics_are_the_fold_of_the_every_tick_trace(zoh, with_ref):
+    from linearmpchumanoid_amd import metrics as hm
+    ctl, S = zoh["ctl"], zoh["S"]
+    host = _everything_on_the_host(zoh, with_ref)
+    z = host["trace"][:, :, 2].cpu().numpy()                       # the host loop's own base heights at the ends of the control ticks
+    z_min, want_fall = np.full(B, -np.inf), np.full(B, -1)
+    for i in range(B):
+        if i % 4 == 3:
+            continue                                               # never down
+        ok = [f for f in range(NT) if f == 0 or z[f, i] < z[:f, i].min()]      # ticks that can be the first below a threshold
+        f = max(c for c in ok if c <= i % NT)
+        z_min[i] = z[f, i] + 1e-7 if f == 0 else 0.5 * (z[f, i] + z[:f, i].min())
+        want_fall[i] = f
+    assert len(set(want_fall.tolist())) >= 3 and (want_fall < 0).sum() >= 4
+    m_alone, m_both = ctl.new_metrics(z_min, np.inf), ctl.new_metrics(z_min, np.inf)
+    alone = _everything(ctl, S, zoh, NT, metrics=m_alone, with_ref=with_ref)
+    both = _everything(ctl, S, zoh, NT, every=1, metrics=m_both, with_ref=with_ref)
+    torch.cuda.synchronize()
+    ref = hm.fold_trace(hm.identity(B, z_min, np.inf), both["trace"].cpu().numpy())
+    assert _same(m_both.cpu().numpy(), ref) and _same(m_alone, m_both)
+    _assert_same("metrics change nothing else", (("state", alone["state"], both["state"]), ("out", alone["out"], both["out"]), ("status", alone["status"], both["status"])))
+    f = ctl.split_metrics(m_alone.cpu().numpy())
+    assert f["first_fall"].tolist() == want_fall.tolist() and f["count"].tolist() == [NT] * B and f["first_flag"].tolist() == [-1] * B
+    assert np.array_equal(f["wmin"], both["log"][:, :, 24:36].cpu().numpy().min(axis=0))      # the controller's wrench out.f, as the log has it
+    # two launches on one record accumulate to the six-tick record
+    m2 = ctl.new_metrics(z_min, np.inf)
+    a = _everything(ctl, S, zoh, 2, metrics=m2, with_ref=with_ref)
+    _everything(ctl, S, zoh, 4, metrics=m2, st=a["state"], status=a["status"].clone(), first_tick=2, with_ref=with_ref)
+    torch.cuda.synchronize()
+    assert _same(m2, m_alone)
+
+
+# ------------------------------------------------------------------------------- 6. split
+@WITH_REF
+def test_six_ticks_are_two_then_four_with_everything_on(zoh, with_ref):
+    """d_ref and the wrench sequence are sliced: the second launch takes records 2..5 of both."""
+    ctl, S = zoh["ctl"], zoh["S"]
+    assert SCHEDULES[1] == [6] and 6 in SCHEDULES[7]                # pushes on the substep the first launch ends on (2 x 3)
+    m6, m24 = ctl.new_metrics(0.3, 0.2), ctl.new_metrics(0.3, 0.2)
+    r6 = _everything(ctl, S, zoh, NT, every=2, metrics=m6, with_ref=with_ref)
+    r2 = _everything(ctl, S, zoh, 2, every=2, metrics=m24, with_ref=with_ref)
+    status2 = r2["status"].clone()
+    mid = r2["state"].clone()
+    r4 = _everything(ctl, S, zoh, 4, every=2, metrics=m24, st=r2["state"], status=r2["status"].clone(), first_tick=2, with_ref=with_ref)
+    torch.cuda.synchronize()
+    # status [1] / [2] of a sample count from its launch's start (lmh_rollout_trace's rule): the second launch's samples merge with the
+    # first launch's record as max / OR
+    tb = r4["trace"].clone()
+    tb[:, :, 177] = torch.maximum(tb[:, :, 177], status2[None, :, 1].double())
+    tb[:, :, 178] = (tb[:, :, 178].long() | status2[None, :, 2].long()).double()
+    _assert_same("split", (("state", r6["state"], r4["state"]), ("out", r6["out"], r4["out"]), ("log", r6["log"], torch.cat([r2["log"], r4["log"]])),
+                           ("trace", r6["trace"], torch.cat([r2["trace"], tb])), ("metrics", m6, m24)))
+    s6, s4 = r6["status"], r4["status"]
+    assert torch.equal(s6[:, 0], s4[:, 0]) and torch.equal(s6[:, 3], s4[:, 3])
+    assert torch.equal(s6[:, 1], torch.maximum(status2[:, 1], s4[:, 1])) and torch.equal(s6[:, 2], status2[:, 2] | s4[:, 2])
+    assert _same(mid[1, 30:60], r6["trace"][0, 1, 30:60])          # the record the first launch wrote does not hold the push at substep 6
+    assert r6["trace"].shape[0] == 3 and r2["trace"].shape[0] == 1
+    host = _everything_on_the_host(zoh, with_ref)                  # and the whole is the definition's
+    _assert_same("six ticks", (("state", r6["state"][:, 0:91], host["trace"][NT - 1, :, 0:91]), ("log", r6["log"], host["log"]),
+                               ("trace", r6["trace"], host["trace"][1::2])))
+    if with_ref:
+        assert _same(r6["out"][:, 72:78].contiguous(), zoh["refs"][NT - 1, :, 0:6].contiguous())
+
+
+# ------------------------------------------------------------------------------- 7. isolation
+def test_a_nan_state_flags_its_robot_alone(zoh):
+    from linearmpchumanoid_amd import capi
+    ctl, S = zoh["ctl"], zoh["S"]
+    bad, others = 5, [i for i in range(B) if i != 5]
+    runs = []
+    for broken in (False, True):
+        st = _fresh(ctl, S)
+        if broken:
+            st[bad, 8] = float("nan")
+        m = ctl.new_metrics(0.0, np.inf)
+        r = _everything(ctl, S, zoh, NT, every=1, metrics=m, st=st)
+        torch.cuda.synchronize()
+        runs.append(dict(r, metrics=m))
+    good, got = runs
+    assert int(got["status"][bad, 2]) & capi.FLAG_NONFINITE and all((int(got["status"][i, 2]) & 15) == 0 for i in others)
+    assert all(int(v) & capi.FLAG_NONFINITE for v in got["trace"][:, bad, 178].tolist())
+    f = ctl.split_metrics(got["metrics"].cpu().numpy())
+    assert f["first_flag"][bad] == 0 and (f["first_flag"][others] == -1).all()
+    for k in ("state", "out", "status", "metrics"):
+        assert _same(good[k][others], got[k][others]), k
+    for k in ("log", "trace"):
+        assert _same(good[k][:, others], got[k][:, others]), k
+
+
+# ------------------------------------------------------------------------------- 8. handle untouched
+def test_the_handle_is_untouched(zoh):
+    ctl, S = zoh["ctl"], zoh["S"]
+    st0 = ctl.new_state(S["q0"], S["v"] * 0.2, t=0.0)
+
+    def run():
+        a = st0.clone()
+        o1, s1 = ctl.stand_step(a)
+        b = st0.clone()
+        o2, s2, _ = ctl.rollout(b, 20)
+        torch.cuda.synchronize()
+        return a, o1, s1, b, o2, s2
+
+    before = run()
+    for _ in range(2):
+        _everything(ctl, S, zoh, NT, every=2, metrics=ctl.new_metrics())
+    torch.cuda.synchronize()
+    after = run()
+    for a, b in zip(before, after):
+        assert _same(a, b)
+
+
+# ------------------------------------------------------------------------------- 9. graph capture
+def test_captured_on_a_fresh_handle_replays_to_the_eager_bytes(zoh):
+    from linearmpchumanoid_amd import capi, metrics as hm
+    S = zoh["S"]
+    L = capi.lib()
+    p = lambda t: C.c_void_p(t.data_ptr())
+    ctl = make_controller(B, DT, TH, S["zcom"], warm_start=1)     # fresh: no launch before the capture
+    ctl.set_refs_stance(2.0, 2)
+    ctl.set_pushes(zoh["ticks"], zoh["dv"])
+    dev = ctl.device
+    refs = torch.zeros((NT, B, 16), dtype=torch.float64, device=dev)
+    refs[:, :, 0:6] = torch.as_tensor(np.random.default_rng(20261114).uniform(-0.01, 0.01, (NT, B, 6))).to(dev)
+    ident = torch.as_tensor(hm.identity(B, 0.3, 0.2)).to(dev)     # (not new_metrics: no launch of the handle's before the capture)
+    st0 = _fresh(ctl, S)
+    sent = lambda *shape: torch.full(shape, -7.0, dtype=torch.float64, device=dev)
+    st, out, status, log, trace, m = st0.clone(), sent(B, 80), ctl.new_status(), sent(NT, B, 36), sent(3, B, 180), ident.clone()
+    bw = zoh["bw_seq"].contiguous()
+    opts = capi.LmhZohOpts(d_base_wrench=p(bw), d_ref=p(refs), d_log=p(log), d_trace=p(trace), d_metrics=p(m), trace_every=2, wrench_per_tick=1, pushes=1, reserved=0)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        rc = L.lmh_rollout_zoh_ex(ctl._h, p(st), p(out), p(status), C.byref(opts), NT, 3, ctl._stream())
+    assert rc == 0
+    torch.cuda.synchronize()
+    assert _same(st, st0) and bool((out == -7).all()) and bool((trace == -7).all()) and _same(m, ident)       # captured, not run
+    g.replay()
+    torch.cuda.synchronize()
+    got = [x.clone() for x in (st, out, status, log, trace, m)]
+    del g
+    e_st, e_m = st0.clone(), ident.clone()
+    e = ctl.rollout_zoh_ex(e_st, NT, 3, base_wrench=bw, ref=refs, pushes=True, log=sent(NT, B, 36), trace_every=2, trace=sent(3, B, 180), metrics=e_m, out=sent(B, 80))
+    torch.cuda.synchronize()
+    for name, a, b in zip(("state", "out", "status", "log", "trace", "metrics"), got, (e_st, e["out"], e["status"], e["log"], e["trace"], e_m)):
+        assert _same(a, b), name
+    assert not bool((got[4] == -7).any()) and float(got[5][0, 0]) == NT
+    ctl.close()
+
+
+# ------------------------------------------------------------------------------- 10. refusals
+def test_refusals(zoh):
+    from linearmpchumanoid_amd import capi
+    S = zoh["S"]
+    L = capi.lib()
+    p = lambda t: C.c_void_p(t.data_ptr())
+    err = lambda: L.lmh_last_error().decode()
+    ctl = zoh["ctl"]
+    dev = ctl.device
+    st, out, status = _fresh(ctl, S), ctl.new_out(), ctl.new_status()
+    bw, trace, m = zoh["bw_seq"].contiguous(), torch.full((NT, B, 180), -7.0, dtype=torch.float64, device=dev), ctl.new_metrics()
+    torch.cuda.synchronize()
+    bufs = (st, out, status, trace, m)
+    sentinels = tuple(x.clone() for x in bufs)
+
+    def untouched():
+        torch.cuda.synchronize()
+        return all(_same(x, y) for x, y in zip(bufs, sentinels))
+
+    s = ctl._stream()
+    Z, Z0 = L.lmh_rollout_zoh_ex, L.lmh_rollout_zoh
+
+    def call(n_ticks=NT, n_substeps=3, state=st, handle=ctl, **fields):
+        o = capi.LmhZohOpts(**{k: (p(v) if isinstance(v, torch.Tensor) else v) for k, v in fields.items()})
+        return Z(handle._h, None if state is None else p(state), p(out), p(status), C.byref(o), n_ticks, n_substeps, s)
+
+    own = [(dict(wrench_per_tick=2, d_base_wrench=bw), "lmh_rollout_zoh_ex: wrench_per_tick must be 0 or 1"),
+           (dict(wrench_per_tick=-1, d_base_wrench=bw), "lmh_rollout_zoh_ex: wrench_per_tick must be 0 or 1"),
+           (dict(pushes=2), "lmh_rollout_zoh_ex: pushes must be 0 or 1"),
+           (dict(reserved=1), "lmh_rollout_zoh_ex: reserved must be 0"),
+           (dict(wrench_per_tick=1), "lmh_rollout_zoh_ex: wrench_per_tick = 1 needs d_base_wrench"),
+           (dict(d_trace=trace), "lmh_rollout_zoh_ex: d_trace and trace_every > 0 go together (NULL and 0: no trace)"),
+           (dict(trace_every=2), "lmh_rollout_zoh_ex: d_trace and trace_every > 0 go together (NULL and 0: no trace)"),
+           (dict(d_trace=trace, trace_every=-1), "lmh_rollout_zoh_ex: d_trace and trace_every > 0 go together (NULL and 0: no trace)")]
+    for fields, words in own:
+        assert call(d_metrics=m, **fields) == -2 and err() == words, fields
+    assert call(n_substeps=0, pushes=1, d_metrics=m) == -2 and err().startswith("lmh_rollout_zoh_ex: pushes = 1 needs n_substeps > 0")
+    assert call(n_ticks=1 << 20, n_substeps=1 << 10, pushes=1, d_metrics=m) == -2 and err() == "lmh_rollout_zoh_ex: pushes = 1 needs n_ticks * n_substeps < 2^30 - 1"
+    assert call(n_ticks=0, n_substeps=0, pushes=1, d_metrics=m, d_trace=trace, trace_every=1) == 0      # no tick: nothing to refuse, nothing enqueued
+    assert untouched()
+    # the refusals shared with lmh_rollout_zoh, in its words
+    assert call(state=None, pushes=1) == -2
+    mine = err()
+    assert Z0(ctl._h, None, p(out), p(status), None, None, NT, 3, s) == -2 and err() == mine == "lmh_rollout_zoh: null device pointer"
+    for n_ticks, n_sub in ((-1, 1), (1, -1)):
+        assert call(n_ticks=n_ticks, n_substeps=n_sub, d_metrics=m) == -2
+        mine = err()
+        assert Z0(ctl._h, p(st), p(out), p(status), None, None, n_ticks, n_sub, s) == -2 and err() == mine and "must be >= 0" in mine
+    assert Z(None, p(st), p(out), p(status), None, NT, 3, s) == -2 and err() == "null handle"
+    assert untouched()
+    # Python: shapes before the C call
+    for bad_call in (lambda: ctl.rollout_zoh_ex(st, -1, 1), lambda: ctl.rollout_zoh_ex(st, 1, 1.5), lambda: ctl.rollout_zoh_ex(st, 2, 1, trace_every=-1),
+                     lambda: ctl.rollout_zoh_ex(st, NT, 1, base_wrench=bw[0:3]), lambda: ctl.rollout_zoh_ex(st, NT, 1, base_wrench=bw[:, :, 0:5].contiguous()),
+                     lambda: ctl.rollout_zoh_ex(st, NT, 1, metrics=m[:, 0:100].contiguous()),
+                     # a trace buffer the launch would overrun, or of another type or layout
+                     lambda: ctl.rollout_zoh_ex(st, NT, 1, trace_every=1, trace=trace[0:NT - 1]), lambda: ctl.rollout_zoh_ex(st, NT, 1, trace_every=2, trace=trace.float()),
+                     lambda: ctl.rollout_zoh_ex(st, NT, 1, trace_every=2, trace=trace[:, :, 0:96]), lambda: ctl.rollout_zoh_ex(st, NT, 1, trace_every=2, trace=trace.cpu())):
+        with pytest.raises(ValueError):
+            bad_call()
+    assert untouched()
+    mixed = make_controller(B, DT, TH, S["zcom"], precision=capi.PRECISION_MIXED)
+    mixed.set_refs_stance(2.0, 2)
+    assert call(handle=mixed, pushes=1, d_metrics=m) == -2
+    mine = err()
+    assert Z0(mixed._h, p(st), p(out), p(status), None, None, NT, 3, s) == -2 and err() == mine and "lmh_rollout_zoh: LMH_PRECISION_FP64 handles only" in mine
+    mixed.close()
+    bad = make_controller(B, DT, TH, S["zcom"], plant=0, contact_k=-1.0)
+    bad.set_refs_stance(2.0, 2)
+    for n_ticks in (NT, 0):
+        assert call(handle=bad, n_ticks=n_ticks, pushes=1, d_metrics=m) == -2
+        mine = err()
+        assert Z0(bad._h, p(st), p(out), p(status), None, None, n_ticks, 3, s) == -2 and err() == mine and "contact_k" in mine
+    bad.close()
+    assert untouched()
+    # pushes = 1 on a handle without a schedule is legal and changes nothing
+    plain = zoh["plain"]
+    sa, sb = _fresh(plain, S), _fresh(plain, S)
+    ra = plain.rollout_zoh_ex(sa, NT, 3, pushes=True)
+    out_b, status_b = plain.rollout_zoh(sb, NT, 3)
+    _assert_same("no schedule", (("state", sa, sb), ("out", ra["out"], out_b), ("status", ra["status"], status_b)))
+
+
+# ------------------------------------------------------------------------------- 11. against the CPU oracle
+def test_against_the_oracle():
+    """Three control ticks x two substeps with a push at substep 3 (inside the second hold) and a wrench sequence against
+    zoh_ex_cases.oracle_ex_run, at the tolerances of test_gpu_zoh.py::test_against_the_oracle: 1e-7 on the state and on v_prev, helpers'
+    TOL_REL on tau and on f (f with the weight's floor), k exact.  Every figure is printed before it is asserted.  The oracle run itself
+    is flag-free (tests/test_zoh_ex.py checks it on the CPU)."""
+    S, I = pc.contact_states(), zx.oracle_ex_inputs()
+    ref = zx.oracle_ex_run()
+    ctl = make_controller(B, DT, TH, S["zcom"])
+    ctl.set_refs_stance(2.0, 2)
+    ctl.set_pushes(I["ticks"][None, :].repeat(B, axis=0), I["dv"])
+    st = _fresh(ctl, S)
+    r = ctl.rollout_zoh_ex(st, *zx.ORACLE_EX_RUN, base_wrench=torch.as_tensor(I["bw"]).to(ctl.device), pushes=True)
+    torch.cuda.synchronize()
+    a, o, s = st.cpu().numpy(), r["out"].cpu().numpy(), r["status"].cpu().numpy()
+    rows = []
+    for i in range(B):
+        w = ref[i]
+        rows.append((i, rel_err(a[i, :60], w["state"]), vec_err(o[i, 0:24], w["tau"]), vec_err(o[i, 24:36], w["f"]), int(s[i, 0]), int(w["k"][-1]), int(s[i, 2])))
+        print("\nzoh_ex vs oracle, robot %2d: state %.2e  tau %.2e  f %.2e  k %d (oracle %d)  flags %d" % rows[-1], end="")
+    print()
+    for i in range(B):
+        w = ref[i]
+        assert s[i, 2] == 0 and s[i, 0] == w["k"][-1], rows[i]
+        assert close(a[i, :60], w["state"], 1e-7), rows[i]
+        assert close(o[i, 0:24], w["tau"], TOL_REL) and close(o[i, 24:36], w["f"], TOL_REL, scale=WEIGHT), rows[i]
+        assert close(a[i, 60:90], w["v_prev"], 1e-7), rows[i]
+        assert a[i, 90] == w["t"]
+    ctl.close()
