@@ -375,7 +375,10 @@ int lmh_get_params(lmh_handle *h, int inst, double *record);
  * instances.  DEVICE pointers; d_state is read AND updated (v_prev <- v, as Robot::v_ is);
  * stream is a hipStream_t (NULL = default stream).  Asynchronous. */
 int lmh_eval(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, void *stream);
-/* same, additionally dumping intermediate terms for unit parity (DEVICE [B][LMH_DEBUG_STRIDE]) */
+/* same, additionally dumping intermediate terms for unit parity (DEVICE [B][LMH_DEBUG_STRIDE]).  The debug evaluation exists in fp64 and
+ * for LMH_PRECISION_FP32: on an LMH_PRECISION_MIXED handle it evaluates in fp64 (out, status and the record are an FP64 handle's, bit for
+ * bit); the taps of the fp32 model-term chain that MIXED shares are read on an FP32 handle.  In FP32 the record's cone Hessian (words
+ * 2093..3116) is only formed on the fp64 free-set route; W and h12 are always there. */
 int lmh_eval_debug(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, double *d_debug, void *stream);
 
 /* replaces: the closed loop of apps/offline/main.cpp:66-122 (rk4Step, rk4.hpp:5-18, of

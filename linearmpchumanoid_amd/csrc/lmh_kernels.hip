@@ -209,9 +209,8 @@ enum {
     F_U = S0 + 0,      // 18 x 30
     F_A = S0 + 540,    // 18 x 25 : [Cm | V] augmented system
     F_BP = S0 + 1016,  // 30 x 7  : bp' = [-qref | D^-1 Mb']
-    F_BQ = S0 + 1226,  // 30 : -qref + D^-1 U' Om beta (V's g column)
     F_S = S0 + 1260,   // 6 x 12 : [S | I]
-    F_OB = S0 + 1382,  // Om*beta (18) | 1/Om (18) | beta (18)
+    F_OB = S0 + 1382,  // 1/Om (18) | beta (18)
     F_T1 = S0 + 1436,  // 12 x 6
     F_K = S0 + 1520,   // 2 x 6 x 12 : [K_f | I] per foot
     F_KI = S0 + 1670,  // 2 x 36 : K_f^-1
@@ -2071,37 +2070,31 @@ __device__ __forceinline__ int qp_setup_f32(double *L, LmhCParams &P)
         const int rr = r0 + lane;
         const float om = (float)((rr < 3) ? P.w_com_ang : (rr < 6) ? P.w_com_lin : P.w_foot);
         const float beta = (rr < 6) ? (ldf(L, P_AGPQP + rr) - ldf(L, P_HREF + rr)) : (ldf(L, P_JPQP + rr - 6) - ldf(L, P_FREF + rr - 6));
-        L[F_OB + lane] = (double)(om * beta);
-        L[F_OB + 18 + lane] = (double)(1.0f / om);
-        L[F_OB + 36 + lane] = (double)beta;
+        L[F_OB + lane] = (double)(1.0f / om);
+        L[F_OB + 18 + lane] = (double)beta;
     }
     for (int e = lane; e < 210; e += 64) {
         const int i = e / 7, c = e % 7;
         L[F_BP + e] = (double)((c == 0) ? -ldf(L, P_QREF + i) : ldf(L, P_MTOP + 30 * (c - 1) + i) * iD(i));
     }
     WSYNC();
-    if (lane < 30) {                                               // q = D^-1 U' Om beta
-        float q = 0.0f;
-        for (int r = 0; r < nU; r++) q = fmaf(ldf(L, F_U + 30 * r + lane), ldf(L, F_OB + r), q);
-        L[F_BQ + lane] = (double)fmaf(q, iD(lane), ldf(L, F_BP + 7 * lane));
-    }
-    WSYNC();
-    for (int e = lane; e < nU * nA; e += 64) {                     // [Cm | V] = [Om^-1 + U D^-1 U' | U (bp'_g + q), U bp'_M]
+    // The g column of the right-hand side is U bp'_g - beta, so that the solve returns t'' itself.  qp_setup15's association (the column
+    // U (bp'_g + D^-1 U' Om beta), then t'' = t_g - Om beta, one fill less on its critical path) is exact algebra, but t_g and Om beta
+    // are w_foot |beta| ~ 1e6 .. 1e7 where t'' ~ 1e2: a difference that costs fp32 four to five of its seven digits.
+    for (int e = lane; e < nU * nA; e += 64) {                     // [Cm | V] = [Om^-1 + U D^-1 U' | U bp'_g - beta, U bp'_M]
         const int r = e / nA, c = e - r * nA;
         float sacc;
         if (c < nU) {
-            sacc = (r == c) ? ldf(L, F_OB + 18 + r) : 0.0f;
+            sacc = (r == c) ? ldf(L, F_OB + r) : 0.0f;
             for (int i = 0; i < 30; i++) sacc = fmaf(ldf(L, F_U + 30 * r + i) * iD(i), ldf(L, F_U + 30 * c + i), sacc);
         } else {
             const int n = c - nU;
-            sacc = 0.0f;
-            for (int i = 0; i < 30; i++) sacc = fmaf(ldf(L, F_U + 30 * r + i), (n == 0) ? ldf(L, F_BQ + i) : ldf(L, F_BP + 7 * i + n), sacc);
+            sacc = (n == 0) ? -ldf(L, F_OB + 18 + r) : 0.0f;
+            for (int i = 0; i < 30; i++) sacc = fmaf(ldf(L, F_U + 30 * r + i), ldf(L, F_BP + 7 * i + n), sacc);
         }
         L[F_A + 25 * r + c] = (double)sacc;
     }
-    if (gj_lds_f32(L + F_A, nU, 7, 25, (1u << nU) - 1u, 0.0f)) flags |= LMH_FLAG_NOT_SPD;
-    if (lane < nU) L[F_A + 25 * lane + nU] = (double)(ldf(L, F_A + 25 * lane + nU) - ldf(L, F_OB + lane));     // t'' = t_g - ob
-    WSYNC();
+    if (gj_lds_f32(L + F_A, nU, 7, 25, (1u << nU) - 1u, 0.0f)) flags |= LMH_FLAG_NOT_SPD;      // the right-hand columns now hold t'' | t_M
     for (int e = lane; e < 210; e += 64) {                         // Y = bp' - D^-1 U' t''  (stored transposed)
         const int n = e / 30, i = e % 30;
         float sacc = 0.0f;
@@ -2269,6 +2262,8 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
     *w_done = 0;
     const bool mine = (lane < 32) && !((forced >> lane) & 1u);
     int ninf = 33, budget = 3;
+    bool check = false;                                            // fp32: the next round closes the Lawson-Hanson pass
+    unsigned polished = 0u;                                        // coefficients a closing round has put into the set
     const int bpp_max = P.bpp_max;
     bool lh = bpp_max < 0;                                         // false: block pivoting, true: Lawson-Hanson
     if (lh) F = 0u;
@@ -2362,8 +2357,33 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
         const int have_ki = F32 ? 0 : __builtin_amdgcn_readfirstlane((F == (unsigned)L[P_KF + 1]) ? (int)L[P_KF + 2] : 0);   // prepared by the helper wave for the warm-start set
         double tolm = toll;                                        // dual sign test of this round
         bool pt;
-        if constexpr (F32) pt = !lh && cone_pushthrough_f32(L, P, F, &sj, &flags);
+        if constexpr (F32) pt = (!lh || check) && cone_pushthrough_f32(L, P, F, &sj, &flags);
         else pt = !lh && cone_pushthrough(L, P, F, have_ki, &sj, &flags);
+        if constexpr (F32) {
+            if (check) {
+                // Closing round of the Lawson-Hanson pass.  A bound coefficient of a foot that carries free ones has the multiplier -eps s_j,
+                // 1e-9 where toll, ten times the round-off of g_j'(W w - h), is 1e-14 |q| = 2e-9: the pass stops with coefficients of a few
+                // percent of max c left out.  On a set whose feet have full rank the push-through form gives s_j itself; it is tested as block
+                // pivoting tests it, and the largest violator joins the set, each coefficient once: should the two forms disagree about
+                // its sign, the pass drops it again and it stays out.
+                check = false;
+                if (!pt) break;                                    // a foot without K_f^-1: the residual form stands (cj holds the accepted point)
+                const bool fr = (lane < 32) && ((F >> lane) & 1u);
+                const double smax = wave_max((lane < 32) ? fabs(sj) : 0.0);
+                const bool footfree = ((lane & 16) ? (F >> 16) : (F & 0xFFFFu)) != 0u;
+                double sb = (mine && !fr && footfree && !((polished >> (lane & 31)) & 1u)) ? sj : -1.0e300;
+                int si = lane;
+                for (int o = 32; o > 0; o >>= 1) {
+                    const double ob = __shfl_xor(sb, o, 64); const int oi = __shfl_xor(si, o, 64);
+                    if (ob > sb || (ob == sb && oi < si)) { sb = ob; si = oi; }
+                }
+                if (!(sb > 2e-5 * (1.0 + smax))) break;
+                const unsigned bit = 1u << (__builtin_amdgcn_readfirstlane(si) & 31);
+                polished |= bit;
+                F |= bit;
+                continue;
+            }
+        }
         if (pt) {                                                  // 12 x 12 route: coefficients and multipliers from one vector
             RT_COUNT(1);
             w_thin = !F32;
@@ -2424,7 +2444,10 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
                     const double ob = __shfl_xor(best, o, 64); const int oi = __shfl_xor(bi, o, 64);
                     if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
                 }
-                if (!(best > toll)) break;                         // optimal
+                if (!(best > toll)) {                              // optimal, as far as the residual form of the multipliers can tell
+                    if (F32 && it < P.max_qp_iters) { check = true; continue; }     // fp32: a closing round (below the push-through solve)
+                    break;
+                }
                 F |= (1u << bi);
             } else {                                               // step towards z until a coefficient hits zero
                 double al = neg ? ((cj - zj > 0.0) ? cj / (cj - zj) : 0.0) : 1.0e300;
@@ -5159,7 +5182,7 @@ extern "C" void lmh_launch_eval(const LmhDevParams *P, double *state, double *ou
         else hipLaunchKernelGGL((lmh_eval_ref_kernel<double>), dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, state, out, status, ref);
         return;
     }
-    // precision 1 (LMH_PRECISION_MIXED): model terms in fp32 arithmetic, references and QP in fp64; the debug kernel is fp64 only
+    // precision 1 (LMH_PRECISION_MIXED): model terms in fp32 arithmetic, references and QP in fp64; the debug kernel is fp64 on such a handle (include/lmh.h)
     // LMH_DIAG_NW2=1: the debug kernel on the two-wave schedule (per-wave phase stamps; diagnostics only)
     static const bool diag_nw2 = getenv("LMH_DIAG_NW2") != nullptr;     // read once
     if (debug && diag_nw2) hipLaunchKernelGGL((lmh_eval_kernel<true, double, 2>), dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, state, out, status, debug);
