@@ -681,6 +681,41 @@ typedef struct lmh_zoh_opts {
 int lmh_rollout_zoh_ex(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts,
                        int n_ticks, int n_substeps, void *stream);
 
+/* ---- The zero-order-hold loop with the box-constrained preview step (lmh_mpc_box_step, below) closed around the MEASURED CoM inside it
+ * (build-defined): the predicted ZMP stays inside the caller's bounds while the robot is pushed, which a replayed plan (lmh_mpc_box_rollout's
+ * traj handed to lmh_rollout_zoh_ref) cannot do, in one launch and on one factorisation of the preview Hessian instead of a host loop of four
+ * launches per control tick that factors it on every tick.
+ * d_box, n_samples, n_sets: exactly what lmh_mpc_box_step takes ([n_sets][4][n_samples], rows LMH_BOX_*, metres, not scaled by xscale; n_sets 1
+ * or n_instances; n_samples == lmh_num_ref_samples).  d_mpc: DEVICE [n_ticks][B][LMH_MPC_STRIDE], sample-major, or NULL: the sample of every
+ * control tick's constrained step (xRef | yRef | zmp | state | t | k | flags | active).  opts: lmh_rollout_zoh_ex's record as it stands, or NULL;
+ * opts->d_ref must be NULL (a reference and the box step are exclusive).
+ * DEFINITION.  For every robot the call leaves, bit for bit, what lmh_rollout_zoh_ex's host loop (above) leaves with its line
+ *         lmh_eval (d_ref == NULL)  or  lmh_eval_ref(...)
+ * replaced by
+ *         x, xdot, y, ydot = out[66], out[69], out[67], out[70] of lmh_eval at the robot's current state record (pure functions of q and v: an
+ *                            lmh_eval on a scratch copy of the record gives them; behind a push that falls on the tick's start)
+ *         lip = x | xdot | y | ydot | state[90]
+ *         m   = lmh_mpc_box_step(lip, d_box, n_samples, n_sets)          -> d_mpc[j][i] when d_mpc != NULL
+ *         lmh_eval_ref(state, ref = m)
+ *         the tick's flags |= (int)m[LMH_MPC_OFF_FLAGS]                  (QP_MAXITER, NOT_SPD, BOX_EMPTY, ZMP_RANGE, NONFINITE)
+ * Everything else is lmh_rollout_zoh_ex's, word for word: the hold pieces, where pushes fall, the trace sample (whose out words are
+ * lmh_eval_ref's: out[72:78] are m[0:6]), the metrics fold, the status words, (a + b) equals (a) then (b) with d_mpc advanced by a records, the
+ * contact-constant checks, LMH_PRECISION_FP64 handles only, no launch slot, nothing written into the handle, capturable into a hipGraph from
+ * the first call on a fresh handle.  A robot whose window holds an empty or NaN box sample gets NaN reference words and so, by lmh_eval_ref's
+ * rule, LMH_FLAG_NONFINITE | LMH_FLAG_BOX_EMPTY; it disturbs no other robot.  Every tick starts from the empty working set.
+ * Refusals, each LMH_ERR_BAD_ARG before anything is enqueued and with a message of its own: NULL d_box, another n_samples, n_sets not 1 or
+ * n_instances, opts->d_ref != NULL; all of lmh_rollout_zoh_ex's apply as well.  n_ticks == 0 enqueues nothing.
+ * LDS: the constrained problem's tiles sit behind the evaluation's 40.9 KB and are sized by the handle's horizon N (7.3 KB at N = 16, 22.6 KB
+ * at N = 32, 77.8 KB at N = 64), which leaves three, two and one robot per CU where the plain loop has four.
+ * Cost: (one MI355X, 4096 standing robots x 200 control ticks, N = 32 x 10 ms): lmh_rollout_zoh itself is unchanged.  At
+ * n_substeps = 1 the call takes 141.7 ms under an infinite box and 269.0 ms with bounds active on every tick, against 62.1 ms for
+ * lmh_rollout_zoh and 227.8 / 467.0 ms for the host loop of four launches it replaces: 1.61 / 1.74 times faster than that loop.  At
+ * n_substeps = 10 the call is NOT faster than the host loop, it is slower: 770.6 / 813.5 ms against 581.9 / 658.5 ms, because the hold
+ * runs at two robots per CU where lmh_plant_step has four.  N = 16: 92.2 / 136.2 ms at n_substeps = 1; N = 64: 405 / 1462 ms.  Other batch
+ * sizes, walking plans and anything multi-GPU were not measured. */
+int lmh_rollout_zoh_box(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts,
+                        const double *d_box, int n_samples, int n_sets, double *d_mpc, int n_ticks, int n_substeps, void *stream);
+
 /* ---- LIPM preview MPC for a batch of reduced states (one kernel family of its own, one wave per robot, fp64): the stage of the controller
  * that lmh_eval runs between the momentum and the PD law, as calls of its own.
  * replaces: Mpc3dLip::compute (src/mpcLinearPendulum.cpp:78-109) for every robot of the handle, at that robot's own clock.

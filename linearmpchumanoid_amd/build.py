@@ -8,7 +8,7 @@ DIAG = os.environ.get("LMH_DIAG") == "1"          # diagnostic build (in-kernel 
 VARIANT = os.environ.get("LMH_VARIANT", "")       # experiment builds: LMH_VARIANT=name[:-DFLAG...] -> liblmh_hip_var_<name>.so (never shipped)
 SO = os.path.join(_HERE, "liblmh_hip_diag.so" if DIAG else ("liblmh_hip_var_%s.so" % VARIANT.split(":")[0] if VARIANT else "liblmh_hip.so"))
 SOURCES = ["lmh_kernels.hip", "lmh_mpc.hip", "lmh_capi.hip"]
-HEADERS = ["lmh_device.h", "lmh_launch.h", "lmh_nao_model.h", "lmh_dpp.h", os.path.join("..", "..", "include", "lmh.h")]
+HEADERS = ["lmh_device.h", "lmh_launch.h", "lmh_nao_model.h", "lmh_dpp.h", "lmh_mpc_qp.h", os.path.join("..", "..", "include", "lmh.h")]
 
 
 def needs_build():

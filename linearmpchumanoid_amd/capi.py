@@ -165,6 +165,7 @@ PROTOTYPES = {
     "lmh_rollout_zoh": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _vp]),
     "lmh_rollout_zoh_ref": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _vp]),
     "lmh_rollout_zoh_ex": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), _ip, _ip, _vp]),
+    "lmh_rollout_zoh_box": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), _vp, _ip, _ip, _vp, _ip, _ip, _vp]),
     "lmh_mpc_step": (_ip, [_vp, _vp, _vp, _vp]),
     "lmh_mpc_rollout": (_ip, [_vp, _vp, _ip, _vp, _vp]),
     "lmh_mpc_preview": (_ip, [_vp, _vp, _vp, _vp]),

@@ -576,6 +576,33 @@ class BatchedController:
         write_trace's sample_dt is trace_every * n_substeps * cfg.dt) and a metrics record (metrics: new_metrics' [B,208], folded once per
         control tick at the tick's end; the records accumulate over launches).  With none of them the call is rollout_zoh's launch.
         -> dict(out, status, log, trace); log and trace are None when not asked for."""
+        return self._rollout_zoh_opts(state, n_ticks, n_substeps, base_wrench, ref, pushes, log, trace_every, trace, metrics, out, status, None)
+
+    def rollout_zoh_box(self, state, box, n_ticks, n_substeps, mpc=True, base_wrench=None, pushes=False, log=False, trace_every=0, trace=None,
+                        metrics=None, out=None, status=None, ref=None):
+        """lmh_rollout_zoh_box: rollout_zoh_ex with the box-constrained preview step closed around the measured CoM inside every control tick
+        -- bit for bit the host loop { lip_from_out(stand_step on a scratch copy) ; mpc_box_step ; stand_step(ref=) ; plant_step } -- on one
+        factorisation per launch.  box as mpc_box_step takes it ([4,n_samples] or [B,4,n_samples]).  mpc=True: the samples [n_ticks,B,16] of
+        every tick's constrained step (split_mpc; word 15: the active samples) are returned under "mpc"; False: not stored; a tensor: filled.
+        There is no ref: a reference and the box step are exclusive.  -> rollout_zoh_ex's dict plus mpc."""
+        if ref is not None:
+            raise ValueError("rollout_zoh_box takes no ref: the box-constrained step is the reference (the two are exclusive)")
+        bx, ns, sets = self._box(box)
+        if int(n_ticks) != n_ticks or n_ticks < 0:
+            raise ValueError("n_ticks must be a whole number >= 0")
+        n = int(n_ticks)
+        tr = torch.zeros((n, self.B, capi.MPC_STRIDE), dtype=torch.float64, device=self.device) if mpc is True else (mpc if mpc is not False else None)
+        if tr is not None and (not isinstance(tr, torch.Tensor) or tr.dtype != torch.float64 or tr.device != self.device or not tr.is_contiguous()
+                               or tr.numel() < n * self.B * capi.MPC_STRIDE):
+            raise ValueError(f"mpc must be a contiguous [{n},{self.B},{capi.MPC_STRIDE}] float64 tensor on {self.device}")
+        mp_arg = tr if (tr is None or tr.numel() > 0) else torch.empty((1,), dtype=torch.float64, device=self.device)
+        res = self._rollout_zoh_opts(state, n_ticks, n_substeps, base_wrench, None, pushes, log, trace_every, trace, metrics, out, status,
+                                     (_dev_ptr(bx), ns, sets, _dev_ptr(mp_arg)))
+        res["mpc"] = tr
+        return res
+
+    def _rollout_zoh_opts(self, state, n_ticks, n_substeps, base_wrench, ref, pushes, log, trace_every, trace, metrics, out, status, box_call):
+        """The argument handling rollout_zoh_ex and rollout_zoh_box share; box_call: None, or lmh_rollout_zoh_box's (d_box, n_samples, n_sets, d_mpc)."""
         state = self._batch("state", state, capi.STATE_STRIDE, in_place=True)
         for name, n in (("n_ticks", n_ticks), ("n_substeps", n_substeps), ("trace_every", trace_every)):
             if int(n) != n or n < 0:
@@ -612,7 +639,12 @@ class BatchedController:
         metrics = self._batch("metrics", metrics, capi.METRICS_STRIDE, optional=True, in_place=True)
         opts = capi.LmhZohOpts(d_base_wrench=_dev_ptr(bw), d_ref=_dev_ptr(ref), d_log=_dev_ptr(lg), d_trace=_dev_ptr(tr_arg), d_metrics=_dev_ptr(metrics),
                                trace_every=trace_every, wrench_per_tick=int(per_tick), pushes=int(bool(pushes)), reserved=0)
-        check(capi.lib().lmh_rollout_zoh_ex(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), n_ticks, n_substeps, self._stream()))
+        if box_call is None:
+            check(capi.lib().lmh_rollout_zoh_ex(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), n_ticks, n_substeps, self._stream()))
+        else:
+            d_box, ns, sets, d_mpc = box_call
+            check(capi.lib().lmh_rollout_zoh_box(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), d_box, ns, sets, d_mpc,
+                                                 n_ticks, n_substeps, self._stream()))
         return dict(out=out, status=status, log=lg, trace=trace)
 
     @staticmethod
@@ -808,6 +840,22 @@ DEBUG_FIELDS = {
     "Y": (1691, (30, 7)), "Si": (1901, (6, 6)), "W": (1937, (12, 12)), "h12": (2081, (12,)),
     "P": (2093, (32, 32)), "qv": (3117, (32,)), "c": (3149, (32,)), "a": (3181, (30,)),
 }
+
+
+def lip_from_out(out, t):
+    """The LIP records [B,8] (x | xdot | y | ydot | t | pad) of out records [B,80] (tensor or array): the CoM and its velocity an evaluation
+    measured, out[66] | out[69] | out[67] | out[70], at the clock(s) t (a scalar or [B]: state[:, 90]) -- what mpc_box_step takes in a host loop
+    that closes the constrained step around the whole-body controller (rollout_zoh_box is that loop in one launch)."""
+    if isinstance(out, torch.Tensor):
+        lip = torch.zeros((out.shape[0], capi.LIP_STRIDE), dtype=out.dtype, device=out.device)
+        lip[:, 0:4] = out[:, [66, 69, 67, 70]]
+        lip[:, 4] = torch.as_tensor(t, dtype=out.dtype, device=out.device)
+        return lip
+    out = np.asarray(out)
+    lip = np.zeros((out.shape[0], capi.LIP_STRIDE), dtype=out.dtype)
+    lip[:, 0:4] = out[:, [66, 69, 67, 70]]
+    lip[:, 4] = np.broadcast_to(np.asarray(t, dtype=out.dtype), (out.shape[0],))
+    return lip
 
 
 def unpack_debug(dbg_row):

@@ -49,6 +49,7 @@ struct RefPlan {
 };
 
 struct lmh_handle {
+    int zoh_box_prepared = -1;   // what the runtime answered when lmh_create asked for lmh_rollout_zoh_box_kernel's dynamic LDS limit (hipSuccess = 0)
     lmh_config cfg;
     double mpc_dt = 0.0;              // resolved MPC sample time (cfg.mpc_dt, or cfg.dt when that is 0)
     int B = 0, device = 0, N = 0, n_models = 0, n_gain = 0;
@@ -448,6 +449,13 @@ extern "C" int lmh_create(const lmh_config *cfg, int n_instances, int device, lm
     h->cfg = *cfg; h->B = n_instances; h->device = device; h->N = N; h->mpc_dt = mpc_dt;
     const int rc = create_body(h, cfg, n_instances);                // every failure path releases what was allocated so far
     if (rc != LMH_OK) { std::string keep = g_err; lmh_destroy(h); g_err = keep; return rc; }
+    {                                                               // lmh_rollout_zoh_box's dynamic LDS: asked for here, never inside the (capturable) call
+        int32_t answer = -1;
+        const LmhZohBox prep = {nullptr, 0, nullptr, 0.0, 0.0, 1, &answer};
+        lmh_launch_rollout_zoh(&h->P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &prep, nullptr);
+        h->zoh_box_prepared = answer;
+    }
+    (void)hipGetLastError();                                        // an answer other than hipSuccess is that call's to report, not a sticky error of this one
     *out = h;
     return LMH_OK;
 }
@@ -1027,12 +1035,21 @@ extern "C" int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_ta
 // with_ref (lmh_rollout_zoh_ref): d_ref is required too, refused behind the call's own pointers; every other refusal is lmh_rollout_zoh's, word for word.
 // opts (lmh_rollout_zoh_ex; nullptr in the two calls above it): its own refusals stand behind the counts they depend on and in front of the precision; an
 // all-zero record launches the kernels of the two calls above, anything else lmh_rollout_zoh_ex_kernel.
+// bx (lmh_rollout_zoh_box; nullptr in the three calls above it): the bounds of lmh_mpc_box_step and where the samples go.  Its refusals stand behind the
+// call's own pointers; the launch is lmh_rollout_zoh_box_kernel's whatever the options.
+struct ZohBoxCall { const double *d_box; int n_samples, n_sets; double *d_mpc; };
 static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log, const double *d_ref, bool with_ref,
-                    int n_ticks, int n_substeps, void *stream, const lmh_zoh_opts *opts = nullptr)
+                    int n_ticks, int n_substeps, void *stream, const lmh_zoh_opts *opts = nullptr, const ZohBoxCall *bx = nullptr)
 {
     int rc = ready(h); if (rc) return rc;
     if (!d_state || !d_out || !d_status) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: null device pointer");
     if (with_ref && !d_ref) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ref: null d_ref");
+    if (bx) {
+        if (const char *why = box_refusal(h, bx->d_box, bx->n_samples, bx->n_sets, "lmh_rollout_zoh_box: null d_box",
+                                          "lmh_rollout_zoh_box: n_samples must be lmh_num_ref_samples", "lmh_rollout_zoh_box: n_sets must be 1 or n_instances"))
+            return fail(LMH_ERR_BAD_ARG, why);
+        if (d_ref) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_box: opts->d_ref must be NULL (the box-constrained step is the reference: the two are exclusive)");
+    }
     if (n_ticks < 0 || n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: n_ticks and n_substeps must be >= 0");
     LmhZohEx ex = {nullptr, nullptr, 0, 0, 0, 0};
     if (opts) {
@@ -1052,8 +1069,14 @@ static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_st
     if (h->cfg.precision != LMH_PRECISION_FP64) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: LMH_PRECISION_FP64 handles only (this handle's precision has no instantiation of the kernel)");
     rc = plant_constants_ok(h); if (rc) return rc;
     if (n_ticks == 0) return LMH_OK;                                 // nothing to enqueue
+    if (bx) {
+        if (h->zoh_box_prepared != 0 && h->N > 33)                   // N >= 34: above 64 KB of LDS in all, only with the limit lmh_create asked for
+            return fail(LMH_ERR_HIP, "lmh_rollout_zoh_box: the runtime refused the kernel's dynamic shared memory limit when the handle was created");
+        const LmhZohBox zb = {bx->d_box, box_stride(h, bx->n_sets), bx->d_mpc, h->cfg.alpha, h->cfg.beta, 0, nullptr};
+        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, nullptr, n_ticks, n_substeps, &ex, &zb, (hipStream_t)stream); });
+    }
     const bool plain = !ex.trace && !ex.metrics && !ex.wrench_per_tick && !ex.pushes;     // no new option: the kernels of before
-    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, plain ? nullptr : &ex, (hipStream_t)stream); });
+    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, plain ? nullptr : &ex, nullptr, (hipStream_t)stream); });
 }
 extern "C" int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
                                int n_ticks, int n_substeps, void *stream)
@@ -1071,6 +1094,16 @@ extern "C" int lmh_rollout_zoh_ex(lmh_handle *h, double *d_state, double *d_out,
     static const lmh_zoh_opts none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
     const lmh_zoh_opts *o = opts ? opts : &none;
     return zoh_body(h, d_state, d_out, d_status, o->d_base_wrench, o->d_log, o->d_ref, false, n_ticks, n_substeps, stream, o);
+}
+
+// lmh_rollout_zoh_ex with lmh_mpc_box_step closing the loop inside every evaluation (include/lmh.h)
+extern "C" int lmh_rollout_zoh_box(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts, const double *d_box, int n_samples, int n_sets,
+                                   double *d_mpc, int n_ticks, int n_substeps, void *stream)
+{
+    static const lmh_zoh_opts none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
+    const lmh_zoh_opts *o = opts ? opts : &none;
+    const ZohBoxCall bx = {d_box, n_samples, n_sets, d_mpc};
+    return zoh_body(h, d_state, d_out, d_status, o->d_base_wrench, o->d_log, o->d_ref, false, n_ticks, n_substeps, stream, o, &bx);
 }
 
 extern "C" int lmh_terms_host(lmh_handle *h, const double *q, const double *v, double *terms)

@@ -70,6 +70,18 @@ struct LmhZohEx {
     int32_t pad;
 };
 
+// lmh_rollout_zoh_box (include/lmh.h): what the launch takes beyond lmh_rollout_zoh_ex's -- lmh_mpc_box_step's bounds and weights, where the samples go.
+// prepare: nothing is launched; the kernel's dynamic shared memory limit is set on the current device for the largest horizon and the runtime's
+// answer (a hipError_t) is stored through `answer`.  Once per handle, when it is created: never inside the call, which is captured into graphs.
+struct LmhZohBox {
+    const double *box;          // the robot's [4][n_samples] bounds at box + box_stride * robot (box_stride 0: one shared set)
+    size_t box_stride;
+    double *mpc;                // [n_ticks][n_instances][LMH_MPC_STRIDE], or nullptr
+    double alpha, beta;         // the preview problem's weights (lmh_config)
+    int32_t prepare;
+    int32_t *answer;
+};
+
 // walking-plan generator (lmh_gen_walk): arguments of the device kernel
 #define LMH_GEN_MAX_STEPS 1022
 struct LmhWalkSpec {

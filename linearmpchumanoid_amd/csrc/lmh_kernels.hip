@@ -1362,6 +1362,53 @@ __device__ __forceinline__ double readlane_f64(double v, int src_lane)       // 
     const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)((unsigned long long)b >> 32), src_lane);
     return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
 }
+struct ZohExArgs { double *state, *out; int32_t *status; const double *base_wrench; double *log; const double *ref; LmhZohEx ex; int n_ticks, n_substeps; };
+static_assert(sizeof(LmhDevParams) % 8 == 0 && alignof(ZohExArgs) == 8, "ZohExArgs mirrors the kernel arguments behind the parameter block");
+// lmh_rollout_zoh_box_kernel's arguments: lmh_rollout_zoh_ex_kernel's, then what the constrained step takes (lmh_mpc_box_step's box, stride and
+// weights) and where its samples go.  The helper wave reads the second part inside its reference chain, where it is used.
+struct ZohBoxArgs { ZohExArgs a; const double *box; size_t box_stride; double *mpc; double alpha, beta; };
+static_assert(sizeof(ZohExArgs) % 8 == 0 && alignof(ZohBoxArgs) == 8, "ZohBoxArgs continues ZohExArgs in the kernel-argument segment");
+typedef const __attribute__((address_space(4))) ZohBoxArgs CZohBoxArgs;
+__device__ __forceinline__ CZohBoxArgs &zoh_box_args()
+{
+    CZohBoxArgs *p_ = (CZohBoxArgs *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(LmhDevParams));
+    asm volatile("" : "+s"(p_));
+    return *p_;
+}
+#include "lmh_mpc_qp.h"
+// The constrained step's LDS, behind the evaluation's static image (dynamic shared memory of lmh_rollout_zoh_box_kernel alone), sized by the
+// handle's horizon n = N + 1: the packed L | G tile (row stride ldb, odd, >= n + 1), the tile T (row stride ld, odd, >= n), sixteen [n] arrays of
+// doubles, three of ints, and three words the waves exchange: H's factor is positive definite | G is formed | the flags of this tick's sample.
+extern __shared__ double lmh_box_lds[];
+__host__ __device__ inline int zoh_box_ld(int n) { return n | 1; }
+__host__ __device__ inline int zoh_box_ldb(int n) { return (n + 1) | 1; }
+__host__ __device__ inline int zoh_box_lds_doubles(int n) { return n * zoh_box_ldb(n) + n * zoh_box_ld(n) + 16 * n + (3 * n + 1) / 2 + 2; }
+enum { ZB_SPD, ZB_HAVE_G, ZB_FLAGS };
+__device__ __forceinline__ int *zoh_box_words(int n) { return (int *)(lmh_box_lds + zoh_box_lds_doubles(n) - 2); }
+__device__ __forceinline__ BoxArrays zoh_box_arrays(int n)
+{
+    double *h = lmh_box_lds, *t = h + n * zoh_box_ldb(n), *a = t + n * zoh_box_ld(n);
+    const BoxArrays A = {h, t, zoh_box_ldb(n), zoh_box_ld(n), a, a + n, a + 2 * n, a + 3 * n, a + 4 * n, a + 5 * n, n, a + 9 * n, n, a + 11 * n, n, a + 13 * n, n,
+                         (int *)(a + 16 * n), n};
+    return A;
+}
+// Once per launch, on the helper wave behind eval_begin: pt, H = L L' (lmh_mpc_qp_kernel's set-up statements).  G waits for the first round.
+__device__ __forceinline__ void zoh_box_setup(LmhCParams &P, int inst)
+{
+    const int lane = LANE, n = P.horizon + 1;
+    const BoxArrays A = zoh_box_arrays(n);
+    const double *mp = P.mpc + (size_t)P.mpc_stride_inst * inst;
+    const double D = mp[3 * n + 1];
+    const double e = pv_pt_entry(P.mpc_dt, P.b0, lane);
+    if (lane < n - 1) A.pt[lane] = e;                              // pt[m], m <= N - 1, is all that is read
+    if (lane == 0) A.pt[n - 1] = 0.0;
+    WSYNC();
+    pv_form_h(A.H, A.ldb, A.pt, D, zoh_box_args().alpha, zoh_box_args().beta, n, lane);
+    const bool spd = pv_factor<true>(A.H, A.ldb, n, lane);
+    WSYNC();
+    if (lane == 0) { int *w = zoh_box_words(n); w[ZB_SPD] = spd ? 1 : 0; w[ZB_HAVE_G] = 0; w[ZB_FLAGS] = 0; }
+    WSYNC();
+}
 // Chain A in one piece: Dynamics::centroidalMatrixAndBias (AG, Dynamics.cpp:103-121), Robot::computeComMomentum (Robot.cpp:300-310),
 // Mpc3dLip::compute (mpcLinearPendulum.cpp:78-109: u0 = -K (Px x_k - z[k : k+N+1]); K (Px x_k - z) = x sum K Px0 + xdot sum K Px1 - sum K z,
 // the three sums do not depend on the robot state and are prepared early, refs_prepare / load_common) and PDMomentumAcc
@@ -1374,12 +1421,16 @@ __device__ __forceinline__ double readlane_f64(double v, int src_lane)       // 
 // `ref` (global memory nobody writes during the launch, wave-uniform address).  The wave that runs this chain loads the six words itself,
 // here, ahead of the AG rows whose sums they follow, so no other wave and no join is involved; the gain sums are not formed.  The CoM velocity,
 // the PD law and the stores to L[P_MPC ..] are the built-in path's.
-template <bool REF = false>
-__device__ __forceinline__ int refs_chain_a(double *L, LmhCParams &P, int inst, int k, double mass, bool ang, const double *ref = nullptr)
+// BOX (lmh_rollout_zoh_box, with REF): xRef | yRef are the sample of lmh_mpc_box_step at this evaluation's CoM state and clock `t`, formed here by
+// this wave's 64 lanes on the factor zoh_box_setup left (box_tick: lmh_mpc_qp_kernel<QP_BOX_STEP>'s statements with the wave-scope fence for
+// the workgroup barrier -- no join is passed).  `ref` is then where the sample goes (this robot's record of this tick, or NULL); its flags
+// reach wave 0 through the word ZB_FLAGS, behind the join that publishes the chain.
+template <bool REF = false, bool BOX = false>
+__device__ __forceinline__ int refs_chain_a(double *L, LmhCParams &P, int inst, int k, double mass, bool ang, const double *ref = nullptr, double t = 0.0)
 {
     const int lane = LANE, l16 = lane & 15, q4 = lane >> 4, a = (q4 < 3) ? q4 : 2;
     double rx[3] = {0.0, 0.0, 0.0}, ry[3] = {0.0, 0.0, 0.0};
-    if constexpr (REF) {
+    if constexpr (REF && !BOX) {
 #pragma unroll
         for (int i = 0; i < 3; i++) { rx[i] = ref[LMH_MPC_OFF_XREF + i]; ry[i] = ref[LMH_MPC_OFF_YREF + i]; }
     }
@@ -1416,7 +1467,25 @@ __device__ __forceinline__ int refs_chain_a(double *L, LmhCParams &P, int inst, 
     // MPC: u0 = -K (Px x_k - z[k : k+N+1]) (refs_mpc)
     const double cxp = L[P_COM], cyp = L[P_COM + 1], czp = L[P_COM + 2];
     double ux, uy, xp, xv, yp, yv;
-    if constexpr (REF) { xp = rx[0]; xv = rx[1]; ux = rx[2]; yp = ry[0]; yv = ry[1]; uy = ry[2]; }
+    if constexpr (BOX) {
+        const int n = N + 1;
+        const BoxArrays A = zoh_box_arrays(n);
+        int *bwd = zoh_box_words(n);
+        const bool spd = __builtin_amdgcn_readfirstlane(bwd[ZB_SPD]) != 0;
+        bool have_g = __builtin_amdgcn_readfirstlane(bwd[ZB_HAVE_G]) != 0;
+        const LipAB M = {P.a00, P.a01, P.a10, P.a11, P.b0, P.b1};
+        const size_t ro = (size_t)P.ref_stride * (size_t)inst;
+        MpcSample S;
+        const int act = box_tick<true>(A, M, n, P.n_samples, lane, k, flags, L[P_RXS], P.zmpx + ro, P.zmpy + ro, mp + n, mp + 2 * n, mp[3 * n + 1], zoh_box_args().beta,
+                                       zoh_box_args().box + zoh_box_args().box_stride * (size_t)inst, spd, have_g, cxp, vxp, cyp, vyp, S);
+        if (lane == 0) { bwd[ZB_HAVE_G] = have_g ? 1 : 0; bwd[ZB_FLAGS] = S.flags; }
+        if (ref) {
+            double *rec = const_cast<double *>(ref);
+            mpc_store_sample(rec, lane, S, cxp, vxp, cyp, vyp, t);
+            if (lane == LMH_MPC_OFF_ACTIVE) rec[lane] = (double)act;
+        }
+        xp = S.xp; xv = S.xv; ux = S.ux; yp = S.yp; yv = S.yv; uy = S.uy;
+    } else if constexpr (REF) { xp = rx[0]; xv = rx[1]; ux = rx[2]; yp = ry[0]; yv = ry[1]; uy = ry[2]; }
     else {
         const double kp0 = L[P_PRE + 2], kp1 = L[P_PRE + 3];
         ux = -((kp0 * cxp + kp1 * vxp) - L[P_RXS] * L[P_PRE]);
@@ -1499,7 +1568,7 @@ __device__ __forceinline__ void refs_pd_feet(double *L, LmhCParams &P, int inst,
     }
 }
 
-template <int NW, bool ORI_MAYBE = false, bool CGLIN = true, bool REF = false>
+template <int NW, bool ORI_MAYBE = false, bool CGLIN = true, bool REF = false, bool BOX = false>
 __device__ __forceinline__ int phase_refs(double *L, LmhCParams &P, int inst, double t, int wid, int *k_out, int *phase_out, bool ang, const double *ref = nullptr)
 {
     int flags = 0;
@@ -1519,7 +1588,8 @@ __device__ __forceinline__ int phase_refs(double *L, LmhCParams &P, int inst, do
         WSYNC();
     } else if (wid == 1) {                                         // chain A
         WSTAMP(66);
-        flags |= refs_chain_a<REF>(L, P, inst, k, mass, ang, ref);
+        if constexpr (BOX) flags |= refs_chain_a<REF, true>(L, P, inst, k, mass, ang, ref, t);
+        else flags |= refs_chain_a<REF>(L, P, inst, k, mass, ang, ref);
         WSYNC();
     } else {                                                       // chain B
         WSTAMP(67);
@@ -3366,7 +3436,8 @@ __device__ __forceinline__ void phase_outputs_qdd(double *L, int a_src = P_A)
 // `window` (phase_qp), and so were the clock-only references; wave 0 starts at the X images.
 // REF: the momentum task tracks the caller's CoM reference `ref` (this robot's record of this evaluation, see refs_chain_a) instead of the
 // built-in preview step's.
-template <int NW, typename R, bool QF32 = false, bool PIPE = false, class WF = NoWindow, bool TAIL = false, bool REF = false>
+// BOX (with REF, NW = 2): the reference is the box-constrained preview step's, formed inside chain A (refs_chain_a); `ref` is where its sample goes.
+template <int NW, typename R, bool QF32 = false, bool PIPE = false, class WF = NoWindow, bool TAIL = false, bool REF = false, bool BOX = false>
 __device__ __forceinline__ int controller_eval(double *L, LmhCParams &P, int inst, double t, int wid, unsigned *Fmask, int *k_out, int *iters_out, double *dbg, bool need_tau = true, WF window = WF(),
                                                const IbPack *ibp = nullptr, RkTail *tailp = nullptr, const double *ref = nullptr)
 {
@@ -3439,7 +3510,7 @@ __device__ __forceinline__ int controller_eval(double *L, LmhCParams &P, int ins
     WSTAMP(6);
     STAMP(6);
     const bool ang = (P.w_com_ang != 0.0) || (dbg != nullptr);     // angular-momentum rows: only when weighted (or dumped)
-    flags |= phase_refs<NW, PIPE, std::is_same_v<R, double>, REF>(L, P, inst, t, wid, k_out, &ph, ang, ref);        // PIPE: the feet's orientation term may have been formed behind the look-ahead kinematics
+    flags |= phase_refs<NW, PIPE, std::is_same_v<R, double>, REF, BOX>(L, P, inst, t, wid, k_out, &ph, ang, ref);        // PIPE: the feet's orientation term may have been formed behind the look-ahead kinematics
     if (NW == 2 && wid == 0 && P.w_com_ang == 0.0 && !QF32) { WSTAMP(68); qp_prefill15(L, P); }      // ahead of the join: wave 1's chain is the longer one
     WSTAMP(7);
     bsync<NW>();
@@ -3448,6 +3519,7 @@ __device__ __forceinline__ int controller_eval(double *L, LmhCParams &P, int ins
         // published (behind the join: wave 0 writes the status record)
         const double w = L[P_MPC + 2 + ((LANE < 6) ? LANE : 0)];
         if (__ballot(!(fabs(w) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
+        if constexpr (BOX) flags |= __builtin_amdgcn_readfirstlane(zoh_box_words(P.horizon + 1)[ZB_FLAGS]);      // the sample's flags (lmh_mpc_box_step's)
     }
     WSTAMP(8);
     STAMP(7);
@@ -4891,8 +4963,7 @@ __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_wav
 //               them behind that join -- the hold's first phase_com_x would race with it -- and in this schedule it does not own the CoM words
 //               in front of it.  Behind the hold: q | v from x, v_prev, the clock, the flags, and metrics_wave0 (the wrench in P_W12 is the
 //               evaluation's still: the torque-driven plant keeps its own in PL_DW and writes P_W12 nowhere).
-struct ZohExArgs { double *state, *out; int32_t *status; const double *base_wrench; double *log; const double *ref; LmhZohEx ex; int n_ticks, n_substeps; };
-static_assert(sizeof(LmhDevParams) % 8 == 0 && alignof(ZohExArgs) == 8, "ZohExArgs mirrors the kernel arguments behind the parameter block");
+// (ZohExArgs: beside the reference chain, which reads the arguments of the box-constrained loop from the same segment)
 // wave 0, behind the hold: the state and status words of a sample and the pads of its three records (the out words left before the hold)
 __device__ __forceinline__ void zoh_trace_state(double *tr, int lane, double x, double vp, double t, int k, int itmax, int flags, unsigned F)
 {
@@ -4902,9 +4973,14 @@ __device__ __forceinline__ void zoh_trace_state(double *tr, int lane, double x, 
     else if (lane < 38) tr[LMH_STATE_STRIDE + 78 + lane - 36] = 0.0;
     else if (lane < 42) tr[LMH_STATE_STRIDE + LMH_OUT_STRIDE + lane - 38] = (lane == 38) ? (double)k : (lane == 39) ? (double)itmax : (lane == 40) ? (double)flags : (double)(int32_t)(~F);
 }
-template <bool REF>
+// MODE: where the momentum task's CoM reference comes from.  ZM_BOX (lmh_rollout_zoh_box_kernel): every control tick runs lmh_mpc_box_step at the
+// measured CoM state inside the evaluation's chain A (refs_chain_a); the preview Hessian is factored once, behind eval_begin, by the helper wave
+// alone (wave-scope fences: both waves pass the same joins as in the other modes) while wave 0 goes on to the pushes and the kinematics.
+enum { ZM_BUILTIN, ZM_REF, ZM_BOX };
+template <int MODE>
 __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
 {
+    constexpr bool REF = MODE != ZM_BUILTIN, BOX = MODE == ZM_BOX;
     LmhCParams &P0 = LMH_KERNARG_PARAMS();
     typedef const __attribute__((address_space(4))) ZohExArgs CArgs;
     auto KA = [&]() -> CArgs & {
@@ -4919,6 +4995,7 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
     double t = KA().state[(size_t)LMH_STATE_STRIDE * inst + 90];
     SET_GDBG(nullptr);
     unsigned F = eval_begin<2>(L, P, inst, KA().state + (size_t)LMH_STATE_STRIDE * inst, KA().status, wid);
+    if constexpr (BOX) { if (wid == 1) zoh_box_setup(P, inst); }
     if (KA().ex.pushes) {                                          // (workgroup-uniform: both waves pass the join)
         if (wid == 0) {
             const int lane = LANE, lim = KA().n_ticks * KA().n_substeps;
@@ -4937,6 +5014,11 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
 #pragma unroll 1
     for (int tick = 0; tick < KA().n_ticks; tick++) {
         int iters = 0;
+        if constexpr (BOX) {
+            double *mpc = zoh_box_args().mpc;
+            flags |= controller_eval<2, double, false, false, NoWindow, false, true, true>(L, P, inst, t, wid, &F, &k, &iters, nullptr, true, NoWindow(), nullptr, nullptr,
+                                                                                           mpc ? mpc + ((size_t)tick * P0.n_instances + inst) * LMH_MPC_STRIDE : nullptr);
+        } else
         flags |= controller_eval<2, double, false, false, NoWindow, false, REF>(L, P, inst, t, wid, &F, &k, &iters, nullptr, true, NoWindow(), nullptr, nullptr,
                                                                                 REF ? KA().ref + ((size_t)tick * P0.n_instances + inst) * LMH_MPC_STRIDE : nullptr);
         itmax = (iters > itmax) ? iters : itmax;
@@ -5004,13 +5086,30 @@ __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_wav
 {
     __shared__ double L[LDS_DOUBLES];
     (void)A_arg;
-    lmh_rollout_zoh_ex_body<REF>(L);
+    lmh_rollout_zoh_ex_body<REF ? ZM_REF : ZM_BUILTIN>(L);
+}
+// lmh_rollout_zoh_box (include/lmh.h): the same body with the box-constrained step in the loop.  The constrained problem's tiles live in dynamic
+// shared memory behind L, sized by the handle's horizon (zoh_box_lds_doubles): 7.3 KB at N = 16, 22.6 KB at N = 32, 77.8 KB at N = 64.
+__global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) lmh_rollout_zoh_box_kernel(LmhDevParams P_arg, ZohBoxArgs A_arg)
+{
+    __shared__ double L[LDS_DOUBLES];
+    (void)A_arg;
+    lmh_rollout_zoh_ex_body<ZM_BOX>(L);
 }
 // ex NULL: lmh_rollout_zoh's kernel exactly as it is when ref is NULL, otherwise lmh_rollout_zoh_ref's; with ex the kernel that takes the options
 extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
-                                       const LmhZohEx *ex, hipStream_t s)
+                                       const LmhZohEx *ex, const LmhZohBox *bx, hipStream_t s)
 {
-    if (ex) {
+    // bx: lmh_rollout_zoh_box_kernel.  The most dynamic shared memory such a launch may ask for (N = LMH_MAX_HORIZON) is above the 64 KB a kernel gets
+    // unasked: bx->prepare sets that limit on the current device and launches nothing.
+    if (bx && bx->prepare) {
+        const int bytes = (int)sizeof(double) * zoh_box_lds_doubles(LMH_MAX_HORIZON + 1);
+        *bx->answer = (int32_t)hipFuncSetAttribute(reinterpret_cast<const void *>(lmh_rollout_zoh_box_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    } else if (bx) {
+        const ZohBoxArgs a = {{state, out, status, base_wrench, log, nullptr, *ex, n_ticks, n_substeps}, bx->box, bx->box_stride, bx->mpc, bx->alpha, bx->beta};
+        const size_t bytes = sizeof(double) * (size_t)zoh_box_lds_doubles(P->horizon + 1);
+        hipLaunchKernelGGL(lmh_rollout_zoh_box_kernel, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), bytes, s, *P, a);
+    } else if (ex) {
         const ZohExArgs a = {state, out, status, base_wrench, log, ref, *ex, n_ticks, n_substeps};
         if (ref) hipLaunchKernelGGL(lmh_rollout_zoh_ex_kernel<true>, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, a);
         else hipLaunchKernelGGL(lmh_rollout_zoh_ex_kernel<false>, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, a);

@@ -25,8 +25,11 @@ extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_
                                    double *trace, int trace_every, double *metrics, hipStream_t s);
 // ex (lmh_rollout_zoh_ex): NULL = the kernels of lmh_rollout_zoh / lmh_rollout_zoh_ref exactly as they are; otherwise lmh_rollout_zoh_ex_kernel with
 // these options (base_wrench is then [n_ticks][B][6] when ex->wrench_per_tick)
+// bx (lmh_rollout_zoh_box; ex is then never NULL and ref is): NULL = the kernels above; otherwise lmh_rollout_zoh_box_kernel, that loop with lmh_mpc_box_step at
+// the measured CoM state inside every evaluation -- or, with bx->prepare, no launch at all (LmhZohBox, lmh_device.h).  The same launcher, not a new symbol: the
+// stand-alone host programs under tests/host link lmh_capi.hip against one stub per launcher.
 extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
-                                       const LmhZohEx *ex, hipStream_t s);
+                                       const LmhZohEx *ex, const LmhZohBox *bx, hipStream_t s);
 extern "C" void lmh_launch_metrics_reset(double *metrics, int n_instances, double z_min, double tilt_max, hipStream_t s);
 extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
 extern "C" void lmh_launch_com(const LmhDevParams *P, const double *q, double *com, hipStream_t s);

@@ -24,17 +24,7 @@
 #define WSYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 #define WSTAMP(i) do { } while (0)
 #include "lmh_dpp.h"
-
-// a * b + c with the product and the sum rounded separately (numpy's c + a * b): the product goes through an opaque register, which the
-// contraction of the build's default (fused multiply-add) cannot see through
-__device__ __forceinline__ double mul_then_add(double a, double b, double c)
-{
-    double p = a * b;
-    asm volatile("" : "+v"(p));
-    return c + p;
-}
-
-__device__ __forceinline__ bool finite_f64(double v) { return fabs(v) <= 1.7976931348623157e308; }      // false for NaN and Inf
+#include "lmh_mpc_qp.h"                                            // the maths the fused closed loop shares (lmh_kernels.hip)
 
 // What a wave keeps of its robot's gain record for a whole launch: K_lane (lane <= N) and K_64 (lane 0, N = 64: the second trip of the
 // window loop), the two state-independent sums, the model's output gain D = -z_com / gravity (the record's first pad word, formed on the
@@ -65,8 +55,6 @@ __device__ __forceinline__ int mpc_index(const LmhDevParams &P, double t, int &f
     return k;
 }
 
-__device__ __forceinline__ int mpc_clamp(int kk, int ns) { return (kk < 0) ? 0 : (kk >= ns ? ns - 1 : kk); }
-
 // sum_j K_j z[k + j] of both axes over the clamped window (refs_prepare): a coalesced window load per axis and trip
 __device__ __forceinline__ void mpc_window(const LmhDevParams &P, const double *zx, const double *zy, const MpcGain &G, int k, int lane, double &wx, double &wy)
 {
@@ -79,11 +67,6 @@ __device__ __forceinline__ void mpc_window(const LmhDevParams &P, const double *
     }
     wx = wave_sum(sx); wy = wave_sum(sy);
 }
-
-struct MpcSample {
-    double xp, xv, ux, yp, yv, uy, zmx, zmy;
-    int k, flags;
-};
 
 // Mpc3dLip::compute at (cxp, vxp | cyp, vyp, t): u0 = -K (Px x_k - z[k : k + N + 1]), then x_next = A x + B u (refs_chain_a's expressions)
 __device__ __forceinline__ void mpc_step_one(const LmhDevParams &P, const double *zx, const double *zy, const MpcGain &G, int lane,
@@ -104,21 +87,6 @@ __device__ __forceinline__ void mpc_step_one(const LmhDevParams &P, const double
     const bool fin = finite_f64(xp) && finite_f64(xv) && finite_f64(ux) && finite_f64(yp) && finite_f64(yv) && finite_f64(uy) &&
                      finite_f64(S.zmx) && finite_f64(S.zmy);
     S.k = k; S.flags = flags | (fin ? 0 : LMH_FLAG_NONFINITE);
-}
-
-// one sample record (LMH_MPC_STRIDE words, pads zero), word `lane` by lane `lane`
-__device__ __forceinline__ void mpc_store_sample(double *rec, int lane, const MpcSample &S, double cxp, double vxp, double cyp, double vyp, double t)
-{
-    if (lane < LMH_MPC_STRIDE) {
-        double w = 0.0;
-        w = (lane == LMH_MPC_OFF_XREF) ? S.xp : w; w = (lane == LMH_MPC_OFF_XREF + 1) ? S.xv : w; w = (lane == LMH_MPC_OFF_XREF + 2) ? S.ux : w;
-        w = (lane == LMH_MPC_OFF_YREF) ? S.yp : w; w = (lane == LMH_MPC_OFF_YREF + 1) ? S.yv : w; w = (lane == LMH_MPC_OFF_YREF + 2) ? S.uy : w;
-        w = (lane == LMH_MPC_OFF_ZMP) ? S.zmx : w; w = (lane == LMH_MPC_OFF_ZMP + 1) ? S.zmy : w;
-        w = (lane == LMH_MPC_OFF_STATE) ? cxp : w; w = (lane == LMH_MPC_OFF_STATE + 1) ? vxp : w;
-        w = (lane == LMH_MPC_OFF_STATE + 2) ? cyp : w; w = (lane == LMH_MPC_OFF_STATE + 3) ? vyp : w;
-        w = (lane == LMH_MPC_OFF_T) ? t : w; w = (lane == LMH_MPC_OFF_K) ? (double)S.k : w; w = (lane == LMH_MPC_OFF_FLAGS) ? (double)S.flags : w;
-        rec[lane] = w;
-    }
 }
 
 // lmh_mpc_step (ROLL = false: one sample into out[inst], the state is left alone) and lmh_mpc_rollout (ROLL = true: n_ticks samples into
@@ -192,153 +160,6 @@ static_assert(LMH_MPC_BOX_MAX_ROUNDS >= 2 * PV_MAXN, "the round cap must allow e
 
 enum { QP_PLAIN, QP_BOX_PREVIEW, QP_BOX_STEP, QP_BOX_ROLL };
 
-// A = L L' in place on the leading n x n lower triangle, right-looking; every lane sees the same pivot.  false: a pivot was not positive.
-__device__ __forceinline__ bool pv_factor(double *A, const int ld, int n, int lane)
-{
-    for (int j = 0; j < n; j++) {
-        __syncthreads();
-        const double d = A[ld * j + j];
-        if (!(d > 0.0)) return false;
-        const double r = sqrt(d);
-        __syncthreads();
-        for (int i = lane; i < n; i += 64) {
-            if (i == j) A[ld * i + j] = r;
-            if (i > j) A[ld * i + j] = A[ld * i + j] / r;
-        }
-        __syncthreads();
-        for (int i = lane; i < n; i += 64)
-            if (i > j) {
-                const double lij = A[ld * i + j];
-                for (int c = j + 1; c <= i; c++) A[ld * i + c] -= lij * A[ld * c + j];
-            }
-    }
-    return true;
-}
-
-// b <- (L L')^-1 b for one (bx) or two (bx, by) right-hand sides
-template <bool TWO>
-__device__ __forceinline__ void pv_solve(const double *A, const int ld, int n, int lane, double *bx, double *by)
-{
-    for (int j = 0; j < n; j++) {                                  // L w = b
-        __syncthreads();
-        const double ljj = A[ld * j + j];
-        const double wx = bx[j] / ljj, wy = TWO ? by[j] / ljj : 0.0;
-        __syncthreads();
-        for (int i = lane; i < n; i += 64) {
-            if (i == j) { bx[i] = wx; if (TWO) by[i] = wy; }
-            if (i > j) { const double lij = A[ld * i + j]; bx[i] -= lij * wx; if (TWO) by[i] -= lij * wy; }
-        }
-    }
-    for (int j = n - 1; j >= 0; j--) {                             // L' v = w
-        __syncthreads();
-        const double ljj = A[ld * j + j];
-        const double vx = bx[j] / ljj, vy = TWO ? by[j] / ljj : 0.0;
-        __syncthreads();
-        for (int i = lane; i < n; i += 64) {
-            if (i == j) { bx[i] = vx; if (TWO) by[i] = vy; }
-            if (i < j) { const double lji = A[ld * j + i]; bx[i] -= lji * vx; if (TWO) by[i] -= lji * vy; }
-        }
-    }
-    __syncthreads();
-}
-
-// G = Pu H^-1 Pu' = Y'Y into the upper triangle of the packed tile, Y = L^-1 Pu' through the second tile (header comment)
-__device__ __forceinline__ void box_form_g(double *HG, double *T, const double *pt, double D, int n, int lane)
-{
-    __syncthreads();
-    for (int c = lane; c < n; c += 64)                             // Y, column c by lane c (Pu'[i][c] = Pu[c][i], zero below the diagonal)
-        for (int i = 0; i < n; i++) {
-            double s = (i == c) ? D : ((i < c) ? pt[c - i - 1] : 0.0);
-            for (int j = 0; j < i; j++) s = fma(-HG[PV_LDB * i + j], T[PV_LD * j + c], s);
-            T[PV_LD * i + c] = s / HG[PV_LDB * i + i];
-        }
-    __syncthreads();
-    for (int c = lane; c < n; c += 64)                             // G = Y'Y, the upper triangle, column c by lane c
-        for (int r = 0; r <= c; r++) {
-            double s = 0.0;
-            for (int i = 0; i < n; i++) s = fma(T[PV_LD * i + r], T[PV_LD * i + c], s);
-            HG[PV_LDB * r + c + 1] = s;
-        }
-    __syncthreads();
-}
-
-// The working-set rounds of one axis on the factor (header comment; include/lmh.h has the exchange rule).  In: u = U0, z = Z0 = p + Pu U0,
-// g, the window's bounds lo / hi.  Out: u, z, lam, side (-1 lower, +1 upper, 0 inactive) of the last iterate; -> rounds, active, flags.
-struct BoxLds {
-    double *T;                                                     // PV_MAXN x PV_LD: the factor of S
-    double *z0, *v, *rhs;                                          // [PV_MAXN] each
-    int *side, *want, *widx;                                       // [PV_MAXN] each
-};
-
-__device__ __forceinline__ void box_rounds(double *HG, const double *pt, double D, int n, int lane, const double *p0, const double *p1,
-                                           double s0, double s1, const double *g, const double *lo, const double *hi, double *u, double *z,
-                                           double *lam, const BoxLds &W, bool &have_g, int &rounds_out, int &active_out, int &flags)
-{
-    for (int i = lane; i < n; i += 64) { W.side[i] = 0; W.z0[i] = z[i]; lam[i] = 0.0; }
-    int rounds = 0, active = 0, best = n + 1, block = 3;
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
-    for (;;) {
-        __syncthreads();
-        for (int i = lane; i < n; i += 64) {                       // what is wrong with this iterate: exact fp64 compares
-            const int s = W.side[i];
-            int w = s;
-            if (s == 0) w = (z[i] < lo[i]) ? -1 : ((z[i] > hi[i]) ? 1 : 0);
-            else if ((s > 0 && lam[i] < 0.0) || (s < 0 && lam[i] > 0.0)) w = 0;
-            W.want[i] = w;
-        }
-        __syncthreads();
-        int nbad = 0, last = -1;
-        for (int i = 0; i < n; i++) if (W.want[i] != W.side[i]) { nbad++; last = i; }
-        if (nbad == 0) break;
-        if (rounds >= LMH_MPC_BOX_MAX_ROUNDS) { flags |= LMH_FLAG_QP_MAXITER; break; }
-        rounds++;
-        if (!have_g) { box_form_g(HG, W.T, pt, D, n, lane); have_g = true; }
-        bool single = false;
-        if (nbad < best) { best = nbad; block = 3; }
-        else if (block > 0) block--;
-        else single = true;
-        __syncthreads();
-        for (int i = lane; i < n; i += 64) if (!single || i == last) W.side[i] = W.want[i];
-        __syncthreads();
-        int m = 0;
-        for (int i = 0; i < n; i++) if (W.side[i] != 0) { if (lane == 0) W.widx[m] = i; m++; }
-        active = m;
-        __syncthreads();
-        for (int a = lane; a < m; a += 64) {                       // S = G[W][W], lower triangle (W ascends); rhs = Z0_W - b_W
-            const int ia = W.widx[a];
-            for (int b = 0; b <= a; b++) W.T[PV_LD * a + b] = HG[PV_LDB * W.widx[b] + ia + 1];
-            W.rhs[a] = W.z0[ia] - ((W.side[ia] > 0) ? hi[ia] : lo[ia]);
-        }
-        for (int i = lane; i < n; i += 64) lam[i] = 0.0;
-        const bool spd = pv_factor(W.T, PV_LD, m, lane);
-        if (!spd) {
-            flags |= LMH_FLAG_NOT_SPD;
-            __syncthreads();
-            for (int i = lane; i < n; i += 64) { u[i] = nan; z[i] = nan; lam[i] = nan; }
-            break;
-        }
-        pv_solve<false>(W.T, PV_LD, m, lane, W.rhs, nullptr);
-        for (int a = lane; a < m; a += 64) lam[W.widx[a]] = W.rhs[a];
-        __syncthreads();
-        for (int j = lane; j < n; j += 64) {                       // v = g + Pu' lambda
-            double s = D * lam[j];
-            for (int l = j + 1; l < n; l++) s = fma(pt[l - j - 1], lam[l], s);
-            W.v[j] = g[j] + s;
-        }
-        pv_solve<false>(HG, PV_LDB, n, lane, W.v, nullptr);
-        for (int i = lane; i < n; i += 64) u[i] = -W.v[i];
-        __syncthreads();
-        for (int l = lane; l < n; l += 64) {                       // Z = p + Pu U; an active sample sits on its bound
-            double s = fma(D, u[l], fma(p0[l], s0, p1[l] * s1));
-            for (int j = 0; j < l; j++) s = fma(pt[l - j - 1], u[j], s);
-            const int sd = W.side[l];
-            z[l] = (sd == 0) ? s : ((sd > 0) ? hi[l] : lo[l]);
-        }
-    }
-    __syncthreads();
-    rounds_out = rounds; active_out = active;
-}
-
 // MODE QP_PLAIN: lmh_mpc_preview.  QP_BOX_PREVIEW: its record with the bounds enforced, the round and active counts in the header and the
 // multipliers behind it.  QP_BOX_STEP: one sample per robot from the same solution.  QP_BOX_ROLL: n_ticks of them in closed loop on one
 // factorisation, the state written back.  box: the robot's bounds at box + box_stride * inst, four rows of n_samples.
@@ -369,72 +190,30 @@ __global__ void __launch_bounds__(64) lmh_mpc_qp_kernel(LmhDevParams P, double a
     const double nan = __longlong_as_double(0x7ff8000000000000ll);
     const size_t B = (size_t)P.n_instances;
 
-    {                                                              // pt[m], m = lane; pt[64] is never read (m <= N - 1)
-        double s = 0.0, mine = 0.0;
-        for (int m = 0; m < 64; m++) { mine = (m == lane) ? s : mine; s = s + dt; }
-        pt[lane] = mul_then_add(mine, dt, P.b0);
-        if (lane == 0) pt[PV_MAXN - 1] = 0.0;
-    }
+    pt[lane] = pv_pt_entry(dt, P.b0, lane);                        // pt[m], m = lane; pt[64] is never read (m <= N - 1)
+    if (lane == 0) pt[PV_MAXN - 1] = 0.0;
     __syncthreads();
-    for (int i = lane; i < n; i += 64)                             // the lower triangle of H, row i
-        for (int j = 0; j <= i; j++) {
-            double s = ((i == j) ? D : pt[i - j - 1]) * D;         // l = i: Pu[i][j] Pu[i][i]
-            for (int l = i + 1; l < n; l++) s += pt[l - j - 1] * pt[l - i - 1];
-            H[LDH * i + j] = ((i == j) ? alpha : 0.0) + beta * s;
-        }
-    const bool spd = pv_factor(H, LDH, n, lane);
+    pv_form_h(H, LDH, pt, D, alpha, beta, n, lane);
+    const bool spd = pv_factor<false>(H, LDH, n, lane);
     __syncthreads();
     bool have_g = false;                                           // G is formed by the first round of the launch, if there is one
+    const BoxArrays A = {H, T, LDH, PV_LD, pt, rx, ry, bx, by, &bw[0][0], PV_MAXN, &gk[0][0], PV_MAXN, &lm[0][0], PV_MAXN, &wk[0][0], PV_MAXN, &iw[0][0], PV_MAXN};
 
 #pragma unroll 1
     for (int tick = 0; tick < (ROLL ? n_ticks : 1); tick++) {
         int flags;
         const int k = mpc_index(P, t, flags);
-        bool empty = false;
-        for (int l = lane; l < n; l += 64) {                       // r = Px x_k - z over the clamped, scaled window
-            const int kk = mpc_clamp(k + l, ns);
-            rx[l] = fma(-xs, zx[kk], fma(px0[l], x, px1[l] * xd));
-            ry[l] = fma(px0[l], y, px1[l] * yd) - zy[kk];
-            if constexpr (BOX) {                                   // the bounds of the same samples, in metres as they are
-                const double *bp = box + box_stride * (size_t)inst + kk;
-#pragma unroll
-                for (int a = 0; a < 4; a++) bw[a][l] = bp[(size_t)a * ns];
-                empty = empty || !(bw[0][l] <= bw[1][l]) || !(bw[2][l] <= bw[3][l]);
-            }
-        }
+        const bool empty = qp_residual<BOX>(n, ns, lane, k, xs, zx, zy, px0, px1, x, xd, y, yd, rx, ry, BOX ? box + box_stride * (size_t)inst : nullptr, A.bw, A.bws);
         __syncthreads();
-        for (int j = lane; j < n; j += 64) {                       // g = beta Pu' r
-            double sx = D * rx[j], sy = D * ry[j];
-            for (int l = j + 1; l < n; l++) { const double p = pt[l - j - 1]; sx += p * rx[l]; sy += p * ry[l]; }
-            bx[j] = beta * sx; by[j] = beta * sy;
-            if constexpr (BOX) { gk[0][j] = bx[j]; gk[1][j] = by[j]; }
-        }
-        if (spd) pv_solve<true>(H, LDH, n, lane, bx, by);
+        qp_gradient<BOX>(n, lane, D, beta, pt, rx, ry, bx, by, A.gk, A.gks);
+        if (spd) pv_solve<true, false>(H, LDH, n, lane, bx, by);
         __syncthreads();
-        for (int i = lane; i < n; i += 64) {                       // U = -H^-1 g
-            bx[i] = spd ? -bx[i] : nan; by[i] = spd ? -by[i] : nan;
-        }
+        qp_negate(n, lane, spd, bx, by);
         __syncthreads();
-        for (int l = lane; l < n; l += 64) {                       // Z = Px x_k + Pu U
-            double sx = fma(D, bx[l], fma(px0[l], x, px1[l] * xd)), sy = fma(D, by[l], fma(px0[l], y, px1[l] * yd));
-            for (int j = 0; j < l; j++) { const double p = pt[l - j - 1]; sx += p * bx[j]; sy += p * by[j]; }
-            rx[l] = sx; ry[l] = sy;
-        }
+        qp_predict(n, lane, D, pt, px0, px1, x, xd, y, yd, bx, by, rx, ry);
         __syncthreads();
         int rounds_x = 0, rounds_y = 0, act_x = 0, act_y = 0;
-        if constexpr (BOX) {
-            if (__any(empty)) {                                    // an empty or NaN box sample: nothing to solve
-                flags |= LMH_FLAG_BOX_EMPTY;
-                for (int i = lane; i < n; i += 64) { bx[i] = nan; by[i] = nan; rx[i] = nan; ry[i] = nan; lm[0][i] = nan; lm[1][i] = nan; }
-            } else if (spd) {
-                const BoxLds W = {T, wk[0], wk[1], wk[2], iw[0], iw[1], iw[2]};
-                box_rounds(H, pt, D, n, lane, px0, px1, x, xd, gk[0], bw[0], bw[1], bx, rx, lm[0], W, have_g, rounds_x, act_x, flags);
-                box_rounds(H, pt, D, n, lane, px0, px1, y, yd, gk[1], bw[2], bw[3], by, ry, lm[1], W, have_g, rounds_y, act_y, flags);
-            } else {
-                for (int i = lane; i < n; i += 64) { lm[0][i] = nan; lm[1][i] = nan; }
-            }
-            __syncthreads();
-        }
+        if constexpr (BOX) box_solve<false>(A, px0, px1, D, n, lane, empty, spd, x, xd, y, yd, have_g, rounds_x, rounds_y, act_x, act_y, flags);
         if (!spd) flags |= LMH_FLAG_NOT_SPD;
         if (RECORD) {
             double *cs = BOX ? T : H;                              // c_0 = x_k, c_{j+1} = A c_j + B u_j: N + 2 states, staged in a tile
@@ -474,13 +253,8 @@ __global__ void __launch_bounds__(64) lmh_mpc_qp_kernel(LmhDevParams P, double a
             }
         } else {                                                   // the sample of lmh_mpc_step from U[0] and Z[0] (mpc_step_one's expressions)
             MpcSample S;
-            const double ux = bx[0], uy = by[0];
-            S.ux = ux; S.uy = uy; S.zmx = rx[0]; S.zmy = ry[0];
-            S.xp = fma(P.b0, ux, fma(P.a00, x, P.a01 * xd)); S.xv = fma(P.b1, ux, fma(P.a10, x, P.a11 * xd));
-            S.yp = fma(P.b0, uy, fma(P.a00, y, P.a01 * yd)); S.yv = fma(P.b1, uy, fma(P.a10, y, P.a11 * yd));
-            const bool fin = finite_f64(S.xp) && finite_f64(S.xv) && finite_f64(ux) && finite_f64(S.yp) && finite_f64(S.yv) && finite_f64(uy) &&
-                             finite_f64(S.zmx) && finite_f64(S.zmy);
-            S.k = k; S.flags = flags | (fin ? 0 : LMH_FLAG_NONFINITE);
+            const LipAB M = {P.a00, P.a01, P.a10, P.a11, P.b0, P.b1};
+            qp_sample(M, bx, by, rx, ry, x, xd, y, yd, k, flags, S);
             double *rec = ROLL ? (out ? out + (size_t)LMH_MPC_STRIDE * ((size_t)tick * B + inst) : nullptr) : out + (size_t)LMH_MPC_STRIDE * inst;
             if (rec) {
                 mpc_store_sample(rec, lane, S, x, xd, y, yd, t);
