@@ -716,6 +716,78 @@ int lmh_rollout_zoh_ex(lmh_handle *h, double *d_state, double *d_out, int32_t *d
 int lmh_rollout_zoh_box(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts,
                         const double *d_box, int n_samples, int n_sets, double *d_mpc, int n_ticks, int n_substeps, void *stream);
 
+/* ---- Sensing and actuation between the controller and the plant of the zero-order-hold loop (build-defined; the reference QP has no torque
+ * bounds and its loop no sensor or motor model): measurement error on what the controller reads, and a latency, a torque limit and a
+ * first-order lag on what the plant receives, per robot and per joint, inside the one launch -- so a gain sweep or a push-recovery margin can
+ * be taken with them without giving up the pushes inside holds, the trace and the on-chip metrics to a host loop.
+ * ACTUATOR RECORDS (lmh_set_actuators; a table of the handle like the push schedule).  records: HOST [n_sets][LMH_ACT_STRIDE], n_sets = 1 (one
+ * record shared by all robots) or n_instances; records = NULL or n_sets = 0 clears the table.  One record: TAU_MAX[24], the torque limit of
+ * every joint, >= 0, +INFINITY = none | ALPHA[24], the lag coefficient of every joint, in (0, 1], 1 = no lag | DELAY, the latency in control
+ * ticks, a whole number 0 .. LMH_ACT_MAX_DELAY | pad, ignored.  A NaN or negative limit, an alpha outside (0, 1] and a delay that is not a
+ * whole number in range are refused (LMH_ERR_BAD_ARG; the text names the first offending robot, "robot 7: ..."); a refused or failed call
+ * leaves the previous table in place (see lmh_set_refs: check first, build aside, replace in one step).  The table is a buffer of its own: it
+ * travels in lmh_rollout_zoh_io's kernel arguments only, the parameter block and the per-robot blocks of lmh_set_params are not rebuilt,
+ * and no other call reads it -- lmh_eval, lmh_rollout*, lmh_plant_* and lmh_rollout_zoh, _ref, _ex and _box are bit for bit what they are
+ * without it.  lmh_get_actuators: robot `inst`'s record (the shared one on a shared table; the defaults inf | 1 | 0 on a handle without one).
+ * ACTUATOR MEMORY (d_act_mem, DEVICE [B][LMH_ACT_MEM_STRIDE], the caller's, in/out): PREV[24], the torques the plant received on the last
+ * control tick | QUEUE[LMH_ACT_MAX_DELAY][24], the commands on their way, oldest first; a robot of delay d uses slots 0 .. d-1 and touches no
+ * other.  The caller fills it before the first launch (zeros, or a holding torque) and hands it on from launch to launch.
+ * DEFINITION.  For every robot i the call leaves, bit for bit, what lmh_rollout_zoh_ex's host loop (above) leaves with its evaluation line
+ * replaced and the torques of its tau30 taken from y (B = n_instances; control tick j of this launch):
+ *         [the push due at the tick's start, as in lmh_rollout_zoh_ex]
+ *         scratch = the state record;  if d_meas:  scratch[0:60] = state[0:60] + d_meas[j][i][0:60]        one fp64 add per word
+ *         lmh_eval / lmh_eval_ref on scratch -> out, status           (the warm start through status[3] as ever)
+ *         state[60:90] = scratch[60:90]                               v_prev is the controller's memory: the v it MEASURED
+ *         cmd = out.tau
+ *         if actuators (d = the robot's delay; for every joint):
+ *             u = cmd                                                            if d == 0
+ *             u = QUEUE[0];  QUEUE[0 .. d-2] = QUEUE[1 .. d-1];  QUEUE[d-1] = cmd     otherwise
+ *             c = u > lim ? lim : (u < -lim ? -lim : u)               a NaN passes through; c != u on any joint raises LMH_FLAG_TAU_LIMIT
+ *             y = c                                                   if alpha == 1 (PREV is not read)
+ *             y = (alpha * c) + ((1 - alpha) * PREV)                  otherwise: the difference, both products and the sum each rounded, no
+ *                                                                     fused multiply-add (numpy's expression gives the same bits)
+ *             PREV = y
+ *         else y = cmd
+ *         d_applied[j][i] = y                                         when d_applied != NULL
+ *         tau30 = [ wrench (6) | y (24) ];  the hold pieces, the pushes inside them, the sample and the fold: lmh_rollout_zoh_ex's, on the TRUE state
+ * Consequences.  (a + b) equals (a) followed by (b) bit for bit with d_meas and d_applied advanced by a records per robot and d_act_mem handed
+ * on, also when the delay is longer than a.  A trace sample holds the TRUE state after the hold; its v_prev words hold the measured v and its
+ * out words are the evaluation's, so CoM and comVel there are those of the measured state.  d_log and the metrics' torque words stay the
+ * COMMANDED torques (the fold of the trace is unchanged); XMIN, XMAX and FIRST_FALL are the true state's.  LMH_FLAG_TAU_LIMIT is informational:
+ * it is outside the mask (& 15) of the metrics' FIRST_FLAG.  A NaN in a robot's d_meas words flags that robot as lmh_eval flags a NaN state
+ * and disturbs no other.  actuators = 1 on a handle without records is legal and applies the defaults.
+ * io == NULL, or a record of NULLs and zeros, is lmh_rollout_zoh_ex(h, ..., opts, ...) exactly: the same kernel is launched.  The
+ * box-constrained loop (lmh_rollout_zoh_box) is NOT offered with these options.
+ * Refusals, each LMH_ERR_BAD_ARG before anything is enqueued and with a message of its own: actuators or reserved outside its values;
+ * actuators = 1 without d_act_mem; every refusal of lmh_rollout_zoh_ex.  The launch rules are lmh_rollout_zoh_ex's: LMH_PRECISION_FP64 handles
+ * only, no launch slot, nothing written into the handle, capturable into a hipGraph as the first call on a fresh handle.  During the launch
+ * words [0, 60) of a robot's d_state record hold its true state (the kernel parks it there across the evaluation).
+ * Cost (one MI355X, 4096 standing robots x 200 control ticks): with nothing set the call launches lmh_rollout_zoh_ex's
+ * kernel (62.3 against 62.1 ms, the parent commit's own timings: 61.4 .. 62.6 ms).  At n_substeps = 1 the measurement alone costs 1.5 %, the
+ * actuator (delays 0 .. 3, a lag and a limit on every joint) 2.0 %, the applied torques 1.2 %, all three 2.4 % (63.6 ms: one millisecond above
+ * the parent's slowest launch), and on top of every option of lmh_rollout_zoh_ex with an every-tick trace 3.3 % of that launch; at
+ * n_substeps = 10 every row lies inside the parent's own range of timings (471 .. 487 ms).  Other batch sizes and anything multi-GPU were
+ * not measured. */
+#define LMH_ACT_STRIDE 56         /* one actuator record (doubles) */
+#define LMH_ACT_OFF_TAU_MAX 0      /* [24] torque limit per joint, >= 0, +INFINITY = none */
+#define LMH_ACT_OFF_ALPHA 24       /* [24] first-order lag coefficient per joint, in (0, 1]; 1 = no lag */
+#define LMH_ACT_OFF_DELAY 48       /* latency in CONTROL ticks, a whole number 0 .. LMH_ACT_MAX_DELAY, as a double; [49, 56) pad, ignored */
+#define LMH_ACT_MAX_DELAY 7
+#define LMH_ACT_MEM_STRIDE 192     /* one robot's actuator memory (doubles): PREV[24] | QUEUE[7][24], oldest command first */
+#define LMH_FLAG_TAU_LIMIT 128     /* informational: on some tick of the launch a joint's torque was cut to its limit */
+int lmh_set_actuators(lmh_handle *h, const double *records, int n_sets);
+int lmh_actuators_per_instance(const lmh_handle *h);      /* 0: none or one shared record, 1: one record per robot */
+int lmh_get_actuators(lmh_handle *h, int inst, double *record);
+typedef struct lmh_zoh_io {
+    const double *d_meas;         /* DEVICE [n_ticks][B][60] or NULL: what is ADDED to q | v as control tick j's evaluation sees them */
+    double *d_act_mem;            /* DEVICE [B][LMH_ACT_MEM_STRIDE], in/out; required when actuators = 1 */
+    double *d_applied;            /* DEVICE [n_ticks][B][24] or NULL: the joint torques the plant received on every control tick */
+    int32_t actuators;            /* 0 | 1: apply the handle's lmh_set_actuators records */
+    int32_t reserved;             /* must be 0 */
+} lmh_zoh_io;
+int lmh_rollout_zoh_io(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts,
+                       const lmh_zoh_io *io, int n_ticks, int n_substeps, void *stream);
+
 /* ---- LIPM preview MPC for a batch of reduced states (one kernel family of its own, one wave per robot, fp64): the stage of the controller
  * that lmh_eval runs between the momentum and the PD law, as calls of its own.
  * replaces: Mpc3dLip::compute (src/mpcLinearPendulum.cpp:78-109) for every robot of the handle, at that robot's own clock.

@@ -20,6 +20,10 @@ LINK_STRIDE = 13
 SEG_STRIDE = 52
 PUSH_STRIDE = 32              # one timed velocity push: tick (as a double) | dv[30] | pad (lmh_set_pushes)
 MAX_PUSHES = 16               # push records per robot
+ACT_STRIDE = 56               # one actuator record: tau_max[24] | alpha[24] | delay | pad (lmh_set_actuators)
+ACT_OFF_TAU_MAX, ACT_OFF_ALPHA, ACT_OFF_DELAY = 0, 24, 48
+ACT_MAX_DELAY = 7             # control ticks
+ACT_MEM_STRIDE = 192          # one robot's actuator memory: PREV[24] | QUEUE[7][24], oldest command first (lmh_rollout_zoh_io)
 IK_TARGET_STRIDE = 16         # one inverse-kinematics target record: rf6 | lf6 | com(3) | pad (lmh_ik_batch)
 PARAM_STRIDE = 20             # one per-robot parameter record (lmh_set_params)
 # name -> offset inside a parameter record: the LMH_PARAM_OFF_* defines of include/lmh.h (lmh_config's own order; [19] is a pad)
@@ -72,6 +76,7 @@ FLAG_ZMP_RANGE = 4
 FLAG_NOT_SPD = 8
 FLAG_QP_FP64_ROUTE = 16
 FLAG_BOX_EMPTY = 64           # lmh_mpc_box_*: a sample of the window has lo > hi or a NaN bound
+FLAG_TAU_LIMIT = 128          # lmh_rollout_zoh_io, informational: a joint's torque was cut to its limit on some tick of the launch
 FLAG_UNFINISHED = 32          # lmh_rollout: the robot did not get all its ticks (a wait of the kernel's work queue ran out)
 ERR_UNFINISHED = -5
 
@@ -105,6 +110,11 @@ class LmhZohOpts(C.Structure):
     """struct lmh_zoh_opts (include/lmh.h): the options of lmh_rollout_zoh_ex; all zero = lmh_rollout_zoh."""
     _fields_ = [(n, C.c_void_p) for n in ("d_base_wrench", "d_ref", "d_log", "d_trace", "d_metrics")] + \
                [(n, C.c_int32) for n in ("trace_every", "wrench_per_tick", "pushes", "reserved")]
+
+
+class LmhZohIo(C.Structure):
+    """struct lmh_zoh_io (include/lmh.h): what lmh_rollout_zoh_io puts between controller and plant; all zero = lmh_rollout_zoh_ex."""
+    _fields_ = [(n, C.c_void_p) for n in ("d_meas", "d_act_mem", "d_applied")] + [("actuators", C.c_int32), ("reserved", C.c_int32)]
 
 
 _vp, _ip, _dp, _str, _u64 = C.c_void_p, C.c_int, C.c_double, C.c_char_p, C.c_uint64
@@ -142,6 +152,9 @@ PROTOTYPES = {
     "lmh_num_pushes": (_ip, [_vp]),
     "lmh_pushes_per_instance": (_ip, [_vp]),
     "lmh_get_pushes": (_ip, [_vp, _ip, _vp]),
+    "lmh_set_actuators": (_ip, [_vp, _vp, _ip]),
+    "lmh_actuators_per_instance": (_ip, [_vp]),
+    "lmh_get_actuators": (_ip, [_vp, _ip, _vp]),
     "lmh_set_params": (_ip, [_vp, _vp, _ip]),
     "lmh_params_per_instance": (_ip, [_vp]),
     "lmh_get_params": (_ip, [_vp, _ip, _vp]),
@@ -166,6 +179,7 @@ PROTOTYPES = {
     "lmh_rollout_zoh_ref": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _vp]),
     "lmh_rollout_zoh_ex": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), _ip, _ip, _vp]),
     "lmh_rollout_zoh_box": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), _vp, _ip, _ip, _vp, _ip, _ip, _vp]),
+    "lmh_rollout_zoh_io": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), C.POINTER(LmhZohIo), _ip, _ip, _vp]),
     "lmh_mpc_step": (_ip, [_vp, _vp, _vp, _vp]),
     "lmh_mpc_rollout": (_ip, [_vp, _vp, _ip, _vp, _vp]),
     "lmh_mpc_preview": (_ip, [_vp, _vp, _vp, _vp]),

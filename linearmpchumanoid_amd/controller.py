@@ -257,6 +257,37 @@ class BatchedController:
         check(capi.lib().lmh_get_pushes(self._h, int(i), _np_ptr(rec) if n else None))
         return dict(ticks=rec[:, 0].astype(np.int64), dv=rec[:, 1:31].copy())
 
+    # -- per-robot actuator records of rollout_zoh_io (include/lmh.h, lmh_set_actuators)
+    def set_actuators(self, tau_max=None, alpha=None, delay=None):
+        """lmh_set_actuators: what rollout_zoh_io(actuators=True) puts between the controller's torques and the plant.  tau_max (the torque
+        limit, >= 0; None or inf: none) and alpha (the first-order lag coefficient in (0, 1]; None or 1: no lag) are scalars, [24] or
+        [B,24]; delay (the latency in control ticks, a whole number 0 .. 7; None: 0) is a scalar or [B].  trajectories.actuator_records
+        forms the records (and refuses what the library refuses, in the same words).  With no argument the table is cleared."""
+        if tau_max is None and alpha is None and delay is None:
+            check(capi.lib().lmh_set_actuators(self._h, None, 0))
+            return
+        rec = np.ascontiguousarray(trajectories.actuator_records(self.B, tau_max, alpha, delay))
+        check(capi.lib().lmh_set_actuators(self._h, _np_ptr(rec), self.B))
+
+    @property
+    def actuators_per_instance(self):
+        """True while every robot has an actuator record of its own."""
+        return bool(capi.lib().lmh_actuators_per_instance(self._h))
+
+    def get_actuators(self, i):
+        """Robot i's actuator record: dict(tau_max [24], alpha [24], delay int); the defaults (inf, 1, 0) on a handle without records."""
+        rec = np.zeros(capi.ACT_STRIDE)
+        check(capi.lib().lmh_get_actuators(self._h, int(i), _np_ptr(rec)))
+        return dict(tau_max=rec[0:24].copy(), alpha=rec[24:48].copy(), delay=int(rec[capi.ACT_OFF_DELAY]))
+
+    def new_act_mem(self, tau0=None):
+        """The actuator memory of rollout_zoh_io [B,192] on the device: PREV and every queue slot filled with tau0 [B,24] (None: zeros)."""
+        mem = torch.zeros((self.B, capi.ACT_MEM_STRIDE), dtype=torch.float64, device=self.device)
+        if tau0 is not None:
+            t0 = tau0 if isinstance(tau0, torch.Tensor) else torch.as_tensor(np.asarray(tau0, dtype=np.float64))
+            mem[:] = t0.to(self.device, torch.float64).expand(self.B, 24).repeat(1, 1 + capi.ACT_MAX_DELAY)
+        return mem
+
     # -- per-robot gains, QP weights, friction and contact parameters (include/lmh.h, lmh_set_params)
     def set_params(self, **fields):
         """lmh_set_params: one set of PD gains, QP weights, eps_coeff, mu and contact constants per robot, e.g.
@@ -601,8 +632,47 @@ class BatchedController:
         res["mpc"] = tr
         return res
 
-    def _rollout_zoh_opts(self, state, n_ticks, n_substeps, base_wrench, ref, pushes, log, trace_every, trace, metrics, out, status, box_call):
-        """The argument handling rollout_zoh_ex and rollout_zoh_box share; box_call: None, or lmh_rollout_zoh_box's (d_box, n_samples, n_sets, d_mpc)."""
+    def rollout_zoh_io(self, state, n_ticks, n_substeps, meas=None, actuators=False, act_mem=None, applied=False, **ex):
+        """lmh_rollout_zoh_io: rollout_zoh_ex (whose keywords it takes as they are) with sensing and actuation between controller and plant.
+        meas [n_ticks,B,60]: what is added to q | v as control tick j's evaluation sees them (the plant goes on from the true state; v_prev
+        keeps the measured v).  actuators=True: the set_actuators records -- latency, torque limit, first-order lag -- stand between the
+        evaluation's torques and the hold, with act_mem (new_act_mem's [B,192], changed in place and handed on from launch to launch;
+        required).  applied=True: the torques the plant received [n_ticks,B,24] are returned under "applied" (a tensor: filled).  log, trace
+        and metrics keep the COMMANDED torques; status[:, 2] & capi.FLAG_TAU_LIMIT: a torque was cut.  With none of the four the call is
+        rollout_zoh_ex's launch.  trajectories.actuator_step states the actuator.  -> rollout_zoh_ex's dict plus applied."""
+        if int(n_ticks) != n_ticks or n_ticks < 0:
+            raise ValueError("n_ticks must be a whole number >= 0")
+        n = int(n_ticks)
+
+        def records(name, t, width):
+            if isinstance(t, np.ndarray) and t.dtype == np.float64:
+                t = torch.from_numpy(np.ascontiguousarray(t)).to(self.device)
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != self.device or tuple(t.shape) != (n, self.B, width) or not t.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous [{n},{self.B},{width}] float64 tensor on {self.device}")
+            return t
+
+        ms = None if meas is None else records("meas", meas, 60)
+        ap = torch.zeros((n, self.B, 24), dtype=torch.float64, device=self.device) if applied is True else (None if applied is False or applied is None else records("applied", applied, 24))
+        if actuators and act_mem is None:
+            raise ValueError("rollout_zoh_io: actuators=True needs act_mem (new_act_mem)")
+        mem = self._batch("act_mem", act_mem, capi.ACT_MEM_STRIDE, optional=True, in_place=True)
+
+        def arg(t):                                                # (an empty tensor has no address to pass; with no tick no record is touched)
+            return _dev_ptr(t if (t is None or t.numel() > 0) else torch.empty((1,), dtype=torch.float64, device=self.device))
+
+        io = capi.LmhZohIo(d_meas=arg(ms), d_act_mem=_dev_ptr(mem), d_applied=arg(ap), actuators=int(bool(actuators)), reserved=0)
+        kw = dict(base_wrench=None, ref=None, pushes=False, log=False, trace_every=0, trace=None, metrics=None, out=None, status=None)
+        if set(ex) - set(kw):
+            raise TypeError(f"rollout_zoh_io: unexpected keyword {sorted(set(ex) - set(kw))[0]!r}")
+        kw.update(ex)
+        res = self._rollout_zoh_opts(state, n_ticks, n_substeps, kw["base_wrench"], kw["ref"], kw["pushes"], kw["log"], kw["trace_every"], kw["trace"],
+                                     kw["metrics"], kw["out"], kw["status"], None, io_call=io)
+        res["applied"] = ap
+        return res
+
+    def _rollout_zoh_opts(self, state, n_ticks, n_substeps, base_wrench, ref, pushes, log, trace_every, trace, metrics, out, status, box_call, io_call=None):
+        """The argument handling rollout_zoh_ex, rollout_zoh_box and rollout_zoh_io share; box_call: None, or lmh_rollout_zoh_box's (d_box, n_samples,
+        n_sets, d_mpc); io_call: None, or lmh_rollout_zoh_io's record."""
         state = self._batch("state", state, capi.STATE_STRIDE, in_place=True)
         for name, n in (("n_ticks", n_ticks), ("n_substeps", n_substeps), ("trace_every", trace_every)):
             if int(n) != n or n < 0:
@@ -639,7 +709,10 @@ class BatchedController:
         metrics = self._batch("metrics", metrics, capi.METRICS_STRIDE, optional=True, in_place=True)
         opts = capi.LmhZohOpts(d_base_wrench=_dev_ptr(bw), d_ref=_dev_ptr(ref), d_log=_dev_ptr(lg), d_trace=_dev_ptr(tr_arg), d_metrics=_dev_ptr(metrics),
                                trace_every=trace_every, wrench_per_tick=int(per_tick), pushes=int(bool(pushes)), reserved=0)
-        if box_call is None:
+        if io_call is not None:
+            check(capi.lib().lmh_rollout_zoh_io(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), C.byref(io_call), n_ticks, n_substeps,
+                                                self._stream()))
+        elif box_call is None:
             check(capi.lib().lmh_rollout_zoh_ex(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), n_ticks, n_substeps, self._stream()))
         else:
             d_box, ns, sets, d_mpc = box_call

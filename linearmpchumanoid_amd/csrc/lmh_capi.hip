@@ -57,6 +57,11 @@ struct lmh_handle {
     RefPlan plan;                     // replaced as a whole, by commit_plan only
     DevBuf<double> d_pushes;          // timed velocity pushes [n_push_sets][n_push][LMH_PUSH_STRIDE] (lmh_set_pushes); empty while n_push = 0
     int n_push = 0, n_push_sets = 1;
+    // Actuator records (lmh_set_actuators): [n_act_sets][LMH_ACT_STRIDE] on the device and on the host (what lmh_get_actuators returns); empty while
+    // n_act_sets = 0.  Read by lmh_rollout_zoh_io alone, through its kernel arguments: no part of the parameter block.
+    DevBuf<double> d_act;
+    std::vector<double> h_act;
+    int n_act_sets = 0;
     // Per-robot parameters (lmh_set_params): the records, one friction table per robot and the table of whole parameter blocks the controller
     // kernels select from.  All empty while the handle runs on its config's one set.  The block table is rebuilt by fill_params, i.e. by
     // every setter that moves a pointer or a stride, and replaces the previous one in one step.
@@ -452,7 +457,7 @@ extern "C" int lmh_create(const lmh_config *cfg, int n_instances, int device, lm
     {                                                               // lmh_rollout_zoh_box's dynamic LDS: asked for here, never inside the (capturable) call
         int32_t answer = -1;
         const LmhZohBox prep = {nullptr, 0, nullptr, 0.0, 0.0, 1, &answer};
-        lmh_launch_rollout_zoh(&h->P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &prep, nullptr);
+        lmh_launch_rollout_zoh(&h->P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &prep, nullptr, nullptr);
         h->zoh_box_prepared = answer;
     }
     (void)hipGetLastError();                                        // an answer other than hipSuccess is that call's to report, not a sticky error of this one
@@ -644,6 +649,51 @@ extern "C" int lmh_get_pushes(lmh_handle *h, int inst, double *records)
     HIPCHK(hipSetDevice(h->device));
     const size_t n = (size_t)LMH_PUSH_STRIDE * h->n_push;
     HIPCHK(hipMemcpy(records, h->d_pushes.get() + ((h->n_push_sets > 1) ? n * (size_t)inst : 0), sizeof(double) * n, hipMemcpyDeviceToHost));
+    return LMH_OK;
+}
+
+// ---------------------------------------------------------------------------- actuator records (lmh_rollout_zoh_io)
+// the rules of one record: nullptr = fine.  trajectories.actuator_records states the same rules with the same words.
+static const char *actuator_record_error(const double *rec)
+{
+    for (int j = 0; j < 24; j++) if (!(rec[LMH_ACT_OFF_TAU_MAX + j] >= 0.0)) return "torque limits must be >= 0 (+inf: none)";
+    for (int j = 0; j < 24; j++) if (!(rec[LMH_ACT_OFF_ALPHA + j] > 0.0) || !(rec[LMH_ACT_OFF_ALPHA + j] <= 1.0)) return "alpha must be in (0, 1]";
+    const double d = rec[LMH_ACT_OFF_DELAY];
+    if (!(d >= 0.0) || !(d <= (double)LMH_ACT_MAX_DELAY) || d != std::floor(d)) return "delay must be a whole number in [0, LMH_ACT_MAX_DELAY (7)]";
+    return nullptr;
+}
+
+extern "C" int lmh_set_actuators(lmh_handle *h, const double *records, int n_sets)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    if (n_sets < 0) return fail(LMH_ERR_BAD_ARG, "n_sets must be >= 0");
+    if (!records) n_sets = 0;
+    if (n_sets != 0 && n_sets != 1 && n_sets != h->B) return fail(LMH_ERR_BAD_ARG, "n_sets must be 1 or n_instances");
+    for (int i = 0; i < n_sets; i++)
+        if (const char *msg = actuator_record_error(records + (size_t)LMH_ACT_STRIDE * i)) return fail(LMH_ERR_BAD_ARG, robot_msg(i, msg));
+    HIPCHK(hipSetDevice(h->device));
+    DevBuf<double> d;
+    std::vector<double> host;
+    if (n_sets > 0) {
+        host.assign(records, records + (size_t)LMH_ACT_STRIDE * n_sets);
+        HIPCHK(d.upload(records, (size_t)LMH_ACT_STRIDE * n_sets));
+    }
+    h->d_act = std::move(d); h->h_act.swap(host); h->n_act_sets = n_sets;     // nothing here fails: the parameter block does not hold the table
+    return LMH_OK;
+}
+
+extern "C" int lmh_actuators_per_instance(const lmh_handle *h) { return (h && h->n_act_sets > 1) ? 1 : 0; }
+
+extern "C" int lmh_get_actuators(lmh_handle *h, int inst, double *record)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    if (inst < 0 || inst >= h->B) return fail(LMH_ERR_BAD_ARG, "instance out of range");
+    if (!record) return fail(LMH_ERR_BAD_ARG, "bad argument");
+    if (h->n_act_sets == 0) {
+        for (int j = 0; j < LMH_ACT_STRIDE; j++) record[j] = (j < 24) ? INFINITY : (j < 48) ? 1.0 : 0.0;
+        return LMH_OK;
+    }
+    std::memcpy(record, h->h_act.data() + (size_t)LMH_ACT_STRIDE * ((h->n_act_sets > 1) ? inst : 0), sizeof(double) * LMH_ACT_STRIDE);
     return LMH_OK;
 }
 
@@ -1037,9 +1087,11 @@ extern "C" int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_ta
 // all-zero record launches the kernels of the two calls above, anything else lmh_rollout_zoh_ex_kernel.
 // bx (lmh_rollout_zoh_box; nullptr in the three calls above it): the bounds of lmh_mpc_box_step and where the samples go.  Its refusals stand behind the
 // call's own pointers; the launch is lmh_rollout_zoh_box_kernel's whatever the options.
+// io (lmh_rollout_zoh_io; nullptr in the four calls above it, never with bx): its own refusals stand behind those of the options record; a record that asks
+// for nothing launches what the call without it launches, anything else lmh_rollout_zoh_io_kernel.
 struct ZohBoxCall { const double *d_box; int n_samples, n_sets; double *d_mpc; };
 static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log, const double *d_ref, bool with_ref,
-                    int n_ticks, int n_substeps, void *stream, const lmh_zoh_opts *opts = nullptr, const ZohBoxCall *bx = nullptr)
+                    int n_ticks, int n_substeps, void *stream, const lmh_zoh_opts *opts = nullptr, const ZohBoxCall *bx = nullptr, const lmh_zoh_io *io = nullptr)
 {
     int rc = ready(h); if (rc) return rc;
     if (!d_state || !d_out || !d_status) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: null device pointer");
@@ -1066,6 +1118,11 @@ static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_st
         ex.trace = opts->d_trace; ex.metrics = opts->d_metrics; ex.trace_every = opts->trace_every;
         ex.wrench_per_tick = opts->wrench_per_tick; ex.pushes = opts->pushes;
     }
+    if (io) {
+        if ((io->actuators | 1) != 1) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_io: actuators must be 0 or 1");
+        if (io->reserved != 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_io: reserved must be 0");
+        if (io->actuators && !io->d_act_mem) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_io: actuators = 1 needs d_act_mem");
+    }
     if (h->cfg.precision != LMH_PRECISION_FP64) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: LMH_PRECISION_FP64 handles only (this handle's precision has no instantiation of the kernel)");
     rc = plant_constants_ok(h); if (rc) return rc;
     if (n_ticks == 0) return LMH_OK;                                 // nothing to enqueue
@@ -1073,10 +1130,14 @@ static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_st
         if (h->zoh_box_prepared != 0 && h->N > 33)                   // N >= 34: above 64 KB of LDS in all, only with the limit lmh_create asked for
             return fail(LMH_ERR_HIP, "lmh_rollout_zoh_box: the runtime refused the kernel's dynamic shared memory limit when the handle was created");
         const LmhZohBox zb = {bx->d_box, box_stride(h, bx->n_sets), bx->d_mpc, h->cfg.alpha, h->cfg.beta, 0, nullptr};
-        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, nullptr, n_ticks, n_substeps, &ex, &zb, (hipStream_t)stream); });
+        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, nullptr, n_ticks, n_substeps, &ex, &zb, nullptr, (hipStream_t)stream); });
+    }
+    if (io && (io->d_meas || io->d_applied || io->actuators)) {
+        const LmhZohIo zi = {io->d_meas, io->actuators ? io->d_act_mem : nullptr, io->d_applied, h->d_act.get(), (h->n_act_sets > 1) ? (size_t)LMH_ACT_STRIDE : 0, io->actuators, 0};
+        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, &ex, nullptr, &zi, (hipStream_t)stream); });
     }
     const bool plain = !ex.trace && !ex.metrics && !ex.wrench_per_tick && !ex.pushes;     // no new option: the kernels of before
-    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, plain ? nullptr : &ex, nullptr, (hipStream_t)stream); });
+    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, plain ? nullptr : &ex, nullptr, nullptr, (hipStream_t)stream); });
 }
 extern "C" int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
                                int n_ticks, int n_substeps, void *stream)
@@ -1094,6 +1155,15 @@ extern "C" int lmh_rollout_zoh_ex(lmh_handle *h, double *d_state, double *d_out,
     static const lmh_zoh_opts none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
     const lmh_zoh_opts *o = opts ? opts : &none;
     return zoh_body(h, d_state, d_out, d_status, o->d_base_wrench, o->d_log, o->d_ref, false, n_ticks, n_substeps, stream, o);
+}
+
+// lmh_rollout_zoh_ex with a measurement in front of the evaluation and an actuator behind it (include/lmh.h)
+extern "C" int lmh_rollout_zoh_io(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts, const lmh_zoh_io *io, int n_ticks, int n_substeps,
+                                  void *stream)
+{
+    static const lmh_zoh_opts none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
+    const lmh_zoh_opts *o = opts ? opts : &none;
+    return zoh_body(h, d_state, d_out, d_status, o->d_base_wrench, o->d_log, o->d_ref, false, n_ticks, n_substeps, stream, o, nullptr, io);
 }
 
 // lmh_rollout_zoh_ex with lmh_mpc_box_step closing the loop inside every evaluation (include/lmh.h)

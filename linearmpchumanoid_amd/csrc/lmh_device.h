@@ -82,6 +82,19 @@ struct LmhZohBox {
     int32_t *answer;
 };
 
+// lmh_rollout_zoh_io (include/lmh.h, lmh_zoh_io): what the launch takes beyond lmh_rollout_zoh_ex's -- what the controller measures and what the
+// plant receives.  act: the handle's lmh_set_actuators table, the robot's record at act + act_stride * robot (act_stride 0: one shared record);
+// nullptr with actuators = 1: the defaults (no limit, no lag, no delay).
+struct LmhZohIo {
+    const double *meas;         // [n_ticks][n_instances][60], or nullptr
+    double *act_mem;            // [n_instances][LMH_ACT_MEM_STRIDE]; read and written with actuators = 1 only
+    double *applied;            // [n_ticks][n_instances][24], or nullptr
+    const double *act;
+    size_t act_stride;
+    int32_t actuators;
+    int32_t pad;
+};
+
 // walking-plan generator (lmh_gen_walk): arguments of the device kernel
 #define LMH_GEN_MAX_STEPS 1022
 struct LmhWalkSpec {

@@ -4973,14 +4973,101 @@ __device__ __forceinline__ void zoh_trace_state(double *tr, int lane, double x, 
     else if (lane < 38) tr[LMH_STATE_STRIDE + 78 + lane - 36] = 0.0;
     else if (lane < 42) tr[LMH_STATE_STRIDE + LMH_OUT_STRIDE + lane - 38] = (lane == 38) ? (double)k : (lane == 39) ? (double)itmax : (lane == 40) ? (double)flags : (double)(int32_t)(~F);
 }
+// ---- lmh_rollout_zoh_io (include/lmh.h): the same body with a measurement added to what the evaluation reads and an actuator between the
+// evaluation's torques and the hold (the IO flag of lmh_rollout_zoh_ex_body; two kernels of their own, the three above keep their code).
+//   true state  the evaluation reads q | v from L[P_Q ..] and writes none of it, so that is where x + meas goes, at the places the loop
+//               writes x: behind eval_begin for the first tick (under one more join, the one the launch-start push uses) and in the
+//               write-back behind the hold for every later one.  The true x cannot stay in registers across controller_eval (no VGPRs to
+//               spare) and there is no LDS left at four robots per CU, so it is parked in words [0, 60) of the robot's own d_state record
+//               and loaded back behind the evaluation by the lane that stored it: no fence.  v_prev = L[P_V] behind the evaluation is
+//               then the MEASURED v by itself.  The last tick's write-back adds nothing: the final store finds the true state.
+//   actuator    lane 6 + i of wave 0 holds joint i's torque for the hold (tau30[6 + i]) and owns that joint's PREV word and queue column in
+//               d_act_mem, which stays in global memory: the literal shift of a delay d is d loads and stores per lane and control tick
+//               beside an evaluation of some 4.6 k instructions.  The joint's limit and alpha and the robot's delay are loaded once per launch
+//               by the lanes that use them (ZohIoJoint: four VGPRs and a scalar across controller_eval -- 244 VGPRs against the 235 / 236 of
+//               lmh_rollout_zoh_ex_kernel, six more scalar spill slots, no scratch).  Ordinary vector stores.
+struct ZohIoArgs { ZohExArgs a; LmhZohIo io; };
+static_assert(sizeof(ZohExArgs) % 8 == 0 && alignof(ZohIoArgs) == 8, "ZohIoArgs continues ZohExArgs in the kernel-argument segment");
+typedef const __attribute__((address_space(4))) ZohIoArgs CZohIoArgs;
+__device__ __forceinline__ CZohIoArgs &zoh_io_args()
+{
+    CZohIoArgs *p_ = (CZohIoArgs *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(LmhDevParams));
+    asm volatile("" : "+s"(p_));
+    return *p_;
+}
+// wave 0, x = the true q | v on lanes 0..59: park it in the state record and give the evaluation of control tick `rec` what it measures
+// (rec == n_ticks: there is no such evaluation, the image gets x itself)
+__device__ __forceinline__ void zoh_io_publish(double *L, double *st, int lane, double x, int rec, int inst)
+{
+    if (lane < 60) {
+        st[lane] = x;
+        double m = x;
+        if (const double *meas = zoh_io_args().io.meas) {
+            if (rec < zoh_io_args().a.n_ticks) m = x + meas[((size_t)rec * LMH_KERNARG_PARAMS().n_instances + inst) * 60 + lane];
+        }
+        L[P_Q + lane] = m;
+    }
+}
+// the robot's actuator record as the lane that owns the joint holds it for the launch (the defaults without a table); d is wave-uniform
+struct ZohIoJoint { double lim, alpha; int d; };
+__device__ __forceinline__ ZohIoJoint zoh_io_joint(int lane, int inst)
+{
+    ZohIoJoint J = {__builtin_inf(), 1.0, 0};
+    if (zoh_io_args().io.actuators) {
+        if (const double *act = zoh_io_args().io.act) {
+            const int j = (lane >= 6 && lane < 30) ? lane - 6 : 0;
+            const double *rec = act + zoh_io_args().io.act_stride * (size_t)inst;
+            J.lim = rec[LMH_ACT_OFF_TAU_MAX + j]; J.alpha = rec[LMH_ACT_OFF_ALPHA + j];
+            const int d = __builtin_amdgcn_readfirstlane((int)rec[LMH_ACT_OFF_DELAY]);
+            J.d = (d < 0) ? 0 : (d > LMH_ACT_MAX_DELAY) ? LMH_ACT_MAX_DELAY : d;      // (lmh_set_actuators refuses anything else: no index leaves the robot's memory)
+        }
+    }
+    return J;
+}
+// wave 0, tau = tau30 of this hold as the evaluation commands it (lanes 6..29 the joints): what the plant receives instead
+__device__ __forceinline__ double zoh_io_actuate(double tau, const ZohIoJoint &J, int lane, int inst, int tick, int &flags)
+{
+    const bool jl = lane >= 6 && lane < 30;
+    const int j = jl ? lane - 6 : 0;
+    double y = tau;
+    if (zoh_io_args().io.actuators) {
+        const double lim = J.lim, alpha = J.alpha;
+        const int d = J.d;
+        double *mem = zoh_io_args().io.act_mem + (size_t)LMH_ACT_MEM_STRIDE * inst + j;
+        double u = tau;
+        if (d > 0 && jl) {                                         // the oldest command leaves, the others move up, this tick's joins behind them
+            double *qc = mem + 24;
+            u = qc[0];
+#pragma unroll 1
+            for (int s = 1; s < d; s++) qc[24 * (s - 1)] = qc[24 * s];
+            qc[24 * (d - 1)] = tau;
+        }
+        const double c = (u > lim) ? lim : (u < -lim) ? -lim : u;  // a NaN passes through
+        if (__ballot(jl && c != u) != 0ull) flags |= LMH_FLAG_TAU_LIMIT;
+        y = c;
+        if (jl) {
+            if (alpha != 1.0) {
+                // (alpha * c) + ((1 - alpha) * PREV), every operation rounded: the products go through opaque registers (see metrics_wave1)
+                double pa = __dmul_rn(alpha, c), pb = __dmul_rn(__dsub_rn(1.0, alpha), mem[0]);
+                asm volatile("" : "+v"(pa), "+v"(pb));
+                y = __dadd_rn(pa, pb);
+            }
+            mem[0] = y;
+        }
+    }
+    if (double *ap = zoh_io_args().io.applied) { if (jl) ap[((size_t)tick * LMH_KERNARG_PARAMS().n_instances + inst) * 24 + j] = y; }
+    return jl ? y : tau;
+}
 // MODE: where the momentum task's CoM reference comes from.  ZM_BOX (lmh_rollout_zoh_box_kernel): every control tick runs lmh_mpc_box_step at the
 // measured CoM state inside the evaluation's chain A (refs_chain_a); the preview Hessian is factored once, behind eval_begin, by the helper wave
 // alone (wave-scope fences: both waves pass the same joins as in the other modes) while wave 0 goes on to the pushes and the kinematics.
 enum { ZM_BUILTIN, ZM_REF, ZM_BOX };
-template <int MODE>
+// IO (lmh_rollout_zoh_io_kernel; never with ZM_BOX): the measurement and the actuator of lmh_rollout_zoh_io, above
+template <int MODE, bool IO = false>
 __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
 {
     constexpr bool REF = MODE != ZM_BUILTIN, BOX = MODE == ZM_BOX;
+    static_assert(!(IO && BOX), "lmh_rollout_zoh_io has no box-constrained form");
     LmhCParams &P0 = LMH_KERNARG_PARAMS();
     typedef const __attribute__((address_space(4))) ZohExArgs CArgs;
     auto KA = [&]() -> CArgs & {
@@ -4996,6 +5083,20 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
     SET_GDBG(nullptr);
     unsigned F = eval_begin<2>(L, P, inst, KA().state + (size_t)LMH_STATE_STRIDE * inst, KA().status, wid);
     if constexpr (BOX) { if (wid == 1) zoh_box_setup(P, inst); }
+    if constexpr (IO) {                                            // the first evaluation's measurement, behind a push due at the launch's first substep
+        if (wid == 0) {
+            const int lane = LANE;
+            double x = L[P_Q + ((lane < 60) ? lane : 0)];
+            if (KA().ex.pushes) {
+                const int lim = KA().n_ticks * KA().n_substeps;
+                int pc = 0;
+                if (push_seek(L, P, inst, lane, t, lim, &pc) == 0) push_apply(L, P, inst, lane, 0, pc, lim, x);
+            }
+            if (KA().n_ticks > 0) zoh_io_publish(L, KA().state + (size_t)LMH_STATE_STRIDE * inst, lane, x, 0, inst);
+            WSYNC();
+        }
+        bsync<2>();
+    } else
     if (KA().ex.pushes) {                                          // (workgroup-uniform: both waves pass the join)
         if (wid == 0) {
             const int lane = LANE, lim = KA().n_ticks * KA().n_substeps;
@@ -5011,6 +5112,8 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
     }
     const double dt = P.dt;
     int k = 0, itmax = 0, flags = 0;
+    ZohIoJoint io_joint = {0.0, 0.0, 0};
+    if constexpr (IO) { if (wid == 0) io_joint = zoh_io_joint(LANE, inst); }
 #pragma unroll 1
     for (int tick = 0; tick < KA().n_ticks; tick++) {
         int iters = 0;
@@ -5042,8 +5145,10 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
             }
             if (double *m = KA().ex.metrics) metrics_wave1<false>(m + (size_t)LMH_METRICS_STRIDE * inst, L, lane);
             double x = L[P_Q + ((lane < 60) ? lane : 0)];          // q | v are one run
+            if constexpr (IO) x = KA().state[(size_t)LMH_STATE_STRIDE * inst + ((lane < 60) ? lane : 0)];      // the true state: L holds what the evaluation measured
             const double vp = L[P_V + ((lane < 30) ? lane : 0)];   // Robot::v_ <- dq (controller.cpp:59): what the next evaluation sees
-            const double tau = (lane < 6) ? bw : L[P_TAU + ((lane >= 6 && lane < 30) ? lane - 6 : 0)];         // lane i < 30: tau30[i] = [base wrench | out.tau]
+            double tau = (lane < 6) ? bw : L[P_TAU + ((lane >= 6 && lane < 30) ? lane - 6 : 0)];               // lane i < 30: tau30[i] = [base wrench | out.tau]
+            if constexpr (IO) tau = zoh_io_actuate(tau, io_joint, lane, inst, tick, flags);
             const bool pushes = KA().ex.pushes != 0;
             // substeps of the launch | of them behind the robot: the cursor's units, formed with pushes only (the host bounds the product then)
             const int lim = pushes ? KA().n_ticks * nsub : 0;
@@ -5069,7 +5174,8 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
             // substep the launch ends on)
             if (pushes) push_poll(L, P, inst, lane, done, lim, x);
             WSYNC();
-            if (lane < 60) L[P_Q + lane] = x;
+            if constexpr (IO) zoh_io_publish(L, KA().state + (size_t)LMH_STATE_STRIDE * inst, lane, x, tick + 1, inst);
+            else if (lane < 60) L[P_Q + lane] = x;
             if (lane < 30) L[P_VP + lane] = vp;
             WSYNC();
         }
@@ -5096,10 +5202,25 @@ __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_wav
     (void)A_arg;
     lmh_rollout_zoh_ex_body<ZM_BOX>(L);
 }
+// lmh_rollout_zoh_io (include/lmh.h): the same body with the measurement and the actuator in the loop
+template <bool REF>
+__global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) lmh_rollout_zoh_io_kernel(LmhDevParams P_arg, ZohIoArgs A_arg)
+{
+    __shared__ double L[LDS_DOUBLES];
+    (void)A_arg;
+    lmh_rollout_zoh_ex_body<REF ? ZM_REF : ZM_BUILTIN, true>(L);
+}
 // ex NULL: lmh_rollout_zoh's kernel exactly as it is when ref is NULL, otherwise lmh_rollout_zoh_ref's; with ex the kernel that takes the options
 extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
-                                       const LmhZohEx *ex, const LmhZohBox *bx, hipStream_t s)
+                                       const LmhZohEx *ex, const LmhZohBox *bx, const LmhZohIo *io, hipStream_t s)
 {
+    // io: lmh_rollout_zoh_io_kernel (ex is then never NULL and bx is)
+    if (io) {
+        const ZohIoArgs a = {{state, out, status, base_wrench, log, ref, *ex, n_ticks, n_substeps}, *io};
+        if (ref) hipLaunchKernelGGL(lmh_rollout_zoh_io_kernel<true>, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, a);
+        else hipLaunchKernelGGL(lmh_rollout_zoh_io_kernel<false>, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, a);
+        return;
+    }
     // bx: lmh_rollout_zoh_box_kernel.  The most dynamic shared memory such a launch may ask for (N = LMH_MAX_HORIZON) is above the 64 KB a kernel gets
     // unasked: bx->prepare sets that limit on the current device and launches nothing.
     if (bx && bx->prepare) {

@@ -28,8 +28,10 @@ extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_
 // bx (lmh_rollout_zoh_box; ex is then never NULL and ref is): NULL = the kernels above; otherwise lmh_rollout_zoh_box_kernel, that loop with lmh_mpc_box_step at
 // the measured CoM state inside every evaluation -- or, with bx->prepare, no launch at all (LmhZohBox, lmh_device.h).  The same launcher, not a new symbol: the
 // stand-alone host programs under tests/host link lmh_capi.hip against one stub per launcher.
+// io (lmh_rollout_zoh_io; ex is then never NULL and bx is): NULL = the kernels above; otherwise lmh_rollout_zoh_io_kernel, lmh_rollout_zoh_ex_kernel's loop
+// with a measurement added to what the evaluation reads and an actuator in front of the hold (LmhZohIo, lmh_device.h).
 extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
-                                       const LmhZohEx *ex, const LmhZohBox *bx, hipStream_t s);
+                                       const LmhZohEx *ex, const LmhZohBox *bx, const LmhZohIo *io, hipStream_t s);
 extern "C" void lmh_launch_metrics_reset(double *metrics, int n_instances, double z_min, double tilt_max, hipStream_t s);
 extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
 extern "C" void lmh_launch_com(const LmhDevParams *P, const double *q, double *com, hipStream_t s);

@@ -8,7 +8,7 @@ definition on top of the reference's conventions (SupportFoot -> ZMP y of -/+0.0
 """
 import numpy as np
 
-from .capi import FLAG_BOX_EMPTY, FLAG_NONFINITE, FLAG_NOT_SPD, FLAG_QP_MAXITER, FLAG_ZMP_RANGE, IK_TARGET_STRIDE, LIP_STRIDE, MAX_PUSHES, MPC_BOX_MAX_ROUNDS, MPC_STRIDE, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE
+from .capi import ACT_MAX_DELAY, ACT_MEM_STRIDE, ACT_OFF_ALPHA, ACT_OFF_DELAY, ACT_OFF_TAU_MAX, ACT_STRIDE, FLAG_BOX_EMPTY, FLAG_NONFINITE, FLAG_NOT_SPD, FLAG_QP_MAXITER, FLAG_ZMP_RANGE, IK_TARGET_STRIDE, LIP_STRIDE, MAX_PUSHES, MPC_BOX_MAX_ROUNDS, MPC_STRIDE, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE
 
 
 def stance_zmp(simulation_time, time_step, support_foot=2):
@@ -592,6 +592,69 @@ def zoh_hold_pieces(ticks, n0, n_ticks, n_substeps):
     return result
 
 
+# the refusals of lmh_set_actuators, word for word (lmh_capi.hip, actuator_record_error)
+ACT_ERR_LIMIT = "torque limits must be >= 0 (+inf: none)"
+ACT_ERR_ALPHA = "alpha must be in (0, 1]"
+ACT_ERR_DELAY = "delay must be a whole number in [0, LMH_ACT_MAX_DELAY (7)]"
+
+
+def actuator_records(n_instances, tau_max=None, alpha=None, delay=None):
+    """Host statement of the table of lmh_set_actuators: tau_max and alpha a scalar, [24] or [B,24] (None: inf / 1), delay a scalar or [B]
+    (None: 0) -> records [B, 56] = tau_max[24] | alpha[24] | delay | pad.  Everything lmh_set_actuators refuses is refused here with the
+    same words, the first offending robot named ("robot 7: ...")."""
+    B = int(n_instances)
+    rec = np.zeros((B, ACT_STRIDE))
+    rec[:, ACT_OFF_TAU_MAX:ACT_OFF_TAU_MAX + 24] = np.broadcast_to(np.asarray(np.inf if tau_max is None else tau_max, dtype=np.float64), (B, 24))
+    rec[:, ACT_OFF_ALPHA:ACT_OFF_ALPHA + 24] = np.broadcast_to(np.asarray(1.0 if alpha is None else alpha, dtype=np.float64), (B, 24))
+    rec[:, ACT_OFF_DELAY] = np.broadcast_to(np.asarray(0.0 if delay is None else delay, dtype=np.float64), (B,))
+    for i, r in enumerate(rec):
+        if not (r[ACT_OFF_TAU_MAX:ACT_OFF_TAU_MAX + 24] >= 0.0).all():
+            raise ValueError(f"robot {i}: {ACT_ERR_LIMIT}")
+        a = r[ACT_OFF_ALPHA:ACT_OFF_ALPHA + 24]
+        if not ((a > 0.0) & (a <= 1.0)).all():
+            raise ValueError(f"robot {i}: {ACT_ERR_ALPHA}")
+        d = r[ACT_OFF_DELAY]
+        if not (d >= 0.0) or not (d <= ACT_MAX_DELAY) or d != np.floor(d):
+            raise ValueError(f"robot {i}: {ACT_ERR_DELAY}")
+    return rec
+
+
+def actuator_step(record, mem, cmd):
+    """Host statement of the actuator of lmh_rollout_zoh_io (include/lmh.h), one control tick: record [..,56] (lmh_set_actuators), mem
+    [..,192] = PREV[24] | QUEUE[7][24] (changed IN PLACE), cmd [..,24] the torques the evaluation commands -> (y [..,24], the torques the
+    plant receives; limited [..] bool, whether a joint's torque was cut: LMH_FLAG_TAU_LIMIT).  Latency in control ticks through the queue
+    (slots at and above the delay are never touched), then the limit (a NaN passes through), then the first-order lag y = alpha * c +
+    (1 - alpha) * PREV with every operation rounded on its own (PREV is not read where alpha is 1), and PREV <- y.  One robot or a batch."""
+    rec, cmd_ = np.asarray(record, dtype=np.float64), np.asarray(cmd, dtype=np.float64)
+    if not isinstance(mem, np.ndarray) or mem.dtype != np.float64 or not mem.flags.c_contiguous or mem.shape[-1] != ACT_MEM_STRIDE \
+            or rec.shape[-1] != ACT_STRIDE or cmd_.shape[-1] != 24:
+        raise ValueError("actuator_step takes record [..,56], mem [..,192] (a contiguous float64 array, changed in place) and cmd [..,24]")
+    lead = mem.shape[:-1]
+    rec2 = np.broadcast_to(rec, lead + (ACT_STRIDE,)).reshape(-1, ACT_STRIDE)
+    cmd2 = np.broadcast_to(cmd_, lead + (24,)).reshape(-1, 24)
+    mem2 = mem.reshape(-1, ACT_MEM_STRIDE)                           # a view: mem is contiguous
+    y = np.empty((len(mem2), 24))
+    limited = np.zeros(len(mem2), dtype=bool)
+    with np.errstate(invalid="ignore"):
+        for i in range(len(mem2)):
+            lim, alpha, d = rec2[i, ACT_OFF_TAU_MAX:ACT_OFF_TAU_MAX + 24], rec2[i, ACT_OFF_ALPHA:ACT_OFF_ALPHA + 24], int(rec2[i, ACT_OFF_DELAY])
+            prev, queue = mem2[i, 0:24], mem2[i, 24:].reshape(ACT_MAX_DELAY, 24)
+            if d == 0:
+                u = cmd2[i].copy()
+            else:
+                u = queue[0].copy()
+                queue[0:d - 1] = queue[1:d].copy()
+                queue[d - 1] = cmd2[i]
+            c = np.where(u > lim, lim, np.where(u < -lim, -lim, u))
+            limited[i] = bool((c != u).any())
+            lag = alpha != 1.0
+            yi = c.copy()
+            yi[lag] = (alpha[lag] * c[lag]) + ((1.0 - alpha[lag]) * prev[lag])
+            prev[:] = yi
+            y[i] = yi
+    return y.reshape(lead + (24,)), limited.reshape(lead)
+
+
 __all__ = ["stance_zmp", "find_poly_coeff", "foot_coeff_trajectory", "walk_plan", "jump_plan", "walk_plans", "jump_plans",
-           "push_schedule", "check_push_records", "draw_pushes", "zoh_hold_pieces", "preview_index", "lip_rollout", "com_targets",
+           "push_schedule", "check_push_records", "draw_pushes", "zoh_hold_pieces", "actuator_records", "actuator_step", "preview_index", "lip_rollout", "com_targets",
            "PHASE_DOUBLE", "PHASE_RIGHT", "PHASE_LEFT", "PHASE_FLIGHT"]
