@@ -1,6 +1,10 @@
 """What the timing scripts of this directory share (a private module, not a tool): the import path, bench.py's config-3 walkers, the
-HIP-event timer with its median / min / max, and the --out writer.  Importing it puts the repository root and tests/ on sys.path."""
+HIP-event timer with its median / min / max, say and the --out writer, and the parent-compare harness of the zoh_*_rate.py scripts (the
+last section).  Importing it puts the repository root and tests/ on sys.path."""
+import argparse
+import json
 import os
+import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,8 +58,113 @@ def summary(times):
     return float(np.median(times)), min(times), max(times)
 
 
+lines = []                                                          # what say() printed: the --out file
+
+
+def say(s):
+    print(s, flush=True)
+    lines.append(s)
+
+
 def write_lines(path, lines):
     """The --out file; no path, no file."""
     if path:
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         open(path, "w").write("\n".join(lines) + "\n")
+
+
+# ------------------------------------------------------------------------------- the zoh_*_rate.py scripts: this build against the parent
+# Each script times rows of launches of this build, interleaved, and -- with --parent-variant NAME and linearmpchumanoid_amd/
+# liblmh_hip_var_NAME.so in place (build.py) -- one launch on the parent's library in two child processes of itself, one before and one after
+# its own rows: the parent's pass-to-pass spread in this session, which the judged rows are held to.
+def zoh_rate_args(child_times, new_prototypes):
+    """The scripts' arguments.  In a child (--child: time `child_times` on the library LMH_VARIANT selects) the prototypes of the entry
+    points the parent's library has not got are dropped; so call this before anything loads the library."""
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--instances", type=int, default=4096)
+    ap.add_argument("--ticks", type=int, default=200)
+    ap.add_argument("--substeps", type=int, nargs="+", default=[1, 10])
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--parent-variant", default=None)
+    ap.add_argument("--child", action="store_true", help="(internal) time %s on the library LMH_VARIANT selects and print one JSON line" % child_times)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    if args.child:
+        from linearmpchumanoid_amd import capi
+        for name in new_prototypes:
+            capi.PROTOTYPES.pop(name, None)
+    assert torch.cuda.is_available(), "%s measures on the GPU only" % os.path.basename(sys.argv[0])
+    return args
+
+
+def standing(B, q0, seed=20261104):
+    """zoh_rate.py's start: every sole vertex half a millimetre into the default ground, small velocities -> (q, v)"""
+    rng = np.random.default_rng(seed)
+    q = np.tile(q0, (B, 1)); q[:, 2] -= 5.0e-4
+    v = np.zeros((B, 30)); v[:, 0:2] = rng.uniform(-0.05, 0.05, (B, 2)); v[:, 6:] = rng.normal(0.0, 0.01, (B, 24))
+    return q, v
+
+
+def child_branch(args, launch_of, before):
+    """In a child: time launch_of(n_substeps) for every n_substeps, print the one JSON line and leave."""
+    if args.child:
+        print(json.dumps({"times": {str(n): time_launches(launch_of(n), args.steps, args.warmup, before=before) for n in args.substeps}}))
+        sys.exit(0)
+
+
+def have_parent(args):
+    return bool(args.parent_variant) and os.path.exists(os.path.join(ROOT, "linearmpchumanoid_amd", "liblmh_hip_var_%s.so" % args.parent_variant))
+
+
+def parent_pass(args):
+    """One child of this script on the parent's library -> {str(n_substeps): times}"""
+    env = {k: val for k, val in os.environ.items() if k != "LMH_DIAG"}
+    env["LMH_VARIANT"] = args.parent_variant
+    r = subprocess.run([sys.executable, os.path.abspath(sys.argv[0]), "--child", "--instances", str(args.instances), "--ticks", str(args.ticks), "--steps", str(args.steps),
+                        "--warmup", str(args.warmup), "--substeps", *map(str, args.substeps)], env=env, cwd=ROOT, capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["times"]
+
+
+def head(args, title):
+    """The first line(s) of the output and the parent's first pass -> [times] or []"""
+    say("%s, %d robots x %d control ticks, fp64 (%s); %d timed launches after %d warm-up"
+        % (title, args.instances, args.ticks, torch.cuda.get_device_name(0), args.steps, args.warmup))
+    if not have_parent(args):
+        say("no parent library (--parent-variant): this build only, nothing is compared with the parent")
+    return [parent_pass(args)] if have_parent(args) else []
+
+
+def time_rows(args, rows, before):
+    """rows [(name, launch)] interleaved, one timed launch each per round (the first round also warms up) -> {name: times}"""
+    times = {name: [] for name, _ in rows}
+    for it in range(args.steps):
+        for name, fn in rows:
+            times[name] += time_launches(fn, 1, args.warmup if it == 0 else 0, before=before)
+    return times
+
+
+def fmt(args, t):
+    m, lo, hi = summary(t)
+    return "%8.2f ms (%.2f .. %.2f, spread %.1f %%) = %.3f M ticks/s" % (m, lo, hi, 100.0 * (hi - lo) / m, args.instances * args.ticks / m / 1e3)
+
+
+def parent_report(args, parent, n_sub, width, judged, one_line=False):
+    """The parent's two passes in a name column of `width`, their pass-to-pass spread, and for every (label, median of this build) of
+    judged whether it lies inside the range of all the parent's timings (or below it); one_line: spread and verdict on one line."""
+    allp = []
+    for i, p in enumerate(parent):
+        say("  %-*s %s" % (width, "parent, pass %d" % (i + 1), fmt(args, p[str(n_sub)])))
+        allp += p[str(n_sub)]
+    meds = [summary(p[str(n_sub)])[0] for p in parent]
+    spread = "  parent pass-to-pass: medians %.2f / %.2f ms (%.2f %%), range of all timings %.2f .. %.2f ms" % (
+        meds[0], meds[1], 100.0 * abs(meds[0] - meds[1]) / min(meds), min(allp), max(allp))
+    verdicts = ["%s / parent median %.4f | inside the parent's own spread (or faster): %s" % (label, m / float(np.median(allp)), "PASS" if m <= max(allp) else "FAIL")
+                for label, m in judged]
+    if one_line:
+        say(" | ".join([spread] + verdicts))
+    else:
+        say(spread)
+        for v in verdicts:
+            say("  " + v)

@@ -15,7 +15,7 @@ import time
 import numpy as np
 import torch
 
-from _bench_common import MPC_DT, DT, write_lines
+from _bench_common import MPC_DT, DT, lines, say, write_lines
 import plan_draw
 from linearmpchumanoid_amd import trajectories as tj
 from linearmpchumanoid_amd.controller import BatchedController, default_config
@@ -28,12 +28,6 @@ ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 assert torch.cuda.is_available(), "mpc_box_rate.py measures on the GPU only"
-lines = []
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
 
 
 def timed(fn):

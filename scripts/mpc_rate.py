@@ -17,7 +17,7 @@ import time
 import numpy as np
 import torch
 
-from _bench_common import MPC_DT, N_PREVIEW, DT, write_lines
+from _bench_common import MPC_DT, N_PREVIEW, DT, lines, say, write_lines
 import plan_draw
 from linearmpchumanoid_amd.controller import BatchedController, default_config, ik_start_posture
 
@@ -30,12 +30,6 @@ ap.add_argument("--eval-launches", type=int, default=20)
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 assert torch.cuda.is_available(), "mpc_rate.py measures on the GPU only"
-lines = []
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
 
 
 def timed(fn):

@@ -18,53 +18,19 @@ The box rows are reported relative to rollout_zoh and to the host loop, not judg
 from rollout_zoh after the run (the gain-row step and the factor solve agree to rounding only).
 Usage: python scripts/zoh_box_rate.py [--instances 4096] [--ticks 200] [--substeps 1 10] [--steps 5] [--warmup 2] [--parent-variant NAME]
                                       [--out FILE]"""
-import argparse
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import torch
 
-from _bench_common import ROOT, summary, time_launches, write_lines
+from _bench_common import child_branch, fmt, head, lines, parent_pass, parent_report, say, standing, summary, time_rows, write_lines, zoh_rate_args
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--instances", type=int, default=4096)
-ap.add_argument("--ticks", type=int, default=200)
-ap.add_argument("--substeps", type=int, nargs="+", default=[1, 10])
-ap.add_argument("--steps", type=int, default=5)
-ap.add_argument("--warmup", type=int, default=2)
-ap.add_argument("--parent-variant", default=None)
-ap.add_argument("--child", action="store_true", help="(internal) time rollout_zoh on the library LMH_VARIANT selects and print one JSON line")
-ap.add_argument("--out", default=None)
-args = ap.parse_args()
-
-from linearmpchumanoid_amd import capi
-
-if args.child:                                                     # a library of the parent tree has not got the new entry point
-    capi.PROTOTYPES.pop("lmh_rollout_zoh_box", None)
-from linearmpchumanoid_amd import trajectories as tj
+args = zoh_rate_args("rollout_zoh", ("lmh_rollout_zoh_box",))
+from linearmpchumanoid_amd import capi, trajectories as tj
 from linearmpchumanoid_amd.controller import BatchedController, default_config, ik_start_posture
 
-assert torch.cuda.is_available(), "zoh_box_rate.py measures on the GPU only"
 B, nt = args.instances, args.ticks
 DT = 1e-3
 q0, zcom = ik_start_posture(0)
-lines = []
 SIM = nt * max(args.substeps) * DT + 1.0
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
-
-
-def standing(seed=20261104):                                       # zoh_rate.py's start
-    rng = np.random.default_rng(seed)
-    q = np.tile(q0, (B, 1)); q[:, 2] -= 5.0e-4
-    v = np.zeros((B, 30)); v[:, 0:2] = rng.uniform(-0.05, 0.05, (B, 2)); v[:, 6:] = rng.normal(0.0, 0.01, (B, 24))
-    return q, v
 
 
 def handle(N, mpc_dt, support):
@@ -87,24 +53,11 @@ def boxes(c, mpc_dt, support):
     return torch.as_tensor(b).to(c.device)
 
 
-q, v = standing()
+q, v = standing(B, q0)
 ctl = handle(32, 1e-2, 2)
 st0 = ctl.new_state(q, v, t=0.0, v_prev=v)
 out, status = ctl.new_out(), ctl.new_status()
-
-if args.child:
-    print(json.dumps({"times": {str(n): time_launches(lambda st: ctl.rollout_zoh(st, nt, n, out=out, status=status), args.steps, args.warmup, before=st0.clone)
-                                for n in args.substeps}}))
-    sys.exit(0)
-
-
-def parent_pass():
-    env = {k: val for k, val in os.environ.items() if k != "LMH_DIAG"}
-    env["LMH_VARIANT"] = args.parent_variant
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--instances", str(B), "--ticks", str(nt), "--steps", str(args.steps),
-                        "--warmup", str(args.warmup), "--substeps", *map(str, args.substeps)], env=env, cwd=ROOT, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["times"]
+child_branch(args, lambda n: (lambda st: ctl.rollout_zoh(st, nt, n, out=out, status=status)), st0.clone)
 
 
 def host_loop(c, box, n_sub):
@@ -125,12 +78,7 @@ def host_loop(c, box, n_sub):
     return run
 
 
-have_parent = bool(args.parent_variant) and os.path.exists(os.path.join(ROOT, "linearmpchumanoid_amd", "liblmh_hip_var_%s.so" % args.parent_variant))
-say("zero-order-hold loop with the box-constrained preview step inside (lmh_rollout_zoh_box), %d robots x %d control ticks, fp64 (%s); %d timed launches after %d warm-up"
-    % (B, nt, torch.cuda.get_device_name(0), args.steps, args.warmup))
-if not have_parent:
-    say("no parent library (--parent-variant): this build only, nothing is compared with the parent")
-parent = [parent_pass()] if have_parent else []
+parent = head(args, "zero-order-hold loop with the box-constrained preview step inside (lmh_rollout_zoh_box)")
 left = handle(32, 1e-2, 1)
 inf32, bind32 = boxes(ctl, 1e-2, 2), boxes(left, 1e-2, 1)
 others = []
@@ -155,15 +103,10 @@ for n_sub in args.substeps:
     info = dict(far=far, far_rel=far / float(sa[:, 0:60].abs().max()), active_inf=float(ri["mpc"][:, :, 15].max()), active_bind_min=float(rb["mpc"][:, :, 15].min()),
                 flagged_inf=int(((ri["status"][:, 2] & 15) != 0).sum()), flagged_bind=int(((rb["status"][:, 2] & 15) != 0).sum()))
     del ri, rb
-    times = {name: [] for name, _ in rows}
-    for it in range(args.steps):                                   # interleaved, one timed launch each (the first round also warms up)
-        for name, fn in rows:
-            times[name] += time_launches(fn, 1, args.warmup if it == 0 else 0, before=st0.clone)
+    times = time_rows(args, rows, st0.clone)
     mine[n_sub] = (times, info, [name for name, _ in rows])
-if have_parent:
-    parent.append(parent_pass())
-fmt = lambda t: "%8.2f ms (%.2f .. %.2f, spread %.1f %%) = %.3f M ticks/s" % (summary(t)[0], summary(t)[1], summary(t)[2],
-                                                                             100.0 * (max(t) - min(t)) / summary(t)[0], B * nt / summary(t)[0] / 1e3)
+if parent:
+    parent.append(parent_pass(args))
 for n_sub in args.substeps:
     times, info, names = mine[n_sub]
     base = summary(times["rollout_zoh"])[0]
@@ -171,16 +114,9 @@ for n_sub in args.substeps:
         "max %d, under the binding box: min %d; robots with a counted flag: %d (infinite), %d (binding)"
         % (n_sub, info["far"], info["far_rel"], info["active_inf"], info["active_bind_min"], info["flagged_inf"], info["flagged_bind"]))
     for name in names:
-        say("  %-26s %s | / rollout_zoh %.4f" % (name, fmt(times[name]), summary(times[name])[0] / base))
+        say("  %-26s %s | / rollout_zoh %.4f" % (name, fmt(args, times[name]), summary(times[name])[0] / base))
     for kind in ("infinite", "binding"):
         say("  host loop / fused, %-9s %.3f" % (kind + ":", summary(times["host loop, " + kind])[0] / summary(times["box, " + kind])[0]))
-    if have_parent:
-        allp = []
-        for i, p in enumerate(parent):
-            say("  parent, pass %d             %s" % (i + 1, fmt(p[str(n_sub)])))
-            allp += p[str(n_sub)]
-        meds = [summary(p[str(n_sub)])[0] for p in parent]
-        say("  parent pass-to-pass: medians %.2f / %.2f ms (%.2f %%), range of all timings %.2f .. %.2f ms" % (meds[0], meds[1], 100.0 * abs(meds[0] - meds[1]) / min(meds), min(allp), max(allp)))
-        m = summary(times["rollout_zoh"])[0]
-        say("  rollout_zoh / parent median %.4f | inside the parent's own spread (or faster): %s" % (m / float(np.median(allp)), "PASS" if m <= max(allp) else "FAIL"))
+    if parent:
+        parent_report(args, parent, n_sub, 26, [("rollout_zoh", base)])
 write_lines(args.out, lines)

@@ -15,80 +15,25 @@ Timed per n_substeps, HIP events around one launch, medians with min..max, the r
 The option rows are reported relative to rollout_zoh, not judged.  Without a parent library only this build is measured, and the output says so.
 Usage: python scripts/zoh_ex_rate.py [--instances 4096] [--ticks 200] [--substeps 1 10] [--steps 5] [--warmup 2] [--parent-variant NAME]
                                      [--out FILE]"""
-import argparse
-import json
-import os
-import subprocess
-import sys
-
 import numpy as np
 import torch
 
-from _bench_common import ROOT, summary, time_launches, write_lines
+from _bench_common import child_branch, fmt, head, lines, parent_pass, parent_report, say, standing, summary, time_rows, write_lines, zoh_rate_args
 
-ap = argparse.ArgumentParser()
-ap.add_argument("--instances", type=int, default=4096)
-ap.add_argument("--ticks", type=int, default=200)
-ap.add_argument("--substeps", type=int, nargs="+", default=[1, 10])
-ap.add_argument("--steps", type=int, default=5)
-ap.add_argument("--warmup", type=int, default=2)
-ap.add_argument("--parent-variant", default=None)
-ap.add_argument("--child", action="store_true", help="(internal) time rollout_zoh on the library LMH_VARIANT selects and print one JSON line")
-ap.add_argument("--out", default=None)
-args = ap.parse_args()
-
-from linearmpchumanoid_amd import capi
-
-if args.child:                                                     # a library of the parent tree has not got the new entry point
-    capi.PROTOTYPES.pop("lmh_rollout_zoh_ex", None)
-from linearmpchumanoid_amd import trajectories
+args = zoh_rate_args("rollout_zoh", ("lmh_rollout_zoh_ex",))
+from linearmpchumanoid_amd import capi, trajectories
 from linearmpchumanoid_amd.controller import BatchedController, default_config, ik_start_posture
 
-assert torch.cuda.is_available(), "zoh_ex_rate.py measures on the GPU only"
 B, nt = args.instances, args.ticks
 q0, zcom = ik_start_posture(0)
-lines = []
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
-
-
-def standing(seed=20261104):                                       # zoh_rate.py's start
-    rng = np.random.default_rng(seed)
-    q = np.tile(q0, (B, 1)); q[:, 2] -= 5.0e-4
-    v = np.zeros((B, 30)); v[:, 0:2] = rng.uniform(-0.05, 0.05, (B, 2)); v[:, 6:] = rng.normal(0.0, 0.01, (B, 24))
-    return q, v
-
-
 ctl = BatchedController(B, default_config(dt=1e-3, time_horizon=0.016, z_com=zcom))
 ctl.set_refs_stance(nt * max(args.substeps) * 1e-3 + 1.0, 2)
-q, v = standing()
+q, v = standing(B, q0)
 st0 = ctl.new_state(q, v, t=0.0, v_prev=v)
 out, status = ctl.new_out(), ctl.new_status()
+child_branch(args, lambda n: (lambda st: ctl.rollout_zoh(st, nt, n, out=out, status=status)), st0.clone)
 
-if args.child:
-    print(json.dumps({"times": {str(n): time_launches(lambda st: ctl.rollout_zoh(st, nt, n, out=out, status=status), args.steps, args.warmup, before=st0.clone)
-                                for n in args.substeps}}))
-    sys.exit(0)
-
-
-def parent_pass():
-    env = {k: val for k, val in os.environ.items() if k != "LMH_DIAG"}
-    env["LMH_VARIANT"] = args.parent_variant
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", "--instances", str(B), "--ticks", str(nt), "--steps", str(args.steps),
-                        "--warmup", str(args.warmup), "--substeps", *map(str, args.substeps)], env=env, cwd=ROOT, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["times"]
-
-
-have_parent = bool(args.parent_variant) and os.path.exists(os.path.join(ROOT, "linearmpchumanoid_amd", "liblmh_hip_var_%s.so" % args.parent_variant))
-say("zero-order-hold loop and the options of lmh_rollout_zoh_ex, %d robots x %d control ticks, fp64 (%s); %d timed launches after %d warm-up"
-    % (B, nt, torch.cuda.get_device_name(0), args.steps, args.warmup))
-if not have_parent:
-    say("no parent library (--parent-variant): this build only, nothing is compared with the parent")
-parent = [parent_pass()] if have_parent else []
+parent = head(args, "zero-order-hold loop and the options of lmh_rollout_zoh_ex")
 bw = torch.as_tensor(np.random.default_rng(20261105).normal(0.0, 0.5, (nt, B, 6))).to(ctl.device)
 metrics = ctl.new_metrics(0.2, 0.5)
 mine = {}
@@ -113,30 +58,17 @@ for n_sub in args.substeps:
     rc = ctl.rollout_zoh_ex(sc, nt, n_sub, pushes=True, base_wrench=bw, metrics=ctl.new_metrics(0.2, 0.5), trace_every=1, trace=tr1)
     torch.cuda.synchronize()
     same = bool(torch.equal(sa.view(torch.int64), sb.view(torch.int64)) and torch.equal(oa.view(torch.int64), rb["out"].view(torch.int64)) and torch.equal(xa, rb["status"]))
-    times = {name: [] for name, _ in rows}
-    for it in range(args.steps):                                   # interleaved, one timed launch each (the first round also warms up)
-        for name, fn in rows:
-            times[name] += time_launches(fn, 1, args.warmup if it == 0 else 0, before=st0.clone)
+    times = time_rows(args, rows, st0.clone)
     mine[n_sub] = (times, same, int(((rc["status"][:, 2] & 15) != 0).sum()), [name for name, _ in rows])
     ctl.set_pushes(None)
-if have_parent:
-    parent.append(parent_pass())
-fmt = lambda t: "%8.2f ms (%.2f .. %.2f, spread %.1f %%) = %.3f M ticks/s" % (summary(t)[0], summary(t)[1], summary(t)[2],
-                                                                             100.0 * (max(t) - min(t)) / summary(t)[0], B * nt / summary(t)[0] / 1e3)
+if parent:
+    parent.append(parent_pass(args))
 for n_sub in args.substeps:
     times, same, flagged, names = mine[n_sub]
     base = summary(times["rollout_zoh"])[0]
     say("n_substeps %2d: (ex with nothing set leaves rollout_zoh's bytes: %s; robots with a counted flag with everything on: %d)" % (n_sub, same, flagged))
     for name in names:
-        say("  %-20s %s | / rollout_zoh %.4f" % (name, fmt(times[name]), summary(times[name])[0] / base))
-    if have_parent:
-        allp = []
-        for i, p in enumerate(parent):
-            say("  parent, pass %d       %s" % (i + 1, fmt(p[str(n_sub)])))
-            allp += p[str(n_sub)]
-        meds = [summary(p[str(n_sub)])[0] for p in parent]
-        say("  parent pass-to-pass: medians %.2f / %.2f ms (%.2f %%), range of all timings %.2f .. %.2f ms" % (meds[0], meds[1], 100.0 * abs(meds[0] - meds[1]) / min(meds), min(allp), max(allp)))
-        for name in ("rollout_zoh", "ex, nothing set"):
-            m = summary(times[name])[0]
-            say("  %-20s / parent median %.4f | inside the parent's own spread (or faster): %s" % (name, m / float(np.median(allp)), "PASS" if m <= max(allp) else "FAIL"))
+        say("  %-20s %s | / rollout_zoh %.4f" % (name, fmt(args, times[name]), summary(times[name])[0] / base))
+    if parent:
+        parent_report(args, parent, n_sub, 20, [("%-20s" % name, summary(times[name])[0]) for name in ("rollout_zoh", "ex, nothing set")])
 write_lines(args.out, lines)

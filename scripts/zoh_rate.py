@@ -15,7 +15,7 @@ import time
 import numpy as np
 import torch
 
-from _bench_common import write_lines
+from _bench_common import lines, say, write_lines
 from linearmpchumanoid_amd.controller import BatchedController, default_config, ik_start_posture
 
 ap = argparse.ArgumentParser()
@@ -30,12 +30,6 @@ ap.add_argument("--out", default=None)
 args = ap.parse_args()
 assert torch.cuda.is_available(), "zoh_rate.py measures on the GPU only"
 q0, zcom = ik_start_posture(0)
-lines = []
-
-
-def say(s):
-    print(s, flush=True)
-    lines.append(s)
 
 
 def standing(B, seed, rest_first=False):

@@ -4,8 +4,8 @@ rollout_zoh(ref=...).
 lmh_eval_ref is lmh_eval with the six words xRef | yRef taken from the caller's record instead of the built-in preview step, so most cases
 are identities against lmh_eval itself, byte for byte (helpers.same_bits): the built-in step's own words handed back (1), handed to a
 handle with other ZMP samples (2), a launch's words replayed (5).  Where the reference is one no preview step produces the checker is the
-numpy restatement with a supplied reference (3, ref_cases.py); lmh_rollout_zoh_ref is held to the host loop that defines it (4); the
-box-constrained MPC's trajectory goes in as it stands (6); refusals, isolation of a bad record and graph capture (7).
+numpy restatement with a supplied reference (3, ref_cases.py); lmh_rollout_zoh_ref is held to the host loop that defines it (4,
+zoh_host_loop.py); the box-constrained MPC's trajectory goes in as it stands (6); refusals, isolation of a bad record and graph capture (7).
 B = 8 everywhere.  States: the first eight of plant_step_cases.contact_states() (the zero-order-hold tests' inputs, v_prev = v), except (3)
 which uses ref_cases.states().  A record's words [6, 16) hold a sentinel the calls must not read."""
 import ctypes as C
@@ -18,6 +18,7 @@ import params_cases as pcs
 import plant_step_cases as pc
 import ref_cases as rc
 from helpers import TOL_REL, WEIGHT, close, make_controller, same_bits as _same, vec_err
+from zoh_host_loop import host_loop
 
 pytestmark = pytest.mark.gpu
 DT, TH, B = pc.DT, pc.TH, 8
@@ -202,25 +203,6 @@ def _zoh_refs(ctl, S, n_ticks, seed):
     return _records(ctl, out[:, 72:78].unsqueeze(0) + torch.as_tensor(d).to(ctl.device), (n_ticks,))
 
 
-def _host_loop(ctl, st, status, refs, n_substeps, bw=None):
-    """The definition (include/lmh.h): -> (out, status with [1] / [2] merged as max / OR over the ticks and the plant's flags, log)."""
-    n_ticks = refs.shape[0]
-    out = ctl.new_out()
-    base = torch.zeros((B, 6), dtype=torch.float64, device=ctl.device) if bw is None else bw
-    rounds = torch.zeros((B,), dtype=torch.int32, device=ctl.device)
-    flags = torch.zeros((B,), dtype=torch.int32, device=ctl.device)
-    log = torch.zeros((n_ticks, B, 36), dtype=torch.float64, device=ctl.device)
-    for tick in range(n_ticks):
-        ctl.stand_step(st, out, status, ref=refs[tick])
-        log[tick] = out[:, 0:36]
-        _, pf = ctl.plant_step(st, torch.cat([base, out[:, 0:24]], dim=1).contiguous(), n_substeps)
-        rounds = torch.maximum(rounds, status[:, 1])
-        flags = flags | status[:, 2] | pf
-    status[:, 1] = rounds
-    status[:, 2] = flags
-    return out, status, log
-
-
 @pytest.fixture(scope="module")
 def zoh():
     S = _states()
@@ -237,7 +219,8 @@ def test_zoh_is_the_host_loop_bit_for_bit(zoh, n_substeps, wrench):
     ctl, S, refs, bw = zoh["ctl"], zoh["S"], zoh["refs"], zoh["bw"] if wrench else None
     sa, sb = _fresh(ctl, S), _fresh(ctl, S)
     out_a, status_a, log_a = ctl.rollout_zoh(sa, 6, n_substeps, base_wrench=bw, log=True, ref=refs)
-    out_b, status_b, log_b = _host_loop(ctl, sb, ctl.new_status(), refs, n_substeps, bw)
+    rb = host_loop(ctl, sb, ctl.new_status(), 6, n_substeps, bw=bw, refs=refs)
+    out_b, status_b, log_b = rb["out"], rb["status"], rb["log"]
     torch.cuda.synchronize()
     for name, a, b in (("state", sa, sb), ("out", out_a, out_b), ("status", status_a, status_b), ("log", log_a, log_b)):
         assert _same(a, b), (n_substeps, wrench, name)

@@ -77,6 +77,25 @@ def test_composition_bit_for_bit(run, warm_start):
     assert float(out[:, 0:24].abs().max()) > 0.0 and _same(log[n_ticks - 1], out[:, 0:36].contiguous())
 
 
+@pytest.mark.parametrize("n_substeps", [3, 1])
+def test_the_shared_host_loop_with_no_option_is_the_written_out_loop(n_substeps):
+    """zoh_host_loop.host_loop, the definition the calls with options are held to, against _host_loop above: six ticks (a warm start
+    carried from evaluation to evaluation) with one wrench, a hold of three substeps and of one."""
+    import zoh_host_loop
+    S = pc.contact_states()
+    ctl = make_controller(B, DT, TH, S["zcom"], warm_start=1)
+    ctl.set_refs_stance(2.0, 2)
+    bw = torch.as_tensor(np.random.default_rng(20261024).normal(0.0, 1.0, (B, 6))).to(ctl.device)
+    sa, sb = _fresh(ctl, S), _fresh(ctl, S)
+    ra = zoh_host_loop.host_loop(ctl, sa, ctl.new_status(), 6, n_substeps, bw=bw)
+    out_b, status_b, log_b = _host_loop(ctl, sb, ctl.new_status(), 6, n_substeps, bw)
+    torch.cuda.synchronize()
+    for name, a, b in (("state", sa, sb), ("out", ra["out"], out_b), ("status", ra["status"], status_b), ("log", ra["log"], log_b)):
+        assert _same(a, b), (n_substeps, name)
+    assert float(ra["out"][:, 0:24].abs().max()) > 0.0 and not _same(sa[:, 0:60], _fresh(ctl, S)[:, 0:60])
+    ctl.close()
+
+
 @pytest.mark.parametrize("warm_start", [0, 1])
 def test_composition_with_a_slower_preview(warm_start):
     """mpc_dt = 4 ms under a control period of 2 ms: k moves every second control tick, so the reference cache of the fused launch both hits

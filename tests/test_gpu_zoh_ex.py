@@ -1,9 +1,9 @@
 """lmh_rollout_zoh_ex on the GPU: the zero-order-hold loop with timed pushes, a wrench per control tick, a trace and a metrics record.
 
 The call is DEFINED by a host loop of calls that exist (include/lmh.h), so the reference of every bit-for-bit case is that loop on a second
-copy of the same buffers (_host_loop: stand_step, plant_step in the pieces trajectories.zoh_hold_pieces gives, v += dv in torch); only
-test_against_the_oracle goes to the CPU (zoh_ex_cases.oracle_ex_run).  Inputs: plant_step_cases.contact_states(), 16 states around
-touch-down, v_prev = v, warm_start = 1, a 2 s stance plan; six control ticks everywhere.  "Bit for bit" is helpers.same_bits.
+copy of the same buffers (zoh_host_loop.host_loop: stand_step, plant_step in the pieces trajectories.zoh_hold_pieces gives, v += dv in
+torch); only test_against_the_oracle goes to the CPU (zoh_ex_cases.oracle_ex_run).  Inputs: plant_step_cases.contact_states(), 16 states
+around touch-down, v_prev = v, warm_start = 1, a 2 s stance plan; six control ticks everywhere.  "Bit for bit" is helpers.same_bits.
 The pushes and wrenches are small enough that the host loop itself leaves no counted flag (flags & 15) on any robot -- asserted on the host
 loop's status wherever it runs, never on the kernel's."""
 import ctypes as C
@@ -15,29 +15,17 @@ import torch
 import plant_step_cases as pc
 import zoh_ex_cases as zx
 from helpers import TOL_REL, WEIGHT, close, make_controller, rel_err, same_bits as _same, vec_err
+from zoh_host_loop import SCHEDULES, assert_same as _assert_same, fresh, host_loop, no_counted_flag as _no_counted_flag, push_schedules, wrench_and_refs
 
 pytestmark = pytest.mark.gpu
 DT, TH, B, NT = pc.DT, pc.TH, pc.B, zx.N_TICKS
 FIVE_DT = sum([DT] * 5)           # a clock of five accumulated dt: the robot's substep number is 5
 NO_PUSH = 8
-# per-robot schedules (plant substep numbers, -1 = unused): between the four runs (n_substeps 3 | 1, from substep 0 | 5) they hold every
-# case of zoh_ex_cases.PIECE_CASES -- substep 0, control-tick boundaries, just behind one, two in one hold, the last substep, the launch's
-# end substep, the past, trailing -1 records
-SCHEDULES = [[0], [6], [7], [4, 5], [17], [18], [3, 9], [2, 6, -1, -1], [-1], [5, 8, 9, 10, 23, 24], [0, 1, 3, 5], [10, 11],
-             [1, 2, 22], [12, 15, 16], [8, 20, 21], [5, 6, 7, 11]]
 SHARED_SCHEDULE = [0, 4, 6, 7, 17, 18]
 
 
-def _schedules():
-    ticks = np.full((B, 6), -1, dtype=np.int64)
-    for i, s in enumerate(SCHEDULES):
-        ticks[i, :len(s)] = s
-    dv = np.stack([zx.push_dv(20261110 + i, 6) for i in range(B)])
-    return ticks, dv
-
-
 def _fresh(ctl, S, t=0.0):
-    return ctl.new_state(S["q"], S["v"], t=t, v_prev=S["v"])       # pads zero: a trace sample writes them as zeros
+    return fresh(ctl, S["q"], S["v"], t)
 
 
 def _applied(ticks, n0, n_ticks, n_substeps):
@@ -50,100 +38,18 @@ def _applied(ticks, n0, n_ticks, n_substeps):
     return res
 
 
-def _host_loop(ctl, st, status, n_ticks, n_substeps, bw=None, sched=None, refs=None):
-    """The definition on a handle WITHOUT a schedule.  bw: None | [B,6] | [n_ticks,B,6]; sched: None | (ticks [B,n] or [n], dv [B,n,30]).
-    -> dict(out, status with [1] / [2] merged as max / OR over the ticks and the plant's flags, log [n_ticks,B,36], trace [n_ticks,B,180]:
-    the three records after every control tick)."""
-    from linearmpchumanoid_amd.trajectories import zoh_hold_pieces
-    dev = ctl.device
-    out = ctl.new_out()
-    zero = torch.zeros((B, 6), dtype=torch.float64, device=dev)
-    rounds = torch.zeros((B,), dtype=torch.int32, device=dev)
-    flags = torch.zeros((B,), dtype=torch.int32, device=dev)
-    log = torch.zeros((n_ticks, B, 36), dtype=torch.float64, device=dev)
-    trace = torch.zeros((n_ticks, B, 180), dtype=torch.float64, device=dev)
-    pieces = None
-    if sched is not None:
-        ticks, dv = sched
-        n0 = np.rint(st[:, 90].cpu().numpy() / DT).astype(np.int64)
-        pieces = [zoh_hold_pieces(ticks[i] if ticks.ndim == 2 else ticks, n0[i], n_ticks, n_substeps) for i in range(B)]
-        dvt = torch.as_tensor(dv).to(dev)
-
-    def push(rows, recs):
-        if rows:
-            r = torch.as_tensor(rows, device=dev)
-            st[r, 30:60] += dvt[r, torch.as_tensor(recs, device=dev)]
-
-    for tick in range(n_ticks):
-        if pieces:
-            rows = [i for i in range(B) if pieces[i][tick][0] is not None]
-            push(rows, [pieces[i][tick][0] for i in rows])
-        ctl.stand_step(st, out, status, ref=None if refs is None else refs[tick])
-        log[tick] = out[:, 0:36]
-        base = zero if bw is None else (bw[tick] if bw.ndim == 3 else bw)
-        tau30 = torch.cat([base, out[:, 0:24]], dim=1).contiguous()
-        # the robots' holds are cut where any robot has a push: plant_step(a + b) is plant_step(a) ; plant_step(b) bit for bit
-        cuts = {}
-        if pieces:
-            for i in range(B):
-                at = 0
-                for s, rec in pieces[i][tick][1]:
-                    at += s
-                    if rec is not None:
-                        cuts.setdefault(at, []).append((i, rec))
-        at = 0
-        for c in sorted(cuts) + [n_substeps]:
-            if c > at:
-                _, pf = ctl.plant_step(st, tau30, c - at)
-                flags = flags | pf
-                at = c
-            if c in cuts:
-                push([i for i, _ in cuts[c]], [r for _, r in cuts[c]])
-        rounds = torch.maximum(rounds, status[:, 1])
-        flags = flags | status[:, 2]
-        trace[tick, :, 0:96] = st
-        trace[tick, :, 96:176] = out
-        trace[tick, :, 176] = status[:, 0].double()
-        trace[tick, :, 177] = rounds.double()
-        trace[tick, :, 178] = flags.double()
-        trace[tick, :, 179] = status[:, 3].double()
-    status[:, 1] = rounds
-    status[:, 2] = flags
-    return dict(out=out, status=status, log=log, trace=trace)
-
-
-def _no_counted_flag(status, but=()):
-    f = (status[:, 2] & 15).tolist()
-    assert all(v == 0 for i, v in enumerate(f) if i not in but), ("the host loop itself raised a counted flag", f)
-
-
-def _assert_same(tag, pairs):
-    for name, a, b in pairs:
-        if not _same(a, b):
-            d = (a.double() - b.double()).abs()
-            where = torch.nonzero(d.reshape(-1, d.shape[-1]).amax(dim=1) > 0).flatten().tolist()
-            raise AssertionError((tag, name, "rows that differ", where[:8], "max |difference|", float(d.max())))
-
-
 @pytest.fixture(scope="module")
 def zoh():
     S = pc.contact_states()
-    ticks, dv = _schedules()
+    ticks, dv = push_schedules()
     mk = lambda: make_controller(B, DT, TH, S["zcom"], warm_start=1)
     ctl, shared, plain = mk(), mk(), mk()                          # per-robot schedules | one shared schedule | none: the host loop's handle
     for c in (ctl, shared, plain):
         c.set_refs_stance(2.0, 2)
     ctl.set_pushes(ticks, dv)
     shared.set_pushes(np.array(SHARED_SCHEDULE), dv[0])
-    dev = ctl.device
-    bw_seq = torch.as_tensor(zx.wrench_sequence(20261111, NT)).to(dev)
-    bw = torch.as_tensor(np.random.default_rng(20261112).normal(0.0, 1.0, (B, 6))).to(dev)
-    # a CoM reference per control tick and robot: the built-in step's words at the start state, moved per tick and robot by up to 5 mm,
-    # 2 cm/s and 0.1 m/s^2 (every record differs from every other: a wrong record shows); the words that are not read carry a sentinel
-    out0, _ = plain.stand_step(_fresh(plain, S))
-    refs = torch.full((NT, B, 16), -7.0e3, dtype=torch.float64, device=dev)
-    d = np.random.default_rng(20261113).uniform(-1.0, 1.0, (NT, B, 6)) * np.array([0.005, 0.02, 0.1, 0.005, 0.02, 0.1])
-    refs[:, :, 0:6] = out0[:, 72:78] + torch.as_tensor(d).to(dev)
+    bw = torch.as_tensor(np.random.default_rng(20261112).normal(0.0, 1.0, (B, 6))).to(ctl.device)
+    bw_seq, refs, _ = wrench_and_refs(plain, _fresh(plain, S), NT)
     yield dict(S=S, ctl=ctl, shared=shared, plain=plain, ticks=ticks, dv=dv, bw_seq=bw_seq, bw=bw, refs=refs)
     for c in (ctl, shared, plain):
         c.close()
@@ -184,7 +90,7 @@ def test_pushes_are_the_host_loop_bit_for_bit(zoh, n_substeps, t0):
         ctl = zoh[name]
         sa, sb, sc = _fresh(ctl, S, t0), _fresh(plain, S, t0), _fresh(ctl, S, t0)
         ra = ctl.rollout_zoh_ex(sa, NT, n_substeps, pushes=True, log=True)
-        rb = _host_loop(plain, sb, plain.new_status(), NT, n_substeps, sched=sched)
+        rb = host_loop(plain, sb, plain.new_status(), NT, n_substeps, sched=sched)
         rc = ctl.rollout_zoh_ex(sc, NT, n_substeps, pushes=False, log=True)
         torch.cuda.synchronize()
         _no_counted_flag(rb["status"])
@@ -203,7 +109,7 @@ def test_pushes_are_the_host_loop_bit_for_bit(zoh, n_substeps, t0):
         assert last or name == "shared"                              # (the per-robot schedules always hold such a push; the trace test checks the rule at sample 2 as well)
         if last:
             sd = _fresh(plain, S, t0)
-            _host_loop(plain, sd, plain.new_status(), NT - 1, n_substeps, sched=sched)
+            host_loop(plain, sd, plain.new_status(), NT - 1, n_substeps, sched=sched)
             for i, rec in last:
                 assert _same(sa[i, 60:90], (sd[i, 30:60] + torch.as_tensor(sched[1][i, rec]).to(sd.device)))
 
@@ -216,7 +122,7 @@ def test_pushes_wrench_sequence_and_reference_are_the_host_loop(zoh, n_substeps,
     ctl, plain, S, refs, bw_seq = zoh["ctl"], zoh["plain"], zoh["S"], zoh["refs"], zoh["bw_seq"]
     sa, sb, sc = _fresh(ctl, S, t0), _fresh(plain, S, t0), _fresh(ctl, S, t0)
     ra = ctl.rollout_zoh_ex(sa, NT, n_substeps, base_wrench=bw_seq, ref=refs, pushes=True, log=True)
-    rb = _host_loop(plain, sb, plain.new_status(), NT, n_substeps, bw=bw_seq, sched=(zoh["ticks"], zoh["dv"]), refs=refs)
+    rb = host_loop(plain, sb, plain.new_status(), NT, n_substeps, bw=bw_seq, sched=(zoh["ticks"], zoh["dv"]), refs=refs)
     swapped = refs.clone()
     swapped[[1, 4]] = refs[[4, 1]]
     rc = ctl.rollout_zoh_ex(sc, NT, n_substeps, base_wrench=bw_seq, ref=swapped, pushes=True, log=True)
@@ -245,7 +151,7 @@ def test_pushes_on_per_robot_walking_plans(zoh):
     ctl, plain = ctls
     sa, sb = _fresh(ctl, S), _fresh(plain, S)
     ra = ctl.rollout_zoh_ex(sa, NT, 3, base_wrench=bw_seq, pushes=True, log=True)
-    rb = _host_loop(plain, sb, plain.new_status(), NT, 3, bw=bw_seq, sched=(ticks, dv))
+    rb = host_loop(plain, sb, plain.new_status(), NT, 3, bw=bw_seq, sched=(ticks, dv))
     torch.cuda.synchronize()
     _assert_same("walking plans", (("state", sa, sb), ("out", ra["out"], rb["out"]), ("status", ra["status"], rb["status"]), ("log", ra["log"], rb["log"])))
     assert len({tuple(ctl.get_plan(i)["seg_of_sample"][:18].tolist()) for i in range(B)}) >= 8
@@ -258,7 +164,7 @@ def test_wrench_sequence(zoh):
     ctl, plain, S, bw_seq, bw = zoh["ctl"], zoh["plain"], zoh["S"], zoh["bw_seq"], zoh["bw"]
     sa, sb = _fresh(ctl, S), _fresh(plain, S)
     ra = ctl.rollout_zoh_ex(sa, NT, 3, base_wrench=bw_seq, log=True)
-    rb = _host_loop(plain, sb, plain.new_status(), NT, 3, bw=bw_seq)
+    rb = host_loop(plain, sb, plain.new_status(), NT, 3, bw=bw_seq)
     torch.cuda.synchronize()
     _no_counted_flag(rb["status"])
     _assert_same("sequence", (("state", sa, sb), ("out", ra["out"], rb["out"]), ("status", ra["status"], rb["status"]), ("log", ra["log"], rb["log"])))
@@ -285,8 +191,8 @@ def _everything(ctl, S, zoh, n_ticks, every=0, trace=None, metrics=None, status=
 
 def _everything_on_the_host(zoh, with_ref):
     plain = zoh["plain"]
-    host = _host_loop(plain, _fresh(plain, zoh["S"]), plain.new_status(), NT, 3, bw=zoh["bw_seq"], sched=(zoh["ticks"], zoh["dv"]),
-                      refs=zoh["refs"] if with_ref else None)
+    host = host_loop(plain, _fresh(plain, zoh["S"]), plain.new_status(), NT, 3, bw=zoh["bw_seq"], sched=(zoh["ticks"], zoh["dv"]),
+                     refs=zoh["refs"] if with_ref else None)
     torch.cuda.synchronize()
     _no_counted_flag(host["status"])
     return host

@@ -2,10 +2,10 @@
 limit and a first-order lag on what the plant receives.
 
 The call is DEFINED by a host loop of calls that exist (include/lmh.h), so the reference of every bit-for-bit case is that loop on a second
-copy of the same buffers (_host_loop: stand_step on a scratch copy with the measurement added in torch, _actuate -- the torch twin of
-trajectories.actuator_step --, plant_step in the pieces trajectories.zoh_hold_pieces gives); only test_against_the_oracle goes to the CPU
-(zoh_io_cases.oracle_io_run).  Inputs: plant_step_cases.contact_states(), 16 states around touch-down, v_prev = v, warm_start = 1, a 2 s
-stance plan; six control ticks everywhere; test_gpu_zoh_ex.py's push schedules.  "Bit for bit" is helpers.same_bits.  Every robot is in
+copy of the same buffers (zoh_host_loop.host_loop: stand_step on a scratch copy with the measurement added in torch, actuate -- the torch
+twin of trajectories.actuator_step --, plant_step in the pieces trajectories.zoh_hold_pieces gives); only test_against_the_oracle goes to the
+CPU (zoh_io_cases.oracle_io_run).  Inputs: plant_step_cases.contact_states(), 16 states around touch-down, v_prev = v, warm_start = 1, a 2 s
+stance plan; six control ticks everywhere; zoh_host_loop's push schedules.  "Bit for bit" is helpers.same_bits.  Every robot is in
 every comparison."""
 import ctypes as C
 import re
@@ -15,129 +15,18 @@ import pytest
 import torch
 
 import plant_step_cases as pc
-import zoh_ex_cases as zx
 import zoh_io_cases as zi
 from helpers import TOL_REL, WEIGHT, close, make_controller, rel_err, same_bits as _same, vec_err
+from zoh_host_loop import SCHEDULES, assert_same as _assert_same, fresh, host_loop, push_schedules, wrench_and_refs
 
 pytestmark = pytest.mark.gpu
 DT, TH, B, NT = pc.DT, pc.TH, pc.B, zi.N_TICKS
 FIVE_DT = sum([DT] * 5)           # a clock of five accumulated dt: the robot's substep number is 5
-SCHEDULES = [[0], [6], [7], [4, 5], [17], [18], [3, 9], [2, 6, -1, -1], [-1], [5, 8, 9, 10, 23, 24], [0, 1, 3, 5], [10, 11],
-             [1, 2, 22], [12, 15, 16], [8, 20, 21], [5, 6, 7, 11]]   # test_gpu_zoh_ex.py's: every way a push can fall in a launch
 DELAYS = (np.arange(B) % 8).tolist()
 
 
-def _schedules():
-    ticks = np.full((B, 6), -1, dtype=np.int64)
-    for i, s in enumerate(SCHEDULES):
-        ticks[i, :len(s)] = s
-    return ticks, np.stack([zx.push_dv(20261110 + i, 6) for i in range(B)])
-
-
 def _fresh(ctl, S, t=0.0):
-    return ctl.new_state(S["q"], S["v"], t=t, v_prev=S["v"])       # pads zero: a trace sample writes them as zeros
-
-
-def _actuate(rec, mem, cmd):
-    """trajectories.actuator_step in torch on the device: rec [B,56], mem [B,192] (in place), cmd [B,24] -> (y [B,24], limited [B] bool).
-    Every elementwise operation is a kernel of its own: the products and the sum are rounded one by one."""
-    lim, alpha = rec[:, 0:24], rec[:, 24:48]
-    queue = mem[:, 24:].view(B, 7, 24)
-    u = cmd.clone()
-    for i, d in enumerate(rec[:, 48].long().tolist()):
-        if d > 0:
-            u[i] = queue[i, 0]
-            if d > 1:
-                queue[i, 0:d - 1] = queue[i, 1:d].clone()
-            queue[i, d - 1] = cmd[i]
-    c = torch.where(u > lim, lim, torch.where(u < -lim, -lim, u))
-    limited = (c != u).any(dim=1)
-    y = torch.where(alpha != 1.0, alpha * c + (1.0 - alpha) * mem[:, 0:24], c)
-    mem[:, 0:24] = y
-    return y, limited
-
-
-def _host_loop(ctl, st, status, n_ticks, n_substeps, bw=None, sched=None, refs=None, meas=None, rec=None, mem=None):
-    """The definition on a handle WITHOUT a schedule and WITHOUT actuator records.  bw: None | [B,6] | [n_ticks,B,6]; sched: None | (ticks
-    [B,n], dv [B,n,30]); meas: None | [n_ticks,B,60]; rec: None | [B,56] with mem [B,192] (in place).  -> dict(out, status with [1] / [2]
-    merged as max / OR over the ticks, the plant's flags and FLAG_TAU_LIMIT, log [n_ticks,B,36], applied [n_ticks,B,24], trace
-    [n_ticks,B,180]: the three records after every control tick)."""
-    from linearmpchumanoid_amd import capi
-    from linearmpchumanoid_amd.trajectories import zoh_hold_pieces
-    dev = ctl.device
-    out = ctl.new_out()
-    zero = torch.zeros((B, 6), dtype=torch.float64, device=dev)
-    rounds = torch.zeros((B,), dtype=torch.int32, device=dev)
-    flags = torch.zeros((B,), dtype=torch.int32, device=dev)
-    log = torch.zeros((n_ticks, B, 36), dtype=torch.float64, device=dev)
-    applied = torch.zeros((n_ticks, B, 24), dtype=torch.float64, device=dev)
-    trace = torch.zeros((n_ticks, B, 180), dtype=torch.float64, device=dev)
-    pieces = None
-    if sched is not None:
-        ticks, dv = sched
-        n0 = np.rint(st[:, 90].cpu().numpy() / DT).astype(np.int64)
-        pieces = [zoh_hold_pieces(ticks[i], n0[i], n_ticks, n_substeps) for i in range(B)]
-        dvt = torch.as_tensor(dv).to(dev)
-
-    def push(rows, recs):
-        if rows:
-            r = torch.as_tensor(rows, device=dev)
-            st[r, 30:60] += dvt[r, torch.as_tensor(recs, device=dev)]
-
-    for tick in range(n_ticks):
-        if pieces:
-            rows = [i for i in range(B) if pieces[i][tick][0] is not None]
-            push(rows, [pieces[i][tick][0] for i in rows])
-        scratch = st.clone()
-        if meas is not None:
-            scratch[:, 0:60] = st[:, 0:60] + meas[tick]
-        ctl.stand_step(scratch, out, status, ref=None if refs is None else refs[tick])
-        st[:, 60:90] = scratch[:, 60:90]                           # v_prev: the v the controller measured
-        log[tick] = out[:, 0:36]
-        cmd = out[:, 0:24].contiguous()
-        if rec is not None:
-            y, limited = _actuate(rec, mem, cmd)
-            flags = flags | (limited.to(torch.int32) * capi.FLAG_TAU_LIMIT)
-        else:
-            y = cmd
-        applied[tick] = y
-        base = zero if bw is None else (bw[tick] if bw.ndim == 3 else bw)
-        tau30 = torch.cat([base, y], dim=1).contiguous()
-        cuts = {}                                                  # the robots' holds are cut where any robot has a push: plant_step(a + b) is plant_step(a) ; plant_step(b)
-        if pieces:
-            for i in range(B):
-                at = 0
-                for s, r in pieces[i][tick][1]:
-                    at += s
-                    if r is not None:
-                        cuts.setdefault(at, []).append((i, r))
-        at = 0
-        for c in sorted(cuts) + [n_substeps]:
-            if c > at:
-                _, pf = ctl.plant_step(st, tau30, c - at)
-                flags = flags | pf
-                at = c
-            if c in cuts:
-                push([i for i, _ in cuts[c]], [r for _, r in cuts[c]])
-        rounds = torch.maximum(rounds, status[:, 1])
-        flags = flags | status[:, 2]
-        trace[tick, :, 0:96] = st
-        trace[tick, :, 96:176] = out
-        trace[tick, :, 176] = status[:, 0].double()
-        trace[tick, :, 177] = rounds.double()
-        trace[tick, :, 178] = flags.double()
-        trace[tick, :, 179] = status[:, 3].double()
-    status[:, 1] = rounds
-    status[:, 2] = flags
-    return dict(out=out, status=status, log=log, trace=trace, applied=applied)
-
-
-def _assert_same(tag, pairs):
-    for name, a, b in pairs:
-        if not _same(a, b):
-            d = (a.double() - b.double()).abs()
-            where = torch.nonzero(d.reshape(-1, d.shape[-1]).amax(dim=1) > 0).flatten().tolist()
-            raise AssertionError((tag, name, "rows that differ", where[:8], "max |difference|", float(d.max())))
+    return fresh(ctl, S["q"], S["v"], t)
 
 
 def _core(tag, sa, ra, sb, rb, more=()):
@@ -148,7 +37,7 @@ def _core(tag, sa, ra, sb, rb, more=()):
 @pytest.fixture(scope="module")
 def zio():
     S = pc.contact_states()
-    ticks, dv = _schedules()
+    ticks, dv = push_schedules()
     mk = lambda: make_controller(B, DT, TH, S["zcom"], warm_start=1)
     ctl, plain = mk(), mk()                                        # push schedules and actuator records | neither: the host loop's handle
     for c in (ctl, plain):
@@ -161,12 +50,8 @@ def zio():
     tau_max[0::4] = np.inf
     rec = zi.robot_records(tau_max)
     ctl.set_actuators(tau_max=rec[:, 0:24], alpha=rec[:, 24:48], delay=rec[:, 48])
-    bw_seq = torch.as_tensor(zx.wrench_sequence(20261111, NT)).to(dev)
     meas = torch.as_tensor(zi.measurement_noise(20261202, NT)).to(dev)
-    out0, _ = plain.stand_step(_fresh(plain, S))
-    refs = torch.full((NT, B, 16), -7.0e3, dtype=torch.float64, device=dev)
-    d = np.random.default_rng(20261113).uniform(-1.0, 1.0, (NT, B, 6)) * np.array([0.005, 0.02, 0.1, 0.005, 0.02, 0.1])
-    refs[:, :, 0:6] = out0[:, 72:78] + torch.as_tensor(d).to(dev)
+    bw_seq, refs, out0 = wrench_and_refs(plain, _fresh(plain, S), NT)
     tau0 = out0[:, 0:24].contiguous() * 0.5                        # a holding torque for the memories: half of the first command
     yield dict(S=S, ctl=ctl, plain=plain, ticks=ticks, dv=dv, bw_seq=bw_seq, meas=meas, refs=refs, rec=torch.as_tensor(rec).to(dev), rec_np=rec, tau0=tau0)
     for c in (ctl, plain):
@@ -204,7 +89,7 @@ def test_a_measurement_error_is_the_host_loop_bit_for_bit(zio, n_substeps):
     ctl, plain, S, meas = zio["ctl"], zio["plain"], zio["S"], zio["meas"]
     sa, sb, sc = _fresh(ctl, S), _fresh(plain, S), _fresh(ctl, S)
     ra = ctl.rollout_zoh_io(sa, NT, n_substeps, meas=meas, applied=True, log=True, trace_every=1)
-    rb = _host_loop(plain, sb, plain.new_status(), NT, n_substeps, meas=meas)
+    rb = host_loop(plain, sb, plain.new_status(), NT, n_substeps, meas=meas)
     rc = ctl.rollout_zoh_ex(sc, NT, n_substeps, log=True)
     torch.cuda.synchronize()
     _core(("meas", n_substeps), sa, ra, sb, rb, (("trace", ra["trace"], rb["trace"]),))
@@ -212,7 +97,7 @@ def test_a_measurement_error_is_the_host_loop_bit_for_bit(zio, n_substeps):
     assert all(not _same(sa[i], sc[i]) and not _same(ra["log"][0, i], rc["log"][0, i]) for i in range(B))      # the error matters, from the first tick on, on every robot
     # v_prev is the v the last evaluation MEASURED: the true v before the last hold plus that tick's error
     sd = _fresh(plain, S)
-    _host_loop(plain, sd, plain.new_status(), NT - 1, n_substeps, meas=meas)
+    host_loop(plain, sd, plain.new_status(), NT - 1, n_substeps, meas=meas)
     assert _same(sa[:, 60:90], sd[:, 30:60] + meas[NT - 1, :, 30:60])
     # the array form of meas
     sn = _fresh(ctl, S)
@@ -237,7 +122,7 @@ def test_the_actuator_is_the_host_loop_bit_for_bit(zio, n_substeps):
     mem_a, mem_b = ctl.new_act_mem(zio["tau0"]), plain.new_act_mem(zio["tau0"])
     assert _same(mem_a[:, 0:24], zio["tau0"]) and _same(mem_a[:, 168:192], zio["tau0"])
     ra = ctl.rollout_zoh_io(sa, NT, n_substeps, actuators=True, act_mem=mem_a, applied=True, log=True, trace_every=1)
-    rb = _host_loop(plain, sb, plain.new_status(), NT, n_substeps, rec=zio["rec"], mem=mem_b)
+    rb = host_loop(plain, sb, plain.new_status(), NT, n_substeps, act=(zio["rec"], mem_b))
     rc = ctl.rollout_zoh_ex(sc, NT, n_substeps, log=True)
     torch.cuda.synchronize()
     _core(("actuators", n_substeps), sa, ra, sb, rb, (("trace", ra["trace"], rb["trace"]), ("act_mem", mem_a, mem_b)))
@@ -262,8 +147,8 @@ def _everything(ctl, zio, n_ticks, n_substeps, t0=0.0, every=0, metrics=None, st
 def _everything_on_the_host(zio, n_ticks, n_substeps, t0=0.0):
     plain = zio["plain"]
     st, mem = _fresh(plain, zio["S"], t0), plain.new_act_mem(zio["tau0"])
-    r = _host_loop(plain, st, plain.new_status(), n_ticks, n_substeps, bw=zio["bw_seq"], sched=(zio["ticks"], zio["dv"]), refs=zio["refs"], meas=zio["meas"],
-                   rec=zio["rec"], mem=mem)
+    r = host_loop(plain, st, plain.new_status(), n_ticks, n_substeps, bw=zio["bw_seq"], sched=(zio["ticks"], zio["dv"]), refs=zio["refs"], meas=zio["meas"],
+                  act=(zio["rec"], mem))
     torch.cuda.synchronize()
     return dict(r, state=st, mem=mem)
 
