@@ -102,6 +102,12 @@ extern "C" {
 #define LMH_CONTACT_OFF_W 0       /* [12] contact wrench n_R f_R n_L f_L about the sole origins, world axes, like out.f */
 #define LMH_CONTACT_OFF_VF 12     /* [8][3] force at every sole vertex, foot-major (right foot first), vertices in the order of Robot.cpp:38-42 */
 #define LMH_CONTACT_OFF_PAD 36    /* [4] zero */
+#define LMH_GROUND_STRIDE 8       /* one ground record n_R(3) | h_R | n_L(3) | h_L, see lmh_set_ground */
+/* offsets into one ground record (doubles) */
+#define LMH_GROUND_OFF_N_R 0      /* [3] unit normal of the plane under the right foot, world axes */
+#define LMH_GROUND_OFF_H_R 3      /* its offset along the normal, metres: the ground is n.x <= h */
+#define LMH_GROUND_OFF_N_L 4      /* [3] the same under the left foot */
+#define LMH_GROUND_OFF_H_L 7
 #define LMH_LIP_STRIDE 8          /* the reduced (LIPM) state of one robot, see lmh_mpc_step */
 /* offsets into one LIP state record (doubles) */
 #define LMH_LIP_OFF_X 0           /* CoM x */
@@ -558,6 +564,45 @@ int lmh_plant_derivative(lmh_handle *h, const double *d_q, const double *d_v, co
  * n_substeps = 0 is legal and enqueues nothing; a negative value returns LMH_ERR_BAD_ARG.  lmh_plant_step(a + b) equals lmh_plant_step(a)
  * followed by lmh_plant_step(b) bit for bit.  d_flags[i] (may be NULL): the flags of lmh_plant_derivative, OR-ed over the substeps. */
 int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_tau30, int n_substeps, int32_t *d_flags, void *stream);
+
+/* ---- Ground planes under the soles (build-defined; lmh_set_ground, a table of the handle like the actuator records): how steep a slope, or
+ * how high a ledge under one foot, the controller survives -- per robot, so that a sweep is one launch.
+ * records: HOST [n_sets][LMH_GROUND_STRIDE], n_sets = 1 (one record for every robot) or n_instances; NULL or n_sets = 0 clears the table.
+ * One record is n_R(3) | h_R | n_L(3) | h_L: the ground under a foot is the half space n.x <= h, world coordinates and metres, n a unit normal
+ * and h the plane's offset along it.  The same plane under both feet is a slope; horizontal planes with different h are a ledge under one foot.
+ * CONTACT MODEL.  Per vertex at x with velocity xdot, on its foot's plane (n, h), with the robot's contact_k, contact_d, contact_dt (c_t),
+ * contact_mu:
+ *     pen = h - n.x
+ *     vn  = n.xdot
+ *     fn  = max(0, k pen - d vn)
+ *     vt  = xdot - vn n
+ *     ft  = -c_t vt
+ *     if |ft| > mu fn:  ft *= mu fn / |ft|
+ *     f   = ft + fn n   if pen > 0,   else exactly 0
+ * The wrench is formed as before: r_v x f_v | f_v about the sole origin, world axes, vertices summed in the same order; the contact record
+ * (LMH_CONTACT_*) keeps its layout.  With n = (0, 0, 1) and h = 0 this is the model of lmh_contact_wrench above (to a few ulps of |ft|: the
+ * table's kernels form their sums with explicit fused multiply-adds).  trajectories.ground_contact is the same statement in numpy.
+ * WHO READS IT.  lmh_contact_wrench, lmh_plant_derivative and lmh_plant_step; lmh_rollout_zoh, _ref, _ex and _io, by their definitions: the
+ * host loops written out below are made of lmh_eval and lmh_plant_step, and their bit-for-bit statements stay true word for word.
+ * lmh_rollout_zoh_box on a handle with a table returns LMH_ERR_BAD_ARG before anything is enqueued.  Every other call (lmh_eval*,
+ * lmh_rollout*, the terms, IK and MPC families) reads nothing of the table and is bit for bit what it is without it.  A handle without a
+ * table, or whose table was cleared, launches exactly the kernels it launches without this feature.
+ * THE CONTROLLER IS NOT TOLD.  Its foot references and its friction pyramid stay the flat ones: standing on ground it does not know about is
+ * the point of a robustness test.  The thresholds Z_MIN and TILT_MAX of the metrics stay the caller's.
+ * CHECKS, each LMH_ERR_BAD_ARG naming the first offending robot ("robot 7: ..."): every word finite; | |n|^2 - 1 | <= 1e-12 (the host does
+ * not normalise, and lmh_get_ground returns the bytes that were set); n_z > 0; n_sets 1 or n_instances.  A handle created with plant = 1 is
+ * refused with a message of its own: the RK4 reference loop (lmh_rollout, lmh_eval with plant = 1) is not offered with a ground.
+ * lmh_set_refs' rule: check first, build aside, replace in one step -- a refused or failed call leaves the previous table in place.  The
+ * table is a device buffer of its own (64 B per robot): the parameter blocks of lmh_set_params are not rebuilt.
+ * COST (MI355X, 4096 standing robots, 200 control ticks, a record per robot, against the same build without a table; other batch sizes not
+ * measured): lmh_plant_step 36.26 against 36.19 ms (+0.2 %) at 200 x 1 substeps and 357.2 against 357.1 ms (+0.0 %) at 200 x 10;
+ * lmh_rollout_zoh 65.0 against 61.7 ms (+5.4 %) at n_substeps = 1 and 477.0 against 474.6 ms (+0.5 %) at 10 -- with a table all four
+ * zero-order-hold entry points run lmh_rollout_zoh_io's loop, so the figure at one substep per tick holds that loop's own cost beside
+ * the planes' loads (not profiled apart).
+ * Without a table both calls run at the parent commit's rate (scripts/ground_rate.py). */
+int lmh_set_ground(lmh_handle *h, const double *records, int n_sets);
+int lmh_ground_per_instance(const lmh_handle *h);                    /* 0: none or one shared record, 1: one per robot */
+int lmh_get_ground(lmh_handle *h, int inst, double *record);         /* HOST [LMH_GROUND_STRIDE]; 0 0 1 0 | 0 0 1 0 on a handle without a table */
 
 /* ---- Zero-order-hold closed loop (build-defined; what apps/mujoco/main.cpp:115-122 intended before its feedback path was commented out):
  * the controller at its own rate, the torque-driven plant at a finer step with the torques held, n_ticks control ticks in ONE launch with

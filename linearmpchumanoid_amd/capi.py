@@ -24,6 +24,8 @@ ACT_STRIDE = 56               # one actuator record: tau_max[24] | alpha[24] | d
 ACT_OFF_TAU_MAX, ACT_OFF_ALPHA, ACT_OFF_DELAY = 0, 24, 48
 ACT_MAX_DELAY = 7             # control ticks
 ACT_MEM_STRIDE = 192          # one robot's actuator memory: PREV[24] | QUEUE[7][24], oldest command first (lmh_rollout_zoh_io)
+GROUND_STRIDE = 8             # one ground record: n_R(3) | h_R | n_L(3) | h_L, the half space n.x <= h under each foot (lmh_set_ground)
+GROUND_OFF_N_R, GROUND_OFF_H_R, GROUND_OFF_N_L, GROUND_OFF_H_L = 0, 3, 4, 7
 IK_TARGET_STRIDE = 16         # one inverse-kinematics target record: rf6 | lf6 | com(3) | pad (lmh_ik_batch)
 PARAM_STRIDE = 20             # one per-robot parameter record (lmh_set_params)
 # name -> offset inside a parameter record: the LMH_PARAM_OFF_* defines of include/lmh.h (lmh_config's own order; [19] is a pad)
@@ -155,6 +157,9 @@ PROTOTYPES = {
     "lmh_set_actuators": (_ip, [_vp, _vp, _ip]),
     "lmh_actuators_per_instance": (_ip, [_vp]),
     "lmh_get_actuators": (_ip, [_vp, _ip, _vp]),
+    "lmh_set_ground": (_ip, [_vp, _vp, _ip]),
+    "lmh_ground_per_instance": (_ip, [_vp]),
+    "lmh_get_ground": (_ip, [_vp, _ip, _vp]),
     "lmh_set_params": (_ip, [_vp, _vp, _ip]),
     "lmh_params_per_instance": (_ip, [_vp]),
     "lmh_get_params": (_ip, [_vp, _ip, _vp]),

@@ -288,6 +288,33 @@ class BatchedController:
             mem[:] = t0.to(self.device, torch.float64).expand(self.B, 24).repeat(1, 1 + capi.ACT_MAX_DELAY)
         return mem
 
+    # -- per-robot ground planes under the soles (include/lmh.h, lmh_set_ground)
+    def set_ground(self, records=None):
+        """lmh_set_ground: the plane under each foot that the plant calls (contact_wrench, plant_derivative, plant_step) and rollout_zoh,
+        rollout_zoh_ex and rollout_zoh_io press the sole vertices against, instead of z = 0.  records [8] (one for every robot) or [B,8]:
+        n_R(3) | h_R | n_L(3) | h_L, the ground under a foot being n.x <= h with a unit normal n, n_z > 0 (trajectories.ground_planes forms
+        them from a slope, its azimuth and per-foot offsets; nothing is normalised here).  The controller is not told: its foot references
+        and friction pyramid stay the flat ones.  rollout_zoh_box is refused while a table is set; every other call ignores it.  None clears
+        the table."""
+        if records is None:
+            check(capi.lib().lmh_set_ground(self._h, None, 0))
+            return
+        rec = np.ascontiguousarray(np.asarray(records, dtype=np.float64))
+        if rec.ndim not in (1, 2) or rec.shape[-1] != capi.GROUND_STRIDE:
+            raise ValueError(f"records must be [{capi.GROUND_STRIDE}] or [n_sets,{capi.GROUND_STRIDE}]")
+        check(capi.lib().lmh_set_ground(self._h, _np_ptr(rec), 1 if rec.ndim == 1 else rec.shape[0]))
+
+    @property
+    def ground_per_instance(self):
+        """True while every robot has a ground record of its own."""
+        return bool(capi.lib().lmh_ground_per_instance(self._h))
+
+    def get_ground(self, inst):
+        """Robot inst's ground record [8], the bytes that were set; the flat record 0 0 1 0 | 0 0 1 0 on a handle without a table."""
+        rec = np.zeros(capi.GROUND_STRIDE)
+        check(capi.lib().lmh_get_ground(self._h, int(inst), _np_ptr(rec)))
+        return rec
+
     # -- per-robot gains, QP weights, friction and contact parameters (include/lmh.h, lmh_set_params)
     def set_params(self, **fields):
         """lmh_set_params: one set of PD gains, QP weights, eps_coeff, mu and contact constants per robot, e.g.
@@ -546,7 +573,8 @@ class BatchedController:
     # -- torque-driven plant (include/lmh.h, lmh_contact_wrench): the compliant-contact plant under torques the caller supplies
     def contact_wrench(self, q, v=None):
         """The ground's forces on the soles for q, v [B,30] (device tensors; v=None is v = 0) -> [B,40], one record per robot
-        (split_contact names its fields): the spring-damper contact of lmh_config.plant with the robot's own contact constants."""
+        (split_contact names its fields): the spring-damper contact of lmh_config.plant with the robot's own contact constants, against
+        the robot's planes of set_ground when there is a table (trajectories.ground_contact states the model), else against z = 0."""
         q, v = self._batch("q", q, 30), self._batch("v", v, 30, optional=True)
         c = torch.empty((self.B, capi.CONTACT_STRIDE), dtype=torch.float64, device=self.device)
         check(capi.lib().lmh_contact_wrench(self._h, _dev_ptr(q), _dev_ptr(v), _dev_ptr(c), self._stream()))
@@ -555,7 +583,8 @@ class BatchedController:
     def plant_derivative(self, q, v, tau=None):
         """xdot of the plant for q, v [B,30] under tau [B,30] in the coordinates of M (rows 6..29 joint torques, rows 0..5 an external wrench
         on the base; None: a passive robot) -> (xdot [B,60], contact [B,40], flags [B] int32: FLAG_NOT_SPD / FLAG_NONFINITE per robot).
-        xdot[:, :30] is qdot from v, xdot[:, 30:] solves M a = tau + J'w_c - C(q, v) (state ordering, world frame)."""
+        xdot[:, :30] is qdot from v, xdot[:, 30:] solves M a = tau + J'w_c - C(q, v) (state ordering, world frame).  w_c is
+        contact_wrench's: the planes of set_ground are honoured."""
         q, v, tau = self._batch("q", q, 30), self._batch("v", v, 30), self._batch("tau", tau, 30, optional=True)
         xdot = torch.empty((self.B, 60), dtype=torch.float64, device=self.device)
         c = torch.empty((self.B, capi.CONTACT_STRIDE), dtype=torch.float64, device=self.device)
@@ -566,7 +595,7 @@ class BatchedController:
 
     def plant_step(self, state, tau=None, n_substeps=1):
         """n_substeps RK4 steps of cfg.dt on (q, v) of the state records [B,96], in place, with tau [B,30] held (None: passive); t advances,
-        v_prev stays.  -> (state, flags [B] int32, OR-ed over the substeps)."""
+        v_prev stays.  The planes of set_ground are honoured.  -> (state, flags [B] int32, OR-ed over the substeps)."""
         tau, state = self._batch("tau", tau, 30, optional=True), self._batch("state", state, capi.STATE_STRIDE, in_place=True)
         if int(n_substeps) != n_substeps or n_substeps < 0:
             raise ValueError("n_substeps must be a whole number >= 0")
@@ -581,6 +610,8 @@ class BatchedController:
         mask a warm-started handle continues from; afterwards [:, 1] is the maximum of the QP rounds and [:, 2] the OR of the controller's
         and the plant's flags over all ticks.  ref [n_ticks,B,16] (lmh_rollout_zoh_ref; None: the built-in preview step): record j is the
         CoM reference of control tick j of this launch, as in stand_step(ref=...) -- the traj of mpc_rollout / mpc_box_rollout as it stands.
+        With a set_ground table the holds are plant_step's on that ground (so the loop statement holds as it reads), here and in
+        rollout_zoh_ex and rollout_zoh_io; the evaluation is not told about the ground.
         -> (out, status), plus the log [n_ticks,B,36] (tau | f of every tick) when log is asked for."""
         state, bw = self._batch("state", state, capi.STATE_STRIDE, in_place=True), self._batch("base_wrench", base_wrench, 6, optional=True)
         for name, n in (("n_ticks", n_ticks), ("n_substeps", n_substeps)):
@@ -615,7 +646,8 @@ class BatchedController:
         -- bit for bit the host loop { lip_from_out(stand_step on a scratch copy) ; mpc_box_step ; stand_step(ref=) ; plant_step } -- on one
         factorisation per launch.  box as mpc_box_step takes it ([4,n_samples] or [B,4,n_samples]).  mpc=True: the samples [n_ticks,B,16] of
         every tick's constrained step (split_mpc; word 15: the active samples) are returned under "mpc"; False: not stored; a tensor: filled.
-        There is no ref: a reference and the box step are exclusive.  -> rollout_zoh_ex's dict plus mpc."""
+        There is no ref: a reference and the box step are exclusive.  Refused on a handle with a set_ground table.
+        -> rollout_zoh_ex's dict plus mpc."""
         if ref is not None:
             raise ValueError("rollout_zoh_box takes no ref: the box-constrained step is the reference (the two are exclusive)")
         bx, ns, sets = self._box(box)

@@ -60,6 +60,12 @@ struct lmh_handle {
     // Actuator records (lmh_set_actuators): [n_act_sets][LMH_ACT_STRIDE] on the device and on the host (what lmh_get_actuators returns); empty while
     // n_act_sets = 0.  Read by lmh_rollout_zoh_io alone, through its kernel arguments: no part of the parameter block.
     DevBuf<double> d_act;
+    // Ground records (lmh_set_ground): [n_ground_sets][LMH_GROUND_STRIDE] on the device and on the host (what lmh_get_ground returns); empty while
+    // n_ground_sets = 0.  Read by the plant calls and the zero-order-hold family through their kernel arguments: no part of the parameter block.
+    DevBuf<double> d_ground;
+    std::vector<double> h_ground;
+    int n_ground_sets = 0;
+    size_t ground_stride() const { return (n_ground_sets > 1) ? (size_t)LMH_GROUND_STRIDE : 0; }
     std::vector<double> h_act;
     int n_act_sets = 0;
     // Per-robot parameters (lmh_set_params): the records, one friction table per robot and the table of whole parameter blocks the controller
@@ -457,7 +463,7 @@ extern "C" int lmh_create(const lmh_config *cfg, int n_instances, int device, lm
     {                                                               // lmh_rollout_zoh_box's dynamic LDS: asked for here, never inside the (capturable) call
         int32_t answer = -1;
         const LmhZohBox prep = {nullptr, 0, nullptr, 0.0, 0.0, 1, &answer};
-        lmh_launch_rollout_zoh(&h->P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &prep, nullptr, nullptr);
+        lmh_launch_rollout_zoh(&h->P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &prep, nullptr, nullptr, 0, nullptr);
         h->zoh_box_prepared = answer;
     }
     (void)hipGetLastError();                                        // an answer other than hipSuccess is that call's to report, not a sticky error of this one
@@ -694,6 +700,54 @@ extern "C" int lmh_get_actuators(lmh_handle *h, int inst, double *record)
         return LMH_OK;
     }
     std::memcpy(record, h->h_act.data() + (size_t)LMH_ACT_STRIDE * ((h->n_act_sets > 1) ? inst : 0), sizeof(double) * LMH_ACT_STRIDE);
+    return LMH_OK;
+}
+
+// ---------------------------------------------------------------------------- ground records (the plant calls and the zero-order-hold family)
+// the rules of one record: nullptr = fine
+static const char *ground_record_error(const double *rec)
+{
+    for (int j = 0; j < LMH_GROUND_STRIDE; j++) if (!std::isfinite(rec[j])) return "every word of a ground record must be finite";
+    for (int off : {LMH_GROUND_OFF_N_R, LMH_GROUND_OFF_N_L}) {
+        const double *n = rec + off;
+        if (!(std::fabs((n[0] * n[0] + n[1] * n[1] + n[2] * n[2]) - 1.0) <= 1e-12)) return "a ground normal must have unit length (| |n|^2 - 1 | <= 1e-12; nothing is normalised here)";
+        if (!(n[2] > 0.0)) return "a ground normal must point up (n_z > 0)";
+    }
+    return nullptr;
+}
+
+extern "C" int lmh_set_ground(lmh_handle *h, const double *records, int n_sets)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    if (h->cfg.plant) return fail(LMH_ERR_BAD_ARG, "lmh_set_ground: not offered on a plant = 1 handle (the RK4 reference loop of lmh_rollout keeps the plane z = 0)");
+    if (n_sets < 0) return fail(LMH_ERR_BAD_ARG, "n_sets must be >= 0");
+    if (!records) n_sets = 0;
+    if (n_sets != 0 && n_sets != 1 && n_sets != h->B) return fail(LMH_ERR_BAD_ARG, "lmh_set_ground: n_sets must be 1 or n_instances");
+    for (int i = 0; i < n_sets; i++)
+        if (const char *msg = ground_record_error(records + (size_t)LMH_GROUND_STRIDE * i)) return fail(LMH_ERR_BAD_ARG, robot_msg(i, msg));
+    HIPCHK(hipSetDevice(h->device));
+    DevBuf<double> d;
+    std::vector<double> host;
+    if (n_sets > 0) {
+        host.assign(records, records + (size_t)LMH_GROUND_STRIDE * n_sets);
+        HIPCHK(d.upload(records, (size_t)LMH_GROUND_STRIDE * n_sets));
+    }
+    h->d_ground = std::move(d); h->h_ground.swap(host); h->n_ground_sets = n_sets;        // nothing here fails: the parameter block does not hold the table
+    return LMH_OK;
+}
+
+extern "C" int lmh_ground_per_instance(const lmh_handle *h) { return (h && h->n_ground_sets > 1) ? 1 : 0; }
+
+extern "C" int lmh_get_ground(lmh_handle *h, int inst, double *record)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    if (inst < 0 || inst >= h->B) return fail(LMH_ERR_BAD_ARG, "instance out of range");
+    if (!record) return fail(LMH_ERR_BAD_ARG, "bad argument");
+    if (h->n_ground_sets == 0) {
+        for (int j = 0; j < LMH_GROUND_STRIDE; j++) record[j] = (j == LMH_GROUND_OFF_N_R + 2 || j == LMH_GROUND_OFF_N_L + 2) ? 1.0 : 0.0;
+        return LMH_OK;
+    }
+    std::memcpy(record, h->h_ground.data() + (size_t)LMH_GROUND_STRIDE * ((h->n_ground_sets > 1) ? inst : 0), sizeof(double) * LMH_GROUND_STRIDE);
     return LMH_OK;
 }
 
@@ -1052,7 +1106,7 @@ static int plant_body(lmh_handle *h, int mode, const double *d_q, const double *
                       int n_substeps, void *stream)
 {
     const int rc = plant_constants_ok(h); if (rc) return rc;
-    return launch(h, nullptr, [&] { lmh_launch_plant(&h->P, mode, d_q, d_v, d_tau30, d_state, d_xdot, d_contact, d_flags, n_substeps, (hipStream_t)stream); });
+    return launch(h, nullptr, [&] { lmh_launch_plant(&h->P, mode, d_q, d_v, d_tau30, d_state, d_xdot, d_contact, d_flags, n_substeps, h->d_ground.get(), h->ground_stride(), (hipStream_t)stream); });
 }
 
 extern "C" int lmh_contact_wrench(lmh_handle *h, const double *d_q, const double *d_v, double *d_contact, void *stream)
@@ -1101,6 +1155,7 @@ static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_st
                                           "lmh_rollout_zoh_box: n_samples must be lmh_num_ref_samples", "lmh_rollout_zoh_box: n_sets must be 1 or n_instances"))
             return fail(LMH_ERR_BAD_ARG, why);
         if (d_ref) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_box: opts->d_ref must be NULL (the box-constrained step is the reference: the two are exclusive)");
+        if (h->n_ground_sets > 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_box: not offered on a handle with a ground table (lmh_set_ground(NULL) clears it)");
     }
     if (n_ticks < 0 || n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: n_ticks and n_substeps must be >= 0");
     LmhZohEx ex = {nullptr, nullptr, 0, 0, 0, 0};
@@ -1130,14 +1185,14 @@ static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_st
         if (h->zoh_box_prepared != 0 && h->N > 33)                   // N >= 34: above 64 KB of LDS in all, only with the limit lmh_create asked for
             return fail(LMH_ERR_HIP, "lmh_rollout_zoh_box: the runtime refused the kernel's dynamic shared memory limit when the handle was created");
         const LmhZohBox zb = {bx->d_box, box_stride(h, bx->n_sets), bx->d_mpc, h->cfg.alpha, h->cfg.beta, 0, nullptr};
-        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, nullptr, n_ticks, n_substeps, &ex, &zb, nullptr, (hipStream_t)stream); });
+        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, nullptr, n_ticks, n_substeps, &ex, &zb, nullptr, nullptr, 0, (hipStream_t)stream); });
     }
     if (io && (io->d_meas || io->d_applied || io->actuators)) {
         const LmhZohIo zi = {io->d_meas, io->actuators ? io->d_act_mem : nullptr, io->d_applied, h->d_act.get(), (h->n_act_sets > 1) ? (size_t)LMH_ACT_STRIDE : 0, io->actuators, 0};
-        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, &ex, nullptr, &zi, (hipStream_t)stream); });
+        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, &ex, nullptr, &zi, h->d_ground.get(), h->ground_stride(), (hipStream_t)stream); });
     }
     const bool plain = !ex.trace && !ex.metrics && !ex.wrench_per_tick && !ex.pushes;     // no new option: the kernels of before
-    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, plain ? nullptr : &ex, nullptr, nullptr, (hipStream_t)stream); });
+    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, plain ? nullptr : &ex, nullptr, nullptr, h->d_ground.get(), h->ground_stride(), (hipStream_t)stream); });
 }
 extern "C" int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
                                int n_ticks, int n_substeps, void *stream)

@@ -3263,8 +3263,30 @@ enum { PL_0 = S0 + 384,     // above S0 + [0, 384): the next evaluation's world 
        PL_AP = PL_0 + 306,  // 30 : plant acceleration (WBC coordinates)
        PL_ZERO = PL_0 + 336 }; // 32
 // The plant in pieces, shared by phase_plant and lmh_plant_kernel (the caller passes its LANE: the helpers add no opaque lane reads).
+// The contact law of include/lmh.h on the plane (n, h) = pl[0..3] for the vertex at x moving with xd: four ordinary loads of read-only words
+// (64 B per robot, cached) where they are used, nothing kept.  Every sum is an explicit fma over single products, so the instantiations in
+// lmh_plant_kernel and in the closed loop round alike whatever the compiler contracts around them.
+__device__ __forceinline__ void ground_vertex_force(LmhCParams &P, const double *pl, const double *x, double xd0, double xd1, double xd2, double *f)
+{
+    const double n0 = pl[0], n1 = pl[1], n2 = pl[2], h = pl[3];
+    const double pen = h - fma(n2, x[2], fma(n1, x[1], n0 * x[0]));
+    const double vn = fma(n2, xd2, fma(n1, xd1, n0 * xd0));
+    double fn = fma(P.contact_k, pen, -(P.contact_d * vn));
+    fn = (fn < 0.0) ? 0.0 : fn;
+    const double ct = -P.contact_dt;
+    const double t0 = ct * fma(-vn, n0, xd0), t1 = ct * fma(-vn, n1, xd1), t2 = ct * fma(-vn, n2, xd2);         // -c_t (xd - vn n)
+    const double ft2 = sqrt(fma(t2, t2, fma(t1, t1, t0 * t0))), lim = P.contact_mu * fn;
+    const bool slide = ft2 > lim, in = pen > 0.0;
+    const double sc = slide ? lim / ft2 : 1.0;
+    f[0] = in ? fma(fn, n0, slide ? t0 * sc : t0) : 0.0;
+    f[1] = in ? fma(fn, n1, slide ? t1 * sc : t1) : 0.0;
+    f[2] = in ? fma(fn, n2, slide ? t2 * sc : t2) : 0.0;
+}
 // (1) spring-damper force of every sole vertex -> PL_VF (r_v x f_v | f_v); clears PL_ZERO
-__device__ __forceinline__ void plant_vertex_forces(double *L, LmhCParams &P, int lane)
+// GROUND (lmh_set_ground): `gnd` is the robot's record n_R h_R n_L h_L and the vertex presses against its foot's half space n.x <= h
+// (ground_vertex_force); without it the plane is z = 0 and the statements are the ones this function always had.
+template <bool GROUND = false>
+__device__ __forceinline__ void plant_vertex_forces(double *L, LmhCParams &P, int lane, const double *gnd = nullptr)
 {
     if (lane < 8) {                                                // one lane per (foot, vertex)
         const int ft = lane >> 2, vi = lane & 3;
@@ -3280,6 +3302,13 @@ __device__ __forceinline__ void plant_vertex_forces(double *L, LmhCParams &P, in
         const double xd0 = vo[0] + (om[1] * rp[2] - om[2] * rp[1]);
         const double xd1 = vo[1] + (om[2] * rp[0] - om[0] * rp[2]);
         const double xd2 = vo[2] + (om[0] * rp[1] - om[1] * rp[0]);
+        if constexpr (GROUND) {
+            double f[3];
+            ground_vertex_force(P, gnd + 4 * ft, x, xd0, xd1, xd2, f);
+            double *o = L + PL_VF + 6 * lane;
+            o[0] = rp[1] * f[2] - rp[2] * f[1]; o[1] = rp[2] * f[0] - rp[0] * f[2]; o[2] = rp[0] * f[1] - rp[1] * f[0];
+            o[3] = f[0]; o[4] = f[1]; o[5] = f[2];
+        } else {                                                   // (the flat statements stand as they stood, indentation included: z = 0)
         const double pen = -x[2];
         double fn = P.contact_k * pen - P.contact_d * xd2;
         fn = (fn < 0.0) ? 0.0 : fn;
@@ -3291,6 +3320,7 @@ __device__ __forceinline__ void plant_vertex_forces(double *L, LmhCParams &P, in
         double *o = L + PL_VF + 6 * lane;
         o[0] = rp[1] * f2 - rp[2] * f1; o[1] = rp[2] * f0 - rp[0] * f2; o[2] = rp[0] * f1 - rp[1] * f0;
         o[3] = f0; o[4] = f1; o[5] = f2;
+        }
     }
     if (lane >= 32) L[PL_ZERO + lane - 32] = 0.0;
     WSYNC();
@@ -4748,16 +4778,18 @@ __global__ void __launch_bounds__(64) lmh_terms_kernel(LmhDevParams P_arg, const
 static_assert(LMH_CONTACT_STRIDE == 12 + 24 + 4, "w | vertex forces | pad");
 
 // the contact wrench of the state in L[P_Q], L[P_V] -> PL_DW (PL_VF: the vertex forces); the tree phases up to the Jacobian have run
-__device__ __forceinline__ void plant_contact(double *L, LmhCParams &P, int lane)
+template <bool GROUND = false>
+__device__ __forceinline__ void plant_contact(double *L, LmhCParams &P, int lane, const double *gnd = nullptr)
 {
     refs_vfoot_pdjoints(L, P);                                     // sole twists J vhat -> P_VFOOT (its PD law on lanes 32..61 rides along unread)
     WSYNC();
-    plant_vertex_forces(L, P, lane);
+    plant_vertex_forces<GROUND>(L, P, lane, gnd);
     if (lane < 12) L[PL_DW + lane] = plant_wrench_entry(L, lane);
     WSYNC();
 }
 // one derivative of the state in L[P_Q], L[P_V]: accelerations -> L[P_QDD] (state ordering, world frame); `tau`: lane i < 30 holds tau30[i]
-__device__ __forceinline__ int plant_derivative(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau)
+template <bool GROUND = false>
+__device__ __forceinline__ int plant_derivative(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau, const double *gnd = nullptr)
 {
     if (lane < 30) L[P_VP + lane] = L[P_V + lane];                 // one velocity for every term
     WSYNC();
@@ -4766,7 +4798,7 @@ __device__ __forceinline__ int plant_derivative(double *L, LmhCParams &P, const 
     phase_newton_euler<double>(L);
     phase_crba<double>(L, ib_unpack(ibp));
     phase_jacobian<double>(L);
-    plant_contact(L, P, lane);
+    plant_contact<GROUND>(L, P, lane, gnd);
     if (lane < 30) L[PL_R + lane] = (tau + plant_jt_dw(L, lane)) - L[P_C + lane];
     WSYNC();
     const int flags = plant_minv<true>(L, lane, [&](double a) { L[PL_AP + lane] = a; });
@@ -4777,7 +4809,8 @@ __device__ __forceinline__ int plant_derivative(double *L, LmhCParams &P, const 
 // and goes out in a register, L[P_Q], L[P_V] carry each stage's state (and are left at the last stage's, not at x: a caller that wants x in
 // LDS writes it), `flags` collects plant_derivative's and LMH_FLAG_NONFINITE of x behind every substep.  Wave-scope fences only; no clock:
 // the callers advance theirs by n_substeps additions of dt (lmh_plant_kernel<PM_STEP>; wave 0 of lmh_rollout_zoh_kernel)
-__device__ __forceinline__ void plant_hold(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau, double dt, int n_substeps, double &x, int &flags)
+template <bool GROUND = false>
+__device__ __forceinline__ void plant_hold(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau, double dt, int n_substeps, double &x, int &flags, const double *gnd = nullptr)
 {
 #pragma unroll 1
     for (int sub = 0; sub < n_substeps; sub++) {
@@ -4787,7 +4820,7 @@ __device__ __forceinline__ void plant_hold(double *L, LmhCParams &P, const IbPac
             WSYNC();
             if (lane < 60) L[P_Q + lane] = xs;                     // q | v are one run
             WSYNC();
-            flags |= plant_derivative(L, P, ibp, lane, tau);
+            flags |= plant_derivative<GROUND>(L, P, ibp, lane, tau, gnd);
             rk4_stage<0>(L, stage, lane, dt, P_SC + 52, x, ksum, xs);
         }
         if (__ballot(lane < 60 && !(fabs(x) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
@@ -4845,6 +4878,55 @@ __global__ void __launch_bounds__(64) lmh_plant_kernel(LmhDevParams P_arg, const
         if (lane == 0 && flags_out) flags_out[inst] = flags;
     }
 }
+// TWIN of lmh_plant_kernel, statement for statement, on a handle with a ground table (lmh_set_ground): `ground` + ground_stride * robot is the
+// robot's record (stride 0: one shared record).  A kernel of its own so that the one above keeps its text, and with it its code: a fix to
+// either belongs in both.
+template <int MODE>
+__global__ void __launch_bounds__(64) lmh_plant_ground_kernel(LmhDevParams P_arg, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact,
+                                                              int32_t *flags_out, int n_substeps, const double *ground, size_t ground_stride)
+{
+    LmhCParams &P0 = LMH_KERNARG_PARAMS();
+    __shared__ double L[LDS_DOUBLES];
+    const int inst = blockIdx.x;
+    if (inst >= P0.n_instances) return;
+    LmhCParams &P = *params_of_robot(&P0, inst);
+    const double *gnd = ground + ground_stride * (size_t)inst;
+    const int lane = LANE;
+    SET_GDBG(nullptr);
+    load_common(L, P, inst);
+    if constexpr (MODE == PM_CONTACT) {
+        load_qv(L, q, v, inst, lane, true);
+        WSYNC();
+        phase_fk<double>(L, P.lcoef);
+        phase_com_x<1, double>(L, 0);
+        phase_jacobian<double>(L);
+        plant_contact<true>(L, P, lane, gnd);
+        plant_store_contact(L, contact + (size_t)LMH_CONTACT_STRIDE * inst, lane);
+    } else {
+        const IbPack ibp = ib_pack();
+        const double tau = (tau30 && lane < 30) ? tau30[30 * (size_t)inst + lane] : 0.0;
+        int flags = 0;
+        if constexpr (MODE == PM_DERIV) {
+            load_qv(L, q, v, inst, lane, false);                   // (plant_derivative sets P_VP itself)
+            WSYNC();
+            flags |= plant_derivative<true>(L, P, ibp, lane, tau, gnd);
+            double x = 0.0, xd = 0.0, xs = 0.0;
+            rk4_stage<0>(L, 0, lane, 0.0, P_SC + 52, x, xd, xs);   // the first stage leaves xdot itself in its sum: fma(1, xdot, 0 * 0)
+            if (__ballot(lane < 60 && !(fabs(xd) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
+            if (lane < 60) xdot[60 * (size_t)inst + lane] = xd;
+            if (contact) plant_store_contact(L, contact + (size_t)LMH_CONTACT_STRIDE * inst, lane);
+        } else {
+            double *st = state + (size_t)LMH_STATE_STRIDE * inst;
+            double x = (lane < 60) ? st[lane] : 0.0, t = st[90];
+            const double dt = P.dt;
+            plant_hold<true>(L, P, ibp, lane, tau, dt, n_substeps, x, flags, gnd);
+#pragma unroll 1
+            for (int sub = 0; sub < n_substeps; sub++) t += dt;    // Clock::step, Clock.hpp:11
+            if (lane < 60) st[lane] = x; else if (lane == 60) st[90] = t;
+        }
+        if (lane == 0 && flags_out) flags_out[inst] = flags;
+    }
+}
 #ifndef LMH_ROLLOUT_ONLY
 extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *q, const double *v, const double *x, const double *w, double *res, int32_t *flags, hipStream_t s)
 {
@@ -4854,9 +4936,15 @@ extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *
     else hipLaunchKernelGGL(lmh_terms_kernel<TM_FWDDYN>, grid, block, 0, s, *P, q, v, x, w, res, flags);
 }
 extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact, int32_t *flags,
-                                 int n_substeps, hipStream_t s)
+                                 int n_substeps, const double *ground, size_t ground_stride, hipStream_t s)
 {
     const dim3 grid(P->n_instances), block(64);
+    if (ground) {                                                  // a handle with a table: the GROUND instantiations; without one the kernels of before
+        if (mode == PM_CONTACT) hipLaunchKernelGGL(lmh_plant_ground_kernel<PM_CONTACT>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps, ground, ground_stride);
+        else if (mode == PM_DERIV) hipLaunchKernelGGL(lmh_plant_ground_kernel<PM_DERIV>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps, ground, ground_stride);
+        else hipLaunchKernelGGL(lmh_plant_ground_kernel<PM_STEP>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps, ground, ground_stride);
+        return;
+    }
     if (mode == PM_CONTACT) hipLaunchKernelGGL(lmh_plant_kernel<PM_CONTACT>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps);
     else if (mode == PM_DERIV) hipLaunchKernelGGL(lmh_plant_kernel<PM_DERIV>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps);
     else hipLaunchKernelGGL(lmh_plant_kernel<PM_STEP>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps);
@@ -5058,16 +5146,30 @@ __device__ __forceinline__ double zoh_io_actuate(double tau, const ZohIoJoint &J
     if (double *ap = zoh_io_args().io.applied) { if (jl) ap[((size_t)tick * LMH_KERNARG_PARAMS().n_instances + inst) * 24 + j] = y; }
     return jl ? y : tau;
 }
+// lmh_rollout_zoh_ground_kernel's arguments: lmh_rollout_zoh_io_kernel's, then the ground table (stride 0: one shared record)
+struct ZohGroundArgs { ZohIoArgs a; const double *ground; size_t ground_stride; };
+static_assert(sizeof(ZohIoArgs) % 8 == 0 && alignof(ZohGroundArgs) == 8, "ZohGroundArgs continues ZohIoArgs in the kernel-argument segment");
+typedef const __attribute__((address_space(4))) ZohGroundArgs CZohGroundArgs;
+__device__ __forceinline__ CZohGroundArgs &zoh_ground_args()
+{
+    CZohGroundArgs *p_ = (CZohGroundArgs *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(LmhDevParams));
+    asm volatile("" : "+s"(p_));
+    return *p_;
+}
 // MODE: where the momentum task's CoM reference comes from.  ZM_BOX (lmh_rollout_zoh_box_kernel): every control tick runs lmh_mpc_box_step at the
 // measured CoM state inside the evaluation's chain A (refs_chain_a); the preview Hessian is factored once, behind eval_begin, by the helper wave
 // alone (wave-scope fences: both waves pass the same joins as in the other modes) while wave 0 goes on to the pushes and the kinematics.
 enum { ZM_BUILTIN, ZM_REF, ZM_BOX };
 // IO (lmh_rollout_zoh_io_kernel; never with ZM_BOX): the measurement and the actuator of lmh_rollout_zoh_io, above
-template <int MODE, bool IO = false>
+// GROUND (lmh_rollout_zoh_ground_kernel; always with IO, whose options may all be off): the hold presses the soles against the robot's planes
+// of lmh_set_ground.  The record's address is formed from the kernel arguments in front of every hold and handed to plant_hold, whose eight
+// vertex lanes load their plane where they use it: nothing of it is carried across controller_eval.
+template <int MODE, bool IO = false, bool GROUND = false>
 __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
 {
     constexpr bool REF = MODE != ZM_BUILTIN, BOX = MODE == ZM_BOX;
     static_assert(!(IO && BOX), "lmh_rollout_zoh_io has no box-constrained form");
+    static_assert(IO || !GROUND, "the ground kernels are instantiations of the IO body");
     LmhCParams &P0 = LMH_KERNARG_PARAMS();
     typedef const __attribute__((address_space(4))) ZohExArgs CArgs;
     auto KA = [&]() -> CArgs & {
@@ -5160,6 +5262,8 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
                     const int rel = __builtin_amdgcn_readfirstlane(((const int *)(L + P_PUSH))[0]);
                     if (rel > done && rel < done + r) s = rel - done;
                 }
+                if constexpr (GROUND) plant_hold<true>(L, P, ib_pack(), lane, tau, dt, s, x, flags, zoh_ground_args().ground + zoh_ground_args().ground_stride * (size_t)inst);
+                else
                 plant_hold(L, P, ib_pack(), lane, tau, dt, s, x, flags);
                 done += s; r -= s;
                 if (r > 0) push_poll(L, P, inst, lane, done, lim, x);      // between two substeps: v += dv on the integrator's register
@@ -5210,10 +5314,28 @@ __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_wav
     (void)A_arg;
     lmh_rollout_zoh_ex_body<REF ? ZM_REF : ZM_BUILTIN, true>(L);
 }
+// lmh_rollout_zoh / _ref / _ex / _io on a handle with a ground table (lmh_set_ground): the IO body, which with no measurement and no actuator
+// leaves the bytes of the ex body and with no option those of lmh_rollout_zoh_kernel, with the GROUND hold
+template <bool REF>
+__global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) lmh_rollout_zoh_ground_kernel(LmhDevParams P_arg, ZohGroundArgs A_arg)
+{
+    __shared__ double L[LDS_DOUBLES];
+    (void)A_arg;
+    lmh_rollout_zoh_ex_body<REF ? ZM_REF : ZM_BUILTIN, true, true>(L);
+}
 // ex NULL: lmh_rollout_zoh's kernel exactly as it is when ref is NULL, otherwise lmh_rollout_zoh_ref's; with ex the kernel that takes the options
 extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
-                                       const LmhZohEx *ex, const LmhZohBox *bx, const LmhZohIo *io, hipStream_t s)
+                                       const LmhZohEx *ex, const LmhZohBox *bx, const LmhZohIo *io, const double *ground, size_t ground_stride, hipStream_t s)
 {
+    // ground: lmh_rollout_zoh_ground_kernel whatever the options (bx is then NULL: the host layer refuses the combination); ex or io NULL = none of theirs
+    if (ground) {
+        const LmhZohEx no_ex = {nullptr, nullptr, 0, 0, 0, 0};
+        const LmhZohIo no_io = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
+        const ZohGroundArgs a = {{{state, out, status, base_wrench, log, ref, ex ? *ex : no_ex, n_ticks, n_substeps}, io ? *io : no_io}, ground, ground_stride};
+        if (ref) hipLaunchKernelGGL(lmh_rollout_zoh_ground_kernel<true>, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, a);
+        else hipLaunchKernelGGL(lmh_rollout_zoh_ground_kernel<false>, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, a);
+        return;
+    }
     // io: lmh_rollout_zoh_io_kernel (ex is then never NULL and bx is)
     if (io) {
         const ZohIoArgs a = {{state, out, status, base_wrench, log, ref, *ex, n_ticks, n_substeps}, *io};

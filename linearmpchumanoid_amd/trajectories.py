@@ -8,7 +8,7 @@ definition on top of the reference's conventions (SupportFoot -> ZMP y of -/+0.0
 """
 import numpy as np
 
-from .capi import ACT_MAX_DELAY, ACT_MEM_STRIDE, ACT_OFF_ALPHA, ACT_OFF_DELAY, ACT_OFF_TAU_MAX, ACT_STRIDE, FLAG_BOX_EMPTY, FLAG_NONFINITE, FLAG_NOT_SPD, FLAG_QP_MAXITER, FLAG_ZMP_RANGE, IK_TARGET_STRIDE, LIP_STRIDE, MAX_PUSHES, MPC_BOX_MAX_ROUNDS, MPC_STRIDE, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE
+from .capi import ACT_MAX_DELAY, ACT_MEM_STRIDE, ACT_OFF_ALPHA, ACT_OFF_DELAY, ACT_OFF_TAU_MAX, ACT_STRIDE, FLAG_BOX_EMPTY, FLAG_NONFINITE, FLAG_NOT_SPD, FLAG_QP_MAXITER, FLAG_ZMP_RANGE, GROUND_OFF_H_L, GROUND_OFF_H_R, GROUND_OFF_N_L, GROUND_OFF_N_R, GROUND_STRIDE, IK_TARGET_STRIDE, LIP_STRIDE, MAX_PUSHES, MPC_BOX_MAX_ROUNDS, MPC_STRIDE, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE
 
 
 def stance_zmp(simulation_time, time_step, support_foot=2):
@@ -655,6 +655,62 @@ def actuator_step(record, mem, cmd):
     return y.reshape(lead + (24,)), limited.reshape(lead)
 
 
+def ground_planes(slope, azimuth, h_r=0.0, h_l=0.0):
+    """Ground records of lmh_set_ground for a common slope and per-foot offsets: slope (radians, |slope| < pi / 2) is the tilt of the ground
+    from the horizontal, azimuth (radians) the horizontal direction in which it RISES, h_r / h_l the offsets of the right and the left foot's
+    plane along the common normal (metres; different values are a ledge).  Scalars or arrays of one entry per robot, broadcast against each
+    other -> records [..., 8] = n | h_r | n | h_l with n = (-sin slope cos azimuth, -sin slope sin azimuth, cos slope).  ground_slope is
+    the way back."""
+    s, a, hr, hl = np.broadcast_arrays(*(np.asarray(x, dtype=np.float64) for x in (slope, azimuth, h_r, h_l)))
+    if not (np.abs(s) < 0.5 * np.pi).all():
+        raise ValueError("slope must be inside (-pi / 2, pi / 2): the normal points up")
+    n = np.stack([-np.sin(s) * np.cos(a), -np.sin(s) * np.sin(a), np.cos(s)], axis=-1)
+    rec = np.zeros(s.shape + (GROUND_STRIDE,))
+    rec[..., GROUND_OFF_N_R:GROUND_OFF_N_R + 3], rec[..., GROUND_OFF_H_R] = n, hr
+    rec[..., GROUND_OFF_N_L:GROUND_OFF_N_L + 3], rec[..., GROUND_OFF_H_L] = n, hl
+    return rec
+
+
+def ground_slope(records):
+    """(slope >= 0, azimuth, h_r, h_l) of the right foot's plane of records [..., 8]: ground_planes' arguments for a record it made with
+    slope >= 0 (the azimuth of a horizontal plane is 0)."""
+    rec = np.asarray(records, dtype=np.float64)
+    n = rec[..., GROUND_OFF_N_R:GROUND_OFF_N_R + 3]
+    hor = np.hypot(n[..., 0], n[..., 1])
+    return np.arctan2(hor, n[..., 2]), np.where(hor > 0.0, np.arctan2(-n[..., 1], -n[..., 0]), 0.0), rec[..., GROUND_OFF_H_R], rec[..., GROUND_OFF_H_L]
+
+
+GROUND_REGIMES = ("out", "stick", "slide", "lifted")
+
+
+def ground_contact(pos, vel, planes, k, d, dt, mu):
+    """Host statement of the contact model of lmh_set_ground (include/lmh.h): pos, vel [8,3] the world positions and velocities of the sole
+    vertices (foot-major, right foot first), planes [8] one ground record, k / d / dt / mu the robot's contact_k / contact_d / contact_dt /
+    contact_mu -> (f [8,3] the force at every vertex, regimes [8]): "out" of the ground (exactly 0) | "lifted" (penetrating, the normal
+    force clamped to 0: exactly 0 too) | "slide" (the tangential force scaled back onto the friction disc mu f_n) | "stick"."""
+    pos, vel, rec = np.asarray(pos, dtype=np.float64), np.asarray(vel, dtype=np.float64), np.asarray(planes, dtype=np.float64)
+    if pos.shape != (8, 3) or vel.shape != (8, 3) or rec.shape != (GROUND_STRIDE,):
+        raise ValueError("ground_contact takes pos [8,3], vel [8,3] and one ground record [8]")
+    f, regimes = np.zeros((8, 3)), []
+    for i in range(8):
+        off = GROUND_OFF_N_L if i >= 4 else GROUND_OFF_N_R
+        n, h = rec[off:off + 3], rec[off + 3]
+        pen = h - n @ pos[i]
+        vn = n @ vel[i]
+        fn = max(0.0, k * pen - d * vn)
+        ft = -dt * (vel[i] - vn * n)
+        mag = np.sqrt(ft @ ft)
+        slide = mag > mu * fn
+        if slide:
+            ft = ft * (mu * fn / mag)
+        if not pen > 0.0:
+            regimes.append("out"); continue
+        f[i] = ft + fn * n
+        regimes.append("lifted" if fn == 0.0 else "slide" if slide else "stick")
+    return f, regimes
+
+
 __all__ = ["stance_zmp", "find_poly_coeff", "foot_coeff_trajectory", "walk_plan", "jump_plan", "walk_plans", "jump_plans",
-           "push_schedule", "check_push_records", "draw_pushes", "zoh_hold_pieces", "actuator_records", "actuator_step", "preview_index", "lip_rollout", "com_targets",
+           "push_schedule", "check_push_records", "draw_pushes", "zoh_hold_pieces", "actuator_records", "actuator_step", "ground_planes", "ground_slope", "ground_contact",
+           "preview_index", "lip_rollout", "com_targets",
            "PHASE_DOUBLE", "PHASE_RIGHT", "PHASE_LEFT", "PHASE_FLIGHT"]

@@ -77,9 +77,10 @@ def write_lines(path, lines):
 # Each script times rows of launches of this build, interleaved, and -- with --parent-variant NAME and linearmpchumanoid_amd/
 # liblmh_hip_var_NAME.so in place (build.py) -- one launch on the parent's library in two child processes of itself, one before and one after
 # its own rows: the parent's pass-to-pass spread in this session, which the judged rows are held to.
-def zoh_rate_args(child_times, new_prototypes):
+def zoh_rate_args(child_times, new_prototypes, calls=None):
     """The scripts' arguments.  In a child (--child: time `child_times` on the library LMH_VARIANT selects) the prototypes of the entry
-    points the parent's library has not got are dropped; so call this before anything loads the library."""
+    points the parent's library has not got are dropped; so call this before anything loads the library.  calls: the names a script that
+    holds more than one call to the parent lets its child choose from (--call; parent_pass hands args.call on)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--instances", type=int, default=4096)
     ap.add_argument("--ticks", type=int, default=200)
@@ -89,6 +90,8 @@ def zoh_rate_args(child_times, new_prototypes):
     ap.add_argument("--parent-variant", default=None)
     ap.add_argument("--child", action="store_true", help="(internal) time %s on the library LMH_VARIANT selects and print one JSON line" % child_times)
     ap.add_argument("--out", default=None)
+    if calls:
+        ap.add_argument("--call", choices=calls, default=calls[0], help="(internal) the call a child times")
     args = ap.parse_args()
     if args.child:
         from linearmpchumanoid_amd import capi
@@ -117,12 +120,12 @@ def have_parent(args):
     return bool(args.parent_variant) and os.path.exists(os.path.join(ROOT, "linearmpchumanoid_amd", "liblmh_hip_var_%s.so" % args.parent_variant))
 
 
-def parent_pass(args):
-    """One child of this script on the parent's library -> {str(n_substeps): times}"""
+def parent_pass(args, variant=None):
+    """One child of this script on the parent's library (variant "": on this build's, timed the way the parent is) -> {str(n_substeps): times}"""
     env = {k: val for k, val in os.environ.items() if k != "LMH_DIAG"}
-    env["LMH_VARIANT"] = args.parent_variant
+    env["LMH_VARIANT"] = args.parent_variant if variant is None else variant
     r = subprocess.run([sys.executable, os.path.abspath(sys.argv[0]), "--child", "--instances", str(args.instances), "--ticks", str(args.ticks), "--steps", str(args.steps),
-                        "--warmup", str(args.warmup), "--substeps", *map(str, args.substeps)], env=env, cwd=ROOT, capture_output=True, text=True)
+                        "--warmup", str(args.warmup), "--substeps", *map(str, args.substeps), *(["--call", args.call] if getattr(args, "call", None) else [])], env=env, cwd=ROOT, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     return json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])["times"]
 

@@ -1,0 +1,123 @@
+"""Shared cases of the ground-plane tests (test_ground.py on the CPU, test_gpu_ground.py on the GPU): the 16 states of
+plant_step_cases.contact_states() with a tilted plane under each foot, placed so that a chosen vertex of a chosen foot sits in the middle of a
+chosen regime of the contact model of lmh_set_ground.  Everything here is computed with the CPU oracle's kinematics and the numpy statement
+trajectories.ground_contact; results are cached per process and never written by a test."""
+import numpy as np
+
+from linearmpchumanoid_amd import trajectories
+from plant_step_cases import GROUND, REGIMES, contact_states, euler_rate_matrix, make_oracle, rk4_tick, vertex_kinematics
+
+FORCE_SCALE = GROUND["k"] * 2.0e-3           # the stick depth's normal force, 40 N: what the force tolerances are relative to
+FLAT = np.array([0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0])
+
+_cache = {}
+
+
+def tilted_normal(rng):
+    """A unit normal tilted 2 .. 6 degrees from the vertical about a random horizontal axis."""
+    ang, ax = np.deg2rad(rng.uniform(2.0, 6.0)), rng.uniform(0.0, 2.0 * np.pi)
+    # Rodrigues about (cos ax, sin ax, 0) applied to e_z
+    return np.array([np.sin(ang) * np.sin(ax), -np.sin(ang) * np.cos(ax), np.cos(ang)])
+
+
+def thresholds(pos, vel, planes, g=GROUND):
+    """Per vertex: pen, and for a penetrating vertex the relative margins from the model's two thresholds -- fn = 0 (k pen against d vn)
+    and, where fn > 0, the friction disc (c_t |vt| against mu fn); inf where a threshold does not apply."""
+    pen, m_fn, m_disc = np.zeros(8), np.full(8, np.inf), np.full(8, np.inf)
+    for i in range(8):
+        n, h = planes[4 * (i // 4):4 * (i // 4) + 3], planes[4 * (i // 4) + 3]
+        pen[i] = h - n @ pos[i]
+        if not pen[i] > 0.0:
+            continue
+        vn = n @ vel[i]
+        a, b = g["k"] * pen[i], g["d"] * vn
+        m_fn[i] = abs(a - b) / max(abs(a), abs(b))
+        if a - b > 0.0:
+            raw, lim = g["dt"] * np.linalg.norm(vel[i] - vn * n), g["mu"] * (a - b)
+            m_disc[i] = abs(raw - lim) / max(raw, lim)
+    return pen, m_fn, m_disc
+
+
+def sole_origins(o):
+    """World positions [2,3] of the sole origins (right, left) of the state the oracle evaluated last."""
+    T = o.terms()["T"]
+    return np.array([T[7][:3, 3], T[14][:3, 3]])
+
+
+def wrench(pos, origins, f):
+    """The contact wrench [12] = n_R f_R n_L f_L about the sole origins, world axes, of vertex forces f [8,3] at pos [8,3]."""
+    w = np.zeros(12)
+    for i in range(8):
+        ft = i // 4
+        w[6 * ft:6 * ft + 3] += np.cross(pos[i] - origins[ft], f[i])
+        w[6 * ft + 3:6 * ft + 6] += f[i]
+    return w
+
+
+def ground_plant_xdot(o, q, v, tau30, planes, g=GROUND):
+    """plant_step_cases.oracle_plant_xdot with the contact wrench taken from the statement on `planes` [8] instead of Oracle.contact():
+    the terms at the one velocity v, a = solve(M, tau30 + J'w - C), the base rows back through X[0], qdot as the oracle maps it.
+    Returns (xdot [60], dict(w, vf, terms, a, pos, vel))."""
+    q, v = np.asarray(q, dtype=np.float64), np.asarray(v, dtype=np.float64)
+    pos, vel = vertex_kinematics(o, q, v)                          # (sets Robot::v_ to v and evaluates)
+    tm = o.terms()
+    vf, _ = trajectories.ground_contact(pos, vel, planes, g["k"], g["d"], g["dt"], g["mu"])
+    w = wrench(pos, sole_origins(o), vf)
+    a = np.linalg.solve(tm["M"], np.asarray(tau30, dtype=np.float64) + tm["J"].T @ w - tm["C"])
+    sol = np.linalg.solve(tm["X"][0], a[:6])
+    qdot = v.copy()
+    qdot[0:3] += np.cross(v[3:6], q[0:3])
+    qdot[3:6] = euler_rate_matrix(q[3:6]) @ v[3:6]
+    return np.concatenate([qdot, sol[3:6], sol[0:3], a[6:]]), dict(w=w, vf=vf, terms=tm, a=a, pos=pos, vel=vel)
+
+
+def ground_plant_steps(o, x, tau30, planes, n, dt):
+    """n RK4 substeps of ground_plant_xdot with the torques held."""
+    x = np.asarray(x, dtype=np.float64).copy()
+    for _ in range(n):
+        x = rk4_tick(x, dt, lambda stage, s: ground_plant_xdot(o, s[:30], s[30:], tau30, planes)[0])
+    return x
+
+
+def tilted_states():
+    """dict(q, v, tau [16,30] of contact_states(), planes [16,8], pos, vel [16,8,3] the oracle's vertex kinematics, force [16,8,3] and
+    regimes [16][8] of the statement, origin [16,2,3] the sole origins, w [16,12] the statement's contact wrench, aimed [16] = (foot, vertex, regime)).  State i: rng = default_rng(20261020 + i); per foot a normal
+    tilted 2 .. 6 degrees about a random horizontal axis; foot i % 2 is aimed at regime REGIMES[(i // 2) % 4] by h = n.x_j + depth for its
+    vertex j with depth in the middle of the regime's band; the other foot gets the stick depth under its lowest vertex."""
+    if _cache:
+        return _cache
+    cs = contact_states()
+    o, g = make_oracle(), GROUND
+    planes, poss, vels, forces, regimes, aimed, origins, ws = [], [], [], [], [], [], [], []
+    for i in range(len(cs["q"])):
+        rng = np.random.default_rng(20261020 + i)
+        normals = [tilted_normal(rng), tilted_normal(rng)]
+        pos, vel = vertex_kinematics(o, cs["q"][i], cs["v"][i])
+        origins.append(sole_origins(o))
+        foot, want = i % 2, REGIMES[(i // 2) % 4]
+        rec = np.zeros(8)
+        for f in range(2):
+            n, mine = normals[f], range(4 * f, 4 * f + 4)
+            vn = {j: n @ vel[j] for j in mine}
+            vt = {j: np.linalg.norm(vel[j] - vn[j] * n) for j in mine}
+            lowest = min(mine, key=lambda j: n @ pos[j])
+            w = want if f == foot else "stick"
+            if w == "out":
+                j, depth = lowest, -1.0e-3
+            elif w == "stick":
+                j, depth = lowest, 2.0e-3
+            elif w == "slide":                                     # mu fn = half the unclamped tangential force
+                j = [j for j in mine if 0.5 * g["dt"] * vt[j] / g["mu"] + g["d"] * vn[j] > 0.0][0]
+                depth = (0.5 * g["dt"] * vt[j] / g["mu"] + g["d"] * vn[j]) / g["k"]
+            else:                                                  # k depth = half of d vn
+                j = [j for j in mine if vn[j] > 0.0][0]
+                depth = 0.5 * g["d"] * vn[j] / g["k"]
+            rec[4 * f:4 * f + 3], rec[4 * f + 3] = n, n @ pos[j] + depth
+            if f == foot:
+                aimed.append((foot, j, want))
+        fv, rg = trajectories.ground_contact(pos, vel, rec, g["k"], g["d"], g["dt"], g["mu"])
+        ws.append(wrench(pos, origins[-1], fv))
+        planes.append(rec); poss.append(pos); vels.append(vel); forces.append(fv); regimes.append(rg)
+    _cache.update(q=cs["q"], v=cs["v"], tau=cs["tau"], planes=np.array(planes), pos=np.array(poss), vel=np.array(vels), force=np.array(forces),
+                  regimes=regimes, aimed=aimed, origin=np.array(origins), w=np.array(ws), zcom=cs["zcom"], q0=cs["q0"])
+    return _cache
