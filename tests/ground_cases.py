@@ -13,9 +13,9 @@ FLAT = np.array([0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0])
 _cache = {}
 
 
-def tilted_normal(rng):
-    """A unit normal tilted 2 .. 6 degrees from the vertical about a random horizontal axis."""
-    ang, ax = np.deg2rad(rng.uniform(2.0, 6.0)), rng.uniform(0.0, 2.0 * np.pi)
+def tilted_normal(rng, lo=2.0, hi=6.0):
+    """A unit normal tilted lo .. hi (2 .. 6) degrees from the vertical about a random horizontal axis."""
+    ang, ax = np.deg2rad(rng.uniform(lo, hi)), rng.uniform(0.0, 2.0 * np.pi)
     # Rodrigues about (cos ax, sin ax, 0) applied to e_z
     return np.array([np.sin(ang) * np.sin(ax), -np.sin(ang) * np.cos(ax), np.cos(ang)])
 

@@ -1,7 +1,8 @@
 """Shared cases of the torque-driven plant tests (test_plant_step.py on the CPU, test_gpu_plant_step.py on the GPU).
 
 Everything here is computed with the CPU oracle alone: the helper oracle_plant_xdot restates lmh_plant_derivative from Oracle.eval / terms /
-contact, and contact_states draws the 16 input states around touch-down.  Results are cached per process and never written by a test."""
+contact, and contact_states draws the 16 input states around touch-down.  Results are cached per process and never written by a test.
+fall_cases.py draws the rest of the range: the postures, tilts and velocities of a fall."""
 import numpy as np
 
 from helpers import oracle_system, posture_sweep
@@ -62,11 +63,8 @@ def oracle_plant_steps(o, x, tau30, n, dt=DT):
     return x
 
 
-def vertex_kinematics(o, q, v):
-    """World position [8,3] and velocity [8,3] of the sole vertices (foot-major) from the oracle's transforms and Jacobian."""
-    o.set_prev_velocity(v)
-    o.eval(q, v, 0.0)
-    tm = o.terms()
+def vertex_kinematics_of(tm, v):
+    """vertex_kinematics from the terms `tm` of an evaluation at (q, v) that has already run."""
     vhat = np.asarray(v, dtype=np.float64).copy()
     X0 = tm["X"][0]
     vhat[:6] = X0 @ np.concatenate([v[3:6], v[0:3]])                # swapBaseVelocityAndRefToWorldFrame
@@ -79,6 +77,13 @@ def vertex_kinematics(o, q, v):
             pos[4 * f + vi] = rp + T[:3, 3]
             vel[4 * f + vi] = twist[6 * f + 3:6 * f + 6] + np.cross(twist[6 * f:6 * f + 3], rp)
     return pos, vel
+
+
+def vertex_kinematics(o, q, v):
+    """World position [8,3] and velocity [8,3] of the sole vertices (foot-major) from the oracle's transforms and Jacobian."""
+    o.set_prev_velocity(v)
+    o.eval(q, v, 0.0)
+    return vertex_kinematics_of(o.terms(), v)
 
 
 def classify(pos, vel, vf, g=GROUND):
