@@ -833,6 +833,84 @@ typedef struct lmh_zoh_io {
 int lmh_rollout_zoh_io(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts,
                        const lmh_zoh_io *io, int n_ticks, int n_substeps, void *stream);
 
+/* ---- Joint servo inside the hold (build-defined; lmh_set_servo, a table of the handle like the actuator records): what a torque-controlled
+ * humanoid has between its whole-body controller and its motors.  It runs at the plant's rate, not the controller's: a feed-forward torque
+ * plus a per-joint PD law on a setpoint, re-formed at every derivative evaluation of the hold -- all four RK4 stages of every substep.
+ * records: HOST [n_sets][LMH_SERVO_STRIDE], n_sets = 1 (one record for every robot) or n_instances; NULL or n_sets = 0 clears the table.
+ * One record is KP[24] (N m / rad) | KD[24] (N m s / rad), a gain per joint.  CHECKS, each LMH_ERR_BAD_ARG naming the first offending robot
+ * ("robot 7: ..."): every word finite and >= 0; n_sets 1 or n_instances.  lmh_set_refs' rule: check first, build aside, replace in one
+ * step -- a refused or failed call leaves the previous table in place.  The table is a device buffer of its own (384 B per robot): the
+ * parameter blocks of lmh_set_params are not rebuilt, and no call but the two below reads it -- lmh_eval*, lmh_rollout*, lmh_plant_step and
+ * lmh_rollout_zoh, _ref, _ex, _io and _box are bit for bit what they are without it.  lmh_get_servo: robot `inst`'s record (the shared one
+ * on a shared table; zeros on a handle without one).
+ * THE SERVO'S TORQUE.  At a stage whose state is (q, v), row 6 + j of the tau30 the derivative uses is
+ *         tau30[6+j] + ((kp_j * (q_des_j - q[6+j])) + (kd_j * (v_des_j - v[6+j])))
+ * in this order: the two differences, the two products, their sum, then the sum with the feed-forward torque, each rounded by itself, no
+ * fused multiply-add (numpy's expression gives the same bits; trajectories.servo_torque).  Rows 0..5, the wrench on the base, are untouched.
+ * Zero gains add +0 to the feed-forward torque.  The device has ONE copy of the expression, used by both calls below.
+ *
+ * lmh_plant_step_servo: lmh_plant_step with that torque.  d_setpoint: DEVICE [B][LMH_SETPOINT_STRIDE], Q_DES[24] | V_DES[24], held for the
+ * launch; required (NULL: LMH_ERR_BAD_ARG).  Everything else is lmh_plant_step's, word for word: t advances and v_prev stays, the flags,
+ * (a + b) equals (a) followed by (b) bit for bit, n_substeps = 0 enqueues nothing, the contact-constant checks on a plant = 0 handle, per-robot
+ * models and lmh_set_params contact constants, and the ground table of lmh_set_ground is honoured.  A handle without a servo table runs with
+ * zero gains.  A NaN setpoint word of a joint with a gain makes that robot's state non-finite (LMH_FLAG_NONFINITE) and disturbs no other.
+ *
+ * lmh_rollout_zoh_servo.  DEFINITION.  For every robot the call leaves, bit for bit, what lmh_rollout_zoh_io's host loop (above) leaves with
+ * every lmh_plant_step(s substeps) of a hold replaced by lmh_plant_step_servo(s substeps, setpoint_j):
+ *         [the push due at the tick's start;  scratch, the measurement, lmh_eval / lmh_eval_ref on scratch -> out, status;  v_prev;  the
+ *          actuator -> y;  d_applied[j][i] = y:  all as in lmh_rollout_zoh_io]
+ *         setpoint_j = d_setpoint[j][i]                               LMH_SERVO_CALLER
+ *         setpoint_j = (q_des | v_des) of                             LMH_SERVO_INTEGRATE
+ *             q_m = scratch[6:30], v_m = scratch[36:60]               the joint words the evaluation READ: with d_meas the measured ones
+ *             a   = out[42:66]                                        the joint rows of out.qdd of this tick's evaluation
+ *             T   = (double)n_substeps * dt;   h2 = (0.5 * T) * T
+ *             v_des = v_m + (T * a)
+ *             q_des = (q_m + (T * v_m)) + (h2 * a)                    every product and sum rounded by itself, no fused multiply-add
+ *                                                                     (numpy's expressions give the same bits; trajectories.servo_setpoint)
+ *         tau30 = [ wrench (6) | y (24) ]
+ *         for every piece of the hold (s substeps; the pushes inside the hold between the pieces, as in lmh_rollout_zoh_ex):
+ *             lmh_plant_step_servo(state, tau30, setpoint_j, s)       the same setpoint serves every piece of control tick j's hold
+ *         [the sample and the fold: lmh_rollout_zoh_ex's, on the TRUE state]
+ * LMH_SERVO_INTEGRATE holds as the servo's target the state the controller's own acceleration reaches at the end of the control period.
+ * Consequences.  The setpoint is not sent through the actuator's delay queue.  d_applied and d_log stay what they are, the feed-forward and
+ * the commanded torques: the PD part changes at every stage and is not recorded.  The trace, the metrics fold, the status words and (a + b) =
+ * (a) then (b) are lmh_rollout_zoh_io's; for (a + b), d_setpoint is advanced by a records per robot and d_act_mem is handed on.  The ground
+ * table is honoured.  LMH_PRECISION_FP64 handles only; the call takes no launch slot, writes nothing into the handle and is capturable into
+ * a hipGraph as the first call on a fresh handle.
+ * servo == NULL or mode == 0 is lmh_rollout_zoh_io(h, ..., opts, io, ...) exactly: the same kernel is launched.  The box-constrained loop
+ * (lmh_rollout_zoh_box) is NOT offered with a servo.
+ * Refusals, each LMH_ERR_BAD_ARG before anything is enqueued and with a message of its own: a mode outside its values; a non-zero reserved;
+ * LMH_SERVO_CALLER without d_setpoint; d_setpoint with another mode; LMH_SERVO_INTEGRATE with n_substeps == 0; every refusal of
+ * lmh_rollout_zoh_io.
+ * Cost (one MI355X, 4096 standing robots x 200 control ticks, a record per robot; scripts/servo_rate.py; other batch
+ * sizes not measured): lmh_plant_step_servo 36.55 against lmh_plant_step's 36.48 ms (+0.2 %) at 200 x 1 substeps and 360.3 against 359.3 ms
+ * (+0.3 %) at 200 x 10; lmh_rollout_zoh_servo against the same call with mode 0 (62.45 ms): LMH_SERVO_INTEGRATE 63.59 ms (+1.8 %),
+ * LMH_SERVO_CALLER 63.13 ms (+1.1 %) at n_substeps = 1, and 479.0 / 478.9 against 469.9 ms (+1.9 %) at 10, where single launches spread
+ * by 4 %.  Without a servo lmh_plant_step and lmh_rollout_zoh_io run at the parent commit's rate: their kernels are the parent's,
+ * instruction for instruction.
+ * What the servo does to the closed loop (scripts/servo_sweep.py, profiles/r32_servo_sweep.txt): on flat ground, from rest, with the
+ * controller's default gains and LMH_SERVO_INTEGRATE, NO cell of a 16 x 15 grid of gains (kp_j = a m_j / dt^2, a = 0 and 1e-4 .. 1;
+ * kd_j = b m_j / dt, b = 0 and 1e-3 .. 2.5; m_j the joint's own inertia) keeps a robot up for 2000 control ticks, at n_substeps = 1 or
+ * 10.  Damping delays the fall -- from control tick 1655 without a servo to 1889 at best (a = 0.072, b = 0.75) at n_substeps = 1, from 165
+ * to 248 at 10 -- and stiffness above a = 0.02 or damping above b = 1 brings it forward.  The zero-order-hold loop still does not stand. */
+#define LMH_SERVO_STRIDE 48        /* one servo record (doubles) */
+#define LMH_SERVO_OFF_KP 0         /* [24] proportional gain per joint, N m / rad, finite and >= 0 */
+#define LMH_SERVO_OFF_KD 24        /* [24] derivative gain per joint, N m s / rad, finite and >= 0 */
+#define LMH_SETPOINT_STRIDE 48     /* one setpoint record (doubles): Q_DES[24] | V_DES[24] */
+#define LMH_SERVO_INTEGRATE 1      /* lmh_zoh_servo.mode: the setpoint integrated from the evaluation's own acceleration */
+#define LMH_SERVO_CALLER 2         /* lmh_zoh_servo.mode: the caller's setpoints, one record per control tick and robot */
+int lmh_set_servo(lmh_handle *h, const double *records, int n_sets);
+int lmh_servo_per_instance(const lmh_handle *h);          /* 0: none or one shared record, 1: one record per robot */
+int lmh_get_servo(lmh_handle *h, int inst, double *record);
+int lmh_plant_step_servo(lmh_handle *h, double *d_state, const double *d_tau30, const double *d_setpoint, int n_substeps, int32_t *d_flags, void *stream);
+typedef struct lmh_zoh_servo {
+    const double *d_setpoint;     /* DEVICE [n_ticks][B][LMH_SETPOINT_STRIDE] with mode LMH_SERVO_CALLER, else NULL */
+    int32_t mode;                 /* 0 off | LMH_SERVO_INTEGRATE 1 | LMH_SERVO_CALLER 2 */
+    int32_t reserved;             /* must be 0 */
+} lmh_zoh_servo;
+int lmh_rollout_zoh_servo(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts,
+                          const lmh_zoh_io *io, const lmh_zoh_servo *servo, int n_ticks, int n_substeps, void *stream);
+
 /* ---- LIPM preview MPC for a batch of reduced states (one kernel family of its own, one wave per robot, fp64): the stage of the controller
  * that lmh_eval runs between the momentum and the PD law, as calls of its own.
  * replaces: Mpc3dLip::compute (src/mpcLinearPendulum.cpp:78-109) for every robot of the handle, at that robot's own clock.

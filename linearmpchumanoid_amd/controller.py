@@ -288,6 +288,29 @@ class BatchedController:
             mem[:] = t0.to(self.device, torch.float64).expand(self.B, 24).repeat(1, 1 + capi.ACT_MAX_DELAY)
         return mem
 
+    # -- per-robot joint servo of plant_step_servo and rollout_zoh_servo (include/lmh.h, lmh_set_servo)
+    def set_servo(self, kp=None, kd=None):
+        """lmh_set_servo: the per-joint PD gains the joint servo adds to the feed-forward torque inside every hold of plant_step_servo and
+        rollout_zoh_servo.  kp (N m / rad) and kd (N m s / rad) are scalars, [24] or [B,24], finite and >= 0 (None: 0);
+        trajectories.servo_records forms the records (and refuses what the library refuses, in the same words).  No other call reads the
+        table.  With no argument the table is cleared."""
+        if kp is None and kd is None:
+            check(capi.lib().lmh_set_servo(self._h, None, 0))
+            return
+        rec = np.ascontiguousarray(trajectories.servo_records(self.B, 0.0 if kp is None else kp, 0.0 if kd is None else kd))
+        check(capi.lib().lmh_set_servo(self._h, _np_ptr(rec), self.B))
+
+    @property
+    def servo_per_instance(self):
+        """True while every robot has a servo record of its own."""
+        return bool(capi.lib().lmh_servo_per_instance(self._h))
+
+    def get_servo(self, i):
+        """Robot i's servo record: dict(kp [24], kd [24]); zeros on a handle without records."""
+        rec = np.zeros(capi.SERVO_STRIDE)
+        check(capi.lib().lmh_get_servo(self._h, int(i), _np_ptr(rec)))
+        return dict(kp=rec[0:24].copy(), kd=rec[24:48].copy())
+
     # -- per-robot ground planes under the soles (include/lmh.h, lmh_set_ground)
     def set_ground(self, records=None):
         """lmh_set_ground: the plane under each foot that the plant calls (contact_wrench, plant_derivative, plant_step) and rollout_zoh,
@@ -603,6 +626,19 @@ class BatchedController:
         check(capi.lib().lmh_plant_step(self._h, _dev_ptr(state), _dev_ptr(tau), int(n_substeps), _dev_ptr(flags), self._stream()))
         return state, flags
 
+    def plant_step_servo(self, state, setpoint, tau=None, n_substeps=1):
+        """lmh_plant_step_servo: plant_step with the joint servo of set_servo re-forming the joint torques at every RK4 stage -- row 6 + j
+        of tau becomes tau + (kp_j (q_des_j - q_j) + kd_j (v_des_j - v_j)) at the stage's own q and v (trajectories.servo_torque).
+        setpoint [B,48] = q_des[24] | v_des[24], held for the launch; tau [B,30] the feed-forward torques (None: zero).  A handle without
+        a servo table runs with zero gains.  -> (state, flags [B] int32, OR-ed over the substeps)."""
+        tau, state = self._batch("tau", tau, 30, optional=True), self._batch("state", state, capi.STATE_STRIDE, in_place=True)
+        setpoint = self._batch("setpoint", setpoint, capi.SETPOINT_STRIDE)
+        if int(n_substeps) != n_substeps or n_substeps < 0:
+            raise ValueError("n_substeps must be a whole number >= 0")
+        flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+        check(capi.lib().lmh_plant_step_servo(self._h, _dev_ptr(state), _dev_ptr(tau), _dev_ptr(setpoint), int(n_substeps), _dev_ptr(flags), self._stream()))
+        return state, flags
+
     def rollout_zoh(self, state, n_ticks, n_substeps, base_wrench=None, log=False, out=None, status=None, ref=None):
         """lmh_rollout_zoh: n_ticks rounds of { stand_step ; plant_step([base_wrench | out.tau], n_substeps) } in one launch, bit for bit
         what that loop leaves; state [B,96] is updated in place.  The control period is n_substeps * cfg.dt.  base_wrench [B,6]: an external
@@ -664,7 +700,34 @@ class BatchedController:
         res["mpc"] = tr
         return res
 
-    def rollout_zoh_io(self, state, n_ticks, n_substeps, meas=None, actuators=False, act_mem=None, applied=False, **ex):
+    def rollout_zoh_servo(self, state, n_ticks, n_substeps, servo="integrate", **io):
+        """lmh_rollout_zoh_servo: rollout_zoh_io (whose keywords it takes as they are) with the joint servo of set_servo inside every hold
+        -- bit for bit that call's host loop with plant_step_servo in the place of plant_step.  servo="integrate": the setpoint of a
+        control tick is where the evaluation's own joint accelerations take the joints it read by the end of the control period
+        (trajectories.servo_setpoint; needs n_substeps > 0); a tensor [n_ticks,B,48]: the caller's setpoint for every control tick and
+        robot; None: no servo, rollout_zoh_io's launch.  log and applied keep the commanded and the feed-forward torques: the PD part
+        changes at every RK4 stage and is not recorded.  -> rollout_zoh_io's dict."""
+        if int(n_ticks) != n_ticks or n_ticks < 0:
+            raise ValueError("n_ticks must be a whole number >= 0")
+        n = int(n_ticks)
+        if servo is None:
+            sv = capi.LmhZohServo(d_setpoint=None, mode=0, reserved=0)
+        elif isinstance(servo, str):
+            if servo != "integrate":
+                raise ValueError('servo must be "integrate", a setpoint tensor [n_ticks,B,48] or None')
+            sv = capi.LmhZohServo(d_setpoint=None, mode=capi.SERVO_INTEGRATE, reserved=0)
+        else:
+            sp = servo
+            if isinstance(sp, np.ndarray) and sp.dtype == np.float64:
+                sp = torch.from_numpy(np.ascontiguousarray(sp)).to(self.device)
+            if not isinstance(sp, torch.Tensor) or sp.dtype != torch.float64 or sp.device != self.device or tuple(sp.shape) != (n, self.B, capi.SETPOINT_STRIDE) \
+                    or not sp.is_contiguous():
+                raise ValueError(f"servo must be a contiguous [{n},{self.B},{capi.SETPOINT_STRIDE}] float64 tensor on {self.device}")
+            keep = sp if sp.numel() > 0 else torch.empty((1,), dtype=torch.float64, device=self.device)
+            sv = capi.LmhZohServo(d_setpoint=_dev_ptr(keep), mode=capi.SERVO_CALLER, reserved=0)
+        return self.rollout_zoh_io(state, n, n_substeps, _servo_call=sv, **io)
+
+    def rollout_zoh_io(self, state, n_ticks, n_substeps, meas=None, actuators=False, act_mem=None, applied=False, _servo_call=None, **ex):
         """lmh_rollout_zoh_io: rollout_zoh_ex (whose keywords it takes as they are) with sensing and actuation between controller and plant.
         meas [n_ticks,B,60]: what is added to q | v as control tick j's evaluation sees them (the plant goes on from the true state; v_prev
         keeps the measured v).  actuators=True: the set_actuators records -- latency, torque limit, first-order lag -- stand between the
@@ -698,13 +761,13 @@ class BatchedController:
             raise TypeError(f"rollout_zoh_io: unexpected keyword {sorted(set(ex) - set(kw))[0]!r}")
         kw.update(ex)
         res = self._rollout_zoh_opts(state, n_ticks, n_substeps, kw["base_wrench"], kw["ref"], kw["pushes"], kw["log"], kw["trace_every"], kw["trace"],
-                                     kw["metrics"], kw["out"], kw["status"], None, io_call=io)
+                                     kw["metrics"], kw["out"], kw["status"], None, io_call=io, servo_call=_servo_call)
         res["applied"] = ap
         return res
 
-    def _rollout_zoh_opts(self, state, n_ticks, n_substeps, base_wrench, ref, pushes, log, trace_every, trace, metrics, out, status, box_call, io_call=None):
+    def _rollout_zoh_opts(self, state, n_ticks, n_substeps, base_wrench, ref, pushes, log, trace_every, trace, metrics, out, status, box_call, io_call=None, servo_call=None):
         """The argument handling rollout_zoh_ex, rollout_zoh_box and rollout_zoh_io share; box_call: None, or lmh_rollout_zoh_box's (d_box, n_samples,
-        n_sets, d_mpc); io_call: None, or lmh_rollout_zoh_io's record."""
+        n_sets, d_mpc); io_call: None, or lmh_rollout_zoh_io's record; servo_call: None, or lmh_rollout_zoh_servo's record (then with io_call)."""
         state = self._batch("state", state, capi.STATE_STRIDE, in_place=True)
         for name, n in (("n_ticks", n_ticks), ("n_substeps", n_substeps), ("trace_every", trace_every)):
             if int(n) != n or n < 0:
@@ -741,7 +804,10 @@ class BatchedController:
         metrics = self._batch("metrics", metrics, capi.METRICS_STRIDE, optional=True, in_place=True)
         opts = capi.LmhZohOpts(d_base_wrench=_dev_ptr(bw), d_ref=_dev_ptr(ref), d_log=_dev_ptr(lg), d_trace=_dev_ptr(tr_arg), d_metrics=_dev_ptr(metrics),
                                trace_every=trace_every, wrench_per_tick=int(per_tick), pushes=int(bool(pushes)), reserved=0)
-        if io_call is not None:
+        if servo_call is not None:
+            check(capi.lib().lmh_rollout_zoh_servo(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), C.byref(io_call), C.byref(servo_call),
+                                                   n_ticks, n_substeps, self._stream()))
+        elif io_call is not None:
             check(capi.lib().lmh_rollout_zoh_io(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), C.byref(io_call), n_ticks, n_substeps,
                                                 self._stream()))
         elif box_call is None:

@@ -68,6 +68,12 @@ struct lmh_handle {
     size_t ground_stride() const { return (n_ground_sets > 1) ? (size_t)LMH_GROUND_STRIDE : 0; }
     std::vector<double> h_act;
     int n_act_sets = 0;
+    // Servo records (lmh_set_servo): [n_servo_sets][LMH_SERVO_STRIDE] on the device and on the host (what lmh_get_servo returns); empty while
+    // n_servo_sets = 0.  Read by lmh_plant_step_servo and lmh_rollout_zoh_servo alone, through their kernel arguments: no part of the parameter block.
+    DevBuf<double> d_servo;
+    std::vector<double> h_servo;
+    int n_servo_sets = 0;
+    size_t servo_stride() const { return (n_servo_sets > 1) ? (size_t)LMH_SERVO_STRIDE : 0; }
     // Per-robot parameters (lmh_set_params): the records, one friction table per robot and the table of whole parameter blocks the controller
     // kernels select from.  All empty while the handle runs on its config's one set.  The block table is rebuilt by fill_params, i.e. by
     // every setter that moves a pointer or a stride, and replaces the previous one in one step.
@@ -463,7 +469,7 @@ extern "C" int lmh_create(const lmh_config *cfg, int n_instances, int device, lm
     {                                                               // lmh_rollout_zoh_box's dynamic LDS: asked for here, never inside the (capturable) call
         int32_t answer = -1;
         const LmhZohBox prep = {nullptr, 0, nullptr, 0.0, 0.0, 1, &answer};
-        lmh_launch_rollout_zoh(&h->P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &prep, nullptr, nullptr, 0, nullptr);
+        lmh_launch_rollout_zoh(&h->P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &prep, nullptr, nullptr, 0, nullptr, nullptr);
         h->zoh_box_prepared = answer;
     }
     (void)hipGetLastError();                                        // an answer other than hipSuccess is that call's to report, not a sticky error of this one
@@ -700,6 +706,48 @@ extern "C" int lmh_get_actuators(lmh_handle *h, int inst, double *record)
         return LMH_OK;
     }
     std::memcpy(record, h->h_act.data() + (size_t)LMH_ACT_STRIDE * ((h->n_act_sets > 1) ? inst : 0), sizeof(double) * LMH_ACT_STRIDE);
+    return LMH_OK;
+}
+
+// ---------------------------------------------------------------------------- servo records (lmh_plant_step_servo, lmh_rollout_zoh_servo)
+// the rules of one record: nullptr = fine.  trajectories.servo_records states the same rule with the same words.
+static const char *servo_record_error(const double *rec)
+{
+    for (int j = 0; j < LMH_SERVO_STRIDE; j++) if (!std::isfinite(rec[j]) || !(rec[j] >= 0.0)) return "servo gains must be finite and >= 0";
+    return nullptr;
+}
+
+extern "C" int lmh_set_servo(lmh_handle *h, const double *records, int n_sets)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    if (n_sets < 0) return fail(LMH_ERR_BAD_ARG, "n_sets must be >= 0");
+    if (!records) n_sets = 0;
+    if (n_sets != 0 && n_sets != 1 && n_sets != h->B) return fail(LMH_ERR_BAD_ARG, "lmh_set_servo: n_sets must be 1 or n_instances");
+    for (int i = 0; i < n_sets; i++)
+        if (const char *msg = servo_record_error(records + (size_t)LMH_SERVO_STRIDE * i)) return fail(LMH_ERR_BAD_ARG, robot_msg(i, msg));
+    HIPCHK(hipSetDevice(h->device));
+    DevBuf<double> d;
+    std::vector<double> host;
+    if (n_sets > 0) {
+        host.assign(records, records + (size_t)LMH_SERVO_STRIDE * n_sets);
+        HIPCHK(d.upload(records, (size_t)LMH_SERVO_STRIDE * n_sets));
+    }
+    h->d_servo = std::move(d); h->h_servo.swap(host); h->n_servo_sets = n_sets;           // nothing here fails: the parameter block does not hold the table
+    return LMH_OK;
+}
+
+extern "C" int lmh_servo_per_instance(const lmh_handle *h) { return (h && h->n_servo_sets > 1) ? 1 : 0; }
+
+extern "C" int lmh_get_servo(lmh_handle *h, int inst, double *record)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    if (inst < 0 || inst >= h->B) return fail(LMH_ERR_BAD_ARG, "instance out of range");
+    if (!record) return fail(LMH_ERR_BAD_ARG, "bad argument");
+    if (h->n_servo_sets == 0) {
+        for (int j = 0; j < LMH_SERVO_STRIDE; j++) record[j] = 0.0;
+        return LMH_OK;
+    }
+    std::memcpy(record, h->h_servo.data() + (size_t)LMH_SERVO_STRIDE * ((h->n_servo_sets > 1) ? inst : 0), sizeof(double) * LMH_SERVO_STRIDE);
     return LMH_OK;
 }
 
@@ -1103,10 +1151,12 @@ static int plant_constants_ok(const lmh_handle *h)
 
 // The caller has found the handle ready and checked its required pointers, which come before the constants in the order of the refusals.
 static int plant_body(lmh_handle *h, int mode, const double *d_q, const double *d_v, const double *d_tau30, double *d_state, double *d_xdot, double *d_contact, int32_t *d_flags,
-                      int n_substeps, void *stream)
+                      int n_substeps, void *stream, const double *d_setpoint = nullptr)
 {
     const int rc = plant_constants_ok(h); if (rc) return rc;
-    return launch(h, nullptr, [&] { lmh_launch_plant(&h->P, mode, d_q, d_v, d_tau30, d_state, d_xdot, d_contact, d_flags, n_substeps, h->d_ground.get(), h->ground_stride(), (hipStream_t)stream); });
+    // d_setpoint (lmh_plant_step_servo): the handle's servo table rides along; without one the launcher never reads it
+    return launch(h, nullptr, [&] { lmh_launch_plant(&h->P, mode, d_q, d_v, d_tau30, d_state, d_xdot, d_contact, d_flags, n_substeps, h->d_ground.get(), h->ground_stride(),
+                                                     d_setpoint ? h->d_servo.get() : nullptr, h->servo_stride(), d_setpoint, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_contact_wrench(lmh_handle *h, const double *d_q, const double *d_v, double *d_contact, void *stream)
@@ -1132,6 +1182,17 @@ extern "C" int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_ta
     return plant_body(h, PM_STEP, nullptr, nullptr, d_tau30, d_state, nullptr, nullptr, d_flags, n_substeps, stream);
 }
 
+// lmh_plant_step with the joint servo re-forming the joint torques at every derivative evaluation (include/lmh.h)
+extern "C" int lmh_plant_step_servo(lmh_handle *h, double *d_state, const double *d_tau30, const double *d_setpoint, int n_substeps, int32_t *d_flags, void *stream)
+{
+    int rc = ready(h); if (rc) return rc;
+    if (!d_state) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step_servo: null device pointer");
+    if (!d_setpoint) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step_servo: null d_setpoint");
+    if (n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step_servo: n_substeps must be >= 0");
+    if (n_substeps == 0) return plant_constants_ok(h);               // nothing to enqueue
+    return plant_body(h, PM_STEP, nullptr, nullptr, d_tau30, d_state, nullptr, nullptr, d_flags, n_substeps, stream, d_setpoint);
+}
+
 // ---------------------------------------------------------------------------- zero-order-hold closed loop
 // n_ticks rounds of { lmh_eval ; lmh_plant_step(tau30 = [base_wrench | out.tau], n_substeps) } in one launch (lmh_kernels.hip,
 // lmh_rollout_zoh_kernel).  Refusals in the order of the two calls it composes: the handle, the pointers, the counts, then the precision and the
@@ -1143,9 +1204,12 @@ extern "C" int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_ta
 // call's own pointers; the launch is lmh_rollout_zoh_box_kernel's whatever the options.
 // io (lmh_rollout_zoh_io; nullptr in the four calls above it, never with bx): its own refusals stand behind those of the options record; a record that asks
 // for nothing launches what the call without it launches, anything else lmh_rollout_zoh_io_kernel.
+// sv (lmh_rollout_zoh_servo; nullptr in the five calls above it, never with bx): its own refusals stand behind those of the io record; mode 0 launches what
+// the call without it launches, anything else lmh_rollout_zoh_servo_kernel whatever the options.
 struct ZohBoxCall { const double *d_box; int n_samples, n_sets; double *d_mpc; };
 static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log, const double *d_ref, bool with_ref,
-                    int n_ticks, int n_substeps, void *stream, const lmh_zoh_opts *opts = nullptr, const ZohBoxCall *bx = nullptr, const lmh_zoh_io *io = nullptr)
+                    int n_ticks, int n_substeps, void *stream, const lmh_zoh_opts *opts = nullptr, const ZohBoxCall *bx = nullptr, const lmh_zoh_io *io = nullptr,
+                    const lmh_zoh_servo *sv = nullptr)
 {
     int rc = ready(h); if (rc) return rc;
     if (!d_state || !d_out || !d_status) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: null device pointer");
@@ -1178,6 +1242,15 @@ static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_st
         if (io->reserved != 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_io: reserved must be 0");
         if (io->actuators && !io->d_act_mem) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_io: actuators = 1 needs d_act_mem");
     }
+    if (sv) {
+        if (sv->mode != 0 && sv->mode != LMH_SERVO_INTEGRATE && sv->mode != LMH_SERVO_CALLER)
+            return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_servo: mode must be 0, LMH_SERVO_INTEGRATE or LMH_SERVO_CALLER");
+        if (sv->reserved != 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_servo: reserved must be 0");
+        if (sv->mode == LMH_SERVO_CALLER && !sv->d_setpoint) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_servo: mode LMH_SERVO_CALLER needs d_setpoint");
+        if (sv->mode != LMH_SERVO_CALLER && sv->d_setpoint) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_servo: d_setpoint goes with mode LMH_SERVO_CALLER only");
+        if (sv->mode == LMH_SERVO_INTEGRATE && n_substeps == 0)
+            return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_servo: mode LMH_SERVO_INTEGRATE needs n_substeps > 0 (the setpoint is the end of a control period: with no substep there is none)");
+    }
     if (h->cfg.precision != LMH_PRECISION_FP64) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: LMH_PRECISION_FP64 handles only (this handle's precision has no instantiation of the kernel)");
     rc = plant_constants_ok(h); if (rc) return rc;
     if (n_ticks == 0) return LMH_OK;                                 // nothing to enqueue
@@ -1185,14 +1258,20 @@ static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_st
         if (h->zoh_box_prepared != 0 && h->N > 33)                   // N >= 34: above 64 KB of LDS in all, only with the limit lmh_create asked for
             return fail(LMH_ERR_HIP, "lmh_rollout_zoh_box: the runtime refused the kernel's dynamic shared memory limit when the handle was created");
         const LmhZohBox zb = {bx->d_box, box_stride(h, bx->n_sets), bx->d_mpc, h->cfg.alpha, h->cfg.beta, 0, nullptr};
-        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, nullptr, n_ticks, n_substeps, &ex, &zb, nullptr, nullptr, 0, (hipStream_t)stream); });
+        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, nullptr, n_ticks, n_substeps, &ex, &zb, nullptr, nullptr, 0, nullptr, (hipStream_t)stream); });
+    }
+    if (sv && sv->mode != 0) {
+        const LmhZohIo zi = {io ? io->d_meas : nullptr, (io && io->actuators) ? io->d_act_mem : nullptr, io ? io->d_applied : nullptr, h->d_act.get(),
+                             (h->n_act_sets > 1) ? (size_t)LMH_ACT_STRIDE : 0, io ? io->actuators : 0, 0};
+        const LmhZohServo zs = {sv->d_setpoint, h->d_servo.get(), h->servo_stride(), sv->mode, 0};
+        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, &ex, nullptr, &zi, h->d_ground.get(), h->ground_stride(), &zs, (hipStream_t)stream); });
     }
     if (io && (io->d_meas || io->d_applied || io->actuators)) {
         const LmhZohIo zi = {io->d_meas, io->actuators ? io->d_act_mem : nullptr, io->d_applied, h->d_act.get(), (h->n_act_sets > 1) ? (size_t)LMH_ACT_STRIDE : 0, io->actuators, 0};
-        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, &ex, nullptr, &zi, h->d_ground.get(), h->ground_stride(), (hipStream_t)stream); });
+        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, &ex, nullptr, &zi, h->d_ground.get(), h->ground_stride(), nullptr, (hipStream_t)stream); });
     }
     const bool plain = !ex.trace && !ex.metrics && !ex.wrench_per_tick && !ex.pushes;     // no new option: the kernels of before
-    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, plain ? nullptr : &ex, nullptr, nullptr, h->d_ground.get(), h->ground_stride(), (hipStream_t)stream); });
+    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, plain ? nullptr : &ex, nullptr, nullptr, h->d_ground.get(), h->ground_stride(), nullptr, (hipStream_t)stream); });
 }
 extern "C" int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
                                int n_ticks, int n_substeps, void *stream)
@@ -1219,6 +1298,15 @@ extern "C" int lmh_rollout_zoh_io(lmh_handle *h, double *d_state, double *d_out,
     static const lmh_zoh_opts none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
     const lmh_zoh_opts *o = opts ? opts : &none;
     return zoh_body(h, d_state, d_out, d_status, o->d_base_wrench, o->d_log, o->d_ref, false, n_ticks, n_substeps, stream, o, nullptr, io);
+}
+
+// lmh_rollout_zoh_io with the joint servo inside every hold (include/lmh.h)
+extern "C" int lmh_rollout_zoh_servo(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts, const lmh_zoh_io *io, const lmh_zoh_servo *servo,
+                                     int n_ticks, int n_substeps, void *stream)
+{
+    static const lmh_zoh_opts none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
+    const lmh_zoh_opts *o = opts ? opts : &none;
+    return zoh_body(h, d_state, d_out, d_status, o->d_base_wrench, o->d_log, o->d_ref, false, n_ticks, n_substeps, stream, o, nullptr, io, servo);
 }
 
 // lmh_rollout_zoh_ex with lmh_mpc_box_step closing the loop inside every evaluation (include/lmh.h)

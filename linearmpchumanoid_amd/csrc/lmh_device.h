@@ -95,6 +95,16 @@ struct LmhZohIo {
     int32_t pad;
 };
 
+// lmh_rollout_zoh_servo (include/lmh.h): what the launch takes beyond lmh_rollout_zoh_io's -- the handle's servo table (servo NULL: zero gains;
+// servo_stride 0: one shared record) and, with mode LMH_SERVO_CALLER, the caller's setpoints.  mode is never 0 here: that is the launch without.
+struct LmhZohServo {
+    const double *setpoint;     // [n_ticks][n_instances][LMH_SETPOINT_STRIDE] with LMH_SERVO_CALLER, else nullptr
+    const double *servo;        // [n_sets][LMH_SERVO_STRIDE], or nullptr
+    size_t servo_stride;
+    int32_t mode;               // LMH_SERVO_INTEGRATE | LMH_SERVO_CALLER
+    int32_t pad;
+};
+
 // walking-plan generator (lmh_gen_walk): arguments of the device kernel
 #define LMH_GEN_MAX_STEPS 1022
 struct LmhWalkSpec {

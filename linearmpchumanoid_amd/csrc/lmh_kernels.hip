@@ -4788,9 +4788,41 @@ __device__ __forceinline__ void plant_contact(double *L, LmhCParams &P, int lane
     WSYNC();
 }
 // one derivative of the state in L[P_Q], L[P_V]: accelerations -> L[P_QDD] (state ordering, world frame); `tau`: lane i < 30 holds tau30[i]
-template <bool GROUND = false>
-__device__ __forceinline__ int plant_derivative(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau, const double *gnd = nullptr)
+// SERVO (lmh_plant_step_servo, lmh_rollout_zoh_servo): lanes 6..29 hold their joint's gains and setpoint for the hold (ServoLane) and the
+// joint rows of tau30 are re-formed from the stage's q and v, which plant_hold has just published in L[P_Q ..], L[P_V ..] and no phase
+// writes, in front of PL_R's formation: servo_torque, the one device copy of the expression of include/lmh.h.
+struct ServoLane { double kp, kd, q_des, v_des; };
+// tau + ((kp * (q_des - q)) + (kd * (v_des - v))): both differences, both products and both sums each rounded, no fused multiply-add (the
+// products and the inner sum go through opaque registers, see metrics_wave1)
+__device__ __forceinline__ double servo_torque(double tau, const ServoLane &S, double q, double v)
 {
+    double pa = __dmul_rn(S.kp, __dsub_rn(S.q_des, q)), pb = __dmul_rn(S.kd, __dsub_rn(S.v_des, v));
+    asm volatile("" : "+v"(pa), "+v"(pb));
+    double pd = __dadd_rn(pa, pb);
+    asm volatile("" : "+v"(pd));
+    double y = __dadd_rn(tau, pd);
+    asm volatile("" : "+v"(y));
+    return y;
+}
+// lanes 6..29: the robot's record KP[24] | KD[24] (rec NULL: zero gains) and setpoint record Q_DES[24] | V_DES[24]; every other lane zeros
+__device__ __forceinline__ ServoLane servo_lane(const double *rec, const double *sp, int lane)
+{
+    ServoLane S = {0.0, 0.0, 0.0, 0.0};
+    if (lane >= 6 && lane < 30) {
+        const int j = lane - 6;
+        if (rec) { S.kp = rec[LMH_SERVO_OFF_KP + j]; S.kd = rec[LMH_SERVO_OFF_KD + j]; }
+        S.q_des = sp[j]; S.v_des = sp[24 + j];
+    }
+    return S;
+}
+template <bool GROUND = false, bool SERVO = false>
+__device__ __forceinline__ int plant_derivative(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau, const double *gnd = nullptr, const ServoLane *servo = nullptr)
+{
+    if constexpr (SERVO) {
+        const int l = (lane >= 6 && lane < 30) ? lane : 6;
+        const double y = servo_torque(tau, *servo, L[P_Q + l], L[P_V + l]);
+        if (lane >= 6 && lane < 30) tau = y;
+    }
     if (lane < 30) L[P_VP + lane] = L[P_V + lane];                 // one velocity for every term
     WSYNC();
     phase_fk<double>(L, P.lcoef);
@@ -4809,8 +4841,9 @@ __device__ __forceinline__ int plant_derivative(double *L, LmhCParams &P, const 
 // and goes out in a register, L[P_Q], L[P_V] carry each stage's state (and are left at the last stage's, not at x: a caller that wants x in
 // LDS writes it), `flags` collects plant_derivative's and LMH_FLAG_NONFINITE of x behind every substep.  Wave-scope fences only; no clock:
 // the callers advance theirs by n_substeps additions of dt (lmh_plant_kernel<PM_STEP>; wave 0 of lmh_rollout_zoh_kernel)
-template <bool GROUND = false>
-__device__ __forceinline__ void plant_hold(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau, double dt, int n_substeps, double &x, int &flags, const double *gnd = nullptr)
+template <bool GROUND = false, bool SERVO = false>
+__device__ __forceinline__ void plant_hold(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau, double dt, int n_substeps, double &x, int &flags, const double *gnd = nullptr,
+                                           const ServoLane *servo = nullptr)
 {
 #pragma unroll 1
     for (int sub = 0; sub < n_substeps; sub++) {
@@ -4820,6 +4853,8 @@ __device__ __forceinline__ void plant_hold(double *L, LmhCParams &P, const IbPac
             WSYNC();
             if (lane < 60) L[P_Q + lane] = xs;                     // q | v are one run
             WSYNC();
+            if constexpr (SERVO) flags |= plant_derivative<GROUND, true>(L, P, ibp, lane, tau, gnd, servo);
+            else
             flags |= plant_derivative<GROUND>(L, P, ibp, lane, tau, gnd);
             rk4_stage<0>(L, stage, lane, dt, P_SC + 52, x, ksum, xs);
         }
@@ -4927,6 +4962,35 @@ __global__ void __launch_bounds__(64) lmh_plant_ground_kernel(LmhDevParams P_arg
         if (lane == 0 && flags_out) flags_out[inst] = flags;
     }
 }
+// lmh_plant_step_servo (include/lmh.h): lmh_plant_kernel<PM_STEP>'s statements (lmh_plant_ground_kernel<PM_STEP>'s with GROUND) with the SERVO
+// hold: `servo` + servo_stride * robot is the robot's gain record (NULL: zero gains; stride 0: one shared record), `setpoint` + 48 * robot its
+// setpoint, both loaded once by the lanes that own the joints.  Kernels of their own: the two above keep their text, and with it their code.
+template <bool GROUND>
+__global__ void __launch_bounds__(64) lmh_plant_servo_kernel(LmhDevParams P_arg, const double *tau30, double *state, int32_t *flags_out, int n_substeps, const double *servo,
+                                                             size_t servo_stride, const double *setpoint, const double *ground, size_t ground_stride)
+{
+    LmhCParams &P0 = LMH_KERNARG_PARAMS();
+    __shared__ double L[LDS_DOUBLES];
+    const int inst = blockIdx.x;
+    if (inst >= P0.n_instances) return;
+    LmhCParams &P = *params_of_robot(&P0, inst);
+    const double *gnd = GROUND ? ground + ground_stride * (size_t)inst : nullptr;
+    const int lane = LANE;
+    SET_GDBG(nullptr);
+    load_common(L, P, inst);
+    const IbPack ibp = ib_pack();
+    const double tau = (tau30 && lane < 30) ? tau30[30 * (size_t)inst + lane] : 0.0;
+    const ServoLane S = servo_lane(servo ? servo + servo_stride * (size_t)inst : nullptr, setpoint + (size_t)LMH_SETPOINT_STRIDE * inst, lane);
+    int flags = 0;
+    double *st = state + (size_t)LMH_STATE_STRIDE * inst;
+    double x = (lane < 60) ? st[lane] : 0.0, t = st[90];
+    const double dt = P.dt;
+    plant_hold<GROUND, true>(L, P, ibp, lane, tau, dt, n_substeps, x, flags, gnd, &S);
+#pragma unroll 1
+    for (int sub = 0; sub < n_substeps; sub++) t += dt;            // Clock::step, Clock.hpp:11
+    if (lane < 60) st[lane] = x; else if (lane == 60) st[90] = t;
+    if (lane == 0 && flags_out) flags_out[inst] = flags;
+}
 #ifndef LMH_ROLLOUT_ONLY
 extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *q, const double *v, const double *x, const double *w, double *res, int32_t *flags, hipStream_t s)
 {
@@ -4936,9 +5000,14 @@ extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *
     else hipLaunchKernelGGL(lmh_terms_kernel<TM_FWDDYN>, grid, block, 0, s, *P, q, v, x, w, res, flags);
 }
 extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact, int32_t *flags,
-                                 int n_substeps, const double *ground, size_t ground_stride, hipStream_t s)
+                                 int n_substeps, const double *ground, size_t ground_stride, const double *servo, size_t servo_stride, const double *setpoint, hipStream_t s)
 {
     const dim3 grid(P->n_instances), block(64);
+    if (setpoint) {                                                // lmh_plant_step_servo (PM_STEP only; servo NULL: zero gains); without one the kernels of before
+        if (ground) hipLaunchKernelGGL(lmh_plant_servo_kernel<true>, grid, block, 0, s, *P, tau30, state, flags, n_substeps, servo, servo_stride, setpoint, ground, ground_stride);
+        else hipLaunchKernelGGL(lmh_plant_servo_kernel<false>, grid, block, 0, s, *P, tau30, state, flags, n_substeps, servo, servo_stride, setpoint, ground, ground_stride);
+        return;
+    }
     if (ground) {                                                  // a handle with a table: the GROUND instantiations; without one the kernels of before
         if (mode == PM_CONTACT) hipLaunchKernelGGL(lmh_plant_ground_kernel<PM_CONTACT>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps, ground, ground_stride);
         else if (mode == PM_DERIV) hipLaunchKernelGGL(lmh_plant_ground_kernel<PM_DERIV>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps, ground, ground_stride);
@@ -5156,6 +5225,46 @@ __device__ __forceinline__ CZohGroundArgs &zoh_ground_args()
     asm volatile("" : "+s"(p_));
     return *p_;
 }
+// lmh_rollout_zoh_servo_kernel's arguments: lmh_rollout_zoh_ground_kernel's (ground NULL without a table: the flat hold), then the servo's
+struct ZohServoArgs { ZohGroundArgs a; LmhZohServo sv; };
+static_assert(sizeof(ZohGroundArgs) % 8 == 0 && alignof(ZohServoArgs) == 8, "ZohServoArgs continues ZohGroundArgs in the kernel-argument segment");
+typedef const __attribute__((address_space(4))) ZohServoArgs CZohServoArgs;
+__device__ __forceinline__ CZohServoArgs &zoh_servo_args()
+{
+    CZohServoArgs *p_ = (CZohServoArgs *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(LmhDevParams));
+    asm volatile("" : "+s"(p_));
+    return *p_;
+}
+// wave 0, behind the evaluation of control tick `tick` and in front of its hold: what lanes 6..29 carry through the hold.  The gains are
+// loaded here, once per control tick, and not held across controller_eval (no VGPRs to spare there).  LMH_SERVO_CALLER: record `tick` of the
+// robot.  LMH_SERVO_INTEGRATE: from what the evaluation READ, L[P_Q ..] and L[P_V ..] (the measured words with d_meas), and the joint rows
+// of its out.qdd, which store_out takes from L[P_QDD ..] and the hold has not yet overwritten:
+//     T = (double)n_substeps * dt;  h2 = (0.5 * T) * T;  v_des = v_m + (T * a);  q_des = (q_m + (T * v_m)) + (h2 * a)
+// every product and sum rounded by itself (opaque registers between them: no fused multiply-add)
+__device__ __forceinline__ ServoLane zoh_servo_lane(const double *L, int lane, int inst, int tick, int nsub, double dt)
+{
+    const double *servo = zoh_servo_args().sv.servo;
+    const double *rec = servo ? servo + zoh_servo_args().sv.servo_stride * (size_t)inst : nullptr;
+    if (zoh_servo_args().sv.mode == LMH_SERVO_CALLER)
+        return servo_lane(rec, zoh_servo_args().sv.setpoint + ((size_t)tick * LMH_KERNARG_PARAMS().n_instances + inst) * LMH_SETPOINT_STRIDE, lane);
+    ServoLane S = {0.0, 0.0, 0.0, 0.0};
+    if (lane >= 6 && lane < 30) {
+        if (rec) { S.kp = rec[LMH_SERVO_OFF_KP + lane - 6]; S.kd = rec[LMH_SERVO_OFF_KD + lane - 6]; }
+        const double q_m = L[P_Q + lane], v_m = L[P_V + lane], a = L[P_QDD + lane];
+        double T = __dmul_rn((double)nsub, dt);
+        asm volatile("" : "+v"(T));
+        double h2 = __dmul_rn(0.5, T);
+        asm volatile("" : "+v"(h2));
+        h2 = __dmul_rn(h2, T);
+        double ta = __dmul_rn(T, a), tv = __dmul_rn(T, v_m), ha = __dmul_rn(h2, a);
+        asm volatile("" : "+v"(ta), "+v"(tv), "+v"(ha));
+        S.v_des = __dadd_rn(v_m, ta);
+        double s1 = __dadd_rn(q_m, tv);
+        asm volatile("" : "+v"(s1));
+        S.q_des = __dadd_rn(s1, ha);
+    }
+    return S;
+}
 // MODE: where the momentum task's CoM reference comes from.  ZM_BOX (lmh_rollout_zoh_box_kernel): every control tick runs lmh_mpc_box_step at the
 // measured CoM state inside the evaluation's chain A (refs_chain_a); the preview Hessian is factored once, behind eval_begin, by the helper wave
 // alone (wave-scope fences: both waves pass the same joins as in the other modes) while wave 0 goes on to the pushes and the kinematics.
@@ -5164,12 +5273,15 @@ enum { ZM_BUILTIN, ZM_REF, ZM_BOX };
 // GROUND (lmh_rollout_zoh_ground_kernel; always with IO, whose options may all be off): the hold presses the soles against the robot's planes
 // of lmh_set_ground.  The record's address is formed from the kernel arguments in front of every hold and handed to plant_hold, whose eight
 // vertex lanes load their plane where they use it: nothing of it is carried across controller_eval.
-template <int MODE, bool IO = false, bool GROUND = false>
+// SERVO (lmh_rollout_zoh_servo_kernel; always with IO; its arguments continue ZohGroundArgs, so GROUND reads the same words): every piece of
+// a control tick's hold is the SERVO plant_hold with the tick's one ServoLane (zoh_servo_lane), formed where wave 0 picks up tau.
+template <int MODE, bool IO = false, bool GROUND = false, bool SERVO = false>
 __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
 {
     constexpr bool REF = MODE != ZM_BUILTIN, BOX = MODE == ZM_BOX;
     static_assert(!(IO && BOX), "lmh_rollout_zoh_io has no box-constrained form");
     static_assert(IO || !GROUND, "the ground kernels are instantiations of the IO body");
+    static_assert(IO || !SERVO, "the servo kernels are instantiations of the IO body");
     LmhCParams &P0 = LMH_KERNARG_PARAMS();
     typedef const __attribute__((address_space(4))) ZohExArgs CArgs;
     auto KA = [&]() -> CArgs & {
@@ -5251,6 +5363,8 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
             const double vp = L[P_V + ((lane < 30) ? lane : 0)];   // Robot::v_ <- dq (controller.cpp:59): what the next evaluation sees
             double tau = (lane < 6) ? bw : L[P_TAU + ((lane >= 6 && lane < 30) ? lane - 6 : 0)];               // lane i < 30: tau30[i] = [base wrench | out.tau]
             if constexpr (IO) tau = zoh_io_actuate(tau, io_joint, lane, inst, tick, flags);
+            ServoLane servo = {0.0, 0.0, 0.0, 0.0};
+            if constexpr (SERVO) servo = zoh_servo_lane(L, lane, inst, tick, nsub, dt);
             const bool pushes = KA().ex.pushes != 0;
             // substeps of the launch | of them behind the robot: the cursor's units, formed with pushes only (the host bounds the product then)
             const int lim = pushes ? KA().n_ticks * nsub : 0;
@@ -5262,6 +5376,9 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
                     const int rel = __builtin_amdgcn_readfirstlane(((const int *)(L + P_PUSH))[0]);
                     if (rel > done && rel < done + r) s = rel - done;
                 }
+                if constexpr (SERVO)
+                    plant_hold<GROUND, true>(L, P, ib_pack(), lane, tau, dt, s, x, flags, GROUND ? zoh_ground_args().ground + zoh_ground_args().ground_stride * (size_t)inst : nullptr, &servo);
+                else
                 if constexpr (GROUND) plant_hold<true>(L, P, ib_pack(), lane, tau, dt, s, x, flags, zoh_ground_args().ground + zoh_ground_args().ground_stride * (size_t)inst);
                 else
                 plant_hold(L, P, ib_pack(), lane, tau, dt, s, x, flags);
@@ -5323,10 +5440,33 @@ __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_wav
     (void)A_arg;
     lmh_rollout_zoh_ex_body<REF ? ZM_REF : ZM_BUILTIN, true, true>(L);
 }
+// lmh_rollout_zoh_servo (include/lmh.h): the IO body with the joint servo inside every hold, on the flat ground or on the handle's ground table
+template <bool REF, bool GROUND>
+__global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) lmh_rollout_zoh_servo_kernel(LmhDevParams P_arg, ZohServoArgs A_arg)
+{
+    __shared__ double L[LDS_DOUBLES];
+    (void)A_arg;
+    lmh_rollout_zoh_ex_body<REF ? ZM_REF : ZM_BUILTIN, true, GROUND, true>(L);
+}
 // ex NULL: lmh_rollout_zoh's kernel exactly as it is when ref is NULL, otherwise lmh_rollout_zoh_ref's; with ex the kernel that takes the options
 extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
-                                       const LmhZohEx *ex, const LmhZohBox *bx, const LmhZohIo *io, const double *ground, size_t ground_stride, hipStream_t s)
+                                       const LmhZohEx *ex, const LmhZohBox *bx, const LmhZohIo *io, const double *ground, size_t ground_stride, const LmhZohServo *sv, hipStream_t s)
 {
+    // sv: lmh_rollout_zoh_servo_kernel whatever the options and the ground (bx is then NULL); NULL = the kernels of before, exactly
+    if (sv) {
+        const LmhZohEx no_ex = {nullptr, nullptr, 0, 0, 0, 0};
+        const LmhZohIo no_io = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
+        const ZohServoArgs a = {{{{state, out, status, base_wrench, log, ref, ex ? *ex : no_ex, n_ticks, n_substeps}, io ? *io : no_io}, ground, ground_stride}, *sv};
+        const dim3 grid(P->n_instances), block(LMH_ROLLOUT_THREADS);
+        if (ground) {
+            if (ref) hipLaunchKernelGGL((lmh_rollout_zoh_servo_kernel<true, true>), grid, block, 0, s, *P, a);
+            else hipLaunchKernelGGL((lmh_rollout_zoh_servo_kernel<false, true>), grid, block, 0, s, *P, a);
+        } else {
+            if (ref) hipLaunchKernelGGL((lmh_rollout_zoh_servo_kernel<true, false>), grid, block, 0, s, *P, a);
+            else hipLaunchKernelGGL((lmh_rollout_zoh_servo_kernel<false, false>), grid, block, 0, s, *P, a);
+        }
+        return;
+    }
     // ground: lmh_rollout_zoh_ground_kernel whatever the options (bx is then NULL: the host layer refuses the combination); ex or io NULL = none of theirs
     if (ground) {
         const LmhZohEx no_ex = {nullptr, nullptr, 0, 0, 0, 0};

@@ -32,8 +32,10 @@ extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_
 // with a measurement added to what the evaluation reads and an actuator in front of the hold (LmhZohIo, lmh_device.h).
 // ground (lmh_set_ground; bx is then NULL): NULL = the kernels above; otherwise ground + ground_stride * robot is that robot's LMH_GROUND_STRIDE words
 // (ground_stride 0: one shared record) and the launch is lmh_rollout_zoh_ground_kernel's whatever ex and io ask for (either may be NULL = nothing).
+// sv (lmh_rollout_zoh_servo; bx is then NULL, ex, io and ground may each be NULL): NULL = the kernels above, exactly; otherwise
+// lmh_rollout_zoh_servo_kernel, the IO body with the joint servo inside every hold (LmhZohServo, lmh_device.h).
 extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
-                                       const LmhZohEx *ex, const LmhZohBox *bx, const LmhZohIo *io, const double *ground, size_t ground_stride, hipStream_t s);
+                                       const LmhZohEx *ex, const LmhZohBox *bx, const LmhZohIo *io, const double *ground, size_t ground_stride, const LmhZohServo *sv, hipStream_t s);
 extern "C" void lmh_launch_metrics_reset(double *metrics, int n_instances, double z_min, double tilt_max, hipStream_t s);
 extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
 extern "C" void lmh_launch_com(const LmhDevParams *P, const double *q, double *com, hipStream_t s);
@@ -41,8 +43,10 @@ extern "C" void lmh_launch_ik(const LmhDevParams *P, double *q, const LmhIkTarge
 extern "C" void lmh_launch_ik_batch(const LmhDevParams *P, const double *q_start, const double *targets, int n_targets, double *q, int32_t *iters, double *crit, hipStream_t s);
 extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *q, const double *v, const double *x, const double *w, double *res, int32_t *flags, hipStream_t s);
 // ground, ground_stride: as in lmh_launch_rollout_zoh; NULL = lmh_plant_kernel exactly as it is, otherwise lmh_plant_ground_kernel
+// setpoint (lmh_plant_step_servo; PM_STEP only): NULL = the kernels above, exactly; otherwise [n_instances][LMH_SETPOINT_STRIDE] and the launch is
+// lmh_plant_servo_kernel's, with servo + servo_stride * robot that robot's LMH_SERVO_STRIDE gains (servo NULL: zero gains; stride 0: one shared record)
 extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact, int32_t *flags,
-                                 int n_substeps, const double *ground, size_t ground_stride, hipStream_t s);
+                                 int n_substeps, const double *ground, size_t ground_stride, const double *servo, size_t servo_stride, const double *setpoint, hipStream_t s);
 // The three MPC launchers carry the box-constrained variants (lmh_mpc_box_*): box NULL = the unconstrained kernels exactly as they are (alpha, beta and
 // box_stride are then not read by step and rollout); otherwise box + box_stride * robot is that robot's [4][n_samples] bounds (box_stride 0: one shared set)
 // and `mpc` / `traj` / `record` take the constrained call's records (record: LMH_MPC_BOX_STRIDE words per robot instead of LMH_MPC_PREVIEW_STRIDE).

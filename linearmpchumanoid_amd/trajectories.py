@@ -8,7 +8,7 @@ definition on top of the reference's conventions (SupportFoot -> ZMP y of -/+0.0
 """
 import numpy as np
 
-from .capi import ACT_MAX_DELAY, ACT_MEM_STRIDE, ACT_OFF_ALPHA, ACT_OFF_DELAY, ACT_OFF_TAU_MAX, ACT_STRIDE, FLAG_BOX_EMPTY, FLAG_NONFINITE, FLAG_NOT_SPD, FLAG_QP_MAXITER, FLAG_ZMP_RANGE, GROUND_OFF_H_L, GROUND_OFF_H_R, GROUND_OFF_N_L, GROUND_OFF_N_R, GROUND_STRIDE, IK_TARGET_STRIDE, LIP_STRIDE, MAX_PUSHES, MPC_BOX_MAX_ROUNDS, MPC_STRIDE, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE
+from .capi import ACT_MAX_DELAY, ACT_MEM_STRIDE, ACT_OFF_ALPHA, ACT_OFF_DELAY, ACT_OFF_TAU_MAX, ACT_STRIDE, FLAG_BOX_EMPTY, FLAG_NONFINITE, FLAG_NOT_SPD, FLAG_QP_MAXITER, FLAG_ZMP_RANGE, GROUND_OFF_H_L, GROUND_OFF_H_R, GROUND_OFF_N_L, GROUND_OFF_N_R, GROUND_STRIDE, IK_TARGET_STRIDE, LIP_STRIDE, MAX_PUSHES, MPC_BOX_MAX_ROUNDS, MPC_STRIDE, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE, SERVO_OFF_KD, SERVO_OFF_KP, SERVO_STRIDE, SETPOINT_STRIDE
 
 
 def stance_zmp(simulation_time, time_step, support_foot=2):
@@ -653,6 +653,49 @@ def actuator_step(record, mem, cmd):
             prev[:] = yi
             y[i] = yi
     return y.reshape(lead + (24,)), limited.reshape(lead)
+
+
+# the refusal of lmh_set_servo, word for word (lmh_capi.hip, servo_record_error)
+SERVO_ERR_GAIN = "servo gains must be finite and >= 0"
+
+
+def servo_records(n_instances, kp=0.0, kd=0.0):
+    """Host statement of the table of lmh_set_servo: kp (N m / rad) and kd (N m s / rad) a scalar, [24] or [B,24] -> records [B,48] =
+    kp[24] | kd[24].  What lmh_set_servo refuses is refused here with the same words, the first offending robot named ("robot 7: ...")."""
+    B = int(n_instances)
+    rec = np.zeros((B, SERVO_STRIDE))
+    rec[:, SERVO_OFF_KP:SERVO_OFF_KP + 24] = np.broadcast_to(np.asarray(kp, dtype=np.float64), (B, 24))
+    rec[:, SERVO_OFF_KD:SERVO_OFF_KD + 24] = np.broadcast_to(np.asarray(kd, dtype=np.float64), (B, 24))
+    for i, r in enumerate(rec):
+        if not (np.isfinite(r) & (r >= 0.0)).all():
+            raise ValueError(f"robot {i}: {SERVO_ERR_GAIN}")
+    return rec
+
+
+def servo_torque(rec, setpoint, q, v, tau):
+    """Host statement of the joint servo (include/lmh.h): rec [..,48] (lmh_set_servo), setpoint [..,48] = q_des[24] | v_des[24], q and v
+    [..,30] the stage's state, tau [..,30] the feed-forward tau30 -> the tau30 the derivative uses.  Rows 6..29 are
+    tau + ((kp * (q_des - q)) + (kd * (v_des - v))), every operation rounded on its own in this order; rows 0..5 are tau's."""
+    rec, sp = np.asarray(rec, dtype=np.float64), np.asarray(setpoint, dtype=np.float64)
+    q, v, tau = np.asarray(q, dtype=np.float64), np.asarray(v, dtype=np.float64), np.asarray(tau, dtype=np.float64)
+    if rec.shape[-1] != SERVO_STRIDE or sp.shape[-1] != SETPOINT_STRIDE or q.shape[-1] != 30 or v.shape[-1] != 30 or tau.shape[-1] != 30:
+        raise ValueError("servo_torque takes rec [..,48], setpoint [..,48], q, v and tau [..,30]")
+    kp, kd = rec[..., SERVO_OFF_KP:SERVO_OFF_KP + 24], rec[..., SERVO_OFF_KD:SERVO_OFF_KD + 24]
+    out = np.array(np.broadcast_to(tau, np.broadcast_shapes(tau.shape, q.shape[:-1] + (30,), rec.shape[:-1] + (30,), sp.shape[:-1] + (30,))))
+    with np.errstate(invalid="ignore"):
+        out[..., 6:30] = tau[..., 6:30] + ((kp * (sp[..., 0:24] - q[..., 6:30])) + (kd * (sp[..., 24:48] - v[..., 6:30])))
+    return out
+
+
+def servo_setpoint(q_m, v_m, qdd, n_substeps, dt):
+    """Host statement of the LMH_SERVO_INTEGRATE setpoint of lmh_rollout_zoh_servo (include/lmh.h): q_m, v_m, qdd [..,24] the joint words
+    the evaluation read and the joint rows of its out.qdd -> setpoint [..,48] = q_des | v_des with T = n_substeps * dt, h2 = (0.5 * T) * T,
+    v_des = v_m + (T * qdd), q_des = (q_m + (T * v_m)) + (h2 * qdd), every operation rounded on its own."""
+    q_m, v_m, a = np.asarray(q_m, dtype=np.float64), np.asarray(v_m, dtype=np.float64), np.asarray(qdd, dtype=np.float64)
+    T = np.float64(float(int(n_substeps))) * np.float64(dt)
+    h2 = (np.float64(0.5) * T) * T
+    with np.errstate(invalid="ignore", over="ignore"):
+        return np.concatenate([(q_m + (T * v_m)) + (h2 * a), v_m + (T * a)], axis=-1)
 
 
 def ground_planes(slope, azimuth, h_r=0.0, h_l=0.0):
