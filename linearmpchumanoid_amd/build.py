@@ -25,7 +25,10 @@ def needs_build():
 #            (tests/test_gpu_round4.py: an incomplete rollout is loud and leaves a clean launch slot)
 #   noedge:  -DLMH_NO_EDGE -- the edge-contact form of the push-through solve is off: a foot pressing on one side of its sole goes the
 #            register / general route (tests/test_gpu_round4.py compares the two routes through a touch-down)
-CHECKER_VARIANTS = {"poison": ["-DLMH_POISON"], "qfault": ["-DLMH_SPIN_LIMIT=64", "-DLMH_TEST_LOSE_PUSH=7"], "noedge": ["-DLMH_NO_EDGE"]}
+#   lanert:  -DLMH_LANE_RUNTIME -- LANE_IS(expr) (csrc/lmh_device.h) evaluates its predicate at run time on the kernel's lane id instead of
+#            taking the constant lane mask (tests/test_gpu_lane_masks.py: the two libraries give the same bytes)
+CHECKER_VARIANTS = {"poison": ["-DLMH_POISON"], "qfault": ["-DLMH_SPIN_LIMIT=64", "-DLMH_TEST_LOSE_PUSH=7"], "noedge": ["-DLMH_NO_EDGE"],
+                    "lanert": ["-DLMH_LANE_RUNTIME"]}
 
 
 def _hipcc_cmd(so, extra):
@@ -125,6 +128,25 @@ def build_dpp_harness(force=False, verbose=False):
         return so
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I" + CSRC, DPP_HARNESS_SRC, "-o", so]
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.check_call(cmd)
+    return so
+
+
+LANE_MASK_HARNESS_SRC = os.path.join(ROOT, "tests", "kernels", "lane_mask_harness.hip")
+LANE_MASK_HARNESS_SO = os.path.join(_HERE, "liblmh_lane_mask_harness.so")
+
+
+def build_lane_mask_harness(force=False, verbose=False):
+    """Test harness of LANE_IS (tests/kernels/lane_mask_harness.hip: lane-only predicates as constant lane masks and at run time, side by
+    side) into liblmh_lane_mask_harness.so -- test infrastructure like the DPP harness, never part of the shipped library."""
+    srcs = [LANE_MASK_HARNESS_SRC, os.path.join(CSRC, "lmh_device.h")]
+    so = LANE_MASK_HARNESS_SO
+    if not force and os.path.exists(so) and all(os.path.getmtime(f) <= os.path.getmtime(so) for f in srcs):
+        return so
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-I" + CSRC, LANE_MASK_HARNESS_SRC, "-o", so]
     if verbose:
         print(" ".join(cmd))
     subprocess.check_call(cmd)

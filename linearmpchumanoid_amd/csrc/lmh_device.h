@@ -10,6 +10,33 @@
 #define LMH_PUSH_STRIDE 32    // one velocity push: tick (as a double) | dv[30] | pad (include/lmh.h, lmh_set_pushes)
 #define LMH_ROLLOUT_THREADS 128   // fused rollout: two waves per robot (lmh_kernels.hip, bsync)
 
+// ---- predicates of the lane id alone, as constant lane masks.  In the 64-lane kernels (lane = threadIdx.x & 63) a condition such as
+// lane < 30 or (lane & 15) < 6 is a compile-time 64-bit constant: LANE_IS(expr) evaluates `expr` for lane = 0 .. 63 while compiling and
+// hands the mask to the wave as a lane predicate -- two scalar moves where it is used, instead of a vector compare (plus the integer work
+// that formed its operand) on the wave that carries the critical path, and nothing to keep alive in an SGPR pair across a phase.  The
+// lambda captures nothing, so an `expr` that mentions anything but `lane`, literals, enumerators and constexpr values does not compile:
+// a predicate with a run-time factor keeps that factor outside the macro (LANE_IS(lane < 12) && ((F >> l16) & 1)).
+// -DLMH_LANE_RUNTIME (the `lanert` checker build): the same expression evaluated at run time on the kernel's LANE, the form the masks
+// replaced -- tests/test_gpu_lane_masks.py holds the two libraries to the same bytes.
+template <class F>
+constexpr uint64_t lane_mask_of(F f)
+{
+    uint64_t m = 0;
+    for (int l = 0; l < 64; l++) m |= f(l) ? (uint64_t)1 << l : (uint64_t)0;
+    return m;
+}
+#ifdef LMH_LANE_RUNTIME
+#define LANE_IS(expr) ([](int lane) -> bool { return (expr); }(LANE))
+#else
+#define LANE_IS(expr) ({ constexpr uint64_t lane_mask_ = lane_mask_of([](int lane) constexpr -> bool { return (expr); }); \
+                         __builtin_amdgcn_inverse_ballot_w64(lane_mask_); })
+#endif
+static_assert(lane_mask_of([](int lane) constexpr -> bool { return lane < 30; }) == 0x3FFFFFFFull, "lane < 30");
+static_assert(lane_mask_of([](int lane) constexpr -> bool { return (lane & 15) == 3; }) == 0x0008000800080008ull, "(lane & 15) == 3");
+static_assert(lane_mask_of([](int lane) constexpr -> bool { return (lane >> 4) < 2; }) == 0x00000000FFFFFFFFull, "lane >> 4 < 2");
+static_assert(lane_mask_of([](int lane) constexpr -> bool { return lane >= 30 && lane < 36; }) == 0x0000000FC0000000ull, "30 <= lane < 36");
+static_assert(lane_mask_of([](int lane) constexpr -> bool { return lane < 0; }) == 0ull && lane_mask_of([](int lane) constexpr -> bool { return lane < 64; }) == ~0ull, "empty and full");
+
 struct LmhIkTarget { double v[16]; };   // rF(6) | lF(6) | com(3) | pad: passed by value in the IK kernel's arguments
 
 struct LmhDevParams {

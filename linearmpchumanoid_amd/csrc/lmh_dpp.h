@@ -6,6 +6,7 @@
 // Everything here needs a full exec mask (wave-uniform control flow only).
 #ifndef LMH_DPP_H
 #define LMH_DPP_H
+#include "lmh_device.h"     // LANE_IS: predicates of the lane id alone as constant lane masks (every `lane` below is the caller's LANE)
 // Lane exchange inside a 16-lane row through DPP (two 32-bit v_mov_dpp per double, ~10 cycles) instead of
 // ds_bpermute (an LDS round trip per step).  CTRL: 0xB1 = quad_perm[1,0,3,2] (lane ^ 1), 0x4E = quad_perm[2,3,0,1]
 // (lane ^ 2), 0x141 = row_half_mirror, 0x140 = row_mirror.  Needs a full exec mask (wave-uniform control flow).
@@ -223,8 +224,8 @@ __device__ __forceinline__ void ldl16_forward(double (&a)[N], double (&b)[M], un
             if (!(d > 0.0)) bad = 1;
             const double invd = fast_rcp(d);
             const double f = a[J] * invd;                         // L_iJ in lanes i > J
-            const double nfm = (lane > J) ? -f : 0.0;
-            if (lane == J) myinv = invd;
+            const double nfm = LANE_IS(lane > J) ? -f : 0.0;
+            if (LANE_IS(lane == J)) myinv = invd;
             dpp_fmac_range<J + 1, J + 1, N - 1 - J>(a, a[J], -f);                 // a[c] -= f * (d_J L_cJ held by lane c)
             dpp_fmac_self<0, M, J>(b, nfm);                       // forward substitution
             a[J] = f;                                             // (rows <= J keep a don't-care there: only L_iJ, i > J, is read back)
@@ -237,8 +238,8 @@ __device__ __forceinline__ void ldl16_backward(double (&b)[M], unsigned live, in
 {
     if constexpr (J > 0) {
         if ((live >> J) & 1u) {
-            const double lv = Ls[J * (N + 1) + ((lane < N) ? lane : 0)];      // unconditional load (clamped), masked by value: no exec branch
-            const double nl = (lane < J) ? -lv : 0.0;
+            const double lv = Ls[J * (N + 1) + (LANE_IS(lane < N) ? lane : 0)];      // unconditional load (clamped), masked by value: no exec branch
+            const double nl = LANE_IS(lane < J) ? -lv : 0.0;
             dpp_fmac_self<0, M, J>(b, nl);
         }
         ldl16_backward<J - 1, N>(b, live, lane, Ls);
@@ -258,31 +259,31 @@ __device__ __forceinline__ void ldl2_forward(double (&a0)[16], double (&a1)[16 +
         if ((live >> J) & 1u) {                                   // wave-uniform
             if constexpr (J < 16) {
                 double d = bcast16<J>(a0[J]);
-                d = (lane < 16) ? d : 1.0;
+                d = LANE_IS(lane < 16) ? d : 1.0;
                 if (!(d > 0.0)) bad = 1;
                 const double invd = fast_rcp(d);
                 const double f0 = a0[J] * invd, f1 = a1[J] * invd;     // L_iJ (rows < 16, valid for lane > J) | L_(16+i)J
-                const double nfm0 = (lane > J) ? -f0 : 0.0;
-                if (lane == J) inv0 = invd;
+                const double nfm0 = LANE_IS(lane > J) ? -f0 : 0.0;
+                if (LANE_IS(lane == J)) inv0 = invd;
                 dpp_fmac_range<J + 1, J + 1, 15 - J>(a0, a0[J], -f0);  // columns J+1..15: lane c holds d_J L_cJ in a0[J]
                 dpp_fmac_range<J + 1, J + 1, 15 - J>(a1, a0[J], -f1);
                 dpp_fmac_range<16, 0, N2>(a1, a1[J], -f1);             // columns 16..N-1: lane c - 16 holds d_J L_cJ in a1[J]
                 dpp_fmac_one<J>(b1, b0, -f1);                          // forward substitution (lane J's b0 is z_J, untouched below)
                 dpp_fmac_one<J>(b0, b0, nfm0);
-                if (lane > J) a0[J] = f0;
+                if (LANE_IS(lane > J)) a0[J] = f0;
                 a1[J] = f1;
             } else {
                 constexpr int Jp = J - 16;
                 double d = bcast16<Jp>(a1[J]);
-                d = (lane < 16) ? d : 1.0;
+                d = LANE_IS(lane < 16) ? d : 1.0;
                 if (!(d > 0.0)) bad = 1;
                 const double invd = fast_rcp(d);
                 const double f1 = a1[J] * invd;
-                const double nfm1 = (lane > Jp) ? -f1 : 0.0;
-                if (lane == Jp) inv1 = invd;
+                const double nfm1 = LANE_IS(lane > Jp) ? -f1 : 0.0;
+                if (LANE_IS(lane == Jp)) inv1 = invd;
                 dpp_fmac_range<J + 1, Jp + 1, N - 1 - J>(a1, a1[J], -f1);
                 dpp_fmac_one<Jp>(b1, b1, nfm1);
-                if (lane > Jp) a1[J] = f1;
+                if (LANE_IS(lane > Jp)) a1[J] = f1;
             }
         }
         ldl2_forward<J + 1, N2>(a0, a1, b0, b1, live, lane, bad, inv0, inv1);
@@ -294,15 +295,15 @@ __device__ __forceinline__ void ldl2_backward(double &b0, double &b1, unsigned l
     constexpr int N = 16 + N2;
     if constexpr (J > 0) {
         if ((live >> J) & 1u) {
-            const int l16 = (lane < 16) ? lane : 0;                // lanes outside DPP row 0 read a valid address
+            const int l16 = LANE_IS(lane < 16) ? lane : 0;         // lanes outside DPP row 0 read a valid address
             if constexpr (J >= 16) {
                 constexpr int Jp = J - 16;
-                const double l0 = (lane < 16) ? Ls[J * (N + 1) + l16] : 0.0;             // L[J][lane], rows < 16
-                const double l1 = (lane < Jp) ? Ls[J * (N + 1) + 16 + l16] : 0.0;        // L[J][16 + lane], rows 16 .. J-1
+                const double l0 = LANE_IS(lane < 16) ? Ls[J * (N + 1) + l16] : 0.0;      // L[J][lane], rows < 16
+                const double l1 = LANE_IS(lane < Jp) ? Ls[J * (N + 1) + 16 + l16] : 0.0;        // L[J][16 + lane], rows 16 .. J-1
                 dpp_fmac_one<Jp>(b0, b1, -l0);
                 dpp_fmac_one<Jp>(b1, b1, -l1);
             } else {
-                const double l0 = (lane < J) ? Ls[J * (N + 1) + l16] : 0.0;
+                const double l0 = LANE_IS(lane < J) ? Ls[J * (N + 1) + l16] : 0.0;
                 dpp_fmac_one<J>(b0, b0, -l0);
             }
         }
@@ -321,11 +322,11 @@ __device__ __forceinline__ int ldl2_solve_regs(double (&a0)[16], double (&a1)[16
     bad = __builtin_amdgcn_readfirstlane(bad);
     b0 *= inv0; b1 *= inv1;                                       // w = D^-1 z
     WSYNC();
-    if (lane < 16) {
+    if (LANE_IS(lane < 16)) {
 #pragma unroll
         for (int c = 0; c < 15; c++) Ls[lane * (N + 1) + c] = a0[c];                 // L[lane][c], c < lane
     }
-    if (lane < N2) {
+    if (LANE_IS(lane < N2)) {
 #pragma unroll
         for (int c = 0; c < N - 1; c++) Ls[(16 + lane) * (N + 1) + c] = a1[c];       // L[16 + lane][c], c < 16 + lane
     }
@@ -354,7 +355,7 @@ __device__ __forceinline__ int ldl_solve_regs(double (&a)[N], double (&b)[M], un
         for (int r = 0; r < M; r++) b[r] *= myinv;                // w = D^-1 z
         WSTAMP(41);
         WSYNC();
-        if (lane < N) {
+        if (LANE_IS(lane < N)) {
 #pragma unroll
             for (int c = 0; c < N - 1; c++) Ls[lane * (N + 1) + c] = a[c];          // L[lane][c], c < lane
         }
@@ -382,7 +383,7 @@ __device__ __forceinline__ int ldl_solve_regs(double (&a)[N], double (&b)[M], un
 #pragma unroll
     for (int r = 0; r < M; r++) b[r] *= myinv;                    // w = D^-1 z
     WSYNC();
-    if (lane < N) {
+    if (LANE_IS(lane < N)) {
 #pragma unroll
         for (int c = 0; c < N - 1; c++) Ls[lane * (N + 1) + c] = a[c];              // L[lane][c], c < lane
     }
@@ -421,7 +422,7 @@ __device__ __forceinline__ void gj16_step(double (&a)[N], double (&b)[M], unsign
                 d = (rowon && d > dmin) ? d : 1.0;
             }
             const double invd = fast_rcp1(d);
-            const bool piv = __builtin_amdgcn_inverse_ballot_w64(0x0001000100010001ull << J);   // l16 == J as a constant lane mask: no compare per pivot
+            const bool piv = LANE_IS((lane & 15) == J);           // l16 == J as a constant lane mask: no compare per pivot
             const double nf = piv ? 0.0 : -(a[J] * invd);
             myinv = piv ? invd : myinv;
             dpp_fmac_self<J + 1, N - 1 - J, J>(a, nf);

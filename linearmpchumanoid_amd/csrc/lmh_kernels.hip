@@ -354,6 +354,10 @@ __device__ __forceinline__ void sincos_r(float x, float *s, float *c) { sincosf(
 // generalizedFunctions.cpp:52-72).  Reads L[P_Q], writes A_T (30 x 3x4) and L[P_SC].
 // AHEAD (helper wave of the rollout, inside the previous evaluation): the configuration comes from a register (lane i < 30 holds q_i)
 // instead of L[P_Q], the roll / pitch / yaw terms go to scratch, and the four the integrator reads (sin / cos of pitch and yaw) to `xd4`.
+// lane maps of phase_fk as functions of the lane id (LANE_IS): slot / chain lfr = l60 / 12 and entry lel = l60 % 12 of lane l60 = lane mod 60
+constexpr int fk_l60(int lane) { return lane < 60 ? lane : lane - 60; }
+constexpr int fk_lfr(int lane) { return fk_l60(lane) / 12; }
+constexpr int fk_lel(int lane) { return fk_l60(lane) % 12; }
 template <typename R, bool AHEAD = false>
 __device__ __forceinline__ void phase_fk(LV<R> L, const LV<R> lcoef, R qn = (R)0, int xd4 = P_SC + 52)
 {
@@ -362,39 +366,39 @@ __device__ __forceinline__ void phase_fk(LV<R> L, const LV<R> lcoef, R qn = (R)0
     // lane = (slot fr < 5, entry el < 12) for the local transforms AND (chain c = fr, entry el) for the chain products; lanes 60..63 repeat
     // lanes 0..3 (the first row of chain 0: a complete quad, so its quad broadcasts see what lanes 0..3 see) -- no lane is switched off, and
     // everything derived from the lane is formed once.
-    const unsigned l60 = (unsigned)((lane < 60) ? lane : lane - 60);
+    const unsigned l60 = (unsigned)((LANE_IS(lane < 60)) ? lane : lane - 60);
     const int lfr = (int)(__umul24(l60, 43u) >> 9), lel = (int)l60 - 12 * lfr;       // l60 / 12, l60 % 12 (exact below 60)
     // DH coefficient loads (L2-resident table) are issued first: their latency hides behind the sincos.  Five of the 28 local transforms
     // per round, six rounds.  An entry takes at most one trigonometric term, and which one depends on its position in the 3 x 4 only
     // (Khalil DH: columns 0, 1 of every row; cos in (0,0), (1,1), (2,1), sin in (0,1), (1,0), (2,0)): two coefficients per entry are loaded
-    const bool cosT = (lel == 0) || (lel == 5) || (lel == 9);
+    const bool cosT = LANE_IS(fk_lel(lane) == 0 || fk_lel(lane) == 5 || fk_lel(lane) == 9);
     const int ksel = cosT ? 1 : 2;
     R c0[6], ck[6];
     {
-        const LV<R> cf = lcoef + 3 * (12 * lfr + lel), cf5 = lcoef + 3 * (12 * ((lfr < 3) ? 25 + lfr : 27) + lel);     // round 5: slots 25..27 (28, 29 do not exist)
+        const LV<R> cf = lcoef + 3 * (12 * lfr + lel), cf5 = lcoef + 3 * (12 * (LANE_IS(fk_lfr(lane) < 3) ? 25 + lfr : 27) + lel);     // round 5: slots 25..27 (28, 29 do not exist)
 #pragma unroll
         for (int u = 0; u < 6; u++) {
             const LV<R> cu = (u < 5) ? cf + 180 * u : cf5;
             c0[u] = cu[0]; ck[u] = cu[ksel];
         }
     }
-    const double dh_off = c_dh_off[(lane < 24) ? lane : 0];        // theta offsets, Robot.cpp:59-87 (constant memory, L2-resident like lcoef)
+    const double dh_off = c_dh_off[(LANE_IS(lane < 24)) ? lane : 0];        // theta offsets, Robot.cpp:59-87 (constant memory, L2-resident like lcoef)
     R qa = (R)0, qpos = (R)0;
     if constexpr (AHEAD) {                                         // lane permutes, outside the branches
-        qa = __shfl(qn, (lane < 24) ? 6 + lane : (lane >= 25 && lane < 28) ? lane - 22 : 0, 64);
-        qpos = __shfl(qn, (lane < 12) ? (lane >> 2) : 0, 64);
+        qa = __shfl(qn, (LANE_IS(lane < 24)) ? 6 + lane : (LANE_IS(lane >= 25 && lane < 28)) ? lane - 22 : 0, 64);
+        qpos = __shfl(qn, (LANE_IS(lane < 12)) ? (lane >> 2) : 0, 64);
     }
-    if (lane < 28) {                                               // one sincos for the 24 joint angles and roll / pitch / yaw
+    if (LANE_IS(lane < 28)) {                                               // one sincos for the 24 joint angles and roll / pitch / yaw
         R x;
-        if constexpr (AHEAD) x = (lane < 24) ? qa + (R)dh_off : qa;
-        else x = (lane < 24) ? (R)L[P_Q + 6 + lane] + (R)dh_off : (R)L[P_Q + 3 + ((lane >= 25) ? lane - 25 : 0)];
+        if constexpr (AHEAD) x = (LANE_IS(lane < 24)) ? qa + (R)dh_off : qa;
+        else x = (LANE_IS(lane < 24)) ? (R)L[P_Q + 6 + lane] + (R)dh_off : (R)L[P_Q + 3 + ((LANE_IS(lane >= 25)) ? lane - 25 : 0)];
         R s, c;
         sincos_r(x, &s, &c);
-        if (lane == 24) { s = -1.0; c = CPI2; }                    // theta[24] = -pi/2 (Robot.cpp:87)
-        const int so = (lane < 25) ? P_SC + 2 * lane : RPY + 2 * (lane - 25);
+        if (LANE_IS(lane == 24)) { s = -1.0; c = CPI2; }                    // theta[24] = -pi/2 (Robot.cpp:87)
+        const int so = (LANE_IS(lane < 25)) ? P_SC + 2 * lane : RPY + 2 * (lane - 25);
         L[so] = s;
         L[so + 1] = c;
-        if (AHEAD && lane >= 26) { L[xd4 + 2 * (lane - 26)] = s; L[xd4 + 2 * (lane - 26) + 1] = c; }
+        if (AHEAD && LANE_IS(lane >= 26)) { L[xd4 + 2 * (lane - 26)] = s; L[xd4 + 2 * (lane - 26) + 1] = c; }
     }
     WSYNC();
     SUBSTAMP(0);
@@ -409,14 +413,15 @@ __device__ __forceinline__ void phase_fk(LV<R> L, const LV<R> lcoef, R qn = (R)0
 #pragma unroll
         for (int u = 0; u < 6; u++) o[60 * u] = fma(ck[u], (R)sc[10 * u], c0[u]);
     }
-    if (lane < 12) {                                               // T0 = [R(rpy) p]
-        const int r = lane >> 2, col = lane & 3;
+    if (LANE_IS(lane < 12)) {                                               // T0 = [R(rpy) p]
+        const int r = lane >> 2;
         const R sr = L[RPY + 0], cr = L[RPY + 1], sp = L[RPY + 2], cp = L[RPY + 3], sy = L[RPY + 4], cy = L[RPY + 5];
         R val;
-        if (col == 3) { if constexpr (AHEAD) val = qpos; else val = L[P_Q + r]; }
-        else if (r == 0) val = (col == 0) ? cy * cp : (col == 1) ? cy * sp * sr - sy * cr : cy * sp * cr + sy * sr;
-        else if (r == 1) val = (col == 0) ? sy * cp : (col == 1) ? sy * sp * sr + cy * cr : sy * sp * cr - cy * sr;
-        else val = (col == 0) ? -sp : (col == 1) ? cp * sr : cp * cr;
+        const bool col0 = LANE_IS((lane & 3) == 0), col1 = LANE_IS((lane & 3) == 1);
+        if (LANE_IS((lane & 3) == 3)) { if constexpr (AHEAD) val = qpos; else val = L[P_Q + r]; }
+        else if (LANE_IS((lane >> 2) == 0)) val = col0 ? cy * cp : col1 ? cy * sp * sr - sy * cr : cy * sp * cr + sy * sr;
+        else if (LANE_IS((lane >> 2) == 1)) val = col0 ? sy * cp : col1 ? sy * sp * sr + cy * cr : sy * sp * cr - cy * sr;
+        else val = col0 ? -sp : col1 ? cp * sr : cp * cr;
         L[A_T0S + lane] = val;
     }
     SUBSTAMP(1);
@@ -431,7 +436,7 @@ __device__ __forceinline__ void phase_fk(LV<R> L, const LV<R> lcoef, R qn = (R)0
     // head (c = 4): steps 0..2 (local 22 + s -> T 25 + s).  So local slot and T slot of a step are (per-lane base) + s except at the
     // legs' ends; a step a chain does not have works on whatever valid slot that gives and stores into T slot 28 / 29, which nobody reads.
     const int c = lfr, el = lel, col = el & 3;
-    const bool leg = c < 2, head = c == 4;
+    const bool leg = LANE_IS(fk_lfr(lane) < 2), head = LANE_IS(fk_lfr(lane) == 4);
     const int lb = leg ? 6 * c - 1 : head ? 22 : 5 * c + 2;        // local slot of step s = lb + s
     const int db = leg ? 7 * c : head ? 25 : 5 * c + 5;            // T slot of step s = db + s
     WSYNC();
@@ -446,9 +451,9 @@ __device__ __forceinline__ void phase_fk(LV<R> L, const LV<R> lcoef, R qn = (R)0
         }
     }
     WSYNC();                                                       // every lane has its local transforms: their place is free
-    if (lane < 12) L[A_T + lane] = tcur;
+    if (LANE_IS(lane < 12)) L[A_T + lane] = tcur;
     {
-        const R m3 = (col == 3) ? (R)1 : (R)0;
+        const R m3 = LANE_IS((fk_lel(lane) & 3) == 3) ? (R)1 : (R)0;
         const LV<R> Dr = L + (A_T + 12 * db + el), Dx = L + (A_T + 12 * 28 + el);        // regular destination of step s: Dr + 12 s | the unread slot
         const LV<R> D0 = leg ? Dx + 12 * c : Dr;
 #pragma unroll
@@ -500,13 +505,16 @@ __device__ __forceinline__ TreeRows tree_rows()
 // 6 x 6 image (A_XF, zero block included).
 // NW = 2: wave 0 owns frames 0..13 and the persistent copies, wave 1 the CoM and frames 14..27 (B of a frame needs
 // only that frame's E, p, so the two halves never wait for each other; the caller joins them).
+// lane maps of phase_com_x as functions of the lane id (LANE_IS): frame slot / entry e9 = 3 a + col of lane min(lane, 62)
+constexpr int cx_ln(int lane) { return lane < 62 ? lane : 62; }
+constexpr int cx_col(int lane) { return cx_ln(lane) % 9 % 3; }
 template <int NW, typename R>
 __device__ __forceinline__ void phase_com_x(LV<R> L, int wid)
 {
     const int lane = LANE;
     if (wid == NW - 1) {                                           // NW = 2: the CoM reduction rides on wave 1 (wave 0 also makes the persistent copies)
         R cx = 0, cy = 0, cz = 0;
-        if (lane < 28) {
+        if (LANE_IS(lane < 28)) {
             const LV<R> T = L + A_T + 12 * lane, mo = L + P_MODEL + LMH_BODY_STRIDE * lane;
             const R m = mo[12];
             if (m != 0.0) {
@@ -519,8 +527,8 @@ __device__ __forceinline__ void phase_com_x(LV<R> L, int wid)
         cx = wave_sum(cx); cy = wave_sum(cy); cz = wave_sum(cz);
         {   // one division sequence for the three components (lanes 0..2), not three on lane 0
             const R mass = L[P_MODEL + 392];
-            const R num = (lane == 0) ? cx : (lane == 1) ? cy : cz;
-            L[(lane < 3) ? P_COM + lane : (int)P_DUMP] = num / mass;
+            const R num = LANE_IS(lane == 0) ? cx : LANE_IS(lane == 1) ? cy : cz;
+            L[LANE_IS(lane < 3) ? P_COM + lane : (int)P_DUMP] = num / mass;
         }
     }
     SUBSTAMP(2);
@@ -556,7 +564,7 @@ __device__ __forceinline__ void phase_com_x(LV<R> L, int wid)
         constexpr int PR = (NW == 1) ? 2 : 1;
 #pragma unroll
         for (int u = 0; u < PR; u++) {
-            const bool on = (NW == 2) ? (fr3 < 14) : (21 * u + fr3 < 27);
+            const bool on = (NW == 2) ? LANE_IS(cx_ln(lane) / 3 < 14) : (21 * u + fr3 < 27);
             const int i = on ? j0 + 21 * u : 1;
             const LV<R> Ti = L + (A_T + 12 * i + 3), Tp = L + (A_T + 12 * f_parent(i));
             const R t0 = Tp[a3], t1 = Tp[4 + a3], t2 = Tp[8 + a3];
@@ -565,9 +573,9 @@ __device__ __forceinline__ void phase_com_x(LV<R> L, int wid)
             L[on ? A_XP + 3 * i + a3 : (int)NE_DUMP + 8] = v1 + v2;
         }
     }
-    if (wid == 0 && lane < 12) {                                   // frame 0: E = R0, p = p0
+    if (wid == 0 && LANE_IS(lane < 12)) {                          // frame 0: E = R0, p = p0
         const LV<R> T0 = L + A_T;
-        if (lane < 9) {
+        if (LANE_IS(lane < 9)) {
             const int a0 = lane / 3, c0 = lane % 3;
             const R v = T0[a0 * 4 + c0];
             L[A_XF + 6 * c0 + a0] = v; L[A_XF + 6 * (3 + c0) + 3 + a0] = v; L[A_XF + 6 * c0 + 3 + a0] = 0.0;
@@ -579,8 +587,9 @@ __device__ __forceinline__ void phase_com_x(LV<R> L, int wid)
     {   // B = (-E') [p]x, entry (a, b) = sg1 E[r1][a] p[j1] + sg2 E[r2][a] p[j2]; same lane map (a, bb = col); frames: wave 0 0..13,
         // wave 1 14..27 (NW = 1: 0..27)
         const int bb = col;
-        const int r1 = (bb == 0) ? 1 : 0, j1 = (bb == 2) ? 1 : 2, r2 = (bb == 2) ? 1 : 2, j2 = (bb == 0) ? 1 : 0;
-        const R sg1 = (bb == 1) ? (R)1 : (R)-1, sg2 = (bb == 1) ? (R)-1 : (R)1;
+        const bool bb0 = LANE_IS(cx_col(lane) == 0), bb1 = LANE_IS(cx_col(lane) == 1), bb2 = LANE_IS(cx_col(lane) == 2);
+        const int r1 = bb0 ? 1 : 0, j1 = bb2 ? 1 : 2, r2 = bb2 ? 1 : 2, j2 = bb0 ? 1 : 0;
+        const R sg1 = bb1 ? (R)1 : (R)-1, sg2 = bb1 ? (R)-1 : (R)1;
         const int ib = ((NW == 2 && wid == 1) ? 14 : 0) + fr;
         const LV<R> X0 = L + (A_XF + (int)__umul24((unsigned)ib, 36u) + 6 * a), q0 = L + (A_XP + 3 * ib);    // E[row][a] = A[a][row]: contiguous in the row index
         const LV<R> X1 = X0 + r1, X2 = X0 + r2, q1 = q0 + j1, q2 = q0 + j2, Ob = X0 + (18 + bb);
@@ -595,18 +604,19 @@ __device__ __forceinline__ void phase_com_x(LV<R> L, int wid)
     WSTAMP(48);
     if (wid == 0) {
         // persistent copies: T0, T7, T14, X0 = E0 (9) | p0 (3) | B0 (9)
-        if (lane < 36) L[P_TB + lane] = L[A_T + 12 * ((lane < 12) ? 0 : (lane < 24) ? 7 : 14) + lane % 12];
-        if (lane < 21) {
-            const int e = (lane < 9) ? lane : (lane < 12) ? 0 : lane - 12, a0 = e / 3, b0 = e % 3;
-            L[P_X0 + lane] = (lane < 9) ? L[A_XF + 6 * b0 + a0] : (lane < 12) ? L[A_XP + lane - 9] : L[A_XF + 6 * (3 + a0) + b0];
+        if (LANE_IS(lane < 36)) L[P_TB + lane] = L[A_T + 12 * (LANE_IS(lane < 12) ? 0 : LANE_IS(lane < 24) ? 7 : 14) + lane % 12];
+        if (LANE_IS(lane < 21)) {
+            const int e = LANE_IS(lane < 9) ? lane : LANE_IS(lane < 12) ? 0 : lane - 12, a0 = e / 3, b0 = e % 3;
+            L[P_X0 + lane] = LANE_IS(lane < 9) ? L[A_XF + 6 * b0 + a0] : LANE_IS(lane < 12) ? L[A_XP + lane - 9] : L[A_XF + 6 * (3 + a0) + b0];
         }
         // base-frame reordered velocities, stale (Robot::v_: lanes 0..29) and fresh (lanes 32..61): swapBaseVelocityAndRefToWorldFrame
         {
-            const int which = lane >> 5, i = lane & 31, ic = (i < 30) ? i : 29, i6 = (i < 6) ? i : 0;
+            const bool which = LANE_IS(lane >= 32), i_lt6 = LANE_IS((lane & 31) < 6);
+            const int i = lane & 31, ic = (i < 30) ? i : 29, i6 = i_lt6 ? i : 0;
             const LV<R> v = L + (which ? P_V : P_VP), X = L + A_XF + 6 * i6;              // row i of X_0
             const R dot = ((R)X[0] * (R)v[3] + (R)X[1] * (R)v[4] + (R)X[2] * (R)v[5]) + ((R)X[3] * (R)v[0] + (R)X[4] * (R)v[1] + (R)X[5] * (R)v[2]);
             const R cpy = v[ic];
-            L[(which ? P_VHN : P_VHS) + ic] = (i < 6) ? dot : cpy;     // (lanes 30, 31 / 62, 63 repeat entry 29)
+            L[(which ? P_VHN : P_VHS) + ic] = i_lt6 ? dot : cpy;       // (lanes 30, 31 / 62, 63 repeat entry 29)
         }
     }
     WSYNC();
@@ -619,14 +629,15 @@ __device__ __forceinline__ void phase_com_x(LV<R> L, int wid)
 // this buys: no "idle lane" store switches at all -- every store address is (per-lane base, computed once per sweep) + (compile-time offset
 // of the level).  The left-arm row repeats the right-arm row's head frames at depths 5, 6 in the same way.
 struct TreeDup { int rho, r, fb, fa, adj; bool arms; };
+constexpr int dup_r(int lane) { return (int)((0x5210543210543210ull >> (4 * (lane & 15))) & 15ull); }   // TreeDup::r of the lane (LANE_IS)
 __device__ __forceinline__ TreeDup tree_dup()
 {
     TreeDup t;
     const int lane = LANE, l16 = lane & 15;
     t.rho = lane >> 4;
     t.r = (int)((0x5210543210543210ull >> (4 * l16)) & 15ull);
-    t.arms = t.rho >= 2;
-    t.fb = 1 + 7 * t.rho - ((t.rho == 3) ? 2 : 0);               // 1, 8, 15, 20: depths 0..4
+    t.arms = LANE_IS(lane >= 32);
+    t.fb = 1 + 7 * t.rho - (LANE_IS(lane >= 48) ? 2 : 0);               // 1, 8, 15, 20: depths 0..4
     t.fa = t.arms ? 20 : t.fb;                                     // depths 5, 6: the head (25, 26) behind either arm
     t.adj = t.arms ? 2 : t.rho;                                    // act(frame) = frame - adj on every limb (Robot.cpp:172)
     return t;
@@ -665,8 +676,8 @@ __device__ __forceinline__ void phase_newton_euler(LV<R> L)
     if constexpr (!LIN) L[A_ACC0 + r] = 0.0;
     {   // velocity and acceleration sweeps down the limbs, one frame per depth, recurrences in registers:
         // v_i = X_i v_p + S qd_i; a_i = X_i a_p + crm(v_i) S qd_i (with / without gravity in the base acceleration)
-        const R s2 = (r == 2) ? (R)1 : (R)0;                       // S = e_z (angular): component 2
-        const R ca = (r == 0 || r == 3) ? (R)1 : (R)0, cb = (r == 1 || r == 4) ? (R)-1 : (R)0;   // crm(v) S = (wy, -wx, 0, vy, -vx, 0)
+        const R s2 = LANE_IS(dup_r(lane) == 2) ? (R)1 : (R)0;      // S = e_z (angular): component 2
+        const R ca = LANE_IS(dup_r(lane) == 0 || dup_r(lane) == 3) ? (R)1 : (R)0, cb = LANE_IS(dup_r(lane) == 1 || dup_r(lane) == 4) ? (R)-1 : (R)0;   // crm(v) S = (wy, -wx, 0, vy, -vx, 0)
         R pv = bv, pg = bg, p0 = 0;
         // the coefficients do not depend on the recursion: all seven depths' loads are issued up front (49 doubles), so that the sweep
         // itself never waits for LDS
@@ -704,7 +715,7 @@ __device__ __forceinline__ void phase_newton_euler(LV<R> L)
     WSTAMP(49);
     // body forces f = I a + v x* (I v), one lane per (body, which)
     {
-        const bool fon = lane < (LIN ? 25 : 50);
+        const bool fon = LANE_IS(lane < (LIN ? 25 : 50));
         const int which = (!LIN && fon) ? lane / 25 : 0, i = f_body(LIN ? (fon ? lane : 0) : lane % 25);
         const LV<R> mo = L + P_MODEL + LMH_BODY_STRIDE * i;
         const LV<R> v = L + A_VEL + 6 * i, a = L + (which ? A_ACC0 : A_ACCG) + 6 * i;
@@ -742,7 +753,7 @@ __device__ __forceinline__ void phase_newton_euler(LV<R> L)
         const LV<R> Xcb = L + (A_XF + 36 * tr.fb + r), Xca = L + (A_XF + 36 * tr.fa + r);              // column r of X_f: stride 6
         const LV<R> Fb = L + (A_FG + 6 * tr.fb + r), Fa = L + (A_FG + 6 * tr.fa + r);                  // A_FG | + 168 A_F0
         // C[5 + act(frame)] = fs[2] (with gravity): the lanes that hold component 2 store, the others go to the dump; depth 6: arms only
-        const bool r2 = r == 2;
+        const bool r2 = LANE_IS(dup_r(lane) == 2);
         const LV<R> Cb = L + (r2 ? CDST + 5 + tr.fb - tr.adj : (int)NE_DUMP), Ca5 = L + (r2 ? CDST + 5 + tr.fa - tr.adj : (int)NE_DUMP);
         const LV<R> Ca6 = L + ((r2 && tr.arms) ? CDST + 5 + tr.fa - tr.adj : (int)NE_DUMP);
         const LV<R> Pk5 = L + (tr.arms ? A_VEL + 48 + r : (int)NE_DUMP + 8);                          // the head's root -> base slot 4 (arm rows)
@@ -786,7 +797,7 @@ __device__ __forceinline__ void phase_newton_euler(LV<R> L)
     WSYNC();
     SUBSTAMP(8);
     WSTAMP(51);
-    if (lane < (LIN ? 6 : 12)) {                                   // base: head, LA, RA, LL, RL (Dynamics.cpp:157-162 order)
+    if (LANE_IS(lane < (LIN ? 6 : 12))) {                          // base: head, LA, RA, LL, RL (Dynamics.cpp:157-162 order)
         const int w2 = LIN ? 0 : lane / 6, k2 = LIN ? lane : lane % 6;
         R acc = L[(w2 ? A_F0 : A_FG) + k2];
 #pragma unroll
@@ -794,7 +805,7 @@ __device__ __forceinline__ void phase_newton_euler(LV<R> L)
         if constexpr (PLANT) { if (w2 == 0) L[P_VHS + k2] = acc; }
         else { if (w2 == 0) L[P_C + k2] = acc; else L[P_CG + k2] = acc; }
     }
-    if (!LIN && !PLANT && lane >= 40 && lane < 52) {               // Jpqp = blkdiag(R,R) acc0[sole]   (LIN: refs_jpqp, behind the Jacobian)
+    if (!LIN && !PLANT && LANE_IS(lane >= 40 && lane < 52)) {               // Jpqp = blkdiag(R,R) acc0[sole]   (LIN: refs_jpqp, behind the Jacobian)
         const int foot = (lane - 40) / 6, k2 = (lane - 40) % 6, rr = k2 % 3, o = (k2 / 3) * 3;
         const LV<R> T = L + P_TB + 12 * (1 + foot), a = L + A_ACC0 + 6 * (foot ? 14 : 7);
         L[P_JPQP + 6 * foot + k2] = T[4 * rr] * a[o] + T[4 * rr + 1] * a[o + 1] + T[4 * rr + 2] * a[o + 2];
@@ -920,7 +931,7 @@ __device__ __forceinline__ void phase_crba_rows(LV<R> L)
     WSYNC();
     SUBSTAMP(10);
     WSTAMP(52);
-    if (lane < 6) {                                                // Ic0 = I0 + head + LA + RA + LL + RL (Dynamics.cpp:80-82 order)
+    if (LANE_IS(lane < 6)) {                                                // Ic0 = I0 + head + LA + RA + LL + RL (Dynamics.cpp:80-82 order)
         const LV<R> mo = L + P_MODEL;
         R acc[6];
 #pragma unroll
@@ -1006,14 +1017,14 @@ __device__ __forceinline__ void phase_crba_mfma(double *L, const IbSel &g)
     // Block 3 (left arm) repeats block 2's head frames at levels 0, 1 (same inputs, same instructions: the stores carry the same bits), and
     // the legs run their massless sole at level 0 on zeros (lmh_set_model insists on that), so no level switches a block off.
     const int rho = lane >> 4, b = (lane >> 2) & 3, q = lane & 3;
-    const bool leg = b < 2, r2 = rho == 2;
+    const bool leg = LANE_IS(((lane >> 2) & 3) < 2), r2 = LANE_IS((lane >> 4) == 2), q2 = LANE_IS((lane & 3) == 2);
     const int fb = leg ? 1 + 7 * b : 5 + 5 * b;                   // 1, 8, 15, 20: frames of levels 2..6 = fb + d (d = 6 - level)
     const int jst = leg ? 6 * b : 2 + 5 * b;                      // 0, 6, 12, 17: first joint of the limb
     const int dh = leg ? 0 : 20 - fb;                             // levels 0, 1: the legs go on (sole, ankle roll), both arm blocks work on the head (26, 25)
     double *const dump = L + (CR_DUMP + 24);
     // (the matrix-core tiles of the QP set-up read two entries past row 5 of P_MTOP, i.e. P_HL[0..1], against zero padding: H has to be
     // finite in EVERY evaluation, also in the ones whose torques nobody asks for -- found with the -DLMH_POISON build)
-    L[P_HL + lane] = 0.0; L[P_HL + 64 + lane] = 0.0; L[(lane < 16) ? P_HL + 128 + lane : (int)CR_DUMP] = 0.0;       // entries outside a limb's block stay zero
+    L[P_HL + lane] = 0.0; L[P_HL + 64 + lane] = 0.0; L[LANE_IS(lane < 16) ? P_HL + 128 + lane : (int)CR_DUMP] = 0.0;       // entries outside a limb's block stay zero
     // X tiles: element (4 tk + rho, 4 tj + q) of the frame's image; outside the 6 x 6 -> a stored zero of the image (row 0, column 3)
     int xo[4], xt[4];
     bool tin[4];
@@ -1030,9 +1041,9 @@ __device__ __forceinline__ void phase_crba_mfma(double *L, const IbSel &g)
         mp[0][t] = L + (P_MODEL + LMH_BODY_STRIDE * fb + g.i[0][t]); mp[1][t] = L + (P_MODEL + LMH_BODY_STRIDE * fb + g.i[1][t]);
     }
     // store pointers (see the level loop): joint-space inertia P_HL[6 a + local column], F2 columns P_MTOP[30 row + 6 + joint]
-    const bool ex0 = q >= (leg ? 1 : 2), ex1 = q <= 2;            // column slot 4 tj + q belongs to the limb (legs: 1..6, arms: 2..6)
-    double *const pD = (r2 && q == 2) ? L + (P_HL + 6 * jst) : dump;                                   // H(a, a): + 7 d
-    double *const pDh = (r2 && q == 2 && !leg) ? L + (P_HL + 6 * 22 - 35) : dump;                      // the head's: + 7 d (d = 6, 5)
+    const bool ex0 = LANE_IS((lane & 3) >= ((((lane >> 2) & 3) < 2) ? 1 : 2)), ex1 = LANE_IS((lane & 3) <= 2);            // column slot 4 tj + q belongs to the limb (legs: 1..6, arms: 2..6)
+    double *const pD = (r2 && q2) ? L + (P_HL + 6 * jst) : dump;                                   // H(a, a): + 7 d
+    double *const pDh = (r2 && q2 && !leg) ? L + (P_HL + 6 * 22 - 35) : dump;                      // the head's: + 7 d (d = 6, 5)
     double *const pH1[2] = {(r2 && ex0) ? L + (P_HL + 6 * jst - q) : dump, (r2 && ex1) ? L + (P_HL + 6 * jst - q) : dump};                  // H(parent, column): + 6 d - 4 tj
     double *const pH2[2] = {(r2 && ex0) ? L + (P_HL + 6 * jst - 6 * q + 35) : dump, (r2 && ex1) ? L + (P_HL + 6 * jst - 6 * q + 35) : dump}; // H(column, parent): + d - 24 tj
     double Z[4] = {0, 0, 0, 0}, F[4] = {0, 0, 0, 0};              // tiles t = 2 (row tile) + (column tile)
@@ -1117,7 +1128,7 @@ __device__ __forceinline__ void phase_crba_mfma(double *L, const IbSel &g)
     WSYNC();
     SUBSTAMP(10);
     WSTAMP(52);
-    if (lane < 6) {                                                // Ic0 = I0 + head + LA + RA + LL + RL (Dynamics.cpp:80-82 order)
+    if (LANE_IS(lane < 6)) {                                                // Ic0 = I0 + head + LA + RA + LL + RL (Dynamics.cpp:80-82 order)
         const BodyRow6<double> bs = body_row6<double>(lane);
         const double *mo = L + P_MODEL;
         double acc[6];
@@ -1143,10 +1154,10 @@ __device__ __forceinline__ void phase_crba(LV<R> L, const IbSel &g)
     if constexpr (std::is_same_v<R, double>) {
         phase_crba_mfma(L.p, g);
         // the gravity part of the bias' base rows, Ic_0 gamma_0 with gamma_0 = 9.81 (0 0 0 | third row of E0): see phase_newton_euler (ONE CHAIN)
-        const int lane = LANE, k = (lane < 6) ? lane : 0;
+        const int lane = LANE, k = LANE_IS(lane < 6) ? lane : 0;
         const double *m = L.p + P_MTOP + 30 * k + 3, *e2 = L.p + P_X0 + 6;
         const double gv = 9.81 * (m[0] * e2[0] + m[1] * e2[1] + m[2] * e2[2]);
-        if (lane < 6) L.p[P_CG + lane] = gv;
+        if (LANE_IS(lane < 6)) L.p[P_CG + lane] = gv;
     }
     else phase_crba_rows<R>(L);
 }
@@ -1194,7 +1205,7 @@ __device__ __forceinline__ void phase_jacobian(LV<R> L)
     WSYNC();
     {   // rotate to world axes: J[ft][3 b + r3][col] = sum_k R_sole[r3][k] JL[ft][3 b + k][col].  DPP row q = (ft, b), lane = column (lanes
         // 12..15 repeat columns 0..3); three outputs per lane
-        const int lane = LANE, q = lane >> 4, l16 = lane & 15, col = (l16 < 12) ? l16 : l16 - 12, ft = q & 1, b3 = q >> 1;
+        const int lane = LANE, q = lane >> 4, l16 = lane & 15, col = LANE_IS((lane & 15) < 12) ? l16 : l16 - 12, ft = q & 1, b3 = q >> 1;
         const LV<R> T = L + (P_TB + 12 + 12 * ft), J = L + (A_JL + 72 * ft + 36 * b3 + col), O = L + (P_JC + 72 * ft + 36 * b3 + col);
         const R j0 = J[0], j1 = J[12], j2 = J[24];
 #pragma unroll
@@ -1208,12 +1219,12 @@ __device__ __forceinline__ void phase_jacobian(LV<R> L)
 // phase_newton_euler has parked the soles' ag raw in P_JPQP; runs behind phase_jacobian, in place.
 __device__ __forceinline__ void refs_jpqp(double *L)
 {
-    const int lane = LANE, l12 = (lane < 12) ? lane : 0, foot = l12 / 6, k2 = l12 % 6, rr = k2 % 3, o = (k2 / 3) * 3;
+    const int lane = LANE, l12 = LANE_IS(lane < 12) ? lane : 0, foot = l12 / 6, k2 = l12 % 6, rr = k2 % 3, o = (k2 / 3) * 3;
     const double *T = L + P_TB + 12 * (1 + foot) + 4 * rr, *a = L + P_JPQP + 6 * foot + o, *J = L + P_JC + 72 * foot + 12 * k2 + 3, *e2 = L + P_X0 + 6;
     double val = T[0] * a[0] + T[1] * a[1] + T[2] * a[2];
     val -= 9.81 * (J[0] * e2[0] + J[1] * e2[1] + J[2] * e2[2]);
     __builtin_amdgcn_sched_barrier(0);                             // every lane has read the raw accelerations before any lane overwrites them
-    if (lane < 12) L[P_JPQP + lane] = val;
+    if (LANE_IS(lane < 12)) L[P_JPQP + lane] = val;
     WSYNC();
 }
 
@@ -1275,15 +1286,15 @@ __device__ __forceinline__ void refs_prepare(double *L, LmhCParams &P, int inst,
         if (P.n_seg > 0) {                                         // walking extension: swing-polynomial segment of sample k, x axis in units of the step length
             const double *sg = P.segs + (size_t)LMH_SEG_STRIDE * ((size_t)P.seg_stride * (size_t)inst + (size_t)(P.seg_of_sample + ro)[k0]);
             const double xs = L[P_RXS];
-            if (lane < 48) L[P_POLY + lane] = sg[1 + lane] * (((lane % 24) < 8) ? xs : 1.0);
-            else if (lane < 54) L[P_POLY + lane] = 8.0;
-            else if (lane == 54) L[P_RT0] = sg[0];
+            if (LANE_IS(lane < 48)) L[P_POLY + lane] = sg[1 + lane] * (LANE_IS((lane % 24) < 8) ? xs : 1.0);
+            else if (LANE_IS(lane < 54)) L[P_POLY + lane] = 8.0;
+            else if (LANE_IS(lane == 54)) L[P_RT0] = sg[0];
         }
         sx = wave_sum(sx); sy = wave_sum(sy);
-        if (lane == 0) { L[P_PRE] = sx; L[P_PRE + 1] = sy; L[P_RK] = (double)k; L[P_RPH] = (double)ph; }
+        if (LANE_IS(lane == 0)) { L[P_PRE] = sx; L[P_PRE + 1] = sy; L[P_RK] = (double)k; L[P_RPH] = (double)ph; }
         WSYNC();
     }
-    if (lane >= 16 && lane < 22) {                                 // polyval / polyder of the foot references (controller.cpp:355-386)
+    if (LANE_IS(lane >= 16 && lane < 22)) {                        // polyval / polyder of the foot references (controller.cpp:355-386)
         const int ft = (lane - 16) / 3, ax = (lane - 16) % 3;
         double co[8];
         const double tl = t - L[P_RT0];
@@ -1319,7 +1330,7 @@ template <bool CGLIN>
 __device__ __forceinline__ void refs_agpqp(double *L, double mass, bool ang)
 {
     const int lane = LANE;
-    if (lane < 6) {
+    if (LANE_IS(lane < 6)) {
         // CGLIN: Cg[0:6] = C[0:6] - Ic_0 gamma_0 (see phase_newton_euler); P_CG holds Ic_0 gamma_0 (refs_cg_gravity, behind the CRBA)
         const double *T0 = L + P_TB, *c = L + P_C, *pg = L + P_CG;
         double cg[6];
@@ -1327,7 +1338,7 @@ __device__ __forceinline__ void refs_agpqp(double *L, double mass, bool ang)
         for (int k = 0; k < 6; k++) cg[k] = CGLIN ? c[k] - pg[k] : pg[k];
         const int r = lane % 3;
         double val = 0.0;
-        if (lane < 3) { if (ang) {
+        if (LANE_IS(lane < 3)) { if (ang) {
             const double p0 = L[P_MTOP + 30 * 2 + 4] / mass, p1 = L[P_MTOP + 30 * 0 + 5] / mass, p2 = L[P_MTOP + 30 * 1 + 3] / mass;
             const double R0 = T0[4 * r], R1 = T0[4 * r + 1], R2 = T0[4 * r + 2];
             const double u0 = -(R1 * p2 + R2 * (-p1)), u1 = -(R0 * (-p2) + R2 * p0), u2 = -(R0 * p1 + R1 * (-p0));
@@ -1339,7 +1350,7 @@ __device__ __forceinline__ void refs_agpqp(double *L, double mass, bool ang)
 __device__ __forceinline__ void refs_vfoot_pdjoints(double *L, LmhCParams &P)
 {
     const int lane = LANE;
-    if (lane >= 8 && lane < 20) {                                  // foot velocities J vhat
+    if (LANE_IS(lane >= 8 && lane < 20)) {                         // foot velocities J vhat
         const int row = lane - 8, ft = row / 6;
         const double *J = L + P_JC + 72 * ft + 12 * (row % 6);
         double s = 0.0;
@@ -1347,12 +1358,13 @@ __device__ __forceinline__ void refs_vfoot_pdjoints(double *L, LmhCParams &P)
         for (int c = 0; c < 6; c++) s += J[6 + c] * L[P_VHN + 6 + 6 * ft + c];
         L[P_VFOOT + row] = s;
     }
-    if (lane >= 32 && lane < 62) {                                 // PDJointsAcc, controller.cpp:296-308
+    if (LANE_IS(lane >= 32 && lane < 62)) {                        // PDJointsAcc, controller.cpp:296-308
         const int i = lane - 32;
+        const bool body = LANE_IS(lane - 32 < 28);
         // Robot::desiredPosture (Robot.cpp:253-262): coordinates 0..27 ride in the spare slot of the model record (lmh_model_kernel); 28, 29 are 0
         const double qd0 = L[P_MODEL + LMH_BODY_STRIDE * ((i < 28) ? i : 27) + 13];
-        const double val = P.kp_joints * (((i < 28) ? qd0 : 0.0) - L[P_Q + i]) + P.kd_joints * (0.0 - L[P_V + i]);
-        L[P_QREF + ((i < 3) ? i + 3 : (i < 6) ? i - 3 : i)] = val;
+        const double val = P.kp_joints * ((body ? qd0 : 0.0) - L[P_Q + i]) + P.kd_joints * (0.0 - L[P_V + i]);
+        L[P_QREF + (LANE_IS(lane - 32 < 3) ? i + 3 : LANE_IS(lane - 32 < 6) ? i - 3 : i)] = val;
     }
 }
 __device__ __forceinline__ double readlane_f64(double v, int src_lane)       // wave-uniform copy of lane src_lane's value (two v_readlane_b32)
@@ -1428,7 +1440,7 @@ __device__ __forceinline__ void zoh_box_setup(LmhCParams &P, int inst)
 template <bool REF = false, bool BOX = false>
 __device__ __forceinline__ int refs_chain_a(double *L, LmhCParams &P, int inst, int k, double mass, bool ang, const double *ref = nullptr, double t = 0.0)
 {
-    const int lane = LANE, l16 = lane & 15, q4 = lane >> 4, a = (q4 < 3) ? q4 : 2;
+    const int lane = LANE, l16 = lane & 15, q4 = lane >> 4, a = LANE_IS((lane >> 4) < 3) ? q4 : 2;
     double rx[3] = {0.0, 0.0, 0.0}, ry[3] = {0.0, 0.0, 0.0};
     if constexpr (REF && !BOX) {
 #pragma unroll
@@ -1445,7 +1457,7 @@ __device__ __forceinline__ int refs_chain_a(double *L, LmhCParams &P, int inst, 
             L[P_AG + e] = R0 * Mt[0] + R1 * Mt[30] + R2 * Mt[60] + u0 * Mt[90] + u1 * Mt[120] + u2 * Mt[150];
         }
     }
-    const bool two = l16 < 14;
+    const bool two = LANE_IS((lane & 15) < 14);
     const int c0 = l16, c1 = two ? l16 + 16 : l16;
     const double *T0 = L + P_TB + 4 * a, *Mt = L + P_MTOP + 90, *vh = L + P_VHN;
     const double r0 = T0[0], r1 = T0[1], r2 = T0[2];
@@ -1493,20 +1505,21 @@ __device__ __forceinline__ int refs_chain_a(double *L, LmhCParams &P, int inst, 
         xp = P.a00 * cxp + P.a01 * vxp + P.b0 * ux; xv = P.a10 * cxp + P.a11 * vxp + P.b1 * ux;
         yp = P.a00 * cyp + P.a01 * vyp + P.b0 * uy; yv = P.a10 * cyp + P.a11 * vyp + P.b1 * uy;
     }
-    if (lane == 0) {
+    if (LANE_IS(lane == 0)) {
         L[P_MPC + 0] = ux; L[P_MPC + 1] = uy;
         L[P_MPC + 2] = xp; L[P_MPC + 3] = xv; L[P_MPC + 4] = ux;
         L[P_MPC + 5] = yp; L[P_MPC + 6] = yv; L[P_MPC + 7] = uy;
     }
-    if (lane < 3) {                                                // PDMomentumAcc (refs_pd_momentum); no angular momentum: h_ref[0:3] = kd (0 - 0)
-        const double posRef = (lane == 0) ? xp : (lane == 1) ? yp : zcom, velRef = (lane == 0) ? xv : (lane == 1) ? yv : 0.0;
-        const double accRef = (lane == 0) ? ux : (lane == 1) ? uy : 0.0;
-        const double cm = (lane == 0) ? cxp : (lane == 1) ? cyp : czp, cvl = (lane == 0) ? vxp : (lane == 1) ? vyp : vzp;
+    if (LANE_IS(lane < 3)) {                                       // PDMomentumAcc (refs_pd_momentum); no angular momentum: h_ref[0:3] = kd (0 - 0)
+        const bool l0 = LANE_IS(lane == 0), l1 = LANE_IS(lane == 1);
+        const double posRef = l0 ? xp : l1 ? yp : zcom, velRef = l0 ? xv : l1 ? yv : 0.0;
+        const double accRef = l0 ? ux : l1 ? uy : 0.0;
+        const double cm = l0 ? cxp : l1 ? cyp : czp, cvl = l0 ? vxp : l1 ? vyp : vzp;
         L[P_HREF + 3 + lane] = mass * (P.kp_mom * (posRef - cm) + P.kd_mom * (velRef - cvl) + accRef);
         L[P_COMV + lane] = cvl;
     }
     if (ang) WSYNC();                                              // the angular rows of AG
-    if (lane < 3) {                                                // angular momentum AG_ang vhat and its PD term
+    if (LANE_IS(lane < 3)) {                                       // angular momentum AG_ang vhat and its PD term
         double hs = 0.0;
         if (ang) for (int c = 0; c < 30; c++) hs += L[P_AG + 30 * lane + c] * L[P_VHN + c];
         L[P_ANGM + lane] = hs;
@@ -1522,7 +1535,7 @@ __device__ __forceinline__ int refs_chain_a(double *L, LmhCParams &P, int inst, 
 __device__ __forceinline__ void refs_feet_orientation(double *L, LmhCParams &P, const double *Ts, int stride)
 {
     const int lane = LANE;
-    if (lane >= 8 && lane < 10) {
+    if (LANE_IS(lane >= 8 && lane < 10)) {
         const int ft = lane - 8;
         const double *T = Ts + stride * ft;
         // err = R_des' R_foot with R_des = Rf_q0_ = [0 0 1; 0 -1 0; 1 0 0] (Robot.cpp:28-31) written out: row 0 = row 2 of R_foot, row 1 = -row 1,
@@ -1546,8 +1559,8 @@ __device__ __forceinline__ void refs_feet_orientation(double *L, LmhCParams &P, 
 __device__ __forceinline__ void refs_feet_angular_velocity_term(double *L, LmhCParams &P)     // P_FREF[angular] += kd (0 - omega_foot)
 {
     const int lane = LANE;
-    if (lane >= 8 && lane < 14) {
-        const int i6 = lane - 8, ft = (i6 >= 3) ? 1 : 0, a = i6 - 3 * ft;
+    if (LANE_IS(lane >= 8 && lane < 14)) {
+        const int i6 = lane - 8, ft = LANE_IS(lane - 8 >= 3) ? 1 : 0, a = i6 - 3 * ft;
         L[P_FREF + 6 * ft + a] = fma(P.kd_feet, 0.0 - L[P_VFOOT + 6 * ft + a], L[P_FREF + 6 * ft + a]);
     }
 }
@@ -1558,7 +1571,7 @@ __device__ __forceinline__ void refs_pd_feet(double *L, LmhCParams &P, int inst,
     const int lane = LANE;
     if (!ORI_MAYBE || __builtin_amdgcn_readfirstlane((int)L[P_ORI]) == 0) { refs_feet_orientation(L, P, L + P_TB + 12, 12); WSYNC(); }
     refs_feet_angular_velocity_term(L, P);
-    if (lane >= 16 && lane < 22) {                                 // position part, polynomials (polyval/polyder)
+    if (LANE_IS(lane >= 16 && lane < 22)) {                        // position part, polynomials (polyval/polyder)
         const int ft = (lane - 16) / 3, ax = (lane - 16) % 3;
         const double *pr = L + P_PRE + 4 + 3 * (3 * ft + ax);     // refs_prepare
         const double pv = pr[0], vv = pr[1], av = pr[2];
@@ -1757,7 +1770,7 @@ __device__ __forceinline__ int solve_compact2(double *L, unsigned F, int nF, int
 __device__ __forceinline__ int solve_free_set(double *L, unsigned F, double eps, double *z_out, double *lam_out)
 {
     const int lane = LANE, r = lane & 31, half = lane >> 5;
-    const bool inF = (lane < 32) && ((F >> lane) & 1u);
+    const bool inF = LANE_IS(lane < 32) && ((F >> lane) & 1u);
     const int nF = __popc(F);
     const int pos = __popc(F & ((1u << r) - 1u));
     int bad;
@@ -1767,13 +1780,13 @@ __device__ __forceinline__ int solve_free_set(double *L, unsigned F, double eps,
     else bad = solve_compact2(L, F, nF, pos, eps, &zr);
     const double zj = inF ? zr : 0.0;
     WSYNC();
-    if (lane < 32) L[P_CC + lane] = zj;
+    if (LANE_IS(lane < 32)) L[P_CC + lane] = zj;
     WSYNC();
     double s = 0.0;
     {   // (P z)_r = g_r' W (G z) + eps z_r through the wrench G z: three short LDS steps instead of a 32 x 32 image of P
         (void)half;
         double *wz = L + C_LS, *Wwz = L + C_LS + 16;               // the rows of L parked by the solve above are dead
-        if (lane < 12) {
+        if (LANE_IS(lane < 12)) {
             const int ft = lane / 6, k = lane % 6;
             double sacc = 0.0;
 #pragma unroll
@@ -1781,7 +1794,7 @@ __device__ __forceinline__ int solve_free_set(double *L, unsigned F, double eps,
             wz[lane] = sacc;
         }
         WSYNC();
-        if (lane < 12) {
+        if (LANE_IS(lane < 12)) {
             double sacc = 0.0;
 #pragma unroll
             for (int k = 0; k < 12; k++) sacc += L[P_W + 12 * lane + k] * wz[k];
@@ -1794,7 +1807,7 @@ __device__ __forceinline__ int solve_free_set(double *L, unsigned F, double eps,
         for (int k = 0; k < 6; k++) s += g[k] * y[k];
     }
     *z_out = zj;
-    *lam_out = (lane < 32 && !((F >> lane) & 1u)) ? s - L[P_QV + r] : 0.0;
+    *lam_out = (LANE_IS(lane < 32) && !((F >> lane) & 1u)) ? s - L[P_QV + r] : 0.0;
     return bad;
 }
 
@@ -1881,12 +1894,12 @@ __device__ __forceinline__ int solve_free_set_thin(double *L, unsigned F_in, dou
     const int bad = ldl_solve_regs<NT, 1>(a, b, (nF >= 32) ? 0xFFFFFFFFu : ((1u << nF) - 1u), L + C_LS, eps);     // + eps I: added where the pivots are read
     const double z = (lane < nF) ? b[0] : 0.0;                     // z_r in lane r; lanes 8..15 of the row must read as zeros below
     // w = G_F z (lanes 0..11: component kk of foot lane / 6), y = W w, r = y - h
-    const int l12 = (lane < 12) ? lane : 0;
-    const bool leftlane = l12 >= 6;
+    const int l12 = LANE_IS(lane < 12) ? lane : 0;
+    const bool leftlane = LANE_IS(lane >= 6 && lane < 12);
     const int kk = l12 - (leftlane ? 6 : 0);
     double wz = 0.0;
     thin_wrench<NT, 0>(L, nF, F, z, kk, leftlane, wz);
-    L[(lane < 12) ? P_W12 + lane : (int)P_DUMP] = wz;              // the wrench G c itself: if this set is accepted the recovery starts from it (cone_qp: w_done)
+    L[LANE_IS(lane < 12) ? P_W12 + lane : (int)P_DUMP] = wz;              // the wrench G c itself: if this set is accepted the recovery starts from it (cone_qp: w_done)
     double y = -L[P_H12 + l12];
     {
         const double *Wk = L + P_W + 12 * l12;
@@ -1896,10 +1909,10 @@ __device__ __forceinline__ int solve_free_set_thin(double *L, unsigned F_in, dou
         dpp_dot12(y, wz, wr);
     }
     WSYNC();                                                       // (the L rows parked by the solve are dead)
-    L[(lane < 12) ? C_LS + lane : C_LS + 16 + (lane & 15)] = y;    // r = W w - h
+    L[LANE_IS(lane < 12) ? C_LS + lane : C_LS + 16 + (lane & 15)] = y;    // r = W w - h
     const int pos = __popc(F & ((1u << (lane & 31)) - 1u));
     const double zr = __shfl(z, pos & (NT - 1), 64);               // coefficient j <- row pos(j)
-    const bool inF = (lane < 32) && ((F >> lane) & 1u);
+    const bool inF = LANE_IS(lane < 32) && ((F >> lane) & 1u);
     const double zj = inF ? zr : 0.0;
     WSYNC();
     double sj = 0.0;
@@ -1909,7 +1922,7 @@ __device__ __forceinline__ int solve_free_set_thin(double *L, unsigned F_in, dou
         for (int k = 0; k < 6; k++) sj += g[k] * rr[k];
     }
     *z_out = zj;
-    *lam_out = (lane < 32 && !inF) ? sj : 0.0;
+    *lam_out = (LANE_IS(lane < 32) && !inF) ? sj : 0.0;
     return bad;
 }
 
@@ -1974,11 +1987,12 @@ __device__ __forceinline__ int kinv_compute(double *L, unsigned F, double *Kdst,
     {   // both 6 x 6 inverses at once, each foot on two DPP rows: rows 0 and 2 = right foot, rows 1 and 3 = left foot.  Both rows of a
         // foot eliminate its full matrix; DPP row k carries unit right-hand sides 3 (k >> 1) .. 3 (k >> 1) + 2 of its foot
         const int ft = row & 1, c0 = 3 * (row >> 1);
-        const bool rowon = (ft == 0) ? useR : useL;
-        const bool on = rowon && l16 < 6;
-        const int rb = 36 * ft, lr = (l16 < 6) ? l16 : 0;
+        const bool rowon = LANE_IS(((lane >> 4) & 1) == 0) ? useR : useL;
+        const bool l16_lt6 = LANE_IS((lane & 15) < 6);
+        const bool on = rowon && l16_lt6;
+        const int rb = 36 * ft, lr = l16_lt6 ? l16 : 0;
         double a[6], bb[3], myinv = 0.0;
-        const int dd = (ft == 0) ? dR : dL;                        // bound torque row of this DPP row's foot (-1: none)
+        const int dd = LANE_IS(((lane >> 4) & 1) == 0) ? dR : dL;  // bound torque row of this DPP row's foot (-1: none)
 #pragma unroll
         for (int c = 0; c < 6; c++) {                              // full rows (Gauss-Jordan), both feet at once; the bound row / column pinned
             const double kv = K[rb + 6 * lr + c];
@@ -1990,7 +2004,7 @@ __device__ __forceinline__ int kinv_compute(double *L, unsigned F, double *Kdst,
         gj16_step<0>(a, bb, 0x3Fu, l16, rowon, 1e-12, bad, myinv);  // (l16 = LANE & 15, as gj16_step's pivot masks assume)
 #pragma unroll
         for (int s = 0; s < 3; s++) bb[s] *= myinv;
-        if (l16 < 6) {
+        if (l16_lt6) {
 #pragma unroll
             for (int s = 0; s < 3; s++) Ki[36 * ft + 6 * l16 + c0 + s] = (on && l16 != dd && c0 + s != dd) ? bb[s] : 0.0;   // K_f^-1 (symmetric); 0 for a foot without force
         }
@@ -2014,11 +2028,12 @@ __device__ __forceinline__ int cone_pushthrough(double *L, LmhCParams &P, unsign
     const double kapR = (dR >= 0) ? kR : 0.0, kapL = (dL >= 0) ? kL : 0.0;      // tau_bound = kappa f_z: p_y | -p_x of the edge, the generator's own entry
     {   // (E'WE + eps K~^-1) w~ = E'h on the rows of the feet that carry force (E = I, K~ = K without edge contact)
         double a[12], b[1];
-        const int l16 = lane & 15, lr = (l16 < 12) ? l16 : 0, fi = (lr >= 6) ? 1 : 0, ri = lr - 6 * fi;          // (a copy of the system per DPP row)
-        const bool rowuse = (l16 < 12) && ((fi == 0) ? useR : useL);
-        const int dd = fi ? dL : dR;
-        const bool rowpin = ri == dd, isz = (ri == 5) && (dd >= 0);
-        const double kz = isz ? (fi ? kapL : kapR) : 0.0;          // the f_z row takes kappa times the bound row
+        const bool l16_lt12 = LANE_IS((lane & 15) < 12), left = LANE_IS((lane & 15) >= 6 && (lane & 15) < 12);    // (a copy of the system per DPP row)
+        const int l16 = lane & 15, lr = l16_lt12 ? l16 : 0, fi = left ? 1 : 0, ri = lr - 6 * fi;
+        const bool rowuse = l16_lt12 && (left ? useL : useR);
+        const int dd = left ? dL : dR;
+        const bool rowpin = ri == dd, isz = LANE_IS((lane & 15) == 5 || (lane & 15) == 11) && (dd >= 0);
+        const double kz = isz ? (left ? kapL : kapR) : 0.0;          // the f_z row takes kappa times the bound row
         const double eps = P.eps_coeff;
         const double *W1 = L + P_W + 12 * lr, *W2 = L + P_W + 12 * (6 * fi + ((dd > 0) ? dd : 0)), *Kr = Ki + 36 * fi + 6 * ri;
         const double *gp = L + P_GCOL + 6 * l16;
@@ -2035,7 +2050,7 @@ __device__ __forceinline__ int cone_pushthrough(double *L, LmhCParams &P, unsign
         for (int c = 0; c < 12; c++) {                             // full rows, unconditional loads: rows / columns of a foot without force are
             const double g = kv[c % 6];                            // never pivots (live mask), so their entries are don't-cares
             const bool colpin = (c % 6) == ((c < 6) ? dR : dL);
-            const double v = base[c] + ((c / 6 == fi) ? eps * g : 0.0);
+            const double v = base[c] + (((c >= 6) == left) ? eps * g : 0.0);
             a[c] = (rowpin || colpin) ? ((lr == c) ? 1.0 : 0.0) : v;
         }
         const double hl = L[P_H12 + lr];
@@ -2046,14 +2061,14 @@ __device__ __forceinline__ int cone_pushthrough(double *L, LmhCParams &P, unsign
         // w = E w~: the bound torque is kappa f_z (lanes 5 / 11 of the lane's own 16-lane row hold f_z).  Lanes 0..11 of every DPP row
         // hold w from here on, so y, the residual and s_j below are row-broadcast chains (no LDS hand-over)
         const double fzR = bcast16<5>(b[0]), fzL = bcast16<11>(b[0]);
-        const double wv = rowpin ? (fi ? kapL * fzL : kapR * fzR) : b[0];
+        const double wv = rowpin ? (left ? kapL * fzL : kapR * fzR) : b[0];
         const double wo = rowuse ? wv : 0.0;
-        if (lane < 12) L[P_W12 + lane] = wo;                       // w: the wrench G c itself (cone_qp: w_done if the round is accepted)
+        if (LANE_IS(lane < 12)) L[P_W12 + lane] = wo;                     // w: the wrench G c itself (cone_qp: w_done if the round is accepted)
         // y = K~^-1 w (free coefficients; the bound column of the inverse is zero), -(W w - h) / eps (the others), foot by foot
         double yR = 0.0, yL = 0.0;
         dpp_dot6x2(yR, yL, wo, kv);
-        const bool used = (fi == 0) ? useR : useL, edge = (fi ? dL : dR) >= 0;
-        const double ky = fi ? yL : yR;
+        const bool used = left ? useL : useR, edge = (left ? dL : dR) >= 0;
+        const double ky = left ? yL : yR;
         double yv = ky, yn = ky;                                   // K regular: g_j'(W w - h) = -eps g_j'y for every coefficient of the foot
         if (!useR || !useL || dR >= 0 || dL >= 0) {                // wave-uniform
             // a foot with no free coefficient, or on an edge: the multipliers are g_j'(W w - h) with the foot's rows of the residual;
@@ -2068,13 +2083,13 @@ __device__ __forceinline__ int cone_pushthrough(double *L, LmhCParams &P, unsign
         // others the residual form (they differ only on an edge foot)
         double sR = 0.0, sL = 0.0;
         dpp_dot6x2(sR, sL, yv, g6);
-        double sj = (lane & 16) ? sL : sR;
+        double sj = LANE_IS((lane & 16) != 0) ? sL : sR;
         if (dR >= 0 || dL >= 0) {                                  // wave-uniform
             double nR = 0.0, nL = 0.0;
             dpp_dot6x2(nR, nL, yn, g6);
-            if (!((F >> (lane & 31)) & 1u)) sj = (lane & 16) ? nL : nR;
+            if (!((F >> (lane & 31)) & 1u)) sj = LANE_IS((lane & 16) != 0) ? nL : nR;
         }
-        *s_out = (lane < 32) ? sj : 0.0;
+        *s_out = LANE_IS(lane < 32) ? sj : 0.0;
     }
     return 1;
 }
@@ -2311,7 +2326,7 @@ __device__ __forceinline__ int cone_pushthrough_f32(double *L, LmhCParams &P, un
 __device__ __forceinline__ void qv_form(double *L)
 {
     const int lane = LANE;
-    if (lane < 32) {
+    if (LANE_IS(lane < 32)) {
         const int o = 6 * (lane / 16);
         double sacc = 0.0;
         for (int k = 0; k < 6; k++) sacc += L[P_GCOL + 6 * (lane & 15) + k] * L[P_H12 + o + k];
@@ -2330,7 +2345,7 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
     WSTAMP(30);
     RT_COUNT(4);
     *w_done = 0;
-    const bool mine = (lane < 32) && !((forced >> lane) & 1u);
+    const bool mine = LANE_IS(lane < 32) && !((forced >> lane) & 1u);
     int ninf = 33, budget = 3;
     bool check = false;                                            // fp32: the next round closes the Lawson-Hanson pass
     unsigned polished = 0u;                                        // coefficients a closing round has put into the set
@@ -2358,12 +2373,13 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
         } else {
         double a[12], b[1];
         {
-            const int l16 = lane & 15, lr = (l16 < 12) ? l16 : 0, fi = (lr >= 6) ? 1 : 0, ri = lr - 6 * fi;      // (a copy of the system per DPP row)
+            const bool left = LANE_IS((lane & 15) >= 6 && (lane & 15) < 12);
+            const int l16 = lane & 15, lr = LANE_IS((lane & 15) < 12) ? l16 : 0, fi = left ? 1 : 0, ri = lr - 6 * fi;      // (a copy of the system per DPP row)
             const double eps = P.eps_coeff;
 #pragma unroll
             for (int c = 0; c < 12; c++) {                         // full rows, unconditional loads (Gauss-Jordan)
                 const double g = L[P_GI6 + 6 * ri + c % 6];
-                a[c] = L[P_W + 12 * lr + c] + ((c / 6 == fi) ? eps * g : 0.0);
+                a[c] = L[P_W + 12 * lr + c] + (((c >= 6) == left) ? eps * g : 0.0);
             }
             b[0] = L[P_H12 + lr];
         }
@@ -2371,25 +2387,25 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
         if (gj_solve_regs<12, 1>(a, b, 0xFFFu)) flags |= LMH_FLAG_NOT_SPD;
         WSTAMP(33);
         WSYNC();
-        if (lane < 12) { L[P_U12 + lane] = b[0]; L[P_W12 + lane] = b[0]; }     // the wrench itself: G c = G G'(G G')^-1 u = u
+        if (LANE_IS(lane < 12)) { L[P_U12 + lane] = b[0]; L[P_W12 + lane] = b[0]; }     // the wrench itself: G c = G G'(G G')^-1 u = u
         {   // c = G'(G G')^-1 u: lanes 0..11 of every DPP row hold u, so the six terms of a foot come through row broadcasts (no way through LDS)
             const double *gp = L + P_GPI + 6 * (lane & 15);
             double g6[6], zr = 0.0, zl = 0.0;
 #pragma unroll
             for (int k = 0; k < 6; k++) g6[k] = gp[k];
             dpp_dot6x2(zr, zl, b[0], g6);
-            zj = (lane < 32) ? ((lane & 16) ? zl : zr) : 0.0;
+            zj = LANE_IS(lane < 32) ? (LANE_IS((lane & 16) != 0) ? zl : zr) : 0.0;
         }
         }
         WSTAMP(34);
         const double cmax = wave_max(fabs(zj));
-        const unsigned bad = (unsigned)__ballot(lane < 32 && zj < -TOLC * (1.0 + cmax));
+        const unsigned bad = (unsigned)__ballot(LANE_IS(lane < 32) && zj < -TOLC * (1.0 + cmax));
         WSTAMP(35);
         cj = zj;
         if (bad == 0u) {
             RT_COUNT(0);
             WSYNC();
-            if (lane < 32) L[P_CC + lane] = cj;
+            if (LANE_IS(lane < 32)) L[P_CC + lane] = cj;
             WSYNC();
             *F_io = F; *iters = it;
             if constexpr (!F32) *w_done = 1;                       // P_W12 holds the wrench (the fp32 form leaves it to the recovery)
@@ -2406,13 +2422,13 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
     if constexpr (!F32) {
         const int l16 = lane & 15;
         const double *gp = L + P_GCOL + 6 * l16;
-        const double hl = L[P_H12 + ((l16 < 12) ? l16 : 0)];
+        const double hl = L[P_H12 + (LANE_IS((lane & 15) < 12) ? l16 : 0)];
         double g6[6], qr = 0.0, ql = 0.0;
 #pragma unroll
         for (int k = 0; k < 6; k++) g6[k] = gp[k];
         dpp_dot6x2(qr, ql, hl, g6);
-        qv = (lane < 32) ? ((lane & 16) ? ql : qr) : 0.0;
-    } else qv = (lane < 32) ? L[P_QV + lane] : 0.0;
+        qv = LANE_IS(lane < 32) ? (LANE_IS((lane & 16) != 0) ? ql : qr) : 0.0;
+    } else qv = LANE_IS(lane < 32) ? L[P_QV + lane] : 0.0;
     const double qmax = wave_max(fabs(qv));
     WSTAMP(31);
     const double toll = 1e-14 * (1.0 + qmax);                    // ~10x the round-off of (P c - q): a looser bound lets a warm start keep a coefficient
@@ -2421,7 +2437,7 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
         if (it >= P.max_qp_iters) { flags |= LMH_FLAG_QP_MAXITER; break; }    // no further solve is started once the cap is reached
         it++;
         double zj;
-        if (dbgp && lane == 0 && it <= 12) dbgp[4020 + 2 * it] = (double)clock64();
+        if (dbgp && LANE_IS(lane == 0) && it <= 12) dbgp[4020 + 2 * it] = (double)clock64();
         double sj;
         bool w_thin = false;                                       // this round's solve left the wrench G z in P_W12 (thin sets; push-through: w itself)
         const int have_ki = F32 ? 0 : __builtin_amdgcn_readfirstlane((F == (unsigned)L[P_KF + 1]) ? (int)L[P_KF + 2] : 0);   // prepared by the helper wave for the warm-start set
@@ -2438,8 +2454,8 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
                 // its sign, the pass drops it again and it stays out.
                 check = false;
                 if (!pt) break;                                    // a foot without K_f^-1: the residual form stands (cj holds the accepted point)
-                const bool fr = (lane < 32) && ((F >> lane) & 1u);
-                const double smax = wave_max((lane < 32) ? fabs(sj) : 0.0);
+                const bool fr = (LANE_IS(lane < 32)) && ((F >> lane) & 1u);
+                const double smax = wave_max((LANE_IS(lane < 32)) ? fabs(sj) : 0.0);
                 const bool footfree = ((lane & 16) ? (F >> 16) : (F & 0xFFFFu)) != 0u;
                 double sb = (mine && !fr && footfree && !((polished >> (lane & 31)) & 1u)) ? sj : -1.0e300;
                 int si = lane;
@@ -2457,20 +2473,20 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
         if (pt) {                                                  // 12 x 12 route: coefficients and multipliers from one vector
             RT_COUNT(1);
             w_thin = !F32;
-            const bool fr = (lane < 32) && ((F >> lane) & 1u);
+            const bool fr = (LANE_IS(lane < 32)) && ((F >> lane) & 1u);
             zj = fr ? sj : 0.0;
-            lj = (lane < 32 && !fr) ? -P.eps_coeff * sj : 0.0;
+            lj = (LANE_IS(lane < 32) && !fr) ? -P.eps_coeff * sj : 0.0;
             if constexpr (F32) {
                 // fp32 multipliers: -eps s_j on a foot with free coefficients (good to eps * 1e-6 |s|); on a foot without, g_j'(W w - h), a
                 // difference of O(|h|) terms (good to 1e-6 |q|)
-                const double smax = wave_max((lane < 32) ? fabs(sj) : 0.0);
+                const double smax = wave_max((LANE_IS(lane < 32)) ? fabs(sj) : 0.0);
                 const bool footfree = ((lane & 16) ? (F >> 16) : (F & 0xFFFFu)) != 0u;
                 tolm = footfree ? 2e-5 * P.eps_coeff * (1.0 + smax) : 2e-5 * (1.0 + qmax);
             }
         } else {
             if constexpr (F32) flags |= LMH_FLAG_QP_FP64_ROUTE;    // rank-deficient contact set (or the Lawson-Hanson pass): fp64 general route
             if (!qv_stored) {                                      // the thin and general routes read qv from LDS
-                if (lane < 32) L[P_QV + lane] = qv;
+                if (LANE_IS(lane < 32)) L[P_QV + lane] = qv;
                 WSYNC();
                 qv_stored = true;
             }
@@ -2488,14 +2504,14 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
                 WSTAMP(83);
             }
         }
-        if (dbgp && lane == 0 && it <= 12) { dbgp[4021 + 2 * it] = (double)clock64(); dbgp[4050 + it] = (double)__popc(F); }
-        const bool inF = (lane < 32) && ((F >> lane) & 1u);
+        if (dbgp && LANE_IS(lane == 0) && it <= 12) { dbgp[4021 + 2 * it] = (double)clock64(); dbgp[4050 + it] = (double)__popc(F); }
+        const bool inF = (LANE_IS(lane < 32)) && ((F >> lane) & 1u);
         if (!lh) {
             const double cmax = wave_max(fabs(zj));
             const double tolc = TOLC * (1.0 + cmax);
             const bool isbad = mine && ((inF && zj < -tolc) || (!inF && lj < -tolm));
             const unsigned bad = (unsigned)__ballot(isbad);
-            if (dbgp && lane == 0 && it <= 12) { dbgp[3960 + it] = (double)F; dbgp[3975 + it] = (double)bad; }   // round trace (diagnostics)
+            if (dbgp && LANE_IS(lane == 0) && it <= 12) { dbgp[3960 + it] = (double)F; dbgp[3975 + it] = (double)bad; }   // round trace (diagnostics)
             cj = zj;
             if (bad == 0u) { if (!F32 && w_thin) *w_done = 1; break; }
             if (it >= bpp_max) { lh = true; F = 0u; cj = 0.0; continue; }    // next solve: F empty, lam = -qv
@@ -2535,7 +2551,7 @@ __device__ __forceinline__ int cone_qp(double *L, LmhCParams &P, unsigned forced
         }
     }
     WSYNC();
-    if (lane < 32) L[P_CC + lane] = ((F >> lane) & 1u) ? cj : 0.0;
+    if (LANE_IS(lane < 32)) L[P_CC + lane] = ((F >> lane) & 1u) ? cj : 0.0;
     WSYNC();
     *F_io = F;
     *iters = it;
@@ -2571,10 +2587,10 @@ __device__ __forceinline__ void qp_prefill15(double *L, LmhCParams &P)
     // load, two multiplications (by 0 | 1 and by 0 | 1 / D_c) and two stores.
     const int lane = LANE, c = lane & 31, rh = lane >> 5;
     const double idp = P.inv_w_base_pos, ida = P.inv_w_base_ang, idj = P.inv_w_joints;
-    const double iD = (c < 3) ? idp : (c < 6) ? ida : idj;
-    const bool ok0 = c < 12, ok1 = (c < 6) || (c >= 12 && c < 18);
+    const double iD = LANE_IS((lane & 31) < 3) ? idp : LANE_IS((lane & 31) < 6) ? ida : idj;
+    const bool ok0 = LANE_IS((lane & 31) < 12), ok1 = LANE_IS((lane & 31) < 6 || ((lane & 31) >= 12 && (lane & 31) < 18));
     const double m0 = ok0 ? 1.0 : 0.0, m1 = ok1 ? 1.0 : 0.0, d0 = ok0 ? iD : 0.0, d1 = ok1 ? iD : 0.0;
-    const double *p0 = L + (P_JC + 12 * rh + (ok0 ? c : 0)), *p1 = L + (P_JC + 72 + 12 * rh + (ok1 ? ((c < 6) ? c : c - 6) : 0));
+    const double *p0 = L + (P_JC + 12 * rh + (ok0 ? c : 0)), *p1 = L + (P_JC + 72 + 12 * rh + (ok1 ? (LANE_IS((lane & 31) < 6) ? c : c - 6) : 0));
     double *o = L + (Q_U + 34 * rh + c);
 #pragma unroll
     for (int it = 0; it < 6; it++) {
@@ -2593,6 +2609,7 @@ __device__ __forceinline__ void qp_prefill15(double *L, LmhCParams &P)
 //     wave while wave 0 solves; the Y tiles (needed only by the recovery) are formed by the helper wave while wave 0 goes on to S^-1, W, h.
 // NW = 2 joins: fills | Cm, q+V | solve, Z+Mbp | (S..qv), Y | -> the caller's join in front of the cone solve.
 // `slack` (rollout): called by the helper wave where it is ahead of wave 0 -- after its Z / Mb bp' tiles, while wave 0 is in the 15 x 15 solve.
+constexpr int qs_row(int l) { return (l < 12) ? 6 + l : (l < 15) ? 3 + (l - 12) : 3; }   // row of [AG ; J] behind operand row l < 16 of qp_setup15 (LANE_IS)
 struct NoWindow { __device__ __forceinline__ void operator()(int) const {} };
 template <int NW, class SF = NoWindow, bool CGLIN = true>
 __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, double *dbgp, SF slack = SF())
@@ -2605,42 +2622,43 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
     // ---- fills: U, U D^-1 (padded 16 x 32; row order: 12 Jacobian rows, 3 linear-momentum rows, one zero row), bp'' (8 x 32), weights
     if constexpr (NW == 1) qp_prefill15(L, P);                     // NW = 2: wave 0 has already written the Jacobian rows (controller_eval)
     {   // lane = (row parity hi, column c); everything derived from the lane once, a pass is a load, one or two multiplications and the stores
-        const int c = lane & 31, hi = lane >> 5, cs = (c < 30) ? c : 0;
-        const double iDc = (c < 3) ? idp : (c < 6) ? ida : idj, dm = (c < 30) ? iDc : 0.0;          // 1 / D_c, 0 on the padding columns
+        const bool c_lt30 = LANE_IS((lane & 31) < 30), hi0 = LANE_IS(lane < 32);
+        const int c = lane & 31, hi = lane >> 5, cs = c_lt30 ? c : 0;
+        const double iDc = LANE_IS((lane & 31) < 3) ? idp : LANE_IS((lane & 31) < 6) ? ida : idj, dm = c_lt30 ? iDc : 0.0;          // 1 / D_c, 0 on the padding columns
         // NW = 2: the helper forms q (below) and the momentum rows of U, wave 0 AGpqp, bp'' and the weights: with everything but q on wave 0 the
         // helper waited ~0.7k cycles at this join, with the bp'' rows split as well wave 0 did (profiles/r04_barrier_share*.txt)
         if (wid == NW - 1) {                                       // rows 12..15 of U, U D^-1
-            const double um = (c < 30) ? 1.0 : 0.0;
+            const double um = c_lt30 ? 1.0 : 0.0;
             const double *ag = L + (P_AG + 90 + 30 * hi + cs);     // linear-momentum rows 3..5 of AG -> operand rows 12..14; row 15 is zero
             double *o = L + (Q_U + 34 * (12 + hi) + c);
-            const double v0 = ag[0], v1 = ag[(hi == 0) ? 60 : 0];
+            const double v0 = ag[0], v1 = ag[hi0 ? 60 : 0];
             o[0] = v0 * um; o[Q_UD - Q_U] = v0 * dm;
-            o[68] = hi ? 0.0 : v1 * um; o[68 + (Q_UD - Q_U)] = hi ? 0.0 : v1 * dm;
+            o[68] = hi0 ? v1 * um : 0.0; o[68 + (Q_UD - Q_U)] = hi0 ? v1 * dm : 0.0;
         }
         // rows 0..6 of bp'' = [-qref | D^-1 Mb'] (row 7: q, below): row parity hi -> rows hi, hi + 4, then hi + 2 and 6
         const int n0 = hi;
         if (wid == 0) {
-            const double *pa = L + ((n0 == 0) ? P_QREF + cs : P_MTOP + 30 * (n0 - 1) + cs);
-            const double sa = (n0 == 0) ? ((c < 30) ? -1.0 : 0.0) : dm;
+            const double *pa = L + (hi0 ? P_QREF + cs : P_MTOP + 30 * (n0 - 1) + cs);
+            const double sa = hi0 ? (c_lt30 ? -1.0 : 0.0) : dm;
             L[Q_BPT + 34 * n0 + c] = pa[0] * sa;
             L[Q_BPT + 34 * (n0 + 4) + c] = L[P_MTOP + 30 * (n0 + 3) + cs] * dm;
             const int n1 = hi + 2;
             L[Q_BPT + 34 * n1 + c] = L[P_MTOP + 30 * (n1 - 1) + cs] * dm;
-            if (hi == 0) L[Q_BPT + 34 * 6 + c] = L[P_MTOP + 30 * 5 + cs] * dm;
+            if (hi0) L[Q_BPT + 34 * 6 + c] = L[P_MTOP + 30 * 5 + cs] * dm;
         }
     }
     if (wid == 0) {                                                // wave 0: it has just formed AGpqp (phase_qp)
-        if (lane < 16) {                                           // Om_r beta_r | 1 / Om_r | beta_r  (row 15: zeros)
-            const bool in = lane < nU;
-            const int rr = (lane < 12) ? 6 + lane : in ? 3 + (lane - 12) : 3;      // row of [AG ; J] behind operand row `lane`
-            const double om = (rr < 6) ? P.w_com_lin : P.w_foot;
-            const double beta = (rr < 6) ? (L[P_AGPQP + rr] - L[P_HREF + rr]) : (L[P_JPQP + rr - 6] - L[P_FREF + rr - 6]);
+        if (LANE_IS(lane < 16)) {                                  // Om_r beta_r | 1 / Om_r | beta_r  (row 15: zeros)
+            const bool in = LANE_IS(lane < nU), mom = LANE_IS(qs_row(lane) < 6);
+            const int rr = LANE_IS(lane < 12) ? 6 + lane : in ? 3 + (lane - 12) : 3;      // row of [AG ; J] behind operand row `lane`
+            const double om = mom ? P.w_com_lin : P.w_foot;
+            const double beta = mom ? (L[P_AGPQP + rr] - L[P_HREF + rr]) : (L[P_JPQP + rr - 6] - L[P_FREF + rr - 6]);
             L[Q_OB + lane] = in ? om * beta : 0.0;
-            L[Q_OB + 16 + lane] = in ? ((rr < 6) ? P.inv_w_com_lin : P.inv_w_foot) : 1.0;
+            L[Q_OB + 16 + lane] = in ? (mom ? P.inv_w_com_lin : P.inv_w_foot) : 1.0;
             L[Q_OB + 32 + lane] = in ? beta : 0.0;
         }
-        if (lane >= 32) L[Q_ZERO + lane - 32] = 0.0;
-        if (lane >= 16 && lane < 24) L[Q_TT + 18 * (lane - 16) + 15] = 0.0;     // k = 15 padding of the right-hand sides
+        if (LANE_IS(lane >= 32)) L[Q_ZERO + lane - 32] = 0.0;
+        if (LANE_IS(lane >= 16 && lane < 24)) L[Q_TT + 18 * (lane - 16) + 15] = 0.0;     // k = 15 padding of the right-hand sides
     }
     if (NW == 2 && wid == 1) {
         // q = D^-1 U' Om beta and with it row 7 of bp'' (the g column of V), already HERE on the two-wave schedule: the helper used to wait ~0.8k
@@ -2648,19 +2666,19 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
         // It forms Om beta itself -- the same expressions wave 0 evaluates for Q_OB beside it -- in lane r of every 16-lane row and feeds it to
         // the column sums through DPP row broadcasts, so nothing has to come back through LDS: q_i = sum_r lane_r(Om beta) U[r][i].
         const int l16 = lane & 15;
-        const bool in = l16 < nU;
-        const int rr = (l16 < 12) ? 6 + l16 : in ? 3 + (l16 - 12) : 3;          // row of [AG ; J] behind operand row l16
-        const int r3 = (rr < 6) ? rr - 3 : 0, rj = (rr >= 6) ? rr - 6 : 0;
+        const bool in = LANE_IS((lane & 15) < nU), mom = LANE_IS(qs_row(lane & 15) < 6);
+        const int rr = LANE_IS((lane & 15) < 12) ? 6 + l16 : in ? 3 + (l16 - 12) : 3;          // row of [AG ; J] behind operand row l16
+        const int r3 = mom ? rr - 3 : 0, rj = mom ? 0 : rr - 6;
         const double *T0 = L + P_TB, *cc = L + P_C, *pg = L + P_CG;
         double cg[6];
 #pragma unroll
         for (int k = 3; k < 6; k++) cg[k] = CGLIN ? cc[k] - pg[k] : pg[k];        // Cg[3:6] (refs_agpqp: the same expressions)
         const double agp = T0[4 * r3] * cg[3] + T0[4 * r3 + 1] * cg[4] + T0[4 * r3 + 2] * cg[5];     // AGpqp, linear rows (refs_agpqp)
         const double bj = L[P_JPQP + rj] - L[P_FREF + rj];
-        const double beta = (rr < 6) ? agp - L[P_HREF + rr] : bj;
-        const double ob = in ? ((rr < 6) ? P.w_com_lin : P.w_foot) * beta : 0.0;
+        const double beta = mom ? agp - L[P_HREF + rr] : bj;
+        const double ob = in ? (mom ? P.w_com_lin : P.w_foot) * beta : 0.0;
         const int ci = lane & 31;
-        const double *ucol = L + (Q_U + ci), *agc = L + (P_AG + 90 + ((ci < 30) ? ci : 29));        // rows 12..14 of U = AG's linear rows, read at their source (this wave has just stored its copies of them in U)
+        const double *ucol = L + (Q_U + ci), *agc = L + (P_AG + 90 + (LANE_IS((lane & 31) < 30) ? ci : 29));        // rows 12..14 of U = AG's linear rows, read at their source (this wave has just stored its copies of them in U)
         double ur[nU];
 #pragma unroll
         for (int r = 0; r < 12; r++) ur[r] = ucol[34 * r];
@@ -2668,9 +2686,9 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
         for (int r = 12; r < nU; r++) ur[r] = agc[30 * (r - 12)];
         double q = 0.0;
         dpp_dot15(q, ob, ur);
-        const double iDi = (ci < 3) ? idp : (ci < 6) ? ida : idj;
-        const double qr = -L[P_QREF + ((ci < 30) ? ci : 0)];
-        L[Q_BPT + 34 * 7 + ci] = (ci < 30) ? qr + q * iDi : 0.0;   // (lanes 32..63 repeat lanes 0..31)
+        const double iDi = LANE_IS((lane & 31) < 3) ? idp : LANE_IS((lane & 31) < 6) ? ida : idj;
+        const double qr = -L[P_QREF + (LANE_IS((lane & 31) < 30) ? ci : 0)];
+        L[Q_BPT + 34 * 7 + ci] = LANE_IS((lane & 31) < 30) ? qr + q * iDi : 0.0;   // (lanes 32..63 repeat lanes 0..31)
     }
     WSTAMP(10);
     bsync<NW>();
@@ -2681,18 +2699,18 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
     // ---- Cm = Om^-1 + U D^-1 U'  (wave 0)  |  q, then V = U [bp'_g + q | bp'_M]  (helper wave)
     if (NW == 1 || wid == 1) {
         if constexpr (NW == 1) {
-        if (lane < 32) {                                           // q_i = D^-1_i sum_r U[r][i] (Om beta)_r ; row 7 of bp'' = -qref + q
+        if (LANE_IS(lane < 32)) {                                  // q_i = D^-1_i sum_r U[r][i] (Om beta)_r ; row 7 of bp'' = -qref + q
             double q = 0.0;
 #pragma unroll
             for (int r = 0; r < nU; r++) q += L[Q_U + 34 * r + lane] * L[Q_OB + r];
-            const double iDi = (lane < 3) ? idp : (lane < 6) ? ida : idj;
+            const double iDi = LANE_IS(lane < 3) ? idp : LANE_IS(lane < 6) ? ida : idj;
             L[Q_BPT + 34 * 7 + lane] = L[Q_BPT + lane] + q * iDi;  // columns 30, 31: 0 + 0
         }
         WSYNC();
         }
-        const double *b_row = (tr == 0) ? L + Q_BPT + 34 * 7 + tq : (tr < 7) ? L + Q_BPT + 34 * tr + tq : zero;
+        const double *b_row = LANE_IS((lane & 15) == 0) ? L + Q_BPT + 34 * 7 + tq : LANE_IS((lane & 15) < 7) ? L + Q_BPT + 34 * tr + tq : zero;
         const v4d vv = mfma_ptr<8, 4, 4>(u_row, b_row);
-        double *const tt = (tr < 8) ? L + Q_TT + 18 * tr + tq : L + Q_TRASH + lane;       // (trash: + 4 g <= lane + 12)
+        double *const tt = LANE_IS((lane & 15) < 8) ? L + Q_TT + 18 * tr + tq : L + Q_TRASH + lane;       // (trash: + 4 g <= lane + 12)
 #pragma unroll
         for (int g = 0; g < 4; g++) tt[4 * g] = vv[g];             // V[r][n] -> TT[n][r], r = tq + 4 g < 16 (row 15 of U is zero: TT[n][15] = 0)
     }
@@ -2716,22 +2734,22 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
 #pragma unroll
         for (int c = 0; c < nU; c++) a[c] = L[Q_CM + 17 * lr + c];
         bb[0] = L[Q_TT + 18 * c0 + lr];
-        bb[1] = L[(c0 < 6) ? Q_TT + 18 * (c0 + 1) + lr : Q_ZERO];
+        bb[1] = L[LANE_IS(lane < 48) ? Q_TT + 18 * (c0 + 1) + lr : Q_ZERO];
         WSTAMP(14);
         if (gj_solve_regs<nU, 2>(a, bb, (1u << nU) - 1u)) flags |= LMH_FLAG_NOT_SPD;
-        bb[0] -= L[(lane < 16) ? Q_OB + lr : Q_ZERO];              // t'' = t_g - ob in column 0 (slot 0 of DPP row 0)
-        L[Q_TT + 18 * c0 + lr] = (lr < nU) ? bb[0] : 0.0;
-        L[(c0 < 6) ? Q_TT + 18 * (c0 + 1) + lr : Q_TRASH + lane] = (lr < nU) ? bb[1] : 0.0;
+        bb[0] -= L[LANE_IS(lane < 16) ? Q_OB + lr : Q_ZERO];       // t'' = t_g - ob in column 0 (slot 0 of DPP row 0)
+        L[Q_TT + 18 * c0 + lr] = LANE_IS((lane & 15) < nU) ? bb[0] : 0.0;
+        L[LANE_IS(lane < 48) ? Q_TT + 18 * (c0 + 1) + lr : Q_TRASH + lane] = LANE_IS((lane & 15) < nU) ? bb[1] : 0.0;
         WSTAMP(15);
     }
     if (NW == 1 || wid == 1) {
-        const double *m_row = (tr < 6) ? L + P_MTOP + 30 * tr + tq : zero;        // k = 30, 31 read the next row's first entries: finite, times the zero padding of B
-        const v4d zz = mfma_ptr<8, 4, 4>(m_row, (tr < nU) ? L + Q_UD + 34 * tr + tq : zero);
-        const v4d mb = mfma_ptr<8, 4, 4>(m_row, (tr < 7) ? L + Q_BPT + 34 * tr + tq : zero);
+        const double *m_row = LANE_IS((lane & 15) < 6) ? L + P_MTOP + 30 * tr + tq : zero;        // k = 30, 31 read the next row's first entries: finite, times the zero padding of B
+        const v4d zz = mfma_ptr<8, 4, 4>(m_row, LANE_IS((lane & 15) < nU) ? L + Q_UD + 34 * tr + tq : zero);
+        const v4d mb = mfma_ptr<8, 4, 4>(m_row, LANE_IS((lane & 15) < 7) ? L + Q_BPT + 34 * tr + tq : zero);
         // rows m = tq + 4 g < 6: register 0 always holds one, register 1 for tq < 2
         double *const trash = L + Q_TRASH + lane;
-        double *const z0 = L + Q_Z + 18 * tq + tr, *const z1 = (tq < 2) ? z0 + 72 : trash;
-        double *const m0 = (tr < 8) ? L + Q_MBP + 8 * tq + tr : trash, *const m1 = (tr < 8 && tq < 2) ? m0 + 32 : trash;
+        double *const z0 = L + Q_Z + 18 * tq + tr, *const z1 = LANE_IS(lane < 32) ? z0 + 72 : trash;
+        double *const m0 = LANE_IS((lane & 15) < 8) ? L + Q_MBP + 8 * tq + tr : trash, *const m1 = LANE_IS((lane & 15) < 8 && lane < 32) ? m0 + 32 : trash;
         z0[0] = zz[0]; m0[0] = mb[0];
         z1[0] = zz[1]; m1[0] = mb[1];
         if constexpr (NW == 2) slack(0);                           // (the helper waits ~1.7k cycles at this join otherwise: profiles/r04_barrier_share_mid2.txt)
@@ -2739,7 +2757,7 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
     bsync<NW>();
     WSTAMP(16);
     if (dbgp && LANE == 0) dbgp[4074] = (double)clock64();
-    const double *t_row = (tr < 7) ? L + Q_TT + 18 * tr + tq : zero;              // B fragment of t'' (column tr)
+    const double *t_row = LANE_IS((lane & 15) < 7) ? L + Q_TT + 18 * tr + tq : zero;      // B fragment of t'' (column tr)
     // ---- helper wave: Y = bp' - D^-1 U' t''  (30 x 7, stored transposed; only the recovery reads it)
     if (NW == 1 || wid == 1) {
         // result register (mt, g) holds row i = tq + off, off = 16 mt + 4 g, of column tr: everything that depends on the lane is formed here,
@@ -2747,12 +2765,12 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
         // off = 4 (i = 4 + tq: 4, 5 angle, 6, 7 joints); i < 30 fails at off = 28 for tq >= 2 only, which gets its own store pointer (its bp'
         // entry is a stored zero of the padding columns 30, 31, or one of Q_ZERO's 32).  Lanes of the columns tr >= 7 read zeros and store
         // into Q_TRASH + (lane & 31) + off < Q_TRASH + 64.
-        const bool col = tr < 7;
+        const bool col = LANE_IS((lane & 15) < 7);
         double *const trash = L + Q_TRASH + (lane & 31);
         const double *const bpc = col ? L + Q_BPT + 34 * tr + tq : zero;
         double *const ytc = col ? L + P_YT + 30 * tr + tq : trash;
-        double *const yt28 = (col && tq < 2) ? ytc + 28 : trash;
-        const double id0 = (tq < 3) ? idp : ida, id4 = (tq < 2) ? ida : idj;
+        double *const yt28 = LANE_IS((lane & 15) < 7 && lane < 32) ? ytc + 28 : trash;
+        const double id0 = LANE_IS(lane < 48) ? idp : ida, id4 = LANE_IS(lane < 32) ? ida : idj;
 #pragma unroll
         for (int mt = 0; mt < 2; mt++) {
             const v4d yy = mfma_ptr<4, 136, 4>(L + Q_U + 34 * tq + 16 * mt + tr, t_row);        // A[m = i][k] = U[k][i]
@@ -2771,12 +2789,12 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
     // ---- wave 0: S | d = Mb bp' - Z t''  ->  S^-1  ->  T1 = Jb S^-1  ->  [W | h]  ->  qv
     if (NW == 1 || wid == 0) {
         {
-            const v4d sy = mfma_ptr<4, 4, 4>((tr < 6) ? L + Q_Z + 18 * tr + tq : zero, t_row);
+            const v4d sy = mfma_ptr<4, 4, 4>(LANE_IS((lane & 15) < 6) ? L + Q_Z + 18 * tr + tq : zero, t_row);
             // rows m = tq + 4 g < 6 (register 1: tq < 2) of the columns tr < 7; column 0 is d = C - (Mb bp' - Z t'')[.][0], columns 1..6 are S
-            const bool col = tr < 7, dcol = tr == 0, ok1 = col && tq < 2;
+            const bool col = LANE_IS((lane & 15) < 7), dcol = LANE_IS((lane & 15) == 0), ok1 = LANE_IS((lane & 15) < 7 && lane < 32);
             double *const trash = L + Q_TRASH + lane;
             const double *const s0 = col ? L + Q_MBP + 8 * tq + tr : zero, *const s1 = ok1 ? s0 + 32 : zero;
-            const double *const c0 = L + P_C + tq, *const c1 = (tq < 2) ? c0 + 4 : L + P_C;
+            const double *const c0 = L + P_C + tq, *const c1 = LANE_IS(lane < 32) ? c0 + 4 : L + P_C;
             double *const d0 = !col ? trash : dcol ? L + P_D6 + tq : L + Q_S + 7 * tq + (tr - 1);
             double *const d1 = !ok1 ? trash : dcol ? d0 + 4 : d0 + 28;
             const double val0 = s0[0] - sy[0], val1 = s1[0] - sy[1];
@@ -2791,50 +2809,51 @@ __device__ __forceinline__ int qp_setup15(double *L, LmhCParams &P, int wid, dou
             // (tolerances ~1e-14) do not survive: LDL' on the lower triangle here.
             double a[6], bb[2];
             // (a copy of the matrix per DPP row; DPP row k < 3 carries unit columns 2k and 2k + 1, row 3 two zero dummies)
-            const int l16 = lane & 15, lr = (l16 < 6) ? l16 : 0, c0 = 2 * (lane >> 4);
+            const int l16 = lane & 15, lr = LANE_IS((lane & 15) < 6) ? l16 : 0, c0 = 2 * (lane >> 4);
             // Gauss-Jordan on the full S, then S^-1 <- (S^-1 + S^-T) / 2: plain Gauss-Jordan leaves S^-1 (hence W) unsymmetric at the 1e-10 level (it loses
             // ~cond(S) more digits than LDL'), which the active-set tests of the cone QP (tolerances ~1e-14) do not survive; symmetrised, W is symmetric to
             // round-off again and the solve is 1.5k cycles shorter than LDL' with its parked factor (LMH_LDL_SI keeps that form for comparison)
 #pragma unroll
             for (int c = 0; c < 6; c++) a[c] = L[Q_S + 7 * lr + c];
-            const bool own = c0 < 6 && l16 < 6;                    // lane l16 of this row's columns: an entry of Si
-            bb[0] = (c0 < 6 && l16 == c0) ? 1.0 : 0.0;
-            bb[1] = (c0 < 6 && l16 == c0 + 1) ? 1.0 : 0.0;
+            const bool own = LANE_IS(lane < 48 && (lane & 15) < 6);                 // lane l16 of this row's columns: an entry of Si
+            bb[0] = LANE_IS(lane < 48 && (lane & 15) == 2 * (lane >> 4)) ? 1.0 : 0.0;
+            bb[1] = LANE_IS(lane < 48 && (lane & 15) == 2 * (lane >> 4) + 1) ? 1.0 : 0.0;
             if (gj_solve_regs<6, 2>(a, bb, 0x3Fu)) flags |= LMH_FLAG_NOT_SPD;
             double *const lso = own ? L + Q_LS + 6 * l16 + c0 : L + Q_TRASH + lane;      // (trash: slots lane, lane + 1 <= Q_TRASH + 64)
             lso[0] = bb[0];
             lso[1] = bb[1];
             WSYNC();
             {
-                const int e = (lane < 36) ? lane : 0, i = e / 6, j = e % 6;
+                const int e = LANE_IS(lane < 36) ? lane : 0, i = e / 6, j = e % 6;
                 const double v = 0.5 * (L[Q_LS + 6 * i + j] + L[Q_LS + 6 * j + i]);
-                L[(lane < 36) ? P_SI + e : Q_TRASH + lane] = v;    // (for the recovery; the tiles below symmetrise their own fragment)
+                L[LANE_IS(lane < 36) ? P_SI + e : Q_TRASH + lane] = v;    // (for the recovery; the tiles below symmetrise their own fragment)
             }
         }
         WSTAMP(20);
         {   // [W | h] = [w_force I + Jb Si Jb' | Jb Si d] as Jb (Si [Jb' | d]): the result fragment of the inner product, D[tq + 4 g][tr] in register g,
             // IS the B fragment B[4 kk + tq][tr] of the outer one for kk = g, so the 6 x 13 intermediate never leaves the registers (the form
             // (Jb Si) Jb' went through LDS twice: T1 out and back in the other fragment shape, behind a stored Si).
-            const bool k2 = tq < 2, r6 = tr < 6;
+            const bool k2 = LANE_IS(lane < 32), r6 = LANE_IS((lane & 15) < 6);
+            const bool t12 = LANE_IS((lane & 15) < 12), t13 = LANE_IS((lane & 15) < 13), is12 = LANE_IS((lane & 15) == 12);
             const int m6 = r6 ? tr : 0;
             const double *ls = L + Q_LS;
             const double s0 = 0.5 * (ls[6 * m6 + tq] + ls[6 * tq + m6]);                        // A[m = tr][k = tq] = Si[tr][tq], symmetrised
             const double s1 = 0.5 * (ls[6 * m6 + (k2 ? 4 + tq : 0)] + ls[6 * (k2 ? 4 + tq : 0) + m6]);   // k = 4 + tq < 6
-            const double sa0 = r6 ? s0 : 0.0, sa1 = (r6 && k2) ? s1 : 0.0;
-            const double *jb = L + ((tr < 12) ? P_JC + 12 * tr + tq : (tr == 12) ? P_D6 + tq : P_D6);   // B[k][n] = Jb[n][k] | d[k] (n = 12) | 0
+            const double sa0 = r6 ? s0 : 0.0, sa1 = LANE_IS((lane & 15) < 6 && lane < 32) ? s1 : 0.0;
+            const double *jb = L + (t12 ? P_JC + 12 * tr + tq : is12 ? P_D6 + tq : P_D6);   // B[k][n] = Jb[n][k] | d[k] (n = 12) | 0
             const double jv0 = jb[0], jv1 = jb[k2 ? 4 : 0];
-            const double b0 = (tr < 13) ? jv0 : 0.0, b1 = (tr < 13 && k2) ? jv1 : 0.0;
+            const double b0 = t13 ? jv0 : 0.0, b1 = LANE_IS((lane & 15) < 13 && lane < 32) ? jv1 : 0.0;
             v4d xt = {0.0, 0.0, 0.0, 0.0};
             xt = __builtin_amdgcn_mfma_f64_16x16x4f64(sa0, b0, xt, 0, 0, 0);
             xt = __builtin_amdgcn_mfma_f64_16x16x4f64(sa1, b1, xt, 0, 0, 0);                    // xt[g] = (Si [Jb' | d])[tq + 4 g][tr]; rows 6, 7 are zero
-            const double a0 = (tr < 12) ? jv0 : 0.0, a1 = (tr < 12 && k2) ? jv1 : 0.0;          // A[m = tr][k] = Jb[tr][k]: the same loads
+            const double a0 = t12 ? jv0 : 0.0, a1 = LANE_IS((lane & 15) < 12 && lane < 32) ? jv1 : 0.0;          // A[m = tr][k] = Jb[tr][k]: the same loads
             v4d ww = {0.0, 0.0, 0.0, 0.0};
             ww = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, xt[0], ww, 0, 0, 0);
             ww = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, xt[1], ww, 0, 0, 0);
             const double wf = P.w_force;
             // row m = tq + 4 g of column tr: W (tr < 12, rows 48 apart), h (tr == 12, entries 4 apart) or trash (+ 4 g <= lane + 8)
-            double *const wo = (tr < 12) ? L + P_W + 12 * tq + tr : (tr == 12) ? L + P_H12 + tq : L + Q_TRASH + lane;
-            const int ws = (tr < 12) ? 48 : 4;
+            double *const wo = t12 ? L + P_W + 12 * tq + tr : is12 ? L + P_H12 + tq : L + Q_TRASH + lane;
+            const int ws = t12 ? 48 : 4;
             const int dg = tr - tq;                                // m == tr <=> dg == 4 g
 #pragma unroll
             for (int g = 0; g < 3; g++) wo[g * ws] = ww[g] + ((dg == 4 * g) ? wf : 0.0);
@@ -3066,7 +3085,7 @@ __device__ __forceinline__ void kinv_prework(double *L, LmhCParams &P)
         const bool thin = (nR > 0 && nR < 6) || (nL > 0 && nL < 6);
         st = thin ? 2 : (kinv_compute(L, F0, L + P_KI, L + A_XR) ? 2 : 1);
     }
-    if (LANE == 0) { L[P_KF + 1] = (double)F0; L[P_KF + 2] = (double)st; }
+    if (LANE_IS(lane == 0)) { L[P_KF + 1] = (double)F0; L[P_KF + 2] = (double)st; }
 }
 
 // Controller::WBC Hessian/gradient + solveQP (controller.cpp:94-132,388-479), see file header.
@@ -3075,21 +3094,25 @@ __device__ __forceinline__ void kinv_prework(double *L, LmhCParams &P)
 // Entry k < 6 of the base acceleration in the world frame, X0 acc = a[0:6]: w = R0 a_ang ; v = R0 (a_lin - B0 w), linear part first.
 // X: the 21 entries of P_X0 (E0 | p0 | B0), er: row k % 3 of E0.  One body for the evaluation kernels (phase_outputs_qdd: six lanes, operands
 // from LDS) and the rollout's register tail (phase_qp: every lane, a from the recovery's registers), so that the two cannot drift apart.
-__device__ __forceinline__ double base_acc_world(const double (&X)[21], const double (&er)[3], const double (&a)[6], int k)
+// (lin, r0, r1: k < 3, k == 3, k == 4 -- a caller whose k is a function of the lane id alone passes them as constant lane masks, LANE_IS)
+__device__ __forceinline__ double base_acc_world(const double (&X)[21], const double (&er)[3], const double (&a)[6], bool lin, bool r0, bool r1)
 {
-    const int r = k % 3;
     const double *E0 = X, *B0 = X + 12;
     const double w0 = E0[0] * a[0] + E0[1] * a[1] + E0[2] * a[2];
     const double w1 = E0[3] * a[0] + E0[4] * a[1] + E0[5] * a[2];
     const double w2 = E0[6] * a[0] + E0[7] * a[1] + E0[8] * a[2];
     double val;
-    if (k < 3) {                                                   // linear part goes first in qdd
+    if (lin) {                                                     // linear part goes first in qdd
         const double u0 = a[3] - (B0[0] * w0 + B0[1] * w1 + B0[2] * w2);
         const double u1 = a[4] - (B0[3] * w0 + B0[4] * w1 + B0[5] * w2);
         const double u2 = a[5] - (B0[6] * w0 + B0[7] * w1 + B0[8] * w2);
         val = er[0] * u0 + er[1] * u1 + er[2] * u2;
-    } else val = (r == 0) ? w0 : (r == 1) ? w1 : w2;
+    } else val = r0 ? w0 : r1 ? w1 : w2;
     return val;
+}
+__device__ __forceinline__ double base_acc_world(const double (&X)[21], const double (&er)[3], const double (&a)[6], int k)
+{
+    return base_acc_world(X, er, a, k < 3, k == 3, k == 4);
 }
 // the operands of base_acc_world that do not depend on the accelerations (k: the lane's entry, < 6)
 __device__ __forceinline__ void base_acc_load(const double *L, int k, double (&X)[21], double (&er)[3])
@@ -3148,7 +3171,7 @@ __device__ __forceinline__ int phase_qp(double *L, LmhCParams &P, int ph, int wi
     WSTAMP(25);
     *Fmask_io = F;
     *iters_out = it;
-    if (lane == 0) L[P_KF] = (double)F;                            // published for the helper wave (next evaluation's warm start)
+    if (LANE_IS(lane == 0)) L[P_KF] = (double)F;                   // published for the helper wave (next evaluation's warm start)
     if (dbgp && LANE == 0) dbgp[4013] = (double)clock64();
     if constexpr (F32) {                                           // the recovery below in fp32
         if (lane < 12) {
@@ -3181,7 +3204,7 @@ __device__ __forceinline__ int phase_qp(double *L, LmhCParams &P, int ph, int wi
     }
     // ---- recover w = G c (unless the solve left the wrench behind), lam = -Si (Jb' w - d), a = -(Y_g + Y_M lam)
     if (!w_done) {                                                 // wave-uniform
-        if (lane < 12) {
+        if (LANE_IS(lane < 12)) {
             const int ft = lane / 6, k = lane % 6;
             double s = 0.0;
             for (int j = 0; j < 16; j++) s += L[P_GCOL + 6 * j + k] * L[P_CC + 16 * ft + j];
@@ -3198,13 +3221,14 @@ __device__ __forceinline__ int phase_qp(double *L, LmhCParams &P, int ph, int wi
         LmhCParams *Pq_ = &P;
         asm volatile("" : "+s"(Pq_));
         const bool fz = TAIL && Pq_->plant == 0;                   // wave-uniform
-        const int l16 = lane & 15, i6 = (l16 < 6) ? l16 : 0, j = TAIL ? ((lane >= 30) ? lane - 30 : lane) : (lane & 31), js = (j < 30) ? j : 0;
-        const double wv = L[P_W12 + ((l16 < 12) ? l16 : 0)];
+        const int l16 = lane & 15, i6 = LANE_IS((lane & 15) < 6) ? l16 : 0, j = TAIL ? (LANE_IS(lane >= 30) ? lane - 30 : lane) : (lane & 31);
+        const int js = LANE_IS((TAIL ? ((lane >= 30) ? lane - 30 : lane) : (lane & 31)) < 30) ? j : 0;
+        const double wv = L[P_W12 + (LANE_IS((lane & 15) < 12) ? l16 : 0)];
         // what the tail needs besides a, ahead of the chains: P_X0 belongs to this evaluation until wave 0's next phase_com_x, the helper
         // wrote P_XDQ before the "solve | tiles" join
         double X0r[21], er[3], xdq = 0.0;
-        const int kb = (lane >= 30 && lane < 36) ? lane - 30 : 0;
-        if constexpr (TAIL) { base_acc_load(L, kb, X0r, er); xdq = L[P_XDQ + ((lane < 30) ? lane : 0)]; }
+        const int kb = LANE_IS(lane >= 30 && lane < 36) ? lane - 30 : 0;
+        if constexpr (TAIL) { base_acc_load(L, kb, X0r, er); xdq = L[P_XDQ + (LANE_IS(lane < 30) ? lane : 0)]; }
         const double *jc = L + P_JC + i6, *si = L + P_SI + 6 * i6, *yt = L + P_YT + js;      // base columns of the feet Jacobian: P_JC[foot][row][0..5]
         double jm[12], sm[6], ym[6];
 #pragma unroll
@@ -3218,7 +3242,7 @@ __device__ __forceinline__ int phase_qp(double *L, LmhCParams &P, int ph, int wi
         bdot6(nl, r, sm);
         const double lam = -nl;                                    // lam = -Si r  (nothing else reads it)
         bdot6(s, lam, ym);
-        if ((!fz || tail.k4) && lane < 30) L[P_A + lane] = -s;     // a = -(Y_g + Y_M lam)
+        if ((!fz || tail.k4) && LANE_IS(lane < 30)) L[P_A + lane] = -s;     // a = -(Y_g + Y_M lam)
         if (fz) {
             WSYNC();
             WSTAMP(26);
@@ -3229,9 +3253,9 @@ __device__ __forceinline__ int phase_qp(double *L, LmhCParams &P, int ph, int wi
             double a6[6];
 #pragma unroll
             for (int c = 0; c < 6; c++) a6[c] = bcast_lane(av, c);
-            const double val = base_acc_world(X0r, er, a6, kb);
+            const double val = base_acc_world(X0r, er, a6, LANE_IS(!(lane >= 33 && lane < 36)), LANE_IS(lane == 33), LANE_IS(lane == 34));     // kb < 3 | kb == 3 | kb == 4
             tail.on = true;
-            tail.xd = (lane < 30) ? xdq : (lane < 36) ? val : av;
+            tail.xd = LANE_IS(lane < 30) ? xdq : LANE_IS(lane < 36) ? val : av;
             // non-finite guard (see controller_eval) on the registers: every a[i] and every w[i] sits in some lane
             if (__ballot(!(fabs(av) <= 1.0e300) || !(fabs(wv) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
             return flags;
@@ -3288,9 +3312,9 @@ __device__ __forceinline__ void ground_vertex_force(LmhCParams &P, const double 
 template <bool GROUND = false>
 __device__ __forceinline__ void plant_vertex_forces(double *L, LmhCParams &P, int lane, const double *gnd = nullptr)
 {
-    if (lane < 8) {                                                // one lane per (foot, vertex)
-        const int ft = lane >> 2, vi = lane & 3;
-        const double pwx = (vi < 2) ? 0.1 : -0.05, pwy = (vi & 1) ? -0.025 : 0.025, pwz = 0.0;        // Robot.cpp:38-42
+    if (LANE_IS(lane < 8)) {                                       // one lane per (foot, vertex)
+        const int ft = lane >> 2;                                  // (vertex vi = lane & 3)
+        const double pwx = LANE_IS((lane & 3) < 2) ? 0.1 : -0.05, pwy = LANE_IS((lane & 1) != 0) ? -0.025 : 0.025, pwz = 0.0;        // Robot.cpp:38-42
         // offsets are world-aligned for the flat foot (controller.cpp:225-270) and turn with it: r_v = R_sole Rf_q0' p_v
         double p[3];
 #pragma unroll
@@ -3322,7 +3346,7 @@ __device__ __forceinline__ void plant_vertex_forces(double *L, LmhCParams &P, in
         o[3] = f0; o[4] = f1; o[5] = f2;
         }
     }
-    if (lane >= 32) L[PL_ZERO + lane - 32] = 0.0;
+    if (LANE_IS(lane >= 32)) L[PL_ZERO + lane - 32] = 0.0;
     WSYNC();
 }
 // entry `lane` < 12 of the contact wrench about the sole origins, vertices summed in order
@@ -3336,7 +3360,7 @@ __device__ __forceinline__ double plant_wrench_entry(const double *L, int lane)
 __device__ __forceinline__ double plant_jt_dw(const double *L, int lane)
 {
     double r = 0.0;
-    if (lane < 18) {
+    if (LANE_IS(lane < 18)) {
 #pragma unroll
         for (int row = 0; row < 12; row++) r += jdense(L, row, lane) * L[PL_DW + row];
     }
@@ -3349,13 +3373,14 @@ __device__ __forceinline__ int plant_minv(double *L, int lane, SINK sink)
 {
     int notspd = 0;
     {   // limb blocks: DPP row dr = limb (RL, LL, RA, LA), lane l16 < 6 = joint of the limb (arms: a unit row pads 5 -> 6)
-        const int dr = lane >> 4, l16 = lane & 15;
-        const int nl = (dr < 2) ? 6 : 5, js = (dr == 0) ? 0 : (dr == 1) ? 6 : (dr == 2) ? 12 : 17;
-        const bool real = l16 < nl;
+        const int l16 = lane & 15;                                 // (DPP row dr = lane >> 4)
+        const bool legrow = LANE_IS(lane < 32);
+        const int js = LANE_IS(lane < 16) ? 0 : legrow ? 6 : LANE_IS(lane < 48) ? 12 : 17;
+        const bool real = LANE_IS((lane & 15) < ((lane < 32) ? 6 : 5));      // l16 < nl, nl = 6 joints of a leg | 5 of an arm
         const int ja = js + (real ? l16 : 0);
         double a[6], b[7];
 #pragma unroll
-        for (int c = 0; c < 6; c++) { const double hv = L[P_HL + 6 * ja + ((c < 5) ? c : (dr < 2 ? 5 : 0))]; a[c] = (real && c < nl) ? hv : ((l16 == c && l16 < 6) ? 1.0 : 0.0); }
+        for (int c = 0; c < 6; c++) { const double hv = L[P_HL + 6 * ja + ((c < 5) ? c : (legrow ? 5 : 0))]; a[c] = (real && (c < 5 || legrow)) ? hv : ((l16 == c && l16 < 6) ? 1.0 : 0.0); }
         { const double rv = L[PL_R + 6 + ja]; b[0] = real ? rv : 0.0; }
 #pragma unroll
         for (int m = 0; m < 6; m++) { const double fv = L[P_MTOP + 30 * m + 6 + ja]; b[1 + m] = real ? fv : 0.0; }
@@ -3366,19 +3391,20 @@ __device__ __forceinline__ int plant_minv(double *L, int lane, SINK sink)
         for (int c = 0; c < 7; c++) L[real ? PL_B + 7 * ja + c : Q_TRASH + lane] = b[c] * myinv;
         if constexpr (CHECK) notspd |= bad;
     }
-    if (lane < 14) {                                               // head: 2 x 2 in closed form
+    if (LANE_IS(lane < 14)) {                                      // head: 2 x 2 in closed form
         const int i = lane / 7, c = lane % 7;
         const double h00 = L[P_HL + 6 * 22], h01 = L[P_HL + 6 * 22 + 1], h10 = L[P_HL + 6 * 23], h11 = L[P_HL + 6 * 23 + 1];
-        const double r0 = (c == 0) ? L[PL_R + 6 + 22] : L[P_MTOP + 30 * (c - 1) + 6 + 22], r1 = (c == 0) ? L[PL_R + 6 + 23] : L[P_MTOP + 30 * (c - 1) + 6 + 23];
+        const bool c0 = LANE_IS(lane % 7 == 0);
+        const double r0 = c0 ? L[PL_R + 6 + 22] : L[P_MTOP + 30 * (c - 1) + 6 + 22], r1 = c0 ? L[PL_R + 6 + 23] : L[P_MTOP + 30 * (c - 1) + 6 + 23];
         const double det = h00 * h11 - h01 * h10;
-        L[PL_B + 7 * (22 + i) + c] = (i == 0) ? (h11 * r0 - h01 * r1) / det : (h00 * r1 - h10 * r0) / det;
+        L[PL_B + 7 * (22 + i) + c] = LANE_IS(lane < 7) ? (h11 * r0 - h01 * r1) / det : (h00 * r1 - h10 * r0) / det;
         if constexpr (CHECK) notspd |= (int)!(h00 > 0.0 && det > 0.0);
     }
     WSYNC();
     {   // base: S_b = Ic0 - F2 B_M, rhs = r_b - F2 B_r   (one matrix-core tile, K = 24)
         const int tr = lane & 15, tq = lane >> 4;
         const double *zero = L + PL_ZERO;
-        const v4d fb = mfma_ptr<6, 4, 28>((tr < 6) ? L + P_MTOP + 30 * tr + 6 + tq : zero, (tr < 7) ? L + PL_B + 7 * tq + tr : zero);
+        const v4d fb = mfma_ptr<6, 4, 28>(LANE_IS((lane & 15) < 6) ? L + P_MTOP + 30 * tr + 6 + tq : zero, LANE_IS((lane & 15) < 7) ? L + PL_B + 7 * tq + tr : zero);
 #pragma unroll
         for (int g = 0; g < 2; g++) {
             const int m = tq + 4 * g;
@@ -3390,18 +3416,18 @@ __device__ __forceinline__ int plant_minv(double *L, int lane, SINK sink)
     WSYNC();
     {
         double a[6], b[1];
-        const int l16 = lane & 15, lr = (l16 < 6) ? l16 : 0;       // (a copy of the system per DPP row)
+        const int l16 = lane & 15, lr = LANE_IS((lane & 15) < 6) ? l16 : 0;       // (a copy of the system per DPP row)
 #pragma unroll
         for (int c = 0; c < 6; c++) a[c] = L[PL_SB + 7 * lr + 1 + c];
         b[0] = L[PL_SB + 7 * lr];
         const int bad6 = gj_solve_regs<6, 1>(a, b, 0x3Fu);
         if constexpr (CHECK) notspd |= bad6; else (void)bad6;
-        if (lane < 6) L[PL_DAB + lane] = b[0];
+        if (LANE_IS(lane < 6)) L[PL_DAB + lane] = b[0];
     }
     WSYNC();
-    if (lane < 30) {
+    if (LANE_IS(lane < 30)) {
         double da;
-        if (lane < 6) da = L[PL_DAB + lane];
+        if (LANE_IS(lane < 6)) da = L[PL_DAB + lane];
         else {
             const double *B = L + PL_B + 7 * (lane - 6);
             da = B[0];
@@ -3418,9 +3444,9 @@ __device__ __forceinline__ void phase_plant(double *L, LmhCParams &P)
 {
     const int lane = LANE;
     plant_vertex_forces(L, P, lane);
-    if (lane < 12) L[PL_DW + lane] = plant_wrench_entry(L, lane) - L[P_W12 + lane];      // w_c - w
+    if (LANE_IS(lane < 12)) L[PL_DW + lane] = plant_wrench_entry(L, lane) - L[P_W12 + lane];      // w_c - w
     WSYNC();
-    if (lane < 30) L[PL_R + lane] = plant_jt_dw(L, lane) + (L[P_C + lane] - L[P_VHS + lane]);    // + C(q, v_prev) - C(q, v); P_VHS: the plant's own Newton-Euler pass at the current velocity
+    if (LANE_IS(lane < 30)) L[PL_R + lane] = plant_jt_dw(L, lane) + (L[P_C + lane] - L[P_VHS + lane]);    // + C(q, v_prev) - C(q, v); P_VHS: the plant's own Newton-Euler pass at the current velocity
     WSYNC();
     (void)plant_minv<false>(L, lane, [&](double da) { L[PL_AP + lane] = L[P_A + lane] + da; });
 }
@@ -3431,9 +3457,9 @@ __device__ __forceinline__ void phase_plant(double *L, LmhCParams &P)
 __device__ __forceinline__ void phase_outputs_tau(double *L)
 {
     const int lane = LANE;
-    if (lane < 24) {
-        const int a = lane, st = f_jstart(a), ft = (a < 6) ? 0 : (a < 12) ? 1 : -1;
-        const int nl = (a < 12) ? 6 : (a < 22) ? 5 : 2;
+    if (LANE_IS(lane < 24)) {
+        const int a = lane, st = f_jstart(a), ft = LANE_IS(lane < 6) ? 0 : LANE_IS(lane < 12) ? 1 : -1;
+        const int nl = LANE_IS(lane < 12) ? 6 : LANE_IS(lane < 22) ? 5 : 2;
         double s = 0.0;
         for (int c = 0; c < 6; c++) s += L[P_MTOP + 30 * c + 6 + a] * L[P_A + c];
         for (int b = 0; b < nl; b++) s += L[P_HL + 6 * a + b] * L[P_A + 6 + st + b];
@@ -3446,7 +3472,7 @@ __device__ __forceinline__ void phase_outputs_tau(double *L)
 __device__ __forceinline__ void phase_outputs_qdd(double *L, int a_src = P_A)
 {
     const int lane = LANE;
-    if (lane >= 32 && lane < 38) {
+    if (LANE_IS(lane >= 32 && lane < 38)) {
         const int k = lane - 32;
         double X[21], er[3], a[6];
         base_acc_load(L, k, X, er);
@@ -3454,7 +3480,7 @@ __device__ __forceinline__ void phase_outputs_qdd(double *L, int a_src = P_A)
         for (int c = 0; c < 6; c++) a[c] = L[a_src + c];
         L[P_QDD + k] = base_acc_world(X, er, a, k);
     }
-    if (lane >= 40 && lane < 64) L[P_QDD + 6 + (lane - 40)] = L[a_src + 6 + (lane - 40)];
+    if (LANE_IS(lane >= 40 && lane < 64)) L[P_QDD + 6 + (lane - 40)] = L[a_src + 6 + (lane - 40)];
     WSYNC();
 }
 
@@ -3487,7 +3513,7 @@ __device__ __forceinline__ int controller_eval(double *L, LmhCParams &P, int ins
         kinv_prework(L, P);
     }
     if constexpr (NW == 1) {                                       // single-wave schedule: no K^-1 prepared; references first
-        if (LANE == 0) L[P_KF + 2] = 0.0;
+        if (LANE_IS(lane == 0)) L[P_KF + 2] = 0.0;
         refs_prepare(L, P, inst, t);
         WSYNC();
     }
@@ -3547,7 +3573,7 @@ __device__ __forceinline__ int controller_eval(double *L, LmhCParams &P, int ins
     if constexpr (REF) {
         // a non-finite word of the caller's reference is the robot's LMH_FLAG_NONFINITE whatever the solver makes of it: on the words chain A
         // published (behind the join: wave 0 writes the status record)
-        const double w = L[P_MPC + 2 + ((LANE < 6) ? LANE : 0)];
+        const double w = L[P_MPC + 2 + ((LANE_IS(lane < 6)) ? LANE : 0)];
         if (__ballot(!(fabs(w) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
         if constexpr (BOX) flags |= __builtin_amdgcn_readfirstlane(zoh_box_words(P.horizon + 1)[ZB_FLAGS]);      // the sample's flags (lmh_mpc_box_step's)
     }
@@ -3590,11 +3616,11 @@ __device__ __forceinline__ int controller_eval(double *L, LmhCParams &P, int ins
     // stages of four any more
     if (TAIL && wid != 0) return flags;
     double chk = 0.0;
-    if (LANE < 30) chk = L[P_A + LANE]; else if (LANE >= 32 && LANE < 44) chk = L[P_W12 + LANE - 32];
+    if (LANE_IS(lane < 30)) chk = L[P_A + LANE]; else if (LANE_IS(lane >= 32 && lane < 44)) chk = L[P_W12 + LANE - 32];
     const bool nf = !(fabs(chk) <= 1.0e300);
     if (__ballot(nf) != 0ull) flags |= LMH_FLAG_NONFINITE;
     if (TAIL && wid == 0) {                                        // (the plant: its xdot from where its path leaves it)
-        const int l60 = (LANE < 60) ? LANE : 0;
+        const int l60 = (LANE_IS(lane < 60)) ? LANE : 0;
         tail.xd = L[(l60 >= 30) ? P_QDD + l60 - 30 : P_XDQ + l60];
     }
     return flags;
@@ -3605,7 +3631,7 @@ __device__ __forceinline__ void load_common(double *L, LmhCParams &P, int inst)
     const double *mo = P.model + (size_t)P.model_stride * inst;
     for (int e = LANE; e < 393; e += 64) L[P_MODEL + e] = mo[e];
     for (int e = LANE; e < 228; e += 64) L[P_GCOL + e] = P.gcol[e];            // gcol | gi6 | gpinv are contiguous
-    if (LANE < 48) {
+    if (LANE_IS(lane < 48)) {
         const int ft = LANE / 24, ax = (LANE % 24) / 8, k = LANE % 8;
         double v = 0.0;
 #pragma unroll
@@ -3615,14 +3641,14 @@ __device__ __forceinline__ void load_common(double *L, LmhCParams &P, int inst)
                 if (ax == a && k == kk) v = ft ? P.lF[a][kk] : P.rF[a][kk];
             }
         L[P_POLY + LANE] = v;
-    } else if (LANE < 54) {
+    } else if (LANE_IS(lane < 54)) {
         const int q = LANE - 48;
         int n = 0;
 #pragma unroll
         for (int a = 0; a < 3; a++) { if (q == a) n = P.rFn[a]; if (q == 3 + a) n = P.lFn[a]; }
         L[P_POLY + LANE] = (double)n;
     }
-    if (LANE == 0) {                                               // clock-only reference cache (refs_prepare): empty
+    if (LANE_IS(lane == 0)) {                                               // clock-only reference cache (refs_prepare): empty
         L[P_RK] = -1073741824.0; L[P_RPH] = 0.0; L[P_RT0] = 0.0;
         L[P_RXS] = P.xscale ? P.xscale[inst] : 1.0;                // walking extension: per-instance step length
     }
@@ -3635,7 +3661,7 @@ __device__ __forceinline__ void load_common(double *L, LmhCParams &P, int inst)
         double s0 = 0.0, s1 = 0.0;                                 // sum K Px0, sum K Px1 (refs_mpc)
         for (int i = LANE; i <= N; i += 64) { s0 += mp[i] * mp[(N + 1) + i]; s1 += mp[i] * mp[2 * (N + 1) + i]; }
         s0 = wave_sum(s0); s1 = wave_sum(s1);
-        if (LANE == 0) { L[P_PRE + 2] = s0; L[P_PRE + 3] = s1; }
+        if (LANE_IS(lane == 0)) { L[P_PRE + 2] = s0; L[P_PRE + 3] = s1; }
     }
     WSYNC();
 }
@@ -3643,7 +3669,7 @@ __device__ __forceinline__ void load_common(double *L, LmhCParams &P, int inst)
 // slot (Robot::v_, P_VP) takes the same v, so that every velocity product is taken at that one velocity.  The caller fences.
 __device__ __forceinline__ void load_qv(double *L, const double *q, const double *v, int inst, int lane, bool with_vp)
 {
-    if (lane < 30) {
+    if (LANE_IS(lane < 30)) {
         const double vv = v ? v[30 * (size_t)inst + lane] : 0.0;
         L[P_Q + lane] = q[30 * (size_t)inst + lane];
         L[P_V + lane] = vv;
@@ -3654,11 +3680,11 @@ __device__ __forceinline__ void load_qv(double *L, const double *q, const double
 __device__ __forceinline__ void store_out(const double *L, double *out, bool keep_qdd_slots = false)
 {
     const int lane = LANE;
-    if (lane < 24) out[lane] = L[P_TAU + lane];
-    else if (lane < 36) out[lane] = L[P_W12 + lane - 24];
+    if (LANE_IS(lane < 24)) out[lane] = L[P_TAU + lane];
+    else if (LANE_IS(lane < 36)) out[lane] = L[P_W12 + lane - 24];
     if (!keep_qdd_slots) for (int e = lane; e < 30; e += 64) out[36 + e] = L[P_QDD + e];   // (the diagnostic rollout keeps its counters there)
-    if (lane >= 32 && lane < 38) out[66 + lane - 32] = L[P_COM + lane - 32];        // CoM | comVel (Robot::getCoM / getComVel)
-    if (lane >= 40 && lane < 46) out[72 + lane - 40] = L[P_MPC + 2 + lane - 40];    // Mpc3dLip::getXRef | getYRef
+    if (LANE_IS(lane >= 32 && lane < 38)) out[66 + lane - 32] = L[P_COM + lane - 32];        // CoM | comVel (Robot::getCoM / getComVel)
+    if (LANE_IS(lane >= 40 && lane < 46)) out[72 + lane - 40] = L[P_MPC + 2 + lane - 40];    // Mpc3dLip::getXRef | getYRef
 }
 
 // What a launch of the NW-wave evaluation schedule does before its first controller_eval (lmh_eval_kernel, lmh_rollout_zoh_kernel): wave 0
@@ -3679,7 +3705,7 @@ __device__ __forceinline__ unsigned eval_begin(double *L, LmhCParams &P, int ins
         for (int e = LANE; e < 91; e += 64) L[P_Q + e] = st[e];    // q | v | v_prev | t
         F = (unsigned)status[LMH_STATUS_STRIDE * inst + 3];
         F = P.warm_start ? ~F : 0xFFFFFFFFu;                       // status keeps the ACTIVE mask
-        if (LANE == 0) { L[P_KF] = (double)F; L[P_KF + 2] = 0.0; L[P_ORI] = 0.0; }             // no K_f^-1 stored yet, no orientation term formed ahead
+        if (LANE_IS(lane == 0)) { L[P_KF] = (double)F; L[P_KF + 2] = 0.0; L[P_ORI] = 0.0; }             // no K_f^-1 stored yet, no orientation term formed ahead
         WSYNC();
     }
     bsync<NW>();
@@ -3717,8 +3743,8 @@ __device__ __forceinline__ void lmh_eval_body(double *L, double *state, double *
     bsync<NW>();                                                   // torques of the helper wave
     if (wid == 0) {
         store_out(L, out + (size_t)LMH_OUT_STRIDE * inst);
-        if (LANE < 30) st[60 + LANE] = L[P_V + LANE];              // Robot::v_ <- dq (controller.cpp:59)
-        if (LANE == 0) store_status(status, inst, k, iters, flags, F);
+        if (LANE_IS(lane < 30)) st[60 + LANE] = L[P_V + LANE];              // Robot::v_ <- dq (controller.cpp:59)
+        if (LANE_IS(lane == 0)) store_status(status, inst, k, iters, flags, F);
     }
 }
 template <bool DEBUG, typename R, int NW = (DEBUG ? 1 : 2), bool QF32 = false>
@@ -3785,25 +3811,31 @@ __device__ __forceinline__ void rk4_stage(double *L, int stage, int lane, double
     // branch-free: every lane loads from a valid address and forms the few products of the base rows, the lane's class picks the result
     // (the lane-class branches and the four-way stage switch were ~100 scalar instructions per call)
     double xd;
-    const int l60 = (lane < 60) ? lane : 0;
+    // (on the pipelined schedules, XDQ != 0, l60 and the class test below stay run-time compares: as constant masks they cost the
+    // mixed-precision trace instantiations a spilled VGPR and 8 B of scratch; the plain schedule of the fp32-QP kernels, XDQ = 0, is the
+    // other way round -- profiles/r32_resource_usage.txt.  The selects on the lane's class further down are masks everywhere)
+    int l60;
+    bool acc;                                                      // l60 >= 30
+    if constexpr (XDQ == 0) { l60 = LANE_IS(lane < 60) ? lane : 0; acc = LANE_IS(lane >= 30 && lane < 60); }
+    else { l60 = (lane < 60) ? lane : 0; acc = l60 >= 30; }
     if constexpr (XDQ == 3) xd = xdr;
-    else if constexpr (XDQ == 2) xd = L[(l60 >= 30) ? P_QDD + l60 - 30 : P_XDQ + l60];
+    else if constexpr (XDQ == 2) xd = L[acc ? P_QDD + l60 - 30 : P_XDQ + l60];
     else {
-        const int l30 = (l60 < 30) ? l60 : 0;
-        const double vq = L[(l60 >= 30) ? P_QDD + l60 - 30 : P_V + l60];       // joint rates | accelerations: xdot as it stands
+        const double vq = L[acc ? P_QDD + l60 - 30 : P_V + l60];               // joint rates | accelerations: xdot as it stands
         const double w0 = L[P_V + 3], w1 = L[P_V + 4], w2 = L[P_V + 5];
         const double p0 = L[P_Q], p1 = L[P_Q + 1], p2 = L[P_Q + 2];
         const double sp = L[xd4], cp = L[xd4 + 1], sy = L[xd4 + 2], cy = L[xd4 + 3];
         // v_classic = v_spatial + w x p (apps/offline/main.cpp:107-112)
-        const double cr = (l30 == 0) ? (-w2 * p1 + w1 * p2) : (l30 == 1) ? (w2 * p0 - w0 * p2) : (-w1 * p0 + w0 * p1);
+        // (l30 = lane below 30, else 0: the lanes that are not base rows shadow row 0)
+        const double cr = LANE_IS(lane == 0 || lane >= 30) ? (-w2 * p1 + w1 * p2) : LANE_IS(lane == 1) ? (w2 * p0 - w0 * p2) : (-w1 * p0 + w0 * p1);
         // matrixAngularVelToEulerDot (generalizedFunctions.cpp:43-50): one reciprocal of cos(pitch) (rcp + two Newton steps, full fp64)
         // serves the three quotients -- each was a ~13-instruction IEEE division on the helper's path beside wave 0's 15 x 15 solve
         const double icp = fast_rcp(cp), tp = sp * icp;
-        const double eu = (l30 == 3) ? (cy * icp) * w0 + (sy * icp) * w1 + 0.0 * w2
-                        : (l30 == 4) ? (-sy) * w0 + cy * w1 + 0.0 * w2
+        const double eu = LANE_IS(lane == 3) ? (cy * icp) * w0 + (sy * icp) * w1 + 0.0 * w2
+                        : LANE_IS(lane == 4) ? (-sy) * w0 + cy * w1 + 0.0 * w2
                                      : (cy * tp) * w0 + (sy * tp) * w1 + 1.0 * w2;
-        xd = (l60 < 3) ? vq + cr : (l60 < 6) ? eu : vq;
-        if constexpr (XDQ == 1) L[(lane < 30) ? P_XDQ + lane : (int)P_DUMP] = xd;
+        xd = LANE_IS(lane < 3 || lane >= 60) ? vq + cr : LANE_IS(lane < 6 || lane >= 60) ? eu : vq;
+        if constexpr (XDQ == 1) L[LANE_IS(lane < 30) ? P_XDQ + lane : (int)P_DUMP] = xd;
     }
     // rk4.hpp:12-17 with the stage's coefficients as scalars: ksum <- a ksum + b xd (k1 + 2 k2 + 2 k3 + k4), x <- x + e ksum (e = dt / 6 at the
     // fourth stage, else 0), xs <- x + c xd (c = dt / 2, dt / 2, dt, 0).  a in {0, 1} and the zero terms are exact: the same roundings as the
@@ -3839,7 +3871,7 @@ __device__ __forceinline__ int push_seek(double *L, LmhCParams &P, int inst, int
         const unsigned long long m = __builtin_amdgcn_ballot_w64(live);
         if (m != 0ull) { c = __builtin_ctzll(m); rel = __builtin_amdgcn_readlane(di, c); }
     }
-    if (lane == 0) { int *pw = (int *)(L + P_PUSH); pw[0] = rel; pw[1] = c; }
+    if (LANE_IS(lane == 0)) { int *pw = (int *)(L + P_PUSH); pw[0] = rel; pw[1] = c; }
     *cur = c;
     return rel;
 }
@@ -3847,12 +3879,12 @@ __device__ __forceinline__ int push_seek(double *L, LmhCParams &P, int inst, int
 __device__ __forceinline__ void push_apply(double *L, LmhCParams &P, int inst, int lane, int rel, int cur, int lim, double &x)
 {
     const double *rec = P.pushes + (size_t)LMH_PUSH_STRIDE * ((size_t)P.push_stride * inst + cur);
-    const bool vl = lane >= 30 && lane < 60;
+    const bool vl = LANE_IS(lane >= 30 && lane < 60);
     const double dv = rec[vl ? 1 + lane - 30 : 1];
     if (vl) x += dv;
     const double tn = (cur + 1 < P.n_push) ? rec[LMH_PUSH_STRIDE] : -1.0;
     const double d = (double)rel + (tn - rec[0]);
-    if (lane == 0) { int *pw = (int *)(L + P_PUSH); pw[0] = (tn >= 0.0 && d < (double)lim) ? (int)d : PUSH_NONE; pw[1] = cur + 1; }
+    if (LANE_IS(lane == 0)) { int *pw = (int *)(L + P_PUSH); pw[0] = (tn >= 0.0 && d < (double)lim) ? (int)d : PUSH_NONE; pw[1] = cur + 1; }
 }
 // per tick (wave 0, once the tick's state is final): is a push due at the start of tick `next` of this chunk?
 __device__ __forceinline__ void push_poll(double *L, LmhCParams &P, int inst, int lane, int next, int lim, double &x)
@@ -3881,21 +3913,21 @@ __device__ __forceinline__ double *trace_slot(double *tr, int every, int done, i
 template <bool QDD_REG>
 __device__ __forceinline__ void trace_wave0(double *tr, const double *L, int lane, double x, double xprev, double xd, double tnext, int k, int itmax, int flags, unsigned F)
 {
-    tr[(lane < 60) ? lane : 30 + lane] = (lane < 60) ? x : (lane == 60) ? tnext : 0.0;      // q | v | t and the pads [91, 94)
-    const bool vp = lane >= 30 && lane < 60;
+    tr[(LANE_IS(lane < 60)) ? lane : 30 + lane] = (LANE_IS(lane < 60)) ? x : (LANE_IS(lane == 60)) ? tnext : 0.0;      // q | v | t and the pads [91, 94)
+    const bool vp = LANE_IS(lane >= 30 && lane < 60);
     // lanes 0..11 the wrench | 12..15 the status record | 16, 17 the state's pads [94, 96) | 18, 19 the out record's pads | 30..59 v_prev
-    const double w = L[P_W12 + ((lane < 12) ? lane : 0)];
-    const double sv = (lane == 12) ? (double)k : (lane == 13) ? (double)itmax : (lane == 14) ? (double)flags : (lane == 15) ? (double)(int32_t)(~F) : 0.0;
-    const int idx = (lane < 12) ? LMH_STATE_STRIDE + 24 + lane : (lane < 16) ? LMH_STATE_STRIDE + LMH_OUT_STRIDE + lane - 12
-                  : (lane < 18) ? 94 + lane - 16 : (lane < 20) ? LMH_STATE_STRIDE + 78 + lane - 18 : 30 + lane;
-    if (lane < 20 || vp) tr[idx] = (lane < 12) ? w : (lane < 20) ? sv : xprev;
+    const double w = L[P_W12 + ((LANE_IS(lane < 12)) ? lane : 0)];
+    const double sv = (LANE_IS(lane == 12)) ? (double)k : (LANE_IS(lane == 13)) ? (double)itmax : (LANE_IS(lane == 14)) ? (double)flags : (LANE_IS(lane == 15)) ? (double)(int32_t)(~F) : 0.0;
+    const int idx = (LANE_IS(lane < 12)) ? LMH_STATE_STRIDE + 24 + lane : (LANE_IS(lane < 16)) ? LMH_STATE_STRIDE + LMH_OUT_STRIDE + lane - 12
+                  : (LANE_IS(lane < 18)) ? 94 + lane - 16 : (LANE_IS(lane < 20)) ? LMH_STATE_STRIDE + 78 + lane - 18 : 30 + lane;
+    if (LANE_IS(lane < 20) || vp) tr[idx] = (LANE_IS(lane < 12)) ? w : (LANE_IS(lane < 20)) ? sv : xprev;
     if constexpr (QDD_REG) { if (vp) tr[LMH_STATE_STRIDE + 36 + lane - 30] = xd; }
-    else { if (lane < 30) tr[LMH_STATE_STRIDE + 36 + lane] = L[P_QDD + lane]; }
+    else { if (LANE_IS(lane < 30)) tr[LMH_STATE_STRIDE + 36 + lane] = L[P_QDD + lane]; }
 }
 // helper wave, behind the fourth stage's evaluation (beside its log store): the words of store_out that it wrote itself
 __device__ __forceinline__ void trace_wave1(double *tr, const double *L, int lane)
 {
-    const bool a = lane < 24, b = lane >= 32 && lane < 38, c = lane >= 40 && lane < 46;
+    const bool a = LANE_IS(lane < 24), b = LANE_IS(lane >= 32 && lane < 38), c = LANE_IS(lane >= 40 && lane < 46);
     const double v = L[a ? P_TAU + lane : b ? P_COM + lane - 32 : c ? P_MPC + 2 + lane - 40 : (int)P_TAU];
     if (a || b || c) tr[LMH_STATE_STRIDE + (a ? lane : b ? 66 + lane - 32 : 72 + lane - 40)] = v;
 }
@@ -3913,12 +3945,12 @@ __device__ __forceinline__ void trace_wave1(double *tr, const double *L, int lan
 __device__ __forceinline__ void metrics_wave0(double *m, const double *L, double x, int flags)
 {
     const int lane = LANE;                                         // its own opaque lane id: the word addresses are formed here, every tick, not carried across the tick loop
-    if (lane < 60) {
+    if (LANE_IS(lane < 60)) {
         double *p = m + LMH_METRICS_OFF_XMIN + lane;
         { const double lo = p[0]; if (x < lo) p[0] = x; }
         { const double hi = p[LMH_METRICS_OFF_XMAX - LMH_METRICS_OFF_XMIN]; if (x > hi) p[LMH_METRICS_OFF_XMAX - LMH_METRICS_OFF_XMIN] = x; }
     }
-    if (lane < 12) {
+    if (LANE_IS(lane < 12)) {
         double *p = m + LMH_METRICS_OFF_WMIN + lane;
         const double w = L[P_W12 + lane];
         { const double lo = p[0]; if (w < lo) p[0] = w; }
@@ -3926,12 +3958,12 @@ __device__ __forceinline__ void metrics_wave0(double *m, const double *L, double
     }
     // down: lane 2 holds the base height, lanes 3 and 4 roll and pitch; each compares its own word against its threshold (a NaN is down)
     bool dn = false;
-    if (lane >= 2 && lane < 5) {
-        const double thr = m[(lane == 2) ? LMH_METRICS_OFF_Z_MIN : LMH_METRICS_OFF_TILT_MAX];
-        dn = (lane == 2) ? !(x >= thr) : !(fabs(x) <= thr);
+    if (LANE_IS(lane >= 2 && lane < 5)) {
+        const double thr = m[(LANE_IS(lane == 2)) ? LMH_METRICS_OFF_Z_MIN : LMH_METRICS_OFF_TILT_MAX];
+        dn = (LANE_IS(lane == 2)) ? !(x >= thr) : !(fabs(x) <= thr);
     }
     const bool down = __ballot(dn) != 0;
-    if (lane == 0) {
+    if (LANE_IS(lane == 0)) {
         const double c = m[LMH_METRICS_OFF_COUNT];
         if ((flags & 15) != 0 && m[LMH_METRICS_OFF_FIRST_FLAG] < 0.0) m[LMH_METRICS_OFF_FIRST_FLAG] = c;
         if (down && m[LMH_METRICS_OFF_FIRST_FALL] < 0.0) m[LMH_METRICS_OFF_FIRST_FALL] = c;
@@ -3947,7 +3979,7 @@ template <bool UNIT_LANE>
 __device__ __forceinline__ void metrics_wave1(double *m, const double *L, int lane_unit)
 {
     const int lane = UNIT_LANE ? lane_unit : LANE;
-    const bool a = lane < 24, e = lane == 32 || lane == 33;
+    const bool a = LANE_IS(lane < 24), e = LANE_IS(lane == 32) || LANE_IS(lane == 33);
     if (a || e) {
         double v = L[a ? P_TAU + lane : P_COM + lane - 32];
         if (e) v = v - L[P_MPC + 2 + 3 * (lane - 32)];
@@ -4056,22 +4088,22 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
     LMH_POISON_LDS(L, LDS_DOUBLES);
     if (wid == 0) {
         load_common(L, P, inst);
-        x = (lane < 60) ? st[lane] : 0.0;
+        x = (LANE_IS(lane < 60)) ? st[lane] : 0.0;
         {   // velocity pushes: the record in HBM never holds a push whose tick has not started, so one due at this chunk's first tick goes in here
             int pc = 0;
             const int pr = push_seek(L, P, inst, lane, t, n_here, &pc);
             if (pr == 0) push_apply(L, P, inst, lane, 0, pc, n_here, x);
         }
-        if (lane < 30) L[P_VP + lane] = st[60 + lane];
+        if (LANE_IS(lane < 30)) L[P_VP + lane] = st[60 + lane];
         F = (unsigned)status[LMH_STATUS_STRIDE * inst + 3];
         F = P.warm_start ? ~F : 0xFFFFFFFFu;
-        if (lane == 0) { L[P_KF] = (double)F; L[P_KF + 2] = 0.0; L[P_ORI] = 0.0; }             // no K_f^-1 stored yet, no orientation term formed ahead
+        if (LANE_IS(lane == 0)) { L[P_KF] = (double)F; L[P_KF + 2] = 0.0; L[P_ORI] = 0.0; }             // no K_f^-1 stored yet, no orientation term formed ahead
         if constexpr (PIPE) {
-            if (lane < 60) L[P_Q + lane] = x;
+            if (LANE_IS(lane < 60)) L[P_Q + lane] = x;
             WSYNC();
             phase_fk<R>(L, P.lcoef);                               // kinematics of the first evaluation (every later one is run ahead by wave 1)
         }
-    } else x = (lane < 30) ? st[lane] : 0.0;
+    } else x = (LANE_IS(lane < 30)) ? st[lane] : 0.0;
     bsync<2>();
     if (PIPE && wid == 1) refs_prepare(L, P, inst, t);             // clock-only references of the first evaluation (needs load_common's cache reset)
     int k = 0, iters = 0, flags = 0, itmax = 0;
@@ -4102,18 +4134,18 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
             RkTail tail = {false, false, 0.0};
             if (!TAIL && wid == 0) {
                 WSYNC();
-                if (lane < 60) L[P_Q + lane] = xs;
+                if (LANE_IS(lane < 60)) L[P_Q + lane] = xs;
                 WSYNC();
             }
 #ifdef LMH_DIAG_TL
-            if (lane == 0) g_tl[wid] = (log && tick0 + tick == n_ticks - 1 && stage == LMH_DIAG_TL) ? log + (size_t)256 * inst : nullptr;
+            if (LANE_IS(lane == 0)) g_tl[wid] = (log && tick0 + tick == n_ticks - 1 && stage == LMH_DIAG_TL) ? log + (size_t)256 * inst : nullptr;
             WSYNC();
 #endif
 #ifdef LMH_SUBSTAMPS
 #ifdef LMH_DIAG_STAGE                                              // the per-join split of ONE Runge-Kutta stage's evaluations (the others land in slot 7)
-            if (lane == 0) L[D_JIDX + wid] = (stage == LMH_DIAG_STAGE) ? 0.0 : 100.0;
+            if (LANE_IS(lane == 0)) L[D_JIDX + wid] = (stage == LMH_DIAG_STAGE) ? 0.0 : 100.0;
 #else
-            if (lane == 0) L[D_JIDX + wid] = 0.0;
+            if (LANE_IS(lane == 0)) L[D_JIDX + wid] = 0.0;
 #endif
 #endif
             // wave 1, once its share of the QP set-up is done: the next stage's configuration (rk4_stage, position half) and the clock-only
@@ -4132,7 +4164,7 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
                         // two shares are level and wave 0 keeps the term (refs_pd_feet)
                         const bool ori = __builtin_amdgcn_readfirstlane((int)L[P_RPH]) != LMH_PHASE_DOUBLE;
                         if (ori) refs_feet_orientation(L, *Pe, L + A_T + 84, 84);
-                        if (lane == 0) L[P_ORI] = ori ? 1.0 : 0.0;
+                        if (LANE_IS(lane == 0)) L[P_ORI] = ori ? 1.0 : 0.0;
                     }
                     WSTAMP(70);
                 }
@@ -4154,8 +4186,8 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
                 }
                 // one publish: Robot::v_ <- dq and the state of the next evaluation; behind the recovery's join wave 0 has read nothing
                 // from LDS, and the helper touches neither.  The accelerations only where somebody reads them (store_out, end of a chunk)
-                if (lane >= 30 && lane < 60) { L[P_VP + lane - 30] = xprev; if (stage == 3) L[P_QDD + lane - 30] = tail.xd; }
-                if (lane < 60) L[P_Q + lane] = xs;
+                if (LANE_IS(lane >= 30 && lane < 60)) { L[P_VP + lane - 30] = xprev; if (stage == 3) L[P_QDD + lane - 30] = tail.xd; }
+                if (LANE_IS(lane < 60)) L[P_Q + lane] = xs;
                 WSYNC();
             } else if (wid == 0) {
                 itmax = (iters > itmax) ? iters : itmax;
@@ -4171,12 +4203,12 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
                 }
                 // Robot::v_ <- dq for the next evaluation
                 WSYNC();
-                if (lane >= 30 && lane < 60) L[P_VP + lane - 30] = xprev;
+                if (LANE_IS(lane >= 30 && lane < 60)) L[P_VP + lane - 30] = xprev;
             }
             WSTAMP(72);
 #ifdef LMH_DIAG_TL
             WSYNC();
-            if (lane == 0) g_tl[wid] = nullptr;
+            if (LANE_IS(lane == 0)) g_tl[wid] = nullptr;
             WSYNC();
 #endif
         }
@@ -4186,8 +4218,8 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
         if (log) {                                                  // each wave logs what it produced: wave 1 the torques, wave 0 the wrench
 #endif
             double *lg = log + ((size_t)(tick0 + tick) * P.n_instances + inst) * 36;
-            if (wid != 0) { if (lane < 24) lg[lane] = L[P_TAU + lane]; }
-            else if (lane >= 24 && lane < 36) lg[lane] = L[P_W12 + lane - 24];
+            if (wid != 0) { if (LANE_IS(lane < 24)) lg[lane] = L[P_TAU + lane]; }
+            else if (LANE_IS(lane >= 24 && lane < 36)) lg[lane] = L[P_W12 + lane - 24];
         }
         if (TRACE && wid != 0) {                                    // the helper's share of the tick's sample (wave 0's left at the fourth stage)
             double *tr = trace_slot(trace, trace_every, tick0 + tick + 1, P.n_instances, inst);
@@ -4198,7 +4230,7 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
     }
     bsync<2>();                                                    // the last torques (helper wave) are in LDS
 #ifdef LMH_SUBSTAMPS
-    if (wid == 1 && lane == 0) st[94] = (double)__builtin_amdgcn_s_getreg(63492);      // HW_ID of wave 1
+    if (wid == 1 && LANE_IS(lane == 0)) st[94] = (double)__builtin_amdgcn_s_getreg(63492);      // HW_ID of wave 1
 #endif
     if (wid == 0) {
         WSYNC();
@@ -4208,7 +4240,7 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
         store_out(L, out + (size_t)LMH_OUT_STRIDE * inst);
 #endif
 #ifdef LMH_SUBSTAMPS
-        if (lane == 0) {                                           // diagnostic build: this robot's cycles in the launch and inside barriers (pad slots), summed over its chunks
+        if (LANE_IS(lane == 0)) {                                           // diagnostic build: this robot's cycles in the launch and inside barriers (pad slots), summed over its chunks
             double *o_ = out + (size_t)LMH_OUT_STRIDE * inst;
             const bool first_ = tick0 == 0;
             const long long now_ = wall_clock64();
@@ -4222,9 +4254,9 @@ lmh_rollout_kernel(const LmhDevParams *__restrict__ Pg, int *__restrict__ ticket
             st[95] = (double)__builtin_amdgcn_s_getreg(63508);
         }
 #endif
-        if (lane < 60) st[lane] = x;
-        if (lane < 30) st[60 + lane] = L[P_VP + lane];
-        if (lane == 0) {
+        if (LANE_IS(lane < 60)) st[lane] = x;
+        if (LANE_IS(lane < 30)) st[60 + lane] = L[P_VP + lane];
+        if (LANE_IS(lane == 0)) {
             st[90] = t;
             int32_t *s = status + LMH_STATUS_STRIDE * inst;
             s[0] = k; s[1] = itmax; s[2] = flags; s[3] = (int32_t)(~F);
@@ -5725,6 +5757,9 @@ extern "C" int lmh_debug_build_flags(void)
 #endif
 #ifdef LMH_TEST_LOSE_PUSH
     f |= 32;
+#endif
+#ifdef LMH_LANE_RUNTIME
+    f |= 64;
 #endif
     return f;
 }
