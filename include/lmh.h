@@ -565,6 +565,60 @@ int lmh_plant_derivative(lmh_handle *h, const double *d_q, const double *d_v, co
  * followed by lmh_plant_step(b) bit for bit.  d_flags[i] (may be NULL): the flags of lmh_plant_derivative, OR-ed over the substeps. */
 int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_tau30, int n_substeps, int32_t *d_flags, void *stream);
 
+/* ---- Rigid-contact plant (build-defined): constrained forward dynamics with held soles.  The same robot under the same tau30 as the two
+ * calls above, but the held soles are kinematic constraints and the contact wrench is their multiplier: no stiffness, no penetration, no
+ * step-size bound from the ground, and a wrench lambda that can be laid directly beside the controller's planned out.f.
+ * DEFINITION, per robot, in the coordinates of M as lmh_forward_dynamics uses them.  The mode m = d_mode[i] & 3 selects the held rows S of
+ * the feet Jacobian J (rows n_R f_R n_L f_L, as in out.f): LMH_PHASE_DOUBLE rows 0..11, LMH_PHASE_RIGHT rows 0..5, LMH_PHASE_LEFT rows
+ * 6..11, LMH_PHASE_FLIGHT none.
+ *         r   = tau30 - C(q, v)                        every velocity product at the v given, as lmh_plant_derivative
+ *         a0  = M^-1 r
+ *         Y   = M^-1 J_S'        A = J_S Y             (M is not exactly symmetric -- the reference's inertia typos -- so neither is A)
+ *         g   = J_S a0 + (Jdot qdot)_S + kv (J_S vhat)       vhat: v in M's coordinates; J vhat is the sole twist
+ *         lambda_S = -A^-1 g     (Gauss-Jordan without pivoting)      lambda = 0 on the rows that are not held
+ *         a   = a0 + Y lambda_S
+ * M^-1 uses the structure of M as lmh_plant_derivative does (limb blocks, the head's, the 6 x 6 Schur complement on the base) with the
+ * twelve columns of J' riding along; the first right-hand side sees lmh_plant_derivative's operations in their order, so with
+ * LMH_PHASE_FLIGHT and every vertex out of the ground xdot is lmh_plant_derivative's bit for bit.  trajectories.rigid_contact_acceleration
+ * is the numpy statement.  xdot[0:30] is lmh_plant_derivative's qdot, xdot[30:60] is a turned back to the state's ordering and the world
+ * frame, as there.
+ * kv >= 0 [1/s] is a velocity-level stabilisation: the constraint is d/dt (J_S vhat) = -kv J_S vhat, so the held soles' twist decays as
+ * e^(-kv t) (kv = 0: it is kept).  Jdot qdot is the reference's -- the sole's spatial acceleration turned to world axes --, so this holds
+ * component by component for the angular part and in magnitude for the linear part, which also turns with the sole (d/dt v = -kv v +
+ * omega x v; about |omega_0| / kv radians in all); a sole at rest stays at rest.  There is NO position-level term: a held sole stays
+ * where its twist leaves it, so a sole that starts with a twist w_0 travels about w_0 / kv before it rests (w_0 t with kv = 0), and the
+ * integrator's own error accumulates in its position undamped (measured drift: DESIGN.md, round 33).
+ * The contact is BILATERAL.  Whether a ground could supply lambda is reported, not enforced: LMH_FLAG_CONTACT_PULL when a held foot's f_z
+ * (rows 5, 11 of lambda) is negative, LMH_FLAG_CONTACT_SLIP when hypot(f_x, f_y) > contact_mu f_z on a held foot, with the robot's own
+ * contact_mu (lmh_config's or the robot's record of lmh_set_params).  Both are informational, like LMH_FLAG_TAU_LIMIT.  LMH_FLAG_NOT_SPD (a
+ * pivot of M's blocks or of A was not positive) and LMH_FLAG_NONFINITE keep their meaning; neither stops the other robots.
+ * A constraint knows no plane and no servo: the two calls read NOTHING of lmh_set_ground and NOTHING of lmh_set_servo, and give the same
+ * bytes with and without either table.
+ * d_mode: DEVICE int32 [B]; only the low two bits of a word are read; NULL = every robot LMH_PHASE_DOUBLE.  d_tau30: NULL = a passive
+ * robot.  d_lambda (DEVICE [B][12]) and d_flags (DEVICE [B]) may be NULL.
+ * lmh_plant_step_rigid: everything else is lmh_plant_step's -- n_substeps RK4 steps of lmh_config.dt, t += dt per substep, v_prev and the
+ * pads untouched, (a + b) equals (a) followed by (b) bit for bit, the flags of the derivative OR-ed over every stage, n_substeps = 0
+ * enqueues nothing.  d_lambda receives the multiplier at the FIRST stage of the LAST substep: with n_substeps = 1 that is
+ * lmh_plant_derivative_rigid's lambda at the input state, bit for bit.  Both calls work on any handle, write nothing into it, are
+ * asynchronous and capturable from the first call, honour per-robot models and check the contact constants as lmh_plant_step does.
+ * Refused with LMH_ERR_BAD_ARG before anything is enqueued: NULL for d_q, d_v, d_xdot or d_state; kv negative or not finite;
+ * n_substeps < 0.
+ * Cost (one MI355X, 4096 standing robots x 200 control ticks, kv = 50; scripts/rigid_rate.py; other batch sizes not
+ * measured): lmh_plant_step_rigid 45.29 against lmh_plant_step's 35.85 ms (x 1.26) at 200 x 1 substeps and 449.4 against 356.5 ms (x 1.26) at
+ * 200 x 10, the same with the modes mixed over the batch (45.08 / 449.0 ms).  lmh_plant_step runs at the parent commit's rate: its kernel is
+ * the parent's, instruction for instruction.
+ * What the rigid plant says about the closed loop (scripts/rigid_stand.py, profiles/r33_rigid_stand.txt): from rest, both soles held, default
+ * gains, stand_step ; lmh_plant_step_rigid(1 substep) is down at control tick 728 (|pitch| > 0.5 rad; the height alone: 816), as the CPU loop
+ * of the oracle and the numpy statement is -- earlier than on the compliant ground (1655), with |lambda - out.f| <= 0.03 N for the first
+ * hundred ticks: the ground's compliance is not what brings the loop down.  With kp_joints raised a hundredfold and kd_joints tenfold (the
+ * damping ratio kept), whatever kp_mom between 0.03 and 30 times its default, the robot is up after 2000 ticks, without pulling on the
+ * ground or leaving the friction disc; no cell with kp_joints up to 19 times its default stands. */
+#define LMH_FLAG_CONTACT_PULL 256  /* informational: a held foot's multiplier pulls (f_z < 0) */
+#define LMH_FLAG_CONTACT_SLIP 512  /* informational: a held foot's multiplier leaves the friction disc contact_mu f_z */
+int lmh_plant_derivative_rigid(lmh_handle *h, const double *d_q, const double *d_v, const double *d_tau30, const int32_t *d_mode, double kv, double *d_xdot, double *d_lambda,
+                               int32_t *d_flags, void *stream);
+int lmh_plant_step_rigid(lmh_handle *h, double *d_state, const double *d_tau30, const int32_t *d_mode, double kv, int n_substeps, double *d_lambda, int32_t *d_flags, void *stream);
+
 /* ---- Ground planes under the soles (build-defined; lmh_set_ground, a table of the handle like the actuator records): how steep a slope, or
  * how high a ledge under one foot, the controller survives -- per robot, so that a sweep is one launch.
  * records: HOST [n_sets][LMH_GROUND_STRIDE], n_sets = 1 (one record for every robot) or n_instances; NULL or n_sets = 0 clears the table.

@@ -83,6 +83,8 @@ FLAG_NOT_SPD = 8
 FLAG_QP_FP64_ROUTE = 16
 FLAG_BOX_EMPTY = 64           # lmh_mpc_box_*: a sample of the window has lo > hi or a NaN bound
 FLAG_TAU_LIMIT = 128          # lmh_rollout_zoh_io, informational: a joint's torque was cut to its limit on some tick of the launch
+FLAG_CONTACT_PULL = 256       # lmh_plant_*_rigid, informational: a held foot's multiplier pulls (f_z < 0)
+FLAG_CONTACT_SLIP = 512       # lmh_plant_*_rigid, informational: a held foot's multiplier leaves the friction disc contact_mu f_z
 FLAG_UNFINISHED = 32          # lmh_rollout: the robot did not get all its ticks (a wait of the kernel's work queue ran out)
 ERR_UNFINISHED = -5
 
@@ -193,6 +195,8 @@ PROTOTYPES = {
     "lmh_plant_derivative": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lmh_plant_step": (_ip, [_vp, _vp, _vp, _ip, _vp, _vp]),
     "lmh_plant_step_servo": (_ip, [_vp, _vp, _vp, _vp, _ip, _vp, _vp]),
+    "lmh_plant_derivative_rigid": (_ip, [_vp, _vp, _vp, _vp, _vp, _dp, _vp, _vp, _vp, _vp]),
+    "lmh_plant_step_rigid": (_ip, [_vp, _vp, _vp, _vp, _dp, _ip, _vp, _vp, _vp]),
     "lmh_rollout_zoh": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _vp]),
     "lmh_rollout_zoh_ref": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _vp]),
     "lmh_rollout_zoh_ex": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), _ip, _ip, _vp]),

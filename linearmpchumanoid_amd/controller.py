@@ -639,6 +639,40 @@ class BatchedController:
         check(capi.lib().lmh_plant_step_servo(self._h, _dev_ptr(state), _dev_ptr(tau), _dev_ptr(setpoint), int(n_substeps), _dev_ptr(flags), self._stream()))
         return state, flags
 
+    # -- rigid-contact plant (include/lmh.h, lmh_plant_derivative_rigid): the held soles as constraints, the contact wrench their multiplier
+    def _rigid_args(self, mode, kv):
+        if mode is not None and (not isinstance(mode, torch.Tensor) or mode.dtype != torch.int32 or tuple(mode.shape) != (self.B,) or mode.device != self.device):
+            raise ValueError(f"mode must be a [{self.B}] int32 tensor on {self.device}")
+        return (None if mode is None else mode.contiguous()), float(kv)
+
+    def plant_derivative_rigid(self, q, v, tau=None, mode=None, kv=0.0):
+        """xdot of the rigid-contact plant for q, v [B,30] under tau [B,30] (None: passive): the soles that mode holds (int32 [B] of
+        PHASE_DOUBLE / PHASE_RIGHT / PHASE_LEFT / PHASE_FLIGHT, low two bits; None: both soles of every robot) are kinematic constraints
+        with the velocity-level stabilisation kv >= 0 [1/s] -> (xdot [B,60], lam [B,12] the contact wrench as the constraint's multiplier,
+        laid out like out.f and exactly 0 on a free foot, flags [B] int32: FLAG_CONTACT_PULL / FLAG_CONTACT_SLIP (informational), FLAG_NOT_SPD,
+        FLAG_NONFINITE).  trajectories.rigid_contact_acceleration states the acceleration; the call reads no ground and no servo table."""
+        q, v, tau = self._batch("q", q, 30), self._batch("v", v, 30), self._batch("tau", tau, 30, optional=True)
+        mode, kv = self._rigid_args(mode, kv)
+        xdot = torch.empty((self.B, 60), dtype=torch.float64, device=self.device)
+        lam = torch.empty((self.B, 12), dtype=torch.float64, device=self.device)
+        flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+        check(capi.lib().lmh_plant_derivative_rigid(self._h, _dev_ptr(q), _dev_ptr(v), _dev_ptr(tau), _dev_ptr(mode), kv, _dev_ptr(xdot), _dev_ptr(lam),
+                                                    _dev_ptr(flags), self._stream()))
+        return xdot, lam, flags
+
+    def plant_step_rigid(self, state, tau=None, mode=None, kv=0.0, n_substeps=1):
+        """n_substeps RK4 steps of cfg.dt of the rigid-contact plant on (q, v) of the state records [B,96], in place, with tau [B,30] held
+        (None: passive); t advances, v_prev stays.  mode and kv as in plant_derivative_rigid.  -> (state, lam [B,12] the multiplier at the
+        first stage of the last substep -- zeros when n_substeps is 0 --, flags [B] int32 OR-ed over every stage)."""
+        tau, state = self._batch("tau", tau, 30, optional=True), self._batch("state", state, capi.STATE_STRIDE, in_place=True)
+        mode, kv = self._rigid_args(mode, kv)
+        if int(n_substeps) != n_substeps:
+            raise ValueError("n_substeps must be a whole number")
+        lam = torch.zeros((self.B, 12), dtype=torch.float64, device=self.device)
+        flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+        check(capi.lib().lmh_plant_step_rigid(self._h, _dev_ptr(state), _dev_ptr(tau), _dev_ptr(mode), kv, int(n_substeps), _dev_ptr(lam), _dev_ptr(flags), self._stream()))
+        return state, lam, flags
+
     def rollout_zoh(self, state, n_ticks, n_substeps, base_wrench=None, log=False, out=None, status=None, ref=None):
         """lmh_rollout_zoh: n_ticks rounds of { stand_step ; plant_step([base_wrench | out.tau], n_substeps) } in one launch, bit for bit
         what that loop leaves; state [B,96] is updated in place.  The control period is n_substeps * cfg.dt.  base_wrench [B,6]: an external

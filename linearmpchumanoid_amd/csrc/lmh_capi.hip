@@ -1151,12 +1151,15 @@ static int plant_constants_ok(const lmh_handle *h)
 
 // The caller has found the handle ready and checked its required pointers, which come before the constants in the order of the refusals.
 static int plant_body(lmh_handle *h, int mode, const double *d_q, const double *d_v, const double *d_tau30, double *d_state, double *d_xdot, double *d_contact, int32_t *d_flags,
-                      int n_substeps, void *stream, const double *d_setpoint = nullptr)
+                      int n_substeps, void *stream, const double *d_setpoint = nullptr, const int32_t *d_hold = nullptr, double kv = 0.0, double *d_lambda = nullptr)
 {
     const int rc = plant_constants_ok(h); if (rc) return rc;
     // d_setpoint (lmh_plant_step_servo): the handle's servo table rides along; without one the launcher never reads it
-    return launch(h, nullptr, [&] { lmh_launch_plant(&h->P, mode, d_q, d_v, d_tau30, d_state, d_xdot, d_contact, d_flags, n_substeps, h->d_ground.get(), h->ground_stride(),
-                                                     d_setpoint ? h->d_servo.get() : nullptr, h->servo_stride(), d_setpoint, (hipStream_t)stream); });
+    // d_hold, kv, d_lambda (PM_RIGID_*): the rigid plant's; it reads neither table, so neither rides along
+    const bool rigid = mode == PM_RIGID_DERIV || mode == PM_RIGID_STEP;
+    return launch(h, nullptr, [&] { lmh_launch_plant(&h->P, mode, d_q, d_v, d_tau30, d_state, d_xdot, d_contact, d_flags, n_substeps, rigid ? nullptr : h->d_ground.get(),
+                                                     rigid ? 0 : h->ground_stride(), d_setpoint ? h->d_servo.get() : nullptr, h->servo_stride(), d_setpoint, d_hold, kv, d_lambda,
+                                                     (hipStream_t)stream); });
 }
 
 extern "C" int lmh_contact_wrench(lmh_handle *h, const double *d_q, const double *d_v, double *d_contact, void *stream)
@@ -1191,6 +1194,27 @@ extern "C" int lmh_plant_step_servo(lmh_handle *h, double *d_state, const double
     if (n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step_servo: n_substeps must be >= 0");
     if (n_substeps == 0) return plant_constants_ok(h);               // nothing to enqueue
     return plant_body(h, PM_STEP, nullptr, nullptr, d_tau30, d_state, nullptr, nullptr, d_flags, n_substeps, stream, d_setpoint);
+}
+
+// The rigid-contact plant (include/lmh.h): the held soles as constraints, the contact wrench their multiplier.  lmh_plant_step's rule set, with
+// kv between the pointers and the count.
+extern "C" int lmh_plant_derivative_rigid(lmh_handle *h, const double *d_q, const double *d_v, const double *d_tau30, const int32_t *d_mode, double kv, double *d_xdot, double *d_lambda,
+                                          int32_t *d_flags, void *stream)
+{
+    int rc = ready(h); if (rc) return rc;
+    if (!d_q || !d_v || !d_xdot) return fail(LMH_ERR_BAD_ARG, "lmh_plant_derivative_rigid: null device pointer");
+    if (!(kv >= 0.0 && kv <= 1.7976931348623157e308)) return fail(LMH_ERR_BAD_ARG, "lmh_plant_derivative_rigid: kv must be finite and >= 0");
+    return plant_body(h, PM_RIGID_DERIV, d_q, d_v, d_tau30, nullptr, d_xdot, nullptr, d_flags, 0, stream, nullptr, d_mode, kv, d_lambda);
+}
+
+extern "C" int lmh_plant_step_rigid(lmh_handle *h, double *d_state, const double *d_tau30, const int32_t *d_mode, double kv, int n_substeps, double *d_lambda, int32_t *d_flags, void *stream)
+{
+    int rc = ready(h); if (rc) return rc;
+    if (!d_state) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step_rigid: null device pointer");
+    if (!(kv >= 0.0 && kv <= 1.7976931348623157e308)) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step_rigid: kv must be finite and >= 0");
+    if (n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step_rigid: n_substeps must be >= 0");
+    if (n_substeps == 0) return plant_constants_ok(h);               // nothing to enqueue
+    return plant_body(h, PM_RIGID_STEP, nullptr, nullptr, d_tau30, d_state, nullptr, nullptr, d_flags, n_substeps, stream, nullptr, d_mode, kv, d_lambda);
 }
 
 // ---------------------------------------------------------------------------- zero-order-hold closed loop

@@ -5023,6 +5023,266 @@ __global__ void __launch_bounds__(64) lmh_plant_servo_kernel(LmhDevParams P_arg,
     if (lane < 60) st[lane] = x; else if (lane == 60) st[90] = t;
     if (lane == 0 && flags_out) flags_out[inst] = flags;
 }
+// ============================================================================ rigid-contact plant: constrained forward dynamics with held soles
+// lmh_plant_derivative_rigid / lmh_plant_step_rigid (include/lmh.h): the held soles are kinematic constraints and the contact wrench is their
+// multiplier.  One wave per robot, the single-wave schedule and statements of lmh_plant_kernel; one derivative is
+//     kinematics -> X images -> Newton-Euler at v -> CRBA -> Jacobian -> sole twists (P_VFOOT) -> Jdot qdot of the soles (P_JPQP) ->
+//     r = tau30 - C -> [a0 | Y] = M^-1 [r | J'] (plant_minv_rigid) -> [A | g] = J [Y | a0] + (Jpqp + kv J vhat) -> lambda_S = -A_SS^-1 g_S
+//     (gj_solve_regs<12, 1> under the mode's live mask) -> a = a0 + Y lambda -> world frame (phase_outputs_qdd)
+// and reads no ground table, servo table, reference plan, MPC row, QP or clock.  A plant kernel runs no QP, so Y and [A | g] lie in the QP's
+// scratch: behind the plant's own PL_* block, in front of Q_TRASH (plant_minv's dump), over tree-phase arrays that are dead once the Jacobian
+// stands (A_FG, A_F0, A_XF).
+enum { RG_Y = S0 + 768,     // 30 x 12 : M^-1 J' (columns of rows that are not held are formed and not read)
+       RG_BX = S0 + 1128,   // 12 x 6  : H_leg^-1 J_leg' of each foot's own leg (every other entry of H^-1 J_joint' is zero)
+       RG_SX = S0 + 1200,   // 6 x 12  : the base Schur complement's extra right-hand sides J_base' - F2 H^-1 J_joint'
+       RG_A = S0 + 1272,    // 12 x 13 : [A | g]
+       RG_LAM = S0 + 1428,  // 12 : lambda
+       RG_END = S0 + 1440 };
+static_assert(RG_Y >= PL_ZERO + 32 && RG_Y >= A_JL + 144, "behind the plant's PL_* block and the sole-axes Jacobian");
+static_assert(RG_BX == RG_Y + 30 * 12 && RG_SX == RG_BX + 12 * 6 && RG_A == RG_SX + 6 * 12 && RG_LAM == RG_A + 12 * 13 && RG_END == RG_LAM + 12, "Y | BX | SX | [A | g] | lambda");
+static_assert(RG_END <= Q_TRASH && Q_TRASH + 64 <= LDS_DOUBLES, "in front of the dump of the lanes outside a tile");
+static_assert(RG_Y >= P_END && P_HL < S0 && P_MTOP < S0 && P_JC < S0 && P_C < S0 && P_VFOOT < S0 && P_JPQP < S0, "the terms the solve reads lie below the scratch");
+
+// plant_minv's sibling: M^-1 [PL_R | J'] by the same structure, the twelve columns of J' riding along.  J has base and leg columns only, so
+// of H^-1 J_joint' only each foot's own leg block is not zero: DPP rows 0, 1 (RL, LL) carry six extra right-hand sides, the arm rows and
+// the head see zeros and form nothing.  The first right-hand side goes through plant_minv's operations in plant_minv's order (every
+// right-hand side of a register elimination is updated from its own entries only), so PL_R's column keeps plant_minv's bits.
+// lane < 30 hands entry `lane` of M^-1 PL_R to sink(da); Y = M^-1 J' -> RG_Y.  Returns LMH_FLAG_NOT_SPD as plant_minv<true> does.
+template <class SINK>
+__device__ __forceinline__ int plant_minv_rigid(double *L, int lane, SINK sink)
+{
+    int notspd = 0;
+    {   // limb blocks: DPP row dr = limb (RL, LL, RA, LA), lane l16 < 6 = joint of the limb (arms: a unit row pads 5 -> 6)
+        const int l16 = lane & 15;                                 // (DPP row dr = lane >> 4)
+        const bool legrow = LANE_IS(lane < 32);
+        const int js = LANE_IS(lane < 16) ? 0 : legrow ? 6 : LANE_IS(lane < 48) ? 12 : 17;
+        const bool real = LANE_IS((lane & 15) < ((lane < 32) ? 6 : 5));      // l16 < nl, nl = 6 joints of a leg | 5 of an arm
+        const bool legj = LANE_IS(lane < 32 && (lane & 15) < 6);
+        const int ja = js + (real ? l16 : 0);
+        double a[6], b[13];
+#pragma unroll
+        for (int c = 0; c < 6; c++) { const double hv = L[P_HL + 6 * ja + ((c < 5) ? c : (legrow ? 5 : 0))]; a[c] = (real && (c < 5 || legrow)) ? hv : ((l16 == c && l16 < 6) ? 1.0 : 0.0); }
+        { const double rv = L[PL_R + 6 + ja]; b[0] = real ? rv : 0.0; }
+#pragma unroll
+        for (int m = 0; m < 6; m++) { const double fv = L[P_MTOP + 30 * m + 6 + ja]; b[1 + m] = real ? fv : 0.0; }
+#pragma unroll
+        for (int m = 0; m < 6; m++) { const double jv = L[P_JC + 72 * ((lane >> 4) & 1) + 12 * m + 6 + (real ? l16 : 0)]; b[7 + m] = legj ? jv : 0.0; }   // J[foot dr][row m][leg joint l16]
+        int bad = 0;
+        double myinv = 0.0;
+        gj16_step<0>(a, b, 0x3Fu, l16, true, 0.0, bad, myinv);     // (l16 = lane & 15 of the caller's LANE, as gj16_step's pivot masks assume)
+#pragma unroll
+        for (int c = 0; c < 7; c++) L[real ? PL_B + 7 * ja + c : Q_TRASH + lane] = b[c] * myinv;
+#pragma unroll
+        for (int m = 0; m < 6; m++) L[legj ? RG_BX + 6 * ja + m : Q_TRASH + lane] = b[7 + m] * myinv;
+        notspd |= bad;
+    }
+    if (LANE_IS(lane < 14)) {                                      // head: 2 x 2 in closed form (its rows of J' are zero)
+        const int i = lane / 7, c = lane % 7;
+        const double h00 = L[P_HL + 6 * 22], h01 = L[P_HL + 6 * 22 + 1], h10 = L[P_HL + 6 * 23], h11 = L[P_HL + 6 * 23 + 1];
+        const bool c0 = LANE_IS(lane % 7 == 0);
+        const double r0 = c0 ? L[PL_R + 6 + 22] : L[P_MTOP + 30 * (c - 1) + 6 + 22], r1 = c0 ? L[PL_R + 6 + 23] : L[P_MTOP + 30 * (c - 1) + 6 + 23];
+        const double det = h00 * h11 - h01 * h10;
+        L[PL_B + 7 * (22 + i) + c] = LANE_IS(lane < 7) ? (h11 * r0 - h01 * r1) / det : (h00 * r1 - h10 * r0) / det;
+        notspd |= (int)!(h00 > 0.0 && det > 0.0);
+    }
+    WSYNC();
+    {   // base: S_b = Ic0 - F2 B_M, rhs = r_b - F2 B_r   (one matrix-core tile, K = 24)
+        const int tr = lane & 15, tq = lane >> 4;
+        const double *zero = L + PL_ZERO;
+        const v4d fb = mfma_ptr<6, 4, 28>(LANE_IS((lane & 15) < 6) ? L + P_MTOP + 30 * tr + 6 + tq : zero, LANE_IS((lane & 15) < 7) ? L + PL_B + 7 * tq + tr : zero);
+#pragma unroll
+        for (int g = 0; g < 2; g++) {
+            const int m = tq + 4 * g;
+            const bool ok = (m < 6) && (tr < 7);
+            const double base = L[!ok ? PL_ZERO : (tr == 0) ? PL_R + m : P_MTOP + 30 * m + (tr - 1)];
+            L[ok ? PL_SB + 7 * m + tr : Q_TRASH + lane] = base - fb[g];
+        }
+    }
+    // the twelve extra right-hand sides of the base system: J_base'[m][k] - F2[m][leg of foot k / 6] BX[.][k % 6]
+#pragma unroll
+    for (int it = 0; it < 2; it++) {
+        const int e = lane + 64 * it, ee = (e < 72) ? e : 0, m = ee / 12, k = ee % 12, ft = k / 6, rr = k % 6;
+        const double *F2 = L + P_MTOP + 30 * m + 6 + 6 * ft, *BX = L + RG_BX + 36 * ft + rr;
+        double s = L[P_JC + 72 * ft + 12 * rr + m];
+#pragma unroll
+        for (int j = 0; j < 6; j++) s -= F2[j] * BX[6 * j];
+        if (e < 72) L[RG_SX + ee] = s;
+    }
+    WSYNC();
+    {   // DPP row dr solves the first right-hand side (a copy per row, as plant_minv) and three of the twelve extra ones
+        double a[6], b[4];
+        const int l16 = lane & 15, lr = LANE_IS((lane & 15) < 6) ? l16 : 0, dr = lane >> 4;
+#pragma unroll
+        for (int c = 0; c < 6; c++) a[c] = L[PL_SB + 7 * lr + 1 + c];
+        b[0] = L[PL_SB + 7 * lr];
+#pragma unroll
+        for (int j = 0; j < 3; j++) b[1 + j] = L[RG_SX + 12 * lr + 3 * dr + j];
+        const int bad6 = gj_solve_regs<6, 4>(a, b, 0x3Fu);
+        notspd |= bad6;
+        if (LANE_IS(lane < 6)) L[PL_DAB + lane] = b[0];
+#pragma unroll
+        for (int j = 0; j < 3; j++) L[LANE_IS((lane & 15) < 6) ? RG_Y + 12 * l16 + 3 * dr + j : Q_TRASH + lane] = b[1 + j];       // rows 0..5 of Y
+    }
+    WSYNC();
+    if (LANE_IS(lane < 30)) {
+        double da;
+        if (LANE_IS(lane < 6)) da = L[PL_DAB + lane];
+        else {
+            const double *B = L + PL_B + 7 * (lane - 6);
+            da = B[0];
+#pragma unroll
+            for (int n = 0; n < 6; n++) da -= B[1 + n] * L[PL_DAB + n];
+        }
+        sink(da);
+    }
+    // rows 6..29 of Y: H^-1 J_joint' - B_M Y_base
+#pragma unroll 1
+    for (int e = lane; e < 288; e += 64) {
+        const int i = e / 12, k = e % 12;
+        const bool own = (i < 12) && (i / 6 == k / 6);
+        const double bx = L[own ? RG_BX + 6 * i + k % 6 : (int)PL_ZERO];
+        const double *B = L + PL_B + 7 * i;
+        double y = own ? bx : 0.0;
+#pragma unroll
+        for (int n = 0; n < 6; n++) y -= B[1 + n] * L[RG_Y + 12 * n + k];
+        L[RG_Y + 12 * (6 + i) + k] = y;
+    }
+    WSYNC();
+    return (__ballot(notspd != 0) != 0ull) ? LMH_FLAG_NOT_SPD : 0;
+}
+// the held rows of the feet Jacobian as a mask (rows n_R f_R n_L f_L): only the low two bits of a mode word are read
+__device__ __forceinline__ unsigned rigid_live(int mode)
+{
+    const int m = mode & 3;
+    return (m == LMH_PHASE_DOUBLE) ? 0xFFFu : (m == LMH_PHASE_RIGHT) ? 0x03Fu : (m == LMH_PHASE_LEFT) ? 0xFC0u : 0u;
+}
+// one derivative of the rigid plant for the state in L[P_Q], L[P_V]: accelerations -> L[P_QDD] (state ordering, world frame), the multiplier
+// -> L[RG_LAM] (zeros on the rows that are not held).  `live`: rigid_live of the robot's mode, wave-uniform.  Returns LMH_FLAG_NOT_SPD |
+// LMH_FLAG_CONTACT_PULL | LMH_FLAG_CONTACT_SLIP, wave-uniform.
+__device__ __forceinline__ int plant_derivative_rigid(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau, unsigned live, double kv)
+{
+    if (lane < 30) L[P_VP + lane] = L[P_V + lane];                 // one velocity for every term
+    WSYNC();
+    phase_fk<double>(L, P.lcoef);
+    phase_com_x<1, double>(L, 0);
+    phase_newton_euler<double>(L);
+    phase_crba<double>(L, ib_unpack(ibp));
+    phase_jacobian<double>(L);
+    refs_vfoot_pdjoints(L, P);                                     // sole twists J vhat -> P_VFOOT (its PD law on lanes 32..61 rides along unread)
+    WSYNC();
+    refs_jpqp(L);                                                  // Jdot qdot of the soles -> P_JPQP
+    if (lane < 30) L[PL_R + lane] = tau - L[P_C + lane];
+    else if (lane >= 32) L[PL_ZERO + lane - 32] = 0.0;
+    WSYNC();
+    int flags = plant_minv_rigid(L, lane, [&](double a) { L[PL_AP + lane] = a; });
+    // A = J Y (12 x 12; base and own-leg columns) and g = J a0 + Jpqp + kv J vhat
+#pragma unroll
+    for (int it = 0; it < 3; it++) {
+        const int e = lane + 64 * it, ee = (e < 144) ? e : 0, r = ee / 12, c = ee % 12, ft = r / 6;
+        const double *Jr = L + P_JC + 72 * ft + 12 * (r % 6), *Yb = L + RG_Y + c, *Yl = L + RG_Y + 12 * (6 + 6 * ft) + c;
+        double s = 0.0;
+#pragma unroll
+        for (int m = 0; m < 6; m++) s += Jr[m] * Yb[12 * m];
+#pragma unroll
+        for (int j = 0; j < 6; j++) s += Jr[6 + j] * Yl[12 * j];
+        if (e < 144) L[RG_A + 13 * r + c] = s;
+    }
+    if (lane >= 52) {
+        const int r = lane - 52, ft = r / 6;
+        const double *Jr = L + P_JC + 72 * ft + 12 * (r % 6), *ab = L + PL_AP, *al = L + PL_AP + 6 + 6 * ft;
+        double s = 0.0;
+#pragma unroll
+        for (int m = 0; m < 6; m++) s += Jr[m] * ab[m];
+#pragma unroll
+        for (int j = 0; j < 6; j++) s += Jr[6 + j] * al[j];
+        L[RG_A + 13 * r + 12] = (s + L[P_JPQP + r]) + kv * L[P_VFOOT + r];
+    }
+    WSYNC();
+    {
+        double a[12], b[1];
+        const int l16 = lane & 15, lr = (l16 < 12) ? l16 : 0;      // (a copy of the system per DPP row)
+#pragma unroll
+        for (int c = 0; c < 12; c++) a[c] = L[RG_A + 13 * lr + c];
+        b[0] = -L[RG_A + 13 * lr + 12];
+        if (live != 0u) { if (gj_solve_regs<12, 1>(a, b, live)) flags |= LMH_FLAG_NOT_SPD; }      // (wave-uniform: FLIGHT solves nothing)
+        if (lane < 12) L[RG_LAM + lane] = ((live >> lane) & 1u) ? b[0] : 0.0;
+    }
+    WSYNC();
+    if (lane < 30) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 12; k++) s += L[RG_Y + 12 * lane + k] * L[RG_LAM + k];
+        const double a0 = L[PL_AP + lane];
+        L[PL_AP + lane] = (live != 0u) ? a0 + s : a0;              // (FLIGHT: a0 itself, whatever Y holds)
+    }
+    {   // what the ground would have to supply, reported and not enforced: a held foot pulls | leaves its friction disc
+        const double mu = P.contact_mu;
+#pragma unroll
+        for (int ft = 0; ft < 2; ft++) {
+            const double fx = L[RG_LAM + 6 * ft + 3], fy = L[RG_LAM + 6 * ft + 4], fz = L[RG_LAM + 6 * ft + 5];
+            const bool held = ((live >> (6 * ft)) & 1u) != 0u;
+            if (held && fz < 0.0) flags |= LMH_FLAG_CONTACT_PULL;
+            if (held && sqrt(fx * fx + fy * fy) > mu * fz) flags |= LMH_FLAG_CONTACT_SLIP;
+        }
+        flags = __builtin_amdgcn_readfirstlane(flags);             // (every lane read the same words)
+    }
+    WSYNC();
+    phase_outputs_qdd(L, PL_AP);
+    return flags;
+}
+// lmh_plant_kernel's PM_DERIV and PM_STEP with the rigid derivative; `lambda` (may be NULL): the multiplier of the derivative call, of the
+// first stage of the last substep for the step
+template <int MODE>
+__global__ void __launch_bounds__(64) lmh_plant_rigid_kernel(LmhDevParams P_arg, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *lambda,
+                                                             int32_t *flags_out, int n_substeps, const int32_t *mode, double kv)
+{
+    static_assert(MODE == PM_DERIV || MODE == PM_STEP, "derivative | RK4 step");
+    LmhCParams &P0 = LMH_KERNARG_PARAMS();
+    __shared__ double L[LDS_DOUBLES];
+    const int inst = blockIdx.x;
+    if (inst >= P0.n_instances) return;
+    LmhCParams &P = *params_of_robot(&P0, inst);
+    const int lane = LANE;
+    SET_GDBG(nullptr);
+    load_common(L, P, inst);
+    const IbPack ibp = ib_pack();
+    const double tau = (tau30 && lane < 30) ? tau30[30 * (size_t)inst + lane] : 0.0;
+    const unsigned live = (unsigned)__builtin_amdgcn_readfirstlane((int)rigid_live(mode ? mode[inst] : (int)LMH_PHASE_DOUBLE));      // (one word per robot: wave-uniform)
+    int flags = 0;
+    if constexpr (MODE == PM_DERIV) {
+        load_qv(L, q, v, inst, lane, false);                       // (plant_derivative_rigid sets P_VP itself)
+        WSYNC();
+        flags |= plant_derivative_rigid(L, P, ibp, lane, tau, live, kv);
+        double x = 0.0, xd = 0.0, xs = 0.0;
+        rk4_stage<0>(L, 0, lane, 0.0, P_SC + 52, x, xd, xs);       // the first stage leaves xdot itself in its sum: fma(1, xdot, 0 * 0)
+        if (__ballot(lane < 60 && !(fabs(xd) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
+        if (lane < 60) xdot[60 * (size_t)inst + lane] = xd;
+        if (lambda && lane < 12) lambda[12 * (size_t)inst + lane] = L[RG_LAM + lane];
+    } else {
+        double *st = state + (size_t)LMH_STATE_STRIDE * inst;
+        double x = (lane < 60) ? st[lane] : 0.0, t = st[90], lam = 0.0;
+        const double dt = P.dt;
+#pragma unroll 1
+        for (int sub = 0; sub < n_substeps; sub++) {               // plant_hold's loop around the rigid derivative
+            double ksum = 0.0, xs = x;
+#pragma unroll 1
+            for (int stage = 0; stage < 4; stage++) {
+                WSYNC();
+                if (lane < 60) L[P_Q + lane] = xs;                 // q | v are one run
+                WSYNC();
+                flags |= plant_derivative_rigid(L, P, ibp, lane, tau, live, kv);
+                if (stage == 0) lam = L[RG_LAM + ((lane < 12) ? lane : 0)];
+                rk4_stage<0>(L, stage, lane, dt, P_SC + 52, x, ksum, xs);
+            }
+            if (__ballot(lane < 60 && !(fabs(x) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
+        }
+#pragma unroll 1
+        for (int sub = 0; sub < n_substeps; sub++) t += dt;        // Clock::step, Clock.hpp:11
+        if (lane < 60) st[lane] = x; else if (lane == 60) st[90] = t;
+        if (lambda && lane < 12) lambda[12 * (size_t)inst + lane] = lam;
+    }
+    if (lane == 0 && flags_out) flags_out[inst] = flags;
+}
 #ifndef LMH_ROLLOUT_ONLY
 extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *q, const double *v, const double *x, const double *w, double *res, int32_t *flags, hipStream_t s)
 {
@@ -5032,9 +5292,15 @@ extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *
     else hipLaunchKernelGGL(lmh_terms_kernel<TM_FWDDYN>, grid, block, 0, s, *P, q, v, x, w, res, flags);
 }
 extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact, int32_t *flags,
-                                 int n_substeps, const double *ground, size_t ground_stride, const double *servo, size_t servo_stride, const double *setpoint, hipStream_t s)
+                                 int n_substeps, const double *ground, size_t ground_stride, const double *servo, size_t servo_stride, const double *setpoint, const int32_t *hold, double kv,
+                                 double *lambda, hipStream_t s)
 {
     const dim3 grid(P->n_instances), block(64);
+    if (mode == PM_RIGID_DERIV || mode == PM_RIGID_STEP) {         // lmh_plant_derivative_rigid / lmh_plant_step_rigid: no ground, no servo, whatever the handle carries
+        if (mode == PM_RIGID_DERIV) hipLaunchKernelGGL(lmh_plant_rigid_kernel<PM_DERIV>, grid, block, 0, s, *P, q, v, tau30, state, xdot, lambda, flags, n_substeps, hold, kv);
+        else hipLaunchKernelGGL(lmh_plant_rigid_kernel<PM_STEP>, grid, block, 0, s, *P, q, v, tau30, state, xdot, lambda, flags, n_substeps, hold, kv);
+        return;
+    }
     if (setpoint) {                                                // lmh_plant_step_servo (PM_STEP only; servo NULL: zero gains); without one the kernels of before
         if (ground) hipLaunchKernelGGL(lmh_plant_servo_kernel<true>, grid, block, 0, s, *P, tau30, state, flags, n_substeps, servo, servo_stride, setpoint, ground, ground_stride);
         else hipLaunchKernelGGL(lmh_plant_servo_kernel<false>, grid, block, 0, s, *P, tau30, state, flags, n_substeps, servo, servo_stride, setpoint, ground, ground_stride);

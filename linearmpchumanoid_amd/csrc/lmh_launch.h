@@ -6,7 +6,8 @@
 #include "lmh_device.h"
 
 enum { TM_TERMS, TM_INVDYN, TM_FWDDYN };    // lmh_launch_terms: the dense terms record | inverse dynamics | forward dynamics (lmh_terms_kernel)
-enum { PM_CONTACT, PM_DERIV, PM_STEP };     // lmh_launch_plant: contact wrench | derivative | RK4 step (lmh_plant_kernel)
+enum { PM_CONTACT, PM_DERIV, PM_STEP,       // lmh_launch_plant: contact wrench | derivative | RK4 step (lmh_plant_kernel)
+       PM_RIGID_DERIV, PM_RIGID_STEP };     //                   derivative | RK4 step of the rigid-contact plant (lmh_plant_rigid_kernel)
 
 extern "C" void lmh_launch_model(const double *raw, double *model, int n_models, const double *lcoef, hipStream_t s);
 extern "C" void lmh_launch_params_expand(const LmhDevParams *P, const double *d_rec, const double *d_gcol_tab, LmhDevParams *d_blocks, int n, hipStream_t s);
@@ -45,8 +46,12 @@ extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *
 // ground, ground_stride: as in lmh_launch_rollout_zoh; NULL = lmh_plant_kernel exactly as it is, otherwise lmh_plant_ground_kernel
 // setpoint (lmh_plant_step_servo; PM_STEP only): NULL = the kernels above, exactly; otherwise [n_instances][LMH_SETPOINT_STRIDE] and the launch is
 // lmh_plant_servo_kernel's, with servo + servo_stride * robot that robot's LMH_SERVO_STRIDE gains (servo NULL: zero gains; stride 0: one shared record)
+// PM_RIGID_DERIV, PM_RIGID_STEP (lmh_plant_derivative_rigid, lmh_plant_step_rigid): lmh_plant_rigid_kernel with hold ([n_instances] support modes, NULL = both
+// soles held), kv and lambda ([n_instances][12], may be NULL); ground, servo and setpoint are not read.  The other modes read none of the three.  The same
+// launcher, not a new symbol, for the reason given at lmh_launch_rollout_zoh.
 extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact, int32_t *flags,
-                                 int n_substeps, const double *ground, size_t ground_stride, const double *servo, size_t servo_stride, const double *setpoint, hipStream_t s);
+                                 int n_substeps, const double *ground, size_t ground_stride, const double *servo, size_t servo_stride, const double *setpoint, const int32_t *hold, double kv,
+                                 double *lambda, hipStream_t s);
 // The three MPC launchers carry the box-constrained variants (lmh_mpc_box_*): box NULL = the unconstrained kernels exactly as they are (alpha, beta and
 // box_stride are then not read by step and rollout); otherwise box + box_stride * robot is that robot's [4][n_samples] bounds (box_stride 0: one shared set)
 // and `mpc` / `traj` / `record` take the constrained call's records (record: LMH_MPC_BOX_STRIDE words per robot instead of LMH_MPC_PREVIEW_STRIDE).

@@ -8,7 +8,7 @@ definition on top of the reference's conventions (SupportFoot -> ZMP y of -/+0.0
 """
 import numpy as np
 
-from .capi import ACT_MAX_DELAY, ACT_MEM_STRIDE, ACT_OFF_ALPHA, ACT_OFF_DELAY, ACT_OFF_TAU_MAX, ACT_STRIDE, FLAG_BOX_EMPTY, FLAG_NONFINITE, FLAG_NOT_SPD, FLAG_QP_MAXITER, FLAG_ZMP_RANGE, GROUND_OFF_H_L, GROUND_OFF_H_R, GROUND_OFF_N_L, GROUND_OFF_N_R, GROUND_STRIDE, IK_TARGET_STRIDE, LIP_STRIDE, MAX_PUSHES, MPC_BOX_MAX_ROUNDS, MPC_STRIDE, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE, SERVO_OFF_KD, SERVO_OFF_KP, SERVO_STRIDE, SETPOINT_STRIDE
+from .capi import FLAG_CONTACT_PULL, FLAG_CONTACT_SLIP, ACT_MAX_DELAY, ACT_MEM_STRIDE, ACT_OFF_ALPHA, ACT_OFF_DELAY, ACT_OFF_TAU_MAX, ACT_STRIDE, FLAG_BOX_EMPTY, FLAG_NONFINITE, FLAG_NOT_SPD, FLAG_QP_MAXITER, FLAG_ZMP_RANGE, GROUND_OFF_H_L, GROUND_OFF_H_R, GROUND_OFF_N_L, GROUND_OFF_N_R, GROUND_STRIDE, IK_TARGET_STRIDE, LIP_STRIDE, MAX_PUSHES, MPC_BOX_MAX_ROUNDS, MPC_STRIDE, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE, SERVO_OFF_KD, SERVO_OFF_KP, SERVO_STRIDE, SETPOINT_STRIDE
 
 
 def stance_zmp(simulation_time, time_step, support_foot=2):
@@ -753,7 +753,73 @@ def ground_contact(pos, vel, planes, k, d, dt, mu):
     return f, regimes
 
 
+RIGID_ROWS = {PHASE_DOUBLE: tuple(range(12)), PHASE_RIGHT: tuple(range(6)), PHASE_LEFT: tuple(range(6, 12)), PHASE_FLIGHT: ()}
+
+
+def gauss_jordan_unpivoted(A, b):
+    """x with A x = b by Gauss-Jordan elimination without pivoting, pivot after pivot in order, as the register solves of the kernels run
+    it -> (x, pivots): pivots[j] is the j-th pivot as the elimination met it."""
+    A, b = np.array(A, dtype=np.float64), np.array(b, dtype=np.float64)
+    n = len(b)
+    piv = np.zeros(n)
+    for j in range(n):
+        piv[j] = A[j, j]
+        for i in range(n):
+            if i != j:
+                f = A[i, j] / A[j, j]
+                A[i, j + 1:] -= f * A[j, j + 1:]
+                b[i] -= f * b[j]
+                A[i, j] = 0.0
+    return b / np.diag(A), piv
+
+
+def rigid_contact_acceleration(M, C, J, Jpqp, vhat, tau30, mode, kv, contact_mu=0.7, info=None):
+    """The numpy statement of the rigid-contact plant (include/lmh.h, lmh_plant_derivative_rigid) for ONE robot, in the coordinates of M:
+    M [30,30], C [30], J [12,30], Jpqp [12] (the soles' Jdot qdot), vhat [30] (v in M's coordinates), tau30 [30] (None: passive), mode (only
+    the low two bits are read) and kv >= 0 -> (a [30], lam [12], flags).  Schur form: a0 = M^-1 (tau30 - C), Y = M^-1 J_S', A = J_S Y,
+    g = J_S a0 + Jpqp_S + kv J_S vhat, lam_S = -A^-1 g by the unpivoted Gauss-Jordan, a = a0 + Y lam_S; lam is exactly 0 on the rows that
+    are not held and LMH_PHASE_FLIGHT is a0 itself.  flags: FLAG_CONTACT_PULL (a held foot's f_z < 0), FLAG_CONTACT_SLIP (hypot(f_x, f_y) >
+    contact_mu f_z on a held foot), FLAG_NONFINITE.  info (a dict, optional) receives A, g, Y, a0, rows and the pivots."""
+    M, C, J = np.asarray(M, dtype=np.float64), np.asarray(C, dtype=np.float64), np.asarray(J, dtype=np.float64)
+    tau30 = np.zeros(30) if tau30 is None else np.asarray(tau30, dtype=np.float64)
+    if not (kv >= 0.0 and np.isfinite(kv)):
+        raise ValueError("kv must be finite and >= 0")
+    rows = list(RIGID_ROWS[int(mode) & 3])
+    a0 = np.linalg.solve(M, tau30 - C)
+    lam, a, flags = np.zeros(12), a0, 0
+    if rows:
+        Js = J[rows]
+        Y = np.linalg.solve(M, Js.T)
+        A = Js @ Y
+        g = Js @ a0 + np.asarray(Jpqp, dtype=np.float64)[rows] + kv * (Js @ np.asarray(vhat, dtype=np.float64))
+        x, piv = gauss_jordan_unpivoted(A, g)
+        lam[rows] = -x
+        a = a0 + Y @ lam[rows]
+        if info is not None:
+            info.update(A=A, g=g, Y=Y, a0=a0, rows=rows, pivots=piv)
+        for ft in range(2):
+            if 6 * ft in rows:
+                fx, fy, fz = lam[6 * ft + 3:6 * ft + 6]
+                flags |= FLAG_CONTACT_PULL if fz < 0.0 else 0
+                flags |= FLAG_CONTACT_SLIP if np.hypot(fx, fy) > contact_mu * fz else 0
+    if not (np.all(np.isfinite(a)) and np.all(np.isfinite(lam))):
+        flags |= FLAG_NONFINITE
+    return a, lam, flags
+
+
+def rigid_modes(phase_samples, k):
+    """The modes lmh_plant_step_rigid takes for a walking host loop: the support phase of the plan(s) at preview index k (preview_index(t,
+    mpc_dt) of the controller evaluation the hold follows), clamped into the arrays as the kernels clamp it.  phase_samples [n] or [B,n]
+    (walk_plan / jump_plan / walk_plans) -> int32 scalar array or [B]: PHASE_DOUBLE holds both soles, PHASE_RIGHT / PHASE_LEFT the
+    supporting one, PHASE_FLIGHT none."""
+    ph = np.asarray(phase_samples)
+    if ph.ndim not in (1, 2) or ph.shape[-1] < 1:
+        raise ValueError("phase_samples must be [n] or [B,n] with n >= 1")
+    k = int(np.clip(int(k), 0, ph.shape[-1] - 1))
+    return (ph[..., k].astype(np.int32) & 3).astype(np.int32)
+
+
 __all__ = ["stance_zmp", "find_poly_coeff", "foot_coeff_trajectory", "walk_plan", "jump_plan", "walk_plans", "jump_plans",
            "push_schedule", "check_push_records", "draw_pushes", "zoh_hold_pieces", "actuator_records", "actuator_step", "ground_planes", "ground_slope", "ground_contact",
-           "preview_index", "lip_rollout", "com_targets",
+           "preview_index", "lip_rollout", "com_targets", "rigid_contact_acceleration", "rigid_modes", "gauss_jordan_unpivoted", "RIGID_ROWS",
            "PHASE_DOUBLE", "PHASE_RIGHT", "PHASE_LEFT", "PHASE_FLIGHT"]

@@ -1,0 +1,168 @@
+"""Shared cases of the rigid-contact plant tests (test_rigid.py on the CPU, test_gpu_rigid.py on the GPU).
+
+Everything here is computed with the CPU oracle and numpy alone: oracle_rigid_xdot restates lmh_plant_derivative_rigid from the oracle's
+M, C, J, Jpqp and trajectories.rigid_contact_acceleration (the numpy statement of include/lmh.h), kkt_reference solves the same
+constrained problem as one KKT system refined in long double, and the 16 input states are plant_step_cases.contact_states().  Results
+are cached per process and never written by a test."""
+import numpy as np
+
+import plant_step_cases as pc
+from linearmpchumanoid_amd.trajectories import RIGID_ROWS, rigid_contact_acceleration
+
+DT, TH, B = pc.DT, pc.TH, pc.B
+MODES = (0, 1, 2)                                                  # LMH_PHASE_DOUBLE, _RIGHT, _LEFT
+KVS = (0.0, 50.0)
+MU = pc.GROUND["mu"]
+
+
+def ninf(a):
+    return float(np.abs(a).sum(axis=1).max()) if np.ndim(a) == 2 else float(np.abs(a).max()) if np.size(a) else 0.0
+
+
+def vhat_of(tm, v):
+    """v in M's coordinates (swapBaseVelocityAndRefToWorldFrame)."""
+    v = np.asarray(v, dtype=np.float64)
+    vh = v.copy()
+    vh[:6] = tm["X"][0] @ np.concatenate([v[3:6], v[0:3]])
+    return vh
+
+
+def oracle_terms(o, q, v):
+    """The oracle's terms at the one velocity v (Robot::v_ set to v before the evaluation), with vhat added."""
+    o.set_prev_velocity(v)
+    o.eval(q, v, 0.0)
+    tm = o.terms()
+    tm["vhat"] = vhat_of(tm, v)
+    return tm
+
+
+def xdot_from_a(q, v, a, X0):
+    """qdot as orc_plant_derivative maps it and the acceleration back in the state's ordering and the world frame."""
+    sol = np.linalg.solve(X0, a[:6])
+    qdot = np.asarray(v, dtype=np.float64).copy()
+    qdot[0:3] += np.cross(v[3:6], q[0:3])
+    qdot[3:6] = pc.euler_rate_matrix(q[3:6]) @ v[3:6]
+    return np.concatenate([qdot, sol[3:6], sol[0:3], a[6:]])
+
+
+def a_from_xdot(xdot, X0):
+    qdd = xdot[30:]
+    return np.concatenate([X0 @ np.concatenate([qdd[3:6], qdd[0:3]]), qdd[6:]])
+
+
+def oracle_rigid_xdot(o, q, v, tau30, mode, kv, mu=MU):
+    """lmh_plant_derivative_rigid from the oracle's parts -> (xdot [60], lam [12], flags, dict(terms, a, info))."""
+    q, v = np.asarray(q, dtype=np.float64), np.asarray(v, dtype=np.float64)
+    tm = oracle_terms(o, q, v)
+    info = {}
+    a, lam, flags = rigid_contact_acceleration(tm["M"], tm["C"], tm["J"], tm["Jpqp"], tm["vhat"], tau30, mode, kv, contact_mu=mu, info=info)
+    return xdot_from_a(q, v, a, tm["X"][0]), lam, flags, dict(terms=tm, a=a, info=info)
+
+
+def oracle_rigid_steps(o, x, tau30, mode, kv, n, dt=DT, mu=MU):
+    """n RK4 substeps of the statement with the torques held -> (state [60], flags OR-ed over every stage, lam at the first stage of the
+    last substep)."""
+    x = np.asarray(x, dtype=np.float64).copy()
+    acc = dict(flags=0, lam=np.zeros(12))
+
+    def xdot_of(stage, s):
+        xd, lam, fl, _ = oracle_rigid_xdot(o, s[:30], s[30:], tau30, mode, kv, mu)
+        acc["flags"] |= fl
+        if stage == 0:
+            acc["lam"] = lam
+        return xd
+
+    for _ in range(n):
+        x = pc.rk4_tick(x, dt, xdot_of)
+    return x, acc["flags"], acc["lam"]
+
+
+def kkt_reference(M, C, J, Jpqp, vhat, tau30, mode, kv):
+    """[M -J_S'; J_S 0] [a; lam_S] = [tau30 - C; -(Jpqp_S + kv J_S vhat)] solved in double and refined against its long-double residual
+    until the correction stalls -> (a, lam [12], cond of the KKT matrix)."""
+    rows = list(RIGID_ROWS[int(mode) & 3])
+    n = len(rows)
+    K = np.zeros((30 + n, 30 + n))
+    K[:30, :30] = M
+    K[:30, 30:] = -J[rows].T
+    K[30:, :30] = J[rows]
+    rhs = np.concatenate([tau30 - C, -(Jpqp[rows] + kv * (J[rows] @ vhat))])
+    Kl, rl = K.astype(np.longdouble), rhs.astype(np.longdouble)
+    x = np.linalg.solve(K, rhs).astype(np.longdouble)
+    for _ in range(6):
+        x = x + np.linalg.solve(K, (rl - Kl @ x).astype(np.float64)).astype(np.longdouble)
+    x = x.astype(np.float64)
+    lam = np.zeros(12)
+    lam[rows] = x[30:]
+    return x[:30], lam, float(np.linalg.cond(K))
+
+
+def bounds(tm, tau30, mode, kv, a, lam):
+    """The three figures of the tests for one case: backward error of the dynamics row M a - J_S' lam = tau30 - C, the constraint residual
+    J_S a + Jpqp_S + kv J_S vhat on its own scale |A| |lam| + |g|, and the forward error of (a, lam) against the refined KKT solve over
+    cond(KKT) -> dict(backward, constraint, forward, cond)."""
+    M, Cv, J, Jp, vh = tm["M"], tm["C"], tm["J"], tm["Jpqp"], tm["vhat"]
+    rows = list(RIGID_ROWS[int(mode) & 3])
+    Js = J[rows]
+    rhs = tau30 - Cv
+    back = ninf(M @ a - Js.T @ lam[rows] - rhs) / (ninf(M) * ninf(a) + ninf(Js.T) * ninf(lam[rows]) + ninf(rhs))
+    a0 = np.linalg.solve(M, rhs)
+    A = Js @ np.linalg.solve(M, Js.T)
+    g = Js @ a0 + Jp[rows] + kv * (Js @ vh)
+    cons = ninf(Js @ a + Jp[rows] + kv * (Js @ vh)) / (ninf(A) * ninf(lam[rows]) + ninf(g))
+    ar, lr, cond = kkt_reference(M, Cv, J, Jp, vh, tau30, mode, kv)
+    fwd = max(ninf(a - ar) / ninf(ar), ninf(lam - lr) / ninf(lr)) / cond
+    return dict(backward=float(back), constraint=float(cons), forward=float(fwd), cond=cond)
+
+
+def sole_twist(o, x):
+    """J vhat [12] of the state x = q | v."""
+    tm = oracle_terms(o, x[:30], x[30:])
+    return tm["J"] @ tm["vhat"]
+
+
+def sole_positions(o, x):
+    """The world positions of the two sole origins [2,3]."""
+    tm = oracle_terms(o, x[:30], x[30:])
+    return np.stack([tm["T"][7][:3, 3], tm["T"][14][:3, 3]])
+
+
+def twist_decay_error(w, w0, kv, t):
+    """How far the twist w [12] of the held soles is from w0 shrunk by e^(-kv t), relative.  The constraint's Jdot qdot is the reference's
+    (the sole's spatial acceleration turned to world axes), so d/dt of the twist J vhat is -kv (J vhat) plus, on the linear part, omega x
+    v_lin: the angular part decays component by component, the linear part decays in magnitude while it turns with the sole.  The
+    figure is therefore the worst of the angular components and of the two linear magnitudes, each over the largest entry of the shrunk
+    twist; the second value is the component-wise figure of the linear part, which the turn (about omega_0 / kv radians) dominates."""
+    w, w0 = np.asarray(w).reshape(2, 2, 3), np.asarray(w0).reshape(2, 2, 3)
+    s = np.exp(-kv * t)
+    scale = s * np.abs(w0).max()
+    ang = np.abs(w[:, 0] - s * w0[:, 0]).max()
+    mag = np.abs(np.linalg.norm(w[:, 1], axis=1) - s * np.linalg.norm(w0[:, 1], axis=1)).max()
+    return float(max(ang, mag) / scale), float(np.abs(w[:, 1] - s * w0[:, 1]).max() / scale)
+
+
+def step_tau():
+    """The torques held over the substep tests: N(0, 0.05^2) N m on every row, as test_gpu_plant_step.py's (the light distal links turn a
+    newton metre into 1e5 rad/s^2, which no 1 ms step follows)."""
+    return np.random.default_rng(20261020).normal(0.0, 0.05, (B, 30))
+
+
+_cache = {}
+
+
+def rigid_cases():
+    """The 96 derivative cases -- 16 contact_states() x MODES x KVS -- on the oracle's terms: dict(q, v, tau, zcom, q0, terms [16], and
+    per (i, mode, kv) dict(a, lam, flags, xdot, info))."""
+    if _cache:
+        return _cache
+    S = pc.contact_states()
+    o = pc.make_oracle()
+    terms, cases = [], {}
+    for i in range(B):
+        for m in MODES:
+            for kv in KVS:
+                xdot, lam, flags, parts = oracle_rigid_xdot(o, S["q"][i], S["v"][i], S["tau"][i], m, kv)
+                cases[(i, m, kv)] = dict(xdot=xdot, lam=lam, flags=flags, a=parts["a"], info=parts["info"])
+        terms.append(parts["terms"])
+    _cache.update(q=S["q"], v=S["v"], tau=S["tau"], zcom=S["zcom"], q0=S["q0"], terms=terms, cases=cases)
+    return _cache

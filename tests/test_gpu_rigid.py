@@ -1,0 +1,465 @@
+"""lmh_plant_derivative_rigid / lmh_plant_step_rigid on the GPU against the numpy statement (trajectories.rigid_contact_acceleration) on the
+CPU oracle's terms.  Every test fails on a library without the two entry points.
+
+Inputs: rigid_cases.rigid_cases() -- plant_step_cases.contact_states(), 16 states, under three support modes and kv in {0, 50}.  Every case
+runs at most 16 robots, 20 substeps or 12 control ticks.
+
+Tolerances are the project's own (test_gpu_plant_step.py, test_gpu_terms.py): backward error 1e-12, forward error 1e-12 cond(KKT) against a
+long-double-refined KKT solve of the terms the comparison is made on, the constraint residual J_S a + Jpqp_S + kv J_S vhat = A lam_S + g to
+1e-12 on that system's own scale |A| |lam| + |g|, states after substeps to the 1e-7 `close`; the closed loop to test_gpu_zoh.py's bounds."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import plant_step_cases as pc
+import rigid_cases as rc
+from helpers import TOL_REL, WEIGHT, close, make_controller, perturbed_velocities, rel_err, same_bits as _same, to_device, vec_err
+
+pytestmark = pytest.mark.gpu
+DT, TH, B = rc.DT, rc.TH, rc.B
+
+
+def _imode(ctl, m):
+    return torch.as_tensor(np.asarray(m, dtype=np.int32)).to(ctl.device)
+
+
+def _inputs(ctl, S):
+    return tuple(to_device(ctl, S[k]) for k in ("q", "v", "tau"))
+
+
+def _fresh(ctl, S, t0=0.0, v_prev=None):
+    st = ctl.new_state(S["q"], S["v"], t=t0, v_prev=S["v"] if v_prev is None else v_prev)
+    st[:, 91:96] = torch.arange(1.0, 6.0, dtype=torch.float64, device=ctl.device)          # the pads: left alone
+    return st
+
+
+def _flag_margins(lam, rows, mu=rc.MU):
+    """Which of the two informational flags the statement decides by more than 1e-9 N on this case -> (pull decided, slip decided)."""
+    held = [ft for ft in range(2) if 6 * ft in rows]
+    pull = all(abs(lam[6 * ft + 5]) > 1e-9 for ft in held)
+    slip = all(abs(np.hypot(lam[6 * ft + 3], lam[6 * ft + 4]) - mu * lam[6 * ft + 5]) > 1e-9 for ft in held)
+    return pull, slip
+
+
+def _derivative_against(terms_of, tag):
+    """Tests 1 and 2: modes mixed over the batch (mode[i] = (i + s) % 3, s = 0, 1, 2), kv 0 and 50, against the statement on terms_of(i)."""
+    from linearmpchumanoid_amd import capi
+    S = rc.rigid_cases()
+    ctl = make_controller(B, DT, TH, S["zcom"])
+    q, v, tau = _inputs(ctl, S)
+    xd_plain, _, _ = ctl.plant_derivative(q, v, tau)
+    worst = dict(backward=0.0, constraint=0.0, forward=0.0)
+    undecided = 0
+    for s in range(3):
+        mode = [(i + s) % 3 for i in range(B)]
+        for kv in rc.KVS:
+            xdot, lam, flags = ctl.plant_derivative_rigid(q, v, tau, _imode(ctl, mode), kv)
+            torch.cuda.synchronize()
+            assert _same(xdot[:, :30], xd_plain[:, :30])           # qdot: lmh_plant_derivative's, bit for bit
+            xdot, lam, flags = xdot.cpu().numpy(), lam.cpu().numpy(), flags.cpu().numpy()
+            for i in range(B):
+                tm = terms_of(i)
+                a = rc.a_from_xdot(xdot[i], S["terms"][i]["X"][0])
+                info = {}
+                _, lam_s, flags_s = rc.rigid_contact_acceleration(tm["M"], tm["C"], tm["J"], tm["Jpqp"], tm["vhat"], S["tau"][i], mode[i], kv, contact_mu=rc.MU, info=info)
+                b = rc.bounds(tm, S["tau"][i], mode[i], kv, a, lam[i])
+                for k in worst:
+                    worst[k] = max(worst[k], b[k])
+                free = [r for r in range(12) if r not in info["rows"]]
+                assert np.isfinite(xdot[i]).all() and not lam[i][free].any(), (tag, s, kv, i)
+                assert b["backward"] <= 1e-12 and b["constraint"] <= 1e-12 and b["forward"] <= 1e-12, (tag, s, kv, i, b)
+                assert not flags[i] & (capi.FLAG_NOT_SPD | capi.FLAG_NONFINITE), (tag, s, kv, i, flags[i])
+                pull, slip = _flag_margins(lam_s, info["rows"])
+                undecided += (not pull) + (not slip)
+                if pull:
+                    assert (flags[i] & capi.FLAG_CONTACT_PULL) == (flags_s & capi.FLAG_CONTACT_PULL), (tag, s, kv, i)
+                if slip:
+                    assert (flags[i] & capi.FLAG_CONTACT_SLIP) == (flags_s & capi.FLAG_CONTACT_SLIP), (tag, s, kv, i)
+    print("\nrigid derivative vs the statement on %s: backward %.2e, constraint %.2e, forward/cond %.2e (flags not compared: %d)"
+          % (tag, worst["backward"], worst["constraint"], worst["forward"], undecided))
+    assert undecided <= 8                                          # the margins leave the comparison its cases
+
+
+def test_derivative_against_the_statement_on_the_oracles_terms():
+    S = rc.rigid_cases()
+    _derivative_against(lambda i: S["terms"][i], "the oracle's terms")
+
+
+def test_derivative_against_the_statement_on_the_devices_terms():
+    """The same with the statement fed with the GPU's own terms(q, v) record (M, C, J, Jpqp; vhat and the base's X_0, pure functions of the
+    base pose, stay the oracle's): the oracle-vs-GPU term difference is out of the comparison."""
+    S = rc.rigid_cases()
+    ctl = make_controller(B, DT, TH, S["zcom"])
+    t = ctl.split_terms(ctl.terms(to_device(ctl, S["q"]), to_device(ctl, S["v"])).cpu().numpy())
+    dev = [dict(M=t["M"][i], C=t["C"][i], J=t["J"][i], Jpqp=t["Jpqp"][i], vhat=S["terms"][i]["vhat"]) for i in range(B)]
+    _derivative_against(lambda i: dev[i], "the device's terms")
+
+
+def test_flight_is_the_plain_derivative_out_of_the_ground():
+    """The 16 states raised by 5 cm (every vertex out of the ground), LMH_PHASE_FLIGHT: xdot is lmh_plant_derivative's bit for bit -- the
+    first right-hand side of the multi-right-hand-side solve sees plant_minv's operations in plant_minv's order -- and lambda is exactly 0."""
+    S = rc.rigid_cases()
+    ctl = make_controller(B, DT, TH, S["zcom"])
+    qn = S["q"].copy(); qn[:, 2] += 0.05
+    q, v, tau = to_device(ctl, qn), to_device(ctl, S["v"]), to_device(ctl, S["tau"])
+    xd, c, f = ctl.plant_derivative(q, v, tau)
+    flight = _imode(ctl, np.full(B, 3))
+    for kv in rc.KVS:
+        xr, lam, fr = ctl.plant_derivative_rigid(q, v, tau, flight, kv)
+        torch.cuda.synchronize()
+        assert float(c.abs().max()) == 0.0 and int(f.abs().max()) == 0
+        worst = float(((xr - xd).abs() / xd.abs().clamp_min(1e-300)).max())
+        print("\nflight vs plant_derivative, kv = %g: largest relative difference %.2e" % (kv, worst))
+        assert _same(xr, xd) and float(lam.abs().max()) == 0.0 and int(fr.abs().max()) == 0
+    held, _, _ = ctl.plant_derivative_rigid(q, v, tau, None, 0.0)
+    torch.cuda.synchronize()
+    assert not _same(held, xd)                                     # a constraint knows no plane: held soles act 5 cm up too
+
+
+def test_defaults_mode_bits_and_permutation():
+    S = rc.rigid_cases()
+    ctl = make_controller(B, DT, TH, S["zcom"])
+    q, v, tau = _inputs(ctl, S)
+    kv = 50.0
+    mode_np = np.array([(i * 7 + 1) % 4 for i in range(B)], dtype=np.int32)        # all four modes
+    res = ctl.plant_derivative_rigid(q, v, tau, _imode(ctl, mode_np), kv)
+    for name, a, b in (("mode None = all DOUBLE", ctl.plant_derivative_rigid(q, v, tau, None, kv), ctl.plant_derivative_rigid(q, v, tau, _imode(ctl, np.zeros(B)), kv)),
+                       ("tau None = zeros", ctl.plant_derivative_rigid(q, v, None, _imode(ctl, mode_np), kv), ctl.plant_derivative_rigid(q, v, torch.zeros_like(tau), _imode(ctl, mode_np), kv)),
+                       ("only the low two bits", res, ctl.plant_derivative_rigid(q, v, tau, _imode(ctl, mode_np + 4), kv)),
+                       ("only the low two bits, high ones", res, ctl.plant_derivative_rigid(q, v, tau, _imode(ctl, mode_np.astype(np.int64) - 2 ** 31 + 1024), kv))):
+        torch.cuda.synchronize()
+        assert all(_same(x, y) for x, y in zip(a, b)), name
+    assert not _same(res[0], ctl.plant_derivative_rigid(q, v, tau, None, kv)[0])
+    perm = np.random.default_rng(20261201).permutation(B)
+    pt = torch.as_tensor(perm).to(ctl.device)
+    pres = ctl.plant_derivative_rigid(q[pt].contiguous(), v[pt].contiguous(), tau[pt].contiguous(), _imode(ctl, mode_np[perm]), kv)
+    sres = ctl.plant_step_rigid(_fresh(ctl, S), tau, _imode(ctl, mode_np), kv, 3)
+    spres = ctl.plant_step_rigid(_fresh(ctl, S)[pt].contiguous(), tau[pt].contiguous(), _imode(ctl, mode_np[perm]), kv, 3)
+    torch.cuda.synchronize()
+    assert all(_same(x[pt], y) for x, y in zip(res, pres)) and all(_same(x[pt], y) for x, y in zip(sres, spres))
+
+
+def _randomised_links(n):
+    from linearmpchumanoid_amd.controller import nominal_links
+    raw = np.tile(nominal_links(), (n, 1, 1))
+    rng = np.random.default_rng(20260004)
+    raw[:, :, 0] *= rng.uniform(0.9, 1.1, (n, 28))
+    raw[:, :, 1:4] += rng.uniform(-5e-3, 5e-3, (n, 28, 3)) * (raw[:, :, 0:1] > 0)
+    return raw
+
+
+def test_per_robot_models_and_friction():
+    """Four robots with four models (set_model) and four contact_mu (set_params) in one handle equal four handles of one robot, bit for
+    bit; the friction coefficients are chosen around the multiplier's own ratio so that the slip flag differs between them."""
+    from linearmpchumanoid_amd import capi
+    S = rc.rigid_cases()
+    n, idx, kv = 4, [1, 6, 11, 12], 50.0
+    raw = _randomised_links(n)
+    mode_np = np.array([0, 1, 2, 0], dtype=np.int32)
+    q, v, tau = S["q"][idx], S["v"][idx], S["tau"][idx]
+    probe = make_controller(n, DT, TH, S["zcom"])
+    probe.set_model(raw)
+    _, lam0, _ = probe.plant_derivative_rigid(to_device(probe, q), to_device(probe, v), to_device(probe, tau), _imode(probe, mode_np), kv)
+    lam0 = lam0.cpu().numpy()
+    held = [[ft for ft in range(2) if mode_np[i] in (0, 1 + ft)] for i in range(n)]
+    ratio = [[np.hypot(lam0[i, 6 * ft + 3], lam0[i, 6 * ft + 4]) / abs(lam0[i, 6 * ft + 5]) for ft in held[i]] for i in range(n)]
+    pulls = [any(lam0[i, 6 * ft + 5] < 0.0 for ft in held[i]) for i in range(n)]
+    mu = np.array([max(ratio[i]) * 2.0 if i % 2 == 0 else min(ratio[i]) * 0.5 for i in range(n)])      # inside every held foot's disc | outside
+    ctl = make_controller(n, DT, TH, S["zcom"])
+    ctl.set_model(raw)
+    ctl.set_params(contact_mu=mu)
+    xdot, lam, flags = ctl.plant_derivative_rigid(to_device(ctl, q), to_device(ctl, v), to_device(ctl, tau), _imode(ctl, mode_np), kv)
+    st, sl, sf = ctl.plant_step_rigid(ctl.new_state(q, v, t=0.0), to_device(ctl, tau * 0.025), _imode(ctl, mode_np), kv, 5)
+    torch.cuda.synchronize()
+    for i in range(n):
+        one = make_controller(1, DT, TH, S["zcom"], contact_mu=float(mu[i]))
+        one.set_model(raw[i])
+        x1, l1, f1 = one.plant_derivative_rigid(to_device(one, q[i:i + 1]), to_device(one, v[i:i + 1]), to_device(one, tau[i:i + 1]), _imode(one, mode_np[i:i + 1]), kv)
+        s1, sl1, sf1 = one.plant_step_rigid(one.new_state(q[i:i + 1], v[i:i + 1], t=0.0), to_device(one, tau[i:i + 1] * 0.025), _imode(one, mode_np[i:i + 1]), kv, 5)
+        torch.cuda.synchronize()
+        assert _same(x1[0], xdot[i]) and _same(l1[0], lam[i]) and _same(f1[0], flags[i]) and _same(s1[0], st[i]) and _same(sl1[0], sl[i]) and _same(sf1[0], sf[i]), i
+    fl = flags.cpu().numpy()
+    for i in range(n):                                             # a pulling foot is outside every disc; otherwise mu decides
+        assert bool(fl[i] & capi.FLAG_CONTACT_SLIP) == (pulls[i] or mu[i] < max(ratio[i])), (i, fl[i], mu[i], ratio[i])
+        assert bool(fl[i] & capi.FLAG_CONTACT_PULL) == pulls[i], (i, fl[i])
+    nominal = make_controller(n, DT, TH, S["zcom"])
+    assert not _same(nominal.plant_derivative_rigid(to_device(nominal, q), to_device(nominal, v), to_device(nominal, tau), _imode(nominal, mode_np), kv)[0], xdot)   # the models matter
+
+
+def test_step_composition_clock_and_lambda():
+    S = rc.rigid_cases()
+    ctl = make_controller(B, DT, TH, S["zcom"])
+    tau = to_device(ctl, rc.step_tau())
+    vprev = np.random.default_rng(20261021).normal(0.0, 1.0, (B, 30))
+    t0, kv = 0.25, 50.0
+    mode = _imode(ctl, [i % 3 for i in range(B)])
+    fresh = lambda: _fresh(ctl, S, t0, vprev)
+    s20, l20, f20 = ctl.plant_step_rigid(fresh(), tau, mode, kv, 20)
+    s7, l7, f7 = ctl.plant_step_rigid(fresh(), tau, mode, kv, 7)
+    s7 = s7.clone()
+    s713, l13, f13 = ctl.plant_step_rigid(s7.clone(), tau, mode, kv, 13)
+    s1, l1, f1 = ctl.plant_step_rigid(fresh(), tau, mode, kv, 1)
+    f0 = fresh()
+    xd, ld, fd = ctl.plant_derivative_rigid(f0[:, 0:30].contiguous(), f0[:, 30:60].contiguous(), tau, mode, kv)
+    # the multiplier of 13 more substeps is the one at the first stage of the LAST substep: the derivative's at the state after 19
+    s19, _, _ = ctl.plant_step_rigid(fresh(), tau, mode, kv, 19)
+    _, ld19, _ = ctl.plant_derivative_rigid(s19[:, 0:30].contiguous(), s19[:, 30:60].contiguous(), tau, mode, kv)
+    torch.cuda.synchronize()
+    assert _same(s713, s20) and _same(f7 | f13, f20) and _same(l13, l20)           # 7 + 13 = 20 in state, t, OR-ed flags (and the last multiplier)
+    assert _same(l1, ld) and _same(l20, ld19)                                      # n_substeps = 1: the derivative call's lambda at the input state
+    assert not (f20.cpu().numpy() & 10).any()                                      # neither FLAG_NOT_SPD nor FLAG_NONFINITE
+    for st, n in ((s1, 1), (s7, 7), (s20, 20)):
+        a = st.cpu().numpy()
+        t = t0
+        for _ in range(n):
+            t += DT
+        assert np.array_equal(a[:, 90], np.full(B, t))                             # n additions of dt
+        assert np.array_equal(a[:, 60:90], vprev) and np.array_equal(a[:, 91:96], np.tile(np.arange(1.0, 6.0), (B, 1)))
+    # n_substeps = 0 leaves every byte: the state, and a multiplier and flags pre-filled with a pattern
+    L = __import__("linearmpchumanoid_amd.capi", fromlist=["lib"]).lib()
+    p = lambda t: C.c_void_p(t.data_ptr())
+    st = fresh()
+    lam = torch.full((B, 12), -7.0, dtype=torch.float64, device=ctl.device)
+    fl = torch.full((B,), -7, dtype=torch.int32, device=ctl.device)
+    assert L.lmh_plant_step_rigid(ctl._h, p(st), p(tau), p(mode), kv, 0, p(lam), p(fl), ctl._stream()) == 0
+    torch.cuda.synchronize()
+    assert _same(st, fresh()) and bool((lam == -7.0).all()) and bool((fl == -7).all())
+    # the NULL outputs are legal
+    st = fresh()
+    assert L.lmh_plant_step_rigid(ctl._h, p(st), p(tau), p(mode), kv, 20, None, None, ctl._stream()) == 0
+    xo = torch.empty((B, 60), dtype=torch.float64, device=ctl.device)
+    assert L.lmh_plant_derivative_rigid(ctl._h, p(f0[:, 0:30].contiguous()), p(f0[:, 30:60].contiguous()), p(tau), p(mode), kv, p(xo), None, None, ctl._stream()) == 0
+    torch.cuda.synchronize()
+    assert _same(st, s20) and _same(xo, xd)
+
+
+def test_twenty_substeps_against_the_statement():
+    """20 substeps against rk4_tick over the statement on the oracle: close(.., 1e-7), with kv = 50 and both soles held, and with kv = 0 and
+    the modes mixed.  The sole-twist decay at kv = 50 is within the CPU test's 1e-3 (rigid_cases.twist_decay_error)."""
+    from linearmpchumanoid_amd import capi
+    S = rc.rigid_cases()
+    ctl = make_controller(B, DT, TH, S["zcom"])
+    tau_np = rc.step_tau()
+    tau = to_device(ctl, tau_np)
+    o = pc.make_oracle()
+    n = 20
+    for kv, mode_np in ((50.0, np.zeros(B, dtype=np.int32)), (0.0, np.array([(i + 1) % 3 for i in range(B)], dtype=np.int32))):
+        st, lam, flags = ctl.plant_step_rigid(_fresh(ctl, S), tau, _imode(ctl, mode_np), kv, n)
+        torch.cuda.synchronize()
+        a, lam, flags = st.cpu().numpy(), lam.cpu().numpy(), flags.cpu().numpy()
+        worst, decay = 0.0, 0.0
+        for i in range(B):
+            x0 = np.concatenate([S["q"][i], S["v"][i]])
+            ref, flags_s, lam_s = rc.oracle_rigid_steps(o, x0, tau_np[i], int(mode_np[i]), kv, n)
+            worst = max(worst, rel_err(a[i, :60], ref))
+            assert close(a[i, :60], ref, 1e-7), (kv, i, rel_err(a[i, :60], ref))
+            assert close(lam[i], lam_s, 1e-7, scale=WEIGHT), (kv, i, vec_err(lam[i], lam_s))
+            assert not flags[i] & (capi.FLAG_NOT_SPD | capi.FLAG_NONFINITE)
+            if kv > 0.0:
+                err, _ = rc.twist_decay_error(rc.sole_twist(o, a[i, :60]), rc.sole_twist(o, x0), kv, n * DT)
+                decay = max(decay, err)
+                assert err <= 1e-3, (i, err)
+        print("\nrigid step vs the statement's RK4, 20 substeps, kv = %g: %.2e%s" % (kv, worst, "; twist decay %.2e" % decay if kv > 0.0 else ""))
+
+
+def test_closed_loop_against_the_cpu_loop():
+    """4 robots x 12 control ticks of the host loop stand_step ; plant_step_rigid([0 | out.tau], DOUBLE, kv, 1) against the CPU loop (oracle
+    evaluation + statement), test_gpu_zoh.py's bounds: state 1e-7, tau and f 1e-6 (f with the weight's floor), k exact, no controller flag."""
+    S = rc.rigid_cases()
+    n, nt, kv = 4, 12, 50.0
+    ctl = make_controller(n, DT, TH, S["zcom"], warm_start=0)
+    ctl.set_refs_stance(2.0, 2)
+    q = np.tile(S["q0"], (n, 1))
+    v = perturbed_velocities(n, seed=20261022) * 0.2
+    v[0] = 0.0                                                     # one robot from rest
+    st = ctl.new_state(q, v, t=0.0, v_prev=v)
+    zero6 = torch.zeros((n, 6), dtype=torch.float64, device=ctl.device)
+    cflags = torch.zeros((n,), dtype=torch.int32, device=ctl.device)
+    for _ in range(nt):
+        out, status = ctl.stand_step(st)
+        cflags |= status[:, 2]
+        st, lam, pf = ctl.plant_step_rigid(st, torch.cat([zero6, out[:, 0:24]], dim=1).contiguous(), None, kv, 1)
+    torch.cuda.synchronize()
+    a, o_, s, lam = st.cpu().numpy(), out.cpu().numpy(), status.cpu().numpy(), lam.cpu().numpy()
+    assert int(cflags.abs().max()) == 0 and not (pf.cpu().numpy() & 10).any()
+    rows = []
+    refs = []
+    for i in range(n):
+        o = pc.make_oracle()
+        x, t, held = np.concatenate([q[i], v[i]]), 0.0, v[i].copy()
+        for _ in range(nt):
+            o.set_prev_velocity(held)
+            last = o.eval(x[:30], x[30:], t)
+            held = x[30:].copy()
+            x, _, lam_s = rc.oracle_rigid_steps(o, x, np.concatenate([np.zeros(6), last["tau"]]), 0, kv, 1)
+            t += DT
+        refs.append((x, t, last, lam_s))
+        rows.append((i, rel_err(a[i, :60], x), vec_err(o_[i, 0:24], last["tau"]), vec_err(o_[i, 24:36], last["f"]), vec_err(lam[i], lam_s), int(s[i, 0]), last["k"]))
+        print("\nrigid closed loop, robot %d: state %.2e  tau %.2e  f %.2e  lambda %.2e  k %d (oracle %d)" % rows[-1], end="")
+    print()
+    for i in range(n):
+        x, t, last, lam_s = refs[i]
+        assert close(a[i, :60], x, 1e-7) and a[i, 90] == t, rows[i]
+        assert close(o_[i, 0:24], last["tau"], TOL_REL) and close(o_[i, 24:36], last["f"], TOL_REL, scale=WEIGHT), rows[i]
+        assert s[i, 0] == last["k"] and s[i, 2] == 0, rows[i]
+
+
+def test_a_nan_flags_its_robot_alone():
+    from linearmpchumanoid_amd import capi
+    S = rc.rigid_cases()
+    ctl = make_controller(B, DT, TH, S["zcom"])
+    q, v, tau = _inputs(ctl, S)
+    mode = _imode(ctl, [i % 3 for i in range(B)])
+    clean = ctl.plant_derivative_rigid(q, v, tau, mode, 50.0)
+    sclean = ctl.plant_step_rigid(_fresh(ctl, S), tau * 0.025, mode, 50.0, 3)
+    qn = q.clone(); qn[9, 11] = float("nan")
+    bad = ctl.plant_derivative_rigid(qn, v, tau, mode, 50.0)
+    stn = _fresh(ctl, S); stn[9, 11] = float("nan")
+    sbad = ctl.plant_step_rigid(stn, tau * 0.025, mode, 50.0, 3)
+    torch.cuda.synchronize()
+    keep = torch.as_tensor([i for i in range(B) if i != 9]).to(ctl.device)
+    for a, b in ((clean, bad), (sclean, sbad)):
+        assert int(b[2][9]) & capi.FLAG_NONFINITE
+        assert not (b[2][keep].cpu().numpy() & capi.FLAG_NONFINITE).any()
+        assert all(_same(x[keep], y[keep]) for x, y in zip(a, b))
+
+
+def test_refusals():
+    from linearmpchumanoid_amd import capi
+    S = rc.rigid_cases()
+    ctl = make_controller(B, DT, TH, S["zcom"])
+    L = capi.lib()
+    err = lambda: L.lmh_last_error().decode()
+    q, v, tau = _inputs(ctl, S)
+    mode = _imode(ctl, np.zeros(B))
+    st = _fresh(ctl, S)
+    st_before = st.clone()
+    sent = lambda *shape: torch.full(shape, -7.0, dtype=torch.float64, device=ctl.device)
+    xo, lam, fl = sent(B, 60), sent(B, 12), torch.full((B,), -7, dtype=torch.int32, device=ctl.device)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    D, Sx = L.lmh_plant_derivative_rigid, L.lmh_plant_step_rigid
+    nan, inf = float("nan"), float("inf")
+    cases = [(D(ctl._h, None, p(v), p(tau), p(mode), 0.0, p(xo), p(lam), p(fl), None), "lmh_plant_derivative_rigid: null device pointer"),
+             (D(ctl._h, p(q), None, p(tau), p(mode), 0.0, p(xo), p(lam), p(fl), None), "lmh_plant_derivative_rigid: null device pointer"),
+             (D(ctl._h, p(q), p(v), p(tau), p(mode), 0.0, None, p(lam), p(fl), None), "lmh_plant_derivative_rigid: null device pointer"),
+             (D(ctl._h, p(q), p(v), p(tau), p(mode), -1.0, p(xo), p(lam), p(fl), None), "lmh_plant_derivative_rigid: kv must be finite and >= 0"),
+             (D(ctl._h, p(q), p(v), p(tau), p(mode), nan, p(xo), p(lam), p(fl), None), "lmh_plant_derivative_rigid: kv must be finite and >= 0"),
+             (D(ctl._h, p(q), p(v), p(tau), p(mode), inf, p(xo), p(lam), p(fl), None), "lmh_plant_derivative_rigid: kv must be finite and >= 0"),
+             (D(None, p(q), p(v), p(tau), p(mode), 0.0, p(xo), p(lam), p(fl), None), "null handle"),
+             (Sx(ctl._h, None, p(tau), p(mode), 0.0, 1, p(lam), p(fl), None), "lmh_plant_step_rigid: null device pointer"),
+             (Sx(ctl._h, p(st), p(tau), p(mode), -1e-300, 1, p(lam), p(fl), None), "lmh_plant_step_rigid: kv must be finite and >= 0"),
+             (Sx(ctl._h, p(st), p(tau), p(mode), nan, 1, p(lam), p(fl), None), "lmh_plant_step_rigid: kv must be finite and >= 0"),
+             (Sx(ctl._h, p(st), p(tau), p(mode), nan, 0, p(lam), p(fl), None), "lmh_plant_step_rigid: kv must be finite and >= 0"),
+             (Sx(ctl._h, p(st), p(tau), p(mode), 0.0, -1, p(lam), p(fl), None), "lmh_plant_step_rigid: n_substeps must be >= 0"),
+             (Sx(None, p(st), p(tau), p(mode), 0.0, 1, p(lam), p(fl), None), "null handle")]
+    # (each call's message is read right after it: the list is built call by call)
+    for rc_, _ in cases:
+        assert rc_ == -2
+    for call, words in ((lambda: D(ctl._h, p(q), p(v), p(tau), p(mode), -1.0, p(xo), p(lam), p(fl), None), "lmh_plant_derivative_rigid: kv must be finite and >= 0"),
+                        (lambda: D(ctl._h, None, p(v), p(tau), p(mode), -1.0, p(xo), p(lam), p(fl), None), "lmh_plant_derivative_rigid: null device pointer"),
+                        (lambda: Sx(ctl._h, None, p(tau), p(mode), nan, -1, p(lam), p(fl), None), "lmh_plant_step_rigid: null device pointer"),
+                        (lambda: Sx(ctl._h, p(st), p(tau), p(mode), nan, -1, p(lam), p(fl), None), "lmh_plant_step_rigid: kv must be finite and >= 0"),
+                        (lambda: Sx(ctl._h, p(st), p(tau), p(mode), 0.0, -1, p(lam), p(fl), None), "lmh_plant_step_rigid: n_substeps must be >= 0"),
+                        (lambda: Sx(None, None, None, None, nan, -1, None, None, None), "null handle")):
+        assert call() == -2 and err() == words, (err(), words)
+    torch.cuda.synchronize()
+    assert _same(st, st_before) and bool((xo == -7.0).all()) and bool((lam == -7.0).all()) and bool((fl == -7).all())      # nothing was enqueued
+    with pytest.raises(ValueError):
+        ctl.plant_derivative_rigid(q, v, tau, mode.to(torch.int64))
+    with pytest.raises(ValueError):
+        ctl.plant_derivative_rigid(q, v, tau, mode[:B - 1])
+    with pytest.raises(capi.LmhError) as e:
+        ctl.plant_step_rigid(st, tau, mode, -1.0, 1)
+    assert e.value.code == -2
+    # plant_constants_ok's checks apply, on a plant = 0 handle too, in that rule set's words
+    bad = make_controller(B, DT, TH, S["zcom"], plant=0, contact_k=-1.0)
+    qb, vb, tb = _inputs(bad, S)
+    sb = _fresh(bad, S)
+    for call in (lambda: bad.plant_derivative_rigid(qb, vb, tb), lambda: bad.plant_step_rigid(sb, tb, None, 0.0, 1), lambda: bad.plant_step_rigid(sb, tb, None, 0.0, 0)):
+        with pytest.raises(capi.LmhError) as e:
+            call()
+        assert e.value.code == -2 and "contact_k" in str(e.value)
+    torch.cuda.synchronize()
+    assert _same(sb, st_before)
+    mu = np.full(B, 0.7); mu[7] = -1.0
+    ok = make_controller(B, DT, TH, S["zcom"], plant=0)
+    ok.set_params(contact_mu=mu)
+    with pytest.raises(capi.LmhError) as e:
+        ok.plant_derivative_rigid(*_inputs(ok, S))
+    assert e.value.code == -2 and "robot 7:" in str(e.value)
+
+
+def test_the_handle_is_not_written_and_no_table_is_read():
+    """stand_step, a 20-tick rollout, plant_step and plant_derivative are bit for bit the same before and after the new calls, with and
+    without a ground table and a servo table -- which the new calls ignore: the same bytes either way."""
+    from linearmpchumanoid_amd.trajectories import ground_planes
+    S = rc.rigid_cases()
+    ctl = make_controller(B, DT, TH, S["zcom"], warm_start=1)
+    ctl.set_refs_stance(2.0, 2)
+    st0 = ctl.new_state(S["q0"], S["v"] * 0.2, t=0.0)
+    q, v, tau = _inputs(ctl, S)
+    small = to_device(ctl, rc.step_tau())
+    mode = _imode(ctl, [i % 4 for i in range(B)])
+
+    def old_calls():
+        a = st0.clone()
+        o1, s1 = ctl.stand_step(a)
+        b = st0.clone()
+        o2, s2, _ = ctl.rollout(b, 20)
+        ps, pf = ctl.plant_step(_fresh(ctl, S), small, 4)
+        xd, c, f = ctl.plant_derivative(q, v, tau)
+        torch.cuda.synchronize()
+        return a, o1, s1, b, o2, s2, ps, pf, xd, c, f
+
+    def new_calls():
+        r = ctl.plant_derivative_rigid(q, v, tau, mode, 50.0) + ctl.plant_step_rigid(_fresh(ctl, S), small, mode, 50.0, 4)
+        torch.cuda.synchronize()
+        return r
+
+    rigid = None
+    for tables in (False, True):
+        if tables:
+            ctl.set_ground(ground_planes(0.05, 0.3, h_r=1e-3, h_l=-1e-3))
+            ctl.set_servo(kp=5.0, kd=0.1)
+        before = old_calls()
+        for _ in range(2):
+            got = new_calls()
+        after = old_calls()
+        assert all(_same(x, y) for x, y in zip(before, after)), tables
+        assert rigid is None or all(_same(x, y) for x, y in zip(rigid, got))       # a constraint knows no plane and no servo
+        rigid = got
+    flat = make_controller(B, DT, TH, S["zcom"])
+    assert not _same(before[8], flat.plant_derivative(*_inputs(flat, S))[0])       # the table does reach the calls that read it
+
+
+def test_captured_as_the_first_call_on_a_fresh_handle():
+    from linearmpchumanoid_amd import capi
+    S = rc.rigid_cases()
+    L, p = capi.lib(), (lambda t: C.c_void_p(t.data_ptr()))
+    ctl = make_controller(B, DT, TH, S["zcom"])                    # fresh: no launch before the capture
+    q, v = to_device(ctl, S["q"]), to_device(ctl, S["v"])
+    tau = to_device(ctl, rc.step_tau())
+    mode = _imode(ctl, [i % 3 for i in range(B)])
+    st0 = _fresh(ctl, S)
+    sent = lambda *shape: torch.full(shape, -7.0, dtype=torch.float64, device=ctl.device)
+    st, xo, lam_d, lam_s = st0.clone(), sent(B, 60), sent(B, 12), sent(B, 12)
+    fd, fs = torch.full((B,), -7, dtype=torch.int32, device=ctl.device), torch.full((B,), -7, dtype=torch.int32, device=ctl.device)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        rc1 = L.lmh_plant_derivative_rigid(ctl._h, p(q), p(v), p(tau), p(mode), 50.0, p(xo), p(lam_d), p(fd), ctl._stream())
+        rc2 = L.lmh_plant_step_rigid(ctl._h, p(st), p(tau), p(mode), 50.0, 5, p(lam_s), p(fs), ctl._stream())
+    assert rc1 == 0 and rc2 == 0
+    torch.cuda.synchronize()
+    assert _same(st, st0) and bool((xo == -7.0).all()) and bool((lam_s == -7.0).all())     # captured, not run
+    g.replay()
+    torch.cuda.synchronize()
+    got = [x.clone() for x in (xo, lam_d, fd, st, lam_s, fs)]
+    del g
+    e = ctl.plant_derivative_rigid(q, v, tau, mode, 50.0) + ctl.plant_step_rigid(st0.clone(), tau, mode, 50.0, 5)
+    torch.cuda.synchronize()
+    for name, a, b in zip(("xdot", "lambda", "flags", "state", "step lambda", "step flags"), got, e):
+        assert _same(a, b), name
+    assert not _same(got[3], st0)
