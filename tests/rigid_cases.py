@@ -77,15 +77,22 @@ def oracle_rigid_steps(o, x, tau30, mode, kv, n, dt=DT, mu=MU):
     return x, acc["flags"], acc["lam"]
 
 
-def kkt_reference(M, C, J, Jpqp, vhat, tau30, mode, kv):
-    """[M -J_S'; J_S 0] [a; lam_S] = [tau30 - C; -(Jpqp_S + kv J_S vhat)] solved in double and refined against its long-double residual
-    until the correction stalls -> (a, lam [12], cond of the KKT matrix)."""
+def kkt_matrix(M, J, mode):
+    """[M -J_S'; J_S 0] of the rows the mode holds."""
     rows = list(RIGID_ROWS[int(mode) & 3])
     n = len(rows)
     K = np.zeros((30 + n, 30 + n))
     K[:30, :30] = M
     K[:30, 30:] = -J[rows].T
     K[30:, :30] = J[rows]
+    return K
+
+
+def kkt_reference(M, C, J, Jpqp, vhat, tau30, mode, kv):
+    """[M -J_S'; J_S 0] [a; lam_S] = [tau30 - C; -(Jpqp_S + kv J_S vhat)] solved in double and refined against its long-double residual
+    until the correction stalls -> (a, lam [12], cond of the KKT matrix)."""
+    rows = list(RIGID_ROWS[int(mode) & 3])
+    K = kkt_matrix(M, J, mode)
     rhs = np.concatenate([tau30 - C, -(Jpqp[rows] + kv * (J[rows] @ vhat))])
     Kl, rl = K.astype(np.longdouble), rhs.astype(np.longdouble)
     x = np.linalg.solve(K, rhs).astype(np.longdouble)

@@ -66,18 +66,18 @@ def servo_steps(o, x, tau30, rec, sp, n, planes=None):
     return x, regimes
 
 
-def _attempt(o, S, i, a):
+def _attempt(o, S, i, a, planes=None):
     """One draw of robot i and its reference, or None where a condition fails: the 20-substep reference is finite; the start state moved
     by 1e-12 relative moves the end state by less than 1e-9 relative; both runs give every vertex the same regime at all 80 evaluations
-    and no regime is undecided."""
+    and no regime is undecided.  planes (a ground record [8], optional): the same draw and conditions on that ground."""
     q, v, tau = S["q"][i], S["v"][i], S["tau"][i]
     rec, sp = draw(o, q, v, i, a)
     x0 = np.concatenate([q, v])
-    ref, regimes = servo_steps(o, x0, tau, rec, sp, N_SUB)
+    ref, regimes = servo_steps(o, x0, tau, rec, sp, N_SUB, planes=planes)
     if not np.isfinite(ref).all() or any("?" in r for r in regimes):
         return None
     sign = np.where(np.random.default_rng([SERVO_SEED, i, a, 1]).integers(0, 2, 60) == 1, 1.0, -1.0)
-    moved, regimes_moved = servo_steps(o, x0 * (1.0 + PERTURB * sign), tau, rec, sp, N_SUB)
+    moved, regimes_moved = servo_steps(o, x0 * (1.0 + PERTURB * sign), tau, rec, sp, N_SUB, planes=planes)
     sens = float(np.abs(moved - ref).max() / np.abs(ref).max())
     if not np.isfinite(moved).all() or not sens < SENSITIVITY or regimes_moved != regimes:
         return None

@@ -43,10 +43,14 @@ def _flag_margins(lam, rows, mu=rc.MU):
     return pull, slip
 
 
-def _derivative_against(terms_of, tag):
-    """Tests 1 and 2: modes mixed over the batch (mode[i] = (i + s) % 3, s = 0, 1, 2), kv 0 and 50, against the statement on terms_of(i)."""
+def _derivative_against(terms_of, tag, S=None, decided=None):
+    """Tests 1 and 2: modes mixed over the batch (mode[i] = (i + s) % 3, s = 0, 1, 2), kv 0 and 50, against the statement on terms_of(i).
+    S: the states (q, v, tau, zcom and the oracle's terms for X_0; rigid_cases.rigid_cases() by default); decided(lam, rows, bounds) ->
+    (pull, slip): which flags the statement's multiplier decides (by 1e-9 N by default).  test_gpu_fall_rigid.py runs the same checks on
+    the states of a fall.  -> (worst figures, flag decisions not compared)."""
     from linearmpchumanoid_amd import capi
-    S = rc.rigid_cases()
+    S = rc.rigid_cases() if S is None else S
+    decided = (lambda lam, rows, b: _flag_margins(lam, rows)) if decided is None else decided
     ctl = make_controller(B, DT, TH, S["zcom"])
     q, v, tau = _inputs(ctl, S)
     xd_plain, _, _ = ctl.plant_derivative(q, v, tau)
@@ -71,7 +75,7 @@ def _derivative_against(terms_of, tag):
                 assert np.isfinite(xdot[i]).all() and not lam[i][free].any(), (tag, s, kv, i)
                 assert b["backward"] <= 1e-12 and b["constraint"] <= 1e-12 and b["forward"] <= 1e-12, (tag, s, kv, i, b)
                 assert not flags[i] & (capi.FLAG_NOT_SPD | capi.FLAG_NONFINITE), (tag, s, kv, i, flags[i])
-                pull, slip = _flag_margins(lam_s, info["rows"])
+                pull, slip = decided(lam_s, info["rows"], b)
                 undecided += (not pull) + (not slip)
                 if pull:
                     assert (flags[i] & capi.FLAG_CONTACT_PULL) == (flags_s & capi.FLAG_CONTACT_PULL), (tag, s, kv, i)
@@ -80,6 +84,7 @@ def _derivative_against(terms_of, tag):
     print("\nrigid derivative vs the statement on %s: backward %.2e, constraint %.2e, forward/cond %.2e (flags not compared: %d)"
           % (tag, worst["backward"], worst["constraint"], worst["forward"], undecided))
     assert undecided <= 8                                          # the margins leave the comparison its cases
+    return worst, undecided
 
 
 def test_derivative_against_the_statement_on_the_oracles_terms():

@@ -2,7 +2,9 @@
 the 16 states of plant_step_cases.contact_states() x three support modes x kv in {0, 50}.  Oracle and numpy only.
 
 Tolerances are the project's own (test_gpu_plant_step.py, test_gpu_terms.py): backward error 1e-12, forward error 1e-12 cond(KKT) against
-a long-double-refined KKT solve, the constraint residual 1e-12 on the scale |A| |lam| + |g| of the system it is the residual of."""
+a long-double-refined KKT solve, the constraint residual 1e-12 on the scale |A| |lam| + |g| of the system it is the residual of.
+That the unpivoted Gauss-Jordan meets only positive pivots is checked here near standing (smallest 0.473) and by test_fall_rigid_cases.py
+over the fall bands (smallest 0.399) and the pitch ladder (0.567)."""
 import numpy as np
 
 import plant_step_cases as pc
