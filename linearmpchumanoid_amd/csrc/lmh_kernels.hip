@@ -1376,17 +1376,20 @@ __device__ __forceinline__ double readlane_f64(double v, int src_lane)       // 
 }
 struct ZohExArgs { double *state, *out; int32_t *status; const double *base_wrench; double *log; const double *ref; LmhZohEx ex; int n_ticks, n_substeps; };
 static_assert(sizeof(LmhDevParams) % 8 == 0 && alignof(ZohExArgs) == 8, "ZohExArgs mirrors the kernel arguments behind the parameter block");
+// The arguments of a zero-order-hold kernel, read from the kernel-argument segment where they are used.  A: the kernel's own record or one it
+// continues (ZohExArgs <- ZohBoxArgs | ZohIoArgs <- ZohGroundArgs <- ZohServoArgs): a shorter record names the same words.
+template <class A>
+__device__ __forceinline__ const __attribute__((address_space(4))) A &zoh_args()
+{
+    typedef const __attribute__((address_space(4))) A CA;
+    CA *p_ = (CA *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(LmhDevParams));
+    asm volatile("" : "+s"(p_));
+    return *p_;
+}
 // lmh_rollout_zoh_box_kernel's arguments: lmh_rollout_zoh_ex_kernel's, then what the constrained step takes (lmh_mpc_box_step's box, stride and
 // weights) and where its samples go.  The helper wave reads the second part inside its reference chain, where it is used.
 struct ZohBoxArgs { ZohExArgs a; const double *box; size_t box_stride; double *mpc; double alpha, beta; };
 static_assert(sizeof(ZohExArgs) % 8 == 0 && alignof(ZohBoxArgs) == 8, "ZohBoxArgs continues ZohExArgs in the kernel-argument segment");
-typedef const __attribute__((address_space(4))) ZohBoxArgs CZohBoxArgs;
-__device__ __forceinline__ CZohBoxArgs &zoh_box_args()
-{
-    CZohBoxArgs *p_ = (CZohBoxArgs *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(LmhDevParams));
-    asm volatile("" : "+s"(p_));
-    return *p_;
-}
 #include "lmh_mpc_qp.h"
 // The constrained step's LDS, behind the evaluation's static image (dynamic shared memory of lmh_rollout_zoh_box_kernel alone), sized by the
 // handle's horizon n = N + 1: the packed L | G tile (row stride ldb, odd, >= n + 1), the tile T (row stride ld, odd, >= n), sixteen [n] arrays of
@@ -1415,7 +1418,7 @@ __device__ __forceinline__ void zoh_box_setup(LmhCParams &P, int inst)
     if (lane < n - 1) A.pt[lane] = e;                              // pt[m], m <= N - 1, is all that is read
     if (lane == 0) A.pt[n - 1] = 0.0;
     WSYNC();
-    pv_form_h(A.H, A.ldb, A.pt, D, zoh_box_args().alpha, zoh_box_args().beta, n, lane);
+    pv_form_h(A.H, A.ldb, A.pt, D, zoh_args<ZohBoxArgs>().alpha, zoh_args<ZohBoxArgs>().beta, n, lane);
     const bool spd = pv_factor<true>(A.H, A.ldb, n, lane);
     WSYNC();
     if (lane == 0) { int *w = zoh_box_words(n); w[ZB_SPD] = spd ? 1 : 0; w[ZB_HAVE_G] = 0; w[ZB_FLAGS] = 0; }
@@ -1488,8 +1491,8 @@ __device__ __forceinline__ int refs_chain_a(double *L, LmhCParams &P, int inst, 
         const LipAB M = {P.a00, P.a01, P.a10, P.a11, P.b0, P.b1};
         const size_t ro = (size_t)P.ref_stride * (size_t)inst;
         MpcSample S;
-        const int act = box_tick<true>(A, M, n, P.n_samples, lane, k, flags, L[P_RXS], P.zmpx + ro, P.zmpy + ro, mp + n, mp + 2 * n, mp[3 * n + 1], zoh_box_args().beta,
-                                       zoh_box_args().box + zoh_box_args().box_stride * (size_t)inst, spd, have_g, cxp, vxp, cyp, vyp, S);
+        const int act = box_tick<true>(A, M, n, P.n_samples, lane, k, flags, L[P_RXS], P.zmpx + ro, P.zmpy + ro, mp + n, mp + 2 * n, mp[3 * n + 1], zoh_args<ZohBoxArgs>().beta,
+                                       zoh_args<ZohBoxArgs>().box + zoh_args<ZohBoxArgs>().box_stride * (size_t)inst, spd, have_g, cxp, vxp, cyp, vyp, S);
         if (lane == 0) { bwd[ZB_HAVE_G] = have_g ? 1 : 0; bwd[ZB_FLAGS] = S.flags; }
         if (ref) {
             double *rec = const_cast<double *>(ref);
@@ -3687,7 +3690,7 @@ __device__ __forceinline__ void store_out(const double *L, double *out, bool kee
     if (LANE_IS(lane >= 40 && lane < 46)) out[72 + lane - 40] = L[P_MPC + 2 + lane - 40];    // Mpc3dLip::getXRef | getYRef
 }
 
-// What a launch of the NW-wave evaluation schedule does before its first controller_eval (lmh_eval_kernel, lmh_rollout_zoh_kernel): wave 0
+// What a launch of the NW-wave evaluation schedule does before its first controller_eval (lmh_eval_kernel, the zero-order-hold kernels): wave 0
 // brings the per-launch tables and the robot's state record q | v | v_prev | t into the image `L`, the waves join, and wave 0 takes the
 // priority (see lmh_rollout_kernel).  Returns the free-set guess F: the complement of the ACTIVE mask the last launch left in status[3], or all
 // ones without warm start (valid on wave 0; the helper wave's copy is never read).
@@ -4869,159 +4872,26 @@ __device__ __forceinline__ int plant_derivative(double *L, LmhCParams &P, const 
     phase_outputs_qdd(L, PL_AP);
     return flags;
 }
-// n_substeps x rk4Step (rk4.hpp:5-18) with the torques held: `x` (lane i < 60 = component i of q | v, as in the rollout's rk4_stage) comes in
-// and goes out in a register, L[P_Q], L[P_V] carry each stage's state (and are left at the last stage's, not at x: a caller that wants x in
-// LDS writes it), `flags` collects plant_derivative's and LMH_FLAG_NONFINITE of x behind every substep.  Wave-scope fences only; no clock:
-// the callers advance theirs by n_substeps additions of dt (lmh_plant_kernel<PM_STEP>; wave 0 of lmh_rollout_zoh_kernel)
-template <bool GROUND = false, bool SERVO = false>
-__device__ __forceinline__ void plant_hold(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau, double dt, int n_substeps, double &x, int &flags, const double *gnd = nullptr,
-                                           const ServoLane *servo = nullptr)
+// what a derivative call leaves: xdot = [v | a] of the state in L (lane i < 60 = component i) -> xd + 60 * robot; LMH_FLAG_NONFINITE of it -> flags
+__device__ __forceinline__ void plant_store_xdot(double *L, double *xdot, int inst, int lane, int &flags)
+{
+    double x = 0.0, xd = 0.0, xs = 0.0;
+    rk4_stage<0>(L, 0, lane, 0.0, P_SC + 52, x, xd, xs);           // the first stage leaves xdot itself in its sum: fma(1, xdot, 0 * 0)
+    if (__ballot(lane < 60 && !(fabs(xd) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
+    if (lane < 60) xdot[60 * (size_t)inst + lane] = xd;
+}
+// what a step call leaves in the robot's state record: q | v from x and the clock t advanced by n_substeps additions of dt
+__device__ __forceinline__ void plant_store_state(double *st, int lane, double x, double t, double dt, int n_substeps)
 {
 #pragma unroll 1
-    for (int sub = 0; sub < n_substeps; sub++) {
-        double ksum = 0.0, xs = x;
-#pragma unroll 1
-        for (int stage = 0; stage < 4; stage++) {
-            WSYNC();
-            if (lane < 60) L[P_Q + lane] = xs;                     // q | v are one run
-            WSYNC();
-            if constexpr (SERVO) flags |= plant_derivative<GROUND, true>(L, P, ibp, lane, tau, gnd, servo);
-            else
-            flags |= plant_derivative<GROUND>(L, P, ibp, lane, tau, gnd);
-            rk4_stage<0>(L, stage, lane, dt, P_SC + 52, x, ksum, xs);
-        }
-        if (__ballot(lane < 60 && !(fabs(x) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
-    }
+    for (int sub = 0; sub < n_substeps; sub++) t += dt;            // Clock::step, Clock.hpp:11
+    if (lane < 60) st[lane] = x; else if (lane == 60) st[90] = t;
 }
 __device__ __forceinline__ void plant_store_contact(const double *L, double *o, int lane)
 {
     const int e = (lane >= 12 && lane < 36) ? lane - 12 : 0;
     const double w = L[PL_DW + ((lane < 12) ? lane : 0)], f = L[PL_VF + 6 * (e / 3) + 3 + e % 3];
     if (lane < LMH_CONTACT_STRIDE) o[lane] = (lane < 12) ? w : (lane < 36) ? f : 0.0;
-}
-
-template <int MODE>
-__global__ void __launch_bounds__(64) lmh_plant_kernel(LmhDevParams P_arg, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact,
-                                                       int32_t *flags_out, int n_substeps)
-{
-    LmhCParams &P0 = LMH_KERNARG_PARAMS();
-    __shared__ double L[LDS_DOUBLES];
-    const int inst = blockIdx.x;
-    if (inst >= P0.n_instances) return;
-    LmhCParams &P = *params_of_robot(&P0, inst);
-    const int lane = LANE;
-    SET_GDBG(nullptr);
-    load_common(L, P, inst);
-    if constexpr (MODE == PM_CONTACT) {
-        load_qv(L, q, v, inst, lane, true);
-        WSYNC();
-        phase_fk<double>(L, P.lcoef);
-        phase_com_x<1, double>(L, 0);
-        phase_jacobian<double>(L);
-        plant_contact(L, P, lane);
-        plant_store_contact(L, contact + (size_t)LMH_CONTACT_STRIDE * inst, lane);
-    } else {
-        const IbPack ibp = ib_pack();
-        const double tau = (tau30 && lane < 30) ? tau30[30 * (size_t)inst + lane] : 0.0;
-        int flags = 0;
-        if constexpr (MODE == PM_DERIV) {
-            load_qv(L, q, v, inst, lane, false);                   // (plant_derivative sets P_VP itself)
-            WSYNC();
-            flags |= plant_derivative(L, P, ibp, lane, tau);
-            double x = 0.0, xd = 0.0, xs = 0.0;
-            rk4_stage<0>(L, 0, lane, 0.0, P_SC + 52, x, xd, xs);   // the first stage leaves xdot itself in its sum: fma(1, xdot, 0 * 0)
-            if (__ballot(lane < 60 && !(fabs(xd) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
-            if (lane < 60) xdot[60 * (size_t)inst + lane] = xd;
-            if (contact) plant_store_contact(L, contact + (size_t)LMH_CONTACT_STRIDE * inst, lane);
-        } else {
-            double *st = state + (size_t)LMH_STATE_STRIDE * inst;
-            double x = (lane < 60) ? st[lane] : 0.0, t = st[90];
-            const double dt = P.dt;
-            plant_hold(L, P, ibp, lane, tau, dt, n_substeps, x, flags);
-#pragma unroll 1
-            for (int sub = 0; sub < n_substeps; sub++) t += dt;    // Clock::step, Clock.hpp:11
-            if (lane < 60) st[lane] = x; else if (lane == 60) st[90] = t;
-        }
-        if (lane == 0 && flags_out) flags_out[inst] = flags;
-    }
-}
-// TWIN of lmh_plant_kernel, statement for statement, on a handle with a ground table (lmh_set_ground): `ground` + ground_stride * robot is the
-// robot's record (stride 0: one shared record).  A kernel of its own so that the one above keeps its text, and with it its code: a fix to
-// either belongs in both.
-template <int MODE>
-__global__ void __launch_bounds__(64) lmh_plant_ground_kernel(LmhDevParams P_arg, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact,
-                                                              int32_t *flags_out, int n_substeps, const double *ground, size_t ground_stride)
-{
-    LmhCParams &P0 = LMH_KERNARG_PARAMS();
-    __shared__ double L[LDS_DOUBLES];
-    const int inst = blockIdx.x;
-    if (inst >= P0.n_instances) return;
-    LmhCParams &P = *params_of_robot(&P0, inst);
-    const double *gnd = ground + ground_stride * (size_t)inst;
-    const int lane = LANE;
-    SET_GDBG(nullptr);
-    load_common(L, P, inst);
-    if constexpr (MODE == PM_CONTACT) {
-        load_qv(L, q, v, inst, lane, true);
-        WSYNC();
-        phase_fk<double>(L, P.lcoef);
-        phase_com_x<1, double>(L, 0);
-        phase_jacobian<double>(L);
-        plant_contact<true>(L, P, lane, gnd);
-        plant_store_contact(L, contact + (size_t)LMH_CONTACT_STRIDE * inst, lane);
-    } else {
-        const IbPack ibp = ib_pack();
-        const double tau = (tau30 && lane < 30) ? tau30[30 * (size_t)inst + lane] : 0.0;
-        int flags = 0;
-        if constexpr (MODE == PM_DERIV) {
-            load_qv(L, q, v, inst, lane, false);                   // (plant_derivative sets P_VP itself)
-            WSYNC();
-            flags |= plant_derivative<true>(L, P, ibp, lane, tau, gnd);
-            double x = 0.0, xd = 0.0, xs = 0.0;
-            rk4_stage<0>(L, 0, lane, 0.0, P_SC + 52, x, xd, xs);   // the first stage leaves xdot itself in its sum: fma(1, xdot, 0 * 0)
-            if (__ballot(lane < 60 && !(fabs(xd) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
-            if (lane < 60) xdot[60 * (size_t)inst + lane] = xd;
-            if (contact) plant_store_contact(L, contact + (size_t)LMH_CONTACT_STRIDE * inst, lane);
-        } else {
-            double *st = state + (size_t)LMH_STATE_STRIDE * inst;
-            double x = (lane < 60) ? st[lane] : 0.0, t = st[90];
-            const double dt = P.dt;
-            plant_hold<true>(L, P, ibp, lane, tau, dt, n_substeps, x, flags, gnd);
-#pragma unroll 1
-            for (int sub = 0; sub < n_substeps; sub++) t += dt;    // Clock::step, Clock.hpp:11
-            if (lane < 60) st[lane] = x; else if (lane == 60) st[90] = t;
-        }
-        if (lane == 0 && flags_out) flags_out[inst] = flags;
-    }
-}
-// lmh_plant_step_servo (include/lmh.h): lmh_plant_kernel<PM_STEP>'s statements (lmh_plant_ground_kernel<PM_STEP>'s with GROUND) with the SERVO
-// hold: `servo` + servo_stride * robot is the robot's gain record (NULL: zero gains; stride 0: one shared record), `setpoint` + 48 * robot its
-// setpoint, both loaded once by the lanes that own the joints.  Kernels of their own: the two above keep their text, and with it their code.
-template <bool GROUND>
-__global__ void __launch_bounds__(64) lmh_plant_servo_kernel(LmhDevParams P_arg, const double *tau30, double *state, int32_t *flags_out, int n_substeps, const double *servo,
-                                                             size_t servo_stride, const double *setpoint, const double *ground, size_t ground_stride)
-{
-    LmhCParams &P0 = LMH_KERNARG_PARAMS();
-    __shared__ double L[LDS_DOUBLES];
-    const int inst = blockIdx.x;
-    if (inst >= P0.n_instances) return;
-    LmhCParams &P = *params_of_robot(&P0, inst);
-    const double *gnd = GROUND ? ground + ground_stride * (size_t)inst : nullptr;
-    const int lane = LANE;
-    SET_GDBG(nullptr);
-    load_common(L, P, inst);
-    const IbPack ibp = ib_pack();
-    const double tau = (tau30 && lane < 30) ? tau30[30 * (size_t)inst + lane] : 0.0;
-    const ServoLane S = servo_lane(servo ? servo + servo_stride * (size_t)inst : nullptr, setpoint + (size_t)LMH_SETPOINT_STRIDE * inst, lane);
-    int flags = 0;
-    double *st = state + (size_t)LMH_STATE_STRIDE * inst;
-    double x = (lane < 60) ? st[lane] : 0.0, t = st[90];
-    const double dt = P.dt;
-    plant_hold<GROUND, true>(L, P, ibp, lane, tau, dt, n_substeps, x, flags, gnd, &S);
-#pragma unroll 1
-    for (int sub = 0; sub < n_substeps; sub++) t += dt;            // Clock::step, Clock.hpp:11
-    if (lane < 60) st[lane] = x; else if (lane == 60) st[90] = t;
-    if (lane == 0 && flags_out) flags_out[inst] = flags;
 }
 // ============================================================================ rigid-contact plant: constrained forward dynamics with held soles
 // lmh_plant_derivative_rigid / lmh_plant_step_rigid (include/lmh.h): the held soles are kinematic constraints and the contact wrench is their
@@ -5230,58 +5100,99 @@ __device__ __forceinline__ int plant_derivative_rigid(double *L, LmhCParams &P, 
     phase_outputs_qdd(L, PL_AP);
     return flags;
 }
-// lmh_plant_kernel's PM_DERIV and PM_STEP with the rigid derivative; `lambda` (may be NULL): the multiplier of the derivative call, of the
-// first stage of the last substep for the step
-template <int MODE>
-__global__ void __launch_bounds__(64) lmh_plant_rigid_kernel(LmhDevParams P_arg, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *lambda,
-                                                             int32_t *flags_out, int n_substeps, const int32_t *mode, double kv)
+// ============================================================================ the hold and the plant kernel: every call of either plant
+// what the RIGID hold takes in place of a ground and a servo: live and kv as in plant_derivative_rigid; lam: lane i < 12 leaves with entry i of
+// the multiplier of the first stage of the last substep
+struct RigidHold { unsigned live; double kv, lam; };
+// n_substeps x rk4Step (rk4.hpp:5-18) with the torques held: `x` (lane i < 60 = component i of q | v, as in the rollout's rk4_stage) comes in
+// and goes out in a register, L[P_Q], L[P_V] carry each stage's state (and are left at the last stage's, not at x: a caller that wants x in
+// LDS writes it), `flags` collects the derivative's and LMH_FLAG_NONFINITE of x behind every substep.  Wave-scope fences only; no clock:
+// the callers advance theirs by n_substeps additions of dt (plant_store_state; wave 0 of the zero-order-hold kernels).
+// The derivative is plant_derivative<GROUND, SERVO> (gnd is read with GROUND only, servo with SERVO only) or, with RIGID, plant_derivative_rigid.
+template <bool GROUND = false, bool SERVO = false, bool RIGID = false>
+__device__ __forceinline__ void plant_hold(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau, double dt, int n_substeps, double &x, int &flags, const double *gnd = nullptr,
+                                           const ServoLane *servo = nullptr, RigidHold *rigid = nullptr)
 {
-    static_assert(MODE == PM_DERIV || MODE == PM_STEP, "derivative | RK4 step");
+    static_assert(!(RIGID && (GROUND || SERVO)), "the rigid plant has no ground table and no servo");
+#pragma unroll 1
+    for (int sub = 0; sub < n_substeps; sub++) {
+        double ksum = 0.0, xs = x;
+#pragma unroll 1
+        for (int stage = 0; stage < 4; stage++) {
+            WSYNC();
+            if (lane < 60) L[P_Q + lane] = xs;                     // q | v are one run
+            WSYNC();
+            if constexpr (RIGID) {
+                flags |= plant_derivative_rigid(L, P, ibp, lane, tau, rigid->live, rigid->kv);
+                if (stage == 0) rigid->lam = L[RG_LAM + ((lane < 12) ? lane : 0)];
+            } else flags |= plant_derivative<GROUND, SERVO>(L, P, ibp, lane, tau, gnd, servo);
+            rk4_stage<0>(L, stage, lane, dt, P_SC + 52, x, ksum, xs);
+        }
+        if (__ballot(lane < 60 && !(fabs(x) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
+    }
+}
+// lmh_launch_plant's arguments behind the parameter block; an instantiation reads the words of its own options and no others.
+//   ground   (GROUND: a handle with a ground table, lmh_set_ground) ground + ground_stride * robot is the robot's record (stride 0: one shared record)
+//   servo    (SERVO: lmh_plant_step_servo) servo + servo_stride * robot is the robot's gain record (NULL: zero gains; stride 0: one shared record),
+//            setpoint + LMH_SETPOINT_STRIDE * robot its setpoint, both loaded once by the lanes that own the joints
+//   hold     (RIGID: lmh_plant_derivative_rigid, lmh_plant_step_rigid) [n_instances] support modes, NULL = both soles held; kv as in
+//            plant_derivative_rigid; lambda (may be NULL) [n_instances][12]: the multiplier of the derivative call, of the first stage of the
+//            last substep for the step
+struct PlantArgs { const double *q, *v, *tau30; double *state, *xdot, *contact; int32_t *flags; int n_substeps; const double *ground; size_t ground_stride;
+                   const double *servo; size_t servo_stride; const double *setpoint; const int32_t *hold; double kv; double *lambda; };
+// MODE: PM_CONTACT | PM_DERIV | PM_STEP.  GROUND, SERVO: the options of the compliant plant (plant_derivative); RIGID: the rigid-contact plant
+// (plant_derivative_rigid) in its place, which reads no ground table and no servo table.
+template <int MODE, bool GROUND = false, bool SERVO = false, bool RIGID = false>
+__global__ void __launch_bounds__(64) lmh_plant_kernel(LmhDevParams P_arg, PlantArgs A)
+{
+    static_assert(MODE == PM_CONTACT || MODE == PM_DERIV || MODE == PM_STEP, "contact wrench | derivative | RK4 step");
+    static_assert(!SERVO || MODE == PM_STEP, "the servo lives inside a hold");
+    static_assert(!RIGID || MODE != PM_CONTACT, "the rigid plant's wrench is its multiplier: derivative | RK4 step");
+    static_assert(!(RIGID && (GROUND || SERVO)), "the rigid plant has no ground table and no servo");
     LmhCParams &P0 = LMH_KERNARG_PARAMS();
     __shared__ double L[LDS_DOUBLES];
     const int inst = blockIdx.x;
     if (inst >= P0.n_instances) return;
     LmhCParams &P = *params_of_robot(&P0, inst);
+    const double *gnd = nullptr;
+    if constexpr (GROUND) gnd = A.ground + A.ground_stride * (size_t)inst;
     const int lane = LANE;
     SET_GDBG(nullptr);
     load_common(L, P, inst);
-    const IbPack ibp = ib_pack();
-    const double tau = (tau30 && lane < 30) ? tau30[30 * (size_t)inst + lane] : 0.0;
-    const unsigned live = (unsigned)__builtin_amdgcn_readfirstlane((int)rigid_live(mode ? mode[inst] : (int)LMH_PHASE_DOUBLE));      // (one word per robot: wave-uniform)
-    int flags = 0;
-    if constexpr (MODE == PM_DERIV) {
-        load_qv(L, q, v, inst, lane, false);                       // (plant_derivative_rigid sets P_VP itself)
+    if constexpr (MODE == PM_CONTACT) {
+        load_qv(L, A.q, A.v, inst, lane, true);
         WSYNC();
-        flags |= plant_derivative_rigid(L, P, ibp, lane, tau, live, kv);
-        double x = 0.0, xd = 0.0, xs = 0.0;
-        rk4_stage<0>(L, 0, lane, 0.0, P_SC + 52, x, xd, xs);       // the first stage leaves xdot itself in its sum: fma(1, xdot, 0 * 0)
-        if (__ballot(lane < 60 && !(fabs(xd) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
-        if (lane < 60) xdot[60 * (size_t)inst + lane] = xd;
-        if (lambda && lane < 12) lambda[12 * (size_t)inst + lane] = L[RG_LAM + lane];
+        phase_fk<double>(L, P.lcoef);
+        phase_com_x<1, double>(L, 0);
+        phase_jacobian<double>(L);
+        plant_contact<GROUND>(L, P, lane, gnd);
+        plant_store_contact(L, A.contact + (size_t)LMH_CONTACT_STRIDE * inst, lane);
     } else {
-        double *st = state + (size_t)LMH_STATE_STRIDE * inst;
-        double x = (lane < 60) ? st[lane] : 0.0, t = st[90], lam = 0.0;
-        const double dt = P.dt;
-#pragma unroll 1
-        for (int sub = 0; sub < n_substeps; sub++) {               // plant_hold's loop around the rigid derivative
-            double ksum = 0.0, xs = x;
-#pragma unroll 1
-            for (int stage = 0; stage < 4; stage++) {
-                WSYNC();
-                if (lane < 60) L[P_Q + lane] = xs;                 // q | v are one run
-                WSYNC();
-                flags |= plant_derivative_rigid(L, P, ibp, lane, tau, live, kv);
-                if (stage == 0) lam = L[RG_LAM + ((lane < 12) ? lane : 0)];
-                rk4_stage<0>(L, stage, lane, dt, P_SC + 52, x, ksum, xs);
-            }
-            if (__ballot(lane < 60 && !(fabs(x) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
+        const IbPack ibp = ib_pack();
+        const double tau = (A.tau30 && lane < 30) ? A.tau30[30 * (size_t)inst + lane] : 0.0;
+        ServoLane S = {0.0, 0.0, 0.0, 0.0};
+        if constexpr (SERVO) S = servo_lane(A.servo ? A.servo + A.servo_stride * (size_t)inst : nullptr, A.setpoint + (size_t)LMH_SETPOINT_STRIDE * inst, lane);
+        RigidHold R = {0u, 0.0, 0.0};
+        if constexpr (RIGID) { R.live = (unsigned)__builtin_amdgcn_readfirstlane((int)rigid_live(A.hold ? A.hold[inst] : (int)LMH_PHASE_DOUBLE)); R.kv = A.kv; }      // (one word per robot: wave-uniform)
+        int flags = 0;
+        if constexpr (MODE == PM_DERIV) {
+            load_qv(L, A.q, A.v, inst, lane, false);               // (the derivative sets P_VP itself)
+            WSYNC();
+            if constexpr (RIGID) flags |= plant_derivative_rigid(L, P, ibp, lane, tau, R.live, R.kv);
+            else flags |= plant_derivative<GROUND>(L, P, ibp, lane, tau, gnd);
+            plant_store_xdot(L, A.xdot, inst, lane, flags);
+            if constexpr (RIGID) { if (A.lambda && lane < 12) A.lambda[12 * (size_t)inst + lane] = L[RG_LAM + lane]; }
+            else if (A.contact) plant_store_contact(L, A.contact + (size_t)LMH_CONTACT_STRIDE * inst, lane);
+        } else {
+            double *st = A.state + (size_t)LMH_STATE_STRIDE * inst;
+            double x = (lane < 60) ? st[lane] : 0.0, t = st[90];
+            const double dt = P.dt;
+            plant_hold<GROUND, SERVO, RIGID>(L, P, ibp, lane, tau, dt, A.n_substeps, x, flags, gnd, &S, &R);
+            plant_store_state(st, lane, x, t, dt, A.n_substeps);
+            if constexpr (RIGID) { if (A.lambda && lane < 12) A.lambda[12 * (size_t)inst + lane] = R.lam; }
         }
-#pragma unroll 1
-        for (int sub = 0; sub < n_substeps; sub++) t += dt;        // Clock::step, Clock.hpp:11
-        if (lane < 60) st[lane] = x; else if (lane == 60) st[90] = t;
-        if (lambda && lane < 12) lambda[12 * (size_t)inst + lane] = lam;
+        if (lane == 0 && A.flags) A.flags[inst] = flags;
     }
-    if (lane == 0 && flags_out) flags_out[inst] = flags;
 }
 #ifndef LMH_ROLLOUT_ONLY
 extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *q, const double *v, const double *x, const double *w, double *res, int32_t *flags, hipStream_t s)
@@ -5295,117 +5206,25 @@ extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *
                                  int n_substeps, const double *ground, size_t ground_stride, const double *servo, size_t servo_stride, const double *setpoint, const int32_t *hold, double kv,
                                  double *lambda, hipStream_t s)
 {
-    const dim3 grid(P->n_instances), block(64);
-    if (mode == PM_RIGID_DERIV || mode == PM_RIGID_STEP) {         // lmh_plant_derivative_rigid / lmh_plant_step_rigid: no ground, no servo, whatever the handle carries
-        if (mode == PM_RIGID_DERIV) hipLaunchKernelGGL(lmh_plant_rigid_kernel<PM_DERIV>, grid, block, 0, s, *P, q, v, tau30, state, xdot, lambda, flags, n_substeps, hold, kv);
-        else hipLaunchKernelGGL(lmh_plant_rigid_kernel<PM_STEP>, grid, block, 0, s, *P, q, v, tau30, state, xdot, lambda, flags, n_substeps, hold, kv);
-        return;
-    }
-    if (setpoint) {                                                // lmh_plant_step_servo (PM_STEP only; servo NULL: zero gains); without one the kernels of before
-        if (ground) hipLaunchKernelGGL(lmh_plant_servo_kernel<true>, grid, block, 0, s, *P, tau30, state, flags, n_substeps, servo, servo_stride, setpoint, ground, ground_stride);
-        else hipLaunchKernelGGL(lmh_plant_servo_kernel<false>, grid, block, 0, s, *P, tau30, state, flags, n_substeps, servo, servo_stride, setpoint, ground, ground_stride);
-        return;
-    }
-    if (ground) {                                                  // a handle with a table: the GROUND instantiations; without one the kernels of before
-        if (mode == PM_CONTACT) hipLaunchKernelGGL(lmh_plant_ground_kernel<PM_CONTACT>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps, ground, ground_stride);
-        else if (mode == PM_DERIV) hipLaunchKernelGGL(lmh_plant_ground_kernel<PM_DERIV>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps, ground, ground_stride);
-        else hipLaunchKernelGGL(lmh_plant_ground_kernel<PM_STEP>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps, ground, ground_stride);
-        return;
-    }
-    if (mode == PM_CONTACT) hipLaunchKernelGGL(lmh_plant_kernel<PM_CONTACT>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps);
-    else if (mode == PM_DERIV) hipLaunchKernelGGL(lmh_plant_kernel<PM_DERIV>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps);
-    else hipLaunchKernelGGL(lmh_plant_kernel<PM_STEP>, grid, block, 0, s, *P, q, v, tau30, state, xdot, contact, flags, n_substeps);
+    // the ten instantiations there are, the compliant ones indexed by [a ground table on the handle].  The rigid calls read no ground and no servo,
+    // whatever the handle carries; a setpoint is lmh_plant_step_servo (PM_STEP only; servo NULL: zero gains)
+    typedef void (*Kernel)(LmhDevParams, PlantArgs);
+    static const Kernel rigid[2] = {lmh_plant_kernel<PM_DERIV, false, false, true>, lmh_plant_kernel<PM_STEP, false, false, true>};
+    static const Kernel with_servo[2] = {lmh_plant_kernel<PM_STEP, false, true>, lmh_plant_kernel<PM_STEP, true, true>};
+    static const Kernel compliant[2][3] = {{lmh_plant_kernel<PM_CONTACT>, lmh_plant_kernel<PM_DERIV>, lmh_plant_kernel<PM_STEP>},
+                                           {lmh_plant_kernel<PM_CONTACT, true>, lmh_plant_kernel<PM_DERIV, true>, lmh_plant_kernel<PM_STEP, true>}};
+    const Kernel kernel = (mode == PM_RIGID_DERIV || mode == PM_RIGID_STEP) ? rigid[mode == PM_RIGID_STEP] :
+                          setpoint ? with_servo[ground != nullptr] : compliant[ground != nullptr][(mode == PM_CONTACT) ? 0 : (mode == PM_DERIV) ? 1 : 2];
+    const PlantArgs a = {q, v, tau30, state, xdot, contact, flags, n_substeps, ground, ground_stride, servo, servo_stride, setpoint, hold, kv, lambda};
+    hipLaunchKernelGGL(kernel, dim3(P->n_instances), dim3(64), 0, s, *P, a);
 }
 
 // ============================================================================ zero-order-hold closed loop: controller and plant rates in one launch
-// lmh_rollout_zoh (include/lmh.h): for every robot exactly what n_ticks rounds of { lmh_eval ; lmh_plant_step(tau30 = [base_wrench | out.tau],
-// n_substeps) } leave, bit for bit, with the robot on chip for the whole launch.  One workgroup per robot; the launch opens with
-// lmh_eval_kernel's eval_begin and runs its two-wave schedule for the evaluation; the hold is plant_hold, the loop lmh_plant_kernel<PM_STEP>
-// calls, on wave 0 (wave-scope fences only) while the helper wave waits at the join that ends the tick, so both waves pass the same number of
-// workgroup barriers.
-// What the separate launches did between two evaluations, and what happens to it here:
-//   v_prev      lmh_eval stores v_prev <- v and lmh_plant_step leaves it alone, but plant_derivative overwrites L[P_VP] with the velocity of
-//               its stage: the v the evaluation saw rides in a register across the hold and goes back to L[P_VP] behind it.
-//   state       wave 0's lanes 0..59 hold q | v during the hold (plant_hold's x), L[P_Q..] holds it across the evaluation, which writes
-//               neither.  The fourth stage's xs is fma(0, xdot, x), not x, when xdot is not finite: x itself is written back.
-//   clock       t += dt once per substep on both waves (wave-uniform, the same fp64 sum as the state record's t through the launches).
-//   warm start  F stays in wave 0's register (the launches carry ~F through status[3]); L[P_KF] is what phase_qp published, which is F.
-//   LDS words   per-launch tables (P_MODEL, P_GCOL.., P_MPCK, P_PRE + 2..3, P_RXS): read-only after load_common, the hold writes none.
-//               Reference cache (P_RK, P_RPH, P_RT0, P_PRE + 0..1, P_POLY): the hold reads and writes none of it and every entry is a pure
-//               function of the preview index k, so a hit returns the bits a fresh launch would form again: it survives.
-//               K_f^-1 cache (P_KI, P_KF + 1..2): P_KI is outside the scratch the hold uses (kinv_compute's own scratch, A_XR, is not:
-//               it is recomputed whenever it is needed) and the stored inverse is a pure function of the free set and the robot's friction
-//               table: it survives.  P_ORI is read by the rollout kernel's pipelined evaluation only: cleared once.
-//               Everything else an evaluation reads it has written itself (lmh_eval_kernel starts from an LDS image nobody initialised).
-// REF (lmh_rollout_zoh_ref_kernel): `ref` [n_ticks][B][LMH_MPC_STRIDE], record `tick` of the robot is the CoM reference of that tick's evaluation;
-// the helper wave, which runs chain A, reads it from global memory inside the chain (refs_chain_a): no broadcast, no further join.
-// TWIN: lmh_rollout_zoh_ex_body below repeats these statements (evaluation, log, hold, write-back, final store) with the options of
-// lmh_rollout_zoh_ex between them: a fix to the loop here belongs there too.
-template <bool REF>
-__device__ __forceinline__ void lmh_rollout_zoh_body(double *L, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps)
-{
-    LmhCParams &P0 = LMH_KERNARG_PARAMS();
-    const int inst = blockIdx.x;
-    if (inst >= P0.n_instances) return;
-    LmhCParams &P = *params_of_robot(&P0, inst);
-    const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    double *st = state + (size_t)LMH_STATE_STRIDE * inst;
-    double t = st[90];
-    SET_GDBG(nullptr);
-    double bw = 0.0;                                               // lane i < 6: the wrench on the base, held for the launch
-    if (wid == 0 && base_wrench && LANE < 6) bw = base_wrench[6 * (size_t)inst + LANE];
-    unsigned F = eval_begin<2>(L, P, inst, st, status, wid);
-    const double dt = P.dt;
-    int k = 0, itmax = 0, flags = 0;
-#pragma unroll 1
-    for (int tick = 0; tick < n_ticks; tick++) {
-        int iters = 0;
-        flags |= controller_eval<2, double, false, false, NoWindow, false, REF>(L, P, inst, t, wid, &F, &k, &iters, nullptr, true, NoWindow(), nullptr, nullptr,
-                                                                                REF ? ref + ((size_t)tick * P0.n_instances + inst) * LMH_MPC_STRIDE : nullptr);
-        itmax = (iters > itmax) ? iters : itmax;
-        bsync<2>();                                                // torques of the helper wave
-        if (wid == 0) {
-            const int lane = LANE;
-            // the record of the launch's last evaluation leaves before the hold overwrites the accelerations and the CoM
-            if (tick == n_ticks - 1) store_out(L, out + (size_t)LMH_OUT_STRIDE * inst);
-            if (log) {
-                double *lg = log + ((size_t)tick * P0.n_instances + inst) * 36;
-                if (lane < 24) lg[lane] = L[P_TAU + lane]; else if (lane < 36) lg[lane] = L[P_W12 + lane - 24];
-            }
-            double x = L[P_Q + ((lane < 60) ? lane : 0)];          // q | v are one run
-            const double vp = L[P_V + ((lane < 30) ? lane : 0)];   // Robot::v_ <- dq (controller.cpp:59): what the next evaluation sees
-            const double tau = (lane < 6) ? bw : L[P_TAU + ((lane >= 6 && lane < 30) ? lane - 6 : 0)];         // lane i < 30: tau30[i] = [base wrench | out.tau]
-            plant_hold(L, P, ib_pack(), lane, tau, dt, n_substeps, x, flags);
-            WSYNC();
-            if (lane < 60) L[P_Q + lane] = x;
-            if (lane < 30) L[P_VP + lane] = vp;
-            WSYNC();
-        }
-#pragma unroll 1
-        for (int sub = 0; sub < n_substeps; sub++) t += dt;        // Clock::step, Clock.hpp:11
-        bsync<2>();                                                // the helper wave starts the next evaluation's references on the new state
-    }
-    if (wid == 0) {
-        for (int e = LANE; e < 90; e += 64) st[e] = L[P_Q + e];    // q | v | v_prev
-        if (LANE == 0) { st[90] = t; store_status(status, inst, k, itmax, flags, F); }
-    }
-}
-__global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) lmh_rollout_zoh_kernel(LmhDevParams P_arg, double *state, double *out, int32_t *status, const double *base_wrench, double *log,
-                                                                               int n_ticks, int n_substeps)
-{
-    __shared__ double L[LDS_DOUBLES];
-    lmh_rollout_zoh_body<false>(L, state, out, status, base_wrench, log, nullptr, n_ticks, n_substeps);
-}
-__global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) lmh_rollout_zoh_ref_kernel(LmhDevParams P_arg, double *state, double *out, int32_t *status, const double *base_wrench, double *log,
-                                                                                   const double *ref, int n_ticks, int n_substeps)
-{
-    __shared__ double L[LDS_DOUBLES];
-    lmh_rollout_zoh_body<true>(L, state, out, status, base_wrench, log, ref, n_ticks, n_substeps);
-}
-// ---- lmh_rollout_zoh_ex (include/lmh.h): the loop above with timed pushes, a wrench per control tick, a trace and a metrics record.  A body
-// of its own, lmh_rollout_zoh_body's statements in its order: the two kernels above keep their text, and with it their code.  What is new:
-//   arguments   everything but the parameter block is read from the kernel-argument segment where it is used (ZohExArgs, as lmh_rollout_kernel
-//               reads its own): nothing of it is carried across controller_eval, where the kernels above already spill 74 / 80 scalars.
+// One body, lmh_rollout_zoh_ex_body, for every call of the family; the loop itself is specified in front of it.  lmh_rollout_zoh and
+// lmh_rollout_zoh_ref are lmh_rollout_zoh_ex without an option (an all-zero LmhZohEx).
+// ---- lmh_rollout_zoh_ex (include/lmh.h): the loop with timed pushes, a wrench per control tick, a trace and a metrics record:
+//   arguments   everything but the parameter block is read from the kernel-argument segment where it is used (zoh_args, as lmh_rollout_kernel
+//               reads its own): nothing of it is carried across controller_eval, which leaves no scalar register to spare.
 //   pushes      ticks are plant substeps.  The cursor is the rollout's (P_PUSH: push_seek once, behind eval_begin, whose state load parks t in
 //               the slot; neither the evaluation nor the hold touches it), counted in substeps done, lim = n_ticks * n_substeps: a push on the
 //               substep the launch ends on stays for the next launch.  One due at a control tick's start goes into L[P_V] (not L[P_VP]) before
@@ -5429,7 +5248,7 @@ __device__ __forceinline__ void zoh_trace_state(double *tr, int lane, double x, 
     else if (lane < 42) tr[LMH_STATE_STRIDE + LMH_OUT_STRIDE + lane - 38] = (lane == 38) ? (double)k : (lane == 39) ? (double)itmax : (lane == 40) ? (double)flags : (double)(int32_t)(~F);
 }
 // ---- lmh_rollout_zoh_io (include/lmh.h): the same body with a measurement added to what the evaluation reads and an actuator between the
-// evaluation's torques and the hold (the IO flag of lmh_rollout_zoh_ex_body; two kernels of their own, the three above keep their code).
+// evaluation's torques and the hold (the IO flag of lmh_rollout_zoh_ex_body).
 //   true state  the evaluation reads q | v from L[P_Q ..] and writes none of it, so that is where x + meas goes, at the places the loop
 //               writes x: behind eval_begin for the first tick (under one more join, the one the launch-start push uses) and in the
 //               write-back behind the hold for every later one.  The true x cannot stay in registers across controller_eval (no VGPRs to
@@ -5443,13 +5262,6 @@ __device__ __forceinline__ void zoh_trace_state(double *tr, int lane, double x, 
 //               lmh_rollout_zoh_ex_kernel, six more scalar spill slots, no scratch).  Ordinary vector stores.
 struct ZohIoArgs { ZohExArgs a; LmhZohIo io; };
 static_assert(sizeof(ZohExArgs) % 8 == 0 && alignof(ZohIoArgs) == 8, "ZohIoArgs continues ZohExArgs in the kernel-argument segment");
-typedef const __attribute__((address_space(4))) ZohIoArgs CZohIoArgs;
-__device__ __forceinline__ CZohIoArgs &zoh_io_args()
-{
-    CZohIoArgs *p_ = (CZohIoArgs *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(LmhDevParams));
-    asm volatile("" : "+s"(p_));
-    return *p_;
-}
 // wave 0, x = the true q | v on lanes 0..59: park it in the state record and give the evaluation of control tick `rec` what it measures
 // (rec == n_ticks: there is no such evaluation, the image gets x itself)
 __device__ __forceinline__ void zoh_io_publish(double *L, double *st, int lane, double x, int rec, int inst)
@@ -5457,8 +5269,8 @@ __device__ __forceinline__ void zoh_io_publish(double *L, double *st, int lane, 
     if (lane < 60) {
         st[lane] = x;
         double m = x;
-        if (const double *meas = zoh_io_args().io.meas) {
-            if (rec < zoh_io_args().a.n_ticks) m = x + meas[((size_t)rec * LMH_KERNARG_PARAMS().n_instances + inst) * 60 + lane];
+        if (const double *meas = zoh_args<ZohIoArgs>().io.meas) {
+            if (rec < zoh_args<ZohIoArgs>().a.n_ticks) m = x + meas[((size_t)rec * LMH_KERNARG_PARAMS().n_instances + inst) * 60 + lane];
         }
         L[P_Q + lane] = m;
     }
@@ -5468,10 +5280,10 @@ struct ZohIoJoint { double lim, alpha; int d; };
 __device__ __forceinline__ ZohIoJoint zoh_io_joint(int lane, int inst)
 {
     ZohIoJoint J = {__builtin_inf(), 1.0, 0};
-    if (zoh_io_args().io.actuators) {
-        if (const double *act = zoh_io_args().io.act) {
+    if (zoh_args<ZohIoArgs>().io.actuators) {
+        if (const double *act = zoh_args<ZohIoArgs>().io.act) {
             const int j = (lane >= 6 && lane < 30) ? lane - 6 : 0;
-            const double *rec = act + zoh_io_args().io.act_stride * (size_t)inst;
+            const double *rec = act + zoh_args<ZohIoArgs>().io.act_stride * (size_t)inst;
             J.lim = rec[LMH_ACT_OFF_TAU_MAX + j]; J.alpha = rec[LMH_ACT_OFF_ALPHA + j];
             const int d = __builtin_amdgcn_readfirstlane((int)rec[LMH_ACT_OFF_DELAY]);
             J.d = (d < 0) ? 0 : (d > LMH_ACT_MAX_DELAY) ? LMH_ACT_MAX_DELAY : d;      // (lmh_set_actuators refuses anything else: no index leaves the robot's memory)
@@ -5485,10 +5297,10 @@ __device__ __forceinline__ double zoh_io_actuate(double tau, const ZohIoJoint &J
     const bool jl = lane >= 6 && lane < 30;
     const int j = jl ? lane - 6 : 0;
     double y = tau;
-    if (zoh_io_args().io.actuators) {
+    if (zoh_args<ZohIoArgs>().io.actuators) {
         const double lim = J.lim, alpha = J.alpha;
         const int d = J.d;
-        double *mem = zoh_io_args().io.act_mem + (size_t)LMH_ACT_MEM_STRIDE * inst + j;
+        double *mem = zoh_args<ZohIoArgs>().io.act_mem + (size_t)LMH_ACT_MEM_STRIDE * inst + j;
         double u = tau;
         if (d > 0 && jl) {                                         // the oldest command leaves, the others move up, this tick's joins behind them
             double *qc = mem + 24;
@@ -5510,29 +5322,15 @@ __device__ __forceinline__ double zoh_io_actuate(double tau, const ZohIoJoint &J
             mem[0] = y;
         }
     }
-    if (double *ap = zoh_io_args().io.applied) { if (jl) ap[((size_t)tick * LMH_KERNARG_PARAMS().n_instances + inst) * 24 + j] = y; }
+    if (double *ap = zoh_args<ZohIoArgs>().io.applied) { if (jl) ap[((size_t)tick * LMH_KERNARG_PARAMS().n_instances + inst) * 24 + j] = y; }
     return jl ? y : tau;
 }
 // lmh_rollout_zoh_ground_kernel's arguments: lmh_rollout_zoh_io_kernel's, then the ground table (stride 0: one shared record)
 struct ZohGroundArgs { ZohIoArgs a; const double *ground; size_t ground_stride; };
 static_assert(sizeof(ZohIoArgs) % 8 == 0 && alignof(ZohGroundArgs) == 8, "ZohGroundArgs continues ZohIoArgs in the kernel-argument segment");
-typedef const __attribute__((address_space(4))) ZohGroundArgs CZohGroundArgs;
-__device__ __forceinline__ CZohGroundArgs &zoh_ground_args()
-{
-    CZohGroundArgs *p_ = (CZohGroundArgs *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(LmhDevParams));
-    asm volatile("" : "+s"(p_));
-    return *p_;
-}
 // lmh_rollout_zoh_servo_kernel's arguments: lmh_rollout_zoh_ground_kernel's (ground NULL without a table: the flat hold), then the servo's
 struct ZohServoArgs { ZohGroundArgs a; LmhZohServo sv; };
 static_assert(sizeof(ZohGroundArgs) % 8 == 0 && alignof(ZohServoArgs) == 8, "ZohServoArgs continues ZohGroundArgs in the kernel-argument segment");
-typedef const __attribute__((address_space(4))) ZohServoArgs CZohServoArgs;
-__device__ __forceinline__ CZohServoArgs &zoh_servo_args()
-{
-    CZohServoArgs *p_ = (CZohServoArgs *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(LmhDevParams));
-    asm volatile("" : "+s"(p_));
-    return *p_;
-}
 // wave 0, behind the evaluation of control tick `tick` and in front of its hold: what lanes 6..29 carry through the hold.  The gains are
 // loaded here, once per control tick, and not held across controller_eval (no VGPRs to spare there).  LMH_SERVO_CALLER: record `tick` of the
 // robot.  LMH_SERVO_INTEGRATE: from what the evaluation READ, L[P_Q ..] and L[P_V ..] (the measured words with d_meas), and the joint rows
@@ -5541,10 +5339,10 @@ __device__ __forceinline__ CZohServoArgs &zoh_servo_args()
 // every product and sum rounded by itself (opaque registers between them: no fused multiply-add)
 __device__ __forceinline__ ServoLane zoh_servo_lane(const double *L, int lane, int inst, int tick, int nsub, double dt)
 {
-    const double *servo = zoh_servo_args().sv.servo;
-    const double *rec = servo ? servo + zoh_servo_args().sv.servo_stride * (size_t)inst : nullptr;
-    if (zoh_servo_args().sv.mode == LMH_SERVO_CALLER)
-        return servo_lane(rec, zoh_servo_args().sv.setpoint + ((size_t)tick * LMH_KERNARG_PARAMS().n_instances + inst) * LMH_SETPOINT_STRIDE, lane);
+    const double *servo = zoh_args<ZohServoArgs>().sv.servo;
+    const double *rec = servo ? servo + zoh_args<ZohServoArgs>().sv.servo_stride * (size_t)inst : nullptr;
+    if (zoh_args<ZohServoArgs>().sv.mode == LMH_SERVO_CALLER)
+        return servo_lane(rec, zoh_args<ZohServoArgs>().sv.setpoint + ((size_t)tick * LMH_KERNARG_PARAMS().n_instances + inst) * LMH_SETPOINT_STRIDE, lane);
     ServoLane S = {0.0, 0.0, 0.0, 0.0};
     if (lane >= 6 && lane < 30) {
         if (rec) { S.kp = rec[LMH_SERVO_OFF_KP + lane - 6]; S.kd = rec[LMH_SERVO_OFF_KD + lane - 6]; }
@@ -5563,6 +5361,27 @@ __device__ __forceinline__ ServoLane zoh_servo_lane(const double *L, int lane, i
     }
     return S;
 }
+// The loop.  lmh_rollout_zoh (include/lmh.h): for every robot exactly what n_ticks rounds of { lmh_eval ; lmh_plant_step(tau30 = [base_wrench |
+// out.tau], n_substeps) } leave, bit for bit, with the robot on chip for the whole launch.  One workgroup per robot; the launch opens with
+// lmh_eval_kernel's eval_begin and runs its two-wave schedule for the evaluation; the hold is plant_hold, the loop lmh_plant_kernel<PM_STEP>
+// calls, on wave 0 (wave-scope fences only) while the helper wave waits at the join that ends the tick, so both waves pass the same number of
+// workgroup barriers.
+// What the separate launches did between two evaluations, and what happens to it here:
+//   v_prev      lmh_eval stores v_prev <- v and lmh_plant_step leaves it alone, but plant_derivative overwrites L[P_VP] with the velocity of
+//               its stage: the v the evaluation saw rides in a register across the hold and goes back to L[P_VP] behind it.
+//   state       wave 0's lanes 0..59 hold q | v during the hold (plant_hold's x), L[P_Q..] holds it across the evaluation, which writes
+//               neither.  The fourth stage's xs is fma(0, xdot, x), not x, when xdot is not finite: x itself is written back.
+//   clock       t += dt once per substep on both waves (wave-uniform, the same fp64 sum as the state record's t through the launches).
+//   warm start  F stays in wave 0's register (the launches carry ~F through status[3]); L[P_KF] is what phase_qp published, which is F.
+//   LDS words   per-launch tables (P_MODEL, P_GCOL.., P_MPCK, P_PRE + 2..3, P_RXS): read-only after load_common, the hold writes none.
+//               Reference cache (P_RK, P_RPH, P_RT0, P_PRE + 0..1, P_POLY): the hold reads and writes none of it and every entry is a pure
+//               function of the preview index k, so a hit returns the bits a fresh launch would form again: it survives.
+//               K_f^-1 cache (P_KI, P_KF + 1..2): P_KI is outside the scratch the hold uses (kinv_compute's own scratch, A_XR, is not:
+//               it is recomputed whenever it is needed) and the stored inverse is a pure function of the free set and the robot's friction
+//               table: it survives.  P_ORI is read by the rollout kernel's pipelined evaluation only: cleared once.
+//               Everything else an evaluation reads it has written itself (lmh_eval_kernel starts from an LDS image nobody initialised).
+// REF (lmh_rollout_zoh_ref; MODE ZM_REF): `ref` [n_ticks][B][LMH_MPC_STRIDE], record `tick` of the robot is the CoM reference of that tick's evaluation;
+// the helper wave, which runs chain A, reads it from global memory inside the chain (refs_chain_a): no broadcast, no further join.
 // MODE: where the momentum task's CoM reference comes from.  ZM_BOX (lmh_rollout_zoh_box_kernel): every control tick runs lmh_mpc_box_step at the
 // measured CoM state inside the evaluation's chain A (refs_chain_a); the preview Hessian is factored once, behind eval_begin, by the helper wave
 // alone (wave-scope fences: both waves pass the same joins as in the other modes) while wave 0 goes on to the pushes and the kinematics.
@@ -5581,37 +5400,31 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
     static_assert(IO || !GROUND, "the ground kernels are instantiations of the IO body");
     static_assert(IO || !SERVO, "the servo kernels are instantiations of the IO body");
     LmhCParams &P0 = LMH_KERNARG_PARAMS();
-    typedef const __attribute__((address_space(4))) ZohExArgs CArgs;
-    auto KA = [&]() -> CArgs & {
-        CArgs *p_ = (CArgs *)((const __attribute__((address_space(4))) char *)__builtin_amdgcn_kernarg_segment_ptr() + sizeof(LmhDevParams));
-        asm volatile("" : "+s"(p_));
-        return *p_;
-    };
     const int inst = blockIdx.x;
     if (inst >= P0.n_instances) return;
     LmhCParams &P = *params_of_robot(&P0, inst);
     const int wid = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    double t = KA().state[(size_t)LMH_STATE_STRIDE * inst + 90];
+    double t = zoh_args<ZohExArgs>().state[(size_t)LMH_STATE_STRIDE * inst + 90];
     SET_GDBG(nullptr);
-    unsigned F = eval_begin<2>(L, P, inst, KA().state + (size_t)LMH_STATE_STRIDE * inst, KA().status, wid);
+    unsigned F = eval_begin<2>(L, P, inst, zoh_args<ZohExArgs>().state + (size_t)LMH_STATE_STRIDE * inst, zoh_args<ZohExArgs>().status, wid);
     if constexpr (BOX) { if (wid == 1) zoh_box_setup(P, inst); }
     if constexpr (IO) {                                            // the first evaluation's measurement, behind a push due at the launch's first substep
         if (wid == 0) {
             const int lane = LANE;
             double x = L[P_Q + ((lane < 60) ? lane : 0)];
-            if (KA().ex.pushes) {
-                const int lim = KA().n_ticks * KA().n_substeps;
+            if (zoh_args<ZohExArgs>().ex.pushes) {
+                const int lim = zoh_args<ZohExArgs>().n_ticks * zoh_args<ZohExArgs>().n_substeps;
                 int pc = 0;
                 if (push_seek(L, P, inst, lane, t, lim, &pc) == 0) push_apply(L, P, inst, lane, 0, pc, lim, x);
             }
-            if (KA().n_ticks > 0) zoh_io_publish(L, KA().state + (size_t)LMH_STATE_STRIDE * inst, lane, x, 0, inst);
+            if (zoh_args<ZohExArgs>().n_ticks > 0) zoh_io_publish(L, zoh_args<ZohExArgs>().state + (size_t)LMH_STATE_STRIDE * inst, lane, x, 0, inst);
             WSYNC();
         }
         bsync<2>();
     } else
-    if (KA().ex.pushes) {                                          // (workgroup-uniform: both waves pass the join)
+    if (zoh_args<ZohExArgs>().ex.pushes) {                                          // (workgroup-uniform: both waves pass the join)
         if (wid == 0) {
-            const int lane = LANE, lim = KA().n_ticks * KA().n_substeps;
+            const int lane = LANE, lim = zoh_args<ZohExArgs>().n_ticks * zoh_args<ZohExArgs>().n_substeps;
             int pc = 0;
             if (push_seek(L, P, inst, lane, t, lim, &pc) == 0) {   // due at the launch's first substep: the first evaluation sees it
                 double x = L[P_Q + ((lane < 60) ? lane : 0)];
@@ -5627,45 +5440,45 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
     ZohIoJoint io_joint = {0.0, 0.0, 0};
     if constexpr (IO) { if (wid == 0) io_joint = zoh_io_joint(LANE, inst); }
 #pragma unroll 1
-    for (int tick = 0; tick < KA().n_ticks; tick++) {
+    for (int tick = 0; tick < zoh_args<ZohExArgs>().n_ticks; tick++) {
         int iters = 0;
         if constexpr (BOX) {
-            double *mpc = zoh_box_args().mpc;
+            double *mpc = zoh_args<ZohBoxArgs>().mpc;
             flags |= controller_eval<2, double, false, false, NoWindow, false, true, true>(L, P, inst, t, wid, &F, &k, &iters, nullptr, true, NoWindow(), nullptr, nullptr,
                                                                                            mpc ? mpc + ((size_t)tick * P0.n_instances + inst) * LMH_MPC_STRIDE : nullptr);
         } else
         flags |= controller_eval<2, double, false, false, NoWindow, false, REF>(L, P, inst, t, wid, &F, &k, &iters, nullptr, true, NoWindow(), nullptr, nullptr,
-                                                                                REF ? KA().ref + ((size_t)tick * P0.n_instances + inst) * LMH_MPC_STRIDE : nullptr);
+                                                                                REF ? zoh_args<ZohExArgs>().ref + ((size_t)tick * P0.n_instances + inst) * LMH_MPC_STRIDE : nullptr);
         itmax = (iters > itmax) ? iters : itmax;
         bsync<2>();                                                // torques of the helper wave
-        const int nsub = KA().n_substeps;
+        const int nsub = zoh_args<ZohExArgs>().n_substeps;
 #pragma unroll 1
         for (int sub = 0; sub < nsub; sub++) t += dt;              // Clock::step, Clock.hpp:11: the clock behind this tick's hold
         if (wid == 0) {
             const int lane = LANE, n_inst = P0.n_instances;
             double bw = 0.0;                                       // lane i < 6: the wrench on the base during this hold
-            if (const double *wr = KA().base_wrench) { if (lane < 6) bw = wr[((size_t)(KA().ex.wrench_per_tick ? tick : 0) * n_inst + inst) * 6 + lane]; }
+            if (const double *wr = zoh_args<ZohExArgs>().base_wrench) { if (lane < 6) bw = wr[((size_t)(zoh_args<ZohExArgs>().ex.wrench_per_tick ? tick : 0) * n_inst + inst) * 6 + lane]; }
             // what the evaluation produced leaves before the hold overwrites the accelerations and the CoM
-            if (tick == KA().n_ticks - 1) store_out(L, KA().out + (size_t)LMH_OUT_STRIDE * inst);
-            if (double *lg = KA().log) {
+            if (tick == zoh_args<ZohExArgs>().n_ticks - 1) store_out(L, zoh_args<ZohExArgs>().out + (size_t)LMH_OUT_STRIDE * inst);
+            if (double *lg = zoh_args<ZohExArgs>().log) {
                 lg += ((size_t)tick * n_inst + inst) * 36;
                 if (lane < 24) lg[lane] = L[P_TAU + lane]; else if (lane < 36) lg[lane] = L[P_W12 + lane - 24];
             }
-            if (double *trace = KA().ex.trace) {
-                double *tr = trace_slot(trace, KA().ex.trace_every, tick + 1, n_inst, inst);
+            if (double *trace = zoh_args<ZohExArgs>().ex.trace) {
+                double *tr = trace_slot(trace, zoh_args<ZohExArgs>().ex.trace_every, tick + 1, n_inst, inst);
                 if (tr) store_out(L, tr + LMH_STATE_STRIDE);
             }
-            if (double *m = KA().ex.metrics) metrics_wave1<false>(m + (size_t)LMH_METRICS_STRIDE * inst, L, lane);
+            if (double *m = zoh_args<ZohExArgs>().ex.metrics) metrics_wave1<false>(m + (size_t)LMH_METRICS_STRIDE * inst, L, lane);
             double x = L[P_Q + ((lane < 60) ? lane : 0)];          // q | v are one run
-            if constexpr (IO) x = KA().state[(size_t)LMH_STATE_STRIDE * inst + ((lane < 60) ? lane : 0)];      // the true state: L holds what the evaluation measured
+            if constexpr (IO) x = zoh_args<ZohExArgs>().state[(size_t)LMH_STATE_STRIDE * inst + ((lane < 60) ? lane : 0)];      // the true state: L holds what the evaluation measured
             const double vp = L[P_V + ((lane < 30) ? lane : 0)];   // Robot::v_ <- dq (controller.cpp:59): what the next evaluation sees
             double tau = (lane < 6) ? bw : L[P_TAU + ((lane >= 6 && lane < 30) ? lane - 6 : 0)];               // lane i < 30: tau30[i] = [base wrench | out.tau]
             if constexpr (IO) tau = zoh_io_actuate(tau, io_joint, lane, inst, tick, flags);
             ServoLane servo = {0.0, 0.0, 0.0, 0.0};
             if constexpr (SERVO) servo = zoh_servo_lane(L, lane, inst, tick, nsub, dt);
-            const bool pushes = KA().ex.pushes != 0;
+            const bool pushes = zoh_args<ZohExArgs>().ex.pushes != 0;
             // substeps of the launch | of them behind the robot: the cursor's units, formed with pushes only (the host bounds the product then)
-            const int lim = pushes ? KA().n_ticks * nsub : 0;
+            const int lim = pushes ? zoh_args<ZohExArgs>().n_ticks * nsub : 0;
             int done = pushes ? tick * nsub : 0, r = nsub;         // r: substeps left of this hold
 #pragma unroll 1
             while (r > 0) {                                        // one piece without pushes; a push inside the hold ends a piece
@@ -5674,26 +5487,21 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
                     const int rel = __builtin_amdgcn_readfirstlane(((const int *)(L + P_PUSH))[0]);
                     if (rel > done && rel < done + r) s = rel - done;
                 }
-                if constexpr (SERVO)
-                    plant_hold<GROUND, true>(L, P, ib_pack(), lane, tau, dt, s, x, flags, GROUND ? zoh_ground_args().ground + zoh_ground_args().ground_stride * (size_t)inst : nullptr, &servo);
-                else
-                if constexpr (GROUND) plant_hold<true>(L, P, ib_pack(), lane, tau, dt, s, x, flags, zoh_ground_args().ground + zoh_ground_args().ground_stride * (size_t)inst);
-                else
-                plant_hold(L, P, ib_pack(), lane, tau, dt, s, x, flags);
+                plant_hold<GROUND, SERVO>(L, P, ib_pack(), lane, tau, dt, s, x, flags, GROUND ? zoh_args<ZohGroundArgs>().ground + zoh_args<ZohGroundArgs>().ground_stride * (size_t)inst : nullptr, SERVO ? &servo : nullptr);
                 done += s; r -= s;
                 if (r > 0) push_poll(L, P, inst, lane, done, lim, x);      // between two substeps: v += dv on the integrator's register
             }
             // the sample and the fold of this control tick: the state, the clock and the flags are the hold's
-            if (double *trace = KA().ex.trace) {
-                double *tr = trace_slot(trace, KA().ex.trace_every, tick + 1, n_inst, inst);
+            if (double *trace = zoh_args<ZohExArgs>().ex.trace) {
+                double *tr = trace_slot(trace, zoh_args<ZohExArgs>().ex.trace_every, tick + 1, n_inst, inst);
                 if (tr) zoh_trace_state(tr, lane, x, vp, t, k, itmax, flags, F);
             }
-            if (double *m = KA().ex.metrics) metrics_wave0(m + (size_t)LMH_METRICS_STRIDE * inst, L, x, flags);
+            if (double *m = zoh_args<ZohExArgs>().ex.metrics) metrics_wave0(m + (size_t)LMH_METRICS_STRIDE * inst, L, x, flags);
             // a push on the first substep of the next control tick joins the state its evaluation reads, behind the sample (lim: never the
             // substep the launch ends on)
             if (pushes) push_poll(L, P, inst, lane, done, lim, x);
             WSYNC();
-            if constexpr (IO) zoh_io_publish(L, KA().state + (size_t)LMH_STATE_STRIDE * inst, lane, x, tick + 1, inst);
+            if constexpr (IO) zoh_io_publish(L, zoh_args<ZohExArgs>().state + (size_t)LMH_STATE_STRIDE * inst, lane, x, tick + 1, inst);
             else if (lane < 60) L[P_Q + lane] = x;
             if (lane < 30) L[P_VP + lane] = vp;
             WSYNC();
@@ -5701,11 +5509,12 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
         bsync<2>();                                                // the helper wave starts the next evaluation's references on the new state
     }
     if (wid == 0) {
-        double *st = KA().state + (size_t)LMH_STATE_STRIDE * inst;
+        double *st = zoh_args<ZohExArgs>().state + (size_t)LMH_STATE_STRIDE * inst;
         for (int e = LANE; e < 90; e += 64) st[e] = L[P_Q + e];    // q | v | v_prev
-        if (LANE == 0) { st[90] = t; store_status(KA().status, inst, k, itmax, flags, F); }
+        if (LANE == 0) { st[90] = t; store_status(zoh_args<ZohExArgs>().status, inst, k, itmax, flags, F); }
     }
 }
+// lmh_rollout_zoh, lmh_rollout_zoh_ref (nothing set in A_arg.ex) and lmh_rollout_zoh_ex (include/lmh.h)
 template <bool REF>
 __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) lmh_rollout_zoh_ex_kernel(LmhDevParams P_arg, ZohExArgs A_arg)
 {
@@ -5730,7 +5539,7 @@ __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_wav
     lmh_rollout_zoh_ex_body<REF ? ZM_REF : ZM_BUILTIN, true>(L);
 }
 // lmh_rollout_zoh / _ref / _ex / _io on a handle with a ground table (lmh_set_ground): the IO body, which with no measurement and no actuator
-// leaves the bytes of the ex body and with no option those of lmh_rollout_zoh_kernel, with the GROUND hold
+// leaves the bytes of the ex body, with the GROUND hold
 template <bool REF>
 __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) lmh_rollout_zoh_ground_kernel(LmhDevParams P_arg, ZohGroundArgs A_arg)
 {
@@ -5746,57 +5555,30 @@ __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_wav
     (void)A_arg;
     lmh_rollout_zoh_ex_body<REF ? ZM_REF : ZM_BUILTIN, true, GROUND, true>(L);
 }
-// ex NULL: lmh_rollout_zoh's kernel exactly as it is when ref is NULL, otherwise lmh_rollout_zoh_ref's; with ex the kernel that takes the options
+// One kernel per launch, the first of: sv -> the servo kernel, ground -> the ground kernel, io -> the io kernel, bx -> the box kernel, otherwise
+// the ex kernel.  ex or io NULL: none of their options (all-zero records), so lmh_rollout_zoh and lmh_rollout_zoh_ref are the ex kernel with
+// nothing set.  The host layer never passes bx with ref, io, ground or sv, and never io without ex.
 extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
                                        const LmhZohEx *ex, const LmhZohBox *bx, const LmhZohIo *io, const double *ground, size_t ground_stride, const LmhZohServo *sv, hipStream_t s)
 {
-    // sv: lmh_rollout_zoh_servo_kernel whatever the options and the ground (bx is then NULL); NULL = the kernels of before, exactly
-    if (sv) {
-        const LmhZohEx no_ex = {nullptr, nullptr, 0, 0, 0, 0};
-        const LmhZohIo no_io = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
-        const ZohServoArgs a = {{{{state, out, status, base_wrench, log, ref, ex ? *ex : no_ex, n_ticks, n_substeps}, io ? *io : no_io}, ground, ground_stride}, *sv};
-        const dim3 grid(P->n_instances), block(LMH_ROLLOUT_THREADS);
-        if (ground) {
-            if (ref) hipLaunchKernelGGL((lmh_rollout_zoh_servo_kernel<true, true>), grid, block, 0, s, *P, a);
-            else hipLaunchKernelGGL((lmh_rollout_zoh_servo_kernel<false, true>), grid, block, 0, s, *P, a);
-        } else {
-            if (ref) hipLaunchKernelGGL((lmh_rollout_zoh_servo_kernel<true, false>), grid, block, 0, s, *P, a);
-            else hipLaunchKernelGGL((lmh_rollout_zoh_servo_kernel<false, false>), grid, block, 0, s, *P, a);
-        }
-        return;
-    }
-    // ground: lmh_rollout_zoh_ground_kernel whatever the options (bx is then NULL: the host layer refuses the combination); ex or io NULL = none of theirs
-    if (ground) {
-        const LmhZohEx no_ex = {nullptr, nullptr, 0, 0, 0, 0};
-        const LmhZohIo no_io = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
-        const ZohGroundArgs a = {{{state, out, status, base_wrench, log, ref, ex ? *ex : no_ex, n_ticks, n_substeps}, io ? *io : no_io}, ground, ground_stride};
-        if (ref) hipLaunchKernelGGL(lmh_rollout_zoh_ground_kernel<true>, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, a);
-        else hipLaunchKernelGGL(lmh_rollout_zoh_ground_kernel<false>, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, a);
-        return;
-    }
-    // io: lmh_rollout_zoh_io_kernel (ex is then never NULL and bx is)
-    if (io) {
-        const ZohIoArgs a = {{state, out, status, base_wrench, log, ref, *ex, n_ticks, n_substeps}, *io};
-        if (ref) hipLaunchKernelGGL(lmh_rollout_zoh_io_kernel<true>, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, a);
-        else hipLaunchKernelGGL(lmh_rollout_zoh_io_kernel<false>, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, a);
-        return;
-    }
-    // bx: lmh_rollout_zoh_box_kernel.  The most dynamic shared memory such a launch may ask for (N = LMH_MAX_HORIZON) is above the 64 KB a kernel gets
+    // The most dynamic shared memory a launch of lmh_rollout_zoh_box_kernel may ask for (N = LMH_MAX_HORIZON) is above the 64 KB a kernel gets
     // unasked: bx->prepare sets that limit on the current device and launches nothing.
     if (bx && bx->prepare) {
         const int bytes = (int)sizeof(double) * zoh_box_lds_doubles(LMH_MAX_HORIZON + 1);
         *bx->answer = (int32_t)hipFuncSetAttribute(reinterpret_cast<const void *>(lmh_rollout_zoh_box_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    } else if (bx) {
-        const ZohBoxArgs a = {{state, out, status, base_wrench, log, nullptr, *ex, n_ticks, n_substeps}, bx->box, bx->box_stride, bx->mpc, bx->alpha, bx->beta};
-        const size_t bytes = sizeof(double) * (size_t)zoh_box_lds_doubles(P->horizon + 1);
-        hipLaunchKernelGGL(lmh_rollout_zoh_box_kernel, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), bytes, s, *P, a);
-    } else if (ex) {
-        const ZohExArgs a = {state, out, status, base_wrench, log, ref, *ex, n_ticks, n_substeps};
-        if (ref) hipLaunchKernelGGL(lmh_rollout_zoh_ex_kernel<true>, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, a);
-        else hipLaunchKernelGGL(lmh_rollout_zoh_ex_kernel<false>, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, a);
+        return;
     }
-    else if (ref) hipLaunchKernelGGL(lmh_rollout_zoh_ref_kernel, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, state, out, status, base_wrench, log, ref, n_ticks, n_substeps);
-    else hipLaunchKernelGGL(lmh_rollout_zoh_kernel, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), 0, s, *P, state, out, status, base_wrench, log, n_ticks, n_substeps);
+    const LmhZohEx no_ex = {nullptr, nullptr, 0, 0, 0, 0};
+    const LmhZohIo no_io = {nullptr, nullptr, nullptr, nullptr, 0, 0, 0};
+    const ZohExArgs a = {state, out, status, base_wrench, log, ref, ex ? *ex : no_ex, n_ticks, n_substeps};
+    const ZohGroundArgs ag = {{a, io ? *io : no_io}, ground, ground_stride};
+    auto launch = [&](auto kernel, const auto &args, size_t lds_bytes) { hipLaunchKernelGGL(kernel, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), lds_bytes, s, *P, args); };
+    if (sv && ground) launch(ref ? lmh_rollout_zoh_servo_kernel<true, true> : lmh_rollout_zoh_servo_kernel<false, true>, ZohServoArgs{ag, *sv}, 0);
+    else if (sv) launch(ref ? lmh_rollout_zoh_servo_kernel<true, false> : lmh_rollout_zoh_servo_kernel<false, false>, ZohServoArgs{ag, *sv}, 0);
+    else if (ground) launch(ref ? lmh_rollout_zoh_ground_kernel<true> : lmh_rollout_zoh_ground_kernel<false>, ag, 0);
+    else if (io) launch(ref ? lmh_rollout_zoh_io_kernel<true> : lmh_rollout_zoh_io_kernel<false>, ag.a, 0);
+    else if (bx) launch(lmh_rollout_zoh_box_kernel, ZohBoxArgs{a, bx->box, bx->box_stride, bx->mpc, bx->alpha, bx->beta}, sizeof(double) * (size_t)zoh_box_lds_doubles(P->horizon + 1));
+    else launch(ref ? lmh_rollout_zoh_ex_kernel<true> : lmh_rollout_zoh_ex_kernel<false>, a, 0);
 }
 
 #endif

@@ -8,7 +8,7 @@ Timed per n_substeps, HIP events around one launch, medians with min..max, the r
   step, per-robot table  lmh_plant_step on a handle with one record per robot: slopes of 0 .. 3 degrees in random directions through the
                          start's contact patch (how many robots end a launch with a counted flag, with and without the table, is reported: the
                          loop does not keep a robot up for long on either ground, DESIGN round 16)
-  zoh, per-robot table   lmh_rollout_zoh on that handle: lmh_rollout_zoh_ground_kernel instead of lmh_rollout_zoh_kernel
+  zoh, per-robot table   lmh_rollout_zoh on that handle: lmh_rollout_zoh_ground_kernel instead of lmh_rollout_zoh_ex_kernel
   parent                 the two calls without a table from a library built from the parent commit (--parent-variant NAME loads
                          linearmpchumanoid_amd/liblmh_hip_var_NAME.so, see build.py), each in two child processes of this one, one before
                          and one after this build's passes: their medians and ranges are the parent's own pass-to-pass spread in this session.

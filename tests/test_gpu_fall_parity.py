@@ -2,9 +2,9 @@
 
 Inputs: fall_cases.fall_states(band), band in (1.0, 3.1) -- 16 states each whose joints, roll, pitch and yaw span the band, moving at
 +-2 m/s, +-5 rad/s (base) and +-5 rad/s (joints), every contact regime on both feet with margin, soles on edge and upside down -- with
-fall_cases.fall_planes(band) (normals tilted 5 .. 35 degrees) for the ground twin, and fall_cases.pitch_ladder() up to 1e-6 rad from the
+fall_cases.fall_planes(band) (normals tilted 5 .. 35 degrees) for the ground table, and fall_cases.pitch_ladder() up to 1e-6 rad from the
 Euler-rate singularity.  test_fall_cases.py asserts on the CPU what the draw covers.  Every check runs on lmh_plant_kernel (a handle
-without a table) and on its twin lmh_plant_ground_kernel (set_ground); every launch is 16 robots at the most and 20 substeps at the most.
+without a table) and on its GROUND instantiation (set_ground); every launch is 16 robots at the most and 20 substeps at the most.
 
 References, reused from the existing tests: test_gpu_terms._oracle_terms / _check_terms, plant_step_cases.oracle_plant_xdot /
 oracle_plant_steps, ground_cases.ground_plant_xdot / ground_plant_steps, Oracle.contact() and trajectories.ground_contact.
