@@ -967,6 +967,65 @@ typedef struct lmh_zoh_servo {
 int lmh_rollout_zoh_servo(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts,
                           const lmh_zoh_io *io, const lmh_zoh_servo *servo, int n_ticks, int n_substeps, void *stream);
 
+/* ---- Rigid-contact plant inside the zero-order-hold loop (build-defined): lmh_rollout_zoh_io's loop with lmh_plant_step_rigid in every hold,
+ * in one launch -- so the timed pushes inside holds, the wrench per tick, the trace, the on-chip metrics fold, caller-supplied CoM
+ * references, measurement error, the actuator model and n_substeps > 1 can be used on the plant that stands, and the held set can change from
+ * control tick to control tick without a return to the host.
+ * lmh_rollout_zoh_rigid.  DEFINITION.  For every robot i the call leaves, bit for bit, what lmh_rollout_zoh_io's host loop (above) leaves with
+ * every lmh_plant_step(s substeps) of a hold replaced by lmh_plant_step_rigid(state, tau30, mode_j, kv, s) (B = n_instances; control tick j of
+ * this launch):
+ *         [the push due at the tick's start;  scratch, the measurement, lmh_eval / lmh_eval_ref on scratch -> out, status;  v_prev;  the
+ *          actuator -> y;  d_applied[j][i] = y:  all as in lmh_rollout_zoh_io]
+ *         mode_j = d_mode[i]  (d_mode NULL: LMH_PHASE_DOUBLE)          LMH_RIGID_FIXED
+ *         mode_j = d_mode[j][i]                                        LMH_RIGID_PER_TICK
+ *         mode_j = phase[min(max(k, 0), n_samples - 1)]                LMH_RIGID_PLAN: the support phase of the robot's own plan (the shared one,
+ *                                                                     or robot i's of lmh_gen_walk_batch / lmh_set_plans) at the preview index k
+ *                                                                     this tick's evaluation reports in status[0], clamped into the arrays as
+ *                                                                     the kernels clamp it; a plan without a phase array: LMH_PHASE_DOUBLE.
+ *                                                                     This is trajectories.rigid_modes(phase, k) and nothing else.
+ *         tau30 = [ wrench (6) | y (24) ]
+ *         for every piece of the hold (s substeps; the pushes inside the hold between the pieces, as in lmh_rollout_zoh_ex):
+ *             lmh_plant_step_rigid(state, tau30, mode_j, kv, s) -> lambda      one mode serves every piece of control tick j's hold
+ *         d_lambda[j][i] = lambda of the LAST piece                   when d_lambda != NULL: the multiplier at the first stage of the last
+ *                                                                     substep of tick j's hold (zeros when n_substeps == 0)
+ *         [the sample and the fold: lmh_rollout_zoh_ex's, on the TRUE state]
+ * Only the low two bits of a mode word are read, as in lmh_plant_step_rigid.
+ * Inherited from lmh_rollout_zoh_io, word for word: where pushes fall, including inside holds; d_ref, the wrench sequence, d_meas, the
+ * actuator and d_applied; the trace sample and the metrics fold, on the true state (WMIN / WMAX stay the controller's out.f, not the
+ * multiplier); status[2] ORs the plant's flags over every stage, so LMH_FLAG_CONTACT_PULL and LMH_FLAG_CONTACT_SLIP arrive there, and both stay
+ * outside the mask (& 15) of the metrics' FIRST_FLAG; (a + b) equals (a) followed by (b) bit for bit with the per-tick arrays advanced by a
+ * records per robot -- d_mode (LMH_RIGID_PER_TICK) and d_lambda included -- and d_act_mem handed on.
+ * THERE IS NO IMPACT MODEL.  A sole that becomes held while it moves keeps its twist and loses it as e^(-kv t): with kv = 0 it keeps it for
+ * good.  The contact stays BILATERAL: a held sole that the ground would have to pull on is held all the same, and reported
+ * (LMH_FLAG_CONTACT_PULL, LMH_FLAG_CONTACT_SLIP), never released.  Which soles are held is the caller's (or the plan's) decision alone.
+ * Tables.  As the two rigid plant calls, the call reads nothing from the ground table (lmh_set_ground) and nothing from the servo table
+ * (lmh_set_servo): it gives the same bytes with or without either.
+ * rigid == NULL or source == 0 is lmh_rollout_zoh_io(h, ..., opts, io, ...) exactly: the same kernel is launched (on that handle's ground
+ * table, then).  The box-constrained loop (lmh_rollout_zoh_box) and the joint servo (lmh_rollout_zoh_servo) are NOT offered with it.
+ * Refusals, each LMH_ERR_BAD_ARG before anything is enqueued and with a message of its own: a source outside its values; a non-zero
+ * reserved; a kv that is negative or not finite; LMH_RIGID_PER_TICK without d_mode; LMH_RIGID_PLAN with d_mode; every refusal of
+ * lmh_rollout_zoh_io.  n_ticks == 0 enqueues nothing.  LMH_PRECISION_FP64 handles only; the call takes no launch slot, writes nothing into
+ * the handle and is capturable into a hipGraph as the first call on a fresh handle.
+ * Cost (one MI355X, 4096 standing robots x 200 control ticks, both soles held, kv = 50; scripts/zoh_rigid_rate.py; other
+ * batch sizes and anything multi-GPU were not measured): the call is SLOWER than the host loop it replaces, stand_step ; plant_step_rigid --
+ * 73.95 against 70.13 ms (x 1.054) at n_substeps = 1 and 597.8 against 491.3 ms (x 1.217) at 10 -- and x 1.19 / x 1.25 of lmh_rollout_zoh_io
+ * with nothing set (62.03 / 478.7 ms); storing d_lambda adds 1.4 % / 0.1 %, LMH_RIGID_PER_TICK modes cost nothing measurable.  The hold runs
+ * on one wave of the evaluation's two-wave workgroup; the plant kernel of the host loop is a one-wave workgroup.  What the call offers is the
+ * family's options on this plant and one launch, not time.  lmh_rollout_zoh_io and lmh_plant_step_rigid run at the parent commit's rate:
+ * their kernels are the parent's, instruction for instruction. */
+#define LMH_RIGID_FIXED 1          /* lmh_zoh_rigid.source: d_mode [B], held for the launch; NULL = LMH_PHASE_DOUBLE for every robot */
+#define LMH_RIGID_PER_TICK 2       /* lmh_zoh_rigid.source: d_mode [n_ticks][B], record j is control tick j's hold */
+#define LMH_RIGID_PLAN 3           /* lmh_zoh_rigid.source: d_mode must be NULL, the robot's own plan decides */
+typedef struct lmh_zoh_rigid {
+    const int32_t *d_mode;        /* DEVICE, low two bits read, as lmh_plant_step_rigid */
+    double *d_lambda;             /* DEVICE [n_ticks][B][12] or NULL */
+    double kv;                    /* >= 0, finite: lmh_plant_step_rigid's */
+    int32_t source;               /* 0 off | LMH_RIGID_FIXED 1 | LMH_RIGID_PER_TICK 2 | LMH_RIGID_PLAN 3 */
+    int32_t reserved;             /* must be 0 */
+} lmh_zoh_rigid;
+int lmh_rollout_zoh_rigid(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts,
+                          const lmh_zoh_io *io, const lmh_zoh_rigid *rigid, int n_ticks, int n_substeps, void *stream);
+
 /* ---- LIPM preview MPC for a batch of reduced states (one kernel family of its own, one wave per robot, fp64): the stage of the controller
  * that lmh_eval runs between the momentum and the PD law, as calls of its own.
  * replaces: Mpc3dLip::compute (src/mpcLinearPendulum.cpp:78-109) for every robot of the handle, at that robot's own clock.

@@ -28,6 +28,7 @@ SERVO_STRIDE = 48             # one servo record: kp[24] | kd[24] (lmh_set_servo
 SERVO_OFF_KP, SERVO_OFF_KD = 0, 24
 SETPOINT_STRIDE = 48          # one setpoint record: q_des[24] | v_des[24] (lmh_plant_step_servo, lmh_rollout_zoh_servo)
 SERVO_INTEGRATE, SERVO_CALLER = 1, 2      # lmh_zoh_servo.mode (0: off)
+RIGID_FIXED, RIGID_PER_TICK, RIGID_PLAN = 1, 2, 3     # lmh_zoh_rigid.source (0: off)
 GROUND_STRIDE = 8             # one ground record: n_R(3) | h_R | n_L(3) | h_L, the half space n.x <= h under each foot (lmh_set_ground)
 GROUND_OFF_N_R, GROUND_OFF_H_R, GROUND_OFF_N_L, GROUND_OFF_H_L = 0, 3, 4, 7
 IK_TARGET_STRIDE = 16         # one inverse-kinematics target record: rf6 | lf6 | com(3) | pad (lmh_ik_batch)
@@ -130,6 +131,11 @@ class LmhZohServo(C.Structure):
     _fields_ = [("d_setpoint", C.c_void_p), ("mode", C.c_int32), ("reserved", C.c_int32)]
 
 
+class LmhZohRigid(C.Structure):
+    """struct lmh_zoh_rigid (include/lmh.h): the rigid-contact hold of lmh_rollout_zoh_rigid; source 0 = lmh_rollout_zoh_io."""
+    _fields_ = [("d_mode", C.c_void_p), ("d_lambda", C.c_void_p), ("kv", C.c_double), ("source", C.c_int32), ("reserved", C.c_int32)]
+
+
 _vp, _ip, _dp, _str, _u64 = C.c_void_p, C.c_int, C.c_double, C.c_char_p, C.c_uint64
 _u64p, _dpp = C.POINTER(C.c_uint64), C.POINTER(C.c_double)
 # name -> (restype, argtypes) of every symbol include/lmh.h declares; tests/test_abi.py holds each row against its prototype
@@ -203,6 +209,7 @@ PROTOTYPES = {
     "lmh_rollout_zoh_box": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), _vp, _ip, _ip, _vp, _ip, _ip, _vp]),
     "lmh_rollout_zoh_io": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), C.POINTER(LmhZohIo), _ip, _ip, _vp]),
     "lmh_rollout_zoh_servo": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), C.POINTER(LmhZohIo), C.POINTER(LmhZohServo), _ip, _ip, _vp]),
+    "lmh_rollout_zoh_rigid": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), C.POINTER(LmhZohIo), C.POINTER(LmhZohRigid), _ip, _ip, _vp]),
     "lmh_mpc_step": (_ip, [_vp, _vp, _vp, _vp]),
     "lmh_mpc_rollout": (_ip, [_vp, _vp, _ip, _vp, _vp]),
     "lmh_mpc_preview": (_ip, [_vp, _vp, _vp, _vp]),

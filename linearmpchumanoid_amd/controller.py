@@ -761,7 +761,48 @@ class BatchedController:
             sv = capi.LmhZohServo(d_setpoint=_dev_ptr(keep), mode=capi.SERVO_CALLER, reserved=0)
         return self.rollout_zoh_io(state, n, n_substeps, _servo_call=sv, **io)
 
-    def rollout_zoh_io(self, state, n_ticks, n_substeps, meas=None, actuators=False, act_mem=None, applied=False, _servo_call=None, **ex):
+    def rollout_zoh_rigid(self, state, n_ticks, n_substeps, mode=None, kv=0.0, lam=False, **io):
+        """lmh_rollout_zoh_rigid: rollout_zoh_io (whose keywords it takes as they are) with the rigid-contact plant in every hold -- bit for
+        bit that call's host loop with plant_step_rigid(mode_j, kv) in the place of plant_step.  mode: None, both soles of every robot held
+        for the launch; an int32 [B] tensor of PHASE_* words, held for the launch; an int32 [n_ticks,B] tensor, record j is control tick
+        j's hold; "plan": the support phase of the robot's own plan at the preview index that tick's evaluation reports
+        (trajectories.rigid_modes).  One mode serves every piece of a tick's hold.  lam=True: the multipliers [n_ticks,B,12] at the first
+        stage of the last substep of every tick's hold are returned under "lam" (a tensor: filled).  There is no impact model and the
+        contact stays bilateral (include/lmh.h); the ground and servo tables are not read.  -> rollout_zoh_io's dict plus lam."""
+        if int(n_ticks) != n_ticks or n_ticks < 0:
+            raise ValueError("n_ticks must be a whole number >= 0")
+        n = int(n_ticks)
+        md = None
+        if mode is None:
+            source = capi.RIGID_FIXED
+        elif isinstance(mode, str):
+            if mode != "plan":
+                raise ValueError('mode must be None, an int32 [B] or [n_ticks,B] tensor, or "plan"')
+            source = capi.RIGID_PLAN
+        else:
+            if isinstance(mode, np.ndarray) and mode.dtype == np.int32:
+                mode = torch.from_numpy(np.ascontiguousarray(mode)).to(self.device)
+            if not isinstance(mode, torch.Tensor) or mode.dtype != torch.int32 or mode.device != self.device or tuple(mode.shape) not in ((self.B,), (n, self.B)):
+                raise ValueError(f"mode must be a [{self.B}] or [{n},{self.B}] int32 tensor on {self.device}")
+            source = capi.RIGID_FIXED if mode.ndim == 1 else capi.RIGID_PER_TICK
+            md = mode.contiguous()
+            if md.numel() == 0:                                    # (an empty tensor has no address to pass; with no tick no record is read)
+                md = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        if lam is True:
+            lm = torch.zeros((n, self.B, 12), dtype=torch.float64, device=self.device)
+        elif lam is False or lam is None:
+            lm = None
+        else:
+            lm = lam
+            if not isinstance(lm, torch.Tensor) or lm.dtype != torch.float64 or lm.device != self.device or tuple(lm.shape) != (n, self.B, 12) or not lm.is_contiguous():
+                raise ValueError(f"lam must be a contiguous [{n},{self.B},12] float64 tensor on {self.device}")
+        lm_arg = lm if (lm is None or lm.numel() > 0) else torch.empty((1,), dtype=torch.float64, device=self.device)
+        rg = capi.LmhZohRigid(d_mode=_dev_ptr(md), d_lambda=_dev_ptr(lm_arg), kv=float(kv), source=source, reserved=0)
+        res = self.rollout_zoh_io(state, n, n_substeps, _rigid_call=rg, **io)
+        res["lam"] = lm
+        return res
+
+    def rollout_zoh_io(self, state, n_ticks, n_substeps, meas=None, actuators=False, act_mem=None, applied=False, _servo_call=None, _rigid_call=None, **ex):
         """lmh_rollout_zoh_io: rollout_zoh_ex (whose keywords it takes as they are) with sensing and actuation between controller and plant.
         meas [n_ticks,B,60]: what is added to q | v as control tick j's evaluation sees them (the plant goes on from the true state; v_prev
         keeps the measured v).  actuators=True: the set_actuators records -- latency, torque limit, first-order lag -- stand between the
@@ -795,13 +836,14 @@ class BatchedController:
             raise TypeError(f"rollout_zoh_io: unexpected keyword {sorted(set(ex) - set(kw))[0]!r}")
         kw.update(ex)
         res = self._rollout_zoh_opts(state, n_ticks, n_substeps, kw["base_wrench"], kw["ref"], kw["pushes"], kw["log"], kw["trace_every"], kw["trace"],
-                                     kw["metrics"], kw["out"], kw["status"], None, io_call=io, servo_call=_servo_call)
+                                     kw["metrics"], kw["out"], kw["status"], None, io_call=io, servo_call=_servo_call, rigid_call=_rigid_call)
         res["applied"] = ap
         return res
 
-    def _rollout_zoh_opts(self, state, n_ticks, n_substeps, base_wrench, ref, pushes, log, trace_every, trace, metrics, out, status, box_call, io_call=None, servo_call=None):
+    def _rollout_zoh_opts(self, state, n_ticks, n_substeps, base_wrench, ref, pushes, log, trace_every, trace, metrics, out, status, box_call, io_call=None, servo_call=None, rigid_call=None):
         """The argument handling rollout_zoh_ex, rollout_zoh_box and rollout_zoh_io share; box_call: None, or lmh_rollout_zoh_box's (d_box, n_samples,
-        n_sets, d_mpc); io_call: None, or lmh_rollout_zoh_io's record; servo_call: None, or lmh_rollout_zoh_servo's record (then with io_call)."""
+        n_sets, d_mpc); io_call: None, or lmh_rollout_zoh_io's record; servo_call: None, or lmh_rollout_zoh_servo's record (then with io_call); rigid_call: None,
+        or lmh_rollout_zoh_rigid's record (then with io_call and without servo_call)."""
         state = self._batch("state", state, capi.STATE_STRIDE, in_place=True)
         for name, n in (("n_ticks", n_ticks), ("n_substeps", n_substeps), ("trace_every", trace_every)):
             if int(n) != n or n < 0:
@@ -838,7 +880,10 @@ class BatchedController:
         metrics = self._batch("metrics", metrics, capi.METRICS_STRIDE, optional=True, in_place=True)
         opts = capi.LmhZohOpts(d_base_wrench=_dev_ptr(bw), d_ref=_dev_ptr(ref), d_log=_dev_ptr(lg), d_trace=_dev_ptr(tr_arg), d_metrics=_dev_ptr(metrics),
                                trace_every=trace_every, wrench_per_tick=int(per_tick), pushes=int(bool(pushes)), reserved=0)
-        if servo_call is not None:
+        if rigid_call is not None:
+            check(capi.lib().lmh_rollout_zoh_rigid(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), C.byref(io_call), C.byref(rigid_call),
+                                                   n_ticks, n_substeps, self._stream()))
+        elif servo_call is not None:
             check(capi.lib().lmh_rollout_zoh_servo(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), C.byref(io_call), C.byref(servo_call),
                                                    n_ticks, n_substeps, self._stream()))
         elif io_call is not None:

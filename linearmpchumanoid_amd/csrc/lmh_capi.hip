@@ -469,7 +469,7 @@ extern "C" int lmh_create(const lmh_config *cfg, int n_instances, int device, lm
     {                                                               // lmh_rollout_zoh_box's dynamic LDS: asked for here, never inside the (capturable) call
         int32_t answer = -1;
         const LmhZohBox prep = {nullptr, 0, nullptr, 0.0, 0.0, 1, &answer};
-        lmh_launch_rollout_zoh(&h->P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &prep, nullptr, nullptr, 0, nullptr, nullptr);
+        lmh_launch_rollout_zoh(&h->P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &prep, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
         h->zoh_box_prepared = answer;
     }
     (void)hipGetLastError();                                        // an answer other than hipSuccess is that call's to report, not a sticky error of this one
@@ -1230,10 +1230,12 @@ extern "C" int lmh_plant_step_rigid(lmh_handle *h, double *d_state, const double
 // for nothing launches what the call without it launches, anything else lmh_rollout_zoh_io_kernel.
 // sv (lmh_rollout_zoh_servo; nullptr in the five calls above it, never with bx): its own refusals stand behind those of the io record; mode 0 launches what
 // the call without it launches, anything else lmh_rollout_zoh_servo_kernel whatever the options.
+// rg (lmh_rollout_zoh_rigid; nullptr in the six calls above it, never with bx or sv): its own refusals stand behind those of the io record; source 0
+// launches what the call without it launches, anything else lmh_rollout_zoh_rigid_kernel whatever the options, with no ground and no servo table.
 struct ZohBoxCall { const double *d_box; int n_samples, n_sets; double *d_mpc; };
 static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log, const double *d_ref, bool with_ref,
                     int n_ticks, int n_substeps, void *stream, const lmh_zoh_opts *opts = nullptr, const ZohBoxCall *bx = nullptr, const lmh_zoh_io *io = nullptr,
-                    const lmh_zoh_servo *sv = nullptr)
+                    const lmh_zoh_servo *sv = nullptr, const lmh_zoh_rigid *rg = nullptr)
 {
     int rc = ready(h); if (rc) return rc;
     if (!d_state || !d_out || !d_status) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: null device pointer");
@@ -1275,6 +1277,14 @@ static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_st
         if (sv->mode == LMH_SERVO_INTEGRATE && n_substeps == 0)
             return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_servo: mode LMH_SERVO_INTEGRATE needs n_substeps > 0 (the setpoint is the end of a control period: with no substep there is none)");
     }
+    if (rg) {
+        if (rg->source != 0 && rg->source != LMH_RIGID_FIXED && rg->source != LMH_RIGID_PER_TICK && rg->source != LMH_RIGID_PLAN)
+            return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_rigid: source must be 0, LMH_RIGID_FIXED, LMH_RIGID_PER_TICK or LMH_RIGID_PLAN");
+        if (rg->reserved != 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_rigid: reserved must be 0");
+        if (!(rg->kv >= 0.0 && rg->kv <= 1.7976931348623157e308)) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_rigid: kv must be finite and >= 0");
+        if (rg->source == LMH_RIGID_PER_TICK && !rg->d_mode) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_rigid: source LMH_RIGID_PER_TICK needs d_mode");
+        if (rg->source == LMH_RIGID_PLAN && rg->d_mode) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_rigid: d_mode must be NULL with source LMH_RIGID_PLAN (the robot's own plan decides)");
+    }
     if (h->cfg.precision != LMH_PRECISION_FP64) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: LMH_PRECISION_FP64 handles only (this handle's precision has no instantiation of the kernel)");
     rc = plant_constants_ok(h); if (rc) return rc;
     if (n_ticks == 0) return LMH_OK;                                 // nothing to enqueue
@@ -1282,20 +1292,26 @@ static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_st
         if (h->zoh_box_prepared != 0 && h->N > 33)                   // N >= 34: above 64 KB of LDS in all, only with the limit lmh_create asked for
             return fail(LMH_ERR_HIP, "lmh_rollout_zoh_box: the runtime refused the kernel's dynamic shared memory limit when the handle was created");
         const LmhZohBox zb = {bx->d_box, box_stride(h, bx->n_sets), bx->d_mpc, h->cfg.alpha, h->cfg.beta, 0, nullptr};
-        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, nullptr, n_ticks, n_substeps, &ex, &zb, nullptr, nullptr, 0, nullptr, (hipStream_t)stream); });
+        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, nullptr, n_ticks, n_substeps, &ex, &zb, nullptr, nullptr, 0, nullptr, nullptr, (hipStream_t)stream); });
+    }
+    if (rg && rg->source != 0) {                                     // the rigid hold reads neither the ground nor the servo table: neither rides along
+        const LmhZohIo zi = {io ? io->d_meas : nullptr, (io && io->actuators) ? io->d_act_mem : nullptr, io ? io->d_applied : nullptr, h->d_act.get(),
+                             (h->n_act_sets > 1) ? (size_t)LMH_ACT_STRIDE : 0, io ? io->actuators : 0, 0};
+        const LmhZohRigid zr = {rg->d_mode, rg->d_lambda, rg->kv, rg->source, 0};
+        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, &ex, nullptr, &zi, nullptr, 0, nullptr, &zr, (hipStream_t)stream); });
     }
     if (sv && sv->mode != 0) {
         const LmhZohIo zi = {io ? io->d_meas : nullptr, (io && io->actuators) ? io->d_act_mem : nullptr, io ? io->d_applied : nullptr, h->d_act.get(),
                              (h->n_act_sets > 1) ? (size_t)LMH_ACT_STRIDE : 0, io ? io->actuators : 0, 0};
         const LmhZohServo zs = {sv->d_setpoint, h->d_servo.get(), h->servo_stride(), sv->mode, 0};
-        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, &ex, nullptr, &zi, h->d_ground.get(), h->ground_stride(), &zs, (hipStream_t)stream); });
+        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, &ex, nullptr, &zi, h->d_ground.get(), h->ground_stride(), &zs, nullptr, (hipStream_t)stream); });
     }
     if (io && (io->d_meas || io->d_applied || io->actuators)) {
         const LmhZohIo zi = {io->d_meas, io->actuators ? io->d_act_mem : nullptr, io->d_applied, h->d_act.get(), (h->n_act_sets > 1) ? (size_t)LMH_ACT_STRIDE : 0, io->actuators, 0};
-        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, &ex, nullptr, &zi, h->d_ground.get(), h->ground_stride(), nullptr, (hipStream_t)stream); });
+        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, &ex, nullptr, &zi, h->d_ground.get(), h->ground_stride(), nullptr, nullptr, (hipStream_t)stream); });
     }
     const bool plain = !ex.trace && !ex.metrics && !ex.wrench_per_tick && !ex.pushes;     // no new option: the kernels of before
-    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, plain ? nullptr : &ex, nullptr, nullptr, h->d_ground.get(), h->ground_stride(), nullptr, (hipStream_t)stream); });
+    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, plain ? nullptr : &ex, nullptr, nullptr, h->d_ground.get(), h->ground_stride(), nullptr, nullptr, (hipStream_t)stream); });
 }
 extern "C" int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
                                int n_ticks, int n_substeps, void *stream)
@@ -1331,6 +1347,15 @@ extern "C" int lmh_rollout_zoh_servo(lmh_handle *h, double *d_state, double *d_o
     static const lmh_zoh_opts none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
     const lmh_zoh_opts *o = opts ? opts : &none;
     return zoh_body(h, d_state, d_out, d_status, o->d_base_wrench, o->d_log, o->d_ref, false, n_ticks, n_substeps, stream, o, nullptr, io, servo);
+}
+
+// lmh_rollout_zoh_io with the rigid-contact plant in every hold (include/lmh.h)
+extern "C" int lmh_rollout_zoh_rigid(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts, const lmh_zoh_io *io, const lmh_zoh_rigid *rigid,
+                                     int n_ticks, int n_substeps, void *stream)
+{
+    static const lmh_zoh_opts none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
+    const lmh_zoh_opts *o = opts ? opts : &none;
+    return zoh_body(h, d_state, d_out, d_status, o->d_base_wrench, o->d_log, o->d_ref, false, n_ticks, n_substeps, stream, o, nullptr, io, nullptr, rigid);
 }
 
 // lmh_rollout_zoh_ex with lmh_mpc_box_step closing the loop inside every evaluation (include/lmh.h)

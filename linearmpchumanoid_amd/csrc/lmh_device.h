@@ -132,6 +132,16 @@ struct LmhZohServo {
     int32_t pad;
 };
 
+// lmh_rollout_zoh_rigid (include/lmh.h, lmh_zoh_rigid): what the launch takes beyond lmh_rollout_zoh_io's -- which soles every control tick's hold
+// keeps and where its multipliers go.  source is never 0 here: that is the launch without.
+struct LmhZohRigid {
+    const int32_t *mode;        // LMH_RIGID_FIXED: [n_instances] or nullptr (both soles); LMH_RIGID_PER_TICK: [n_ticks][n_instances]; LMH_RIGID_PLAN: nullptr
+    double *lambda;             // [n_ticks][n_instances][12], or nullptr
+    double kv;                  // plant_derivative_rigid's velocity-level stabilisation
+    int32_t source;             // LMH_RIGID_FIXED | LMH_RIGID_PER_TICK | LMH_RIGID_PLAN
+    int32_t pad;
+};
+
 // walking-plan generator (lmh_gen_walk): arguments of the device kernel
 #define LMH_GEN_MAX_STEPS 1022
 struct LmhWalkSpec {

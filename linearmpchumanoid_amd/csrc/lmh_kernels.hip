@@ -5109,7 +5109,10 @@ struct RigidHold { unsigned live; double kv, lam; };
 // LDS writes it), `flags` collects the derivative's and LMH_FLAG_NONFINITE of x behind every substep.  Wave-scope fences only; no clock:
 // the callers advance theirs by n_substeps additions of dt (plant_store_state; wave 0 of the zero-order-hold kernels).
 // The derivative is plant_derivative<GROUND, SERVO> (gnd is read with GROUND only, servo with SERVO only) or, with RIGID, plant_derivative_rigid.
-template <bool GROUND = false, bool SERVO = false, bool RIGID = false>
+// LOOP changes no statement: the zero-order-hold kernels take the RIGID hold as an instantiation of their own, so that lmh_plant_kernel's stays
+// the only caller of its copy and that kernel keeps its instruction stream (what the compiler propagates into a function from its one call
+// site, the kernel's own LDS array among it, it no longer propagates once other kernels call the same instantiation).
+template <bool GROUND = false, bool SERVO = false, bool RIGID = false, bool LOOP = false>
 __device__ __forceinline__ void plant_hold(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau, double dt, int n_substeps, double &x, int &flags, const double *gnd = nullptr,
                                            const ServoLane *servo = nullptr, RigidHold *rigid = nullptr)
 {
@@ -5361,6 +5364,35 @@ __device__ __forceinline__ ServoLane zoh_servo_lane(const double *L, int lane, i
     }
     return S;
 }
+// ---- lmh_rollout_zoh_rigid (include/lmh.h): the IO body with the rigid-contact plant in every hold (the RIGID flag of lmh_rollout_zoh_ex_body).
+// lmh_rollout_zoh_rigid_kernel's arguments: lmh_rollout_zoh_io_kernel's, then the hold's record.  Neither the ground nor the servo table follows.
+struct ZohRigidArgs { ZohIoArgs a; LmhZohRigid rg; };
+static_assert(sizeof(ZohIoArgs) % 8 == 0 && alignof(ZohRigidArgs) == 8, "ZohRigidArgs continues ZohIoArgs in the kernel-argument segment");
+// What the RIGID hold needs survives it below the scratch, as with the compliant plant's PL_* block: the per-launch tables, the reference cache,
+// the K_f^-1 cache and the push cursor.  RG_* lies in S0 + [768, 1440): in front of Q_TRASH and of kinv_compute's scratch (A_XR), which is formed
+// again whenever it is needed.  plant_derivative_rigid writes P_VP, P_VFOOT, P_QREF and P_JPQP below S0 -- words every evaluation forms for itself
+// before it reads them -- and P_W12 nowhere: metrics_wave0 finds the evaluation's wrench there behind the hold.
+static_assert(RG_Y == S0 + 768 && RG_END == S0 + 1440 && RG_END <= Q_TRASH && RG_END <= A_XR, "RG_* inside the QP scratch, in front of the dump and of kinv_compute's scratch");
+static_assert(P_MODEL + LMH_MODEL_STRIDE <= S0 && P_GCOL < S0 && P_GI6 < S0 && P_GPI < S0 && P_MPCK < S0, "the per-launch tables lie below the scratch");
+static_assert(P_POLY < S0 && P_PRE + 22 <= S0, "the reference cache lies below the scratch");
+static_assert(P_KI + 72 <= P_KF && P_KF + 3 <= S0 && P_PUSH < S0 && P_W12 + 12 <= S0, "the K_f^-1 cache, the push cursor and the evaluation's wrench lie below the scratch");
+// wave 0, behind the evaluation of control tick `tick` (k: the preview index it returned, status[0]) and in front of its hold: the tick's mode
+// word, read here and not held across controller_eval -- LMH_RIGID_FIXED mode[robot] (NULL: both soles), LMH_RIGID_PER_TICK mode[tick][robot],
+// LMH_RIGID_PLAN the phase byte of the robot's own plan at k, clamped as refs clamp it (no phase array: both soles) -- and kv
+__device__ __forceinline__ RigidHold zoh_rigid_hold(LmhCParams &P, int inst, int tick, int k)
+{
+    const int src = zoh_args<ZohRigidArgs>().rg.source;
+    int mode = LMH_PHASE_DOUBLE;
+    if (src == LMH_RIGID_PLAN) {
+        if (const uint8_t *ph = P.phase) {
+            const int ns = P.n_samples, k0 = (k < 0) ? 0 : (k >= ns ? ns - 1 : k);
+            mode = (int)(ph + (size_t)P.ref_stride * (size_t)inst)[k0];
+        }
+    } else if (const int32_t *m = zoh_args<ZohRigidArgs>().rg.mode)
+        mode = m[((src == LMH_RIGID_PER_TICK) ? (size_t)tick * (size_t)LMH_KERNARG_PARAMS().n_instances : (size_t)0) + (size_t)inst];
+    RigidHold R = {(unsigned)__builtin_amdgcn_readfirstlane((int)rigid_live(mode)), zoh_args<ZohRigidArgs>().rg.kv, 0.0};      // (one word per robot: wave-uniform)
+    return R;
+}
 // The loop.  lmh_rollout_zoh (include/lmh.h): for every robot exactly what n_ticks rounds of { lmh_eval ; lmh_plant_step(tau30 = [base_wrench |
 // out.tau], n_substeps) } leave, bit for bit, with the robot on chip for the whole launch.  One workgroup per robot; the launch opens with
 // lmh_eval_kernel's eval_begin and runs its two-wave schedule for the evaluation; the hold is plant_hold, the loop lmh_plant_kernel<PM_STEP>
@@ -5392,13 +5424,17 @@ enum { ZM_BUILTIN, ZM_REF, ZM_BOX };
 // vertex lanes load their plane where they use it: nothing of it is carried across controller_eval.
 // SERVO (lmh_rollout_zoh_servo_kernel; always with IO; its arguments continue ZohGroundArgs, so GROUND reads the same words): every piece of
 // a control tick's hold is the SERVO plant_hold with the tick's one ServoLane (zoh_servo_lane), formed where wave 0 picks up tau.
-template <int MODE, bool IO = false, bool GROUND = false, bool SERVO = false>
+// RIGID (lmh_rollout_zoh_rigid_kernel; always with IO, never with GROUND, SERVO or ZM_BOX; its arguments continue ZohIoArgs): every piece of a
+// control tick's hold is the RIGID plant_hold with the tick's one RigidHold (zoh_rigid_hold); the multiplier leaves behind the hold.
+template <int MODE, bool IO = false, bool GROUND = false, bool SERVO = false, bool RIGID = false>
 __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
 {
     constexpr bool REF = MODE != ZM_BUILTIN, BOX = MODE == ZM_BOX;
     static_assert(!(IO && BOX), "lmh_rollout_zoh_io has no box-constrained form");
     static_assert(IO || !GROUND, "the ground kernels are instantiations of the IO body");
     static_assert(IO || !SERVO, "the servo kernels are instantiations of the IO body");
+    static_assert(IO || !RIGID, "the rigid kernels are instantiations of the IO body");
+    static_assert(!(RIGID && (GROUND || SERVO || BOX)), "the rigid hold has no ground table, no servo and no box-constrained form");
     LmhCParams &P0 = LMH_KERNARG_PARAMS();
     const int inst = blockIdx.x;
     if (inst >= P0.n_instances) return;
@@ -5476,6 +5512,8 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
             if constexpr (IO) tau = zoh_io_actuate(tau, io_joint, lane, inst, tick, flags);
             ServoLane servo = {0.0, 0.0, 0.0, 0.0};
             if constexpr (SERVO) servo = zoh_servo_lane(L, lane, inst, tick, nsub, dt);
+            RigidHold rigid = {0u, 0.0, 0.0};
+            if constexpr (RIGID) rigid = zoh_rigid_hold(P, inst, tick, k);
             const bool pushes = zoh_args<ZohExArgs>().ex.pushes != 0;
             // substeps of the launch | of them behind the robot: the cursor's units, formed with pushes only (the host bounds the product then)
             const int lim = pushes ? zoh_args<ZohExArgs>().n_ticks * nsub : 0;
@@ -5487,9 +5525,13 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
                     const int rel = __builtin_amdgcn_readfirstlane(((const int *)(L + P_PUSH))[0]);
                     if (rel > done && rel < done + r) s = rel - done;
                 }
-                plant_hold<GROUND, SERVO>(L, P, ib_pack(), lane, tau, dt, s, x, flags, GROUND ? zoh_args<ZohGroundArgs>().ground + zoh_args<ZohGroundArgs>().ground_stride * (size_t)inst : nullptr, SERVO ? &servo : nullptr);
+                plant_hold<GROUND, SERVO, RIGID, RIGID>(L, P, ib_pack(), lane, tau, dt, s, x, flags, GROUND ? zoh_args<ZohGroundArgs>().ground + zoh_args<ZohGroundArgs>().ground_stride * (size_t)inst : nullptr, SERVO ? &servo : nullptr,
+                                                        RIGID ? &rigid : nullptr);
                 done += s; r -= s;
                 if (r > 0) push_poll(L, P, inst, lane, done, lim, x);      // between two substeps: v += dv on the integrator's register
+            }
+            if constexpr (RIGID) {                                 // the multiplier of the first stage of the last substep of this tick's hold
+                if (double *lm = zoh_args<ZohRigidArgs>().rg.lambda) { if (lane < 12) lm[((size_t)tick * n_inst + inst) * 12 + lane] = rigid.lam; }
             }
             // the sample and the fold of this control tick: the state, the clock and the flags are the hold's
             if (double *trace = zoh_args<ZohExArgs>().ex.trace) {
@@ -5555,11 +5597,20 @@ __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_wav
     (void)A_arg;
     lmh_rollout_zoh_ex_body<REF ? ZM_REF : ZM_BUILTIN, true, GROUND, true>(L);
 }
-// One kernel per launch, the first of: sv -> the servo kernel, ground -> the ground kernel, io -> the io kernel, bx -> the box kernel, otherwise
+// lmh_rollout_zoh_rigid (include/lmh.h): the IO body with the rigid-contact plant in every hold; no ground table and no servo
+template <bool REF>
+__global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) lmh_rollout_zoh_rigid_kernel(LmhDevParams P_arg, ZohRigidArgs A_arg)
+{
+    __shared__ double L[LDS_DOUBLES];
+    (void)A_arg;
+    lmh_rollout_zoh_ex_body<REF ? ZM_REF : ZM_BUILTIN, true, false, false, true>(L);
+}
+// One kernel per launch, the first of: rg -> the rigid kernel (the host layer passes neither ground nor sv with it), sv -> the servo kernel, ground -> the ground kernel, io -> the io kernel, bx -> the box kernel, otherwise
 // the ex kernel.  ex or io NULL: none of their options (all-zero records), so lmh_rollout_zoh and lmh_rollout_zoh_ref are the ex kernel with
 // nothing set.  The host layer never passes bx with ref, io, ground or sv, and never io without ex.
 extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
-                                       const LmhZohEx *ex, const LmhZohBox *bx, const LmhZohIo *io, const double *ground, size_t ground_stride, const LmhZohServo *sv, hipStream_t s)
+                                       const LmhZohEx *ex, const LmhZohBox *bx, const LmhZohIo *io, const double *ground, size_t ground_stride, const LmhZohServo *sv, const LmhZohRigid *rg,
+                                       hipStream_t s)
 {
     // The most dynamic shared memory a launch of lmh_rollout_zoh_box_kernel may ask for (N = LMH_MAX_HORIZON) is above the 64 KB a kernel gets
     // unasked: bx->prepare sets that limit on the current device and launches nothing.
@@ -5573,7 +5624,8 @@ extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, dou
     const ZohExArgs a = {state, out, status, base_wrench, log, ref, ex ? *ex : no_ex, n_ticks, n_substeps};
     const ZohGroundArgs ag = {{a, io ? *io : no_io}, ground, ground_stride};
     auto launch = [&](auto kernel, const auto &args, size_t lds_bytes) { hipLaunchKernelGGL(kernel, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), lds_bytes, s, *P, args); };
-    if (sv && ground) launch(ref ? lmh_rollout_zoh_servo_kernel<true, true> : lmh_rollout_zoh_servo_kernel<false, true>, ZohServoArgs{ag, *sv}, 0);
+    if (rg) launch(ref ? lmh_rollout_zoh_rigid_kernel<true> : lmh_rollout_zoh_rigid_kernel<false>, ZohRigidArgs{ag.a, *rg}, 0);
+    else if (sv && ground) launch(ref ? lmh_rollout_zoh_servo_kernel<true, true> : lmh_rollout_zoh_servo_kernel<false, true>, ZohServoArgs{ag, *sv}, 0);
     else if (sv) launch(ref ? lmh_rollout_zoh_servo_kernel<true, false> : lmh_rollout_zoh_servo_kernel<false, false>, ZohServoArgs{ag, *sv}, 0);
     else if (ground) launch(ref ? lmh_rollout_zoh_ground_kernel<true> : lmh_rollout_zoh_ground_kernel<false>, ag, 0);
     else if (io) launch(ref ? lmh_rollout_zoh_io_kernel<true> : lmh_rollout_zoh_io_kernel<false>, ag.a, 0);

@@ -36,8 +36,11 @@ extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_
 // (ground_stride 0: one shared record) and the launch is lmh_rollout_zoh_ground_kernel's whatever ex and io ask for (either may be NULL = nothing).
 // sv (lmh_rollout_zoh_servo; bx is then NULL, ex, io and ground may each be NULL): NULL = no servo; otherwise lmh_rollout_zoh_servo_kernel, the IO body
 // with the joint servo inside every hold (LmhZohServo, lmh_device.h).
+// rg (lmh_rollout_zoh_rigid; bx, ground and sv are then NULL, ex and io may each be NULL): NULL = not that call; otherwise lmh_rollout_zoh_rigid_kernel, the IO
+// body with the rigid-contact plant in every hold (LmhZohRigid, lmh_device.h).
 extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
-                                       const LmhZohEx *ex, const LmhZohBox *bx, const LmhZohIo *io, const double *ground, size_t ground_stride, const LmhZohServo *sv, hipStream_t s);
+                                       const LmhZohEx *ex, const LmhZohBox *bx, const LmhZohIo *io, const double *ground, size_t ground_stride, const LmhZohServo *sv, const LmhZohRigid *rg,
+                                       hipStream_t s);
 extern "C" void lmh_launch_metrics_reset(double *metrics, int n_instances, double z_min, double tilt_max, hipStream_t s);
 extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
 extern "C" void lmh_launch_com(const LmhDevParams *P, const double *q, double *com, hipStream_t s);

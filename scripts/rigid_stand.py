@@ -14,7 +14,11 @@ Run 2, the controller's own gains through set_params, one robot per cell of a 16
 Reported: the first-fall tick of every cell (-1 = stood for the whole run), the cells that stand, the latest fall; and, because the contact is
 bilateral, for the cells that stand whether a held foot ever pulled or left its friction disc (LMH_FLAG_CONTACT_PULL / _SLIP OR-ed over
 the run) and where they are at the end: a cell that stands only by pulling on the ground does not stand on a real one.
-Usage: python scripts/rigid_stand.py [--ticks 2000] [--kv 50] [--z-min 0.2] [--tilt-max 0.5] [--out FILE]"""
+--zoh: the same two runs, each as ONE launch of rollout_zoh_rigid with a metrics record (FIRST_FALL is the host loop's first-fall tick, the
+multipliers and the log give |lambda - out.f|), which must reproduce the host loop's table; then, with the call in hand, run 2 again at
+n_substeps = 10 (a control period of 10 ms) and with mode="plan" on a walking plan (gen_walk's defaults, x scale 0.03 m: the plan decides
+which soles are held; there is no impact model and the contact stays bilateral).
+Usage: python scripts/rigid_stand.py [--ticks 2000] [--kv 50] [--z-min 0.2] [--tilt-max 0.5] [--zoh] [--out FILE]"""
 import argparse
 
 import numpy as np
@@ -27,6 +31,7 @@ ap.add_argument("--ticks", type=int, default=2000)
 ap.add_argument("--kv", type=float, default=50.0)
 ap.add_argument("--z-min", type=float, default=0.2)
 ap.add_argument("--tilt-max", type=float, default=0.5)
+ap.add_argument("--zoh", action="store_true", help="one rollout_zoh_rigid launch per run instead of the host loop; then n_substeps = 10 and a walking plan")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 assert torch.cuda.is_available(), "rigid_stand.py runs on the GPU only"
@@ -66,8 +71,25 @@ def run(ctl, control):
     return first, float(g.max()), at, flags.cpu().numpy(), st
 
 
+def run_zoh(ctl, control, n_substeps=1, mode=None):
+    """run() as one launch of rollout_zoh_rigid with a metrics record -> the same tuple"""
+    st = ctl.new_state(q, v, t=0.0, v_prev=v)
+    m = ctl.new_metrics(args.z_min, args.tilt_max)
+    r = ctl.rollout_zoh_rigid(st, args.ticks, n_substeps, mode=mode, kv=args.kv, lam=True, log=True, metrics=m)
+    torch.cuda.synchronize()
+    first = ctl.split_metrics(m.cpu().numpy())["first_fall"].astype(np.int64)
+    n = args.ticks if first[control] < 0 else int(first[control])
+    g = (r["lam"][:max(n, 1), control] - r["log"][:max(n, 1), control, 24:36]).abs().cpu().numpy()
+    at = np.unravel_index(int(np.argmax(g)), g.shape)
+    return first, float(g.max()), at, (r["status"][:, 2] & ~255).cpu().numpy(), st      # (the plant's informational flags: the bits above the controller's)
+
+
+if args.zoh:
+    run = run_zoh
 ctl = BatchedController(B, cfg)
 ctl.set_refs_stance(args.ticks * DT + 1.0, 2)
+if args.zoh:
+    say("each run below is ONE launch of rollout_zoh_rigid with a metrics record; the host loop's table: profiles/r33_rigid_stand.txt")
 say("closed loop on the rigid-contact plant on %s: %d robots from rest, both soles held, kv = %g /s, n_substeps = 1, %d control ticks of %g s; down: z < %.2f m or tilt > %.2f rad"
     % (torch.cuda.get_device_name(0), B, args.kv, args.ticks, DT, args.z_min, args.tilt_max))
 first, gap, at, flags, st = run(ctl, 0)
@@ -84,24 +106,40 @@ grid = BatchedController(B, cfg)
 grid.set_refs_stance(args.ticks * DT + 1.0, 2)
 grid.set_params(**fields)
 control = 7 * G + 7
-first2, gap2, at2, flags2, st2 = run(grid, control)
-nonfinite = ~np.isfinite(st2[:, :60].cpu().numpy()).all(axis=1)
-say("")
-say("run 2, the controller's gains, one robot per cell; control cell (row 7, column 7): first fall %d (run 1: %d), largest |lambda - out.f| %.4g" % (first2[control], first[0], gap2))
-say("  first fall per cell (rows: s on kp_mom, sqrt(s) on kd_mom; last row: w_foot x 100; columns: c on kp_joints, sqrt(c) on kd_joints; -1 = stood; * = end state not finite):")
-say("  %9s |" % "s \\ c" + "".join(" %7.3g" % c for c in Cj))
-for i in range(G):
-    say("  %9s |" % ("w_foot" if i == G - 1 else "%.3g" % S[i]) + "".join(" %6d%s" % (first2[i * G + j], "*" if nonfinite[i * G + j] else " ") for j in range(G)))
-stood = [i for i in range(B) if first2[i] < 0 and not nonfinite[i]]
-best = max(range(B), key=lambda i: (args.ticks if first2[i] < 0 else first2[i]))
-say("  cells that stand for the whole run: %d of %d%s" % (len(stood), B, "" if not stood else ": " + ", ".join("(row %d, column %d)" % divmod(i, G) for i in stood)))
 from linearmpchumanoid_amd import capi
-end = st2.cpu().numpy()
-pulled = [i for i in stood if flags2[i] & capi.FLAG_CONTACT_PULL]
-slipped = [i for i in stood if flags2[i] & capi.FLAG_CONTACT_SLIP]
-say("  of the cells that stand: %d pulled on the ground at some tick, %d left the friction disc at some tick, %d did neither" % (len(pulled), len(slipped), len([i for i in stood if i not in pulled and i not in slipped])))
-if stood:
-    say("  their end states: base height %.4f .. %.4f m (start %.4f), |pitch| <= %.4f rad, |roll| <= %.2e rad, largest |v| %.3e"
-        % (end[stood, 2].min(), end[stood, 2].max(), q0[2], np.abs(end[stood, 4]).max(), np.abs(end[stood, 3]).max(), np.abs(end[stood, 30:60]).max()))
-say("  latest fall: cell (row %d, column %d) at control tick %s" % (*divmod(best, G), "none" if first2[best] < 0 else str(first2[best])))
+
+
+def report(title, first2, gap2, flags2, st2):
+    nonfinite = ~np.isfinite(st2[:, :60].cpu().numpy()).all(axis=1)
+    say("")
+    say("%s, the controller's gains, one robot per cell; control cell (row 7, column 7): first fall %d (run 1: %d), largest |lambda - out.f| %.4g" % (title, first2[control], first[0], gap2))
+    say("  first fall per cell (rows: s on kp_mom, sqrt(s) on kd_mom; last row: w_foot x 100; columns: c on kp_joints, sqrt(c) on kd_joints; -1 = stood; * = end state not finite):")
+    say("  %9s |" % "s \\ c" + "".join(" %7.3g" % c for c in Cj))
+    for i in range(G):
+        say("  %9s |" % ("w_foot" if i == G - 1 else "%.3g" % S[i]) + "".join(" %6d%s" % (first2[i * G + j], "*" if nonfinite[i * G + j] else " ") for j in range(G)))
+    stood = [i for i in range(B) if first2[i] < 0 and not nonfinite[i]]
+    best = max(range(B), key=lambda i: (args.ticks if first2[i] < 0 else first2[i]))
+    say("  cells that stand for the whole run: %d of %d%s" % (len(stood), B, "" if not stood else ": " + ", ".join("(row %d, column %d)" % divmod(i, G) for i in stood)))
+    end = st2.cpu().numpy()
+    pulled = [i for i in stood if flags2[i] & capi.FLAG_CONTACT_PULL]
+    slipped = [i for i in stood if flags2[i] & capi.FLAG_CONTACT_SLIP]
+    say("  of the cells that stand: %d pulled on the ground at some tick, %d left the friction disc at some tick, %d did neither" % (len(pulled), len(slipped), len([i for i in stood if i not in pulled and i not in slipped])))
+    if stood:
+        say("  their end states: base height %.4f .. %.4f m (start %.4f), |pitch| <= %.4f rad, |roll| <= %.2e rad, largest |v| %.3e"
+            % (end[stood, 2].min(), end[stood, 2].max(), q0[2], np.abs(end[stood, 4]).max(), np.abs(end[stood, 3]).max(), np.abs(end[stood, 30:60]).max()))
+    say("  latest fall: cell (row %d, column %d) at control tick %s" % (*divmod(best, G), "none" if first2[best] < 0 else str(first2[best])))
+    return stood
+
+
+first2, gap2, at2, flags2, st2 = run(grid, control)
+stood1 = report("run 2", first2, gap2, flags2, st2)
+if args.zoh:
+    f10, g10, _, fl10, st10 = run_zoh(grid, control, n_substeps=10)
+    report("run 3, n_substeps = 10 (control period 10 ms; first falls in control ticks of 10 ms)", f10, g10, fl10, st10)
+    walk = BatchedController(B, cfg)
+    walk.set_xscale(np.full(B, 0.03))
+    walk.gen_walk(args.ticks * DT + 1.0)
+    walk.set_params(**fields)
+    fw, gw, _, flw, stw = run_zoh(walk, control, mode="plan")
+    report("run 4, mode=\"plan\" on gen_walk's default plan (step length 0.03 m), n_substeps = 1", fw, gw, flw, stw)
 write_lines(args.out, lines)

@@ -1,0 +1,503 @@
+"""lmh_rollout_zoh_rigid on the GPU: the zero-order-hold loop of lmh_rollout_zoh_io with the rigid-contact plant in every hold, the held set
+fixed for the launch, given per control tick, or decided by the robot's own plan.
+
+The call is DEFINED by a host loop of calls that exist (include/lmh.h), so the reference of every bit-for-bit case is that loop on a second
+copy of the same buffers (zoh_rigid_host_loop.host_loop_rigid: stand_step, plant_step_rigid in the pieces trajectories.zoh_hold_pieces gives,
+v += dv, zoh_host_loop.actuate, trajectories.rigid_modes); only test_parity_with_the_cpu_loop goes to the CPU oracle.  Inputs:
+plant_step_cases.contact_states(), 16 states around touch-down, v_prev = v, warm_start = 1; six control ticks; n_substeps 3 and 1; kv 0 and
+50; zoh_host_loop's push schedules.  "Bit for bit" is helpers.same_bits.  Every robot is in every comparison.  Every test fails on a library
+without the entry point: the method and the symbol do not exist there."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import plant_step_cases as pc
+import rigid_cases as rc
+import zoh_io_cases as zi
+import zoh_rigid_cases as zr
+from helpers import TOL_REL, WEIGHT, close, make_controller, perturbed_velocities, rel_err, same_bits as _same, vec_err
+from zoh_host_loop import SCHEDULES
+from zoh_rigid_host_loop import assert_same as _assert_same, fresh, host_loop_rigid, push_schedules, wrench_and_refs
+
+pytestmark = pytest.mark.gpu
+DT, TH, B, NT = zr.DT, zr.TH, zr.B, zr.NT
+FIVE_DT = sum([DT] * 5)           # a clock of five accumulated dt: the robot's substep number is 5
+CASES = [(3, 0.0), (3, 50.0), (1, 0.0), (1, 50.0)]
+CASE_IDS = ["3 substeps, kv 0", "3 substeps, kv 50", "1 substep, kv 0", "1 substep, kv 50"]
+
+
+def _fresh(ctl, S, t=0.0):
+    return fresh(ctl, S["q"], S["v"], t)
+
+
+def _imode(ctl, m):
+    return torch.as_tensor(np.ascontiguousarray(m, dtype=np.int32)).to(ctl.device)
+
+
+def _core(tag, sa, ra, sb, rb, more=()):
+    _assert_same(tag, (("state", sa, sb), ("out", ra["out"], rb["out"]), ("status", ra["status"], rb["status"]), ("log", ra["log"], rb["log"]),
+                       ("applied", ra["applied"], rb["applied"]), ("lam", ra["lam"], rb["lam"])) + tuple(more))
+
+
+@pytest.fixture(scope="module")
+def zrg():
+    S = pc.contact_states()
+    ticks, dv = push_schedules()
+    mk = lambda: make_controller(B, DT, TH, S["zcom"], warm_start=1)
+    ctl, plain = mk(), mk()                                        # push schedules and actuator records | neither: the host loop's handle
+    for c in (ctl, plain):
+        c.set_refs_stance(2.0, 2)
+    ctl.set_pushes(ticks, dv)
+    dev = ctl.device
+    # delays 0 .. 3, a lag on two thirds of the robots, limits per robot and joint with none on every fourth robot
+    tau_max = 0.05 + 0.1 * ((np.arange(B)[:, None] + np.arange(24)[None, :]) % 5)
+    tau_max[0::4] = np.inf
+    rec = zi.robot_records(tau_max)
+    rec[:, 48] = np.arange(B) % 4
+    ctl.set_actuators(tau_max=rec[:, 0:24], alpha=rec[:, 24:48], delay=rec[:, 48])
+    meas = torch.as_tensor(zi.measurement_noise(20261202, NT)).to(dev)
+    bw_seq, refs, out0 = wrench_and_refs(plain, _fresh(plain, S), NT)
+    tau0 = out0[:, 0:24].contiguous() * 0.5                        # a holding torque for the memories: half of the first command
+    yield dict(S=S, ctl=ctl, plain=plain, ticks=ticks, dv=dv, bw_seq=bw_seq, meas=meas, refs=refs, rec=torch.as_tensor(rec).to(dev), rec_np=rec, tau0=tau0,
+               mode3=_imode(ctl, zr.fixed_modes()), per_tick=_imode(ctl, zr.per_tick_modes()))
+    for c in (ctl, plain):
+        c.close()
+
+
+# ------------------------------------------------------------------------------- 1. FIXED against the host loop
+@pytest.mark.parametrize("mixed", [True, False], ids=["modes i % 3", "mode None"])
+@pytest.mark.parametrize("n_substeps,kv", CASES, ids=CASE_IDS)
+def test_fixed_modes_are_the_host_loop_bit_for_bit(zrg, n_substeps, kv, mixed):
+    """Nothing set in opts or io beyond the every-tick trace, the metrics, the log and applied."""
+    from linearmpchumanoid_amd import metrics as hm
+    ctl, plain, S = zrg["ctl"], zrg["plain"], zrg["S"]
+    mode = zrg["mode3"] if mixed else None
+    sa, sb = _fresh(ctl, S), _fresh(plain, S)
+    m = ctl.new_metrics(0.3, 0.2)
+    ra = ctl.rollout_zoh_rigid(sa, NT, n_substeps, mode=mode, kv=kv, lam=True, applied=True, log=True, trace_every=1, metrics=m)
+    rb = host_loop_rigid(plain, sb, plain.new_status(), NT, n_substeps, mode=mode, kv=kv)
+    torch.cuda.synchronize()
+    _core(("fixed", n_substeps, kv, mixed), sa, ra, sb, rb, (("trace", ra["trace"], rb["trace"]),))
+    assert _same(m.cpu().numpy(), hm.fold_trace(hm.identity(B, 0.3, 0.2), rb["trace"].cpu().numpy()))
+    assert _same(ra["applied"], ra["log"][:, :, 0:24].contiguous())                          # no actuator: the plant receives the command
+    held = torch.as_tensor(np.array([[1.0] * 12, [1.0] * 6 + [0.0] * 6, [0.0] * 6 + [1.0] * 6])[zr.fixed_modes() if mixed else np.zeros(B, dtype=int)]).to(ctl.device)
+    assert bool((ra["lam"][:, held == 0.0] == 0.0).all()) and bool((ra["lam"][:, held == 1.0] != 0.0).all())
+    # the rigid hold is not the compliant one
+    sc = _fresh(ctl, S)
+    ctl.rollout_zoh_io(sc, NT, n_substeps)
+    assert all(not _same(sa[i], sc[i]) for i in range(B))
+
+
+@pytest.mark.parametrize("kv", zr.KVS)
+def test_lam_of_one_tick_of_one_substep_is_the_derivatives_at_the_start_of_the_hold(zrg, kv):
+    ctl, S = zrg["ctl"], zrg["S"]
+    st = _fresh(ctl, S)
+    r = ctl.rollout_zoh_rigid(st, 1, 1, mode=zrg["mode3"], kv=kv, lam=True)
+    s0 = _fresh(ctl, S)
+    zero6 = torch.zeros((B, 6), dtype=torch.float64, device=ctl.device)
+    tau30 = torch.cat([zero6, r["out"][:, 0:24]], dim=1).contiguous()
+    _, lam, _ = ctl.plant_derivative_rigid(s0[:, 0:30].contiguous(), s0[:, 30:60].contiguous(), tau30, zrg["mode3"], kv)
+    torch.cuda.synchronize()
+    assert r["lam"].shape == (1, B, 12) and _same(r["lam"][0], lam)
+
+
+# ------------------------------------------------------------------------------- 2. every option at once
+def _everything(ctl, zrg, n_ticks, n_substeps, kv, t0=0.0, every=0, metrics=None, st=None, status=None, mem=None, first_tick=0, meas=None, mode="mode3"):
+    """Pushes, the wrench sequence, the reference sequence, the measurement, the actuator, the log, applied and lam on; the sequences sliced from first_tick."""
+    st = _fresh(ctl, zrg["S"], t0) if st is None else st
+    mem = ctl.new_act_mem(zrg["tau0"]) if mem is None else mem
+    cut = slice(first_tick, first_tick + n_ticks)
+    meas = zrg["meas"] if meas is None else meas
+    md = zrg[mode][cut].contiguous() if mode == "per_tick" else zrg[mode]
+    r = ctl.rollout_zoh_rigid(st, n_ticks, n_substeps, mode=md, kv=kv, lam=True, meas=meas[cut].contiguous(), actuators=True, act_mem=mem, applied=True,
+                              base_wrench=zrg["bw_seq"][cut], ref=zrg["refs"][cut], pushes=True, log=True, trace_every=every, metrics=metrics, status=status)
+    return dict(r, state=st, mem=mem)
+
+
+def _everything_on_the_host(zrg, n_ticks, n_substeps, kv, t0=0.0, mode="mode3"):
+    plain = zrg["plain"]
+    st, mem = _fresh(plain, zrg["S"], t0), plain.new_act_mem(zrg["tau0"])
+    r = host_loop_rigid(plain, st, plain.new_status(), n_ticks, n_substeps, mode=zrg[mode], kv=kv, bw=zrg["bw_seq"], sched=(zrg["ticks"], zrg["dv"]), refs=zrg["refs"],
+                        meas=zrg["meas"], act=(zrg["rec"], mem))
+    torch.cuda.synchronize()
+    return dict(r, state=st, mem=mem)
+
+
+@pytest.mark.parametrize("t0", [0.0, FIVE_DT], ids=["from substep 0", "from substep 5"])
+@pytest.mark.parametrize("n_substeps,kv", CASES, ids=CASE_IDS)
+def test_every_option_at_once_is_the_host_loop(zrg, n_substeps, kv, t0):
+    """The 16 push schedules (pushes inside holds split the pieces), a wrench per tick, ref=, meas, actuators with delays 0 .. 3, the
+    every-tick trace and the metrics."""
+    from linearmpchumanoid_amd import metrics as hm
+    ctl = zrg["ctl"]
+    assert sorted(set(zrg["rec_np"][:, 48].astype(int).tolist())) == [0, 1, 2, 3] and len(SCHEDULES) == B
+    m1 = ctl.new_metrics(0.3, 0.2)
+    r1 = _everything(ctl, zrg, NT, n_substeps, kv, t0, every=1, metrics=m1)
+    host = _everything_on_the_host(zrg, NT, n_substeps, kv, t0)
+    torch.cuda.synchronize()
+    _core(("everything", n_substeps, kv, t0), r1["state"], r1, host["state"], host, (("act_mem", r1["mem"], host["mem"]), ("trace", r1["trace"], host["trace"])))
+    assert _same(m1.cpu().numpy(), hm.fold_trace(hm.identity(B, 0.3, 0.2), host["trace"].cpu().numpy()))
+    # WMIN / WMAX stay the controller's out.f
+    f = ctl.split_metrics(m1.cpu().numpy())
+    assert np.array_equal(f["wmax"], host["log"][:, :, 24:36].cpu().numpy().max(axis=0))
+    assert float(r1["state"][0, 90]) == sum([t0] + [DT] * (NT * n_substeps))
+
+
+# ------------------------------------------------------------------------------- 3. PER_TICK modes
+@pytest.mark.parametrize("n_substeps,kv", CASES, ids=CASE_IDS)
+def test_per_tick_modes_are_the_host_loop_bit_for_bit(zrg, n_substeps, kv):
+    ctl, plain, S = zrg["ctl"], zrg["plain"], zrg["S"]
+    words = zr.per_tick_modes()
+    changes, values = zr.mode_changes(words)                       # on the host, before the launch
+    assert (changes >= 2).all() and values == {0, 1, 2, 3} and (words > 3).any()
+    sa, sb = _fresh(ctl, S), _fresh(plain, S)
+    ra = ctl.rollout_zoh_rigid(sa, NT, n_substeps, mode=zrg["per_tick"], kv=kv, lam=True, applied=True, log=True, trace_every=1)
+    rb = host_loop_rigid(plain, sb, plain.new_status(), NT, n_substeps, mode=zrg["per_tick"], kv=kv)
+    torch.cuda.synchronize()
+    _core(("per tick", n_substeps, kv), sa, ra, sb, rb, (("trace", ra["trace"], rb["trace"]),))
+    rows = np.array([[1] * 12, [1] * 6 + [0] * 6, [0] * 6 + [1] * 6, [0] * 12])[words & 3]          # [NT,B,12]: 1 = held
+    lam = ra["lam"].cpu().numpy()
+    assert not lam[rows == 0].any() and lam[rows == 1].all()       # exactly zero on rows not held
+    # with everything else on as well
+    r1 = _everything(ctl, zrg, NT, n_substeps, kv, mode="per_tick", every=1)
+    host = _everything_on_the_host(zrg, NT, n_substeps, kv, mode="per_tick")
+    _core(("per tick, everything", n_substeps, kv), r1["state"], r1, host["state"], host, (("act_mem", r1["mem"], host["mem"]), ("trace", r1["trace"], host["trace"])))
+
+
+# ------------------------------------------------------------------------------- 4. PLAN modes
+def _plan_handles(S, plans):
+    """-> (per-robot plans generated on the device, the jump robots' phase arrays replaced | the same without a schedule: the host loop's)"""
+    hs = []
+    for _ in range(2):
+        c = make_controller(B, DT, TH, S["zcom"], warm_start=1)
+        c.gen_walk_batch(zr.SIM_TIME, zr.walk_specs())
+        got = [c.get_plan(i) for i in range(B)]
+        assert all(np.array_equal(got[i]["phase"], plans["phase"][i]) for i in range(B) if i not in zr.JUMP_ROBOTS)      # gen_walk_batch's plans are walk_plans'
+        stack = {k: np.stack([g[k] for g in got]) for k in ("zmp_x", "zmp_y", "phase", "segs", "seg_of_sample")}
+        stack["phase"] = plans["phase"]
+        c.set_plans(**stack)
+        hs.append(c)
+    return hs
+
+
+@pytest.mark.parametrize("n_substeps,kv", CASES, ids=CASE_IDS)
+def test_plan_modes_are_the_host_loop_and_the_per_tick_call(zrg, n_substeps, kv):
+    from linearmpchumanoid_amd import trajectories as tj
+    S = zrg["S"]
+    plans = zr.plans()
+    t0 = zr.start_clocks(plans["phase"], n_substeps)
+    want = zr.plan_modes(plans["phase"], zr.preview_indices(t0, NT, n_substeps))
+    changes, values = zr.mode_changes(want)                        # a condition on the inputs, checked before the launch
+    assert values == {tj.PHASE_DOUBLE, tj.PHASE_RIGHT, tj.PHASE_LEFT, tj.PHASE_FLIGHT} and int((changes > 0).sum()) >= 4 and zr.plan_condition(want)
+    ctl, plain = _plan_handles(S, plans)
+    sa, sb, sc = _fresh(ctl, S, t0), _fresh(plain, S, t0), _fresh(ctl, S, t0)
+    kw = dict(kv=kv, lam=True, applied=True, log=True, trace_every=1)
+    ra = ctl.rollout_zoh_rigid(sa, NT, n_substeps, mode="plan", **kw)
+    rb = host_loop_rigid(plain, sb, plain.new_status(), NT, n_substeps, mode="plan", phase=plans["phase"], kv=kv)
+    torch.cuda.synchronize()
+    _core(("plan", n_substeps, kv), sa, ra, sb, rb, (("trace", ra["trace"], rb["trace"]),))
+    assert np.array_equal(rb["modes"].cpu().numpy(), want)         # the evaluations' k are the clock's
+    rc_ = ctl.rollout_zoh_rigid(sc, NT, n_substeps, mode=_imode(ctl, want), **kw)
+    torch.cuda.synchronize()
+    _core(("plan against per tick", n_substeps, kv), sa, ra, sc, rc_, (("trace", ra["trace"], rc_["trace"]),))
+    for c in (ctl, plain):
+        c.close()
+
+
+@pytest.mark.parametrize("n_substeps,kv", [(3, 50.0), (1, 0.0)], ids=["3 substeps, kv 50", "1 substep, kv 0"])
+def test_plan_modes_on_a_shared_plan_and_without_a_phase_array(zrg, n_substeps, kv):
+    from linearmpchumanoid_amd import trajectories as tj
+    S = zrg["S"]
+    kw = dict(kv=kv, lam=True, applied=True, log=True, trace_every=1)
+    # one plan shared by every robot, per-robot start clocks around its boundaries
+    ctl, plain = (make_controller(B, DT, TH, S["zcom"], warm_start=1) for _ in range(2))
+    for c in (ctl, plain):
+        c.gen_walk(zr.SIM_TIME)
+    phase = ctl.get_refs()["phase"]
+    assert np.array_equal(phase, tj.walk_plan(zr.SIM_TIME, DT)["phase"]) and not ctl.plans_per_instance
+    t0 = zr.start_clocks(phase, n_substeps)
+    want = zr.plan_modes(phase, zr.preview_indices(t0, NT, n_substeps))
+    changes, values = zr.mode_changes(want)
+    assert values == {tj.PHASE_DOUBLE, tj.PHASE_RIGHT, tj.PHASE_LEFT} and int((changes > 0).sum()) >= 4
+    sa, sb = _fresh(ctl, S, t0), _fresh(plain, S, t0)
+    ra = ctl.rollout_zoh_rigid(sa, NT, n_substeps, mode="plan", **kw)
+    rb = host_loop_rigid(plain, sb, plain.new_status(), NT, n_substeps, mode="plan", phase=phase, kv=kv)
+    torch.cuda.synchronize()
+    _core(("shared plan", n_substeps, kv), sa, ra, sb, rb, (("trace", ra["trace"], rb["trace"]),))
+    assert np.array_equal(rb["modes"].cpu().numpy(), want)
+    # a plan without a phase array: DOUBLE, the call with mode None
+    zx, zy = tj.stance_zmp(zr.SIM_TIME, DT, 2)
+    for c in (ctl, plain):
+        c.set_refs(zx, zy, None)
+    sa, sb, sc = _fresh(ctl, S, t0), _fresh(plain, S, t0), _fresh(ctl, S, t0)
+    ra = ctl.rollout_zoh_rigid(sa, NT, n_substeps, mode="plan", **kw)
+    rb = host_loop_rigid(plain, sb, plain.new_status(), NT, n_substeps, mode="plan", phase=None, kv=kv)
+    rc_ = ctl.rollout_zoh_rigid(sc, NT, n_substeps, mode=None, **kw)
+    torch.cuda.synchronize()
+    _core(("no phase array", n_substeps, kv), sa, ra, sb, rb, (("trace", ra["trace"], rb["trace"]),))
+    _core(("no phase array against None", n_substeps, kv), sa, ra, sc, rc_, (("trace", ra["trace"], rc_["trace"]),))
+    for c in (ctl, plain):
+        c.close()
+
+
+# ------------------------------------------------------------------------------- 5. splitting
+@pytest.mark.parametrize("mode", ["per_tick", "mode3"])
+def test_six_ticks_are_two_then_four_with_everything_carried(zrg, mode):
+    """d_mode (per tick), d_lambda, d_meas, d_applied, d_ref and the wrench sequence are advanced by two records, act_mem is handed on;
+    robots 3, 7, 11 and 15 have a delay longer than the first launch; pushes fall on the substep the first launch ends on (2 x 3)."""
+    ctl = zrg["ctl"]
+    assert SCHEDULES[1] == [6] and 6 in SCHEDULES[7] and sum(d > 2 for d in zrg["rec_np"][:, 48]) == 4
+    m6, m24 = ctl.new_metrics(0.3, 0.2), ctl.new_metrics(0.3, 0.2)
+    r6 = _everything(ctl, zrg, NT, 3, 50.0, every=2, metrics=m6, mode=mode)
+    r2 = _everything(ctl, zrg, 2, 3, 50.0, every=2, metrics=m24, mode=mode)
+    status2 = r2["status"].clone()
+    r4 = _everything(ctl, zrg, 4, 3, 50.0, every=2, metrics=m24, st=r2["state"], status=r2["status"].clone(), mem=r2["mem"], first_tick=2, mode=mode)
+    torch.cuda.synchronize()
+    tb = r4["trace"].clone()                                       # status [1] / [2] of a sample count from its launch's start
+    tb[:, :, 177] = torch.maximum(tb[:, :, 177], status2[None, :, 1].double())
+    tb[:, :, 178] = (tb[:, :, 178].long() | status2[None, :, 2].long()).double()
+    _assert_same("split", (("state", r6["state"], r4["state"]), ("out", r6["out"], r4["out"]), ("log", r6["log"], torch.cat([r2["log"], r4["log"]])),
+                           ("applied", r6["applied"], torch.cat([r2["applied"], r4["applied"]])), ("lam", r6["lam"], torch.cat([r2["lam"], r4["lam"]])),
+                           ("act_mem", r6["mem"], r4["mem"]), ("trace", r6["trace"], torch.cat([r2["trace"], tb])), ("metrics", m6, m24)))
+    s6, s4 = r6["status"], r4["status"]
+    assert torch.equal(s6[:, 0], s4[:, 0]) and torch.equal(s6[:, 3], s4[:, 3])
+    assert torch.equal(s6[:, 1], torch.maximum(status2[:, 1], s4[:, 1])) and torch.equal(s6[:, 2], status2[:, 2] | s4[:, 2])
+
+
+# ------------------------------------------------------------------------------- 6. neutral calls and tables
+def test_source_0_is_rollout_zoh_io_and_the_tables_change_no_byte(zrg):
+    from linearmpchumanoid_amd import capi, trajectories as tj
+    ctl, S = zrg["ctl"], zrg["S"]
+    p = lambda t: C.c_void_p(t.data_ptr())
+    kw = dict(meas=zrg["meas"], actuators=True, applied=True, base_wrench=zrg["bw_seq"], ref=zrg["refs"], pushes=True, log=True, trace_every=1)
+
+    def tables():
+        return [(ctl.get_ground(i).tobytes(), ctl.get_servo(i)["kp"].tobytes(), ctl.get_servo(i)["kd"].tobytes(), ctl.get_actuators(i)["tau_max"].tobytes(),
+                 ctl.get_actuators(i)["alpha"].tobytes(), ctl.get_actuators(i)["delay"], ctl.get_pushes(i)["ticks"].tobytes(), ctl.get_pushes(i)["dv"].tobytes(),
+                 tuple(sorted(ctl.get_params(i).items())), ctl.get_plan(i)["zmp_x"].tobytes(), ctl.get_plan(i)["phase"].tobytes()) for i in (0, 5, B - 1)]
+
+    # rigid = NULL and source = 0 (whatever else the record holds): lmh_rollout_zoh_io's bytes
+    sb, mb, mem_b = _fresh(ctl, S), ctl.new_metrics(0.3, 0.2), ctl.new_act_mem(zrg["tau0"])
+    rb = ctl.rollout_zoh_io(sb, NT, 3, act_mem=mem_b, metrics=mb, **kw)
+    junk = torch.full((NT, B, 12), -7.0, dtype=torch.float64, device=ctl.device)
+    for rigid in (None, capi.LmhZohRigid(), capi.LmhZohRigid(d_mode=p(zrg["per_tick"]), d_lambda=p(junk), kv=3.0, source=0)):
+        sa, ma, mem_a = _fresh(ctl, S), ctl.new_metrics(0.3, 0.2), ctl.new_act_mem(zrg["tau0"])
+        out, status, log, applied, trace = ctl.new_out(), ctl.new_status(), torch.zeros_like(rb["log"]), torch.zeros_like(rb["applied"]), torch.zeros_like(rb["trace"])
+        opts = capi.LmhZohOpts(d_base_wrench=p(zrg["bw_seq"]), d_ref=p(zrg["refs"]), d_log=p(log), d_trace=p(trace), d_metrics=p(ma), trace_every=1, wrench_per_tick=1, pushes=1)
+        io = capi.LmhZohIo(d_meas=p(zrg["meas"]), d_act_mem=p(mem_a), d_applied=p(applied), actuators=1)
+        assert capi.lib().lmh_rollout_zoh_rigid(ctl._h, p(sa), p(out), p(status), C.byref(opts), C.byref(io), None if rigid is None else C.byref(rigid), NT, 3, ctl._stream()) == 0
+        torch.cuda.synchronize()
+        _assert_same("source 0", (("state", sa, sb), ("out", out, rb["out"]), ("status", status, rb["status"]), ("log", log, rb["log"]), ("applied", applied, rb["applied"]),
+                                  ("trace", trace, rb["trace"]), ("metrics", ma, mb), ("act_mem", mem_a, mem_b)))
+        assert bool((junk == -7.0).all())
+    # the ground and the servo table, set and cleared, change no byte of the rigid call; no table of the handle changes
+    before = tables()
+    runs = []
+    for step in ("none", "ground and servo", "cleared"):
+        if step == "ground and servo":
+            ctl.set_ground(tj.ground_planes(0.05, 0.3, 0.002, -0.001))
+            ctl.set_servo(kp=np.full((B, 24), 3.0), kd=0.1)
+        elif step == "cleared":
+            ctl.set_ground(None)
+            ctl.set_servo()
+        t_in = tables()
+        r = _everything(ctl, zrg, NT, 3, 50.0, every=1, metrics=ctl.new_metrics(0.3, 0.2), mode="per_tick")
+        torch.cuda.synchronize()
+        assert tables() == t_in, step                              # get_* of every handle table is unchanged after the call
+        runs.append(r)
+    for r in runs[1:]:
+        _core("tables", runs[0]["state"], runs[0], r["state"], r, (("act_mem", runs[0]["mem"], r["mem"]), ("trace", runs[0]["trace"], r["trace"])))
+    assert tables() == before
+
+
+# ------------------------------------------------------------------------------- 7. parity with the CPU
+def test_parity_with_the_cpu_loop():
+    """4 robots x 12 control ticks, both soles held, kv = 50, n_substeps = 1, in ONE launch against the CPU loop of
+    test_gpu_rigid.py::test_closed_loop_against_the_cpu_loop (oracle evaluation + rigid_cases.oracle_rigid_steps) at that test's own bounds:
+    state 1e-7, tau and f at TOL_REL (f with the weight's floor), k exact, no controller flag."""
+    S = rc.rigid_cases()
+    n, nt, kv = 4, 12, 50.0
+    ctl = make_controller(n, DT, TH, S["zcom"], warm_start=0)
+    ctl.set_refs_stance(2.0, 2)
+    q = np.tile(S["q0"], (n, 1))
+    v = perturbed_velocities(n, seed=20261022) * 0.2
+    v[0] = 0.0                                                     # one robot from rest
+    st = ctl.new_state(q, v, t=0.0, v_prev=v)
+    r = ctl.rollout_zoh_rigid(st, nt, 1, mode=None, kv=kv, lam=True)
+    torch.cuda.synchronize()
+    a, o_, s, lam = st.cpu().numpy(), r["out"].cpu().numpy(), r["status"].cpu().numpy(), r["lam"][-1].cpu().numpy()
+    rows, refs = [], []
+    for i in range(n):
+        o = pc.make_oracle()
+        x, t, held = np.concatenate([q[i], v[i]]), 0.0, v[i].copy()
+        for _ in range(nt):
+            o.set_prev_velocity(held)
+            last = o.eval(x[:30], x[30:], t)
+            held = x[30:].copy()
+            x, _, lam_s = rc.oracle_rigid_steps(o, x, np.concatenate([np.zeros(6), last["tau"]]), 0, kv, 1)
+            t += DT
+        refs.append((x, t, last, lam_s))
+        rows.append((i, rel_err(a[i, :60], x), vec_err(o_[i, 0:24], last["tau"]), vec_err(o_[i, 24:36], last["f"]), vec_err(lam[i], lam_s), int(s[i, 0]), last["k"], int(s[i, 2])))
+        print("\nzoh_rigid vs the CPU loop, robot %d: state %.2e  tau %.2e  f %.2e  lambda %.2e  k %d (oracle %d)  flags %d" % rows[-1], end="")
+    print()
+    for i in range(n):
+        x, t, last, lam_s = refs[i]
+        assert close(a[i, :60], x, 1e-7) and a[i, 90] == t, rows[i]
+        assert close(o_[i, 0:24], last["tau"], TOL_REL) and close(o_[i, 24:36], last["f"], TOL_REL, scale=WEIGHT), rows[i]
+        assert s[i, 0] == last["k"] and (s[i, 2] & 31) == 0, rows[i]            # no controller flag (the plant's informational ones lie above)
+    ctl.close()
+
+
+# ------------------------------------------------------------------------------- 8. NaN isolation
+@pytest.mark.parametrize("where", ["state", "meas"])
+def test_a_nan_flags_its_robot_alone(zrg, where):
+    from linearmpchumanoid_amd import capi
+    ctl = zrg["ctl"]
+    bad, others = 5, [i for i in range(B) if i != 5]
+    runs = []
+    for broken in (False, True):
+        meas, st = zrg["meas"].clone(), _fresh(ctl, zrg["S"])
+        if broken and where == "meas":
+            meas[2, bad, 8] = float("nan")
+        if broken and where == "state":
+            st[bad, 11] = float("nan")
+        m = ctl.new_metrics(0.0, np.inf)
+        r = _everything(ctl, zrg, NT, 3, 50.0, every=1, metrics=m, meas=meas, st=st, mode="per_tick")
+        torch.cuda.synchronize()
+        runs.append(dict(r, metrics=m))
+    good, got = runs
+    assert int(got["status"][bad, 2]) & capi.FLAG_NONFINITE and not int(good["status"][bad, 2]) & capi.FLAG_NONFINITE
+    assert not (good["status"][:, 2] & capi.FLAG_NONFINITE).any() and not (got["status"][others, 2] & capi.FLAG_NONFINITE).any()
+    for k in ("state", "out", "status", "metrics", "mem"):
+        assert _same(good[k][others], got[k][others]), k
+    for k in ("log", "trace", "applied", "lam"):
+        assert _same(good[k][:, others], got[k][:, others]), k
+        if where == "meas":
+            assert _same(good[k][:2], got[k][:2]), k               # and the robot itself up to the tick of the NaN
+
+
+# ------------------------------------------------------------------------------- 9. refusals
+def test_refusals(zrg):
+    from linearmpchumanoid_amd import capi
+    S, ctl = zrg["S"], zrg["ctl"]
+    L = capi.lib()
+    p = lambda t: C.c_void_p(t.data_ptr())
+    err = lambda: L.lmh_last_error().decode()
+    dev = ctl.device
+    sent = lambda *shape: torch.full(shape, -7.0, dtype=torch.float64, device=dev)
+    st, out, status = _fresh(ctl, S), ctl.new_out(), ctl.new_status()
+    mem, applied, lam, trace, meas = ctl.new_act_mem(zrg["tau0"]), sent(NT, B, 24), sent(NT, B, 12), sent(NT, B, 180), zrg["meas"].contiguous()
+    torch.cuda.synchronize()
+    bufs = (st, out, status, mem, applied, lam, trace)
+    sentinels = tuple(x.clone() for x in bufs)
+
+    def untouched():
+        torch.cuda.synchronize()
+        return all(_same(x, y) for x, y in zip(bufs, sentinels))
+
+    s = ctl._stream()
+    Z, ZI = L.lmh_rollout_zoh_rigid, L.lmh_rollout_zoh_io
+    rec = lambda cls, fields: cls(**{k: (p(v) if isinstance(v, torch.Tensor) else v) for k, v in fields.items()})
+
+    def call(n_ticks=NT, n_substeps=3, state=st, handle=ctl, opts=None, io=None, **fields):
+        o = None if opts is None else C.byref(rec(capi.LmhZohOpts, opts))
+        i = None if io is None else C.byref(rec(capi.LmhZohIo, io))
+        fields.setdefault("d_lambda", lam)
+        return Z(handle._h, None if state is None else p(state), p(out), p(status), o, i, C.byref(rec(capi.LmhZohRigid, fields)), n_ticks, n_substeps, s)
+
+    own = [(dict(source=4), "lmh_rollout_zoh_rigid: source must be 0, LMH_RIGID_FIXED, LMH_RIGID_PER_TICK or LMH_RIGID_PLAN"),
+           (dict(source=-1), "lmh_rollout_zoh_rigid: source must be 0, LMH_RIGID_FIXED, LMH_RIGID_PER_TICK or LMH_RIGID_PLAN"),
+           (dict(source=1, reserved=1), "lmh_rollout_zoh_rigid: reserved must be 0"),
+           (dict(source=0, reserved=2), "lmh_rollout_zoh_rigid: reserved must be 0"),
+           (dict(source=1, kv=-1.0), "lmh_rollout_zoh_rigid: kv must be finite and >= 0"),
+           (dict(source=1, kv=float("nan")), "lmh_rollout_zoh_rigid: kv must be finite and >= 0"),
+           (dict(source=3, kv=float("inf")), "lmh_rollout_zoh_rigid: kv must be finite and >= 0"),
+           (dict(source=2), "lmh_rollout_zoh_rigid: source LMH_RIGID_PER_TICK needs d_mode"),
+           (dict(source=3, d_mode=zrg["per_tick"]), "lmh_rollout_zoh_rigid: d_mode must be NULL with source LMH_RIGID_PLAN (the robot's own plan decides)")]
+    io_on = dict(actuators=1, d_act_mem=mem, d_applied=applied, d_meas=meas)
+    for fields, words in own:
+        assert call(io=io_on, opts=dict(d_trace=trace, trace_every=1), **fields) == -2 and err() == words, fields
+    assert call(n_ticks=0, source=2, d_mode=zrg["per_tick"], io=io_on) == 0         # no tick: nothing enqueued
+    assert untouched()
+    # every refusal of lmh_rollout_zoh_io, in its words, with the rigid hold on
+    on = dict(source=2, d_mode=zrg["per_tick"], kv=50.0)
+    for io, words in ((dict(actuators=2, d_act_mem=mem), "lmh_rollout_zoh_io: actuators must be 0 or 1"), (dict(reserved=1), "lmh_rollout_zoh_io: reserved must be 0"),
+                      (dict(actuators=1), "lmh_rollout_zoh_io: actuators = 1 needs d_act_mem")):
+        assert call(io=io, **on) == -2 and err() == words, io
+    shared = [dict(wrench_per_tick=2, d_base_wrench=zrg["bw_seq"]), dict(pushes=2), dict(reserved=1), dict(wrench_per_tick=1), dict(d_trace=trace), dict(trace_every=2),
+              dict(d_trace=trace, trace_every=-1)]
+    for o in shared:
+        assert call(opts=o, io=io_on, **on) == -2
+        mine = err()
+        assert ZI(ctl._h, p(st), p(out), p(status), C.byref(rec(capi.LmhZohOpts, o)), C.byref(rec(capi.LmhZohIo, io_on)), NT, 3, s) == -2
+        assert err() == mine and mine.startswith("lmh_rollout_zoh_ex: "), o
+    assert call(n_substeps=0, opts=dict(pushes=1), **on) == -2 and err().startswith("lmh_rollout_zoh_ex: pushes = 1 needs n_substeps > 0")
+    assert call(state=None, **on) == -2 and err() == "lmh_rollout_zoh: null device pointer"
+    for n_ticks, n_sub in ((-1, 1), (1, -1)):
+        assert call(n_ticks=n_ticks, n_substeps=n_sub, **on) == -2 and err() == "lmh_rollout_zoh: n_ticks and n_substeps must be >= 0"
+    assert Z(None, p(st), p(out), p(status), None, None, C.byref(rec(capi.LmhZohRigid, on)), NT, 3, s) == -2 and err() == "null handle"
+    assert untouched()
+    # Python: shapes and kinds before the C call
+    for bad_call in (lambda: ctl.rollout_zoh_rigid(st, NT, 1, mode="walk"), lambda: ctl.rollout_zoh_rigid(st, NT, 1, mode=zrg["per_tick"][0:3].contiguous()),
+                     lambda: ctl.rollout_zoh_rigid(st, NT, 1, mode=zrg["mode3"].long()), lambda: ctl.rollout_zoh_rigid(st, NT, 1, mode=zrg["mode3"].cpu()),
+                     lambda: ctl.rollout_zoh_rigid(st, NT, 1, lam=lam[0:3]), lambda: ctl.rollout_zoh_rigid(st, NT, 1, lam=lam.float()), lambda: ctl.rollout_zoh_rigid(st, -1, 1)):
+        with pytest.raises(ValueError):
+            bad_call()
+    with pytest.raises(TypeError):
+        ctl.rollout_zoh_rigid(st, NT, 1, servo="integrate")
+    with pytest.raises(capi.LmhError, match="kv must be finite"):
+        ctl.rollout_zoh_rigid(st, NT, 1, kv=-2.0)
+    assert untouched()
+    # MIXED and FP32 handles are refused in lmh_rollout_zoh's words
+    for prec in (capi.PRECISION_MIXED, capi.PRECISION_FP32):
+        other = make_controller(B, DT, TH, S["zcom"], precision=prec)
+        other.set_refs_stance(2.0, 2)
+        assert call(handle=other, **on) == -2 and "lmh_rollout_zoh: LMH_PRECISION_FP64 handles only" in err()
+        other.close()
+    assert untouched()
+
+
+# ------------------------------------------------------------------------------- 10. graph capture
+def test_captured_on_a_fresh_handle_replays_to_the_eager_bytes(zrg):
+    from linearmpchumanoid_amd import capi, metrics as hm
+    S = zrg["S"]
+    L = capi.lib()
+    p = lambda t: C.c_void_p(t.data_ptr())
+    ctl = make_controller(B, DT, TH, S["zcom"], warm_start=1)     # fresh: no launch before the capture
+    ctl.set_refs_stance(2.0, 2)
+    ctl.set_pushes(zrg["ticks"], zrg["dv"])
+    rec = zrg["rec_np"]
+    ctl.set_actuators(tau_max=rec[:, 0:24], alpha=rec[:, 24:48], delay=rec[:, 48])
+    dev = ctl.device
+    ident = torch.as_tensor(hm.identity(B, 0.3, 0.2)).to(dev)     # (not new_metrics: no launch of the handle's before the capture)
+    st0 = _fresh(ctl, S)
+    mem0 = zrg["tau0"].repeat(1, 8).contiguous()
+    sent = lambda *shape: torch.full(shape, -7.0, dtype=torch.float64, device=dev)
+    st, out, status, log, trace, m, mem, applied, lam = (st0.clone(), sent(B, 80), ctl.new_status(), sent(NT, B, 36), sent(3, B, 180), ident.clone(), mem0.clone(),
+                                                         sent(NT, B, 24), sent(NT, B, 12))
+    bw, refs, meas, modes = zrg["bw_seq"].contiguous(), zrg["refs"].contiguous(), zrg["meas"].contiguous(), zrg["per_tick"].to(dev).contiguous()
+    opts = capi.LmhZohOpts(d_base_wrench=p(bw), d_ref=p(refs), d_log=p(log), d_trace=p(trace), d_metrics=p(m), trace_every=2, wrench_per_tick=1, pushes=1, reserved=0)
+    io = capi.LmhZohIo(d_meas=p(meas), d_act_mem=p(mem), d_applied=p(applied), actuators=1, reserved=0)
+    rg = capi.LmhZohRigid(d_mode=p(modes), d_lambda=p(lam), kv=50.0, source=capi.RIGID_PER_TICK, reserved=0)
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        rc_ = L.lmh_rollout_zoh_rigid(ctl._h, p(st), p(out), p(status), C.byref(opts), C.byref(io), C.byref(rg), NT, 3, ctl._stream())
+    assert rc_ == 0
+    torch.cuda.synchronize()
+    assert _same(st, st0) and bool((out == -7).all()) and bool((lam == -7).all()) and _same(m, ident) and _same(mem, mem0)       # captured, not run
+    g.replay()
+    torch.cuda.synchronize()
+    got = [x.clone() for x in (st, out, status, log, trace, m, mem, applied, lam)]
+    del g
+    e_st, e_m, e_mem = st0.clone(), ident.clone(), mem0.clone()
+    e = ctl.rollout_zoh_rigid(e_st, NT, 3, mode=modes, kv=50.0, lam=sent(NT, B, 12), meas=meas, actuators=True, act_mem=e_mem, applied=sent(NT, B, 24), base_wrench=bw,
+                              ref=refs, pushes=True, log=sent(NT, B, 36), trace_every=2, trace=sent(3, B, 180), metrics=e_m, out=sent(B, 80))
+    torch.cuda.synchronize()
+    for name, a, b in zip(("state", "out", "status", "log", "trace", "metrics", "act_mem", "applied", "lam"), got,
+                          (e_st, e["out"], e["status"], e["log"], e["trace"], e_m, e_mem, e["applied"], e["lam"])):
+        assert _same(a, b), name
+    assert not bool((got[8] == -7).any()) and float(got[5][0, 0]) == NT and not _same(got[6], mem0)
+    ctl.close()
