@@ -87,6 +87,20 @@ def _dev_ptr(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+_NP_DTYPE = {torch.float64: np.float64, torch.int32: np.int32}     # the array dtype that becomes a tensor of the key's
+
+
+# rollout_zoh_ex's option keywords and their defaults: what rollout_zoh_box, _io, _servo and _rigid take as they are
+_ZOH_OPTIONS = dict(base_wrench=None, ref=None, pushes=False, log=False, trace_every=0, trace=None, metrics=None, out=None, status=None)
+
+
+def _count(name, n):
+    """A whole number >= 0, as an int."""
+    if int(n) != n or n < 0:
+        raise ValueError(f"{name} must be a whole number >= 0")
+    return int(n)
+
+
 def _split(rec, fields):
     """Named views of records [.., stride] (tensor or array) by one of the name -> (offset, shape) tables."""
     lead = tuple(rec.shape[:-1])
@@ -620,10 +634,8 @@ class BatchedController:
         """n_substeps RK4 steps of cfg.dt on (q, v) of the state records [B,96], in place, with tau [B,30] held (None: passive); t advances,
         v_prev stays.  The planes of set_ground are honoured.  -> (state, flags [B] int32, OR-ed over the substeps)."""
         tau, state = self._batch("tau", tau, 30, optional=True), self._batch("state", state, capi.STATE_STRIDE, in_place=True)
-        if int(n_substeps) != n_substeps or n_substeps < 0:
-            raise ValueError("n_substeps must be a whole number >= 0")
         flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
-        check(capi.lib().lmh_plant_step(self._h, _dev_ptr(state), _dev_ptr(tau), int(n_substeps), _dev_ptr(flags), self._stream()))
+        check(capi.lib().lmh_plant_step(self._h, _dev_ptr(state), _dev_ptr(tau), _count("n_substeps", n_substeps), _dev_ptr(flags), self._stream()))
         return state, flags
 
     def plant_step_servo(self, state, setpoint, tau=None, n_substeps=1):
@@ -633,10 +645,8 @@ class BatchedController:
         a servo table runs with zero gains.  -> (state, flags [B] int32, OR-ed over the substeps)."""
         tau, state = self._batch("tau", tau, 30, optional=True), self._batch("state", state, capi.STATE_STRIDE, in_place=True)
         setpoint = self._batch("setpoint", setpoint, capi.SETPOINT_STRIDE)
-        if int(n_substeps) != n_substeps or n_substeps < 0:
-            raise ValueError("n_substeps must be a whole number >= 0")
         flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
-        check(capi.lib().lmh_plant_step_servo(self._h, _dev_ptr(state), _dev_ptr(tau), _dev_ptr(setpoint), int(n_substeps), _dev_ptr(flags), self._stream()))
+        check(capi.lib().lmh_plant_step_servo(self._h, _dev_ptr(state), _dev_ptr(tau), _dev_ptr(setpoint), _count("n_substeps", n_substeps), _dev_ptr(flags), self._stream()))
         return state, flags
 
     # -- rigid-contact plant (include/lmh.h, lmh_plant_derivative_rigid): the held soles as constraints, the contact wrench their multiplier
@@ -673,6 +683,30 @@ class BatchedController:
         check(capi.lib().lmh_plant_step_rigid(self._h, _dev_ptr(state), _dev_ptr(tau), _dev_ptr(mode), kv, int(n_substeps), _dev_ptr(lam), _dev_ptr(flags), self._stream()))
         return state, lam, flags
 
+    # -- zero-order-hold closed loop (include/lmh.h, lmh_rollout_zoh): the argument handling the seven calls share
+    def _tick_records(self, name, v, n, tail, dtype=torch.float64, out=False, at_least=False, also=()):
+        """Per-tick records [n,B,*tail] of a launch (or one of the whole shapes `also`; at_least: [m,B,*tail] with m >= n) -> (the tensor the
+        caller is handed back, the tensor whose address is passed: a one-word placeholder when the first is empty, since an empty tensor has
+        no address and with no tick no record is touched).  None and False are (None, None).  An input (out=False) may be an array of the
+        dtype and is made contiguous; an output is written in place, so it is contiguous as it comes, and True allocates zeros."""
+        if v is None or (v is False and out):
+            return None, None
+        shape = (n, self.B) + tuple(tail)
+        if v is True and out:
+            t = torch.zeros(shape, dtype=dtype, device=self.device)
+        else:
+            t = v
+            if not out and isinstance(t, np.ndarray) and t.dtype == _NP_DTYPE[dtype]:
+                t = torch.from_numpy(np.ascontiguousarray(t)).to(self.device)
+            has = tuple(t.shape) if isinstance(t, torch.Tensor) else None
+            fits = has == shape or has in also or (at_least and has is not None and len(has) == len(shape) and has[1:] == shape[1:] and has[0] >= n)
+            if not fits or t.dtype != dtype or t.device != self.device or (out and not t.is_contiguous()):
+                what = " or ".join(str(list(x)) for x in (shape,) + tuple(also)) + (" (or longer)" if at_least else "")
+                raise ValueError(f"{name} must be a {'contiguous ' if out else ''}{what} {str(dtype)[6:]} tensor on {self.device}")
+            if not out:
+                t = t.contiguous()
+        return t, (t if t.numel() > 0 else torch.empty((1,), dtype=dtype, device=self.device))
+
     def rollout_zoh(self, state, n_ticks, n_substeps, base_wrench=None, log=False, out=None, status=None, ref=None):
         """lmh_rollout_zoh: n_ticks rounds of { stand_step ; plant_step([base_wrench | out.tau], n_substeps) } in one launch, bit for bit
         what that loop leaves; state [B,96] is updated in place.  The control period is n_substeps * cfg.dt.  base_wrench [B,6]: an external
@@ -684,19 +718,14 @@ class BatchedController:
         rollout_zoh_ex and rollout_zoh_io; the evaluation is not told about the ground.
         -> (out, status), plus the log [n_ticks,B,36] (tau | f of every tick) when log is asked for."""
         state, bw = self._batch("state", state, capi.STATE_STRIDE, in_place=True), self._batch("base_wrench", base_wrench, 6, optional=True)
-        for name, n in (("n_ticks", n_ticks), ("n_substeps", n_substeps)):
-            if int(n) != n or n < 0:
-                raise ValueError(f"{name} must be a whole number >= 0")
-        out, status, lg = self._rollout_buffers(int(n_ticks), out, status, log)
+        n, ns = _count("n_ticks", n_ticks), _count("n_substeps", n_substeps)
+        out, status, lg = self._rollout_buffers(n, out, status, log)
+        args = (self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), _dev_ptr(bw), _dev_ptr(lg))
         if ref is not None:
-            ref = self._ref_records(ref, (int(n_ticks),))
-            if ref.numel() == 0:                                   # (an empty tensor has no address to pass; with no tick no record is read)
-                ref = torch.empty((1,), dtype=torch.float64, device=self.device)
-            check(capi.lib().lmh_rollout_zoh_ref(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), _dev_ptr(bw), _dev_ptr(lg), _dev_ptr(ref),
-                                                 int(n_ticks), int(n_substeps), self._stream()))
-            return (out, status) if lg is None else (out, status, lg)
-        check(capi.lib().lmh_rollout_zoh(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), _dev_ptr(bw), _dev_ptr(lg),
-                                         int(n_ticks), int(n_substeps), self._stream()))
+            ref = self._tick_records("ref", self._ref_records(ref, (n,)), n, (capi.MPC_STRIDE,))[1]
+            check(capi.lib().lmh_rollout_zoh_ref(*args, _dev_ptr(ref), n, ns, self._stream()))
+        else:
+            check(capi.lib().lmh_rollout_zoh(*args, n, ns, self._stream()))
         return (out, status) if lg is None else (out, status, lg)
 
     def rollout_zoh_ex(self, state, n_ticks, n_substeps, base_wrench=None, ref=None, pushes=False, log=False, trace_every=0, trace=None,
@@ -708,7 +737,8 @@ class BatchedController:
         write_trace's sample_dt is trace_every * n_substeps * cfg.dt) and a metrics record (metrics: new_metrics' [B,208], folded once per
         control tick at the tick's end; the records accumulate over launches).  With none of them the call is rollout_zoh's launch.
         -> dict(out, status, log, trace); log and trace are None when not asked for."""
-        return self._rollout_zoh_opts(state, n_ticks, n_substeps, base_wrench, ref, pushes, log, trace_every, trace, metrics, out, status, None)
+        return self._zoh_launch(state, n_ticks, n_substeps, dict(base_wrench=base_wrench, ref=ref, pushes=pushes, log=log, trace_every=trace_every, trace=trace,
+                                                                 metrics=metrics, out=out, status=status), capi.lib().lmh_rollout_zoh_ex)
 
     def rollout_zoh_box(self, state, box, n_ticks, n_substeps, mpc=True, base_wrench=None, pushes=False, log=False, trace_every=0, trace=None,
                         metrics=None, out=None, status=None, ref=None):
@@ -721,17 +751,29 @@ class BatchedController:
         if ref is not None:
             raise ValueError("rollout_zoh_box takes no ref: the box-constrained step is the reference (the two are exclusive)")
         bx, ns, sets = self._box(box)
-        if int(n_ticks) != n_ticks or n_ticks < 0:
-            raise ValueError("n_ticks must be a whole number >= 0")
-        n = int(n_ticks)
-        tr = torch.zeros((n, self.B, capi.MPC_STRIDE), dtype=torch.float64, device=self.device) if mpc is True else (mpc if mpc is not False else None)
-        if tr is not None and (not isinstance(tr, torch.Tensor) or tr.dtype != torch.float64 or tr.device != self.device or not tr.is_contiguous()
-                               or tr.numel() < n * self.B * capi.MPC_STRIDE):
-            raise ValueError(f"mpc must be a contiguous [{n},{self.B},{capi.MPC_STRIDE}] float64 tensor on {self.device}")
-        mp_arg = tr if (tr is None or tr.numel() > 0) else torch.empty((1,), dtype=torch.float64, device=self.device)
-        res = self._rollout_zoh_opts(state, n_ticks, n_substeps, base_wrench, None, pushes, log, trace_every, trace, metrics, out, status,
-                                     (_dev_ptr(bx), ns, sets, _dev_ptr(mp_arg)))
+        tr, tr_arg = self._tick_records("mpc", mpc, _count("n_ticks", n_ticks), (capi.MPC_STRIDE,), out=True, at_least=True)
+        res = self._zoh_launch(state, n_ticks, n_substeps, dict(base_wrench=base_wrench, pushes=pushes, log=log, trace_every=trace_every, trace=trace, metrics=metrics,
+                                                                out=out, status=status), capi.lib().lmh_rollout_zoh_box, _dev_ptr(bx), ns, sets, _dev_ptr(tr_arg))
         res["mpc"] = tr
+        return res
+
+    def _zoh_io(self, n, meas=None, actuators=False, act_mem=None, applied=False):
+        """rollout_zoh_io's own arguments for a launch of n ticks -> (lmh_zoh_io record, the applied tensor or None)"""
+        ms = self._tick_records("meas", meas, n, (60,))[1]
+        ap, ap_arg = self._tick_records("applied", applied, n, (24,), out=True)
+        if actuators and act_mem is None:
+            raise ValueError("rollout_zoh_io: actuators=True needs act_mem (new_act_mem)")
+        mem = self._batch("act_mem", act_mem, capi.ACT_MEM_STRIDE, optional=True, in_place=True)
+        io = capi.LmhZohIo(d_meas=_dev_ptr(ms), d_act_mem=_dev_ptr(mem), d_applied=_dev_ptr(ap_arg), actuators=int(bool(actuators)), reserved=0)
+        io.keep = (ms, mem, ap_arg)                                # (the record holds addresses only)
+        return io, ap
+
+    def _zoh_io_launch(self, state, n, n_substeps, kw, call, record):
+        """The two calls that take rollout_zoh_io's keywords as they are (kw: its own arguments and rollout_zoh_ex's options together) with a
+        record of their own behind the io record -> rollout_zoh_ex's dict plus applied."""
+        io, ap = self._zoh_io(n, kw.pop("meas", None), kw.pop("actuators", False), kw.pop("act_mem", None), kw.pop("applied", False))
+        res = self._zoh_launch(state, n, n_substeps, kw, call, C.byref(io), C.byref(record))
+        res["applied"] = ap
         return res
 
     def rollout_zoh_servo(self, state, n_ticks, n_substeps, servo="integrate", **io):
@@ -741,25 +783,12 @@ class BatchedController:
         (trajectories.servo_setpoint; needs n_substeps > 0); a tensor [n_ticks,B,48]: the caller's setpoint for every control tick and
         robot; None: no servo, rollout_zoh_io's launch.  log and applied keep the commanded and the feed-forward torques: the PD part
         changes at every RK4 stage and is not recorded.  -> rollout_zoh_io's dict."""
-        if int(n_ticks) != n_ticks or n_ticks < 0:
-            raise ValueError("n_ticks must be a whole number >= 0")
-        n = int(n_ticks)
-        if servo is None:
-            sv = capi.LmhZohServo(d_setpoint=None, mode=0, reserved=0)
-        elif isinstance(servo, str):
-            if servo != "integrate":
-                raise ValueError('servo must be "integrate", a setpoint tensor [n_ticks,B,48] or None')
-            sv = capi.LmhZohServo(d_setpoint=None, mode=capi.SERVO_INTEGRATE, reserved=0)
-        else:
-            sp = servo
-            if isinstance(sp, np.ndarray) and sp.dtype == np.float64:
-                sp = torch.from_numpy(np.ascontiguousarray(sp)).to(self.device)
-            if not isinstance(sp, torch.Tensor) or sp.dtype != torch.float64 or sp.device != self.device or tuple(sp.shape) != (n, self.B, capi.SETPOINT_STRIDE) \
-                    or not sp.is_contiguous():
-                raise ValueError(f"servo must be a contiguous [{n},{self.B},{capi.SETPOINT_STRIDE}] float64 tensor on {self.device}")
-            keep = sp if sp.numel() > 0 else torch.empty((1,), dtype=torch.float64, device=self.device)
-            sv = capi.LmhZohServo(d_setpoint=_dev_ptr(keep), mode=capi.SERVO_CALLER, reserved=0)
-        return self.rollout_zoh_io(state, n, n_substeps, _servo_call=sv, **io)
+        n = _count("n_ticks", n_ticks)
+        if isinstance(servo, str) and servo != "integrate":
+            raise ValueError('servo must be "integrate", a setpoint tensor [n_ticks,B,48] or None')
+        sp = None if isinstance(servo, str) else self._tick_records("servo", servo, n, (capi.SETPOINT_STRIDE,))[1]
+        mode = 0 if servo is None else capi.SERVO_INTEGRATE if sp is None else capi.SERVO_CALLER
+        return self._zoh_io_launch(state, n, n_substeps, io, capi.lib().lmh_rollout_zoh_servo, capi.LmhZohServo(d_setpoint=_dev_ptr(sp), mode=mode, reserved=0))
 
     def rollout_zoh_rigid(self, state, n_ticks, n_substeps, mode=None, kv=0.0, lam=False, **io):
         """lmh_rollout_zoh_rigid: rollout_zoh_io (whose keywords it takes as they are) with the rigid-contact plant in every hold -- bit for
@@ -769,40 +798,18 @@ class BatchedController:
         (trajectories.rigid_modes).  One mode serves every piece of a tick's hold.  lam=True: the multipliers [n_ticks,B,12] at the first
         stage of the last substep of every tick's hold are returned under "lam" (a tensor: filled).  There is no impact model and the
         contact stays bilateral (include/lmh.h); the ground and servo tables are not read.  -> rollout_zoh_io's dict plus lam."""
-        if int(n_ticks) != n_ticks or n_ticks < 0:
-            raise ValueError("n_ticks must be a whole number >= 0")
-        n = int(n_ticks)
-        md = None
-        if mode is None:
-            source = capi.RIGID_FIXED
-        elif isinstance(mode, str):
-            if mode != "plan":
-                raise ValueError('mode must be None, an int32 [B] or [n_ticks,B] tensor, or "plan"')
-            source = capi.RIGID_PLAN
-        else:
-            if isinstance(mode, np.ndarray) and mode.dtype == np.int32:
-                mode = torch.from_numpy(np.ascontiguousarray(mode)).to(self.device)
-            if not isinstance(mode, torch.Tensor) or mode.dtype != torch.int32 or mode.device != self.device or tuple(mode.shape) not in ((self.B,), (n, self.B)):
-                raise ValueError(f"mode must be a [{self.B}] or [{n},{self.B}] int32 tensor on {self.device}")
-            source = capi.RIGID_FIXED if mode.ndim == 1 else capi.RIGID_PER_TICK
-            md = mode.contiguous()
-            if md.numel() == 0:                                    # (an empty tensor has no address to pass; with no tick no record is read)
-                md = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        if lam is True:
-            lm = torch.zeros((n, self.B, 12), dtype=torch.float64, device=self.device)
-        elif lam is False or lam is None:
-            lm = None
-        else:
-            lm = lam
-            if not isinstance(lm, torch.Tensor) or lm.dtype != torch.float64 or lm.device != self.device or tuple(lm.shape) != (n, self.B, 12) or not lm.is_contiguous():
-                raise ValueError(f"lam must be a contiguous [{n},{self.B},12] float64 tensor on {self.device}")
-        lm_arg = lm if (lm is None or lm.numel() > 0) else torch.empty((1,), dtype=torch.float64, device=self.device)
+        n = _count("n_ticks", n_ticks)
+        if isinstance(mode, str) and mode != "plan":
+            raise ValueError('mode must be None, an int32 [B] or [n_ticks,B] tensor, or "plan"')
+        md = None if isinstance(mode, str) else self._tick_records("mode", mode, n, (), dtype=torch.int32, also=((self.B,),))[1]
+        source = capi.RIGID_PLAN if isinstance(mode, str) else capi.RIGID_PER_TICK if (md is not None and mode.ndim == 2) else capi.RIGID_FIXED
+        lm, lm_arg = self._tick_records("lam", lam, n, (12,), out=True)
         rg = capi.LmhZohRigid(d_mode=_dev_ptr(md), d_lambda=_dev_ptr(lm_arg), kv=float(kv), source=source, reserved=0)
-        res = self.rollout_zoh_io(state, n, n_substeps, _rigid_call=rg, **io)
+        res = self._zoh_io_launch(state, n, n_substeps, io, capi.lib().lmh_rollout_zoh_rigid, rg)
         res["lam"] = lm
         return res
 
-    def rollout_zoh_io(self, state, n_ticks, n_substeps, meas=None, actuators=False, act_mem=None, applied=False, _servo_call=None, _rigid_call=None, **ex):
+    def rollout_zoh_io(self, state, n_ticks, n_substeps, meas=None, actuators=False, act_mem=None, applied=False, **ex):
         """lmh_rollout_zoh_io: rollout_zoh_ex (whose keywords it takes as they are) with sensing and actuation between controller and plant.
         meas [n_ticks,B,60]: what is added to q | v as control tick j's evaluation sees them (the plant goes on from the true state; v_prev
         keeps the measured v).  actuators=True: the set_actuators records -- latency, torque limit, first-order lag -- stand between the
@@ -810,91 +817,33 @@ class BatchedController:
         required).  applied=True: the torques the plant received [n_ticks,B,24] are returned under "applied" (a tensor: filled).  log, trace
         and metrics keep the COMMANDED torques; status[:, 2] & capi.FLAG_TAU_LIMIT: a torque was cut.  With none of the four the call is
         rollout_zoh_ex's launch.  trajectories.actuator_step states the actuator.  -> rollout_zoh_ex's dict plus applied."""
-        if int(n_ticks) != n_ticks or n_ticks < 0:
-            raise ValueError("n_ticks must be a whole number >= 0")
-        n = int(n_ticks)
-
-        def records(name, t, width):
-            if isinstance(t, np.ndarray) and t.dtype == np.float64:
-                t = torch.from_numpy(np.ascontiguousarray(t)).to(self.device)
-            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or t.device != self.device or tuple(t.shape) != (n, self.B, width) or not t.is_contiguous():
-                raise ValueError(f"{name} must be a contiguous [{n},{self.B},{width}] float64 tensor on {self.device}")
-            return t
-
-        ms = None if meas is None else records("meas", meas, 60)
-        ap = torch.zeros((n, self.B, 24), dtype=torch.float64, device=self.device) if applied is True else (None if applied is False or applied is None else records("applied", applied, 24))
-        if actuators and act_mem is None:
-            raise ValueError("rollout_zoh_io: actuators=True needs act_mem (new_act_mem)")
-        mem = self._batch("act_mem", act_mem, capi.ACT_MEM_STRIDE, optional=True, in_place=True)
-
-        def arg(t):                                                # (an empty tensor has no address to pass; with no tick no record is touched)
-            return _dev_ptr(t if (t is None or t.numel() > 0) else torch.empty((1,), dtype=torch.float64, device=self.device))
-
-        io = capi.LmhZohIo(d_meas=arg(ms), d_act_mem=_dev_ptr(mem), d_applied=arg(ap), actuators=int(bool(actuators)), reserved=0)
-        kw = dict(base_wrench=None, ref=None, pushes=False, log=False, trace_every=0, trace=None, metrics=None, out=None, status=None)
-        if set(ex) - set(kw):
-            raise TypeError(f"rollout_zoh_io: unexpected keyword {sorted(set(ex) - set(kw))[0]!r}")
-        kw.update(ex)
-        res = self._rollout_zoh_opts(state, n_ticks, n_substeps, kw["base_wrench"], kw["ref"], kw["pushes"], kw["log"], kw["trace_every"], kw["trace"],
-                                     kw["metrics"], kw["out"], kw["status"], None, io_call=io, servo_call=_servo_call, rigid_call=_rigid_call)
+        n = _count("n_ticks", n_ticks)
+        io, ap = self._zoh_io(n, meas, actuators, act_mem, applied)
+        res = self._zoh_launch(state, n, n_substeps, ex, capi.lib().lmh_rollout_zoh_io, C.byref(io))
         res["applied"] = ap
         return res
 
-    def _rollout_zoh_opts(self, state, n_ticks, n_substeps, base_wrench, ref, pushes, log, trace_every, trace, metrics, out, status, box_call, io_call=None, servo_call=None, rigid_call=None):
-        """The argument handling rollout_zoh_ex, rollout_zoh_box and rollout_zoh_io share; box_call: None, or lmh_rollout_zoh_box's (d_box, n_samples,
-        n_sets, d_mpc); io_call: None, or lmh_rollout_zoh_io's record; servo_call: None, or lmh_rollout_zoh_servo's record (then with io_call); rigid_call: None,
-        or lmh_rollout_zoh_rigid's record (then with io_call and without servo_call)."""
+    def _zoh_launch(self, state, n_ticks, n_substeps, kw, call, *own):
+        """The one launch of rollout_zoh_ex, _box, _io, _servo and _rigid: forms lmh_zoh_opts from kw, rollout_zoh_ex's option keywords (another
+        name is a TypeError), and makes the C call `call` with `own`, the arguments it has between the options and the counts.
+        -> dict(out, status, log, trace)"""
+        if not kw.keys() <= _ZOH_OPTIONS.keys():
+            raise TypeError(f"{call.__name__[4:]}: unexpected keyword {sorted(kw.keys() - _ZOH_OPTIONS.keys())[0]!r}")
+        o = {**_ZOH_OPTIONS, **kw}
         state = self._batch("state", state, capi.STATE_STRIDE, in_place=True)
-        for name, n in (("n_ticks", n_ticks), ("n_substeps", n_substeps), ("trace_every", trace_every)):
-            if int(n) != n or n < 0:
-                raise ValueError(f"{name} must be a whole number >= 0")
-        n_ticks, n_substeps, trace_every = int(n_ticks), int(n_substeps), int(trace_every)
-        per_tick = base_wrench is not None and getattr(base_wrench, "ndim", 0) == 3
-        if per_tick:
-            if isinstance(base_wrench, np.ndarray) and base_wrench.dtype == np.float64:           # (arrays as _ref_records takes them)
-                base_wrench = torch.from_numpy(np.ascontiguousarray(base_wrench)).to(self.device)
-            if not isinstance(base_wrench, torch.Tensor) or base_wrench.dtype != torch.float64 or tuple(base_wrench.shape) != (n_ticks, self.B, 6) \
-                    or base_wrench.device != self.device:
-                raise ValueError(f"base_wrench must be a [{self.B},6] or [{n_ticks},{self.B},6] float64 tensor on {self.device} (or such an array)")
-            bw = base_wrench.contiguous()
-            if bw.numel() == 0:                                    # (an empty tensor has no address to pass; with no tick no record is read)
-                bw = torch.empty((1,), dtype=torch.float64, device=self.device)
-        else:
-            bw = self._batch("base_wrench", base_wrench, 6, optional=True)
-        if trace is not None:                                      # the kernel writes n_samples records into it: a smaller buffer is an out-of-bounds write
-            n_samples = capi.lib().lmh_trace_samples(n_ticks, trace_every)
-            if not isinstance(trace, torch.Tensor) or trace.dtype != torch.float64 or trace.device != self.device or not trace.is_contiguous() \
-                    or trace.ndim != 3 or tuple(trace.shape[1:]) != (self.B, capi.TRACE_STRIDE) or trace.shape[0] < n_samples:
-                raise ValueError(f"trace must be a contiguous [n,{self.B},{capi.TRACE_STRIDE}] float64 tensor on {self.device} with n >= {n_samples}")
-        out, status, lg = self._rollout_buffers(n_ticks, out, status, log)
-        if ref is not None:
-            ref = self._ref_records(ref, (n_ticks,))
-            if ref.numel() == 0:
-                ref = torch.empty((1,), dtype=torch.float64, device=self.device)
-        if trace is None and trace_every > 0:
-            trace = torch.zeros((capi.lib().lmh_trace_samples(n_ticks, trace_every), self.B, capi.TRACE_STRIDE), dtype=torch.float64, device=self.device)
-        if trace is not None and trace.numel() == 0:               # zero samples: nothing is written, but the pointer has to be one
-            tr_arg = torch.empty((1,), dtype=torch.float64, device=self.device)
-        else:
-            tr_arg = trace
-        metrics = self._batch("metrics", metrics, capi.METRICS_STRIDE, optional=True, in_place=True)
+        n, ns, every = _count("n_ticks", n_ticks), _count("n_substeps", n_substeps), _count("trace_every", o["trace_every"])
+        per_tick = getattr(o["base_wrench"], "ndim", 0) == 3
+        bw = self._tick_records("base_wrench", o["base_wrench"], n, (6,))[1] if per_tick else self._batch("base_wrench", o["base_wrench"], 6, optional=True)
+        trace = tr_arg = None
+        if o["trace"] is not None or every > 0:                    # the kernel writes lmh_trace_samples records: a smaller buffer is an out-of-bounds write
+            trace, tr_arg = self._tick_records("trace", True if o["trace"] is None else o["trace"], capi.lib().lmh_trace_samples(n, every), (capi.TRACE_STRIDE,),
+                                               out=True, at_least=True)
+        out, status, lg = self._rollout_buffers(n, o["out"], o["status"], o["log"])
+        ref = None if o["ref"] is None else self._tick_records("ref", self._ref_records(o["ref"], (n,)), n, (capi.MPC_STRIDE,))[1]
+        metrics = self._batch("metrics", o["metrics"], capi.METRICS_STRIDE, optional=True, in_place=True)
         opts = capi.LmhZohOpts(d_base_wrench=_dev_ptr(bw), d_ref=_dev_ptr(ref), d_log=_dev_ptr(lg), d_trace=_dev_ptr(tr_arg), d_metrics=_dev_ptr(metrics),
-                               trace_every=trace_every, wrench_per_tick=int(per_tick), pushes=int(bool(pushes)), reserved=0)
-        if rigid_call is not None:
-            check(capi.lib().lmh_rollout_zoh_rigid(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), C.byref(io_call), C.byref(rigid_call),
-                                                   n_ticks, n_substeps, self._stream()))
-        elif servo_call is not None:
-            check(capi.lib().lmh_rollout_zoh_servo(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), C.byref(io_call), C.byref(servo_call),
-                                                   n_ticks, n_substeps, self._stream()))
-        elif io_call is not None:
-            check(capi.lib().lmh_rollout_zoh_io(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), C.byref(io_call), n_ticks, n_substeps,
-                                                self._stream()))
-        elif box_call is None:
-            check(capi.lib().lmh_rollout_zoh_ex(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), n_ticks, n_substeps, self._stream()))
-        else:
-            d_box, ns, sets, d_mpc = box_call
-            check(capi.lib().lmh_rollout_zoh_box(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), d_box, ns, sets, d_mpc,
-                                                 n_ticks, n_substeps, self._stream()))
+                               trace_every=every, wrench_per_tick=int(per_tick), pushes=int(bool(o["pushes"])), reserved=0)
+        check(call(self._h, _dev_ptr(state), _dev_ptr(out), _dev_ptr(status), C.byref(opts), *own, n, ns, self._stream()))
         return dict(out=out, status=status, log=lg, trace=trace)
 
     @staticmethod
@@ -923,9 +872,7 @@ class BatchedController:
         """lmh_mpc_rollout: n_ticks MPC steps of the reduced model in closed loop, in one launch; lip [B,8] is updated in place.
         traj=True: -> the samples [n_ticks,B,16]; False: -> None (only the final state); a tensor: filled and returned."""
         lip = self._batch("lip", lip, capi.LIP_STRIDE, in_place=True)
-        if int(n_ticks) != n_ticks or n_ticks < 0:
-            raise ValueError("n_ticks must be a whole number >= 0")
-        n = int(n_ticks)
+        n = _count("n_ticks", n_ticks)
         tr = torch.zeros((n, self.B, capi.MPC_STRIDE), dtype=torch.float64, device=self.device) if traj is True else (traj if traj is not False else None)
         if tr is not None and (tr.dtype != torch.float64 or tr.device != self.device or not tr.is_contiguous() or tr.numel() < n * self.B * capi.MPC_STRIDE):
             raise ValueError(f"traj must be a contiguous [{n},{self.B},{capi.MPC_STRIDE}] float64 tensor on {self.device}")
@@ -965,9 +912,7 @@ class BatchedController:
         """lmh_mpc_box_rollout: n_ticks constrained steps of the reduced model in closed loop, in one launch on one factorisation;
         lip [B,8] is updated in place.  traj as in mpc_rollout."""
         lip = self._batch("lip", lip, capi.LIP_STRIDE, in_place=True)
-        if int(n_ticks) != n_ticks or n_ticks < 0:
-            raise ValueError("n_ticks must be a whole number >= 0")
-        n = int(n_ticks)
+        n = _count("n_ticks", n_ticks)
         bx, ns, sets = self._box(box)
         tr = torch.zeros((n, self.B, capi.MPC_STRIDE), dtype=torch.float64, device=self.device) if traj is True else (traj if traj is not False else None)
         if tr is not None and (tr.dtype != torch.float64 or tr.device != self.device or not tr.is_contiguous() or tr.numel() < n * self.B * capi.MPC_STRIDE):

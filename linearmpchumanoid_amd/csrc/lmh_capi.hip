@@ -48,6 +48,18 @@ struct RefPlan {
     bool per_robot() const { return n_plans > 1; }
 };
 
+// A table of records the kernels read through their arguments (no part of the parameter block): [n_sets][width] on the device and on the host
+// (what get returns), n_sets = 1 shared by all robots or n_instances, empty while n_sets = 0.  set and get are defined with the three tables below.
+struct RecordTable {
+    DevBuf<double> d;
+    std::vector<double> h;
+    int n_sets = 0;
+    const double *device() const { return d.get(); }
+    size_t stride(int width) const { return (n_sets > 1) ? (size_t)width : 0; }   // 0: shared or empty
+    int set(const lmh_handle *hd, const char *who, const double *records, int n, int width, const char *(*rule)(const double *));
+    int get(const lmh_handle *hd, int inst, double *record, int width, double (*default_word)(int)) const;
+};
+
 struct lmh_handle {
     int zoh_box_prepared = -1;   // what the runtime answered when lmh_create asked for lmh_rollout_zoh_box_kernel's dynamic LDS limit (hipSuccess = 0)
     lmh_config cfg;
@@ -57,23 +69,9 @@ struct lmh_handle {
     RefPlan plan;                     // replaced as a whole, by commit_plan only
     DevBuf<double> d_pushes;          // timed velocity pushes [n_push_sets][n_push][LMH_PUSH_STRIDE] (lmh_set_pushes); empty while n_push = 0
     int n_push = 0, n_push_sets = 1;
-    // Actuator records (lmh_set_actuators): [n_act_sets][LMH_ACT_STRIDE] on the device and on the host (what lmh_get_actuators returns); empty while
-    // n_act_sets = 0.  Read by lmh_rollout_zoh_io alone, through its kernel arguments: no part of the parameter block.
-    DevBuf<double> d_act;
-    // Ground records (lmh_set_ground): [n_ground_sets][LMH_GROUND_STRIDE] on the device and on the host (what lmh_get_ground returns); empty while
-    // n_ground_sets = 0.  Read by the plant calls and the zero-order-hold family through their kernel arguments: no part of the parameter block.
-    DevBuf<double> d_ground;
-    std::vector<double> h_ground;
-    int n_ground_sets = 0;
-    size_t ground_stride() const { return (n_ground_sets > 1) ? (size_t)LMH_GROUND_STRIDE : 0; }
-    std::vector<double> h_act;
-    int n_act_sets = 0;
-    // Servo records (lmh_set_servo): [n_servo_sets][LMH_SERVO_STRIDE] on the device and on the host (what lmh_get_servo returns); empty while
-    // n_servo_sets = 0.  Read by lmh_plant_step_servo and lmh_rollout_zoh_servo alone, through their kernel arguments: no part of the parameter block.
-    DevBuf<double> d_servo;
-    std::vector<double> h_servo;
-    int n_servo_sets = 0;
-    size_t servo_stride() const { return (n_servo_sets > 1) ? (size_t)LMH_SERVO_STRIDE : 0; }
+    RecordTable act;                  // lmh_set_actuators, LMH_ACT_STRIDE: read by the io records of the zero-order-hold family alone
+    RecordTable servo;                // lmh_set_servo, LMH_SERVO_STRIDE: read by lmh_plant_step_servo and lmh_rollout_zoh_servo alone
+    RecordTable ground;               // lmh_set_ground, LMH_GROUND_STRIDE: read by the plant calls and the zero-order-hold family (the rigid plant apart)
     // Per-robot parameters (lmh_set_params): the records, one friction table per robot and the table of whole parameter blocks the controller
     // kernels select from.  All empty while the handle runs on its config's one set.  The block table is rebuilt by fill_params, i.e. by
     // every setter that moves a pointer or a stride, and replaces the previous one in one step.
@@ -675,38 +673,49 @@ static const char *actuator_record_error(const double *rec)
     return nullptr;
 }
 
-extern "C" int lmh_set_actuators(lmh_handle *h, const double *records, int n_sets)
+// The shared work of lmh_set_actuators, lmh_set_servo and lmh_set_ground behind their handle checks: NULL records clear the table, n is 0, 1 or
+// n_instances (who: the call's prefix of that refusal), every record passes `rule` (the first offending robot is named), then both copies are built
+// aside and put in place together.  Whatever fails leaves the previous table: the parameter block does not hold it, so nothing after the upload can.
+int RecordTable::set(const lmh_handle *hd, const char *who, const double *records, int n, int width, const char *(*rule)(const double *))
 {
-    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
-    if (n_sets < 0) return fail(LMH_ERR_BAD_ARG, "n_sets must be >= 0");
-    if (!records) n_sets = 0;
-    if (n_sets != 0 && n_sets != 1 && n_sets != h->B) return fail(LMH_ERR_BAD_ARG, "n_sets must be 1 or n_instances");
-    for (int i = 0; i < n_sets; i++)
-        if (const char *msg = actuator_record_error(records + (size_t)LMH_ACT_STRIDE * i)) return fail(LMH_ERR_BAD_ARG, robot_msg(i, msg));
-    HIPCHK(hipSetDevice(h->device));
-    DevBuf<double> d;
+    if (n < 0) return fail(LMH_ERR_BAD_ARG, "n_sets must be >= 0");
+    if (!records) n = 0;
+    if (n != 0 && n != 1 && n != hd->B) return fail(LMH_ERR_BAD_ARG, std::string(who) + "n_sets must be 1 or n_instances");
+    for (int i = 0; i < n; i++)
+        if (const char *msg = rule(records + (size_t)width * i)) return fail(LMH_ERR_BAD_ARG, robot_msg(i, msg));
+    HIPCHK(hipSetDevice(hd->device));
+    DevBuf<double> dev;
     std::vector<double> host;
-    if (n_sets > 0) {
-        host.assign(records, records + (size_t)LMH_ACT_STRIDE * n_sets);
-        HIPCHK(d.upload(records, (size_t)LMH_ACT_STRIDE * n_sets));
+    if (n > 0) {
+        host.assign(records, records + (size_t)width * n);
+        HIPCHK(dev.upload(records, host.size()));
     }
-    h->d_act = std::move(d); h->h_act.swap(host); h->n_act_sets = n_sets;     // nothing here fails: the parameter block does not hold the table
+    d = std::move(dev); h.swap(host); n_sets = n;
     return LMH_OK;
 }
 
-extern "C" int lmh_actuators_per_instance(const lmh_handle *h) { return (h && h->n_act_sets > 1) ? 1 : 0; }
+// robot inst's record: the defaults word by word from an empty table, the one record of a shared table, else the robot's own
+int RecordTable::get(const lmh_handle *hd, int inst, double *record, int width, double (*default_word)(int)) const
+{
+    if (inst < 0 || inst >= hd->B) return fail(LMH_ERR_BAD_ARG, "instance out of range");
+    if (!record) return fail(LMH_ERR_BAD_ARG, "bad argument");
+    if (n_sets == 0) for (int j = 0; j < width; j++) record[j] = default_word(j);
+    else std::memcpy(record, h.data() + (size_t)width * ((n_sets > 1) ? inst : 0), sizeof(double) * width);
+    return LMH_OK;
+}
+
+extern "C" int lmh_set_actuators(lmh_handle *h, const double *records, int n_sets)
+{
+    if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
+    return h->act.set(h, "", records, n_sets, LMH_ACT_STRIDE, actuator_record_error);
+}
+
+extern "C" int lmh_actuators_per_instance(const lmh_handle *h) { return (h && h->act.n_sets > 1) ? 1 : 0; }
 
 extern "C" int lmh_get_actuators(lmh_handle *h, int inst, double *record)
 {
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
-    if (inst < 0 || inst >= h->B) return fail(LMH_ERR_BAD_ARG, "instance out of range");
-    if (!record) return fail(LMH_ERR_BAD_ARG, "bad argument");
-    if (h->n_act_sets == 0) {
-        for (int j = 0; j < LMH_ACT_STRIDE; j++) record[j] = (j < 24) ? INFINITY : (j < 48) ? 1.0 : 0.0;
-        return LMH_OK;
-    }
-    std::memcpy(record, h->h_act.data() + (size_t)LMH_ACT_STRIDE * ((h->n_act_sets > 1) ? inst : 0), sizeof(double) * LMH_ACT_STRIDE);
-    return LMH_OK;
+    return h->act.get(h, inst, record, LMH_ACT_STRIDE, [](int j) { return (j < 24) ? (double)INFINITY : (j < 48) ? 1.0 : 0.0; });   // inf | 1 | 0
 }
 
 // ---------------------------------------------------------------------------- servo records (lmh_plant_step_servo, lmh_rollout_zoh_servo)
@@ -720,35 +729,15 @@ static const char *servo_record_error(const double *rec)
 extern "C" int lmh_set_servo(lmh_handle *h, const double *records, int n_sets)
 {
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
-    if (n_sets < 0) return fail(LMH_ERR_BAD_ARG, "n_sets must be >= 0");
-    if (!records) n_sets = 0;
-    if (n_sets != 0 && n_sets != 1 && n_sets != h->B) return fail(LMH_ERR_BAD_ARG, "lmh_set_servo: n_sets must be 1 or n_instances");
-    for (int i = 0; i < n_sets; i++)
-        if (const char *msg = servo_record_error(records + (size_t)LMH_SERVO_STRIDE * i)) return fail(LMH_ERR_BAD_ARG, robot_msg(i, msg));
-    HIPCHK(hipSetDevice(h->device));
-    DevBuf<double> d;
-    std::vector<double> host;
-    if (n_sets > 0) {
-        host.assign(records, records + (size_t)LMH_SERVO_STRIDE * n_sets);
-        HIPCHK(d.upload(records, (size_t)LMH_SERVO_STRIDE * n_sets));
-    }
-    h->d_servo = std::move(d); h->h_servo.swap(host); h->n_servo_sets = n_sets;           // nothing here fails: the parameter block does not hold the table
-    return LMH_OK;
+    return h->servo.set(h, "lmh_set_servo: ", records, n_sets, LMH_SERVO_STRIDE, servo_record_error);
 }
 
-extern "C" int lmh_servo_per_instance(const lmh_handle *h) { return (h && h->n_servo_sets > 1) ? 1 : 0; }
+extern "C" int lmh_servo_per_instance(const lmh_handle *h) { return (h && h->servo.n_sets > 1) ? 1 : 0; }
 
 extern "C" int lmh_get_servo(lmh_handle *h, int inst, double *record)
 {
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
-    if (inst < 0 || inst >= h->B) return fail(LMH_ERR_BAD_ARG, "instance out of range");
-    if (!record) return fail(LMH_ERR_BAD_ARG, "bad argument");
-    if (h->n_servo_sets == 0) {
-        for (int j = 0; j < LMH_SERVO_STRIDE; j++) record[j] = 0.0;
-        return LMH_OK;
-    }
-    std::memcpy(record, h->h_servo.data() + (size_t)LMH_SERVO_STRIDE * ((h->n_servo_sets > 1) ? inst : 0), sizeof(double) * LMH_SERVO_STRIDE);
-    return LMH_OK;
+    return h->servo.get(h, inst, record, LMH_SERVO_STRIDE, [](int) { return 0.0; });
 }
 
 // ---------------------------------------------------------------------------- ground records (the plant calls and the zero-order-hold family)
@@ -768,35 +757,15 @@ extern "C" int lmh_set_ground(lmh_handle *h, const double *records, int n_sets)
 {
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
     if (h->cfg.plant) return fail(LMH_ERR_BAD_ARG, "lmh_set_ground: not offered on a plant = 1 handle (the RK4 reference loop of lmh_rollout keeps the plane z = 0)");
-    if (n_sets < 0) return fail(LMH_ERR_BAD_ARG, "n_sets must be >= 0");
-    if (!records) n_sets = 0;
-    if (n_sets != 0 && n_sets != 1 && n_sets != h->B) return fail(LMH_ERR_BAD_ARG, "lmh_set_ground: n_sets must be 1 or n_instances");
-    for (int i = 0; i < n_sets; i++)
-        if (const char *msg = ground_record_error(records + (size_t)LMH_GROUND_STRIDE * i)) return fail(LMH_ERR_BAD_ARG, robot_msg(i, msg));
-    HIPCHK(hipSetDevice(h->device));
-    DevBuf<double> d;
-    std::vector<double> host;
-    if (n_sets > 0) {
-        host.assign(records, records + (size_t)LMH_GROUND_STRIDE * n_sets);
-        HIPCHK(d.upload(records, (size_t)LMH_GROUND_STRIDE * n_sets));
-    }
-    h->d_ground = std::move(d); h->h_ground.swap(host); h->n_ground_sets = n_sets;        // nothing here fails: the parameter block does not hold the table
-    return LMH_OK;
+    return h->ground.set(h, "lmh_set_ground: ", records, n_sets, LMH_GROUND_STRIDE, ground_record_error);
 }
 
-extern "C" int lmh_ground_per_instance(const lmh_handle *h) { return (h && h->n_ground_sets > 1) ? 1 : 0; }
+extern "C" int lmh_ground_per_instance(const lmh_handle *h) { return (h && h->ground.n_sets > 1) ? 1 : 0; }
 
 extern "C" int lmh_get_ground(lmh_handle *h, int inst, double *record)
 {
     if (!h) return fail(LMH_ERR_BAD_ARG, "null handle");
-    if (inst < 0 || inst >= h->B) return fail(LMH_ERR_BAD_ARG, "instance out of range");
-    if (!record) return fail(LMH_ERR_BAD_ARG, "bad argument");
-    if (h->n_ground_sets == 0) {
-        for (int j = 0; j < LMH_GROUND_STRIDE; j++) record[j] = (j == LMH_GROUND_OFF_N_R + 2 || j == LMH_GROUND_OFF_N_L + 2) ? 1.0 : 0.0;
-        return LMH_OK;
-    }
-    std::memcpy(record, h->h_ground.data() + (size_t)LMH_GROUND_STRIDE * ((h->n_ground_sets > 1) ? inst : 0), sizeof(double) * LMH_GROUND_STRIDE);
-    return LMH_OK;
+    return h->ground.get(h, inst, record, LMH_GROUND_STRIDE, [](int j) { return (j == LMH_GROUND_OFF_N_R + 2 || j == LMH_GROUND_OFF_N_L + 2) ? 1.0 : 0.0; });   // 0 0 1 0 | 0 0 1 0
 }
 
 extern "C" int lmh_set_xscale(lmh_handle *h, const double *xscale, int n)
@@ -1149,51 +1118,61 @@ static int plant_constants_ok(const lmh_handle *h)
     return LMH_OK;
 }
 
-// The caller has found the handle ready and checked its required pointers, which come before the constants in the order of the refusals.
-static int plant_body(lmh_handle *h, int mode, const double *d_q, const double *d_v, const double *d_tau30, double *d_state, double *d_xdot, double *d_contact, int32_t *d_flags,
-                      int n_substeps, void *stream, const double *d_setpoint = nullptr, const int32_t *d_hold = nullptr, double kv = 0.0, double *d_lambda = nullptr)
+// One plant call: the mode, the pointers its launch takes (those a call does not have stay NULL) and the step count.
+// servo (lmh_plant_step_servo): d_setpoint is required and the handle's servo table rides along; without one the launcher never reads it.
+// d_hold, kv, d_lambda (PM_RIGID_*): the rigid plant's; it reads neither the ground nor the servo table, so neither rides along.
+struct PlantCall {
+    int mode, n_substeps;
+    const double *d_q, *d_v, *d_tau30, *d_setpoint;
+    double *d_state, *d_xdot, *d_contact, *d_lambda;
+    int32_t *d_flags;
+    const int32_t *d_hold;
+    double kv;
+    bool servo;
+};
+static bool kv_ok(double kv) { return kv >= 0.0 && kv <= 1.7976931348623157e308; }     // finite and >= 0 (a NaN fails both)
+
+// The seven plant calls behind their names.  Refusals in this order: the handle, the pointers the mode requires, the servo's setpoint, the rigid
+// plant's kv, the count, the contact constants; a step call with no substep enqueues nothing but still answers for all of them.
+static int plant_body(lmh_handle *h, const char *name, const PlantCall &c, void *stream)
 {
-    const int rc = plant_constants_ok(h); if (rc) return rc;
-    // d_setpoint (lmh_plant_step_servo): the handle's servo table rides along; without one the launcher never reads it
-    // d_hold, kv, d_lambda (PM_RIGID_*): the rigid plant's; it reads neither table, so neither rides along
-    const bool rigid = mode == PM_RIGID_DERIV || mode == PM_RIGID_STEP;
-    return launch(h, nullptr, [&] { lmh_launch_plant(&h->P, mode, d_q, d_v, d_tau30, d_state, d_xdot, d_contact, d_flags, n_substeps, rigid ? nullptr : h->d_ground.get(),
-                                                     rigid ? 0 : h->ground_stride(), d_setpoint ? h->d_servo.get() : nullptr, h->servo_stride(), d_setpoint, d_hold, kv, d_lambda,
-                                                     (hipStream_t)stream); });
+    const int rc = ready(h); if (rc) return rc;
+    const std::string who = std::string(name) + ": ";
+    const bool step = c.mode == PM_STEP || c.mode == PM_RIGID_STEP, rigid = c.mode == PM_RIGID_DERIV || c.mode == PM_RIGID_STEP;
+    if (step ? !c.d_state : (c.mode == PM_CONTACT) ? (!c.d_q || !c.d_contact) : (!c.d_q || !c.d_v || !c.d_xdot)) return fail(LMH_ERR_BAD_ARG, who + "null device pointer");
+    if (c.servo && !c.d_setpoint) return fail(LMH_ERR_BAD_ARG, who + "null d_setpoint");
+    if (rigid && !kv_ok(c.kv)) return fail(LMH_ERR_BAD_ARG, who + "kv must be finite and >= 0");
+    if (c.n_substeps < 0) return fail(LMH_ERR_BAD_ARG, who + "n_substeps must be >= 0");
+    const int bad = plant_constants_ok(h);
+    if (bad || (step && c.n_substeps == 0)) return bad;              // no substep: nothing to enqueue
+    return launch(h, nullptr, [&] { lmh_launch_plant(&h->P, c.mode, c.d_q, c.d_v, c.d_tau30, c.d_state, c.d_xdot, c.d_contact, c.d_flags, c.n_substeps, rigid ? nullptr : h->ground.device(),
+                                                     rigid ? 0 : h->ground.stride(LMH_GROUND_STRIDE), c.servo ? h->servo.device() : nullptr, h->servo.stride(LMH_SERVO_STRIDE), c.d_setpoint,
+                                                     c.d_hold, c.kv, c.d_lambda, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_contact_wrench(lmh_handle *h, const double *d_q, const double *d_v, double *d_contact, void *stream)
 {
-    int rc = ready(h); if (rc) return rc;
-    if (!d_q || !d_contact) return fail(LMH_ERR_BAD_ARG, "lmh_contact_wrench: null device pointer");
-    return plant_body(h, PM_CONTACT, d_q, d_v, nullptr, nullptr, nullptr, d_contact, nullptr, 0, stream);
+    PlantCall c = {}; c.mode = PM_CONTACT; c.d_q = d_q; c.d_v = d_v; c.d_contact = d_contact;
+    return plant_body(h, "lmh_contact_wrench", c, stream);
 }
 
 extern "C" int lmh_plant_derivative(lmh_handle *h, const double *d_q, const double *d_v, const double *d_tau30, double *d_xdot, double *d_contact, int32_t *d_flags, void *stream)
 {
-    int rc = ready(h); if (rc) return rc;
-    if (!d_q || !d_v || !d_xdot) return fail(LMH_ERR_BAD_ARG, "lmh_plant_derivative: null device pointer");
-    return plant_body(h, PM_DERIV, d_q, d_v, d_tau30, nullptr, d_xdot, d_contact, d_flags, 0, stream);
+    PlantCall c = {}; c.mode = PM_DERIV; c.d_q = d_q; c.d_v = d_v; c.d_tau30 = d_tau30; c.d_xdot = d_xdot; c.d_contact = d_contact; c.d_flags = d_flags;
+    return plant_body(h, "lmh_plant_derivative", c, stream);
 }
 
 extern "C" int lmh_plant_step(lmh_handle *h, double *d_state, const double *d_tau30, int n_substeps, int32_t *d_flags, void *stream)
 {
-    int rc = ready(h); if (rc) return rc;
-    if (!d_state) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step: null device pointer");
-    if (n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step: n_substeps must be >= 0");
-    if (n_substeps == 0) return plant_constants_ok(h);               // nothing to enqueue
-    return plant_body(h, PM_STEP, nullptr, nullptr, d_tau30, d_state, nullptr, nullptr, d_flags, n_substeps, stream);
+    PlantCall c = {}; c.mode = PM_STEP; c.d_state = d_state; c.d_tau30 = d_tau30; c.n_substeps = n_substeps; c.d_flags = d_flags;
+    return plant_body(h, "lmh_plant_step", c, stream);
 }
 
 // lmh_plant_step with the joint servo re-forming the joint torques at every derivative evaluation (include/lmh.h)
 extern "C" int lmh_plant_step_servo(lmh_handle *h, double *d_state, const double *d_tau30, const double *d_setpoint, int n_substeps, int32_t *d_flags, void *stream)
 {
-    int rc = ready(h); if (rc) return rc;
-    if (!d_state) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step_servo: null device pointer");
-    if (!d_setpoint) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step_servo: null d_setpoint");
-    if (n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step_servo: n_substeps must be >= 0");
-    if (n_substeps == 0) return plant_constants_ok(h);               // nothing to enqueue
-    return plant_body(h, PM_STEP, nullptr, nullptr, d_tau30, d_state, nullptr, nullptr, d_flags, n_substeps, stream, d_setpoint);
+    PlantCall c = {}; c.mode = PM_STEP; c.d_state = d_state; c.d_tau30 = d_tau30; c.n_substeps = n_substeps; c.d_flags = d_flags; c.servo = true; c.d_setpoint = d_setpoint;
+    return plant_body(h, "lmh_plant_step_servo", c, stream);
 }
 
 // The rigid-contact plant (include/lmh.h): the held soles as constraints, the contact wrench their multiplier.  lmh_plant_step's rule set, with
@@ -1201,171 +1180,177 @@ extern "C" int lmh_plant_step_servo(lmh_handle *h, double *d_state, const double
 extern "C" int lmh_plant_derivative_rigid(lmh_handle *h, const double *d_q, const double *d_v, const double *d_tau30, const int32_t *d_mode, double kv, double *d_xdot, double *d_lambda,
                                           int32_t *d_flags, void *stream)
 {
-    int rc = ready(h); if (rc) return rc;
-    if (!d_q || !d_v || !d_xdot) return fail(LMH_ERR_BAD_ARG, "lmh_plant_derivative_rigid: null device pointer");
-    if (!(kv >= 0.0 && kv <= 1.7976931348623157e308)) return fail(LMH_ERR_BAD_ARG, "lmh_plant_derivative_rigid: kv must be finite and >= 0");
-    return plant_body(h, PM_RIGID_DERIV, d_q, d_v, d_tau30, nullptr, d_xdot, nullptr, d_flags, 0, stream, nullptr, d_mode, kv, d_lambda);
+    PlantCall c = {}; c.mode = PM_RIGID_DERIV; c.d_q = d_q; c.d_v = d_v; c.d_tau30 = d_tau30; c.d_xdot = d_xdot; c.d_flags = d_flags; c.d_hold = d_mode; c.kv = kv; c.d_lambda = d_lambda;
+    return plant_body(h, "lmh_plant_derivative_rigid", c, stream);
 }
 
 extern "C" int lmh_plant_step_rigid(lmh_handle *h, double *d_state, const double *d_tau30, const int32_t *d_mode, double kv, int n_substeps, double *d_lambda, int32_t *d_flags, void *stream)
 {
-    int rc = ready(h); if (rc) return rc;
-    if (!d_state) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step_rigid: null device pointer");
-    if (!(kv >= 0.0 && kv <= 1.7976931348623157e308)) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step_rigid: kv must be finite and >= 0");
-    if (n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_plant_step_rigid: n_substeps must be >= 0");
-    if (n_substeps == 0) return plant_constants_ok(h);               // nothing to enqueue
-    return plant_body(h, PM_RIGID_STEP, nullptr, nullptr, d_tau30, d_state, nullptr, nullptr, d_flags, n_substeps, stream, nullptr, d_mode, kv, d_lambda);
+    PlantCall c = {}; c.mode = PM_RIGID_STEP; c.d_state = d_state; c.d_tau30 = d_tau30; c.n_substeps = n_substeps; c.d_flags = d_flags; c.d_hold = d_mode; c.kv = kv; c.d_lambda = d_lambda;
+    return plant_body(h, "lmh_plant_step_rigid", c, stream);
 }
 
 // ---------------------------------------------------------------------------- zero-order-hold closed loop
 // n_ticks rounds of { lmh_eval ; lmh_plant_step(tau30 = [base_wrench | out.tau], n_substeps) } in one launch (lmh_kernels.hip,
-// lmh_rollout_zoh_kernel).  Refusals in the order of the two calls it composes: the handle, the pointers, the counts, then the precision and the
-// contact constants; the parameter block travels by value, so the call takes no launch slot.
-// with_ref (lmh_rollout_zoh_ref): d_ref is required too, refused behind the call's own pointers; every other refusal is lmh_rollout_zoh's, word for word.
-// opts (lmh_rollout_zoh_ex; nullptr in the two calls above it): its own refusals stand behind the counts they depend on and in front of the precision; an
-// all-zero record launches the kernels of the two calls above, anything else lmh_rollout_zoh_ex_kernel.
-// bx (lmh_rollout_zoh_box; nullptr in the three calls above it): the bounds of lmh_mpc_box_step and where the samples go.  Its refusals stand behind the
-// call's own pointers; the launch is lmh_rollout_zoh_box_kernel's whatever the options.
-// io (lmh_rollout_zoh_io; nullptr in the four calls above it, never with bx): its own refusals stand behind those of the options record; a record that asks
-// for nothing launches what the call without it launches, anything else lmh_rollout_zoh_io_kernel.
-// sv (lmh_rollout_zoh_servo; nullptr in the five calls above it, never with bx): its own refusals stand behind those of the io record; mode 0 launches what
-// the call without it launches, anything else lmh_rollout_zoh_servo_kernel whatever the options.
-// rg (lmh_rollout_zoh_rigid; nullptr in the six calls above it, never with bx or sv): its own refusals stand behind those of the io record; source 0
-// launches what the call without it launches, anything else lmh_rollout_zoh_rigid_kernel whatever the options, with no ground and no servo table.
+// lmh_rollout_zoh_ex_body's kernels).  The parameter block travels by value, so the call takes no launch slot.
+// One call of the family: the records its entry point was given, NULL for those it does not have (and for those its caller left out: either is the
+// all-zero record).  lmh_rollout_zoh and lmh_rollout_zoh_ref hand their three pointers over in an options record of their own.
 struct ZohBoxCall { const double *d_box; int n_samples, n_sets; double *d_mpc; };
-static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log, const double *d_ref, bool with_ref,
-                    int n_ticks, int n_substeps, void *stream, const lmh_zoh_opts *opts = nullptr, const ZohBoxCall *bx = nullptr, const lmh_zoh_io *io = nullptr,
-                    const lmh_zoh_servo *sv = nullptr, const lmh_zoh_rigid *rg = nullptr)
+struct ZohCall {
+    const lmh_zoh_opts *opts;
+    const ZohBoxCall *box;        // lmh_rollout_zoh_box: never with io, servo or rigid
+    const lmh_zoh_io *io;
+    const lmh_zoh_servo *servo;   // lmh_rollout_zoh_servo: never with rigid
+    const lmh_zoh_rigid *rigid;
+    bool d_ref_required;          // lmh_rollout_zoh_ref
+};
+static const lmh_zoh_opts kNoOpts = {}; static const lmh_zoh_io kNoIo = {}; static const lmh_zoh_servo kNoServo = {}; static const lmh_zoh_rigid kNoRigid = {};
+
+// The refusals of each record, in the words and the order they always had; nullptr = fine
+static const char *zoh_box_refusal(const lmh_handle *h, const ZohBoxCall &bx, const lmh_zoh_opts &o)
 {
-    int rc = ready(h); if (rc) return rc;
-    if (!d_state || !d_out || !d_status) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: null device pointer");
-    if (with_ref && !d_ref) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ref: null d_ref");
-    if (bx) {
-        if (const char *why = box_refusal(h, bx->d_box, bx->n_samples, bx->n_sets, "lmh_rollout_zoh_box: null d_box",
-                                          "lmh_rollout_zoh_box: n_samples must be lmh_num_ref_samples", "lmh_rollout_zoh_box: n_sets must be 1 or n_instances"))
-            return fail(LMH_ERR_BAD_ARG, why);
-        if (d_ref) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_box: opts->d_ref must be NULL (the box-constrained step is the reference: the two are exclusive)");
-        if (h->n_ground_sets > 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_box: not offered on a handle with a ground table (lmh_set_ground(NULL) clears it)");
-    }
-    if (n_ticks < 0 || n_substeps < 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: n_ticks and n_substeps must be >= 0");
-    LmhZohEx ex = {nullptr, nullptr, 0, 0, 0, 0};
-    if (opts) {
-        if ((opts->wrench_per_tick | 1) != 1) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ex: wrench_per_tick must be 0 or 1");
-        if ((opts->pushes | 1) != 1) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ex: pushes must be 0 or 1");
-        if (opts->reserved != 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ex: reserved must be 0");
-        if (opts->wrench_per_tick && !d_base_wrench) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ex: wrench_per_tick = 1 needs d_base_wrench");
-        if (opts->trace_every < 0 || (opts->d_trace != nullptr) != (opts->trace_every > 0))
-            return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ex: d_trace and trace_every > 0 go together (NULL and 0: no trace)");
-        if (opts->pushes && n_substeps == 0 && n_ticks > 0)
-            return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ex: pushes = 1 needs n_substeps > 0 (push ticks are plant substeps: with none the clock does not move)");
-        if (opts->pushes && (long long)n_ticks * n_substeps >= 0x3fffffffll)
-            return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_ex: pushes = 1 needs n_ticks * n_substeps < 2^30 - 1");
-        ex.trace = opts->d_trace; ex.metrics = opts->d_metrics; ex.trace_every = opts->trace_every;
-        ex.wrench_per_tick = opts->wrench_per_tick; ex.pushes = opts->pushes;
-    }
-    if (io) {
-        if ((io->actuators | 1) != 1) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_io: actuators must be 0 or 1");
-        if (io->reserved != 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_io: reserved must be 0");
-        if (io->actuators && !io->d_act_mem) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_io: actuators = 1 needs d_act_mem");
-    }
-    if (sv) {
-        if (sv->mode != 0 && sv->mode != LMH_SERVO_INTEGRATE && sv->mode != LMH_SERVO_CALLER)
-            return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_servo: mode must be 0, LMH_SERVO_INTEGRATE or LMH_SERVO_CALLER");
-        if (sv->reserved != 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_servo: reserved must be 0");
-        if (sv->mode == LMH_SERVO_CALLER && !sv->d_setpoint) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_servo: mode LMH_SERVO_CALLER needs d_setpoint");
-        if (sv->mode != LMH_SERVO_CALLER && sv->d_setpoint) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_servo: d_setpoint goes with mode LMH_SERVO_CALLER only");
-        if (sv->mode == LMH_SERVO_INTEGRATE && n_substeps == 0)
-            return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_servo: mode LMH_SERVO_INTEGRATE needs n_substeps > 0 (the setpoint is the end of a control period: with no substep there is none)");
-    }
-    if (rg) {
-        if (rg->source != 0 && rg->source != LMH_RIGID_FIXED && rg->source != LMH_RIGID_PER_TICK && rg->source != LMH_RIGID_PLAN)
-            return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_rigid: source must be 0, LMH_RIGID_FIXED, LMH_RIGID_PER_TICK or LMH_RIGID_PLAN");
-        if (rg->reserved != 0) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_rigid: reserved must be 0");
-        if (!(rg->kv >= 0.0 && rg->kv <= 1.7976931348623157e308)) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_rigid: kv must be finite and >= 0");
-        if (rg->source == LMH_RIGID_PER_TICK && !rg->d_mode) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_rigid: source LMH_RIGID_PER_TICK needs d_mode");
-        if (rg->source == LMH_RIGID_PLAN && rg->d_mode) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh_rigid: d_mode must be NULL with source LMH_RIGID_PLAN (the robot's own plan decides)");
-    }
-    if (h->cfg.precision != LMH_PRECISION_FP64) return fail(LMH_ERR_BAD_ARG, "lmh_rollout_zoh: LMH_PRECISION_FP64 handles only (this handle's precision has no instantiation of the kernel)");
+    if (const char *why = box_refusal(h, bx.d_box, bx.n_samples, bx.n_sets, "lmh_rollout_zoh_box: null d_box",
+                                      "lmh_rollout_zoh_box: n_samples must be lmh_num_ref_samples", "lmh_rollout_zoh_box: n_sets must be 1 or n_instances"))
+        return why;
+    if (o.d_ref) return "lmh_rollout_zoh_box: opts->d_ref must be NULL (the box-constrained step is the reference: the two are exclusive)";
+    if (h->ground.n_sets > 0) return "lmh_rollout_zoh_box: not offered on a handle with a ground table (lmh_set_ground(NULL) clears it)";
+    return nullptr;
+}
+static const char *zoh_opts_refusal(const lmh_zoh_opts &o, int n_ticks, int n_substeps)
+{
+    if ((o.wrench_per_tick | 1) != 1) return "lmh_rollout_zoh_ex: wrench_per_tick must be 0 or 1";
+    if ((o.pushes | 1) != 1) return "lmh_rollout_zoh_ex: pushes must be 0 or 1";
+    if (o.reserved != 0) return "lmh_rollout_zoh_ex: reserved must be 0";
+    if (o.wrench_per_tick && !o.d_base_wrench) return "lmh_rollout_zoh_ex: wrench_per_tick = 1 needs d_base_wrench";
+    if (o.trace_every < 0 || (o.d_trace != nullptr) != (o.trace_every > 0)) return "lmh_rollout_zoh_ex: d_trace and trace_every > 0 go together (NULL and 0: no trace)";
+    if (o.pushes && n_substeps == 0 && n_ticks > 0)
+        return "lmh_rollout_zoh_ex: pushes = 1 needs n_substeps > 0 (push ticks are plant substeps: with none the clock does not move)";
+    if (o.pushes && (long long)n_ticks * n_substeps >= 0x3fffffffll) return "lmh_rollout_zoh_ex: pushes = 1 needs n_ticks * n_substeps < 2^30 - 1";
+    return nullptr;
+}
+static const char *zoh_io_refusal(const lmh_zoh_io &io)
+{
+    if ((io.actuators | 1) != 1) return "lmh_rollout_zoh_io: actuators must be 0 or 1";
+    if (io.reserved != 0) return "lmh_rollout_zoh_io: reserved must be 0";
+    if (io.actuators && !io.d_act_mem) return "lmh_rollout_zoh_io: actuators = 1 needs d_act_mem";
+    return nullptr;
+}
+static const char *zoh_servo_refusal(const lmh_zoh_servo &sv, int n_substeps)
+{
+    if (sv.mode != 0 && sv.mode != LMH_SERVO_INTEGRATE && sv.mode != LMH_SERVO_CALLER) return "lmh_rollout_zoh_servo: mode must be 0, LMH_SERVO_INTEGRATE or LMH_SERVO_CALLER";
+    if (sv.reserved != 0) return "lmh_rollout_zoh_servo: reserved must be 0";
+    if (sv.mode == LMH_SERVO_CALLER && !sv.d_setpoint) return "lmh_rollout_zoh_servo: mode LMH_SERVO_CALLER needs d_setpoint";
+    if (sv.mode != LMH_SERVO_CALLER && sv.d_setpoint) return "lmh_rollout_zoh_servo: d_setpoint goes with mode LMH_SERVO_CALLER only";
+    if (sv.mode == LMH_SERVO_INTEGRATE && n_substeps == 0)
+        return "lmh_rollout_zoh_servo: mode LMH_SERVO_INTEGRATE needs n_substeps > 0 (the setpoint is the end of a control period: with no substep there is none)";
+    return nullptr;
+}
+static const char *zoh_rigid_refusal(const lmh_zoh_rigid &rg)
+{
+    if (rg.source != 0 && rg.source != LMH_RIGID_FIXED && rg.source != LMH_RIGID_PER_TICK && rg.source != LMH_RIGID_PLAN)
+        return "lmh_rollout_zoh_rigid: source must be 0, LMH_RIGID_FIXED, LMH_RIGID_PER_TICK or LMH_RIGID_PLAN";
+    if (rg.reserved != 0) return "lmh_rollout_zoh_rigid: reserved must be 0";
+    if (!kv_ok(rg.kv)) return "lmh_rollout_zoh_rigid: kv must be finite and >= 0";
+    if (rg.source == LMH_RIGID_PER_TICK && !rg.d_mode) return "lmh_rollout_zoh_rigid: source LMH_RIGID_PER_TICK needs d_mode";
+    if (rg.source == LMH_RIGID_PLAN && rg.d_mode) return "lmh_rollout_zoh_rigid: d_mode must be NULL with source LMH_RIGID_PLAN (the robot's own plan decides)";
+    return nullptr;
+}
+
+// Refusals in the order of the two calls the loop composes, every record's own behind the counts they depend on: the handle, the pointers, d_ref
+// where it is required, the box, the counts, the options, io, servo, rigid, then the precision and the contact constants.
+static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, int n_ticks, int n_substeps, void *stream, const ZohCall &c)
+{
+    int rc = ready(h); if (rc) return rc;                            // no record is read before this
+    const lmh_zoh_opts &o = c.opts ? *c.opts : kNoOpts;
+    const lmh_zoh_io &io = c.io ? *c.io : kNoIo;
+    const lmh_zoh_servo &sv = c.servo ? *c.servo : kNoServo;
+    const lmh_zoh_rigid &rg = c.rigid ? *c.rigid : kNoRigid;
+    const char *why = nullptr;
+    if (!d_state || !d_out || !d_status) why = "lmh_rollout_zoh: null device pointer";
+    else if (c.d_ref_required && !o.d_ref) why = "lmh_rollout_zoh_ref: null d_ref";
+    if (!why && c.box) why = zoh_box_refusal(h, *c.box, o);
+    if (!why && (n_ticks < 0 || n_substeps < 0)) why = "lmh_rollout_zoh: n_ticks and n_substeps must be >= 0";
+    if (!why) why = zoh_opts_refusal(o, n_ticks, n_substeps);
+    if (!why) why = zoh_io_refusal(io);
+    if (!why) why = zoh_servo_refusal(sv, n_substeps);
+    if (!why) why = zoh_rigid_refusal(rg);
+    if (!why && h->cfg.precision != LMH_PRECISION_FP64) why = "lmh_rollout_zoh: LMH_PRECISION_FP64 handles only (this handle's precision has no instantiation of the kernel)";
+    if (why) return fail(LMH_ERR_BAD_ARG, why);
     rc = plant_constants_ok(h); if (rc) return rc;
     if (n_ticks == 0) return LMH_OK;                                 // nothing to enqueue
-    if (bx) {
-        if (h->zoh_box_prepared != 0 && h->N > 33)                   // N >= 34: above 64 KB of LDS in all, only with the limit lmh_create asked for
-            return fail(LMH_ERR_HIP, "lmh_rollout_zoh_box: the runtime refused the kernel's dynamic shared memory limit when the handle was created");
-        const LmhZohBox zb = {bx->d_box, box_stride(h, bx->n_sets), bx->d_mpc, h->cfg.alpha, h->cfg.beta, 0, nullptr};
-        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, nullptr, n_ticks, n_substeps, &ex, &zb, nullptr, nullptr, 0, nullptr, nullptr, (hipStream_t)stream); });
-    }
-    if (rg && rg->source != 0) {                                     // the rigid hold reads neither the ground nor the servo table: neither rides along
-        const LmhZohIo zi = {io ? io->d_meas : nullptr, (io && io->actuators) ? io->d_act_mem : nullptr, io ? io->d_applied : nullptr, h->d_act.get(),
-                             (h->n_act_sets > 1) ? (size_t)LMH_ACT_STRIDE : 0, io ? io->actuators : 0, 0};
-        const LmhZohRigid zr = {rg->d_mode, rg->d_lambda, rg->kv, rg->source, 0};
-        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, &ex, nullptr, &zi, nullptr, 0, nullptr, &zr, (hipStream_t)stream); });
-    }
-    if (sv && sv->mode != 0) {
-        const LmhZohIo zi = {io ? io->d_meas : nullptr, (io && io->actuators) ? io->d_act_mem : nullptr, io ? io->d_applied : nullptr, h->d_act.get(),
-                             (h->n_act_sets > 1) ? (size_t)LMH_ACT_STRIDE : 0, io ? io->actuators : 0, 0};
-        const LmhZohServo zs = {sv->d_setpoint, h->d_servo.get(), h->servo_stride(), sv->mode, 0};
-        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, &ex, nullptr, &zi, h->d_ground.get(), h->ground_stride(), &zs, nullptr, (hipStream_t)stream); });
-    }
-    if (io && (io->d_meas || io->d_applied || io->actuators)) {
-        const LmhZohIo zi = {io->d_meas, io->actuators ? io->d_act_mem : nullptr, io->d_applied, h->d_act.get(), (h->n_act_sets > 1) ? (size_t)LMH_ACT_STRIDE : 0, io->actuators, 0};
-        return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, &ex, nullptr, &zi, h->d_ground.get(), h->ground_stride(), nullptr, nullptr, (hipStream_t)stream); });
-    }
-    const bool plain = !ex.trace && !ex.metrics && !ex.wrench_per_tick && !ex.pushes;     // no new option: the kernels of before
-    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, n_ticks, n_substeps, plain ? nullptr : &ex, nullptr, nullptr, h->d_ground.get(), h->ground_stride(), nullptr, nullptr, (hipStream_t)stream); });
+    if (c.box && h->zoh_box_prepared != 0 && h->N > 33)              // N >= 34: above 64 KB of LDS in all, only with the limit lmh_create asked for
+        return fail(LMH_ERR_HIP, "lmh_rollout_zoh_box: the runtime refused the kernel's dynamic shared memory limit when the handle was created");
+    // What the one launch is given, and with it which kernel of the family runs (lmh_launch.h); the options record always rides along:
+    //   box                     the box record; ref is NULL and the handle has no ground table (both refused above); no io, servo, rigid
+    //   rigid, source != 0      the io record always and the rigid record; no ground, no servo
+    //   servo, mode != 0        the io record always, the ground as the handle has it, the servo record with the handle's table and stride
+    //   io that asks something  the io record, the ground
+    //   otherwise               no io record, the ground
+    const bool rigid = rg.source != 0, servo = sv.mode != 0;
+    const bool with_io = rigid || servo || io.d_meas || io.d_applied || io.actuators;
+    LmhZohEx ex = {};
+    ex.trace = o.d_trace; ex.metrics = o.d_metrics; ex.trace_every = o.trace_every; ex.wrench_per_tick = o.wrench_per_tick; ex.pushes = o.pushes;
+    const LmhZohBox zb = {c.box ? c.box->d_box : nullptr, c.box ? box_stride(h, c.box->n_sets) : 0, c.box ? c.box->d_mpc : nullptr, h->cfg.alpha, h->cfg.beta, 0, nullptr};
+    const LmhZohIo zi = {io.d_meas, io.actuators ? io.d_act_mem : nullptr, io.d_applied, h->act.device(), h->act.stride(LMH_ACT_STRIDE), io.actuators, 0};
+    const LmhZohServo zs = {sv.d_setpoint, h->servo.device(), h->servo.stride(LMH_SERVO_STRIDE), sv.mode, 0};
+    const LmhZohRigid zr = {rg.d_mode, rg.d_lambda, rg.kv, rg.source, 0};
+    return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, o.d_base_wrench, o.d_log, o.d_ref, n_ticks, n_substeps, &ex, c.box ? &zb : nullptr, with_io ? &zi : nullptr,
+                                                           rigid ? nullptr : h->ground.device(), rigid ? 0 : h->ground.stride(LMH_GROUND_STRIDE), servo ? &zs : nullptr, rigid ? &zr : nullptr,
+                                                           (hipStream_t)stream); });
 }
+
 extern "C" int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
                                int n_ticks, int n_substeps, void *stream)
 {
-    return zoh_body(h, d_state, d_out, d_status, d_base_wrench, d_log, nullptr, false, n_ticks, n_substeps, stream);
+    lmh_zoh_opts o = {}; o.d_base_wrench = d_base_wrench; o.d_log = d_log;
+    ZohCall c = {}; c.opts = &o;
+    return zoh_body(h, d_state, d_out, d_status, n_ticks, n_substeps, stream, c);
 }
 extern "C" int lmh_rollout_zoh_ref(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log, const double *d_ref,
                                    int n_ticks, int n_substeps, void *stream)
 {
-    return zoh_body(h, d_state, d_out, d_status, d_base_wrench, d_log, d_ref, true, n_ticks, n_substeps, stream);
+    lmh_zoh_opts o = {}; o.d_base_wrench = d_base_wrench; o.d_log = d_log; o.d_ref = d_ref;
+    ZohCall c = {}; c.opts = &o; c.d_ref_required = true;
+    return zoh_body(h, d_state, d_out, d_status, n_ticks, n_substeps, stream, c);
 }
 // the wrench, the reference and the log ride in the record: NULL there is what NULL is in the two calls above (d_ref NULL: the built-in preview step)
 extern "C" int lmh_rollout_zoh_ex(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts, int n_ticks, int n_substeps, void *stream)
 {
-    static const lmh_zoh_opts none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
-    const lmh_zoh_opts *o = opts ? opts : &none;
-    return zoh_body(h, d_state, d_out, d_status, o->d_base_wrench, o->d_log, o->d_ref, false, n_ticks, n_substeps, stream, o);
+    ZohCall c = {}; c.opts = opts;
+    return zoh_body(h, d_state, d_out, d_status, n_ticks, n_substeps, stream, c);
 }
 
 // lmh_rollout_zoh_ex with a measurement in front of the evaluation and an actuator behind it (include/lmh.h)
 extern "C" int lmh_rollout_zoh_io(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts, const lmh_zoh_io *io, int n_ticks, int n_substeps,
                                   void *stream)
 {
-    static const lmh_zoh_opts none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
-    const lmh_zoh_opts *o = opts ? opts : &none;
-    return zoh_body(h, d_state, d_out, d_status, o->d_base_wrench, o->d_log, o->d_ref, false, n_ticks, n_substeps, stream, o, nullptr, io);
+    ZohCall c = {}; c.opts = opts; c.io = io;
+    return zoh_body(h, d_state, d_out, d_status, n_ticks, n_substeps, stream, c);
 }
 
 // lmh_rollout_zoh_io with the joint servo inside every hold (include/lmh.h)
 extern "C" int lmh_rollout_zoh_servo(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts, const lmh_zoh_io *io, const lmh_zoh_servo *servo,
                                      int n_ticks, int n_substeps, void *stream)
 {
-    static const lmh_zoh_opts none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
-    const lmh_zoh_opts *o = opts ? opts : &none;
-    return zoh_body(h, d_state, d_out, d_status, o->d_base_wrench, o->d_log, o->d_ref, false, n_ticks, n_substeps, stream, o, nullptr, io, servo);
+    ZohCall c = {}; c.opts = opts; c.io = io; c.servo = servo;
+    return zoh_body(h, d_state, d_out, d_status, n_ticks, n_substeps, stream, c);
 }
 
 // lmh_rollout_zoh_io with the rigid-contact plant in every hold (include/lmh.h)
 extern "C" int lmh_rollout_zoh_rigid(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts, const lmh_zoh_io *io, const lmh_zoh_rigid *rigid,
                                      int n_ticks, int n_substeps, void *stream)
 {
-    static const lmh_zoh_opts none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
-    const lmh_zoh_opts *o = opts ? opts : &none;
-    return zoh_body(h, d_state, d_out, d_status, o->d_base_wrench, o->d_log, o->d_ref, false, n_ticks, n_substeps, stream, o, nullptr, io, nullptr, rigid);
+    ZohCall c = {}; c.opts = opts; c.io = io; c.rigid = rigid;
+    return zoh_body(h, d_state, d_out, d_status, n_ticks, n_substeps, stream, c);
 }
 
 // lmh_rollout_zoh_ex with lmh_mpc_box_step closing the loop inside every evaluation (include/lmh.h)
 extern "C" int lmh_rollout_zoh_box(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts, const double *d_box, int n_samples, int n_sets,
                                    double *d_mpc, int n_ticks, int n_substeps, void *stream)
 {
-    static const lmh_zoh_opts none = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0, 0};
-    const lmh_zoh_opts *o = opts ? opts : &none;
     const ZohBoxCall bx = {d_box, n_samples, n_sets, d_mpc};
-    return zoh_body(h, d_state, d_out, d_status, o->d_base_wrench, o->d_log, o->d_ref, false, n_ticks, n_substeps, stream, o, &bx);
+    ZohCall c = {}; c.opts = opts; c.box = &bx;
+    return zoh_body(h, d_state, d_out, d_status, n_ticks, n_substeps, stream, c);
 }
 
 extern "C" int lmh_terms_host(lmh_handle *h, const double *q, const double *v, double *terms)

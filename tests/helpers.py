@@ -147,6 +147,38 @@ def to_device(ctl, a):
     return torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(ctl.device)
 
 
+def check_record_table(ctl, name, defaults, records, bad, words):
+    """What lmh_set_<name> / lmh_get_<name> / lmh_<name>_per_instance (name: "actuators" | "servo" | "ground") owe on a handle of TWO robots
+    with no table, whole records through the C calls, no launch: an empty table reads as `defaults` [width] for both robots; one shared
+    record reads back through both; a table of two (records [2,width], two different good ones) reads back robot by robot; a refused set
+    (bad [2,width]: robot 1 breaks the rule `words`; three records for two robots) leaves the shared and the per-robot table readable as
+    they were; NULL clears."""
+    import ctypes as C
+    from linearmpchumanoid_amd import capi
+    L, h = capi.lib(), ctl._h
+    set_, get, per = getattr(L, "lmh_set_" + name), getattr(L, "lmh_get_" + name), getattr(L, "lmh_%s_per_instance" % name)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p)
+    assert ctl.B == 2 and records.shape == bad.shape == (2,) + defaults.shape and not same_bits(records[0], records[1])
+
+    def reads(want0, want1, per_robot):
+        got = np.full((2,) + defaults.shape, -7.0)
+        assert all(get(h, i, ptr(got[i])) == 0 for i in (0, 1))
+        return same_bits(got[0], want0) and same_bits(got[1], want1) and per(h) == per_robot
+
+    def refused():
+        three = np.concatenate([records, records[:1]])
+        return (set_(h, ptr(bad), 2) == -2 and L.lmh_last_error().decode() == "robot 1: " + words
+                and set_(h, ptr(three), 3) == -2 and L.lmh_last_error().decode().endswith("n_sets must be 1 or n_instances"))
+
+    assert reads(defaults, defaults, 0), "defaults from an empty table"
+    assert refused() and reads(defaults, defaults, 0), "a refused set leaves the empty table"
+    assert set_(h, ptr(records[1].copy()), 1) == 0 and reads(records[1], records[1], 0), "a shared table through every robot"
+    assert refused() and reads(records[1], records[1], 0), "a refused set leaves the shared table"
+    assert set_(h, ptr(records), 2) == 0 and reads(records[0], records[1], 1), "a per-robot table robot by robot"
+    assert refused() and reads(records[0], records[1], 1), "a refused set leaves the per-robot table"
+    assert set_(h, None, 0) == 0 and reads(defaults, defaults, 0), "NULL clears"
+
+
 def same_bits(a, b):
     """Two numpy arrays or two torch tensors (on any device) are the same shape, dtype and bytes: -0.0 is not 0.0, and a NaN equals only
     the same NaN pattern."""

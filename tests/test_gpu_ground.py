@@ -17,7 +17,7 @@ import ground_cases as gc
 import plant_step_cases as pc
 import zoh_ex_cases as zx
 import zoh_io_cases as zi
-from helpers import close, close_on, make_controller, rel_err, same_bits as _same, to_device
+from helpers import check_record_table, close, close_on, make_controller, rel_err, same_bits as _same, to_device
 from zoh_host_loop import assert_same as _assert_same, fresh, host_loop
 
 pytestmark = pytest.mark.gpu
@@ -406,6 +406,15 @@ def test_captured_on_a_fresh_handle_replays_to_the_eager_bytes(loop):
 
 
 # ------------------------------------------------------------------------------- 8. refusals and the setter rule
+def test_the_table_reads_back_empty_shared_per_robot_and_after_a_refused_set():
+    S = gc.tilted_states()
+    ctl = _ctl(S, n=2)
+    planes = np.ascontiguousarray(S["planes"][:2])
+    bad = planes.copy(); bad[1, 0:3] *= 2.0
+    check_record_table(ctl, "ground", gc.FLAT, planes, bad, "a ground normal must have unit length (| |n|^2 - 1 | <= 1e-12; nothing is normalised here)")
+    ctl.close()
+
+
 def test_refusals_leave_the_table_in_place():
     from linearmpchumanoid_amd import capi
     from linearmpchumanoid_amd.capi import LmhError

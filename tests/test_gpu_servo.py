@@ -18,7 +18,7 @@ import ground_cases as gc
 import plant_step_cases as pc
 import servo_cases as sc
 import zoh_io_cases as zi
-from helpers import close, make_controller, rel_err, same_bits as _same, to_device
+from helpers import check_record_table, close, make_controller, rel_err, same_bits as _same, to_device
 from servo_host_loop import servo_host_loop
 from zoh_host_loop import SCHEDULES, assert_same as _assert_same, fresh, push_schedules, wrench_and_refs
 
@@ -148,6 +148,16 @@ def test_a_nan_setpoint_flags_its_robot_alone():
     torch.cuda.synchronize()
     assert int(fb[bad]) & capi.FLAG_NONFINITE and int(fg.abs().max()) == 0 and not bool(torch.isfinite(got[bad, :60]).all())
     assert _same(good[others], got[others]) and _same(fg[others], fb[others])
+    ctl.close()
+
+
+def test_the_table_reads_back_empty_shared_per_robot_and_after_a_refused_set():
+    from linearmpchumanoid_amd import trajectories as tj
+    S = sc.servo_cases()
+    ctl = _ctl(S, n=2)
+    rec = np.ascontiguousarray(S["rec"][:2])
+    bad = rec.copy(); bad[1, 30] = -1.0
+    check_record_table(ctl, "servo", np.zeros(rec.shape[1]), rec, bad, tj.SERVO_ERR_GAIN)
     ctl.close()
 
 

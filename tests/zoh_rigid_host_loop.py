@@ -1,11 +1,48 @@
-"""The host loop that DEFINES lmh_rollout_zoh_rigid (include/lmh.h): zoh_host_loop.host_loop's loop for lmh_rollout_zoh_io with every
-plant_step of a hold replaced by plant_step_rigid(mode_j, kv).  It is made of calls that exist: stand_step for the evaluation, plant_step_rigid
-for the hold in the pieces trajectories.zoh_hold_pieces gives, v += dv in torch for a push, zoh_host_loop.actuate for the actuator, and
-trajectories.rigid_modes for the modes a plan decides."""
+"""The host loop that DEFINES lmh_rollout_zoh_rigid (include/lmh.h): zoh_host_loop.host_loop, as it stands, with every plant_step of a hold
+replaced by plant_step_rigid(mode_j, kv).  host_loop is handed a controller whose stand_step fixes the mode of its control tick behind the
+evaluation -- the caller's word, the caller's record of the tick, or trajectories.rigid_modes at the preview index the evaluation reports --
+and whose plant_step is plant_step_rigid on it; every other piece (the pushes, the measurement, the actuator, the samples) is host_loop's
+own, as in servo_host_loop.py.  The handle carries, like host_loop's, neither a push schedule nor actuator records."""
 import numpy as np
 import torch
 
-from zoh_host_loop import actuate, assert_same, fresh, push_schedules, wrench_and_refs        # noqa: F401  (shared with the tests)
+from zoh_host_loop import actuate, assert_same, fresh, host_loop, push_schedules, wrench_and_refs        # noqa: F401  (shared with the tests)
+
+
+class RigidLoopController:
+    """What host_loop sees in the place of the controller: stand_step also fixes the mode of its control tick -- one word per robot for every
+    piece of the hold --, plant_step is plant_step_rigid on it and keeps the multiplier of the tick's last piece (that of the first stage of
+    the hold's last substep wherever the cuts fall); everything else is the controller's."""
+
+    def __init__(self, ctl, n_ticks, mode, kv, phase):
+        self._ctl, self._mode, self._kv, self._phase = ctl, mode, kv, phase
+        self._tick, self._m = -1, None
+        self.lam = torch.zeros((n_ticks, ctl.B, 12), dtype=torch.float64, device=ctl.device)
+        self.modes = torch.zeros((n_ticks, ctl.B), dtype=torch.int32, device=ctl.device)
+
+    def __getattr__(self, name):
+        return getattr(self._ctl, name)
+
+    def stand_step(self, state, out=None, status=None, **kw):
+        from linearmpchumanoid_amd.trajectories import rigid_modes
+        res = self._ctl.stand_step(state, out, status, **kw)
+        self._tick += 1
+        mode, m = self._mode, None
+        if isinstance(mode, str):
+            assert mode == "plan"
+            if self._phase is not None:
+                ph, ks = np.asarray(self._phase), res[1][:, 0].cpu().numpy()
+                m = torch.as_tensor(np.array([int(rigid_modes(ph[i] if ph.ndim == 2 else ph, ks[i])) for i in range(len(ks))], dtype=np.int32)).to(self._ctl.device)
+        elif mode is not None:
+            m = (mode[self._tick] if mode.ndim == 2 else mode).contiguous()
+        self._m = m
+        self.modes[self._tick] = 0 if m is None else (m & 3)
+        return res
+
+    def plant_step(self, state, tau=None, n_substeps=1):
+        state, lm, flags = self._ctl.plant_step_rigid(state, tau, self._m, self._kv, n_substeps)
+        self.lam[self._tick] = lm
+        return state, flags
 
 
 def host_loop_rigid(ctl, st, status, n_ticks, n_substeps, *, mode=None, kv=0.0, phase=None, bw=None, sched=None, refs=None, meas=None, act=None):
@@ -15,90 +52,6 @@ def host_loop_rigid(ctl, st, status, n_ticks, n_substeps, *, mode=None, kv=0.0, 
     zoh_host_loop.host_loop takes them.
     -> dict(out, status with [1] / [2] merged as max / OR over the ticks and the plant's flags, log [n_ticks,B,36], applied [n_ticks,B,24],
     trace [n_ticks,B,180], lam [n_ticks,B,12]: the multiplier the last piece of every tick's hold returned, modes [n_ticks,B])."""
-    from linearmpchumanoid_amd import capi
-    from linearmpchumanoid_amd.trajectories import rigid_modes, zoh_hold_pieces
-    dev, B = ctl.device, st.shape[0]
-    out = ctl.new_out()
-    zero = torch.zeros((B, 6), dtype=torch.float64, device=dev)
-    rounds = torch.zeros((B,), dtype=torch.int32, device=dev)
-    flags = torch.zeros((B,), dtype=torch.int32, device=dev)
-    log = torch.zeros((n_ticks, B, 36), dtype=torch.float64, device=dev)
-    applied = torch.zeros((n_ticks, B, 24), dtype=torch.float64, device=dev)
-    trace = torch.zeros((n_ticks, B, 180), dtype=torch.float64, device=dev)
-    lam = torch.zeros((n_ticks, B, 12), dtype=torch.float64, device=dev)
-    modes = torch.zeros((n_ticks, B), dtype=torch.int32, device=dev)
-    pieces = None
-    if sched is not None:
-        ticks, dv = sched
-        n0 = np.rint(st[:, 90].cpu().numpy() / ctl.cfg.dt).astype(np.int64)
-        pieces = [zoh_hold_pieces(ticks[i] if ticks.ndim == 2 else ticks, n0[i], n_ticks, n_substeps) for i in range(B)]
-        dvt = torch.as_tensor(dv).to(dev)
-
-    def push(rows, recs):
-        if rows:
-            r = torch.as_tensor(rows, device=dev)
-            st[r, 30:60] += dvt[r, torch.as_tensor(recs, device=dev)]
-
-    for tick in range(n_ticks):
-        if pieces:
-            rows = [i for i in range(B) if pieces[i][tick][0] is not None]
-            push(rows, [pieces[i][tick][0] for i in rows])
-        ref = None if refs is None else refs[tick]
-        if meas is None:
-            ctl.stand_step(st, out, status, ref=ref)
-        else:
-            scratch = st.clone()
-            scratch[:, 0:60] = st[:, 0:60] + meas[tick]
-            ctl.stand_step(scratch, out, status, ref=ref)
-            st[:, 60:90] = scratch[:, 60:90]                       # v_prev: the v the controller measured
-        log[tick] = out[:, 0:36]
-        y = out[:, 0:24].contiguous()
-        if act is not None:
-            y, limited = actuate(*act, y)
-            flags = flags | (limited.to(torch.int32) * capi.FLAG_TAU_LIMIT)
-        applied[tick] = y
-        base = zero if bw is None else (bw[tick] if bw.ndim == 3 else bw)
-        tau30 = torch.cat([base, y], dim=1).contiguous()
-        # the tick's mode: one word per robot for every piece of the hold
-        if isinstance(mode, str):
-            assert mode == "plan"
-            if phase is None:
-                m = None
-            else:
-                ph, ks = np.asarray(phase), status[:, 0].cpu().numpy()
-                m = torch.as_tensor(np.array([int(rigid_modes(ph[i] if ph.ndim == 2 else ph, ks[i])) for i in range(B)], dtype=np.int32)).to(dev)
-        elif mode is None:
-            m = None
-        else:
-            m = (mode[tick] if mode.ndim == 2 else mode).contiguous()
-        modes[tick] = 0 if m is None else (m & 3)
-        # the robots' holds are cut where any robot has a push: plant_step_rigid(a + b) is plant_step_rigid(a) ; plant_step_rigid(b) bit for
-        # bit, and the multiplier of the last piece is that of the first stage of the hold's last substep wherever the cuts fall
-        cuts = {}
-        if pieces:
-            for i in range(B):
-                at = 0
-                for s, rec in pieces[i][tick][1]:
-                    at += s
-                    if rec is not None:
-                        cuts.setdefault(at, []).append((i, rec))
-        at = 0
-        for c in sorted(cuts) + [n_substeps]:
-            if c > at:
-                _, lm, pf = ctl.plant_step_rigid(st, tau30, m, kv, c - at)
-                lam[tick] = lm
-                flags = flags | pf
-                at = c
-            if c in cuts:
-                push([i for i, _ in cuts[c]], [r for _, r in cuts[c]])
-        rounds = torch.maximum(rounds, status[:, 1])
-        flags = flags | status[:, 2]
-        trace[tick, :, 0:96] = st
-        trace[tick, :, 96:176] = out
-        trace[tick, :, 176] = status[:, 0].double()
-        trace[tick, :, 177] = rounds.double()
-        trace[tick, :, 178] = flags.double()
-        trace[tick, :, 179] = status[:, 3].double()
-    status[:, 1] = rounds
-    status[:, 2] = flags
-    return dict(out=out, status=status, log=log, applied=applied, trace=trace, lam=lam, modes=modes)
+    proxy = RigidLoopController(ctl, n_ticks, mode, kv, phase)
+    res = host_loop(proxy, st, status, n_ticks, n_substeps, bw=bw, sched=sched, refs=refs, meas=meas, act=act)
+    return dict(res, lam=proxy.lam, modes=proxy.modes)
