@@ -621,6 +621,35 @@ int lmh_plant_derivative_rigid(lmh_handle *h, const double *d_q, const double *d
                                int32_t *d_flags, void *stream);
 int lmh_plant_step_rigid(lmh_handle *h, double *d_state, const double *d_tau30, const int32_t *d_mode, double kv, int n_substeps, double *d_lambda, int32_t *d_flags, void *stream);
 
+/* ---- Rigid-contact plant: plastic touchdown impact (build-defined).  What the two calls above lack at the instant a sole BECOMES held: the
+ * velocity jumps to the nearest velocity, in the metric of M, that satisfies the mode's constraints, and the impulse is the multiplier of that
+ * projection.  Without it a sole that lands moving is braked over about 1 / kv seconds and drifts by about w_0 / kv meanwhile.
+ * DEFINITION, per robot, in the coordinates of M as lmh_plant_derivative_rigid uses them; S: the rows d_mode[i] & 3 holds (NULL:
+ * LMH_PHASE_DOUBLE), exactly as there.
+ *         w      = J_S vhat                     the held soles' twist at (q, v)
+ *         Y      = M^-1 J_S'       A = J_S Y
+ *         Lam_S  = -A^-1 w         (Gauss-Jordan without pivoting, as the derivative's solve)      Lam = 0 on the rows that are not held
+ *         dvhat  = Y Lam_S
+ *         dv     = dvhat turned back to the state's ordering and the world frame, by the map the derivative applies to its acceleration
+ *         v_plus = v + dv
+ * ALL soles the mode holds take part, not only a newly held one: a touchdown into double support keeps the stance sole at rest.  There is no
+ * kv, no torque, no C and no Jdot qdot in it; M, J, Y and A are the derivative's, operation for operation.  The update is v + dv and not a
+ * round trip of vhat, so LMH_PHASE_FLIGHT gives v_plus == v bit for bit and an impulse of exact zeros.  J_S (vhat + dvhat) = 0 to rounding;
+ * the kinetic energy vhat' M vhat / 2 does not rise; a second impact on v_plus changes nothing beyond rounding.  No restitution.
+ * trajectories.rigid_contact_impact is the numpy statement (tests/test_impact.py: backward, constraint and forward figures <= 1e-12 on 48
+ * cases, every pivot of A positive, smallest 0.473).
+ * d_v_plus: DEVICE [B][30].  d_impulse: DEVICE [B][12] in the layout of out.f (N s and N m s), may be NULL.  d_flags: DEVICE [B], may be
+ * NULL: LMH_FLAG_NOT_SPD and LMH_FLAG_NONFINITE (of v_plus) as in the derivative, and two informational flags, reported and not enforced,
+ * both outside the mask (& 15) of the metrics' FIRST_FLAG: LMH_FLAG_IMPULSE_PULL when a held foot's impulse has f_z < 0 -- the sole was
+ * moving away from the ground, a real contact would not have closed --, LMH_FLAG_IMPULSE_SLIP when hypot(f_x, f_y) > contact_mu f_z on a held
+ * foot, with the robot's own contact_mu.
+ * As the two rigid calls: works on any handle and writes nothing into it, reads nothing of the ground or servo table, honours per-robot
+ * models, checks the contact constants, is asynchronous and capturable as the first call.  Refused with LMH_ERR_BAD_ARG before anything is
+ * enqueued, each with a message of its own: NULL d_q, NULL d_v, NULL d_v_plus. */
+#define LMH_FLAG_IMPULSE_PULL 1024 /* informational: a held foot's impulse pulls (f_z < 0): the sole was leaving the ground */
+#define LMH_FLAG_IMPULSE_SLIP 2048 /* informational: a held foot's impulse leaves the friction disc contact_mu f_z */
+int lmh_plant_impact_rigid(lmh_handle *h, const double *d_q, const double *d_v, const int32_t *d_mode, double *d_v_plus, double *d_impulse, int32_t *d_flags, void *stream);
+
 /* ---- Ground planes under the soles (build-defined; lmh_set_ground, a table of the handle like the actuator records): how steep a slope, or
  * how high a ledge under one foot, the controller survives -- per robot, so that a sweep is one launch.
  * records: HOST [n_sets][LMH_GROUND_STRIDE], n_sets = 1 (one record for every robot) or n_instances; NULL or n_sets = 0 clears the table.
@@ -998,6 +1027,7 @@ int lmh_rollout_zoh_servo(lmh_handle *h, double *d_state, double *d_out, int32_t
  * THERE IS NO IMPACT MODEL.  A sole that becomes held while it moves keeps its twist and loses it as e^(-kv t): with kv = 0 it keeps it for
  * good.  The contact stays BILATERAL: a held sole that the ground would have to pull on is held all the same, and reported
  * (LMH_FLAG_CONTACT_PULL, LMH_FLAG_CONTACT_SLIP), never released.  Which soles are held is the caller's (or the plan's) decision alone.
+ * lmh_rollout_zoh_rigid_impact (below) is this loop with the plastic impact at every touchdown; this call itself still has none.
  * Tables.  As the two rigid plant calls, the call reads nothing from the ground table (lmh_set_ground) and nothing from the servo table
  * (lmh_set_servo): it gives the same bytes with or without either.
  * rigid == NULL or source == 0 is lmh_rollout_zoh_io(h, ..., opts, io, ...) exactly: the same kernel is launched (on that handle's ground
@@ -1025,6 +1055,50 @@ typedef struct lmh_zoh_rigid {
 } lmh_zoh_rigid;
 int lmh_rollout_zoh_rigid(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts,
                           const lmh_zoh_io *io, const lmh_zoh_rigid *rigid, int n_ticks, int n_substeps, void *stream);
+
+/* ---- The plastic impact inside the zero-order-hold loop (build-defined): lmh_rollout_zoh_rigid with lmh_plant_impact_rigid at every control
+ * tick whose hold keeps a foot the hold before it did not.
+ * lmh_rollout_zoh_rigid_impact.  DEFINITION.  lmh_rollout_zoh_rigid's host loop, as written out above, with one step between mode_j and the
+ * hold of control tick j (held(m): the feet m & 3 holds; prev_i: d_mode_prev[i] & 3 on the launch's first tick):
+ *         if held(mode_j) \ held(prev_i) is not empty:                                   a foot becomes held
+ *             (v_plus, Lam, fl) = lmh_plant_impact_rigid(q, v of the TRUE state, mode_j)
+ *             v <- v_plus ;  status flags |= fl ;  d_impulse[j][i] = Lam
+ *         else:
+ *             d_impulse[j][i] = 0  (all twelve words)
+ *         prev_i = mode_j & 3
+ * The push due at the tick's start, the measurement, the evaluation, v_prev, the actuator and d_applied all come before the impact, as in
+ * lmh_rollout_zoh_rigid (the mode of LMH_RIGID_PLAN is only known behind the evaluation): the torques of tick j are those computed on the
+ * pre-impact state, and v_prev, q and t are not touched by the impact.  The hold's pieces and the pushes inside it come after it; the trace
+ * sample and the metrics fold are lmh_rollout_zoh_rigid's, on the state behind the hold.  The impact holds ALL the feet of mode_j, so a
+ * touchdown into double support keeps the stance sole at rest.
+ * d_mode_prev[i] leaves the launch with the last tick's mode & 3; n_ticks == 0 leaves it alone; only the low two bits of a word are read.
+ * (a + b) equals (a) followed by (b) bit for bit with the per-tick arrays advanced (d_impulse included) and d_mode_prev handed on.  A caller
+ * who wants no impact on the first tick hands in that tick's mode; LMH_PHASE_FLIGHT makes every foot held at tick 0 a touchdown.
+ * impact == NULL or enable == 0 is lmh_rollout_zoh_rigid exactly: the same kernel and the same bytes.
+ * Refusals, each LMH_ERR_BAD_ARG before anything is enqueued and with a message of its own: enable outside {0, 1}; a non-zero reserved;
+ * enable without a rigid record whose source != 0; enable without d_mode_prev; every refusal of lmh_rollout_zoh_rigid.
+ * LMH_PRECISION_FP64 handles only; no launch slot, nothing written into the handle, capturable as the first call on a fresh handle.
+ * Not offered: restitution, friction-limited or unilateral impulses (LMH_FLAG_IMPULSE_PULL and LMH_FLAG_IMPULSE_SLIP report them in
+ * status[2], nothing enforces them), a position-level term.
+ * Cost (one MI355X, 4096 standing robots x 200 control ticks, kv = 50, n_substeps = 1 / 10; scripts/rigid_impact_rate.py, DESIGN.md round
+ * 38; other batch sizes and anything multi-GPU were not measured): with enable = 1 and no foot ever newly held -- the price of the check, one
+ * word loaded and stored per control tick -- 75.38 / 599.2 ms beside lmh_rollout_zoh_rigid's 75.50 / 596.7 ms in the same run, inside the
+ * parent commit's own range of timings for that call (73.27 .. 77.85 and 596.9 .. 606.5 ms).  With the left sole landing on every second
+ * control tick 81.86 / 598.5 ms against 77.31 / 593.6 ms for the same modes without the impact: about 0.05 ms per landing of 4096 robots,
+ * 12 % of a control tick of one substep and 1.7 % of one of ten.  lmh_plant_impact_rigid alone: 0.0695 ms per launch beside
+ * lmh_plant_derivative_rigid's 0.0791 ms (x 0.88: no Newton-Euler pass).  lmh_rollout_zoh_rigid runs at the parent commit's rate: its kernel
+ * is the parent's, instruction for instruction.
+ * What it says about walking on this plant (scripts/rigid_stand.py --zoh --impact, profiles/r38_rigid_stand.txt): on round 36's mode = "plan"
+ * sweep the impact changes next to nothing -- no cell stands, first falls at control ticks 649 .. 1024 with and without it, 250 of 256
+ * cells at the same tick -- and 245 of 256 cells raise LMH_FLAG_IMPULSE_PULL: the soles the plan puts down are moving away from the ground. */
+typedef struct lmh_zoh_impact {
+    int32_t *d_mode_prev;         /* DEVICE [B], in and out: the mode of the hold before this launch's first tick; after the launch, the last tick's */
+    double *d_impulse;            /* DEVICE [n_ticks][B][12] or NULL */
+    int32_t enable;               /* 0 off | 1 */
+    int32_t reserved;             /* must be 0 */
+} lmh_zoh_impact;
+int lmh_rollout_zoh_rigid_impact(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts,
+                                 const lmh_zoh_io *io, const lmh_zoh_rigid *rigid, const lmh_zoh_impact *impact, int n_ticks, int n_substeps, void *stream);
 
 /* ---- LIPM preview MPC for a batch of reduced states (one kernel family of its own, one wave per robot, fp64): the stage of the controller
  * that lmh_eval runs between the momentum and the PD law, as calls of its own.

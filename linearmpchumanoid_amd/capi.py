@@ -86,6 +86,8 @@ FLAG_BOX_EMPTY = 64           # lmh_mpc_box_*: a sample of the window has lo > h
 FLAG_TAU_LIMIT = 128          # lmh_rollout_zoh_io, informational: a joint's torque was cut to its limit on some tick of the launch
 FLAG_CONTACT_PULL = 256       # lmh_plant_*_rigid, informational: a held foot's multiplier pulls (f_z < 0)
 FLAG_CONTACT_SLIP = 512       # lmh_plant_*_rigid, informational: a held foot's multiplier leaves the friction disc contact_mu f_z
+FLAG_IMPULSE_PULL = 1024      # lmh_plant_impact_rigid, informational: a held foot's impulse pulls (f_z < 0)
+FLAG_IMPULSE_SLIP = 2048      # lmh_plant_impact_rigid, informational: a held foot's impulse leaves the friction disc contact_mu f_z
 FLAG_UNFINISHED = 32          # lmh_rollout: the robot did not get all its ticks (a wait of the kernel's work queue ran out)
 ERR_UNFINISHED = -5
 
@@ -134,6 +136,11 @@ class LmhZohServo(C.Structure):
 class LmhZohRigid(C.Structure):
     """struct lmh_zoh_rigid (include/lmh.h): the rigid-contact hold of lmh_rollout_zoh_rigid; source 0 = lmh_rollout_zoh_io."""
     _fields_ = [("d_mode", C.c_void_p), ("d_lambda", C.c_void_p), ("kv", C.c_double), ("source", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LmhZohImpact(C.Structure):
+    """struct lmh_zoh_impact (include/lmh.h): the plastic impact of lmh_rollout_zoh_rigid_impact; enable 0 = lmh_rollout_zoh_rigid."""
+    _fields_ = [("d_mode_prev", C.c_void_p), ("d_impulse", C.c_void_p), ("enable", C.c_int32), ("reserved", C.c_int32)]
 
 
 _vp, _ip, _dp, _str, _u64 = C.c_void_p, C.c_int, C.c_double, C.c_char_p, C.c_uint64
@@ -203,6 +210,7 @@ PROTOTYPES = {
     "lmh_plant_step_servo": (_ip, [_vp, _vp, _vp, _vp, _ip, _vp, _vp]),
     "lmh_plant_derivative_rigid": (_ip, [_vp, _vp, _vp, _vp, _vp, _dp, _vp, _vp, _vp, _vp]),
     "lmh_plant_step_rigid": (_ip, [_vp, _vp, _vp, _vp, _dp, _ip, _vp, _vp, _vp]),
+    "lmh_plant_impact_rigid": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "lmh_rollout_zoh": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _vp]),
     "lmh_rollout_zoh_ref": (_ip, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _ip, _ip, _vp]),
     "lmh_rollout_zoh_ex": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), _ip, _ip, _vp]),
@@ -210,6 +218,7 @@ PROTOTYPES = {
     "lmh_rollout_zoh_io": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), C.POINTER(LmhZohIo), _ip, _ip, _vp]),
     "lmh_rollout_zoh_servo": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), C.POINTER(LmhZohIo), C.POINTER(LmhZohServo), _ip, _ip, _vp]),
     "lmh_rollout_zoh_rigid": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), C.POINTER(LmhZohIo), C.POINTER(LmhZohRigid), _ip, _ip, _vp]),
+    "lmh_rollout_zoh_rigid_impact": (_ip, [_vp, _vp, _vp, _vp, C.POINTER(LmhZohOpts), C.POINTER(LmhZohIo), C.POINTER(LmhZohRigid), C.POINTER(LmhZohImpact), _ip, _ip, _vp]),
     "lmh_mpc_step": (_ip, [_vp, _vp, _vp, _vp]),
     "lmh_mpc_rollout": (_ip, [_vp, _vp, _ip, _vp, _vp]),
     "lmh_mpc_preview": (_ip, [_vp, _vp, _vp, _vp]),

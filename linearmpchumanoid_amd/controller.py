@@ -683,6 +683,19 @@ class BatchedController:
         check(capi.lib().lmh_plant_step_rigid(self._h, _dev_ptr(state), _dev_ptr(tau), _dev_ptr(mode), kv, int(n_substeps), _dev_ptr(lam), _dev_ptr(flags), self._stream()))
         return state, lam, flags
 
+    def plant_impact_rigid(self, q, v, mode=None):
+        """lmh_plant_impact_rigid: the plastic impact of the rigid-contact plant at q, v [B,30] -- the velocity jumps to the nearest one, in
+        the metric of M, at which every sole that mode holds (as in plant_derivative_rigid; None: both soles) is at rest -> (v_plus [B,30],
+        impulse [B,12] laid out like out.f and exactly 0 on a free foot, flags [B] int32: FLAG_IMPULSE_PULL / FLAG_IMPULSE_SLIP
+        (informational), FLAG_NOT_SPD, FLAG_NONFINITE).  PHASE_FLIGHT leaves v bit for bit.  trajectories.rigid_contact_impact states it."""
+        q, v = self._batch("q", q, 30), self._batch("v", v, 30)
+        mode, _ = self._rigid_args(mode, 0.0)
+        v_plus = torch.empty((self.B, 30), dtype=torch.float64, device=self.device)
+        impulse = torch.empty((self.B, 12), dtype=torch.float64, device=self.device)
+        flags = torch.zeros((self.B,), dtype=torch.int32, device=self.device)
+        check(capi.lib().lmh_plant_impact_rigid(self._h, _dev_ptr(q), _dev_ptr(v), _dev_ptr(mode), _dev_ptr(v_plus), _dev_ptr(impulse), _dev_ptr(flags), self._stream()))
+        return v_plus, impulse, flags
+
     # -- zero-order-hold closed loop (include/lmh.h, lmh_rollout_zoh): the argument handling the seven calls share
     def _tick_records(self, name, v, n, tail, dtype=torch.float64, out=False, at_least=False, also=()):
         """Per-tick records [n,B,*tail] of a launch (or one of the whole shapes `also`; at_least: [m,B,*tail] with m >= n) -> (the tensor the
@@ -768,11 +781,11 @@ class BatchedController:
         io.keep = (ms, mem, ap_arg)                                # (the record holds addresses only)
         return io, ap
 
-    def _zoh_io_launch(self, state, n, n_substeps, kw, call, record):
-        """The two calls that take rollout_zoh_io's keywords as they are (kw: its own arguments and rollout_zoh_ex's options together) with a
-        record of their own behind the io record -> rollout_zoh_ex's dict plus applied."""
+    def _zoh_io_launch(self, state, n, n_substeps, kw, call, *records):
+        """The calls that take rollout_zoh_io's keywords as they are (kw: its own arguments and rollout_zoh_ex's options together) with
+        records of their own behind the io record -> rollout_zoh_ex's dict plus applied."""
         io, ap = self._zoh_io(n, kw.pop("meas", None), kw.pop("actuators", False), kw.pop("act_mem", None), kw.pop("applied", False))
-        res = self._zoh_launch(state, n, n_substeps, kw, call, C.byref(io), C.byref(record))
+        res = self._zoh_launch(state, n, n_substeps, kw, call, C.byref(io), *[C.byref(r) for r in records])
         res["applied"] = ap
         return res
 
@@ -790,22 +803,39 @@ class BatchedController:
         mode = 0 if servo is None else capi.SERVO_INTEGRATE if sp is None else capi.SERVO_CALLER
         return self._zoh_io_launch(state, n, n_substeps, io, capi.lib().lmh_rollout_zoh_servo, capi.LmhZohServo(d_setpoint=_dev_ptr(sp), mode=mode, reserved=0))
 
-    def rollout_zoh_rigid(self, state, n_ticks, n_substeps, mode=None, kv=0.0, lam=False, **io):
+    def rollout_zoh_rigid(self, state, n_ticks, n_substeps, mode=None, kv=0.0, lam=False, impact=None, impulse=False, **io):
         """lmh_rollout_zoh_rigid: rollout_zoh_io (whose keywords it takes as they are) with the rigid-contact plant in every hold -- bit for
         bit that call's host loop with plant_step_rigid(mode_j, kv) in the place of plant_step.  mode: None, both soles of every robot held
         for the launch; an int32 [B] tensor of PHASE_* words, held for the launch; an int32 [n_ticks,B] tensor, record j is control tick
         j's hold; "plan": the support phase of the robot's own plan at the preview index that tick's evaluation reports
         (trajectories.rigid_modes).  One mode serves every piece of a tick's hold.  lam=True: the multipliers [n_ticks,B,12] at the first
-        stage of the last substep of every tick's hold are returned under "lam" (a tensor: filled).  There is no impact model and the
-        contact stays bilateral (include/lmh.h); the ground and servo tables are not read.  -> rollout_zoh_io's dict plus lam."""
+        stage of the last substep of every tick's hold are returned under "lam" (a tensor: filled).  The contact stays bilateral
+        (include/lmh.h); the ground and servo tables are not read.
+        impact=None: there is no impact model, a sole that becomes held while it moves loses its twist as e^(-kv t).  impact: an int32 [B]
+        tensor, the mode of the hold before this launch's first tick (lmh_rollout_zoh_rigid_impact's d_mode_prev, updated in place to the
+        last tick's mode and handed on from launch to launch): every tick whose mode holds a foot the hold before it did not runs
+        plant_impact_rigid on the true state in front of its hold.  impulse=True: the impulses [n_ticks,B,12], zeros on a tick without a
+        touchdown, are returned under "impulse" (a tensor: filled); only with impact.  -> rollout_zoh_io's dict plus lam (and impulse)."""
         n = _count("n_ticks", n_ticks)
         if isinstance(mode, str) and mode != "plan":
             raise ValueError('mode must be None, an int32 [B] or [n_ticks,B] tensor, or "plan"')
+        if impact is None and impulse is not False:
+            raise ValueError("impulse goes with impact (the int32 [B] tensor of the modes before the launch) only")
+        if impact is not None and (not isinstance(impact, torch.Tensor) or impact.dtype != torch.int32):
+            raise ValueError("impact must be None or a contiguous [B] int32 tensor on the handle's device")
         md = None if isinstance(mode, str) else self._tick_records("mode", mode, n, (), dtype=torch.int32, also=((self.B,),))[1]
         source = capi.RIGID_PLAN if isinstance(mode, str) else capi.RIGID_PER_TICK if (md is not None and mode.ndim == 2) else capi.RIGID_FIXED
         lm, lm_arg = self._tick_records("lam", lam, n, (12,), out=True)
         rg = capi.LmhZohRigid(d_mode=_dev_ptr(md), d_lambda=_dev_ptr(lm_arg), kv=float(kv), source=source, reserved=0)
-        res = self._zoh_io_launch(state, n, n_substeps, io, capi.lib().lmh_rollout_zoh_rigid, rg)
+        if impact is None:
+            res = self._zoh_io_launch(state, n, n_substeps, io, capi.lib().lmh_rollout_zoh_rigid, rg)
+        else:
+            if tuple(impact.shape) != (self.B,) or impact.device != self.device or not impact.is_contiguous():
+                raise ValueError(f"impact must be a contiguous [{self.B}] int32 tensor on {self.device}")
+            ip, ip_arg = self._tick_records("impulse", impulse, n, (12,), out=True)
+            im = capi.LmhZohImpact(d_mode_prev=_dev_ptr(impact), d_impulse=_dev_ptr(ip_arg), enable=1, reserved=0)
+            res = self._zoh_io_launch(state, n, n_substeps, io, capi.lib().lmh_rollout_zoh_rigid_impact, rg, im)
+            res["impulse"] = ip
         res["lam"] = lm
         return res
 

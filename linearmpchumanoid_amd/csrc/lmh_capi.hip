@@ -467,7 +467,7 @@ extern "C" int lmh_create(const lmh_config *cfg, int n_instances, int device, lm
     {                                                               // lmh_rollout_zoh_box's dynamic LDS: asked for here, never inside the (capturable) call
         int32_t answer = -1;
         const LmhZohBox prep = {nullptr, 0, nullptr, 0.0, 0.0, 1, &answer};
-        lmh_launch_rollout_zoh(&h->P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &prep, nullptr, nullptr, 0, nullptr, nullptr, nullptr);
+        lmh_launch_rollout_zoh(&h->P, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, nullptr, &prep, nullptr, nullptr, 0, nullptr, nullptr, nullptr, nullptr);
         h->zoh_box_prepared = answer;
     }
     (void)hipGetLastError();                                        // an answer other than hipSuccess is that call's to report, not a sticky error of this one
@@ -1121,6 +1121,7 @@ static int plant_constants_ok(const lmh_handle *h)
 // One plant call: the mode, the pointers its launch takes (those a call does not have stay NULL) and the step count.
 // servo (lmh_plant_step_servo): d_setpoint is required and the handle's servo table rides along; without one the launcher never reads it.
 // d_hold, kv, d_lambda (PM_RIGID_*): the rigid plant's; it reads neither the ground nor the servo table, so neither rides along.
+// PM_RIGID_IMPACT (lmh_plant_impact_rigid): d_q, d_v, d_hold; d_xdot is d_v_plus and d_lambda the impulse; no torque, no kv, no count.
 struct PlantCall {
     int mode, n_substeps;
     const double *d_q, *d_v, *d_tau30, *d_setpoint;
@@ -1132,13 +1133,16 @@ struct PlantCall {
 };
 static bool kv_ok(double kv) { return kv >= 0.0 && kv <= 1.7976931348623157e308; }     // finite and >= 0 (a NaN fails both)
 
-// The seven plant calls behind their names.  Refusals in this order: the handle, the pointers the mode requires, the servo's setpoint, the rigid
+// The eight plant calls behind their names.  Refusals in this order: the handle, the pointers the mode requires, the servo's setpoint, the rigid
 // plant's kv, the count, the contact constants; a step call with no substep enqueues nothing but still answers for all of them.
 static int plant_body(lmh_handle *h, const char *name, const PlantCall &c, void *stream)
 {
     const int rc = ready(h); if (rc) return rc;
     const std::string who = std::string(name) + ": ";
-    const bool step = c.mode == PM_STEP || c.mode == PM_RIGID_STEP, rigid = c.mode == PM_RIGID_DERIV || c.mode == PM_RIGID_STEP;
+    const bool step = c.mode == PM_STEP || c.mode == PM_RIGID_STEP, impact = c.mode == PM_RIGID_IMPACT, rigid = c.mode == PM_RIGID_DERIV || c.mode == PM_RIGID_STEP || impact;
+    if (impact && !c.d_q) return fail(LMH_ERR_BAD_ARG, who + "null d_q");
+    if (impact && !c.d_v) return fail(LMH_ERR_BAD_ARG, who + "null d_v");
+    if (impact && !c.d_xdot) return fail(LMH_ERR_BAD_ARG, who + "null d_v_plus");
     if (step ? !c.d_state : (c.mode == PM_CONTACT) ? (!c.d_q || !c.d_contact) : (!c.d_q || !c.d_v || !c.d_xdot)) return fail(LMH_ERR_BAD_ARG, who + "null device pointer");
     if (c.servo && !c.d_setpoint) return fail(LMH_ERR_BAD_ARG, who + "null d_setpoint");
     if (rigid && !kv_ok(c.kv)) return fail(LMH_ERR_BAD_ARG, who + "kv must be finite and >= 0");
@@ -1190,6 +1194,13 @@ extern "C" int lmh_plant_step_rigid(lmh_handle *h, double *d_state, const double
     return plant_body(h, "lmh_plant_step_rigid", c, stream);
 }
 
+// The rigid plant's plastic impact (include/lmh.h): the two rigid calls' rule set without a torque, a kv or a count
+extern "C" int lmh_plant_impact_rigid(lmh_handle *h, const double *d_q, const double *d_v, const int32_t *d_mode, double *d_v_plus, double *d_impulse, int32_t *d_flags, void *stream)
+{
+    PlantCall c = {}; c.mode = PM_RIGID_IMPACT; c.d_q = d_q; c.d_v = d_v; c.d_xdot = d_v_plus; c.d_flags = d_flags; c.d_hold = d_mode; c.d_lambda = d_impulse;
+    return plant_body(h, "lmh_plant_impact_rigid", c, stream);
+}
+
 // ---------------------------------------------------------------------------- zero-order-hold closed loop
 // n_ticks rounds of { lmh_eval ; lmh_plant_step(tau30 = [base_wrench | out.tau], n_substeps) } in one launch (lmh_kernels.hip,
 // lmh_rollout_zoh_ex_body's kernels).  The parameter block travels by value, so the call takes no launch slot.
@@ -1202,9 +1213,11 @@ struct ZohCall {
     const lmh_zoh_io *io;
     const lmh_zoh_servo *servo;   // lmh_rollout_zoh_servo: never with rigid
     const lmh_zoh_rigid *rigid;
+    const lmh_zoh_impact *impact; // lmh_rollout_zoh_rigid_impact: only with a rigid record that is on
     bool d_ref_required;          // lmh_rollout_zoh_ref
 };
 static const lmh_zoh_opts kNoOpts = {}; static const lmh_zoh_io kNoIo = {}; static const lmh_zoh_servo kNoServo = {}; static const lmh_zoh_rigid kNoRigid = {};
+static const lmh_zoh_impact kNoImpact = {};
 
 // The refusals of each record, in the words and the order they always had; nullptr = fine
 static const char *zoh_box_refusal(const lmh_handle *h, const ZohBoxCall &bx, const lmh_zoh_opts &o)
@@ -1256,8 +1269,17 @@ static const char *zoh_rigid_refusal(const lmh_zoh_rigid &rg)
     return nullptr;
 }
 
+static const char *zoh_impact_refusal(const lmh_zoh_impact &im, const lmh_zoh_rigid &rg)
+{
+    if ((im.enable | 1) != 1) return "lmh_rollout_zoh_rigid_impact: enable must be 0 or 1";
+    if (im.reserved != 0) return "lmh_rollout_zoh_rigid_impact: reserved must be 0";
+    if (im.enable && rg.source == 0) return "lmh_rollout_zoh_rigid_impact: enable = 1 needs a rigid record with a source (the impact is the rigid plant's)";
+    if (im.enable && !im.d_mode_prev) return "lmh_rollout_zoh_rigid_impact: enable = 1 needs d_mode_prev";
+    return nullptr;
+}
+
 // Refusals in the order of the two calls the loop composes, every record's own behind the counts they depend on: the handle, the pointers, d_ref
-// where it is required, the box, the counts, the options, io, servo, rigid, then the precision and the contact constants.
+// where it is required, the box, the counts, the options, io, servo, rigid, impact, then the precision and the contact constants.
 static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, int n_ticks, int n_substeps, void *stream, const ZohCall &c)
 {
     int rc = ready(h); if (rc) return rc;                            // no record is read before this
@@ -1265,6 +1287,7 @@ static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_st
     const lmh_zoh_io &io = c.io ? *c.io : kNoIo;
     const lmh_zoh_servo &sv = c.servo ? *c.servo : kNoServo;
     const lmh_zoh_rigid &rg = c.rigid ? *c.rigid : kNoRigid;
+    const lmh_zoh_impact &im = c.impact ? *c.impact : kNoImpact;
     const char *why = nullptr;
     if (!d_state || !d_out || !d_status) why = "lmh_rollout_zoh: null device pointer";
     else if (c.d_ref_required && !o.d_ref) why = "lmh_rollout_zoh_ref: null d_ref";
@@ -1274,6 +1297,7 @@ static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_st
     if (!why) why = zoh_io_refusal(io);
     if (!why) why = zoh_servo_refusal(sv, n_substeps);
     if (!why) why = zoh_rigid_refusal(rg);
+    if (!why) why = zoh_impact_refusal(im, rg);
     if (!why && h->cfg.precision != LMH_PRECISION_FP64) why = "lmh_rollout_zoh: LMH_PRECISION_FP64 handles only (this handle's precision has no instantiation of the kernel)";
     if (why) return fail(LMH_ERR_BAD_ARG, why);
     rc = plant_constants_ok(h); if (rc) return rc;
@@ -1283,6 +1307,7 @@ static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_st
     // What the one launch is given, and with it which kernel of the family runs (lmh_launch.h); the options record always rides along:
     //   box                     the box record; ref is NULL and the handle has no ground table (both refused above); no io, servo, rigid
     //   rigid, source != 0      the io record always and the rigid record; no ground, no servo
+    //   impact, enable != 0     the rigid launch's records and the impact record (never without rigid: refused above)
     //   servo, mode != 0        the io record always, the ground as the handle has it, the servo record with the handle's table and stride
     //   io that asks something  the io record, the ground
     //   otherwise               no io record, the ground
@@ -1294,9 +1319,10 @@ static int zoh_body(lmh_handle *h, double *d_state, double *d_out, int32_t *d_st
     const LmhZohIo zi = {io.d_meas, io.actuators ? io.d_act_mem : nullptr, io.d_applied, h->act.device(), h->act.stride(LMH_ACT_STRIDE), io.actuators, 0};
     const LmhZohServo zs = {sv.d_setpoint, h->servo.device(), h->servo.stride(LMH_SERVO_STRIDE), sv.mode, 0};
     const LmhZohRigid zr = {rg.d_mode, rg.d_lambda, rg.kv, rg.source, 0};
+    const LmhZohImpact zm = {im.d_mode_prev, im.d_impulse};
     return launch(h, nullptr, [&] { lmh_launch_rollout_zoh(&h->P, d_state, d_out, d_status, o.d_base_wrench, o.d_log, o.d_ref, n_ticks, n_substeps, &ex, c.box ? &zb : nullptr, with_io ? &zi : nullptr,
                                                            rigid ? nullptr : h->ground.device(), rigid ? 0 : h->ground.stride(LMH_GROUND_STRIDE), servo ? &zs : nullptr, rigid ? &zr : nullptr,
-                                                           (hipStream_t)stream); });
+                                                           im.enable ? &zm : nullptr, (hipStream_t)stream); });
 }
 
 extern "C" int lmh_rollout_zoh(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const double *d_base_wrench, double *d_log,
@@ -1341,6 +1367,14 @@ extern "C" int lmh_rollout_zoh_rigid(lmh_handle *h, double *d_state, double *d_o
                                      int n_ticks, int n_substeps, void *stream)
 {
     ZohCall c = {}; c.opts = opts; c.io = io; c.rigid = rigid;
+    return zoh_body(h, d_state, d_out, d_status, n_ticks, n_substeps, stream, c);
+}
+
+// lmh_rollout_zoh_rigid with the plastic impact in front of every hold that holds a foot more than the hold before it (include/lmh.h)
+extern "C" int lmh_rollout_zoh_rigid_impact(lmh_handle *h, double *d_state, double *d_out, int32_t *d_status, const lmh_zoh_opts *opts, const lmh_zoh_io *io, const lmh_zoh_rigid *rigid,
+                                            const lmh_zoh_impact *impact, int n_ticks, int n_substeps, void *stream)
+{
+    ZohCall c = {}; c.opts = opts; c.io = io; c.rigid = rigid; c.impact = impact;
     return zoh_body(h, d_state, d_out, d_status, n_ticks, n_substeps, stream, c);
 }
 

@@ -142,6 +142,13 @@ struct LmhZohRigid {
     int32_t pad;
 };
 
+// lmh_rollout_zoh_rigid_impact (include/lmh.h, lmh_zoh_impact): what the launch takes beyond lmh_rollout_zoh_rigid's -- the mode of the hold before
+// each robot's next one, and where the impulses go.  Passed with enable = 1 only: without it the launch is lmh_rollout_zoh_rigid's.
+struct LmhZohImpact {
+    int32_t *mode_prev;         // [n_instances], read and written once per control tick by the robot's own wave 0
+    double *impulse;            // [n_ticks][n_instances][12], or nullptr
+};
+
 // walking-plan generator (lmh_gen_walk): arguments of the device kernel
 #define LMH_GEN_MAX_STEPS 1022
 struct LmhWalkSpec {

@@ -5100,6 +5100,75 @@ __device__ __forceinline__ int plant_derivative_rigid(double *L, LmhCParams &P, 
     phase_outputs_qdd(L, PL_AP);
     return flags;
 }
+// the plastic impact of the rigid plant (lmh_plant_impact_rigid, include/lmh.h) for the state in L[P_Q], L[P_V]: the velocity jumps to the
+// nearest one, in the metric of M, that the mode's constraints admit.  The derivative's sibling -- the same kinematics, M, J, Y = M^-1 J'
+// (plant_minv_rigid, whose first right-hand side is an exact zero here and whose sink is dropped), A = J Y and register solve under `live` --
+// with the sole twist J vhat (P_VFOOT) as the right-hand side: no torque, no C, no Jdot qdot, no kv, so neither phase_newton_euler nor
+// refs_jpqp runs (nothing behind them reads what they write: the CRBA runs beside the Newton-Euler pass on the two-wave schedule).
+// dv (state ordering, world frame) -> L[P_QDD], the impulse -> L[RG_LAM] (zeros on the rows that are not held); FLIGHT: dvhat is an exact
+// zero whatever Y holds.  L[P_V] is left alone: the caller forms v + dv, and with FLIGHT takes v as it is.  Returns LMH_FLAG_NOT_SPD | LMH_FLAG_NONFINITE (of v + dv) |
+// LMH_FLAG_IMPULSE_PULL | LMH_FLAG_IMPULSE_SLIP, wave-uniform.
+__device__ __forceinline__ int plant_impact_rigid(double *L, LmhCParams &P, const IbPack &ibp, int lane, unsigned live)
+{
+    if (lane < 30) L[P_VP + lane] = L[P_V + lane];                 // one velocity for every term
+    WSYNC();
+    phase_fk<double>(L, P.lcoef);
+    phase_com_x<1, double>(L, 0);
+    phase_crba<double>(L, ib_unpack(ibp));
+    phase_jacobian<double>(L);
+    refs_vfoot_pdjoints(L, P);                                     // sole twists J vhat -> P_VFOOT (its PD law on lanes 32..61 rides along unread)
+    if (lane < 30) L[PL_R + lane] = 0.0;
+    else if (lane >= 32) L[PL_ZERO + lane - 32] = 0.0;
+    WSYNC();
+    int flags = plant_minv_rigid(L, lane, [&](double) {});
+    // [A | w]: A = J Y as the derivative forms it, column 12 the sole twist
+#pragma unroll
+    for (int it = 0; it < 3; it++) {
+        const int e = lane + 64 * it, ee = (e < 144) ? e : 0, r = ee / 12, c = ee % 12, ft = r / 6;
+        const double *Jr = L + P_JC + 72 * ft + 12 * (r % 6), *Yb = L + RG_Y + c, *Yl = L + RG_Y + 12 * (6 + 6 * ft) + c;
+        double s = 0.0;
+#pragma unroll
+        for (int m = 0; m < 6; m++) s += Jr[m] * Yb[12 * m];
+#pragma unroll
+        for (int j = 0; j < 6; j++) s += Jr[6 + j] * Yl[12 * j];
+        if (e < 144) L[RG_A + 13 * r + c] = s;
+    }
+    if (lane >= 52) L[RG_A + 13 * (lane - 52) + 12] = L[P_VFOOT + lane - 52];
+    WSYNC();
+    {
+        double a[12], b[1];
+        const int l16 = lane & 15, lr = (l16 < 12) ? l16 : 0;      // (a copy of the system per DPP row)
+#pragma unroll
+        for (int c = 0; c < 12; c++) a[c] = L[RG_A + 13 * lr + c];
+        b[0] = -L[RG_A + 13 * lr + 12];
+        if (live != 0u) { if (gj_solve_regs<12, 1>(a, b, live)) flags |= LMH_FLAG_NOT_SPD; }      // (wave-uniform: FLIGHT solves nothing)
+        if (lane < 12) L[RG_LAM + lane] = ((live >> lane) & 1u) ? b[0] : 0.0;
+    }
+    WSYNC();
+    if (lane < 30) {
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 12; k++) s += L[RG_Y + 12 * lane + k] * L[RG_LAM + k];
+        L[PL_AP + lane] = (live != 0u) ? s : 0.0;                  // (FLIGHT: an exact zero, whatever Y holds)
+    }
+    {   // what the ground would have had to supply, reported and not enforced: a held foot's impulse pulls | leaves its friction disc
+        const double mu = P.contact_mu;
+#pragma unroll
+        for (int ft = 0; ft < 2; ft++) {
+            const double fx = L[RG_LAM + 6 * ft + 3], fy = L[RG_LAM + 6 * ft + 4], fz = L[RG_LAM + 6 * ft + 5];
+            const bool held = ((live >> (6 * ft)) & 1u) != 0u;
+            if (held && fz < 0.0) flags |= LMH_FLAG_IMPULSE_PULL;
+            if (held && sqrt(fx * fx + fy * fy) > mu * fz) flags |= LMH_FLAG_IMPULSE_SLIP;
+        }
+        flags = __builtin_amdgcn_readfirstlane(flags);             // (every lane read the same words)
+    }
+    WSYNC();
+    phase_outputs_qdd(L, PL_AP);
+    const int l30 = (lane < 30) ? lane : 0;
+    const double v0 = L[P_V + l30], v1 = (live != 0u) ? v0 + L[P_QDD + l30] : v0;       // (FLIGHT: v itself, the sign of a zero included; the callers add the same way)
+    if (__ballot(!(fabs(v1) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
+    return flags;
+}
 // ============================================================================ the hold and the plant kernel: every call of either plant
 // what the RIGID hold takes in place of a ground and a servo: live and kv as in plant_derivative_rigid; lam: lane i < 12 leaves with entry i of
 // the multiplier of the first stage of the last substep
@@ -5111,8 +5180,9 @@ struct RigidHold { unsigned live; double kv, lam; };
 // The derivative is plant_derivative<GROUND, SERVO> (gnd is read with GROUND only, servo with SERVO only) or, with RIGID, plant_derivative_rigid.
 // LOOP changes no statement: the zero-order-hold kernels take the RIGID hold as an instantiation of their own, so that lmh_plant_kernel's stays
 // the only caller of its copy and that kernel keeps its instruction stream (what the compiler propagates into a function from its one call
-// site, the kernel's own LDS array among it, it no longer propagates once other kernels call the same instantiation).
-template <bool GROUND = false, bool SERVO = false, bool RIGID = false, bool LOOP = false>
+// site, the kernel's own LDS array among it, it no longer propagates once other kernels call the same instantiation).  For the same reason the
+// kernels with the impact take a third copy (LOOP = 2), and lmh_rollout_zoh_rigid_kernel's stays its own.
+template <bool GROUND = false, bool SERVO = false, bool RIGID = false, int LOOP = 0>
 __device__ __forceinline__ void plant_hold(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau, double dt, int n_substeps, double &x, int &flags, const double *gnd = nullptr,
                                            const ServoLane *servo = nullptr, RigidHold *rigid = nullptr)
 {
@@ -5143,12 +5213,14 @@ __device__ __forceinline__ void plant_hold(double *L, LmhCParams &P, const IbPac
 //            last substep for the step
 struct PlantArgs { const double *q, *v, *tau30; double *state, *xdot, *contact; int32_t *flags; int n_substeps; const double *ground; size_t ground_stride;
                    const double *servo; size_t servo_stride; const double *setpoint; const int32_t *hold; double kv; double *lambda; };
-// MODE: PM_CONTACT | PM_DERIV | PM_STEP.  GROUND, SERVO: the options of the compliant plant (plant_derivative); RIGID: the rigid-contact plant
-// (plant_derivative_rigid) in its place, which reads no ground table and no servo table.
+// MODE: PM_CONTACT | PM_DERIV | PM_STEP | PM_RIGID_IMPACT.  GROUND, SERVO: the options of the compliant plant (plant_derivative); RIGID: the
+// rigid-contact plant (plant_derivative_rigid) in its place, which reads no ground table and no servo table.  PM_RIGID_IMPACT
+// (lmh_plant_impact_rigid; RIGID only): plant_impact_rigid at (q, v) under hold; xdot takes v_plus [n_instances][30], lambda the impulse.
 template <int MODE, bool GROUND = false, bool SERVO = false, bool RIGID = false>
 __global__ void __launch_bounds__(64) lmh_plant_kernel(LmhDevParams P_arg, PlantArgs A)
 {
-    static_assert(MODE == PM_CONTACT || MODE == PM_DERIV || MODE == PM_STEP, "contact wrench | derivative | RK4 step");
+    static_assert(MODE == PM_CONTACT || MODE == PM_DERIV || MODE == PM_STEP || MODE == PM_RIGID_IMPACT, "contact wrench | derivative | RK4 step | impact");
+    static_assert(RIGID || MODE != PM_RIGID_IMPACT, "the impact is the rigid plant's");
     static_assert(!SERVO || MODE == PM_STEP, "the servo lives inside a hold");
     static_assert(!RIGID || MODE != PM_CONTACT, "the rigid plant's wrench is its multiplier: derivative | RK4 step");
     static_assert(!(RIGID && (GROUND || SERVO)), "the rigid plant has no ground table and no servo");
@@ -5178,7 +5250,13 @@ __global__ void __launch_bounds__(64) lmh_plant_kernel(LmhDevParams P_arg, Plant
         RigidHold R = {0u, 0.0, 0.0};
         if constexpr (RIGID) { R.live = (unsigned)__builtin_amdgcn_readfirstlane((int)rigid_live(A.hold ? A.hold[inst] : (int)LMH_PHASE_DOUBLE)); R.kv = A.kv; }      // (one word per robot: wave-uniform)
         int flags = 0;
-        if constexpr (MODE == PM_DERIV) {
+        if constexpr (MODE == PM_RIGID_IMPACT) {
+            load_qv(L, A.q, A.v, inst, lane, false);               // (the impact sets P_VP itself)
+            WSYNC();
+            flags |= plant_impact_rigid(L, P, ibp, lane, R.live);
+            if (lane < 30) A.xdot[30 * (size_t)inst + lane] = (R.live != 0u) ? L[P_V + lane] + L[P_QDD + lane] : L[P_V + lane];
+            if (A.lambda && lane < 12) A.lambda[12 * (size_t)inst + lane] = L[RG_LAM + lane];
+        } else if constexpr (MODE == PM_DERIV) {
             load_qv(L, A.q, A.v, inst, lane, false);               // (the derivative sets P_VP itself)
             WSYNC();
             if constexpr (RIGID) flags |= plant_derivative_rigid(L, P, ibp, lane, tau, R.live, R.kv);
@@ -5209,14 +5287,14 @@ extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *
                                  int n_substeps, const double *ground, size_t ground_stride, const double *servo, size_t servo_stride, const double *setpoint, const int32_t *hold, double kv,
                                  double *lambda, hipStream_t s)
 {
-    // the ten instantiations there are, the compliant ones indexed by [a ground table on the handle].  The rigid calls read no ground and no servo,
+    // the eleven instantiations there are, the compliant ones indexed by [a ground table on the handle].  The rigid calls read no ground and no servo,
     // whatever the handle carries; a setpoint is lmh_plant_step_servo (PM_STEP only; servo NULL: zero gains)
     typedef void (*Kernel)(LmhDevParams, PlantArgs);
-    static const Kernel rigid[2] = {lmh_plant_kernel<PM_DERIV, false, false, true>, lmh_plant_kernel<PM_STEP, false, false, true>};
+    static const Kernel rigid[3] = {lmh_plant_kernel<PM_DERIV, false, false, true>, lmh_plant_kernel<PM_STEP, false, false, true>, lmh_plant_kernel<PM_RIGID_IMPACT, false, false, true>};
     static const Kernel with_servo[2] = {lmh_plant_kernel<PM_STEP, false, true>, lmh_plant_kernel<PM_STEP, true, true>};
     static const Kernel compliant[2][3] = {{lmh_plant_kernel<PM_CONTACT>, lmh_plant_kernel<PM_DERIV>, lmh_plant_kernel<PM_STEP>},
                                            {lmh_plant_kernel<PM_CONTACT, true>, lmh_plant_kernel<PM_DERIV, true>, lmh_plant_kernel<PM_STEP, true>}};
-    const Kernel kernel = (mode == PM_RIGID_DERIV || mode == PM_RIGID_STEP) ? rigid[mode == PM_RIGID_STEP] :
+    const Kernel kernel = (mode == PM_RIGID_DERIV || mode == PM_RIGID_STEP || mode == PM_RIGID_IMPACT) ? rigid[mode - PM_RIGID_DERIV] :
                           setpoint ? with_servo[ground != nullptr] : compliant[ground != nullptr][(mode == PM_CONTACT) ? 0 : (mode == PM_DERIV) ? 1 : 2];
     const PlantArgs a = {q, v, tau30, state, xdot, contact, flags, n_substeps, ground, ground_stride, servo, servo_stride, setpoint, hold, kv, lambda};
     hipLaunchKernelGGL(kernel, dim3(P->n_instances), dim3(64), 0, s, *P, a);
@@ -5368,6 +5446,9 @@ __device__ __forceinline__ ServoLane zoh_servo_lane(const double *L, int lane, i
 // lmh_rollout_zoh_rigid_kernel's arguments: lmh_rollout_zoh_io_kernel's, then the hold's record.  Neither the ground nor the servo table follows.
 struct ZohRigidArgs { ZohIoArgs a; LmhZohRigid rg; };
 static_assert(sizeof(ZohIoArgs) % 8 == 0 && alignof(ZohRigidArgs) == 8, "ZohRigidArgs continues ZohIoArgs in the kernel-argument segment");
+// lmh_rollout_zoh_rigid_impact_kernel's arguments: lmh_rollout_zoh_rigid_kernel's, then the impact's record
+struct ZohImpactArgs { ZohRigidArgs a; LmhZohImpact im; };
+static_assert(sizeof(ZohRigidArgs) % 8 == 0 && alignof(ZohImpactArgs) == 8, "ZohImpactArgs continues ZohRigidArgs in the kernel-argument segment");
 // What the RIGID hold needs survives it below the scratch, as with the compliant plant's PL_* block: the per-launch tables, the reference cache,
 // the K_f^-1 cache and the push cursor.  RG_* lies in S0 + [768, 1440): in front of Q_TRASH and of kinv_compute's scratch (A_XR), which is formed
 // again whenever it is needed.  plant_derivative_rigid writes P_VP, P_VFOOT, P_QREF and P_JPQP below S0 -- words every evaluation forms for itself
@@ -5392,6 +5473,33 @@ __device__ __forceinline__ RigidHold zoh_rigid_hold(LmhCParams &P, int inst, int
         mode = m[((src == LMH_RIGID_PER_TICK) ? (size_t)tick * (size_t)LMH_KERNARG_PARAMS().n_instances : (size_t)0) + (size_t)inst];
     RigidHold R = {(unsigned)__builtin_amdgcn_readfirstlane((int)rigid_live(mode)), zoh_args<ZohRigidArgs>().rg.kv, 0.0};      // (one word per robot: wave-uniform)
     return R;
+}
+// ---- lmh_rollout_zoh_rigid_impact (include/lmh.h): the RIGID body with the plastic impact between the tick's mode and its hold (the IMPACT
+// flag).  wave 0, behind zoh_rigid_hold: the feet the tick's mode holds and the hold before it did not (rigid_live of mode_prev[robot]) make
+// a touchdown; then plant_impact_rigid runs on the TRUE state under the tick's whole mode, v <- v + dv on the integrator's register, and the
+// impulse leaves (zeros on a tick without a touchdown).  Nothing is carried across controller_eval: the previous mode is one word in global
+// memory, read here by lane 0 and written back by lane 0 -- the lane that stored it loads it, ordinary vector accesses, no fence, as the
+// true state parked in d_state is.  The impact writes what the derivative writes and less, so what survives the hold survives it too.
+__device__ __forceinline__ int rigid_mode_of_live(unsigned live)
+{
+    return (live == 0xFFFu) ? (int)LMH_PHASE_DOUBLE : (live == 0x03Fu) ? (int)LMH_PHASE_RIGHT : (live == 0xFC0u) ? (int)LMH_PHASE_LEFT : (int)LMH_PHASE_FLIGHT;
+}
+__device__ __forceinline__ void zoh_rigid_impact(double *L, LmhCParams &P, int inst, int tick, int lane, unsigned live, double &x, int &flags)
+{
+    int32_t *mp = zoh_args<ZohImpactArgs>().im.mode_prev + inst;
+    int prev = 0;
+    if (lane == 0) { prev = *mp; *mp = rigid_mode_of_live(live); }
+    const unsigned newly = live & ~(unsigned)__builtin_amdgcn_readfirstlane((int)rigid_live(__builtin_amdgcn_readfirstlane(prev)));      // (one word per robot: wave-uniform)
+    double imp = 0.0;
+    if (newly != 0u) {
+        WSYNC();
+        if (lane < 60) L[P_Q + lane] = x;                          // q | v are one run: the true state, not what the evaluation measured
+        WSYNC();
+        flags |= plant_impact_rigid(L, P, ib_pack(), lane, live);
+        if (lane >= 30 && lane < 60) x += L[P_QDD + lane - 30];
+        imp = L[RG_LAM + ((lane < 12) ? lane : 0)];
+    }
+    if (double *ip = zoh_args<ZohImpactArgs>().im.impulse) { if (lane < 12) ip[((size_t)tick * LMH_KERNARG_PARAMS().n_instances + inst) * 12 + lane] = imp; }
 }
 // The loop.  lmh_rollout_zoh (include/lmh.h): for every robot exactly what n_ticks rounds of { lmh_eval ; lmh_plant_step(tau30 = [base_wrench |
 // out.tau], n_substeps) } leave, bit for bit, with the robot on chip for the whole launch.  One workgroup per robot; the launch opens with
@@ -5426,7 +5534,8 @@ enum { ZM_BUILTIN, ZM_REF, ZM_BOX };
 // a control tick's hold is the SERVO plant_hold with the tick's one ServoLane (zoh_servo_lane), formed where wave 0 picks up tau.
 // RIGID (lmh_rollout_zoh_rigid_kernel; always with IO, never with GROUND, SERVO or ZM_BOX; its arguments continue ZohIoArgs): every piece of a
 // control tick's hold is the RIGID plant_hold with the tick's one RigidHold (zoh_rigid_hold); the multiplier leaves behind the hold.
-template <int MODE, bool IO = false, bool GROUND = false, bool SERVO = false, bool RIGID = false>
+// IMPACT (lmh_rollout_zoh_rigid_impact_kernel; always with RIGID; its arguments continue ZohRigidArgs): zoh_rigid_impact in front of the hold.
+template <int MODE, bool IO = false, bool GROUND = false, bool SERVO = false, bool RIGID = false, bool IMPACT = false>
 __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
 {
     constexpr bool REF = MODE != ZM_BUILTIN, BOX = MODE == ZM_BOX;
@@ -5435,6 +5544,7 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
     static_assert(IO || !SERVO, "the servo kernels are instantiations of the IO body");
     static_assert(IO || !RIGID, "the rigid kernels are instantiations of the IO body");
     static_assert(!(RIGID && (GROUND || SERVO || BOX)), "the rigid hold has no ground table, no servo and no box-constrained form");
+    static_assert(RIGID || !IMPACT, "the impact is the rigid plant's");
     LmhCParams &P0 = LMH_KERNARG_PARAMS();
     const int inst = blockIdx.x;
     if (inst >= P0.n_instances) return;
@@ -5514,6 +5624,7 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
             if constexpr (SERVO) servo = zoh_servo_lane(L, lane, inst, tick, nsub, dt);
             RigidHold rigid = {0u, 0.0, 0.0};
             if constexpr (RIGID) rigid = zoh_rigid_hold(P, inst, tick, k);
+            if constexpr (IMPACT) zoh_rigid_impact(L, P, inst, tick, lane, rigid.live, x, flags);
             const bool pushes = zoh_args<ZohExArgs>().ex.pushes != 0;
             // substeps of the launch | of them behind the robot: the cursor's units, formed with pushes only (the host bounds the product then)
             const int lim = pushes ? zoh_args<ZohExArgs>().n_ticks * nsub : 0;
@@ -5525,7 +5636,7 @@ __device__ __forceinline__ void lmh_rollout_zoh_ex_body(double *L)
                     const int rel = __builtin_amdgcn_readfirstlane(((const int *)(L + P_PUSH))[0]);
                     if (rel > done && rel < done + r) s = rel - done;
                 }
-                plant_hold<GROUND, SERVO, RIGID, RIGID>(L, P, ib_pack(), lane, tau, dt, s, x, flags, GROUND ? zoh_args<ZohGroundArgs>().ground + zoh_args<ZohGroundArgs>().ground_stride * (size_t)inst : nullptr, SERVO ? &servo : nullptr,
+                plant_hold<GROUND, SERVO, RIGID, RIGID ? (IMPACT ? 2 : 1) : 0>(L, P, ib_pack(), lane, tau, dt, s, x, flags, GROUND ? zoh_args<ZohGroundArgs>().ground + zoh_args<ZohGroundArgs>().ground_stride * (size_t)inst : nullptr, SERVO ? &servo : nullptr,
                                                         RIGID ? &rigid : nullptr);
                 done += s; r -= s;
                 if (r > 0) push_poll(L, P, inst, lane, done, lim, x);      // between two substeps: v += dv on the integrator's register
@@ -5605,12 +5716,20 @@ __global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_wav
     (void)A_arg;
     lmh_rollout_zoh_ex_body<REF ? ZM_REF : ZM_BUILTIN, true, false, false, true>(L);
 }
-// One kernel per launch, the first of: rg -> the rigid kernel (the host layer passes neither ground nor sv with it), sv -> the servo kernel, ground -> the ground kernel, io -> the io kernel, bx -> the box kernel, otherwise
+// lmh_rollout_zoh_rigid_impact (include/lmh.h): the rigid kernel's body with the plastic impact in front of a hold whose mode holds a foot more
+template <bool REF>
+__global__ void __launch_bounds__(LMH_ROLLOUT_THREADS) __attribute__((amdgpu_waves_per_eu(2, 2))) lmh_rollout_zoh_rigid_impact_kernel(LmhDevParams P_arg, ZohImpactArgs A_arg)
+{
+    __shared__ double L[LDS_DOUBLES];
+    (void)A_arg;
+    lmh_rollout_zoh_ex_body<REF ? ZM_REF : ZM_BUILTIN, true, false, false, true, true>(L);
+}
+// One kernel per launch, the first of: im -> the rigid kernel with the impact (always with rg), rg -> the rigid kernel (the host layer passes neither ground nor sv with it), sv -> the servo kernel, ground -> the ground kernel, io -> the io kernel, bx -> the box kernel, otherwise
 // the ex kernel.  ex or io NULL: none of their options (all-zero records), so lmh_rollout_zoh and lmh_rollout_zoh_ref are the ex kernel with
 // nothing set.  The host layer never passes bx with ref, io, ground or sv, and never io without ex.
 extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
                                        const LmhZohEx *ex, const LmhZohBox *bx, const LmhZohIo *io, const double *ground, size_t ground_stride, const LmhZohServo *sv, const LmhZohRigid *rg,
-                                       hipStream_t s)
+                                       const LmhZohImpact *im, hipStream_t s)
 {
     // The most dynamic shared memory a launch of lmh_rollout_zoh_box_kernel may ask for (N = LMH_MAX_HORIZON) is above the 64 KB a kernel gets
     // unasked: bx->prepare sets that limit on the current device and launches nothing.
@@ -5624,7 +5743,8 @@ extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, dou
     const ZohExArgs a = {state, out, status, base_wrench, log, ref, ex ? *ex : no_ex, n_ticks, n_substeps};
     const ZohGroundArgs ag = {{a, io ? *io : no_io}, ground, ground_stride};
     auto launch = [&](auto kernel, const auto &args, size_t lds_bytes) { hipLaunchKernelGGL(kernel, dim3(P->n_instances), dim3(LMH_ROLLOUT_THREADS), lds_bytes, s, *P, args); };
-    if (rg) launch(ref ? lmh_rollout_zoh_rigid_kernel<true> : lmh_rollout_zoh_rigid_kernel<false>, ZohRigidArgs{ag.a, *rg}, 0);
+    if (rg && im) launch(ref ? lmh_rollout_zoh_rigid_impact_kernel<true> : lmh_rollout_zoh_rigid_impact_kernel<false>, ZohImpactArgs{{ag.a, *rg}, *im}, 0);
+    else if (rg) launch(ref ? lmh_rollout_zoh_rigid_kernel<true> : lmh_rollout_zoh_rigid_kernel<false>, ZohRigidArgs{ag.a, *rg}, 0);
     else if (sv && ground) launch(ref ? lmh_rollout_zoh_servo_kernel<true, true> : lmh_rollout_zoh_servo_kernel<false, true>, ZohServoArgs{ag, *sv}, 0);
     else if (sv) launch(ref ? lmh_rollout_zoh_servo_kernel<true, false> : lmh_rollout_zoh_servo_kernel<false, false>, ZohServoArgs{ag, *sv}, 0);
     else if (ground) launch(ref ? lmh_rollout_zoh_ground_kernel<true> : lmh_rollout_zoh_ground_kernel<false>, ag, 0);

@@ -7,7 +7,8 @@
 
 enum { TM_TERMS, TM_INVDYN, TM_FWDDYN };    // lmh_launch_terms: the dense terms record | inverse dynamics | forward dynamics (lmh_terms_kernel)
 enum { PM_CONTACT, PM_DERIV, PM_STEP,       // lmh_launch_plant: contact wrench | derivative | RK4 step (lmh_plant_kernel)
-       PM_RIGID_DERIV, PM_RIGID_STEP };     //                   derivative | RK4 step of the rigid-contact plant (lmh_plant_kernel's RIGID instantiations)
+       PM_RIGID_DERIV, PM_RIGID_STEP,       //                   derivative | RK4 step of the rigid-contact plant (lmh_plant_kernel's RIGID instantiations)
+       PM_RIGID_IMPACT };                   //                   its plastic impact (lmh_plant_impact_rigid)
 
 extern "C" void lmh_launch_model(const double *raw, double *model, int n_models, const double *lcoef, hipStream_t s);
 extern "C" void lmh_launch_params_expand(const LmhDevParams *P, const double *d_rec, const double *d_gcol_tab, LmhDevParams *d_blocks, int n, hipStream_t s);
@@ -38,9 +39,11 @@ extern "C" void lmh_launch_rollout(const LmhDevParams *P, const LmhDevParams *d_
 // with the joint servo inside every hold (LmhZohServo, lmh_device.h).
 // rg (lmh_rollout_zoh_rigid; bx, ground and sv are then NULL, ex and io may each be NULL): NULL = not that call; otherwise lmh_rollout_zoh_rigid_kernel, the IO
 // body with the rigid-contact plant in every hold (LmhZohRigid, lmh_device.h).
+// im (lmh_rollout_zoh_rigid_impact with enable = 1; rg is then never NULL): NULL = not that call; otherwise lmh_rollout_zoh_rigid_impact_kernel, the rigid
+// kernel's body with the plastic impact in front of every hold that holds a foot more than the hold before it (LmhZohImpact, lmh_device.h).
 extern "C" void lmh_launch_rollout_zoh(const LmhDevParams *P, double *state, double *out, int32_t *status, const double *base_wrench, double *log, const double *ref, int n_ticks, int n_substeps,
                                        const LmhZohEx *ex, const LmhZohBox *bx, const LmhZohIo *io, const double *ground, size_t ground_stride, const LmhZohServo *sv, const LmhZohRigid *rg,
-                                       hipStream_t s);
+                                       const LmhZohImpact *im, hipStream_t s);
 extern "C" void lmh_launch_metrics_reset(double *metrics, int n_instances, double z_min, double tilt_max, hipStream_t s);
 extern "C" void lmh_launch_summary(int n, const double *state, const double *out, const int32_t *status, double *summary, hipStream_t s);
 extern "C" void lmh_launch_com(const LmhDevParams *P, const double *q, double *com, hipStream_t s);
@@ -54,6 +57,8 @@ extern "C" void lmh_launch_terms(const LmhDevParams *P, int mode, const double *
 // PM_RIGID_DERIV, PM_RIGID_STEP (lmh_plant_derivative_rigid, lmh_plant_step_rigid): the RIGID instantiations with hold ([n_instances] support modes, NULL = both
 // soles held), kv and lambda ([n_instances][12], may be NULL); ground, servo and setpoint are not read.  The other modes read none of the three.  The same
 // launcher, not a new symbol, for the reason given at lmh_launch_rollout_zoh.
+// PM_RIGID_IMPACT (lmh_plant_impact_rigid): the RIGID instantiation that runs plant_impact_rigid at (q, v) under hold; xdot takes v_plus
+// ([n_instances][30]) and lambda the impulse ([n_instances][12], may be NULL); tau30, state, contact, n_substeps and kv are not read.
 extern "C" void lmh_launch_plant(const LmhDevParams *P, int mode, const double *q, const double *v, const double *tau30, double *state, double *xdot, double *contact, int32_t *flags,
                                  int n_substeps, const double *ground, size_t ground_stride, const double *servo, size_t servo_stride, const double *setpoint, const int32_t *hold, double kv,
                                  double *lambda, hipStream_t s);

@@ -8,7 +8,7 @@ definition on top of the reference's conventions (SupportFoot -> ZMP y of -/+0.0
 """
 import numpy as np
 
-from .capi import FLAG_CONTACT_PULL, FLAG_CONTACT_SLIP, ACT_MAX_DELAY, ACT_MEM_STRIDE, ACT_OFF_ALPHA, ACT_OFF_DELAY, ACT_OFF_TAU_MAX, ACT_STRIDE, FLAG_BOX_EMPTY, FLAG_NONFINITE, FLAG_NOT_SPD, FLAG_QP_MAXITER, FLAG_ZMP_RANGE, GROUND_OFF_H_L, GROUND_OFF_H_R, GROUND_OFF_N_L, GROUND_OFF_N_R, GROUND_STRIDE, IK_TARGET_STRIDE, LIP_STRIDE, MAX_PUSHES, MPC_BOX_MAX_ROUNDS, MPC_STRIDE, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE, SERVO_OFF_KD, SERVO_OFF_KP, SERVO_STRIDE, SETPOINT_STRIDE
+from .capi import FLAG_CONTACT_PULL, FLAG_CONTACT_SLIP, FLAG_IMPULSE_PULL, FLAG_IMPULSE_SLIP, ACT_MAX_DELAY, ACT_MEM_STRIDE, ACT_OFF_ALPHA, ACT_OFF_DELAY, ACT_OFF_TAU_MAX, ACT_STRIDE, FLAG_BOX_EMPTY, FLAG_NONFINITE, FLAG_NOT_SPD, FLAG_QP_MAXITER, FLAG_ZMP_RANGE, GROUND_OFF_H_L, GROUND_OFF_H_R, GROUND_OFF_N_L, GROUND_OFF_N_R, GROUND_STRIDE, IK_TARGET_STRIDE, LIP_STRIDE, MAX_PUSHES, MPC_BOX_MAX_ROUNDS, MPC_STRIDE, PHASE_DOUBLE, PHASE_LEFT, PHASE_RIGHT, PHASE_FLIGHT, PUSH_STRIDE, SERVO_OFF_KD, SERVO_OFF_KP, SERVO_STRIDE, SETPOINT_STRIDE
 
 
 def stance_zmp(simulation_time, time_step, support_foot=2):
@@ -807,6 +807,39 @@ def rigid_contact_acceleration(M, C, J, Jpqp, vhat, tau30, mode, kv, contact_mu=
     return a, lam, flags
 
 
+def rigid_contact_impact(M, J, vhat, mode, contact_mu=0.7, info=None):
+    """The numpy statement of the rigid plant's plastic impact (include/lmh.h, lmh_plant_impact_rigid) for ONE robot, in the coordinates of
+    M: M [30,30], J [12,30], vhat [30] (v in M's coordinates) and mode (only the low two bits are read) -> (dvhat [30], impulse [12],
+    flags).  The velocity jumps to the nearest one, in the metric of M, at which every held sole rests: w = J_S vhat, Y = M^-1 J_S',
+    A = J_S Y, Lam_S = -A^-1 w by the unpivoted Gauss-Jordan, dvhat = Y Lam_S; ALL rows the mode holds take part.  The impulse is exactly 0
+    on the rows that are not held, and LMH_PHASE_FLIGHT gives exact zeros for both.  flags: FLAG_IMPULSE_PULL (a held foot's f_z < 0: the
+    sole was leaving the ground), FLAG_IMPULSE_SLIP (hypot(f_x, f_y) > contact_mu f_z on a held foot), FLAG_NOT_SPD (a pivot of A was not
+    positive), FLAG_NONFINITE.  info (a dict, optional) receives A, w, Y, rows and the pivots."""
+    M, J, vhat = np.asarray(M, dtype=np.float64), np.asarray(J, dtype=np.float64), np.asarray(vhat, dtype=np.float64)
+    rows = list(RIGID_ROWS[int(mode) & 3])
+    lam, dvhat, flags = np.zeros(12), np.zeros(30), 0
+    if rows:
+        Js = J[rows]
+        w = Js @ vhat
+        Y = np.linalg.solve(M, Js.T)
+        A = Js @ Y
+        x, piv = gauss_jordan_unpivoted(A, w)
+        lam[rows] = -x
+        dvhat = Y @ lam[rows]
+        if info is not None:
+            info.update(A=A, w=w, Y=Y, rows=rows, pivots=piv)
+        if not np.all(piv > 0.0):
+            flags |= FLAG_NOT_SPD
+        for ft in range(2):
+            if 6 * ft in rows:
+                fx, fy, fz = lam[6 * ft + 3:6 * ft + 6]
+                flags |= FLAG_IMPULSE_PULL if fz < 0.0 else 0
+                flags |= FLAG_IMPULSE_SLIP if np.hypot(fx, fy) > contact_mu * fz else 0
+    if not (np.all(np.isfinite(dvhat)) and np.all(np.isfinite(lam)) and np.all(np.isfinite(vhat))):
+        flags |= FLAG_NONFINITE
+    return dvhat, lam, flags
+
+
 def rigid_modes(phase_samples, k):
     """The modes lmh_plant_step_rigid takes for a walking host loop: the support phase of the plan(s) at preview index k (preview_index(t,
     mpc_dt) of the controller evaluation the hold follows), clamped into the arrays as the kernels clamp it.  phase_samples [n] or [B,n]
@@ -821,5 +854,5 @@ def rigid_modes(phase_samples, k):
 
 __all__ = ["stance_zmp", "find_poly_coeff", "foot_coeff_trajectory", "walk_plan", "jump_plan", "walk_plans", "jump_plans",
            "push_schedule", "check_push_records", "draw_pushes", "zoh_hold_pieces", "actuator_records", "actuator_step", "ground_planes", "ground_slope", "ground_contact",
-           "preview_index", "lip_rollout", "com_targets", "rigid_contact_acceleration", "rigid_modes", "gauss_jordan_unpivoted", "RIGID_ROWS",
+           "preview_index", "lip_rollout", "com_targets", "rigid_contact_acceleration", "rigid_contact_impact", "FLAG_IMPULSE_PULL", "FLAG_IMPULSE_SLIP", "rigid_modes", "gauss_jordan_unpivoted", "RIGID_ROWS",
            "PHASE_DOUBLE", "PHASE_RIGHT", "PHASE_LEFT", "PHASE_FLIGHT"]

@@ -18,7 +18,9 @@ the run) and where they are at the end: a cell that stands only by pulling on th
 multipliers and the log give |lambda - out.f|), which must reproduce the host loop's table; then, with the call in hand, run 2 again at
 n_substeps = 10 (a control period of 10 ms) and with mode="plan" on a walking plan (gen_walk's defaults, x scale 0.03 m: the plan decides
 which soles are held; there is no impact model and the contact stays bilateral).
-Usage: python scripts/rigid_stand.py [--ticks 2000] [--kv 50] [--z-min 0.2] [--tilt-max 0.5] [--zoh] [--out FILE]"""
+--impact (with --zoh): the walking-plan run once more as rollout_zoh_rigid_impact -- the plastic impact at every touchdown of the plan,
+d_mode_prev = the plan's first mode -- laid beside the run without it, with the cells that raise LMH_FLAG_IMPULSE_PULL / _SLIP counted.
+Usage: python scripts/rigid_stand.py [--ticks 2000] [--kv 50] [--z-min 0.2] [--tilt-max 0.5] [--zoh [--impact]] [--out FILE]"""
 import argparse
 
 import numpy as np
@@ -32,6 +34,7 @@ ap.add_argument("--kv", type=float, default=50.0)
 ap.add_argument("--z-min", type=float, default=0.2)
 ap.add_argument("--tilt-max", type=float, default=0.5)
 ap.add_argument("--zoh", action="store_true", help="one rollout_zoh_rigid launch per run instead of the host loop; then n_substeps = 10 and a walking plan")
+ap.add_argument("--impact", action="store_true", help="with --zoh: the walking-plan run again with the plastic impact at every touchdown")
 ap.add_argument("--out", default=None)
 args = ap.parse_args()
 assert torch.cuda.is_available(), "rigid_stand.py runs on the GPU only"
@@ -71,11 +74,11 @@ def run(ctl, control):
     return first, float(g.max()), at, flags.cpu().numpy(), st
 
 
-def run_zoh(ctl, control, n_substeps=1, mode=None):
-    """run() as one launch of rollout_zoh_rigid with a metrics record -> the same tuple"""
+def run_zoh(ctl, control, n_substeps=1, mode=None, impact=None):
+    """run() as one launch of rollout_zoh_rigid with a metrics record -> the same tuple.  impact: None | d_mode_prev (int32 [B])"""
     st = ctl.new_state(q, v, t=0.0, v_prev=v)
     m = ctl.new_metrics(args.z_min, args.tilt_max)
-    r = ctl.rollout_zoh_rigid(st, args.ticks, n_substeps, mode=mode, kv=args.kv, lam=True, log=True, metrics=m)
+    r = ctl.rollout_zoh_rigid(st, args.ticks, n_substeps, mode=mode, kv=args.kv, lam=True, log=True, metrics=m, impact=impact)
     torch.cuda.synchronize()
     first = ctl.split_metrics(m.cpu().numpy())["first_fall"].astype(np.int64)
     n = args.ticks if first[control] < 0 else int(first[control])
@@ -142,4 +145,15 @@ if args.zoh:
     walk.set_params(**fields)
     fw, gw, _, flw, stw = run_zoh(walk, control, mode="plan")
     report("run 4, mode=\"plan\" on gen_walk's default plan (step length 0.03 m), n_substeps = 1", fw, gw, flw, stw)
+    if args.impact:
+        phase = walk.get_refs()["phase"]
+        prev = torch.full((B,), int(phase[0]) & 3, dtype=torch.int32, device=walk.device)       # no impact on the first tick
+        fi, gi, _, fli, sti = run_zoh(walk, control, mode="plan", impact=prev)
+        report("run 5, run 4 with the plastic impact at every touchdown of the plan (rollout_zoh_rigid_impact)", fi, gi, fli, sti)
+        falls = lambda f: "%d .. %d" % (f[f >= 0].min(), f[f >= 0].max()) if (f >= 0).any() else "none"
+        say("  first-fall ticks of the cells that fall: %s with the impact, %s without (round 36: 649 .. 1024); cells that raise LMH_FLAG_IMPULSE_PULL: %d of %d, "
+            "LMH_FLAG_IMPULSE_SLIP: %d; later than without: %d cells, earlier: %d, the same tick: %d"
+            % (falls(fi), falls(fw), int(((fli & capi.FLAG_IMPULSE_PULL) != 0).sum()), B, int(((fli & capi.FLAG_IMPULSE_SLIP) != 0).sum()),
+               int((np.where(fi < 0, args.ticks, fi) > np.where(fw < 0, args.ticks, fw)).sum()), int((np.where(fi < 0, args.ticks, fi) < np.where(fw < 0, args.ticks, fw)).sum()),
+               int((fi == fw).sum())))
 write_lines(args.out, lines)
