@@ -3369,32 +3369,60 @@ __device__ __forceinline__ double plant_jt_dw(const double *L, int lane)
     }
     return r;
 }
+// What the rigid-contact plant (below, behind the compliant plant's calls) adds to the solve.  A plant kernel runs no QP, so Y and [A | g] lie in
+// the QP's scratch: behind the plant's own PL_* block, in front of Q_TRASH (plant_minv's dump), over tree-phase arrays that are dead once the
+// Jacobian stands (A_FG, A_F0, A_XF).  Only plant_minv<.., 12> and rigid_solve write them.
+enum { RG_Y = S0 + 768,     // 30 x 12 : M^-1 J' (columns of rows that are not held are formed and not read)
+       RG_BX = S0 + 1128,   // 12 x 6  : H_leg^-1 J_leg' of each foot's own leg (every other entry of H^-1 J_joint' is zero)
+       RG_SX = S0 + 1200,   // 6 x 12  : the base Schur complement's extra right-hand sides J_base' - F2 H^-1 J_joint'
+       RG_A = S0 + 1272,    // 12 x 13 : [A | g]
+       RG_LAM = S0 + 1428,  // 12 : lambda
+       RG_END = S0 + 1440 };
+static_assert(RG_Y >= PL_ZERO + 32 && RG_Y >= A_JL + 144, "behind the plant's PL_* block and the sole-axes Jacobian");
+static_assert(RG_BX == RG_Y + 30 * 12 && RG_SX == RG_BX + 12 * 6 && RG_A == RG_SX + 6 * 12 && RG_LAM == RG_A + 12 * 13 && RG_END == RG_LAM + 12, "Y | BX | SX | [A | g] | lambda");
+static_assert(RG_END <= Q_TRASH && Q_TRASH + 64 <= LDS_DOUBLES, "in front of the dump of the lanes outside a tile");
+static_assert(RG_Y >= P_END && P_HL < S0 && P_MTOP < S0 && P_JC < S0 && P_C < S0 && P_VFOOT < S0 && P_JPQP < S0, "the terms the solve reads lie below the scratch");
 // (2) M^-1 PL_R by the structure above; lane < 30 hands entry `lane` to sink(da).  CHECK: returns LMH_FLAG_NOT_SPD (wave-uniform) when a
-// pivot of a limb block, the head's block or the Schur complement was not positive -- nobody pays for the test otherwise
-template <bool CHECK, class SINK>
+// pivot of a limb block, the head's block or the Schur complement was not positive -- nobody pays for the test otherwise.
+// NX = 12 (the rigid plant): M^-1 [PL_R | J'], the twelve columns of J' riding along, Y = M^-1 J' -> RG_Y.  J has base and leg columns only,
+// so of H^-1 J_joint' only each foot's own leg block is not zero: DPP rows 0, 1 (RL, LL) carry six extra right-hand sides, the arm rows and
+// the head see zeros and form nothing.  Every right-hand side of a register elimination is updated from its own entries only, and the first
+// one stands in one text for both forms: PL_R's column goes through the same operations in the same order with NX = 0 and with NX = 12.
+// NX = 0 touches no RG_* word.
+template <bool CHECK, int NX = 0, class SINK>
 __device__ __forceinline__ int plant_minv(double *L, int lane, SINK sink)
 {
+    static_assert(NX == 0 || NX == 12, "no extra right-hand side | J'");
     int notspd = 0;
     {   // limb blocks: DPP row dr = limb (RL, LL, RA, LA), lane l16 < 6 = joint of the limb (arms: a unit row pads 5 -> 6)
         const int l16 = lane & 15;                                 // (DPP row dr = lane >> 4)
         const bool legrow = LANE_IS(lane < 32);
         const int js = LANE_IS(lane < 16) ? 0 : legrow ? 6 : LANE_IS(lane < 48) ? 12 : 17;
         const bool real = LANE_IS((lane & 15) < ((lane < 32) ? 6 : 5));      // l16 < nl, nl = 6 joints of a leg | 5 of an arm
+        [[maybe_unused]] const bool legj = LANE_IS(lane < 32 && (lane & 15) < 6);
         const int ja = js + (real ? l16 : 0);
-        double a[6], b[7];
+        double a[6], b[7 + NX / 2];
 #pragma unroll
         for (int c = 0; c < 6; c++) { const double hv = L[P_HL + 6 * ja + ((c < 5) ? c : (legrow ? 5 : 0))]; a[c] = (real && (c < 5 || legrow)) ? hv : ((l16 == c && l16 < 6) ? 1.0 : 0.0); }
         { const double rv = L[PL_R + 6 + ja]; b[0] = real ? rv : 0.0; }
 #pragma unroll
         for (int m = 0; m < 6; m++) { const double fv = L[P_MTOP + 30 * m + 6 + ja]; b[1 + m] = real ? fv : 0.0; }
+        if constexpr (NX != 0) {
+#pragma unroll
+            for (int m = 0; m < 6; m++) { const double jv = L[P_JC + 72 * ((lane >> 4) & 1) + 12 * m + 6 + (real ? l16 : 0)]; b[7 + m] = legj ? jv : 0.0; }   // J[foot dr][row m][leg joint l16]
+        }
         int bad = 0;
         double myinv = 0.0;
         gj16_step<0>(a, b, 0x3Fu, l16, true, 0.0, bad, myinv);     // (l16 = lane & 15 of the caller's LANE, as gj16_step's pivot masks assume)
 #pragma unroll
         for (int c = 0; c < 7; c++) L[real ? PL_B + 7 * ja + c : Q_TRASH + lane] = b[c] * myinv;
+        if constexpr (NX != 0) {
+#pragma unroll
+            for (int m = 0; m < 6; m++) L[legj ? RG_BX + 6 * ja + m : Q_TRASH + lane] = b[7 + m] * myinv;
+        }
         if constexpr (CHECK) notspd |= bad;
     }
-    if (LANE_IS(lane < 14)) {                                      // head: 2 x 2 in closed form
+    if (LANE_IS(lane < 14)) {                                      // head: 2 x 2 in closed form (its rows of J' are zero)
         const int i = lane / 7, c = lane % 7;
         const double h00 = L[P_HL + 6 * 22], h01 = L[P_HL + 6 * 22 + 1], h10 = L[P_HL + 6 * 23], h11 = L[P_HL + 6 * 23 + 1];
         const bool c0 = LANE_IS(lane % 7 == 0);
@@ -3416,16 +3444,36 @@ __device__ __forceinline__ int plant_minv(double *L, int lane, SINK sink)
             L[ok ? PL_SB + 7 * m + tr : Q_TRASH + lane] = base - fb[g];
         }
     }
+    if constexpr (NX != 0) {                                       // the twelve extra right-hand sides of the base system: J_base'[m][k] - F2[m][leg of foot k / 6] BX[.][k % 6]
+#pragma unroll
+        for (int it = 0; it < 2; it++) {
+            const int e = lane + 64 * it, ee = (e < 72) ? e : 0, m = ee / 12, k = ee % 12, ft = k / 6, rr = k % 6;
+            const double *F2 = L + P_MTOP + 30 * m + 6 + 6 * ft, *BX = L + RG_BX + 36 * ft + rr;
+            double s = L[P_JC + 72 * ft + 12 * rr + m];
+#pragma unroll
+            for (int j = 0; j < 6; j++) s -= F2[j] * BX[6 * j];
+            if (e < 72) L[RG_SX + ee] = s;
+        }
+    }
     WSYNC();
-    {
-        double a[6], b[1];
-        const int l16 = lane & 15, lr = LANE_IS((lane & 15) < 6) ? l16 : 0;       // (a copy of the system per DPP row)
+    {   // a copy of the system per DPP row; NX: DPP row dr solves three of the twelve extra right-hand sides beside the first
+        double a[6], b[1 + NX / 4];
+        const int l16 = lane & 15, lr = LANE_IS((lane & 15) < 6) ? l16 : 0;
+        [[maybe_unused]] const int dr = lane >> 4;
 #pragma unroll
         for (int c = 0; c < 6; c++) a[c] = L[PL_SB + 7 * lr + 1 + c];
         b[0] = L[PL_SB + 7 * lr];
-        const int bad6 = gj_solve_regs<6, 1>(a, b, 0x3Fu);
+        if constexpr (NX != 0) {
+#pragma unroll
+            for (int j = 0; j < 3; j++) b[1 + j] = L[RG_SX + 12 * lr + 3 * dr + j];
+        }
+        const int bad6 = gj_solve_regs<6, 1 + NX / 4>(a, b, 0x3Fu);
         if constexpr (CHECK) notspd |= bad6; else (void)bad6;
         if (LANE_IS(lane < 6)) L[PL_DAB + lane] = b[0];
+        if constexpr (NX != 0) {
+#pragma unroll
+            for (int j = 0; j < 3; j++) L[LANE_IS((lane & 15) < 6) ? RG_Y + 12 * l16 + 3 * dr + j : Q_TRASH + lane] = b[1 + j];   // rows 0..5 of Y
+        }
     }
     WSYNC();
     if (LANE_IS(lane < 30)) {
@@ -3438,6 +3486,19 @@ __device__ __forceinline__ int plant_minv(double *L, int lane, SINK sink)
             for (int n = 0; n < 6; n++) da -= B[1 + n] * L[PL_DAB + n];
         }
         sink(da);
+    }
+    if constexpr (NX != 0) {                                       // rows 6..29 of Y: H^-1 J_joint' - B_M Y_base
+#pragma unroll 1
+        for (int e = lane; e < 288; e += 64) {
+            const int i = e / 12, k = e % 12;
+            const bool own = (i < 12) && (i / 6 == k / 6);
+            const double bx = L[own ? RG_BX + 6 * i + k % 6 : (int)PL_ZERO];
+            const double *B = L + PL_B + 7 * i;
+            double y = own ? bx : 0.0;
+#pragma unroll
+            for (int n = 0; n < 6; n++) y -= B[1 + n] * L[RG_Y + 12 * n + k];
+            L[RG_Y + 12 * (6 + i) + k] = y;
+        }
     }
     WSYNC();
     if constexpr (CHECK) return (__ballot(notspd != 0) != 0ull) ? LMH_FLAG_NOT_SPD : 0;
@@ -4897,155 +4958,51 @@ __device__ __forceinline__ void plant_store_contact(const double *L, double *o, 
 // lmh_plant_derivative_rigid / lmh_plant_step_rigid (include/lmh.h): the held soles are kinematic constraints and the contact wrench is their
 // multiplier.  One wave per robot, the single-wave schedule and statements of lmh_plant_kernel; one derivative is
 //     kinematics -> X images -> Newton-Euler at v -> CRBA -> Jacobian -> sole twists (P_VFOOT) -> Jdot qdot of the soles (P_JPQP) ->
-//     r = tau30 - C -> [a0 | Y] = M^-1 [r | J'] (plant_minv_rigid) -> [A | g] = J [Y | a0] + (Jpqp + kv J vhat) -> lambda_S = -A_SS^-1 g_S
+//     r = tau30 - C -> [a0 | Y] = M^-1 [r | J'] (plant_minv<true, 12>) -> [A | g] = J [Y | a0] + (Jpqp + kv J vhat) -> lambda_S = -A_SS^-1 g_S
 //     (gj_solve_regs<12, 1> under the mode's live mask) -> a = a0 + Y lambda -> world frame (phase_outputs_qdd)
-// and reads no ground table, servo table, reference plan, MPC row, QP or clock.  A plant kernel runs no QP, so Y and [A | g] lie in the QP's
-// scratch: behind the plant's own PL_* block, in front of Q_TRASH (plant_minv's dump), over tree-phase arrays that are dead once the Jacobian
-// stands (A_FG, A_F0, A_XF).
-enum { RG_Y = S0 + 768,     // 30 x 12 : M^-1 J' (columns of rows that are not held are formed and not read)
-       RG_BX = S0 + 1128,   // 12 x 6  : H_leg^-1 J_leg' of each foot's own leg (every other entry of H^-1 J_joint' is zero)
-       RG_SX = S0 + 1200,   // 6 x 12  : the base Schur complement's extra right-hand sides J_base' - F2 H^-1 J_joint'
-       RG_A = S0 + 1272,    // 12 x 13 : [A | g]
-       RG_LAM = S0 + 1428,  // 12 : lambda
-       RG_END = S0 + 1440 };
-static_assert(RG_Y >= PL_ZERO + 32 && RG_Y >= A_JL + 144, "behind the plant's PL_* block and the sole-axes Jacobian");
-static_assert(RG_BX == RG_Y + 30 * 12 && RG_SX == RG_BX + 12 * 6 && RG_A == RG_SX + 6 * 12 && RG_LAM == RG_A + 12 * 13 && RG_END == RG_LAM + 12, "Y | BX | SX | [A | g] | lambda");
-static_assert(RG_END <= Q_TRASH && Q_TRASH + 64 <= LDS_DOUBLES, "in front of the dump of the lanes outside a tile");
-static_assert(RG_Y >= P_END && P_HL < S0 && P_MTOP < S0 && P_JC < S0 && P_C < S0 && P_VFOOT < S0 && P_JPQP < S0, "the terms the solve reads lie below the scratch");
-
-// plant_minv's sibling: M^-1 [PL_R | J'] by the same structure, the twelve columns of J' riding along.  J has base and leg columns only, so
-// of H^-1 J_joint' only each foot's own leg block is not zero: DPP rows 0, 1 (RL, LL) carry six extra right-hand sides, the arm rows and
-// the head see zeros and form nothing.  The first right-hand side goes through plant_minv's operations in plant_minv's order (every
-// right-hand side of a register elimination is updated from its own entries only), so PL_R's column keeps plant_minv's bits.
-// lane < 30 hands entry `lane` of M^-1 PL_R to sink(da); Y = M^-1 J' -> RG_Y.  Returns LMH_FLAG_NOT_SPD as plant_minv<true> does.
-template <class SINK>
-__device__ __forceinline__ int plant_minv_rigid(double *L, int lane, SINK sink)
-{
-    int notspd = 0;
-    {   // limb blocks: DPP row dr = limb (RL, LL, RA, LA), lane l16 < 6 = joint of the limb (arms: a unit row pads 5 -> 6)
-        const int l16 = lane & 15;                                 // (DPP row dr = lane >> 4)
-        const bool legrow = LANE_IS(lane < 32);
-        const int js = LANE_IS(lane < 16) ? 0 : legrow ? 6 : LANE_IS(lane < 48) ? 12 : 17;
-        const bool real = LANE_IS((lane & 15) < ((lane < 32) ? 6 : 5));      // l16 < nl, nl = 6 joints of a leg | 5 of an arm
-        const bool legj = LANE_IS(lane < 32 && (lane & 15) < 6);
-        const int ja = js + (real ? l16 : 0);
-        double a[6], b[13];
-#pragma unroll
-        for (int c = 0; c < 6; c++) { const double hv = L[P_HL + 6 * ja + ((c < 5) ? c : (legrow ? 5 : 0))]; a[c] = (real && (c < 5 || legrow)) ? hv : ((l16 == c && l16 < 6) ? 1.0 : 0.0); }
-        { const double rv = L[PL_R + 6 + ja]; b[0] = real ? rv : 0.0; }
-#pragma unroll
-        for (int m = 0; m < 6; m++) { const double fv = L[P_MTOP + 30 * m + 6 + ja]; b[1 + m] = real ? fv : 0.0; }
-#pragma unroll
-        for (int m = 0; m < 6; m++) { const double jv = L[P_JC + 72 * ((lane >> 4) & 1) + 12 * m + 6 + (real ? l16 : 0)]; b[7 + m] = legj ? jv : 0.0; }   // J[foot dr][row m][leg joint l16]
-        int bad = 0;
-        double myinv = 0.0;
-        gj16_step<0>(a, b, 0x3Fu, l16, true, 0.0, bad, myinv);     // (l16 = lane & 15 of the caller's LANE, as gj16_step's pivot masks assume)
-#pragma unroll
-        for (int c = 0; c < 7; c++) L[real ? PL_B + 7 * ja + c : Q_TRASH + lane] = b[c] * myinv;
-#pragma unroll
-        for (int m = 0; m < 6; m++) L[legj ? RG_BX + 6 * ja + m : Q_TRASH + lane] = b[7 + m] * myinv;
-        notspd |= bad;
-    }
-    if (LANE_IS(lane < 14)) {                                      // head: 2 x 2 in closed form (its rows of J' are zero)
-        const int i = lane / 7, c = lane % 7;
-        const double h00 = L[P_HL + 6 * 22], h01 = L[P_HL + 6 * 22 + 1], h10 = L[P_HL + 6 * 23], h11 = L[P_HL + 6 * 23 + 1];
-        const bool c0 = LANE_IS(lane % 7 == 0);
-        const double r0 = c0 ? L[PL_R + 6 + 22] : L[P_MTOP + 30 * (c - 1) + 6 + 22], r1 = c0 ? L[PL_R + 6 + 23] : L[P_MTOP + 30 * (c - 1) + 6 + 23];
-        const double det = h00 * h11 - h01 * h10;
-        L[PL_B + 7 * (22 + i) + c] = LANE_IS(lane < 7) ? (h11 * r0 - h01 * r1) / det : (h00 * r1 - h10 * r0) / det;
-        notspd |= (int)!(h00 > 0.0 && det > 0.0);
-    }
-    WSYNC();
-    {   // base: S_b = Ic0 - F2 B_M, rhs = r_b - F2 B_r   (one matrix-core tile, K = 24)
-        const int tr = lane & 15, tq = lane >> 4;
-        const double *zero = L + PL_ZERO;
-        const v4d fb = mfma_ptr<6, 4, 28>(LANE_IS((lane & 15) < 6) ? L + P_MTOP + 30 * tr + 6 + tq : zero, LANE_IS((lane & 15) < 7) ? L + PL_B + 7 * tq + tr : zero);
-#pragma unroll
-        for (int g = 0; g < 2; g++) {
-            const int m = tq + 4 * g;
-            const bool ok = (m < 6) && (tr < 7);
-            const double base = L[!ok ? PL_ZERO : (tr == 0) ? PL_R + m : P_MTOP + 30 * m + (tr - 1)];
-            L[ok ? PL_SB + 7 * m + tr : Q_TRASH + lane] = base - fb[g];
-        }
-    }
-    // the twelve extra right-hand sides of the base system: J_base'[m][k] - F2[m][leg of foot k / 6] BX[.][k % 6]
-#pragma unroll
-    for (int it = 0; it < 2; it++) {
-        const int e = lane + 64 * it, ee = (e < 72) ? e : 0, m = ee / 12, k = ee % 12, ft = k / 6, rr = k % 6;
-        const double *F2 = L + P_MTOP + 30 * m + 6 + 6 * ft, *BX = L + RG_BX + 36 * ft + rr;
-        double s = L[P_JC + 72 * ft + 12 * rr + m];
-#pragma unroll
-        for (int j = 0; j < 6; j++) s -= F2[j] * BX[6 * j];
-        if (e < 72) L[RG_SX + ee] = s;
-    }
-    WSYNC();
-    {   // DPP row dr solves the first right-hand side (a copy per row, as plant_minv) and three of the twelve extra ones
-        double a[6], b[4];
-        const int l16 = lane & 15, lr = LANE_IS((lane & 15) < 6) ? l16 : 0, dr = lane >> 4;
-#pragma unroll
-        for (int c = 0; c < 6; c++) a[c] = L[PL_SB + 7 * lr + 1 + c];
-        b[0] = L[PL_SB + 7 * lr];
-#pragma unroll
-        for (int j = 0; j < 3; j++) b[1 + j] = L[RG_SX + 12 * lr + 3 * dr + j];
-        const int bad6 = gj_solve_regs<6, 4>(a, b, 0x3Fu);
-        notspd |= bad6;
-        if (LANE_IS(lane < 6)) L[PL_DAB + lane] = b[0];
-#pragma unroll
-        for (int j = 0; j < 3; j++) L[LANE_IS((lane & 15) < 6) ? RG_Y + 12 * l16 + 3 * dr + j : Q_TRASH + lane] = b[1 + j];       // rows 0..5 of Y
-    }
-    WSYNC();
-    if (LANE_IS(lane < 30)) {
-        double da;
-        if (LANE_IS(lane < 6)) da = L[PL_DAB + lane];
-        else {
-            const double *B = L + PL_B + 7 * (lane - 6);
-            da = B[0];
-#pragma unroll
-            for (int n = 0; n < 6; n++) da -= B[1 + n] * L[PL_DAB + n];
-        }
-        sink(da);
-    }
-    // rows 6..29 of Y: H^-1 J_joint' - B_M Y_base
-#pragma unroll 1
-    for (int e = lane; e < 288; e += 64) {
-        const int i = e / 12, k = e % 12;
-        const bool own = (i < 12) && (i / 6 == k / 6);
-        const double bx = L[own ? RG_BX + 6 * i + k % 6 : (int)PL_ZERO];
-        const double *B = L + PL_B + 7 * i;
-        double y = own ? bx : 0.0;
-#pragma unroll
-        for (int n = 0; n < 6; n++) y -= B[1 + n] * L[RG_Y + 12 * n + k];
-        L[RG_Y + 12 * (6 + i) + k] = y;
-    }
-    WSYNC();
-    return (__ballot(notspd != 0) != 0ull) ? LMH_FLAG_NOT_SPD : 0;
-}
+// and reads no ground table, servo table, reference plan, MPC row, QP or clock.  The plastic impact (lmh_plant_impact_rigid) is the same
+// constrained solve with another right-hand side, so both are rigid_solve<KIND>: one body, `if constexpr` where they differ.  Y, [A | g] and
+// lambda lie in the RG_* words in front of plant_minv.
 // the held rows of the feet Jacobian as a mask (rows n_R f_R n_L f_L): only the low two bits of a mode word are read
 __device__ __forceinline__ unsigned rigid_live(int mode)
 {
     const int m = mode & 3;
     return (m == LMH_PHASE_DOUBLE) ? 0xFFFu : (m == LMH_PHASE_RIGHT) ? 0x03Fu : (m == LMH_PHASE_LEFT) ? 0xFC0u : 0u;
 }
-// one derivative of the rigid plant for the state in L[P_Q], L[P_V]: accelerations -> L[P_QDD] (state ordering, world frame), the multiplier
-// -> L[RG_LAM] (zeros on the rows that are not held).  `live`: rigid_live of the robot's mode, wave-uniform.  Returns LMH_FLAG_NOT_SPD |
-// LMH_FLAG_CONTACT_PULL | LMH_FLAG_CONTACT_SLIP, wave-uniform.
-__device__ __forceinline__ int plant_derivative_rigid(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau, unsigned live, double kv)
+// The constrained solve of the rigid plant for the state in L[P_Q], L[P_V], `live` = rigid_live of the robot's mode (wave-uniform): kinematics,
+// M, J, Y = M^-1 J', A = J Y, lambda_S = -A_SS^-1 g_S by the register solve under `live`, Y lambda; the result (state ordering, world frame)
+// -> L[P_QDD], lambda -> L[RG_LAM] (zeros on the rows that are not held).  KIND says what g is and what lambda is added to:
+//   RIGID_DERIVATIVE  g = (J a0 + Jpqp) + kv J vhat with a0 = M^-1 (tau - C); the accelerations a0 + Y lambda (FLIGHT: a0 itself).
+//                     Returns LMH_FLAG_NOT_SPD | LMH_FLAG_CONTACT_PULL | LMH_FLAG_CONTACT_SLIP, wave-uniform.
+//   RIGID_IMPACT      the plastic impact (lmh_plant_impact_rigid, include/lmh.h): the velocity jumps to the nearest one, in the metric of M,
+//                     that the mode's constraints admit.  g = J vhat, the sole twist (P_VFOOT): no torque, no C, no Jdot qdot, no kv (tau and
+//                     kv are not read), so neither phase_newton_euler nor refs_jpqp runs (nothing behind them reads what they write: the
+//                     CRBA runs beside the Newton-Euler pass on the two-wave schedule), plant_minv's first right-hand side is an exact zero
+//                     and its sink is empty.  dv = Y lambda (FLIGHT: an exact zero), lambda the impulse.  L[P_V] is left alone: the caller
+//                     forms v + dv, and with FLIGHT takes v as it is.  Returns LMH_FLAG_NOT_SPD | LMH_FLAG_NONFINITE (of v + dv) |
+//                     LMH_FLAG_IMPULSE_PULL | LMH_FLAG_IMPULSE_SLIP, wave-uniform.
+enum RigidKind { RIGID_DERIVATIVE, RIGID_IMPACT };
+template <RigidKind KIND>
+__device__ __forceinline__ int rigid_solve(double *L, LmhCParams &P, const IbPack &ibp, int lane, double tau, unsigned live, double kv)
 {
+    constexpr bool IMPACT = KIND == RIGID_IMPACT;
     if (lane < 30) L[P_VP + lane] = L[P_V + lane];                 // one velocity for every term
     WSYNC();
     phase_fk<double>(L, P.lcoef);
     phase_com_x<1, double>(L, 0);
-    phase_newton_euler<double>(L);
+    if constexpr (!IMPACT) phase_newton_euler<double>(L);
     phase_crba<double>(L, ib_unpack(ibp));
     phase_jacobian<double>(L);
     refs_vfoot_pdjoints(L, P);                                     // sole twists J vhat -> P_VFOOT (its PD law on lanes 32..61 rides along unread)
-    WSYNC();
-    refs_jpqp(L);                                                  // Jdot qdot of the soles -> P_JPQP
-    if (lane < 30) L[PL_R + lane] = tau - L[P_C + lane];
+    if constexpr (!IMPACT) {
+        WSYNC();
+        refs_jpqp(L);                                              // Jdot qdot of the soles -> P_JPQP
+    }
+    if (lane < 30) { if constexpr (IMPACT) L[PL_R + lane] = 0.0; else L[PL_R + lane] = tau - L[P_C + lane]; }
     else if (lane >= 32) L[PL_ZERO + lane - 32] = 0.0;
     WSYNC();
-    int flags = plant_minv_rigid(L, lane, [&](double a) { L[PL_AP + lane] = a; });
-    // A = J Y (12 x 12; base and own-leg columns) and g = J a0 + Jpqp + kv J vhat
+    int flags = plant_minv<true, 12>(L, lane, [&]([[maybe_unused]] double a) { if constexpr (!IMPACT) L[PL_AP + lane] = a; });
+    // A = J Y (12 x 12; base and own-leg columns); column 12 of [A | g]
 #pragma unroll
     for (int it = 0; it < 3; it++) {
         const int e = lane + 64 * it, ee = (e < 144) ? e : 0, r = ee / 12, c = ee % 12, ft = r / 6;
@@ -5057,7 +5014,8 @@ __device__ __forceinline__ int plant_derivative_rigid(double *L, LmhCParams &P, 
         for (int j = 0; j < 6; j++) s += Jr[6 + j] * Yl[12 * j];
         if (e < 144) L[RG_A + 13 * r + c] = s;
     }
-    if (lane >= 52) {
+    if constexpr (IMPACT) { if (lane >= 52) L[RG_A + 13 * (lane - 52) + 12] = L[P_VFOOT + lane - 52]; }
+    else if (lane >= 52) {
         const int r = lane - 52, ft = r / 6;
         const double *Jr = L + P_JC + 72 * ft + 12 * (r % 6), *ab = L + PL_AP, *al = L + PL_AP + 6 + 6 * ft;
         double s = 0.0;
@@ -5082,102 +5040,42 @@ __device__ __forceinline__ int plant_derivative_rigid(double *L, LmhCParams &P, 
         double s = 0.0;
 #pragma unroll
         for (int k = 0; k < 12; k++) s += L[RG_Y + 12 * lane + k] * L[RG_LAM + k];
-        const double a0 = L[PL_AP + lane];
-        L[PL_AP + lane] = (live != 0u) ? a0 + s : a0;              // (FLIGHT: a0 itself, whatever Y holds)
+        if constexpr (IMPACT) L[PL_AP + lane] = (live != 0u) ? s : 0.0;        // (FLIGHT: an exact zero, whatever Y holds)
+        else {
+            const double a0 = L[PL_AP + lane];
+            L[PL_AP + lane] = (live != 0u) ? a0 + s : a0;          // (FLIGHT: a0 itself, whatever Y holds)
+        }
     }
-    {   // what the ground would have to supply, reported and not enforced: a held foot pulls | leaves its friction disc
+    {   // what the ground would have (had) to supply, reported and not enforced: a held foot (its impulse) pulls | leaves its friction disc
+        constexpr int PULL = IMPACT ? LMH_FLAG_IMPULSE_PULL : LMH_FLAG_CONTACT_PULL, SLIP = IMPACT ? LMH_FLAG_IMPULSE_SLIP : LMH_FLAG_CONTACT_SLIP;
         const double mu = P.contact_mu;
 #pragma unroll
         for (int ft = 0; ft < 2; ft++) {
             const double fx = L[RG_LAM + 6 * ft + 3], fy = L[RG_LAM + 6 * ft + 4], fz = L[RG_LAM + 6 * ft + 5];
             const bool held = ((live >> (6 * ft)) & 1u) != 0u;
-            if (held && fz < 0.0) flags |= LMH_FLAG_CONTACT_PULL;
-            if (held && sqrt(fx * fx + fy * fy) > mu * fz) flags |= LMH_FLAG_CONTACT_SLIP;
+            if (held && fz < 0.0) flags |= PULL;
+            if (held && sqrt(fx * fx + fy * fy) > mu * fz) flags |= SLIP;
         }
         flags = __builtin_amdgcn_readfirstlane(flags);             // (every lane read the same words)
     }
     WSYNC();
     phase_outputs_qdd(L, PL_AP);
-    return flags;
-}
-// the plastic impact of the rigid plant (lmh_plant_impact_rigid, include/lmh.h) for the state in L[P_Q], L[P_V]: the velocity jumps to the
-// nearest one, in the metric of M, that the mode's constraints admit.  The derivative's sibling -- the same kinematics, M, J, Y = M^-1 J'
-// (plant_minv_rigid, whose first right-hand side is an exact zero here and whose sink is dropped), A = J Y and register solve under `live` --
-// with the sole twist J vhat (P_VFOOT) as the right-hand side: no torque, no C, no Jdot qdot, no kv, so neither phase_newton_euler nor
-// refs_jpqp runs (nothing behind them reads what they write: the CRBA runs beside the Newton-Euler pass on the two-wave schedule).
-// dv (state ordering, world frame) -> L[P_QDD], the impulse -> L[RG_LAM] (zeros on the rows that are not held); FLIGHT: dvhat is an exact
-// zero whatever Y holds.  L[P_V] is left alone: the caller forms v + dv, and with FLIGHT takes v as it is.  Returns LMH_FLAG_NOT_SPD | LMH_FLAG_NONFINITE (of v + dv) |
-// LMH_FLAG_IMPULSE_PULL | LMH_FLAG_IMPULSE_SLIP, wave-uniform.
-__device__ __forceinline__ int plant_impact_rigid(double *L, LmhCParams &P, const IbPack &ibp, int lane, unsigned live)
-{
-    if (lane < 30) L[P_VP + lane] = L[P_V + lane];                 // one velocity for every term
-    WSYNC();
-    phase_fk<double>(L, P.lcoef);
-    phase_com_x<1, double>(L, 0);
-    phase_crba<double>(L, ib_unpack(ibp));
-    phase_jacobian<double>(L);
-    refs_vfoot_pdjoints(L, P);                                     // sole twists J vhat -> P_VFOOT (its PD law on lanes 32..61 rides along unread)
-    if (lane < 30) L[PL_R + lane] = 0.0;
-    else if (lane >= 32) L[PL_ZERO + lane - 32] = 0.0;
-    WSYNC();
-    int flags = plant_minv_rigid(L, lane, [&](double) {});
-    // [A | w]: A = J Y as the derivative forms it, column 12 the sole twist
-#pragma unroll
-    for (int it = 0; it < 3; it++) {
-        const int e = lane + 64 * it, ee = (e < 144) ? e : 0, r = ee / 12, c = ee % 12, ft = r / 6;
-        const double *Jr = L + P_JC + 72 * ft + 12 * (r % 6), *Yb = L + RG_Y + c, *Yl = L + RG_Y + 12 * (6 + 6 * ft) + c;
-        double s = 0.0;
-#pragma unroll
-        for (int m = 0; m < 6; m++) s += Jr[m] * Yb[12 * m];
-#pragma unroll
-        for (int j = 0; j < 6; j++) s += Jr[6 + j] * Yl[12 * j];
-        if (e < 144) L[RG_A + 13 * r + c] = s;
+    if constexpr (IMPACT) {
+        const int l30 = (lane < 30) ? lane : 0;
+        const double v0 = L[P_V + l30], v1 = (live != 0u) ? v0 + L[P_QDD + l30] : v0;   // (FLIGHT: v itself, the sign of a zero included; the callers add the same way)
+        if (__ballot(!(fabs(v1) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
     }
-    if (lane >= 52) L[RG_A + 13 * (lane - 52) + 12] = L[P_VFOOT + lane - 52];
-    WSYNC();
-    {
-        double a[12], b[1];
-        const int l16 = lane & 15, lr = (l16 < 12) ? l16 : 0;      // (a copy of the system per DPP row)
-#pragma unroll
-        for (int c = 0; c < 12; c++) a[c] = L[RG_A + 13 * lr + c];
-        b[0] = -L[RG_A + 13 * lr + 12];
-        if (live != 0u) { if (gj_solve_regs<12, 1>(a, b, live)) flags |= LMH_FLAG_NOT_SPD; }      // (wave-uniform: FLIGHT solves nothing)
-        if (lane < 12) L[RG_LAM + lane] = ((live >> lane) & 1u) ? b[0] : 0.0;
-    }
-    WSYNC();
-    if (lane < 30) {
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < 12; k++) s += L[RG_Y + 12 * lane + k] * L[RG_LAM + k];
-        L[PL_AP + lane] = (live != 0u) ? s : 0.0;                  // (FLIGHT: an exact zero, whatever Y holds)
-    }
-    {   // what the ground would have had to supply, reported and not enforced: a held foot's impulse pulls | leaves its friction disc
-        const double mu = P.contact_mu;
-#pragma unroll
-        for (int ft = 0; ft < 2; ft++) {
-            const double fx = L[RG_LAM + 6 * ft + 3], fy = L[RG_LAM + 6 * ft + 4], fz = L[RG_LAM + 6 * ft + 5];
-            const bool held = ((live >> (6 * ft)) & 1u) != 0u;
-            if (held && fz < 0.0) flags |= LMH_FLAG_IMPULSE_PULL;
-            if (held && sqrt(fx * fx + fy * fy) > mu * fz) flags |= LMH_FLAG_IMPULSE_SLIP;
-        }
-        flags = __builtin_amdgcn_readfirstlane(flags);             // (every lane read the same words)
-    }
-    WSYNC();
-    phase_outputs_qdd(L, PL_AP);
-    const int l30 = (lane < 30) ? lane : 0;
-    const double v0 = L[P_V + l30], v1 = (live != 0u) ? v0 + L[P_QDD + l30] : v0;       // (FLIGHT: v itself, the sign of a zero included; the callers add the same way)
-    if (__ballot(!(fabs(v1) <= 1.0e300)) != 0ull) flags |= LMH_FLAG_NONFINITE;
     return flags;
 }
 // ============================================================================ the hold and the plant kernel: every call of either plant
-// what the RIGID hold takes in place of a ground and a servo: live and kv as in plant_derivative_rigid; lam: lane i < 12 leaves with entry i of
+// what the RIGID hold takes in place of a ground and a servo: live and kv as in rigid_solve; lam: lane i < 12 leaves with entry i of
 // the multiplier of the first stage of the last substep
 struct RigidHold { unsigned live; double kv, lam; };
 // n_substeps x rk4Step (rk4.hpp:5-18) with the torques held: `x` (lane i < 60 = component i of q | v, as in the rollout's rk4_stage) comes in
 // and goes out in a register, L[P_Q], L[P_V] carry each stage's state (and are left at the last stage's, not at x: a caller that wants x in
 // LDS writes it), `flags` collects the derivative's and LMH_FLAG_NONFINITE of x behind every substep.  Wave-scope fences only; no clock:
 // the callers advance theirs by n_substeps additions of dt (plant_store_state; wave 0 of the zero-order-hold kernels).
-// The derivative is plant_derivative<GROUND, SERVO> (gnd is read with GROUND only, servo with SERVO only) or, with RIGID, plant_derivative_rigid.
+// The derivative is plant_derivative<GROUND, SERVO> (gnd is read with GROUND only, servo with SERVO only) or, with RIGID, rigid_solve<RIGID_DERIVATIVE>.
 // LOOP changes no statement: the zero-order-hold kernels take the RIGID hold as an instantiation of their own, so that lmh_plant_kernel's stays
 // the only caller of its copy and that kernel keeps its instruction stream (what the compiler propagates into a function from its one call
 // site, the kernel's own LDS array among it, it no longer propagates once other kernels call the same instantiation).  For the same reason the
@@ -5196,7 +5094,7 @@ __device__ __forceinline__ void plant_hold(double *L, LmhCParams &P, const IbPac
             if (lane < 60) L[P_Q + lane] = xs;                     // q | v are one run
             WSYNC();
             if constexpr (RIGID) {
-                flags |= plant_derivative_rigid(L, P, ibp, lane, tau, rigid->live, rigid->kv);
+                flags |= rigid_solve<RIGID_DERIVATIVE>(L, P, ibp, lane, tau, rigid->live, rigid->kv);
                 if (stage == 0) rigid->lam = L[RG_LAM + ((lane < 12) ? lane : 0)];
             } else flags |= plant_derivative<GROUND, SERVO>(L, P, ibp, lane, tau, gnd, servo);
             rk4_stage<0>(L, stage, lane, dt, P_SC + 52, x, ksum, xs);
@@ -5209,13 +5107,13 @@ __device__ __forceinline__ void plant_hold(double *L, LmhCParams &P, const IbPac
 //   servo    (SERVO: lmh_plant_step_servo) servo + servo_stride * robot is the robot's gain record (NULL: zero gains; stride 0: one shared record),
 //            setpoint + LMH_SETPOINT_STRIDE * robot its setpoint, both loaded once by the lanes that own the joints
 //   hold     (RIGID: lmh_plant_derivative_rigid, lmh_plant_step_rigid) [n_instances] support modes, NULL = both soles held; kv as in
-//            plant_derivative_rigid; lambda (may be NULL) [n_instances][12]: the multiplier of the derivative call, of the first stage of the
+//            rigid_solve; lambda (may be NULL) [n_instances][12]: the multiplier of the derivative call, of the first stage of the
 //            last substep for the step
 struct PlantArgs { const double *q, *v, *tau30; double *state, *xdot, *contact; int32_t *flags; int n_substeps; const double *ground; size_t ground_stride;
                    const double *servo; size_t servo_stride; const double *setpoint; const int32_t *hold; double kv; double *lambda; };
 // MODE: PM_CONTACT | PM_DERIV | PM_STEP | PM_RIGID_IMPACT.  GROUND, SERVO: the options of the compliant plant (plant_derivative); RIGID: the
-// rigid-contact plant (plant_derivative_rigid) in its place, which reads no ground table and no servo table.  PM_RIGID_IMPACT
-// (lmh_plant_impact_rigid; RIGID only): plant_impact_rigid at (q, v) under hold; xdot takes v_plus [n_instances][30], lambda the impulse.
+// rigid-contact plant (rigid_solve<RIGID_DERIVATIVE>) in its place, which reads no ground table and no servo table.  PM_RIGID_IMPACT
+// (lmh_plant_impact_rigid; RIGID only): rigid_solve<RIGID_IMPACT> at (q, v) under hold; xdot takes v_plus [n_instances][30], lambda the impulse.
 template <int MODE, bool GROUND = false, bool SERVO = false, bool RIGID = false>
 __global__ void __launch_bounds__(64) lmh_plant_kernel(LmhDevParams P_arg, PlantArgs A)
 {
@@ -5253,13 +5151,13 @@ __global__ void __launch_bounds__(64) lmh_plant_kernel(LmhDevParams P_arg, Plant
         if constexpr (MODE == PM_RIGID_IMPACT) {
             load_qv(L, A.q, A.v, inst, lane, false);               // (the impact sets P_VP itself)
             WSYNC();
-            flags |= plant_impact_rigid(L, P, ibp, lane, R.live);
+            flags |= rigid_solve<RIGID_IMPACT>(L, P, ibp, lane, 0.0, R.live, 0.0);
             if (lane < 30) A.xdot[30 * (size_t)inst + lane] = (R.live != 0u) ? L[P_V + lane] + L[P_QDD + lane] : L[P_V + lane];
             if (A.lambda && lane < 12) A.lambda[12 * (size_t)inst + lane] = L[RG_LAM + lane];
         } else if constexpr (MODE == PM_DERIV) {
             load_qv(L, A.q, A.v, inst, lane, false);               // (the derivative sets P_VP itself)
             WSYNC();
-            if constexpr (RIGID) flags |= plant_derivative_rigid(L, P, ibp, lane, tau, R.live, R.kv);
+            if constexpr (RIGID) flags |= rigid_solve<RIGID_DERIVATIVE>(L, P, ibp, lane, tau, R.live, R.kv);
             else flags |= plant_derivative<GROUND>(L, P, ibp, lane, tau, gnd);
             plant_store_xdot(L, A.xdot, inst, lane, flags);
             if constexpr (RIGID) { if (A.lambda && lane < 12) A.lambda[12 * (size_t)inst + lane] = L[RG_LAM + lane]; }
@@ -5451,7 +5349,7 @@ struct ZohImpactArgs { ZohRigidArgs a; LmhZohImpact im; };
 static_assert(sizeof(ZohRigidArgs) % 8 == 0 && alignof(ZohImpactArgs) == 8, "ZohImpactArgs continues ZohRigidArgs in the kernel-argument segment");
 // What the RIGID hold needs survives it below the scratch, as with the compliant plant's PL_* block: the per-launch tables, the reference cache,
 // the K_f^-1 cache and the push cursor.  RG_* lies in S0 + [768, 1440): in front of Q_TRASH and of kinv_compute's scratch (A_XR), which is formed
-// again whenever it is needed.  plant_derivative_rigid writes P_VP, P_VFOOT, P_QREF and P_JPQP below S0 -- words every evaluation forms for itself
+// again whenever it is needed.  rigid_solve writes P_VP, P_VFOOT, P_QREF and P_JPQP below S0 -- words every evaluation forms for itself
 // before it reads them -- and P_W12 nowhere: metrics_wave0 finds the evaluation's wrench there behind the hold.
 static_assert(RG_Y == S0 + 768 && RG_END == S0 + 1440 && RG_END <= Q_TRASH && RG_END <= A_XR, "RG_* inside the QP scratch, in front of the dump and of kinv_compute's scratch");
 static_assert(P_MODEL + LMH_MODEL_STRIDE <= S0 && P_GCOL < S0 && P_GI6 < S0 && P_GPI < S0 && P_MPCK < S0, "the per-launch tables lie below the scratch");
@@ -5476,7 +5374,7 @@ __device__ __forceinline__ RigidHold zoh_rigid_hold(LmhCParams &P, int inst, int
 }
 // ---- lmh_rollout_zoh_rigid_impact (include/lmh.h): the RIGID body with the plastic impact between the tick's mode and its hold (the IMPACT
 // flag).  wave 0, behind zoh_rigid_hold: the feet the tick's mode holds and the hold before it did not (rigid_live of mode_prev[robot]) make
-// a touchdown; then plant_impact_rigid runs on the TRUE state under the tick's whole mode, v <- v + dv on the integrator's register, and the
+// a touchdown; then rigid_solve<RIGID_IMPACT> runs on the TRUE state under the tick's whole mode, v <- v + dv on the integrator's register, and the
 // impulse leaves (zeros on a tick without a touchdown).  Nothing is carried across controller_eval: the previous mode is one word in global
 // memory, read here by lane 0 and written back by lane 0 -- the lane that stored it loads it, ordinary vector accesses, no fence, as the
 // true state parked in d_state is.  The impact writes what the derivative writes and less, so what survives the hold survives it too.
@@ -5495,7 +5393,7 @@ __device__ __forceinline__ void zoh_rigid_impact(double *L, LmhCParams &P, int i
         WSYNC();
         if (lane < 60) L[P_Q + lane] = x;                          // q | v are one run: the true state, not what the evaluation measured
         WSYNC();
-        flags |= plant_impact_rigid(L, P, ib_pack(), lane, live);
+        flags |= rigid_solve<RIGID_IMPACT>(L, P, ib_pack(), lane, 0.0, live, 0.0);
         if (lane >= 30 && lane < 60) x += L[P_QDD + lane - 30];
         imp = L[RG_LAM + ((lane < 12) ? lane : 0)];
     }

@@ -773,6 +773,22 @@ def gauss_jordan_unpivoted(A, b):
     return b / np.diag(A), piv
 
 
+def _rigid_multiplier(rows, M, Js, rhs, flag_pull, flag_slip, contact_mu):
+    """What the two statements below share for the held rows (Js = J[rows]): Y = M^-1 Js', A = Js Y, lam[rows] = -A^-1 rhs by the unpivoted
+    Gauss-Jordan, per held foot flag_pull (f_z < 0) | flag_slip (hypot(f_x, f_y) > contact_mu f_z) -> (Y, A, lam [12], pivots, bits)."""
+    Y = np.linalg.solve(M, Js.T)
+    A = Js @ Y
+    x, piv = gauss_jordan_unpivoted(A, rhs)
+    lam, bits = np.zeros(12), 0
+    lam[rows] = -x
+    for ft in range(2):
+        if 6 * ft in rows:
+            fx, fy, fz = lam[6 * ft + 3:6 * ft + 6]
+            bits |= flag_pull if fz < 0.0 else 0
+            bits |= flag_slip if np.hypot(fx, fy) > contact_mu * fz else 0
+    return Y, A, lam, piv, bits
+
+
 def rigid_contact_acceleration(M, C, J, Jpqp, vhat, tau30, mode, kv, contact_mu=0.7, info=None):
     """The numpy statement of the rigid-contact plant (include/lmh.h, lmh_plant_derivative_rigid) for ONE robot, in the coordinates of M:
     M [30,30], C [30], J [12,30], Jpqp [12] (the soles' Jdot qdot), vhat [30] (v in M's coordinates), tau30 [30] (None: passive), mode (only
@@ -789,19 +805,11 @@ def rigid_contact_acceleration(M, C, J, Jpqp, vhat, tau30, mode, kv, contact_mu=
     lam, a, flags = np.zeros(12), a0, 0
     if rows:
         Js = J[rows]
-        Y = np.linalg.solve(M, Js.T)
-        A = Js @ Y
         g = Js @ a0 + np.asarray(Jpqp, dtype=np.float64)[rows] + kv * (Js @ np.asarray(vhat, dtype=np.float64))
-        x, piv = gauss_jordan_unpivoted(A, g)
-        lam[rows] = -x
+        Y, A, lam, piv, flags = _rigid_multiplier(rows, M, Js, g, FLAG_CONTACT_PULL, FLAG_CONTACT_SLIP, contact_mu)
         a = a0 + Y @ lam[rows]
         if info is not None:
             info.update(A=A, g=g, Y=Y, a0=a0, rows=rows, pivots=piv)
-        for ft in range(2):
-            if 6 * ft in rows:
-                fx, fy, fz = lam[6 * ft + 3:6 * ft + 6]
-                flags |= FLAG_CONTACT_PULL if fz < 0.0 else 0
-                flags |= FLAG_CONTACT_SLIP if np.hypot(fx, fy) > contact_mu * fz else 0
     if not (np.all(np.isfinite(a)) and np.all(np.isfinite(lam))):
         flags |= FLAG_NONFINITE
     return a, lam, flags
@@ -821,20 +829,12 @@ def rigid_contact_impact(M, J, vhat, mode, contact_mu=0.7, info=None):
     if rows:
         Js = J[rows]
         w = Js @ vhat
-        Y = np.linalg.solve(M, Js.T)
-        A = Js @ Y
-        x, piv = gauss_jordan_unpivoted(A, w)
-        lam[rows] = -x
+        Y, A, lam, piv, flags = _rigid_multiplier(rows, M, Js, w, FLAG_IMPULSE_PULL, FLAG_IMPULSE_SLIP, contact_mu)
         dvhat = Y @ lam[rows]
         if info is not None:
             info.update(A=A, w=w, Y=Y, rows=rows, pivots=piv)
         if not np.all(piv > 0.0):
             flags |= FLAG_NOT_SPD
-        for ft in range(2):
-            if 6 * ft in rows:
-                fx, fy, fz = lam[6 * ft + 3:6 * ft + 6]
-                flags |= FLAG_IMPULSE_PULL if fz < 0.0 else 0
-                flags |= FLAG_IMPULSE_SLIP if np.hypot(fx, fy) > contact_mu * fz else 0
     if not (np.all(np.isfinite(dvhat)) and np.all(np.isfinite(lam)) and np.all(np.isfinite(vhat))):
         flags |= FLAG_NONFINITE
     return dvhat, lam, flags

@@ -42,18 +42,8 @@ def oracle_impact(o, q, v, mode, mu=MU):
 
 
 def kkt_reference(M, J, vhat, mode):
-    """[M -J_S'; J_S 0] [dvhat; Lam_S] = [0; -w] solved in double and refined against its long-double residual -> (dvhat, Lam [12], cond)."""
-    rows = list(RIGID_ROWS[int(mode) & 3])
-    K = rc.kkt_matrix(M, J, mode)
-    rhs = np.concatenate([np.zeros(30), -(J[rows] @ vhat)])
-    Kl, rl = K.astype(np.longdouble), rhs.astype(np.longdouble)
-    x = np.linalg.solve(K, rhs).astype(np.longdouble)
-    for _ in range(6):
-        x = x + np.linalg.solve(K, (rl - Kl @ x).astype(np.float64)).astype(np.longdouble)
-    x = x.astype(np.float64)
-    lam = np.zeros(12)
-    lam[rows] = x[30:]
-    return x[:30], lam, float(np.linalg.cond(K))
+    """The refined KKT solve of the impact (rigid_cases.kkt_refined): [dvhat; Lam_S] for [0; -w] -> (dvhat, Lam [12], cond)."""
+    return rc.kkt_refined(M, J, mode, np.zeros(30), -(J[list(RIGID_ROWS[int(mode) & 3])] @ vhat))
 
 
 def bounds(tm, mode, dvhat, lam):

@@ -88,12 +88,12 @@ def kkt_matrix(M, J, mode):
     return K
 
 
-def kkt_reference(M, C, J, Jpqp, vhat, tau30, mode, kv):
-    """[M -J_S'; J_S 0] [a; lam_S] = [tau30 - C; -(Jpqp_S + kv J_S vhat)] solved in double and refined against its long-double residual
-    until the correction stalls -> (a, lam [12], cond of the KKT matrix)."""
+def kkt_refined(M, J, mode, top, bottom):
+    """[M -J_S'; J_S 0] [y; lam_S] = [top; bottom] solved in double and refined against its long-double residual until the correction
+    stalls -> (y, lam [12], cond of the KKT matrix)."""
     rows = list(RIGID_ROWS[int(mode) & 3])
     K = kkt_matrix(M, J, mode)
-    rhs = np.concatenate([tau30 - C, -(Jpqp[rows] + kv * (J[rows] @ vhat))])
+    rhs = np.concatenate([top, bottom])
     Kl, rl = K.astype(np.longdouble), rhs.astype(np.longdouble)
     x = np.linalg.solve(K, rhs).astype(np.longdouble)
     for _ in range(6):
@@ -102,6 +102,12 @@ def kkt_reference(M, C, J, Jpqp, vhat, tau30, mode, kv):
     lam = np.zeros(12)
     lam[rows] = x[30:]
     return x[:30], lam, float(np.linalg.cond(K))
+
+
+def kkt_reference(M, C, J, Jpqp, vhat, tau30, mode, kv):
+    """The refined KKT solve of the derivative: [a; lam_S] for [tau30 - C; -(Jpqp_S + kv J_S vhat)] -> (a, lam [12], cond)."""
+    rows = list(RIGID_ROWS[int(mode) & 3])
+    return kkt_refined(M, J, mode, tau30 - C, -(Jpqp[rows] + kv * (J[rows] @ vhat)))
 
 
 def bounds(tm, tau30, mode, kv, a, lam):

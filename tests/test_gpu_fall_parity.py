@@ -22,9 +22,8 @@ import torch
 import fall_cases as fc
 import ground_cases as gc
 import plant_step_cases as pc
+from dynamics_support import check_contact as _check_contact, check_terms as _check_terms, ninf as _ninf, oracle_terms as _oracle_terms, to_m_coordinates as _to_m_coordinates
 from helpers import WEIGHT, close, close_on, make_controller, rel_err, same_bits, to_device
-from test_gpu_plant_step import _check_contact, _ninf, _to_m_coordinates
-from test_gpu_terms import _check_terms, _oracle_terms
 
 pytestmark = pytest.mark.gpu
 DT, TH, B = pc.DT, pc.TH, pc.B

@@ -20,7 +20,7 @@ import fall_rigid_cases as frc
 import plant_step_cases as pc
 import rigid_cases as rc
 from helpers import WEIGHT, close, make_controller, rel_err, same_bits as _same, to_device, vec_err
-from test_gpu_rigid import _derivative_against, _imode
+from rigid_support import check_figures, derivative_against as _derivative_against, device_terms, flight_against_the_plain_derivative, imode as _imode
 
 pytestmark = pytest.mark.gpu
 DT, TH, B = pc.DT, pc.TH, pc.B
@@ -32,18 +32,6 @@ def _ctl(S, n=B):
 
 def _state(ctl, x0, t=0.25):
     return ctl.new_state(x0[:, :30], x0[:, 30:], t=t)
-
-
-def _check_bounds(tm, tau, mode, kv, xdot, lam, worst, tag):
-    """The three bounds of one robot's derivative against the statement's system on the terms tm; lambda exactly 0 on the free rows."""
-    a = rc.a_from_xdot(xdot, tm["X"][0])
-    b = rc.bounds(tm, tau, mode, kv, a, lam)
-    for k in worst:
-        worst[k] = max(worst[k], b[k])
-    free = [r for r in range(12) if r not in rc.RIGID_ROWS[int(mode) & 3]]
-    assert np.isfinite(xdot).all() and not lam[free].any(), tag
-    assert b["backward"] <= 1e-12 and b["constraint"] <= 1e-12 and b["forward"] <= 1e-12, (tag, b)
-    return b
 
 
 # ------------------------------------------------------------------------------- derivative
@@ -58,8 +46,7 @@ def test_derivative_against_the_statement_on_the_devices_terms(band):
     """The statement fed with the GPU's own terms(q, v) record (M, C, J, Jpqp; vhat and the base's X_0 stay the oracle's)."""
     S = frc.rigid_fall_cases(band)
     ctl = _ctl(S)
-    t = ctl.split_terms(ctl.terms(to_device(ctl, S["q"]), to_device(ctl, S["v"])).cpu().numpy())
-    dev = [dict(M=t["M"][i], C=t["C"][i], J=t["J"][i], Jpqp=t["Jpqp"][i], vhat=S["terms"][i]["vhat"]) for i in range(B)]
+    dev = device_terms(ctl, S)
     _derivative_against(lambda i: dev[i], "the device's terms, band %g" % band, S=S, decided=frc.decided_on)
     ctl.close()
 
@@ -67,25 +54,14 @@ def test_derivative_against_the_statement_on_the_devices_terms(band):
 @pytest.mark.parametrize("band", fc.BANDS)
 def test_flight_is_the_plain_derivative_out_of_the_ground(band):
     """The 16 states lifted until their lowest vertex is 5 cm above z = 0, LMH_PHASE_FLIGHT: xdot is lmh_plant_derivative's bit for bit --
-    the first right-hand side of plant_minv_rigid sees plant_minv's operations in plant_minv's order at tilted postures too -- and lambda
-    is exactly 0."""
+    the first right-hand side of the multi-right-hand-side solve sees plant_minv's operations in plant_minv's order at tilted postures
+    too -- and lambda is exactly 0."""
     S, F = frc.rigid_fall_cases(band), fc.fall_states(band)
     ctl = _ctl(S)
     qn = S["q"].copy()
     qn[:, 2] += 0.05 - F["pos"][:, :, 2].min(axis=1)
     q, v, tau = to_device(ctl, qn), to_device(ctl, S["v"]), to_device(ctl, S["tau"])
-    xd, c, f = ctl.plant_derivative(q, v, tau)
-    flight = _imode(ctl, np.full(B, 3))
-    for kv in rc.KVS:
-        xr, lam, fr = ctl.plant_derivative_rigid(q, v, tau, flight, kv)
-        torch.cuda.synchronize()
-        assert float(c.abs().max()) == 0.0 and int(f.abs().max()) == 0
-        assert bool(torch.isfinite(xd).all())
-        worst = float(((xr - xd).abs() / xd.abs().clamp_min(1e-300)).max())
-        print("\nflight vs plant_derivative, band %g, kv = %g: largest relative difference %.2e" % (band, kv, worst))
-        assert _same(xr, xd) and float(lam.abs().max()) == 0.0 and int(fr.abs().max()) == 0
-    held, _, _ = ctl.plant_derivative_rigid(q, v, tau, None, 0.0)
-    torch.cuda.synchronize()
+    xd, held = flight_against_the_plain_derivative(ctl, q, v, tau, "band %g, " % band)
     assert all(not _same(held[i], xd[i]) for i in range(B))        # held soles act 5 cm up too, on every robot
     ctl.close()
 
@@ -106,7 +82,8 @@ def test_derivative_on_the_pitch_ladder():
     print()
     for i in range(n):
         worst = dict(backward=0.0, constraint=0.0, forward=0.0)
-        _check_bounds(Ld["terms"][i], Ld["tau"][i], 0, 50.0, xr[i], lam[i], worst, i)
+        b = rc.bounds(Ld["terms"][i], Ld["tau"][i], 0, 50.0, rc.a_from_xdot(xr[i], Ld["terms"][i]["X"][0]), lam[i])
+        check_figures(b, xr[i], lam[i], rc.RIGID_ROWS[0], worst, i)
         assert not flags[i] & (capi.FLAG_NOT_SPD | capi.FLAG_NONFINITE), (i, flags[i])
         print("pitch %+.6f (delta %.0e): backward %.2e, constraint %.2e, forward/cond %.2e (largest |qdot| %.2e)"
               % (Ld["q"][i, 4], Ld["delta"][i], worst["backward"], worst["constraint"], worst["forward"], np.abs(xr[i, :30]).max()))

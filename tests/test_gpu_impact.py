@@ -19,16 +19,13 @@ import plant_step_cases as pc
 import zoh_io_cases as zi
 import zoh_rigid_cases as zr
 from helpers import TOL_REL, WEIGHT, close, make_controller, rel_err, same_bits as _same, to_device, vec_err
+from rigid_support import against_the_statement, device_terms as _device_terms, imode as _imode, randomised_links
 from zoh_rigid_host_loop import assert_same as _assert_same, fresh, push_schedules, wrench_and_refs
 
 pytestmark = pytest.mark.gpu
 DT, TH, B, NT = ic.DT, ic.TH, ic.B, ic.NT
 CASES = [(3, 50.0), (1, 0.0)]
 CASE_IDS = ["3 substeps, kv 50", "1 substep, kv 0"]
-
-
-def _imode(ctl, m):
-    return torch.as_tensor(np.ascontiguousarray(m, dtype=np.int32)).to(ctl.device)
 
 
 def _fresh(ctl, S, t=0.0):
@@ -39,43 +36,24 @@ def _fresh(ctl, S, t=0.0):
 def _impact_against(terms_of, tag):
     """Modes mixed over the batch (mode[i] = (i + s) % 3, s = 0, 1, 2) against the statement on terms_of(i): the three figures <= 1e-12,
     the flags the statement's."""
-    from linearmpchumanoid_amd import capi, trajectories as tj
+    from linearmpchumanoid_amd import trajectories as tj
     S = ic.impact_cases()
     ctl = make_controller(B, DT, TH, S["zcom"])
     q, v = to_device(ctl, S["q"]), to_device(ctl, S["v"])
-    worst = dict(backward=0.0, constraint=0.0, forward=0.0)
-    for s in range(3):
-        mode = [(i + s) % 3 for i in range(B)]
-        v_plus, imp, flags = ctl.plant_impact_rigid(q, v, _imode(ctl, mode))
-        torch.cuda.synchronize()
-        v_plus, imp, flags = v_plus.cpu().numpy(), imp.cpu().numpy(), flags.cpu().numpy()
-        for i in range(B):
-            tm = terms_of(i)
-            dvhat = ic.dvhat_from_dv(v_plus[i] - S["v"][i], S["terms"][i]["X"][0])
-            info = {}
-            _, lam_s, flags_s = tj.rigid_contact_impact(tm["M"], tm["J"], tm["vhat"], mode[i], contact_mu=ic.MU, info=info)
-            b = ic.bounds(tm, mode[i], dvhat, imp[i])
-            for k in worst:
-                worst[k] = max(worst[k], b[k])
-            free = [r for r in range(12) if r not in info["rows"]]
-            print("\nimpact vs the statement on %s, shift %d, robot %d: backward %.2e constraint %.2e forward/cond %.2e flags %d (statement %d)"
-                  % (tag, s, i, b["backward"], b["constraint"], b["forward"], flags[i], flags_s), end="")
-            assert np.isfinite(v_plus[i]).all() and not imp[i][free].any() and imp[i][info["rows"]].all(), (tag, s, i)
-            assert b["backward"] <= 1e-12 and b["constraint"] <= 1e-12 and b["forward"] <= 1e-12, (tag, s, i, b)
-            assert flags[i] == flags_s and not flags[i] & (capi.FLAG_NOT_SPD | capi.FLAG_NONFINITE), (tag, s, i, flags[i], flags_s)
-    print("\nimpact vs the statement on %s: backward %.2e, constraint %.2e, forward/cond %.2e" % (tag, worst["backward"], worst["constraint"], worst["forward"]))
+
+    def robot(i, mode, kv, v_plus, imp, flags, where):
+        tm, info = terms_of(i), {}
+        _, lam_s, flags_s = tj.rigid_contact_impact(tm["M"], tm["J"], tm["vhat"], mode, contact_mu=ic.MU, info=info)
+        assert imp[info["rows"]].all() and flags == flags_s, (where, flags, flags_s)
+        return ic.bounds(tm, mode, ic.dvhat_from_dv(v_plus - S["v"][i], S["terms"][i]["X"][0]), imp), info["rows"], flags_s, 0
+
+    against_the_statement(ctl, "impact", tag, (None,), lambda mode, kv: ctl.plant_impact_rigid(q, v, mode), robot)
     ctl.close()
 
 
 def test_impact_against_the_statement_on_the_oracles_terms():
     S = ic.impact_cases()
     _impact_against(lambda i: S["terms"][i], "the oracle's terms")
-
-
-def _device_terms(ctl, S, q=None, v=None):
-    """The GPU's own terms(q, v) record (M, J); vhat and the base's X_0, pure functions of the base pose, stay the oracle's."""
-    t = ctl.split_terms(ctl.terms(to_device(ctl, S["q"] if q is None else q), to_device(ctl, S["v"] if v is None else v)).cpu().numpy())
-    return [dict(M=t["M"][i], J=t["J"][i], vhat=S["terms"][i]["vhat"], X=S["terms"][i]["X"]) for i in range(B)]
 
 
 def test_impact_against_the_statement_on_the_devices_terms():
@@ -152,13 +130,9 @@ def test_per_robot_models_and_friction_and_a_nan_flags_its_robot_alone():
     """Four robots with four models (set_model) and four contact_mu (set_params) in one handle equal four handles of one robot, bit for
     bit; the coefficients are chosen around the impulse's own ratio so that the slip flag differs between them."""
     from linearmpchumanoid_amd import capi
-    from linearmpchumanoid_amd.controller import nominal_links
     S = ic.impact_cases()
     n, idx = 4, [1, 6, 11, 12]
-    raw = np.tile(nominal_links(), (n, 1, 1))
-    rng = np.random.default_rng(20260004)
-    raw[:, :, 0] *= rng.uniform(0.9, 1.1, (n, 28))
-    raw[:, :, 1:4] += rng.uniform(-5e-3, 5e-3, (n, 28, 3)) * (raw[:, :, 0:1] > 0)
+    raw = randomised_links(n)
     mode_np = np.array([0, 1, 2, 0], dtype=np.int32)
     q, v = S["q"][idx], S["v"][idx]
     probe = make_controller(n, DT, TH, S["zcom"])

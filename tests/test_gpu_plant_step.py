@@ -15,7 +15,9 @@ import pytest
 import torch
 
 import plant_step_cases as pc
-from helpers import close, close_on, make_controller, perturbed_velocities, rel_err, to_device
+from dynamics_support import check_contact as _check_contact, ninf as _ninf, to_m_coordinates as _to_m_coordinates
+from helpers import close, make_controller, perturbed_velocities, rel_err, to_device
+from rigid_support import randomised_links as _randomised_links
 
 pytestmark = pytest.mark.gpu
 DT, TH, B = pc.DT, pc.TH, pc.B
@@ -37,31 +39,6 @@ def _setup():
         ref.append(dict(xdot=xdot, pos=pos, vel=vel, **parts))
     _cache.update(S, ref=ref)
     return _cache
-
-
-def _ninf(a):
-    return float(np.abs(a).sum(axis=1).max()) if np.ndim(a) == 2 else float(np.abs(a).max())
-
-
-def _to_m_coordinates(qdd, X0):
-    """The state-ordered, world-frame acceleration back in the coordinates of M: the inverse of plant_acceleration's last step."""
-    return np.concatenate([X0 @ np.concatenate([qdd[3:6], qdd[0:3]]), qdd[6:]])
-
-
-def _check_contact(rec, r, tag):
-    from linearmpchumanoid_amd.controller import BatchedController
-    g = pc.GROUND
-    s = BatchedController.split_contact(rec)
-    scale = g["k"] * np.abs(r["pos"]).max() + (g["d"] + g["dt"]) * np.abs(r["vel"]).max()
-    out = r["pos"][:, 2] >= 0.0
-    assert not s["vertex_force"][out].any(), (tag, s["vertex_force"][out])          # exactly 0 out of the ground
-    assert np.array_equal(s["vertex_force"] == 0.0, r["vf"] == 0.0), tag             # and the same clamps as the oracle
-    assert close_on(s["vertex_force"], r["vf"], 1e-11, scale), (tag, np.abs(s["vertex_force"] - r["vf"]).max() / scale)
-    w, wr = s["w"].reshape(2, 2, 3), r["w"].reshape(2, 2, 3)
-    assert close_on(w[:, 1], wr[:, 1], 1e-11, 4 * scale), (tag, np.abs(w[:, 1] - wr[:, 1]).max() / scale)
-    assert close_on(w[:, 0], wr[:, 0], 1e-11, 4 * scale * 0.11), (tag, np.abs(w[:, 0] - wr[:, 0]).max() / scale)
-    assert not s["pad"].any()
-    return float(max(np.abs(s["vertex_force"] - r["vf"]).max(), np.abs(s["w"] - r["w"]).max()) / scale)
 
 
 def test_contact_wrench():
@@ -239,15 +216,6 @@ def test_zero_order_hold_loop():
         worst = max(worst, rel_err(a[i, :60], x))
         assert close(a[i, :60], x, 1e-7) and a[i, 90] == t, (i, rel_err(a[i, :60], x))
     print("\nzero-order-hold loop, 20 ticks: %.2e" % worst)
-
-
-def _randomised_links(n):
-    from linearmpchumanoid_amd.controller import nominal_links
-    raw = np.tile(nominal_links(), (n, 1, 1))
-    rng = np.random.default_rng(20260004)
-    raw[:, :, 0] *= rng.uniform(0.9, 1.1, (n, 28))
-    raw[:, :, 1:4] += rng.uniform(-5e-3, 5e-3, (n, 28, 3)) * (raw[:, :, 0:1] > 0)
-    return raw
 
 
 def test_per_robot_grounds_and_models():

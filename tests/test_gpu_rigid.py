@@ -16,75 +16,14 @@ import torch
 import plant_step_cases as pc
 import rigid_cases as rc
 from helpers import TOL_REL, WEIGHT, close, make_controller, perturbed_velocities, rel_err, same_bits as _same, to_device, vec_err
+from rigid_support import derivative_against as _derivative_against, device_terms, flight_against_the_plain_derivative, fresh as _fresh, imode as _imode, randomised_links as _randomised_links
 
 pytestmark = pytest.mark.gpu
 DT, TH, B = rc.DT, rc.TH, rc.B
 
 
-def _imode(ctl, m):
-    return torch.as_tensor(np.asarray(m, dtype=np.int32)).to(ctl.device)
-
-
 def _inputs(ctl, S):
     return tuple(to_device(ctl, S[k]) for k in ("q", "v", "tau"))
-
-
-def _fresh(ctl, S, t0=0.0, v_prev=None):
-    st = ctl.new_state(S["q"], S["v"], t=t0, v_prev=S["v"] if v_prev is None else v_prev)
-    st[:, 91:96] = torch.arange(1.0, 6.0, dtype=torch.float64, device=ctl.device)          # the pads: left alone
-    return st
-
-
-def _flag_margins(lam, rows, mu=rc.MU):
-    """Which of the two informational flags the statement decides by more than 1e-9 N on this case -> (pull decided, slip decided)."""
-    held = [ft for ft in range(2) if 6 * ft in rows]
-    pull = all(abs(lam[6 * ft + 5]) > 1e-9 for ft in held)
-    slip = all(abs(np.hypot(lam[6 * ft + 3], lam[6 * ft + 4]) - mu * lam[6 * ft + 5]) > 1e-9 for ft in held)
-    return pull, slip
-
-
-def _derivative_against(terms_of, tag, S=None, decided=None):
-    """Tests 1 and 2: modes mixed over the batch (mode[i] = (i + s) % 3, s = 0, 1, 2), kv 0 and 50, against the statement on terms_of(i).
-    S: the states (q, v, tau, zcom and the oracle's terms for X_0; rigid_cases.rigid_cases() by default); decided(lam, rows, bounds) ->
-    (pull, slip): which flags the statement's multiplier decides (by 1e-9 N by default).  test_gpu_fall_rigid.py runs the same checks on
-    the states of a fall.  -> (worst figures, flag decisions not compared)."""
-    from linearmpchumanoid_amd import capi
-    S = rc.rigid_cases() if S is None else S
-    decided = (lambda lam, rows, b: _flag_margins(lam, rows)) if decided is None else decided
-    ctl = make_controller(B, DT, TH, S["zcom"])
-    q, v, tau = _inputs(ctl, S)
-    xd_plain, _, _ = ctl.plant_derivative(q, v, tau)
-    worst = dict(backward=0.0, constraint=0.0, forward=0.0)
-    undecided = 0
-    for s in range(3):
-        mode = [(i + s) % 3 for i in range(B)]
-        for kv in rc.KVS:
-            xdot, lam, flags = ctl.plant_derivative_rigid(q, v, tau, _imode(ctl, mode), kv)
-            torch.cuda.synchronize()
-            assert _same(xdot[:, :30], xd_plain[:, :30])           # qdot: lmh_plant_derivative's, bit for bit
-            xdot, lam, flags = xdot.cpu().numpy(), lam.cpu().numpy(), flags.cpu().numpy()
-            for i in range(B):
-                tm = terms_of(i)
-                a = rc.a_from_xdot(xdot[i], S["terms"][i]["X"][0])
-                info = {}
-                _, lam_s, flags_s = rc.rigid_contact_acceleration(tm["M"], tm["C"], tm["J"], tm["Jpqp"], tm["vhat"], S["tau"][i], mode[i], kv, contact_mu=rc.MU, info=info)
-                b = rc.bounds(tm, S["tau"][i], mode[i], kv, a, lam[i])
-                for k in worst:
-                    worst[k] = max(worst[k], b[k])
-                free = [r for r in range(12) if r not in info["rows"]]
-                assert np.isfinite(xdot[i]).all() and not lam[i][free].any(), (tag, s, kv, i)
-                assert b["backward"] <= 1e-12 and b["constraint"] <= 1e-12 and b["forward"] <= 1e-12, (tag, s, kv, i, b)
-                assert not flags[i] & (capi.FLAG_NOT_SPD | capi.FLAG_NONFINITE), (tag, s, kv, i, flags[i])
-                pull, slip = decided(lam_s, info["rows"], b)
-                undecided += (not pull) + (not slip)
-                if pull:
-                    assert (flags[i] & capi.FLAG_CONTACT_PULL) == (flags_s & capi.FLAG_CONTACT_PULL), (tag, s, kv, i)
-                if slip:
-                    assert (flags[i] & capi.FLAG_CONTACT_SLIP) == (flags_s & capi.FLAG_CONTACT_SLIP), (tag, s, kv, i)
-    print("\nrigid derivative vs the statement on %s: backward %.2e, constraint %.2e, forward/cond %.2e (flags not compared: %d)"
-          % (tag, worst["backward"], worst["constraint"], worst["forward"], undecided))
-    assert undecided <= 8                                          # the margins leave the comparison its cases
-    return worst, undecided
 
 
 def test_derivative_against_the_statement_on_the_oracles_terms():
@@ -97,8 +36,7 @@ def test_derivative_against_the_statement_on_the_devices_terms():
     base pose, stay the oracle's): the oracle-vs-GPU term difference is out of the comparison."""
     S = rc.rigid_cases()
     ctl = make_controller(B, DT, TH, S["zcom"])
-    t = ctl.split_terms(ctl.terms(to_device(ctl, S["q"]), to_device(ctl, S["v"])).cpu().numpy())
-    dev = [dict(M=t["M"][i], C=t["C"][i], J=t["J"][i], Jpqp=t["Jpqp"][i], vhat=S["terms"][i]["vhat"]) for i in range(B)]
+    dev = device_terms(ctl, S)
     _derivative_against(lambda i: dev[i], "the device's terms")
 
 
@@ -109,17 +47,7 @@ def test_flight_is_the_plain_derivative_out_of_the_ground():
     ctl = make_controller(B, DT, TH, S["zcom"])
     qn = S["q"].copy(); qn[:, 2] += 0.05
     q, v, tau = to_device(ctl, qn), to_device(ctl, S["v"]), to_device(ctl, S["tau"])
-    xd, c, f = ctl.plant_derivative(q, v, tau)
-    flight = _imode(ctl, np.full(B, 3))
-    for kv in rc.KVS:
-        xr, lam, fr = ctl.plant_derivative_rigid(q, v, tau, flight, kv)
-        torch.cuda.synchronize()
-        assert float(c.abs().max()) == 0.0 and int(f.abs().max()) == 0
-        worst = float(((xr - xd).abs() / xd.abs().clamp_min(1e-300)).max())
-        print("\nflight vs plant_derivative, kv = %g: largest relative difference %.2e" % (kv, worst))
-        assert _same(xr, xd) and float(lam.abs().max()) == 0.0 and int(fr.abs().max()) == 0
-    held, _, _ = ctl.plant_derivative_rigid(q, v, tau, None, 0.0)
-    torch.cuda.synchronize()
+    xd, held = flight_against_the_plain_derivative(ctl, q, v, tau, "")
     assert not _same(held, xd)                                     # a constraint knows no plane: held soles act 5 cm up too
 
 
@@ -144,15 +72,6 @@ def test_defaults_mode_bits_and_permutation():
     spres = ctl.plant_step_rigid(_fresh(ctl, S)[pt].contiguous(), tau[pt].contiguous(), _imode(ctl, mode_np[perm]), kv, 3)
     torch.cuda.synchronize()
     assert all(_same(x[pt], y) for x, y in zip(res, pres)) and all(_same(x[pt], y) for x, y in zip(sres, spres))
-
-
-def _randomised_links(n):
-    from linearmpchumanoid_amd.controller import nominal_links
-    raw = np.tile(nominal_links(), (n, 1, 1))
-    rng = np.random.default_rng(20260004)
-    raw[:, :, 0] *= rng.uniform(0.9, 1.1, (n, 28))
-    raw[:, :, 1:4] += rng.uniform(-5e-3, 5e-3, (n, 28, 3)) * (raw[:, :, 0:1] > 0)
-    return raw
 
 
 def test_per_robot_models_and_friction():

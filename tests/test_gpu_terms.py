@@ -13,19 +13,13 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import WEIGHT, close_on, dense_terms_from_debug, make_controller, oracle_system, posture_sweep, rel_err, to_device
+from dynamics_support import check_terms as _check_terms, oracle_terms as _oracle_terms
+from helpers import WEIGHT, close_on, dense_terms_from_debug, make_controller, posture_sweep, rel_err, to_device
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DT, TH = 1e-3, 0.016
 B = 16
-
-
-def _oracle_terms(q, v, raw_links=None):
-    o = oracle_system(DT, TH, raw_links=raw_links)
-    o.set_prev_velocity(v)
-    o.eval(q, v, 0.0)
-    return dict(t=o.terms(), rb=o.robot(), mass=o.mass)
 
 
 _cache = {}
@@ -44,32 +38,6 @@ def _setup():
     tau = np.stack([r["t"]["M"] @ qdd[i] + r["t"]["C"] - r["t"]["J"].T @ w[i] for i, r in enumerate(ref)])
     _cache.update(q0=q0, zcom=zcom, q=q, v=v, ref=ref, qdd=qdd, w=w, tau=tau)
     return _cache
-
-
-def _check_terms(rec, r, v, mass, worst, tag):
-    """One record against one oracle evaluation: the checks of test 1."""
-    from linearmpchumanoid_amd.controller import BatchedController
-    s = BatchedController.split_terms(rec)
-    t, rb = r["t"], r["rb"]
-    bad = []
-
-    def check(name, err, tol):
-        worst[name] = max(worst.get(name, 0.0), float(err))
-        if not err < tol:
-            bad.append((tag, name, float(err)))
-
-    for name, a, b in (("M", s["M"], t["M"]), ("C", s["C"], t["C"]), ("AG", s["AG"], t["AG"]), ("J", s["J"], t["J"]),
-                       ("T", s["T"], t["T"][:, :3, :]), ("CoM", s["CoM"], rb["CoM"])):
-        check(name, rel_err(a, b), 1e-11)
-    cs = np.abs(t["C"]).max()                                     # velocity-product terms: differences of O(50) quantities
-    check("Cg", np.abs(s["Cg"] - t["Cg"][:6]).max() / cs, 1e-11)
-    check("AGpqp", np.abs(s["AGpqp"] - t["AGpqp"]).max() / cs, 1e-11)
-    check("Jpqp", np.abs(s["Jpqp"] - t["Jpqp"]).max() / cs, 1e-11)
-    ms = np.abs(t["AG"]).max() * max(np.abs(v).max(), 1e-300)     # momenta: AG vhat, sums of |AG| |vhat| terms
-    check("comVel", np.abs(s["comVel"] - rb["comVel"]).max() * mass / ms, 1e-11)      # (m comVel = AG_lin vhat, as the posture sweep scales it)
-    check("angMom", np.abs(s["angMom"] - rb["angMom"]).max() / ms, 1e-11)
-    assert float(s["mass"]) == mass, (tag, float(s["mass"]), mass)
-    return bad
 
 
 def test_terms_parity():

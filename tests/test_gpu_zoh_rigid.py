@@ -18,6 +18,7 @@ import rigid_cases as rc
 import zoh_io_cases as zi
 import zoh_rigid_cases as zr
 from helpers import TOL_REL, WEIGHT, close, make_controller, perturbed_velocities, rel_err, same_bits as _same, vec_err
+from rigid_support import imode as _imode
 from zoh_host_loop import SCHEDULES
 from zoh_rigid_host_loop import assert_same as _assert_same, fresh, host_loop_rigid, push_schedules, wrench_and_refs
 
@@ -30,10 +31,6 @@ CASE_IDS = ["3 substeps, kv 0", "3 substeps, kv 50", "1 substep, kv 0", "1 subst
 
 def _fresh(ctl, S, t=0.0):
     return fresh(ctl, S["q"], S["v"], t)
-
-
-def _imode(ctl, m):
-    return torch.as_tensor(np.ascontiguousarray(m, dtype=np.int32)).to(ctl.device)
 
 
 def _core(tag, sa, ra, sb, rb, more=()):
